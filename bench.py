@@ -3,7 +3,7 @@
 Headline benchmark: leaf-UCB predictions/s (+ GP-fit ms) on synthetic {N_train, D, N_leaves}.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--dtype float32|mixed|float64]
-                    [--seed 0..4] [--leaves batch|grow --depth d]
+                    [--seed 0..4] [--leaves batch|grow --depth d] [--full] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one leaf batch: ``gpso_best_ucb`` (prep -> leaf-tile MFMA
 kernel -> finalize -> arg-max) on leaves ALREADY RESIDENT in HBM, posterior resident.  N = 1 runs
@@ -15,20 +15,24 @@ every rank repeats the same deterministic fit itself (``posterior_replicate_ms``
 picks which of the two the timed steps use) --, each rank scores its shard, the winners are all-gathered -- all of it
 inside the library (gpso_comm_init / gpso_broadcast_posterior / gpso_best_ucb_sharded).
 
-Order of a run: fit (timed by the library's events: ``fit_ms``) -> [broadcast] -> leaves to HBM -> ``--settle-s`` seconds
+Order of a run: fit -> [broadcast] -> leaves to HBM -> ``--settle-s`` seconds
 (default 0.3) of UNTIMED calls of the same step, so that the device holds busy-state clocks (reported as ``settle_s``;
 with 20 / 5 steps the kernel otherwise runs at start-up clocks: 0.93 ms against 0.86) -> W untimed warm-up steps ->
-barrier + synchronize -> EXACTLY K timed steps -> synchronize + barrier -> CPU baseline and accuracy report (untimed).
+barrier + synchronize -> EXACTLY K timed steps -> synchronize + barrier -> [``--dump-outputs DIR``: the last timed step's
+(index, mean, var, ucb) as DIR/<name>.npy, float64] -> [``--full``: the measurements and checks below] -> the line.
 
-Beside the contract's fields the line carries (round 5) ``ms_per_step_pipelined`` / ``value_pipelined`` (the same K steps with two
-calls in flight through gpso_best_ucb_begin / _end; the headline ``value`` keeps the synchronous protocol), ``fit_ms`` =
-{posterior, nlml_grad, append_k7 (gpso_append of 7 points), hyperopt (one warm-started L-BFGS-B fit: wall / device ms,
-evaluations)} with ``roofline_fit``, and for N > 1 ``allgather_us`` (the winners' all-gather + fold per step on rank 0).
+A plain run does only what the headline needs.  ``--full`` adds (untimed, outside the K steps): the fit timed by the library's
+events, ``fit_ms`` = {posterior, nlml_grad, append_k7 (gpso_append of 7 points), hyperopt (one warm-started L-BFGS-B fit:
+wall / device ms, evaluations)} with ``roofline_fit``; ``ms_per_step_pipelined`` / ``value_pipelined`` (the same K steps with
+two calls in flight through gpso_best_ucb_begin / _end; the headline ``value`` keeps the synchronous protocol); for N > 1 both
+ways of distributing the posterior with their fingerprints; the CPU baseline and the checks against the oracle; every predict
+math on the same leaves (``predict_math_modes``).  ``allgather_us`` (N > 1: the winners' all-gather + fold per step on
+rank 0) and ``roofline`` come from the timed steps themselves and are in every line.
 
 Rank 0 prints ONE JSON line.  ``roofline`` is for the dominant kernel (leaf_tiles_kernel):
 achieved = algorithmic FLOPs per launch (N^2 + 2ND + 20N per leaf) / its average
 duration measured with HIP events on the library's stream inside the timed region.
-``cpu_baseline`` times the CPU oracle (numpy/scipy float64, the stand-in for the reference's
+``cpu_baseline`` (``--full``) times the CPU oracle (numpy/scipy float64, the stand-in for the reference's
 GPflow path, which cannot be installed here) on a bounded sample of the same workload.
 """
 import argparse
@@ -321,7 +325,14 @@ def main():
     ap.add_argument("--math", default="auto", choices=["auto", "native", "bf16x3", "bf16x6", "f16x3"],
                     help="predict math of float32 workloads (auto = the library default: the first rung of the ladder "
                          "f16x3 -> bf16x6 -> native f32 the posterior's self-test passes with)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: fit timings and roofline_fit, the hyper-parameter fit, the pipelined steps, both "
+                         "posterior distributions (N > 1), the CPU baseline, the oracle checks and every predict math")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the winners' index, mean, var, ucb) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -411,7 +422,7 @@ def main():
 
     math_mode = "native"
     if rank == 0:
-        fit_here(timed=True)
+        fit_here(timed=args.full)
         if float_predict:  # what GPSO_MATH_AUTO settled on for this posterior (its self-test ran here)
             math_mode = eng.precision_info()["predict_math"]
     bcast_ms = repl_ms = None
@@ -451,26 +462,32 @@ def main():
             dist.all_gather_object(hs, eng.posterior_hash())
             return hs
 
-        # both ways, the chosen one last (its posterior is the one the timed steps use; the bits are the same)
-        if args.posterior == "broadcast":
-            repl_ms = by_replication()
-            hs = fingerprints()
-            bcast_ms = by_broadcast()
+        if not args.full:  # the chosen way only
+            if args.posterior == "broadcast":
+                bcast_ms = by_broadcast()
+            else:
+                repl_ms = by_replication()
         else:
-            bcast_ms = by_broadcast()
-            repl_ms = by_replication()
-            hs = fingerprints()
-        hashes_agree = len(set(hs)) == 1
-        if not hashes_agree:
-            # reported in the line, never fatal for the measurement: the timed steps then run on ONE posterior, rank 0's
-            print(f"[bench] replicated fits disagree across ranks: {[f'{h:016x}' for h in hs]} -- broadcasting rank 0's",
-                  file=sys.stderr, flush=True)
-            if args.posterior == "replicate":
-                by_broadcast()
-                args.posterior = "broadcast"
-        resident_agree = len(set(fingerprints())) == 1
-        if not resident_agree:
-            print("[bench] posterior fingerprints differ across ranks at the start of the timed steps", file=sys.stderr, flush=True)
+            # both ways, the chosen one last (its posterior is the one the timed steps use; the bits are the same)
+            if args.posterior == "broadcast":
+                repl_ms = by_replication()
+                hs = fingerprints()
+                bcast_ms = by_broadcast()
+            else:
+                bcast_ms = by_broadcast()
+                repl_ms = by_replication()
+                hs = fingerprints()
+            hashes_agree = len(set(hs)) == 1
+            if not hashes_agree:
+                # reported in the line, never fatal for the measurement: the timed steps then run on ONE posterior, rank 0's
+                print(f"[bench] replicated fits disagree across ranks: {[f'{h:016x}' for h in hs]} -- broadcasting rank 0's",
+                      file=sys.stderr, flush=True)
+                if args.posterior == "replicate":
+                    by_broadcast()
+                    args.posterior = "broadcast"
+            resident_agree = len(set(fingerprints())) == 1
+            if not resident_agree:
+                print("[bench] posterior fingerprints differ across ranks at the start of the timed steps", file=sys.stderr, flush=True)
         posterior_bytes = int(eng.posterior_span()[2])
         distribution = ("fit on rank 0, ONE RCCL broadcast of the contiguous predict-ready range of its posterior arena "
                         "(gpso_broadcast_posterior)" if args.posterior == "broadcast" else
@@ -480,6 +497,7 @@ def main():
     lo, hi = (0, m_total) if grow else D.shard_range(m_total, rank, world)
     np_dtype = np.float32 if float_predict else np.float64
     leaves_dev = None if grow else torch.from_numpy(np.ascontiguousarray(leaves_all[lo:hi].astype(np_dtype))).cuda(local_rank)
+    returned = {}  # what the last step's call handed back (--dump-outputs)
 
     def step():
         if grow:
@@ -489,12 +507,14 @@ def main():
                 idx, mean, var, ucb = D.best_ucb_grow_sharded(eng, boxes, args.depth, varsigma)
             else:
                 idx, mean, var, ucb = eng.best_ucb_grow(boxes, args.depth, varsigma)
+            returned.update(index=idx, mean=mean, var=var, ucb=ucb)
             j = int(np.argmax(ucb))
             return int(idx[j]) + j * (rows_ref // 2), float(mean[j]), float(var[j]), float(ucb[j])
         if use_dist:  # gpso_best_ucb_sharded: local scoring, RCCL all-gather of the winners, fold on device
             idx, mean, var, ucb = D.best_ucb_sharded(eng, leaves_dev, m_total, varsigma)
         else:
             idx, mean, var, ucb = eng.best_ucb(leaves_dev, varsigma)
+        returned.update(index=idx, mean=mean, var=var, ucb=ucb)
         return int(idx[0]), float(mean[0]), float(var[0]), float(ucb[0])
 
     # clock settle (untimed, BEFORE the W warm-up steps the contract asks for): the fit, the uploads and the process
@@ -539,12 +559,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     eng.set_timing(1)
-    # the same K steps through the non-blocking pair, two deep (gpso_best_ucb_begin / _end): the device work of step i + 1
+    if args.dump_outputs and rank == 0:
+        # the winners of the last timed step as the caller received them (per segment; identical on every rank under N > 1)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in returned.items():
+            np.save(os.path.join(args.dump_outputs, f"{name}.npy"), np.asarray(a, dtype=np.float64))
+    # (--full) the same K steps through the non-blocking pair, two deep (gpso_best_ucb_begin / _end): the device work of step i + 1
     # is queued before the host reads the result of step i, so the GPU does not idle over the host's round trip.  Reported
     # BESIDE the headline (which keeps the synchronous protocol above); single-GPU runs only (the sharded call is a
     # collective and stays blocking).
     pipelined_ms = pipelined_same = None
-    if not use_dist and not grow:
+    if args.full and not use_dist and not grow:
         for _ in range(3):
             eng.best_ucb_end(eng.best_ucb_begin(leaves_dev, varsigma))
         torch.cuda.synchronize()
@@ -638,7 +663,7 @@ def main():
             },
         }
         post = None
-        if grow and world == 1 and not args.no_cpu_baseline:
+        if args.full and grow and world == 1 and not args.no_cpu_baseline:
             # the checker for the grown leaves: the oracle grows the first box on the host (small depths only) and scores it
             from oracle import gpr, tree
 
@@ -652,7 +677,7 @@ def main():
                 ucb_ref = np.concatenate(ucbs)
                 out["winner"]["oracle_argmax"] = int(np.argmax(ucb_ref))
                 out["winner"]["oracle_ucb_gap"] = float(ucb_ref.max() - ucb_ref[winner[0]])
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             cb, post = cpu_baseline(X, y, theta, leaves_all, varsigma)
             out["cpu_baseline"] = cb
             # the checker: the GPU winner must be (within fp tolerance) the oracle's winner on the sample
@@ -667,7 +692,7 @@ def main():
                 out["winner"]["oracle_argmax_over_sample"] = int(np.argmax(ucb_ref))
                 out["winner"]["oracle_ucb_gap"] = float(ucb_ref.max() - ucb_ref[winner[0]])
                 out["winner"]["same_argmax_as_oracle"] = bool(int(np.argmax(ucb_ref)) == winner[0]) if n_s == leaves_all.shape[0] else None
-        if world == 1 and float_predict and math_opt == "auto" and not grow:
+        if args.full and world == 1 and float_predict and math_opt == "auto" and not grow:
             # every predict math on the same leaves in the same run: throughput + accuracy vs the oracle
             out["predict_math_modes"] = split_bf16_report(eng, leaves_dev, leaves_all, varsigma, m_total,
                                                   flops_per_leaf, post, max(3, args.steps // 2))

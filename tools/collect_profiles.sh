@@ -8,25 +8,25 @@ PART=${2:-all}   # a = bench lines + kernel stats + PMC, b = fit timelines, loop
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$TAG; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 KPAT="leaf_tiles_bf16_kernel<2, float, 0, true, true, 1, false, 1>"   # the fp16 split instantiation at C3 (first rung of GPSO_MATH_AUTO; fused step, one chunk of the fp16 contraction, 16x16x32, packed contraction)
 if [ $PART = a ] || [ $PART = all ]; then
-python3 $R/bench.py > $O/bench_c3.json 2> $O/bench_c3.err
-for w in c2 c4 c5 c3f64; do python3 $R/bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null; done
+python3 $R/bench.py --full > $O/bench_c3.json 2> $O/bench_c3.err
+for w in c2 c4 c5 c3f64; do python3 $R/bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null; done
 # (round 6) the reference's own dtype and "mixed" at the large shares; SURVEY 8(d) family A leaves (grown on the device)
-for w in c4 c5; do for t in float64 mixed; do python3 $R/bench.py --workload $w --dtype $t --no-cpu-baseline --steps 30 --warmup 5 > $O/bench_${w}_$t.json 2>/dev/null; done; done
-for cfg in "c2 8" "c3 11" "c4 12"; do set -- $cfg; python3 $R/bench.py --workload $1 --leaves grow --depth $2 --steps 100 --no-hyperopt > $O/bench_grow_d$2.json 2>/dev/null; done
-for sd in 1 2 3 4; do python3 $R/bench.py --seed $sd --no-cpu-baseline --no-hyperopt > $O/bench_c3_seed$sd.json 2>/dev/null; done
-for m in native bf16x6; do python3 $R/bench.py --math $m --no-cpu-baseline > $O/bench_c3_$m.json 2>/dev/null; done
+for w in c4 c5; do for t in float64 mixed; do python3 $R/bench.py --full --workload $w --dtype $t --no-cpu-baseline --steps 30 --warmup 5 > $O/bench_${w}_$t.json 2>/dev/null; done; done
+for cfg in "c2 8" "c3 11" "c4 12"; do set -- $cfg; python3 $R/bench.py --full --workload $1 --leaves grow --depth $2 --steps 100 --no-hyperopt > $O/bench_grow_d$2.json 2>/dev/null; done
+for sd in 1 2 3 4; do python3 $R/bench.py --full --seed $sd --no-cpu-baseline --no-hyperopt > $O/bench_c3_seed$sd.json 2>/dev/null; done
+for m in native bf16x6; do python3 $R/bench.py --full --math $m --no-cpu-baseline > $O/bench_c3_$m.json 2>/dev/null; done
 echo "bench lines done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_c3_under_rocprof.json 2>/dev/null
 cp $(ls $O/prof/*/*kernel_stats.csv | head -1) $O/bench_c3_kernel_stats.csv
 python3 $R/tools/rocprof_fullsize.py $O/prof "$KPAT" $O/bench_c3_rocprof_fullsize.json
-rocprofv3 --pmc FETCH_SIZE TCC_HIT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc1 -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc1 rc $?"
-rocprofv3 --pmc WRITE_SIZE TCC_MISS TCC_REQ --kernel-trace --output-format csv -d $O/pmc2 -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc2 rc $?"
-rocprofv3 --pmc SQ_INSTS_MFMA SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $O/pmc3 -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc3 rc $?"
+rocprofv3 --pmc FETCH_SIZE TCC_HIT GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc1 -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc1 rc $?"
+rocprofv3 --pmc WRITE_SIZE TCC_MISS TCC_REQ --kernel-trace --output-format csv -d $O/pmc2 -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc2 rc $?"
+rocprofv3 --pmc SQ_INSTS_MFMA SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES --kernel-trace --output-format csv -d $O/pmc3 -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1; echo "pmc3 rc $?"
 for pat in "$KPAT" "leaf_tiles_bf16_kernel<3" "leaf_tiles_v2_kernel" potrf_step gram_kernel; do echo "## $pat (largest-grid dispatches only)"; for p in pmc1 pmc2 pmc3; do python3 $R/tools/pmc_summary.py $O/$p "$pat"; done; done > $O/pmc_summary.txt 2>&1
 python3 $R/tools/pmc_traffic_json.py $O/pmc_leaf_tiles_f16x3_c3.json c3 "$KPAT" "leaf_tiles_bf16_kernel<2, float, 0, true, true, 1, false, 1> (fp16 split x3, fused step, fp16 contraction with its small products packed: first rung of GPSO_MATH_AUTO)" $O/pmc1 $O/pmc2 $O/pmc3 > /dev/null
 rm -rf $O/prof $O/pmc1 $O/pmc2 $O/pmc3
 echo "bench profile done"
-rocprofv3 --kernel-trace --output-format csv -d $O/steptrace -- python3 $R/bench.py --steps 60 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/steptrace -- python3 $R/bench.py --full --steps 60 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
 python3 $R/tools/step_timeline.py $O/steptrace > $O/step_timeline.txt 2>&1; rm -rf $O/steptrace
 python3 $R/tools/c16_check.py > $O/c16_check.jsonl 2>/dev/null
 python3 $R/tools/sweep.py 2>/dev/null | grep "^{" > $O/sweep.jsonl

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/lds; mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $O/c3 -- python3 $R/tools/fit_trace.py 2048 12 float32 grad > /dev/null 2>&1
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $O/c4 -- python3 $R/tools/fit_trace.py 8192 40 float32 grad > /dev/null 2>&1
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $O/b3 -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $O/b3 -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 python3 - <<P
 import csv, glob, collections
 for tag in ("c3", "c4", "b3"):

@@ -1,5 +1,5 @@
 """Timeline of a few bench steps from a rocprofv3 kernel trace: python tools/step_timeline.py <trace dir> [kernel substring]
-(on the GPU box: rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline)."""
+(on an MI355X: rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline)."""
 import csv
 import glob
 import sys
