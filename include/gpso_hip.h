@@ -223,6 +223,39 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
                        int64_t n, int d, int kernel, const double* lengthscales, int n_ls,
                        double variance, double noise, double mean_c);
 
+/* ---- variational GP (VGPSurrogate._gp_train, gpso/gp_surrogate.py:536-699) ------------------------------------------
+ * GPflow 2's whitened VGP with a Gaussian likelihood on the resident training data (gpso_set_data): q(v) = N(mu, S S^T),
+ * f = L v + c, L = chol(k(X, X) + 1e-6 I) (GPflow's default jitter).  u, n_ls, train_mean, mean_c_fixed: the optimiser's
+ * vector and transforms exactly as gpso_fit_eval_u (the likelihood variance s2 = 1e-6 + softplus(u[n_ls + 1])).  float64
+ * arithmetic throughout: GPSO_F64 and GPSO_MIXED contexts (GPSO_F32: GPSO_E_ARG).  Every call replaces whatever posterior
+ * was resident.  q starts at the prior (mu = 0, S = I) whenever the shape of the data changes. */
+
+/* Replaces: assigning q_mu / q_sqrt of a GPflow VGP (gpflow.utilities.multiple_assign, gpso/gp_surrogate.py:667-671).
+ * Host float64 mu[n], S[n*n] (row-major, lower triangle read); n must equal the resident N; both NULL: the prior. */
+int gpso_vgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t n);
+/* Reading q_mu / q_sqrt back (gpflow.utilities.parameter_dict, gpso/gp_surrogate.py:690-692): mu[N], S[N*N] (nullable). */
+int gpso_vgp_get_q(gpso_ctx* ctx, double* mu, double* S);
+/* Replaces: assigning grown data to a VGP whose q keeps its old size (gpso/gp_surrogate.py:630-633; GPflow's
+ * update_vgp_data).  After gpso_set_data with the rows q was made for FIRST, in the same order: q keeps its leading block
+ * and the new rows get the prior (mu = 0, an identity block of S), on the device. */
+int gpso_vgp_extend_q(gpso_ctx* ctx);
+/* Replaces: natgrad_optimiser.minimize(training_loss, [(q_mu, q_sqrt)]) (gpso/gp_surrogate.py:639-642): one natural-gradient
+ * step of length gamma in (0, 1] on q at theta.  GPSO_E_NOTPD (q then restarts at the prior) when a factorisation fails. */
+int gpso_vgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double gamma);
+/* Replaces: ONE evaluation of the VGP training_loss (-ELBO) and its reverse-mode gradient in the trainable variables inside
+ * optimiser.minimize (gpso/gp_surrogate.py:643-646), at fixed q.  *loss; grad_u (nullable) [n_ls + 2 + (train_mean != 0)];
+ * theta_out (nullable) [n_ls + 3] = (lengthscales..., variance, s2, mean). */
+int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                    double* loss, double* grad_u, double* theta_out);
+/* Replaces: the predict_y / predict_f of the trained VGP (gpso/gp_surrogate.py:298, 325).  Installs the predictive at theta
+ * as the resident posterior: mean = k*^T L^-T mu + c, var = k** - |C k*|^2 + s2 with C = R L^-1, I - S S^T = R^T R -- the
+ * form every predict path evaluates, so gpso_predict, gpso_best_ucb (+ _begin / _end, _grow), the sharded and hand-off
+ * calls serve it unchanged.  Like gpso_set_posterior the installed posterior carries no GPR targets: the float-predict
+ * self-test is skipped (generation in double) and gpso_append returns GPSO_E_STATE.  The getters follow the installed form:
+ * GPSO_MAT_LINV returns C and GPSO_VEC_ALPHA returns L^-T mu; GPSO_MAT_CHOL and GPSO_VEC_WHITE return GPSO_E_STATE. */
+int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed);
+
 /* ---- predict (gpflow_model.predict_y users) ----------------------------------------------- */
 
 /* Replaces: gpflow_model.predict_y(coords) at gpso/gp_surrogate.py:298 (gp_predict) and

@@ -80,6 +80,13 @@ SIGNATURES = {
     "gpso_set_posterior": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64,
                                      C.c_int, C.c_int, _c_double_p, C.c_int, C.c_double, C.c_double,
                                      C.c_double]),
+    "gpso_vgp_set_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64]),
+    "gpso_vgp_get_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
+    "gpso_vgp_extend_q": (C.c_int, [C.c_void_p]),
+    "gpso_vgp_natgrad": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "gpso_vgp_elbo_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                  _c_double_p, _c_double_p]),
+    "gpso_vgp_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double]),
     "gpso_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int]),
     "gpso_best_ucb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p,

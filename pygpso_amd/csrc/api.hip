@@ -118,6 +118,14 @@ struct Engine {
                                  double* payload) = 0;
   virtual int fold_winners(const double* gathered, int world, int64_t m_global, const int64_t* seg_off, int nseg,
                            int64_t* idx, double* mean, double* var, double* ucb) = 0;
+  // variational GP (vgp.hip)
+  virtual int vgp_set_q(const double* mu, const double* S, int64_t n) = 0;
+  virtual int vgp_get_q(double* mu, double* S) = 0;
+  virtual int vgp_extend_q() = 0;
+  virtual int vgp_natgrad(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double gamma) = 0;
+  virtual int vgp_elbo(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double* loss,
+                       double* grad) = 0;
+  virtual int vgp_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c) = 0;
 };
 
 // contiguous share [lo, hi) of m items for `rank` of `world`: global order is preserved across ranks
@@ -415,7 +423,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -893,6 +901,7 @@ struct EngineT : Engine {
     if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
     have_data = true;
     have_post = have_kinv = chol_valid = linv_p_valid = false;
+    vgp_post = false;
     st_done = st_have = false;
     forget_peers();
     return GPSO_OK;
@@ -910,6 +919,7 @@ struct EngineT : Engine {
     const bool small = fused_small && small_fit_eligible(n, dp);
     if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c, !small))) return rc;
     have_post = have_kinv = chol_valid = false;
+    vgp_post = false;
     st_done = st_have = false;
     forget_peers();
     reset_generation();
@@ -1075,6 +1085,7 @@ struct EngineT : Engine {
     ctx->tick_timing();
     if (!Xn || !yn) return ctx->fail(GPSO_E_ARG, "Xnew / ynew must not be NULL");
     if (k < 1) return ctx->fail(GPSO_E_ARG, "need at least one new point (k=%lld)", (long long)k);
+    if (vgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
     if (int rca = refuse_if_async("gpso_append")) return rca;
     if (!have_data || !have_post || !chol_valid || (int64_t)y_host.size() != n)
       return ctx->fail(GPSO_E_STATE, "gpso_append needs a posterior fitted on this context (gpso_set_data + gpso_fit_eval)");
@@ -1195,6 +1206,7 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(tmp, L, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp + (size_t)n * n, alpha64, (size_t)n * 8, hipMemcpyHostToDevice, s));
     have_data = false;  // y unknown: a later fit needs gpso_set_data
+    vgp_post = false;
     have_post = have_kinv = chol_valid = false;
     st_done = st_have = false;
     forget_peers();
@@ -1212,6 +1224,270 @@ struct EngineT : Engine {
     HIPCHECK(hipStreamSynchronize(s));  // the caller's host buffers are free again on return
     if ((rc = launch_status())) return rc;
     have_post = chol_valid = linv_p_valid = true;
+    return GPSO_OK;
+  }
+
+  // ---- variational GP (GPflow 2 VGP, whitened, Gaussian likelihood) ----------------------------
+  // q(v) = N(mu, S S^T) lives here beside the training data: vq_mu [N_pad], vq_S [N_pad^2] (lower; identity on the padding).
+  // Every product is a whole-matrix float64 GEMM (launch_dgemm), every factorisation the fit's launch_potrf; the calls leave
+  // the fit's buffers (K, Lf, linv, work) holding VGP intermediates, so they invalidate any GPR posterior first.
+  DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;
+  int64_t vq_n = -1, vq_npad = -1;  // shape q was made for (another shape: q restarts at the prior)
+  bool vgp_post = false;            // the resident posterior is a VGP predictive (no targets: no append, no self-test)
+  static constexpr double kVgpJitter = 1.0e-6;  // GPflow's default_jitter, in the K of the ELBO and of the predictive
+  enum { kVgpR = 0, kVgpFvar = 1, kVgpSrow = 2, kVgpH = 3, kVgpH2 = 4, kVgpZero = 5, kVgpVecs = 6 };
+  double* vvec_at(int k) const { return as<double>(vvec) + (size_t)k * npad; }
+  // vsmall: [0, 6) the -ELBO sums, [8, 8 + kGradMaxLs + 3) the gradient (launch_gradient: n_ls + 3 doubles), then the four
+  // int verdicts of the factorisations (Gram, Lambda, Sigma, I - Sigma) in two doubles of their own
+  static constexpr int kVgpGradAt = 8, kVgpInfoAt = kVgpGradAt + kGradMaxLs + 3, kVgpSmall = kVgpInfoAt + 2;
+  static_assert(kVgpGradAt >= 6 && kVgpInfoAt >= kVgpGradAt + kGradMaxLs + 3, "vsmall layout: sums, gradient and verdicts overlap");
+  int* vinfo() const { return reinterpret_cast<int*>(as<double>(vsmall) + kVgpInfoAt); }
+
+  int vgp_begin() {
+    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "VGP call before gpso_set_data");
+    int rc = refuse_if_async("a VGP call");
+    if (rc) return rc;
+    if ((rc = ensure_fit_buffers())) return rc;
+    const size_t mat = (size_t)npad * npad * 8;
+    for (DevBuf* b : {&vA, &vB, &vC, &vq_S})
+      if ((rc = ensure(*b, mat))) return rc;
+    if ((rc = ensure(vq_mu, (size_t)npad * 8))) return rc;
+    if ((rc = ensure(vvec, (size_t)kVgpVecs * npad * 8))) return rc;
+    if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
+    if (vq_n != n || vq_npad != npad) vgp_prior();
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = false;
+    linv_p_lazy = false;
+    st_done = st_have = false;
+    forget_peers();
+    reset_generation();
+    return GPSO_OK;
+  }
+  void vgp_prior() {
+    (void)hipMemsetAsync(vq_mu.p, 0, (size_t)npad * 8, st());
+    launch_vgp_pad_identity(st(), as<double>(vq_S), 0, npad, nullptr);
+    vq_n = n;
+    vq_npad = npad;
+  }
+  // A (destroyed: lower triangle read, identity padding) = Lout Lout^T; Linv = Lout^-1.  Both leave as clean lower triangles:
+  // zero above the diagonal, pad_diag on the diagonal of the padding, zero elsewhere on it
+  int vgp_chol(double* A, double* Lout, double* Linv, int* info, double pad_diag) {
+    hipStream_t s = st();
+    HIPCHECK(hipMemsetAsync(Linv, 0, (size_t)npad * npad * 8, s));
+    const int done = launch_potrf<double>(s, A, Lout, Linv, as<double>(work), nullptr, n, npad, as<double>(logdet), info,
+                                          single_level_max, nullptr);
+    if (!(done & 1)) launch_trtri<double>(s, Lout, Linv, as<double>(work), npad, fit_outer_panel(npad));
+    launch_vgp_clean_lower(s, Lout, Lout, n, npad, pad_diag);
+    launch_vgp_clean_lower(s, Linv, Linv, n, npad, pad_diag);
+    return GPSO_OK;
+  }
+  // L = chol(k(X, X) + 1e-6 I) into Lf, L^-1 into linv (clean lower, zero padding)
+  int vgp_factor(int kernel, const double* ls, int n_ls_, double variance, double mean_c) {
+    int rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, mean_c);
+    if (rc) return rc;
+    if ((rc = scale_inputs())) return rc;
+    launch_gram<double>(st(), as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<double>(K), vinfo() + 0);
+    return vgp_chol(as<double>(K), as<double>(Lf), as<double>(linv), vinfo() + 0, 0.0);
+  }
+  // wait for the stream, then the verdicts of the factorisations (out: host copy of vsmall)
+  int vgp_finish(double** out) {
+    double* host = ctx->pinned_scratch(kVgpSmall);
+    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    HIPCHECK(hipMemcpyAsync(host, vsmall.p, kVgpSmall * 8, hipMemcpyDeviceToHost, st()));
+    HIPCHECK(ctx->wait(st()));
+    int rc = launch_status();
+    if (rc) return rc;
+    int info[4];
+    std::memcpy(info, host + kVgpInfoAt, sizeof(info));
+    static const char* what[4] = {"k(X, X) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
+                                  "I - S S^T (reversed order)"};
+    for (int q = 0; q < 4; ++q)
+      if (info[q] != INT_MAX)
+        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d", what[q], info[q]);
+    *out = host;
+    return GPSO_OK;
+  }
+  void vgp_reset_info() {
+    for (int q = 0; q < 4; ++q) launch_vgp_pad_identity(st(), nullptr, 0, 0, vinfo() + q);  // (INT_MAX; no matrix)
+  }
+
+  int vgp_set_q(const double* mu, const double* S, int64_t n_) override {
+    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_set_q before gpso_set_data");
+    if (n_ != n) return ctx->fail(GPSO_E_ARG, "q of %lld points for training data of %lld", (long long)n_, (long long)n);
+    int rc = vgp_begin();
+    if (rc) return rc;
+    if (mu == nullptr || S == nullptr) {  // NULL: the prior
+      vgp_prior();
+      HIPCHECK(ctx->wait(st()));
+      return launch_status();
+    }
+    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
+    double* tmp = as<double>(getter_tmp);
+    hipStream_t s = st();
+    HIPCHECK(hipMemcpyAsync(tmp, S, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(vq_mu.p, 0, (size_t)npad * 8, s));
+    HIPCHECK(hipMemcpyAsync(vq_mu.p, mu, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    launch_vgp_pad_identity(s, as<double>(vq_S), 0, npad, nullptr);
+    launch_convert_in<double>(s, tmp, as<double>(vq_S), n, n, npad);
+    launch_vgp_clean_lower(s, as<double>(vq_S), as<double>(vq_S), n, npad, 1.0);
+    HIPCHECK(hipStreamSynchronize(s));  // (the caller's host buffers are free again on return)
+    vq_n = n;
+    vq_npad = npad;
+    return launch_status();
+  }
+  // data that grew behind the rows q was made for (the caller keeps those rows first, in the same order): q keeps its
+  // leading block and takes the prior (mu = 0, an identity block of S) for the new rows -- on the device, no host copy.
+  // Inside one padded size the padding of q already IS that prior; a new padded size re-lays the leading block out.
+  int vgp_extend_q() override {
+    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_extend_q before gpso_set_data");
+    if (vq_n < 1 || vq_n > n) return ctx->fail(GPSO_E_STATE, "no variational state of at most %lld rows to extend", (long long)n);
+    int rc = refuse_if_async("gpso_vgp_extend_q");
+    if (rc) return rc;
+    hipStream_t s = st();
+    if (vq_npad != npad) {
+      void *nS = nullptr, *nmu = nullptr;
+      HIPCHECK(hipMalloc(&nS, (size_t)npad * npad * 8));
+      HIPCHECK(hipMalloc(&nmu, (size_t)npad * 8));
+      launch_vgp_pad_identity(s, static_cast<double*>(nS), 0, npad, nullptr);
+      HIPCHECK(hipMemsetAsync(nmu, 0, (size_t)npad * 8, s));
+      HIPCHECK(hipMemcpy2DAsync(nS, (size_t)npad * 8, vq_S.p, (size_t)vq_npad * 8, (size_t)vq_n * 8, (size_t)vq_n,
+                                hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(nmu, vq_mu.p, (size_t)vq_n * 8, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipStreamSynchronize(s));
+      HIPCHECK(hipFree(vq_S.p));
+      HIPCHECK(hipFree(vq_mu.p));
+      vq_S = DevBuf{nS, (size_t)npad * npad * 8, false};
+      vq_mu = DevBuf{nmu, (size_t)npad * 8, false};
+    }
+    vq_n = n;
+    vq_npad = npad;
+    HIPCHECK(ctx->wait(s));
+    return launch_status();
+  }
+  int vgp_get_q(double* mu, double* S) override {
+    if (vq_n != n || vq_npad != npad || vq_n < 1) return ctx->fail(GPSO_E_STATE, "no variational state for the resident data");
+    int rc;
+    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
+    double* tmp = as<double>(getter_tmp);
+    hipStream_t s = st();
+    if (S) {
+      launch_convert_out<double>(s, as<double>(vq_S), npad, tmp, n, n, 0);
+      HIPCHECK(hipMemcpyAsync(S, tmp, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (mu) HIPCHECK(hipMemcpyAsync(mu, vq_mu.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return launch_status();
+  }
+
+  // one natural-gradient step on q at theta (GPflow's NaturalGradient with a conjugate likelihood, gamma in (0, 1])
+  int vgp_natgrad(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double gamma) override {
+    if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
+    int rc = vgp_begin();
+    if (rc) return rc;
+    hipStream_t s = st();
+    vgp_reset_info();
+    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
+    double *h = vvec_at(kVgpH), *h2 = vvec_at(kVgpH2);
+    launch_vgp_pad_identity(s, A, 0, npad, nullptr);          // A := I
+    launch_dgemm(s, L, true, L, false, A, npad, 1.0 / s2, 1.0);  // Lambda* = I + L^T L / s2
+    launch_vgp_gemv(s, L, true, as<double>(y64), mean_c, 1.0 / s2, 0.0, nullptr, h, n, npad);  // h* = L^T (y - c) / s2
+    if (gamma != 1.0) {
+      // the current natural parameters: Lambda = S^-T S^-1, h = Lambda mu
+      HIPCHECK(hipMemsetAsync(Cm, 0, (size_t)npad * npad * 8, s));
+      launch_install_chol<double>(s, as<double>(vq_S), npad, npad, B, Cm);
+      launch_trtri<double>(s, B, Cm, as<double>(work), npad, kFitBlock);
+      launch_vgp_clean_lower(s, Cm, Cm, n, npad, 0.0);
+      launch_dgemm(s, Cm, true, Cm, false, B, npad, 1.0, 0.0);
+      launch_vgp_gemv(s, B, false, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, h2, n, npad);
+      launch_vgp_axpby(s, B, A, npad * npad, 1.0 - gamma, gamma);
+      launch_vgp_axpby(s, h2, h, npad, 1.0 - gamma, gamma);
+    }
+    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 1);
+    // GPflow's natural_to_meanvarsqrt: V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
+    if ((rc = vgp_chol(A, B, Cm, vinfo() + 1, 0.0))) return rc;
+    launch_dgemm(s, Cm, true, Cm, false, A, npad, 1.0, 0.0);
+    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, as<double>(vq_mu), n, npad);
+    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 2);
+    if ((rc = vgp_chol(A, as<double>(vq_S), Cm, vinfo() + 2, 1.0))) return rc;
+    double* host;
+    if ((rc = vgp_finish(&host))) {
+      vgp_prior();  // (a failed step leaves q at the prior, not half written)
+      return rc;
+    }
+    return GPSO_OK;
+  }
+
+  // -ELBO at fixed q and its gradient in the constrained theta: grad[n_ls + 3] = (ls..., variance, s2, c)
+  int vgp_elbo(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss, double* grad) override {
+    int rc = vgp_begin();
+    if (rc) return rc;
+    hipStream_t s = st();
+    vgp_reset_info();
+    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    double *L = as<double>(Lf), *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
+    double *Sq = as<double>(vq_S), *mu = as<double>(vq_mu), *r = vvec_at(kVgpR);
+    launch_vgp_gemv(s, L, false, mu, 0.0, 1.0, mean_c, as<double>(y64), r, n, npad);  // r = y - (L mu + c)
+    launch_dgemm(s, L, false, Sq, false, A, npad, 1.0, 0.0);                           // L S
+    launch_vgp_rownorm(s, A, vvec_at(kVgpFvar), n, npad);                              // fvar
+    launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
+    launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma = (L S) S^T
+    launch_vgp_elbo_sums(s, r, vvec_at(kVgpFvar), mu, vvec_at(kVgpSrow), Sq, n, npad, as<double>(vsmall));
+    if (grad) {
+      launch_vgp_lbar(s, B, r, mu, n, npad, 1.0 / s2);                  // Lbar
+      launch_dgemm(s, L, true, B, false, Cm, npad, 1.0, 0.0);          // P = L^T Lbar
+      launch_vgp_phi_sym(s, Cm, A, n, npad);                           // M = Phi(P) + Phi(P)^T
+      launch_dgemm(s, A, false, Li, false, B, npad, 1.0, 0.0);         // M L^-1
+      launch_dgemm(s, Li, true, B, false, Cm, npad, 1.0, 0.0);         // 2 Kbar = L^-T M L^-1
+      HIPCHECK(hipMemsetAsync(vvec_at(kVgpZero), 0, (size_t)npad * 8, s));
+      // the NLML gradient's contraction with K^-1 := 2 Kbar and alpha := 0: W = Kbar, sum_ij Kbar_ij dK_ij / dtheta
+      launch_gradient<double>(s, Li, vvec_at(kVgpZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(),
+                              kp, Cm, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
+    }
+    double* host;
+    if ((rc = vgp_finish(&host))) return rc;
+    const double N = (double)n;
+    const double data = 0.5 * N * std::log(2.0 * M_PI * s2) + (host[1] + host[2]) / (2.0 * s2);
+    const double kl = 0.5 * (host[4] + host[3] - N - host[5]);
+    *loss = data + kl;
+    if (grad) {
+      for (int k = 0; k <= n_ls; ++k) grad[k] = host[kVgpGradAt + k];  // lengthscales..., kernel variance
+      grad[n_ls + 1] = N / (2.0 * s2) - (host[1] + host[2]) / (2.0 * s2 * s2);
+      grad[n_ls + 2] = -host[0] / s2;
+    }
+    return GPSO_OK;
+  }
+
+  // install the predictive at theta: L^-1 := C = R L^-1 (I - S S^T = R^T R), alpha := L^-T mu, noise := s2, mean := c --
+  // every predict path then serves the VGP unchanged
+  int vgp_posterior(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c) override {
+    int rc = vgp_begin();
+    if (rc) return rc;
+    hipStream_t s = st();
+    vgp_reset_info();
+    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sq = as<double>(vq_S);
+    launch_vgp_gemv(s, Li, true, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
+    launch_dgemm(s, Sq, false, Sq, true, A, npad, 1.0, 0.0);        // Sigma
+    launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);           // J (I - Sigma) J
+    if ((rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0))) return rc;     // G
+    launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R = J G^T J
+    launch_dgemm(s, B, false, Li, false, A, npad, 1.0, 0.0);        // C = R L^-1
+    HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+    if ((rc = set_theta(kernel, ls, n_ls_, variance, s2, mean_c))) return rc;
+    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
+    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
+    small_tile_rows = 8;
+    chol_valid = true;  // (the split pieces are packed from linv)
+    if ((rc = pack_bf16())) return rc;
+    double* host;
+    if ((rc = vgp_finish(&host))) {
+      chol_valid = false;
+      return rc;
+    }
+    have_post = linv_p_valid = vgp_post = true;
     return GPSO_OK;
   }
 
@@ -2531,6 +2807,7 @@ struct EngineT : Engine {
     switch (which) {
       case GPSO_MAT_CHOL:
         if (!chol_valid) return ctx->fail(GPSO_E_STATE, "no factor resident");
+        if (vgp_post) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no Cholesky factor of its own (GPSO_MAT_LINV holds C = R L^-1)");
         src = as<TF>(Lf);
         break;
       case GPSO_MAT_LINV:
@@ -2556,6 +2833,7 @@ struct EngineT : Engine {
   int get_vector(int which, double* out) override {
     if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
     if (!have_post || !chol_valid) return ctx->fail(GPSO_E_STATE, "no fitted posterior resident");
+    if (which == GPSO_VEC_WHITE && vgp_post) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no whitened targets");
     const TF* src = (which == GPSO_VEC_ALPHA) ? as<TF>(alpha_f) : (which == GPSO_VEC_WHITE) ? as<TF>(white) : nullptr;
     if (!src) return ctx->fail(GPSO_E_ARG, "unknown vector id %d", which);
     int rc = ensure(getter_tmp, (size_t)n * 8);
@@ -2940,6 +3218,67 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
                        double variance, double noise, double mean_c) {
   ENTER();
   return ctx->eng->set_posterior(X, L, alpha, n, d, kernel, lengthscales, n_ls, variance, noise, mean_c);
+}
+
+// ---- variational GP --------------------------------------------------------------------------------------------
+// theta from the optimiser's vector u, GPflow's transforms (as gpso_fit_eval_u); th[n_ls + 3] = (ls..., variance, s2, c)
+static int vgp_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, double mean_c_fixed, double* th) {
+  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
+  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
+  for (int k = 0; k < n_ls; ++k) th[k] = gpso_softplus(u[k]);
+  th[n_ls] = gpso_softplus(u[n_ls]);
+  th[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
+  th[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
+  return GPSO_OK;
+}
+
+int gpso_vgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t n) {
+  ENTER();
+  if ((mu == nullptr) != (S == nullptr)) return ctx->fail(GPSO_E_ARG, "mu and S: both or neither");
+  return ctx->eng->vgp_set_q(mu, S, n);
+}
+
+int gpso_vgp_extend_q(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->vgp_extend_q();
+}
+
+int gpso_vgp_get_q(gpso_ctx* ctx, double* mu, double* S) {
+  ENTER();
+  return ctx->eng->vgp_get_q(mu, S);
+}
+
+int gpso_vgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double gamma) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->vgp_natgrad(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], gamma);
+}
+
+int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                    double* loss, double* grad_u, double* theta_out) {
+  ENTER();
+  if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
+  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  if (theta_out)
+    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
+  rc = ctx->eng->vgp_elbo(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->vgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2]);
 }
 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,

@@ -1005,6 +1005,26 @@ static void launch_gemm(hipStream_t st, const GemmDesc& g) {
   else launch_gemm_dma<T, 64>(st, g, a_kc, b_kc);
 }
 
+// C = alpha op(A) op(B) + beta C over whole N_pad x N_pad float64 matrices (the products of the VGP path: api.hip
+// EngineT::vgp_*); op = transpose when the flag is set
+void launch_dgemm(hipStream_t st, const double* A, bool trans_a, const double* B, bool trans_b, double* C, int64_t npad,
+                  double alpha, double beta) {
+  GemmDesc g{};
+  g.A = A;
+  g.sai = trans_a ? 1 : npad;
+  g.sak = trans_a ? npad : 1;
+  g.B = B;
+  g.sbk = trans_b ? 1 : npad;
+  g.sbj = trans_b ? npad : 1;
+  g.C = C;
+  g.ldc = npad;
+  g.m = g.n = g.k = g.m_last = (int)npad;
+  g.nbatch = 1;
+  g.alpha = alpha;
+  g.beta = beta;
+  launch_gemm<double>(st, g);
+}
+
 // =============================================================================================
 // rank-W update of the trailing matrix on the bf16 matrix cores (float fits, two-level path)
 // =============================================================================================

@@ -294,6 +294,22 @@ void launch_convert_out(hipStream_t st, const T* src, int64_t ld_src, double* ds
 template <typename T>
 void launch_install_chol(hipStream_t st, const double* L64, int64_t n, int64_t npad, T* K, T* linv);
 
+// C = alpha op(A) op(B) + beta C, whole N_pad x N_pad float64 matrices (fit.hip; N_pad a multiple of 64)
+void launch_dgemm(hipStream_t st, const double* A, bool trans_a, const double* B, bool trans_b, double* C, int64_t npad,
+                  double alpha, double beta);
+// ---- vgp.hip: variational GP (dense N_pad x N_pad float64 buffers, rows / columns >= n are padding) --------------------
+void launch_vgp_clean_lower(hipStream_t st, const double* src, double* dst, int64_t n, int64_t npad, double pad_diag);
+void launch_vgp_pad_identity(hipStream_t st, double* m, int64_t n, int64_t npad, int* info /* nullable: := INT_MAX */);
+void launch_vgp_axpby(hipStream_t st, const double* x, double* y, int64_t len, double a, double b);
+// out = (sub ? sub - v : v), v = alpha op(A) (x - xshift) + add on rows < n (trans: add ignored, sub must be NULL)
+void launch_vgp_gemv(hipStream_t st, const double* A, bool trans, const double* x, double xshift, double alpha, double add,
+                     const double* sub, double* out, int64_t n, int64_t npad);
+void launch_vgp_rownorm(hipStream_t st, const double* A, double* out, int64_t n, int64_t npad);
+void launch_vgp_lbar(hipStream_t st, double* lsig, const double* r, const double* mu, int64_t n, int64_t npad, double inv_s2);
+void launch_vgp_phi_sym(hipStream_t st, const double* p, double* m, int64_t n, int64_t npad);
+void launch_vgp_reverse(hipStream_t st, const double* src, double* out, int64_t n, int64_t npad, int mode, int* info);
+void launch_vgp_elbo_sums(hipStream_t st, const double* r, const double* fvar, const double* mu, const double* srow,
+                          const double* S, int64_t n, int64_t npad, double* out);
 // ---- append.hip: rank-k append at fixed hyper-parameters ----------------------------------------------------------------
 // The posterior of the first n points is resident; k <= kAppendMax new points (already copied behind the old ones in
 // x64 / y64) extend L, L^-1, a, alpha, diag(K_y^-1), the NLML and the scaled inputs in place: two passes over L^-1

@@ -261,6 +261,55 @@ class HipGPEngine:
     def last_message(self):
         return self._lib.gpso_last_error(self._h).decode()
 
+    # -- variational GP (include/gpso_hip.h: gpso_vgp_*) ---------------------------------------------------------------
+    def vgp_set_q(self, mu=None, S=None):
+        """q(v) = N(mu, S S^T) for the resident data; None, None: the prior (mu = 0, S = I)."""
+        if mu is None and S is None:
+            self._check(self._lib.gpso_vgp_set_q(self._h, None, None, self.n))
+            return
+        m = L.as_f64(np.asarray(mu).reshape(-1), (self.n,))
+        Sa = L.as_f64(S, (self.n, self.n))
+        self._check(self._lib.gpso_vgp_set_q(self._h, L.dptr(m), L.dptr(Sa), self.n))
+
+    def vgp_extend_q(self):
+        """After ``set_data`` with the rows q was made for first, in the same order: q keeps its leading block and the
+        new rows get the prior (on the device)."""
+        self._check(self._lib.gpso_vgp_extend_q(self._h))
+
+    def vgp_get_q(self):
+        """(mu [N], S [N, N]) of the variational state on the device."""
+        m = np.empty(self.n, dtype=np.float64)
+        Sa = np.empty((self.n, self.n), dtype=np.float64)
+        self._check(self._lib.gpso_vgp_get_q(self._h, L.dptr(m), L.dptr(Sa)))
+        return m, Sa
+
+    def vgp_natgrad(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, gamma=1.0):
+        """One natural-gradient step of length ``gamma`` on q at the theta of ``u``."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        self._check(self._lib.gpso_vgp_natgrad(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                               float(mean_c_fixed), float(gamma)))
+
+    def vgp_elbo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
+        """-ELBO at fixed q and its gradient in ``u``.  Returns (loss, grad_u or None, theta)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
+        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
+        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+        loss = C.c_double()
+        self._check(self._lib.gpso_vgp_elbo_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                              float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
+                                              L.dptr(ta)))
+        return loss.value, ga, ta
+
+    def vgp_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
+        """Install the VGP predictive at the theta of ``u`` as the resident posterior."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        self._check(self._lib.gpso_vgp_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                                 float(mean_c_fixed)))
+
     def set_posterior(self, X, Lchol, alpha, kernel, lengthscales, variance, noise, mean_c):
         X = L.as_f64(X)
         n, d = X.shape

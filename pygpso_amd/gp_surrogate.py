@@ -13,7 +13,8 @@ What differs is underneath: ``gpflow_model`` is a ``HipGPR`` whose training loss
 ``predict_y`` run as HIP kernels on the MI355X (pygpso_amd/csrc), the point store answers the
 duplicate queries with one vectorised pass over a coordinate array instead of a Python scan, and
 ``gp_eval_best_ucb_grow`` scores whole ternary sub-trees without materialising them on the host.
-``VGPSurrogate`` (variational GP) is out of scope.
+``VGPSurrogate`` (gpso/gp_surrogate.py:536-699) keeps a ``HipVGP``: natural-gradient steps on q and the
+hyper-parameter steps of ``Adam`` (or ``Scipy``) run on the device, and its predictive goes through the same kernels.
 """
 from __future__ import annotations
 
@@ -27,8 +28,9 @@ import math
 import numpy as np
 from scipy.special import erfcinv
 
-from .kernels import KERNEL_CLASSES, Constant, Kernel, Matern52, MeanFunction, Scipy, Zero
+from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, Zero
 from .model import HipGPR
+from .vgp import HipVGP, carried_order
 from .utils import JSON_EXT, PointLabels
 
 DUPLICATE_TOLERANCE = 1.0e-12
@@ -527,3 +529,125 @@ class GPRSurrogate(GPSurrogate):
                    gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
                    points=points, gpflow_model=model, dtype=info.get("dtype", "float64"), device=device,
                    devices=devices, refit_every=info.get("refit_every", 1), refit_guard=info.get("refit_guard", 2.0))
+
+
+VGP_TRAIN_ITERATIONS = 10
+
+
+class VGPSurrogate(GPSurrogate):
+    """Variational GP surrogate (gpso/gp_surrogate.py:536-699): per ``_gp_train`` iteration one natural-gradient step on
+    the variational state q, then one step of the hyper-parameter optimiser (``Adam``, or ``Scipy``) on -ELBO at fixed q
+    -- all on the device (``HipVGP``).  Gaussian likelihood only.
+
+    The model keeps its rows in their order of arrival between updates and grows q by the prior for new rows; when a held
+    row disappears or its score changes, q restarts at the prior in the caller's order (``pygpso_amd.vgp``)."""
+
+    def __init__(self, gp_kernel, gp_meanf=None, likelihood=None, optimiser=None, varsigma=erfcinv(0.01), points=None,
+                 gpflow_model=None, natgrad_learning_rate=1.0, train_iterations=VGP_TRAIN_ITERATIONS, dtype="float64",
+                 device=0, engine_options=None):
+        """
+        :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``); any other likelihood raises
+            NotImplementedError
+        :param optimiser: hyper-parameter optimiser, default ``Adam(0.01)`` (its moments persist across updates)
+        :param natgrad_learning_rate: step length gamma in (0, 1] of the natural gradient
+        :param train_iterations: natgrad / optimiser iterations per ``_gp_train``
+        :param dtype: "float64" (default) or "mixed" (float64 training, float predict arithmetic); "float32" raises
+        """
+        likelihood = likelihood if likelihood is not None else Gaussian(1.0e-3)
+        if not isinstance(likelihood, Gaussian):
+            raise NotImplementedError(f"{type(likelihood).__name__}: only the Gaussian likelihood is supported")
+        gamma = float(natgrad_learning_rate)
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError(f"natgrad_learning_rate {gamma} outside (0, 1]")
+        if dtype not in ("float64", "mixed"):
+            raise ValueError(f"VGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
+        super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf,
+                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma,
+                         points=points, gpflow_model=gpflow_model, dtype=dtype, device=device,
+                         engine_options=engine_options)
+        self.likelihood = likelihood
+        self.natgrad_gamma = gamma
+        self.train_iters = int(train_iterations)
+
+    def _gp_train(self, x, y):
+        assert x.shape[0] == y.shape[0]
+        assert x.ndim == 2 and y.ndim == 2
+        if self.gpflow_model is None:
+            self.gpflow_model = HipVGP(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
+                                       likelihood=self.likelihood, dtype=self.dtype, device=self.device,
+                                       engine_options=self.engine_options)
+        else:
+            self.gpflow_model.data = (x, y)
+        model = self.gpflow_model
+        for i in range(self.train_iters):
+            model.natgrad(self.natgrad_gamma)
+            self.optimiser.minimize(model.training_loss, model.trainable_variables)
+            if logging.getLogger().isEnabledFor(logging.DEBUG):
+                logging.debug(f"VGP iteration {i + 1}. ELBO: {model.elbo():.04f}")
+
+    def _serialise_optimiser(self):
+        if isinstance(self.optimiser, Adam):
+            return ["Adam", self.optimiser.learning_rate]
+        return [type(self.optimiser).__name__]
+
+    @staticmethod
+    def _deserialise_optimiser(info):
+        if info[0] == "Adam":
+            return Adam(info[1])
+        if info[0] == "Scipy":
+            return Scipy()
+        raise ValueError(f"{info} not currently supported.")
+
+    def save(self, folder):
+        os.makedirs(folder, exist_ok=True)
+        self.points.save(os.path.join(folder, self.POINTS_FILE))
+        model = self.gpflow_model
+        params = {k: np.asarray(v).tolist() for k, v in model.parameter_dict().items()}
+        with open(os.path.join(folder, self.GPR_FILE), "w") as fh:
+            fh.write(json.dumps(params))
+        # the model's rows as indices into the evaluated points (its order of arrival may differ from the list's)
+        ev_x, ev_y = self.current_training_data
+        order = carried_order(model.data[0], model.data[1], ev_x, ev_y[:, np.newaxis])
+        info = {
+            "vgp_kernel": model.kernel.name,
+            "vgp_kernel_shape": list(np.shape(model.kernel.lengthscales)),
+            "vgp_meanf": type(model.mean_function).__name__,
+            "vgp_meanf_shape": [1] if isinstance(model.mean_function, Constant) else [],  # (the shape of c)
+            "vgp_likelihood": self.likelihood.name,
+            "gp_varsigma": self.gp_varsigma,
+            "optimiser": self._serialise_optimiser(),
+            "vgp_iters": self.train_iters,
+            "vgp_natgrad_lr": self.natgrad_gamma,
+            "dtype": self.dtype,  # (extra keys, not in the reference's schema)
+            "vgp_row_order": None if order is None else order[: model.data[0].shape[0]].tolist(),
+        }
+        with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
+            fh.write(json.dumps(info))
+
+    @classmethod
+    def from_saved(cls, folder, device=0):
+        points = GPListOfPoints.from_file(os.path.join(folder, cls.POINTS_FILE))
+        ev = [p for p in points if p.label == PointLabels.evaluated]
+        x = np.array([p.normed_coord for p in ev])
+        y = np.array([p.score_mu for p in ev])[:, np.newaxis]
+        with open(os.path.join(folder, cls.GPR_INFO)) as fh:
+            info = json.load(fh)
+        with open(os.path.join(folder, cls.GPR_FILE)) as fh:
+            params = json.load(fh)
+        assert info["vgp_kernel"] in KERNEL_CLASSES
+        if info.get("vgp_likelihood", "Gaussian") != "Gaussian":
+            raise NotImplementedError(f"{info['vgp_likelihood']}: only the Gaussian likelihood is supported")
+        kernel = KERNEL_CLASSES[info["vgp_kernel"]](
+            lengthscales=np.array(params[".kernel.lengthscales"]), variance=params[".kernel.variance"])
+        meanf = Constant(params[".mean_function.c"]) if info["vgp_meanf"] == "Constant" else Zero()
+        likelihood = Gaussian(params[".likelihood.variance"])
+        dtype = info.get("dtype", "float64")
+        order = info.get("vgp_row_order")
+        if order is not None:
+            x, y = x[order], y[order]
+        model = HipVGP(data=(x, y), kernel=kernel, mean_function=meanf, likelihood=likelihood, dtype=dtype,
+                       device=device, q_mu=np.array(params[".q_mu"]), q_sqrt=np.array(params[".q_sqrt"]))
+        return cls(gp_kernel=kernel, gp_meanf=meanf, likelihood=likelihood,
+                   optimiser=cls._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
+                   points=points, gpflow_model=model, natgrad_learning_rate=info["vgp_natgrad_lr"],
+                   train_iterations=info["vgp_iters"], dtype=dtype, device=device)

@@ -73,6 +73,54 @@ class Zero(MeanFunction):
     c = 0.0
 
 
+class Gaussian:
+    """Gaussian likelihood spec (``gpflow.likelihoods.Gaussian(variance=...)``): the initial noise variance."""
+
+    name = "Gaussian"
+
+    def __init__(self, variance=1.0e-3):
+        self.variance = float(variance)
+
+    def __repr__(self):
+        return f"Gaussian(variance={self.variance})"
+
+
+class Adam:
+    """Keras's Adam (``tf.optimizers.Adam(learning_rate)``, the VGP surrogate's default optimiser,
+    gpso/gp_surrogate.py:543): ``minimize(closure, variables)`` takes ONE step on the model's unconstrained vector,
+    u -= lr sqrt(1 - beta2^t) / (1 - beta1^t) m / (sqrt(v) + epsilon).  The moments m, v and the step count t live in this
+    object and persist across calls, as in Keras."""
+
+    def __init__(self, learning_rate=0.01, beta_1=0.9, beta_2=0.999, epsilon=1.0e-7):
+        self.learning_rate = float(learning_rate)
+        self.beta_1, self.beta_2, self.epsilon = float(beta_1), float(beta_2), float(epsilon)
+        self.m = self.v = None
+        self.iterations = 0
+
+    def step(self, u, g):
+        g = np.asarray(g, dtype=np.float64)
+        if self.m is None or self.m.shape != g.shape:
+            self.m = np.zeros_like(g)
+            self.v = np.zeros_like(g)
+        self.iterations += 1
+        t = self.iterations
+        self.m = self.beta_1 * self.m + (1.0 - self.beta_1) * g
+        self.v = self.beta_2 * self.v + (1.0 - self.beta_2) * g * g
+        a = self.learning_rate * np.sqrt(1.0 - self.beta_2 ** t) / (1.0 - self.beta_1 ** t)
+        return np.asarray(u, dtype=np.float64) - a * self.m / (np.sqrt(self.v) + self.epsilon)
+
+    def minimize(self, closure, variables=None):
+        model = getattr(closure, "__self__", None)
+        if model is None or not hasattr(model, "_loss_and_grad"):
+            raise TypeError("Adam.minimize expects the bound training_loss of a pygpso_amd model")
+        u = model._pack()
+        _, g = model._loss_and_grad(u)
+        model._assign(self.step(u, g))
+
+    def __repr__(self):
+        return f"Adam(learning_rate={self.learning_rate})"
+
+
 class Scipy:
     """L-BFGS-B through SciPy with SciPy's defaults -- what
     ``gpflow.optimizers.Scipy().minimize(model.training_loss, model.trainable_variables)`` does

@@ -1,0 +1,173 @@
+"""
+``HipVGP``: the variational GP the ``VGPSurrogate`` keeps in ``.gpflow_model``.
+
+Stands where ``gpflow.models.VGP`` (Gaussian likelihood) stands in the reference (gpso/gp_surrogate.py:536-699):
+whitened variational state q(v) = N(q_mu, q_sqrt q_sqrt^T) on the device beside the training data, the -ELBO and its
+gradient in the hyper-parameters (``training_loss`` / ``_loss_and_grad``, driven by ``Adam`` or ``Scipy``), one natural-
+gradient step on q (``natgrad``) and ``predict_y`` / ``best_ucb`` through the predict kernels of the GPR path: the
+predictive is installed as (C = R L^-1, beta = L^-T mu, sigma^2, c) with I - S S^T = R^T R (include/gpso_hip.h:
+gpso_vgp_posterior).  Hyper-parameters and their transforms are ``HipGPR``'s.
+
+Data that grows between updates.  GPflow's VGP keeps q sized to the data it was built with; here the model keeps its rows
+in their order of arrival: when every row it holds is still among the new data with its score, the new rows go behind
+the old ones and q grows by mu = 0 and an identity block of S for them (Cholesky factors keep their leading block, so at
+fixed theta this is the GP's conditional for the new rows).  When a held row disappears or its score changes, the model
+takes the caller's rows in the caller's order and q restarts at the prior.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .kernels import Gaussian
+from .model import HipGPR
+
+
+def _row_keys(x, y):
+    return [xr.tobytes() + yr.tobytes() for xr, yr in zip(np.ascontiguousarray(x), np.ascontiguousarray(y))]
+
+
+def carried_order(old_x, old_y, x, y):
+    """Row order of the model after new data (x, y): indices into (x, y), the rows the model held first (in its order),
+    then the others in the caller's order -- or None when a held row (coordinates and score, bit for bit) is missing."""
+    if old_x is None or old_x.shape[1] != x.shape[1] or x.shape[0] < old_x.shape[0]:
+        return None
+    where = {}
+    for i, k in enumerate(_row_keys(x, y)):
+        where.setdefault(k, []).append(i)
+    taken = np.zeros(x.shape[0], dtype=bool)
+    order = []
+    for k in _row_keys(old_x, old_y):
+        cand = where.get(k)
+        if not cand:
+            return None
+        i = cand.pop(0)
+        taken[i] = True
+        order.append(i)
+    order.extend(np.flatnonzero(~taken).tolist())
+    return np.asarray(order, dtype=np.int64)
+
+
+class HipVGP(HipGPR):
+    def __init__(self, data, kernel, mean_function=None, likelihood=None, dtype="float64", device=0, engine=None,
+                 engine_options=None, q_mu=None, q_sqrt=None):
+        """``dtype``: "float64" or "mixed" (float64 training, float predict arithmetic).  ``q_mu`` [N] / [N, 1] and
+        ``q_sqrt`` [N, N] / [1, N, N] (optional): the variational state for ``data`` in its row order."""
+        if dtype not in ("float64", "mixed"):
+            raise ValueError(f"VGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
+        likelihood = likelihood if likelihood is not None else Gaussian()
+        if not isinstance(likelihood, Gaussian):
+            raise NotImplementedError("only the Gaussian likelihood is supported by the device VGP")
+        super().__init__(data, kernel, mean_function=mean_function, noise_variance=likelihood.variance, dtype=dtype,
+                         device=device, engine=engine, engine_options=engine_options, escalate=False)
+        if q_mu is not None:
+            self.set_q(q_mu, q_sqrt)
+
+    # -- data and q -------------------------------------------------------------------------------
+    @property
+    def data(self):
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        x, y = value
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 1)
+        assert x.ndim == 2 and x.shape[0] == y.shape[0]
+        old = self._data
+        order = None if old is None else carried_order(old[0], old[1], x, y)
+        if order is not None:
+            x, y = x[order], y[order]
+        self._data = (x, y)
+        self.engine.set_data(x, y[:, 0])
+        if order is not None:
+            self.engine.vgp_extend_q()  # q of the held rows kept, the prior for the new ones: on the device
+        else:
+            self.engine.vgp_set_q()
+        self.q_carried = order is not None
+        self._resident = False
+        self._device_theta = None
+
+    def set_q(self, q_mu, q_sqrt):
+        n = self._data[0].shape[0]
+        self.engine.vgp_set_q(np.asarray(q_mu, dtype=np.float64).reshape(n),
+                              np.asarray(q_sqrt, dtype=np.float64).reshape(n, n))
+        self._resident = False
+
+    def get_q(self):
+        """(q_mu [N], q_sqrt [N, N]) in the model's row order."""
+        return self.engine.vgp_get_q()
+
+    def append_data(self, x_new, y_new):
+        """New rows behind the held ones; q grows by the prior for them (no in-place posterior update for a VGP)."""
+        x = np.concatenate([self._data[0], np.atleast_2d(x_new)])
+        y = np.concatenate([self._data[1], np.asarray(y_new, dtype=np.float64).reshape(-1, 1)])
+        self.data = (x, y)
+        return False
+
+    # -- training -------------------------------------------------------------------------------
+    def _args(self):
+        return self.kernel.name, self.n_ls, self._train_mean, float(self.mean_function.c)
+
+    def natgrad(self, gamma=1.0):
+        """One natural-gradient step of length gamma in (0, 1] on q at the current hyper-parameters."""
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError(f"natural-gradient step {gamma} outside (0, 1]")
+        name, k, tm, c = self._args()
+        self.engine.vgp_natgrad(name, self._pack(), k, tm, c, gamma)
+        self._resident = False
+
+    def _loss_and_grad(self, u):
+        """-ELBO and its gradient in u at fixed q (one device evaluation)."""
+        name, k, tm, c = self._args()
+        f, gu, _ = self.engine.vgp_elbo_u(name, u, k, tm, c)
+        self._last_nlml = f
+        self.num_loss_evals += 1
+        self._resident = False
+        return f, gu
+
+    def training_loss(self):
+        """-ELBO at the current hyper-parameters and q."""
+        name, k, tm, c = self._args()
+        f, _, _ = self.engine.vgp_elbo_u(name, self._pack(), k, tm, c, want_grad=False)
+        self._resident = False
+        return f
+
+    def elbo(self):
+        return -self.training_loss()
+
+    def log_marginal_likelihood(self):
+        raise NotImplementedError("a VGP has no exact marginal likelihood: use elbo()")
+
+    def _ensure_resident(self):
+        if not self._resident:
+            name, k, tm, c = self._args()
+            self.engine.vgp_posterior(name, self._pack(), k, tm, c)
+            self._resident = True
+
+    def _escalate(self, err, fit=False):
+        return False
+
+    # -- reporting -----------------------------------------------------------------------------
+    def parameter_dict(self):
+        mu, S = self.get_q()
+        d = super().parameter_dict()
+        d[".q_mu"] = mu.reshape(-1, 1)
+        d[".q_sqrt"] = S.reshape(1, S.shape[0], S.shape[1])
+        return d
+
+    def summary(self):
+        rows = [
+            ("VGP.mean_function.c", "", self.mean_function.c),
+            ("VGP.kernel.variance", "Softplus", self.kernel.variance),
+            ("VGP.kernel.lengthscales", "Softplus", self.kernel.lengthscales),
+            ("VGP.likelihood.variance", "Softplus + Shift", self.likelihood.variance),
+        ]
+        lines = [f"{'name':<24} {'transform':<17} {'value'}"]
+        for name, tr, val in rows:
+            v = np.array2string(np.asarray(val), precision=6) if np.ndim(val) else f"{val:.6g}"
+            lines.append(f"{name:<24} {tr:<17} {v}")
+        n = self._data[0].shape[0]
+        lines.append(f"{'VGP.q_mu':<24} {'':<17} shape ({n}, 1)")
+        lines.append(f"{'VGP.q_sqrt':<24} {'FillTriangular':<17} shape (1, {n}, {n})")
+        return "\n".join(lines)
+
