@@ -224,11 +224,32 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
                        double variance, double noise, double mean_c);
 
 /* ---- variational GP (VGPSurrogate._gp_train, gpso/gp_surrogate.py:536-699) ------------------------------------------
- * GPflow 2's whitened VGP with a Gaussian likelihood on the resident training data (gpso_set_data): q(v) = N(mu, S S^T),
+ * GPflow 2's whitened VGP (Gaussian likelihood unless gpso_vgp_set_likelihood says otherwise) on the resident training data (gpso_set_data): q(v) = N(mu, S S^T),
  * f = L v + c, L = chol(k(X, X) + 1e-6 I) (GPflow's default jitter).  u, n_ls, train_mean, mean_c_fixed: the optimiser's
  * vector and transforms exactly as gpso_fit_eval_u (the likelihood variance s2 = 1e-6 + softplus(u[n_ls + 1])).  float64
  * arithmetic throughout: GPSO_F64 and GPSO_MIXED contexts (GPSO_F32: GPSO_E_ARG).  Every call replaces whatever posterior
  * was resident.  q starts at the prior (mu = 0, S = I) whenever the shape of the data changes. */
+
+/* The VGP's likelihood (gpso_vgp_set_likelihood).  GPSO_LIK_GAUSSIAN (the default of every context): the closed-form
+ * Gaussian sequence; u[n_ls + 1] is softplus^-1(s2 - 1e-6).  GPSO_LIK_STUDENT_T: gpflow.likelihoods.StudentT(scale, df),
+ * df fixed, through GPflow's Gauss-Hermite variational expectations; u[n_ls + 1] is softplus^-1(scale) (GPflow's
+ * positive(), no shift), theta_out[n_ls + 1] the scale, grad_u[n_ls + 1] d(-ELBO)/du of it, and gpso_vgp_posterior
+ * installs the predictive variance var_f + scale^2 df / (df - 2).  Under either quadrature kind S S^T can exceed I in a
+ * direction; the install then serves var_f + delta (k** - |L^-1 k*|^2), delta the first of 0, 1e-8, 2e-8, ... for which
+ * I - S S^T / (1 + delta) factorises: never below var_f, at most delta k** above it.  GPSO_LIK_GAUSSIAN_GH: the Gaussian through the
+ * same quadrature sequence as the Student-t (u as GPSO_LIK_GAUSSIAN): a check of that sequence against the closed form. */
+#define GPSO_LIK_GAUSSIAN 0
+#define GPSO_LIK_STUDENT_T 1
+#define GPSO_LIK_GAUSSIAN_GH 2
+
+/* Replaces: choosing the likelihood of gpflow.models.VGP(likelihood=...) (gpso/gp_surrogate.py:536-541).  kind:
+ * GPSO_LIK_*; df: the Student-t's degrees of freedom (> 2; ignored otherwise); gh_x[n_gh], gh_w[n_gh]: the Gauss-Hermite
+ * nodes and weights of numpy.polynomial.hermite.hermgauss(n_gh) (GPflow's 20 points), 1 <= n_gh <= 64 (both ignored
+ * for GPSO_LIK_GAUSSIAN).  Anything else: GPSO_E_ARG.  Takes effect at the next gpso_vgp_* call; q is kept.
+ * Under a quadrature likelihood gpso_vgp_natgrad forms the step at the current q (Lambda* = I + L^T diag(a) L,
+ * h* = L^T (g_m + a (m - c))); when a factorisation fails -- an indefinite step, e.g. at gross outliers with gamma = 1 --
+ * it returns GPSO_E_NOTPD and leaves q exactly as it was (as GPflow), where the Gaussian restarts q at the prior. */
+int gpso_vgp_set_likelihood(gpso_ctx* ctx, int kind, double df, int n_gh, const double* gh_x, const double* gh_w);
 
 /* Replaces: assigning q_mu / q_sqrt of a GPflow VGP (gpflow.utilities.multiple_assign, gpso/gp_surrogate.py:667-671).
  * Host float64 mu[n], S[n*n] (row-major, lower triangle read); n must equal the resident N; both NULL: the prior. */

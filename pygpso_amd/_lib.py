@@ -24,6 +24,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 UNIQUE_ID_BYTES = 128
 MAT_CHOL, MAT_LINV, MAT_KINV, MAT_GRAM = 0, 1, 2, 3
 VEC_ALPHA, VEC_WHITE = 0, 1
+LIK_GAUSSIAN, LIK_STUDENT_T, LIK_GAUSSIAN_GH = 0, 1, 2
+LIKELIHOOD_IDS = {"Gaussian": LIK_GAUSSIAN, "StudentT": LIK_STUDENT_T, "GaussianGH": LIK_GAUSSIAN_GH}
 OPT_PREDICT_MATH = 1
 OPT_FIT_SINGLE_LEVEL_MAX = 2
 OPT_GENERATION = 3
@@ -80,6 +82,7 @@ SIGNATURES = {
     "gpso_set_posterior": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64,
                                      C.c_int, C.c_int, _c_double_p, C.c_int, C.c_double, C.c_double,
                                      C.c_double]),
+    "gpso_vgp_set_likelihood": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, _c_double_p, _c_double_p]),
     "gpso_vgp_set_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64]),
     "gpso_vgp_get_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
     "gpso_vgp_extend_q": (C.c_int, [C.c_void_p]),

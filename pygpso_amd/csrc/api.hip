@@ -126,6 +126,8 @@ struct Engine {
   virtual int vgp_elbo(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double* loss,
                        double* grad) = 0;
   virtual int vgp_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c) = 0;
+  virtual int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) = 0;
+  int vlik_kind = GPSO_LIK_GAUSSIAN;  // the VGP's likelihood (GPSO_LIK_*): what slot n_ls + 1 of u means
 };
 
 // contiguous share [lo, hi) of m items for `rank` of `world`: global order is preserved across ranks
@@ -423,7 +425,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -1242,6 +1244,58 @@ struct EngineT : Engine {
   static constexpr int kVgpGradAt = 8, kVgpInfoAt = kVgpGradAt + kGradMaxLs + 3, kVgpSmall = kVgpInfoAt + 2;
   static_assert(kVgpGradAt >= 6 && kVgpInfoAt >= kVgpGradAt + kGradMaxLs + 3, "vsmall layout: sums, gradient and verdicts overlap");
   int* vinfo() const { return reinterpret_cast<int*>(as<double>(vsmall) + kVgpInfoAt); }
+  // a general scalar likelihood (vlik_kind != GPSO_LIK_GAUSSIAN): df, the Gauss-Hermite rule on the device (vgh: [0, 64)
+  // nodes x sqrt(2), [64, 128) weights / sqrt(pi)) and the per-point vectors of the quadrature (vlvec)
+  DevBuf vgh, vlvec;
+  double vlik_df = 0.0;
+  int vlik_n_gh = 0;
+  enum { kLikM = 0, kLikV = 1, kLikGm = 2, kLikA = 3, kLikT = 4, kLikVe = 5, kLikDve = 6, kLikMu = 7, kLikVecs = 8 };
+  double* lvec_at(int k) const { return as<double>(vlvec) + (size_t)k * npad; }
+  // the f-free part of log p(y | f) at the likelihood parameter p (Student-t: the scale; Gaussian: the variance)
+  double vlik_const(double p) const {
+    if (vlik_kind == GPSO_LIK_STUDENT_T)
+      return std::lgamma(0.5 * (vlik_df + 1.0)) - std::lgamma(0.5 * vlik_df) -
+             0.5 * (std::log(p * p) + std::log(vlik_df) + std::log(M_PI));
+    return -0.5 * (std::log(2.0 * M_PI) + std::log(p));
+  }
+  // m = L mu + c, v = rownorm(L S) (A := L S), then the quadrature at q: gm, a, t, VE, dVE/dp
+  void vgp_quadrature(const double* L, double* A, double p, double mean_c) {
+    hipStream_t s = st();
+    launch_vgp_gemv(s, L, false, as<double>(vq_mu), 0.0, 1.0, mean_c, nullptr, lvec_at(kLikM), n, npad);
+    launch_dgemm(s, L, false, as<double>(vq_S), false, A, npad, 1.0, 0.0);
+    launch_vgp_rownorm(s, A, lvec_at(kLikV), n, npad);
+    launch_vgp_quad(s, as<double>(y64), lvec_at(kLikM), lvec_at(kLikV), as<double>(vgh), vlik_n_gh, vlik_kind, p, vlik_df,
+                    vlik_const(p), mean_c, lvec_at(kLikGm), lvec_at(kLikA), lvec_at(kLikT), lvec_at(kLikVe),
+                    lvec_at(kLikDve), n, npad);
+  }
+
+  int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) override {
+    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
+    if (kind != GPSO_LIK_GAUSSIAN && kind != GPSO_LIK_STUDENT_T && kind != GPSO_LIK_GAUSSIAN_GH)
+      return ctx->fail(GPSO_E_ARG, "unknown likelihood kind %d", kind);
+    if (kind != GPSO_LIK_GAUSSIAN) {
+      if (n_gh < 1 || n_gh > 64) return ctx->fail(GPSO_E_ARG, "n_gh=%d outside [1, 64]", n_gh);
+      if (!gh_x || !gh_w) return ctx->fail(GPSO_E_ARG, "gh_x / gh_w must not be NULL");
+      if (kind == GPSO_LIK_STUDENT_T && !(df > 2.0))
+        return ctx->fail(GPSO_E_ARG, "Student-t df=%g: need df > 2 (a finite predictive variance)", df);
+    }
+    int rc = refuse_if_async("gpso_vgp_set_likelihood");
+    if (rc) return rc;
+    if (kind != GPSO_LIK_GAUSSIAN) {
+      if ((rc = ensure(vgh, 128 * 8))) return rc;
+      double host[128] = {};
+      for (int k = 0; k < n_gh; ++k) {  // (GPflow's ndiagquad: x sqrt(2), w / sqrt(pi))
+        host[k] = gh_x[k] * std::sqrt(2.0);
+        host[64 + k] = gh_w[k] / std::sqrt(M_PI);
+      }
+      HIPCHECK(hipMemcpyAsync(vgh.p, host, sizeof(host), hipMemcpyHostToDevice, st()));
+      HIPCHECK(hipStreamSynchronize(st()));
+    }
+    vlik_kind = kind;
+    vlik_df = kind == GPSO_LIK_STUDENT_T ? df : 0.0;
+    vlik_n_gh = kind == GPSO_LIK_GAUSSIAN ? 0 : n_gh;
+    return launch_status();
+  }
 
   int vgp_begin() {
     if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
@@ -1255,6 +1309,7 @@ struct EngineT : Engine {
     if ((rc = ensure(vq_mu, (size_t)npad * 8))) return rc;
     if ((rc = ensure(vvec, (size_t)kVgpVecs * npad * 8))) return rc;
     if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
+    if (vlik_kind != GPSO_LIK_GAUSSIAN && (rc = ensure(vlvec, (size_t)kLikVecs * npad * 8))) return rc;
     if (vq_n != n || vq_npad != npad) vgp_prior();
     have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = false;
     linv_p_lazy = false;
@@ -1391,9 +1446,20 @@ struct EngineT : Engine {
     if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
     double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
     double *h = vvec_at(kVgpH), *h2 = vvec_at(kVgpH2);
-    launch_vgp_pad_identity(s, A, 0, npad, nullptr);          // A := I
-    launch_dgemm(s, L, true, L, false, A, npad, 1.0 / s2, 1.0);  // Lambda* = I + L^T L / s2
-    launch_vgp_gemv(s, L, true, as<double>(y64), mean_c, 1.0 / s2, 0.0, nullptr, h, n, npad);  // h* = L^T (y - c) / s2
+    const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
+    if (!general) {
+      launch_vgp_pad_identity(s, A, 0, npad, nullptr);          // A := I
+      launch_dgemm(s, L, true, L, false, A, npad, 1.0 / s2, 1.0);  // Lambda* = I + L^T L / s2
+      launch_vgp_gemv(s, L, true, as<double>(y64), mean_c, 1.0 / s2, 0.0, nullptr, h, n, npad);  // h* = L^T (y - c) / s2
+    } else {
+      // the per-point derivatives at the current q (s2: the likelihood's parameter), then
+      // Lambda* = I + L^T diag(a) L and h* = L^T (gm + a (m - c))
+      vgp_quadrature(L, A, s2, mean_c);
+      launch_vgp_rowscale(s, L, lvec_at(kLikA), B, n, npad);
+      launch_vgp_pad_identity(s, A, 0, npad, nullptr);
+      launch_dgemm(s, L, true, B, false, A, npad, 1.0, 1.0);
+      launch_vgp_gemv(s, L, true, lvec_at(kLikT), 0.0, 1.0, 0.0, nullptr, h, n, npad);
+    }
     if (gamma != 1.0) {
       // the current natural parameters: Lambda = S^-T S^-1, h = Lambda mu
       HIPCHECK(hipMemsetAsync(Cm, 0, (size_t)npad * npad * 8, s));
@@ -1407,15 +1473,25 @@ struct EngineT : Engine {
     }
     launch_vgp_pad_identity(s, A, n, npad, vinfo() + 1);
     // GPflow's natural_to_meanvarsqrt: V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
+    // (a general likelihood builds the new q in scratch -- mu in its vector, S in the Gram's buffer, free by now -- and
+    // commits it only when every factorisation held: GPflow's natgrad assigns nothing when natural_to_meanvarsqrt fails)
+    double* mu_out = general ? lvec_at(kLikMu) : as<double>(vq_mu);
+    double* S_out = general ? as<double>(K) : as<double>(vq_S);
     if ((rc = vgp_chol(A, B, Cm, vinfo() + 1, 0.0))) return rc;
     launch_dgemm(s, Cm, true, Cm, false, A, npad, 1.0, 0.0);
-    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, as<double>(vq_mu), n, npad);
+    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, mu_out, n, npad);
     launch_vgp_pad_identity(s, A, n, npad, vinfo() + 2);
-    if ((rc = vgp_chol(A, as<double>(vq_S), Cm, vinfo() + 2, 1.0))) return rc;
+    if ((rc = vgp_chol(A, S_out, Cm, vinfo() + 2, 1.0))) return rc;
     double* host;
     if ((rc = vgp_finish(&host))) {
-      vgp_prior();  // (a failed step leaves q at the prior, not half written)
+      if (!general) vgp_prior();  // (a failed Gaussian step leaves q at the prior, not half written; a general one: q as it was)
       return rc;
+    }
+    if (general) {
+      HIPCHECK(hipMemcpyAsync(vq_mu.p, mu_out, (size_t)npad * 8, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(vq_S.p, S_out, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(ctx->wait(s));
+      return launch_status();
     }
     return GPSO_OK;
   }
@@ -1429,14 +1505,24 @@ struct EngineT : Engine {
     if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
     double *L = as<double>(Lf), *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
     double *Sq = as<double>(vq_S), *mu = as<double>(vq_mu), *r = vvec_at(kVgpR);
-    launch_vgp_gemv(s, L, false, mu, 0.0, 1.0, mean_c, as<double>(y64), r, n, npad);  // r = y - (L mu + c)
-    launch_dgemm(s, L, false, Sq, false, A, npad, 1.0, 0.0);                           // L S
-    launch_vgp_rownorm(s, A, vvec_at(kVgpFvar), n, npad);                              // fvar
-    launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
-    launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma = (L S) S^T
-    launch_vgp_elbo_sums(s, r, vvec_at(kVgpFvar), mu, vvec_at(kVgpSrow), Sq, n, npad, as<double>(vsmall));
+    const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
+    if (!general) {
+      launch_vgp_gemv(s, L, false, mu, 0.0, 1.0, mean_c, as<double>(y64), r, n, npad);  // r = y - (L mu + c)
+      launch_dgemm(s, L, false, Sq, false, A, npad, 1.0, 0.0);                           // L S
+      launch_vgp_rownorm(s, A, vvec_at(kVgpFvar), n, npad);                              // fvar
+      launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
+      launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma = (L S) S^T
+      launch_vgp_elbo_sums(s, r, vvec_at(kVgpFvar), mu, vvec_at(kVgpSrow), Sq, n, npad, as<double>(vsmall));
+    } else {
+      vgp_quadrature(L, A, s2, mean_c);                                                  // A = L S; gm, a, VE, dVE/dp
+      launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
+      launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma
+      launch_vgp_lik_sums(s, lvec_at(kLikVe), lvec_at(kLikDve), lvec_at(kLikGm), mu, vvec_at(kVgpSrow), Sq, n, npad,
+                          as<double>(vsmall));
+    }
     if (grad) {
-      launch_vgp_lbar(s, B, r, mu, n, npad, 1.0 / s2);                  // Lbar
+      if (!general) launch_vgp_lbar(s, B, r, mu, n, npad, 1.0 / s2);   // Lbar
+      else launch_vgp_lbar_w(s, B, lvec_at(kLikA), lvec_at(kLikGm), mu, n, npad);  // Lbar = tril(diag(a) L Sigma - gm mu^T)
       launch_dgemm(s, L, true, B, false, Cm, npad, 1.0, 0.0);          // P = L^T Lbar
       launch_vgp_phi_sym(s, Cm, A, n, npad);                           // M = Phi(P) + Phi(P)^T
       launch_dgemm(s, A, false, Li, false, B, npad, 1.0, 0.0);         // M L^-1
@@ -1449,6 +1535,15 @@ struct EngineT : Engine {
     double* host;
     if ((rc = vgp_finish(&host))) return rc;
     const double N = (double)n;
+    if (general) {  // -sum VE + KL; d/dp = -sum dVE/dp, d/dc = -sum gm
+      *loss = -host[0] + 0.5 * (host[4] + host[3] - N - host[5]);
+      if (grad) {
+        for (int k = 0; k <= n_ls; ++k) grad[k] = host[kVgpGradAt + k];
+        grad[n_ls + 1] = -host[1];
+        grad[n_ls + 2] = -host[2];
+      }
+      return GPSO_OK;
+    }
     const double data = 0.5 * N * std::log(2.0 * M_PI * s2) + (host[1] + host[2]) / (2.0 * s2);
     const double kl = 0.5 * (host[4] + host[3] - N - host[5]);
     *loss = data + kl;
@@ -1458,6 +1553,34 @@ struct EngineT : Engine {
       grad[n_ls + 2] = -host[0] / s2;
     }
     return GPSO_OK;
+  }
+
+  // install under a quadrature likelihood: G = chol J (I - Sigma / (1 + delta)) J into vC (G^-1 in vA), with the
+  // smallest delta of 0, 1e-8, 2e-8, 4e-8, ... <= 1 that makes it positive definite.  A non-log-concave likelihood (the
+  // Student-t: a < 0 in its tails) can leave Sigma above I in a direction, where the predict kernels' one-term form
+  // k** - |C k*|^2 cannot hold var_f exactly; the install then serves k** - k*^T L^-T ((1 + delta) I - Sigma) L^-1 k*
+  // + delta k**, i.e. var_f + delta (k** - |L^-1 k*|^2), in [var_f, var_f + delta k**].
+  int vgp_shifted_root(double* delta_out) {
+    hipStream_t s = st();
+    double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sig = as<double>(K);
+    launch_dgemm(s, as<double>(vq_S), false, as<double>(vq_S), true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
+    int* host = reinterpret_cast<int*>(ctx->pinned_scratch(kVgpSmall));
+    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    for (double delta = 0.0; delta <= 1.0; delta = (delta == 0.0 ? 1.0e-8 : 2.0 * delta)) {
+      HIPCHECK(hipMemsetAsync(A, 0, (size_t)npad * npad * 8, s));
+      launch_vgp_axpby(s, Sig, A, npad * npad, 1.0 / (1.0 + delta), 0.0);
+      launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);
+      int rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0);
+      if (rc) return rc;
+      HIPCHECK(hipMemcpyAsync(host, vinfo(), 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+      HIPCHECK(ctx->wait(s));
+      if ((rc = launch_status())) return rc;
+      if (host[0] != INT_MAX || host[3] == INT_MAX) {  // (a Gram that failed is vgp_finish's to report)
+        *delta_out = delta;
+        return GPSO_OK;
+      }
+    }
+    return ctx->fail(GPSO_E_NOTPD, "I - S S^T: no shift delta <= 1 makes it positive definite (q far above the prior)");
   }
 
   // install the predictive at theta: L^-1 := C = R L^-1 (I - S S^T = R^T R), alpha := L^-T mu, noise := s2, mean := c --
@@ -1470,13 +1593,24 @@ struct EngineT : Engine {
     if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
     double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sq = as<double>(vq_S);
     launch_vgp_gemv(s, Li, true, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
-    launch_dgemm(s, Sq, false, Sq, true, A, npad, 1.0, 0.0);        // Sigma
-    launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);           // J (I - Sigma) J
-    if ((rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0))) return rc;     // G
-    launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R = J G^T J
-    launch_dgemm(s, B, false, Li, false, A, npad, 1.0, 0.0);        // C = R L^-1
-    HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, s2, mean_c))) return rc;
+    if (vlik_kind == GPSO_LIK_GAUSSIAN) {
+      launch_dgemm(s, Sq, false, Sq, true, A, npad, 1.0, 0.0);        // Sigma
+      launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);           // J (I - Sigma) J
+      if ((rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0))) return rc;     // G
+      launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R = J G^T J
+      launch_dgemm(s, B, false, Li, false, A, npad, 1.0, 0.0);        // C = R L^-1
+      HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+      if ((rc = set_theta(kernel, ls, n_ls_, variance, s2, mean_c))) return rc;
+    } else {
+      double shift = 0.0;
+      if ((rc = vgp_shifted_root(&shift))) return rc;                 // G of J (I - Sigma / (1 + delta)) J
+      launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R
+      launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R L^-1
+      HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+      // the likelihood's variance in the predictive: scale^2 df / (df - 2) (Student-t, closed form) or s2; + delta k**
+      const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
+      if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
+    }
     launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
     launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
     small_tile_rows = 8;
@@ -3227,9 +3361,15 @@ static int vgp_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, d
   if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
   for (int k = 0; k < n_ls; ++k) th[k] = gpso_softplus(u[k]);
   th[n_ls] = gpso_softplus(u[n_ls]);
-  th[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
+  // the likelihood's parameter: the Gaussian variance (1e-6 + softplus) or the Student-t scale (softplus, GPflow's positive())
+  th[n_ls + 1] = (ctx->eng->vlik_kind == GPSO_LIK_STUDENT_T ? 0.0 : 1.0e-6) + gpso_softplus(u[n_ls + 1]);
   th[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
   return GPSO_OK;
+}
+
+int gpso_vgp_set_likelihood(gpso_ctx* ctx, int kind, double df, int n_gh, const double* gh_x, const double* gh_w) {
+  ENTER();
+  return ctx->eng->vgp_set_likelihood(kind, df, n_gh, gh_x, gh_w);
 }
 
 int gpso_vgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t n) {

@@ -310,6 +310,16 @@ void launch_vgp_phi_sym(hipStream_t st, const double* p, double* m, int64_t n, i
 void launch_vgp_reverse(hipStream_t st, const double* src, double* out, int64_t n, int64_t npad, int mode, int* info);
 void launch_vgp_elbo_sums(hipStream_t st, const double* r, const double* fvar, const double* mu, const double* srow,
                           const double* S, int64_t n, int64_t npad, double* out);
+// general scalar likelihoods (kind: GPSO_LIK_STUDENT_T or GPSO_LIK_GAUSSIAN_GH; p: its parameter; gh: [0, 64) nodes,
+// [64, 128) weights, scaled as GPflow's): per point gm, a, t = gm + a (m - c), VE and dVE/dp
+void launch_vgp_quad(hipStream_t st, const double* y, const double* m, const double* v, const double* gh, int n_gh, int kind,
+                     double p, double nu, double cst, double c, double* gm, double* a, double* t, double* ve, double* dve,
+                     int64_t n, int64_t npad);
+void launch_vgp_lik_sums(hipStream_t st, const double* ve, const double* dve, const double* gm, const double* mu,
+                         const double* srow, const double* S, int64_t n, int64_t npad, double* out);
+void launch_vgp_lbar_w(hipStream_t st, double* lsig, const double* a, const double* gm, const double* mu, int64_t n,
+                       int64_t npad);
+void launch_vgp_rowscale(hipStream_t st, const double* A, const double* a, double* B, int64_t n, int64_t npad);
 // ---- append.hip: rank-k append at fixed hyper-parameters ----------------------------------------------------------------
 // The posterior of the first n points is resident; k <= kAppendMax new points (already copied behind the old ones in
 // x64 / y64) extend L, L^-1, a, alpha, diag(K_y^-1), the NLML and the scaled inputs in place: two passes over L^-1

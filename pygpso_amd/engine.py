@@ -262,6 +262,15 @@ class HipGPEngine:
         return self._lib.gpso_last_error(self._h).decode()
 
     # -- variational GP (include/gpso_hip.h: gpso_vgp_*) ---------------------------------------------------------------
+    def vgp_set_likelihood(self, kind="Gaussian", df=3.0, n_gh=20):
+        """The VGP's likelihood: "Gaussian" (closed form, the default), "StudentT" (``df`` > 2, slot n_ls + 1 of u: the
+        scale) or "GaussianGH" (the Gaussian through the quadrature sequence), with the ``n_gh``-point Gauss-Hermite rule
+        of ``numpy.polynomial.hermite.hermgauss`` (GPflow's)."""
+        kid = L.LIKELIHOOD_IDS[kind] if isinstance(kind, str) else int(kind)
+        x, w = np.polynomial.hermite.hermgauss(int(n_gh))
+        x, w = L.as_f64(x), L.as_f64(w)
+        self._check(self._lib.gpso_vgp_set_likelihood(self._h, kid, float(df), int(n_gh), L.dptr(x), L.dptr(w)))
+
     def vgp_set_q(self, mu=None, S=None):
         """q(v) = N(mu, S S^T) for the resident data; None, None: the prior (mu = 0, S = I)."""
         if mu is None and S is None:

@@ -28,7 +28,7 @@ import math
 import numpy as np
 from scipy.special import erfcinv
 
-from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, Zero
+from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero
 from .model import HipGPR
 from .vgp import HipVGP, carried_order
 from .utils import JSON_EXT, PointLabels
@@ -537,7 +537,14 @@ VGP_TRAIN_ITERATIONS = 10
 class VGPSurrogate(GPSurrogate):
     """Variational GP surrogate (gpso/gp_surrogate.py:536-699): per ``_gp_train`` iteration one natural-gradient step on
     the variational state q, then one step of the hyper-parameter optimiser (``Adam``, or ``Scipy``) on -ELBO at fixed q
-    -- all on the device (``HipVGP``).  Gaussian likelihood only.
+    -- all on the device (``HipVGP``).  Gaussian or Student-t likelihood: the Student-t (GPflow's ``StudentT``, heavy
+    tails) keeps gross outliers among the scores -- a diverged simulation, a bad seed -- from dragging the mean and the UCB
+    of their whole neighbourhood; its per-point terms come from GPflow's 20-point Gauss-Hermite quadrature.
+
+    The natural-gradient step of a non-Gaussian likelihood is formed at the current q and can be indefinite where a point
+    lies far out in the tails (|y - f| > sqrt(df) scale): with ``natgrad_learning_rate`` = 1 heavy outliers can make it
+    fail with ``numpy.linalg.LinAlgError``, leaving q as it was -- exactly as GPflow's NaturalGradient fails in its
+    Cholesky before assigning q.  gamma of about 0.1 is the usual choice for a non-conjugate likelihood.
 
     The model keeps its rows in their order of arrival between updates and grows q by the prior for new rows; when a held
     row disappears or its score changes, q restarts at the prior in the caller's order (``pygpso_amd.vgp``)."""
@@ -546,16 +553,16 @@ class VGPSurrogate(GPSurrogate):
                  gpflow_model=None, natgrad_learning_rate=1.0, train_iterations=VGP_TRAIN_ITERATIONS, dtype="float64",
                  device=0, engine_options=None):
         """
-        :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``); any other likelihood raises
-            NotImplementedError
+        :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``; any other
+            likelihood raises NotImplementedError
         :param optimiser: hyper-parameter optimiser, default ``Adam(0.01)`` (its moments persist across updates)
         :param natgrad_learning_rate: step length gamma in (0, 1] of the natural gradient
         :param train_iterations: natgrad / optimiser iterations per ``_gp_train``
         :param dtype: "float64" (default) or "mixed" (float64 training, float predict arithmetic); "float32" raises
         """
         likelihood = likelihood if likelihood is not None else Gaussian(1.0e-3)
-        if not isinstance(likelihood, Gaussian):
-            raise NotImplementedError(f"{type(likelihood).__name__}: only the Gaussian likelihood is supported")
+        if not isinstance(likelihood, (Gaussian, StudentT)):
+            raise NotImplementedError(f"{type(likelihood).__name__}: only the Gaussian and Student-t likelihoods are supported")
         gamma = float(natgrad_learning_rate)
         if not (0.0 < gamma <= 1.0):
             raise ValueError(f"natgrad_learning_rate {gamma} outside (0, 1]")
@@ -621,6 +628,8 @@ class VGPSurrogate(GPSurrogate):
             "dtype": self.dtype,  # (extra keys, not in the reference's schema)
             "vgp_row_order": None if order is None else order[: model.data[0].shape[0]].tolist(),
         }
+        if isinstance(self.likelihood, StudentT):  # (df is no GPflow Parameter: the reference's from_saved resets it to 3)
+            info["vgp_likelihood_df"] = model.likelihood.df
         with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
             fh.write(json.dumps(info))
 
@@ -635,12 +644,16 @@ class VGPSurrogate(GPSurrogate):
         with open(os.path.join(folder, cls.GPR_FILE)) as fh:
             params = json.load(fh)
         assert info["vgp_kernel"] in KERNEL_CLASSES
-        if info.get("vgp_likelihood", "Gaussian") != "Gaussian":
-            raise NotImplementedError(f"{info['vgp_likelihood']}: only the Gaussian likelihood is supported")
+        lik_name = info.get("vgp_likelihood", "Gaussian")
+        if lik_name not in ("Gaussian", "StudentT"):
+            raise NotImplementedError(f"{lik_name}: only the Gaussian and Student-t likelihoods are supported")
         kernel = KERNEL_CLASSES[info["vgp_kernel"]](
             lengthscales=np.array(params[".kernel.lengthscales"]), variance=params[".kernel.variance"])
         meanf = Constant(params[".mean_function.c"]) if info["vgp_meanf"] == "Constant" else Zero()
-        likelihood = Gaussian(params[".likelihood.variance"])
+        if lik_name == "StudentT":
+            likelihood = StudentT(params[".likelihood.scale"], info.get("vgp_likelihood_df", 3.0))
+        else:
+            likelihood = Gaussian(params[".likelihood.variance"])
         dtype = info.get("dtype", "float64")
         order = info.get("vgp_row_order")
         if order is not None:

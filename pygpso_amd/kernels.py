@@ -85,6 +85,24 @@ class Gaussian:
         return f"Gaussian(variance={self.variance})"
 
 
+class StudentT:
+    """Student-t likelihood spec (``gpflow.likelihoods.StudentT(scale=..., df=...)``): the initial scale (trained, through
+    GPflow's softplus ``positive()``) and the fixed degrees of freedom.  df <= 2 raises ValueError, where GPflow would
+    build a model whose ``predict_y`` variance scale^2 df / (df - 2) is negative or infinite."""
+
+    name = "StudentT"
+
+    def __init__(self, scale=1.0, df=3.0):
+        self.scale, self.df = float(scale), float(df)
+        if not self.df > 2.0:
+            raise ValueError(f"StudentT df={self.df}: need df > 2 (a finite predictive variance)")
+        if not self.scale > 0.0:
+            raise ValueError(f"StudentT scale={self.scale} must be positive")
+
+    def __repr__(self):
+        return f"StudentT(scale={self.scale}, df={self.df})"
+
+
 class Adam:
     """Keras's Adam (``tf.optimizers.Adam(learning_rate)``, the VGP surrogate's default optimiser,
     gpso/gp_surrogate.py:543): ``minimize(closure, variables)`` takes ONE step on the model's unconstrained vector,

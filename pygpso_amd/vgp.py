@@ -1,12 +1,14 @@
 """
 ``HipVGP``: the variational GP the ``VGPSurrogate`` keeps in ``.gpflow_model``.
 
-Stands where ``gpflow.models.VGP`` (Gaussian likelihood) stands in the reference (gpso/gp_surrogate.py:536-699):
+Stands where ``gpflow.models.VGP`` (Gaussian or Student-t likelihood) stands in the reference (gpso/gp_surrogate.py:536-699):
 whitened variational state q(v) = N(q_mu, q_sqrt q_sqrt^T) on the device beside the training data, the -ELBO and its
 gradient in the hyper-parameters (``training_loss`` / ``_loss_and_grad``, driven by ``Adam`` or ``Scipy``), one natural-
 gradient step on q (``natgrad``) and ``predict_y`` / ``best_ucb`` through the predict kernels of the GPR path: the
 predictive is installed as (C = R L^-1, beta = L^-T mu, sigma^2, c) with I - S S^T = R^T R (include/gpso_hip.h:
-gpso_vgp_posterior).  Hyper-parameters and their transforms are ``HipGPR``'s.
+gpso_vgp_posterior).  Hyper-parameters and their transforms are ``HipGPR``'s; under ``StudentT`` the likelihood's slot of
+the optimiser's vector holds softplus^-1(scale) (GPflow's ``positive()``) and df stays fixed, and the per-point terms of
+the ELBO and of the natural-gradient step come from GPflow's 20-point Gauss-Hermite quadrature on the device.
 
 Data that grows between updates.  GPflow's VGP keeps q sized to the data it was built with; here the model keeps its rows
 in their order of arrival: when every row it holds is still among the new data with its score, the new rows go behind
@@ -16,10 +18,14 @@ takes the caller's rows in the caller's order and q restarts at the prior.
 """
 from __future__ import annotations
 
+import types
+
 import numpy as np
 
-from .kernels import Gaussian
-from .model import HipGPR
+from .kernels import Gaussian, StudentT
+from .model import HipGPR, _as_result, _softplus, _softplus_inv
+
+GH_POINTS = 20  # gpflow.likelihoods.ScalarLikelihood's Gauss-Hermite points
 
 
 def _row_keys(x, y):
@@ -55,10 +61,15 @@ class HipVGP(HipGPR):
         if dtype not in ("float64", "mixed"):
             raise ValueError(f"VGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
         likelihood = likelihood if likelihood is not None else Gaussian()
-        if not isinstance(likelihood, Gaussian):
-            raise NotImplementedError("only the Gaussian likelihood is supported by the device VGP")
-        super().__init__(data, kernel, mean_function=mean_function, noise_variance=likelihood.variance, dtype=dtype,
-                         device=device, engine=engine, engine_options=engine_options, escalate=False)
+        if not isinstance(likelihood, (Gaussian, StudentT)):
+            raise NotImplementedError("the device VGP supports the Gaussian and the Student-t likelihoods")
+        self._student = isinstance(likelihood, StudentT)
+        super().__init__(data, kernel, mean_function=mean_function,
+                         noise_variance=1.0 if self._student else likelihood.variance, dtype=dtype, device=device,
+                         engine=engine, engine_options=engine_options, escalate=False)
+        if self._student:
+            self.likelihood = types.SimpleNamespace(scale=likelihood.scale, df=likelihood.df)
+            self.engine.vgp_set_likelihood("StudentT", likelihood.df, GH_POINTS)
         if q_mu is not None:
             self.set_q(q_mu, q_sqrt)
 
@@ -103,6 +114,46 @@ class HipVGP(HipGPR):
         y = np.concatenate([self._data[1], np.asarray(y_new, dtype=np.float64).reshape(-1, 1)])
         self.data = (x, y)
         return False
+
+    # -- hyper-parameters: the likelihood's slot ------------------------------------------------
+    def _pack(self):
+        if not self._student:
+            return super()._pack()
+        parts = [np.atleast_1d(_softplus_inv(self.kernel.lengthscales)), [float(_softplus_inv(self.kernel.variance))],
+                 [float(_softplus_inv(self.likelihood.scale))]]
+        if self._train_mean:
+            parts.append([self.mean_function.c])
+        return np.concatenate(parts).astype(np.float64)
+
+    def _unpack(self, u):
+        """(lengthscales, variance, likelihood parameter, c): the parameter is the Gaussian's variance or the Student-t's
+        scale."""
+        ls, var, p, c = super()._unpack(u)
+        if self._student:
+            p = float(_softplus(np.asarray(u, dtype=np.float64)[self.n_ls + 1]))
+        return ls, var, p, c
+
+    def _assign(self, u):
+        if not self._student:
+            return super()._assign(u)
+        ls, var, scale, c = self._unpack(u)
+        self.kernel.lengthscales = ls.copy() if self.kernel.ard else float(ls[0])
+        self.kernel.variance = var
+        self.likelihood.scale = scale
+        if self._train_mean:
+            self.mean_function.c = c
+        self._resident = False
+
+    def predictive_noise(self):
+        """The likelihood's variance in ``predict_y``: sigma^2, or scale^2 df / (df - 2) for the Student-t (the closed
+        form of GPflow's quadrature E[y^2] - E[y]^2)."""
+        if self._student:
+            return self.likelihood.scale ** 2 * self.likelihood.df / (self.likelihood.df - 2.0)
+        return self.likelihood.variance
+
+    def predict_f(self, Xnew):
+        mean, var = self.predict_y(Xnew)
+        return mean, _as_result(np.asarray(var) - self.predictive_noise())
 
     # -- training -------------------------------------------------------------------------------
     def _args(self):
@@ -150,7 +201,13 @@ class HipVGP(HipGPR):
     # -- reporting -----------------------------------------------------------------------------
     def parameter_dict(self):
         mu, S = self.get_q()
-        d = super().parameter_dict()
+        if self._student:
+            d = {".kernel.lengthscales": np.asarray(self.kernel.lengthscales, dtype=np.float64),
+                 ".kernel.variance": np.float64(self.kernel.variance),
+                 ".likelihood.scale": np.float64(self.likelihood.scale),
+                 ".mean_function.c": np.float64(self.mean_function.c)}
+        else:
+            d = super().parameter_dict()
         d[".q_mu"] = mu.reshape(-1, 1)
         d[".q_sqrt"] = S.reshape(1, S.shape[0], S.shape[1])
         return d
@@ -160,6 +217,7 @@ class HipVGP(HipGPR):
             ("VGP.mean_function.c", "", self.mean_function.c),
             ("VGP.kernel.variance", "Softplus", self.kernel.variance),
             ("VGP.kernel.lengthscales", "Softplus", self.kernel.lengthscales),
+            ("VGP.likelihood.scale", "Softplus", self.likelihood.scale) if self._student else
             ("VGP.likelihood.variance", "Softplus + Shift", self.likelihood.variance),
         ]
         lines = [f"{'name':<24} {'transform':<17} {'value'}"]

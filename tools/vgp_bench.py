@@ -8,7 +8,11 @@ Cost of the variational GP on one MI355X (float64):
     shape -- the same kernels serve both;
   * a torch.linalg yardstick of the same iteration (natgrad + -ELBO with autograd) on the same GPU.
 
-Usage: python tools/vgp_bench.py [--sizes 50,500,2048,8192] [--out profiles/vgp_bench.json]
+Usage: python tools/vgp_bench.py [--sizes 50,500,2048,8192] [--likelihood {gaussian,studentt}] [--out FILE]
+
+--likelihood studentt times the same training with ``StudentT(scale=1, df=3)`` and natgrad gamma 0.1 (the quadrature
+sequence: one more GEMM and two small passes per natgrad step), beside the Gaussian's numbers of the same run; the torch
+yardstick (Gaussian only) is skipped there.
 
 Device time per stage: run ONE training call (10 iterations + the predictive install) under the kernel tracer and fold
 its kernels by stage --
@@ -32,16 +36,23 @@ from pygpso_amd.gp_surrogate import VGPSurrogate  # noqa: E402
 from tests.helpers import synthetic_leaves, synthetic_problem  # noqa: E402
 
 
-def time_train(n, d, iters=10):
+def _surrogate(d, iters, likelihood="gaussian"):
+    if likelihood == "studentt":
+        return VGPSurrogate(gp_kernel=K.Matern52(lengthscales=0.25 * np.sqrt(d)), gp_meanf=K.Constant(),
+                            likelihood=K.StudentT(scale=1.0, df=3.0), natgrad_learning_rate=0.1, train_iterations=iters)
+    return VGPSurrogate(gp_kernel=K.Matern52(lengthscales=0.25 * np.sqrt(d)), gp_meanf=K.Constant(), train_iterations=iters)
+
+
+def time_train(n, d, iters=10, likelihood="gaussian"):
     X, y = synthetic_problem(n, d, seed=0)
-    s = VGPSurrogate(gp_kernel=K.Matern52(lengthscales=0.25 * np.sqrt(d)), gp_meanf=K.Constant(), train_iterations=iters)
+    s = _surrogate(d, iters, likelihood)
     s._gp_train(X, y[:, None])  # warm-up: allocations, code objects
     t0 = time.perf_counter()
     s._gp_train(X, y[:, None])
     t1 = time.perf_counter()
     s.gpflow_model.predict_y(X[:1])  # installs the predictive
     t2 = time.perf_counter()
-    return {"n": n, "d": d, "iterations": iters, "train_ms": (t1 - t0) * 1e3, "per_iteration_ms": (t1 - t0) * 1e3 / iters,
+    return {**({"likelihood": likelihood} if likelihood != "gaussian" else {}), "n": n, "d": d, "iterations": iters, "train_ms": (t1 - t0) * 1e3, "per_iteration_ms": (t1 - t0) * 1e3 / iters,
             "install_and_first_predict_ms": (t2 - t1) * 1e3}
 
 
@@ -133,6 +144,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="50,500,2048,8192")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--likelihood", choices=("gaussian", "studentt"), default="gaussian")
     ap.add_argument("--one-train", type=int, default=None, help="run ONE _gp_train of 10 iterations at this N (D = 12)")
     ap.add_argument("--stages", default=None, help="rocprofv3 database of a --one-train run: print device ms per stage")
     a = ap.parse_args()
@@ -141,7 +153,7 @@ def main():
         return
     if a.one_train:
         X, y = synthetic_problem(a.one_train, 12, seed=0)
-        s = VGPSurrogate(gp_kernel=K.Matern52(lengthscales=0.25 * np.sqrt(12)), gp_meanf=K.Constant(), train_iterations=10)
+        s = _surrogate(12, 10, a.likelihood)
         s._gp_train(X, y[:, None])
         s.gpflow_model.predict_y(X[:1])
         return
@@ -151,6 +163,18 @@ def main():
         torch.zeros(1, device="cuda:0")
     except Exception:
         pass
+    if a.likelihood == "studentt":
+        res = {"train": [], "train_gaussian": [], "ratio_to_gaussian": []}
+        for n in [int(v) for v in a.sizes.split(",")]:
+            res["train"].append(time_train(n, 12, likelihood="studentt"))
+            res["train_gaussian"].append(time_train(n, 12))
+            res["ratio_to_gaussian"].append({"n": n, "train_ms": res["train"][-1]["train_ms"] / res["train_gaussian"][-1]["train_ms"]})
+            for key in ("train", "train_gaussian", "ratio_to_gaussian"):
+                print(json.dumps(res[key][-1]), flush=True)
+        if a.out:
+            with open(a.out, "w") as fh:
+                fh.write(json.dumps(res, indent=1) + "\n")
+        return
     res = {"train": [], "leaf_ucb": [], "torch_yardstick": []}
     for n in [int(v) for v in a.sizes.split(",")]:
         res["train"].append(time_train(n, 12))
