@@ -277,6 +277,56 @@ int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
  * GPSO_MAT_LINV returns C and GPSO_VEC_ALPHA returns L^-T mu; GPSO_MAT_CHOL and GPSO_VEC_WHITE return GPSO_E_STATE. */
 int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed);
 
+/* ---- sparse GP regression on inducing points (no counterpart in the reference: gpflow.models.SGPR, Titsias 2009) -------
+ * GPflow 2's SGPR, Gaussian likelihood, with M fixed inducing points Z summarising the N resident training rows:
+ * Kuu = k(Z, Z) + 1e-6 I, Lu = chol Kuu, A = Lu^-1 k(Z, X) / sigma, B = I + A A^T, LB = chol B, cv = LB^-1 A (y - c) / sigma;
+ * training costs O(N M^2), a prediction O(M^2) whatever N.  u, n_ls, train_mean, mean_c_fixed: as
+ * gpso_fit_eval_u (s2 = 1e-6 + softplus(u[n_ls + 1])).  float64 throughout: GPSO_F64 and GPSO_MIXED contexts (GPSO_F32:
+ * GPSO_E_ARG).  Sequence: gpso_set_data (X, y), then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing, then any number
+ * of gpso_sgpr_bound_u, then gpso_sgpr_posterior; a call out of that order returns GPSO_E_STATE.
+ * WHAT THE CONTEXT DESCRIBES AFTERWARDS: setting the inducing points moves the training data into SGPR buffers of its own and
+ * makes Z the context's resident rows.  From then on gpso_problem_shape reports (M, D), gpso_padded_n the padding of M, and
+ * after gpso_sgpr_posterior the getters return the installed form over the rows Z: GPSO_MAT_LINV the M x M matrix C,
+ * GPSO_VEC_ALPHA beta (M values); GPSO_MAT_CHOL / GPSO_VEC_WHITE return GPSO_E_STATE and gpso_append returns GPSO_E_STATE
+ * (set the grown data and train again).  The next gpso_set_data replaces the data and drops Z; a gpso_fit_eval or
+ * gpso_set_posterior on the context ends the SGPR sequence too (the resident rows are then no inducing points). */
+
+/* Z[m * D] row-major, used as given (1 <= m <= 65536; m > N is allowed).  May be called again to replace Z for the same
+ * data.  A call rejected for its arguments or its place in the sequence (GPSO_E_ARG / GPSO_E_STATE) leaves the context as it
+ * was; a HIP or allocation failure inside it leaves the context without data (gpso_set_data again). */
+int gpso_sgpr_set_inducing(gpso_ctx* ctx, const double* Z, int64_t m);
+/* Greedy conditional-variance selection of m <= N training rows ON THE DEVICE (pivoted partial Cholesky of k(X, X) at the
+ * kernel hyper-parameters of u; only u[0 .. n_ls] are read): d_i = variance; m times: p = arg-max d over the unpicked rows,
+ * the lowest index on exact ties; l = (k(X, x_p) - L L[p]^T) / sqrt(d_p); d -= l^2.  O(N m^2).  The picked rows become Z;
+ * idx_out (nullable) [m] receives their indices in pick order.  Arguments are checked first (a rejected call leaves the
+ * context as it was); after that the call replaces whatever posterior was resident.  When the largest remaining d falls to
+ * 1e-12 variance or below before m rows are picked -- k(X, X) numerically of rank < m: duplicated rows, very long
+ * lengthscales, m close to N -- the call returns GPSO_E_NOTPD with the rank reached in gpso_last_error and sets no Z. */
+int gpso_sgpr_select_inducing(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int64_t m, int64_t* idx_out);
+/* Z (nullable) [M * D], *m (nullable) = M, *n_data (nullable) = N of the training data held beside it. */
+int gpso_sgpr_get_inducing(gpso_ctx* ctx, double* Z, int64_t* m, int64_t* n_data);
+/* The intermediates of the last successful gpso_sgpr_bound_u, for checks against a reference (tests): out receives
+ * GPSO_SGPR_KUF: k(Z, X) [M * N] row-major; GPSO_SGPR_LU: Lu [M * M]; GPSO_SGPR_LB: LB [M * M] (lower, zero above);
+ * GPSO_SGPR_CV: cv [M].  GPSO_E_STATE once any call other than a getter has followed that evaluation. */
+#define GPSO_SGPR_KUF 0
+#define GPSO_SGPR_LU 1
+#define GPSO_SGPR_LB 2
+#define GPSO_SGPR_CV 3
+int gpso_sgpr_get_factor(gpso_ctx* ctx, int which, double* out);
+/* ONE evaluation of SGPR.training_loss (-bound of Titsias) and its gradient in the trainable variables, Z fixed.  *loss;
+ * grad_u (nullable) [n_ls + 2 + (train_mean != 0)]; theta_out (nullable) [n_ls + 3] = (lengthscales..., variance, s2, mean).
+ * GPSO_E_NOTPD names the matrix (Kuu or B) and the pivot.  Replaces whatever posterior was resident. */
+int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      double* loss, double* grad_u, double* theta_out);
+/* SGPR.predict_y at theta, installed as the resident posterior over the rows Z: mean = k*u^T beta + c with
+ * beta = Lu^-T LB^-T cv, var = k** - |C k*u|^2 + s2 with C = R Lu^-1, I - B^-1 = R^T R -- the form every predict path
+ * evaluates, so gpso_predict, gpso_best_ucb (+ _begin / _end, _grow), the sharded and hand-off calls serve it unchanged.
+ * Where I - B^-1 does not factor (N < M, duplicated rows of Z) the install serves var + delta (k** - |Lu^-1 k*u|^2) with
+ * delta the first of 0, 1e-8, 2e-8, ... for which I - B^-1 / (1 + delta) factors: never below the exact variance, at most
+ * delta k** above it, exact when delta = 0 (DESIGN.md sections 7a.1, 7b).  *delta_out (nullable) = delta. */
+int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* delta_out);
+
 /* ---- predict (gpflow_model.predict_y users) ----------------------------------------------- */
 
 /* Replaces: gpflow_model.predict_y(coords) at gpso/gp_surrogate.py:298 (gp_predict) and

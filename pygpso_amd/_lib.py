@@ -24,6 +24,7 @@ MEM_HOST, MEM_DEVICE = 0, 1
 UNIQUE_ID_BYTES = 128
 MAT_CHOL, MAT_LINV, MAT_KINV, MAT_GRAM = 0, 1, 2, 3
 VEC_ALPHA, VEC_WHITE = 0, 1
+SGPR_KUF, SGPR_LU, SGPR_LB, SGPR_CV = 0, 1, 2, 3
 LIK_GAUSSIAN, LIK_STUDENT_T, LIK_GAUSSIAN_GH = 0, 1, 2
 LIKELIHOOD_IDS = {"Gaussian": LIK_GAUSSIAN, "StudentT": LIK_STUDENT_T, "GaussianGH": LIK_GAUSSIAN_GH}
 OPT_PREDICT_MATH = 1
@@ -90,6 +91,13 @@ SIGNATURES = {
     "gpso_vgp_elbo_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
                                   _c_double_p, _c_double_p]),
     "gpso_vgp_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double]),
+    "gpso_sgpr_set_inducing": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
+    "gpso_sgpr_select_inducing": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int64, _c_int64_p]),
+    "gpso_sgpr_get_inducing": (C.c_int, [C.c_void_p, _c_double_p, _c_int64_p, _c_int64_p]),
+    "gpso_sgpr_get_factor": (C.c_int, [C.c_void_p, C.c_int, _c_double_p]),
+    "gpso_sgpr_bound_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                    _c_double_p, _c_double_p]),
+    "gpso_sgpr_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p]),
     "gpso_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int]),
     "gpso_best_ucb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p,

@@ -127,6 +127,15 @@ struct Engine {
                        double* grad) = 0;
   virtual int vgp_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c) = 0;
   virtual int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) = 0;
+  // sparse GP regression on inducing points (sgpr.hip)
+  virtual int sgpr_set_inducing(const double* Z, int64_t m) = 0;
+  virtual int sgpr_select_inducing(int kernel, const double* ls, int n_ls, double variance, int64_t m, int64_t* idx_out) = 0;
+  virtual int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) = 0;
+  virtual int sgpr_get_factor(int which, double* out) = 0;
+  virtual int sgpr_bound(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double* loss,
+                         double* grad) = 0;
+  virtual int sgpr_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c,
+                             double* delta_out) = 0;
   int vlik_kind = GPSO_LIK_GAUSSIAN;  // the VGP's likelihood (GPSO_LIK_*): what slot n_ls + 1 of u means
 };
 
@@ -903,7 +912,9 @@ struct EngineT : Engine {
     if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
     have_data = true;
     have_post = have_kinv = chol_valid = linv_p_valid = false;
-    vgp_post = false;
+    vgp_post = sgpr_post = false;
+    if (!sg_keep) sg_have = sg_have_z = false;  // (the caller's own gpso_set_data: new data, no inducing points)
+    sg_factors = false;
     st_done = st_have = false;
     forget_peers();
     return GPSO_OK;
@@ -921,7 +932,8 @@ struct EngineT : Engine {
     const bool small = fused_small && small_fit_eligible(n, dp);
     if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c, !small))) return rc;
     have_post = have_kinv = chol_valid = false;
-    vgp_post = false;
+    vgp_post = sgpr_post = false;
+    sg_have_z = sg_factors = false;  // (a GPR fit on the resident rows: they are no inducing points any more)
     st_done = st_have = false;
     forget_peers();
     reset_generation();
@@ -1087,6 +1099,7 @@ struct EngineT : Engine {
     ctx->tick_timing();
     if (!Xn || !yn) return ctx->fail(GPSO_E_ARG, "Xnew / ynew must not be NULL");
     if (k < 1) return ctx->fail(GPSO_E_ARG, "need at least one new point (k=%lld)", (long long)k);
+    if (sgpr_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SGPR predictive: its rows are the inducing points; set the grown data and train again");
     if (vgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
     if (int rca = refuse_if_async("gpso_append")) return rca;
     if (!have_data || !have_post || !chol_valid || (int64_t)y_host.size() != n)
@@ -1208,7 +1221,8 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(tmp, L, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp + (size_t)n * n, alpha64, (size_t)n * 8, hipMemcpyHostToDevice, s));
     have_data = false;  // y unknown: a later fit needs gpso_set_data
-    vgp_post = false;
+    vgp_post = sgpr_post = false;
+    sg_have = sg_have_z = sg_factors = false;
     have_post = have_kinv = chol_valid = false;
     st_done = st_have = false;
     forget_peers();
@@ -1311,7 +1325,7 @@ struct EngineT : Engine {
     if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
     if (vlik_kind != GPSO_LIK_GAUSSIAN && (rc = ensure(vlvec, (size_t)kLikVecs * npad * 8))) return rc;
     if (vq_n != n || vq_npad != npad) vgp_prior();
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = false;
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = false;
     linv_p_lazy = false;
     st_done = st_have = false;
     forget_peers();
@@ -1345,7 +1359,7 @@ struct EngineT : Engine {
     return vgp_chol(as<double>(K), as<double>(Lf), as<double>(linv), vinfo() + 0, 0.0);
   }
   // wait for the stream, then the verdicts of the factorisations (out: host copy of vsmall)
-  int vgp_finish(double** out) {
+  int vgp_finish(double** out, bool sgpr = false) {
     double* host = ctx->pinned_scratch(kVgpSmall);
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(host, vsmall.p, kVgpSmall * 8, hipMemcpyDeviceToHost, st()));
@@ -1356,9 +1370,10 @@ struct EngineT : Engine {
     std::memcpy(info, host + kVgpInfoAt, sizeof(info));
     static const char* what[4] = {"k(X, X) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
                                   "I - S S^T (reversed order)"};
+    static const char* what_sgpr[4] = {"Kuu = k(Z, Z) + 1e-6 I", "B = I + A A^T", "(unused)", "I - B^-1 (reversed order)"};
     for (int q = 0; q < 4; ++q)
       if (info[q] != INT_MAX)
-        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d", what[q], info[q]);
+        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d", (sgpr ? what_sgpr : what)[q], info[q]);
     *out = host;
     return GPSO_OK;
   }
@@ -1560,10 +1575,10 @@ struct EngineT : Engine {
   // Student-t: a < 0 in its tails) can leave Sigma above I in a direction, where the predict kernels' one-term form
   // k** - |C k*|^2 cannot hold var_f exactly; the install then serves k** - k*^T L^-T ((1 + delta) I - Sigma) L^-1 k*
   // + delta k**, i.e. var_f + delta (k** - |L^-1 k*|^2), in [var_f, var_f + delta k**].
-  int vgp_shifted_root(double* delta_out) {
+  int vgp_shifted_root(double* delta_out, bool sigma_ready = false /* K already holds Sigma (the SGPR install: B^-1) */) {
     hipStream_t s = st();
     double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sig = as<double>(K);
-    launch_dgemm(s, as<double>(vq_S), false, as<double>(vq_S), true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
+    if (!sigma_ready) launch_dgemm(s, as<double>(vq_S), false, as<double>(vq_S), true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
     int* host = reinterpret_cast<int*>(ctx->pinned_scratch(kVgpSmall));
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     for (double delta = 0.0; delta <= 1.0; delta = (delta == 0.0 ? 1.0e-8 : 2.0 * delta)) {
@@ -1575,12 +1590,13 @@ struct EngineT : Engine {
       HIPCHECK(hipMemcpyAsync(host, vinfo(), 4 * sizeof(int), hipMemcpyDeviceToHost, s));
       HIPCHECK(ctx->wait(s));
       if ((rc = launch_status())) return rc;
-      if (host[0] != INT_MAX || host[3] == INT_MAX) {  // (a Gram that failed is vgp_finish's to report)
+      if (host[0] != INT_MAX || (sigma_ready && host[1] != INT_MAX) || host[3] == INT_MAX) {  // (a Gram -- or the SGPR's B -- that failed is vgp_finish's to report)
         *delta_out = delta;
         return GPSO_OK;
       }
     }
-    return ctx->fail(GPSO_E_NOTPD, "I - S S^T: no shift delta <= 1 makes it positive definite (q far above the prior)");
+    return ctx->fail(GPSO_E_NOTPD, sigma_ready ? "I - B^-1: no shift delta <= 1 makes it positive definite"
+                                               : "I - S S^T: no shift delta <= 1 makes it positive definite (q far above the prior)");
   }
 
   // install the predictive at theta: L^-1 := C = R L^-1 (I - S S^T = R^T R), alpha := L^-T mu, noise := s2, mean := c --
@@ -1622,6 +1638,274 @@ struct EngineT : Engine {
       return rc;
     }
     have_post = linv_p_valid = vgp_post = true;
+    sgpr_post = false;
+    return GPSO_OK;
+  }
+
+
+  // ---- sparse GP regression on inducing points (GPflow 2 SGPR, Gaussian likelihood, Z fixed) --------
+  // gpso_sgpr_set_inducing / gpso_sgpr_select_inducing move the training data (N rows) into buffers of their own (sgX raw,
+  // sgY) and make Z the context's resident rows (n = M): Kuu, its factor and everything M x M then run through the fit's
+  // buffers and kernels at size M_pad exactly as the VGP's do at N_pad, the installed predictive is a posterior over the M
+  // rows Z that every predict path serves, and the rectangular [M_pad x N_pad] work lives in sgKuf / sgA / sgW.
+  DevBuf sgX, sgY, sgXs, sgXn, sgKuf, sgA, sgW, sgPart, sgM1, sgM2, sgM3, sgvecN, sgvecM, sgsmall, sggpart, sgidx;
+  std::vector<double> sg_xh;  // host mirror of the training inputs (the rows greedy selection gathers Z from)
+  int64_t sg_n = 0, sg_npad = 0;
+  bool sg_have = false, sg_have_z = false, sg_keep = false;
+  bool sg_factors = false;  // Kuf, Lu, LB, cv of the last gpso_sgpr_bound_u are still in their buffers (gpso_sgpr_get_factor)
+  bool sgpr_post = false;  // the resident posterior is an SGPR predictive over the rows Z
+  enum { kSgE = 0, kSgW = 1, kSgT = 2, kSgVecsN = 3 };
+  enum { kSgAe = 0, kSgCv = 1, kSgMu = 2, kSgAvec = 3, kSgRows = 4, kSgZero = 5, kSgVecsM = 6 };
+  static constexpr int kSgGradAt = 16, kSgSmall = kSgGradAt + kGradMaxLs + 1;
+  double* sgn_at(int k) const { return as<double>(sgvecN) + (size_t)k * sg_npad; }
+  double* sgm_at(int k) const { return as<double>(sgvecM) + (size_t)k * npad; }
+
+  int sgpr_need_f64() {
+    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "SGPR needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
+    return GPSO_OK;
+  }
+  // the resident rows are the caller's data: keep them as the SGPR's training set
+  int sgpr_stash() {
+    if (sg_have) return GPSO_OK;
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "SGPR call before gpso_set_data");
+    int rc;
+    sg_n = n;
+    sg_npad = npad;  // (a multiple of 128: the tile GEMM's k and n extents)
+    if ((rc = ensure(sgX, (size_t)sg_npad * d * 8))) return rc;
+    if ((rc = ensure(sgY, (size_t)sg_npad * 8))) return rc;
+    HIPCHECK(hipMemcpyAsync(sgX.p, x64.p, (size_t)sg_n * d * 8, hipMemcpyDeviceToDevice, st()));
+    HIPCHECK(hipMemcpyAsync(sgY.p, y64.p, (size_t)sg_n * 8, hipMemcpyDeviceToDevice, st()));
+    HIPCHECK(hipStreamSynchronize(st()));
+    sg_xh = x_host;
+    sg_have = true;
+    sg_have_z = false;
+    return GPSO_OK;
+  }
+
+  int sgpr_set_inducing(const double* Z, int64_t m) override {
+    int rc = sgpr_need_f64();
+    if (rc) return rc;
+    if (!Z) return ctx->fail(GPSO_E_ARG, "Z must not be NULL");
+    if (m < 1 || m > 65536) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, 65536]", (long long)m);
+    if (!sg_have && !have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_set_inducing before gpso_set_data");
+    if ((rc = refuse_if_async("gpso_sgpr_set_inducing"))) return rc;
+    for (int64_t e = 0; e < m * (int64_t)d; ++e)
+      if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
+    if ((rc = sgpr_stash())) return rc;
+    std::vector<double> zeros((size_t)m, 0.0), zc(Z, Z + (size_t)m * d);  // (Z may alias the mirror set_data overwrites)
+    sg_keep = true;
+    rc = set_data(zc.data(), zeros.data(), m, d);
+    sg_keep = false;
+    if (rc) {  // (a HIP / allocation failure: the arguments were checked above.  The resident rows are unknown now)
+      sg_have = sg_have_z = have_data = false;
+      return rc;
+    }
+    sg_have_z = true;
+    return GPSO_OK;
+  }
+
+  int sgpr_select_inducing(int kernel, const double* ls, int n_ls_, double variance, int64_t m, int64_t* idx_out) override {
+    int rc = sgpr_need_f64();
+    if (rc) return rc;
+    if (!sg_have && !have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_select_inducing before gpso_set_data");
+    if ((rc = refuse_if_async("gpso_sgpr_select_inducing"))) return rc;
+    const int64_t N = sg_have ? sg_n : n;
+    if (m < 1 || m > N) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, N=%lld]", (long long)m, (long long)N);
+    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
+    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    for (int k = 0; k < n_ls_; ++k)
+      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
+    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    // (from here on the call replaces whatever posterior was resident: the hyper block is the selection's)
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = false;
+    sg_factors = false;
+    if ((rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, 0.0))) return rc;
+    if ((rc = sgpr_stash())) return rc;
+    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
+    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
+    if ((rc = ensure(sgW, (size_t)m * sg_npad * 8))) return rc;
+    if ((rc = ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
+    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
+    if ((rc = ensure(sgidx, (size_t)m * 8))) return rc;
+    hipStream_t s = st();
+    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
+    launch_sgpr_greedy(s, as<double>(sgXs), sg_n, sg_npad, dp, kp, (int)m, as<double>(sgW), sgn_at(0), as<double>(sgsmall),
+                       as<int64_t>(sgidx));
+    std::vector<int64_t> idx((size_t)m);
+    HIPCHECK(hipMemcpyAsync(idx.data(), sgidx.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if ((rc = launch_status())) return rc;
+    std::vector<double> Z((size_t)m * d);
+    for (int64_t j = 0; j < m; ++j) {
+      if (idx[j] == -1)
+        return ctx->fail(GPSO_E_NOTPD, "greedy selection: k(X, X) is numerically of rank %lld < m=%lld at these hyper-parameters "
+                         "(the largest remaining conditional variance is below 1e-12 of the kernel variance): ask for fewer inducing points",
+                         (long long)j, (long long)m);
+      if (idx[j] < 0 || idx[j] >= sg_n) return ctx->fail(GPSO_E_HIP, "greedy selection returned row %lld of %lld", (long long)idx[j], (long long)sg_n);
+      std::memcpy(&Z[(size_t)j * d], &sg_xh[(size_t)idx[j] * d], (size_t)d * 8);
+    }
+    if (idx_out) std::memcpy(idx_out, idx.data(), (size_t)m * 8);
+    return sgpr_set_inducing(Z.data(), m);
+  }
+
+  int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) override {
+    if (!sg_have || !sg_have_z) return ctx->fail(GPSO_E_STATE, "no inducing points set (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing)");
+    if (m_out) *m_out = n;
+    if (n_data_out) *n_data_out = sg_n;
+    if (Z) std::memcpy(Z, x_host.data(), (size_t)n * d * 8);
+    return GPSO_OK;
+  }
+
+  // the intermediates of the last successful gpso_sgpr_bound_u, for checks against a reference
+  int sgpr_get_factor(int which, double* out) override {
+    if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
+    if (which < GPSO_SGPR_KUF || which > GPSO_SGPR_CV) return ctx->fail(GPSO_E_ARG, "unknown SGPR factor id %d", which);
+    if (!sg_have || !sg_have_z || !sg_factors)
+      return ctx->fail(GPSO_E_STATE, "gpso_sgpr_get_factor: no gpso_sgpr_bound_u result resident (any later call but a getter drops it)");
+    int rc = refuse_if_async("gpso_sgpr_get_factor");
+    if (rc) return rc;
+    const double* src = which == GPSO_SGPR_KUF ? as<double>(sgKuf) : which == GPSO_SGPR_LU ? as<double>(Lf)
+                        : which == GPSO_SGPR_LB ? as<double>(vC) : sgm_at(kSgCv);
+    const int64_t rows = n, cols = which == GPSO_SGPR_KUF ? sg_n : which == GPSO_SGPR_CV ? 1 : n;
+    const int64_t ld = which == GPSO_SGPR_KUF ? sg_npad : which == GPSO_SGPR_CV ? 1 : npad;
+    HIPCHECK(hipMemcpy2DAsync(out, (size_t)cols * 8, src, (size_t)ld * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost, st()));
+    HIPCHECK(hipStreamSynchronize(st()));
+    return GPSO_OK;
+  }
+
+  // Lu (Lf), Lu^-1 (linv), Kuf, A, A A^T (vA), LB (vC), LB^-1 (sgM2), e, A e, cv at theta; the verdicts in vinfo() 0 and 1
+  int sgpr_factor(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, const char* who) {
+    int rc = sgpr_need_f64();
+    if (rc) return rc;
+    if (!sg_have || !sg_have_z)
+      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
+    if (!(s2 > 0.0)) return ctx->fail(GPSO_E_ARG, "noise variance %g must be positive", s2);
+    // (the arguments set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
+    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
+    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    for (int k = 0; k < n_ls_; ++k)
+      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
+    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    if ((rc = vgp_begin())) return rc;
+    sgpr_post = sg_factors = false;
+    const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
+    int nsplit = 1;
+    while (nsplit < 16 && sg_npad % (256 * nsplit) == 0 && sg_npad / (2 * nsplit) >= 512) nsplit *= 2;
+    for (DevBuf* b : {&sgKuf, &sgA, &sgW})
+      if ((rc = ensure(*b, rect))) return rc;
+    for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
+      if ((rc = ensure(*b, sq))) return rc;
+    if ((rc = ensure(sgPart, sq * nsplit))) return rc;
+    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
+    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
+    if ((rc = ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
+    if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
+    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
+    if ((rc = ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8))) return rc;
+    hipStream_t s = st();
+    vgp_reset_info();
+    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
+    const double sig = std::sqrt(s2);
+    double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *A = as<double>(sgA);
+    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
+    launch_sgpr_cross_gram(s, as<double>(xs64), as<double>(sgXs), n, npad, sg_n, sg_npad, dp, kp, Kuf);
+    launch_dgemm_rect(s, Li, npad, 1, Kuf, sg_npad, 1, A, sg_npad, npad, sg_npad, npad, 1.0 / sig, 0.0);  // A = Lu^-1 Kuf / sigma
+    // A A^T: the long-K product, split along N into nsplit partial products summed in a fixed order
+    launch_dgemm_rect(s, A, sg_npad, 1, A, 1, sg_npad, as<double>(sgPart), npad, npad, npad, sg_npad, 1.0, 0.0, nsplit);
+    launch_sgpr_splitk_sum(s, as<double>(sgPart), nsplit, n, npad, as<double>(vA), as<double>(vB), vinfo() + 1);
+    if ((rc = vgp_chol(as<double>(vB), as<double>(vC), as<double>(sgM2), vinfo() + 1, 0.0))) return rc;  // LB, LB^-1
+    launch_sgpr_resid(s, as<double>(sgY), mean_c, sgn_at(kSgE), sg_n, sg_npad);
+    launch_sgpr_gemv(s, A, false, sgn_at(kSgE), 1.0, sgm_at(kSgAe), n, npad, sg_n, sg_npad);
+    launch_vgp_gemv(s, as<double>(sgM2), false, sgm_at(kSgAe), 0.0, 1.0 / sig, 0.0, nullptr, sgm_at(kSgCv), n, npad);
+    return GPSO_OK;
+  }
+
+  int sgpr_bound(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss,
+                 double* grad) override {
+    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, "gpso_sgpr_bound_u");
+    if (rc) return rc;
+    hipStream_t s = st();
+    const double b = 1.0 / s2;
+    double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *AAT = as<double>(vA), *T1 = as<double>(vB), *LB = as<double>(vC);
+    double *LBi = as<double>(sgM2), *G1 = as<double>(K), *M1 = as<double>(sgM1), *M3 = as<double>(sgM3);
+    if (grad) {
+      launch_dgemm(s, LBi, false, Li, false, T1, npad, 1.0, 0.0);   // T1 = LB^-1 Lu^-1
+      launch_vgp_gemv(s, T1, true, sgm_at(kSgCv), 0.0, s2, 0.0, nullptr, sgm_at(kSgAvec), n, npad);  // a = Q^-1 Kuf e
+      launch_sgpr_gemv(s, Kuf, true, sgm_at(kSgAvec), 1.0, sgn_at(kSgW), n, npad, sg_n, sg_npad);    // w = Kfu a
+      launch_dgemm(s, T1, true, T1, false, G1, npad, 1.0, 0.0);     // Q^-1
+      launch_dgemm(s, Li, true, Li, false, M1, npad, 1.0, 0.0);     // Kuu^-1
+      launch_vgp_axpby(s, M1, G1, npad * npad, b, -b);              // G1 = b (Kuu^-1 - Q^-1)
+      launch_dgemm_rect(s, G1, npad, 1, Kuf, sg_npad, 1, as<double>(sgW), sg_npad, npad, sg_npad, npad, 1.0, 0.0);  // G1 Kuf
+      launch_sgpr_tvec(s, sgn_at(kSgE), sgn_at(kSgW), b * b, -b * b * b, sgn_at(kSgT), sg_n, sg_npad);
+      // dF/dKuf = G1 Kuf + a t^T, contracted with dKuf/dtheta tile by tile
+      launch_sgpr_cross_grad(s, as<double>(sgW), sgm_at(kSgAvec), sgn_at(kSgT), as<double>(xs64), as<double>(sgXs), n, npad,
+                             sg_n, sg_npad, dp, n_ls, ls_dev(), kp, as<double>(sggpart), as<double>(sgsmall) + kSgGradAt);
+      launch_dgemm(s, AAT, false, Li, false, M1, npad, 1.0, 0.0);   // A A^T Lu^-1
+      launch_dgemm(s, Li, true, M1, false, M3, npad, 1.0, 0.0);     // P = Lu^-T A A^T Lu^-1
+      launch_sgpr_wuu(s, G1, M3, sgm_at(kSgAvec), b, M1, n, npad);  // -2 dF/dKuu (M1 is free again)
+      HIPCHECK(hipMemsetAsync(sgm_at(kSgZero), 0, (size_t)npad * 8, s));
+      // the Kuu part: the NLML gradient's contraction with K^-1 := -2 dF/dKuu and alpha := 0
+      launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
+                              M1, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
+      launch_vgp_rownorm(s, LBi, sgm_at(kSgRows), n, npad);
+    }
+    launch_sgpr_sums(s, LB, AAT, sgm_at(kSgCv), sgn_at(kSgE), grad ? sgn_at(kSgW) : nullptr, grad ? sgm_at(kSgRows) : nullptr, n,
+                     npad, sg_n, as<double>(sgsmall));
+    double* host;
+    if ((rc = vgp_finish(&host, true))) return rc;
+    double guu[kGradMaxLs + 1];
+    for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
+    double* h = ctx->pinned_scratch(kSgSmall);
+    if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx->wait(s));
+    const double N = (double)sg_n, M = (double)n;
+    const double F = -0.5 * N * std::log(2.0 * M_PI) - h[0] - 0.5 * N * std::log(s2) - 0.5 * b * h[1] + 0.5 * h[2] -
+                     0.5 * N * variance * b + 0.5 * h[3];
+    *loss = -F;
+    sg_factors = true;
+    if (grad) {
+      // d(-F)/dtheta: the Kuu contraction already is of -F; the cross one is of F; Kdiag: dF/dvariance = -N b / 2
+      for (int k = 0; k <= n_ls; ++k) grad[k] = guu[k] - h[kSgGradAt + k];
+      grad[n_ls] += 0.5 * N * b;
+      const double dF_db = 0.5 * N * s2 - 0.5 * s2 * (M - h[8]) - 0.5 * h[1] + b * h[4] - 0.5 * b * b * h[5] -
+                           0.5 * N * variance + 0.5 * s2 * h[3];
+      grad[n_ls + 1] = b * b * dF_db;
+      grad[n_ls + 2] = -(b * h[6] - b * b * h[7]);
+    }
+    return GPSO_OK;
+  }
+
+  // install the predictive over the rows Z: L^-1 := C = sqrt(1 + delta) R Lu^-1 (I - B^-1 / (1 + delta) = R^T R, delta the
+  // smallest of 0, 1e-8, 2e-8, ... that factors), alpha := Lu^-T LB^-T cv, noise := s2 + delta variance, mean := c
+  int sgpr_posterior(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c,
+                     double* delta_out) override {
+    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, "gpso_sgpr_posterior");
+    if (rc) return rc;
+    hipStream_t s = st();
+    double *Li = as<double>(linv), *LBi = as<double>(sgM2);
+    launch_vgp_gemv(s, LBi, true, sgm_at(kSgCv), 0.0, 1.0, 0.0, nullptr, sgm_at(kSgMu), n, npad);        // mu = LB^-T cv
+    launch_vgp_gemv(s, Li, true, sgm_at(kSgMu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);   // beta = Lu^-T mu
+    launch_dgemm(s, LBi, true, LBi, false, as<double>(K), npad, 1.0, 0.0);                               // B^-1
+    sg_factors = false;  // (vC is about to hold G)
+    double shift = 0.0;
+    if ((rc = vgp_shifted_root(&shift, true))) return rc;                                                // G in vC
+    launch_vgp_reverse(s, as<double>(vC), as<double>(vB), n, npad, 1, nullptr);                          // R
+    launch_dgemm(s, as<double>(vB), false, Li, false, as<double>(vA), npad, std::sqrt(1.0 + shift), 0.0);
+    HIPCHECK(hipMemcpyAsync(Li, vA.p, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+    if ((rc = set_theta(kernel, ls, n_ls_, variance, s2 + shift * variance, mean_c))) return rc;
+    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
+    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
+    small_tile_rows = 8;
+    chol_valid = true;  // (the split pieces are packed from linv)
+    if ((rc = pack_bf16())) return rc;
+    double* host;
+    if ((rc = vgp_finish(&host, true))) {
+      chol_valid = false;
+      return rc;
+    }
+    if (delta_out) *delta_out = shift;
+    have_post = linv_p_valid = vgp_post = sgpr_post = true;
     return GPSO_OK;
   }
 
@@ -3419,6 +3703,64 @@ int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
   return ctx->eng->vgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2]);
+}
+
+// ---- sparse GP regression on inducing points ---------------------------------------------------------------------
+static int sgpr_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, double mean_c_fixed, double* th) {
+  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
+  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
+  for (int k = 0; k <= n_ls; ++k) th[k] = gpso_softplus(u[k]);
+  th[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
+  th[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
+  return GPSO_OK;
+}
+
+int gpso_sgpr_set_inducing(gpso_ctx* ctx, const double* Z, int64_t m) {
+  ENTER();
+  return ctx->eng->sgpr_set_inducing(Z, m);
+}
+
+int gpso_sgpr_select_inducing(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int64_t m, int64_t* idx_out) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = sgpr_theta(ctx, u, n_ls, 0, 0.0, th);
+  if (rc) return rc;
+  return ctx->eng->sgpr_select_inducing(kernel, th, n_ls, th[n_ls], m, idx_out);
+}
+
+int gpso_sgpr_get_inducing(gpso_ctx* ctx, double* Z, int64_t* m, int64_t* n_data) {
+  ENTER();
+  return ctx->eng->sgpr_get_inducing(Z, m, n_data);
+}
+
+int gpso_sgpr_get_factor(gpso_ctx* ctx, int which, double* out) {
+  ENTER();
+  return ctx->eng->sgpr_get_factor(which, out);
+}
+
+int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      double* loss, double* grad_u, double* theta_out) {
+  ENTER();
+  if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
+  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
+  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  if (theta_out)
+    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
+  rc = ctx->eng->sgpr_bound(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* delta_out) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->sgpr_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
 }
 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,

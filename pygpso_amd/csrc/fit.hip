@@ -1025,6 +1025,35 @@ void launch_dgemm(hipStream_t st, const double* A, bool trans_a, const double* B
   launch_gemm<double>(st, g);
 }
 
+// the rectangular sibling (the products of the SGPR path: api.hip EngineT::sgpr_*): any m x n x k with strided operands,
+// optionally split along k into nsplit batch entries that land in consecutive m x ldc slabs of C
+void launch_dgemm_rect(hipStream_t st, const double* A, int64_t sai, int64_t sak, const double* B, int64_t sbk, int64_t sbj,
+                       double* C, int64_t ldc, int64_t m, int64_t n, int64_t k, double alpha, double beta, int nsplit) {
+  if (nsplit < 1 || k % nsplit != 0 || (nsplit > 1 && (k / nsplit) % 128 != 0)) {
+    note_launch_error("launch_dgemm_rect: k does not split into equal chunks of a multiple of 128");
+    return;
+  }
+  GemmDesc g{};
+  g.A = A;
+  g.sai = sai;
+  g.sak = sak;
+  g.B = B;
+  g.sbk = sbk;
+  g.sbj = sbj;
+  g.C = C;
+  g.ldc = ldc;
+  g.m = g.m_last = (int)m;
+  g.n = (int)n;
+  g.k = (int)(k / nsplit);
+  g.nbatch = nsplit;
+  g.batchA = (k / nsplit) * sak;
+  g.batchB = (k / nsplit) * sbk;
+  g.batchC = nsplit > 1 ? m * ldc : 0;
+  g.alpha = alpha;
+  g.beta = nsplit > 1 ? 0.0 : beta;
+  launch_gemm<double>(st, g);
+}
+
 // =============================================================================================
 // rank-W update of the trailing matrix on the bf16 matrix cores (float fits, two-level path)
 // =============================================================================================

@@ -320,6 +320,34 @@ void launch_vgp_lik_sums(hipStream_t st, const double* ve, const double* dve, co
 void launch_vgp_lbar_w(hipStream_t st, double* lsig, const double* a, const double* gm, const double* mu, int64_t n,
                        int64_t npad);
 void launch_vgp_rowscale(hipStream_t st, const double* A, const double* a, double* B, int64_t n, int64_t npad);
+// ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
+// C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
+// j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).
+// nsplit > 1: split-K -- k is cut into nsplit equal chunks (each a multiple of 128) and chunk s goes to C + s * m * ldc
+// (beta ignored); the caller sums the partial products in their fixed order (launch_sgpr_splitk_sum).
+void launch_dgemm_rect(hipStream_t st, const double* A, int64_t sai, int64_t sak, const double* B, int64_t sbk, int64_t sbj,
+                       double* C, int64_t ldc, int64_t m, int64_t n, int64_t k, double alpha, double beta, int nsplit = 1);
+void launch_sgpr_cross_gram(hipStream_t st, const double* zs, const double* xs, int64_t m, int64_t mpad, int64_t n,
+                            int64_t npad, int dp, const KernParams& kp, double* kuf);
+// out[n_ls + 1] = sum_ij (g_ij + a_i t_j) dKuf_ij / d(lengthscales..., variance); partial: (mpad / 64) (npad / 64) (n_ls + 1)
+void launch_sgpr_cross_grad(hipStream_t st, const double* g, const double* a, const double* t, const double* zs,
+                            const double* xs, int64_t m, int64_t mpad, int64_t n, int64_t npad, int dp, int n_ls,
+                            const double* ls, const KernParams& kp, double* partial, double* out);
+void launch_sgpr_splitk_sum(hipStream_t st, const double* part, int nsplit, int64_t m, int64_t mpad, double* aat, double* bm,
+                            int* info);
+// out = alpha op(A) x over the real block of a [mpad x npad] matrix (trans: out has n entries, x has m)
+void launch_sgpr_gemv(hipStream_t st, const double* A, bool trans, const double* x, double alpha, double* out, int64_t m,
+                      int64_t mpad, int64_t n, int64_t npad);
+void launch_sgpr_resid(hipStream_t st, const double* y, double c, double* e, int64_t n, int64_t npad);
+void launch_sgpr_tvec(hipStream_t st, const double* e, const double* w, double p, double q, double* t, int64_t n, int64_t npad);
+void launch_sgpr_wuu(hipStream_t st, const double* g1, const double* p, const double* a, double b, double* kin, int64_t m,
+                     int64_t mpad);
+constexpr int kSgprSums = 9;
+void launch_sgpr_sums(hipStream_t st, const double* lb, const double* aat, const double* cv, const double* e, const double* w,
+                      const double* lbinv_rows, int64_t m, int64_t mpad, int64_t n, double* out);
+// greedy conditional-variance selection of m rows of xs (scaled inputs, n rows): idx[m]; lg: m * npad doubles of scratch
+void launch_sgpr_greedy(hipStream_t st, const double* xs, int64_t n, int64_t npad, int dp, const KernParams& kp, int m,
+                        double* lg, double* dvec, double* pivot, int64_t* idx);
 // ---- append.hip: rank-k append at fixed hyper-parameters ----------------------------------------------------------------
 // The posterior of the first n points is resident; k <= kAppendMax new points (already copied behind the old ones in
 // x64 / y64) extend L, L^-1, a, alpha, diag(K_y^-1), the NLML and the scaled inputs in place: two passes over L^-1

@@ -319,6 +319,68 @@ class HipGPEngine:
         self._check(self._lib.gpso_vgp_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
                                                  float(mean_c_fixed)))
 
+    # -- sparse GP regression on inducing points (include/gpso_hip.h: gpso_sgpr_*) ----------------
+    def sgpr_set_inducing(self, Z):
+        """Z [M, D] summarises the resident training data; afterwards the engine's resident rows are Z (``n`` = M)."""
+        Z = L.as_f64(Z)
+        if Z.ndim != 2 or Z.shape[1] != self.d:
+            raise ValueError(f"Z must be [M, {self.d}]")
+        self._check(self._lib.gpso_sgpr_set_inducing(self._h, L.dptr(Z), Z.shape[0]))
+        self.n = int(Z.shape[0])
+
+    def sgpr_select_inducing(self, kernel, u, n_ls, m):
+        """Greedy conditional-variance selection of ``m`` training rows on the device at the kernel hyper-parameters of
+        ``u``; they become Z.  Returns their indices in pick order."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        idx = np.empty(int(m), dtype=np.int64)
+        self._check(self._lib.gpso_sgpr_select_inducing(self._h, kid, L.dptr(ua), int(n_ls), int(m),
+                                                        idx.ctypes.data_as(C.POINTER(C.c_int64))))
+        self.n = int(m)
+        return idx
+
+    def sgpr_get_inducing(self):
+        """(Z [M, D], N of the training data held beside it)."""
+        m, n = C.c_int64(), C.c_int64()
+        self._check(self._lib.gpso_sgpr_get_inducing(self._h, None, C.byref(m), C.byref(n)))
+        Z = np.empty((m.value, self.d), dtype=np.float64)
+        self._check(self._lib.gpso_sgpr_get_inducing(self._h, L.dptr(Z), None, None))
+        return Z, int(n.value)
+
+    def sgpr_get_factor(self, which):
+        """An intermediate of the last ``sgpr_bound_u``: "Kuf" [M, N], "Lu" [M, M], "LB" [M, M] or "cv" [M] (for checks)."""
+        ids = {"Kuf": L.SGPR_KUF, "Lu": L.SGPR_LU, "LB": L.SGPR_LB, "cv": L.SGPR_CV}
+        if which == "Kuf":
+            n = C.c_int64()
+            self._check(self._lib.gpso_sgpr_get_inducing(self._h, None, None, C.byref(n)))
+            out = np.empty((self.n, n.value), dtype=np.float64)
+        else:
+            out = np.empty(self.n if which == "cv" else (self.n, self.n), dtype=np.float64)
+        self._check(self._lib.gpso_sgpr_get_factor(self._h, ids[which], L.dptr(out)))
+        return out
+
+    def sgpr_bound_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
+        """-bound (Titsias) and its gradient in ``u``, Z fixed.  Returns (loss, grad_u or None, theta)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
+        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
+        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+        loss = C.c_double()
+        self._check(self._lib.gpso_sgpr_bound_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                                float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
+                                                L.dptr(ta)))
+        return loss.value, ga, ta
+
+    def sgpr_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
+        """Install the SGPR predictive at the theta of ``u`` over the rows Z.  Returns the shift delta (0: exact)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        delta = C.c_double()
+        self._check(self._lib.gpso_sgpr_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                                  float(mean_c_fixed), C.byref(delta)))
+        return delta.value
+
     def set_posterior(self, X, Lchol, alpha, kernel, lengthscales, variance, noise, mean_c):
         X = L.as_f64(X)
         n, d = X.shape

@@ -30,6 +30,7 @@ from scipy.special import erfcinv
 
 from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero
 from .model import HipGPR
+from .sgpr import HipSGPR
 from .vgp import HipVGP, carried_order
 from .utils import JSON_EXT, PointLabels
 
@@ -529,6 +530,110 @@ class GPRSurrogate(GPSurrogate):
                    gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
                    points=points, gpflow_model=model, dtype=info.get("dtype", "float64"), device=device,
                    devices=devices, refit_every=info.get("refit_every", 1), refit_guard=info.get("refit_guard", 2.0))
+
+
+class SGPRSurrogate(GPSurrogate):
+    """Sparse GP regression surrogate on inducing points (GPflow's ``SGPR``, Titsias 2009): M points Z summarise the N
+    evaluated points, an update costs O(N M^2) per loss evaluation and every leaf-UCB prediction O(M^2) whatever N -- the
+    surrogate for runs whose N outgrows the exact GPR.  While N <= M, Z is the data and the model is the exact GPR up to
+    GPflow's 1e-6 jitter on Kuu.  Z is not trained: each ``_gp_train`` chooses it again (``"greedy"``: the conditional-
+    variance selection on the device at the hyper-parameters the search starts from; or an array used as given) and
+    keeps it fixed while L-BFGS-B searches the hyper-parameters (``HipSGPR``)."""
+
+    def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3,
+                 num_inducing=256, inducing="greedy", points=None, gpflow_model=None, dtype="float64", device=0,
+                 engine_options=None):
+        """
+        :param gauss_likelihood_sigma: initial noise VARIANCE of the Gaussian likelihood (as ``GPRSurrogate``)
+        :param num_inducing: M (ignored when ``inducing`` is an array)
+        :param inducing: "greedy" or an [M, D] array of normed coordinates used as given
+        """
+        if dtype not in ("float64", "mixed"):
+            raise ValueError(f"SGPR trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
+        if isinstance(inducing, str):
+            if inducing != "greedy":
+                raise ValueError(f"inducing must be 'greedy' or an [M, D] array, not {inducing!r}")
+            if int(num_inducing) < 1:
+                raise ValueError(f"num_inducing={num_inducing}: need at least one inducing point")
+        else:
+            inducing = np.ascontiguousarray(inducing, dtype=np.float64)
+            if inducing.ndim != 2 or inducing.shape[0] < 1 or not np.all(np.isfinite(inducing)):
+                raise ValueError("inducing must be a finite [M, D] array with M >= 1")
+            num_inducing = inducing.shape[0]
+        super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf, optimiser=optimiser, varsigma=varsigma, points=points,
+                         gpflow_model=gpflow_model, dtype=dtype, device=device, engine_options=engine_options)
+        self.gp_lik_sigma = gauss_likelihood_sigma
+        self.num_inducing = int(num_inducing)
+        self.inducing = inducing
+
+    @classmethod
+    def default(cls, num_inducing=256, dtype="float64", device=0, engine_options=None):
+        """``GPRSurrogate.default()``'s specification with M inducing points."""
+        return cls(gp_kernel=Matern52(lengthscales=np.sum(NORM_PARAMS_BOUNDS) * 0.25, variance=1.0), gp_meanf=Constant(0.0),
+                   optimiser=Scipy(), varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3, num_inducing=num_inducing,
+                   dtype=dtype, device=device, engine_options=engine_options)
+
+    def _gp_train(self, x, y):
+        assert x.shape[0] == y.shape[0]
+        assert x.ndim == 2 and y.ndim == 2
+        if self.gpflow_model is None:
+            self.gpflow_model = HipSGPR(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
+                                        noise_variance=self.gp_lik_sigma, num_inducing=self.num_inducing,
+                                        inducing=self.inducing, dtype=self.dtype, device=self.device,
+                                        engine_options=self.engine_options)
+        else:
+            self.gpflow_model.data = (x, y)  # Z chosen again at the hyper-parameters the search warm-starts from
+        self.optimiser.minimize(self.gpflow_model.training_loss, self.gpflow_model.trainable_variables)
+
+    # -- persistence: the GPR schema plus num_inducing, the policy and Z ----------------------------
+    def save(self, folder):
+        os.makedirs(folder, exist_ok=True)
+        self.points.save(os.path.join(folder, self.POINTS_FILE))
+        model = self.gpflow_model
+        params = {k: np.asarray(v).tolist() for k, v in model.parameter_dict().items()}
+        with open(os.path.join(folder, self.GPR_FILE), "w") as fh:
+            fh.write(json.dumps(params))
+        info = {
+            "gpr_kernel": model.kernel.name,
+            "gpr_kernel_shape": list(np.shape(model.kernel.lengthscales)),
+            "gpr_meanf": type(model.mean_function).__name__,
+            "gpr_meanf_shape": [],
+            "gp_varsigma": self.gp_varsigma,
+            "gp_likelihood": self.gp_lik_sigma,
+            "optimiser": [type(self.optimiser).__name__],
+            "dtype": self.dtype,
+            "model": "SGPR",
+            "num_inducing": self.num_inducing,
+            "inducing": "greedy" if isinstance(self.inducing, str) else "given",
+        }
+        with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
+            fh.write(json.dumps(info))
+
+    @classmethod
+    def from_saved(cls, folder, device=0):
+        points = GPListOfPoints.from_file(os.path.join(folder, cls.POINTS_FILE))
+        ev = [p for p in points if p.label == PointLabels.evaluated]
+        x = np.array([p.normed_coord for p in ev])
+        y = np.array([p.score_mu for p in ev])[:, np.newaxis]
+        with open(os.path.join(folder, cls.GPR_INFO)) as fh:
+            info = json.load(fh)
+        with open(os.path.join(folder, cls.GPR_FILE)) as fh:
+            params = json.load(fh)
+        assert info.get("model") == "SGPR", "not a saved SGPRSurrogate"
+        assert info["gpr_kernel"] in KERNEL_CLASSES
+        kernel = KERNEL_CLASSES[info["gpr_kernel"]](
+            lengthscales=np.array(params[".kernel.lengthscales"]), variance=params[".kernel.variance"])
+        meanf = Constant(params[".mean_function.c"]) if info["gpr_meanf"] == "Constant" else Zero()
+        assert info["optimiser"][0] == "Scipy", f"{info['optimiser']} not currently supported."
+        z = np.array(params[".inducing_variable.Z"], dtype=np.float64).reshape(-1, x.shape[1])
+        inducing = z if info["inducing"] == "given" else "greedy"
+        dtype = info.get("dtype", "float64")
+        model = HipSGPR(data=(x, y), kernel=kernel, mean_function=meanf, noise_variance=params[".likelihood.variance"],
+                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device)
+        model.set_inducing(z)  # the Z the saved posterior was built on (the next update chooses again)
+        return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=Scipy(), gauss_likelihood_sigma=info["gp_likelihood"],
+                   varsigma=info["gp_varsigma"], num_inducing=info["num_inducing"], inducing=inducing, points=points,
+                   gpflow_model=model, dtype=dtype, device=device)
 
 
 VGP_TRAIN_ITERATIONS = 10

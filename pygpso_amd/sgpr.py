@@ -1,0 +1,147 @@
+"""
+``HipSGPR``: sparse GP regression on inducing points, the model the ``SGPRSurrogate`` keeps in ``.gpflow_model``.
+
+Stands where ``gpflow.models.SGPR`` (Titsias 2009, Gaussian likelihood) would: M inducing points Z summarise the N training
+rows, ``training_loss`` is the negative collapsed bound and costs O(N M^2) on the device, and a prediction costs O(M^2)
+whatever N: the predictive is installed as a whitened Gaussian over the M rows Z (include/gpso_hip.h: gpso_sgpr_posterior),
+so ``predict_y`` / ``best_ucb`` / ``best_ucb_grow`` run through the predict kernels of the GPR path.  Hyper-parameters and
+their transforms are ``HipGPR``'s.  Z is not trained (GPflow's ``set_trainable(model.inducing_variable, False)``): it is
+chosen by ``choose_inducing`` -- the data itself while N <= M, beyond that the greedy conditional-variance selection on the
+device (pivoted partial Cholesky of k(X, X)) at the current kernel hyper-parameters, or an array given by the caller.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .model import HipGPR, _as_result
+
+
+class HipSGPR(HipGPR):
+    def __init__(self, data, kernel, mean_function=None, noise_variance=1.0e-3, num_inducing=256, inducing="greedy",
+                 dtype="float64", device=0, engine=None, engine_options=None):
+        """``num_inducing``: M.  ``inducing``: "greedy" or an [M, D] array used as given.  ``dtype``: "float64" or "mixed"
+        (float64 training, float predict arithmetic)."""
+        if dtype not in ("float64", "mixed"):
+            raise ValueError(f"SGPR trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
+        if isinstance(inducing, str):
+            if inducing != "greedy":
+                raise ValueError(f"inducing must be 'greedy' or an [M, D] array, not {inducing!r}")
+            if int(num_inducing) < 1:
+                raise ValueError(f"num_inducing={num_inducing}: need at least one inducing point")
+            self.inducing_policy, self._z_given = "greedy", None
+            self.num_inducing = int(num_inducing)
+        else:
+            z = np.ascontiguousarray(inducing, dtype=np.float64)
+            if z.ndim != 2 or z.shape[0] < 1 or not np.all(np.isfinite(z)):
+                raise ValueError("inducing must be a finite [M, D] array with M >= 1")
+            self.inducing_policy, self._z_given = "given", z
+            self.num_inducing = int(z.shape[0])
+        self.inducing_index = None  # rows of the data the greedy selection picked (None: Z is the data or was given)
+        self.install_delta = 0.0    # shift of the last install (0: the served variance is exact)
+        super().__init__(data, kernel, mean_function=mean_function, noise_variance=noise_variance, dtype=dtype,
+                         device=device, engine=engine, engine_options=engine_options, escalate=False)
+
+    # -- data and Z -------------------------------------------------------------------------------
+    @property
+    def data(self):
+        return self._data
+
+    @data.setter
+    def data(self, value):
+        x, y = value
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 1)
+        assert x.ndim == 2 and x.shape[0] == y.shape[0]
+        if self._z_given is not None and self._z_given.shape[1] != x.shape[1]:
+            raise ValueError(f"inducing points have D={self._z_given.shape[1]}, the data D={x.shape[1]}")
+        self._data = (x, y)
+        self._resident = False
+        self._device_theta = None
+        self.choose_inducing()
+
+    def choose_inducing(self):
+        """(Re-)choose Z for the current data at the current kernel hyper-parameters and put both on the device."""
+        x, y = self._data
+        self.engine.set_data(x, y[:, 0])
+        self.inducing_index = None
+        if self._z_given is not None:
+            self.engine.sgpr_set_inducing(self._z_given)
+        elif x.shape[0] <= self.num_inducing:
+            self.engine.sgpr_set_inducing(x)
+        else:
+            self.inducing_index = self.engine.sgpr_select_inducing(self.kernel.name, self._pack(), self.n_ls, self.num_inducing)
+        self._resident = False
+
+    @property
+    def inducing_points(self):
+        """Z [M, D] as the device holds it."""
+        return self.engine.sgpr_get_inducing()[0]
+
+    def set_inducing(self, Z):
+        """Use Z [M, D] as given for the current data (kept until the data changes, unless the policy is an array)."""
+        z = np.ascontiguousarray(Z, dtype=np.float64)
+        x, y = self._data
+        self.engine.set_data(x, y[:, 0])
+        self.engine.sgpr_set_inducing(z)
+        self.inducing_index = None
+        self._resident = False
+
+    def append_data(self, x_new, y_new):
+        """New rows behind the held ones; Z is chosen again (no in-place posterior update for an SGPR)."""
+        x = np.concatenate([self._data[0], np.atleast_2d(x_new)])
+        y = np.concatenate([self._data[1], np.asarray(y_new, dtype=np.float64).reshape(-1, 1)])
+        self.data = (x, y)
+        return False
+
+    # -- training -------------------------------------------------------------------------------
+    def _args(self):
+        return self.kernel.name, self.n_ls, self._train_mean, float(self.mean_function.c)
+
+    def _loss_and_grad(self, u):
+        """-bound and its gradient in u at fixed Z (one device evaluation)."""
+        name, k, tm, c = self._args()
+        f, gu, _ = self.engine.sgpr_bound_u(name, u, k, tm, c)
+        self._last_nlml = f
+        self.num_loss_evals += 1
+        self._resident = False
+        return f, gu
+
+    def training_loss(self):
+        """-bound at the current hyper-parameters and Z."""
+        name, k, tm, c = self._args()
+        f, _, _ = self.engine.sgpr_bound_u(name, self._pack(), k, tm, c, want_grad=False)
+        self._resident = False
+        return f
+
+    def elbo(self):
+        return -self.training_loss()
+
+    def log_marginal_likelihood(self):
+        raise NotImplementedError("an SGPR has a lower bound of the marginal likelihood: use elbo()")
+
+    def _ensure_resident(self):
+        if not self._resident:
+            name, k, tm, c = self._args()
+            self.install_delta = self.engine.sgpr_posterior(name, self._pack(), k, tm, c)
+            self._resident = True
+
+    def _escalate(self, err, fit=False):
+        return False
+
+    def predict_f(self, Xnew):
+        """Latent mean and variance.  After a shifted install (``install_delta`` > 0) the variance keeps the shift's
+        surplus delta (k** - |Lu^-1 k*u|^2) >= 0: never below the exact latent variance."""
+        mean, var = self.predict_y(Xnew)
+        return mean, _as_result(np.asarray(var) - self.likelihood.variance)
+
+    # -- reporting -----------------------------------------------------------------------------
+    def parameter_dict(self):
+        d = super().parameter_dict()
+        d[".inducing_variable.Z"] = self.inducing_points
+        return d
+
+    def summary(self):
+        lines = super().summary().replace("GPR.", "SGPR.").split("\n")
+        z = self.inducing_points
+        lines.append(f"{'SGPR.inducing_variable.Z':<24} {'(not trained)':<17} shape {z.shape}")
+        return "\n".join(lines)
