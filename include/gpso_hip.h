@@ -245,7 +245,8 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
 /* Replaces: choosing the likelihood of gpflow.models.VGP(likelihood=...) (gpso/gp_surrogate.py:536-541).  kind:
  * GPSO_LIK_*; df: the Student-t's degrees of freedom (> 2; ignored otherwise); gh_x[n_gh], gh_w[n_gh]: the Gauss-Hermite
  * nodes and weights of numpy.polynomial.hermite.hermgauss(n_gh) (GPflow's 20 points), 1 <= n_gh <= 64 (both ignored
- * for GPSO_LIK_GAUSSIAN).  Anything else: GPSO_E_ARG.  Takes effect at the next gpso_vgp_* call; q is kept.
+ * for GPSO_LIK_GAUSSIAN).  Anything else: GPSO_E_ARG.  Takes effect at the next gpso_vgp_* call; q is kept.  The
+ * same setting is the likelihood of the sparse variational GP (gpso_svgp_*, below).
  * Under a quadrature likelihood gpso_vgp_natgrad forms the step at the current q (Lambda* = I + L^T diag(a) L,
  * h* = L^T (g_m + a (m - c))); when a factorisation fails -- an indefinite step, e.g. at gross outliers with gamma = 1 --
  * it returns GPSO_E_NOTPD and leaves q exactly as it was (as GPflow), where the Gaussian restarts q at the prior. */
@@ -325,6 +326,45 @@ int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
  * delta the first of 0, 1e-8, 2e-8, ... for which I - B^-1 / (1 + delta) factors: never below the exact variance, at most
  * delta k** above it, exact when delta = 0 (DESIGN.md sections 7a.1, 7b).  *delta_out (nullable) = delta. */
 int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* delta_out);
+
+/* ---- sparse variational GP on inducing points (GPflow 2 SVGP, whitened, full q_sqrt, full batch) ---------------------
+ * q(v) = N(mu, S S^T) over the M inducing values, f(x) = k(x, Z) Lu^-T v + c, Lu = chol(k(Z, Z) + 1e-6 I), trained against
+ * the likelihood of gpso_vgp_set_likelihood (that call sets the likelihood of the VGP AND of the SVGP: Gaussian in closed
+ * form, Student-t or the Gaussian through 20-point Gauss-Hermite quadrature).  Training costs O(N M^2), a prediction
+ * O(M^2).  Z and the training data are the SGPR's: gpso_set_data, then gpso_sgpr_set_inducing or
+ * gpso_sgpr_select_inducing; Z is then the context's resident rows (see the SGPR block above).  Setting Z starts q at the
+ * prior (mu = 0, S = I); the next gpso_set_data drops Z and q.  A call before Z is set returns GPSO_E_STATE, a
+ * GPSO_F32 context GPSO_E_ARG.  u, n_ls, train_mean, mean_c_fixed: the optimiser's vector and transforms exactly as
+ * gpso_vgp_elbo_u, the likelihood slot u[n_ls + 1] included (the Student-t scale, or 1e-6 + softplus for the Gaussian
+ * variance).  The SGPR's and the VGP's own state and entry points are untouched by these calls. */
+
+/* Start q: noise_variance <= 0: the prior (u may be NULL); else the conjugate start -- one natural-gradient step of
+ * length 1 with a Gaussian likelihood of variance noise_variance, at the theta of u, whatever the context's likelihood
+ * (SVGPSurrogate passes the Student-t's predictive variance scale^2 df / (df - 2)).  GPSO_E_NOTPD: q unchanged. */
+int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double noise_variance);
+/* Host float64 mu[m], S[m*m] (row-major, lower triangle read) of the resident Z (m must equal M); both NULL: the prior.
+ * gpso_svgp_get_q copies q out (either pointer nullable). */
+int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m);
+int gpso_svgp_get_q(gpso_ctx* ctx, double* mu /* [M] */, double* S /* [M*M] */);
+/* One natural-gradient step of length gamma in (0, 1] on q at theta (GPflow's NaturalGradient): with A = Lu^-1 Kuf and
+ * the per-point g_m = dVE/dm, a = -2 dVE/dv at the current q, Lambda* = I + A diag(a) A^T, h* = A (g_m + a (m - c)), mixed
+ * with q's natural parameters by gamma.  When a factorisation fails (an indefinite step: gross outliers under the
+ * Student-t) it returns GPSO_E_NOTPD and leaves q exactly as it was, for every likelihood. */
+int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      double gamma);
+/* -ELBO = -sum_i VE_i(m_i, v_i) + KL(q || N(0, I)) at fixed q and Z, m_i = A_i^T mu + c, v_i = variance - |A_i|^2 +
+ * |S^T A_i|^2; grad_u (nullable) d(-ELBO)/du; theta_out[n_ls + 3] (nullable) (lengthscales..., variance, likelihood
+ * parameter, c).  Deterministic: the same call gives the same bits. */
+int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double* loss, double* grad_u, double* theta_out);
+/* Install the SVGP predictive over the rows Z: mean = k*u^T Lu^-T mu + c, var = k** - k*u^T Lu^-T (I - S S^T) Lu^-1 k*u
+ * + the likelihood's variance (s2, or scale^2 df / (df - 2) for the Student-t) -- the VGP's install with L := Lu, delta
+ * shift included (where I - S S^T does not factor: var + delta (k** - |Lu^-1 k*u|^2), delta the first of 0, 1e-8, 2e-8, ...
+ * for which I - S S^T / (1 + delta) does; *delta_out, nullable).  Every predict path then serves it; the getters return
+ * the installed form as after gpso_sgpr_posterior, and gpso_append returns GPSO_E_STATE. */
+int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out);
 
 /* ---- predict (gpflow_model.predict_y users) ----------------------------------------------- */

@@ -98,6 +98,13 @@ SIGNATURES = {
     "gpso_sgpr_bound_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_sgpr_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p]),
+    "gpso_svgp_init_q": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "gpso_svgp_set_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64]),
+    "gpso_svgp_get_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
+    "gpso_svgp_natgrad": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "gpso_svgp_elbo_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                   _c_double_p, _c_double_p]),
+    "gpso_svgp_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p]),
     "gpso_predict": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p,
                                C.c_void_p, C.c_int]),
     "gpso_best_ucb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p,

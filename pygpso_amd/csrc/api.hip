@@ -136,6 +136,15 @@ struct Engine {
                          double* grad) = 0;
   virtual int sgpr_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c,
                              double* delta_out) = 0;
+  // sparse variational GP on inducing points (svgp.hip)
+  virtual int svgp_init_q(int kernel, const double* ls, int n_ls, double variance, double mean_c, double s2) = 0;
+  virtual int svgp_set_q(const double* mu, const double* S, int64_t m) = 0;
+  virtual int svgp_get_q(double* mu, double* S) = 0;
+  virtual int svgp_natgrad(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, double gamma) = 0;
+  virtual int svgp_elbo(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, double* loss,
+                        double* grad) = 0;
+  virtual int svgp_posterior(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c,
+                             double* delta_out) = 0;
   int vlik_kind = GPSO_LIK_GAUSSIAN;  // the VGP's likelihood (GPSO_LIK_*): what slot n_ls + 1 of u means
 };
 
@@ -912,7 +921,7 @@ struct EngineT : Engine {
     if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
     have_data = true;
     have_post = have_kinv = chol_valid = linv_p_valid = false;
-    vgp_post = sgpr_post = false;
+    vgp_post = sgpr_post = svgp_post = false;
     if (!sg_keep) sg_have = sg_have_z = false;  // (the caller's own gpso_set_data: new data, no inducing points)
     sg_factors = false;
     st_done = st_have = false;
@@ -932,7 +941,7 @@ struct EngineT : Engine {
     const bool small = fused_small && small_fit_eligible(n, dp);
     if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c, !small))) return rc;
     have_post = have_kinv = chol_valid = false;
-    vgp_post = sgpr_post = false;
+    vgp_post = sgpr_post = svgp_post = false;
     sg_have_z = sg_factors = false;  // (a GPR fit on the resident rows: they are no inducing points any more)
     st_done = st_have = false;
     forget_peers();
@@ -1099,6 +1108,7 @@ struct EngineT : Engine {
     ctx->tick_timing();
     if (!Xn || !yn) return ctx->fail(GPSO_E_ARG, "Xnew / ynew must not be NULL");
     if (k < 1) return ctx->fail(GPSO_E_ARG, "need at least one new point (k=%lld)", (long long)k);
+    if (svgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SVGP predictive: its rows are the inducing points; set the grown data and train again");
     if (sgpr_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SGPR predictive: its rows are the inducing points; set the grown data and train again");
     if (vgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
     if (int rca = refuse_if_async("gpso_append")) return rca;
@@ -1221,7 +1231,7 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(tmp, L, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp + (size_t)n * n, alpha64, (size_t)n * 8, hipMemcpyHostToDevice, s));
     have_data = false;  // y unknown: a later fit needs gpso_set_data
-    vgp_post = sgpr_post = false;
+    vgp_post = sgpr_post = svgp_post = false;
     sg_have = sg_have_z = sg_factors = false;
     have_post = have_kinv = chol_valid = false;
     st_done = st_have = false;
@@ -1325,7 +1335,7 @@ struct EngineT : Engine {
     if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
     if (vlik_kind != GPSO_LIK_GAUSSIAN && (rc = ensure(vlvec, (size_t)kLikVecs * npad * 8))) return rc;
     if (vq_n != n || vq_npad != npad) vgp_prior();
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = false;
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
     linv_p_lazy = false;
     st_done = st_have = false;
     forget_peers();
@@ -1359,7 +1369,8 @@ struct EngineT : Engine {
     return vgp_chol(as<double>(K), as<double>(Lf), as<double>(linv), vinfo() + 0, 0.0);
   }
   // wait for the stream, then the verdicts of the factorisations (out: host copy of vsmall)
-  int vgp_finish(double** out, bool sgpr = false) {
+  // (model: 0 the VGP, 1 the SGPR, 2 the SVGP -- the names in a failure's message)
+  int vgp_finish(double** out, int model = 0) {
     double* host = ctx->pinned_scratch(kVgpSmall);
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(host, vsmall.p, kVgpSmall * 8, hipMemcpyDeviceToHost, st()));
@@ -1371,9 +1382,12 @@ struct EngineT : Engine {
     static const char* what[4] = {"k(X, X) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
                                   "I - S S^T (reversed order)"};
     static const char* what_sgpr[4] = {"Kuu = k(Z, Z) + 1e-6 I", "B = I + A A^T", "(unused)", "I - B^-1 (reversed order)"};
+    static const char* what_svgp[4] = {"Kuu = k(Z, Z) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
+                                       "I - S S^T (reversed order)"};
     for (int q = 0; q < 4; ++q)
       if (info[q] != INT_MAX)
-        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d", (sgpr ? what_sgpr : what)[q], info[q]);
+        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d",
+                         (model == 2 ? what_svgp : model == 1 ? what_sgpr : what)[q], info[q]);
     *out = host;
     return GPSO_OK;
   }
@@ -1451,6 +1465,34 @@ struct EngineT : Engine {
     return launch_status();
   }
 
+  // the update of q = N(qmu, qS qS^T) from the step's natural parameters Lambda* (vA, destroyed; identity padding) and h*
+  // (vvec kVgpH), at the context's size n: gamma-mixing with q's current natural parameters (Lambda = S^-T S^-1, h =
+  // Lambda mu), then GPflow's natural_to_meanvarsqrt into (mu_out, S_out); the verdicts in vinfo() 1 and 2
+  int vgp_natural_update(const double* qmu, const double* qS, double gamma, double* mu_out, double* S_out) {
+    hipStream_t s = st();
+    double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
+    double *h = vvec_at(kVgpH), *h2 = vvec_at(kVgpH2);
+    int rc;
+    if (gamma != 1.0) {
+      // the current natural parameters: Lambda = S^-T S^-1, h = Lambda mu
+      HIPCHECK(hipMemsetAsync(Cm, 0, (size_t)npad * npad * 8, s));
+      launch_install_chol<double>(s, qS, npad, npad, B, Cm);
+      launch_trtri<double>(s, B, Cm, as<double>(work), npad, kFitBlock);
+      launch_vgp_clean_lower(s, Cm, Cm, n, npad, 0.0);
+      launch_dgemm(s, Cm, true, Cm, false, B, npad, 1.0, 0.0);
+      launch_vgp_gemv(s, B, false, qmu, 0.0, 1.0, 0.0, nullptr, h2, n, npad);
+      launch_vgp_axpby(s, B, A, npad * npad, 1.0 - gamma, gamma);
+      launch_vgp_axpby(s, h2, h, npad, 1.0 - gamma, gamma);
+    }
+    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 1);
+    // V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
+    if ((rc = vgp_chol(A, B, Cm, vinfo() + 1, 0.0))) return rc;
+    launch_dgemm(s, Cm, true, Cm, false, A, npad, 1.0, 0.0);
+    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, mu_out, n, npad);
+    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 2);
+    return vgp_chol(A, S_out, Cm, vinfo() + 2, 1.0);
+  }
+
   // one natural-gradient step on q at theta (GPflow's NaturalGradient with a conjugate likelihood, gamma in (0, 1])
   int vgp_natgrad(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double gamma) override {
     if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
@@ -1459,8 +1501,7 @@ struct EngineT : Engine {
     hipStream_t s = st();
     vgp_reset_info();
     if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
-    double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
-    double *h = vvec_at(kVgpH), *h2 = vvec_at(kVgpH2);
+    double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *h = vvec_at(kVgpH);
     const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
     if (!general) {
       launch_vgp_pad_identity(s, A, 0, npad, nullptr);          // A := I
@@ -1475,28 +1516,12 @@ struct EngineT : Engine {
       launch_dgemm(s, L, true, B, false, A, npad, 1.0, 1.0);
       launch_vgp_gemv(s, L, true, lvec_at(kLikT), 0.0, 1.0, 0.0, nullptr, h, n, npad);
     }
-    if (gamma != 1.0) {
-      // the current natural parameters: Lambda = S^-T S^-1, h = Lambda mu
-      HIPCHECK(hipMemsetAsync(Cm, 0, (size_t)npad * npad * 8, s));
-      launch_install_chol<double>(s, as<double>(vq_S), npad, npad, B, Cm);
-      launch_trtri<double>(s, B, Cm, as<double>(work), npad, kFitBlock);
-      launch_vgp_clean_lower(s, Cm, Cm, n, npad, 0.0);
-      launch_dgemm(s, Cm, true, Cm, false, B, npad, 1.0, 0.0);
-      launch_vgp_gemv(s, B, false, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, h2, n, npad);
-      launch_vgp_axpby(s, B, A, npad * npad, 1.0 - gamma, gamma);
-      launch_vgp_axpby(s, h2, h, npad, 1.0 - gamma, gamma);
-    }
-    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 1);
     // GPflow's natural_to_meanvarsqrt: V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
     // (a general likelihood builds the new q in scratch -- mu in its vector, S in the Gram's buffer, free by now -- and
     // commits it only when every factorisation held: GPflow's natgrad assigns nothing when natural_to_meanvarsqrt fails)
     double* mu_out = general ? lvec_at(kLikMu) : as<double>(vq_mu);
     double* S_out = general ? as<double>(K) : as<double>(vq_S);
-    if ((rc = vgp_chol(A, B, Cm, vinfo() + 1, 0.0))) return rc;
-    launch_dgemm(s, Cm, true, Cm, false, A, npad, 1.0, 0.0);
-    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, mu_out, n, npad);
-    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 2);
-    if ((rc = vgp_chol(A, S_out, Cm, vinfo() + 2, 1.0))) return rc;
+    if ((rc = vgp_natural_update(as<double>(vq_mu), as<double>(vq_S), gamma, mu_out, S_out))) return rc;
     double* host;
     if ((rc = vgp_finish(&host))) {
       if (!general) vgp_prior();  // (a failed Gaussian step leaves q at the prior, not half written; a general one: q as it was)
@@ -1575,10 +1600,12 @@ struct EngineT : Engine {
   // Student-t: a < 0 in its tails) can leave Sigma above I in a direction, where the predict kernels' one-term form
   // k** - |C k*|^2 cannot hold var_f exactly; the install then serves k** - k*^T L^-T ((1 + delta) I - Sigma) L^-1 k*
   // + delta k**, i.e. var_f + delta (k** - |L^-1 k*|^2), in [var_f, var_f + delta k**].
-  int vgp_shifted_root(double* delta_out, bool sigma_ready = false /* K already holds Sigma (the SGPR install: B^-1) */) {
+  int vgp_shifted_root(double* delta_out, bool sigma_ready = false /* K already holds Sigma (the SGPR install: B^-1) */,
+                       const double* qS = nullptr /* the root of Sigma when it is not the VGP's (the SVGP's q) */) {
     hipStream_t s = st();
     double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sig = as<double>(K);
-    if (!sigma_ready) launch_dgemm(s, as<double>(vq_S), false, as<double>(vq_S), true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
+    if (!qS) qS = as<double>(vq_S);
+    if (!sigma_ready) launch_dgemm(s, qS, false, qS, true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
     int* host = reinterpret_cast<int*>(ctx->pinned_scratch(kVgpSmall));
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     for (double delta = 0.0; delta <= 1.0; delta = (delta == 0.0 ? 1.0e-8 : 2.0 * delta)) {
@@ -1638,7 +1665,7 @@ struct EngineT : Engine {
       return rc;
     }
     have_post = linv_p_valid = vgp_post = true;
-    sgpr_post = false;
+    sgpr_post = svgp_post = false;
     return GPSO_OK;
   }
 
@@ -1654,6 +1681,7 @@ struct EngineT : Engine {
   bool sg_have = false, sg_have_z = false, sg_keep = false;
   bool sg_factors = false;  // Kuf, Lu, LB, cv of the last gpso_sgpr_bound_u are still in their buffers (gpso_sgpr_get_factor)
   bool sgpr_post = false;  // the resident posterior is an SGPR predictive over the rows Z
+  bool svgp_post = false;  // ... an SVGP predictive over the rows Z (sgpr_post is set with it)
   enum { kSgE = 0, kSgW = 1, kSgT = 2, kSgVecsN = 3 };
   enum { kSgAe = 0, kSgCv = 1, kSgMu = 2, kSgAvec = 3, kSgRows = 4, kSgZero = 5, kSgVecsM = 6 };
   static constexpr int kSgGradAt = 16, kSgSmall = kSgGradAt + kGradMaxLs + 1;
@@ -1701,6 +1729,7 @@ struct EngineT : Engine {
       return rc;
     }
     sg_have_z = true;
+    svq_m = -1;  // (the SVGP's q restarts at the prior on the new Z)
     return GPSO_OK;
   }
 
@@ -1717,7 +1746,7 @@ struct EngineT : Engine {
       if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
     if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
     // (from here on the call replaces whatever posterior was resident: the hyper block is the selection's)
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = false;
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
     sg_factors = false;
     if ((rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, 0.0))) return rc;
     if ((rc = sgpr_stash())) return rc;
@@ -1906,6 +1935,275 @@ struct EngineT : Engine {
     }
     if (delta_out) *delta_out = shift;
     have_post = linv_p_valid = vgp_post = sgpr_post = true;
+    return GPSO_OK;
+  }
+
+  // ---- sparse variational GP on inducing points (GPflow 2 SVGP, whitened, full q_sqrt, full batch) --------
+  // Z and the training data are the SGPR's (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing: Z the resident rows, n = M),
+  // the likelihood the VGP's (gpso_vgp_set_likelihood).  q(v) = N(mu, S S^T) over the M inducing values lives in svq_mu
+  // [M_pad] and svq_S [M_pad^2] (lower; identity on the padding), made for the resident Z: a new Z restarts it at the
+  // prior.  A = Lu^-1 Kuf sits in the SGPR's sgA (without its 1 / sigma); svB holds S^T A, later the cross weight g;
+  // svD the column-scaled A diag(a).  The M x M work runs through the fit's and the VGP's buffers at M_pad.
+  DevBuf svq_mu, svq_S, svB, svD, svvecN;
+  int64_t svq_m = -1, svq_mpad = -1;  // the rows q was made for (-1: none; the next call starts q at the prior)
+  enum { kSvM = 0, kSvV = 1, kSvGm = 2, kSvA = 3, kSvT = 4, kSvVe = 5, kSvDve = 6, kSvVecsN = 7 };
+  double* svn_at(int k) const { return as<double>(svvecN) + (size_t)k * sg_npad; }
+  // the long-K products A diag(a) A^T split along N into this many fixed-order partial products (as the SGPR's A A^T)
+  int svgp_nsplit() const {
+    int ns = 1;
+    while (ns < 16 && sg_npad % (256 * ns) == 0 && sg_npad / (2 * ns) >= 512) ns *= 2;
+    return ns;
+  }
+
+  int svgp_need_z(const char* who) {
+    int rc = sgpr_need_f64();
+    if (rc) return rc;
+    if (!sg_have || !sg_have_z)
+      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
+    return GPSO_OK;
+  }
+  void svgp_prior() {
+    (void)hipMemsetAsync(svq_mu.p, 0, (size_t)npad * 8, st());
+    launch_vgp_pad_identity(st(), as<double>(svq_S), 0, npad, nullptr);
+    svq_m = n;
+    svq_mpad = npad;
+  }
+  // q's buffers at the resident M; the prior when q was made for other rows
+  int svgp_q() {
+    int rc;
+    if (svq_m == n && svq_mpad == npad) return GPSO_OK;
+    if ((rc = ensure(svq_mu, (size_t)npad * 8))) return rc;
+    if ((rc = ensure(svq_S, (size_t)npad * npad * 8))) return rc;
+    svgp_prior();
+    return GPSO_OK;
+  }
+
+  // Lu (Lf), Lu^-1 (linv) at theta; rect: also Kuf (sgKuf) and A = Lu^-1 Kuf (sgA).  The verdict of Kuu in vinfo() 0
+  int svgp_begin(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, const char* who, bool rect) {
+    int rc = svgp_need_z(who);
+    if (rc) return rc;
+    if (!(p > 0.0)) return ctx->fail(GPSO_E_ARG, "likelihood parameter %g must be positive", p);
+    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
+    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    for (int k = 0; k < n_ls_; ++k)
+      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
+    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    if ((rc = vgp_begin())) return rc;
+    sg_factors = false;
+    if ((rc = svgp_q())) return rc;
+    if (rect) {
+      const size_t rect_b = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
+      for (DevBuf* b : {&sgKuf, &sgA, &svB, &svD})
+        if ((rc = ensure(*b, rect_b))) return rc;
+      for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
+        if ((rc = ensure(*b, sq))) return rc;
+      if ((rc = ensure(sgPart, sq * svgp_nsplit()))) return rc;
+      if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
+      if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
+      if ((rc = ensure(svvecN, (size_t)kSvVecsN * sg_npad * 8))) return rc;
+      if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
+      if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
+      if ((rc = ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8))) return rc;
+    }
+    hipStream_t s = st();
+    vgp_reset_info();
+    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
+    if (!rect) return GPSO_OK;
+    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
+    launch_sgpr_cross_gram(s, as<double>(xs64), as<double>(sgXs), n, npad, sg_n, sg_npad, dp, kp, as<double>(sgKuf));
+    launch_dgemm_rect(s, as<double>(linv), npad, 1, as<double>(sgKuf), sg_npad, 1, as<double>(sgA), sg_npad, npad, sg_npad,
+                      npad, 1.0, 0.0);  // A = Lu^-1 Kuf
+    return GPSO_OK;
+  }
+
+  // the moments of q(f) at the training points (fm = A^T mu + c; fv = variance - |A_j|^2 + |S^T A_j|^2 when want_v) and
+  // the per-point terms of the likelihood there: gm, a = -2 dVE/dv, t = gm + a (fm - c), VE, dVE/dp (closed form for the
+  // Gaussian -- gauss -- else the VGP's Gauss-Hermite kernel)
+  void svgp_pointwise(double variance, double p, double mean_c, bool want_v, bool gauss) {
+    hipStream_t s = st();
+    double *A = as<double>(sgA), *B = want_v ? as<double>(svB) : nullptr;
+    if (want_v)
+      launch_dgemm_rect(s, as<double>(svq_S), 1, npad, A, sg_npad, 1, B, sg_npad, npad, sg_npad, npad, 1.0, 0.0);  // S^T A
+    launch_svgp_moments(s, A, B, as<double>(svq_mu), variance, mean_c, svn_at(kSvM), svn_at(kSvV), n, sg_n, sg_npad);
+    if (gauss)
+      launch_svgp_gauss(s, as<double>(sgY), svn_at(kSvM), svn_at(kSvV), p, mean_c, svn_at(kSvGm), svn_at(kSvA), svn_at(kSvT),
+                        svn_at(kSvVe), svn_at(kSvDve), sg_n, sg_npad);
+    else
+      launch_vgp_quad(s, as<double>(sgY), svn_at(kSvM), svn_at(kSvV), as<double>(vgh), vlik_n_gh, vlik_kind, p, vlik_df,
+                      vlik_const(p), mean_c, svn_at(kSvGm), svn_at(kSvA), svn_at(kSvT), svn_at(kSvVe), svn_at(kSvDve), sg_n,
+                      sg_npad);
+  }
+
+  // P = A diag(a) A^T (into aat) and I + P (into lam, identity padding): the long-K product in its fixed split-K order
+  void svgp_adat(double* aat, double* lam) {
+    hipStream_t s = st();
+    const int ns = svgp_nsplit();
+    launch_svgp_colscale(s, as<double>(sgA), svn_at(kSvA), as<double>(svD), n, npad, sg_n, sg_npad);  // D = A diag(a)
+    launch_dgemm_rect(s, as<double>(sgA), sg_npad, 1, as<double>(svD), 1, sg_npad, as<double>(sgPart), npad, npad, npad,
+                      sg_npad, 1.0, 0.0, ns);
+    launch_sgpr_splitk_sum(s, as<double>(sgPart), ns, n, npad, aat, lam, nullptr);
+  }
+
+  // one natural-gradient step on q (gamma in (0, 1]): Lambda* = I + A diag(a) A^T, h* = A t at the current q, then the
+  // VGP's mixing and natural_to_meanvarsqrt at size M.  conj: the Gaussian step at noise variance p whatever the likelihood
+  // (the conjugate start).  The new q is built in scratch and committed only when every factorisation held: a failed
+  // step returns GPSO_E_NOTPD with q exactly as it was, for every likelihood.
+  int svgp_step(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double gamma, bool conj,
+                const char* who) {
+    if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
+    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, who, true);
+    if (rc) return rc;
+    hipStream_t s = st();
+    const bool gauss = conj || vlik_kind == GPSO_LIK_GAUSSIAN;
+    svgp_pointwise(variance, p, mean_c, !gauss, gauss);  // (the Gaussian's a and t do not depend on fv)
+    svgp_adat(as<double>(sgM1), as<double>(vA));          // Lambda* in vA
+    launch_sgpr_gemv(s, as<double>(sgA), false, svn_at(kSvT), 1.0, vvec_at(kVgpH), n, npad, sg_n, sg_npad);  // h* = A t
+    double *mu_out = sgm_at(kSgMu), *S_out = as<double>(K);
+    if ((rc = vgp_natural_update(as<double>(svq_mu), as<double>(svq_S), gamma, mu_out, S_out))) return rc;
+    double* host;
+    if ((rc = vgp_finish(&host, 2))) return rc;
+    HIPCHECK(hipMemcpyAsync(svq_mu.p, mu_out, (size_t)npad * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(hipMemcpyAsync(svq_S.p, S_out, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(ctx->wait(s));
+    return launch_status();
+  }
+
+  int svgp_natgrad(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double gamma) override {
+    return svgp_step(kernel, ls, n_ls_, variance, p, mean_c, gamma, false, "gpso_svgp_natgrad");
+  }
+
+  int svgp_init_q(int kernel, const double* ls, int n_ls_, double variance, double mean_c, double s2) override {
+    if (s2 > 0.0) return svgp_step(kernel, ls, n_ls_, variance, s2, mean_c, 1.0, true, "gpso_svgp_init_q");
+    int rc = svgp_need_z("gpso_svgp_init_q");
+    if (rc || (rc = vgp_begin()) || (rc = svgp_q())) return rc;
+    svgp_prior();
+    HIPCHECK(ctx->wait(st()));
+    return launch_status();
+  }
+
+  int svgp_set_q(const double* mu, const double* S, int64_t m) override {
+    int rc = svgp_need_z("gpso_svgp_set_q");
+    if (rc) return rc;
+    if (m != n) return ctx->fail(GPSO_E_ARG, "q of %lld inducing values for %lld inducing points", (long long)m, (long long)n);
+    if ((rc = vgp_begin()) || (rc = svgp_q())) return rc;
+    hipStream_t s = st();
+    if (mu == nullptr || S == nullptr) {
+      svgp_prior();
+      HIPCHECK(ctx->wait(s));
+      return launch_status();
+    }
+    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
+    double* tmp = as<double>(getter_tmp);
+    HIPCHECK(hipMemcpyAsync(tmp, S, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(svq_mu.p, 0, (size_t)npad * 8, s));
+    HIPCHECK(hipMemcpyAsync(svq_mu.p, mu, (size_t)n * 8, hipMemcpyHostToDevice, s));
+    launch_vgp_pad_identity(s, as<double>(svq_S), 0, npad, nullptr);
+    launch_convert_in<double>(s, tmp, as<double>(svq_S), n, n, npad);
+    launch_vgp_clean_lower(s, as<double>(svq_S), as<double>(svq_S), n, npad, 1.0);
+    HIPCHECK(hipStreamSynchronize(s));  // (the caller's host buffers are free again on return)
+    return launch_status();
+  }
+
+  int svgp_get_q(double* mu, double* S) override {
+    int rc = svgp_need_z("gpso_svgp_get_q");
+    if (rc || (rc = refuse_if_async("gpso_svgp_get_q")) || (rc = svgp_q())) return rc;
+    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
+    double* tmp = as<double>(getter_tmp);
+    hipStream_t s = st();
+    if (S) {
+      launch_convert_out<double>(s, as<double>(svq_S), npad, tmp, n, n, 0);
+      HIPCHECK(hipMemcpyAsync(S, tmp, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (mu) HIPCHECK(hipMemcpyAsync(mu, svq_mu.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return launch_status();
+  }
+
+  // -ELBO = -sum VE + KL(q || N(0, I)) at fixed q and its gradient in the constrained theta: grad[n_ls + 3] = (ls...,
+  // variance, p, c).  With Abar = dELBO/dA = mu gm^T - (Sigma - I) A diag(a):  dELBO/dKuf = Lu^-T Abar = g + a' gm^T
+  // (g = Lu^-T (I - Sigma) A diag(a), a' = Lu^-T mu), contracted tile by tile; d(-ELBO)/dLu = tril(Lu^-T Abar A^T) =
+  // tril(T P + a' (A gm)^T) (T = Lu^-T (I - Sigma), P = A diag(a) A^T), taken to Kuu through the VGP's Cholesky backward
+  // pass and the fit's contraction; the k_diag term sum dVE/dv = -sum a / 2 joins the variance.
+  int svgp_elbo(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double* loss,
+                double* grad) override {
+    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, "gpso_svgp_elbo_u", true);
+    if (rc) return rc;
+    hipStream_t s = st();
+    double *Sq = as<double>(svq_S), *mu = as<double>(svq_mu), *A = as<double>(sgA), *Li = as<double>(linv);
+    svgp_pointwise(variance, p, mean_c, true, vlik_kind == GPSO_LIK_GAUSSIAN);
+    launch_vgp_rownorm(s, Sq, sgm_at(kSgRows), n, npad);
+    launch_svgp_sums(s, svn_at(kSvVe), svn_at(kSvDve), svn_at(kSvGm), svn_at(kSvA), sg_n, mu, sgm_at(kSgRows), Sq, n, npad,
+                     as<double>(sgsmall));
+    if (grad) {
+      double *P = as<double>(sgM1), *Sig = as<double>(sgM2), *T = as<double>(vC), *X1 = as<double>(vA), *X2 = as<double>(vB);
+      svgp_adat(P, as<double>(sgM3));                                   // P = A diag(a) A^T; D = A diag(a) in svD
+      launch_dgemm(s, Sq, false, Sq, true, Sig, npad, 1.0, 0.0);        // Sigma
+      launch_vgp_pad_identity(s, X2, 0, npad, nullptr);
+      launch_vgp_axpby(s, Sig, X2, npad * npad, -1.0, 1.0);             // I - Sigma
+      launch_dgemm(s, Li, true, X2, false, T, npad, 1.0, 0.0);          // T = Lu^-T (I - Sigma)
+      launch_dgemm_rect(s, T, npad, 1, as<double>(svD), sg_npad, 1, as<double>(svB), sg_npad, npad, sg_npad, npad, 1.0,
+                        0.0);                                           // g = T A diag(a)
+      launch_vgp_gemv(s, Li, true, mu, 0.0, 1.0, 0.0, nullptr, sgm_at(kSgAvec), n, npad);  // a' = Lu^-T mu
+      launch_sgpr_cross_grad(s, as<double>(svB), sgm_at(kSgAvec), svn_at(kSvGm), as<double>(xs64), as<double>(sgXs), n, npad,
+                             sg_n, sg_npad, dp, n_ls, ls_dev(), kp, as<double>(sggpart), as<double>(sgsmall) + kSgGradAt);
+      launch_sgpr_gemv(s, A, false, svn_at(kSvGm), -1.0, sgm_at(kSgAe), n, npad, sg_n, sg_npad);  // -A gm
+      launch_dgemm(s, T, false, P, false, X1, npad, 1.0, 0.0);          // T P
+      launch_vgp_lbar(s, X1, sgm_at(kSgAvec), sgm_at(kSgAe), n, npad, 1.0);  // Lbar = tril(T P + a' (A gm)^T)
+      launch_dgemm(s, as<double>(Lf), true, X1, false, T, npad, 1.0, 0.0);  // Lu^T Lbar
+      launch_vgp_phi_sym(s, T, X2, n, npad);                            // M = Phi + Phi^T
+      launch_dgemm(s, X2, false, Li, false, X1, npad, 1.0, 0.0);        // M Lu^-1
+      launch_dgemm(s, Li, true, X1, false, T, npad, 1.0, 0.0);          // 2 Kbar = Lu^-T M Lu^-1
+      HIPCHECK(hipMemsetAsync(sgm_at(kSgZero), 0, (size_t)npad * 8, s));
+      launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
+                              T, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
+    }
+    double* host;
+    if ((rc = vgp_finish(&host, 2))) return rc;
+    double guu[kGradMaxLs + 1];
+    for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
+    double* h = ctx->pinned_scratch(kSgSmall);
+    if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(ctx->wait(s));
+    *loss = -h[0] + 0.5 * (h[5] + h[4] - (double)n - h[6]);
+    if (grad) {
+      // the Kuu contraction is of -ELBO, the cross one of the ELBO; k_diag: d(-ELBO)/dvariance = -sum dVE/dv = sum a / 2
+      for (int k = 0; k <= n_ls; ++k) grad[k] = guu[k] - h[kSgGradAt + k];
+      grad[n_ls] += 0.5 * h[3];
+      grad[n_ls + 1] = -h[1];
+      grad[n_ls + 2] = -h[2];
+    }
+    return GPSO_OK;
+  }
+
+  // install the predictive over the rows Z: the VGP's install with L := Lu and q := the SVGP's q (C = sqrt(1 + delta) R
+  // Lu^-1 with I - S S^T / (1 + delta) = R^T R, beta = Lu^-T mu, noise := the likelihood's variance + delta variance)
+  int svgp_posterior(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c,
+                     double* delta_out) override {
+    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, "gpso_svgp_posterior", false);
+    if (rc) return rc;
+    hipStream_t s = st();
+    double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
+    launch_vgp_gemv(s, Li, true, as<double>(svq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
+    double shift = 0.0;
+    if ((rc = vgp_shifted_root(&shift, false, as<double>(svq_S)))) return rc;  // G of J (I - Sigma / (1 + delta)) J
+    launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);                         // R
+    launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R Lu^-1
+    HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
+    const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? p * p * vlik_df / (vlik_df - 2.0) : p;
+    if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
+    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
+    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
+    small_tile_rows = 8;
+    chol_valid = true;  // (the split pieces are packed from linv)
+    if ((rc = pack_bf16())) return rc;
+    double* host;
+    if ((rc = vgp_finish(&host, 2))) {
+      chol_valid = false;
+      return rc;
+    }
+    if (delta_out) *delta_out = shift;
+    have_post = linv_p_valid = vgp_post = sgpr_post = svgp_post = true;
     return GPSO_OK;
   }
 
@@ -3761,6 +4059,62 @@ int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, in
   int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
   return ctx->eng->sgpr_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
+}
+
+// ---- sparse variational GP on inducing points (theta from u as the VGP's: vgp_theta) ------------------------------------
+int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double noise_variance) {
+  ENTER();
+  if (!(noise_variance > 0.0)) return ctx->eng->svgp_init_q(0, nullptr, 0, 0.0, 0.0, 0.0);  // the prior
+  double th[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->svgp_init_q(kernel, th, n_ls, th[n_ls], th[n_ls + 2], noise_variance);
+}
+
+int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m) {
+  ENTER();
+  if ((mu == nullptr) != (S == nullptr)) return ctx->fail(GPSO_E_ARG, "mu and S: both or neither");
+  return ctx->eng->svgp_set_q(mu, S, m);
+}
+
+int gpso_svgp_get_q(gpso_ctx* ctx, double* mu, double* S) {
+  ENTER();
+  return ctx->eng->svgp_get_q(mu, S);
+}
+
+int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      double gamma) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->svgp_natgrad(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], gamma);
+}
+
+int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                     double* loss, double* grad_u, double* theta_out) {
+  ENTER();
+  if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
+  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  if (theta_out)
+    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
+  rc = ctx->eng->svgp_elbo(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* delta_out) {
+  ENTER();
+  double th[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  return ctx->eng->svgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
 }
 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,

@@ -348,6 +348,17 @@ void launch_sgpr_sums(hipStream_t st, const double* lb, const double* aat, const
 // greedy conditional-variance selection of m rows of xs (scaled inputs, n rows): idx[m]; lg: m * npad doubles of scratch
 void launch_sgpr_greedy(hipStream_t st, const double* xs, int64_t n, int64_t npad, int dp, const KernParams& kp, int m,
                         double* lg, double* dvec, double* pivot, int64_t* idx);
+// ---- svgp.hip: sparse variational GP on inducing points (the [M_pad x N_pad] layout of sgpr.hip) -----------------------
+// fm = A^T mu + c, fv = variance - colnorm(A) + colnorm(B) (B nullable) over the n columns of an [m x npad] A, B
+void launch_svgp_moments(hipStream_t st, const double* A, const double* B, const double* mu, double variance, double c,
+                         double* fm, double* fv, int64_t m, int64_t n, int64_t npad);
+void launch_svgp_colscale(hipStream_t st, const double* A, const double* a, double* D, int64_t m, int64_t mpad, int64_t n,
+                          int64_t npad);
+void launch_svgp_gauss(hipStream_t st, const double* y, const double* fm, const double* fv, double s2, double c, double* gm,
+                       double* a, double* t, double* ve, double* dve, int64_t n, int64_t npad);
+constexpr int kSvgpSums = 7;
+void launch_svgp_sums(hipStream_t st, const double* ve, const double* dve, const double* gm, const double* a, int64_t n,
+                      const double* mu, const double* srow, const double* S, int64_t m, int64_t mpad, double* out);
 // ---- append.hip: rank-k append at fixed hyper-parameters ----------------------------------------------------------------
 // The posterior of the first n points is resident; k <= kAppendMax new points (already copied behind the old ones in
 // x64 / y64) extend L, L^-1, a, alpha, diag(K_y^-1), the NLML and the scaled inputs in place: two passes over L^-1

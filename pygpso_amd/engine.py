@@ -381,6 +381,63 @@ class HipGPEngine:
                                                   float(mean_c_fixed), C.byref(delta)))
         return delta.value
 
+    # -- sparse variational GP on inducing points (include/gpso_hip.h: gpso_svgp_*; Z from sgpr_set / select_inducing) -----
+    def svgp_init_q(self, kernel=None, u=None, n_ls=1, train_mean=False, mean_c_fixed=0.0, noise_variance=0.0):
+        """Start q: the prior (``noise_variance`` <= 0), or one Gaussian natural-gradient step of length 1 at that noise
+        variance and the theta of ``u`` (the conjugate start)."""
+        if not noise_variance > 0.0:
+            self._check(self._lib.gpso_svgp_init_q(self._h, 0, None, 0, 0, 0.0, 0.0))
+            return
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        self._check(self._lib.gpso_svgp_init_q(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                               float(mean_c_fixed), float(noise_variance)))
+
+    def svgp_set_q(self, mu=None, S=None):
+        """q(v) = N(mu, S S^T) over the M inducing values; None, None: the prior."""
+        if mu is None and S is None:
+            self._check(self._lib.gpso_svgp_set_q(self._h, None, None, self.n))
+            return
+        m = L.as_f64(np.asarray(mu).reshape(-1), (self.n,))
+        Sa = L.as_f64(np.asarray(S).reshape(self.n, self.n), (self.n, self.n))
+        self._check(self._lib.gpso_svgp_set_q(self._h, L.dptr(m), L.dptr(Sa), self.n))
+
+    def svgp_get_q(self):
+        """(mu [M], S [M, M]) of the SVGP's variational state on the device."""
+        m = np.empty(self.n, dtype=np.float64)
+        Sa = np.empty((self.n, self.n), dtype=np.float64)
+        self._check(self._lib.gpso_svgp_get_q(self._h, L.dptr(m), L.dptr(Sa)))
+        return m, Sa
+
+    def svgp_natgrad(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, gamma=1.0):
+        """One natural-gradient step of length ``gamma`` on the SVGP's q at the theta of ``u``."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        self._check(self._lib.gpso_svgp_natgrad(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                                float(mean_c_fixed), float(gamma)))
+
+    def svgp_elbo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
+        """-ELBO of the SVGP at fixed q and Z and its gradient in ``u``.  Returns (loss, grad_u or None, theta)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
+        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
+        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+        loss = C.c_double()
+        self._check(self._lib.gpso_svgp_elbo_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                               float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
+                                               L.dptr(ta)))
+        return loss.value, ga, ta
+
+    def svgp_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
+        """Install the SVGP predictive at the theta of ``u`` over the rows Z.  Returns the shift delta (0: exact)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        delta = C.c_double()
+        self._check(self._lib.gpso_svgp_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
+                                                  float(mean_c_fixed), C.byref(delta)))
+        return delta.value
+
     def set_posterior(self, X, Lchol, alpha, kernel, lengthscales, variance, noise, mean_c):
         X = L.as_f64(X)
         n, d = X.shape

@@ -31,6 +31,7 @@ from scipy.special import erfcinv
 from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero
 from .model import HipGPR
 from .sgpr import HipSGPR
+from .svgp import HipSVGP
 from .vgp import HipVGP, carried_order
 from .utils import JSON_EXT, PointLabels
 
@@ -769,3 +770,140 @@ class VGPSurrogate(GPSurrogate):
                    optimiser=cls._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
                    points=points, gpflow_model=model, natgrad_learning_rate=info["vgp_natgrad_lr"],
                    train_iterations=info["vgp_iters"], dtype=dtype, device=device)
+
+
+SVGP_TRAIN_ITERATIONS = 10
+
+
+class SVGPSurrogate(GPSurrogate):
+    """Sparse variational GP surrogate on inducing points (GPflow's ``SVGP``, whitened, full ``q_sqrt``, full batch):
+    the Student-t likelihood of ``VGPSurrogate`` at the scale of ``SGPRSurrogate`` -- an update costs O(N M^2) per
+    natural-gradient step or -ELBO evaluation, a leaf-UCB prediction O(M^2), whatever the number N of evaluated points.
+
+    Each ``_gp_train`` chooses Z as ``SGPRSurrogate`` does (the data itself while N <= M, else the greedy conditional-
+    variance selection at the current kernel hyper-parameters, or an array used as given), starts q (the prior under the
+    Gaussian likelihood; under the Student-t the conjugate start, one Gaussian natural-gradient step at the noise variance
+    scale^2 df / (df - 2)), then runs ``train_iterations`` times one natural-gradient step on q and one step of the
+    hyper-parameter optimiser on -ELBO at fixed q (``HipSVGP``).  An indefinite natural-gradient step raises
+    ``numpy.linalg.LinAlgError`` and leaves q as it was (GPflow's behaviour); gamma of about 0.1 is the usual choice for
+    the Student-t."""
+
+    def __init__(self, gp_kernel, gp_meanf=None, likelihood=None, num_inducing=256, inducing="greedy",
+                 natgrad_learning_rate=1.0, train_iterations=SVGP_TRAIN_ITERATIONS, optimiser=None,
+                 varsigma=erfcinv(0.01), points=None, gpflow_model=None, dtype="float64", device=0, engine_options=None):
+        """
+        :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``; any other
+            likelihood raises NotImplementedError
+        :param num_inducing: M (ignored when ``inducing`` is an array)
+        :param inducing: "greedy" or an [M, D] array of normed coordinates used as given
+        :param natgrad_learning_rate: step length gamma in (0, 1] of the natural gradient
+        :param train_iterations: natgrad / optimiser iterations per ``_gp_train``
+        :param optimiser: hyper-parameter optimiser, default ``Adam(0.01)`` (its moments persist across updates), or
+            ``Scipy()``
+        :param dtype: "float64" (default) or "mixed" (float64 training, float predict arithmetic); "float32" raises
+        """
+        likelihood = likelihood if likelihood is not None else Gaussian(1.0e-3)
+        if not isinstance(likelihood, (Gaussian, StudentT)):
+            raise NotImplementedError(f"{type(likelihood).__name__}: only the Gaussian and Student-t likelihoods are supported")
+        gamma = float(natgrad_learning_rate)
+        if not (0.0 < gamma <= 1.0):
+            raise ValueError(f"natgrad_learning_rate {gamma} outside (0, 1]")
+        if dtype not in ("float64", "mixed"):
+            raise ValueError(f"SVGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
+        if isinstance(inducing, str):
+            if inducing != "greedy":
+                raise ValueError(f"inducing must be 'greedy' or an [M, D] array, not {inducing!r}")
+            if int(num_inducing) < 1:
+                raise ValueError(f"num_inducing={num_inducing}: need at least one inducing point")
+        else:
+            inducing = np.ascontiguousarray(inducing, dtype=np.float64)
+            if inducing.ndim != 2 or inducing.shape[0] < 1 or not np.all(np.isfinite(inducing)):
+                raise ValueError("inducing must be a finite [M, D] array with M >= 1")
+            num_inducing = inducing.shape[0]
+        super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf,
+                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma,
+                         points=points, gpflow_model=gpflow_model, dtype=dtype, device=device,
+                         engine_options=engine_options)
+        self.likelihood = likelihood
+        self.num_inducing = int(num_inducing)
+        self.inducing = inducing
+        self.natgrad_gamma = gamma
+        self.train_iters = int(train_iterations)
+
+    def _gp_train(self, x, y):
+        assert x.shape[0] == y.shape[0]
+        assert x.ndim == 2 and y.ndim == 2
+        if self.gpflow_model is None:
+            self.gpflow_model = HipSVGP(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
+                                        likelihood=self.likelihood, num_inducing=self.num_inducing,
+                                        inducing=self.inducing, dtype=self.dtype, device=self.device,
+                                        engine_options=self.engine_options)
+        else:
+            self.gpflow_model.data = (x, y)  # Z chosen again at the current hyper-parameters
+        model = self.gpflow_model
+        model.start_q()
+        for i in range(self.train_iters):
+            model.natgrad(self.natgrad_gamma)
+            self.optimiser.minimize(model.training_loss, model.trainable_variables)
+            if logging.getLogger().isEnabledFor(logging.DEBUG):
+                logging.debug(f"SVGP iteration {i + 1}. ELBO: {model.elbo():.04f}")
+
+    # -- persistence: the VGP's schema plus the SGPR's num_inducing, policy and Z ---------------------
+    def save(self, folder):
+        os.makedirs(folder, exist_ok=True)
+        self.points.save(os.path.join(folder, self.POINTS_FILE))
+        model = self.gpflow_model
+        params = {k: np.asarray(v).tolist() for k, v in model.parameter_dict().items()}
+        with open(os.path.join(folder, self.GPR_FILE), "w") as fh:
+            fh.write(json.dumps(params))
+        info = {
+            "model": "SVGP",
+            "svgp_kernel": model.kernel.name,
+            "svgp_kernel_shape": list(np.shape(model.kernel.lengthscales)),
+            "svgp_meanf": type(model.mean_function).__name__,
+            "svgp_likelihood": self.likelihood.name,
+            "gp_varsigma": self.gp_varsigma,
+            "optimiser": VGPSurrogate._serialise_optimiser(self),
+            "svgp_iters": self.train_iters,
+            "svgp_natgrad_lr": self.natgrad_gamma,
+            "num_inducing": self.num_inducing,
+            "inducing": "greedy" if isinstance(self.inducing, str) else "given",
+            "dtype": self.dtype,
+        }
+        if isinstance(self.likelihood, StudentT):
+            info["svgp_likelihood_df"] = model.likelihood.df
+        with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
+            fh.write(json.dumps(info))
+
+    @classmethod
+    def from_saved(cls, folder, device=0):
+        points = GPListOfPoints.from_file(os.path.join(folder, cls.POINTS_FILE))
+        ev = [p for p in points if p.label == PointLabels.evaluated]
+        x = np.array([p.normed_coord for p in ev])
+        y = np.array([p.score_mu for p in ev])[:, np.newaxis]
+        with open(os.path.join(folder, cls.GPR_INFO)) as fh:
+            info = json.load(fh)
+        with open(os.path.join(folder, cls.GPR_FILE)) as fh:
+            params = json.load(fh)
+        assert info.get("model") == "SVGP", "not a saved SVGPSurrogate"
+        assert info["svgp_kernel"] in KERNEL_CLASSES
+        kernel = KERNEL_CLASSES[info["svgp_kernel"]](
+            lengthscales=np.array(params[".kernel.lengthscales"]), variance=params[".kernel.variance"])
+        meanf = Constant(params[".mean_function.c"]) if info["svgp_meanf"] == "Constant" else Zero()
+        if info["svgp_likelihood"] == "StudentT":
+            likelihood = StudentT(params[".likelihood.scale"], info.get("svgp_likelihood_df", 3.0))
+        elif info["svgp_likelihood"] == "Gaussian":
+            likelihood = Gaussian(params[".likelihood.variance"])
+        else:
+            raise NotImplementedError(f"{info['svgp_likelihood']}: only the Gaussian and Student-t likelihoods are supported")
+        z = np.array(params[".inducing_variable.Z"], dtype=np.float64).reshape(-1, x.shape[1])
+        inducing = z if info["inducing"] == "given" else "greedy"
+        dtype = info.get("dtype", "float64")
+        model = HipSVGP(data=(x, y), kernel=kernel, mean_function=meanf, likelihood=likelihood,
+                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device)
+        model.set_inducing(z)  # the Z the saved q belongs to (the next update chooses again)
+        model.set_q(np.array(params[".q_mu"]), np.array(params[".q_sqrt"]))
+        return cls(gp_kernel=kernel, gp_meanf=meanf, likelihood=likelihood, num_inducing=info["num_inducing"],
+                   inducing=inducing, natgrad_learning_rate=info["svgp_natgrad_lr"], train_iterations=info["svgp_iters"],
+                   optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
+                   points=points, gpflow_model=model, dtype=dtype, device=device)
