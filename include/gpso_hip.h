@@ -279,7 +279,8 @@ int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
 int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed);
 
 /* ---- sparse GP regression on inducing points (no counterpart in the reference: gpflow.models.SGPR, Titsias 2009) -------
- * GPflow 2's SGPR, Gaussian likelihood, with M fixed inducing points Z summarising the N resident training rows:
+ * GPflow 2's SGPR, Gaussian likelihood, with M inducing points Z summarising the N resident training rows (fixed in the
+ * calls of this block; the block "at a moving Z" below trains them):
  * Kuu = k(Z, Z) + 1e-6 I, Lu = chol Kuu, A = Lu^-1 k(Z, X) / sigma, B = I + A A^T, LB = chol B, cv = LB^-1 A (y - c) / sigma;
  * training costs O(N M^2), a prediction O(M^2) whatever N.  u, n_ls, train_mean, mean_c_fixed: as
  * gpso_fit_eval_u (s2 = 1e-6 + softplus(u[n_ls + 1])).  float64 throughout: GPSO_F64 and GPSO_MIXED contexts (GPSO_F32:
@@ -366,6 +367,35 @@ int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
  * the installed form as after gpso_sgpr_posterior, and gpso_append returns GPSO_E_STATE. */
 int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out);
+
+/* ---- the sparse models at a moving Z: training the inducing points (GPflow's default: inducing_variable.Z trainable) -----
+ * The entry points above keep Z fixed; these evaluate at a Z the optimiser moves, and return the gradient in it (DESIGN.md
+ * section 7d).  Z[M * D] (row-major; nullable: keep the resident Z) REPLACES THE RESIDENT INDUCING ROWS IN PLACE: same M, the
+ * training data buffers untouched, no allocation, no upload of X or y, and the SVGP's q kept (it is whitened: valid at any
+ * Z).  WHAT STAYS RESIDENT: the new Z -- gpso_sgpr_get_inducing returns it (n_data unchanged) and gpso_sgpr_bound_u,
+ * gpso_sgpr_posterior, gpso_svgp_natgrad, gpso_svgp_elbo_u and gpso_svgp_posterior then work at it; whatever posterior was
+ * resident is replaced, as by the fixed-Z evaluations.  With Z = NULL, or Z equal to the resident rows, *loss and grad_u are
+ * bit for bit those of the fixed-Z entry point; the same call gives the same bits (fixed-order reductions, no atomics).
+ * grad_z (nullable) [M * D] = d loss / d Z:  with zs = Z / l, xs = X / l, k' = dk/dr^2, Vc = dF/dKuf (.) k'(Z, X) and
+ * Vu = 2 dF/dKuu (.) k'(Z, Z) (diagonal 0),  dF/dZ[m, d] = (2 / l_d) (zs[m, d] (rowsum Vc + rowsum Vu)[m] - (Vc xs + Vu zs)[m, d]).
+ * COINCIDENT PAIRS: a pair with r^2 <= 1e-36 (a row of Z equal to a row of X, or to another row of Z) contributes zero, as
+ * in GPflow; that is the exact derivative for the Matern-3/2, -5/2 and the squared exponential, and the convention at the
+ * Matern-1/2's kink.
+ * ERRORS: a call rejected for its arguments or its place in the sequence -- before Z is set: GPSO_E_STATE; a GPSO_F32
+ * context, a non-finite value in Z, a non-positive hyper-parameter: GPSO_E_ARG -- leaves the context as it was, the
+ * resident Z included.  GPSO_E_NOTPD names the matrix and the pivot as the fixed-Z calls do (two rows of Z collapsing onto
+ * each other can make Kuu singular beyond the 1e-6 jitter); the new Z is resident then. */
+
+/* Replace the resident inducing rows by Z[M * D] and evaluate nothing. */
+int gpso_sgpr_move_inducing(gpso_ctx* ctx, const double* Z);
+/* gpso_sgpr_bound_u at Z, and the gradient of the loss in Z. */
+int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                       const double* Z /* [M*D], nullable */, double* loss, double* grad_u,
+                       double* grad_z /* [M*D], nullable */, double* theta_out);
+/* gpso_svgp_elbo_u at Z (q fixed), and the gradient of the loss in Z. */
+int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      const double* Z /* [M*D], nullable */, double* loss, double* grad_u,
+                      double* grad_z /* [M*D], nullable */, double* theta_out);
 
 /* ---- predict (gpflow_model.predict_y users) ----------------------------------------------- */
 

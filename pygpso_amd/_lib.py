@@ -98,6 +98,11 @@ SIGNATURES = {
     "gpso_sgpr_bound_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_sgpr_posterior": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p]),
+    "gpso_sgpr_move_inducing": (C.c_int, [C.c_void_p, _c_double_p]),
+    "gpso_sgpr_bound_uz": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_svgp_elbo_uz": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                    _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "gpso_svgp_init_q": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, C.c_double]),
     "gpso_svgp_set_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64]),
     "gpso_svgp_get_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),

@@ -136,6 +136,12 @@ struct Engine {
                          double* grad) = 0;
   virtual int sgpr_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c,
                              double* delta_out) = 0;
+  // ... and at a moving Z (inducing.hip): Z (nullable) replaces the resident inducing rows in place
+  virtual int sgpr_move_inducing(const double* Z) = 0;
+  virtual int sgpr_bound_z(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, const double* Z,
+                           double* loss, double* grad, double* grad_z) = 0;
+  virtual int svgp_elbo_z(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, const double* Z,
+                          double* loss, double* grad, double* grad_z) = 0;
   // sparse variational GP on inducing points (svgp.hip)
   virtual int svgp_init_q(int kernel, const double* ls, int n_ls, double variance, double mean_c, double s2) = 0;
   virtual int svgp_set_q(const double* mu, const double* S, int64_t m) = 0;
@@ -1676,6 +1682,7 @@ struct EngineT : Engine {
   // buffers and kernels at size M_pad exactly as the VGP's do at N_pad, the installed predictive is a posterior over the M
   // rows Z that every predict path serves, and the rectangular [M_pad x N_pad] work lives in sgKuf / sgA / sgW.
   DevBuf sgX, sgY, sgXs, sgXn, sgKuf, sgA, sgW, sgPart, sgM1, sgM2, sgM3, sgvecN, sgvecM, sgsmall, sggpart, sgidx;
+  DevBuf sgZpart, sgZg;  // the moving-Z evaluations' slice partials and dF/dZ [M x D] (inducing.hip)
   std::vector<double> sg_xh;  // host mirror of the training inputs (the rows greedy selection gathers Z from)
   int64_t sg_n = 0, sg_npad = 0;
   bool sg_have = false, sg_have_z = false, sg_keep = false;
@@ -1851,8 +1858,15 @@ struct EngineT : Engine {
 
   int sgpr_bound(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss,
                  double* grad) override {
-    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, "gpso_sgpr_bound_u");
+    return sgpr_bound_impl(kernel, ls, n_ls_, variance, s2, mean_c, loss, grad, nullptr, "gpso_sgpr_bound_u");
+  }
+
+  // grad_z (nullable, with grad): also d(-F)/dZ [M * D], from the weights the theta gradient has just formed
+  int sgpr_bound_impl(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss,
+                      double* grad, double* grad_z, const char* who) {
+    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, who);
     if (rc) return rc;
+    if (grad_z && (rc = inducing_buffers())) return rc;
     hipStream_t s = st();
     const double b = 1.0 / s2;
     double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *AAT = as<double>(vA), *T1 = as<double>(vB), *LB = as<double>(vC);
@@ -1877,6 +1891,11 @@ struct EngineT : Engine {
       launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
                               M1, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
       launch_vgp_rownorm(s, LBi, sgm_at(kSgRows), n, npad);
+      // dF/dKuf = G1 Kuf + a t^T is of F, dF/dKuu = -M1 / 2 of F: the loss takes the cross part with -1, the Kuu part with +1
+      if (grad_z && (rc = launch_inducing_grad(s, as<double>(sgW), sgm_at(kSgAvec), sgn_at(kSgT), M1, as<double>(xs64),
+                                               as<double>(sgXs), n, npad, sg_n, sg_npad, d, dp, ls_dev(), kp, -1.0, 1.0,
+                                               as<double>(sgZpart), as<double>(sgZg))))
+        return rc;
     }
     launch_sgpr_sums(s, LB, AAT, sgm_at(kSgCv), sgn_at(kSgE), grad ? sgn_at(kSgW) : nullptr, grad ? sgm_at(kSgRows) : nullptr, n,
                      npad, sg_n, as<double>(sgsmall));
@@ -1887,6 +1906,7 @@ struct EngineT : Engine {
     double* h = ctx->pinned_scratch(kSgSmall);
     if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
+    if (grad && grad_z) HIPCHECK(hipMemcpyAsync(grad_z, sgZg.p, (size_t)n * d * 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(ctx->wait(s));
     const double N = (double)sg_n, M = (double)n;
     const double F = -0.5 * N * std::log(2.0 * M_PI) - h[0] - 0.5 * N * std::log(s2) - 0.5 * b * h[1] + 0.5 * h[2] -
@@ -2126,8 +2146,16 @@ struct EngineT : Engine {
   // pass and the fit's contraction; the k_diag term sum dVE/dv = -sum a / 2 joins the variance.
   int svgp_elbo(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double* loss,
                 double* grad) override {
-    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, "gpso_svgp_elbo_u", true);
+    return svgp_elbo_impl(kernel, ls, n_ls_, variance, p, mean_c, loss, grad, nullptr, "gpso_svgp_elbo_u");
+  }
+
+  // grad_z (nullable, with grad): also d(-ELBO)/dZ [M * D] at fixed q (whitened: q stays valid while Z moves; the k_diag
+  // term does not depend on Z)
+  int svgp_elbo_impl(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double* loss,
+                     double* grad, double* grad_z, const char* who) {
+    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, who, true);
     if (rc) return rc;
+    if (grad_z && (rc = inducing_buffers())) return rc;
     hipStream_t s = st();
     double *Sq = as<double>(svq_S), *mu = as<double>(svq_mu), *A = as<double>(sgA), *Li = as<double>(linv);
     svgp_pointwise(variance, p, mean_c, true, vlik_kind == GPSO_LIK_GAUSSIAN);
@@ -2156,6 +2184,11 @@ struct EngineT : Engine {
       HIPCHECK(hipMemsetAsync(sgm_at(kSgZero), 0, (size_t)npad * 8, s));
       launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
                               T, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
+      // dELBO/dKuf = g + a' gm^T is of the ELBO, T = 2 d(-ELBO)/dKuu of the loss: -1 and +1 as in the SGPR
+      if (grad_z && (rc = launch_inducing_grad(s, as<double>(svB), sgm_at(kSgAvec), svn_at(kSvGm), T, as<double>(xs64),
+                                               as<double>(sgXs), n, npad, sg_n, sg_npad, d, dp, ls_dev(), kp, -1.0, 1.0,
+                                               as<double>(sgZpart), as<double>(sgZg))))
+        return rc;
     }
     double* host;
     if ((rc = vgp_finish(&host, 2))) return rc;
@@ -2164,6 +2197,7 @@ struct EngineT : Engine {
     double* h = ctx->pinned_scratch(kSgSmall);
     if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
+    if (grad && grad_z) HIPCHECK(hipMemcpyAsync(grad_z, sgZg.p, (size_t)n * d * 8, hipMemcpyDeviceToHost, s));
     HIPCHECK(ctx->wait(s));
     *loss = -h[0] + 0.5 * (h[5] + h[4] - (double)n - h[6]);
     if (grad) {
@@ -2205,6 +2239,77 @@ struct EngineT : Engine {
     if (delta_out) *delta_out = shift;
     have_post = linv_p_valid = vgp_post = sgpr_post = svgp_post = true;
     return GPSO_OK;
+  }
+
+  // ---- the sparse models at a moving Z (inducing.hip) ---------------------------------------------
+  // Z replaces the resident inducing rows IN PLACE: same M, the training data buffers untouched, no allocation, no upload
+  // of X or y, the SVGP's q kept (it is whitened: valid at any Z).  Everything that could refuse the call is checked
+  // before the rows are touched, so a rejected call leaves the context as it was.
+  int inducing_buffers() {
+    int rc = ensure(sgZpart, (size_t)(inducing_slices(npad, sg_npad) + 1) * npad * (dp + 1) * 8);
+    if (rc) return rc;
+    return ensure(sgZg, (size_t)n * d * 8);
+  }
+  int inducing_args(const char* who, const double* Z) {
+    int rc = sgpr_need_f64();
+    if (rc) return rc;
+    if (!sg_have || !sg_have_z)
+      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
+    if ((rc = refuse_if_async(who))) return rc;
+    if (Z)
+      for (int64_t e = 0; e < n * (int64_t)d; ++e)
+        if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
+    return GPSO_OK;
+  }
+  int inducing_theta_args(int kernel, const double* ls, int n_ls_, double variance, double p, const char* what_p) {
+    if (!(p > 0.0)) return ctx->fail(GPSO_E_ARG, "%s %g must be positive", what_p, p);
+    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
+    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    for (int k = 0; k < n_ls_; ++k)
+      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
+    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    return GPSO_OK;
+  }
+  int inducing_put(const double* Z) {
+    const size_t doubles = (size_t)n * d;
+    double* stage = doubles <= (1u << 17) ? ctx->pinned_stage(doubles) : nullptr;
+    if (stage) {
+      std::memcpy(stage, Z, doubles * 8);
+      HIPCHECK(hipMemcpyAsync(x64.p, stage, doubles * 8, hipMemcpyHostToDevice, st()));
+    } else {
+      HIPCHECK(hipMemcpyAsync(x64.p, Z, doubles * 8, hipMemcpyHostToDevice, st()));
+      HIPCHECK(hipStreamSynchronize(st()));
+    }
+    if (Z != x_host.data()) std::memcpy(x_host.data(), Z, doubles * 8);
+    // (whatever was built on the old rows is gone; the data, q and the likelihood stay)
+    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
+    sg_factors = false;
+    st_done = st_have = false;
+    forget_peers();
+    return GPSO_OK;
+  }
+
+  int sgpr_move_inducing(const double* Z) override {
+    if (!Z) return ctx->fail(GPSO_E_ARG, "Z must not be NULL");
+    int rc = inducing_args("gpso_sgpr_move_inducing", Z);
+    if (rc) return rc;
+    return inducing_put(Z);
+  }
+
+  int sgpr_bound_z(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, const double* Z,
+                   double* loss, double* grad, double* grad_z) override {
+    int rc = inducing_args("gpso_sgpr_bound_uz", Z);
+    if (rc || (rc = inducing_theta_args(kernel, ls, n_ls_, variance, s2, "noise variance"))) return rc;
+    if (Z && (rc = inducing_put(Z))) return rc;
+    return sgpr_bound_impl(kernel, ls, n_ls_, variance, s2, mean_c, loss, grad, grad_z, "gpso_sgpr_bound_uz");
+  }
+
+  int svgp_elbo_z(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, const double* Z,
+                  double* loss, double* grad, double* grad_z) override {
+    int rc = inducing_args("gpso_svgp_elbo_uz", Z);
+    if (rc || (rc = inducing_theta_args(kernel, ls, n_ls_, variance, p, "likelihood parameter"))) return rc;
+    if (Z && (rc = inducing_put(Z))) return rc;
+    return svgp_elbo_impl(kernel, ls, n_ls_, variance, p, mean_c, loss, grad, grad_z, "gpso_svgp_elbo_uz");
   }
 
   // ------------------------------------------------------------------------------------------
@@ -4115,6 +4220,46 @@ int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, in
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
   return ctx->eng->svgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
+}
+
+// ---- the sparse models at a moving Z ------------------------------------------------------------------------------------
+int gpso_sgpr_move_inducing(gpso_ctx* ctx, const double* Z) {
+  ENTER();
+  return ctx->eng->sgpr_move_inducing(Z);
+}
+
+int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                       const double* Z, double* loss, double* grad_u, double* grad_z, double* theta_out) {
+  ENTER();
+  if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
+  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
+  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  if (theta_out)
+    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
+  const bool want = grad_u || grad_z;
+  rc = ctx->eng->sgpr_bound_z(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], Z, loss, want ? g : nullptr, grad_z);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                      const double* Z, double* loss, double* grad_u, double* grad_z, double* theta_out) {
+  ENTER();
+  if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
+  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
+  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  if (rc) return rc;
+  if (theta_out)
+    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
+  const bool want = grad_u || grad_z;
+  rc = ctx->eng->svgp_elbo_z(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], Z, loss, want ? g : nullptr, grad_z);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
 }
 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,

@@ -359,6 +359,16 @@ void launch_svgp_gauss(hipStream_t st, const double* y, const double* fm, const 
 constexpr int kSvgpSums = 7;
 void launch_svgp_sums(hipStream_t st, const double* ve, const double* dve, const double* gm, const double* a, int64_t n,
                       const double* mu, const double* srow, const double* S, int64_t m, int64_t mpad, double* out);
+// ---- inducing.hip: the gradient of the sparse objectives in the inducing points -----------------
+// grad_z[m * d] = cc dFc/dZ + cu dFu/dZ: Fc's weights dF/dKuf = wc + a t^T ([mpad x npad], [mpad], [npad], the operands of
+// launch_sgpr_cross_grad), Fu's weights dF/dKuu = kin / 2 (lower triangle read, as launch_gradient reads its K^-1).
+// part: (inducing_slices(mpad, npad) + 1) * mpad * (dp + 1) doubles of scratch.  0, or a negative GPSO_E_* code.
+constexpr int kInducingSlicesLargeM = 16;  // slices of the N direction from M_pad = 1024 on
+constexpr int kInducingSlicesMax = 64;     // ... and at most, for a smaller M_pad (inducing_slices)
+int inducing_slices(int64_t mpad, int64_t npad);
+int launch_inducing_grad(hipStream_t st, const double* wc, const double* a, const double* t, const double* kin,
+                         const double* zs, const double* xs, int64_t m, int64_t mpad, int64_t n, int64_t npad, int d, int dp,
+                         const double* ls, const KernParams& kp, double cc, double cu, double* part, double* grad_z);
 // ---- append.hip: rank-k append at fixed hyper-parameters ----------------------------------------------------------------
 // The posterior of the first n points is resident; k <= kAppendMax new points (already copied behind the old ones in
 // x64 / y64) extend L, L^-1, a, alpha, diag(K_y^-1), the NLML and the scaled inputs in place: two passes over L^-1

@@ -438,6 +438,44 @@ class HipGPEngine:
                                                   float(mean_c_fixed), C.byref(delta)))
         return delta.value
 
+    # -- the sparse models at a moving Z (include/gpso_hip.h: gpso_sgpr_move_inducing, gpso_sgpr_bound_uz, gpso_svgp_elbo_uz) --
+    def _z_arg(self, Z):
+        if Z is None:
+            return None
+        Z = L.as_f64(np.asarray(Z).reshape(-1, self.d))
+        if Z.shape[0] != self.n:
+            raise ValueError(f"Z must be [{self.n}, {self.d}]: the resident inducing rows are replaced in place")
+        return Z
+
+    def sgpr_move_inducing(self, Z):
+        """Replace the resident inducing rows by Z [M, D] in place (same M; the data, and the SVGP's q, stay)."""
+        Z = self._z_arg(Z)
+        self._check(self._lib.gpso_sgpr_move_inducing(self._h, L.dptr(Z) if Z is not None else None))
+
+    def _eval_uz(self, fn, kernel, u, n_ls, train_mean, mean_c_fixed, Z, want_grad):
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))
+        Z = self._z_arg(Z)
+        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
+        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
+        gz = np.empty((self.n, self.d), dtype=np.float64) if want_grad else None
+        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+        loss = C.c_double()
+        self._check(fn(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0, float(mean_c_fixed),
+                       L.dptr(Z) if Z is not None else None, C.byref(loss), L.dptr(ga) if want_grad else None,
+                       L.dptr(gz) if want_grad else None, L.dptr(ta)))
+        return loss.value, ga, gz, ta
+
+    def sgpr_bound_uz(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, Z=None, want_grad=True):
+        """-bound at the inducing points Z [M, D] (None: the resident ones), which replace the resident rows in place,
+        and its gradient in ``u`` and in Z.  Returns (loss, grad_u or None, grad_z [M, D] or None, theta)."""
+        return self._eval_uz(self._lib.gpso_sgpr_bound_uz, kernel, u, n_ls, train_mean, mean_c_fixed, Z, want_grad)
+
+    def svgp_elbo_uz(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, Z=None, want_grad=True):
+        """-ELBO at fixed q and the inducing points Z [M, D] (None: the resident ones; q is kept), and its gradient in
+        ``u`` and in Z.  Returns (loss, grad_u or None, grad_z [M, D] or None, theta)."""
+        return self._eval_uz(self._lib.gpso_svgp_elbo_uz, kernel, u, n_ls, train_mean, mean_c_fixed, Z, want_grad)
+
     def set_posterior(self, X, Lchol, alpha, kernel, lengthscales, variance, noise, mean_c):
         X = L.as_f64(X)
         n, d = X.shape

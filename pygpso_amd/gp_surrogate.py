@@ -537,18 +537,23 @@ class SGPRSurrogate(GPSurrogate):
     """Sparse GP regression surrogate on inducing points (GPflow's ``SGPR``, Titsias 2009): M points Z summarise the N
     evaluated points, an update costs O(N M^2) per loss evaluation and every leaf-UCB prediction O(M^2) whatever N -- the
     surrogate for runs whose N outgrows the exact GPR.  While N <= M, Z is the data and the model is the exact GPR up to
-    GPflow's 1e-6 jitter on Kuu.  Z is not trained: each ``_gp_train`` chooses it again (``"greedy"``: the conditional-
-    variance selection on the device at the hyper-parameters the search starts from; or an array used as given) and
-    keeps it fixed while L-BFGS-B searches the hyper-parameters (``HipSGPR``)."""
+    GPflow's 1e-6 jitter on Kuu.  With ``train_inducing=False`` (the default) Z is not trained: each ``_gp_train`` chooses it
+    again (``"greedy"``: the conditional-variance selection on the device at the hyper-parameters the search starts from;
+    or an array used as given) and keeps it fixed while L-BFGS-B searches the hyper-parameters (``HipSGPR``).  With
+    ``train_inducing=True`` that choice only names where Z starts: once N > M, L-BFGS-B searches the hyper-parameters and
+    Z jointly (GPflow's default for ``SGPR``), and later updates warm-start from the trained Z without a selection."""
 
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3,
                  num_inducing=256, inducing="greedy", points=None, gpflow_model=None, dtype="float64", device=0,
-                 engine_options=None):
+                 engine_options=None, train_inducing=False):
         """
         :param gauss_likelihood_sigma: initial noise VARIANCE of the Gaussian likelihood (as ``GPRSurrogate``)
         :param num_inducing: M (ignored when ``inducing`` is an array)
         :param inducing: "greedy" or an [M, D] array of normed coordinates used as given
+        :param train_inducing: train Z beside the hyper-parameters once N > M (``inducing`` then names where Z starts)
         """
+        if not isinstance(train_inducing, (bool, np.bool_)):
+            raise TypeError(f"train_inducing must be True or False, not {train_inducing!r}")
         if dtype not in ("float64", "mixed"):
             raise ValueError(f"SGPR trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
         if isinstance(inducing, str):
@@ -566,13 +571,14 @@ class SGPRSurrogate(GPSurrogate):
         self.gp_lik_sigma = gauss_likelihood_sigma
         self.num_inducing = int(num_inducing)
         self.inducing = inducing
+        self.train_inducing = bool(train_inducing)
 
     @classmethod
-    def default(cls, num_inducing=256, dtype="float64", device=0, engine_options=None):
+    def default(cls, num_inducing=256, dtype="float64", device=0, engine_options=None, train_inducing=False):
         """``GPRSurrogate.default()``'s specification with M inducing points."""
         return cls(gp_kernel=Matern52(lengthscales=np.sum(NORM_PARAMS_BOUNDS) * 0.25, variance=1.0), gp_meanf=Constant(0.0),
                    optimiser=Scipy(), varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3, num_inducing=num_inducing,
-                   dtype=dtype, device=device, engine_options=engine_options)
+                   dtype=dtype, device=device, engine_options=engine_options, train_inducing=train_inducing)
 
     def _gp_train(self, x, y):
         assert x.shape[0] == y.shape[0]
@@ -581,9 +587,10 @@ class SGPRSurrogate(GPSurrogate):
             self.gpflow_model = HipSGPR(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
                                         noise_variance=self.gp_lik_sigma, num_inducing=self.num_inducing,
                                         inducing=self.inducing, dtype=self.dtype, device=self.device,
-                                        engine_options=self.engine_options)
+                                        engine_options=self.engine_options, train_inducing=self.train_inducing)
         else:
-            self.gpflow_model.data = (x, y)  # Z chosen again at the hyper-parameters the search warm-starts from
+            # Z chosen again at the hyper-parameters the search warm-starts from (or, trained, kept as it is)
+            self.gpflow_model.data = (x, y)
         self.optimiser.minimize(self.gpflow_model.training_loss, self.gpflow_model.trainable_variables)
 
     # -- persistence: the GPR schema plus num_inducing, the policy and Z ----------------------------
@@ -601,12 +608,14 @@ class SGPRSurrogate(GPSurrogate):
             "gpr_meanf_shape": [],
             "gp_varsigma": self.gp_varsigma,
             "gp_likelihood": self.gp_lik_sigma,
-            "optimiser": [type(self.optimiser).__name__],
+            "optimiser": VGPSurrogate._serialise_optimiser(self),
             "dtype": self.dtype,
             "model": "SGPR",
             "num_inducing": self.num_inducing,
             "inducing": "greedy" if isinstance(self.inducing, str) else "given",
         }
+        if self.train_inducing:  # (absent: False -- a surrogate that does not train Z writes the file it always wrote)
+            info["train_inducing"] = True
         with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
             fh.write(json.dumps(info))
 
@@ -629,12 +638,16 @@ class SGPRSurrogate(GPSurrogate):
         z = np.array(params[".inducing_variable.Z"], dtype=np.float64).reshape(-1, x.shape[1])
         inducing = z if info["inducing"] == "given" else "greedy"
         dtype = info.get("dtype", "float64")
+        train_z = bool(info.get("train_inducing", False))
         model = HipSGPR(data=(x, y), kernel=kernel, mean_function=meanf, noise_variance=params[".likelihood.variance"],
-                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device)
-        model.set_inducing(z)  # the Z the saved posterior was built on (the next update chooses again)
-        return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=Scipy(), gauss_likelihood_sigma=info["gp_likelihood"],
-                   varsigma=info["gp_varsigma"], num_inducing=info["num_inducing"], inducing=inducing, points=points,
-                   gpflow_model=model, dtype=dtype, device=device)
+                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device,
+                        train_inducing=train_z)
+        # the Z the saved posterior was built on (the next update chooses again, or -- trained -- continues from it)
+        model.set_inducing(z)
+        return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]),
+                   gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
+                   num_inducing=info["num_inducing"], inducing=inducing, points=points, gpflow_model=model, dtype=dtype,
+                   device=device, train_inducing=train_z)
 
 
 VGP_TRAIN_ITERATIONS = 10
@@ -701,6 +714,8 @@ class VGPSurrogate(GPSurrogate):
     def _serialise_optimiser(self):
         if isinstance(self.optimiser, Adam):
             return ["Adam", self.optimiser.learning_rate]
+        if isinstance(self.optimiser, Scipy) and self.optimiser.options:  # (absent: SciPy's defaults, the file of before)
+            return ["Scipy", dict(self.optimiser.options)]
         return [type(self.optimiser).__name__]
 
     @staticmethod
@@ -708,7 +723,7 @@ class VGPSurrogate(GPSurrogate):
         if info[0] == "Adam":
             return Adam(info[1])
         if info[0] == "Scipy":
-            return Scipy()
+            return Scipy(options=info[1] if len(info) > 1 else None)
         raise ValueError(f"{info} not currently supported.")
 
     def save(self, folder):
@@ -781,7 +796,9 @@ class SVGPSurrogate(GPSurrogate):
     natural-gradient step or -ELBO evaluation, a leaf-UCB prediction O(M^2), whatever the number N of evaluated points.
 
     Each ``_gp_train`` chooses Z as ``SGPRSurrogate`` does (the data itself while N <= M, else the greedy conditional-
-    variance selection at the current kernel hyper-parameters, or an array used as given), starts q (the prior under the
+    variance selection at the current kernel hyper-parameters, or an array used as given; with ``train_inducing=True``
+    that is only where Z starts, the hyper-parameter optimiser then moves Z too, at fixed q, and later updates keep the
+    trained Z without a selection), starts q (the prior under the
     Gaussian likelihood; under the Student-t the conjugate start, one Gaussian natural-gradient step at the noise variance
     scale^2 df / (df - 2)), then runs ``train_iterations`` times one natural-gradient step on q and one step of the
     hyper-parameter optimiser on -ELBO at fixed q (``HipSVGP``).  An indefinite natural-gradient step raises
@@ -790,12 +807,14 @@ class SVGPSurrogate(GPSurrogate):
 
     def __init__(self, gp_kernel, gp_meanf=None, likelihood=None, num_inducing=256, inducing="greedy",
                  natgrad_learning_rate=1.0, train_iterations=SVGP_TRAIN_ITERATIONS, optimiser=None,
-                 varsigma=erfcinv(0.01), points=None, gpflow_model=None, dtype="float64", device=0, engine_options=None):
+                 varsigma=erfcinv(0.01), points=None, gpflow_model=None, dtype="float64", device=0, engine_options=None,
+                 train_inducing=False):
         """
         :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``; any other
             likelihood raises NotImplementedError
         :param num_inducing: M (ignored when ``inducing`` is an array)
         :param inducing: "greedy" or an [M, D] array of normed coordinates used as given
+        :param train_inducing: train Z beside the hyper-parameters once N > M (``inducing`` then names where Z starts)
         :param natgrad_learning_rate: step length gamma in (0, 1] of the natural gradient
         :param train_iterations: natgrad / optimiser iterations per ``_gp_train``
         :param optimiser: hyper-parameter optimiser, default ``Adam(0.01)`` (its moments persist across updates), or
@@ -805,6 +824,8 @@ class SVGPSurrogate(GPSurrogate):
         likelihood = likelihood if likelihood is not None else Gaussian(1.0e-3)
         if not isinstance(likelihood, (Gaussian, StudentT)):
             raise NotImplementedError(f"{type(likelihood).__name__}: only the Gaussian and Student-t likelihoods are supported")
+        if not isinstance(train_inducing, (bool, np.bool_)):
+            raise TypeError(f"train_inducing must be True or False, not {train_inducing!r}")
         gamma = float(natgrad_learning_rate)
         if not (0.0 < gamma <= 1.0):
             raise ValueError(f"natgrad_learning_rate {gamma} outside (0, 1]")
@@ -827,6 +848,7 @@ class SVGPSurrogate(GPSurrogate):
         self.likelihood = likelihood
         self.num_inducing = int(num_inducing)
         self.inducing = inducing
+        self.train_inducing = bool(train_inducing)
         self.natgrad_gamma = gamma
         self.train_iters = int(train_iterations)
 
@@ -837,9 +859,9 @@ class SVGPSurrogate(GPSurrogate):
             self.gpflow_model = HipSVGP(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
                                         likelihood=self.likelihood, num_inducing=self.num_inducing,
                                         inducing=self.inducing, dtype=self.dtype, device=self.device,
-                                        engine_options=self.engine_options)
+                                        engine_options=self.engine_options, train_inducing=self.train_inducing)
         else:
-            self.gpflow_model.data = (x, y)  # Z chosen again at the current hyper-parameters
+            self.gpflow_model.data = (x, y)  # Z chosen again at the current hyper-parameters (or, trained, kept as it is)
         model = self.gpflow_model
         model.start_q()
         for i in range(self.train_iters):
@@ -870,6 +892,8 @@ class SVGPSurrogate(GPSurrogate):
             "inducing": "greedy" if isinstance(self.inducing, str) else "given",
             "dtype": self.dtype,
         }
+        if self.train_inducing:  # (absent: False)
+            info["train_inducing"] = True
         if isinstance(self.likelihood, StudentT):
             info["svgp_likelihood_df"] = model.likelihood.df
         with open(os.path.join(folder, self.GPR_INFO), "w") as fh:
@@ -899,11 +923,13 @@ class SVGPSurrogate(GPSurrogate):
         z = np.array(params[".inducing_variable.Z"], dtype=np.float64).reshape(-1, x.shape[1])
         inducing = z if info["inducing"] == "given" else "greedy"
         dtype = info.get("dtype", "float64")
+        train_z = bool(info.get("train_inducing", False))
         model = HipSVGP(data=(x, y), kernel=kernel, mean_function=meanf, likelihood=likelihood,
-                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device)
-        model.set_inducing(z)  # the Z the saved q belongs to (the next update chooses again)
+                        num_inducing=info["num_inducing"], inducing=inducing, dtype=dtype, device=device,
+                        train_inducing=train_z)
+        model.set_inducing(z)  # the Z the saved q belongs to (the next update chooses again, or -- trained -- continues from it)
         model.set_q(np.array(params[".q_mu"]), np.array(params[".q_sqrt"]))
         return cls(gp_kernel=kernel, gp_meanf=meanf, likelihood=likelihood, num_inducing=info["num_inducing"],
                    inducing=inducing, natgrad_learning_rate=info["svgp_natgrad_lr"], train_iterations=info["svgp_iters"],
                    optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
-                   points=points, gpflow_model=model, dtype=dtype, device=device)
+                   points=points, gpflow_model=model, dtype=dtype, device=device, train_inducing=train_z)

@@ -155,7 +155,15 @@ class Scipy:
 
     _SETULB_DOC = "setulb(m,x,l,u,nbd,f,g,factr,pgtol,wa,iwa,task,lsave,isave,dsave,maxls,ln_task)"
 
+    def __init__(self, options=None):
+        """``options``: SciPy's ``options`` dictionary for every ``minimize`` of this object that is given none of its own,
+        e.g. ``Scipy(options={"maxfun": 200})`` to cap the evaluations of an update (a search over (u, Z) with
+        ``train_inducing=True`` has M D more dimensions and can use thousands).  None: SciPy's defaults."""
+        self.options = dict(options) if options else None
+
     def minimize(self, closure, variables=None, method="L-BFGS-B", **scipy_kwargs):
+        if getattr(self, "options", None) and "options" not in scipy_kwargs:
+            scipy_kwargs["options"] = dict(self.options)
         model = getattr(closure, "__self__", None)
         if model is None or not hasattr(model, "_loss_and_grad"):
             raise TypeError("Scipy.minimize expects the bound training_loss of a HipGPR model")

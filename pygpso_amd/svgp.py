@@ -2,7 +2,8 @@
 ``HipSVGP``: the sparse variational GP on inducing points, the model the ``SVGPSurrogate`` keeps in ``.gpflow_model``.
 
 Stands where ``gpflow.models.SVGP`` (whitened, full ``q_sqrt``, full batch) would: M inducing points Z summarise the N
-training rows as in ``HipSGPR`` (chosen the same way, not trained), and a whitened variational state q(v) = N(q_mu,
+training rows as in ``HipSGPR`` (chosen the same way; trained beside the hyper-parameters with ``train_inducing=True``,
+at fixed q -- q is whitened, so it stays valid while Z moves), and a whitened variational state q(v) = N(q_mu,
 q_sqrt q_sqrt^T) over the M inducing values is trained against the Gaussian or the Student-t likelihood -- the robust
 likelihood of ``HipVGP`` at the cost of the SGPR: O(N M^2) per natural-gradient step or -ELBO evaluation on the device,
 O(M^2) per prediction.  The predictive is installed over the rows Z as the VGP's is over its training rows
@@ -28,9 +29,10 @@ from .vgp import GH_POINTS
 
 class HipSVGP(HipSGPR):
     def __init__(self, data, kernel, mean_function=None, likelihood=None, num_inducing=256, inducing="greedy",
-                 dtype="float64", device=0, engine=None, engine_options=None, q_mu=None, q_sqrt=None):
+                 dtype="float64", device=0, engine=None, engine_options=None, q_mu=None, q_sqrt=None,
+                 train_inducing=False):
         """``likelihood``: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``.
-        ``num_inducing`` / ``inducing``: as ``HipSGPR``.  ``dtype``: "float64" or "mixed".  ``q_mu`` [M] / [M, 1] and
+        ``num_inducing`` / ``inducing`` / ``train_inducing``: as ``HipSGPR``.  ``dtype``: "float64" or "mixed".  ``q_mu`` [M] / [M, 1] and
         ``q_sqrt`` [M, M] / [1, M, M] (optional): the variational state for the Z the data leads to."""
         if dtype not in ("float64", "mixed"):
             raise ValueError(f"SVGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
@@ -40,7 +42,8 @@ class HipSVGP(HipSGPR):
         self._student = isinstance(likelihood, StudentT)
         super().__init__(data, kernel, mean_function=mean_function,
                          noise_variance=1.0 if self._student else likelihood.variance, num_inducing=num_inducing,
-                         inducing=inducing, dtype=dtype, device=device, engine=engine, engine_options=engine_options)
+                         inducing=inducing, dtype=dtype, device=device, engine=engine, engine_options=engine_options,
+                         train_inducing=train_inducing)
         if self._student:
             self.likelihood = types.SimpleNamespace(scale=likelihood.scale, df=likelihood.df)
             self.engine.vgp_set_likelihood("StudentT", likelihood.df, GH_POINTS)
@@ -57,7 +60,7 @@ class HipSVGP(HipSGPR):
             self.engine.svgp_init_q()
         else:
             name, k, tm, c = self._args()
-            self.engine.svgp_init_q(name, self._pack(), k, tm, c, self.predictive_noise())
+            self.engine.svgp_init_q(name, self._pack_theta(), k, tm, c, self.predictive_noise())
         self._resident = False
 
     def set_q(self, q_mu, q_sqrt):
@@ -71,11 +74,11 @@ class HipSVGP(HipSGPR):
         return self.engine.svgp_get_q()
 
     # -- hyper-parameters: the likelihood's slot (as HipVGP) ----------------------------------------
-    def _pack(self):
+    def _pack_theta(self):
         # (while HipGPR.__init__ chooses Z the likelihood is not yet the Student-t's: the selection reads only the kernel's
         # slots of u)
         if not self._student or not hasattr(self.likelihood, "scale"):
-            return super()._pack()
+            return super()._pack_theta()
         parts = [np.atleast_1d(_softplus_inv(self.kernel.lengthscales)), [float(_softplus_inv(self.kernel.variance))],
                  [float(_softplus_inv(self.likelihood.scale))]]
         if self._train_mean:
@@ -88,9 +91,9 @@ class HipSVGP(HipSGPR):
             p = float(_softplus(np.asarray(u, dtype=np.float64)[self.n_ls + 1]))
         return ls, var, p, c
 
-    def _assign(self, u):
+    def _assign_theta(self, u):
         if not self._student:
-            return super()._assign(u)
+            return super()._assign_theta(u)
         ls, var, scale, c = self._unpack(u)
         self.kernel.lengthscales = ls.copy() if self.kernel.ard else float(ls[0])
         self.kernel.variance = var
@@ -113,21 +116,19 @@ class HipSVGP(HipSGPR):
             raise ValueError(f"natural-gradient step {gamma} outside (0, 1]")
         name, k, tm, c = self._args()
         self._resident = False
-        self.engine.svgp_natgrad(name, self._pack(), k, tm, c, gamma)
+        self.engine.svgp_natgrad(name, self._pack_theta(), k, tm, c, gamma)
 
-    def _loss_and_grad(self, u):
-        """-ELBO and its gradient in u at fixed q and Z (one device evaluation)."""
-        name, k, tm, c = self._args()
-        f, gu, _ = self.engine.svgp_elbo_u(name, u, k, tm, c)
-        self._last_nlml = f
-        self.num_loss_evals += 1
-        self._resident = False
-        return f, gu
+    # (``_loss_and_grad`` is HipSGPR's: -ELBO at fixed q and its gradient in u, or in (u, Z) while Z is trained)
+    def _eval_fixed(self, *args, **kwargs):
+        return self.engine.svgp_elbo_u(*args, **kwargs)
+
+    def _eval_moving(self, *args, **kwargs):
+        return self.engine.svgp_elbo_uz(*args, **kwargs)
 
     def training_loss(self):
         """-ELBO at the current hyper-parameters, q and Z."""
         name, k, tm, c = self._args()
-        f, _, _ = self.engine.svgp_elbo_u(name, self._pack(), k, tm, c, want_grad=False)
+        f, _, _ = self.engine.svgp_elbo_u(name, self._pack_theta(), k, tm, c, want_grad=False)
         self._resident = False
         return f
 
@@ -137,7 +138,7 @@ class HipSVGP(HipSGPR):
     def _ensure_resident(self):
         if not self._resident:
             name, k, tm, c = self._args()
-            self.install_delta = self.engine.svgp_posterior(name, self._pack(), k, tm, c)
+            self.install_delta = self.engine.svgp_posterior(name, self._pack_theta(), k, tm, c)
             self._resident = True
 
     def predict_f(self, Xnew):
@@ -172,7 +173,7 @@ class HipSVGP(HipSGPR):
             v = np.array2string(np.asarray(val), precision=6) if np.ndim(val) else f"{val:.6g}"
             lines.append(f"{name:<25} {tr:<17} {v}")
         m = self.engine.n
-        lines.append(f"{'SVGP.inducing_variable.Z':<25} {'(not trained)':<17} shape ({m}, {self._data[0].shape[1]})")
+        lines.append(f"{'SVGP.inducing_variable.Z':<25} {self._z_note():<17} shape ({m}, {self._data[0].shape[1]})")
         lines.append(f"{'SVGP.q_mu':<25} {'':<17} shape ({m}, 1)")
         lines.append(f"{'SVGP.q_sqrt':<25} {'FillTriangular':<17} shape (1, {m}, {m})")
         return "\n".join(lines)
