@@ -199,6 +199,24 @@ int gpso_fit_eval(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_l
 int gpso_fit_eval_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                     double* nlml, double* grad_u, double* theta_out);
 
+/* Multi-start hyper-parameter search: the pending evaluations of several L-BFGS-B searches in one launch, one workgroup
+ * per theta (fit.hip: small_fit_batch_kernel -- the one-launch fit's arithmetic, bit for bit).
+ * gpso_fit_batch_max: how many entries one gpso_fit_eval_u_batch call may hold for the resident data: 256 when the
+ * one-launch fit applies (N <= 64, or N <= 128 with a padded D <= 32, and GPSO_OPT_FIT_FUSED_SMALL on), else 0. */
+int gpso_fit_batch_max(gpso_ctx* ctx);
+
+/* B evaluations of gpso_fit_eval_u at U[b*nu .. ], nu = n_ls + 2 + (train_mean != 0), in one launch.
+ * loss[B]; grad_u[B*nu] (nullable); status[B]: what gpso_fit_eval_u returns for that entry alone -- GPSO_OK,
+ * GPSO_E_NOTPD (pivot[B], nullable, gets the failing pivot; -1 otherwise), or GPSO_E_ARG for an entry whose lengthscale
+ * or kernel variance does not come out positive (NaN included; such an entry is not launched).
+ * Returns GPSO_OK when the launch ran, whatever the entries' verdicts; a failed entry has loss = NaN (and a NaN
+ * gradient), and gpso_last_error names the first one.  Refused before anything is done: no data or an asynchronous
+ * call in flight (GPSO_E_STATE); b < 1, b > gpso_fit_batch_max, a NULL U / loss / status (GPSO_E_ARG).
+ * Leaves the context as it found it: a resident posterior stays resident and predict-ready, bit for bit.
+ * gpso_last_ms(ctx, 2) is the launch's device time, as for a fit. */
+int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int n_ls, int train_mean,
+                          double mean_c_fixed, double* loss, double* grad_u, int* status, int64_t* pivot);
+
 /* Replaces: `model.data = (x, y)` at gpso/gp_surrogate.py:496-498 for an update that KEEPS the hyper-parameters (the
  * reference always re-optimises right after, :500-503, and so refactorises from scratch although N grew by 1-7 points
  * per iteration, gpso/optimisation.py:324-329).  With the posterior of the N points resident at theta

@@ -13,6 +13,7 @@
 #include <set>
 #include <string>
 #include <utility>
+#include <limits>
 #include <vector>
 
 #include "../../include/gpso_hip.h"
@@ -77,6 +78,9 @@ struct Engine {
   virtual int set_posterior(const double* X, const double* L, const double* alpha, int64_t n, int d,
                             int kernel, const double* ls, int n_ls, double variance, double noise,
                             double mean_c) = 0;
+  virtual int fit_batch_max() = 0;
+  virtual int fit_eval_batch(int kernel, const double* th, int nv, int n_ls, double* loss, double* grad, int* info) = 0;
+  virtual int fit_eval_batch_check(int kernel, int b, int n_ls) = 0;
   virtual int append(const double* Xnew, const double* ynew, int64_t k, double* nlml) = 0;
   virtual int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,
                       double* var, int out_mem) = 0;
@@ -438,6 +442,7 @@ struct EngineT : Engine {
   // predict workspace
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
+  DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   // precision self-test
   bool check = false, st_done = false, st_have = false;
   double tol_var = 1.0e-4, tol_mean = 1.0e-4;
@@ -449,7 +454,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -1096,6 +1101,72 @@ struct EngineT : Engine {
     if (small) linv_p_lazy = false;
     return GPSO_OK;
   }
+  // ---- batched evaluation (multi-start hyper-parameter search): fit.hip small_fit_batch_kernel -------------------------
+  // entries one launch may hold for the resident data: one workgroup per CU where the one-launch fit applies, else none
+  int fit_batch_max() override { return (have_data && fused_small && small_fit_eligible(n, dp)) ? kSmallBatchMax : 0; }
+
+  // everything a batched call is refused for, before anything is touched
+  int fit_eval_batch_check(int kernel, int b, int n_ls_) override {
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval_u_batch before gpso_set_data");
+    int rc = refuse_if_async("gpso_fit_eval_u_batch");
+    if (rc) return rc;
+    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
+    if (!(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    if (b < 1) return ctx->fail(GPSO_E_ARG, "a batch needs at least one entry (b=%d)", b);
+    const int cap = fit_batch_max();
+    if (cap == 0) {
+      if (!fused_small) return ctx->fail(GPSO_E_ARG, "no batched evaluation: GPSO_OPT_FIT_FUSED_SMALL is off (gpso_fit_batch_max = 0)");
+      if (n > 128) return ctx->fail(GPSO_E_ARG, "no batched evaluation for N > 128 (N=%lld; gpso_fit_batch_max = 0)", (long long)n);
+      return ctx->fail(GPSO_E_ARG, "no batched evaluation for N > 64 with a padded D > 32 (N=%lld, D=%d; gpso_fit_batch_max = 0)",
+                       (long long)n, d);
+    }
+    if (b > cap) return ctx->fail(GPSO_E_ARG, "b=%d entries exceed the limit of %d per call (gpso_fit_batch_max)", b, cap);
+    return GPSO_OK;
+  }
+
+  // nv <= fit_batch_max() constrained hyper-parameter vectors th[nv][n_ls + 3] = (ls..., variance, noise, c), every one
+  // acceptable to set_theta; loss[nv], grad[nv][n_ls + 3] (nullable), info[nv] (failing pivot or INT_MAX).  One launch;
+  // no member that describes the resident posterior is touched.
+  int fit_eval_batch(int kernel, const double* th, int nv, int n_ls_, double* loss, double* grad, int* info) override {
+    ctx->tick_timing();
+    const int H = n_ls_ + 3;
+    int rc = ensure(batch_theta, (size_t)nv * kSmallBatchTheta * 8);
+    if (rc) return rc;
+    double* stage = ctx->pinned_stage((size_t)nv * kSmallBatchTheta);  // (waits for the stream)
+    if (!stage) return ctx->fail(GPSO_E_OOM, "pinned host staging");
+    for (int e = 0; e < nv; ++e) {
+      double* r = stage + (size_t)e * kSmallBatchTheta;
+      const double* t = th + (size_t)e * H;
+      std::memset(r, 0, kSmallBatchTheta * 8);
+      r[0] = t[n_ls_]; r[1] = t[n_ls_ + 1]; r[2] = t[n_ls_ + 2];
+      for (int k = 0; k < kMaxD; ++k) r[kHyperHeader + k] = t[n_ls_ == 1 ? 0 : std::min(k, n_ls_ - 1)];
+    }
+    // results: straight into pinned host memory from the kernel (as the single fit's scalars), read behind the wait
+    const size_t out_doubles = (size_t)nv * (1 + H) + ((size_t)nv + 1) / 2;
+    double* host = ctx->pinned_scratch(out_doubles);
+    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    hipStream_t s = st();
+    HIPCHECK(hipMemcpyAsync(batch_theta.p, stage, (size_t)nv * kSmallBatchTheta * 8, hipMemcpyHostToDevice, s));
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
+    SmallBatchArgs a{};
+    a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.theta = as<double>(batch_theta);
+    a.loss = host; a.grad = host + nv; a.info = reinterpret_cast<int*>(host + (size_t)nv * (1 + H));
+    a.n = (int)n; a.d = d; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls_; a.want_grad = grad ? 1 : 0;
+    if (launch_small_fit_batch<TF, TP>(s, a, nv)) {
+      rc = launch_status();
+      return rc ? rc : ctx->fail(GPSO_E_HIP, "internal: the batched fit refused %d entries", nv);
+    }
+    if ((rc = launch_status())) return rc;
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
+    HIPCHECK(ctx->wait(s));
+    float ms = 0;
+    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
+    std::memcpy(loss, a.loss, (size_t)nv * 8);
+    if (grad) std::memcpy(grad, a.grad, (size_t)nv * H * 8);
+    std::memcpy(info, a.info, (size_t)nv * sizeof(int));
+    return GPSO_OK;
+  }
+
   // the packed native-type L^-1, made on demand from the resident factor's inverse
   bool linv_p_lazy = false;
   int ensure_linv_p() {
@@ -4026,6 +4097,69 @@ int gpso_fit_eval_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
   // chain rule: d/du = d/dtheta * sigmoid(u) for the softplus-transformed parameters, identity for the mean
   for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
   if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_fit_batch_max(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->fit_batch_max();
+}
+
+int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int n_ls, int train_mean,
+                          double mean_c_fixed, double* loss, double* grad_u, int* status, int64_t* pivot) {
+  ENTER();
+  if (!U || !loss || !status) return ctx->fail(GPSO_E_ARG, "U, loss and status must not be NULL");
+  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
+  int rc = ctx->eng->fit_eval_batch_check(kernel, b, n_ls);
+  if (rc) return rc;
+  const int nu = n_ls + 2 + (train_mean ? 1 : 0), H = n_ls + 3;
+  // the transforms of gpso_fit_eval_u, entry by entry; an entry the single call would refuse for its values (a
+  // lengthscale or a variance that is not positive: NaN included) is not launched and reports GPSO_E_ARG as there
+  std::vector<double> th((size_t)b * H), g((size_t)b * H), f((size_t)b);
+  std::vector<int> slot((size_t)b), info((size_t)b);
+  int nv = 0, first_bad = -1;
+  for (int e = 0; e < b; ++e) {
+    const double* u = U + (size_t)e * nu;
+    double* t = th.data() + (size_t)nv * H;
+    bool ok = true;
+    for (int k = 0; k < n_ls; ++k) {
+      t[k] = gpso_softplus(u[k]);
+      ok = ok && (t[k] > 0.0);
+    }
+    t[n_ls] = gpso_softplus(u[n_ls]);
+    ok = ok && (t[n_ls] > 0.0);
+    t[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
+    t[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
+    slot[e] = ok ? nv++ : -1;
+  }
+  if (nv > 0 && (rc = ctx->eng->fit_eval_batch(kernel, th.data(), nv, n_ls, f.data(), grad_u ? g.data() : nullptr, info.data())))
+    return rc;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int e = 0; e < b; ++e) {
+    const double* u = U + (size_t)e * nu;
+    const int v = slot[e];
+    const bool fine = v >= 0 && info[v] == INT_MAX;
+    status[e] = fine ? GPSO_OK : (v < 0 ? GPSO_E_ARG : GPSO_E_NOTPD);
+    if (pivot) pivot[e] = (v >= 0 && !fine) ? info[v] : -1;
+    loss[e] = fine ? f[v] : nan;
+    if (!fine && first_bad < 0) first_bad = e;
+    if (!grad_u) continue;
+    double* gu = grad_u + (size_t)e * nu;
+    if (!fine) {
+      for (int k = 0; k < nu; ++k) gu[k] = nan;
+      continue;
+    }
+    const double* ge = g.data() + (size_t)v * H;
+    for (int k = 0; k < n_ls + 2; ++k) gu[k] = ge[k] * gpso_sigmoid(u[k]);
+    if (train_mean) gu[n_ls + 2] = ge[n_ls + 2];
+  }
+  if (first_bad >= 0) {
+    if (slot[first_bad] < 0)
+      (void)ctx->fail(GPSO_E_ARG, "batch entry %d: a lengthscale or the kernel variance is not positive", first_bad);
+    else
+      (void)ctx->fail(GPSO_E_NOTPD, "batch entry %d: K + noise*I is not positive definite: Cholesky failed at pivot %d",
+                      first_bad, info[slot[first_bad]]);
+  }
   return GPSO_OK;
 }
 

@@ -450,7 +450,8 @@ __device__ __forceinline__ void chol_panel16(double* Ls, F* Cs, int c0, int lane
 __device__ __forceinline__ double* early_t10(double* Xs) { return Xs + kPB; }
 __device__ __forceinline__ double* early_t32(double* Xs) { return Xs + 2 * kPB * kDS + 3 * kPB; }
 __device__ __forceinline__ double* early_t(double* Xs) { return Xs + 2 * kPB; }
-template <int NEWTON, typename T, bool F32CHAIN = false, bool EARLY = false>
+// STORE = false (the batched small fit): nothing goes to Lout -- the factor stays in LDS
+template <int NEWTON, typename T, bool F32CHAIN = false, bool EARLY = false, bool STORE = true>
 __device__ __forceinline__ void chol64_lds(double* Ls, double* Xs, T* __restrict__ Lout, int64_t ld,
                                            int64_t k0, int64_t n, int* info, double* scratch) {
   const int tid = threadIdx.x, lane = tid & 63;
@@ -486,7 +487,7 @@ __device__ __forceinline__ void chol64_lds(double* Ls, double* Xs, T* __restrict
         for (int r = 0; r < 4; ++r) t32[((lane >> 4) + 4 * r) * kDS + (lane & 15)] = t[r];
       }
     } else if (wave == 2 && c0 > 0) {
-      lower_cols_to_global<T>(Ls, Lout, ld, lane, c0 - kPB);
+      if constexpr (STORE) lower_cols_to_global<T>(Ls, Lout, ld, lane, c0 - kPB);
       if (EARLY && c0 == 3 * kPB) {  // T[a][1] = L21[a][1] X11: X11 was finished during panel 2
         for (int a = 0; a < 2; ++a) {
           const f64x4 t = mma16_lds<16>(Ls + (32 + kPB * a) * kDS + kPB, kDS, 1, Xs + kPB * kDS + kPB, kDS, 1, lane);
@@ -2851,8 +2852,13 @@ __device__ __forceinline__ void small_store_strip(double* blk, int wave, int lan
     for (int r = 0; r < 4; ++r) blk[(16 * wave + (lane >> 4) + 4 * r) * kDS + 16 * t + (lane & 15)] = sign * v[t][r];
 }
 
-template <typename T, typename TP>
-__global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
+// The evaluation itself, shared by the two kernels below.  BATCH = false: small_fit_kernel, one workgroup, theta by
+// value in SmallFitArgs, every product of the fit written to the context's buffers.  BATCH = true:
+// small_fit_batch_kernel, workgroup b evaluates theta_b read from memory and writes loss[b], info[b] and its row of
+// grad -- nothing else leaves LDS (`if constexpr (!BATCH)` around every other global store), so a resident posterior
+// is not touched.  The arithmetic is one text: same operations on the same operands in the same order, same bits.
+template <typename T, typename TP, bool BATCH, typename Args>
+__device__ __forceinline__ void small_fit_body(const Args& g) {
   extern __shared__ __align__(32) unsigned char lds_raw[];
   double* A = reinterpret_cast<double*>(lds_raw);
   double* B = A + kBlk;
@@ -2870,16 +2876,37 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = g.n, dp = g.dp, nb = (n > 64) ? 2 : 1, rows = 64 * nb;
-  int* info = reinterpret_cast<int*>(g.scal + 1);
-  T* Lf = static_cast<T*>(g.Lf);
-  T* linv = static_cast<T*>(g.linv);
   constexpr int64_t ld = kSmallN;
+  // theta: by value (single) or this workgroup's record of the theta buffer (batch; layout: SmallBatchArgs)
+  const double* th = nullptr;
+  double variance, noise, mean_c;
+  int* info;
+  T* Lf = nullptr;
+  T* linv = nullptr;
+  if constexpr (BATCH) {
+    th = g.theta + (size_t)blockIdx.x * kSmallBatchTheta;
+    variance = th[0];
+    noise = th[1];
+    mean_c = th[2];
+    info = reinterpret_cast<int*>(red + 12);  // (the factorisation's verdict stays in LDS: slots 12.. of red are free)
+  } else {
+    variance = g.variance;
+    noise = g.noise;
+    mean_c = g.mean_c;
+    info = reinterpret_cast<int*>(g.scal + 1);
+    Lf = static_cast<T*>(g.Lf);
+    linv = static_cast<T*>(g.linv);
+  }
+  auto ls_at = [&](int k) -> double {
+    if constexpr (BATCH) return th[8 + k];
+    else return g.ls[k];
+  };
 
   GPSO_SSTAMP(0);
   // ---- 0. scaled inputs: LDS (in B, free until X00 is formed) + the global copies the predict path reads
   double* xs = B;
   if (tid == 0) *info = INT_MAX;
-  if (tid < 8 + 48) {  // the hyper-parameter block (layout: api.hip set_theta)
+  if constexpr (!BATCH) if (tid < 8 + 48) {  // the hyper-parameter block (layout: api.hip set_theta)
     double h = 0.0;
     if (tid == 0) h = (double)n;
     else if (tid == 1) h = (double)g.d;
@@ -2894,9 +2921,9 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   for (int e = tid; e < kSmallN * dp; e += 256) {
     const int i = e / dp, k = e % dp;
     double v = 0.0;
-    if (i < n && k < g.d) v = g.x64[(int64_t)i * g.d + k] / g.ls[k];
+    if (i < n && k < g.d) v = g.x64[(int64_t)i * g.d + k] / ls_at(k);
     if (i < rows) xs[e] = v;
-    g.xs64[e] = v;
+    if constexpr (!BATCH) g.xs64[e] = v;
   }
   __syncthreads();
   if (tid < kSmallN) {
@@ -2904,10 +2931,10 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     if (tid < rows)
       for (int k = 0; k < dp; ++k) acc += xs[tid * dp + k] * xs[tid * dp + k];
     nrm[tid] = acc;
-    g.xnorm64[tid] = acc;
-    resid[tid] = (tid < n) ? g.y64[tid] - g.mean_c : 0.0;
+    if constexpr (!BATCH) g.xnorm64[tid] = acc;
+    resid[tid] = (tid < n) ? g.y64[tid] - mean_c : 0.0;
   }
-  {  // MFMA A-fragment packing (pack_xs_kernel<double>)
+  if constexpr (!BATCH) {  // MFMA A-fragment packing (pack_xs_kernel<double>)
     const int dp4 = dp / 4;
     for (int idx = tid; idx < kSmallN * dp; idx += 256) {
       const int l = idx & 63, q = idx >> 6, c = q % dp4, kt = q / dp4;
@@ -2918,17 +2945,17 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   __syncthreads();
   GPSO_SSTAMP(1);
   // ---- 1. Gram blocks: K00 -> A, K10 -> C, K11 -> D4
-  small_gram_block(xs, nrm, dp, 0, 0, n, g.kernel, g.variance, g.noise, A, wave, lane);
+  small_gram_block(xs, nrm, dp, 0, 0, n, g.kernel, variance, noise, A, wave, lane);
   if (nb == 2) {
-    small_gram_block(xs, nrm, dp, 1, 0, n, g.kernel, g.variance, g.noise, C, wave, lane);
-    small_gram_block(xs, nrm, dp, 1, 1, n, g.kernel, g.variance, g.noise, D4, wave, lane);
+    small_gram_block(xs, nrm, dp, 1, 0, n, g.kernel, variance, noise, C, wave, lane);
+    small_gram_block(xs, nrm, dp, 1, 1, n, g.kernel, variance, noise, D4, wave, lane);
   }
   __syncthreads();
   for (int e = tid; e < kBlk; e += 256) B[e] = 0.0;  // X00 is written on and below the diagonal only
   __syncthreads();
   // ---- 2. K00 = L00 L00^T, X00 = L00^-1 (B)
   GPSO_SSTAMP(2);
-  chol64_lds<2, T>(A, B, Lf, ld, 0, n, info, Ts);
+  chol64_lds<2, T, false, false, !BATCH>(A, B, Lf, ld, 0, n, info, Ts);
   if (tid < kFitBlock) dg[tid] = A[tid * kDS + tid];
   GPSO_SSTAMP(3);
   trinv64_lds<true, T>(A, B, Ts, Lf, ld);
@@ -2940,11 +2967,13 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     __syncthreads();
     small_store_strip(C, wave, lane, v, 1.0);
     for (int e = tid; e < kBlk; e += 256) A[e] = 0.0;  // L00 is dead: A becomes X11
+    if constexpr (!BATCH) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
+      for (int t = 0; t < 4; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r)
-        Lf[(int64_t)(64 + 16 * wave + (lane >> 4) + 4 * r) * ld + 16 * t + (lane & 15)] = (T)v[t][r];
+        for (int r = 0; r < 4; ++r)
+          Lf[(int64_t)(64 + 16 * wave + (lane >> 4) + 4 * r) * ld + 16 * t + (lane & 15)] = (T)v[t][r];
+    }
     __syncthreads();
     // ---- 4. S = K11 - L10 L10^T (lower 16x16 tiles) in place in D4
     for (int t = wave; t < 10; t += 4) {
@@ -2960,10 +2989,10 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     __syncthreads();
     // ---- 5. S = L11 L11^T, X11 = L11^-1 (A)
     GPSO_SSTAMP(5);
-    chol64_lds<2, T>(D4, A, Lf + 64 * ld + 64, ld, 64, n, info, Ts);
+    chol64_lds<2, T, false, false, !BATCH>(D4, A, BATCH ? nullptr : Lf + 64 * ld + 64, ld, 64, n, info, Ts);
     if (tid < kFitBlock) dg[64 + tid] = D4[tid * kDS + tid];
     GPSO_SSTAMP(6);
-    trinv64_lds<true, T>(D4, A, Ts, Lf + 64 * ld + 64, ld);
+    trinv64_lds<true, T>(D4, A, Ts, BATCH ? nullptr : Lf + 64 * ld + 64, ld);
     GPSO_SSTAMP(7);
     // ---- 6. X10 = -X11 (L10 X00) -> C
     small_mm_strip(C, B, kDS, 1, wave, lane, v);  // W = L10 X00
@@ -2984,6 +3013,7 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   // ---- 7. L^-1 to global: the lower triangle of rows < 64 nb (all any later reader looks at: the bf16
   //         packing and the debug getters read on / below the diagonal, rows < n) + the predict
   //         kernels' tile packing (every tile row of the 128-padded problem: rows >= n are zero)
+  if constexpr (!BATCH) {
   lower_tile_to_global<T>(B, linv, ld, tid);
   if (nb == 2) {
     lower_tile_to_global<T>(A, linv + 64 * ld + 64, ld, tid);
@@ -3020,6 +3050,7 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
       out[idx] = v;
     }
   }
+  }  // !BATCH
   GPSO_SSTAMP(9);
   // ---- 8. a = X (y - c), alpha = X^T a, diag(K_y^-1) = column norms of X, NLML -- on the MFMA: a vector
   //         is fed as a B operand whose 16 columns are all that vector (column stride 0), the result is read
@@ -3055,7 +3086,7 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     kd[64 + tid] = 1.0;
   }
   __syncthreads();
-  if (tid < kSmallN) {
+  if constexpr (!BATCH) if (tid < kSmallN) {
     const bool live = tid < n;  // (padding rows: unit rows of X -- zero them like the general path does)
     static_cast<T*>(g.white)[tid] = (T)(live ? wht[tid] : 0.0);
     static_cast<T*>(g.alpha_f)[tid] = (T)(live ? alp[tid] : 0.0);
@@ -3085,6 +3116,11 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     const double ldet = (red[4] + red[5]) + (red[6] + red[7]);
     const double nl = 0.5 * quad + ldet + 0.5 * (double)n * 1.83787706640934548356;  // log(2 pi)
     const double gc = -((red[8] + red[9]) + (red[10] + red[11]));
+    if constexpr (BATCH) {
+      g.loss[blockIdx.x] = nl;
+      g.info[blockIdx.x] = *info;
+      if (g.want_grad) g.grad[(size_t)blockIdx.x * (g.n_ls + 3) + g.n_ls + 2] = gc;
+    } else {
     g.scal[0] = nl;
     if (g.want_grad) g.scal[8 + g.n_ls + 2] = gc;
     if (g.scal_host != nullptr) {
@@ -3096,6 +3132,7 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
         *reinterpret_cast<volatile double*>(g.scal_host + 7) = g.done_token;
       }
     }
+    }  // !BATCH
   }
   GPSO_SSTAMP(10);
   if (!g.want_grad) return;
@@ -3104,13 +3141,14 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   double* xg = D4;  // scaled inputs again (D4 is dead)
   for (int e = tid; e < rows * dp; e += 256) {
     const int i = e / dp, k = e % dp;
-    xg[e] = (i < n && k < g.d) ? g.x64[(int64_t)i * g.d + k] / g.ls[k] : 0.0;
+    xg[e] = (i < n && k < g.d) ? g.x64[(int64_t)i * g.d + k] / ls_at(k) : 0.0;
   }
   const int H = g.n_ls + 2;
   for (int h = tid; h < 4 * (kGradMaxLs + 2); h += 256) gacc[h] = 0.0;
   __syncthreads();
   const int nt16 = (n + 15) / 16;
-  T* kinv = static_cast<T*>(g.kinv);
+  T* kinv = nullptr;
+  if constexpr (!BATCH) kinv = static_cast<T*>(g.kinv);
   double g_var = 0.0, g_noise = 0.0, g_iso = 0.0;  // per lane, over all tiles of this wave
   for (int t = wave; t < nt16 * (nt16 + 1) / 2; t += 4) {
     int ti = 0, tj = t;
@@ -3149,13 +3187,13 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
     for (int r = 0; r < 4; ++r) {
       const int i = irow0 + 4 * r, j = jcol;
       base[r] = 0.0;
-      if (kinv != nullptr && i < kSmallN) kinv[(int64_t)i * ld + j] = (T)acc[r];
+      if constexpr (!BATCH) if (kinv != nullptr && i < kSmallN) kinv[(int64_t)i * ld + j] = (T)acc[r];
       if (i >= n || j >= n || j > i) continue;
       const double w = (i == j) ? 1.0 : 2.0;
       const double Wij = 0.5 * (acc[r] - alp[i] * alp[j]);
       double kv, dk;
-      kern_and_dkern_same(g.kernel, r2d[r], g.variance, kv, dk);
-      g_var += w * Wij * kv / g.variance;
+      kern_and_dkern_same(g.kernel, r2d[r], variance, kv, dk);
+      g_var += w * Wij * kv / variance;
       if (i == j) g_noise += Wij;
       base[r] = w * Wij * dk;
       g_iso += base[r] * (-2.0 * r2d[r]);
@@ -3186,16 +3224,30 @@ __global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
   __syncthreads();
   if (tid < H) {
     double v = (gacc[tid] + gacc[(kGradMaxLs + 2) + tid]) + (gacc[2 * (kGradMaxLs + 2) + tid] + gacc[3 * (kGradMaxLs + 2) + tid]);
-    if (tid < g.n_ls) v /= g.ls[g.n_ls == 1 ? 0 : tid];
-    g.scal[8 + tid] = v;
-    if (g.scal_host != nullptr) g.scal_host[8 + tid] = v;
+    if (tid < g.n_ls) v /= ls_at(g.n_ls == 1 ? 0 : tid);
+    if constexpr (BATCH) {
+      g.grad[(size_t)blockIdx.x * (g.n_ls + 3) + tid] = v;
+    } else {
+      g.scal[8 + tid] = v;
+      if (g.scal_host != nullptr) g.scal_host[8 + tid] = v;
+    }
   }
-  if (g.scal_host != nullptr && g.done_token != 0.0) {  // every writer releases at system scope, then the token
+  if constexpr (!BATCH) if (g.scal_host != nullptr && g.done_token != 0.0) {  // every writer releases at system scope, then the token
     __threadfence_system();
     __syncthreads();
     if (tid == 0) *reinterpret_cast<volatile double*>(g.scal_host + 7) = g.done_token;
   }
   GPSO_SSTAMP(11);
+}
+
+template <typename T, typename TP>
+__global__ __launch_bounds__(256) void small_fit_kernel(SmallFitArgs g) {
+  small_fit_body<T, TP, false>(g);
+}
+// one workgroup per theta (grid <= kSmallBatchMax: the LDS of a workgroup leaves room for one per CU)
+template <typename T, typename TP>
+__global__ __launch_bounds__(256) void small_fit_batch_kernel(SmallBatchArgs g) {
+  small_fit_body<T, TP, true>(g);
 }
 
 bool small_fit_eligible(int64_t n, int dp) { return n <= kSmallN && (n <= 64 || dp <= 32); }
@@ -3210,6 +3262,18 @@ int launch_small_fit(hipStream_t st, const SmallFitArgs& args) {
 template int launch_small_fit<double, double>(hipStream_t, const SmallFitArgs&);
 template int launch_small_fit<double, float>(hipStream_t, const SmallFitArgs&);
 template int launch_small_fit<float, float>(hipStream_t, const SmallFitArgs&);
+
+template <typename T, typename TP>
+int launch_small_fit_batch(hipStream_t st, const SmallBatchArgs& args, int b) {
+  if (b < 1 || b > kSmallBatchMax) return -1;
+  const int rc = ensure_dyn_lds(reinterpret_cast<const void*>(&small_fit_batch_kernel<T, TP>), kSmallLdsBytes);
+  if (rc) return rc;
+  hipLaunchKernelGGL((small_fit_batch_kernel<T, TP>), dim3((unsigned)b), dim3(256), kSmallLdsBytes, st, args);
+  return 0;
+}
+template int launch_small_fit_batch<double, double>(hipStream_t, const SmallBatchArgs&, int);
+template int launch_small_fit_batch<double, float>(hipStream_t, const SmallBatchArgs&, int);
+template int launch_small_fit_batch<float, float>(hipStream_t, const SmallBatchArgs&, int);
 
 // =============================================================================================
 // precision self-test (float-predict contexts): the predict path at the training inputs against the

@@ -274,6 +274,24 @@ bool small_fit_eligible(int64_t n, int dp);
 template <typename T, typename TP>
 int launch_small_fit(hipStream_t st, const SmallFitArgs& args);
 
+// the same evaluation at B values of theta in ONE launch, one workgroup per theta (multi-start hyper-parameter search):
+// loss, gradient and the factorisation's verdict per entry and nothing else -- no buffer a predict or a later fit reads
+// is written, so a resident posterior stays as it is
+constexpr int kSmallBatchMax = 256;   // workgroups per launch: one per CU (the LDS of one fills a CU's)
+constexpr int kSmallBatchTheta = 56;  // doubles per theta record: [0] variance, [1] noise, [2] mean c, [8 + k] lengthscale of
+                                      // padded dimension k < 48 (isotropic: repeated) -- the hyper block's layout
+struct SmallBatchArgs {
+  const double* x64;
+  const double* y64;
+  const double* theta;  // [B][kSmallBatchTheta], device memory
+  double* loss;         // [B]
+  double* grad;         // [B][n_ls + 3]: d nlml / d (ls..., variance, noise, c)
+  int* info;            // [B]: failing pivot, INT_MAX = positive definite
+  int n, d, dp, kernel, n_ls, want_grad;
+};
+template <typename T, typename TP>
+int launch_small_fit_batch(hipStream_t st, const SmallBatchArgs& args, int b);
+
 // precision self-test: predictions at the training inputs vs the closed form the fit implies;
 // out[6] = max |d mean|, max |d var|, max |y - c|, min predicted var, max |alpha|, max_i (K_y^-1)_ii
 template <typename T>

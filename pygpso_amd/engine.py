@@ -239,6 +239,50 @@ class HipGPEngine:
             self._check(rc)
         return nl.value, ga.copy(), ta.copy()
 
+    def fit_batch_max(self):
+        """Entries one ``gpso_fit_eval_u_batch`` call may hold for the resident data (256 where the one-launch fit applies,
+        0 otherwise: N > 128, or N > 64 with a padded D > 32)."""
+        return int(self._lib.gpso_fit_batch_max(self._h))
+
+    def fit_eval_u_batch(self, kernel, U, n_ls, train_mean, mean_c_fixed=0.0):
+        """``fit_eval_u`` at every row of ``U [B, nu]``: the pending evaluations of a multi-start hyper-parameter search.
+        Where the one-launch fit applies they run as launches of up to 256 workgroups, one per row
+        (``gpso_fit_eval_u_batch``), bit-identical to the single calls, and the resident posterior is left alone.
+        Elsewhere (``fit_batch_max() == 0``) the rows go through ``fit_eval_u`` one after another: correct, no faster, and
+        -- as any fit -- the resident posterior is replaced.  Returns (loss [B], grad [B, nu], ok [B]); a row whose matrix
+        is not positive definite (or whose theta the library refuses) has ok False and NaN loss and gradient."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        nu = int(n_ls) + 2 + (1 if train_mean else 0)
+        U = L.as_f64(np.atleast_2d(U))
+        if U.ndim != 2 or U.shape[1] != nu:
+            raise ValueError(f"U must be [B, {nu}]")
+        B = U.shape[0]
+        loss = np.full(B, np.nan)
+        grad = np.full((B, nu), np.nan)
+        ok = np.zeros(B, dtype=bool)
+        cap = self.fit_batch_max()
+        if cap < 0:
+            self._check(cap)
+        if cap == 0:
+            for b in range(B):
+                try:
+                    loss[b], grad[b], _ = self.fit_eval_u(kid, U[b], n_ls, train_mean, mean_c_fixed)
+                    ok[b] = True
+                except (np.linalg.LinAlgError, ValueError):
+                    pass
+            return loss, grad, ok
+        for lo in range(0, B, cap):
+            hi = min(B, lo + cap)
+            u = np.ascontiguousarray(U[lo:hi])
+            f = np.empty(hi - lo, dtype=np.float64)
+            g = np.empty((hi - lo, nu), dtype=np.float64)
+            st = np.empty(hi - lo, dtype=np.intc)
+            self._check(self._lib.gpso_fit_eval_u_batch(self._h, kid, L.dptr(u), hi - lo, int(n_ls), 1 if train_mean else 0,
+                                                        float(mean_c_fixed), L.dptr(f), L.dptr(g),
+                                                        st.ctypes.data_as(C.POINTER(C.c_int)), None))
+            loss[lo:hi], grad[lo:hi], ok[lo:hi] = f, g, st == L.OK
+        return loss, grad, ok
+
     def append(self, Xnew, ynew):
         """``gpso_append``: k new training points extend the resident posterior at its hyper-parameters (two passes over
         L^-1 instead of a factorisation).  Returns (nlml of the N + k points, in_place): ``in_place`` False when the

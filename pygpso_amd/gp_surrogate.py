@@ -486,6 +486,20 @@ class GPRSurrogate(GPSurrogate):
         return np.flatnonzero(~held)
 
     # -- persistence: points JSON (reference schema) + hyper-parameters as plain JSON ---------------
+    def _optimiser_record(self):
+        """["Scipy"] as ever; a multi-start optimiser adds its settings (explicit ``starts`` are not kept: they belong to one
+        problem).  A record without them loads as ``restarts=1``."""
+        opt = self.optimiser
+        if isinstance(opt, Scipy) and getattr(opt, "restarts", 1) > 1:
+            return ["Scipy", {"restarts": opt.restarts, "restart_scale": opt.restart_scale, "seed": opt.seed}]
+        return [type(opt).__name__]
+
+    @staticmethod
+    def _optimiser_from_record(record):
+        extra = record[1] if len(record) > 1 and isinstance(record[1], dict) else {}
+        return Scipy(restarts=extra.get("restarts", 1), restart_scale=extra.get("restart_scale", 1.0),
+                     seed=extra.get("seed", 0))
+
     def save(self, folder):
         os.makedirs(folder, exist_ok=True)
         self.points.save(os.path.join(folder, self.POINTS_FILE))
@@ -500,7 +514,7 @@ class GPRSurrogate(GPSurrogate):
             "gpr_meanf_shape": [],
             "gp_varsigma": self.gp_varsigma,
             "gp_likelihood": self.gp_lik_sigma,
-            "optimiser": [type(self.optimiser).__name__],
+            "optimiser": self._optimiser_record(),
             "dtype": self.dtype,
             "refit_every": self.refit_every,  # (not in the reference's schema: an extra key; 1 = the reference's behaviour)
             "refit_guard": self.refit_guard,
@@ -527,7 +541,7 @@ class GPRSurrogate(GPSurrogate):
         model = HipGPR(data=(x, y), kernel=kernel, mean_function=meanf,
                        noise_variance=params[".likelihood.variance"], dtype=info.get("dtype", "float64"),
                        device=device, engine=engine, devices=devices)
-        return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=Scipy(),
+        return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=cls._optimiser_from_record(info["optimiser"]),
                    gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
                    points=points, gpflow_model=model, dtype=info.get("dtype", "float64"), device=device,
                    devices=devices, refit_every=info.get("refit_every", 1), refit_guard=info.get("refit_guard", 2.0))

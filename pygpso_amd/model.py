@@ -224,6 +224,31 @@ class HipGPR:
             gu[k + 2] = g[k + 2]
         return f, gu
 
+    def _loss_and_grad_batch(self, U):
+        """``_loss_and_grad`` at every row of ``U [B, nu]`` -- the pending evaluations of a multi-start search
+        (``Scipy(restarts=R)``) in one launch where the one-launch fit applies.  Returns (loss [B], grad [B, nu], ok [B]);
+        a failed row (not positive definite) has ok False.  The batched launch leaves the device's posterior alone, so
+        what the model knows about it stands; the row-by-row fallbacks (N > 128, an engine without the batched call) replace
+        it as any fit does."""
+        U = np.atleast_2d(np.asarray(U, dtype=np.float64))
+        if not hasattr(self.engine, "fit_eval_u_batch"):
+            # an engine without the batched call (a multi-GPU group, a test double): the rows one after another
+            loss, grad, ok = np.full(U.shape[0], np.nan), np.full(U.shape, np.nan), np.zeros(U.shape[0], dtype=bool)
+            for b, u in enumerate(U):
+                try:
+                    loss[b], grad[b] = self._loss_and_grad(u)
+                    ok[b] = True
+                except np.linalg.LinAlgError:
+                    self._device_theta = None
+            return loss, grad, ok
+        if self.engine.fit_batch_max() == 0:
+            self._device_theta = None
+            self._resident = False
+        loss, grad, ok = self.engine.fit_eval_u_batch(self.kernel.name, U, self.n_ls, self._train_mean,
+                                                      float(self.mean_function.c))
+        self.num_loss_evals += U.shape[0]
+        return loss, grad, ok
+
     @staticmethod
     def _theta_key(name, ls, var, noise, c):
         return (name, np.asarray(ls, dtype=np.float64).tobytes(), float(var), float(noise), float(c))

@@ -21,6 +21,8 @@ from .model import HipGPR, _as_result
 
 
 class HipSGPR(HipGPR):
+    _loss_and_grad_batch = None  # no batched evaluation of this loss: Scipy(restarts > 1) refuses the model
+
     def __init__(self, data, kernel, mean_function=None, noise_variance=1.0e-3, num_inducing=256, inducing="greedy",
                  dtype="float64", device=0, engine=None, engine_options=None, train_inducing=False):
         """``num_inducing``: M.  ``inducing``: "greedy" or an [M, D] array used as given (with ``train_inducing``: where Z

@@ -54,6 +54,8 @@ def carried_order(old_x, old_y, x, y):
 
 
 class HipVGP(HipGPR):
+    _loss_and_grad_batch = None  # no batched evaluation of this loss: Scipy(restarts > 1) refuses the model
+
     def __init__(self, data, kernel, mean_function=None, likelihood=None, dtype="float64", device=0, engine=None,
                  engine_options=None, q_mu=None, q_sqrt=None):
         """``dtype``: "float64" or "mixed" (float64 training, float predict arithmetic).  ``q_mu`` [N] / [N, 1] and
