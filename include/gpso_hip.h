@@ -135,7 +135,7 @@ typedef struct gpso_ctx gpso_ctx;
                                    /* modelled makespan (C3: one -- 256 workgroups of 288 k-steps instead of 2 048 of 8 .. 64; ragged   */
                                    /* batches and batches whose live count only the device knows: one row block per workgroup);        */
                                    /* 0: one row block per workgroup always (rounds 1-5); v >= 2: exactly min(v, row blocks)            */
-                                   /* workgroups per leaf tile (tests).  Process-wide.  Same bits whatever the value.                   */
+                                   /* workgroups per leaf tile (tests).  Per context.   Same bits whatever the value.                   */
 /* floating-point options (gpso_set_option_f64): tolerances of the self-test */
 #define GPSO_OPTF_TOL_VAR 100  /* max |d var| at the training inputs, relative to the kernel variance (default 1e-4; GPSO_F32: 1e-3) */
 #define GPSO_OPTF_TOL_MEAN 101 /* max |d mean| at the training inputs, relative to max |y - c|   (default 1e-4; GPSO_F32: 1e-3) */
@@ -614,7 +614,7 @@ double gpso_last_ms(gpso_ctx* ctx, int what);
  * the fit is priced against -- the f32 / f64 matrix instruction, or the two-level float fit's 16-bit pieces: six bf16 or
  * three fp16 MFMAs per f32 product).
  * what = 3: how many workgroups shared a leaf tile's row blocks in the last launch of a split predict kernel (GPSO_OPT_ROW_LOOP;
- * process-wide, for tests and tools). */
+ * per context: the last launch THIS context made; for tests and tools). */
 #define GPSO_FITMATH_NONE 0
 #define GPSO_FITMATH_SMALL 1   /* N <= 128: one launch, vector arithmetic in double */
 #define GPSO_FITMATH_F32 2     /* v_mfma_f32_16x16x4_f32 (float fits up to N_pad = 3584, or GPSO_OPT_FIT_BF16_SYRK = 0) */

@@ -200,7 +200,10 @@ struct gpso_ctx {
   // handed to a collective again either (need_comm refuses until gpso_comm_destroy + gpso_comm_init)
   std::atomic<bool> comm_aborted{false};
   int rank = 0, world = 1;
-  int64_t last_count[3] = {0, 0, 0};  // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit
+  // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit; [3] workgroups per
+  // leaf tile of this context's last split-kernel launch
+  int64_t last_count[4] = {0, 0, 0, 0};
+  int cu_count = 256;  // compute units of `device` (gpso_create): sizes the split predict kernels' and the bf16 GEMMs' grids
   std::string err;
   Engine* eng = nullptr;
   hipEvent_t ev_wait = nullptr;  // completion marker of the call in flight
@@ -408,6 +411,7 @@ struct EngineT : Engine {
   bool gen_decided = false;     // AUTO: has the self-test ruled on this posterior?
   bool gen32_inputs_ok = false; // xs32 / xnorm32 / xs_p32 match the resident posterior
   int split_variant = GPSO_SPLIT_KERNEL_AUTO;  // GPSO_OPT_SPLIT_KERNEL
+  int row_loop = 1;  // GPSO_OPT_ROW_LOOP (leaf_split.hpp: leaf_row_splits)
   int contraction = GPSO_CONTRACTION_AUTO;     // GPSO_OPT_CONTRACTION
   // the x.x* contraction of the fp16-split kernel runs on the fp16 pipe under float generation (D_pad + 1 slots in at most
   // two chunks of 32: every D this library accepts).  Measured in one process on one posterior (tools/c16_check.py,
@@ -540,7 +544,7 @@ struct EngineT : Engine {
         return GPSO_OK;
       case GPSO_OPT_ROW_LOOP:
         if (value < 0) return ctx->fail(GPSO_E_ARG, "row loop: 0, 1 or a split count >= 2");
-        gpso::g_leaf_row_loop = (int)value;  // (process-wide: a property of the kernels' launch, not of a posterior)
+        row_loop = value;
         return GPSO_OK;
       case GPSO_OPT_FIT_OVERLAP:
         if (value < 0) return ctx->fail(GPSO_E_ARG, "fit overlap must be >= 0");
@@ -1003,6 +1007,7 @@ struct EngineT : Engine {
             HIPCHECK(hipEventCreateWithFlags(&ctx->ev_col, hipEventDisableTiming));
             HIPCHECK(hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
           }
+          planes.cu_count = ctx->cu_count;
           planes.side = ctx->side_stream;
           planes.ev_col = ctx->ev_col;
           planes.ev_chain = ctx->ev_chain;
@@ -2442,7 +2447,6 @@ struct EngineT : Engine {
       // live, the caller's leaves in float.  A NaN coordinate reaches the partial sums by itself on this path (no clamp in
       // float generation), so the finalize stage needs no norms.
       RawLeaves rawl{};
-      rawl.step32 = split_variant == GPSO_SPLIT_KERNEL_FUSED32;
       if constexpr (kFloatPredict && sizeof(TG) == 4) {
         if (fuse_prep && use_bf16 && !prepared && xs_dtype == GPSO_F32 && nchunk == 1 && m_live_c == nullptr && c16_in_use(false)) {
           rawl.x = reinterpret_cast<const float*>(src);
@@ -2468,11 +2472,18 @@ struct EngineT : Engine {
       }
       if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs], s));
       if (use_bf16) {
-        if constexpr (kFloatPredict)
-          rc = launch_leaf_tiles_bf16<TG>(s, nsplit(), split_planes(), xsp, xnr, as<float>(alpha), as<TG>(leaves_s),
-                                          as<TG>(lnorm), as<double>(pvar), as<double>(pmean), npad, dp / 4, mp,
-                                          kp, m_live_c, f16_split() ? f16_scale() : nullptr, split_variant,
-                                          c16_in_use(sizeof(TG) == 8) ? xs_h16.p : nullptr, as<float>(c16_scal), n, rawl);
+        if constexpr (kFloatPredict) {
+          SplitLeafLaunch<TG> a;
+          a.nsplit = nsplit(); a.linv_b = split_planes(); a.f16_inv_scale_a = f16_split() ? f16_scale() : nullptr;
+          a.xs_p = xsp; a.xnorm = xnr; a.alpha = as<float>(alpha);
+          a.xs_h16 = c16_in_use(sizeof(TG) == 8) ? xs_h16.p : nullptr; a.c16_scale = as<float>(c16_scal);
+          a.leaves_s = as<TG>(leaves_s); a.lnorm = as<TG>(lnorm); a.raw = rawl; a.m_live = m_live_c;
+          a.part_var = as<double>(pvar); a.part_mean = as<double>(pmean);
+          a.npad = npad; a.dp4 = dp / 4; a.mpad = mp; a.n_rows = n;
+          a.step32 = split_variant == GPSO_SPLIT_KERNEL_FUSED32; a.row_loop = row_loop; a.cu_count = ctx->cu_count;
+          a.splits_out = &ctx->last_count[3];
+          rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+        }
       } else {
         rc = launch_leaf_tiles<TP, TG>(s, as<TP>(linv_p), xsp, xnr, as<TP>(alpha), as<TG>(leaves_s),
                                        as<TG>(lnorm), as<double>(pvar), as<double>(pmean), npad, dp / 4, mp, kp,
@@ -3923,6 +3934,8 @@ int gpso_create(gpso_ctx** out, int device, int dtype) {
   gpso_ctx* ctx = new gpso_ctx();
   ctx->device = device;
   ctx->dtype = dtype;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->cu_count = cus;
   ContextPool::Set pooled;
   if (ContextPool::get().take(device, pooled)) {  // a destroyed context's stream, events and pinned buffers
     ctx->own_stream = pooled.stream;
@@ -4640,7 +4653,6 @@ int gpso_comm_abort(gpso_ctx* ctx) {
 
 int64_t gpso_last_count(gpso_ctx* ctx, int what) {
   if (!ctx || what < 0 || what > 3) return -1;
-  if (what == 3) return gpso::g_leaf_last_splits;
   return ctx->last_count[what];
 }
 

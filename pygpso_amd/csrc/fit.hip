@@ -1461,28 +1461,19 @@ __global__ __launch_bounds__(256, 1) void gemm_bf16_kernel(GemmBf16Desc g) {
   }
 }
 
-static int bf16_gemm_grid(int total_slots) {
-  static int cus[64] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64) dev = 0;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n / 8 * 8 > 0 ? n / 8 * 8 : 8;  // a multiple of the 8 XCDs
-  }
-  return std::min(total_slots, cus[dev]);
-}
+// workgroups of the persistent bf16 GEMM: one per compute unit of the fitting context's device (FitPlanes::cu_count),
+// a multiple of the 8 XCDs
+static int bf16_gemm_grid(int total_slots, int cu_count) { return std::min(total_slots, std::max(8, cu_count / 8 * 8)); }
 // reserve_cus: compute units left to another stream (a workgroup of this kernel fills a CU's LDS, so that many
 // CUs stay free for whatever else is in flight)
-static void launch_gemm_bf16(hipStream_t st, GemmBf16Desc g, int reserve_cus = 0) {
+static void launch_gemm_bf16(hipStream_t st, GemmBf16Desc g, int cu_count, int reserve_cus = 0) {
   if (g.np != 2) g.np = 3;
   const int lds = syrk_lds_bytes(g.np);
   const void* fn = g.np == 2 ? reinterpret_cast<const void*>(&gemm_bf16_kernel<2>) : reinterpret_cast<const void*>(&gemm_bf16_kernel<3>);
   if (ensure_dyn_lds(fn, lds)) return;
   g.tl = bf16_tiling(g);
-  int grid = bf16_gemm_grid(g.tl.total_slots);
-  if (reserve_cus > 0) grid = std::max(8, std::min(grid, (bf16_gemm_grid(INT_MAX) - reserve_cus) / 8 * 8));
+  int grid = bf16_gemm_grid(g.tl.total_slots, cu_count);
+  if (reserve_cus > 0) grid = std::max(8, std::min(grid, (bf16_gemm_grid(INT_MAX, cu_count) - reserve_cus) / 8 * 8));
   if (g.np == 2) hipLaunchKernelGGL(gemm_bf16_kernel<2>, dim3((unsigned)grid), dim3(256), lds, st, g);
   else hipLaunchKernelGGL(gemm_bf16_kernel<3>, dim3((unsigned)grid), dim3(256), lds, st, g);
 }
@@ -2218,13 +2209,13 @@ int launch_potrf(hipStream_t st, T* K, T* Lf, T* linv, T* work, T* kinv, int64_t
           GemmBf16Desc col = sy;  // its block column first: rows r1.., columns r1 .. r1 + wn
           col.n = (int)wn;
           col.lower_only = 0;
-          launch_gemm_bf16(st, col);
+          launch_gemm_bf16(st, col, planes->cu_count);
           (void)hipEventRecord(planes->ev_col, st);
           GemmBf16Desc rest = sy;  // then everything to the right of it (enqueued before the chain's 17 launches:
           rest.a_row0 = rest.b_row0 = r1 + wn;  // the host needs ~100 us for those)
           rest.C = reinterpret_cast<float*>(K + (r1 + wn) * npad + (r1 + wn));
           rest.m = rest.n = (int)(m2 - wn);
-          launch_gemm_bf16(st, rest, kLookaheadCus);
+          launch_gemm_bf16(st, rest, planes->cu_count, kLookaheadCus);
           (void)hipStreamWaitEvent(planes->side, planes->ev_col, 0);
           const int64_t off1 = r1 * npad + r1;
           potrf_block<T>(planes->side, K + off1, Lf + off1, linv + off1, work + off1, nullptr, npad,
@@ -2232,7 +2223,7 @@ int launch_potrf(hipStream_t st, T* K, T* Lf, T* linv, T* work, T* kinv, int64_t
           (void)hipEventRecord(planes->ev_chain, planes->side);
           chain_on_side = true;
         } else {
-          launch_gemm_bf16(st, sy);
+          launch_gemm_bf16(st, sy, planes->cu_count);
         }
       }
       continue;
@@ -2346,7 +2337,7 @@ void launch_trtri_bf16(hipStream_t st, float* linv, const FitPlanes& pl, int64_t
     a.nbatch = nb; a.batch_shift = 2 * s;
     a.out = WT; a.o_row0 = 0; a.o_col0 = s;
     a.out_t = none;
-    launch_gemm_bf16(st, a);
+    launch_gemm_bf16(st, a, pl.cu_count);
     GemmBf16Desc b{};  // Linv[B,A]
     b.np = pl.np;
     b.A = X; b.a_row0 = s; b.a_col0 = s;
@@ -2361,7 +2352,7 @@ void launch_trtri_bf16(hipStream_t st, float* linv, const FitPlanes& pl, int64_t
       b.out = none;
       if (!keep_xt) b.out_t = none;
     }
-    launch_gemm_bf16(st, b);
+    launch_gemm_bf16(st, b, pl.cu_count);
   }
 }
 bool trtri_bf16_applies(int64_t npad, int64_t first_level) {
@@ -2753,7 +2744,7 @@ void launch_gradient(hipStream_t st, const T* linv, const T* alpha, const double
       g.lower_only = 1;
       g.kmode = 2;
       g.nbatch = 1;
-      launch_gemm_bf16(st, g);
+      launch_gemm_bf16(st, g, xt_planes->cu_count);
     }
   } else if (!kinv_ready) {
     // Kinv = Linv^T Linv, lower tiles:  opA(i,k) = Linv[k][i],  opB(k,j) = Linv[k][j],  k >= 64 ti

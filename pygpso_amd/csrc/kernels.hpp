@@ -48,8 +48,6 @@ void launch_pack_linv_bf16(hipStream_t st, int nsplit, const TF* linv, int64_t n
 // c16: the contraction runs on the fp16 pipe (float generation only): the X fragments of a k-step and the leaf fragments
 // of a wave are fp16 piece pairs of 32-dimension chunks instead of float groups of four dimensions
 bool leaf_step32_built();  // predict_split_f32.hip: was the library built with -DGPSO_STEP32=1 (leaf_split.hpp)
-extern int g_leaf_last_splits;  // predict.hip: what the launcher of the split kernels chose last (gpso_last_count(ctx, 3))
-extern int g_leaf_row_loop;  // predict.hip: GPSO_OPT_ROW_LOOP (a workgroup of the split predict kernels loops over row blocks)
 inline int leaf_c16_chunks(int dp4) { return (dp4 + 8) / 8; }  // D_pad inputs + the norm slot, 32 slots per chunk
 inline size_t leaf_bf16_lds_bytes(int nsplit, int dp4, int tg_bytes, bool c16 = false) {
   const size_t xfrag = c16 ? (size_t)leaf_c16_chunks(dp4) * 4096 : (size_t)2 * dp4 * 64 * tg_bytes;
@@ -59,10 +57,6 @@ inline size_t leaf_bf16_lds_bytes(int nsplit, int dp4, int tg_bytes, bool c16 = 
 // floats ([0] max |x / l|, [1] := 2^sx, [2] := 2^-2sx); xs_h16: npad / 16 * leaf_c16_chunks * 2 KB
 void launch_gen_inputs_f16(hipStream_t st, const float* xs32, const float* xnorm32, int64_t npad, int dp, float* scal,
                            void* xs_h16);
-// f16_inv_scale_a != nullptr: the fp16 split (two pieces, three products; predict.hip) -- linv_b and the scale (device,
-// 2 floats: max |L^-1|, 2^-sa) come from launch_pack_linv_f16
-// FUSED: the fused step (round 4) or round 3's two-phase step -- same bits; one explicit instantiation per slice
-// (TG, FUSED, KS) in predict_split_*.hip
 // the caller's unscaled float leaves for the fp16-contraction kernels, whose prologue can scale them itself (round 5: the
 // prep launch and the dependency gap behind it are 12 us of a 740 us step at C3); x == nullptr: leaves_s / lnorm are read
 struct RawLeaves {
@@ -70,30 +64,48 @@ struct RawLeaves {
   const double* ls = nullptr;  // lengthscale per input dimension (device)
   int64_t m = 0;
   int d = 0;
-  bool step32 = false;  // (rides along: GPSO_SPLIT_KERNEL_FUSED32 -- the fused step on the 32x32x16 instruction, where built)
 };
-template <typename TG, bool FUSED, int KS /* kernel families 0-1 | 2-3 */>
-int launch_leaf_tiles_bf16_v(hipStream_t st, int nsplit, const void* linv_b, const TG* xs_p,
-                             const TG* xnorm, const float* alpha, const TG* leaves_s,
-                             const TG* lnorm, double* part_var, double* part_mean, int64_t npad,
-                             int dp4, int64_t mpad, const KernParams& kp, const int64_t* m_live,
-                             const float* f16_inv_scale_a, const void* xs_h16, const float* c16_scale, int64_t n_rows,
-                             const RawLeaves& rawl);
-// variant: GPSO_OPT_SPLIT_KERNEL (0 the fused step, 1 the two-phase step); xs_h16 and c16_scale both set: the contraction
-// on the fp16 pipe (fp16 split, float generation); n_rows: N (0: unknown) -- the fused step stops at the k-steps that
-// hold padding points only
+// What one launch of the split leaf-tile kernels reads and reports (launch_leaf_tiles_bf16): the posterior's operands,
+// the leaf batch, and the launching context's own settings -- nothing about a launch lives outside this struct
 template <typename TG>
-inline int launch_leaf_tiles_bf16(hipStream_t st, int nsplit, const void* linv_b, const TG* xs_p,
-                                  const TG* xnorm, const float* alpha, const TG* leaves_s,
-                                  const TG* lnorm, double* part_var, double* part_mean, int64_t npad,
-                                  int dp4, int64_t mpad, const KernParams& kp, const int64_t* m_live,
-                                  const float* f16_inv_scale_a = nullptr, int variant = 0, const void* xs_h16 = nullptr,
-                                  const float* c16_scale = nullptr, int64_t n_rows = 0, const RawLeaves& rawl = RawLeaves{}) {
-#define GPSO_V(FUSED, KS) launch_leaf_tiles_bf16_v<TG, FUSED, KS>(st, nsplit, linv_b, xs_p, xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, f16_inv_scale_a, xs_h16, c16_scale, n_rows, rawl)
+struct SplitLeafLaunch {
+  int nsplit = 2;                // pieces of L^-1: 2 -> bf16x3 (or f16x3: f16_inv_scale_a), 3 -> bf16x6
+  const void* linv_b = nullptr;  // nsplit * npad * npad 16-bit pieces (launch_pack_linv_bf16 / _f16)
+  const TG* xs_p = nullptr;
+  const TG* xnorm = nullptr;
+  const float* alpha = nullptr;
+  const TG* leaves_s = nullptr;
+  const TG* lnorm = nullptr;
+  double* part_var = nullptr;  // partial sums per row block of L^-1: [npad / 256][mpad] double
+  double* part_mean = nullptr;
+  int64_t npad = 0;  // a multiple of 256
+  int dp4 = 0;
+  int64_t mpad = 0;
+  const int64_t* m_live = nullptr;  // (nullable, device): number of live leaves; rows at or beyond it are padding
+  // != nullptr: the fp16 split (two pieces, three products; predict.hip) -- linv_b and the scale (device, 2 floats:
+  // max |L^-1|, 2^-sa) come from launch_pack_linv_f16
+  const float* f16_inv_scale_a = nullptr;
+  // both set: the contraction on the fp16 pipe as well (fp16 split, float generation; launch_gen_inputs_f16)
+  const void* xs_h16 = nullptr;
+  const float* c16_scale = nullptr;
+  int64_t n_rows = 0;  // N (0: unknown) -- the fused step stops at the k-steps that hold padding points only
+  RawLeaves raw;       // (fp16 contraction only)
+  bool step32 = false;  // GPSO_SPLIT_KERNEL_FUSED32 -- the fused step on the 32x32x16 instruction, where built
+  int row_loop = 1;     // GPSO_OPT_ROW_LOOP of the launching context (leaf_split.hpp: leaf_row_splits)
+  int cu_count = 256;   // compute units of the launching context's device
+  int64_t* splits_out = nullptr;  // (nullable) receives the workgroups per leaf tile the launcher chose
+};
+// FUSED: the fused step (round 4) or round 3's two-phase step -- same bits; one explicit instantiation per slice
+// (TG, FUSED, KS) in predict_split_*.hip
+template <typename TG, bool FUSED, int KS /* kernel families 0-1 | 2-3 */>
+int launch_leaf_tiles_bf16_v(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a);
+// variant: GPSO_OPT_SPLIT_KERNEL (0 the fused step, 1 the two-phase step)
+template <typename TG>
+inline int launch_leaf_tiles_bf16(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a, int variant = 0) {
   const bool low = kp.kernel == 0 || kp.kernel == 1;
-  const int rc = variant != 1 ? (low ? GPSO_V(true, 0) : GPSO_V(true, 1)) : (low ? GPSO_V(false, 0) : GPSO_V(false, 1));
-#undef GPSO_V
-  return rc;
+  auto* fn = variant != 1 ? (low ? launch_leaf_tiles_bf16_v<TG, true, 0> : launch_leaf_tiles_bf16_v<TG, true, 1>)
+                          : (low ? launch_leaf_tiles_bf16_v<TG, false, 0> : launch_leaf_tiles_bf16_v<TG, false, 1>);
+  return fn(st, kp, a);
 }
 // scal: 2 device floats -- [0] max |L^-1|, [1] := 2^-sa.  have_max false: the maximum is computed here first (memset +
 // absmax_kernel); true: the fit left it in scal[0] (launch_solve_alpha: its own pass over L^-1).
@@ -189,6 +201,7 @@ struct FitPlanes {
   hipStream_t inv = nullptr;
   hipEvent_t ev_panel = nullptr, ev_inv = nullptr;
   int overlap = 0;  // double fits: bit 0 look-ahead on `side`, bit 1 the inverse on `inv` (GPSO_OPT_FIT_OVERLAP)
+  int cu_count = 256;  // compute units of the fitting context's device: the grid of the persistent bf16 GEMMs
 };
 inline size_t fit_plane_set_bytes(int64_t npad) { return (size_t)3 * (size_t)npad * (size_t)npad * 2; }
 // power-of-two scales of the fp16 planes for hyper-parameters (variance, noise); false: a scale leaves the range in which

@@ -95,10 +95,6 @@ constexpr bool kEarlyDma = GPSO_EARLY_DMA != 0;  // the next row block's first D
 #define GPSO_STEP32 0
 #endif
 constexpr bool kLeafStep32 = GPSO_STEP32 != 0;
-// GPSO_OPT_ROW_LOOP (process-wide switch of the split kernels' workgroup shape; api.hip sets it): predict.hip owns both
-extern int g_leaf_row_loop;
-extern int g_leaf_last_splits;
-int leaf_cu_count();
 #ifndef GPSO_BSTAMP
 #define GPSO_BSTAMP(q, i)  // tools/micro/leaf_bf16_phases.hip defines this to record s_memtime stamps
 #endif
@@ -1151,8 +1147,8 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 // (128): 2; C5 share (512): 1; ragged batches (462 or 1 384 tiles): nbi -- a coarser grain there costs a whole round of tail
 // (measured: +4.7 % on bench.py --leaves grow --depth 11 with the first version of this rule, which only looked at the
 // workgroup count).  A batch whose live row count only the device knows (m_live) keeps one row block per workgroup.
-inline int leaf_row_splits(int64_t ltiles, int nbi, int ncu, bool live_known) {
-  const int mode = g_leaf_row_loop;
+// mode: the launching context's GPSO_OPT_ROW_LOOP; ncu: its device's compute units.
+inline int leaf_row_splits(int mode, int64_t ltiles, int nbi, int ncu, bool live_known) {
   if (mode == 0 || nbi <= 1) return nbi;
   if (mode >= 2) return std::min(mode, nbi);
   if (!live_known) return nbi;
@@ -1182,12 +1178,13 @@ inline int leaf_row_splits(int64_t ltiles, int nbi, int ncu, bool live_known) {
 // the launchers: each (TG, FUSED, KS) slice of the kernels is instantiated in a translation unit of its own
 // (launch_leaf_tiles_bf16_v<TG, FUSED, KS>, predict_split_*.hip), and the slices compile in parallel
 template <bool FUSED, int KS, int NS, typename TG, bool F16 = false, int C16 = 0>
-static int launch_leaf_tiles_bf16_ns(hipStream_t st, const void* linv_b, const TG* xs_p,
-                                     const TG* xnorm, const float* alpha, const TG* leaves_s,
-                                     const TG* lnorm, double* part_var, double* part_mean,
-                                     int64_t npad, int dp4, int64_t mpad, const KernParams& kp,
-                                     const int64_t* m_live, const float* inv_scale_a = nullptr,
-                                     const float* c16_scale = nullptr, int64_t n_rows = 0, const RawLeaves& rawl = RawLeaves{}) {
+static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a) {
+  const int64_t npad = a.npad, mpad = a.mpad;
+  const int dp4 = a.dp4;
+  // what only the fp16 contraction reads: its X fragments (in place of xs_p), its scales, the caller's raw leaves
+  const TG* xs_p = C16 ? static_cast<const TG*>(a.xs_h16) : a.xs_p;
+  const float* c16_scale = C16 ? a.c16_scale : nullptr;
+  const RawLeaves rawl = C16 ? a.raw : RawLeaves{};
   const int nbi = (int)(npad / 256);
   const dim3 grid((unsigned)(mpad / 256), (unsigned)nbi);
   constexpr bool STAG = kLeafStagger && FUSED && NS == 2 && F16 && C16 == 1;
@@ -1201,14 +1198,14 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const void* linv_b, const T
   (void)frexp(kp.variance, &eb);
   const float var_arg = F16 ? (float)ldexp(kp.variance, 14 - eb) : (float)kp.variance;
   const float inv_b = F16 ? (float)ldexp(1.0, eb - 14) : 1.0f;
-  const int q_max = n_rows > 0 ? (int)((n_rows + 31) / 32) : (int)(npad / 32);
-  const int S = leaf_row_splits(mpad / 256, nbi, leaf_cu_count(), m_live == nullptr);
-  g_leaf_last_splits = S;
+  const int q_max = a.n_rows > 0 ? (int)((a.n_rows + 31) / 32) : (int)(npad / 32);
+  const int S = leaf_row_splits(a.row_loop, mpad / 256, nbi, a.cu_count, a.m_live == nullptr);
+  if (a.splits_out != nullptr) *a.splits_out = S;
   const dim3 grid_s((unsigned)(mpad / 256), (unsigned)S);
   // FUSED (GPSO_SPLIT_KERNEL_AUTO): the fused step; otherwise round 3's two-phase step.  Same bits either way.
-  // rawl.step32 (GPSO_SPLIT_KERNEL_AUTO): the fused step on the 32x32x16 instruction, where that kernel exists
+  // a.step32 (GPSO_SPLIT_KERNEL_FUSED32): the fused step on the 32x32x16 instruction, where that kernel exists
   constexpr bool kHasM32 = kLeafStep32 && FUSED && F16 && NS == 2 && C16 != 0 && sizeof(TG) == 4;
-  const bool m32 = kHasM32 && rawl.step32;
+  const bool m32 = kHasM32 && a.step32;
   // xp: the last chunk of the fp16 contraction uses <= 16 slots (the scaled inputs and the norm slot behind them)
   const bool xp = C16 != 0 && dp4 * 4 + 1 - 32 * (C16 - 1) <= 16;
 #define GPSO_L1(K, M32, XP)                                                                         \
@@ -1216,9 +1213,9 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const void* linv_b, const T
     const int rc = ensure_dyn_lds((const void*)leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP>, (int)lds); \
     if (rc) return rc;                                                                              \
     hipLaunchKernelGGL((leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP>), grid_s, dim3(512), lds, st, \
-                       static_cast<const u32x4*>(linv_b), xs_p, xnorm, alpha, leaves_s, lnorm,      \
-                       part_var, part_mean, (int)(npad / 16), dp4, mpad, nbi, var_arg, m_live,      \
-                       inv_scale_a, inv_b, c16_scale, q_max, C16 ? rawl.x : nullptr, rawl.ls, rawl.m, rawl.d); \
+                       static_cast<const u32x4*>(a.linv_b), xs_p, a.xnorm, a.alpha, a.leaves_s, a.lnorm, \
+                       a.part_var, a.part_mean, (int)(npad / 16), dp4, mpad, nbi, var_arg, a.m_live, \
+                       a.f16_inv_scale_a, inv_b, c16_scale, q_max, rawl.x, rawl.ls, rawl.m, rawl.d); \
   } while (0)
 #define GPSO_L(K)                                   \
   do {                                              \
@@ -1248,24 +1245,17 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const void* linv_b, const T
 }
 
 template <typename TG, bool FUSED, int KS>
-int launch_leaf_tiles_bf16_v(hipStream_t st, int nsplit, const void* linv_b, const TG* xs_p,
-                           const TG* xnorm, const float* alpha, const TG* leaves_s,
-                           const TG* lnorm, double* part_var, double* part_mean, int64_t npad,
-                           int dp4, int64_t mpad, const KernParams& kp, const int64_t* m_live,
-                           const float* f16_inv_scale_a, const void* xs_h16, const float* c16_scale,
-                           int64_t n_rows, const RawLeaves& rawl) {
-  if (f16_inv_scale_a != nullptr) {  // fp16 split (nsplit == 2 pieces)
+int launch_leaf_tiles_bf16_v(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a) {
+  if (a.f16_inv_scale_a != nullptr) {  // fp16 split (nsplit == 2 pieces)
     if constexpr (sizeof(TG) == 4) {
-      if (xs_h16 != nullptr && c16_scale != nullptr) {  // ... with the contraction on the fp16 pipe as well
-        if (leaf_c16_chunks(dp4) == 1)
-          return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true, 1>(st, linv_b, static_cast<const TG*>(xs_h16), xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, f16_inv_scale_a, c16_scale, n_rows, rawl);
-        return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true, 2>(st, linv_b, static_cast<const TG*>(xs_h16), xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, f16_inv_scale_a, c16_scale, n_rows, rawl);
+      if (a.xs_h16 != nullptr && a.c16_scale != nullptr) {  // ... with the contraction on the fp16 pipe as well
+        if (leaf_c16_chunks(a.dp4) == 1) return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true, 1>(st, kp, a);
+        return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true, 2>(st, kp, a);
       }
     }
-    return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true>(st, linv_b, xs_p, xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, f16_inv_scale_a, nullptr, n_rows);
+    return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG, true>(st, kp, a);
   }
-  if (nsplit == 3)
-    return launch_leaf_tiles_bf16_ns<FUSED, KS, 3, TG>(st, linv_b, xs_p, xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, nullptr, nullptr, n_rows);
-  return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG>(st, linv_b, xs_p, xnorm, alpha, leaves_s, lnorm, part_var, part_mean, npad, dp4, mpad, kp, m_live, nullptr, nullptr, n_rows);
+  if (a.nsplit == 3) return launch_leaf_tiles_bf16_ns<FUSED, KS, 3, TG>(st, kp, a);
+  return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG>(st, kp, a);
 }
 }  // namespace gpso

@@ -5,6 +5,6 @@
 #include "leaf_split.hpp"
 
 namespace gpso {
-template int launch_leaf_tiles_bf16_v<double, true, 0>(hipStream_t, int, const void*, const double*, const double*, const float*, const double*, const double*, double*, double*, int64_t, int, int64_t, const KernParams&, const int64_t*, const float*, const void*, const float*, int64_t, const RawLeaves&);
-template int launch_leaf_tiles_bf16_v<double, true, 1>(hipStream_t, int, const void*, const double*, const double*, const float*, const double*, const double*, double*, double*, int64_t, int, int64_t, const KernParams&, const int64_t*, const float*, const void*, const float*, int64_t, const RawLeaves&);
+template int launch_leaf_tiles_bf16_v<double, true, 0>(hipStream_t, const KernParams&, const SplitLeafLaunch<double>&);
+template int launch_leaf_tiles_bf16_v<double, true, 1>(hipStream_t, const KernParams&, const SplitLeafLaunch<double>&);
 }  // namespace gpso

@@ -128,7 +128,7 @@ class HipGPEngine:
         self._check(self._lib.gpso_set_option(self._h, L.OPT_SMALL_CALLS, int(on)))
 
     def set_row_loop(self, on):
-        """GPSO_OPT_ROW_LOOP (process-wide): 1 / True = a workgroup of the split predict kernels keeps its leaf tile and loops
+        """GPSO_OPT_ROW_LOOP (per context): 1 / True = a workgroup of the split predict kernels keeps its leaf tile and loops
         over row blocks, the launcher choosing how many workgroups share a tile (default); 0 = one row block per workgroup
         (rounds 1-5); v >= 2 = exactly min(v, row blocks) workgroups per leaf tile.  Same bits."""
         self._check(self._lib.gpso_set_option(self._h, L.OPT_ROW_LOOP, int(on)))

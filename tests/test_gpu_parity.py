@@ -1254,16 +1254,12 @@ def test_row_block_loop_gives_the_one_row_block_kernels_bits(dtype, math, n, d, 
     Xs = synthetic_leaves(m, d).astype(np.float32)
     seg = np.array([0, m // 3, m // 3, m - 5, m], dtype=np.int64)
     out = {}
-    try:
-        for on in (1, 0, 2, 3, 4, 1000):  # (2, 3, 4, 1000: that many workgroups per leaf tile, capped at the row blocks)
-            eng.set_row_loop(on)
-            for which in ("auto", "two-phase"):
-                eng.set_split_kernel(which)
-                mean, var = eng.predict(Xs)
-                out[(on, which)] = (mean.tobytes(), var.tobytes(), tuple(a.tobytes() for a in eng.best_ucb(Xs, VS, seg)))
-    finally:
-        eng.set_row_loop(1)
-        eng.set_split_kernel("auto")
+    for on in (1, 0, 2, 3, 4, 1000):  # (2, 3, 4, 1000: that many workgroups per leaf tile, capped at the row blocks)
+        eng.set_row_loop(on)
+        for which in ("auto", "two-phase"):
+            eng.set_split_kernel(which)
+            mean, var = eng.predict(Xs)
+            out[(on, which)] = (mean.tobytes(), var.tobytes(), tuple(a.tobytes() for a in eng.best_ucb(Xs, VS, seg)))
     assert len(set(out.values())) == 1, [k for k, v in out.items() if v != out[(0, "auto")]]
 
 
@@ -1283,11 +1279,107 @@ def test_row_block_split_count_follows_the_makespan_model():
         eng.best_ucb(synthetic_leaves(m, 12).astype(np.float32), VS)
         assert eng.last_count(3) == want, (m, eng.last_count(3))
     eng.set_row_loop(0)
-    try:
-        eng.best_ucb(synthetic_leaves(65536, 12).astype(np.float32), VS)
-        assert eng.last_count(3) == nbi
-    finally:
-        eng.set_row_loop(1)
+    eng.best_ucb(synthetic_leaves(65536, 12).astype(np.float32), VS)
+    assert eng.last_count(3) == nbi
+    eng.set_row_loop(1)
     boxes = np.array([[[0.0, 1.0 / 3]] + [[0.0, 1.0]] * 11, [[2.0 / 3, 1.0]] + [[0.0, 1.0]] * 11])
     eng.best_ucb_grow(boxes, 9, VS)
     assert eng.last_count(3) == nbi
+
+
+def _leaf_row_splits(mode, ltiles, nbi, ncu, live_known=True):
+    """leaf_row_splits (leaf_split.hpp) restated: workgroups per leaf tile for GPSO_OPT_ROW_LOOP = mode."""
+    if mode == 0 or nbi <= 1:
+        return nbi
+    if mode >= 2:
+        return min(mode, nbi)
+    if not live_known:
+        return nbi
+    prologue = 1.2
+    total = 4.0 * nbi * (nbi + 1)
+    best, best_s = max(ltiles * (total + prologue * nbi) / ncu + 8.0, 8.0 * nbi + prologue), nbi
+    S = nbi // 2
+    while S >= 1:
+        heaviest = 0.0
+        for split in range(S):
+            w, j = 0.0, 0
+            while True:
+                rank = j * S + ((S - 1 - split) if j & 1 else split)
+                if rank >= nbi:
+                    break
+                w += 8.0 * (nbi - rank)
+                j += 1
+            heaviest = max(heaviest, w)
+        t = ((ltiles * S + ncu - 1) // ncu) * (heaviest + prologue)
+        if t <= best:
+            best, best_s = t, S
+        S //= 2
+    return best_s
+
+
+# the smallest shape at which the split count can differ: four 256-row blocks, two leaf tiles
+_ROW_LOOP_SHAPE = (1024, 6, 300)
+
+
+def _row_loop_engine(X, y, th, row_loop=None):
+    from pygpso_amd import HipGPEngine
+
+    eng = HipGPEngine("float32", predict_math="f16x3", precision_check=False)
+    _fit(eng, X, y, th, grad=False)
+    if row_loop is not None:
+        eng.set_row_loop(row_loop)
+    return eng
+
+
+def test_row_loop_option_and_split_count_belong_to_one_context():
+    """GPSO_OPT_ROW_LOOP set on one context steers that context's launches only, and gpso_last_count(ctx, 3) reports the last
+    launch that context made: two engines on the same data with different options keep their own counts across interleaved
+    calls, and a third that was never given the option launches by the default rule and returns the same bits."""
+    import torch
+
+    n, d, m = _ROW_LOOP_SHAPE
+    X, y, th = _problem(n, d, variance=1.0)
+    Xs = synthetic_leaves(m, d).astype(np.float32)
+    A, B = _row_loop_engine(X, y, th, 0), _row_loop_engine(X, y, th, 2)
+    A.best_ucb(Xs, VS)
+    B.best_ucb(Xs, VS)
+    assert A.last_count(3) == 4 and B.last_count(3) == 2, (A.last_count(3), B.last_count(3))
+    A.best_ucb(Xs, VS)
+    assert A.last_count(3) == 4 and B.last_count(3) == 2, (A.last_count(3), B.last_count(3))
+    C = _row_loop_engine(X, y, th)
+    out = []
+    for eng in (A, B, C):
+        mean, var = eng.predict(Xs)
+        out.append((mean.tobytes(), var.tobytes(), tuple(a.tobytes() for a in eng.best_ucb(Xs, VS))))
+    assert out[0] == out[1] == out[2]
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    assert C.last_count(3) == _leaf_row_splits(1, (m + 255) // 256, n // 256, ncu)
+    assert A.last_count(3) == 4 and B.last_count(3) == 2, (A.last_count(3), B.last_count(3))
+
+
+def test_row_loop_option_and_split_count_per_context_from_two_threads():
+    """The same from one host thread per engine (what HipGPEngineGroup does per device): every call reports its own
+    context's split count, every time -- nothing a launch reads or writes is shared between contexts."""
+    import threading
+
+    n, d, m = _ROW_LOOP_SHAPE
+    X, y, th = _problem(n, d, variance=1.0)
+    Xs = synthetic_leaves(m, d).astype(np.float32)
+    failures = []
+
+    def work(eng, want):
+        try:
+            for it in range(20):
+                eng.best_ucb(Xs, VS)
+                got = eng.last_count(3)
+                if got != want:
+                    failures.append((want, it, got))
+        except Exception as e:  # noqa: BLE001  (reported by the assertion below)
+            failures.append((want, repr(e)))
+
+    threads = [threading.Thread(target=work, args=(_row_loop_engine(X, y, th, on), want)) for on, want in ((0, 4), (2, 2))]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    assert not failures, failures

@@ -75,12 +75,16 @@ int main(int argc, char** argv) {
     launch_pack_linv_bf16<float>(0, ns, dl, npad, npad, lb);
   }
   KernParams kp{0, 1.0, 1e-3, 0.0};
+  SplitLeafLaunch<float> args;  // (row_loop 1, 256 compute units: the defaults)
+  args.nsplit = ns; args.linv_b = lb; args.f16_inv_scale_a = f16 ? f16_scal : nullptr;
+  args.xs_p = dx; args.xnorm = dn; args.alpha = da; args.leaves_s = dlv; args.lnorm = dln;
+  args.part_var = pv; args.part_mean = pm; args.npad = npad; args.dp4 = dp4; args.mpad = m;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int rep = 0; rep < 6; ++rep) {
     hipEventRecord(e0, 0);
     if (stream) launch_leaf_tiles_bf16s(0, ns, lb, dxw, da, dlv, dln, pv, pm, npad, dp, dp, m, kp, nullptr);
     else if (wide) launch_leaf_tiles_bf16w(0, ns, lb, dxw, da, dlv, dln, pv, pm, npad, dp, dp, m, kp, nullptr);
-    else launch_leaf_tiles_bf16<float>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr, f16 ? f16_scal : nullptr, two_phase ? 1 : 0);
+    else launch_leaf_tiles_bf16<float>(0, kp, args, two_phase ? 1 : 0);
     hipEventRecord(e1, 0);
     hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);

@@ -50,10 +50,14 @@ int main(int argc, char** argv) {
   hipMemcpy(dlv, lv.data(), lv.size() * 4, hipMemcpyHostToDevice); hipMemcpy(dln, ln.data(), m * 4, hipMemcpyHostToDevice);
   launch_pack_linv_f16<float>(0, dl, npad, npad, f16_scal, planes);
   KernParams kp{0, 1.0, 1e-3, 0.0};
+  SplitLeafLaunch<float> args;  // (row_loop 1, 256 compute units: the defaults)
+  args.nsplit = ns; args.linv_b = planes; args.f16_inv_scale_a = f16_scal;
+  args.xs_p = dx; args.xnorm = dn; args.alpha = da; args.leaves_s = dlv; args.lnorm = dln;
+  args.part_var = pv; args.part_mean = pm; args.npad = npad; args.dp4 = dp4; args.mpad = m;
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int rep = 0; rep < 5; ++rep) {
     hipEventRecord(e0, 0);
-    launch_leaf_tiles_bf16<float>(0, ns, planes, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr, f16_scal, variant);
+    launch_leaf_tiles_bf16<float>(0, kp, args, variant);
     hipEventRecord(e1, 0);
     hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);

@@ -52,15 +52,20 @@ static void run(int64_t npad, int d, int ns, int64_t m, int reps) {
   void* lb2; hipMalloc(&lb2, (size_t)3 * npad * npad * 2);
   launch_pack_linv_bf16<float>(0, 5 - ns, dl, npad, npad, lb2);
   std::vector<double> mfirst(m0.size());
-  launch_leaf_tiles_bf16<TG>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);  // the instantiation's first launch
+  SplitLeafLaunch<TG> args;  // (row_loop 1, 256 compute units: the defaults)
+  args.nsplit = ns; args.linv_b = lb; args.xs_p = dx; args.xnorm = dn; args.alpha = da; args.leaves_s = dlv; args.lnorm = dln;
+  args.part_var = pv; args.part_mean = pm; args.npad = npad; args.dp4 = dp4; args.mpad = m;
+  SplitLeafLaunch<TG> other = args;  // the other instantiation of the kernel, on its own pieces
+  other.nsplit = 5 - ns; other.linv_b = lb2;
+  launch_leaf_tiles_bf16<TG>(0, kp, args);  // the instantiation's first launch
   hipDeviceSynchronize();
   hipMemcpy(mfirst.data(), pm, mfirst.size() * 8, hipMemcpyDeviceToHost);
-  for (int w = 0; w < 2; ++w) launch_leaf_tiles_bf16<TG>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);
+  for (int w = 0; w < 2; ++w) launch_leaf_tiles_bf16<TG>(0, kp, args);
   hipDeviceSynchronize();
   for (int rep = 0; rep < reps; ++rep) {
-    if (rep > 0) launch_leaf_tiles_bf16<TG>(0, 5 - ns, lb2, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);
+    if (rep > 0) launch_leaf_tiles_bf16<TG>(0, kp, other);
     hipMemset(pm, 0xff, m0.size() * 8); hipMemset(pv, 0xff, m0.size() * 8);
-    launch_leaf_tiles_bf16<TG>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);
+    launch_leaf_tiles_bf16<TG>(0, kp, args);
     hipDeviceSynchronize();
     hipMemcpy(m1.data(), pm, m1.size() * 8, hipMemcpyDeviceToHost); hipMemcpy(v1.data(), pv, v1.size() * 8, hipMemcpyDeviceToHost);
     if (rep == 0) { m0 = m1; v0 = v1; continue; }
@@ -112,10 +117,13 @@ static void dump_run() {
   hipMemcpyToSymbol(HIP_SYMBOL(gpso_probe_macc), &dd, sizeof(dd));
   KernParams kp{0, 1.0, 1e-3, 0.0};
   std::vector<float> A(nd), B(nd);
-  launch_leaf_tiles_bf16<TG>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);
+  SplitLeafLaunch<TG> args;
+  args.nsplit = ns; args.linv_b = lb; args.xs_p = dx; args.xnorm = dn; args.alpha = da; args.leaves_s = dlv; args.lnorm = dln;
+  args.part_var = pv; args.part_mean = pm; args.npad = npad; args.dp4 = dp4; args.mpad = m;
+  launch_leaf_tiles_bf16<TG>(0, kp, args);
   hipDeviceSynchronize();
   hipMemcpy(A.data(), dd, nd * 4, hipMemcpyDeviceToHost);
-  for (int w = 0; w < 3; ++w) launch_leaf_tiles_bf16<TG>(0, ns, lb, dx, dn, da, dlv, dln, pv, pm, npad, dp4, m, kp, nullptr);
+  for (int w = 0; w < 3; ++w) launch_leaf_tiles_bf16<TG>(0, kp, args);
   hipDeviceSynchronize();
   hipMemcpy(B.data(), dd, nd * 4, hipMemcpyDeviceToHost);
   size_t ndiff = 0;
