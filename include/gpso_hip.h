@@ -147,6 +147,7 @@ typedef struct gpso_ctx gpso_ctx;
 #define GPSO_MAT_GRAM 3  /* K + noise*I as assembled (only valid before factorisation: debug)    */
 #define GPSO_VEC_ALPHA 0 /* alpha = (K + noise*I)^-1 (y - c)                                     */
 #define GPSO_VEC_WHITE 1 /* a = L^-1 (y - c)                                                     */
+#define GPSO_VEC_NOISE_DIAG 2 /* s, the per-point noise of gpso_set_noise_diag (zeros when none is set); needs data only */
 
 /* ---- lifetime ---------------------------------------------------------------------------- */
 
@@ -177,6 +178,20 @@ int gpso_wait_stream(gpso_ctx* ctx, void* producer_stream);
 /* Replaces: GPSurrogate.current_training_data hand-off + `model.data = (x, y)`
  * (gpso/gp_surrogate.py:232-244, :498).  X[N*D], y[N] float64 host. */
 int gpso_set_data(gpso_ctx* ctx, const double* X, const double* y, int64_t n, int d);
+
+/* No counterpart in the reference (its pinned GPflow has one likelihood variance for all points; newer GPflow takes a
+ * per-point one): replaces nothing, adds the known variance of each observation -- e.g. of the mean of eval_repeats scores,
+ * which gpso/optimisation.py:220-241 reduces to that mean alone.  s[N] (host float64, s_i >= 0) is fixed, not trained:
+ * every later fit on this data factorises K_y = k(X, X) + diag(noise + s_i), noise being the trained shared variance of
+ * gpso_fit_eval / gpso_fit_eval_u / gpso_fit_eval_u_batch, whose NLML, alpha, L^-1 and gradient keep their formulas with
+ * that K_y (d K_y / d noise is still I).  Predictions add the shared noise only: s is not known at a new point.
+ * Call it after gpso_set_data with the same n.  s = NULL clears the vector; every gpso_set_data (and gpso_set_posterior)
+ * clears it too.  A resident posterior is invalidated as by new data: fit again before predicting.  The vector itself stays
+ * resident (N_pad doubles on the device, a host mirror for GPSO_VEC_NOISE_DIAG and the refits of gpso_append).
+ * GPSO_E_ARG: n is not the resident N, or some s_i is negative or not finite.  GPSO_E_STATE: no training data, or an
+ * asynchronous best-UCB call in flight.
+ * The VGP, SGPR, SVGP and inducing-point entry points return GPSO_E_ARG on a context with a vector set. */
+int gpso_set_noise_diag(gpso_ctx* ctx, const double* s /* [n] host, nullable */, int64_t n);
 
 /* Replaces: ONE evaluation of gpflow GPR.training_loss (+ its reverse-mode gradient) inside
  * optimiser.minimize (gpso/gp_surrogate.py:500-503).  Hyper-parameters are the CONSTRAINED values:
@@ -233,6 +248,14 @@ int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int
  * unchanged; GPSO_E_STATE without a posterior fitted on this context.  The gradient-side K^-1 (GPSO_MAT_KINV) is not
  * extended.  The precision self-test runs again before the next prediction of a float-predict context. */
 int gpso_append(gpso_ctx* ctx, const double* Xnew, const double* ynew, int64_t k, double* nlml);
+
+/* gpso_append for points that carry per-point noise (gpso_set_noise_diag): snew[k] (host float64, >= 0; NULL = zeros) is
+ * filed behind the resident vector and the appended block is K22 + diag(noise + snew_j) - L21 L21^T.  Statuses, the
+ * in-place / refit rule (a refit carries the whole vector along) and what stays resident are gpso_append's; additionally
+ * GPSO_E_ARG for a negative or non-finite snew_j.  On a context without a vector, a non-zero snew creates one with zeros
+ * for the resident points.  gpso_append itself, on a context with a vector set, appends zeros. */
+int gpso_append_noise(gpso_ctx* ctx, const double* Xnew, const double* ynew, const double* snew /* [k], nullable */,
+                      int64_t k, double* nlml);
 
 /* Interop / debug: install a posterior computed elsewhere (host float64: X[N*D], L[N*N] row-major
  * lower, alpha[N]) -- the device still derives L^-1 and its tile packing itself.  Mirrors loading

@@ -23,7 +23,7 @@ MATERN52, MATERN32, MATERN12, SQEXP = 0, 1, 2, 3
 MEM_HOST, MEM_DEVICE = 0, 1
 UNIQUE_ID_BYTES = 128
 MAT_CHOL, MAT_LINV, MAT_KINV, MAT_GRAM = 0, 1, 2, 3
-VEC_ALPHA, VEC_WHITE = 0, 1
+VEC_ALPHA, VEC_WHITE, VEC_NOISE_DIAG = 0, 1, 2
 SGPR_KUF, SGPR_LU, SGPR_LB, SGPR_CV = 0, 1, 2, 3
 LIK_GAUSSIAN, LIK_STUDENT_T, LIK_GAUSSIAN_GH = 0, 1, 2
 LIKELIHOOD_IDS = {"Gaussian": LIK_GAUSSIAN, "StudentT": LIK_STUDENT_T, "GaussianGH": LIK_GAUSSIAN_GH}
@@ -82,7 +82,9 @@ SIGNATURES = {
     "gpso_fit_batch_max": (C.c_int, [C.c_void_p]),
     "gpso_fit_eval_u_batch": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                         _c_double_p, _c_double_p, C.POINTER(C.c_int), _c_int64_p]),
+    "gpso_set_noise_diag": (C.c_int, [C.c_void_p, _c_double_p, C.c_int64]),
     "gpso_append": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p]),
+    "gpso_append_noise": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p]),
     "gpso_set_posterior": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p, C.c_int64,
                                      C.c_int, C.c_int, _c_double_p, C.c_int, C.c_double, C.c_double,
                                      C.c_double]),

@@ -81,7 +81,9 @@ struct Engine {
   virtual int fit_batch_max() = 0;
   virtual int fit_eval_batch(int kernel, const double* th, int nv, int n_ls, double* loss, double* grad, int* info) = 0;
   virtual int fit_eval_batch_check(int kernel, int b, int n_ls) = 0;
-  virtual int append(const double* Xnew, const double* ynew, int64_t k, double* nlml) = 0;
+  virtual int set_noise_diag(const double* s, int64_t n) = 0;
+  virtual bool has_noise_diag() const = 0;
+  virtual int append(const double* Xnew, const double* ynew, const double* snew, int64_t k, double* nlml) = 0;
   virtual int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,
                       double* var, int out_mem) = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
@@ -393,6 +395,15 @@ struct EngineT : Engine {
   DevBuf pl_L, pl_X, pl_XT, pl_WT;  // bf16 plane sets of the two-level float fit (kernels.hpp: FitPlanes)
   DevBuf app;                       // scratch of gpso_append (kernels.hpp: append_scratch_doubles)
   std::vector<double> x_host, y_host;  // host mirror of the training data (gpso_append's refit path needs all of it)
+  // per-point observation noise (gpso_set_noise_diag): K_y = k(X, X) + diag(noise + s_i), s fixed.  sdiag [npad] on the
+  // device (zero padding), read wherever a fit adds `noise` to a diagonal; s_dev() is NULL while none is set, and every
+  // such site then runs what it ran before the vector existed
+  DevBuf sdiag;
+  bool have_s = false;
+  std::vector<double> s_host;  // [n] host mirror (the refit paths of gpso_append, GPSO_VEC_NOISE_DIAG)
+  double s_max = 0.0;          // max s_i: fit_plane_scales' bounds
+  const double* s_dev() const { return have_s ? static_cast<const double*>(sdiag.p) : nullptr; }
+  bool has_noise_diag() const override { return have_s; }
   int fit_overlap = 2;              // GPSO_OPT_FIT_OVERLAP (bit 0 look-ahead, bit 1 overlapped inverse: the default): two-level double fits overlap chains, updates and the inverse (0: sequential, round 5)
   int fit_planes_mode = 2;          // GPSO_OPT_FIT_BF16_SYRK: 0 f32 MFMA | 1 bf16 pieces (6 MFMAs per product) | 2 fp16 pieces (3) where representable
   // predict math: the OPTION (math_auto: GPSO_MATH_AUTO) and what the resident posterior uses (math, and
@@ -458,7 +469,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -935,9 +946,45 @@ struct EngineT : Engine {
     if (X != x_host.data()) x_host.assign(X, X + (size_t)n * d);
     if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
     have_data = true;
+    have_s = false;  // (every gpso_set_data clears the per-point noise: it belonged to the rows just replaced)
+    s_host.clear();
+    s_max = 0.0;
     have_post = have_kinv = chol_valid = linv_p_valid = false;
     vgp_post = sgpr_post = svgp_post = false;
     if (!sg_keep) sg_have = sg_have_z = false;  // (the caller's own gpso_set_data: new data, no inducing points)
+    sg_factors = false;
+    st_done = st_have = false;
+    forget_peers();
+    return GPSO_OK;
+  }
+
+  // s[n_] >= 0 beside the resident data (NULL: none); the posterior is invalidated as by new data
+  int set_noise_diag(const double* sv, int64_t n_) override {
+    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_set_noise_diag before gpso_set_data");
+    int rc = refuse_if_async("gpso_set_noise_diag");
+    if (rc) return rc;
+    if (n_ != n) return ctx->fail(GPSO_E_ARG, "gpso_set_noise_diag: n=%lld does not match the resident data (N=%lld)", (long long)n_, (long long)n);
+    double top = 0.0;
+    if (sv != nullptr) {
+      for (int64_t i = 0; i < n; ++i) {
+        if (!(sv[i] >= 0.0) || !std::isfinite(sv[i]))
+          return ctx->fail(GPSO_E_ARG, "gpso_set_noise_diag: s[%lld]=%g must be finite and >= 0", (long long)i, sv[i]);
+        top = std::max(top, sv[i]);
+      }
+      if ((rc = ensure(sdiag, (size_t)npad * 8))) return rc;
+      double* stage = ctx->pinned_stage((size_t)npad);  // (waits for the stream)
+      if (!stage) return ctx->fail(GPSO_E_OOM, "pinned host staging");
+      std::memcpy(stage, sv, (size_t)n * 8);
+      std::memset(stage + n, 0, (size_t)(npad - n) * 8);
+      HIPCHECK(hipMemcpyAsync(sdiag.p, stage, (size_t)npad * 8, hipMemcpyHostToDevice, st()));
+      if (sv != s_host.data()) s_host.assign(sv, sv + (size_t)n);
+    } else {
+      s_host.clear();
+    }
+    have_s = sv != nullptr;
+    s_max = top;
+    have_post = have_kinv = chol_valid = linv_p_valid = false;
+    vgp_post = sgpr_post = svgp_post = false;
     sg_factors = false;
     st_done = st_have = false;
     forget_peers();
@@ -975,6 +1022,7 @@ struct EngineT : Engine {
       a.zero_tile_rows = small_tile_rows;  // (tile rows of linv_p beyond this fit's that may hold old data)
       small_tile_rows = (int)((n + 15) / 16);
       a.variance = variance; a.noise = noise; a.mean_c = mean_c;
+      a.sdiag = s_dev();
       a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
       a.Lf = Lf.p; a.linv = linv.p; a.kinv = grad ? kinvb.p : nullptr;
       a.white = white.p; a.alpha_f = alpha_f.p; a.alpha_p = alpha.p; a.linv_p = linv_p.p;
@@ -989,7 +1037,7 @@ struct EngineT : Engine {
     } else {
       if ((rc = scale_inputs())) return rc;
       int* info_dev = reinterpret_cast<int*>(as<double>(scal) + 1);
-      launch_gram<TF>(s, as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<TF>(K), info_dev);
+      launch_gram<TF>(s, as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<TF>(K), info_dev, s_dev());
       // (the single-level factorisation writes all of L^-1 that is ever read: no 4 N_pad^2-byte zero fill -- 10 us at C3)
       if (!potrf_is_single_level<TF>(npad, single_level_max))
         HIPCHECK(hipMemsetAsync(linv.p, 0, (size_t)npad * npad * sizeof(TF), s));
@@ -1013,7 +1061,7 @@ struct EngineT : Engine {
           planes.ev_chain = ctx->ev_chain;
           // fp16 pieces (three MFMAs per product) when the hyper-parameters leave every plane set inside fp16's range
           // after its power-of-two scaling; bf16 pieces (six) otherwise -- the fallback rung
-          if (fit_planes_mode == 2) (void)fit_plane_scales(variance, noise, planes);
+          if (fit_planes_mode == 2) (void)fit_plane_scales(variance, noise, planes, have_s ? s_max : 0.0);
           pl = &planes;
           ctx->last_count[2] = planes.np == 2 ? GPSO_FITMATH_F16X3 : GPSO_FITMATH_BF16X6;
         }
@@ -1157,6 +1205,7 @@ struct EngineT : Engine {
     a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.theta = as<double>(batch_theta);
     a.loss = host; a.grad = host + nv; a.info = reinterpret_cast<int*>(host + (size_t)nv * (1 + H));
     a.n = (int)n; a.d = d; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls_; a.want_grad = grad ? 1 : 0;
+    a.sdiag = s_dev();
     if (launch_small_fit_batch<TF, TP>(s, a, nv)) {
       rc = launch_status();
       return rc ? rc : ctx->fail(GPSO_E_HIP, "internal: the batched fit refused %d entries", nv);
@@ -1186,10 +1235,19 @@ struct EngineT : Engine {
   // ---- rank-k append at the resident hyper-parameters (append.hip) ------------------------------------------------------
   // Returns GPSO_OK when the resident factor was extended in place, 1 when the posterior of the n + k points was refitted
   // from scratch at the same hyper-parameters instead (gpso_last_error says why), or a negative status.
-  int append(const double* Xn, const double* yn, int64_t k, double* nlml) override {
+  // sn (nullable = zeros): the per-point noise of the new points; a context without a vector gets one (zeros for the
+  // resident rows) when some sn[j] is not zero
+  int append(const double* Xn, const double* yn, const double* sn, int64_t k, double* nlml) override {
     ctx->tick_timing();
     if (!Xn || !yn) return ctx->fail(GPSO_E_ARG, "Xnew / ynew must not be NULL");
     if (k < 1) return ctx->fail(GPSO_E_ARG, "need at least one new point (k=%lld)", (long long)k);
+    bool sn_nonzero = false;
+    if (sn != nullptr)
+      for (int64_t j = 0; j < k; ++j) {
+        if (!(sn[j] >= 0.0) || !std::isfinite(sn[j]))
+          return ctx->fail(GPSO_E_ARG, "gpso_append_noise: snew[%lld]=%g must be finite and >= 0", (long long)j, sn[j]);
+        sn_nonzero = sn_nonzero || sn[j] > 0.0;
+      }
     if (svgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SVGP predictive: its rows are the inducing points; set the grown data and train again");
     if (sgpr_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SGPR predictive: its rows are the inducing points; set the grown data and train again");
     if (vgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
@@ -1209,10 +1267,19 @@ struct EngineT : Engine {
       std::vector<double> X(x_host), y(y_host), ls(ls_host);
       X.insert(X.end(), Xn, Xn + (size_t)k * d);
       y.insert(y.end(), yn, yn + (size_t)k);
+      // (set_data clears the per-point noise: the refit carries it along, the new points' values behind the resident ones)
+      const bool with_s = have_s || sn_nonzero, had_s = have_s;
+      std::vector<double> sv;
+      if (with_s) {
+        sv = have_s ? s_host : std::vector<double>((size_t)n, 0.0);
+        if (sn != nullptr) sv.insert(sv.end(), sn, sn + (size_t)k);
+        else sv.resize((size_t)n_new, 0.0);
+      }
       const KernParams th = kp;
       const int nls = n_ls, d_ = d;
       const int64_t n_old = n;
       int rc = set_data(X.data(), y.data(), n_new, d_);
+      if (rc == GPSO_OK && with_s) rc = set_noise_diag(sv.data(), n_new);
       if (rc == GPSO_OK) rc = fit_eval(th.kernel, ls.data(), nls, th.variance, th.noise, th.mean_c, nlml, nullptr);
       if (rc < 0) {
         // the header's promise holds on this path too: a failed append leaves the posterior of the first n points resident
@@ -1222,6 +1289,10 @@ struct EngineT : Engine {
         X.resize((size_t)n_old * d_);
         y.resize((size_t)n_old);
         int rc2 = set_data(X.data(), y.data(), n_old, d_);
+        if (rc2 == GPSO_OK && had_s) {
+          sv.resize((size_t)n_old);
+          rc2 = set_noise_diag(sv.data(), n_old);
+        }
         if (rc2 == GPSO_OK) rc2 = fit_eval(th.kernel, ls.data(), nls, th.variance, th.noise, th.mean_c, nullptr, nullptr);
         if (rc2 < 0) return ctx->fail(rc, "%s (and the posterior of the first %lld points could not be restored: status %d -- "
                                           "gpso_set_data + gpso_fit_eval start over)", why.c_str(), (long long)n_old, rc2);
@@ -1235,16 +1306,27 @@ struct EngineT : Engine {
     int rc;
     const int kpad = append_kp((int)k);
     if ((rc = ensure(app, append_scratch_doubles(npad, kpad) * 8))) return rc;
-    double* stage = ctx->pinned_stage((size_t)k * d + (size_t)k);  // (waits for the stream)
+    // the first per-point noise of this context: the resident rows carry zeros.  The context only COUNTS as carrying a
+    // vector (have_s) once the append has succeeded: a failed one leaves it as it found it
+    const bool new_s = !have_s && sn_nonzero, use_s = have_s || new_s;
+    if (new_s) {
+      if ((rc = ensure(sdiag, (size_t)npad * 8))) return rc;
+      HIPCHECK(hipMemsetAsync(sdiag.p, 0, (size_t)npad * 8, s));
+    }
+    double* stage = ctx->pinned_stage((size_t)k * d + 2 * (size_t)k);  // (waits for the stream)
     double* host = ctx->pinned_scratch(8);
     if (!stage || !host) return ctx->fail(GPSO_E_OOM, "pinned host staging");
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
     // (no copies: append_cross_kernel reads the new points from this pinned buffer and files them in x64 / y64 itself)
     std::memcpy(stage, Xn, (size_t)k * d * 8);
     std::memcpy(stage + (size_t)k * d, yn, (size_t)k * 8);
+    const bool pass_s = use_s && sn != nullptr;
+    if (pass_s) std::memcpy(stage + (size_t)k * d + (size_t)k, sn, (size_t)k * 8);
     AppendArgs a{};
     a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.ls = ls_dev();
     a.xnew = stage; a.ynew = stage + (size_t)k * d;
+    a.snew = pass_s ? stage + (size_t)k * d + (size_t)k : nullptr;
+    a.sdiag = use_s ? as<double>(sdiag) : nullptr;
     a.n = n; a.npad = npad; a.k = (int)k; a.d = d; a.dp = dp; a.kernel = kp.kernel;
     a.variance = kp.variance; a.noise = kp.noise; a.mean_c = kp.mean_c;
     a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
@@ -1278,6 +1360,7 @@ struct EngineT : Engine {
       // (append_cols_kernel did not run); the tiles just repacked and the scaled-input rows go back to their padding state
       const int pivot = (int)host[2];
       repack(n);
+      if (have_s) HIPCHECK(hipMemsetAsync(as<double>(sdiag) + n, 0, (size_t)k * 8, s));  // (back to padding; a vector this call made is simply not adopted)
       (void)scale_inputs();
       gen32_inputs_ok = false;
       HIPCHECK(hipStreamSynchronize(s));
@@ -1286,6 +1369,16 @@ struct EngineT : Engine {
     }
     x_host.insert(x_host.end(), Xn, Xn + (size_t)k * d);
     y_host.insert(y_host.end(), yn, yn + (size_t)k);
+    if (new_s) {
+      s_host.assign((size_t)n, 0.0);
+      s_max = 0.0;
+      have_s = true;
+    }
+    if (have_s) {
+      if (pass_s) s_host.insert(s_host.end(), sn, sn + (size_t)k);
+      else s_host.resize((size_t)n_new, 0.0);
+      if (pass_s) s_max = std::max(s_max, *std::max_element(sn, sn + (size_t)k));
+    }
     n = n_new;
     if (nlml) *nlml = host[0];
     have_kinv = false;
@@ -1313,6 +1406,9 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(tmp, L, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp + (size_t)n * n, alpha64, (size_t)n * 8, hipMemcpyHostToDevice, s));
     have_data = false;  // y unknown: a later fit needs gpso_set_data
+    have_s = false;     // (... and gpso_set_noise_diag behind it)
+    s_host.clear();
+    s_max = 0.0;
     vgp_post = sgpr_post = svgp_post = false;
     sg_have = sg_have_z = sg_factors = false;
     have_post = have_kinv = chol_valid = false;
@@ -2563,7 +2659,7 @@ struct EngineT : Engine {
     if ((rc = ensure(st_out, 8 * 8))) return rc;  // 6 used
     if ((rc = score_device_leaves(x64.p, GPSO_F64, n, 0.0, false, as<double>(st_mean), as<double>(st_var), nullptr))) return rc;
     launch_selftest<TF>(st(), as<double>(st_mean), as<double>(st_var), as<double>(y64), as<TF>(alpha_f),
-                        as<double>(kinv_diag), n, kp.noise, kp.mean_c, as<double>(st_out));
+                        as<double>(kinv_diag), n, kp.noise, kp.mean_c, as<double>(st_out), s_dev());
     double* host = ctx->pinned_scratch(8);
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(host, st_out.p, 6 * 8, hipMemcpyDeviceToHost, st()));
@@ -3735,6 +3831,12 @@ struct EngineT : Engine {
 
   int get_vector(int which, double* out) override {
     if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
+    if (which == GPSO_VEC_NOISE_DIAG) {  // a property of the data, not of a posterior: the host mirror, or zeros
+      if (!have_data) return ctx->fail(GPSO_E_STATE, "GPSO_VEC_NOISE_DIAG needs training data (gpso_set_data)");
+      if (have_s) std::memcpy(out, s_host.data(), (size_t)n * 8);
+      else std::memset(out, 0, (size_t)n * 8);
+      return GPSO_OK;
+    }
     if (!have_post || !chol_valid) return ctx->fail(GPSO_E_STATE, "no fitted posterior resident");
     if (which == GPSO_VEC_WHITE && vgp_post) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no whitened targets");
     const TF* src = (which == GPSO_VEC_ALPHA) ? as<TF>(alpha_f) : (which == GPSO_VEC_WHITE) ? as<TF>(white) : nullptr;
@@ -4176,9 +4278,28 @@ int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int
   return GPSO_OK;
 }
 
+int gpso_set_noise_diag(gpso_ctx* ctx, const double* s, int64_t n) {
+  ENTER();
+  return ctx->eng->set_noise_diag(s, n);
+}
+
 int gpso_append(gpso_ctx* ctx, const double* Xnew, const double* ynew, int64_t k, double* nlml) {
   ENTER();
-  return ctx->eng->append(Xnew, ynew, k, nlml);
+  return ctx->eng->append(Xnew, ynew, nullptr, k, nlml);
+}
+
+int gpso_append_noise(gpso_ctx* ctx, const double* Xnew, const double* ynew, const double* snew, int64_t k, double* nlml) {
+  ENTER();
+  return ctx->eng->append(Xnew, ynew, snew, k, nlml);
+}
+
+// the variational and sparse families model ONE noise variance: a context that carries per-point noise is refused by
+// every entry point of theirs that computes, instead of having the vector silently ignored
+static int refuse_noise_diag(gpso_ctx* ctx) {
+  if (!ctx->eng->has_noise_diag()) return GPSO_OK;
+  return ctx->fail(GPSO_E_ARG, "a per-point noise vector is set on this context (gpso_set_noise_diag): the VGP, SGPR, SVGP and "
+                               "inducing-point entry points have one shared noise variance and would ignore it -- clear it "
+                               "with gpso_set_noise_diag(ctx, NULL, n) first");
 }
 
 int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const double* alpha,
@@ -4208,12 +4329,14 @@ int gpso_vgp_set_likelihood(gpso_ctx* ctx, int kind, double df, int n_gh, const 
 
 int gpso_vgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t n) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if ((mu == nullptr) != (S == nullptr)) return ctx->fail(GPSO_E_ARG, "mu and S: both or neither");
   return ctx->eng->vgp_set_q(mu, S, n);
 }
 
 int gpso_vgp_extend_q(gpso_ctx* ctx) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   return ctx->eng->vgp_extend_q();
 }
 
@@ -4225,6 +4348,7 @@ int gpso_vgp_get_q(gpso_ctx* ctx, double* mu, double* S) {
 int gpso_vgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double gamma) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
@@ -4234,6 +4358,7 @@ int gpso_vgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
 int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                     double* loss, double* grad_u, double* theta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
@@ -4249,6 +4374,7 @@ int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
 
 int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
@@ -4267,11 +4393,13 @@ static int sgpr_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, 
 
 int gpso_sgpr_set_inducing(gpso_ctx* ctx, const double* Z, int64_t m) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   return ctx->eng->sgpr_set_inducing(Z, m);
 }
 
 int gpso_sgpr_select_inducing(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int64_t m, int64_t* idx_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = sgpr_theta(ctx, u, n_ls, 0, 0.0, th);
   if (rc) return rc;
@@ -4291,6 +4419,7 @@ int gpso_sgpr_get_factor(gpso_ctx* ctx, int which, double* out) {
 int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                       double* loss, double* grad_u, double* theta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
   int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
@@ -4307,6 +4436,7 @@ int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
 int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
@@ -4317,6 +4447,7 @@ int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, in
 int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double noise_variance) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!(noise_variance > 0.0)) return ctx->eng->svgp_init_q(0, nullptr, 0, 0.0, 0.0, 0.0);  // the prior
   double th[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
@@ -4326,6 +4457,7 @@ int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
 
 int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if ((mu == nullptr) != (S == nullptr)) return ctx->fail(GPSO_E_ARG, "mu and S: both or neither");
   return ctx->eng->svgp_set_q(mu, S, m);
 }
@@ -4338,6 +4470,7 @@ int gpso_svgp_get_q(gpso_ctx* ctx, double* mu, double* S) {
 int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                       double gamma) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
@@ -4347,6 +4480,7 @@ int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
 int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double* loss, double* grad_u, double* theta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
@@ -4363,6 +4497,7 @@ int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
 int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   double th[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
   if (rc) return rc;
@@ -4372,12 +4507,14 @@ int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, in
 // ---- the sparse models at a moving Z ------------------------------------------------------------------------------------
 int gpso_sgpr_move_inducing(gpso_ctx* ctx, const double* Z) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   return ctx->eng->sgpr_move_inducing(Z);
 }
 
 int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                        const double* Z, double* loss, double* grad_u, double* grad_z, double* theta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
   int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
@@ -4395,6 +4532,7 @@ int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int
 int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                       const double* Z, double* loss, double* grad_u, double* grad_z, double* theta_out) {
   ENTER();
+  if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
   int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);

@@ -66,6 +66,7 @@ __global__ __launch_bounds__(256) void append_cross_kernel(AppendArgs a) {
     if (tid < k) a.xnorm64[n + tid] = nn[tid];
     for (int e = tid; e < k * d; e += 256) a.x64[n * d + e] = a.xnew[e];
     if (tid < k) a.y64[n + tid] = a.ynew[tid];
+    if (a.sdiag != nullptr && tid < k) a.sdiag[n + tid] = (a.snew != nullptr) ? a.snew[tid] : 0.0;
     if (tid == 0) {
       *a.info = INT_MAX;
       if (a.f16_scal != nullptr) a.f16_scal[3] = a.f16_scal[1];  // the scale the resident pieces were packed with
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(256) void append_cross_kernel(AppendArgs a) {
       double s = 0.0;
       for (int kk = 0; kk < dp; ++kk) s = fma(xr[rr * st + kk], xn[j * dp + kk], s);
       kv = kern_from_r2_lean(a.kernel, fma(-2.0, s, ni + nn[j]), a.variance);
-      if (i - n == j) kv += a.noise;
+      if (i - n == j) kv += (a.snew != nullptr ? a.noise + a.snew[j] : a.noise);
     }
     out[j] = kv;
   }

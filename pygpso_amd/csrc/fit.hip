@@ -120,7 +120,8 @@ template <typename T>
 __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ xs,
                                                    const double* __restrict__ xnorm, int64_t n,
                                                    int64_t npad, int dp, int kernel, double variance,
-                                                   double noise, T* __restrict__ K, int* __restrict__ info) {
+                                                   double noise, T* __restrict__ K, int* __restrict__ info,
+                                                   const double* __restrict__ sdiag) {
   using vec4 = typename Mfma<T>::vec4;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t blk = blockIdx.x;
@@ -170,7 +171,8 @@ __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ xs
       if (i < n && j < n) {
         const double r2 = fma(-2.0, s[x][r], nai + nbj[x]);
         T kv = kern_from_r2_lean(kernel, (T)r2, (T)variance);
-        if (i == j) kv += (T)noise;
+        // (per-point noise, nullable: d_i = noise + s_i is ONE double addition, rounded to T where noise is)
+        if (i == j) kv += (T)(sdiag != nullptr ? noise + sdiag[i] : noise);
         v[x] = kv;
       } else {
         v[x] = (i == j) ? T(1) : T(0);
@@ -182,14 +184,14 @@ __global__ __launch_bounds__(256) void gram_kernel(const double* __restrict__ xs
 
 template <typename T>
 void launch_gram(hipStream_t st, const double* xs, const double* xnorm, int64_t n, int64_t npad, int dp,
-                 const KernParams& kp, T* K, int* info) {
+                 const KernParams& kp, T* K, int* info, const double* sdiag) {
   const int64_t nt = npad / 64;
   hipLaunchKernelGGL((gram_kernel<T>), dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256),
                      (size_t)2 * 64 * (dp + 1) * sizeof(double), st, xs, xnorm, n, npad, dp, kp.kernel, kp.variance,
-                     kp.noise, K, info);
+                     kp.noise, K, info, sdiag);
 }
-template void launch_gram<float>(hipStream_t, const double*, const double*, int64_t, int64_t, int, const KernParams&, float*, int*);
-template void launch_gram<double>(hipStream_t, const double*, const double*, int64_t, int64_t, int, const KernParams&, double*, int*);
+template void launch_gram<float>(hipStream_t, const double*, const double*, int64_t, int64_t, int, const KernParams&, float*, int*, const double*);
+template void launch_gram<double>(hipStream_t, const double*, const double*, int64_t, int64_t, int, const KernParams&, double*, int*, const double*);
 
 // =============================================================================================
 // 64x64 diagonal block: Cholesky + triangular inverse in LDS, 4 waves, blocked by 16 columns
@@ -1477,12 +1479,14 @@ static void launch_gemm_bf16(hipStream_t st, GemmBf16Desc g, int cu_count, int r
   if (g.np == 2) hipLaunchKernelGGL(gemm_bf16_kernel<2>, dim3((unsigned)grid), dim3(256), lds, st, g);
   else hipLaunchKernelGGL(gemm_bf16_kernel<3>, dim3((unsigned)grid), dim3(256), lds, st, g);
 }
-bool fit_plane_scales(double variance, double noise, FitPlanes& pl) {
+bool fit_plane_scales(double variance, double noise, FitPlanes& pl, double s_max) {
   // scaled bound 2^13; the scale itself must leave a typical entry's SECOND piece (2^-11 of it) a normal fp16 number
   auto scale_for = [](double bound) { return std::ldexp(1.0, 13 - (int)std::ceil(std::log2(std::max(bound, 1e-300)))); };
   if (!(variance > 0.0) || !(noise > 0.0)) return false;
-  const double sl = scale_for(std::sqrt(variance + noise)), sx = scale_for(1.0 / std::sqrt(noise)),
-               sw = scale_for(std::sqrt((variance + noise) / noise));
+  // (per-point noise raises the diagonal by at most s_max: it widens the bounds on L and on L[B,A] L^-1[A,A]; 1 / sqrt(noise)
+  // still bounds L^-1, whose largest entry only shrinks with a larger diagonal)
+  const double top = variance + noise + s_max;
+  const double sl = scale_for(std::sqrt(top)), sx = scale_for(1.0 / std::sqrt(noise)), sw = scale_for(std::sqrt(top / noise));
   // typical entries: |L| ~ sqrt(variance), |L^-1| and the W blocks ~ 1 / sqrt(variance) and up
   const double lo = std::ldexp(1.0, -2), hi = std::ldexp(1.0, 40);
   if (sl * std::sqrt(variance) < lo || sx / std::sqrt(variance) < lo || sw < lo * 0.25 || sl > hi || sx > hi || sw > hi) return false;
@@ -2793,6 +2797,7 @@ constexpr int kSmallLdsBytes = kSmallLdsDoubles * 8;
 // same MFMA sequence and epilogue as gram_kernel<double>, so the entries are bit-identical to it
 __device__ __forceinline__ void small_gram_block(const double* xs, const double* nrm, int dp, int bi, int bj,
                                                  int n, int kernel, double variance, double noise,
+                                                 const double* __restrict__ sdiag /* [128] global, nullable */,
                                                  double* blk, int wave, int lane) {
   // (a diagonal block is only read on and below its diagonal: column tiles t <= wave)
   const int tmax = (bi == bj) ? wave : 3;
@@ -2820,7 +2825,7 @@ __device__ __forceinline__ void small_gram_block(const double* xs, const double*
       if (i < n && j < n) {
         const double r2 = fma(-2.0, s[t][r], nrm[i] + nrm[j]);
         v = kern_from_r2_lean(kernel, r2, variance);
-        if (i == j) v += noise;
+        if (i == j) v += (sdiag != nullptr ? noise + sdiag[i] : noise);
       } else {
         v = (i == j) ? 1.0 : 0.0;
       }
@@ -2936,10 +2941,10 @@ __device__ __forceinline__ void small_fit_body(const Args& g) {
   __syncthreads();
   GPSO_SSTAMP(1);
   // ---- 1. Gram blocks: K00 -> A, K10 -> C, K11 -> D4
-  small_gram_block(xs, nrm, dp, 0, 0, n, g.kernel, variance, noise, A, wave, lane);
+  small_gram_block(xs, nrm, dp, 0, 0, n, g.kernel, variance, noise, g.sdiag, A, wave, lane);
   if (nb == 2) {
-    small_gram_block(xs, nrm, dp, 1, 0, n, g.kernel, variance, noise, C, wave, lane);
-    small_gram_block(xs, nrm, dp, 1, 1, n, g.kernel, variance, noise, D4, wave, lane);
+    small_gram_block(xs, nrm, dp, 1, 0, n, g.kernel, variance, noise, g.sdiag, C, wave, lane);
+    small_gram_block(xs, nrm, dp, 1, 1, n, g.kernel, variance, noise, g.sdiag, D4, wave, lane);
   }
   __syncthreads();
   for (int e = tid; e < kBlk; e += 256) B[e] = 0.0;  // X00 is written on and below the diagonal only
@@ -3273,6 +3278,10 @@ template int launch_small_fit_batch<float, float>(hipStream_t, const SmallBatchA
 // With K_y = K + noise I = L L^T, alpha = K_y^-1 (y - c) and k_i = K_y e_i - noise e_i:
 //     mean(x_i) = k_i . alpha + c                       = y_i - noise * alpha_i
 //     var_y(x_i) = sigma^2 - |L^-1 k_i|^2 + noise       = 2 noise - noise^2 * (K_y^-1)_ii
+// With per-point noise (sdiag set: K_y = K + diag(d), d_i = noise + s_i) k_i = K_y e_i - d_i e_i and (K_y)_ii = sigma^2 + d_i:
+//     mean(x_i) = y_i - d_i * alpha_i
+//     var_y(x_i) = sigma^2 - (sigma^2 + d_i - 2 d_i + d_i^2 (K_y^-1)_ii) + noise = noise + d_i - d_i^2 * (K_y^-1)_ii
+// (the prediction adds the shared noise only: s is a property of the observations, not of the point).
 // (K_y^-1)_ii = squared column norm of L^-1 (alpha_sum_kernel).  The predict kernels recompute k_i
 // from X, so the differences measure the whole chain: the rounding of the apply (the training inputs
 // are where var is smallest, i.e. where the cancellation sigma^2 - |A|^2 is worst) and, for a float
@@ -3288,13 +3297,21 @@ __global__ __launch_bounds__(256) void selftest_kernel(const double* __restrict_
                                                        const T* __restrict__ alpha,
                                                        const double* __restrict__ kinv_diag, int64_t n,
                                                        double noise, double mean_c,
+                                                       const double* __restrict__ sdiag /* nullable */,
                                                        double* __restrict__ out) {
   __shared__ double sh[6][4];
   double v[6] = {0.0, 0.0, 0.0, 1.0e300, 0.0, 0.0};
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
     const double a = (double)alpha[i];
-    const double m_ref = y64[i] - noise * a;
-    const double v_ref = 2.0 * noise - noise * noise * kinv_diag[i];
+    double m_ref, v_ref;
+    if (sdiag == nullptr) {
+      m_ref = y64[i] - noise * a;
+      v_ref = 2.0 * noise - noise * noise * kinv_diag[i];
+    } else {
+      const double di = noise + sdiag[i];
+      m_ref = y64[i] - di * a;
+      v_ref = (noise + di) - di * di * kinv_diag[i];
+    }
     const double dm = fabs(mean[i] - m_ref), dv = fabs(var[i] - v_ref);
     v[0] = (dm > v[0] || dm != dm) ? dm : v[0];  // NaN sticks
     v[1] = (dv > v[1] || dv != dv) ? dv : v[1];
@@ -3329,12 +3346,12 @@ __global__ __launch_bounds__(256) void selftest_kernel(const double* __restrict_
 template <typename T>
 void launch_selftest(hipStream_t st, const double* mean, const double* var, const double* y64,
                      const T* alpha, const double* kinv_diag, int64_t n, double noise, double mean_c,
-                     double* out) {
+                     double* out, const double* sdiag) {
   hipLaunchKernelGGL((selftest_kernel<T>), dim3(1), dim3(256), 0, st, mean, var, y64, alpha, kinv_diag, n,
-                     noise, mean_c, out);
+                     noise, mean_c, sdiag, out);
 }
-template void launch_selftest<float>(hipStream_t, const double*, const double*, const double*, const float*, const double*, int64_t, double, double, double*);
-template void launch_selftest<double>(hipStream_t, const double*, const double*, const double*, const double*, const double*, int64_t, double, double, double*);
+template void launch_selftest<float>(hipStream_t, const double*, const double*, const double*, const float*, const double*, int64_t, double, double, double*, const double*);
+template void launch_selftest<double>(hipStream_t, const double*, const double*, const double*, const double*, const double*, int64_t, double, double, double*, const double*);
 
 // =============================================================================================
 // conversions / interop

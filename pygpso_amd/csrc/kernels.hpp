@@ -167,10 +167,12 @@ void launch_scale_x(hipStream_t st, const double* x64, int64_t n, int64_t npad, 
 void launch_gen_inputs_f32(hipStream_t st, const double* xs64, int64_t npad, int dp, float* xs, float* xnorm,
                            float* xs_p);
 // K = k(X, X) + noise * I on rows < n (lower 64x64 tiles only); identity on the padding.  r^2 is
-// always formed in double from the double scaled inputs.
+// always formed in double from the double scaled inputs.  sdiag (device [npad], nullable): per-point noise s, the
+// diagonal then receives noise + s_i (one double addition, rounded to T where noise is).
 template <typename T>
 void launch_gram(hipStream_t st, const double* xs, const double* xnorm, int64_t n, int64_t npad, int dp,
-                 const KernParams& kp, T* K, int* info = nullptr /* device: set to INT_MAX ("no failing pivot") */);
+                 const KernParams& kp, T* K, int* info = nullptr /* device: set to INT_MAX ("no failing pivot") */,
+                 const double* sdiag = nullptr);
 // blocked right-looking Cholesky, K (destroyed) -> Lf (lower); also writes the inverted 64x64 diagonal
 // blocks into linv, the unrounded diagonal of L to diag64[npad], and the first failing pivot (or
 // INT_MAX) to info
@@ -206,7 +208,8 @@ struct FitPlanes {
 inline size_t fit_plane_set_bytes(int64_t npad) { return (size_t)3 * (size_t)npad * (size_t)npad * 2; }
 // power-of-two scales of the fp16 planes for hyper-parameters (variance, noise); false: a scale leaves the range in which
 // the second piece of a typical entry is still a normal fp16 number (noise / variance below ~1e-9): keep bf16 pieces
-bool fit_plane_scales(double variance, double noise, FitPlanes& pl);
+// s_max: the largest per-point noise term on the diagonal (0 without one) -- |L| <= sqrt(s2 + noise + s_max)
+bool fit_plane_scales(double variance, double noise, FitPlanes& pl, double s_max = 0.0);
 // planes (float fits, nullable): with them the TRSM GEMMs also emit L into planes->L and the rank-W trailing
 // updates run on the bf16 matrix cores
 // does launch_potrf take the single-level path at this size?  (It then writes every entry of L^-1 that anything reads --
@@ -264,6 +267,7 @@ struct SmallFitArgs {
   int n, d, dp, kernel, n_ls, want_grad;
   int zero_tile_rows;  // 16-row tile rows of linv_p an earlier fit may have left non-zero (8 = unknown)
   double variance, noise, mean_c;
+  const double* sdiag;  // [128] per-point noise s (device, nullable): the diagonal receives noise + s_i
   // outputs
   double* xs64;    // [128 * dp] scaled inputs
   double* xnorm64; // [128]
@@ -301,6 +305,7 @@ struct SmallBatchArgs {
   double* grad;         // [B][n_ls + 3]: d nlml / d (ls..., variance, noise, c)
   int* info;            // [B]: failing pivot, INT_MAX = positive definite
   int n, d, dp, kernel, n_ls, want_grad;
+  const double* sdiag;  // [128] per-point noise s shared by every entry (device, nullable)
 };
 template <typename T, typename TP>
 int launch_small_fit_batch(hipStream_t st, const SmallBatchArgs& args, int b);
@@ -310,7 +315,7 @@ int launch_small_fit_batch(hipStream_t st, const SmallBatchArgs& args, int b);
 template <typename T>
 void launch_selftest(hipStream_t st, const double* mean, const double* var, const double* y64,
                      const T* alpha, const double* kinv_diag, int64_t n, double noise, double mean_c,
-                     double* out);
+                     double* out, const double* sdiag = nullptr /* device [n], per-point noise: the closed forms use noise + s_i */);
 
 // conversions and getters
 template <typename TS, typename TD>
@@ -409,6 +414,8 @@ struct AppendArgs {
   double* x64;         // [npad * d] raw inputs: rows n .. n + k - 1 are filed by the cross kernel
   double* y64;         // [npad]
   const double *xnew, *ynew;  // the k new points [k * d], [k] in pinned HOST memory (read by the cross kernel itself: no copies)
+  const double* snew;  // [k] their per-point noise, pinned host (nullable = zeros)
+  double* sdiag;       // [npad] per-point noise of the resident rows (device, nullable: none set); rows n .. n + k - 1 are filed
 
   const double* ls;    // lengthscale per input dimension (device)
   int64_t n, npad;

@@ -286,6 +286,12 @@ class HipGPEngineGroup:
         self.n, self.d = self.engines[0].n, self.engines[0].d
         self._new_posterior()
 
+    def set_noise_diag(self, s):
+        """``HipGPEngine.set_noise_diag`` on the fitting rank(s): only fits read the vector, so sharding and the posterior
+        hand-off need nothing more."""
+        self._fitters(lambda e: e.set_noise_diag(s))
+        self._new_posterior()
+
     def fit_eval(self, *a, **kw):
         self._new_posterior()
         return self._fitters(lambda e: e.fit_eval(*a, **kw))
@@ -294,9 +300,10 @@ class HipGPEngineGroup:
         self._new_posterior()
         return self._fitters(lambda e: e.fit_eval_u(*a, **kw))
 
-    def append(self, Xnew, ynew):
-        """``HipGPEngine.append`` on the fitting rank(s); the peers get the extended posterior like a fitted one."""
-        out = self._fitters(lambda e: e.append(Xnew, ynew))
+    def append(self, Xnew, ynew, s=None):
+        """``HipGPEngine.append`` on the fitting rank(s); the peers get the extended posterior like a fitted one.
+        ``s``: the new points' per-point noise (None: the two-argument call)."""
+        out = self._fitters(lambda e: e.append(Xnew, ynew) if s is None else e.append(Xnew, ynew, s))
         self.n = self.engines[0].n
         # "broadcast" groups: the next predict-type call moves only what the append wrote (gpso_broadcast_posterior_rows; the
         # library falls back to the whole range on every rank when a peer does not hold the base) -- not the whole posterior

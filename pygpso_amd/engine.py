@@ -203,6 +203,16 @@ class HipGPEngine:
         self._check(self._lib.gpso_set_data(self._h, L.dptr(X), L.dptr(y), X.shape[0], X.shape[1]))
         self.n, self.d = X.shape
 
+    def set_noise_diag(self, s):
+        """``gpso_set_noise_diag``: the known variance s [N] >= 0 of each resident observation (None clears it).  Later fits
+        factorise K + diag(noise + s); predictions add the shared noise only.  ``set_data`` clears it; a resident posterior
+        is invalidated."""
+        if s is None:
+            self._check(self._lib.gpso_set_noise_diag(self._h, None, self.n))
+            return
+        sa = L.as_f64(np.asarray(s).reshape(-1))
+        self._check(self._lib.gpso_set_noise_diag(self._h, L.dptr(sa), sa.shape[0]))
+
     @staticmethod
     def _theta_args(kernel, lengthscales, variance, noise, mean_c):
         kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
@@ -283,17 +293,23 @@ class HipGPEngine:
             loss[lo:hi], grad[lo:hi], ok[lo:hi] = f, g, st == L.OK
         return loss, grad, ok
 
-    def append(self, Xnew, ynew):
+    def append(self, Xnew, ynew, s=None):
         """``gpso_append``: k new training points extend the resident posterior at its hyper-parameters (two passes over
         L^-1 instead of a factorisation).  Returns (nlml of the N + k points, in_place): ``in_place`` False when the
-        library refitted from scratch instead (pad crossing, k > 64, N + k <= 128: ``last_message()`` says which)."""
+        library refitted from scratch instead (pad crossing, k > 64, N + k <= 128: ``last_message()`` says which).
+        ``s`` [k] (``gpso_append_noise``): the new points' per-point noise; None appends zeros."""
         Xn = L.as_f64(np.atleast_2d(Xnew))
         if Xn.ndim != 2 or Xn.shape[1] != self.d:
             raise ValueError(f"Xnew must be [k, {self.d}]")
         yn = L.as_f64(np.asarray(ynew).reshape(-1), (Xn.shape[0],))
         nlml = C.c_double()
+        sn = None if s is None else L.as_f64(np.asarray(s).reshape(-1), (Xn.shape[0],))
         try:
-            rc = self._check(self._lib.gpso_append(self._h, L.dptr(Xn), L.dptr(yn), Xn.shape[0], C.byref(nlml)))
+            if sn is None:
+                rc = self._check(self._lib.gpso_append(self._h, L.dptr(Xn), L.dptr(yn), Xn.shape[0], C.byref(nlml)))
+            else:
+                rc = self._check(self._lib.gpso_append_noise(self._h, L.dptr(Xn), L.dptr(yn), L.dptr(sn), Xn.shape[0],
+                                                             C.byref(nlml)))
         finally:
             # whatever happened, N is what the library says it holds (a failed append leaves the first N points, in place
             # or refitted: include/gpso_hip.h)

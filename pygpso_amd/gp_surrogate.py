@@ -90,6 +90,71 @@ class GPListOfPoints(list):
         # every point came in through append(): no two stored points lie within the duplicate tolerance of each other (the
         # constructor does not de-duplicate, list surgery may break it: cleared by anything but append / score updates)
         self._unique = len(self) == 0
+        # known variance of a stored point's score (the variance of a mean of repeated evaluations), beside the five-field
+        # GPPoint: keyed by the point's coordinate row, as the index above is; a point without an entry has variance 0
+        self._noise = {}
+        self.noise_given = False  # was a variance ever stored (``current_training_noise`` is None until then)
+        if args and isinstance(args[0], GPListOfPoints):  # (a copy of a store keeps its variances)
+            self._noise = dict(args[0]._noise)
+            self.noise_given = args[0].noise_given
+
+    # -- per-point score variances (parallel store) ---------------------------------------------------
+    def set_noise_at(self, index, variance):
+        """The score variance of the point stored at ``index``."""
+        variance = float(variance)
+        if not (math.isfinite(variance) and variance >= 0.0):
+            raise ValueError(f"score variance {variance} must be finite and >= 0")
+        self._index()
+        self._noise[self._rows[index]] = variance
+        self.noise_given = True
+
+    def noise_at(self, index):
+        self._index()
+        return self._noise.get(self._rows[index], 0.0)
+
+    def noise_by_coords(self, coords):
+        """The stored variance of the point within the duplicate tolerance of ``coords`` (0.0: none stored, or no such point)."""
+        i = self.find_index_by_coords(coords)
+        return 0.0 if i is None else self._noise.get(self._rows[i], 0.0)
+
+    def noise_vector(self, label=None):
+        """Variances of the stored points (of ``label`` only when given), in list order."""
+        self._index()
+        get, rows = self._noise.get, self._rows
+        return np.array([get(rows[i], 0.0) for i, p in enumerate(self) if label is None or p.label == label], dtype=np.float64)
+
+    def save_noise(self, filename):
+        """One variance per stored point, in list order -- written only when some variance is non-zero.  A store without any
+        leaves the folder as it always was: nothing is written, and a file an earlier save left there is REMOVED (it would
+        otherwise be read back beside points it no longer describes).  So a store that was only ever given zero variances
+        loads as one that was given none (``current_training_noise`` None instead of zeros: the same model).  Returns True
+        when written."""
+        if not filename.endswith(JSON_EXT):
+            filename += JSON_EXT
+        values = self.noise_vector()
+        if not np.any(values != 0.0):
+            if os.path.exists(filename):
+                os.remove(filename)
+            return False
+        with open(filename, "w") as fh:
+            fh.write(json.dumps(values.tolist()))
+        return True
+
+    def load_noise(self, filename):
+        """Read what ``save_noise`` wrote beside this list's points file; a missing file is a store without variances."""
+        if not filename.endswith(JSON_EXT):
+            filename += JSON_EXT
+        if not os.path.exists(filename):
+            return False
+        with open(filename) as fh:
+            values = json.load(fh)
+        if len(values) != len(self):
+            raise ValueError(f"{filename}: {len(values)} variances for {len(self)} points")
+        for i, v in enumerate(values):
+            if v != 0.0:
+                self.set_noise_at(i, v)
+        self.noise_given = True
+        return True
 
     # -- index kept in sync ------------------------------------------------------------------------
     # (plain Python floats on purpose: a look-up touches one or two candidate rows of D numbers, and the
@@ -244,6 +309,7 @@ class GPSurrogate:
     """Base class: point bookkeeping + predict/UCB on top of ``self.gpflow_model``."""
 
     POINTS_FILE = f"points{JSON_EXT}"
+    POINTS_NOISE_FILE = f"points_noise{JSON_EXT}"  # (beside the points file, only when some score variance is non-zero)
     GPR_FILE = f"GPRmodel{JSON_EXT}"
     GPR_INFO = f"GPRinfo{JSON_EXT}"
 
@@ -315,6 +381,20 @@ class GPSurrogate:
         return np.array([p.normed_coord for p in ev]), np.array([p.score_mu for p in ev])
 
     @property
+    def current_training_noise(self):
+        """Known variance of each evaluated point's score, [N] aligned with ``current_training_data`` (zeros where none was
+        given); None when none was ever given."""
+        if not self.points.noise_given:
+            return None
+        return self.points.noise_vector(PointLabels.evaluated)
+
+    def _refuse_score_variances(self, s):
+        """The variational and sparse surrogates model one shared noise variance: they refuse non-zero score variances."""
+        if s is not None and np.any(np.asarray(s) != 0.0):
+            raise NotImplementedError(f"per-point observation noise (score_vars / eval_repeats_noise) is only modelled by "
+                                      f"GPRSurrogate, not by {type(self).__name__}")
+
+    @property
     def gp_based_coords(self):
         return np.array([p.normed_coord for p in self._with_label(PointLabels.gp_based)])
 
@@ -322,13 +402,26 @@ class GPSurrogate:
     def _gp_train(self, x, y):
         raise NotImplementedError
 
-    def append(self, coords, scores):
-        """Store evaluated points (normalised coordinates [n, D], scores [n])."""
+    def append(self, coords, scores, score_vars=None):
+        """Store evaluated points (normalised coordinates [n, D], scores [n]).  ``score_vars`` [n] >= 0 (not in the
+        reference): the known variance of each score, kept beside the points and modelled as per-point observation noise."""
         assert coords.ndim == 2
         assert scores.ndim == 1
         assert coords.shape[0] == scores.shape[0]
-        for c, s in zip(coords, scores):
-            self.points.append(GPPoint(c, s, 0.0, 0.0, PointLabels.evaluated))
+        if score_vars is None:
+            for c, s in zip(coords, scores):
+                self.points.append(GPPoint(c, s, 0.0, 0.0, PointLabels.evaluated))
+            return
+        score_vars = np.asarray(score_vars, dtype=np.float64)
+        assert score_vars.ndim == 1 and score_vars.shape[0] == scores.shape[0]
+        if not (np.all(np.isfinite(score_vars)) and np.all(score_vars >= 0.0)):
+            raise ValueError("score_vars must be finite and >= 0")
+        self.points.noise_given = True
+        for c, s, v in zip(coords, scores, score_vars):
+            point = GPPoint(c, s, 0.0, 0.0, PointLabels.evaluated)
+            i = self.points.append(point)
+            if self.points[i] is point:  # (an evaluated duplicate keeps its score, and so its variance)
+                self.points.set_noise_at(i, v)
 
     # -- predict / UCB ------------------------------------------------------------------------------
     def _require_model(self):
@@ -363,7 +456,11 @@ class GPSurrogate:
         x_train, y_train = self.current_training_data
         if logging.getLogger().isEnabledFor(logging.DEBUG):  # (formatting the arrays is not free)
             logging.debug(f"Retraining GPR with x data: {x_train}; y data: {y_train}")
-        self._gp_train(x=x_train, y=y_train[:, np.newaxis])
+        s_train = self.current_training_noise
+        if s_train is None:
+            self._gp_train(x=x_train, y=y_train[:, np.newaxis])
+        else:
+            self._gp_train(x=x_train, y=y_train[:, np.newaxis], s=s_train)
         # re-predict every gp-based point.  The reference re-appends them (gpso/gp_surrogate.py:341-342): each overwrites its
         # own entry -- done here by index, one predict call and no look-ups, while the store can vouch that no two points are
         # duplicates of each other; otherwise the reference's way
@@ -427,20 +524,32 @@ class GPRSurrogate(GPSurrogate):
             devices=devices,
         )
 
-    def _gp_train(self, x, y):
+    def _gp_train(self, x, y, s=None):
+        """``s`` [N] (None: none): the known variance of each score, a fixed per-point noise term beside the trained one."""
         assert x.shape[0] == y.shape[0]
         assert x.ndim == 2 and y.ndim == 2
+        if s is not None:
+            s = np.ascontiguousarray(s, dtype=np.float64).reshape(-1)
+            assert s.shape[0] == x.shape[0]
         if self.gpflow_model is None:
             engine = self.engine_factory() if self.engine_factory is not None else None
             self.gpflow_model = HipGPR(data=(x, y), kernel=self.gp_kernel, mean_function=self.gp_meanf,
                                        noise_variance=self.gp_lik_sigma, dtype=self.dtype,
                                        device=self.device, engine=engine,
-                                       engine_options=self.engine_options, devices=self.devices)
+                                       engine_options=self.engine_options, devices=self.devices, noise_diag=s)
         else:
             n_old = self.gpflow_model.data[0].shape[0]
             new_rows = None
             if self.refit_every > 1 and self._updates % self.refit_every != 0 and x.shape[0] > n_old:
-                new_rows = self._rows_beyond(self.gpflow_model.data, x, y)
+                if s is None and self.gpflow_model.noise_diag is None:
+                    new_rows = self._rows_beyond(self.gpflow_model.data, x, y)
+                else:
+                    # (a held row must also have kept its variance: it rides as one more coordinate of the comparison)
+                    old_x, old_y = self.gpflow_model.data
+                    old_s = self.gpflow_model.noise_diag if self.gpflow_model.noise_diag is not None else np.zeros(n_old)
+                    new_s = s if s is not None else np.zeros(x.shape[0])
+                    new_rows = self._rows_beyond((np.hstack([old_x, old_s[:, np.newaxis]]), old_y),
+                                                 np.hstack([x, new_s[:, np.newaxis]]), y)
             if new_rows is not None:
                 # the model's points are all still there with their scores: extend the posterior at the kept
                 # hyper-parameters by the others.  (The evaluated points do NOT only grow at the end of the list: an
@@ -451,7 +560,10 @@ class GPRSurrogate(GPSurrogate):
                     model = self.gpflow_model
                     model._ensure_resident()
                     nlml_before = float(model._last_nlml)
-                    model.append_data(x[new_rows], y[new_rows])
+                    if s is None:
+                        model.append_data(x[new_rows], y[new_rows])
+                    else:
+                        model.append_data(x[new_rows], y[new_rows], s_new=s[new_rows])
                     per_new = (float(model._last_nlml) - nlml_before) / (x.shape[0] - n_old)
                     if self.refit_guard is None or not (per_new > nlml_before / n_old + self.refit_guard):
                         self._updates += 1
@@ -467,6 +579,8 @@ class GPRSurrogate(GPSurrogate):
                     logging.warning(f"{err}; this update re-optimises the hyper-parameters instead of appending")
             else:
                 self.gpflow_model.data = (x, y)  # hyper-parameters warm-start from the last optimum
+                if s is not None:
+                    self.gpflow_model.noise_diag = s
         self._updates += 1
         self.optimiser.minimize(self.gpflow_model.training_loss, self.gpflow_model.trainable_variables)
 
@@ -501,8 +615,12 @@ class GPRSurrogate(GPSurrogate):
                      seed=extra.get("seed", 0))
 
     def save(self, folder):
+        """Points, hyper-parameters and settings as JSON.  ``points_noise.json`` exists in ``folder`` afterwards exactly when
+        some stored score variance is non-zero: it is written then, and otherwise a copy left by an earlier save is deleted
+        (``GPListOfPoints.save_noise``)."""
         os.makedirs(folder, exist_ok=True)
         self.points.save(os.path.join(folder, self.POINTS_FILE))
+        self.points.save_noise(os.path.join(folder, self.POINTS_NOISE_FILE))
         model = self.gpflow_model
         params = {k: np.asarray(v).tolist() for k, v in model.parameter_dict().items()}
         with open(os.path.join(folder, self.GPR_FILE), "w") as fh:
@@ -525,6 +643,7 @@ class GPRSurrogate(GPSurrogate):
     @classmethod
     def from_saved(cls, folder, device=0, devices=None):
         points = GPListOfPoints.from_file(os.path.join(folder, cls.POINTS_FILE))
+        has_noise = points.load_noise(os.path.join(folder, cls.POINTS_NOISE_FILE))  # (an older folder has none)
         ev = [p for p in points if p.label == PointLabels.evaluated]
         x = np.array([p.normed_coord for p in ev])
         y = np.array([p.score_mu for p in ev])[:, np.newaxis]
@@ -540,7 +659,8 @@ class GPRSurrogate(GPSurrogate):
         engine = cls.engine_factory() if cls.engine_factory is not None else None
         model = HipGPR(data=(x, y), kernel=kernel, mean_function=meanf,
                        noise_variance=params[".likelihood.variance"], dtype=info.get("dtype", "float64"),
-                       device=device, engine=engine, devices=devices)
+                       device=device, engine=engine, devices=devices,
+                       noise_diag=points.noise_vector(PointLabels.evaluated) if has_noise else None)
         return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=cls._optimiser_from_record(info["optimiser"]),
                    gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
                    points=points, gpflow_model=model, dtype=info.get("dtype", "float64"), device=device,
@@ -594,7 +714,8 @@ class SGPRSurrogate(GPSurrogate):
                    optimiser=Scipy(), varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3, num_inducing=num_inducing,
                    dtype=dtype, device=device, engine_options=engine_options, train_inducing=train_inducing)
 
-    def _gp_train(self, x, y):
+    def _gp_train(self, x, y, s=None):
+        self._refuse_score_variances(s)
         assert x.shape[0] == y.shape[0]
         assert x.ndim == 2 and y.ndim == 2
         if self.gpflow_model is None:
@@ -709,7 +830,8 @@ class VGPSurrogate(GPSurrogate):
         self.natgrad_gamma = gamma
         self.train_iters = int(train_iterations)
 
-    def _gp_train(self, x, y):
+    def _gp_train(self, x, y, s=None):
+        self._refuse_score_variances(s)
         assert x.shape[0] == y.shape[0]
         assert x.ndim == 2 and y.ndim == 2
         if self.gpflow_model is None:
@@ -866,7 +988,8 @@ class SVGPSurrogate(GPSurrogate):
         self.natgrad_gamma = gamma
         self.train_iters = int(train_iterations)
 
-    def _gp_train(self, x, y):
+    def _gp_train(self, x, y, s=None):
+        self._refuse_score_variances(s)
         assert x.shape[0] == y.shape[0]
         assert x.ndim == 2 and y.ndim == 2
         if self.gpflow_model is None:

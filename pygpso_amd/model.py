@@ -71,8 +71,11 @@ def _as_result(a):
 
 class HipGPR:
     def __init__(self, data, kernel, mean_function=None, noise_variance=1.0e-3, dtype="float64",
-                 device=0, engine=None, engine_options=None, escalate=True, devices=None):
-        """``dtype``: "float64" | "mixed" | "float32" (see ``HipGPEngine``).  ``engine_options``: extra
+                 device=0, engine=None, engine_options=None, escalate=True, devices=None, noise_diag=None):
+        """``noise_diag`` [N] >= 0 (or None): the known variance of each observation, a fixed per-point term beside the
+        trained likelihood variance -- the fits factorise K + diag(likelihood.variance + noise_diag); ``predict_y`` adds
+        the likelihood variance only.
+        ``dtype``: "float64" | "mixed" | "float32" (see ``HipGPEngine``).  ``engine_options``: extra
         keyword arguments of ``HipGPEngine`` (predict_math, generation, tolerances).  ``escalate``:
         when the device reports that float predictions fail their self-test on the current posterior
         (GPSO_E_PRECISION), reopen it as "mixed", then "float64", with a logged warning, instead of
@@ -97,7 +100,10 @@ class HipGPR:
         self._data = None
         self._resident = False  # posterior on the device matches (data, hyper-parameters)?
         self.num_loss_evals = 0
+        self._noise_diag = None
         self.data = data
+        if noise_diag is not None:
+            self.noise_diag = noise_diag
 
     def _open_engine(self, dtype):
         """One engine on ``device``, or -- ``devices=[...]`` -- a group that shards every predict-type
@@ -122,35 +128,81 @@ class HipGPR:
         y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1, 1)
         assert x.ndim == 2 and x.shape[0] == y.shape[0]
         self._data = (x, y)
+        self._noise_diag = None  # (it belonged to the rows just replaced: set ``noise_diag`` again behind new data)
         self.engine.set_data(x, y[:, 0])
         self._resident = False
         self._device_theta = None  # hyper-parameters of the posterior on the device (None: none / unknown)
 
-    def append_data(self, x_new, y_new):
+    @property
+    def noise_diag(self):
+        """Per-point observation variance [N] beside the current data, or None."""
+        return self._noise_diag
+
+    @noise_diag.setter
+    def noise_diag(self, value):
+        if value is not None:
+            value = np.ascontiguousarray(value, dtype=np.float64).reshape(-1)
+            if value.shape[0] != self._data[0].shape[0]:
+                raise ValueError(f"noise_diag has {value.shape[0]} entries, the data {self._data[0].shape[0]} points")
+            if not (np.all(np.isfinite(value)) and np.all(value >= 0.0)):
+                raise ValueError("noise_diag must be finite and >= 0")
+        had = self._noise_diag is not None
+        self._noise_diag = value
+        if value is not None or had:
+            self._upload_noise_diag()
+            self._resident = False
+            self._device_theta = None
+
+    def _upload_noise_diag(self):
+        """The per-point term goes wherever the data goes: every engine this model opens gets it behind ``set_data``."""
+        if not hasattr(self.engine, "set_noise_diag"):
+            if self._noise_diag is not None and np.any(self._noise_diag != 0.0):
+                raise NotImplementedError(f"per-point observation noise (noise_diag) is not available on {type(self.engine).__name__}")
+            return
+        self.engine.set_noise_diag(self._noise_diag)
+
+    def append_data(self, x_new, y_new, s_new=None):
         """Extend the training data by ``x_new [k, D]``, ``y_new [k]`` or ``[k, 1]`` WITHOUT touching the hyper-parameters
         (``gpso_append``): when the posterior on the device is the one of the current hyper-parameters it is extended in
         place -- O(N^2 k) -- instead of refactorised.  Returns True when the device posterior was extended (or refitted at
-        the same hyper-parameters by the library: pad crossing, N <= 128), False for engines without ``append``."""
+        the same hyper-parameters by the library: pad crossing, N <= 128), False for engines without ``append``.
+        ``s_new`` [k]: the new points' per-point noise (``gpso_append_noise``); None = zeros."""
         x_new = np.ascontiguousarray(np.atleast_2d(x_new), dtype=np.float64)
         y_new = np.ascontiguousarray(y_new, dtype=np.float64).reshape(-1, 1)
         assert x_new.shape[0] == y_new.shape[0] and x_new.shape[1] == self._data[0].shape[1]
         x = np.concatenate([self._data[0], x_new])
         y = np.concatenate([self._data[1], y_new])
+        s = None  # the per-point noise of the N + k points; stays None while none was ever given
+        if s_new is not None:
+            s_new = np.ascontiguousarray(s_new, dtype=np.float64).reshape(-1)
+            assert s_new.shape[0] == x_new.shape[0]
+        if self._noise_diag is not None or (s_new is not None and np.any(s_new != 0.0)):
+            s_old = self._noise_diag if self._noise_diag is not None else np.zeros(self._data[0].shape[0])
+            s_new = s_new if s_new is not None else np.zeros(x_new.shape[0])
+            s = np.concatenate([s_old, s_new])
         if not hasattr(self.engine, "append"):
             self.data = (x, y)
+            if s is not None:
+                self.noise_diag = s
             return False
         self._ensure_resident()  # the posterior of the data so far at the current hyper-parameters (a fit only if it is not there)
         try:
-            nlml, _ = self.engine.append(x_new, y_new[:, 0])
+            if s is None:
+                nlml, _ = self.engine.append(x_new, y_new[:, 0])
+            else:
+                nlml, _ = self.engine.append(x_new, y_new[:, 0], s_new)
         except np.linalg.LinAlgError:
             # the appended block is not positive definite in this arithmetic (GPSO_E_NOTPD): whatever the device still
             # holds, the model's state must be ONE consistent thing -- the N + k points as data, no resident posterior,
             # nothing known about the device's hyper-parameters -- so that the caller's next step (GPRSurrogate: a
             # re-optimisation, which may reopen a float32 engine as "mixed") starts from a plain ``model.data = (x, y)``
             self.data = (x, y)
+            if s is not None:
+                self.noise_diag = s
             raise
         # only a successful append changes what the model claims
         self._data = (x, y)
+        self._noise_diag = s
         self._last_nlml = nlml
         self._resident = True
         return True
@@ -290,6 +342,8 @@ class HipGPR:
         old.close()
         x, y = self._data
         self.engine.set_data(x, y[:, 0])
+        if self._noise_diag is not None:
+            self._upload_noise_diag()
         self._resident = False
         self._device_theta = None
         return True

@@ -73,6 +73,7 @@ class GPSOptimiser:
         self.update_cycle = update_cycle
         self.n_eval_counter = 0
         self.iterations = 0
+        self.eval_repeats_noise = False  # (``run``: store the variance of each aggregated score with its point)
         self.n_workers = n_workers
         callbacks = callbacks or []
         assert all(isinstance(cb, GPSOCallback) for cb in callbacks)
@@ -128,10 +129,16 @@ class GPSOptimiser:
             raise TypeError("init_samples must be None or a numpy array of original coordinates")
         centre_orig = self.param_space.denormalise_coords(np.array([[mid] * d]))
         all_coords = np.vstack([orig_coords, centre_orig])
-        all_scores = self.evaluate_objective_function(all_coords)
+        if self.eval_repeats_noise:
+            all_scores, all_vars = self.evaluate_objective_function(all_coords)
+        else:
+            all_scores = self.evaluate_objective_function(all_coords)
         self.param_space.score = float(all_scores[-1])
         self.param_space.label = PointLabels.evaluated
-        self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores)
+        if self.eval_repeats_noise:
+            self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores, score_vars=all_vars)
+        else:
+            self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores)
         logging.debug(f"Initialised with {all_coords.shape[0]} points")
 
     # -- update --------------------------------------------------------------------------------
@@ -206,10 +213,16 @@ class GPSOptimiser:
             max_score = float(leaf.score)  # the pre-evaluation score drives the comparison
             point = self._point_of(leaf)
             if point.label == PointLabels.gp_based:
-                new_score = float(self.evaluate_objective_function(
-                    self.param_space.denormalise_coords(point.normed_coord[np.newaxis, :]))[0])
-                self.gp_surr.points.append(
-                    GPPoint(point.normed_coord, new_score, 0.0, 0.0, PointLabels.evaluated))
+                orig = self.param_space.denormalise_coords(point.normed_coord[np.newaxis, :])
+                if self.eval_repeats_noise:
+                    scores, variances = self.evaluate_objective_function(orig)
+                    new_score = float(scores[0])
+                    self.gp_surr.append(point.normed_coord[np.newaxis, :], np.array([new_score]),
+                                        score_vars=np.array([float(variances[0])]))
+                else:
+                    new_score = float(self.evaluate_objective_function(orig)[0])
+                    self.gp_surr.points.append(
+                        GPPoint(point.normed_coord, new_score, 0.0, 0.0, PointLabels.evaluated))
                 leaf.score = new_score
                 leaf.label = PointLabels.evaluated
                 logging.debug(f"Leaf {leaf.name} updated to new evaluated score: {leaf.score}")
@@ -237,8 +250,11 @@ class GPSOptimiser:
             for i, coords in enumerate(orig_coords):
                 self.saver.save_runs(results[i::n], scores[i::n],
                                      dict(zip(self.param_space.parameter_names, coords)))
-        return self.eval_repeats_function(
-            np.array(scores).astype(float).reshape((self.eval_repeats, -1)))
+        table = np.array(scores).astype(float).reshape((self.eval_repeats, -1))
+        if self.eval_repeats_noise:
+            # the variance of the MEAN of the repeats: what the aggregated score is known to, a fixed per-point noise term
+            return self.eval_repeats_function(table), np.var(table, axis=0, ddof=1) / self.eval_repeats
+        return self.eval_repeats_function(table)
 
     def _stopping_condition(self):
         if self.stop_cond == "evaluations":
@@ -271,9 +287,24 @@ class GPSOptimiser:
         self.last_update_idx = update_idx
         return self.gp_surr.highest_score
 
+    @staticmethod
+    def _check_repeats_noise(eval_repeats_noise, eval_repeats, eval_repeats_function):
+        """s = var(scores, ddof=1) / eval_repeats is the variance of a mean, and of nothing else."""
+        if not eval_repeats_noise:
+            return
+        if eval_repeats < 2:
+            raise ValueError(f"eval_repeats_noise needs eval_repeats >= 2 to estimate a variance (eval_repeats={eval_repeats})")
+        if eval_repeats_function is not np.mean:
+            raise ValueError("eval_repeats_noise is the variance of the mean of the repeats: eval_repeats_function must be np.mean")
+
     def run(self, objective_function, init_samples=None, eval_repeats=1, eval_repeats_function=np.mean,
-            **kwargs):
+            eval_repeats_noise=False, **kwargs):
+        """``eval_repeats_noise`` (not in the reference): with ``eval_repeats`` >= 2 and the mean as the aggregate, store
+        the variance of each mean score, var(repeats, ddof=1) / eval_repeats, with its point; the surrogate then models it
+        as a fixed per-point noise term beside the trained one (``GPRSurrogate``).  False: the reference's behaviour."""
         assert callable(objective_function)
+        self._check_repeats_noise(eval_repeats_noise, eval_repeats, eval_repeats_function)
+        self.eval_repeats_noise = bool(eval_repeats_noise)
         self.obj_func = objective_function
         self.eval_repeats = eval_repeats
         assert callable(eval_repeats_function)
@@ -303,13 +334,17 @@ class GPSOptimiser:
         self.param_space.save(os.path.join(folder, self.PARAM_SPACE_FILE))
         self.gp_surr.save(folder)
         attrs = {a: getattr(self, a) for a in self.SAVE_ATTRS}
+        if self.eval_repeats_noise:  # (absent: False -- a run without it writes the file it always wrote)
+            attrs["eval_repeats_noise"] = True
         with open(os.path.join(folder, self.OPT_ATTRS_FILE), "w") as fh:
             fh.write(json.dumps(attrs))
         logging.info(f"Saved optimiser to {folder}")
 
     @classmethod
     def resume_from_saved(cls, folder, additional_budget, objective_function, gp_surrogate=GPRSurrogate,
-                          eval_repeats_function=np.mean, callbacks=None, saver=None):
+                          eval_repeats_function=np.mean, callbacks=None, saver=None, eval_repeats_noise=None):
+        """``eval_repeats_noise``: None (default) continues as the saved run did (a state file without the key: False);
+        True / False overrides it."""
         space = ParameterSpace.from_file(os.path.join(folder, cls.PARAM_SPACE_FILE))
         surr = gp_surrogate.from_saved(folder)
         with open(os.path.join(folder, cls.OPT_ATTRS_FILE)) as fh:
@@ -317,6 +352,9 @@ class GPSOptimiser:
         opt = cls(parameter_space=space, gp_surrogate=surr, callbacks=callbacks, saver=saver)
         for name, value in attrs.items():
             setattr(opt, name, value)
+        if eval_repeats_noise is not None:
+            opt.eval_repeats_noise = bool(eval_repeats_noise)
+        cls._check_repeats_noise(opt.eval_repeats_noise, opt.eval_repeats, eval_repeats_function)
         assert callable(objective_function)
         opt.obj_func = objective_function
         assert callable(eval_repeats_function)
