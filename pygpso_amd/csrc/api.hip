@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "rccl_api.hpp"
+#include "resident.hpp"
 
 using namespace gpso;
 
@@ -379,7 +380,10 @@ struct EngineT : Engine {
   // problem
   int64_t n = 0, npad = 0;
   int d = 0, dp = 0;
-  bool have_data = false, have_post = false, have_kinv = false, chol_valid = false;
+  // which of the buffers below mean something (resident.hpp: the record and its transitions, its only writers)
+  gpso::Resident res{kFloatPredict ? GPSO_MATH_F16X3 : GPSO_MATH_NATIVE};
+  using Post = gpso::Post;
+  using Copy = gpso::Copy;
   KernParams kp{0, 1.0, 1e-3, 0.0};
   int n_ls = 1;
   std::vector<double> ls_host;
@@ -399,37 +403,27 @@ struct EngineT : Engine {
   // device (zero padding), read wherever a fit adds `noise` to a diagonal; s_dev() is NULL while none is set, and every
   // such site then runs what it ran before the vector existed
   DevBuf sdiag;
-  bool have_s = false;
   std::vector<double> s_host;  // [n] host mirror (the refit paths of gpso_append, GPSO_VEC_NOISE_DIAG)
   double s_max = 0.0;          // max s_i: fit_plane_scales' bounds
-  const double* s_dev() const { return have_s ? static_cast<const double*>(sdiag.p) : nullptr; }
-  bool has_noise_diag() const override { return have_s; }
+  const double* s_dev() const { return res.have_s ? static_cast<const double*>(sdiag.p) : nullptr; }
+  bool has_noise_diag() const override { return res.have_s; }
   int fit_overlap = 2;              // GPSO_OPT_FIT_OVERLAP (bit 0 look-ahead, bit 1 overlapped inverse: the default): two-level double fits overlap chains, updates and the inverse (0: sequential, round 5)
   int fit_planes_mode = 2;          // GPSO_OPT_FIT_BF16_SYRK: 0 f32 MFMA | 1 bf16 pieces (6 MFMAs per product) | 2 fp16 pieces (3) where representable
-  // predict math: the OPTION (math_auto: GPSO_MATH_AUTO) and what the resident posterior uses (math, and
-  // math_native_fallback when the self-test preferred the f32 MFMA kernel for it)
-  // GPSO_MATH_AUTO walks the ladder fp16 split (3 MFMAs per product) -> bf16x6 -> f32 MFMA kernel, one rung down each
-  // time the self-test of the posterior at hand fails with the rung it is on (selftest_with_fallback)
+  // predict math, the OPTION (what the posterior uses: res.math).  GPSO_MATH_AUTO walks the ladder fp16 split (3 MFMAs per
+  // product) -> bf16x6 -> f32 MFMA kernel, one rung down each time the posterior's self-test fails on it (selftest_with_fallback)
   static constexpr int kAutoFirst = kFloatPredict ? GPSO_MATH_F16X3 : GPSO_MATH_NATIVE;
-  int math = kAutoFirst;
-  bool math_auto = kFloatPredict, math_native_fallback = false;
-  // generation of the cross-Gram tile in float-predict contexts: the OPTION (gen_mode) and what the
-  // resident posterior actually uses (gen_eff32).  GPSO_GEN_AUTO starts every posterior in float -- the
-  // fast form -- and lets the precision self-test decide: if the float form misses the tolerances the
-  // posterior moves to double generation and is tested again (decide_generation).
+  bool math_auto = kFloatPredict;
+  // generation of the cross-Gram tile in float-predict contexts, the OPTION (what the posterior uses: res.gen_eff32).  AUTO:
+  // a posterior whose float form misses the tolerances moves to double generation and is tested again (decide_generation)
   int gen_mode = GPSO_GEN_AUTO;
-  bool gen_eff32 = true;
-  bool gen_decided = false;     // AUTO: has the self-test ruled on this posterior?
-  bool gen32_inputs_ok = false; // xs32 / xnorm32 / xs_p32 match the resident posterior
   int split_variant = GPSO_SPLIT_KERNEL_AUTO;  // GPSO_OPT_SPLIT_KERNEL
   int row_loop = 1;  // GPSO_OPT_ROW_LOOP (leaf_split.hpp: leaf_row_splits)
   int contraction = GPSO_CONTRACTION_AUTO;     // GPSO_OPT_CONTRACTION
   // the x.x* contraction of the fp16-split kernel runs on the fp16 pipe under float generation (D_pad + 1 slots in at most
   // two chunks of 32: every D this library accepts).  Measured in one process on one posterior (tools/c16_check.py,
   // profiles/r04_c16_check.jsonl), fp16 pipe against the f32 instruction: D = 6 +4 %, 12 +8 %, 20 +17 %, 33 +28 %, 40 +30 %
-  bool c16_fallback = false;  // this posterior's float generation keeps the f32 contraction (decide_generation)
   bool c16_in_use(bool gen64) const {
-    if (!kFloatPredict || gen64 || c16_fallback || !f16_split() || contraction == GPSO_CONTRACTION_F32 || leaf_c16_chunks(dp / 4) > 2) return false;
+    if (!kFloatPredict || gen64 || res.c16_fallback || !f16_split() || contraction == GPSO_CONTRACTION_F32 || leaf_c16_chunks(dp / 4) > 2) return false;
     return leaf_bf16_lds_bytes(2, dp / 4, 4, true) <= 160 * 1024;
   }
   bool small_calls = true, one_launch = true, one_launch_everywhere = false;  // GPSO_OPT_SMALL_CALLS
@@ -437,9 +431,6 @@ struct EngineT : Engine {
   bool one_refused = false;                    // the one-launch kernel asked for the general sequence (this call only)
   int64_t single_level_max = -1;  // < 0: library default
   bool fused_small = true;        // GPSO_OPT_FIT_FUSED_SMALL
-  int small_tile_rows = 8;        // tile rows of the 128-padded linv_p that may be non-zero (8: all / unknown)
-  bool linv_b_valid = false;
-  bool linv_b_pending = false;  // the split pieces of the resident L^-1 are still to be packed (a fit that returned a gradient)
   std::vector<int64_t> segoff_cache;  // what the device copy of seg_off currently holds
   double* host_direct = nullptr;      // pinned host memory the arg-max of the call in flight writes its records to
   double* result_slot = nullptr;      // asynchronous call being enqueued: its own pinned slot instead of the shared scratch
@@ -459,7 +450,8 @@ struct EngineT : Engine {
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   // precision self-test
-  bool check = false, st_done = false, st_have = false;
+  bool check = false;
+  bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
   double tol_var = 1.0e-4, tol_mean = 1.0e-4;
   double st_vals[6] = {0, 0, 0, 0, 0, 0};
   DevBuf st_mean, st_var, st_out;
@@ -480,15 +472,15 @@ struct EngineT : Engine {
   }
 
   // generation type actually used by the resident posterior
-  bool gen_double() const { return !kFloatPredict || !gen_eff32; }
+  bool gen_double() const { return !kFloatPredict || !res.gen_eff32; }
   // the split-bf16 kernel keeps its leaf fragments in LDS: with double generation they do not fit the
   // 160 KB for D > 24 (bf16x6) / D > 36 (bf16x3) -- those calls run the native f32 kernel instead (accuracy
   // decides the generation type, the kernel follows)
   bool bf16_fits(bool gen64) const {
     return c16_in_use(gen64) || leaf_bf16_lds_bytes(nsplit(), dp / 4, gen64 ? 8 : 4) <= 160 * 1024;
   }
-  int nsplit() const { return math == GPSO_MATH_BF16X6 ? 3 : 2; }
-  bool f16_split() const { return math == GPSO_MATH_F16X3; }
+  int nsplit() const { return res.math == GPSO_MATH_BF16X6 ? 3 : 2; }
+  bool f16_split() const { return res.math == GPSO_MATH_F16X3; }
   // bytes of the split copy of L^-1: the planes and, behind them, one 256-byte slot for the power-of-two scale of the
   // fp16 split (2 floats, written on the device at packing time) -- it travels with the planes in a hand-off.  Under
   // GPSO_MATH_AUTO room for three planes whatever the stage, so that both sides of a hand-off list the same sizes.
@@ -513,21 +505,21 @@ struct EngineT : Engine {
     f16_handed_at = f16_scale();
     return f16_scale();
   }
-  bool bf16_usable() const { return kFloatPredict && math != GPSO_MATH_NATIVE && !math_native_fallback && npad > 0 && npad % 256 == 0; }
+  bool bf16_usable() const { return res.split_usable(kFloatPredict, npad); }
 
   // An evaluation WITH gradient is a step of the hyper-parameter search: the next call is another evaluation, not a
   // prediction, and its 16-bit pieces of L^-1 (10 us at C3, 0.5 ms at C5) would be packed for nothing.  They are packed
   // when something first asks for them: every predict-type call, the self-test and the hand-off paths come through
   // decide_generation(), which calls this.
   int ensure_split_pieces() {
-    if (!linv_b_pending) return GPSO_OK;
-    linv_b_pending = false;
-    return chol_valid ? pack_bf16() : GPSO_OK;
+    if (res.linv_b != Copy::Deferred) return GPSO_OK;
+    if (res.chol_valid) return pack_bf16();
+    res.split_packed(false);
+    return GPSO_OK;
   }
   // (re)build the bf16 pieces of L^-1 from the fit-type L^-1 resident in `linv`
   int pack_bf16() {
-    linv_b_valid = false;
-    linv_b_pending = false;
+    res.split_packed(false);
     if (!bf16_usable()) return GPSO_OK;
     int rc = ensure(linv_b, split_bytes());
     if (rc) return rc;
@@ -539,7 +531,7 @@ struct EngineT : Engine {
       launch_pack_linv_bf16<TF>(st(), nsplit(), as<TF>(linv), n, npad, split_planes());
     }
     HIPCHECK(hipGetLastError());
-    linv_b_valid = true;
+    res.split_packed(true);
     return GPSO_OK;
   }
 
@@ -586,8 +578,7 @@ struct EngineT : Engine {
         if (value != GPSO_CONTRACTION_AUTO && value != GPSO_CONTRACTION_F32 && value != GPSO_CONTRACTION_F16) return ctx->fail(GPSO_E_ARG, "unknown contraction %d", value);
         if (value != contraction) {
           contraction = value;
-          gen_decided = false;  // (other bits: the self-test rules again)
-          st_done = false;
+          res.contraction_changed();
         }
         return GPSO_OK;
       case GPSO_OPT_SPLIT_KERNEL:
@@ -608,7 +599,7 @@ struct EngineT : Engine {
           return GPSO_OK;
         }
         if (value != gen_mode) {
-          if (have_post && !have_data && value != GPSO_GEN_F64)
+          if (res.has_post() && !res.have_data && value != GPSO_GEN_F64)
             return ctx->fail(GPSO_E_STATE, "set GPSO_OPT_GENERATION before installing a posterior");
           gen_mode = value;
           reset_generation();
@@ -626,14 +617,11 @@ struct EngineT : Engine {
       return ctx->fail(GPSO_E_ARG, "split (bf16 / fp16) predict math needs a GPSO_F32 or GPSO_MIXED context");
     const bool want_auto = value == GPSO_MATH_AUTO;
     if (want_auto) value = kAutoFirst;
-    if (value == math && want_auto == math_auto && !math_native_fallback) return GPSO_OK;
-    math = value;
+    if (value == res.math && want_auto == math_auto && !res.math_native_fallback) return GPSO_OK;
     math_auto = want_auto;
-    math_native_fallback = false;
-    linv_b_valid = false;
-    st_done = false;
+    res.math_chosen(value);
     reset_generation();
-    if (chol_valid) {  // L^-1 is resident: make the new mode usable right away
+    if (res.chol_valid) {  // L^-1 is resident: make the new mode usable right away
       int rc = pack_bf16();
       if (rc) return rc;
     }
@@ -778,9 +766,7 @@ struct EngineT : Engine {
     slice(linv_b, b_split);
     arena_npad = npad;
     arena_dp = dp;
-    small_tile_rows = 8;  // the slices moved: whatever linv_p's bytes held belongs to another layout
-    linv_b_valid = false;
-    linv_p_valid = false;
+    res.recarved();
     return GPSO_OK;
   }
   // the contiguous range of the arena the resident posterior uses: offset into the arena and length
@@ -794,22 +780,18 @@ struct EngineT : Engine {
       *bytes = (size_t)(static_cast<const char*>(alpha.p) - base) + alpha.bytes;
     }
   }
-  bool linv_p_valid = false;  // the packed f32 / f64 L^-1 of the resident posterior is here (a receiver of a split posterior: no)
 
   // ---- what the peers of a group hold of THIS posterior (round 6: gpso_broadcast_posterior_rows) --------------------------------
   // A hand-off (gpso_broadcast_posterior, or a span copy followed by gpso_posterior_mark_synced / gpso_adopt_posterior)
   // records the rows the other side then holds; gpso_append extends the posterior in place and leaves the record alone, so
   // the NEXT hand-off may move only what the appends wrote -- the new rows of the scaled inputs and of each predict-ready
   // copy of L^-1, alpha, the hyper block -- instead of the whole range (C5: ~1.1 MB instead of 1.07 GB for 7 points).
-  // Anything that makes another posterior (gpso_set_data, gpso_fit_eval, gpso_set_posterior, a new shape) clears it.
-  int64_t sync_n = -1;      // rows the peers hold; -1: unknown
-  int sync_math = -1;       // predict math in use then (the ladder may move: other pieces)
-  float sync_scale = 0.0f;  // fp16 split: the scale the peers' planes were packed with (an append that crosses a power of two repacks all rows)
-  void forget_peers() { sync_n = -1; }
+  // Anything that makes another posterior clears it (res.sync_n: posterior_dropped), an append that crosses a power of two of the
+  // fp16 scale repacks all rows (res.sync_scale).
   // the scale slot's [1] (2^-sa) of the fp16 split as the device holds it now; 0 where it does not apply
   int current_split_scale(float* out) {
     *out = 0.0f;
-    if (!(kFloatPredict && f16_split() && bf16_usable() && linv_b_valid)) return GPSO_OK;
+    if (!(kFloatPredict && f16_split() && bf16_usable() && res.linv_b == Copy::Valid)) return GPSO_OK;
     float* h = reinterpret_cast<float*>(ctx->pinned_scratch(256) + 124);  // (a slot of the scratch nothing else reads)
     HIPCHECK(hipMemcpyAsync(h, f16_scale() + 1, 4, hipMemcpyDeviceToHost, st()));
     HIPCHECK(hipStreamSynchronize(st()));
@@ -841,8 +823,8 @@ struct EngineT : Engine {
   }
   // can the peers be brought up to date by rows?  (root side; scale = current_split_scale)
   bool rows_apply(float scale) const {
-    return have_post && sync_n >= 0 && sync_n <= n && sync_math == math_in_use() && scale == sync_scale &&
-           (sync_n == n || sync_n / 16 <= (n - 1) / 16);
+    return res.has_post() && res.sync_n >= 0 && res.sync_n <= n && res.sync_math == math_in_use() && scale == res.sync_scale &&
+           (res.sync_n == n || res.sync_n / 16 <= (n - 1) / 16);
   }
 
   int ensure_fit_buffers() {
@@ -900,30 +882,24 @@ struct EngineT : Engine {
                            as<double>(xs_p64));
     return GPSO_OK;
   }
-  // a new posterior (or new options): generation starts over -- float unless double was asked for -- and the
-  // self-test has to rule again
   void reset_generation() {
     f16_handed_at = nullptr;  // (a fit that failed between its solve and its packing leaves nothing behind)
-    math_native_fallback = false;
-    if (math_auto) math = kAutoFirst;  // the ladder starts over with every posterior
-    gen_eff32 = kFloatPredict && gen_mode != GPSO_GEN_F64;
-    gen_decided = false;
-    gen32_inputs_ok = false;
-    c16_fallback = false;
-    st_done = false;
+    res.reset_generation(kFloatPredict, math_auto, gen_mode);
   }
   // float copies of the scaled inputs, made when a float-generation predict first needs them, from the
   // double ones (resident after a fit AND after a hand-off): two short launches, not two per loss evaluation
   int ensure_generation_inputs() {
-    if (gen_double() || gen32_inputs_ok) return GPSO_OK;
+    if (gen_double() || res.gen32_inputs_ok) return GPSO_OK;
     launch_gen_inputs_f32(st(), as<double>(xs64), npad, dp, as<float>(xs32), as<float>(xnorm32), as<float>(xs_p32));
     launch_gen_inputs_f16(st(), as<float>(xs32), as<float>(xnorm32), npad, dp, as<float>(c16_scal), xs_h16.p);
-    gen32_inputs_ok = true;
+    res.gen_inputs_made();
     return GPSO_OK;
   }
 
   // ------------------------------------------------------------------------------------------
-  int set_data(const double* X, const double* y, int64_t n_, int d_) override {
+  int set_data(const double* X, const double* y, int64_t n_, int d_) override { return put_rows(X, y, n_, d_, false); }
+  // keep_stash: the rows are the inducing points of the stashed training set (gpso_sgpr_set_inducing), not new data
+  int put_rows(const double* X, const double* y, int64_t n_, int d_, bool keep_stash) {
     if (!X || !y) return ctx->fail(GPSO_E_ARG, "X / y must not be NULL");
     int rc = refuse_if_async("gpso_set_data");
     if (rc) return rc;
@@ -945,22 +921,15 @@ struct EngineT : Engine {
     }
     if (X != x_host.data()) x_host.assign(X, X + (size_t)n * d);
     if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
-    have_data = true;
-    have_s = false;  // (every gpso_set_data clears the per-point noise: it belonged to the rows just replaced)
-    s_host.clear();
+    s_host.clear();  // (every gpso_set_data clears the per-point noise: it belonged to the rows just replaced)
     s_max = 0.0;
-    have_post = have_kinv = chol_valid = linv_p_valid = false;
-    vgp_post = sgpr_post = svgp_post = false;
-    if (!sg_keep) sg_have = sg_have_z = false;  // (the caller's own gpso_set_data: new data, no inducing points)
-    sg_factors = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.new_data(keep_stash);
     return GPSO_OK;
   }
 
   // s[n_] >= 0 beside the resident data (NULL: none); the posterior is invalidated as by new data
   int set_noise_diag(const double* sv, int64_t n_) override {
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_set_noise_diag before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_set_noise_diag before gpso_set_data");
     int rc = refuse_if_async("gpso_set_noise_diag");
     if (rc) return rc;
     if (n_ != n) return ctx->fail(GPSO_E_ARG, "gpso_set_noise_diag: n=%lld does not match the resident data (N=%lld)", (long long)n_, (long long)n);
@@ -981,20 +950,15 @@ struct EngineT : Engine {
     } else {
       s_host.clear();
     }
-    have_s = sv != nullptr;
     s_max = top;
-    have_post = have_kinv = chol_valid = linv_p_valid = false;
-    vgp_post = sgpr_post = svgp_post = false;
-    sg_factors = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.noise_changed(sv != nullptr);
     return GPSO_OK;
   }
 
   int fit_eval(int kernel, const double* ls, int n_ls_, double variance, double noise,
                double mean_c, double* nlml, double* grad) override {
     ctx->tick_timing();
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval before gpso_set_data");
     if (!ls) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
     int rc = refuse_if_async("gpso_fit_eval");
     if (rc) return rc;
@@ -1002,14 +966,12 @@ struct EngineT : Engine {
     if (rc) return rc;
     const bool small = fused_small && small_fit_eligible(n, dp);
     if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c, !small))) return rc;
-    have_post = have_kinv = chol_valid = false;
-    vgp_post = sgpr_post = svgp_post = false;
-    sg_have_z = sg_factors = false;  // (a GPR fit on the resident rows: they are no inducing points any more)
-    st_done = st_have = false;
-    forget_peers();
+    // (tile rows of linv_p beyond a one-launch fit's that may hold old data; every other fit writes, or will write, all 8)
+    const int zero_tile_rows = res.fit_begun(small ? (int)((n + 15) / 16) : 8);
     reset_generation();
     hipStream_t s = st();
     double fit_token = 0.0;
+    bool linv_p_deferred = false;
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
     if (grad && (rc = ensure(kinvb, (size_t)npad * npad * sizeof(TF)))) return rc;
     ctx->last_count[2] = small ? GPSO_FITMATH_SMALL : (sizeof(TF) == 8 ? GPSO_FITMATH_F64 : GPSO_FITMATH_F32);
@@ -1019,8 +981,7 @@ struct EngineT : Engine {
       a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.hyper = as<double>(hyper);
       for (int k = 0; k < kMaxD; ++k) a.ls[k] = ls[n_ls_ == 1 ? 0 : std::min(k, n_ls_ - 1)];
       a.n = (int)n; a.d = d; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls; a.want_grad = grad ? 1 : 0;
-      a.zero_tile_rows = small_tile_rows;  // (tile rows of linv_p beyond this fit's that may hold old data)
-      small_tile_rows = (int)((n + 15) / 16);
+      a.zero_tile_rows = zero_tile_rows;
       a.variance = variance; a.noise = noise; a.mean_c = mean_c;
       a.sdiag = s_dev();
       a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
@@ -1061,7 +1022,7 @@ struct EngineT : Engine {
           planes.ev_chain = ctx->ev_chain;
           // fp16 pieces (three MFMAs per product) when the hyper-parameters leave every plane set inside fp16's range
           // after its power-of-two scaling; bf16 pieces (six) otherwise -- the fallback rung
-          if (fit_planes_mode == 2) (void)fit_plane_scales(variance, noise, planes, have_s ? s_max : 0.0);
+          if (fit_planes_mode == 2) (void)fit_plane_scales(variance, noise, planes, res.have_s ? s_max : 0.0);
           pl = &planes;
           ctx->last_count[2] = planes.np == 2 ? GPSO_FITMATH_F16X3 : GPSO_FITMATH_BF16X6;
         }
@@ -1119,16 +1080,11 @@ struct EngineT : Engine {
       // the packed f32 / f64 copy of L^-1 feeds the NATIVE tile kernel only: a posterior that is going to predict with
       // split math (the default of float-predict contexts) packs it when -- if ever -- something asks for it
       // (ensure_linv_p: the self-test walking down GPSO_MATH_AUTO's ladder, a hand-off of all buffers)
-      linv_p_lazy = bf16_usable();
-      if (!linv_p_lazy) launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));  // (alpha's predict-type copy: alpha_sum_kernel)
-      small_tile_rows = 8;
+      linv_p_deferred = bf16_usable();
+      if (!linv_p_deferred) launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));  // (alpha's predict-type copy: alpha_sum_kernel)
     }
-    if (grad && !small) {  // (see ensure_split_pieces)
-      linv_b_valid = false;
-      linv_b_pending = bf16_usable();
-    } else if ((rc = pack_bf16())) {
-      return rc;
-    }
+    const bool split_deferred = grad && !small;  // (see ensure_split_pieces)
+    if (!split_deferred && (rc = pack_bf16())) return rc;
     if ((rc = launch_status())) return rc;
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
     constexpr size_t kHostDoubles = 8 + kGradMaxLs + 3;
@@ -1144,23 +1100,18 @@ struct EngineT : Engine {
     if (info != INT_MAX)
       return ctx->fail(GPSO_E_NOTPD, "K + noise*I is not positive definite: Cholesky failed at pivot %d", info);
     if (nlml) *nlml = host[0];
-    if (grad) {
-      // device order: ls..., variance, noise, then -sum(alpha)
+    if (grad)  // device order: ls..., variance, noise, then -sum(alpha)
       for (int h = 0; h < n_ls + 3; ++h) grad[h] = host[8 + h];
-      have_kinv = true;
-    }
-    have_post = chol_valid = st_have = true;
-    linv_p_valid = small || !linv_p_lazy;
-    if (small) linv_p_lazy = false;
+    res.fit_done(grad != nullptr, linv_p_deferred, split_deferred, bf16_usable());
     return GPSO_OK;
   }
   // ---- batched evaluation (multi-start hyper-parameter search): fit.hip small_fit_batch_kernel -------------------------
   // entries one launch may hold for the resident data: one workgroup per CU where the one-launch fit applies, else none
-  int fit_batch_max() override { return (have_data && fused_small && small_fit_eligible(n, dp)) ? kSmallBatchMax : 0; }
+  int fit_batch_max() override { return (res.have_data && fused_small && small_fit_eligible(n, dp)) ? kSmallBatchMax : 0; }
 
   // everything a batched call is refused for, before anything is touched
   int fit_eval_batch_check(int kernel, int b, int n_ls_) override {
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval_u_batch before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval_u_batch before gpso_set_data");
     int rc = refuse_if_async("gpso_fit_eval_u_batch");
     if (rc) return rc;
     if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
@@ -1222,13 +1173,10 @@ struct EngineT : Engine {
   }
 
   // the packed native-type L^-1, made on demand from the resident factor's inverse
-  bool linv_p_lazy = false;
   int ensure_linv_p() {
-    if (linv_p_valid || !linv_p_lazy || !chol_valid) return GPSO_OK;
+    if (res.linv_p != Copy::Deferred || !res.chol_valid) return GPSO_OK;
     launch_pack_linv<TF, TP>(st(), as<TF>(linv), n, npad, as<TP>(linv_p));
-    small_tile_rows = 8;
-    linv_p_valid = true;
-    linv_p_lazy = false;
+    res.linv_p_packed();
     return launch_status();
   }
 
@@ -1248,11 +1196,14 @@ struct EngineT : Engine {
           return ctx->fail(GPSO_E_ARG, "gpso_append_noise: snew[%lld]=%g must be finite and >= 0", (long long)j, sn[j]);
         sn_nonzero = sn_nonzero || sn[j] > 0.0;
       }
-    if (svgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SVGP predictive: its rows are the inducing points; set the grown data and train again");
-    if (sgpr_post) return ctx->fail(GPSO_E_STATE, "gpso_append on an SGPR predictive: its rows are the inducing points; set the grown data and train again");
-    if (vgp_post) return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
+    switch (res.post) {
+      case Post::Svgp: return ctx->fail(GPSO_E_STATE, "gpso_append on an SVGP predictive: its rows are the inducing points; set the grown data and train again");
+      case Post::Sgpr: return ctx->fail(GPSO_E_STATE, "gpso_append on an SGPR predictive: its rows are the inducing points; set the grown data and train again");
+      case Post::Vgp: return ctx->fail(GPSO_E_STATE, "gpso_append on a VGP predictive: append the data and train q again");
+      default: break;
+    }
     if (int rca = refuse_if_async("gpso_append")) return rca;
-    if (!have_data || !have_post || !chol_valid || (int64_t)y_host.size() != n)
+    if (!res.have_data || !res.has_post() || !res.chol_valid || (int64_t)y_host.size() != n)
       return ctx->fail(GPSO_E_STATE, "gpso_append needs a posterior fitted on this context (gpso_set_data + gpso_fit_eval)");
     const int64_t n_new = n + k;
     if (n_new > 65536) return ctx->fail(GPSO_E_ARG, "n=%lld above the supported 65536", (long long)n_new);
@@ -1268,10 +1219,10 @@ struct EngineT : Engine {
       X.insert(X.end(), Xn, Xn + (size_t)k * d);
       y.insert(y.end(), yn, yn + (size_t)k);
       // (set_data clears the per-point noise: the refit carries it along, the new points' values behind the resident ones)
-      const bool with_s = have_s || sn_nonzero, had_s = have_s;
+      const bool with_s = res.have_s || sn_nonzero, had_s = res.have_s;
       std::vector<double> sv;
       if (with_s) {
-        sv = have_s ? s_host : std::vector<double>((size_t)n, 0.0);
+        sv = res.have_s ? s_host : std::vector<double>((size_t)n, 0.0);
         if (sn != nullptr) sv.insert(sv.end(), sn, sn + (size_t)k);
         else sv.resize((size_t)n_new, 0.0);
       }
@@ -1307,8 +1258,8 @@ struct EngineT : Engine {
     const int kpad = append_kp((int)k);
     if ((rc = ensure(app, append_scratch_doubles(npad, kpad) * 8))) return rc;
     // the first per-point noise of this context: the resident rows carry zeros.  The context only COUNTS as carrying a
-    // vector (have_s) once the append has succeeded: a failed one leaves it as it found it
-    const bool new_s = !have_s && sn_nonzero, use_s = have_s || new_s;
+    // vector (res.have_s) once the append has succeeded: a failed one leaves it as it found it
+    const bool new_s = !res.have_s && sn_nonzero, use_s = res.have_s || new_s;
     if (new_s) {
       if ((rc = ensure(sdiag, (size_t)npad * 8))) return rc;
       HIPCHECK(hipMemsetAsync(sdiag.p, 0, (size_t)npad * 8, s));
@@ -1335,7 +1286,7 @@ struct EngineT : Engine {
     // the fp16 split's scale follows max |L^-1|: the slot holds it when the pieces are built, or when the fit's solve
     // handed it over for a packing still to come
     const bool f16_max_live = kFloatPredict && f16_split() && bf16_usable() &&
-                              (linv_b_valid || (linv_b_pending && f16_handed_at != nullptr && f16_handed_at == f16_scale()));
+                              (res.linv_b == Copy::Valid || (res.linv_b == Copy::Deferred && f16_handed_at != nullptr && f16_handed_at == f16_scale()));
     a.f16_scal = f16_max_live ? f16_scale() : nullptr;
     host[0] = host[1] = 0.0;
     launch_append<TF, TP>(s, a, app.p, as<TF>(linv), as<TF>(Lf), as<TF>(white), as<TF>(alpha_f));
@@ -1343,11 +1294,11 @@ struct EngineT : Engine {
     // demand from the extended matrix)
     const int64_t rt0 = n / 16;
     auto repack = [&](int64_t rows) {
-      if (linv_b_valid) {
+      if (res.linv_b == Copy::Valid) {
         if (f16_split()) launch_pack_linv_f16<TF>(s, as<TF>(linv), rows, npad, f16_scale(), split_planes(), true, rt0);
         else launch_pack_linv_bf16<TF>(s, nsplit(), as<TF>(linv), rows, npad, split_planes(), rt0);
       }
-      if (linv_p_valid) launch_pack_linv<TF, TP>(s, as<TF>(linv), rows, npad, as<TP>(linv_p), rt0);
+      if (res.linv_p == Copy::Valid) launch_pack_linv<TF, TP>(s, as<TF>(linv), rows, npad, as<TP>(linv_p), rt0);
     };
     repack(n_new);
     if ((rc = launch_status())) return rc;
@@ -1360,9 +1311,9 @@ struct EngineT : Engine {
       // (append_cols_kernel did not run); the tiles just repacked and the scaled-input rows go back to their padding state
       const int pivot = (int)host[2];
       repack(n);
-      if (have_s) HIPCHECK(hipMemsetAsync(as<double>(sdiag) + n, 0, (size_t)k * 8, s));  // (back to padding; a vector this call made is simply not adopted)
+      if (res.have_s) HIPCHECK(hipMemsetAsync(as<double>(sdiag) + n, 0, (size_t)k * 8, s));  // (back to padding; a vector this call made is simply not adopted)
       (void)scale_inputs();
-      gen32_inputs_ok = false;
+      res.append_refused();
       HIPCHECK(hipStreamSynchronize(s));
       return ctx->fail(GPSO_E_NOTPD, "K + noise*I is not positive definite: the appended block's Cholesky failed at pivot %d "
                        "(the posterior of the first %lld points is unchanged)", pivot, (long long)n);
@@ -1372,19 +1323,15 @@ struct EngineT : Engine {
     if (new_s) {
       s_host.assign((size_t)n, 0.0);
       s_max = 0.0;
-      have_s = true;
     }
-    if (have_s) {
+    if (use_s) {
       if (pass_s) s_host.insert(s_host.end(), sn, sn + (size_t)k);
       else s_host.resize((size_t)n_new, 0.0);
       if (pass_s) s_max = std::max(s_max, *std::max_element(sn, sn + (size_t)k));
     }
     n = n_new;
     if (nlml) *nlml = host[0];
-    have_kinv = false;
-    st_done = false;           // the self-test looks at the extended posterior before the next prediction
-    gen32_inputs_ok = false;   // float / fp16 copies of the scaled inputs: derived again from the extended double ones
-    small_tile_rows = 8;
+    res.appended(new_s);
     return GPSO_OK;
   }
 
@@ -1405,15 +1352,9 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(x64.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp, L, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
     HIPCHECK(hipMemcpyAsync(tmp + (size_t)n * n, alpha64, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    have_data = false;  // y unknown: a later fit needs gpso_set_data
-    have_s = false;     // (... and gpso_set_noise_diag behind it)
     s_host.clear();
     s_max = 0.0;
-    vgp_post = sgpr_post = svgp_post = false;
-    sg_have = sg_have_z = sg_factors = false;
-    have_post = have_kinv = chol_valid = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.install_begun();
     reset_generation();
     if ((rc = scale_inputs())) return rc;
     HIPCHECK(hipMemsetAsync(linv.p, 0, (size_t)npad * npad * sizeof(TF), s));
@@ -1423,11 +1364,10 @@ struct EngineT : Engine {
     launch_convert_in<TF>(s, tmp + (size_t)n * n, as<TF>(alpha_f), 1, n, npad);
     launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
     launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    small_tile_rows = 8;
     if ((rc = pack_bf16())) return rc;
     HIPCHECK(hipStreamSynchronize(s));  // the caller's host buffers are free again on return
     if ((rc = launch_status())) return rc;
-    have_post = chol_valid = linv_p_valid = true;
+    res.installed();
     return GPSO_OK;
   }
 
@@ -1437,7 +1377,6 @@ struct EngineT : Engine {
   // the fit's buffers (K, Lf, linv, work) holding VGP intermediates, so they invalidate any GPR posterior first.
   DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;
   int64_t vq_n = -1, vq_npad = -1;  // shape q was made for (another shape: q restarts at the prior)
-  bool vgp_post = false;            // the resident posterior is a VGP predictive (no targets: no append, no self-test)
   static constexpr double kVgpJitter = 1.0e-6;  // GPflow's default_jitter, in the K of the ELBO and of the predictive
   enum { kVgpR = 0, kVgpFvar = 1, kVgpSrow = 2, kVgpH = 3, kVgpH2 = 4, kVgpZero = 5, kVgpVecs = 6 };
   double* vvec_at(int k) const { return as<double>(vvec) + (size_t)k * npad; }
@@ -1499,9 +1438,9 @@ struct EngineT : Engine {
     return launch_status();
   }
 
-  int vgp_begin() {
+  int vgp_begin(bool sparse = false /* the rows are inducing points: the SGPR's factors go too */) {
     if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "VGP call before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "VGP call before gpso_set_data");
     int rc = refuse_if_async("a VGP call");
     if (rc) return rc;
     if ((rc = ensure_fit_buffers())) return rc;
@@ -1513,10 +1452,7 @@ struct EngineT : Engine {
     if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
     if (vlik_kind != GPSO_LIK_GAUSSIAN && (rc = ensure(vlvec, (size_t)kLikVecs * npad * 8))) return rc;
     if (vq_n != n || vq_npad != npad) vgp_prior();
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
-    linv_p_lazy = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.variational_begun(sparse);
     reset_generation();
     return GPSO_OK;
   }
@@ -1547,8 +1483,8 @@ struct EngineT : Engine {
     return vgp_chol(as<double>(K), as<double>(Lf), as<double>(linv), vinfo() + 0, 0.0);
   }
   // wait for the stream, then the verdicts of the factorisations (out: host copy of vsmall)
-  // (model: 0 the VGP, 1 the SGPR, 2 the SVGP -- the names in a failure's message)
-  int vgp_finish(double** out, int model = 0) {
+  // (kind: whose factorisations these are -- the names in a failure's message)
+  int vgp_finish(double** out, Post kind = Post::Vgp) {
     double* host = ctx->pinned_scratch(kVgpSmall);
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     HIPCHECK(hipMemcpyAsync(host, vsmall.p, kVgpSmall * 8, hipMemcpyDeviceToHost, st()));
@@ -1565,7 +1501,7 @@ struct EngineT : Engine {
     for (int q = 0; q < 4; ++q)
       if (info[q] != INT_MAX)
         return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d",
-                         (model == 2 ? what_svgp : model == 1 ? what_sgpr : what)[q], info[q]);
+                         (kind == Post::Svgp ? what_svgp : kind == Post::Sgpr ? what_sgpr : what)[q], info[q]);
     *out = host;
     return GPSO_OK;
   }
@@ -1575,7 +1511,7 @@ struct EngineT : Engine {
 
   int vgp_set_q(const double* mu, const double* S, int64_t n_) override {
     if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_set_q before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_set_q before gpso_set_data");
     if (n_ != n) return ctx->fail(GPSO_E_ARG, "q of %lld points for training data of %lld", (long long)n_, (long long)n);
     int rc = vgp_begin();
     if (rc) return rc;
@@ -1603,7 +1539,7 @@ struct EngineT : Engine {
   // Inside one padded size the padding of q already IS that prior; a new padded size re-lays the leading block out.
   int vgp_extend_q() override {
     if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_extend_q before gpso_set_data");
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_extend_q before gpso_set_data");
     if (vq_n < 1 || vq_n > n) return ctx->fail(GPSO_E_STATE, "no variational state of at most %lld rows to extend", (long long)n);
     int rc = refuse_if_async("gpso_vgp_extend_q");
     if (rc) return rc;
@@ -1832,19 +1768,19 @@ struct EngineT : Engine {
       const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
       if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
     }
+    return install_predictive(Post::Vgp);
+  }
+  // what the three variational installs share once linv holds C and alpha_f holds beta: the predict-ready copies, the
+  // factorisations' verdicts, and the posterior's kind
+  int install_predictive(Post kind) {
+    hipStream_t s = st();
+    int rc;
+    double* host;
     launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
     launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    small_tile_rows = 8;
-    chol_valid = true;  // (the split pieces are packed from linv)
-    if ((rc = pack_bf16())) return rc;
-    double* host;
-    if ((rc = vgp_finish(&host))) {
-      chol_valid = false;
-      return rc;
-    }
-    have_post = linv_p_valid = vgp_post = true;
-    sgpr_post = svgp_post = false;
-    return GPSO_OK;
+    if (!(rc = pack_bf16())) rc = vgp_finish(&host, kind);
+    res.variational_ready(kind, rc == GPSO_OK);
+    return rc;
   }
 
 
@@ -1857,10 +1793,6 @@ struct EngineT : Engine {
   DevBuf sgZpart, sgZg;  // the moving-Z evaluations' slice partials and dF/dZ [M x D] (inducing.hip)
   std::vector<double> sg_xh;  // host mirror of the training inputs (the rows greedy selection gathers Z from)
   int64_t sg_n = 0, sg_npad = 0;
-  bool sg_have = false, sg_have_z = false, sg_keep = false;
-  bool sg_factors = false;  // Kuf, Lu, LB, cv of the last gpso_sgpr_bound_u are still in their buffers (gpso_sgpr_get_factor)
-  bool sgpr_post = false;  // the resident posterior is an SGPR predictive over the rows Z
-  bool svgp_post = false;  // ... an SVGP predictive over the rows Z (sgpr_post is set with it)
   enum { kSgE = 0, kSgW = 1, kSgT = 2, kSgVecsN = 3 };
   enum { kSgAe = 0, kSgCv = 1, kSgMu = 2, kSgAvec = 3, kSgRows = 4, kSgZero = 5, kSgVecsM = 6 };
   static constexpr int kSgGradAt = 16, kSgSmall = kSgGradAt + kGradMaxLs + 1;
@@ -1873,8 +1805,8 @@ struct EngineT : Engine {
   }
   // the resident rows are the caller's data: keep them as the SGPR's training set
   int sgpr_stash() {
-    if (sg_have) return GPSO_OK;
-    if (!have_data) return ctx->fail(GPSO_E_STATE, "SGPR call before gpso_set_data");
+    if (res.sg_have) return GPSO_OK;
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "SGPR call before gpso_set_data");
     int rc;
     sg_n = n;
     sg_npad = npad;  // (a multiple of 128: the tile GEMM's k and n extents)
@@ -1884,8 +1816,7 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(sgY.p, y64.p, (size_t)sg_n * 8, hipMemcpyDeviceToDevice, st()));
     HIPCHECK(hipStreamSynchronize(st()));
     sg_xh = x_host;
-    sg_have = true;
-    sg_have_z = false;
+    res.stashed();
     return GPSO_OK;
   }
 
@@ -1894,20 +1825,17 @@ struct EngineT : Engine {
     if (rc) return rc;
     if (!Z) return ctx->fail(GPSO_E_ARG, "Z must not be NULL");
     if (m < 1 || m > 65536) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, 65536]", (long long)m);
-    if (!sg_have && !have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_set_inducing before gpso_set_data");
+    if (!res.sg_have && !res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_set_inducing before gpso_set_data");
     if ((rc = refuse_if_async("gpso_sgpr_set_inducing"))) return rc;
     for (int64_t e = 0; e < m * (int64_t)d; ++e)
       if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
     if ((rc = sgpr_stash())) return rc;
     std::vector<double> zeros((size_t)m, 0.0), zc(Z, Z + (size_t)m * d);  // (Z may alias the mirror set_data overwrites)
-    sg_keep = true;
-    rc = set_data(zc.data(), zeros.data(), m, d);
-    sg_keep = false;
+    rc = put_rows(zc.data(), zeros.data(), m, d, true);
     if (rc) {  // (a HIP / allocation failure: the arguments were checked above.  The resident rows are unknown now)
-      sg_have = sg_have_z = have_data = false;
+      res.rows_unknown();
       return rc;
     }
-    sg_have_z = true;
     svq_m = -1;  // (the SVGP's q restarts at the prior on the new Z)
     return GPSO_OK;
   }
@@ -1915,9 +1843,9 @@ struct EngineT : Engine {
   int sgpr_select_inducing(int kernel, const double* ls, int n_ls_, double variance, int64_t m, int64_t* idx_out) override {
     int rc = sgpr_need_f64();
     if (rc) return rc;
-    if (!sg_have && !have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_select_inducing before gpso_set_data");
+    if (!res.sg_have && !res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_select_inducing before gpso_set_data");
     if ((rc = refuse_if_async("gpso_sgpr_select_inducing"))) return rc;
-    const int64_t N = sg_have ? sg_n : n;
+    const int64_t N = res.sg_have ? sg_n : n;
     if (m < 1 || m > N) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, N=%lld]", (long long)m, (long long)N);
     if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
     if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
@@ -1925,8 +1853,7 @@ struct EngineT : Engine {
       if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
     if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
     // (from here on the call replaces whatever posterior was resident: the hyper block is the selection's)
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
-    sg_factors = false;
+    res.selection_begun();
     if ((rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, 0.0))) return rc;
     if ((rc = sgpr_stash())) return rc;
     if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
@@ -1957,7 +1884,7 @@ struct EngineT : Engine {
   }
 
   int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) override {
-    if (!sg_have || !sg_have_z) return ctx->fail(GPSO_E_STATE, "no inducing points set (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing)");
+    if (!res.sg_have || !res.sg_have_z) return ctx->fail(GPSO_E_STATE, "no inducing points set (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing)");
     if (m_out) *m_out = n;
     if (n_data_out) *n_data_out = sg_n;
     if (Z) std::memcpy(Z, x_host.data(), (size_t)n * d * 8);
@@ -1968,7 +1895,7 @@ struct EngineT : Engine {
   int sgpr_get_factor(int which, double* out) override {
     if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
     if (which < GPSO_SGPR_KUF || which > GPSO_SGPR_CV) return ctx->fail(GPSO_E_ARG, "unknown SGPR factor id %d", which);
-    if (!sg_have || !sg_have_z || !sg_factors)
+    if (!res.sg_have || !res.sg_have_z || !res.sg_factors)
       return ctx->fail(GPSO_E_STATE, "gpso_sgpr_get_factor: no gpso_sgpr_bound_u result resident (any later call but a getter drops it)");
     int rc = refuse_if_async("gpso_sgpr_get_factor");
     if (rc) return rc;
@@ -1985,7 +1912,7 @@ struct EngineT : Engine {
   int sgpr_factor(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, const char* who) {
     int rc = sgpr_need_f64();
     if (rc) return rc;
-    if (!sg_have || !sg_have_z)
+    if (!res.sg_have || !res.sg_have_z)
       return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
     if (!(s2 > 0.0)) return ctx->fail(GPSO_E_ARG, "noise variance %g must be positive", s2);
     // (the arguments set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
@@ -1994,8 +1921,7 @@ struct EngineT : Engine {
     for (int k = 0; k < n_ls_; ++k)
       if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
     if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
-    if ((rc = vgp_begin())) return rc;
-    sgpr_post = sg_factors = false;
+    if ((rc = vgp_begin(true))) return rc;
     const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
     int nsplit = 1;
     while (nsplit < 16 && sg_npad % (256 * nsplit) == 0 && sg_npad / (2 * nsplit) >= 512) nsplit *= 2;
@@ -2072,7 +1998,7 @@ struct EngineT : Engine {
     launch_sgpr_sums(s, LB, AAT, sgm_at(kSgCv), sgn_at(kSgE), grad ? sgn_at(kSgW) : nullptr, grad ? sgm_at(kSgRows) : nullptr, n,
                      npad, sg_n, as<double>(sgsmall));
     double* host;
-    if ((rc = vgp_finish(&host, true))) return rc;
+    if ((rc = vgp_finish(&host, Post::Sgpr))) return rc;
     double guu[kGradMaxLs + 1];
     for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
     double* h = ctx->pinned_scratch(kSgSmall);
@@ -2084,7 +2010,7 @@ struct EngineT : Engine {
     const double F = -0.5 * N * std::log(2.0 * M_PI) - h[0] - 0.5 * N * std::log(s2) - 0.5 * b * h[1] + 0.5 * h[2] -
                      0.5 * N * variance * b + 0.5 * h[3];
     *loss = -F;
-    sg_factors = true;
+    res.bound_ready();
     if (grad) {
       // d(-F)/dtheta: the Kuu contraction already is of -F; the cross one is of F; Kdiag: dF/dvariance = -N b / 2
       for (int k = 0; k <= n_ls; ++k) grad[k] = guu[k] - h[kSgGradAt + k];
@@ -2108,25 +2034,14 @@ struct EngineT : Engine {
     launch_vgp_gemv(s, LBi, true, sgm_at(kSgCv), 0.0, 1.0, 0.0, nullptr, sgm_at(kSgMu), n, npad);        // mu = LB^-T cv
     launch_vgp_gemv(s, Li, true, sgm_at(kSgMu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);   // beta = Lu^-T mu
     launch_dgemm(s, LBi, true, LBi, false, as<double>(K), npad, 1.0, 0.0);                               // B^-1
-    sg_factors = false;  // (vC is about to hold G)
     double shift = 0.0;
     if ((rc = vgp_shifted_root(&shift, true))) return rc;                                                // G in vC
     launch_vgp_reverse(s, as<double>(vC), as<double>(vB), n, npad, 1, nullptr);                          // R
     launch_dgemm(s, as<double>(vB), false, Li, false, as<double>(vA), npad, std::sqrt(1.0 + shift), 0.0);
     HIPCHECK(hipMemcpyAsync(Li, vA.p, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
     if ((rc = set_theta(kernel, ls, n_ls_, variance, s2 + shift * variance, mean_c))) return rc;
-    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
-    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    small_tile_rows = 8;
-    chol_valid = true;  // (the split pieces are packed from linv)
-    if ((rc = pack_bf16())) return rc;
-    double* host;
-    if ((rc = vgp_finish(&host, true))) {
-      chol_valid = false;
-      return rc;
-    }
+    if ((rc = install_predictive(Post::Sgpr))) return rc;
     if (delta_out) *delta_out = shift;
-    have_post = linv_p_valid = vgp_post = sgpr_post = true;
     return GPSO_OK;
   }
 
@@ -2150,7 +2065,7 @@ struct EngineT : Engine {
   int svgp_need_z(const char* who) {
     int rc = sgpr_need_f64();
     if (rc) return rc;
-    if (!sg_have || !sg_have_z)
+    if (!res.sg_have || !res.sg_have_z)
       return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
     return GPSO_OK;
   }
@@ -2180,8 +2095,7 @@ struct EngineT : Engine {
     for (int k = 0; k < n_ls_; ++k)
       if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
     if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
-    if ((rc = vgp_begin())) return rc;
-    sg_factors = false;
+    if ((rc = vgp_begin(true))) return rc;
     if ((rc = svgp_q())) return rc;
     if (rect) {
       const size_t rect_b = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
@@ -2253,7 +2167,7 @@ struct EngineT : Engine {
     double *mu_out = sgm_at(kSgMu), *S_out = as<double>(K);
     if ((rc = vgp_natural_update(as<double>(svq_mu), as<double>(svq_S), gamma, mu_out, S_out))) return rc;
     double* host;
-    if ((rc = vgp_finish(&host, 2))) return rc;
+    if ((rc = vgp_finish(&host, Post::Svgp))) return rc;
     HIPCHECK(hipMemcpyAsync(svq_mu.p, mu_out, (size_t)npad * 8, hipMemcpyDeviceToDevice, s));
     HIPCHECK(hipMemcpyAsync(svq_S.p, S_out, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
     HIPCHECK(ctx->wait(s));
@@ -2363,7 +2277,7 @@ struct EngineT : Engine {
         return rc;
     }
     double* host;
-    if ((rc = vgp_finish(&host, 2))) return rc;
+    if ((rc = vgp_finish(&host, Post::Svgp))) return rc;
     double guu[kGradMaxLs + 1];
     for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
     double* h = ctx->pinned_scratch(kSgSmall);
@@ -2398,18 +2312,8 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
     const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? p * p * vlik_df / (vlik_df - 2.0) : p;
     if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
-    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
-    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    small_tile_rows = 8;
-    chol_valid = true;  // (the split pieces are packed from linv)
-    if ((rc = pack_bf16())) return rc;
-    double* host;
-    if ((rc = vgp_finish(&host, 2))) {
-      chol_valid = false;
-      return rc;
-    }
+    if ((rc = install_predictive(Post::Svgp))) return rc;
     if (delta_out) *delta_out = shift;
-    have_post = linv_p_valid = vgp_post = sgpr_post = svgp_post = true;
     return GPSO_OK;
   }
 
@@ -2425,7 +2329,7 @@ struct EngineT : Engine {
   int inducing_args(const char* who, const double* Z) {
     int rc = sgpr_need_f64();
     if (rc) return rc;
-    if (!sg_have || !sg_have_z)
+    if (!res.sg_have || !res.sg_have_z)
       return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
     if ((rc = refuse_if_async(who))) return rc;
     if (Z)
@@ -2454,10 +2358,7 @@ struct EngineT : Engine {
     }
     if (Z != x_host.data()) std::memcpy(x_host.data(), Z, doubles * 8);
     // (whatever was built on the old rows is gone; the data, q and the likelihood stay)
-    have_post = have_kinv = chol_valid = linv_p_valid = vgp_post = sgpr_post = svgp_post = false;
-    sg_factors = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.inducing_moved();
     return GPSO_OK;
   }
 
@@ -2496,12 +2397,12 @@ struct EngineT : Engine {
                      bool prepared = false /* leaves_s / lnorm already hold the scaled rows (one chunk): no prep launch */) {
     // row blocks of L^-1 = partial sums per leaf: the split-bf16 kernel always works on 256-row blocks,
     // the native kernels on the shape leaf_tiles_bm picks
-    const bool use_bf16 = bf16_usable() && linv_b_valid && bf16_fits(sizeof(TG) == 8);
+    const bool use_bf16 = bf16_usable() && res.linv_b == Copy::Valid && bf16_fits(sizeof(TG) == 8);
     if (!use_bf16) {
       int rcp = ensure_linv_p();
       if (rcp) return rcp;
     }
-    if (!use_bf16 && !linv_p_valid)
+    if (!use_bf16 && res.linv_p != Copy::Valid)
       return ctx->fail(GPSO_E_STATE, "this posterior was received with the split pieces of L^-1 only (the sender predicts with "
                                      "split math): the f32 MFMA kernel has nothing to read -- keep the sender's predict math, or "
                                      "hand the posterior over with gpso_posterior_buffers (all buffers)");
@@ -2651,8 +2552,8 @@ struct EngineT : Engine {
   // a few of the gate is better served by it
   static constexpr double kAutoMargin = 8.0;
   int run_selftest() {
-    if (st_done) return GPSO_OK;
-    if (!st_have || !have_data) return ctx->fail(GPSO_E_STATE, "self-test needs a posterior fitted on this context (gpso_fit_eval)");
+    if (res.st_done) return GPSO_OK;
+    if (!res.st_have || !res.have_data) return ctx->fail(GPSO_E_STATE, "self-test needs a posterior fitted on this context (gpso_fit_eval)");
     int rc;
     if ((rc = ensure(st_mean, (size_t)n * 8))) return rc;
     if ((rc = ensure(st_var, (size_t)n * 8))) return rc;
@@ -2666,52 +2567,50 @@ struct EngineT : Engine {
     HIPCHECK(ctx->wait(st()));
     if ((rc = launch_status())) return rc;
     for (int i = 0; i < 6; ++i) st_vals[i] = host[i];
-    st_done = true;
+    res.selftest_ran();
     return GPSO_OK;
   }
   // GPSO_GEN_AUTO: let the self-test choose the generation arithmetic of this posterior.  Without a
   // self-test (switched off, or a posterior installed from outside: no targets) the choice is double.
   int decide_generation() {
     if (int rcp = ensure_split_pieces()) return rcp;
-    if (!kFloatPredict || gen_decided) return GPSO_OK;
+    if (!kFloatPredict || res.gen_decided) return GPSO_OK;
     if (gen_mode != GPSO_GEN_AUTO) {
-      gen_decided = true;
+      res.generation_ruled();
       return GPSO_OK;
     }
     // Matern-1/2 is exp(-sqrt(r^2)): near r = 0 the square root turns the 1e-6-class error of a float r^2
     // into 1e-3 of k -- for leaves CLOSE to a training input, while AT the training inputs (where the
     // self-test looks) the float form cancels exactly.  The test cannot see it, so this kernel generates
     // in double.
-    const bool can_test = check && st_have && have_data && kp.kernel != GPSO_MATERN12;
-    if (!can_test) {
-      gen_eff32 = false;
-      st_done = false;
-      gen_decided = true;
+    if (!can_selftest() || kp.kernel == GPSO_MATERN12) {
+      res.generation_trial(false, res.c16_fallback);
+      res.generation_ruled();
       return GPSO_OK;
     }
     int rc = run_selftest();
     if (rc) return rc;
-    if (!st_pass(kAutoMargin) && gen_eff32) {
+    if (!st_pass(kAutoMargin) && res.gen_eff32) {
       // not comfortably inside with float generation: measure double generation as well
       double r32[6];
       std::copy(st_vals, st_vals + 6, r32);
       const bool pass32 = st_pass();
       const bool was_c16 = c16_in_use(false);
-      if (pass32 && bf16_usable() && linv_b_valid && !bf16_fits(true)) {
+      if (pass32 && bf16_usable() && res.linv_b == Copy::Valid && !bf16_fits(true)) {
         // the split-bf16 kernel the caller opted into cannot hold double fragments at this D: double
         // generation would also mean the (slower) native kernel.  Inside the tolerances: stay.
-        gen_decided = true;
+        res.generation_ruled();
         return GPSO_OK;
       }
-      gen_eff32 = false;
-      st_done = false;
+      res.generation_trial(false, res.c16_fallback);
       if ((rc = run_selftest())) return rc;
       // the float form of r^2 is what fails at small lengthscales / noise -- then double is clearly
       // better and stays.  Where the readings are the same within 1.5x the error is not the generation's
       // (a float factor's, the apply's): float generation is as good and is kept.
       const bool finite64 = std::isfinite(st_vals[0]) && std::isfinite(st_vals[1]);
+      bool f32 = false, c32 = res.c16_fallback;  // (the ruling; st_vals end as the readings of what it keeps)
       if (pass32 && finite64 && r32[0] <= 1.5 * st_vals[0] && r32[1] <= 1.5 * st_vals[1]) {
-        gen_eff32 = true;
+        f32 = true;
         std::copy(r32, r32 + 6, st_vals);
       } else if (was_c16 && finite64) {
         // float generation with the contraction on the fp16 pipe is not as good as double here: before paying for double
@@ -2720,19 +2619,16 @@ struct EngineT : Engine {
         // and the products), which is where this test looks
         double r64[6];
         std::copy(st_vals, st_vals + 6, r64);
-        c16_fallback = true;
-        gen_eff32 = true;
-        st_done = false;
+        res.generation_trial(true, true);
         if ((rc = run_selftest())) return rc;
         // (kept on the terms it is kept on when it runs first: comfortably inside the tolerances, or as good as double)
-        if (!(st_pass(kAutoMargin) || (st_pass() && st_vals[0] <= 1.5 * r64[0] && st_vals[1] <= 1.5 * r64[1]))) {
-          c16_fallback = false;
-          gen_eff32 = false;
-          std::copy(r64, r64 + 6, st_vals);
-        }
+        f32 = c32 = st_pass(kAutoMargin) || (st_pass() && st_vals[0] <= 1.5 * r64[0] && st_vals[1] <= 1.5 * r64[1]);
+        if (!f32) std::copy(r64, r64 + 6, st_vals);
       }
+      res.generation_ruled(f32, c32);
+      return GPSO_OK;
     }
-    gen_decided = true;
+    res.generation_ruled();
     return GPSO_OK;
   }
   // the self-test, and under GPSO_MATH_AUTO a second look with the f32 MFMA kernel where the split-bf16 apply
@@ -2740,27 +2636,25 @@ struct EngineT : Engine {
   int selftest_with_fallback() {
     int rc = run_selftest();
     if (rc) return rc;
-    if (!st_pass() && math_auto && bf16_usable() && linv_b_valid) {
-      if (math == GPSO_MATH_F16X3 && chol_valid) {  // next rung: six bf16 products (L^-1 is resident: repack)
-        math = GPSO_MATH_BF16X6;
+    if (!st_pass() && math_auto && bf16_usable() && res.linv_b == Copy::Valid) {
+      if (res.math == GPSO_MATH_F16X3 && res.chol_valid) {  // next rung: six bf16 products (L^-1 is resident: repack)
+        res.ladder_down(GPSO_MATH_BF16X6);
         if ((rc = pack_bf16())) return rc;
-        st_done = false;
         if ((rc = run_selftest()) || st_pass()) return rc;
       }
-      math_native_fallback = true;
-      st_done = false;
+      res.ladder_down(GPSO_MATH_NATIVE);
       rc = run_selftest();
     }
     return rc;
   }
   int math_in_use() const {
-    return (bf16_usable() && linv_b_valid && bf16_fits(gen_double())) ? math : GPSO_MATH_NATIVE;
+    return (bf16_usable() && res.linv_b == Copy::Valid && bf16_fits(gen_double())) ? res.math : GPSO_MATH_NATIVE;
   }
   // called at the top of every predict-type entry point
   int precision_gate() {
     int rc = decide_generation();
     if (rc) return rc;
-    if (!check || !st_have || !have_data) return GPSO_OK;  // posteriors installed from outside carry no targets
+    if (!can_selftest()) return GPSO_OK;
     if ((rc = selftest_with_fallback())) return rc;
     if (!st_pass())
       return ctx->fail(GPSO_E_PRECISION,
@@ -2773,7 +2667,7 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
   int precision_info(double* out) override {
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident");
     int rc = decide_generation();
     if (rc) return rc;
     if ((rc = selftest_with_fallback())) return rc;
@@ -2804,7 +2698,7 @@ struct EngineT : Engine {
   }
 
   int check_predict_args(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     if (m < 0) return ctx->fail(GPSO_E_ARG, "negative leaf count");
     if (m > 0 && !xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
     if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
@@ -2922,7 +2816,7 @@ struct EngineT : Engine {
     // cost; the single launch only pays at N_pad = 256
     if (npad == 128 && !one_launch_everywhere) return 2;
     if (math_in_use() != GPSO_MATH_NATIVE) return 2;
-    if (ensure_linv_p() != GPSO_OK || !linv_p_valid) return 2;
+    if (ensure_linv_p() != GPSO_OK || res.linv_p != Copy::Valid) return 2;
     if (leaf_tiles_nbi<TP>(npad, dp / 4) != 1) return 2;
     if constexpr (kFloatPredict) {
       if (!gen_double()) {
@@ -3181,7 +3075,7 @@ struct EngineT : Engine {
     return rc;
   }
   int sharded_local_grow(int rank, int world, const double* bounds, int nseg, int depth, double varsigma) {
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_broadcast_posterior first");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_broadcast_posterior first");
     int rc = precision_gate();
     if (rc) return rc;
     int64_t lo, hi;
@@ -3306,7 +3200,7 @@ struct EngineT : Engine {
   int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double varsigma,
                      const double* bounds, int depth) override {
     const bool grown = bounds != nullptr;
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     if (nseg < 1 || (size_t)nseg * 4 + 3 > gpso_ctx::kSlotDoubles) return ctx->fail(GPSO_E_ARG, "nseg must be in [1, 1024] for an asynchronous call");
     int rc = grown ? precision_gate() : check_predict_args(xs, xs_dtype, xs_mem, m);
     if (rc) return rc;
@@ -3468,7 +3362,7 @@ struct EngineT : Engine {
   int best_ucb_grow(const double* bounds, int nseg, int depth, double varsigma, int64_t* idx,
                     double* mean, double* var, double* ucb) override {
     ctx->tick_timing();
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     int rc = precision_gate();
     if (rc) return rc;
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
@@ -3612,11 +3506,11 @@ struct EngineT : Engine {
     std::string why;
     if (is_root) {
       // still take part in the collectives below when something is wrong: every rank must leave together
-      if (!have_post) {
+      if (!res.has_post()) {
         mine = ctx->fail(GPSO_E_STATE, "gpso_broadcast_posterior: the root has no posterior resident");
       } else if ((rc = decide_generation()) != GPSO_OK) {
         mine = rc;
-      } else if (check && st_have && have_data) {
+      } else if (can_selftest()) {
         if ((rc = selftest_with_fallback()) != GPSO_OK) mine = rc;  // (settles GPSO_MATH_AUTO)
         else if (!st_pass()) mine = precision_gate();                // GPSO_E_PRECISION with the measured errors
       }
@@ -3624,7 +3518,7 @@ struct EngineT : Engine {
     }
     // the predict math the posterior travels with (under GPSO_MATH_AUTO the root's self-test has chosen)
     // (bit 12: GPSO_MATH_AUTO -- its split buffer has room for three planes whatever the rung, so the option itself must agree)
-    const int64_t my_opts = (int64_t)(math_native_fallback ? GPSO_MATH_NATIVE : math) | ((int64_t)math_auto << 12) | ((int64_t)ctx->dtype << 16);
+    const int64_t my_opts = (int64_t)(res.math_native_fallback ? GPSO_MATH_NATIVE : res.math) | ((int64_t)math_auto << 12) | ((int64_t)ctx->dtype << 16);
     // the ONE range of the root's posterior arena that travels (offset and length are the same on every rank: the
     // arena's layout depends on the shape and the types only)
     void* span_ptr = nullptr;
@@ -3648,9 +3542,8 @@ struct EngineT : Engine {
       if (rdtype == (int64_t)ctx->dtype && math_auto && rauto &&
           (rmath == GPSO_MATH_F16X3 || rmath == GPSO_MATH_BF16X6 || rmath == GPSO_MATH_NATIVE)) {
         // the root's choice (its self-test ruled): the rung of the ladder, or the f32 MFMA kernel
-        math_native_fallback = rmath == GPSO_MATH_NATIVE && kFloatPredict;
-        if (rmath != GPSO_MATH_NATIVE) math = (int)rmath;
-      } else if (rdtype != (int64_t)ctx->dtype || rmath != math || rauto != (int64_t)math_auto) {
+        res.ladder_follows((int)rmath, kFloatPredict);
+      } else if (rdtype != (int64_t)ctx->dtype || rmath != res.math || rauto != (int64_t)math_auto) {
         mine = ctx->fail(GPSO_E_ARG, "gpso_broadcast_posterior: dtype / predict math options differ from the root's");
         why = ctx->err;
       }
@@ -3691,13 +3584,11 @@ struct EngineT : Engine {
 
   // ---- the peers of a group brought up to date after gpso_append: only what the appends wrote travels -----------------------
   int posterior_mark_synced() override {
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident");
     float scale = 0.0f;
     int rc = current_split_scale(&scale);
     if (rc) return rc;
-    sync_n = n;
-    sync_math = math_in_use();
-    sync_scale = scale;
+    res.peers_hold(n, math_in_use(), scale);
     return GPSO_OK;
   }
   // the ranges (offsets into the posterior arena: the same on every context of this shape and type) that a peer holding the
@@ -3716,9 +3607,9 @@ struct EngineT : Engine {
       nbytes[0] = span_bytes;
       return 1;
     }
-    if (sync_n == n) return 0;
+    if (res.sync_n == n) return 0;
     std::vector<std::pair<int64_t, int64_t>> rr;
-    rows_ranges(sync_n, rr);
+    rows_ranges(res.sync_n, rr);
     for (size_t i = 0; i < rr.size(); ++i) {
       offsets[i] = rr[i].first;
       nbytes[i] = rr[i].second;
@@ -3746,9 +3637,9 @@ struct EngineT : Engine {
       void* span_ptr = nullptr;
       int64_t span_off = 0, span_bytes = 0;
       float scale = 0.0f;
-      if (have_post && posterior_span(&span_ptr, &span_off, &span_bytes) == GPSO_OK && current_split_scale(&scale) == GPSO_OK &&
-          rows_apply(scale) && !(check && st_have && have_data && !st_pass())) {
-        n_base = sync_n;
+      if (res.has_post() && posterior_span(&span_ptr, &span_off, &span_bytes) == GPSO_OK && current_split_scale(&scale) == GPSO_OK &&
+          rows_apply(scale) && !(can_selftest() && !st_pass())) {
+        n_base = res.sync_n;
         n_now = n;
         mth = math_in_use();
         scale_bits = (int64_t)__builtin_bit_cast(unsigned, scale);
@@ -3765,8 +3656,8 @@ struct EngineT : Engine {
     int64_t mine = 1;
     if (n_base < 0) mine = 0;
     else if (!is_root)
-      mine = (have_post && arena.p != nullptr && sync_n == n_base && n == n_base && npad == r_npad && dp == r_dp && math_in_use() == (int)mth &&
-              (int64_t)__builtin_bit_cast(unsigned, sync_scale) == scale_bits && n_now <= npad) ? 1 : 0;
+      mine = (res.has_post() && arena.p != nullptr && res.sync_n == n_base && n == n_base && npad == r_npad && dp == r_dp && math_in_use() == (int)mth &&
+              (int64_t)__builtin_bit_cast(unsigned, res.sync_scale) == scale_bits && n_now <= npad) ? 1 : 0;
     int64_t agreed = 0;
     if ((rc = agree_min(hd + 8, host + 8, mine, &agreed))) return rc;
     if (agreed != 1) {
@@ -3805,16 +3696,16 @@ struct EngineT : Engine {
     int lower = 1;
     switch (which) {
       case GPSO_MAT_CHOL:
-        if (!chol_valid) return ctx->fail(GPSO_E_STATE, "no factor resident");
-        if (vgp_post) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no Cholesky factor of its own (GPSO_MAT_LINV holds C = R L^-1)");
+        if (!res.chol_valid) return ctx->fail(GPSO_E_STATE, "no factor resident");
+        if (res.variational()) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no Cholesky factor of its own (GPSO_MAT_LINV holds C = R L^-1)");
         src = as<TF>(Lf);
         break;
       case GPSO_MAT_LINV:
-        if (!chol_valid) return ctx->fail(GPSO_E_STATE, "no factor resident");
+        if (!res.chol_valid) return ctx->fail(GPSO_E_STATE, "no factor resident");
         src = as<TF>(linv);
         break;
       case GPSO_MAT_KINV:
-        if (!have_kinv) return ctx->fail(GPSO_E_STATE, "Kinv only exists after gpso_fit_eval with grad");
+        if (!res.have_kinv) return ctx->fail(GPSO_E_STATE, "Kinv only exists after gpso_fit_eval with grad");
         src = as<TF>(kinvb);
         lower = 2;
         break;
@@ -3832,13 +3723,13 @@ struct EngineT : Engine {
   int get_vector(int which, double* out) override {
     if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
     if (which == GPSO_VEC_NOISE_DIAG) {  // a property of the data, not of a posterior: the host mirror, or zeros
-      if (!have_data) return ctx->fail(GPSO_E_STATE, "GPSO_VEC_NOISE_DIAG needs training data (gpso_set_data)");
-      if (have_s) std::memcpy(out, s_host.data(), (size_t)n * 8);
+      if (!res.have_data) return ctx->fail(GPSO_E_STATE, "GPSO_VEC_NOISE_DIAG needs training data (gpso_set_data)");
+      if (res.have_s) std::memcpy(out, s_host.data(), (size_t)n * 8);
       else std::memset(out, 0, (size_t)n * 8);
       return GPSO_OK;
     }
-    if (!have_post || !chol_valid) return ctx->fail(GPSO_E_STATE, "no fitted posterior resident");
-    if (which == GPSO_VEC_WHITE && vgp_post) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no whitened targets");
+    if (!res.has_post() || !res.chol_valid) return ctx->fail(GPSO_E_STATE, "no fitted posterior resident");
+    if (which == GPSO_VEC_WHITE && res.variational()) return ctx->fail(GPSO_E_STATE, "a VGP predictive has no whitened targets");
     const TF* src = (which == GPSO_VEC_ALPHA) ? as<TF>(alpha_f) : (which == GPSO_VEC_WHITE) ? as<TF>(white) : nullptr;
     if (!src) return ctx->fail(GPSO_E_ARG, "unknown vector id %d", which);
     int rc = ensure(getter_tmp, (size_t)n * 8);
@@ -3850,24 +3741,20 @@ struct EngineT : Engine {
   }
 
   // hyper | packed L^-1 | scaled inputs (double: plain, MFMA fragments, norms) | alpha [| bf16 pieces].
-  // The generation inputs always travel in double; a receiver derives the float copies itself when the
-  // sender's choice (slot 7 of the hyper block, written here: 1 = float generation, + 2 = GPSO_MATH_AUTO
-  // settled on the f32 MFMA kernel for this posterior) is float generation.
-  // settle the posterior's arithmetic choices (generation, GPSO_MATH_AUTO's rung) and write them into slot 7 of the
-  // hyper block, which travels: 1 = float generation, 2 = GPSO_MATH_AUTO settled on the f32 MFMA kernel, 4 = the split
-  // pieces are built, 8 = the packed L^-1 travels too, 16 = float generation keeps the f32 contraction, 256 x the predict math
+  // The generation inputs always travel in double; a receiver derives the float copies itself when the sender's choice is
+  // float generation.  settle the posterior's arithmetic choices (generation, GPSO_MATH_AUTO's rung) and write them into
+  // slot 7 of the hyper block, which travels (resident.hpp: handoff_word)
   // (span_only: the flag describes the contiguous range of posterior_span -- the packed L^-1 is part of it only when the
   // posterior runs the f32 / f64 MFMA kernel; otherwise every buffer travels)
   int settle_and_flag(bool span_only) {
-    if (!have_post) return GPSO_OK;
+    if (!res.has_post()) return GPSO_OK;
     int rc = decide_generation();
     if (rc) return rc;
-    if (check && st_have && have_data && (rc = selftest_with_fallback())) return rc;  // settles GPSO_MATH_AUTO
+    if (can_selftest() && (rc = selftest_with_fallback())) return rc;  // settles GPSO_MATH_AUTO
     const bool with_linv_p = !span_only || math_in_use() == GPSO_MATH_NATIVE;
     if (with_linv_p && (rc = ensure_linv_p())) return rc;
     double* flag = ctx->pinned_scratch(256) + 120;  // (a slot neither the read-backs nor set_theta use)
-    *flag = (gen_double() ? 0.0 : 1.0) + (math_native_fallback ? 2.0 : 0.0) + ((bf16_usable() && linv_b_valid) ? 4.0 : 0.0) +
-            ((with_linv_p && linv_p_valid) ? 8.0 : 0.0) + (c16_fallback ? 16.0 : 0.0) + 256.0 * math;  // (which split the pieces are: a receiver under GPSO_MATH_AUTO follows)
+    *flag = res.handoff_word(gen_double(), bf16_usable(), with_linv_p);
     HIPCHECK(hipMemcpyAsync(as<double>(hyper) + 7, flag, 8, hipMemcpyHostToDevice, st()));
     HIPCHECK(hipStreamSynchronize(st()));  // callers copy these buffers on streams of their own
     return GPSO_OK;
@@ -3897,10 +3784,10 @@ struct EngineT : Engine {
   // *offset = its distance from the arena's start -- the same on every context of the same shape and type.
   int posterior_span(void** ptr, int64_t* offset, int64_t* nbytes) override {
     if (npad == 0 || arena.p == nullptr) return ctx->fail(GPSO_E_STATE, "no problem shape yet");
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident");
     int rc = settle_and_flag(true);
     if (rc) return rc;
-    if (math_in_use() == GPSO_MATH_NATIVE && !linv_p_valid)
+    if (math_in_use() == GPSO_MATH_NATIVE && res.linv_p != Copy::Valid)
       return ctx->fail(GPSO_E_STATE, "this context received its posterior without the packed L^-1 and cannot pass it on for the f32 kernel");
     size_t off, bytes;
     posterior_range(&off, &bytes);
@@ -3923,7 +3810,7 @@ struct EngineT : Engine {
   // every rank compares instead of broadcasting ("measure both")
   DevBuf hash_out;
   int posterior_hash(uint64_t* out) override {
-    if (!have_post) return ctx->fail(GPSO_E_STATE, "no posterior resident");
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident");
     int rc = settle_and_flag(true);
     if (rc) return rc;
     if ((rc = ensure(hash_out, 8))) return rc;
@@ -3957,9 +3844,7 @@ struct EngineT : Engine {
     if (rc) return rc;
     rc = shape(n_, d_);
     if (rc) return rc;
-    have_data = have_post = have_kinv = chol_valid = linv_p_valid = false;
-    st_done = st_have = false;
-    forget_peers();
+    res.shape_allocated();
     return GPSO_OK;
   }
 
@@ -3982,23 +3867,7 @@ struct EngineT : Engine {
     kp.noise = h[5];
     kp.mean_c = h[6];
     ls_host.assign(h + kHyperHeader, h + kHyperHeader + n_ls);
-    have_post = true;
-    chol_valid = have_kinv = false;
-    small_tile_rows = 8;           // linv_p came from elsewhere
-    st_done = st_have = false;     // the fitting rank ran the self-test; no targets here
-    // generation arithmetic and predict math: the sender's choice (its self-test ruled), unless this context insists
-    const int sender = (int)h[7];
-    math_native_fallback = math_auto && (sender & 2) != 0;
-    const int sender_math = sender >> 8;
-    if (math_auto && kFloatPredict && (sender_math == GPSO_MATH_F16X3 || sender_math == GPSO_MATH_BF16X6)) math = sender_math;
-    // the split pieces the sender actually built travel with it (and are the split this context runs)
-    linv_b_valid = bf16_usable() && (sender & 4) != 0 && sender_math == math;
-    linv_b_pending = false;
-    linv_p_valid = (sender & 8) != 0;
-    gen_eff32 = kFloatPredict && (gen_mode == GPSO_GEN_F32 || (gen_mode == GPSO_GEN_AUTO && (sender & 1) != 0));
-    gen_decided = true;
-    gen32_inputs_ok = false;
-    c16_fallback = (sender & 16) != 0;  // (the sender's float generation kept the f32 contraction: same arithmetic here)
+    res.adopted((int)h[7], kFloatPredict, math_auto, gen_mode, npad);
     return GPSO_OK;
   }
 };

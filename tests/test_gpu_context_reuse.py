@@ -1,13 +1,14 @@
 """
 A context's history never changes a call's result bits.
 
-One ``gpso_ctx`` serves a whole optimiser run and any C-ABI caller's mix of calls; its device buffers only grow and keep
-their old bytes, and about 25 members say what is resident.  The stages of tests/context_stages.py are run here (a) on a
-fresh context, where they are held to the float64 oracle at the tolerances the family's own test file states (imported
-from there, not restated), (b) on a second fresh context (determinism), and (c) after every other stage, after failed
-calls, along seeded walks and along the optimiser's growth path -- where every observable must equal the fresh run's
-bit for bit: fits and predictions are deterministic (test_deterministic_bitwise, test_repeated_calls_give_identical_bits),
-so any difference is an effect of what the context held before.  No tolerance applies to (b) and (c).
+One ``gpso_ctx`` serves a whole optimiser run and any C-ABI caller's mix of calls; its device buffers only grow and
+keep their old bytes, and one host-side record (pygpso_amd/csrc/resident.hpp) says what is resident. The stages of
+tests/context_stages.py are run here (a) on a fresh context, where they are held to the float64 oracle at the
+tolerances the family's own test file states (imported from there, not restated), (b) on a second fresh context
+(determinism), and (c) after every other stage, after failed calls, along seeded walks and along the optimiser's
+growth path -- where every observable must equal the fresh run's bit for bit: fits and predictions are deterministic
+(test_deterministic_bitwise, test_repeated_calls_give_identical_bits), so any difference is an effect of what the
+context held before. No tolerance applies to (b) and (c).
 
 Run on the GPU box with ``pytest -m gpu``.  test_fresh_results_are_the_oracles prints each stage's errors against the
 oracle as a ``CONTEXT_REUSE_PARITY`` line (``-s`` shows them): the material for a profiles/ record.

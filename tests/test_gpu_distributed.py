@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import gpr, tree
+from tests import context_stages as CS
 from tests.helpers import load_goldens, rotated_peaks, synthetic_leaves, synthetic_problem
 
 pytestmark = pytest.mark.gpu
@@ -206,6 +207,59 @@ def test_posterior_handoff_between_two_contexts(dtype):
     m2, v2 = dst.predict(Xs)
     assert np.array_equal(m1, m2) and np.array_equal(v1, v2)
     assert all(np.array_equal(p, q) for p, q in zip(src.best_ucb(Xs, VS), dst.best_ucb(Xs, VS)))
+
+
+def _after_handoff(eng):
+    """Everything a caller can see of a receiver: arrays as they are, a refusal as exception type plus message."""
+    from pygpso_amd import _lib as L
+
+    obs = {}
+    Xs = synthetic_leaves(257, 5)
+    CS._try(obs, "predict", lambda: eng.predict(Xs), ("mean", "var"))
+    CS._try(obs, "best_ucb", lambda: eng.best_ucb(Xs, VS, CS.SEG_RAGGED), CS.WIN)
+    CS._try(obs, "hash", lambda: eng.posterior_hash())
+    for name, which in (("chol", L.MAT_CHOL), ("linv", L.MAT_LINV), ("kinv", L.MAT_KINV)):
+        CS._try(obs, name, lambda: eng.get_matrix(which))
+    for name, which in (("alpha", L.VEC_ALPHA), ("white", L.VEC_WHITE)):
+        CS._try(obs, name, lambda: eng.get_vector(which))
+    CS._try(obs, "append", lambda: eng.append(np.full((1, 5), 0.5), [0.1]), ("nlml", "in_place"))
+    CS._try(obs, "vgp_get_q", lambda: eng.vgp_get_q(), ("mu", "S"))
+    # (last: the stash of an earlier sparse model is gone with the hand-off, so both are refused as on a fresh receiver)
+    CS._try(obs, "sgpr_inducing", lambda: eng.sgpr_get_inducing(), ("Z", "n_data"))
+    CS._try(obs, "sgpr_bound", lambda: eng.sgpr_bound_u(CS.KERNEL, CS.inputs("sgpr").u, 1, True, 0.0), ("loss", "grad_u", "theta"))
+    return obs
+
+
+@pytest.mark.parametrize("dtype", ["float64", "mixed", "float32"])
+def test_a_receivers_history_does_not_show_after_a_handoff(dtype):
+    """Whatever a context held before -- a one-launch fit (fewer than 8 tile rows of the packed L^-1 in use), an
+    installed posterior, a VGP / SGPR (D = 12: the hand-off changes D too) / SVGP predictive, a failed fit --, after
+    gpso_alloc_posterior + gpso_adopt_posterior it answers every call as a fresh receiver does: arrays bit for bit,
+    refusals character for character (the sparse entry points included: they find no stash). N = 300 pads to 512 in
+    float-predict contexts (the split pieces travel) and to 384 in float64 (the packed L^-1 does)."""
+    from pygpso_amd import HipGPEngine
+
+    src = _fitted(dtype)
+    assert src.padded_n == (384 if dtype == "float64" else 512)
+    fresh_eng = HipGPEngine(dtype)
+    _handoff_span(src, fresh_eng)
+    fresh = _after_handoff(fresh_eng)
+    fresh_eng.close()
+    sent = src.predict(synthetic_leaves(257, 5))
+    assert np.array_equal(fresh["predict.mean"], sent[0]) and np.array_equal(fresh["predict.var"], sent[1])
+    histories = [h for h in ("gpr_small", "set_posterior", "vgp_gauss", "sgpr_small_m", "svgp", "failed_fit") if h in CS.stages_for(dtype)]
+    assert len(histories) == (3 if dtype == "float32" else 6)
+    bad = []
+    for h in histories:
+        eng = HipGPEngine(dtype)
+        CS.STAGES[h](eng)
+        _handoff_span(src, eng)
+        for m in CS.compare("hand-off", _after_handoff(eng), fresh):
+            m.note = (m.note + "; " if m.note else "") + f"receiver after {h}"
+            bad.append(m)
+        eng.close()
+    src.close()
+    assert not bad, CS.report(bad)
 
 
 def test_the_packed_posterior_holds_lower_tiles_only():
