@@ -214,6 +214,39 @@ int gpso_fit_eval(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_l
 int gpso_fit_eval_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                     double* nlml, double* grad_u, double* theta_out);
 
+/* ---- leave-one-out (no counterpart in the reference: GPflow's GPR has no LOO predictive and no LOO-CV objective) -------
+ * With alpha = K_y^-1 (y - c) and kappa_i = (K_y^-1)_ii, K_y = k(X, X) + diag(noise + s_i) (s: gpso_set_noise_diag, else 0):
+ *   mean_i = y_i - alpha_i / kappa_i,  var_i = 1 / kappa_i  (the predictive variance of the OBSERVATION y_i: its own
+ *   noise + s_i included, as gpso_predict includes the noise),  lpd_i = (log kappa_i - alpha_i^2 / kappa_i - log 2pi) / 2:
+ * what N refits without point i would predict for it at the resident hyper-parameters, in O(N) from what a fit leaves
+ * (Rasmussen & Williams, section 5.4.2). */
+
+/* The LOO predictive of the resident fitted posterior: mean[N], var[N], lpd[N] (host float64, each nullable), *loss
+ * (nullable) = -sum lpd.  Every context type (GPSO_F32 reads its float factor's alpha and diagonal); after gpso_append /
+ * gpso_append_noise it covers the appended points.  Reads only: the posterior stays resident, bit for bit, and the same
+ * call gives the same bits.  GPSO_E_STATE when no posterior fitted WITH TARGETS on this context is resident (the condition
+ * of gpso_precision_info: a posterior from gpso_set_posterior, gpso_vgp_posterior, gpso_sgpr_posterior, gpso_svgp_posterior
+ * or a hand-off has none), or while an asynchronous best-UCB ticket is open; GPSO_E_ARG for N < 2. */
+int gpso_loo(gpso_ctx* ctx, double* mean, double* var, double* lpd, double* loss);
+
+/* ONE evaluation of the LOO-CV loss F = -sum lpd_i and its gradient: arguments, the order of grad (n_ls + 3 values,
+ * nullable) and the statuses as gpso_fit_eval; *nlml (nullable) receives the NLML at the same theta, which the
+ * factorisation gives for free.  dF/dtheta = sum_ab W_ab dK_y,ab/dtheta with W = K_y^-1 diag(c) K_y^-1 - (h alpha^T +
+ * alpha h^T) / 2, c_i = (1 + alpha_i^2 / kappa_i) / (2 kappa_i), h = K_y^-1 (alpha / kappa); dF/dnoise = tr W, dF/dc =
+ * -sum h: one N^3 product more than the NLML's gradient, then the same tile contraction.
+ * GPSO_F64 and GPSO_MIXED contexts (the fit is in double); GPSO_F32: GPSO_E_ARG.  GPSO_E_ARG for N < 2; GPSO_E_NOTPD as
+ * gpso_fit_eval.  Runs the factorisation of gpso_fit_eval with a gradient and leaves THE SAME L, L^-1, alpha, packed
+ * copies and hyper block, bit for bit: the posterior is predict-ready afterwards.  GPSO_MAT_KINV is still K_y^-1 (the
+ * weights are built in scratch the fit has finished with).  N <= 128 with GPSO_OPT_FIT_FUSED_SMALL on: two launches (the
+ * one-launch fit, one workgroup for everything else) and no copy operation; otherwise the general sequence -- results
+ * agree to rounding.  gpso_last_ms(ctx, 2) covers the whole call.  The same call gives the same bits. */
+int gpso_fit_eval_loo(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_ls, double variance, double noise,
+                      double mean_c, double* loss, double* grad, double* nlml);
+/* The same evaluation in the optimiser's variables: u, train_mean, mean_c_fixed, grad_u, theta_out, the host-side
+ * transforms and the chain rule exactly as gpso_fit_eval_u. */
+int gpso_fit_eval_loo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* loss, double* grad_u, double* theta_out, double* nlml);
+
 /* Multi-start hyper-parameter search: the pending evaluations of several L-BFGS-B searches in one launch, one workgroup
  * per theta (fit.hip: small_fit_batch_kernel -- the one-launch fit's arithmetic, bit for bit).
  * gpso_fit_batch_max: how many entries one gpso_fit_eval_u_batch call may hold for the resident data: 256 when the

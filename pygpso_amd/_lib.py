@@ -79,6 +79,11 @@ SIGNATURES = {
                                 C.c_double, _c_double_p, _c_double_p]),
     "gpso_fit_eval_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
                                   _c_double_p, _c_double_p]),
+    "gpso_loo": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_fit_eval_loo": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_double, C.c_double,
+                                    C.c_double, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_fit_eval_loo_u": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_double, _c_double_p,
+                                      _c_double_p, _c_double_p, _c_double_p]),
     "gpso_fit_batch_max": (C.c_int, [C.c_void_p]),
     "gpso_fit_eval_u_batch": (C.c_int, [C.c_void_p, C.c_int, _c_double_p, C.c_int, C.c_int, C.c_int, C.c_double,
                                         _c_double_p, _c_double_p, C.POINTER(C.c_int), _c_int64_p]),

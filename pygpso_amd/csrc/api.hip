@@ -79,6 +79,10 @@ struct Engine {
   virtual int set_posterior(const double* X, const double* L, const double* alpha, int64_t n, int d,
                             int kernel, const double* ls, int n_ls, double variance, double noise,
                             double mean_c) = 0;
+  // leave-one-out predictive of the resident fitted posterior / one evaluation of the LOO-CV objective (loo.hip)
+  virtual int loo(double* mean, double* var, double* lpd, double* loss) = 0;
+  virtual int fit_eval_loo(int kernel, const double* ls, int n_ls, double variance, double noise, double mean_c,
+                           double* loss, double* grad, double* nlml) = 0;
   virtual int fit_batch_max() = 0;
   virtual int fit_eval_batch(int kernel, const double* th, int nv, int n_ls, double* loss, double* grad, int* info) = 0;
   virtual int fit_eval_batch_check(int kernel, int b, int n_ls) = 0;
@@ -449,6 +453,7 @@ struct EngineT : Engine {
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
+  DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -461,7 +466,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag, &loov, &loo_scal})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -957,11 +962,41 @@ struct EngineT : Engine {
 
   int fit_eval(int kernel, const double* ls, int n_ls_, double variance, double noise,
                double mean_c, double* nlml, double* grad) override {
+    return fit_eval_impl(kernel, ls, n_ls_, variance, noise, mean_c, nlml, grad, nullptr, nullptr);
+  }
+  // One evaluation of the LOO-CV objective: the fit with a gradient as gpso_fit_eval runs it -- so L, L^-1, alpha, the
+  // packed copies and the hyper block come out the same bits -- and behind it, on the same stream, the LOO launches (loo.hip)
+  int fit_eval_loo(int kernel, const double* ls, int n_ls_, double variance, double noise, double mean_c, double* loss,
+                   double* grad, double* nlml) override {
+    if (sizeof(TF) == 4)
+      return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context (the LOO objective "
+                                   "of a float factor is not supported)");
+    double g_nlml[kGradMaxLs + 3], g_loo[kGradMaxLs + 3], f_loo = 0.0;
+    const int rc = fit_eval_impl(kernel, ls, n_ls_, variance, noise, mean_c, nlml, g_nlml, &f_loo, g_loo);
+    if (rc != GPSO_OK) return rc;
+    if (loss) *loss = f_loo;
+    if (grad)
+      for (int h = 0; h < n_ls + 3; ++h) grad[h] = g_loo[h];
+    return GPSO_OK;
+  }
+
+  static constexpr size_t kLooHostAt = 256;  // the LOO scalars in the pinned scratch: behind set_theta's staging block
+  int fit_eval_impl(int kernel, const double* ls, int n_ls_, double variance, double noise, double mean_c, double* nlml,
+                    double* grad, double* loo_loss, double* loo_grad) {
     ctx->tick_timing();
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval before gpso_set_data");
+    const bool want_loo = loo_loss != nullptr;
+    const char* who = want_loo ? "gpso_fit_eval_loo" : "gpso_fit_eval";
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "%s before gpso_set_data", who);
     if (!ls) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
-    int rc = refuse_if_async("gpso_fit_eval");
+    int rc = refuse_if_async(who);
     if (rc) return rc;
+    if (want_loo) {
+      if (n < 2) return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs at least two training points (N=%lld)", (long long)n);
+      // (the scratch at its final size before anything below takes a pointer into it)
+      if (!ctx->pinned_scratch(kLooHostAt + 8 + kGradMaxLs + 3)) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+      if ((rc = ensure(loov, (size_t)kLooVecs * npad * 8))) return rc;
+      if ((rc = ensure(loo_scal, (size_t)(8 + kGradMaxLs + 3) * 8))) return rc;
+    }
     rc = ensure_fit_buffers();
     if (rc) return rc;
     const bool small = fused_small && small_fit_eligible(n, dp);
@@ -1085,13 +1120,39 @@ struct EngineT : Engine {
     }
     const bool split_deferred = grad && !small;  // (see ensure_split_pieces)
     if (!split_deferred && (rc = pack_bf16())) return rc;
-    if ((rc = launch_status())) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
     constexpr size_t kHostDoubles = 8 + kGradMaxLs + 3;
     double* host = ctx->pinned_scratch(kHostDoubles);
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    double loo_token = 0.0;
+    if constexpr (sizeof(TF) == 8) {
+      if (want_loo && small) {
+        // N <= 128: ONE workgroup behind the one-launch fit, its scalars straight into pinned host memory
+        LooSmallArgs a{};
+        a.kinv = as<double>(kinvb); a.alpha = as<double>(alpha_f); a.kinv_diag = as<double>(kinv_diag);
+        a.y64 = as<double>(y64); a.xs = as<double>(xs64); a.ls = ls_dev();
+        a.n = (int)n; a.npad = (int)npad; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls; a.variance = variance;
+        a.vec = nullptr; a.scal = as<double>(loo_scal); a.scal_host = host + kLooHostAt;
+        loo_token = ctx->timing ? 0.0 : ctx->next_token();
+        a.scal_host[7] = 0.0;
+        a.done_token = loo_token;
+        if (launch_loo_small(s, a)) return launch_status();
+      } else if (want_loo) {
+        // any N: S = diag(sqrt c) K^-1 in the Gram buffer, M = S^T S in the factorisation's scratch (both free behind the
+        // fit), 2 W over S, then the NLML gradient's own contraction with (kinv := 2 W, alpha := 0); kinvb stays K_y^-1
+        double* vec = as<double>(loov);
+        launch_loo_points<double>(s, as<double>(alpha_f), as<double>(kinv_diag), as<double>(y64), n, npad, vec, as<double>(loo_scal));
+        launch_loo_weights(s, as<double>(kinvb), as<double>(alpha_f), vec, as<double>(K), as<double>(work), n, npad);
+        launch_gradient<double>(s, as<double>(linv), vec + (size_t)kLooZero * npad, as<double>(xs64), as<double>(xnorm64), n, npad,
+                                d, dp, n_ls, ls_dev(), kp, as<double>(K), true, as<double>(gpart), as<double>(loo_scal) + 8);
+        launch_loo_mean_grad(s, vec, n, npad, as<double>(loo_scal) + 8 + n_ls + 2);
+        HIPCHECK(hipMemcpyAsync(host + kLooHostAt, loo_scal.p, kHostDoubles * 8, hipMemcpyDeviceToHost, s));
+      }
+    }
+    if ((rc = launch_status())) return rc;
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
     if (!small) HIPCHECK(hipMemcpyAsync(host, scal.p, kHostDoubles * 8, hipMemcpyDeviceToHost, s));
-    if (small && fit_token != 0.0 && !ctx->timing) HIPCHECK(ctx->wait_token(&host[7], fit_token, s));
+    if (loo_token != 0.0) HIPCHECK(ctx->wait_token(&host[kLooHostAt + 7], loo_token, s));
+    else if (small && fit_token != 0.0 && !ctx->timing && !want_loo) HIPCHECK(ctx->wait_token(&host[7], fit_token, s));
     else HIPCHECK(ctx->wait(s));
     float ms = 0;
     if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
@@ -1102,9 +1163,35 @@ struct EngineT : Engine {
     if (nlml) *nlml = host[0];
     if (grad)  // device order: ls..., variance, noise, then -sum(alpha)
       for (int h = 0; h < n_ls + 3; ++h) grad[h] = host[8 + h];
+    if (want_loo) {
+      *loo_loss = host[kLooHostAt];
+      for (int h = 0; h < n_ls + 3; ++h) loo_grad[h] = host[kLooHostAt + 8 + h];
+    }
     res.fit_done(grad != nullptr, linv_p_deferred, split_deferred, bf16_usable());
     return GPSO_OK;
   }
+  // ---- leave-one-out predictive of the resident fitted posterior (loo.hip): reads alpha and kinv_diag, changes nothing a
+  // predict or a later call reads
+  int loo(double* mean, double* var, double* lpd, double* loss) override {
+    if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
+      return ctx->fail(GPSO_E_STATE, "gpso_loo needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
+    int rc = refuse_if_async("gpso_loo");
+    if (rc) return rc;
+    if (n < 2) return ctx->fail(GPSO_E_ARG, "gpso_loo needs at least two training points (N=%lld)", (long long)n);
+    if ((rc = ensure(loov, (size_t)kLooVecs * npad * 8))) return rc;
+    if ((rc = ensure(loo_scal, (size_t)(8 + kGradMaxLs + 3) * 8))) return rc;
+    hipStream_t s = st();
+    double* vec = as<double>(loov);
+    launch_loo_points<TF>(s, as<TF>(alpha_f), as<double>(kinv_diag), as<double>(y64), n, npad, vec, as<double>(loo_scal));
+    if ((rc = launch_status())) return rc;
+    if (mean) HIPCHECK(hipMemcpyAsync(mean, vec + (size_t)kLooMean * npad, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    if (var) HIPCHECK(hipMemcpyAsync(var, vec + (size_t)kLooVar * npad, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    if (lpd) HIPCHECK(hipMemcpyAsync(lpd, vec + (size_t)kLooLpd * npad, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    if (loss) HIPCHECK(hipMemcpyAsync(loss, loo_scal.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    return GPSO_OK;
+  }
+
   // ---- batched evaluation (multi-start hyper-parameter search): fit.hip small_fit_batch_kernel -------------------------
   // entries one launch may hold for the resident data: one workgroup per CU where the one-launch fit applies, else none
   int fit_batch_max() override { return (res.have_data && fused_small && small_fit_eligible(n, dp)) ? kSmallBatchMax : 0; }
@@ -4079,6 +4166,41 @@ int gpso_fit_eval_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
   const int rc = ctx->eng->fit_eval(kernel, ls, n_ls, variance, noise, mean_c, nlml, grad_u ? g : nullptr);
   if (rc != GPSO_OK || !grad_u) return rc;
   // chain rule: d/du = d/dtheta * sigmoid(u) for the softplus-transformed parameters, identity for the mean
+  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
+  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
+  return GPSO_OK;
+}
+
+int gpso_loo(gpso_ctx* ctx, double* mean, double* var, double* lpd, double* loss) {
+  ENTER();
+  return ctx->eng->loo(mean, var, lpd, loss);
+}
+
+int gpso_fit_eval_loo(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_ls, double variance, double noise,
+                      double mean_c, double* loss, double* grad, double* nlml) {
+  ENTER();
+  return ctx->eng->fit_eval_loo(kernel, lengthscales, n_ls, variance, noise, mean_c, loss, grad, nlml);
+}
+
+int gpso_fit_eval_loo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
+                        double* loss, double* grad_u, double* theta_out, double* nlml) {
+  ENTER();
+  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
+  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
+  // the transforms and the chain rule of gpso_fit_eval_u
+  double ls[kGradMaxLs], g[kGradMaxLs + 3];
+  for (int k = 0; k < n_ls; ++k) ls[k] = gpso_softplus(u[k]);
+  const double variance = gpso_softplus(u[n_ls]);
+  const double noise = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
+  const double mean_c = train_mean ? u[n_ls + 2] : mean_c_fixed;
+  if (theta_out) {
+    for (int k = 0; k < n_ls; ++k) theta_out[k] = ls[k];
+    theta_out[n_ls] = variance;
+    theta_out[n_ls + 1] = noise;
+    theta_out[n_ls + 2] = mean_c;
+  }
+  const int rc = ctx->eng->fit_eval_loo(kernel, ls, n_ls, variance, noise, mean_c, loss, grad_u ? g : nullptr, nlml);
+  if (rc != GPSO_OK || !grad_u) return rc;
   for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
   if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
   return GPSO_OK;

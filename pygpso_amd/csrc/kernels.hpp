@@ -356,6 +356,37 @@ void launch_vgp_lik_sums(hipStream_t st, const double* ve, const double* dve, co
 void launch_vgp_lbar_w(hipStream_t st, double* lsig, const double* a, const double* gm, const double* mu, int64_t n,
                        int64_t npad);
 void launch_vgp_rowscale(hipStream_t st, const double* A, const double* a, double* B, int64_t n, int64_t npad);
+// ---- loo.hip: leave-one-out predictive and LOO-CV objective of the exact GP ---------------------
+// vec: kLooVecs vectors of N_pad doubles, zero on the padding -- the predictive (mean, var, lpd), sqrt c, g / sqrt c, h and
+// a vector of zeros (the alpha the weight contraction is called with)
+enum { kLooMean = 0, kLooVar = 1, kLooLpd = 2, kLooSc = 3, kLooT = 4, kLooH = 5, kLooZero = 6, kLooVecs = 7 };
+// the per-point pass from the resident alpha (fit type) and kinv_diag; loss_out[0] = -sum lpd (one workgroup, fixed order)
+template <typename T>
+void launch_loo_points(hipStream_t st, const T* alpha, const double* kinv_diag, const double* y64, int64_t n, int64_t npad,
+                       double* vec, double* loss_out);
+// after launch_loo_points: S := diag(sqrt c) K_y^-1 (kinv: lower triangle read), M := S^T S, h := K_y^-1 g into vec, then
+// S := 2 W = 2 M - (h alpha^T + alpha h^T) on the lower 64-tiles, zero on the padding -- what launch_gradient takes as its
+// kinv with kinv_ready and the zero vector for alpha.  S, M: N_pad^2 doubles each
+void launch_loo_weights(hipStream_t st, const double* kinv, const double* alpha, double* vec, double* S, double* M, int64_t n,
+                        int64_t npad);
+// out[0] = dF/dc = -sum h
+void launch_loo_mean_grad(hipStream_t st, const double* vec, int64_t n, int64_t npad, double* out);
+// N <= 128, behind the one-launch fit with want_grad: the point pass, M, h and the contraction with dK in ONE workgroup
+struct LooSmallArgs {
+  const double* kinv;       // [npad * npad] K_y^-1, lower triangle read
+  const double* alpha;      // [npad]
+  const double* kinv_diag;  // [npad]
+  const double* y64;        // [n]
+  const double* xs;         // [npad * dp] scaled inputs
+  const double* ls;         // lengthscale per padded dimension (device: the hyper block)
+  int n, npad, dp, kernel, n_ls;
+  double variance;
+  double* vec;        // nullable: mean, var, lpd at kLooMean / kLooVar / kLooLpd
+  double* scal;       // [0] loss, [8 ..] gradient (ls..., variance, noise, c)
+  double* scal_host;  // nullable: pinned host memory that receives the same scalars
+  double done_token;  // != 0: scal_host[7] := token behind the scalars
+};
+int launch_loo_small(hipStream_t st, const LooSmallArgs& args);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

@@ -249,6 +249,51 @@ class HipGPEngine:
             self._check(rc)
         return nl.value, ga.copy(), ta.copy()
 
+    # -- leave-one-out (include/gpso_hip.h: gpso_loo, gpso_fit_eval_loo*; no counterpart in the reference) -----------------
+    def loo(self):
+        """``gpso_loo``: the leave-one-out predictive of the resident fitted posterior at its hyper-parameters.  Returns
+        (mean [N], var [N], lpd [N], loss): what N refits without point i predict for y_i (its own noise included), the log
+        predictive density of each y_i and loss = -sum lpd.  Reads only; GpsoHipError (GPSO_E_STATE) without a posterior
+        fitted with targets on this engine."""
+        n = C.c_int64()
+        d = C.c_int()
+        self._check(self._lib.gpso_problem_shape(self._h, C.byref(n), C.byref(d)))
+        mean, var, lpd = (np.empty(max(int(n.value), 1), dtype=np.float64) for _ in range(3))
+        loss = C.c_double()
+        self._check(self._lib.gpso_loo(self._h, L.dptr(mean), L.dptr(var), L.dptr(lpd), C.byref(loss)))
+        return mean, var, lpd, loss.value
+
+    def fit_eval_loo(self, kernel, lengthscales, variance, noise, mean_c, want_grad=True):
+        """One evaluation of the LOO-CV loss (-sum of the leave-one-out log predictive densities) and its gradient
+        (``gpso_fit_eval_loo``); leaves the posterior resident exactly as ``fit_eval`` does.  Returns (loss, grad or None,
+        nlml): grad order (ls..., variance, noise, c); nlml is the NLML at the same theta.  "float64" / "mixed" engines."""
+        kid, ls, n_ls, var, nz, mc = self._theta_args(kernel, lengthscales, variance, noise, mean_c)
+        loss, nlml = C.c_double(), C.c_double()
+        grad = np.empty(n_ls + 3, dtype=np.float64) if want_grad else None
+        self._check(self._lib.gpso_fit_eval_loo(self._h, kid, L.dptr(ls), n_ls, var, nz, mc, C.byref(loss),
+                                                L.dptr(grad) if want_grad else None, C.byref(nlml)))
+        return loss.value, grad, nlml.value
+
+    def fit_eval_loo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
+        """``fit_eval_u`` for the LOO-CV loss (``gpso_fit_eval_loo_u``).  Returns (loss, grad_u, theta, nlml)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
+        key = ("loo", int(n_ls), bool(train_mean))
+        buf = self._u_bufs.get(key)
+        if buf is None:  # (as fit_eval_u: made once per problem shape)
+            ua = np.empty(n_u, dtype=np.float64)
+            ga = np.empty(n_u, dtype=np.float64)
+            ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+            fl, nl = C.c_double(), C.c_double()
+            buf = self._u_bufs[key] = (ua, ga, ta, fl, nl, L.dptr(ua), L.dptr(ga), L.dptr(ta), C.byref(fl), C.byref(nl))
+        ua, ga, ta, fl, nl, up, gp, tp, flp, nlp = buf
+        ua[:] = u
+        rc = self._lib.gpso_fit_eval_loo_u(self._h, kid, up, int(n_ls), 1 if train_mean else 0, float(mean_c_fixed), flp, gp,
+                                           tp, nlp)
+        if rc < 0:
+            self._check(rc)
+        return fl.value, ga.copy(), ta.copy(), nl.value
+
     def fit_batch_max(self):
         """Entries one ``gpso_fit_eval_u_batch`` call may hold for the resident data (256 where the one-launch fit applies,
         0 otherwise: N > 128, or N > 64 with a padded D > 32)."""

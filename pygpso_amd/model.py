@@ -71,8 +71,13 @@ def _as_result(a):
 
 class HipGPR:
     def __init__(self, data, kernel, mean_function=None, noise_variance=1.0e-3, dtype="float64",
-                 device=0, engine=None, engine_options=None, escalate=True, devices=None, noise_diag=None):
-        """``noise_diag`` [N] >= 0 (or None): the known variance of each observation, a fixed per-point term beside the
+                 device=0, engine=None, engine_options=None, escalate=True, devices=None, noise_diag=None,
+                 objective="nlml"):
+        """``objective``: what the hyper-parameter search minimises -- "nlml" (default: the negative log marginal
+        likelihood, as the reference) or "loo" (the leave-one-out log pseudo-likelihood, Rasmussen & Williams 5.4.2:
+        -sum of the log predictive density of every point under the fit without it; ``gpso_fit_eval_loo``; "float64" and
+        "mixed" engines).  No counterpart in the reference.
+        ``noise_diag`` [N] >= 0 (or None): the known variance of each observation, a fixed per-point term beside the
         trained likelihood variance -- the fits factorise K + diag(likelihood.variance + noise_diag); ``predict_y`` adds
         the likelihood variance only.
         ``dtype``: "float64" | "mixed" | "float32" (see ``HipGPEngine``).  ``engine_options``: extra
@@ -96,7 +101,15 @@ class HipGPR:
         self.escalate = bool(escalate)
         self.fit_escalations = 0  # hyper-parameter searches restarted on a more precise engine (Scipy.minimize)
         self.fused_transforms = True  # loss evaluations through gpso_fit_eval_u (False: transforms in Python)
+        if objective not in ("nlml", "loo"):
+            raise ValueError(f"objective must be 'nlml' or 'loo', not {objective!r}")
+        self.objective = objective
         self.engine = engine if engine is not None else self._open_engine(dtype)
+        if objective == "loo":
+            if getattr(self.engine, "dtype_name", None) == "float32":
+                raise NotImplementedError("objective='loo' needs a float64 fit: use dtype='float64' or 'mixed'")
+            if not hasattr(self.engine, "fit_eval_loo_u"):
+                raise NotImplementedError(f"objective='loo' is not available on {type(self.engine).__name__}")
         self._data = None
         self._resident = False  # posterior on the device matches (data, hyper-parameters)?
         self.num_loss_evals = 0
@@ -255,6 +268,14 @@ class HipGPR:
         """f(u), df/du for L-BFGS-B: one device evaluation (Gram -> Cholesky -> ... -> gradient)."""
         self._device_theta = None
         k = self.n_ls
+        if self.objective == "loo":
+            # the LOO-CV loss: the same factorisation, the same posterior left on the device, another loss and gradient
+            f, gu, th, nlml = self.engine.fit_eval_loo_u(self.kernel.name, u, k, self._train_mean, float(self.mean_function.c))
+            self._device_theta = self._theta_key(self.kernel.name, th[:k], th[k], th[k + 1], th[k + 2])
+            self._last_nlml = nlml
+            self.num_loss_evals += 1
+            self._resident = False
+            return f, gu
         if self.fused_transforms and hasattr(self.engine, "fit_eval_u"):
             # transforms + chain rule inside the library: one C-ABI call per evaluation (bit-identical to the branch
             # below: tests/test_gpu_goldens.py::test_loss_evaluation_in_the_optimisers_variables)
@@ -283,8 +304,9 @@ class HipGPR:
         what the model knows about it stands; the row-by-row fallbacks (N > 128, an engine without the batched call) replace
         it as any fit does."""
         U = np.atleast_2d(np.asarray(U, dtype=np.float64))
-        if not hasattr(self.engine, "fit_eval_u_batch"):
-            # an engine without the batched call (a multi-GPU group, a test double): the rows one after another
+        if self.objective == "loo" or not hasattr(self.engine, "fit_eval_u_batch"):
+            # an engine without the batched call (a multi-GPU group, a test double), or the LOO objective (the batched
+            # kernel evaluates the NLML): the rows one after another
             loss, grad, ok = np.full(U.shape[0], np.nan), np.full(U.shape, np.nan), np.zeros(U.shape[0], dtype=bool)
             for b, u in enumerate(U):
                 try:
@@ -317,13 +339,29 @@ class HipGPR:
             self._resident = True
 
     def training_loss(self):
-        """Negative log marginal likelihood at the current hyper-parameters."""
+        """The objective at the current hyper-parameters: the negative log marginal likelihood, or -- objective="loo" --
+        the LOO-CV loss."""
         self._resident = False
         self._ensure_resident()
+        if self.objective == "loo":
+            return self.engine.loo()[3]
         return self._last_nlml
 
     def log_marginal_likelihood(self):
-        return -self.training_loss()
+        self._resident = False
+        self._ensure_resident()
+        return -self._last_nlml
+
+    def loo(self):
+        """Leave-one-out predictive of the training points at the current hyper-parameters (``gpso_loo``; O(N) behind
+        the resident posterior, whatever the objective).  Returns (mean [N], var [N], lpd [N], loss, z [N]): what the fit
+        without point i predicts for y_i (the variance includes its noise), the log predictive density of y_i,
+        loss = -sum lpd, and the standardised residuals z = (y - mean) / sqrt(var)."""
+        if not hasattr(self.engine, "loo"):
+            raise NotImplementedError(f"the leave-one-out predictive is not available on {type(self.engine).__name__}")
+        self._ensure_resident()
+        mean, var, lpd, loss = self.engine.loo()
+        return mean, var, lpd, loss, (self._data[1][:, 0] - mean) / np.sqrt(var)
 
     # -- predict ------------------------------------------------------------------------------
     def _escalate(self, err, fit=False):
