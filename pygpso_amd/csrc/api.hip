@@ -21,6 +21,7 @@
 #include "kernels.hpp"
 #include "rccl_api.hpp"
 #include "resident.hpp"
+#include "theta.hpp"
 
 using namespace gpso;
 
@@ -64,6 +65,7 @@ thread_local std::string g_create_error;
 constexpr int kMaxD = 48;                      // padded input dimension limit (LDS budgets)
 constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass of the tile kernel
 constexpr int kHyperHeader = 8;                // doubles in front of the lengthscales
+static_assert(kThetaMaxLs == kGradMaxLs, "a Theta holds as many lengthscales as the gradient kernels take");
 
 struct DevBuf {
   void* p = nullptr;
@@ -74,15 +76,13 @@ struct DevBuf {
 struct Engine {
   virtual ~Engine() {}
   virtual int set_data(const double* X, const double* y, int64_t n, int d) = 0;
-  virtual int fit_eval(int kernel, const double* ls, int n_ls, double variance, double noise,
-                       double mean_c, double* nlml, double* grad) = 0;
-  virtual int set_posterior(const double* X, const double* L, const double* alpha, int64_t n, int d,
-                            int kernel, const double* ls, int n_ls, double variance, double noise,
-                            double mean_c) = 0;
+  // theta crosses this interface as one Theta (theta.hpp): lik is the noise variance, the likelihood's variance or its scale.
+  // (gpso_fit_eval / gpso_fit_eval_loo: th is NULL when the caller passed no lengthscales -- refused where it always was)
+  virtual int fit_eval(const Theta* th, double* nlml, double* grad) = 0;
+  virtual int set_posterior(const double* X, const double* L, const double* alpha, int64_t n, int d, const Theta& th) = 0;
   // leave-one-out predictive of the resident fitted posterior / one evaluation of the LOO-CV objective (loo.hip)
   virtual int loo(double* mean, double* var, double* lpd, double* loss) = 0;
-  virtual int fit_eval_loo(int kernel, const double* ls, int n_ls, double variance, double noise, double mean_c,
-                           double* loss, double* grad, double* nlml) = 0;
+  virtual int fit_eval_loo(const Theta* th, double* loss, double* grad, double* nlml) = 0;
   virtual int fit_batch_max() = 0;
   virtual int fit_eval_batch(int kernel, const double* th, int nv, int n_ls, double* loss, double* grad, int* info) = 0;
   virtual int fit_eval_batch_check(int kernel, int b, int n_ls) = 0;
@@ -133,35 +133,29 @@ struct Engine {
   virtual int vgp_set_q(const double* mu, const double* S, int64_t n) = 0;
   virtual int vgp_get_q(double* mu, double* S) = 0;
   virtual int vgp_extend_q() = 0;
-  virtual int vgp_natgrad(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double gamma) = 0;
-  virtual int vgp_elbo(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double* loss,
-                       double* grad) = 0;
-  virtual int vgp_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c) = 0;
+  virtual int vgp_natgrad(const Theta& th, double gamma) = 0;
+  virtual int vgp_elbo(const Theta& th, double* loss, double* grad) = 0;
+  virtual int vgp_posterior(const Theta& th) = 0;
   virtual int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) = 0;
   // sparse GP regression on inducing points (sgpr.hip)
   virtual int sgpr_set_inducing(const double* Z, int64_t m) = 0;
-  virtual int sgpr_select_inducing(int kernel, const double* ls, int n_ls, double variance, int64_t m, int64_t* idx_out) = 0;
+  virtual int sgpr_select_inducing(const Theta& th, int64_t m, int64_t* idx_out) = 0;
   virtual int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) = 0;
   virtual int sgpr_get_factor(int which, double* out) = 0;
-  virtual int sgpr_bound(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, double* loss,
-                         double* grad) = 0;
-  virtual int sgpr_posterior(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c,
-                             double* delta_out) = 0;
+  virtual int sgpr_bound(const Theta& th, double* loss, double* grad) = 0;
+  virtual int sgpr_posterior(const Theta& th, double* delta_out) = 0;
   // ... and at a moving Z (inducing.hip): Z (nullable) replaces the resident inducing rows in place
   virtual int sgpr_move_inducing(const double* Z) = 0;
-  virtual int sgpr_bound_z(int kernel, const double* ls, int n_ls, double variance, double s2, double mean_c, const double* Z,
-                           double* loss, double* grad, double* grad_z) = 0;
-  virtual int svgp_elbo_z(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, const double* Z,
-                          double* loss, double* grad, double* grad_z) = 0;
+  virtual int sgpr_bound_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) = 0;
+  virtual int svgp_elbo_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) = 0;
   // sparse variational GP on inducing points (svgp.hip)
-  virtual int svgp_init_q(int kernel, const double* ls, int n_ls, double variance, double mean_c, double s2) = 0;
+  // s2 > 0: the conjugate start at that noise variance (th.lik is not read); else the prior (th is not read)
+  virtual int svgp_init_q(const Theta& th, double s2) = 0;
   virtual int svgp_set_q(const double* mu, const double* S, int64_t m) = 0;
   virtual int svgp_get_q(double* mu, double* S) = 0;
-  virtual int svgp_natgrad(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, double gamma) = 0;
-  virtual int svgp_elbo(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c, double* loss,
-                        double* grad) = 0;
-  virtual int svgp_posterior(int kernel, const double* ls, int n_ls, double variance, double p, double mean_c,
-                             double* delta_out) = 0;
+  virtual int svgp_natgrad(const Theta& th, double gamma) = 0;
+  virtual int svgp_elbo(const Theta& th, double* loss, double* grad) = 0;
+  virtual int svgp_posterior(const Theta& th, double* delta_out) = 0;
   int vlik_kind = GPSO_LIK_GAUSSIAN;  // the VGP's likelihood (GPSO_LIK_*): what slot n_ls + 1 of u means
 };
 
@@ -850,21 +844,36 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  // upload = false: the caller's kernel writes the device copy of the block itself (fused small fit)
-  int set_theta(int kernel, const double* ls, int n_ls_, double variance, double noise, double mean_c,
-                bool upload = true) {
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
-    if (n_ls_ > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "too many lengthscales");
-    for (int k = 0; k < n_ls_; ++k)
-      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
-    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
-    kp.kernel = kernel;
-    kp.variance = variance;
-    kp.noise = noise;
-    kp.mean_c = mean_c;
-    n_ls = n_ls_;
-    ls_host.assign(ls, ls + n_ls_);
+  // GPSO_OK, or the message of what theta_refusal / theta_shape_refusal (theta.hpp) found.  what_lik: the likelihood
+  // parameter's name at this entry point
+  int theta_status(const ThetaRefusal& r, const char* what_lik = "noise variance") {
+    switch (r.rule) {
+      case ThetaRule::None: return GPSO_OK;
+      case ThetaRule::Lik: return ctx->fail(GPSO_E_ARG, "%s %g must be positive", what_lik, r.value);
+      case ThetaRule::Kernel: return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", r.index);
+      case ThetaRule::Nls: return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", r.index, d);
+      case ThetaRule::Lengthscale: return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", r.index, r.value);
+      case ThetaRule::Variance: return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", r.value);
+    }
+    return GPSO_OK;
+  }
+  // the resident theta, as a fit at the same hyper-parameters takes it (gpso_append's refit)
+  Theta resident_theta() const {
+    Theta th;
+    theta_from_parts(kp.kernel, ls_host.data(), n_ls, kp.variance, kp.noise, kp.mean_c, &th);
+    return th;
+  }
+
+  // th.lik: the noise variance of the hyper block.  upload = false: the caller's kernel writes the device copy of the block
+  // itself (fused small fit)
+  int set_theta(const Theta& th, bool upload = true) {
+    if (int rc = theta_status(theta_refusal(th, d, false))) return rc;
+    kp.kernel = th.kernel;
+    kp.variance = th.variance;
+    kp.noise = th.lik;
+    kp.mean_c = th.mean_c;
+    n_ls = th.n_ls;
+    ls_host.assign(th.ls, th.ls + n_ls);
     if (!upload) return GPSO_OK;
     // staged in pinned memory (upper half of the scratch; the read-backs use the lower half): the copy
     // is then a plain stream operation and needs no host synchronisation here
@@ -874,9 +883,9 @@ struct EngineT : Engine {
     double* h = scratch + 128;
     constexpr size_t kHyperBytes = (size_t)(kHyperHeader + kMaxD) * 8;
     std::memset(h, 0, kHyperBytes);
-    h[0] = (double)n; h[1] = (double)d; h[2] = (double)kernel; h[3] = (double)n_ls_;
-    h[4] = variance; h[5] = noise; h[6] = mean_c;
-    for (int k = 0; k < kMaxD; ++k) h[kHyperHeader + k] = ls[n_ls_ == 1 ? 0 : std::min(k, n_ls_ - 1)];
+    h[0] = (double)n; h[1] = (double)d; h[2] = (double)th.kernel; h[3] = (double)n_ls;
+    h[4] = th.variance; h[5] = th.lik; h[6] = th.mean_c;
+    for (int k = 0; k < kMaxD; ++k) h[kHyperHeader + k] = th.ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
     HIPCHECK(hipMemcpyAsync(hyper.p, h, kHyperBytes, hipMemcpyHostToDevice, st()));
     return GPSO_OK;
   }
@@ -960,19 +969,15 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int fit_eval(int kernel, const double* ls, int n_ls_, double variance, double noise,
-               double mean_c, double* nlml, double* grad) override {
-    return fit_eval_impl(kernel, ls, n_ls_, variance, noise, mean_c, nlml, grad, nullptr, nullptr);
-  }
+  int fit_eval(const Theta* th, double* nlml, double* grad) override { return fit_eval_impl(th, nlml, grad, nullptr, nullptr); }
   // One evaluation of the LOO-CV objective: the fit with a gradient as gpso_fit_eval runs it -- so L, L^-1, alpha, the
   // packed copies and the hyper block come out the same bits -- and behind it, on the same stream, the LOO launches (loo.hip)
-  int fit_eval_loo(int kernel, const double* ls, int n_ls_, double variance, double noise, double mean_c, double* loss,
-                   double* grad, double* nlml) override {
+  int fit_eval_loo(const Theta* th, double* loss, double* grad, double* nlml) override {
     if (sizeof(TF) == 4)
       return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context (the LOO objective "
                                    "of a float factor is not supported)");
     double g_nlml[kGradMaxLs + 3], g_loo[kGradMaxLs + 3], f_loo = 0.0;
-    const int rc = fit_eval_impl(kernel, ls, n_ls_, variance, noise, mean_c, nlml, g_nlml, &f_loo, g_loo);
+    const int rc = fit_eval_impl(th, nlml, g_nlml, &f_loo, g_loo);
     if (rc != GPSO_OK) return rc;
     if (loss) *loss = f_loo;
     if (grad)
@@ -981,13 +986,13 @@ struct EngineT : Engine {
   }
 
   static constexpr size_t kLooHostAt = 256;  // the LOO scalars in the pinned scratch: behind set_theta's staging block
-  int fit_eval_impl(int kernel, const double* ls, int n_ls_, double variance, double noise, double mean_c, double* nlml,
-                    double* grad, double* loo_loss, double* loo_grad) {
+  int fit_eval_impl(const Theta* thp, double* nlml, double* grad, double* loo_loss, double* loo_grad) {
     ctx->tick_timing();
     const bool want_loo = loo_loss != nullptr;
     const char* who = want_loo ? "gpso_fit_eval_loo" : "gpso_fit_eval";
     if (!res.have_data) return ctx->fail(GPSO_E_STATE, "%s before gpso_set_data", who);
-    if (!ls) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
+    if (!thp) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
+    const Theta& th = *thp;
     int rc = refuse_if_async(who);
     if (rc) return rc;
     if (want_loo) {
@@ -1000,7 +1005,7 @@ struct EngineT : Engine {
     rc = ensure_fit_buffers();
     if (rc) return rc;
     const bool small = fused_small && small_fit_eligible(n, dp);
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c, !small))) return rc;
+    if ((rc = set_theta(th, !small))) return rc;
     // (tile rows of linv_p beyond a one-launch fit's that may hold old data; every other fit writes, or will write, all 8)
     const int zero_tile_rows = res.fit_begun(small ? (int)((n + 15) / 16) : 8);
     reset_generation();
@@ -1014,10 +1019,10 @@ struct EngineT : Engine {
       // N <= 128: the whole evaluation in ONE launch (fit.hip: small_fit_kernel)
       SmallFitArgs a{};
       a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.hyper = as<double>(hyper);
-      for (int k = 0; k < kMaxD; ++k) a.ls[k] = ls[n_ls_ == 1 ? 0 : std::min(k, n_ls_ - 1)];
-      a.n = (int)n; a.d = d; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls; a.want_grad = grad ? 1 : 0;
+      for (int k = 0; k < kMaxD; ++k) a.ls[k] = th.ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
+      a.n = (int)n; a.d = d; a.dp = dp; a.kernel = th.kernel; a.n_ls = n_ls; a.want_grad = grad ? 1 : 0;
       a.zero_tile_rows = zero_tile_rows;
-      a.variance = variance; a.noise = noise; a.mean_c = mean_c;
+      a.variance = th.variance; a.noise = th.lik; a.mean_c = th.mean_c;
       a.sdiag = s_dev();
       a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
       a.Lf = Lf.p; a.linv = linv.p; a.kinv = grad ? kinvb.p : nullptr;
@@ -1057,7 +1062,7 @@ struct EngineT : Engine {
           planes.ev_chain = ctx->ev_chain;
           // fp16 pieces (three MFMAs per product) when the hyper-parameters leave every plane set inside fp16's range
           // after its power-of-two scaling; bf16 pieces (six) otherwise -- the fallback rung
-          if (fit_planes_mode == 2) (void)fit_plane_scales(variance, noise, planes, res.have_s ? s_max : 0.0);
+          if (fit_planes_mode == 2) (void)fit_plane_scales(th.variance, th.lik, planes, res.have_s ? s_max : 0.0);
           pl = &planes;
           ctx->last_count[2] = planes.np == 2 ? GPSO_FITMATH_F16X3 : GPSO_FITMATH_BF16X6;
         }
@@ -1105,7 +1110,7 @@ struct EngineT : Engine {
       }
       if (!inv_done) launch_trtri<TF>(s, as<TF>(Lf), as<TF>(linv), as<TF>(work), npad, fit_outer_panel(npad));
       float* linv_max_out = f16_max_for_fit();  // (may allocate amax_rows: before the argument list below)
-      launch_solve_alpha<TF>(s, as<TF>(linv), as<double>(y64), n, npad, mean_c, as<double>(logdet),
+      launch_solve_alpha<TF>(s, as<TF>(linv), as<double>(y64), n, npad, th.mean_c, as<double>(logdet),
                              as<TF>(white), as<TF>(alpha_f), as<double>(apart), as<double>(kinv_diag),
                              as<double>(scal), alpha.p, sizeof(TP) == 8, as<float>(amax_rows), linv_max_out);
       if (grad)
@@ -1130,7 +1135,7 @@ struct EngineT : Engine {
         LooSmallArgs a{};
         a.kinv = as<double>(kinvb); a.alpha = as<double>(alpha_f); a.kinv_diag = as<double>(kinv_diag);
         a.y64 = as<double>(y64); a.xs = as<double>(xs64); a.ls = ls_dev();
-        a.n = (int)n; a.npad = (int)npad; a.dp = dp; a.kernel = kernel; a.n_ls = n_ls; a.variance = variance;
+        a.n = (int)n; a.npad = (int)npad; a.dp = dp; a.kernel = th.kernel; a.n_ls = n_ls; a.variance = th.variance;
         a.vec = nullptr; a.scal = as<double>(loo_scal); a.scal_host = host + kLooHostAt;
         loo_token = ctx->timing ? 0.0 : ctx->next_token();
         a.scal_host[7] = 0.0;
@@ -1201,8 +1206,7 @@ struct EngineT : Engine {
     if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval_u_batch before gpso_set_data");
     int rc = refuse_if_async("gpso_fit_eval_u_batch");
     if (rc) return rc;
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
+    if ((rc = theta_status(theta_shape_refusal(kernel, n_ls_, d)))) return rc;
     if (b < 1) return ctx->fail(GPSO_E_ARG, "a batch needs at least one entry (b=%d)", b);
     const int cap = fit_batch_max();
     if (cap == 0) {
@@ -1302,7 +1306,7 @@ struct EngineT : Engine {
     // is factorised by one workgroup; at N = 8192 the same 64 points take 1.1 ms against 4.2: profiles/r05_append_bench.jsonl)
     else if (k > 32 && npad < 4096) refit = "more than 32 new points beside fewer than 4096: the refit is as fast";
     if (refit != nullptr) {
-      std::vector<double> X(x_host), y(y_host), ls(ls_host);
+      std::vector<double> X(x_host), y(y_host);
       X.insert(X.end(), Xn, Xn + (size_t)k * d);
       y.insert(y.end(), yn, yn + (size_t)k);
       // (set_data clears the per-point noise: the refit carries it along, the new points' values behind the resident ones)
@@ -1313,12 +1317,12 @@ struct EngineT : Engine {
         if (sn != nullptr) sv.insert(sv.end(), sn, sn + (size_t)k);
         else sv.resize((size_t)n_new, 0.0);
       }
-      const KernParams th = kp;
-      const int nls = n_ls, d_ = d;
+      const Theta th = resident_theta();
+      const int d_ = d;
       const int64_t n_old = n;
       int rc = set_data(X.data(), y.data(), n_new, d_);
       if (rc == GPSO_OK && with_s) rc = set_noise_diag(sv.data(), n_new);
-      if (rc == GPSO_OK) rc = fit_eval(th.kernel, ls.data(), nls, th.variance, th.noise, th.mean_c, nlml, nullptr);
+      if (rc == GPSO_OK) rc = fit_eval(&th, nlml, nullptr);
       if (rc < 0) {
         // the header's promise holds on this path too: a failed append leaves the posterior of the first n points resident
         // (set_data dropped it: put the old points back and refit at the resident hyper-parameters -- the fit that
@@ -1331,7 +1335,7 @@ struct EngineT : Engine {
           sv.resize((size_t)n_old);
           rc2 = set_noise_diag(sv.data(), n_old);
         }
-        if (rc2 == GPSO_OK) rc2 = fit_eval(th.kernel, ls.data(), nls, th.variance, th.noise, th.mean_c, nullptr, nullptr);
+        if (rc2 == GPSO_OK) rc2 = fit_eval(&th, nullptr, nullptr);
         if (rc2 < 0) return ctx->fail(rc, "%s (and the posterior of the first %lld points could not be restored: status %d -- "
                                           "gpso_set_data + gpso_fit_eval start over)", why.c_str(), (long long)n_old, rc2);
         return ctx->fail(rc, "%s (the posterior of the first %lld points is resident again)", why.c_str(), (long long)n_old);
@@ -1423,16 +1427,14 @@ struct EngineT : Engine {
   }
 
 
-  int set_posterior(const double* X, const double* L, const double* alpha64, int64_t n_, int d_,
-                    int kernel, const double* ls, int n_ls_, double variance, double noise,
-                    double mean_c) override {
-    if (!X || !L || !alpha64 || !ls) return ctx->fail(GPSO_E_ARG, "NULL argument");
+  int set_posterior(const double* X, const double* L, const double* alpha64, int64_t n_, int d_, const Theta& th) override {
+    if (!X || !L || !alpha64) return ctx->fail(GPSO_E_ARG, "NULL argument");
     int rc = refuse_if_async("gpso_set_posterior");
     if (rc) return rc;
     rc = shape(n_, d_);
     if (rc) return rc;
     if ((rc = ensure_fit_buffers())) return rc;
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, noise, mean_c))) return rc;
+    if ((rc = set_theta(th))) return rc;
     if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
     hipStream_t s = st();
     double* tmp = as<double>(getter_tmp);
@@ -1562,8 +1564,8 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
   // L = chol(k(X, X) + 1e-6 I) into Lf, L^-1 into linv (clean lower, zero padding)
-  int vgp_factor(int kernel, const double* ls, int n_ls_, double variance, double mean_c) {
-    int rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, mean_c);
+  int vgp_factor(const Theta& th) {
+    int rc = set_theta(th.with_lik(kVgpJitter));
     if (rc) return rc;
     if ((rc = scale_inputs())) return rc;
     launch_gram<double>(st(), as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<double>(K), vinfo() + 0);
@@ -1695,13 +1697,14 @@ struct EngineT : Engine {
   }
 
   // one natural-gradient step on q at theta (GPflow's NaturalGradient with a conjugate likelihood, gamma in (0, 1])
-  int vgp_natgrad(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double gamma) override {
+  int vgp_natgrad(const Theta& th, double gamma) override {
+    const double s2 = th.lik, mean_c = th.mean_c;
     if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
     int rc = vgp_begin();
     if (rc) return rc;
     hipStream_t s = st();
     vgp_reset_info();
-    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    if ((rc = vgp_factor(th))) return rc;
     double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *h = vvec_at(kVgpH);
     const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
     if (!general) {
@@ -1738,12 +1741,13 @@ struct EngineT : Engine {
   }
 
   // -ELBO at fixed q and its gradient in the constrained theta: grad[n_ls + 3] = (ls..., variance, s2, c)
-  int vgp_elbo(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss, double* grad) override {
+  int vgp_elbo(const Theta& th, double* loss, double* grad) override {
+    const double s2 = th.lik, mean_c = th.mean_c;
     int rc = vgp_begin();
     if (rc) return rc;
     hipStream_t s = st();
     vgp_reset_info();
-    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    if ((rc = vgp_factor(th))) return rc;
     double *L = as<double>(Lf), *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
     double *Sq = as<double>(vq_S), *mu = as<double>(vq_mu), *r = vvec_at(kVgpR);
     const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
@@ -1829,12 +1833,13 @@ struct EngineT : Engine {
 
   // install the predictive at theta: L^-1 := C = R L^-1 (I - S S^T = R^T R), alpha := L^-T mu, noise := s2, mean := c --
   // every predict path then serves the VGP unchanged
-  int vgp_posterior(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c) override {
+  int vgp_posterior(const Theta& th) override {
+    const double s2 = th.lik;
     int rc = vgp_begin();
     if (rc) return rc;
     hipStream_t s = st();
     vgp_reset_info();
-    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;
+    if ((rc = vgp_factor(th))) return rc;
     double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sq = as<double>(vq_S);
     launch_vgp_gemv(s, Li, true, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
     if (vlik_kind == GPSO_LIK_GAUSSIAN) {
@@ -1844,7 +1849,7 @@ struct EngineT : Engine {
       launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R = J G^T J
       launch_dgemm(s, B, false, Li, false, A, npad, 1.0, 0.0);        // C = R L^-1
       HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-      if ((rc = set_theta(kernel, ls, n_ls_, variance, s2, mean_c))) return rc;
+      if ((rc = set_theta(th))) return rc;
     } else {
       double shift = 0.0;
       if ((rc = vgp_shifted_root(&shift))) return rc;                 // G of J (I - Sigma / (1 + delta)) J
@@ -1853,7 +1858,7 @@ struct EngineT : Engine {
       HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
       // the likelihood's variance in the predictive: scale^2 df / (df - 2) (Student-t, closed form) or s2; + delta k**
       const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
-      if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
+      if ((rc = set_theta(th.with_lik(noise + shift * th.variance)))) return rc;
     }
     return install_predictive(Post::Vgp);
   }
@@ -1927,21 +1932,17 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int sgpr_select_inducing(int kernel, const double* ls, int n_ls_, double variance, int64_t m, int64_t* idx_out) override {
+  int sgpr_select_inducing(const Theta& th, int64_t m, int64_t* idx_out) override {
     int rc = sgpr_need_f64();
     if (rc) return rc;
     if (!res.sg_have && !res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_select_inducing before gpso_set_data");
     if ((rc = refuse_if_async("gpso_sgpr_select_inducing"))) return rc;
     const int64_t N = res.sg_have ? sg_n : n;
     if (m < 1 || m > N) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, N=%lld]", (long long)m, (long long)N);
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
-    for (int k = 0; k < n_ls_; ++k)
-      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
-    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    if ((rc = theta_status(theta_refusal(th, d, false)))) return rc;
     // (from here on the call replaces whatever posterior was resident: the hyper block is the selection's)
     res.selection_begun();
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, kVgpJitter, 0.0))) return rc;
+    if ((rc = set_theta(th.with_lik(kVgpJitter)))) return rc;
     if ((rc = sgpr_stash())) return rc;
     if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
     if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
@@ -1996,18 +1997,14 @@ struct EngineT : Engine {
   }
 
   // Lu (Lf), Lu^-1 (linv), Kuf, A, A A^T (vA), LB (vC), LB^-1 (sgM2), e, A e, cv at theta; the verdicts in vinfo() 0 and 1
-  int sgpr_factor(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, const char* who) {
+  int sgpr_factor(const Theta& th, const char* who) {
+    const double s2 = th.lik, mean_c = th.mean_c;
     int rc = sgpr_need_f64();
     if (rc) return rc;
     if (!res.sg_have || !res.sg_have_z)
       return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
-    if (!(s2 > 0.0)) return ctx->fail(GPSO_E_ARG, "noise variance %g must be positive", s2);
-    // (the arguments set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
-    for (int k = 0; k < n_ls_; ++k)
-      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
-    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    // (what set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
+    if ((rc = theta_status(theta_refusal(th, d, true), "noise variance"))) return rc;
     if ((rc = vgp_begin(true))) return rc;
     const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
     int nsplit = 1;
@@ -2025,7 +2022,7 @@ struct EngineT : Engine {
     if ((rc = ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8))) return rc;
     hipStream_t s = st();
     vgp_reset_info();
-    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
+    if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
     const double sig = std::sqrt(s2);
     double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *A = as<double>(sgA);
     launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
@@ -2041,15 +2038,14 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int sgpr_bound(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss,
-                 double* grad) override {
-    return sgpr_bound_impl(kernel, ls, n_ls_, variance, s2, mean_c, loss, grad, nullptr, "gpso_sgpr_bound_u");
+  int sgpr_bound(const Theta& th, double* loss, double* grad) override {
+    return sgpr_bound_impl(th, loss, grad, nullptr, "gpso_sgpr_bound_u");
   }
 
   // grad_z (nullable, with grad): also d(-F)/dZ [M * D], from the weights the theta gradient has just formed
-  int sgpr_bound_impl(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, double* loss,
-                      double* grad, double* grad_z, const char* who) {
-    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, who);
+  int sgpr_bound_impl(const Theta& th, double* loss, double* grad, double* grad_z, const char* who) {
+    const double variance = th.variance, s2 = th.lik;
+    int rc = sgpr_factor(th, who);
     if (rc) return rc;
     if (grad_z && (rc = inducing_buffers())) return rc;
     hipStream_t s = st();
@@ -2112,9 +2108,8 @@ struct EngineT : Engine {
 
   // install the predictive over the rows Z: L^-1 := C = sqrt(1 + delta) R Lu^-1 (I - B^-1 / (1 + delta) = R^T R, delta the
   // smallest of 0, 1e-8, 2e-8, ... that factors), alpha := Lu^-T LB^-T cv, noise := s2 + delta variance, mean := c
-  int sgpr_posterior(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c,
-                     double* delta_out) override {
-    int rc = sgpr_factor(kernel, ls, n_ls_, variance, s2, mean_c, "gpso_sgpr_posterior");
+  int sgpr_posterior(const Theta& th, double* delta_out) override {
+    int rc = sgpr_factor(th, "gpso_sgpr_posterior");
     if (rc) return rc;
     hipStream_t s = st();
     double *Li = as<double>(linv), *LBi = as<double>(sgM2);
@@ -2126,7 +2121,7 @@ struct EngineT : Engine {
     launch_vgp_reverse(s, as<double>(vC), as<double>(vB), n, npad, 1, nullptr);                          // R
     launch_dgemm(s, as<double>(vB), false, Li, false, as<double>(vA), npad, std::sqrt(1.0 + shift), 0.0);
     HIPCHECK(hipMemcpyAsync(Li, vA.p, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, s2 + shift * variance, mean_c))) return rc;
+    if ((rc = set_theta(th.with_lik(th.lik + shift * th.variance)))) return rc;
     if ((rc = install_predictive(Post::Sgpr))) return rc;
     if (delta_out) *delta_out = shift;
     return GPSO_OK;
@@ -2173,15 +2168,10 @@ struct EngineT : Engine {
   }
 
   // Lu (Lf), Lu^-1 (linv) at theta; rect: also Kuf (sgKuf) and A = Lu^-1 Kuf (sgA).  The verdict of Kuu in vinfo() 0
-  int svgp_begin(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, const char* who, bool rect) {
+  int svgp_begin(const Theta& th, const char* who, bool rect) {
     int rc = svgp_need_z(who);
     if (rc) return rc;
-    if (!(p > 0.0)) return ctx->fail(GPSO_E_ARG, "likelihood parameter %g must be positive", p);
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
-    for (int k = 0; k < n_ls_; ++k)
-      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
-    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
+    if ((rc = theta_status(theta_refusal(th, d, true), "likelihood parameter"))) return rc;
     if ((rc = vgp_begin(true))) return rc;
     if ((rc = svgp_q())) return rc;
     if (rect) {
@@ -2200,7 +2190,7 @@ struct EngineT : Engine {
     }
     hipStream_t s = st();
     vgp_reset_info();
-    if ((rc = vgp_factor(kernel, ls, n_ls_, variance, mean_c))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
+    if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
     if (!rect) return GPSO_OK;
     launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
     launch_sgpr_cross_gram(s, as<double>(xs64), as<double>(sgXs), n, npad, sg_n, sg_npad, dp, kp, as<double>(sgKuf));
@@ -2241,10 +2231,10 @@ struct EngineT : Engine {
   // VGP's mixing and natural_to_meanvarsqrt at size M.  conj: the Gaussian step at noise variance p whatever the likelihood
   // (the conjugate start).  The new q is built in scratch and committed only when every factorisation held: a failed
   // step returns GPSO_E_NOTPD with q exactly as it was, for every likelihood.
-  int svgp_step(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double gamma, bool conj,
-                const char* who) {
+  int svgp_step(const Theta& th, double gamma, bool conj, const char* who) {
+    const double variance = th.variance, p = th.lik, mean_c = th.mean_c;
     if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
-    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, who, true);
+    int rc = svgp_begin(th, who, true);
     if (rc) return rc;
     hipStream_t s = st();
     const bool gauss = conj || vlik_kind == GPSO_LIK_GAUSSIAN;
@@ -2261,12 +2251,10 @@ struct EngineT : Engine {
     return launch_status();
   }
 
-  int svgp_natgrad(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double gamma) override {
-    return svgp_step(kernel, ls, n_ls_, variance, p, mean_c, gamma, false, "gpso_svgp_natgrad");
-  }
+  int svgp_natgrad(const Theta& th, double gamma) override { return svgp_step(th, gamma, false, "gpso_svgp_natgrad"); }
 
-  int svgp_init_q(int kernel, const double* ls, int n_ls_, double variance, double mean_c, double s2) override {
-    if (s2 > 0.0) return svgp_step(kernel, ls, n_ls_, variance, s2, mean_c, 1.0, true, "gpso_svgp_init_q");
+  int svgp_init_q(const Theta& th, double s2) override {
+    if (s2 > 0.0) return svgp_step(th.with_lik(s2), 1.0, true, "gpso_svgp_init_q");
     int rc = svgp_need_z("gpso_svgp_init_q");
     if (rc || (rc = vgp_begin()) || (rc = svgp_q())) return rc;
     svgp_prior();
@@ -2317,16 +2305,15 @@ struct EngineT : Engine {
   // (g = Lu^-T (I - Sigma) A diag(a), a' = Lu^-T mu), contracted tile by tile; d(-ELBO)/dLu = tril(Lu^-T Abar A^T) =
   // tril(T P + a' (A gm)^T) (T = Lu^-T (I - Sigma), P = A diag(a) A^T), taken to Kuu through the VGP's Cholesky backward
   // pass and the fit's contraction; the k_diag term sum dVE/dv = -sum a / 2 joins the variance.
-  int svgp_elbo(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double* loss,
-                double* grad) override {
-    return svgp_elbo_impl(kernel, ls, n_ls_, variance, p, mean_c, loss, grad, nullptr, "gpso_svgp_elbo_u");
+  int svgp_elbo(const Theta& th, double* loss, double* grad) override {
+    return svgp_elbo_impl(th, loss, grad, nullptr, "gpso_svgp_elbo_u");
   }
 
   // grad_z (nullable, with grad): also d(-ELBO)/dZ [M * D] at fixed q (whitened: q stays valid while Z moves; the k_diag
   // term does not depend on Z)
-  int svgp_elbo_impl(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, double* loss,
-                     double* grad, double* grad_z, const char* who) {
-    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, who, true);
+  int svgp_elbo_impl(const Theta& th, double* loss, double* grad, double* grad_z, const char* who) {
+    const double variance = th.variance, p = th.lik, mean_c = th.mean_c;
+    int rc = svgp_begin(th, who, true);
     if (rc) return rc;
     if (grad_z && (rc = inducing_buffers())) return rc;
     hipStream_t s = st();
@@ -2385,9 +2372,9 @@ struct EngineT : Engine {
 
   // install the predictive over the rows Z: the VGP's install with L := Lu and q := the SVGP's q (C = sqrt(1 + delta) R
   // Lu^-1 with I - S S^T / (1 + delta) = R^T R, beta = Lu^-T mu, noise := the likelihood's variance + delta variance)
-  int svgp_posterior(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c,
-                     double* delta_out) override {
-    int rc = svgp_begin(kernel, ls, n_ls_, variance, p, mean_c, "gpso_svgp_posterior", false);
+  int svgp_posterior(const Theta& th, double* delta_out) override {
+    const double p = th.lik;
+    int rc = svgp_begin(th, "gpso_svgp_posterior", false);
     if (rc) return rc;
     hipStream_t s = st();
     double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
@@ -2398,7 +2385,7 @@ struct EngineT : Engine {
     launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R Lu^-1
     HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
     const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? p * p * vlik_df / (vlik_df - 2.0) : p;
-    if ((rc = set_theta(kernel, ls, n_ls_, variance, noise + shift * variance, mean_c))) return rc;
+    if ((rc = set_theta(th.with_lik(noise + shift * th.variance)))) return rc;
     if ((rc = install_predictive(Post::Svgp))) return rc;
     if (delta_out) *delta_out = shift;
     return GPSO_OK;
@@ -2424,15 +2411,6 @@ struct EngineT : Engine {
         if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
     return GPSO_OK;
   }
-  int inducing_theta_args(int kernel, const double* ls, int n_ls_, double variance, double p, const char* what_p) {
-    if (!(p > 0.0)) return ctx->fail(GPSO_E_ARG, "%s %g must be positive", what_p, p);
-    if (kernel < 0 || kernel > 3) return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", kernel);
-    if (!ls || !(n_ls_ == 1 || n_ls_ == d)) return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", n_ls_, d);
-    for (int k = 0; k < n_ls_; ++k)
-      if (!(ls[k] > 0.0)) return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", k, ls[k]);
-    if (!(variance > 0.0)) return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", variance);
-    return GPSO_OK;
-  }
   int inducing_put(const double* Z) {
     const size_t doubles = (size_t)n * d;
     double* stage = doubles <= (1u << 17) ? ctx->pinned_stage(doubles) : nullptr;
@@ -2456,20 +2434,18 @@ struct EngineT : Engine {
     return inducing_put(Z);
   }
 
-  int sgpr_bound_z(int kernel, const double* ls, int n_ls_, double variance, double s2, double mean_c, const double* Z,
-                   double* loss, double* grad, double* grad_z) override {
+  int sgpr_bound_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) override {
     int rc = inducing_args("gpso_sgpr_bound_uz", Z);
-    if (rc || (rc = inducing_theta_args(kernel, ls, n_ls_, variance, s2, "noise variance"))) return rc;
+    if (rc || (rc = theta_status(theta_refusal(th, d, true), "noise variance"))) return rc;
     if (Z && (rc = inducing_put(Z))) return rc;
-    return sgpr_bound_impl(kernel, ls, n_ls_, variance, s2, mean_c, loss, grad, grad_z, "gpso_sgpr_bound_uz");
+    return sgpr_bound_impl(th, loss, grad, grad_z, "gpso_sgpr_bound_uz");
   }
 
-  int svgp_elbo_z(int kernel, const double* ls, int n_ls_, double variance, double p, double mean_c, const double* Z,
-                  double* loss, double* grad, double* grad_z) override {
+  int svgp_elbo_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) override {
     int rc = inducing_args("gpso_svgp_elbo_uz", Z);
-    if (rc || (rc = inducing_theta_args(kernel, ls, n_ls_, variance, p, "likelihood parameter"))) return rc;
+    if (rc || (rc = theta_status(theta_refusal(th, d, true), "likelihood parameter"))) return rc;
     if (Z && (rc = inducing_put(Z))) return rc;
-    return svgp_elbo_impl(kernel, ls, n_ls_, variance, p, mean_c, loss, grad, grad_z, "gpso_svgp_elbo_uz");
+    return svgp_elbo_impl(th, loss, grad, grad_z, "gpso_svgp_elbo_uz");
   }
 
   // ------------------------------------------------------------------------------------------
@@ -3961,6 +3937,38 @@ struct EngineT : Engine {
 
 }  // namespace
 
+// ---- the optimiser's vector u -> theta -> the engine, and the gradient back (theta.hpp) --------------------------------------
+// theta (theta.hpp) from the optimiser's vector u, or why not.  lik_floor: what stands in front of the softplus of slot n_ls + 1
+static int theta_of_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed, double lik_floor,
+                      Theta* th) {
+  switch (theta_from_u(kernel, u, n_ls, train_mean != 0, mean_c_fixed, lik_floor, th)) {
+    case ThetaDecode::NullU: return ctx->fail(GPSO_E_ARG, "u must not be NULL");
+    case ThetaDecode::NlsRange: return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
+    case ThetaDecode::Ok: break;
+  }
+  return GPSO_OK;
+}
+constexpr double kGaussianFloor = 1.0e-6;  // gpflow.likelihoods.Gaussian DEFAULT_VARIANCE_LOWER_BOUND
+// the VGP's and the SVGP's likelihood parameter: the Gaussian variance (1e-6 + softplus) or the Student-t scale (softplus,
+// GPflow's positive())
+static double vlik_floor(const gpso_ctx* ctx) { return ctx->eng->vlik_kind == GPSO_LIK_STUDENT_T ? 0.0 : kGaussianFloor; }
+// what the evaluations in u share behind their guards: decode, optional copy-out, engine call, chain rule.  eval(th, g): the
+// engine call, g the constrained gradient (NULL: none); want_g: a gradient is computed although grad_u is NULL (the moving-Z
+// calls' grad_z)
+template <typename Eval>
+static int eval_in_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed, double lik_floor,
+                     double* grad_u, bool want_g, double* theta_out, Eval eval) {
+  Theta th;
+  double g[kGradMaxLs + 3];
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, lik_floor, &th);
+  if (rc) return rc;
+  if (theta_out) theta_copy_out(th, theta_out);
+  rc = eval(th, (grad_u || want_g) ? g : nullptr);
+  if (rc != GPSO_OK || !grad_u) return rc;
+  grad_to_u(u, n_ls, train_mean != 0, g, grad_u);
+  return GPSO_OK;
+}
+
 // ==============================================================================================
 extern "C" {
 
@@ -4133,42 +4141,16 @@ int gpso_set_data(gpso_ctx* ctx, const double* X, const double* y, int64_t n, in
 int gpso_fit_eval(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_ls, double variance,
                   double noise, double mean_c, double* nlml, double* grad) {
   ENTER();
-  return ctx->eng->fit_eval(kernel, lengthscales, n_ls, variance, noise, mean_c, nlml, grad);
+  Theta th;
+  if (lengthscales) theta_from_parts(kernel, lengthscales, n_ls, variance, noise, mean_c, &th);
+  return ctx->eng->fit_eval(lengthscales ? &th : nullptr, nlml, grad);
 }
-
-// GPflow-2's parameter transforms, bit for bit what numpy computes for them on the host
-// side of the reference's optimiser loop: softplus(u) = logaddexp(0, u) in numpy's own case split (libm log1p / exp),
-// sigmoid(u) = (1 + tanh(u / 2)) / 2.
-static double gpso_softplus(double u) {
-  if (u == 0.0) return 0.693147180559945309417232121458176568;  // log 2
-  if (u < 0.0) return 0.0 + std::log1p(std::exp(u));
-  if (u > 0.0) return u + std::log1p(std::exp(-u));
-  return u;  // NaN
-}
-static double gpso_sigmoid(double u) { return 0.5 * (1.0 + std::tanh(0.5 * u)); }
 
 int gpso_fit_eval_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                     double* nlml, double* grad_u, double* theta_out) {
   ENTER();
-  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
-  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
-  double ls[kGradMaxLs], g[kGradMaxLs + 3];
-  for (int k = 0; k < n_ls; ++k) ls[k] = gpso_softplus(u[k]);
-  const double variance = gpso_softplus(u[n_ls]);
-  const double noise = 1.0e-6 + gpso_softplus(u[n_ls + 1]);  // gpflow.likelihoods.Gaussian DEFAULT_VARIANCE_LOWER_BOUND
-  const double mean_c = train_mean ? u[n_ls + 2] : mean_c_fixed;
-  if (theta_out) {
-    for (int k = 0; k < n_ls; ++k) theta_out[k] = ls[k];
-    theta_out[n_ls] = variance;
-    theta_out[n_ls + 1] = noise;
-    theta_out[n_ls + 2] = mean_c;
-  }
-  const int rc = ctx->eng->fit_eval(kernel, ls, n_ls, variance, noise, mean_c, nlml, grad_u ? g : nullptr);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  // chain rule: d/du = d/dtheta * sigmoid(u) for the softplus-transformed parameters, identity for the mean
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, kGaussianFloor, grad_u, false, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->fit_eval(&th, nlml, g); });
 }
 
 int gpso_loo(gpso_ctx* ctx, double* mean, double* var, double* lpd, double* loss) {
@@ -4179,31 +4161,16 @@ int gpso_loo(gpso_ctx* ctx, double* mean, double* var, double* lpd, double* loss
 int gpso_fit_eval_loo(gpso_ctx* ctx, int kernel, const double* lengthscales, int n_ls, double variance, double noise,
                       double mean_c, double* loss, double* grad, double* nlml) {
   ENTER();
-  return ctx->eng->fit_eval_loo(kernel, lengthscales, n_ls, variance, noise, mean_c, loss, grad, nlml);
+  Theta th;
+  if (lengthscales) theta_from_parts(kernel, lengthscales, n_ls, variance, noise, mean_c, &th);
+  return ctx->eng->fit_eval_loo(lengthscales ? &th : nullptr, loss, grad, nlml);
 }
 
 int gpso_fit_eval_loo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* loss, double* grad_u, double* theta_out, double* nlml) {
   ENTER();
-  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
-  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
-  // the transforms and the chain rule of gpso_fit_eval_u
-  double ls[kGradMaxLs], g[kGradMaxLs + 3];
-  for (int k = 0; k < n_ls; ++k) ls[k] = gpso_softplus(u[k]);
-  const double variance = gpso_softplus(u[n_ls]);
-  const double noise = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
-  const double mean_c = train_mean ? u[n_ls + 2] : mean_c_fixed;
-  if (theta_out) {
-    for (int k = 0; k < n_ls; ++k) theta_out[k] = ls[k];
-    theta_out[n_ls] = variance;
-    theta_out[n_ls + 1] = noise;
-    theta_out[n_ls + 2] = mean_c;
-  }
-  const int rc = ctx->eng->fit_eval_loo(kernel, ls, n_ls, variance, noise, mean_c, loss, grad_u ? g : nullptr, nlml);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, kGaussianFloor, grad_u, false, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->fit_eval_loo(&th, loss, g, nlml); });
 }
 
 int gpso_fit_batch_max(gpso_ctx* ctx) {
@@ -4225,24 +4192,16 @@ int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int
   std::vector<int> slot((size_t)b), info((size_t)b);
   int nv = 0, first_bad = -1;
   for (int e = 0; e < b; ++e) {
-    const double* u = U + (size_t)e * nu;
-    double* t = th.data() + (size_t)nv * H;
-    bool ok = true;
-    for (int k = 0; k < n_ls; ++k) {
-      t[k] = gpso_softplus(u[k]);
-      ok = ok && (t[k] > 0.0);
-    }
-    t[n_ls] = gpso_softplus(u[n_ls]);
-    ok = ok && (t[n_ls] > 0.0);
-    t[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
-    t[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
-    slot[e] = ok ? nv++ : -1;
+    Theta t;
+    (void)theta_from_u(kernel, U + (size_t)e * nu, n_ls, train_mean != 0, mean_c_fixed, kGaussianFloor, &t);
+    theta_copy_out(t, th.data() + (size_t)nv * H);
+    // (the kernel id and n_ls passed the check above: with D := n_ls only the values are left to refuse)
+    slot[e] = theta_refusal(t, n_ls, false) ? -1 : nv++;
   }
   if (nv > 0 && (rc = ctx->eng->fit_eval_batch(kernel, th.data(), nv, n_ls, f.data(), grad_u ? g.data() : nullptr, info.data())))
     return rc;
   const double nan = std::numeric_limits<double>::quiet_NaN();
   for (int e = 0; e < b; ++e) {
-    const double* u = U + (size_t)e * nu;
     const int v = slot[e];
     const bool fine = v >= 0 && info[v] == INT_MAX;
     status[e] = fine ? GPSO_OK : (v < 0 ? GPSO_E_ARG : GPSO_E_NOTPD);
@@ -4251,13 +4210,9 @@ int gpso_fit_eval_u_batch(gpso_ctx* ctx, int kernel, const double* U, int b, int
     if (!fine && first_bad < 0) first_bad = e;
     if (!grad_u) continue;
     double* gu = grad_u + (size_t)e * nu;
-    if (!fine) {
+    if (fine) grad_to_u(U + (size_t)e * nu, n_ls, train_mean != 0, g.data() + (size_t)v * H, gu);
+    else
       for (int k = 0; k < nu; ++k) gu[k] = nan;
-      continue;
-    }
-    const double* ge = g.data() + (size_t)v * H;
-    for (int k = 0; k < n_ls + 2; ++k) gu[k] = ge[k] * gpso_sigmoid(u[k]);
-    if (train_mean) gu[n_ls + 2] = ge[n_ls + 2];
   }
   if (first_bad >= 0) {
     if (slot[first_bad] < 0)
@@ -4297,22 +4252,13 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
                        int64_t n, int d, int kernel, const double* lengthscales, int n_ls,
                        double variance, double noise, double mean_c) {
   ENTER();
-  return ctx->eng->set_posterior(X, L, alpha, n, d, kernel, lengthscales, n_ls, variance, noise, mean_c);
+  if (!lengthscales) return ctx->fail(GPSO_E_ARG, "NULL argument");  // (with X, L and alpha: the engine's first check)
+  Theta th;
+  theta_from_parts(kernel, lengthscales, n_ls, variance, noise, mean_c, &th);
+  return ctx->eng->set_posterior(X, L, alpha, n, d, th);
 }
 
 // ---- variational GP --------------------------------------------------------------------------------------------
-// theta from the optimiser's vector u, GPflow's transforms (as gpso_fit_eval_u); th[n_ls + 3] = (ls..., variance, s2, c)
-static int vgp_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, double mean_c_fixed, double* th) {
-  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
-  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
-  for (int k = 0; k < n_ls; ++k) th[k] = gpso_softplus(u[k]);
-  th[n_ls] = gpso_softplus(u[n_ls]);
-  // the likelihood's parameter: the Gaussian variance (1e-6 + softplus) or the Student-t scale (softplus, GPflow's positive())
-  th[n_ls + 1] = (ctx->eng->vlik_kind == GPSO_LIK_STUDENT_T ? 0.0 : 1.0e-6) + gpso_softplus(u[n_ls + 1]);
-  th[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
-  return GPSO_OK;
-}
-
 int gpso_vgp_set_likelihood(gpso_ctx* ctx, int kind, double df, int n_gh, const double* gh_x, const double* gh_w) {
   ENTER();
   return ctx->eng->vgp_set_likelihood(kind, df, n_gh, gh_x, gh_w);
@@ -4340,10 +4286,10 @@ int gpso_vgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
                      double gamma) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
   if (rc) return rc;
-  return ctx->eng->vgp_natgrad(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], gamma);
+  return ctx->eng->vgp_natgrad(th, gamma);
 }
 
 int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
@@ -4351,37 +4297,20 @@ int gpso_vgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int tr
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
-  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
-  if (rc) return rc;
-  if (theta_out)
-    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
-  rc = ctx->eng->vgp_elbo(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), grad_u, false, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->vgp_elbo(th, loss, g); });
 }
 
 int gpso_vgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
   if (rc) return rc;
-  return ctx->eng->vgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2]);
+  return ctx->eng->vgp_posterior(th);
 }
 
 // ---- sparse GP regression on inducing points ---------------------------------------------------------------------
-static int sgpr_theta(gpso_ctx* ctx, const double* u, int n_ls, int train_mean, double mean_c_fixed, double* th) {
-  if (!u) return ctx->fail(GPSO_E_ARG, "u must not be NULL");
-  if (n_ls < 1 || n_ls > kGradMaxLs) return ctx->fail(GPSO_E_ARG, "n_ls=%d outside [1, %d]", n_ls, kGradMaxLs);
-  for (int k = 0; k <= n_ls; ++k) th[k] = gpso_softplus(u[k]);
-  th[n_ls + 1] = 1.0e-6 + gpso_softplus(u[n_ls + 1]);
-  th[n_ls + 2] = train_mean ? u[n_ls + 2] : mean_c_fixed;
-  return GPSO_OK;
-}
-
 int gpso_sgpr_set_inducing(gpso_ctx* ctx, const double* Z, int64_t m) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
@@ -4391,10 +4320,10 @@ int gpso_sgpr_set_inducing(gpso_ctx* ctx, const double* Z, int64_t m) {
 int gpso_sgpr_select_inducing(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int64_t m, int64_t* idx_out) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = sgpr_theta(ctx, u, n_ls, 0, 0.0, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, 0, 0.0, kGaussianFloor, &th);
   if (rc) return rc;
-  return ctx->eng->sgpr_select_inducing(kernel, th, n_ls, th[n_ls], m, idx_out);
+  return ctx->eng->sgpr_select_inducing(th, m, idx_out);
 }
 
 int gpso_sgpr_get_inducing(gpso_ctx* ctx, double* Z, int64_t* m, int64_t* n_data) {
@@ -4412,38 +4341,30 @@ int gpso_sgpr_bound_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
-  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
-  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
-  if (rc) return rc;
-  if (theta_out)
-    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
-  rc = ctx->eng->sgpr_bound(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, kGaussianFloor, grad_u, false, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->sgpr_bound(th, loss, g); });
 }
 
 int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, kGaussianFloor, &th);
   if (rc) return rc;
-  return ctx->eng->sgpr_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
+  return ctx->eng->sgpr_posterior(th, delta_out);
 }
 
-// ---- sparse variational GP on inducing points (theta from u as the VGP's: vgp_theta) ------------------------------------
+// ---- sparse variational GP on inducing points (theta from u as the VGP's: vlik_floor) ------------------------------------
 int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double noise_variance) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  if (!(noise_variance > 0.0)) return ctx->eng->svgp_init_q(0, nullptr, 0, 0.0, 0.0, 0.0);  // the prior
-  double th[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th{};
+  if (!(noise_variance > 0.0)) return ctx->eng->svgp_init_q(th, 0.0);  // the prior
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
   if (rc) return rc;
-  return ctx->eng->svgp_init_q(kernel, th, n_ls, th[n_ls], th[n_ls + 2], noise_variance);
+  return ctx->eng->svgp_init_q(th, noise_variance);
 }
 
 int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m) {
@@ -4462,10 +4383,10 @@ int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
                       double gamma) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
   if (rc) return rc;
-  return ctx->eng->svgp_natgrad(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], gamma);
+  return ctx->eng->svgp_natgrad(th, gamma);
 }
 
 int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
@@ -4473,26 +4394,18 @@ int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
-  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
-  if (rc) return rc;
-  if (theta_out)
-    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
-  rc = ctx->eng->svgp_elbo(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], loss, grad_u ? g : nullptr);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), grad_u, false, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->svgp_elbo(th, loss, g); });
 }
 
 int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out) {
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
-  double th[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
+  Theta th;
+  int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
   if (rc) return rc;
-  return ctx->eng->svgp_posterior(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], delta_out);
+  return ctx->eng->svgp_posterior(th, delta_out);
 }
 
 // ---- the sparse models at a moving Z ------------------------------------------------------------------------------------
@@ -4507,17 +4420,8 @@ int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
-  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
-  int rc = sgpr_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
-  if (rc) return rc;
-  if (theta_out)
-    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
-  const bool want = grad_u || grad_z;
-  rc = ctx->eng->sgpr_bound_z(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], Z, loss, want ? g : nullptr, grad_z);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, kGaussianFloor, grad_u, grad_z != nullptr, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->sgpr_bound_z(th, Z, loss, g, grad_z); });
 }
 
 int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
@@ -4525,17 +4429,8 @@ int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
   ENTER();
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
-  double th[kGradMaxLs + 3], g[kGradMaxLs + 3];
-  int rc = vgp_theta(ctx, u, n_ls, train_mean, mean_c_fixed, th);
-  if (rc) return rc;
-  if (theta_out)
-    for (int k = 0; k < n_ls + 3; ++k) theta_out[k] = th[k];
-  const bool want = grad_u || grad_z;
-  rc = ctx->eng->svgp_elbo_z(kernel, th, n_ls, th[n_ls], th[n_ls + 1], th[n_ls + 2], Z, loss, want ? g : nullptr, grad_z);
-  if (rc != GPSO_OK || !grad_u) return rc;
-  for (int k = 0; k < n_ls + 2; ++k) grad_u[k] = g[k] * gpso_sigmoid(u[k]);
-  if (train_mean) grad_u[n_ls + 2] = g[n_ls + 2];
-  return GPSO_OK;
+  return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), grad_u, grad_z != nullptr, theta_out,
+                   [&](const Theta& th, double* g) { return ctx->eng->svgp_elbo_z(th, Z, loss, g, grad_z); });
 }
 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,

@@ -219,6 +219,43 @@ class HipGPEngine:
         ls = L.as_f64(np.atleast_1d(lengthscales))
         return kid, ls, int(ls.shape[0]), float(variance), float(noise), float(mean_c)
 
+    @staticmethod
+    def _u_args(kernel, u, n_ls, train_mean, mean_c_fixed, grad=False, theta=False):
+        """What every entry point in the optimiser's variables takes: -> (kernel id, u, n_ls, train_mean, mean_c_fixed) as the
+        C call wants them, then the ``grad_u`` and ``theta`` output arrays (None where not asked for)."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        ua = L.as_f64(np.asarray(u).reshape(-1))  # (the returned pointer keeps it alive: ctypes' data_as holds its array)
+        ga = np.empty(int(n_ls) + 2 + (1 if train_mean else 0), dtype=np.float64) if grad else None
+        ta = np.empty(int(n_ls) + 3, dtype=np.float64) if theta else None
+        return (kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0, float(mean_c_fixed)), ga, ta
+
+    def _u_cached(self, fn, kernel, u, n_ls, train_mean, mean_c_fixed, n_loss):
+        """``fit_eval_u`` / ``fit_eval_loo_u``: the optimiser's inner loop, so the marshalling buffers are made once per
+        entry point and problem shape.  -> the ``n_loss`` scalars the call returns, grad_u, theta."""
+        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
+        key = (n_loss, int(n_ls), bool(train_mean))  # (n_u alone is ambiguous: theta_out has n_ls + 3 entries whatever train_mean)
+        buf = self._u_bufs.get(key)
+        if buf is None:
+            ua, ga = (np.empty(int(n_ls) + 2 + (1 if train_mean else 0), dtype=np.float64) for _ in range(2))
+            ta = np.empty(int(n_ls) + 3, dtype=np.float64)
+            out = [C.c_double() for _ in range(n_loss)]
+            # (the C argument lists: ..., loss, grad_u, theta and then any further scalar)
+            tail = (C.byref(out[0]), L.dptr(ga), L.dptr(ta)) + tuple(C.byref(o) for o in out[1:])
+            buf = self._u_bufs[key] = (ua, ga, ta, out, L.dptr(ua), tail)
+        ua, ga, ta, out, up, tail = buf
+        ua[:] = u
+        rc = fn(self._h, kid, up, int(n_ls), 1 if train_mean else 0, float(mean_c_fixed), *tail)
+        if rc < 0:
+            self._check(rc)
+        return [o.value for o in out], ga.copy(), ta.copy()
+
+    def _eval_u(self, fn, kernel, u, n_ls, train_mean, mean_c_fixed, want_grad):
+        """A family's loss at fixed q (and Z) in ``u``: -> (loss, grad_u or None, theta)."""
+        args, ga, ta = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed, grad=want_grad, theta=True)
+        loss = C.c_double()
+        self._check(fn(self._h, *args, C.byref(loss), L.dptr(ga) if want_grad else None, L.dptr(ta)))
+        return loss.value, ga, ta
+
     def fit_eval(self, kernel, lengthscales, variance, noise, mean_c, want_grad=True):
         """One NLML (+ gradient w.r.t. the constrained hyper-parameters) evaluation; leaves the
         posterior resident.  Returns (nlml, grad or None); grad order (ls..., variance, noise, c)."""
@@ -232,22 +269,8 @@ class HipGPEngine:
     def fit_eval_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
         """One loss evaluation in the optimiser's unconstrained variables (``gpso_fit_eval_u``: transforms and chain
         rule inside the library).  Returns (nlml, grad_u, theta): theta = constrained (ls..., variance, noise, mean)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        key = (int(n_ls), bool(train_mean))  # (n_u alone is ambiguous: theta_out has n_ls + 3 entries whatever train_mean)
-        buf = self._u_bufs.get(key)
-        if buf is None:  # marshalling buffers are made once per problem shape: this call is the optimiser's inner loop
-            ua = np.empty(n_u, dtype=np.float64)
-            ga = np.empty(n_u, dtype=np.float64)
-            ta = np.empty(int(n_ls) + 3, dtype=np.float64)
-            nl = C.c_double()
-            buf = self._u_bufs[key] = (ua, ga, ta, nl, L.dptr(ua), L.dptr(ga), L.dptr(ta), C.byref(nl))
-        ua, ga, ta, nl, up, gp, tp, nlp = buf
-        ua[:] = u
-        rc = self._lib.gpso_fit_eval_u(self._h, kid, up, int(n_ls), 1 if train_mean else 0, float(mean_c_fixed), nlp, gp, tp)
-        if rc < 0:
-            self._check(rc)
-        return nl.value, ga.copy(), ta.copy()
+        (nlml,), grad_u, theta = self._u_cached(self._lib.gpso_fit_eval_u, kernel, u, n_ls, train_mean, mean_c_fixed, 1)
+        return nlml, grad_u, theta
 
     # -- leave-one-out (include/gpso_hip.h: gpso_loo, gpso_fit_eval_loo*; no counterpart in the reference) -----------------
     def loo(self):
@@ -276,23 +299,8 @@ class HipGPEngine:
 
     def fit_eval_loo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
         """``fit_eval_u`` for the LOO-CV loss (``gpso_fit_eval_loo_u``).  Returns (loss, grad_u, theta, nlml)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        key = ("loo", int(n_ls), bool(train_mean))
-        buf = self._u_bufs.get(key)
-        if buf is None:  # (as fit_eval_u: made once per problem shape)
-            ua = np.empty(n_u, dtype=np.float64)
-            ga = np.empty(n_u, dtype=np.float64)
-            ta = np.empty(int(n_ls) + 3, dtype=np.float64)
-            fl, nl = C.c_double(), C.c_double()
-            buf = self._u_bufs[key] = (ua, ga, ta, fl, nl, L.dptr(ua), L.dptr(ga), L.dptr(ta), C.byref(fl), C.byref(nl))
-        ua, ga, ta, fl, nl, up, gp, tp, flp, nlp = buf
-        ua[:] = u
-        rc = self._lib.gpso_fit_eval_loo_u(self._h, kid, up, int(n_ls), 1 if train_mean else 0, float(mean_c_fixed), flp, gp,
-                                           tp, nlp)
-        if rc < 0:
-            self._check(rc)
-        return fl.value, ga.copy(), ta.copy(), nl.value
+        (loss, nlml), grad_u, theta = self._u_cached(self._lib.gpso_fit_eval_loo_u, kernel, u, n_ls, train_mean, mean_c_fixed, 2)
+        return loss, grad_u, theta, nlml
 
     def fit_batch_max(self):
         """Entries one ``gpso_fit_eval_u_batch`` call may hold for the resident data (256 where the one-launch fit applies,
@@ -399,30 +407,17 @@ class HipGPEngine:
 
     def vgp_natgrad(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, gamma=1.0):
         """One natural-gradient step of length ``gamma`` on q at the theta of ``u``."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        self._check(self._lib.gpso_vgp_natgrad(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                               float(mean_c_fixed), float(gamma)))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
+        self._check(self._lib.gpso_vgp_natgrad(self._h, *args, float(gamma)))
 
     def vgp_elbo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
         """-ELBO at fixed q and its gradient in ``u``.  Returns (loss, grad_u or None, theta)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
-        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
-        loss = C.c_double()
-        self._check(self._lib.gpso_vgp_elbo_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                              float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
-                                              L.dptr(ta)))
-        return loss.value, ga, ta
+        return self._eval_u(self._lib.gpso_vgp_elbo_u, kernel, u, n_ls, train_mean, mean_c_fixed, want_grad)
 
     def vgp_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
         """Install the VGP predictive at the theta of ``u`` as the resident posterior."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        self._check(self._lib.gpso_vgp_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                                 float(mean_c_fixed)))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
+        self._check(self._lib.gpso_vgp_posterior(self._h, *args))
 
     # -- sparse GP regression on inducing points (include/gpso_hip.h: gpso_sgpr_*) ----------------
     def sgpr_set_inducing(self, Z):
@@ -436,11 +431,9 @@ class HipGPEngine:
     def sgpr_select_inducing(self, kernel, u, n_ls, m):
         """Greedy conditional-variance selection of ``m`` training rows on the device at the kernel hyper-parameters of
         ``u``; they become Z.  Returns their indices in pick order."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
+        (kid, up, n_ls, _, _), _, _ = self._u_args(kernel, u, n_ls, False, 0.0)
         idx = np.empty(int(m), dtype=np.int64)
-        self._check(self._lib.gpso_sgpr_select_inducing(self._h, kid, L.dptr(ua), int(n_ls), int(m),
-                                                        idx.ctypes.data_as(C.POINTER(C.c_int64))))
+        self._check(self._lib.gpso_sgpr_select_inducing(self._h, kid, up, n_ls, int(m), L.i64ptr(idx)))
         self.n = int(m)
         return idx
 
@@ -466,24 +459,13 @@ class HipGPEngine:
 
     def sgpr_bound_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
         """-bound (Titsias) and its gradient in ``u``, Z fixed.  Returns (loss, grad_u or None, theta)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
-        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
-        loss = C.c_double()
-        self._check(self._lib.gpso_sgpr_bound_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                                float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
-                                                L.dptr(ta)))
-        return loss.value, ga, ta
+        return self._eval_u(self._lib.gpso_sgpr_bound_u, kernel, u, n_ls, train_mean, mean_c_fixed, want_grad)
 
     def sgpr_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
         """Install the SGPR predictive at the theta of ``u`` over the rows Z.  Returns the shift delta (0: exact)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
         delta = C.c_double()
-        self._check(self._lib.gpso_sgpr_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                                  float(mean_c_fixed), C.byref(delta)))
+        self._check(self._lib.gpso_sgpr_posterior(self._h, *args, C.byref(delta)))
         return delta.value
 
     # -- sparse variational GP on inducing points (include/gpso_hip.h: gpso_svgp_*; Z from sgpr_set / select_inducing) -----
@@ -493,10 +475,8 @@ class HipGPEngine:
         if not noise_variance > 0.0:
             self._check(self._lib.gpso_svgp_init_q(self._h, 0, None, 0, 0, 0.0, 0.0))
             return
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        self._check(self._lib.gpso_svgp_init_q(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                               float(mean_c_fixed), float(noise_variance)))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
+        self._check(self._lib.gpso_svgp_init_q(self._h, *args, float(noise_variance)))
 
     def svgp_set_q(self, mu=None, S=None):
         """q(v) = N(mu, S S^T) over the M inducing values; None, None: the prior."""
@@ -516,31 +496,18 @@ class HipGPEngine:
 
     def svgp_natgrad(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, gamma=1.0):
         """One natural-gradient step of length ``gamma`` on the SVGP's q at the theta of ``u``."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        self._check(self._lib.gpso_svgp_natgrad(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                                float(mean_c_fixed), float(gamma)))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
+        self._check(self._lib.gpso_svgp_natgrad(self._h, *args, float(gamma)))
 
     def svgp_elbo_u(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0, want_grad=True):
         """-ELBO of the SVGP at fixed q and Z and its gradient in ``u``.  Returns (loss, grad_u or None, theta)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
-        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
-        loss = C.c_double()
-        self._check(self._lib.gpso_svgp_elbo_u(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                               float(mean_c_fixed), C.byref(loss), L.dptr(ga) if want_grad else None,
-                                               L.dptr(ta)))
-        return loss.value, ga, ta
+        return self._eval_u(self._lib.gpso_svgp_elbo_u, kernel, u, n_ls, train_mean, mean_c_fixed, want_grad)
 
     def svgp_posterior(self, kernel, u, n_ls, train_mean, mean_c_fixed=0.0):
         """Install the SVGP predictive at the theta of ``u`` over the rows Z.  Returns the shift delta (0: exact)."""
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
+        args, _, _ = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed)
         delta = C.c_double()
-        self._check(self._lib.gpso_svgp_posterior(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0,
-                                                  float(mean_c_fixed), C.byref(delta)))
+        self._check(self._lib.gpso_svgp_posterior(self._h, *args, C.byref(delta)))
         return delta.value
 
     # -- the sparse models at a moving Z (include/gpso_hip.h: gpso_sgpr_move_inducing, gpso_sgpr_bound_uz, gpso_svgp_elbo_uz) --
@@ -558,16 +525,11 @@ class HipGPEngine:
         self._check(self._lib.gpso_sgpr_move_inducing(self._h, L.dptr(Z) if Z is not None else None))
 
     def _eval_uz(self, fn, kernel, u, n_ls, train_mean, mean_c_fixed, Z, want_grad):
-        kid = L.KERNEL_IDS[kernel] if isinstance(kernel, str) else int(kernel)
-        ua = L.as_f64(np.asarray(u).reshape(-1))
+        args, ga, ta = self._u_args(kernel, u, n_ls, train_mean, mean_c_fixed, grad=want_grad, theta=True)
         Z = self._z_arg(Z)
-        n_u = int(n_ls) + 2 + (1 if train_mean else 0)
-        ga = np.empty(n_u, dtype=np.float64) if want_grad else None
         gz = np.empty((self.n, self.d), dtype=np.float64) if want_grad else None
-        ta = np.empty(int(n_ls) + 3, dtype=np.float64)
         loss = C.c_double()
-        self._check(fn(self._h, kid, L.dptr(ua), int(n_ls), 1 if train_mean else 0, float(mean_c_fixed),
-                       L.dptr(Z) if Z is not None else None, C.byref(loss), L.dptr(ga) if want_grad else None,
+        self._check(fn(self._h, *args, L.dptr(Z) if Z is not None else None, C.byref(loss), L.dptr(ga) if want_grad else None,
                        L.dptr(gz) if want_grad else None, L.dptr(ta)))
         return loss.value, ga, gz, ta
 

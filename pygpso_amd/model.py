@@ -30,7 +30,7 @@ FIT_ESCALATION = {"float32": "mixed"}
 
 def _softplus1(u):
     """softplus(u) = numpy's ``logaddexp(0, u)``, spelled out with its case split on libm's log1p / exp (what numpy's
-    scalar loop calls) so that this module and ``gpso_fit_eval_u`` (csrc/api.hip: gpso_softplus) give the same bits."""
+    scalar loop calls) so that this module and ``gpso_fit_eval_u`` (csrc/theta.hpp: gpso_softplus) give the same bits."""
     if u == 0.0:
         return 0.693147180559945309417232121458176568
     if u < 0.0:
@@ -53,7 +53,7 @@ def _softplus_inv(x):
 
 
 def _sigmoid(u):
-    """(1 + tanh(u / 2)) / 2 on libm's tanh (the same bits as csrc/api.hip: gpso_sigmoid)."""
+    """(1 + tanh(u / 2)) / 2 on libm's tanh (the same bits as csrc/theta.hpp: gpso_sigmoid)."""
     u = np.asarray(u, dtype=np.float64)
     return np.array([0.5 * (1.0 + math.tanh(0.5 * float(v))) for v in u.ravel()], dtype=np.float64).reshape(u.shape)
 

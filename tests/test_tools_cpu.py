@@ -114,3 +114,29 @@ _Z4ringv:
     assert any(l.startswith("by design") and "_Z4ringv" in l for l in r.stdout.splitlines())
     p.write_text(good + ring)
     assert subprocess.run([sys.executable, tool, "--allow=ringv", str(p)], capture_output=True, text=True).returncode == 0
+
+
+def test_theta_header_on_its_own_and_its_python_twins(tmp_path):
+    """tools/theta_check.cpp -- csrc/theta.hpp compiled by the host compiler alone -- passes its own checks (decoder,
+    copy-out, chain rule, every rule of the validator), and pygpso_amd/model.py's _softplus1 / _sigmoid reproduce the bits
+    it prints for softplus(u), 1e-6 + softplus(u) and sigmoid(u) at 432 values of u (both branches, the ends of exp's
+    range, +-inf)."""
+    import shutil
+    import struct
+
+    from pygpso_amd.model import _sigmoid, _softplus1
+
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    exe = str(tmp_path / "theta_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tools", "theta_check.cpp"),
+                    "-o", exe], check=True)
+    lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split("\n")[:-1]
+    assert len(lines) == 432
+
+    def h(x):
+        return struct.pack(">d", x).hex()
+
+    for line in lines:
+        u = struct.unpack(">d", bytes.fromhex(line.split()[0]))[0]
+        s = _softplus1(u)
+        assert line == f"{h(u)} {h(s)} {h(1.0e-6 + s)} {h(float(_sigmoid(u)))}", u

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Do two builds of libgpso_hip.so give the SAME BITS?  Every library named on the command line predicts the same leaves
 from the same posteriors in a fresh process (a list of engine configurations x shapes); the SHA-1 of mean and variance
-are printed side by side, differing rows marked.
+are printed side by side, differing rows marked.  A last section hashes (loss, grad_u, theta) of every entry point in the
+optimiser's variables u (and of the batch) at the shapes of tests/test_gpu_theta.py; --theta runs that section alone.
 
-    python tools/ab_bits.py pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
+    python tools/ab_bits.py [--theta] pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
 """
 import hashlib
 import json
@@ -25,6 +26,37 @@ CASES = [  # dtype, math, generation, contraction (None: leave the default)
 SHAPES = [(256, 6, 1000, "Matern52"), (2048, 12, 4096, "Matern52"), (768, 20, 700, "Matern32"), (512, 40, 513, "SquaredExponential")]
 
 
+def theta_section(out):
+    """(loss, grad_u, theta) of the calls in u: the exact GP on every engine type, the families on float64."""
+    import numpy as np
+
+    from tests import test_gpu_theta as T
+
+    def put(name, *parts):
+        out[name] = hashlib.sha1(b"".join(np.asarray(p, dtype=np.float64).tobytes() for p in parts)).hexdigest()[:12]
+
+    Z = T._problem()[2]
+    exact = {dtype: T._engine(dtype) for dtype in ("float64", "float32", "mixed")}
+    family = [(entry, lik, T._engine("float64", lik, inducing=not entry.startswith("vgp"))) for entry, lik in T.FAMILY]
+    for n_ls, train_mean in T.SHAPES:
+        for which in ("ordinary", "branches"):
+            u, tag = T._u(n_ls, train_mean, which), f"n_ls={n_ls} mean={int(train_mean)} {which}"
+            for dtype, eng in exact.items():
+                put(f"fit_eval_u {dtype} {tag}", *eng.fit_eval_u(T.KERNEL, u, n_ls, train_mean, 0.375))
+                if dtype != "float32":
+                    put(f"fit_eval_loo_u {dtype} {tag}", *eng.fit_eval_loo_u(T.KERNEL, u, n_ls, train_mean, 0.375))
+            for entry, lik, eng in family:
+                res = getattr(eng, entry)(T.KERNEL, u, n_ls, train_mean, 0.375, **({"Z": Z} if entry.endswith("uz") else {}))
+                put(f"{entry} {lik[0]} {tag}", *res)
+        a, b = T._u(n_ls, train_mean, "ordinary"), T._u(n_ls, train_mean, "branches")
+        bad = a.copy()
+        bad[n_ls - 1] = -800.0
+        put(f"fit_eval_u_batch n_ls={n_ls} mean={int(train_mean)}",
+            *exact["float64"].fit_eval_u_batch(T.KERNEL, np.stack([a, b, bad, 0.5 * (a + b), a + 0.25]), n_ls, train_mean, 0.375))
+    for eng in list(exact.values()) + [f[2] for f in family]:
+        eng.close()
+
+
 def worker():
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -33,6 +65,10 @@ def worker():
     from tests.helpers import synthetic_leaves, synthetic_problem
 
     out = {}
+    if "--theta" in sys.argv:
+        theta_section(out)
+        print("AB_BITS " + json.dumps(out), flush=True)
+        return
     for n, d, m, kernel in SHAPES:
         X, y = synthetic_problem(n, d, seed=1)
         Xs = synthetic_leaves(m, d, seed=3)
@@ -70,17 +106,19 @@ def worker():
                          + (eng.get_matrix(L.MAT_LINV)[n - k:].tobytes() if n <= 4096 else b"")).hexdigest()[:12]
         out[f"append N{n - k}+{k} D{d} {dtype} in_place={in_place}"] = h
         eng.close()
+    theta_section(out)
     print("AB_BITS " + json.dumps(out), flush=True)
 
 
 def main():
     if "--worker" in sys.argv:
         return worker()
-    libs = sys.argv[1:]
+    libs = [a for a in sys.argv[1:] if not a.startswith("--")]
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
     res = []
     for lib in libs:
         env = dict(os.environ, GPSO_HIP_LIB=os.path.abspath(lib), GPSO_HIP_LIB_OLDER="1")
-        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"], env=env, capture_output=True, text=True)
+        p = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + flags, env=env, capture_output=True, text=True)
         line = [l for l in p.stdout.splitlines() if l.startswith("AB_BITS ")]
         if not line:
             print(lib, "FAILED", p.stderr[-1500:])
