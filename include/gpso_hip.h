@@ -479,6 +479,28 @@ int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
 int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,
                  double* var, int out_mem);
 
+/* No counterpart in the reference (a GPflow user differentiates predict_f / predict_y by tf.GradientTape).
+ * gpso_predict's mean and var at the m test points AND their gradients in the test points' coordinates, as passed (not
+ * scaled by the lengthscales): with xs = x / l, r2_i = |xs* - xs_i|^2 formed from direct differences in double, k_i =
+ * k(r2_i), k'_i = dk/dr2, v = C k*, w = C^T v,
+ *   mean = alpha^T k* + c,  var = variance - |v|^2 + noise (noise INCLUDED, as gpso_predict),
+ *   dmean/dx*_d = sum_i alpha_i g_id,  dvar/dx*_d = -2 sum_i w_i g_id,  g_id = 2 k'_i (xs*_d - xs_i,d) / l_d
+ * (DESIGN.md section 7h).  A pair with r2 <= 1e-36 contributes zero to the gradients: exact for the squared exponential and
+ * the Matern-3/2 and -5/2, the convention at the Matern-1/2's kink (as gpso_sgpr_bound_uz).
+ * xs, xs_dtype, xs_mem, out_mem as gpso_predict; mean[m], var[m], dmean[m * D], dvar[m * D] (row-major) float64 living in
+ * out_mem, each nullable.  Reads the dense fit-type factor (GPSO_MAT_LINV), so every output is double-class on GPSO_F64 AND
+ * GPSO_MIXED contexts, also where gpso_predict is float-class; GPSO_F32: GPSO_E_ARG.  Serves every resident posterior that
+ * has its dense factor: fitted (after gpso_append / gpso_append_noise too), gpso_set_posterior, gpso_vgp_posterior,
+ * gpso_sgpr_posterior and gpso_svgp_posterior (the sparse ones over the rows Z, a shift delta included as installed).
+ * GPSO_E_STATE: no posterior, a posterior from a hand-off (the dense factor may not have travelled), or an asynchronous
+ * best-UCB ticket open.  GPSO_E_ARG: a GPSO_F32 context, m < 1, xs NULL, or all four outputs NULL.
+ * Reads only: the posterior, its packed copies and the hyper block stay bit for bit; the precision self-test is neither run
+ * nor consumed; the same call gives the same bits, and a test point's bits do not depend on the rest of the batch.
+ * gpso_last_ms(ctx, 1) covers the call when timing is on; gpso_last_count(ctx, 0) and (ctx, 1) are m, as after gpso_predict. */
+int gpso_predict_grad(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m,
+                      double* mean /* [m], nullable */, double* var /* [m], nullable */,
+                      double* dmean /* [m*D] row-major, nullable */, double* dvar /* [m*D], nullable */, int out_mem);
+
 /* Replaces: GPSurrogate.gp_eval_best_ucb (gpso/gp_surrogate.py:313-328): predict_y, then
  * ucb = mean + varsigma * VAR, then first arg-max -- per segment.  seg_off[nseg+1] (host) delimits
  * independent leaf batches (NULL with nseg = 1 means one segment [0, M)); outputs (host, nseg each):

@@ -91,6 +91,9 @@ struct Engine {
   virtual int append(const double* Xnew, const double* ynew, const double* snew, int64_t k, double* nlml) = 0;
   virtual int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,
                       double* var, int out_mem) = 0;
+  // mean, var and their gradients in the test points, from the dense factor (predict_grad.hip)
+  virtual int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean,
+                           double* dvar, int out_mem) = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
                        int nseg, double varsigma, int64_t* idx, double* mean, double* var,
                        double* ucb) = 0;
@@ -448,6 +451,7 @@ struct EngineT : Engine {
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
+  DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -460,7 +464,7 @@ struct EngineT : Engine {
                       &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
                       &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
                       &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag, &loov, &loo_scal})
+                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag, &loov, &loo_scal, &pg_ts, &pg_norm, &pg_work, &pg_out})
       if (b->p && !b->view) (void)hipFree(b->p);
   }
 
@@ -2801,6 +2805,78 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
+  // ---- mean, var and their gradients in the test points (predict_grad.hip).  Reads the dense fit-type
+  // factor, alpha_f, xs64 and the hyper block and writes buffers of its own only: the posterior, its packed copies and the
+  // self-test's verdicts stay as they are.  M is worked off in chunks of kPredictGradChunk, so the workspace is a few
+  // N_pad x chunk doubles whatever M is
+  int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean, double* dvar,
+                   int out_mem) override {
+    if constexpr (sizeof(TF) != 8) {
+      return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs a GPSO_F64 or GPSO_MIXED context (the dense factor in double)");
+    } else {
+      ctx->tick_timing();
+      if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs at least one test point (m=%lld)", (long long)m);
+      if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+      if (!mean && !var && !dmean && !dvar) return ctx->fail(GPSO_E_ARG, "mean, var, dmean and dvar are all NULL");
+      if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
+      if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
+      if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+      if (res.post == Post::Adopted || !res.chol_valid)
+        return ctx->fail(GPSO_E_STATE, "gpso_predict_grad needs the dense factor of the posterior: an adopted posterior may have travelled without it");
+      int rc = refuse_if_async("gpso_predict_grad");
+      if (rc) return rc;
+      const int64_t chunk = std::min<int64_t>(kPredictGradChunk, (m + 63) / 64 * 64);
+      if ((rc = ensure(pg_ts, (size_t)chunk * dp * 8))) return rc;
+      if ((rc = ensure(pg_norm, (size_t)chunk * 8))) return rc;
+      if ((rc = ensure(pg_work, predict_grad_workspace_doubles(npad, dp, chunk) * 8))) return rc;
+      const bool to_host = out_mem == GPSO_MEM_HOST;
+      double *md = mean, *vd = var, *dmd = dmean, *dvd = dvar;
+      if (to_host) {
+        if ((rc = ensure(pg_out, (size_t)m * (2 + 2 * (size_t)d) * 8))) return rc;
+        double* o = as<double>(pg_out);
+        md = mean ? o : nullptr;
+        vd = var ? o + m : nullptr;
+        dmd = dmean ? o + 2 * m : nullptr;
+        dvd = dvar ? o + 2 * m + m * d : nullptr;
+      }
+      hipStream_t s = st();
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+      const void* dev = nullptr;
+      if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+      PredictGradLaunch g;
+      g.C = as<double>(linv); g.alpha = as<double>(alpha_f); g.xs = as<double>(xs64); g.ls = ls_dev();
+      g.ts = as<double>(pg_ts); g.n = n; g.npad = npad; g.d = d; g.dp = dp; g.kp = kp; g.work = as<double>(pg_work);
+      for (int64_t off = 0; off < m; off += chunk) {
+        const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+        if (xs_dtype == GPSO_F64)
+          launch_prep_leaves<double, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
+                                             as<double>(pg_ts), as<double>(pg_norm));
+        else
+          launch_prep_leaves<double, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
+                                            as<double>(pg_ts), as<double>(pg_norm));
+        g.m = mc;
+        g.mean = md ? md + off : nullptr;
+        g.var = vd ? vd + off : nullptr;
+        g.dmean = dmd ? dmd + off * d : nullptr;
+        g.dvar = dvd ? dvd + off * d : nullptr;
+        if (launch_predict_grad(s, g) != 0) return launch_status();
+        if ((rc = launch_status())) return rc;
+      }
+      if (to_host) {
+        if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        if (dmean) HIPCHECK(hipMemcpyAsync(dmean, dmd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+        if (dvar) HIPCHECK(hipMemcpyAsync(dvar, dvd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+      }
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+      HIPCHECK(ctx->wait(s));
+      ctx->last_count[0] = ctx->last_count[1] = m;  // (as gpso_predict: the counts and last_ms[1] describe the same call)
+      float ms = 0;
+      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+      return GPSO_OK;
+    }
+  }
+
   // ---- best-UCB sequencing: enqueue the local work (winners stay on the device, no host wait) ->
   //      [multi-GPU: all-gather + fold] -> one read-back ------------------------------------------------
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
@@ -4438,6 +4514,13 @@ int gpso_predict(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_
   ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
   return ctx->eng->predict(xs, xs_dtype, xs_mem, m, mean, var, out_mem);
+}
+
+int gpso_predict_grad(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var,
+                      double* dmean, double* dvar, int out_mem) {
+  ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  return ctx->eng->predict_grad(xs, xs_dtype, xs_mem, m, mean, var, dmean, dvar, out_mem);
 }
 
 int gpso_best_ucb(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m,

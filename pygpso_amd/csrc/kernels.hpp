@@ -387,6 +387,22 @@ struct LooSmallArgs {
   double done_token;  // != 0: scal_host[7] := token behind the scalars
 };
 int launch_loo_small(hipStream_t st, const LooSmallArgs& args);
+// ---- predict_grad.hip: mean, variance and their gradients in the test points ---------------------
+constexpr int64_t kPredictGradChunk = 1024;  // test points per launch sequence: the workspace does not grow with M
+struct PredictGradLaunch {
+  const double* C = nullptr;      // [npad * npad] dense fit-type factor; read only where column <= row < n
+  const double* alpha = nullptr;  // [npad]
+  const double* xs = nullptr;     // [npad * dp] scaled rows
+  const double* ls = nullptr;     // lengthscale per padded dimension (device: the hyper block)
+  const double* ts = nullptr;     // [roundup(m, 64) * dp] scaled test points, zero rows behind the m live ones
+  int64_t n = 0, npad = 0, m = 0; // m <= kPredictGradChunk
+  int d = 0, dp = 0;
+  KernParams kp{0, 1.0, 0.0, 0.0};
+  double* work = nullptr;         // predict_grad_workspace_doubles(npad, dp, roundup(m, 64)) doubles
+  double *mean = nullptr, *var = nullptr, *dmean = nullptr, *dvar = nullptr;  // device, [m], [m], [m * d], [m * d]; each nullable
+};
+size_t predict_grad_workspace_doubles(int64_t npad, int dp, int64_t mc);
+int launch_predict_grad(hipStream_t st, const PredictGradLaunch& g);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

@@ -620,6 +620,28 @@ class HipGPEngine:
                                            C.c_void_p(var.ctypes.data), L.MEM_HOST))
         return mean, var
 
+    def predict_grad(self, xs, out=None):
+        """predict_y and its gradients in the test points: (mean[M], var[M], dmean[M, D], dvar[M, D]) float64, var with
+        the noise variance, gradients in the coordinates as passed.  float64 and mixed engines (the dense factor in
+        double); any resident posterior but an adopted one.  ``out`` may be four float64 CUDA tensors of those shapes to
+        keep the results on the device; an entry may be None for an output that is not wanted (not all four)."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        if out is not None:
+            if len(out) != 4:
+                raise ValueError("out must hold four entries: mean, var, dmean, dvar (tensors or None)")
+            for t in out:
+                if t is not None:
+                    self._order_after(t)
+            self._check(self._lib.gpso_predict_grad(self._h, ptr, dt, mem, m,
+                                                    *[None if t is None else C.c_void_p(t.data_ptr()) for t in out], L.MEM_DEVICE))
+            return tuple(out)
+        d = int(keep.shape[1])
+        mean, var = np.empty(m, dtype=np.float64), np.empty(m, dtype=np.float64)
+        dmean, dvar = np.empty((m, d), dtype=np.float64), np.empty((m, d), dtype=np.float64)
+        self._check(self._lib.gpso_predict_grad(self._h, ptr, dt, mem, m, *[C.c_void_p(a.ctypes.data) for a in (mean, var, dmean, dvar)],
+                                                L.MEM_HOST))
+        return mean, var, dmean, dvar
+
     def best_ucb(self, xs, varsigma, seg_off=None):
         """gp_eval_best_ucb per segment -> (idx, mean, var, ucb) arrays of length nseg."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)

@@ -26,9 +26,10 @@ from collections import namedtuple
 import math
 
 import numpy as np
+import scipy.optimize
 from scipy.special import erfcinv
 
-from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero
+from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero, _LbfgsbSearch
 from .model import HipGPR
 from .sgpr import HipSGPR
 from .svgp import HipSVGP
@@ -305,6 +306,45 @@ for _name in ("extend", "insert", "pop", "remove", "clear", "sort", "reverse", "
 del _name
 
 
+def polish_lockstep(value_and_grad, starts, lower, upper, options=None):
+    """R bounded L-BFGS-B searches (``kernels._LbfgsbSearch``) that MAXIMISE a function, advanced side by side: each round
+    the points the live searches wait at are stacked and evaluated by one ``value_and_grad(X [P, D]) -> (value [P],
+    grad [P, D])`` call.  ``starts``, ``lower``, ``upper``: [R, D].  Returns one ``scipy.optimize.OptimizeResult`` per start
+    (``x``: the end point, ``fun``: minus the value there).  With a SciPy whose private routine has another signature the
+    starts go one after another through ``scipy.optimize.minimize(method="L-BFGS-B", bounds=...)``, as ``kernels.Scipy``
+    falls back: the same answers, one evaluation per call."""
+    names = {"maxiter": "maxiter", "maxfun": "maxfun", "gtol": "pgtol", "maxls": "maxls"}
+    for key in (options or {}):
+        if key != "ftol" and key not in names:
+            raise ValueError(f"polish: unknown option {key!r}")
+    setulb = _LbfgsbSearch.routine()
+    if setulb is None:
+        def one(x):
+            value, grad = value_and_grad(np.asarray(x, dtype=np.float64)[np.newaxis, :])
+            return -float(value[0]), -np.asarray(grad[0], dtype=np.float64)
+
+        return [scipy.optimize.minimize(one, np.clip(s, lo, up), jac=True, method="L-BFGS-B", bounds=list(zip(lo, up)),
+                                        options=dict(options or {}))
+                for s, lo, up in zip(starts, lower, upper)]
+    searches = [_LbfgsbSearch(setulb, s, lower=lo, upper=up) for s, lo, up in zip(starts, lower, upper)]
+    for key, val in (options or {}).items():
+        for s in searches:
+            if key == "ftol":
+                s.factr = float(val) / np.finfo(float).eps
+            else:
+                setattr(s, names[key], type(getattr(s, names[key]))(val))
+    live = list(range(len(searches)))
+    while live:
+        pending = [(i, searches[i].advance()) for i in live]
+        pending = [(i, x) for i, x in pending if x is not None]
+        live = [i for i, _ in pending]
+        if pending:
+            value, grad = value_and_grad(np.stack([x for _, x in pending]))
+            for (i, _), v, g in zip(pending, value, grad):
+                searches[i].feed(-float(v), -np.asarray(g, dtype=np.float64))
+    return [s.result() for s in searches]
+
+
 class GPSurrogate:
     """Base class: point bookkeeping + predict/UCB on top of ``self.gpflow_model``."""
 
@@ -435,6 +475,51 @@ class GPSurrogate:
             m, v = float(mean[i, 0]), float(var[i, 0])
             self.points.append(GPPoint(normed_coords[i, :], m, v, float(m + self.gp_varsigma * v),
                                        PointLabels.gp_based))
+
+    def gp_predict_grad(self, normed_coords):
+        """predict_y and its gradients in normed coordinates at the rows of ``normed_coords``: (mean [M], var [M],
+        dmean [M, D], dvar [M, D]); stores nothing.  One ``gpso_predict_grad`` call (not in the reference, where it would
+        be a tf.GradientTape around predict_y).  A multi-GPU engine group raises NotImplementedError."""
+        self._require_model()
+        from .distributed import HipGPEngineGroup
+
+        if isinstance(self.gpflow_model.engine, HipGPEngineGroup):
+            raise NotImplementedError("gp_predict_grad / polish: not offered on a multi-GPU engine group")
+        return self.gpflow_model.predict_y_grad(np.ascontiguousarray(normed_coords, dtype=np.float64))
+
+    def polish(self, normed_coords, objective="ucb", box=None, options=None):
+        """Gradient polish of R candidate points on the surrogate: from each row of ``normed_coords`` [R, D], L-BFGS-B
+        maximises ``mean + varsigma * var`` (``objective="ucb"``, the package's UCB on the variance) or the mean
+        (``"mean"``) inside ``box`` -- the unit cube by default, or [R, D, 2] (lower, upper) per start, one leaf's bounds
+        being the intended use.  The R searches advance in lockstep; each round their pending points are ONE
+        ``gp_predict_grad`` call, and every search takes the iterates it would take alone.  ``options``: ``maxiter``,
+        ``maxfun``, ``gtol``, ``ftol``, ``maxls`` as SciPy's L-BFGS-B names them; ``ftol`` defaults to ten machine epsilons
+        here, so a search ends on its projected gradient (``gtol``, 1e-5).  Changes neither the point store nor
+        anything saved.  Returns (coords [R, D], mean [R], var [R], value [R], results)."""
+        if objective not in ("ucb", "mean"):
+            raise ValueError(f"objective={objective!r}: 'ucb' or 'mean'")
+        starts = np.array(normed_coords, dtype=np.float64, ndmin=2)
+        r, d = starts.shape
+        if box is None:
+            lower, upper = np.zeros((r, d)), np.ones((r, d))
+        else:
+            box = np.asarray(box, dtype=np.float64)
+            if box.shape != (r, d, 2):
+                raise ValueError(f"box has shape {box.shape}, expected {(r, d, 2)}")
+            lower, upper = box[:, :, 0], box[:, :, 1]
+        weight = self.gp_varsigma if objective == "ucb" else 0.0
+
+        def value_and_grad(x):
+            mean, var, dmean, dvar = self.gp_predict_grad(x)
+            return mean + weight * var, dmean + weight * dvar
+
+        # (a polish is after the last digits: SciPy's default ftol, 1e7 machine epsilons, would end it on the flat top first)
+        opts = {"ftol": 10.0 * np.finfo(float).eps}
+        opts.update(options or {})
+        results = polish_lockstep(value_and_grad, starts, lower, upper, opts)
+        coords = np.stack([np.asarray(r.x, dtype=np.float64) for r in results])
+        mean, var, _, _ = self.gp_predict_grad(coords)
+        return coords, mean, var, mean + weight * var, results
 
     def gp_eval_best_ucb(self, normed_coords):
         """(mean, var, ucb) of the row with the highest ucb = mean + varsigma * var; stores nothing."""

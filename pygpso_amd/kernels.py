@@ -140,8 +140,9 @@ class Adam:
 
 
 class _LbfgsbSearch:
-    """One L-BFGS-B search as a resumable state: the loop of scipy.optimize._lbfgsb_py._minimize_lbfgsb (SciPy 1.15) for an
-    unbounded problem with an exact gradient and default options, cut open where it asks for f and g.  ``advance()`` runs
+    """One L-BFGS-B search as a resumable state: the loop of scipy.optimize._lbfgsb_py._minimize_lbfgsb (SciPy 1.15) for a
+    problem with an exact gradient and default options -- unbounded (the hyper-parameter searches) or inside a box
+    (``lower=`` / ``upper=``: ``GPSurrogate.polish``) --, cut open where it asks for f and g.  ``advance()`` runs
     the routine until it wants an evaluation (returns a copy of x) or ends (returns None); ``feed(f, g)`` hands the
     evaluation back.  One ``setulb`` workspace per search, so any number of them advance side by side
     (``Scipy(restarts=R)``)."""
@@ -160,7 +161,9 @@ class _LbfgsbSearch:
             return None
         return _lbfgsb.setulb
 
-    def __init__(self, setulb, x0):
+    def __init__(self, setulb, x0, lower=None, upper=None):
+        """``lower`` / ``upper`` (each None or [n], +-inf where open): box bounds as ``scipy.optimize.minimize(bounds=...)``
+        hands them to the routine, x0 clipped into them.  Both None: the unbounded setup (nbd = 0)."""
         self.setulb = setulb
         self.m, self.maxls, self.maxfun, self.maxiter = 10, 20, 15000, 15000
         self.factr = 2.2204460492503131e-09 / np.finfo(float).eps
@@ -171,6 +174,17 @@ class _LbfgsbSearch:
         self.nbd = np.zeros(n, np.int32)
         self.low_bnd = np.zeros(n, np.float64)
         self.upper_bnd = np.zeros(n, np.float64)
+        if lower is not None or upper is not None:
+            lo = np.full(n, -np.inf) if lower is None else np.array(np.asarray(lower).ravel(), dtype=np.float64)
+            up = np.full(n, np.inf) if upper is None else np.array(np.asarray(upper).ravel(), dtype=np.float64)
+            if lo.shape != (n,) or up.shape != (n,) or np.any(lo > up):
+                raise ValueError("bounds must be [n] arrays with lower <= upper")
+            has_lo, has_up = np.isfinite(lo), np.isfinite(up)
+            # setulb's codes: 0 unbounded, 1 only a lower bound, 2 both, 3 only an upper bound
+            self.nbd[:] = np.where(has_lo & has_up, 2, np.where(has_lo, 1, np.where(has_up, 3, 0)))
+            self.low_bnd[has_lo] = lo[has_lo]
+            self.upper_bnd[has_up] = up[has_up]
+            self.x = np.clip(self.x, lo, up)
         self.f = np.array(0.0, dtype=np.int32)
         self.g = np.zeros((n,), dtype=np.int32)
         self.wa = np.zeros(2 * m * n + 5 * n + 11 * m * m + 8 * m, np.float64)

@@ -417,6 +417,22 @@ class HipGPR:
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.likelihood.variance)
 
+    def predictive_noise(self):
+        """The likelihood's variance in ``predict_y`` (the families with another likelihood override this)."""
+        return self.likelihood.variance
+
+    def predict_y_grad(self, Xnew):
+        """``predict_y`` and its gradients in the rows of Xnew: (mean [M], var [M], dmean [M, D], dvar [M, D]), float64
+        from the dense double factor on float64 and mixed engines (what a GPflow user gets from tf.GradientTape).  Plain
+        arrays, mean and var FLAT [M] -- not the [M, 1] results of ``predict_y``."""
+        Xnew = np.asarray(Xnew)
+        return self._predicting(lambda: self.engine.predict_grad(Xnew))
+
+    def predict_f_grad(self, Xnew):
+        """As ``predict_y_grad`` with the likelihood's variance taken off ``var``; the gradients are the same."""
+        mean, var, dmean, dvar = self.predict_y_grad(Xnew)
+        return mean, var - self.predictive_noise(), dmean, dvar
+
     def best_ucb(self, Xnew, varsigma, seg_off=None):
         return self._predicting(lambda: self.engine.best_ucb(Xnew, varsigma, seg_off))
 
