@@ -692,7 +692,9 @@ double gpso_last_ms(gpso_ctx* ctx, int what);
  * the fit is priced against -- the f32 / f64 matrix instruction, or the two-level float fit's 16-bit pieces: six bf16 or
  * three fp16 MFMAs per f32 product).
  * what = 3: how many workgroups shared a leaf tile's row blocks in the last launch of a split predict kernel (GPSO_OPT_ROW_LOOP;
- * per context: the last launch THIS context made; for tests and tools). */
+ * per context: the last launch THIS context made; for tests and tools).
+ * what = 4: bytes of device memory the buffers of ALL contexts of this process hold now (process-wide, whichever ctx asks;
+ * back where it stood once a context is destroyed; for tests and tools). */
 #define GPSO_FITMATH_NONE 0
 #define GPSO_FITMATH_SMALL 1   /* N <= 128: one launch, vector arithmetic in double */
 #define GPSO_FITMATH_F32 2     /* v_mfma_f32_16x16x4_f32 (float fits up to N_pad = 3584, or GPSO_OPT_FIT_BF16_SYRK = 0) */

@@ -18,6 +18,7 @@
 
 #include "../../include/gpso_hip.h"
 #include "common.hpp"
+#include "devbuf.hpp"
 #include "kernels.hpp"
 #include "rccl_api.hpp"
 #include "resident.hpp"
@@ -66,12 +67,6 @@ constexpr int kMaxD = 48;                      // padded input dimension limit (
 constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass of the tile kernel
 constexpr int kHyperHeader = 8;                // doubles in front of the lengthscales
 static_assert(kThetaMaxLs == kGradMaxLs, "a Theta holds as many lengthscales as the gradient kernels take");
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  bool view = false;  // a slice of the posterior arena (EngineT::carve_posterior): not freed, not re-allocated on its own
-};
 
 struct Engine {
   virtual ~Engine() {}
@@ -459,15 +454,6 @@ struct EngineT : Engine {
   double st_vals[6] = {0, 0, 0, 0, 0, 0};
   DevBuf st_mean, st_var, st_out;
 
-  ~EngineT() override {
-    for (DevBuf* b : {&xs_h16, &c16_scal, &x64, &y64, &hyper, &xs64, &xnorm64, &xs_p64, &xs32, &xnorm32, &xs_p32, &K, &Lf, &linv,
-                      &work, &kinvb, &linv_p, &white, &alpha_f, &alpha, &logdet, &scal, &gpart, &apart,
-                      &kinv_diag, &getter_tmp, &leaves_raw, &leaves_s, &lnorm, &pvar, &pmean, &omean, &ovar,
-                      &oucb, &segoff, &best, &oidx, &ovals, &linv_b, &st_mean, &st_var, &st_out, &grow_key, &live_cnt,
-                      &best_pos, &gath, &wbase, &ovals2, &bhdr, &pl_L, &pl_X, &pl_XT, &pl_WT, &app, &amax_rows, &arena, &hash_out, &extra_cnt, &one_ctl, &one_partial, &one_ppos, &vq_mu, &vq_S, &vA, &vB, &vC, &vvec, &vsmall, &vgh, &vlvec, &batch_theta, &sdiag, &loov, &loo_scal, &pg_ts, &pg_norm, &pg_work, &pg_out})
-      if (b->p && !b->view) (void)hipFree(b->p);
-  }
-
   int64_t padded_n() const override { return npad; }
   void problem_shape(int64_t* n_out, int* d_out) const override {
     *n_out = n;
@@ -650,35 +636,21 @@ struct EngineT : Engine {
   template <typename U>
   U* as(const DevBuf& b) const { return static_cast<U*>(b.p); }
 
-  int ensure(DevBuf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return GPSO_OK;
-    if (b.view) return ctx->fail(GPSO_E_STATE, "internal: a slice of the posterior arena (%zu bytes) was asked to hold %zu", b.bytes, bytes);
-    if (b.p) {
-      HIPCHECK(hipStreamSynchronize(st()));
-      HIPCHECK(hipFree(b.p));
-      b.p = nullptr;
-      b.bytes = 0;
-    }
-    HIPCHECK(hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return GPSO_OK;
+  // room for at least `bytes` in b (devbuf.hpp: grow-only; the stream is synchronised before an old block is freed)
+  int ensure(DevBuf& b, size_t bytes, bool keep = false) {
+    const size_t had = b.bytes;
+    const BufStatus r = b.ensure(bytes, st(), keep);
+    if (!r) return GPSO_OK;
+    if (r.step == BufStep::View)
+      return ctx->fail(GPSO_E_STATE, "internal: a slice of the posterior arena (%zu bytes) was asked to hold %zu", had, bytes);
+    // (indexed by BufStep, in the words these steps have always failed with)
+    static const char* const call[] = {"", "", "hipMalloc(&b.p, bytes)", "hipMemcpyAsync(np_, b.p, b.bytes, hipMemcpyDeviceToDevice, st())",
+                                       "hipStreamSynchronize(st())", "hipFree(b.p)"};
+    const hipError_t e = (hipError_t)r.err;
+    return ctx->fail(e == hipErrorOutOfMemory ? GPSO_E_OOM : GPSO_E_HIP, "%s failed: %s", call[(int)r.step], hipGetErrorString(e));
   }
-
   // like ensure(), but the old contents survive a re-allocation
-  int ensure_keep(DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes) return GPSO_OK;
-    void* np_ = nullptr;
-    HIPCHECK(hipMalloc(&np_, bytes));
-    if (b.p) {
-      HIPCHECK(hipMemcpyAsync(np_, b.p, b.bytes, hipMemcpyDeviceToDevice, st()));
-      HIPCHECK(hipStreamSynchronize(st()));
-      HIPCHECK(hipFree(b.p));
-    }
-    b.p = np_;
-    b.bytes = bytes;
-    return GPSO_OK;
-  }
+  int ensure_keep(DevBuf& b, size_t bytes) { return ensure(b, bytes, true); }
 
   // launcher-side errors (hipFuncSetAttribute, unsupported GEMM shapes) + the HIP launch status
   int launch_status() {
@@ -741,24 +713,16 @@ struct EngineT : Engine {
     // room for three planes whatever the option: GPSO_OPT_PREDICT_MATH may change after the shape is known
     const size_t b_split = split_slot_exists() ? up256((size_t)3 * npad * npad * 2 + 256) : 0;
     const size_t total = b_linv + b_hyper + 2 * b_xs + b_norm + b_alpha + b_split;
-    if (arena.bytes < total) {
-      if (arena.p) {
-        HIPCHECK(hipStreamSynchronize(st()));
-        HIPCHECK(hipFree(arena.p));
-        arena.p = nullptr;
-        arena.bytes = 0;
-        arena_npad = -1;
-        for (DevBuf* b : {&linv_p, &hyper, &xs64, &xs_p64, &xnorm64, &alpha, &linv_b}) *b = DevBuf{};
-      }
-      HIPCHECK(hipMalloc(&arena.p, total));
-      arena.bytes = total;
+    if (arena.bytes < total) {  // (the old slices go first: whatever becomes of the arena, none of them points into a freed block)
+      arena_npad = -1;
+      for (DevBuf* b : {&linv_p, &hyper, &xs64, &xs_p64, &xnorm64, &alpha, &linv_b}) b->drop();
+      int rc = ensure(arena, total);
+      if (rc) return rc;
     }
-    char* q = static_cast<char*>(arena.p);
+    size_t off = 0;
     auto slice = [&](DevBuf& b, size_t bytes) {
-      b.p = bytes ? q : nullptr;
-      b.bytes = bytes;
-      b.view = true;
-      q += bytes;
+      b.slice(arena, off, bytes);
+      off += bytes;
     };
     slice(linv_p, b_linv);
     slice(hyper, b_hyper);
@@ -1638,19 +1602,17 @@ struct EngineT : Engine {
     if (rc) return rc;
     hipStream_t s = st();
     if (vq_npad != npad) {
-      void *nS = nullptr, *nmu = nullptr;
-      HIPCHECK(hipMalloc(&nS, (size_t)npad * npad * 8));
-      HIPCHECK(hipMalloc(&nmu, (size_t)npad * 8));
-      launch_vgp_pad_identity(s, static_cast<double*>(nS), 0, npad, nullptr);
-      HIPCHECK(hipMemsetAsync(nmu, 0, (size_t)npad * 8, s));
-      HIPCHECK(hipMemcpy2DAsync(nS, (size_t)npad * 8, vq_S.p, (size_t)vq_npad * 8, (size_t)vq_n * 8, (size_t)vq_n,
+      DevBuf nS, nmu;  // (an early return frees them: q stays as it was)
+      if ((rc = ensure(nS, (size_t)npad * npad * 8))) return rc;
+      if ((rc = ensure(nmu, (size_t)npad * 8))) return rc;
+      launch_vgp_pad_identity(s, as<double>(nS), 0, npad, nullptr);
+      HIPCHECK(hipMemsetAsync(nmu.p, 0, (size_t)npad * 8, s));
+      HIPCHECK(hipMemcpy2DAsync(nS.p, (size_t)npad * 8, vq_S.p, (size_t)vq_npad * 8, (size_t)vq_n * 8, (size_t)vq_n,
                                 hipMemcpyDeviceToDevice, s));
-      HIPCHECK(hipMemcpyAsync(nmu, vq_mu.p, (size_t)vq_n * 8, hipMemcpyDeviceToDevice, s));
+      HIPCHECK(hipMemcpyAsync(nmu.p, vq_mu.p, (size_t)vq_n * 8, hipMemcpyDeviceToDevice, s));
       HIPCHECK(hipStreamSynchronize(s));
-      HIPCHECK(hipFree(vq_S.p));
-      HIPCHECK(hipFree(vq_mu.p));
-      vq_S = DevBuf{nS, (size_t)npad * npad * 8, false};
-      vq_mu = DevBuf{nmu, (size_t)npad * 8, false};
+      vq_S = std::move(nS);
+      vq_mu = std::move(nmu);
     }
     vq_n = n;
     vq_npad = npad;
@@ -2010,20 +1972,8 @@ struct EngineT : Engine {
     // (what set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
     if ((rc = theta_status(theta_refusal(th, d, true), "noise variance"))) return rc;
     if ((rc = vgp_begin(true))) return rc;
-    const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
-    int nsplit = 1;
-    while (nsplit < 16 && sg_npad % (256 * nsplit) == 0 && sg_npad / (2 * nsplit) >= 512) nsplit *= 2;
-    for (DevBuf* b : {&sgKuf, &sgA, &sgW})
-      if ((rc = ensure(*b, rect))) return rc;
-    for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
-      if ((rc = ensure(*b, sq))) return rc;
-    if ((rc = ensure(sgPart, sq * nsplit))) return rc;
-    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
-    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
-    if ((rc = ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
-    if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
-    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
-    if ((rc = ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8))) return rc;
+    if ((rc = sparse_workspace(false))) return rc;
+    const int nsplit = sparse_nsplit();
     hipStream_t s = st();
     vgp_reset_info();
     if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
@@ -2141,11 +2091,32 @@ struct EngineT : Engine {
   int64_t svq_m = -1, svq_mpad = -1;  // the rows q was made for (-1: none; the next call starts q at the prior)
   enum { kSvM = 0, kSvV = 1, kSvGm = 2, kSvA = 3, kSvT = 4, kSvVe = 5, kSvDve = 6, kSvVecsN = 7 };
   double* svn_at(int k) const { return as<double>(svvecN) + (size_t)k * sg_npad; }
-  // the long-K products A diag(a) A^T split along N into this many fixed-order partial products (as the SGPR's A A^T)
-  int svgp_nsplit() const {
+  // the long-K products A A^T (SGPR) and A diag(a) A^T (SVGP) are split along N into this many fixed-order partial products
+  int sparse_nsplit() const {
     int ns = 1;
     while (ns < 16 && sg_npad % (256 * ns) == 0 && sg_npad / (2 * ns) >= 512) ns *= 2;
     return ns;
+  }
+  // the rectangular [M_pad x N_pad] and square [M_pad^2] work of an evaluation at the resident M and N.  Each family asks
+  // for its own third rectangle(s) and N-vectors only: sgW / sgvecN the SGPR, svB / svD / svvecN the SVGP
+  int sparse_workspace(bool svgp) {
+    const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
+    int rc;
+    if ((rc = ensure(sgKuf, rect)) || (rc = ensure(sgA, rect))) return rc;
+    if (svgp) {
+      if ((rc = ensure(svB, rect)) || (rc = ensure(svD, rect))) return rc;
+    } else if ((rc = ensure(sgW, rect))) {
+      return rc;
+    }
+    for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
+      if ((rc = ensure(*b, sq))) return rc;
+    if ((rc = ensure(sgPart, sq * sparse_nsplit()))) return rc;
+    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
+    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
+    if ((rc = svgp ? ensure(svvecN, (size_t)kSvVecsN * sg_npad * 8) : ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
+    if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
+    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
+    return ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8);
   }
 
   int svgp_need_z(const char* who) {
@@ -2178,20 +2149,7 @@ struct EngineT : Engine {
     if ((rc = theta_status(theta_refusal(th, d, true), "likelihood parameter"))) return rc;
     if ((rc = vgp_begin(true))) return rc;
     if ((rc = svgp_q())) return rc;
-    if (rect) {
-      const size_t rect_b = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
-      for (DevBuf* b : {&sgKuf, &sgA, &svB, &svD})
-        if ((rc = ensure(*b, rect_b))) return rc;
-      for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
-        if ((rc = ensure(*b, sq))) return rc;
-      if ((rc = ensure(sgPart, sq * svgp_nsplit()))) return rc;
-      if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
-      if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
-      if ((rc = ensure(svvecN, (size_t)kSvVecsN * sg_npad * 8))) return rc;
-      if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
-      if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
-      if ((rc = ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8))) return rc;
-    }
+    if (rect && (rc = sparse_workspace(true))) return rc;
     hipStream_t s = st();
     vgp_reset_info();
     if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
@@ -2224,7 +2182,7 @@ struct EngineT : Engine {
   // P = A diag(a) A^T (into aat) and I + P (into lam, identity padding): the long-K product in its fixed split-K order
   void svgp_adat(double* aat, double* lam) {
     hipStream_t s = st();
-    const int ns = svgp_nsplit();
+    const int ns = sparse_nsplit();
     launch_svgp_colscale(s, as<double>(sgA), svn_at(kSvA), as<double>(svD), n, npad, sg_n, sg_npad);  // D = A diag(a)
     launch_dgemm_rect(s, as<double>(sgA), sg_npad, 1, as<double>(svD), 1, sg_npad, as<double>(sgPart), npad, npad, npad,
                       sg_npad, 1.0, 0.0, ns);
@@ -4759,8 +4717,8 @@ int gpso_comm_abort(gpso_ctx* ctx) {
 }
 
 int64_t gpso_last_count(gpso_ctx* ctx, int what) {
-  if (!ctx || what < 0 || what > 3) return -1;
-  return ctx->last_count[what];
+  if (!ctx || what < 0 || what > 4) return -1;
+  return what == 4 ? g_dev_bytes_held.load(std::memory_order_relaxed) : ctx->last_count[what];
 }
 
 const char* gpso_version(void) { return "gpso-hip 0.5.0 (gfx950)"; }

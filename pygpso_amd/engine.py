@@ -178,7 +178,8 @@ class HipGPEngine:
         return float(self._lib.gpso_last_ms(self._h, int(what)))
 
     def last_count(self, what=0):
-        """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list."""
+        """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list; 2 .. 4: see
+        ``gpso_last_count`` in include/gpso_hip.h (4: bytes of device memory the contexts of this process hold now)."""
         return int(self._lib.gpso_last_count(self._h, int(what)))
 
     FIT_MATH = {L.FITMATH_NONE: None, L.FITMATH_SMALL: "small", L.FITMATH_F32: "f32", L.FITMATH_F64: "f64",

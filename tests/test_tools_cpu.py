@@ -140,3 +140,18 @@ def test_theta_header_on_its_own_and_its_python_twins(tmp_path):
         u = struct.unpack(">d", bytes.fromhex(line.split()[0]))[0]
         s = _softplus1(u)
         assert line == f"{h(u)} {h(s)} {h(1.0e-6 + s)} {h(float(_sigmoid(u)))}", u
+
+
+def test_devbuf_header_on_its_own(tmp_path):
+    """tools/devbuf_check.cpp -- csrc/devbuf.hpp compiled by the host compiler alone, over a counting host allocator --
+    passes its own checks: every owned block freed exactly once, views free nothing, what a move leaves behind, the
+    grow-only rule and the order of a re-allocation, kept bytes, refused views, and no byte left with any one allocation
+    of a call sequence failing."""
+    import shutil
+
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    exe = str(tmp_path / "devbuf_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tools", "devbuf_check.cpp"),
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "devbuf_check: ok\n", (r.returncode, r.stdout, r.stderr)
