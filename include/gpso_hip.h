@@ -501,6 +501,37 @@ int gpso_predict_grad(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
                       double* mean /* [m], nullable */, double* var /* [m], nullable */,
                       double* dmean /* [m*D] row-major, nullable */, double* dvar /* [m*D], nullable */, int out_mem);
 
+/* Replaces: gpflow_model.predict_f(Xnew, full_cov=True) -- and predict_y's, by way of diag_add -- for the reference's users
+ * (gpso/gp_surrogate.py hands them the GPflow model).  The JOINT predictive at the m test points: with V = C K* (N x m,
+ * K*[i, a] = k(x_i, t_a)) and K**[a, b] = k(t_a, t_b) from direct differences in double,
+ *   mean = K*^T alpha + c,   cov = K** - V^T V + diag_add I   (m x m row-major, EXACTLY symmetric)
+ * (DESIGN.md section 7i).  diag_add is an absolute term the caller chooses: 0 for the latent f, the family's predictive noise
+ * for y, plus a jitter where a factorisation follows; the library adds no noise of its own here.
+ * xs, xs_dtype, xs_mem, out_mem as gpso_predict; mean[m] (nullable) and cov[m * m] float64 living in out_mem.  Contexts,
+ * posteriors and statuses as gpso_predict_grad: GPSO_F64 and GPSO_MIXED contexts (GPSO_F32: GPSO_E_ARG); every resident
+ * posterior that has its dense factor; GPSO_E_STATE without a posterior, for a posterior from a hand-off and while an
+ * asynchronous best-UCB ticket is open.  GPSO_E_ARG also for m < 1, m > 1024 (the joint covariance of more test points is out
+ * of scope: the workspace and the factorisation are sized for one chunk), xs or cov NULL, a diag_add that is not finite.
+ * Reads only: the posterior, its packed copies, the hyper block, the self-test's verdicts and gpso_posterior_hash stay as
+ * they are; the same call gives the same bits.  gpso_last_ms(ctx, 1) and gpso_last_count as after gpso_predict_grad. */
+int gpso_predict_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add,
+                       double* mean /* [m], nullable */, double* cov /* [m*m] row-major */, int out_mem);
+
+/* Replaces: gpflow_model.predict_f_samples(Xnew, num_samples) for the reference's users, and the arg-max of every draw over
+ * the m test points (Thompson sampling over a set of candidates).  With gpso_predict_joint's mean and cov (diag_add
+ * included: the jitter, and the predictive noise for draws of y), L = chol(cov):
+ *   samples[q, :] = mean + L z[q, :]   for the s rows of z,
+ *   best_idx[q] = the index of the highest entry of draw q (the lowest index on ties), best_val[q] that entry.
+ * z[s * m]: standard normals from the CALLER, host memory (there is no random generator on the device: draws are
+ * reproducible from a seed on the host).  samples[s * m], best_idx[s], best_val[s]: host memory, each nullable, not all
+ * three -- with samples NULL the draws never leave the device.  Conditions and statuses as gpso_predict_joint; GPSO_E_ARG
+ * also for s < 1, s > 2^20 (draw in several calls), s * m > 2^31 and z NULL.  GPSO_E_NOTPD: the Cholesky of cov met a pivot that is not positive --
+ * gpso_last_error names it, the outputs then hold nothing of use and a larger diag_add (jitter) is the remedy; the posterior
+ * is untouched and serves the next call.  Reads only, as gpso_predict_joint. */
+int gpso_sample_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add,
+                      const double* z /* [s*m] host */, int64_t s, double* samples /* [s*m] host, nullable */,
+                      int64_t* best_idx /* [s], nullable */, double* best_val /* [s], nullable */);
+
 /* Replaces: GPSurrogate.gp_eval_best_ucb (gpso/gp_surrogate.py:313-328): predict_y, then
  * ucb = mean + varsigma * VAR, then first arg-max -- per segment.  seg_off[nseg+1] (host) delimits
  * independent leaf batches (NULL with nseg = 1 means one segment [0, M)); outputs (host, nseg each):

@@ -124,6 +124,10 @@ SIGNATURES = {
                                C.c_void_p, C.c_int]),
     "gpso_predict_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_int]),
+    "gpso_predict_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                     C.c_int]),
+    "gpso_sample_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, C.c_int64,
+                                    _c_double_p, _c_int64_p, _c_double_p]),
     "gpso_best_ucb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p,
                                 C.c_int, C.c_double, _c_int64_p, _c_double_p, _c_double_p,
                                 _c_double_p]),

@@ -89,6 +89,11 @@ struct Engine {
   // mean, var and their gradients in the test points, from the dense factor (predict_grad.hip)
   virtual int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean,
                            double* dvar, int out_mem) = 0;
+  // the joint predictive at m test points: mean and full covariance, or draws and their arg-max (joint.hip)
+  virtual int predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
+                            int out_mem) = 0;
+  virtual int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t s,
+                           double* samples, int64_t* best_idx, double* best_val) = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
                        int nseg, double varsigma, int64_t* idx, double* mean, double* var,
                        double* ucb) = 0;
@@ -447,6 +452,9 @@ struct EngineT : Engine {
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
   DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
+  // gpso_predict_joint / gpso_sample_joint: scaled test points, V (+ partial |v|^2), partial tiles, mean, Sigma; then the
+  // Cholesky's buffers (factor, inverse, scratch, diagonal, info), the normals, the draws and their winners
+  DevBuf pj_ts, pj_norm, pj_v, pj_part, pj_mu, pj_sigma, pj_l, pj_linv, pj_cwork, pj_diag, pj_info, pj_z, pj_f, pj_best;
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -2835,6 +2843,142 @@ struct EngineT : Engine {
     }
   }
 
+  // ---- the joint predictive (joint.hip).  Like gpso_predict_grad it reads the dense fit-type factor,
+  // alpha_f, xs64 and the hyper block and writes buffers of its own only.  joint_enqueue scales the test
+  // points, forms V with predict_grad.hip's apply stage and launches mean and Sigma (into `cov`, leading dimension ldc)
+  int joint_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean_dev,
+                    double* cov_dev, int64_t ldc, bool pad_identity) {
+    const int64_t mc = (m + 63) / 64 * 64;
+    int rc;
+    if ((rc = ensure(pj_ts, (size_t)mc * dp * 8))) return rc;
+    if ((rc = ensure(pj_norm, (size_t)mc * 8))) return rc;
+    if ((rc = ensure(pj_v, predict_grad_apply_workspace_doubles(npad, mc) * 8))) return rc;
+    if ((rc = ensure(pj_part, std::max<size_t>(joint_partial_doubles(n, m), 1) * 8))) return rc;
+    hipStream_t s = st();
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    if (xs_dtype == GPSO_F64)
+      launch_prep_leaves<double, double>(s, static_cast<const double*>(dev), m, mc, d, dp, ls_dev(), nullptr, as<double>(pj_ts),
+                                         as<double>(pj_norm));
+    else
+      launch_prep_leaves<double, float>(s, static_cast<const float*>(dev), m, mc, d, dp, ls_dev(), nullptr, as<double>(pj_ts),
+                                        as<double>(pj_norm));
+    PredictGradLaunch g;
+    g.C = as<double>(linv); g.xs = as<double>(xs64); g.ts = as<double>(pj_ts); g.n = n; g.npad = npad; g.m = m; g.d = d; g.dp = dp;
+    g.kp = kp; g.work = as<double>(pj_v);
+    if (launch_predict_grad_apply(s, g) != 0) return launch_status();
+    JointLaunch j;
+    j.V = as<double>(pj_v); j.ts = as<double>(pj_ts); j.alpha = as<double>(alpha_f); j.xs = as<double>(xs64);
+    j.n = n; j.npad = npad; j.m = m; j.dp = dp; j.kp = kp; j.diag_add = diag_add; j.part = as<double>(pj_part);
+    j.mean = mean_dev; j.cov = cov_dev; j.ldc = ldc; j.pad_identity = pad_identity;
+    (void)launch_joint(s, j);  // (a refused shape is on record: launch_status reports it)
+    return launch_status();
+  }
+  // the conditions gpso_predict_joint and gpso_sample_joint share with gpso_predict_grad
+  int joint_check(const char* what, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add) {
+    if (m < 1 || m > kPredictGradChunk)
+      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld test points (m=%lld): the joint covariance of more is out of scope", what,
+                       (long long)kPredictGradChunk, (long long)m);
+    if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+    if (!(diag_add == diag_add) || diag_add - diag_add != 0.0) return ctx->fail(GPSO_E_ARG, "diag_add must be finite");
+    if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
+    if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (res.post == Post::Adopted || !res.chol_valid)
+      return ctx->fail(GPSO_E_STATE, "%s needs the dense factor of the posterior: an adopted posterior may have travelled without it", what);
+    return refuse_if_async(what);
+  }
+  int joint_done(hipStream_t s, int64_t m) {
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+    HIPCHECK(ctx->wait(s));
+    ctx->last_count[0] = ctx->last_count[1] = m;  // (as gpso_predict_grad)
+    float ms = 0;
+    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+    return GPSO_OK;
+  }
+
+  int predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
+                    int out_mem) override {
+    if constexpr (sizeof(TF) != 8) {
+      return ctx->fail(GPSO_E_ARG, "gpso_predict_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    } else {
+      ctx->tick_timing();
+      if (!cov) return ctx->fail(GPSO_E_ARG, "cov must not be NULL");
+      int rc = joint_check("gpso_predict_joint", xs, xs_dtype, xs_mem, m, diag_add);
+      if (rc) return rc;
+      const bool to_host = out_mem == GPSO_MEM_HOST;
+      double *md = mean, *cd = cov;
+      if (to_host) {
+        if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+        if ((rc = ensure(pj_sigma, (size_t)m * m * 8))) return rc;
+        md = mean ? as<double>(pj_mu) : nullptr;
+        cd = as<double>(pj_sigma);
+      }
+      hipStream_t s = st();
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+      if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, md, cd, m, false))) return rc;
+      if (to_host) {
+        if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)m * m * 8, hipMemcpyDeviceToHost, s));
+      }
+      return joint_done(s, m);
+    }
+  }
+
+  // Sigma (identity on the padding up to a multiple of 128) -> launch_potrf as vgp_chol uses it -> F = mu 1^T + Z L^T ->
+  // the arg-max per draw.  One wait at the end; a failing pivot is reported then and the outputs hold nothing of use
+  int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t ns,
+                   double* samples, int64_t* best_idx, double* best_val) override {
+    if constexpr (sizeof(TF) != 8) {
+      return ctx->fail(GPSO_E_ARG, "gpso_sample_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    } else {
+      ctx->tick_timing();
+      if (ns < 1 || ns > kJointMaxDraws)
+        return ctx->fail(GPSO_E_ARG, "gpso_sample_joint takes 1 to %lld draws a call (s=%lld)", (long long)kJointMaxDraws, (long long)ns);
+      if (!z) return ctx->fail(GPSO_E_ARG, "z must not be NULL");
+      if (!samples && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "samples, best_idx and best_val are all NULL");
+      int rc = joint_check("gpso_sample_joint", xs, xs_dtype, xs_mem, m, diag_add);
+      if (rc) return rc;
+      if (ns > ((int64_t)1 << 31) / m) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint: s * m above 2^31 (s=%lld, m=%lld)", (long long)ns, (long long)m);
+      const int64_t mpad = (m + kPadN - 1) / kPadN * kPadN;
+      const size_t mat = (size_t)mpad * mpad * 8;
+      for (DevBuf* b : {&pj_sigma, &pj_l, &pj_linv, &pj_cwork})
+        if ((rc = ensure(*b, mat))) return rc;
+      if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+      if ((rc = ensure(pj_diag, (size_t)mpad * 8))) return rc;
+      if ((rc = ensure(pj_info, 256))) return rc;
+      if ((rc = ensure(pj_z, (size_t)ns * m * 8))) return rc;
+      if ((rc = ensure(pj_f, (size_t)ns * m * 8))) return rc;
+      if ((rc = ensure(pj_best, (size_t)ns * 16))) return rc;
+      int* info_host = reinterpret_cast<int*>(ctx->pinned_scratch(8));
+      if (!info_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+      hipStream_t s = st();
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+      HIPCHECK(hipMemcpyAsync(pj_z.p, z, (size_t)ns * m * 8, hipMemcpyHostToDevice, s));
+      int* info = static_cast<int*>(pj_info.p);
+      launch_vgp_pad_identity(s, as<double>(pj_sigma), 0, mpad, info);  // (Sigma := I, info := INT_MAX; the tiles overwrite their part)
+      if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, as<double>(pj_mu), as<double>(pj_sigma), mpad, true)))
+        return rc;
+      HIPCHECK(hipMemsetAsync(pj_linv.p, 0, mat, s));
+      (void)launch_potrf<double>(s, as<double>(pj_sigma), as<double>(pj_l), as<double>(pj_linv), as<double>(pj_cwork), nullptr, m, mpad,
+                                 as<double>(pj_diag), info, -1, nullptr);
+      HIPCHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
+      launch_joint_draw(s, as<double>(pj_l), mpad, as<double>(pj_z), as<double>(pj_mu), m, ns, as<double>(pj_f));
+      int64_t* bi = as<int64_t>(pj_best);
+      double* bv = reinterpret_cast<double*>(bi + ns);
+      if (best_idx || best_val) launch_joint_argmax(s, as<double>(pj_f), m, ns, bi, bv);
+      if ((rc = launch_status())) return rc;
+      if (samples) HIPCHECK(hipMemcpyAsync(samples, pj_f.p, (size_t)ns * m * 8, hipMemcpyDeviceToHost, s));
+      if (best_idx) HIPCHECK(hipMemcpyAsync(best_idx, bi, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+      if (best_val) HIPCHECK(hipMemcpyAsync(best_val, bv, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+      if ((rc = joint_done(s, m))) return rc;
+      if (*info_host != INT_MAX)
+        return ctx->fail(GPSO_E_NOTPD, "gpso_sample_joint: Sigma + diag_add*I is not positive definite: Cholesky failed at pivot %d "
+                                       "(a larger diag_add -- jitter -- is the remedy)", *info_host);
+      return GPSO_OK;
+    }
+  }
+
   // ---- best-UCB sequencing: enqueue the local work (winners stay on the device, no host wait) ->
   //      [multi-GPU: all-gather + fold] -> one read-back ------------------------------------------------
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
@@ -4479,6 +4623,19 @@ int gpso_predict_grad(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
   ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
   return ctx->eng->predict_grad(xs, xs_dtype, xs_mem, m, mean, var, dmean, dvar, out_mem);
+}
+
+int gpso_predict_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean,
+                       double* cov, int out_mem) {
+  ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  return ctx->eng->predict_joint(xs, xs_dtype, xs_mem, m, diag_add, mean, cov, out_mem);
+}
+
+int gpso_sample_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z,
+                      int64_t s, double* samples, int64_t* best_idx, double* best_val) {
+  ENTER();
+  return ctx->eng->sample_joint(xs, xs_dtype, xs_mem, m, diag_add, z, s, samples, best_idx, best_val);
 }
 
 int gpso_best_ucb(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m,

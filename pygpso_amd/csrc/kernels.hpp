@@ -388,6 +388,7 @@ struct LooSmallArgs {
 };
 int launch_loo_small(hipStream_t st, const LooSmallArgs& args);
 // ---- predict_grad.hip: mean, variance and their gradients in the test points ---------------------
+constexpr int64_t kJointMaxDraws = (int64_t)1 << 20;  // draws per gpso_sample_joint call (a workgroup of pj_argmax_kernel each)
 constexpr int64_t kPredictGradChunk = 1024;  // test points per launch sequence: the workspace does not grow with M
 struct PredictGradLaunch {
   const double* C = nullptr;      // [npad * npad] dense fit-type factor; read only where column <= row < n
@@ -403,6 +404,39 @@ struct PredictGradLaunch {
 };
 size_t predict_grad_workspace_doubles(int64_t npad, int dp, int64_t mc);
 int launch_predict_grad(hipStream_t st, const PredictGradLaunch& g);
+// the apply stage alone: V = C k* in the layout [roundup(m, 64) / 64][npad][64] at g.work, whose rows are written up to
+// ceil(n / 128) * 128 only, followed by the partial |v|^2 (g.alpha, g.ls and the outputs are not read); g.work holds
+// predict_grad_apply_workspace_doubles(npad, roundup(m, 64)) doubles
+size_t predict_grad_apply_workspace_doubles(int64_t npad, int64_t mc);
+int launch_predict_grad_apply(hipStream_t st, const PredictGradLaunch& g);
+// ---- joint.hip: the joint predictive at m <= kPredictGradChunk test points -----------------------
+struct JointLaunch {
+  const double* V = nullptr;      // launch_predict_grad_apply's V for the same n, npad, m, ts
+  const double* ts = nullptr;     // [roundup(m, 64) * dp] scaled test points, zero rows behind the m live ones
+  const double* alpha = nullptr;  // [npad]
+  const double* xs = nullptr;     // [npad * dp] scaled rows
+  int64_t n = 0, npad = 0, m = 0;
+  int dp = 0;
+  KernParams kp{0, 1.0, 0.0, 0.0};
+  double diag_add = 0.0;          // added to the diagonal of Sigma
+  double* part = nullptr;         // joint_partial_doubles(n, m) doubles
+  double* mean = nullptr;         // [m], nullable
+  double* cov = nullptr;          // Sigma = K** - V^T V + diag_add I with leading dimension ldc, nullable
+  int64_t ldc = 0;
+  // true: ldc >= roundup(m, 64) and the rows / columns m .. roundup(m, 64) - 1 receive the identity's entries (a matrix
+  // handed to launch_potrf); false: ldc >= m and nothing beyond the m x m block is written
+  bool pad_identity = false;
+};
+// the contraction over the training rows is split into this many pieces of *chunk_rows rows (a multiple of 128) each: a
+// function of (n, m) alone, so a call's bits are too
+int joint_splits(int64_t n, int64_t m, int64_t* chunk_rows);
+size_t joint_partial_doubles(int64_t n, int64_t m);
+int launch_joint(hipStream_t st, const JointLaunch& g);
+// f[s][c] = mu[c] + sum_{j <= c} L[c][j] z[s][j] (L lower with leading dimension ldl; z, f [s][m] row-major)
+void launch_joint_draw(hipStream_t st, const double* L, int64_t ldl, const double* z, const double* mu, int64_t m, int64_t s,
+                       double* f);
+// per row of f [s][m]: the highest value and its index, the lowest on ties (idx, val [s], each nullable)
+void launch_joint_argmax(hipStream_t st, const double* f, int64_t m, int64_t s, int64_t* idx, double* val);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

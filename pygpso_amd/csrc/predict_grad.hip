@@ -302,6 +302,29 @@ size_t predict_grad_workspace_doubles(int64_t npad, int dp, int64_t mc) {
   return (size_t)mc * npad + nrb * mc + ncb * (size_t)(3 + 2 * dp) * mc;
 }
 
+size_t predict_grad_apply_workspace_doubles(int64_t npad, int64_t mc) {
+  return (size_t)mc * npad + (size_t)(npad / kRowBlock) * mc;
+}
+
+// the apply stage alone, for joint.hip: the launch launch_predict_grad makes first, V and pv at the same places of g.work
+int launch_predict_grad_apply(hipStream_t st, const PredictGradLaunch& g) {
+  if (g.n < 1 || g.n > g.npad || g.npad % kRowBlock != 0 || g.dp < 4 || g.dp % 4 != 0 || g.dp > 48 || g.m < 1 || g.m > kPredictGradChunk) {
+    note_launch_error("launch_predict_grad_apply: shape outside the kernels'");
+    return -1;
+  }
+  const int64_t mc = (g.m + kCols - 1) / kCols * kCols;
+  const int nrb = (int)((g.n + kRowBlock - 1) / kRowBlock);
+  PgArgs a;
+  a.C = g.C; a.alpha = nullptr; a.xs = g.xs; a.ts = g.ts;
+  a.V = g.work;
+  a.pv = a.V + (size_t)mc * g.npad;
+  a.pq = nullptr;
+  a.n = g.n; a.npad = g.npad; a.mc = mc; a.dp = g.dp; a.kernel = g.kp.kernel; a.variance = g.kp.variance;
+  hipLaunchKernelGGL(pg_apply_kernel, dim3((unsigned)(mc / kCols), (unsigned)nrb), dim3(kThreads),
+                     (kRowBlock * kStageLd + kStage * (g.dp + 1)) * 8 + kCols * (g.dp + 1) * 8, st, a);
+  return 0;
+}
+
 int launch_predict_grad(hipStream_t st, const PredictGradLaunch& g) {
   if (g.n < 1 || g.n > g.npad || g.npad % kRowBlock != 0 || g.dp < 4 || g.dp % 4 != 0 || g.d < 1 || g.d > g.dp || g.dp > 48 || g.m < 1 ||
       g.m > kPredictGradChunk) {

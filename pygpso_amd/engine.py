@@ -643,6 +643,47 @@ class HipGPEngine:
                                                 L.MEM_HOST))
         return mean, var, dmean, dvar
 
+    def predict_joint(self, xs, diag_add=0.0, out=None):
+        """The joint predictive at the M <= 1024 rows of ``xs``: (mean [M], cov [M, M]) float64, cov = K** - V^T V +
+        diag_add I, exactly symmetric (``gpso_predict_joint``; GPflow's ``predict_f(full_cov=True)``).  ``diag_add``: 0 for
+        the latent f, the predictive noise for y.  float64 and mixed engines; any resident posterior but an adopted one.
+        ``out`` may be a pair (mean [M] or None, cov [M, M]) of contiguous float64 CUDA tensors to keep the results on the
+        device."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        if out is not None:
+            mean_t, cov_t = out
+            if cov_t is None or tuple(cov_t.shape) != (m, m) or not cov_t.is_contiguous():
+                raise ValueError(f"out[1] must be a contiguous [{m}, {m}] tensor")
+            for t in out:
+                if t is not None:
+                    self._order_after(t)
+            self._check(self._lib.gpso_predict_joint(self._h, ptr, dt, mem, m, float(diag_add),
+                                                     None if mean_t is None else C.c_void_p(mean_t.data_ptr()),
+                                                     C.c_void_p(cov_t.data_ptr()), L.MEM_DEVICE))
+            return mean_t, cov_t
+        mean, cov = np.empty(m, dtype=np.float64), np.empty((m, m), dtype=np.float64)
+        self._check(self._lib.gpso_predict_joint(self._h, ptr, dt, mem, m, float(diag_add), C.c_void_p(mean.ctypes.data),
+                                                 C.c_void_p(cov.ctypes.data), L.MEM_HOST))
+        return mean, cov
+
+    def sample_joint(self, xs, z, diag_add, want_samples=True):
+        """S draws of the joint predictive at the M <= 1024 rows of ``xs`` from the standard normals ``z`` [S, M]:
+        mean + chol(cov + diag_add I) z per draw (``gpso_sample_joint``; GPflow's ``predict_f_samples``).  Returns
+        (samples [S, M] or None, best_idx [S], best_val [S]): the draws, and per draw the index (the lowest on ties) and
+        the value of its highest entry.  ``want_samples=False`` leaves the draws on the device.  A cov + diag_add I that is
+        not positive definite raises ``numpy.linalg.LinAlgError``: pass a larger ``diag_add`` (jitter)."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        if z.ndim != 2 or z.shape[1] != m:
+            raise ValueError(f"z must be [S, M] with M={m}, got {z.shape}")
+        s = int(z.shape[0])
+        samples = np.empty((s, m), dtype=np.float64) if want_samples else None
+        best_idx, best_val = np.empty(s, dtype=np.int64), np.empty(s, dtype=np.float64)
+        self._check(self._lib.gpso_sample_joint(self._h, ptr, dt, mem, m, float(diag_add), L.dptr(z), s,
+                                                None if samples is None else L.dptr(samples), L.i64ptr(best_idx),
+                                                L.dptr(best_val)))
+        return samples, best_idx, best_val
+
     def best_ucb(self, xs, varsigma, seg_off=None):
         """gp_eval_best_ucb per segment -> (idx, mean, var, ucb) arrays of length nseg."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)

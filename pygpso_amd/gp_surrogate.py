@@ -30,7 +30,7 @@ import scipy.optimize
 from scipy.special import erfcinv
 
 from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero, _LbfgsbSearch
-from .model import HipGPR
+from .model import HipGPR, _standard_normals
 from .sgpr import HipSGPR
 from .svgp import HipSVGP
 from .vgp import HipVGP, carried_order
@@ -486,6 +486,45 @@ class GPSurrogate:
         if isinstance(self.gpflow_model.engine, HipGPEngineGroup):
             raise NotImplementedError("gp_predict_grad / polish: not offered on a multi-GPU engine group")
         return self.gpflow_model.predict_y_grad(np.ascontiguousarray(normed_coords, dtype=np.float64))
+
+    def _joint_model(self, what):
+        self._require_model()
+        from .distributed import HipGPEngineGroup
+
+        if isinstance(self.gpflow_model.engine, HipGPEngineGroup):
+            raise NotImplementedError(f"{what}: not offered on a multi-GPU engine group")
+        return self.gpflow_model
+
+    def gp_predict_joint(self, normed_coords, noise=False):
+        """The JOINT predictive at the rows of ``normed_coords`` (M <= 1024): (mean [M], cov [M, M]) of the latent f, or
+        of y (``noise=True``: the model's predictive noise on the diagonal); stores nothing.  One ``gpso_predict_joint``
+        call -- GPflow's ``predict_f(full_cov=True)`` on the reference's model."""
+        model = self._joint_model("gp_predict_joint")
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        mean, cov = model.predict_y(coords, full_cov=True) if noise else model.predict_f(coords, full_cov=True)
+        return np.asarray(mean)[:, 0], cov
+
+    def _draw(self, model, normed_coords, n_draws, rng, diag_add, want_samples):
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        z = _standard_normals(rng, n_draws, coords.shape[0])
+        return model._predicting(lambda: model.engine.sample_joint(coords, z, diag_add, want_samples=want_samples))
+
+    def gp_sample(self, normed_coords, n_draws, rng=None, noise=False, jitter=1e-6):
+        """``n_draws`` draws [S, M] from the joint posterior at the rows of ``normed_coords`` (M <= 1024): of the latent f,
+        or of y (``noise=True``).  ``rng``: a seed or a ``numpy.random.Generator`` (the normals are drawn on the host);
+        ``jitter`` is added to the diagonal before the Cholesky, as GPflow's ``predict_f_samples`` adds its default_jitter.
+        Stores nothing."""
+        model = self._joint_model("gp_sample")
+        diag_add = jitter + (model.predictive_noise() if noise else 0.0)
+        return self._draw(model, normed_coords, n_draws, rng, diag_add, True)[0]
+
+    def thompson_select(self, normed_coords, n_draws, rng=None, jitter=1e-6):
+        """Thompson sampling over the candidate rows of ``normed_coords`` (M <= 1024): (indices [S], values [S]), the
+        arg-max (the first on ties) and the maximum of each of ``n_draws`` latent draws of ``gp_sample`` for the same
+        ``rng`` -- S candidates for an evaluation pool in one step rather than S times the same arg-max.  The draws never
+        leave the device.  Stores nothing."""
+        _, idx, val = self._draw(self._joint_model("thompson_select"), normed_coords, n_draws, rng, jitter, False)
+        return idx, val
 
     def polish(self, normed_coords, objective="ucb", box=None, options=None):
         """Gradient polish of R candidate points on the surrogate: from each row of ``normed_coords`` [R, D], L-BFGS-B

@@ -69,6 +69,14 @@ def _as_result(a):
     return np.asarray(a, dtype=np.float64).reshape(-1, 1).view(_Result)
 
 
+def _standard_normals(rng, num_samples, m):
+    """[S, M] standard normals from a seed or a ``numpy.random.Generator`` (None: a fresh generator)."""
+    if int(num_samples) < 1:
+        raise ValueError(f"num_samples={num_samples}: at least one draw")
+    gen = rng if isinstance(rng, np.random.Generator) else np.random.default_rng(rng)
+    return gen.standard_normal((int(num_samples), int(m)))
+
+
 class HipGPR:
     def __init__(self, data, kernel, mean_function=None, noise_variance=1.0e-3, dtype="float64",
                  device=0, engine=None, engine_options=None, escalate=True, devices=None, noise_diag=None,
@@ -407,15 +415,33 @@ class HipGPR:
                 if not self._escalate(err):
                     raise
 
-    def predict_y(self, Xnew):
-        """(mean [M,1], var [M,1]); the variance includes the likelihood (noise) variance."""
+    def predict_y(self, Xnew, full_cov=False):
+        """(mean [M,1], var [M,1]); the variance includes the likelihood (noise) variance.  ``full_cov=True``:
+        (mean [M,1], cov [M,M]) with ``predictive_noise()`` on the diagonal (M <= 1024)."""
         Xnew = np.asarray(Xnew)
+        if full_cov:
+            return self._predict_joint(Xnew, self.predictive_noise())
         mean, var = self._predicting(lambda: self.engine.predict(Xnew))
         return _as_result(mean), _as_result(var)
 
-    def predict_f(self, Xnew):
+    def predict_f(self, Xnew, full_cov=False):
+        """Latent mean and variance; ``full_cov=True``: (mean [M,1], cov [M,M]), GPflow's ``predict_f(Xnew, full_cov=True)``."""
+        if full_cov:
+            return self._predict_joint(np.asarray(Xnew), 0.0)
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.likelihood.variance)
+
+    def _predict_joint(self, Xnew, diag_add):
+        mean, cov = self._predicting(lambda: self.engine.predict_joint(Xnew, diag_add))
+        return _as_result(mean), cov
+
+    def predict_f_samples(self, Xnew, num_samples=1, jitter=1e-6, rng=None):
+        """``num_samples`` draws [S, M] of the latent f at the rows of Xnew (M <= 1024) from their JOINT posterior: mean +
+        chol(cov + jitter I) z, GPflow's ``predict_f_samples`` (1e-6 is its default_jitter).  ``rng``: a seed or a
+        ``numpy.random.Generator`` -- the normals are drawn on the host, so a seed reproduces the draws."""
+        Xnew = np.asarray(Xnew)
+        z = _standard_normals(rng, num_samples, Xnew.shape[0])
+        return self._predicting(lambda: self.engine.sample_joint(Xnew, z, jitter))[0]
 
     def predictive_noise(self):
         """The likelihood's variance in ``predict_y`` (the families with another likelihood override this)."""

@@ -206,9 +206,11 @@ class HipSGPR(HipGPR):
     def _escalate(self, err, fit=False):
         return False
 
-    def predict_f(self, Xnew):
+    def predict_f(self, Xnew, full_cov=False):
         """Latent mean and variance.  After a shifted install (``install_delta`` > 0) the variance keeps the shift's
         surplus delta (k** - |Lu^-1 k*u|^2) >= 0: never below the exact latent variance."""
+        if full_cov:
+            return self._predict_joint(np.asarray(Xnew), 0.0)
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.likelihood.variance)
 

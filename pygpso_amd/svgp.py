@@ -141,7 +141,9 @@ class HipSVGP(HipSGPR):
             self.install_delta = self.engine.svgp_posterior(name, self._pack_theta(), k, tm, c)
             self._resident = True
 
-    def predict_f(self, Xnew):
+    def predict_f(self, Xnew, full_cov=False):
+        if full_cov:
+            return self._predict_joint(np.asarray(Xnew), 0.0)
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.predictive_noise())
 

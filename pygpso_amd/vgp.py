@@ -153,7 +153,9 @@ class HipVGP(HipGPR):
             return self.likelihood.scale ** 2 * self.likelihood.df / (self.likelihood.df - 2.0)
         return self.likelihood.variance
 
-    def predict_f(self, Xnew):
+    def predict_f(self, Xnew, full_cov=False):
+        if full_cov:
+            return self._predict_joint(np.asarray(Xnew), 0.0)
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.predictive_noise())
 
