@@ -135,7 +135,20 @@ typedef struct gpso_ctx gpso_ctx;
                                    /* modelled makespan (C3: one -- 256 workgroups of 288 k-steps instead of 2 048 of 8 .. 64; ragged   */
                                    /* batches and batches whose live count only the device knows: one row block per workgroup);        */
                                    /* 0: one row block per workgroup always (rounds 1-5); v >= 2: exactly min(v, row blocks)            */
-                                   /* workgroups per leaf tile (tests).  Per context.   Same bits whatever the value.                   */
+                                   /* workgroups per leaf tile, -1: exactly one, whatever the batch (tests).  Per context.  Same bits   */
+                                   /* whatever the value.                                                                               */
+#define GPSO_OPT_PARK_BYTES 14     /* the default split predict kernel (fp16 split, fused step, one chunk of the fp16 contraction:      */
+                                   /* D <= 28) regenerates every k-step's cross-Gram pieces in every row block a workgroup loops over.  */
+                                   /* v > 0: a budget in bytes for PARKING the lowest even k-steps instead -- stored once by a          */
+                                   /* workgroup's first row block (32 KB per step and workgroup, in a buffer of the context that is     */
+                                   /* allocated by the first launch that parks and reused from then on) and reloaded by its later row   */
+                                   /* blocks, odd steps and diagonal steps generated as ever; as many steps as the budget pays for,     */
+                                   /* none where a workgroup has fewer than three row blocks or the kernel's LDS has no room for the    */
+                                   /* reload windows.  0: off -- exactly the kernel without it.  Per context.  Same bits whatever the   */
+                                   /* value.  gpso_last_count(ctx, 5) and (ctx, 6) say what the last launch did.                        */
+                                   /* Default 256 MB (268435456): the best of 0 / 64 / 128 / 256 MB at C3 -- +3.6 / +3.7 % predictions/s */
+                                   /* on two boxes, level with off on a third; C4 share +2.4 % | level (profiles/park_reload_ab_*.txt). */
+                                   /* The buffer (201 MB at C3) is held until the context is destroyed.                                 */
 /* floating-point options (gpso_set_option_f64): tolerances of the self-test */
 #define GPSO_OPTF_TOL_VAR 100  /* max |d var| at the training inputs, relative to the kernel variance (default 1e-4; GPSO_F32: 1e-3) */
 #define GPSO_OPTF_TOL_MEAN 101 /* max |d mean| at the training inputs, relative to max |y - c|   (default 1e-4; GPSO_F32: 1e-3) */
@@ -724,6 +737,8 @@ double gpso_last_ms(gpso_ctx* ctx, int what);
  * three fp16 MFMAs per f32 product).
  * what = 3: how many workgroups shared a leaf tile's row blocks in the last launch of a split predict kernel (GPSO_OPT_ROW_LOOP;
  * per context: the last launch THIS context made; for tests and tools).
+ * what = 5, 6: k-steps per leaf tile that the last launch of a split predict kernel parked (5) and reloaded instead of generating
+ * them (6) under GPSO_OPT_PARK_BYTES; 0 where it parked nothing.  Per context, like what = 3.
  * what = 4: bytes of device memory the buffers of ALL contexts of this process hold now (process-wide, whichever ctx asks;
  * back where it stood once a context is destroyed; for tests and tools). */
 #define GPSO_FITMATH_NONE 0

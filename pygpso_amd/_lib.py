@@ -40,6 +40,7 @@ OPT_CONTRACTION = 10
 OPT_FUSED_PREP = 11
 OPT_FIT_OVERLAP = 12
 OPT_ROW_LOOP = 13
+OPT_PARK_BYTES = 14
 CONTRACTION_AUTO, CONTRACTION_F32, CONTRACTION_F16 = 0, 1, 2
 SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FUSED32 = 0, 1, 2, 3
 OPTF_TOL_VAR, OPTF_TOL_MEAN = 100, 101

@@ -65,6 +65,12 @@ thread_local std::string g_create_error;
 
 constexpr int kMaxD = 48;                      // padded input dimension limit (LDS budgets)
 constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass of the tile kernel
+// GPSO_OPT_PARK_BYTES as a context is created: 256 MB, the best median of the sweeps 0 | 64 | 128 | 256 MB at C3
+// (profiles/park_reload_ab_sweep_c3.txt, park_reload_ab_pairs.txt; -DGPSO_PARK_BYTES_DEFAULT=... builds the other arms)
+#ifndef GPSO_PARK_BYTES_DEFAULT
+#define GPSO_PARK_BYTES_DEFAULT (256 << 20)
+#endif
+constexpr int64_t kParkBytesDefault = GPSO_PARK_BYTES_DEFAULT;
 constexpr int kHyperHeader = 8;                // doubles in front of the lengthscales
 static_assert(kThetaMaxLs == kGradMaxLs, "a Theta holds as many lengthscales as the gradient kernels take");
 
@@ -206,7 +212,7 @@ struct gpso_ctx {
   int rank = 0, world = 1;
   // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit; [3] workgroups per
   // leaf tile of this context's last split-kernel launch
-  int64_t last_count[4] = {0, 0, 0, 0};
+  int64_t last_count[7] = {0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
   int cu_count = 256;  // compute units of `device` (gpso_create): sizes the split predict kernels' and the bf16 GEMMs' grids
   std::string err;
   Engine* eng = nullptr;
@@ -419,6 +425,22 @@ struct EngineT : Engine {
   int gen_mode = GPSO_GEN_AUTO;
   int split_variant = GPSO_SPLIT_KERNEL_AUTO;  // GPSO_OPT_SPLIT_KERNEL
   int row_loop = 1;  // GPSO_OPT_ROW_LOOP (leaf_split.hpp: leaf_row_splits)
+  // GPSO_OPT_PARK_BYTES (leaf_split.hpp, PARK): the budget of the parked cross-Gram pieces of the default split predict kernel,
+  // and the buffer that holds them -- allocated by the first launch that parks, reused by every later call and chunk
+  int64_t park_bytes = kParkBytesDefault;
+  DevBuf park_buf;
+  size_t park_refused = 0;  // the smallest size an allocation of park_buf failed at: not asked for again (a new budget clears it)
+  static void* park_cb(void* owner, size_t bytes) {
+    auto* self = static_cast<EngineT*>(owner);
+    if (self->park_buf.bytes >= bytes) return self->park_buf.p;
+    if (self->park_refused != 0 && bytes >= self->park_refused) return nullptr;
+    if (self->park_buf.ensure(bytes, self->st(), false)) {  // (no room: this launch and the later ones of its size park nothing)
+      (void)hipGetLastError();
+      self->park_refused = bytes;
+      return nullptr;
+    }
+    return self->park_buf.p;
+  }
   int contraction = GPSO_CONTRACTION_AUTO;     // GPSO_OPT_CONTRACTION
   // the x.x* contraction of the fp16-split kernel runs on the fp16 pipe under float generation (D_pad + 1 slots in at most
   // two chunks of 32: every D this library accepts).  Measured in one process on one posterior (tools/c16_check.py,
@@ -543,8 +565,13 @@ struct EngineT : Engine {
         fit_planes_mode = value;
         return GPSO_OK;
       case GPSO_OPT_ROW_LOOP:
-        if (value < 0) return ctx->fail(GPSO_E_ARG, "row loop: 0, 1 or a split count >= 2");
+        if (value < -1) return ctx->fail(GPSO_E_ARG, "row loop: 0, 1, a split count >= 2 or -1 (one workgroup per leaf tile)");
         row_loop = value;
+        return GPSO_OK;
+      case GPSO_OPT_PARK_BYTES:
+        if (value < 0) return ctx->fail(GPSO_E_ARG, "park bytes: 0 (off) or a budget in bytes");
+        park_bytes = value;
+        park_refused = 0;
         return GPSO_OK;
       case GPSO_OPT_FIT_OVERLAP:
         if (value < 0) return ctx->fail(GPSO_E_ARG, "fit overlap must be >= 0");
@@ -2512,6 +2539,7 @@ struct EngineT : Engine {
           a.npad = npad; a.dp4 = dp / 4; a.mpad = mp; a.n_rows = n;
           a.step32 = split_variant == GPSO_SPLIT_KERNEL_FUSED32; a.row_loop = row_loop; a.cu_count = ctx->cu_count;
           a.splits_out = &ctx->last_count[3];
+          a.park_bytes = park_bytes; a.park_scratch = &EngineT::park_cb; a.park_owner = this; a.park_out = &ctx->last_count[5];
           rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
         }
       } else {
@@ -4874,7 +4902,7 @@ int gpso_comm_abort(gpso_ctx* ctx) {
 }
 
 int64_t gpso_last_count(gpso_ctx* ctx, int what) {
-  if (!ctx || what < 0 || what > 4) return -1;
+  if (!ctx || what < 0 || what > 6) return -1;
   return what == 4 ? g_dev_bytes_held.load(std::memory_order_relaxed) : ctx->last_count[what];
 }
 

@@ -94,6 +94,12 @@ struct SplitLeafLaunch {
   int row_loop = 1;     // GPSO_OPT_ROW_LOOP of the launching context (leaf_split.hpp: leaf_row_splits)
   int cu_count = 256;   // compute units of the launching context's device
   int64_t* splits_out = nullptr;  // (nullable) receives the workgroups per leaf tile the launcher chose
+  // GPSO_OPT_PARK_BYTES of the launching context (leaf_split.hpp, PARK): the budget (0: off), and who grants a device buffer of
+  // at least `bytes` for the parked pieces (nullptr to decline: the launch then parks nothing); owner: the launching context
+  int64_t park_bytes = 0;
+  void* (*park_scratch)(void* owner, size_t bytes) = nullptr;
+  void* park_owner = nullptr;
+  int64_t* park_out = nullptr;  // (nullable) receives, per leaf tile: [0] k-steps parked, [1] k-steps reloaded instead of generated
 };
 // FUSED: the fused step (round 4) or round 3's two-phase step -- same bits; one explicit instantiation per slice
 // (TG, FUSED, KS) in predict_split_*.hip

@@ -689,7 +689,20 @@ __device__ __forceinline__ void leaf_bf16_fused_half(int lane, int dp4, const u3
 // (pack_xs_f16_kernel's order) and c16_scale at their scale (device: [1] = 2^sx, [2] = 2^-2sx)
 // M32P: the fused step on the 32x32x16 matrix instruction (leaf_split_m32.hpp; fp16 split with the fp16 contraction only)
 // XP: the last chunk of the fp16 contraction packs its two small products into one instruction (leaf_contract)
-template <int NS, typename TG, int KERNEL, bool F16 = false, bool FUSED = false, int C16 = 0, bool M32P = false, int XP = 0>
+// PARK: a workgroup that loops over row blocks regenerates every k-step's fp16 pieces in every later row block, bit for bit
+// ((n_blocks + 1) / 2 = 4.5 x at N = 2048).  Generating is bound by the vector issue port, reloading everything by HBM (both
+// measured: profiles/r06_predict_experiments.txt, section 12) -- so this kernel does HALF of each: the lowest park_steps EVEN
+// k-steps (the most reused) are PARKED once -- in the workgroup's first, heaviest row block, each wave storing its own 4 KB from
+// the step that applies them -- and RELOADED in every later row block, where they lie below that block's diagonal steps: the
+// fused step in front of a reloaded step runs the body that generates nothing (GMODE 0), and the pieces come from the wave's
+// own 4 KB LDS window, filled by LDS-DMA from its slot of `park`.  Odd steps and a row block's own eight diagonal steps (which
+// carry the mean's shares) are generated as ever.  Same pieces, same products, same k order: the same bits as PARK = false.
+// A window is READ by its own wave only and FILLED by a wave of the DMA half (wave w fills its own and that of wave w + 4), so a
+// workgroup barrier stands between every read of a window and the next DMA into it, and between a DMA's wait (the issuing
+// wave's vmcnt(0) in leaf_sync, a full step after the issue) and the read of what it brought: the barriers of the steps in the
+// loop, and one of its own behind the read of step 0 at the top of a later row block.
+// Default kernels only: fp16 split, fused step, one chunk of the fp16 contraction.
+template <int NS, typename TG, int KERNEL, bool F16 = false, bool FUSED = false, int C16 = 0, bool M32P = false, int XP = 0, bool PARK = false>
 __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     const u32x4* __restrict__ linv_b, const TG* __restrict__ xs_p, const TG* __restrict__ xnorm,
     const float* __restrict__ alpha, const TG* __restrict__ leaves_s,
@@ -698,8 +711,10 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     const float* __restrict__ inv_scale_a, float inv_scale_b, const float* __restrict__ c16_scale, int q_max,
     const float* __restrict__ raw /* nullable (C16 only): the caller's UNSCALED float leaves [raw_m][raw_d] -- the prologue
     scales them itself ((float)(x / l), rows beyond raw_m are padding): no prep launch in front of this kernel */,
-    const double* __restrict__ raw_ls, int64_t raw_m, int raw_d) {
+    const double* __restrict__ raw_ls, int64_t raw_m, int raw_d,
+    unsigned char* __restrict__ park /* PARK: park_steps x 32 KB per workgroup of the launch */, int park_steps) {
   constexpr int RT = 16, CT = 2, NW = 8;
+  static_assert(!PARK || (FUSED && F16 && NS == 2 && C16 == 1 && !M32P && !kLeafStagger && sizeof(TG) == 4), "PARK: the default kernels only");
   constexpr TG SC = (TG)GenScale<KERNEL>::SC;
   constexpr bool M32 = M32P && FUSED && F16 && NS == 2 && C16 != 0 && sizeof(TG) == 4;
   static_assert(M32 == M32P, "the 32x32x16 step exists for the fp16 split with the fp16 contraction");
@@ -844,13 +859,17 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 
   // the first DMAs of a row block: its L^-1 pieces of step 0 into buffer 0 and the inputs of steps 0 and 1 (every row block has
   // at least eight steps)
-  auto issue_block_start = [&]() {
+  auto issue_block_start = [&](bool with_x0 /* false: step 0 of the row block is reloaded (PARK) and needs no inputs */) {
     issue_panel(0, 0);
-    issue_x(0);
-    issue_x(1);
+    if (with_x0) issue_x(0);
+    int one = 1;
+    // (PARK has two scalar registers fewer to spare: opaque, the addresses of step 1's inputs are formed here, once per row block,
+    // instead of living -- spilled -- across the loops as loop invariants)
+    if constexpr (PARK) asm volatile("" : "+s"(one));
+    issue_x(one);
   };
   set_row_block(0);
-  issue_block_start();
+  issue_block_start(true);
   TG cm = TG(-2) * SC;
   float nb_c16[CT] = {0, 0};
   if constexpr (C16) {
@@ -931,10 +950,63 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   // (Measured and not kept: the next row block's first DMAs issued during the LAST step of the one in hand -- its buffers are
   // free there.  The second set of wave-uniform pointers spills 87 scalar registers into vector lanes inside the hot loop: C3
   // 0.7193 | 0.7221 ms against 0.7464 | 0.7304 without the prefetch, C4 / C5 +2.5 %.  r06_predict_experiments.txt.)
+  // ---- PARK: this wave's window (behind the leaf fragments) and its slots: slot s of workgroup w at ((w P + s) 8 + wave) 4 KB --
+  u32x4* const pwin = reinterpret_cast<u32x4*>(xsl + 3 * xstride + (size_t)NW * xfrag) + wave * (NS * CT * 64);
+  // (ONE wave-uniform 64-bit base lives across the loops -- this wave's slot 0; a slot is 32 KB further per step)
+  const unsigned char* const park_w =
+      PARK ? park + ((size_t)(((unsigned)(leaf_tile * S + split) * (unsigned)park_steps) * NW + wave) << 12) : nullptr;
+  auto park_at = [&](int slot) { return uniform(park_w + ((size_t)(unsigned)slot << 15)); };
+  auto park_store = [&](int slot, const bf16x8 (&b)[NS][CT]) {  // (streaming stores: read back once per later row block, by this wave)
+    // (a GLOBAL store by its address space: through the rebuilt generic pointer it would be a flat one, which counts on lgkmcnt too)
+    auto* dst = (__attribute__((address_space(1))) u32x4*)(park_at(slot));
+#pragma unroll
+    for (int sp = 0; sp < NS; ++sp)
+#pragma unroll
+      for (int t = 0; t < CT; ++t) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, b[sp][t]), dst + (sp * CT + t) * 64 + lane);
+  };
+  // slot -> window: four 1 KB DMAs around the window's centre.  Like every DMA of the fused step they are issued by waves 0-3,
+  // which have the time (see DW above): wave w fills its own window and that of wave w + 4 -- whose slot lies 16 KB behind its
+  // own in `park`, as its window does in LDS.  A window is read by its owner a barrier or more after the issuing wave's wait.
+  auto park_issue = [&](int slot) {
+    if (!dma_wave) return;
+    static_for<0, NW / DW>([&](auto h_) {
+      constexpr int h = decltype(h_)::value;
+      const unsigned char* src = uniform(park_at(slot) + h * (DW * 4096) + 2048);
+      unsigned char* centre = reinterpret_cast<unsigned char*>(pwin) + h * (DW * 4096) + 2048;
+      static_for<0, NS * CT>([&](auto j_) {
+        constexpr int j = decltype(j_)::value;
+        glds16_off<j * 1024 - 2048>(src + lane16, centre);
+      });
+    });
+  };
+  auto park_read = [&](bf16x8 (&b)[NS][CT]) {  // four ds_read_b128
+#pragma unroll
+    for (int sp = 0; sp < NS; ++sp)
+#pragma unroll
+      for (int t = 0; t < CT; ++t) b[sp][t] = __builtin_bit_cast(bf16x8, pwin[(sp * CT + t) * 64 + lane]);
+  };
+  // even steps below the row block's diagonal steps and below 2 park_steps are parked (a workgroup's first row block) or reloaded
+  // (its later row blocks).  One word: plim > 0 -- reload the even steps below plim; plim < 0 -- park the even steps below -plim
+  int plim = 0;
+  auto park_limits = [&](int j_mine) {
+    const int lim = PARK ? min(2 * park_steps, q_diag0) : 0;
+    plim = j_mine == 0 ? -lim : lim;
+  };
+  auto reloaded = [&](int g) { return PARK && (g & 1) == 0 && g < plim; };
+  // the first DMAs of a LATER row block: ... and its parked step 0 (the window was last read in front of the diagonal steps)
+  auto issue_next_block_start = [&](int j_mine) {
+    park_limits(j_mine);
+    issue_block_start(!reloaded(0));
+    if constexpr (PARK) {
+      if (plim > 0) park_issue(0);
+    }
+  };
+  (void)park_store; (void)park_issue; (void)park_read; (void)reloaded;
+  park_limits(0);
   for (int rbj = 0;; ++rbj) {
   if (!kEarlyDma && rbj > 0) {
     set_row_block(rbj);
-    issue_block_start();
+    issue_next_block_start(rbj);
   }
   if constexpr (M32) {
 #pragma unroll
@@ -953,7 +1025,8 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 
   auto issue_for = [&](int k) {
     if (k + 1 < q_lim) issue_panel(k + 1, STAG ? (k + 1) % 3 : (k + 1) & 1);
-    if (k + 2 < q_end && k + 2 <= q_lim) issue_x(k + 2);  // (step q_lim is still GENERATED by step q_lim - 1: padding points, alpha = 0)
+    // (step q_lim is still GENERATED by step q_lim - 1: padding points, alpha = 0; a RELOADED step needs no inputs)
+    if (k + 2 < q_end && k + 2 <= q_lim && !reloaded(k + 2)) issue_x(k + 2);
   };
   if constexpr (FUSED) {
     // Interval q (between workgroup barriers q - 1 and q), every wave alike: the DMAs of the L^-1 pieces of step q + 1
@@ -970,7 +1043,12 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
       if (q_diag0 == 0) leaf_gen32<KERNEL, true, C16>(dp4, xsl, xb, ml, nb32, (float)cm, vc, bfrag32, macc32);
       else leaf_gen32<KERNEL, false, C16>(dp4, xsl, xb, ml, nb32, (float)cm, vc, bfrag32, macc32);
     } else {
-      if (q_diag0 == 0) leaf_bf16_gen<NS, TG, KERNEL, F16, true, C16, 2, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
+      if (reloaded(0)) {  // (PARK, workgroup-uniform) step 0 from the window
+        park_read(bfrag);
+        // step 0 (q = 0) issues the DMA of step 2 into EVERY window as soon as it starts, waves 0-3 on behalf of waves 4-7: all
+        // eight reads of step 0 must have returned first.  (In the loop the barrier of the reload step does this.)
+        leaf_sync();
+      } else if (q_diag0 == 0) leaf_bf16_gen<NS, TG, KERNEL, F16, true, C16, 2, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
       else leaf_bf16_gen<NS, TG, KERNEL, F16, false, C16, 2, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
     }
     // Measured and NOT kept (tools/ab_time.py, same box, f16x3 at C3: two-phase 0.850 | this 0.7955 ms): the step's DMAs
@@ -981,9 +1059,33 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     // need 5 000; flipping the priority flips who waits, the sum grows); with the fp16 contraction (a third fewer vector
     // instructions per step) the DMA duties dealt over all eight waves again (0.6976 against 0.6897 ms); a fourth product
     // h1 h1' in the fp16 contraction (self-test readings 20 % lower, kernel +2.5 %).
+    // (PARK) step q, whose successor is reloaded: the body that generates nothing, then the window is read -- its DMA was issued
+    // two steps ago and waited for at the end of that step.  The step that follows (even, generating) issues the DMA of the next
+    // reloaded step into the window as soon as it starts: a full step ahead of the wait for it
+#define GPSO_RELOAD_STEP()                                                                                            \
+  {                                                                                                                   \
+    issue_for(q);                                                                                                     \
+    leaf_bf16_fused_step<NS, TG, KERNEL, F16, 0, 0, C16, RTL, XP>(q, q_diag0, lane, dp4,                              \
+                                                                 panel + (q & 1) * NS * RT * 64,                      \
+                                                                 xsl + ((q + 1) % 3) * xstride, xb, nb, cm, vc,       \
+                                                                 bfrag, bnxt, acc, macc);                             \
+    park_read(bnxt);                                                                                                  \
+    leaf_sync();                                                                                                      \
+    for (int sp = 0; sp < NS; ++sp)                                                                                   \
+      for (int t = 0; t < CT; ++t) bfrag[sp][t] = bnxt[sp][t];                                                        \
+  }
 #define GPSO_FUSED_STEP(ASKIP, GMODE)                                                                                 \
   {                                                                                                                   \
     GPSO_BSTAMP(q, 0);                                                                                                \
+    if constexpr (PARK && ASKIP == 0 && GMODE != 0) {                                                                 \
+      if ((q & 1) == 0) {                                                                                             \
+        if (q < -plim) park_store(q >> 1, bfrag);   /* (first row block) the pieces this step applies */              \
+        else if (reloaded(q + 2)) { /* (later row blocks) this step's pieces came from the window: it is free */      \
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                          \
+          park_issue((q + 2) >> 1);                                                                                   \
+        }                                                                                                             \
+      }                                                                                                               \
+    }                                                                                                                 \
     issue_for(q);                                                                                                     \
     GPSO_BSTAMP(q, 1);                                                                                                \
     if constexpr (STAG) {                                                                                             \
@@ -1026,7 +1128,17 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     auto fused_loops = [&](auto rtl_) {
       constexpr int RTL = decltype(rtl_)::value;
       int q = 0;
-      for (; q + 1 < q_diag0; ++q) GPSO_FUSED_STEP(0, 1)
+      if constexpr (PARK) {
+        while (q + 2 < plim) {  // (later row blocks) pairs: an even step that generates, an odd one whose successor is reloaded
+          GPSO_FUSED_STEP(0, 1)
+          ++q;
+          GPSO_RELOAD_STEP()
+          ++q;
+        }
+        for (; q + 1 < q_diag0; ++q) GPSO_FUSED_STEP(0, 1)
+      } else {
+        for (; q + 1 < q_diag0; ++q) GPSO_FUSED_STEP(0, 1)
+      }
       if (q < q_diag0) {  // the last step below the diagonal block generates the block's first step: with its k*.alpha
         GPSO_FUSED_STEP(0, 2)
         ++q;
@@ -1045,6 +1157,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     if (q_max <= q_diag0 + RT / 4) fused_loops(std::integral_constant<int, RT / 2>{});
     else fused_loops(std::integral_constant<int, RT>{});
 #undef GPSO_FUSED_STEP
+#undef GPSO_RELOAD_STEP
   } else {
   // Interval k (between workgroup barriers k - 1 and k): waves 0-3 generate and apply step k; waves 4-7 apply step
   // k and generate step k + 1.  One copy of the code: every wave runs gen(q), apply(q) for q = 0, 1, ...; only the
@@ -1086,7 +1199,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   if (kEarlyDma && more) {  // (workgroup-uniform)
     if constexpr (STAG) leaf_sync();  // (waves 4-7 meet their last barrier in the middle of a step)
     set_row_block(rbj + 1);
-    issue_block_start();
+    issue_next_block_start(rbj + 1);
   }
   // (fp16 split: undo the power-of-two scales of the two operands -- exact)
   double unscale2 = 1.0, unscale_m = 1.0;
@@ -1140,7 +1253,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 }
 
 // How many workgroups share a leaf tile's row blocks (gridDim.y of the split kernels).  GPSO_OPT_ROW_LOOP = 0: nbi, one row block
-// each (rounds 1-5); v >= 2: v (tests); 1 (default): the count with the shortest modelled makespan.  In k-steps: row block bi costs
+// each (rounds 1-5); v >= 2: v, -1: one (tests); 1 (default): the count with the shortest modelled makespan.  In k-steps: row block bi costs
 // 8 (bi + 1), a workgroup kPrologue on top (the leaf prologue + a cold first DMA, from the C3 A/B: 2.7 % of 288 + 8 x that);
 // with S < nbi equal-weight workgroups the chip runs ceil(tiles S / CUs) rounds of the heaviest split; with one row block per
 // workgroup, heaviest first, the dispatcher packs them to within a light block of the mean.  C3 (256 tiles): 1; C4 share
@@ -1150,6 +1263,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 // mode: the launching context's GPSO_OPT_ROW_LOOP; ncu: its device's compute units.
 inline int leaf_row_splits(int mode, int64_t ltiles, int nbi, int ncu, bool live_known) {
   if (mode == 0 || nbi <= 1) return nbi;
+  if (mode < 0) return 1;  // (tests: one workgroup per leaf tile walks every row block, whatever the batch)
   if (mode >= 2) return std::min(mode, nbi);
   if (!live_known) return nbi;
   constexpr double kPrologue = 1.2;
@@ -1208,14 +1322,51 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   const bool m32 = kHasM32 && a.step32;
   // xp: the last chunk of the fp16 contraction uses <= 16 slots (the scaled inputs and the norm slot behind them)
   const bool xp = C16 != 0 && dp4 * 4 + 1 - 32 * (C16 - 1) <= 16;
-#define GPSO_L1(K, M32, XP)                                                                         \
+  // PARK (GPSO_OPT_PARK_BYTES): the lowest P even k-steps are parked by a workgroup's first row block and reloaded by its later
+  // ones.  Reloadable are the even steps below the diagonal steps of a workgroup's SECOND row block -- the heaviest of those is
+  // row block nbi - 1 - S (split S - 1): 4 (nbi - 1 - S) steps, none unless a workgroup owns at least three row blocks at S = 1.
+  // P = what the budget pays for (32 KB per parked step and workgroup of the launch), where the kernel exists, its window (one
+  // 4 KB per wave) still fits the 160 KB of LDS, and the context grants the scratch; otherwise 0: the kernel without PARK.
+  constexpr bool kHasPark = FUSED && F16 && NS == 2 && C16 == 1 && sizeof(TG) == 4 && !kLeafStagger;
+  constexpr size_t kParkWindow = (size_t)8 * 4096, kParkStepBytes = (size_t)8 * 4096;
+  int park_steps = 0;
+  unsigned char* park = nullptr;
+  if (kHasPark && !m32 && a.park_bytes > 0 && a.park_scratch != nullptr && nbi - 1 - S >= 1 && lds + kParkWindow <= (size_t)160 * 1024) {
+    const size_t wgs = (size_t)(mpad / 256) * (size_t)S;
+    park_steps = (int)std::min<size_t>((size_t)a.park_bytes / (kParkStepBytes * wgs), (size_t)4 * (nbi - 1 - S));
+    if (park_steps > 0) park = static_cast<unsigned char*>(a.park_scratch(a.park_owner, (size_t)park_steps * kParkStepBytes * wgs));
+    if (park == nullptr) park_steps = 0;
+  }
+  if (a.park_out != nullptr) {  // per leaf tile: [0] steps parked, [1] steps reloaded instead of generated
+    int64_t parked = 0, reloads = 0;
+    for (int split = 0; split < S && park_steps > 0; ++split) {
+      for (int j = 0;; ++j) {
+        const int rank = j * S + ((j & 1) ? S - 1 - split : split);
+        if (rank >= nbi) break;
+        const int lim = std::min(2 * park_steps, 8 * (nbi - 1 - rank));  // (even steps below the row block's diagonal steps)
+        (j == 0 ? parked : reloads) += (lim + 1) / 2;
+      }
+    }
+    a.park_out[0] = parked;
+    a.park_out[1] = reloads;
+  }
+#define GPSO_L2(K, M32, XP, PK, LDS)                                                                \
   do {                                                                                              \
-    const int rc = ensure_dyn_lds((const void*)leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP>, (int)lds); \
+    const int rc = ensure_dyn_lds((const void*)leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK>, (int)(LDS)); \
     if (rc) return rc;                                                                              \
-    hipLaunchKernelGGL((leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP>), grid_s, dim3(512), lds, st, \
+    hipLaunchKernelGGL((leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK>), grid_s, dim3(512), (LDS), st, \
                        static_cast<const u32x4*>(a.linv_b), xs_p, a.xnorm, a.alpha, a.leaves_s, a.lnorm, \
                        a.part_var, a.part_mean, (int)(npad / 16), dp4, mpad, nbi, var_arg, a.m_live, \
-                       a.f16_inv_scale_a, inv_b, c16_scale, q_max, rawl.x, rawl.ls, rawl.m, rawl.d); \
+                       a.f16_inv_scale_a, inv_b, c16_scale, q_max, rawl.x, rawl.ls, rawl.m, rawl.d, park, park_steps); \
+  } while (0)
+#define GPSO_L1(K, M32, XP)                                     \
+  do {                                                          \
+    if constexpr (kHasPark && !(M32)) {                         \
+      if (park_steps > 0) GPSO_L2(K, M32, XP, true, lds + kParkWindow); \
+      else GPSO_L2(K, M32, XP, false, lds);                     \
+    } else {                                                    \
+      GPSO_L2(K, M32, XP, false, lds);                          \
+    }                                                           \
   } while (0)
 #define GPSO_L(K)                                   \
   do {                                              \
@@ -1239,6 +1390,7 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   }
 #undef GPSO_L
 #undef GPSO_L1
+#undef GPSO_L2
   (void)m32;
   (void)xp;
   return 0;

@@ -130,8 +130,16 @@ class HipGPEngine:
     def set_row_loop(self, on):
         """GPSO_OPT_ROW_LOOP (per context): 1 / True = a workgroup of the split predict kernels keeps its leaf tile and loops
         over row blocks, the launcher choosing how many workgroups share a tile (default); 0 = one row block per workgroup
-        (rounds 1-5); v >= 2 = exactly min(v, row blocks) workgroups per leaf tile.  Same bits."""
+        (rounds 1-5); v >= 2 = exactly min(v, row blocks) workgroups per leaf tile; -1 = exactly one, whatever the batch (a
+        test aid: small batches then walk every row block in one workgroup, as C3's 65 536 leaves do).  Same bits."""
         self._check(self._lib.gpso_set_option(self._h, L.OPT_ROW_LOOP, int(on)))
+
+    def set_park_bytes(self, nbytes):
+        """GPSO_OPT_PARK_BYTES (per context): 0 = the default split predict kernel regenerates every k-step's cross-Gram pieces in
+        every row block; v > 0 = a budget in bytes for parking the lowest even k-steps once per workgroup and reloading them in
+        its later row blocks.  Same bits.  ``last_count(5)`` / ``last_count(6)``: k-steps per leaf tile the last launch parked /
+        reloaded."""
+        self._check(self._lib.gpso_set_option(self._h, L.OPT_PARK_BYTES, int(nbytes)))
 
     def set_precision_check(self, on):
         self._check(self._lib.gpso_set_option(self._h, L.OPT_PRECISION_CHECK, 1 if on else 0))
@@ -178,8 +186,9 @@ class HipGPEngine:
         return float(self._lib.gpso_last_ms(self._h, int(what)))
 
     def last_count(self, what=0):
-        """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list; 2 .. 4: see
-        ``gpso_last_count`` in include/gpso_hip.h (4: bytes of device memory the contexts of this process hold now)."""
+        """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list; 2 .. 6: see
+        ``gpso_last_count`` in include/gpso_hip.h (4: bytes of device memory the contexts of this process hold now; 5 / 6:
+        k-steps per leaf tile the last split predict launch parked / reloaded under GPSO_OPT_PARK_BYTES)."""
         return int(self._lib.gpso_last_count(self._h, int(what)))
 
     FIT_MATH = {L.FITMATH_NONE: None, L.FITMATH_SMALL: "small", L.FITMATH_F32: "f32", L.FITMATH_F64: "f64",
