@@ -545,6 +545,44 @@ int gpso_sample_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
                       const double* z /* [s*m] host */, int64_t s, double* samples /* [s*m] host, nullable */,
                       int64_t* best_idx /* [s], nullable */, double* best_val /* [s], nullable */);
 
+/* Pathwise posterior draws (no counterpart in the reference): s posterior FUNCTIONS of the resident
+ * fitted exact GP, kept on the context (the "path set") and evaluated by gpso_paths_eval at any number of points -- Matheron's
+ * rule over a random-Fourier-feature prior, no m x m object anywhere.  With phi_j(x) = sqrt(2 variance / f) cos(omega_j . x/l
+ * + phase_j),
+ *   value[q, a] = c + sum_{j < f} phi_j(t_a) w[q, j] + sum_{i < N} k(x_i, t_a) v[i, q],   v = L^-T L^-1 R,
+ *   R[i, q] = (y_i - c) - sum_j phi_j(x_i) w[q, j] - sqrt(noise + s_i) eps[q, i]
+ * (k from direct differences in double, s_i the gpso_set_noise_diag vector or 0).  With w = 0 and eps = 0 a path is the
+ * posterior mean.  omega[f * D]: frequencies in SCALED coordinates, drawn from the kernel's spectral density (standard normal
+ * for the squared exponential; Student-t with 2 nu degrees of freedom for the Matern-nu); phase[f] uniform on [0, 2 pi);
+ * w[s * f] feature weights and eps[s * N] (nullable = zeros) standard normals -- all host float64, all from the CALLER (no
+ * generator on the device, as gpso_sample_joint).
+ * Posteriors: one fitted with targets on this context (gpso_loo's condition; after gpso_append / gpso_append_noise too), on
+ * GPSO_F64 and GPSO_MIXED contexts.  GPSO_E_ARG: a GPSO_F32 context, s outside [1, 256], f outside [1, 65536], a NULL omega /
+ * phase / w, an input that is not finite.  GPSO_E_STATE: no posterior, an installed, adopted or variational one (no targets),
+ * or an asynchronous best-UCB ticket open.  A call that fails or is refused leaves the previous path set as it was.
+ * The set lives until the posterior changes: every fit, append, gpso_set_data, gpso_set_noise_diag, install and hand-off ends
+ * it.  Reads only: the posterior, its packed copies, the hyper block, the self-test's verdicts and gpso_posterior_hash stay
+ * bit for bit; the same call gives the same set, and a draw's bits do not depend on s.  gpso_last_ms(ctx, 1) covers the call. */
+int gpso_paths_draw(gpso_ctx* ctx, const double* omega /* [f*D] host */, const double* phase /* [f] host */, int64_t f,
+                    const double* w /* [s*f] host */, const double* eps /* [s*N] host, nullable */, int64_t s);
+
+/* Evaluates the resident path set at m points (xs, xs_dtype, xs_mem as gpso_predict; any m >= 1, worked off in chunks of
+ * 16384 points inside, so the workspace does not grow with m): values[s * m] (draw-major, float64 living in out_mem, nullable);
+ * best_idx / best_val [s * nseg] (host, nullable; not all three NULL): per draw and segment the highest value and its index
+ * relative to the segment start, the lowest index on ties; an empty segment gives -1 and a NaN.  seg_off / nseg as
+ * gpso_best_ucb (nseg <= 1024).  With values NULL the values never leave the device.
+ * GPSO_E_STATE: no valid path set (none drawn, or the posterior changed since), or an asynchronous best-UCB ticket open.
+ * GPSO_E_ARG: a GPSO_F32 context, m < 1, xs NULL, all three outputs NULL, a bad seg_off / nseg.
+ * Reads only, as gpso_paths_draw.  The same call gives the same bits; a point's value bits depend neither on the rest of the
+ * batch, nor on its place in it, nor on how m is chunked.  gpso_last_ms(ctx, 1) covers the call; gpso_last_count(ctx, 0) and
+ * (ctx, 1) are m. */
+int gpso_paths_eval(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                    double* values /* [s*m], nullable */, int out_mem, int64_t* best_idx /* [s*nseg] host, nullable */,
+                    double* best_val /* [s*nseg] host, nullable */);
+
+/* Draws and features of the valid path set; 0, 0 when none is resident. */
+int gpso_paths_info(gpso_ctx* ctx, int64_t* s, int64_t* f);
+
 /* Replaces: GPSurrogate.gp_eval_best_ucb (gpso/gp_surrogate.py:313-328): predict_y, then
  * ucb = mean + varsigma * VAR, then first arg-max -- per segment.  seg_off[nseg+1] (host) delimits
  * independent leaf batches (NULL with nseg = 1 means one segment [0, M)); outputs (host, nseg each):

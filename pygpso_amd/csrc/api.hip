@@ -100,6 +100,11 @@ struct Engine {
                             int out_mem) = 0;
   virtual int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t s,
                            double* samples, int64_t* best_idx, double* best_val) = 0;
+  // pathwise posterior draws: functions kept on the context, evaluated at any number of points (paths.hip)
+  virtual int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t s) = 0;
+  virtual int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values,
+                         int out_mem, int64_t* best_idx, double* best_val) = 0;
+  virtual void paths_info(int64_t* s, int64_t* f) const = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
                        int nseg, double varsigma, int64_t* idx, double* mean, double* var,
                        double* ucb) = 0;
@@ -477,6 +482,16 @@ struct EngineT : Engine {
   // gpso_predict_joint / gpso_sample_joint: scaled test points, V (+ partial |v|^2), partial tiles, mean, Sigma; then the
   // Cholesky's buffers (factor, inverse, scratch, diagonal, info), the normals, the draws and their winners
   DevBuf pj_ts, pj_norm, pj_v, pj_part, pj_mu, pj_sigma, pj_l, pj_linv, pj_cwork, pj_diag, pj_info, pj_z, pj_f, pj_best;
+  // gpso_paths_draw / gpso_paths_eval (paths.hip): the resident path set -- frequencies, phases, weights and v^T, padded as
+  // the kernels read them; res.paths_valid says whether it means something -- and the set a draw in progress builds, swapped
+  // in when it succeeds (a failed draw leaves the resident one as it was).  Then the draw's scratch (eps, Phi(X) w^T, R, U)
+  // and the evaluation's: scaled points and values of one chunk, segment offsets, running winners
+  struct PathSet {
+    DevBuf omega, phase, w, vt;
+    int64_t s = 0, f = 0, ldw = 0;
+  };
+  PathSet pth, pth_next;
+  DevBuf pth_eps, pth_p, pth_r, pth_u, pe_ts, pe_norm, pe_vals, pe_seg, pe_best;
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -3007,6 +3022,163 @@ struct EngineT : Engine {
     }
   }
 
+  // ---- pathwise posterior draws (paths.hip).  Both calls read the dense fit-type factor, the scaled
+  // rows, y, the per-point noise and the hyper block and write buffers of their own only: the posterior, its packed copies and
+  // the self-test's verdicts stay as they are.  gpso_paths_draw builds the set beside the resident one and swaps it in at the end
+  static bool all_finite(const double* v, size_t len) {
+    for (size_t i = 0; i < len; ++i)
+      if (!std::isfinite(v[i])) return false;
+    return true;
+  }
+  int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t ns) override {
+    if constexpr (sizeof(TF) != 8) {
+      return ctx->fail(GPSO_E_ARG, "gpso_paths_draw needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    } else {
+      ctx->tick_timing();
+      if (ns < 1 || ns > kPathsMaxDraws)
+        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw takes 1 to %lld draws (s=%lld)", (long long)kPathsMaxDraws, (long long)ns);
+      if (f < 1 || f > kPathsMaxFeatures)
+        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw takes 1 to %lld features (f=%lld)", (long long)kPathsMaxFeatures, (long long)f);
+      if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
+      if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
+        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
+      int rc = refuse_if_async("gpso_paths_draw");
+      if (rc) return rc;
+      if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
+          (eps && !all_finite(eps, (size_t)ns * n)))
+        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw: omega, phase, w and eps must be finite");
+      const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
+      PathSet& nx = pth_next;
+      if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
+      if ((rc = ensure(nx.phase, (size_t)f16 * 8))) return rc;
+      if ((rc = ensure(nx.w, (size_t)ns * f16 * 8))) return rc;
+      if ((rc = ensure(nx.vt, (size_t)spad * npad * 8))) return rc;
+      if (eps && (rc = ensure(pth_eps, (size_t)ns * n * 8))) return rc;
+      if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
+      if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
+      if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
+      // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
+      std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
+      for (int64_t j = 0; j < f; ++j) {
+        std::memcpy(&ho[(size_t)j * dp], omega + (size_t)j * d, (size_t)d * 8);
+        hp[(size_t)j] = phase[j];
+      }
+      for (int64_t r = 0; r < ns; ++r) std::memcpy(&hw[(size_t)r * f16], w + (size_t)r * f, (size_t)f * 8);
+      hipStream_t s = st();
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+      HIPCHECK(hipMemcpyAsync(nx.omega.p, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(nx.phase.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemcpyAsync(nx.w.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, s));
+      if (eps) HIPCHECK(hipMemcpyAsync(pth_eps.p, eps, (size_t)ns * n * 8, hipMemcpyHostToDevice, s));
+      PathsEvalLaunch g;  // Phi(X) w^T: the evaluation over the training rows, kernel part off
+      g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
+      g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
+      if (launch_paths_eval(s, g) != 0) return launch_status();
+      launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
+                         n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
+      if ((rc = launch_status())) return rc;
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+      HIPCHECK(ctx->wait(s));
+      nx.s = ns; nx.f = f; nx.ldw = f16;
+      std::swap(pth, pth_next);
+      res.paths_drawn();
+      float ms = 0;
+      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+      return GPSO_OK;
+    }
+  }
+
+  // M is worked off in chunks of kPathsChunk: values of one chunk [S][chunk], copied out and / or reduced into the running
+  // winners per (draw, segment) before the next chunk overwrites them
+  int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values, int out_mem,
+                 int64_t* best_idx, double* best_val) override {
+    if constexpr (sizeof(TF) != 8) {
+      return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    } else {
+      ctx->tick_timing();
+      if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs at least one point (m=%lld)", (long long)m);
+      if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+      if (!values && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "values, best_idx and best_val are all NULL");
+      if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
+      if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
+      if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+      if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "nseg=%d outside [1, 1024]", nseg);
+      if (!res.paths_valid)
+        return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
+      int rc = refuse_if_async("gpso_paths_eval");
+      if (rc) return rc;
+      std::vector<int64_t> so(nseg + 1);
+      if (seg_off) {
+        for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
+        if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
+        for (int i = 0; i < nseg; ++i)
+          if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
+      } else {
+        if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
+        so[0] = 0;
+        so[1] = m;
+      }
+      const bool want_best = best_idx || best_val;
+      const int64_t ns = pth.s, chunk = std::min<int64_t>(kPathsChunk, (m + 63) / 64 * 64);
+      if ((rc = ensure(pe_ts, (size_t)chunk * dp * 8))) return rc;
+      if ((rc = ensure(pe_norm, (size_t)chunk * 8))) return rc;
+      if ((rc = ensure(pe_vals, (size_t)ns * chunk * 8))) return rc;
+      if ((rc = ensure(pe_seg, (size_t)(nseg + 1) * 8))) return rc;
+      if ((rc = ensure(pe_best, (size_t)ns * nseg * 16))) return rc;
+      int64_t* bi = as<int64_t>(pe_best);
+      double* bv = reinterpret_cast<double*>(bi + ns * nseg);
+      std::vector<int64_t> hi_(want_best ? (size_t)ns * nseg : 0);
+      std::vector<double> hv_(want_best ? (size_t)ns * nseg : 0);
+      hipStream_t s = st();
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+      const void* dev = nullptr;
+      if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+      if (want_best) {
+        HIPCHECK(hipMemcpyAsync(pe_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+        HIPCHECK(hipMemsetAsync(pe_best.p, 0xFF, (size_t)ns * nseg * 16, s));  // (index -1: no winner yet; the value a NaN)
+      }
+      PathsEvalLaunch g;
+      g.ts = as<double>(pe_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
+      g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
+      g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.out = as<double>(pe_vals); g.ldo = chunk;
+      for (int64_t off = 0; off < m; off += chunk) {
+        const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+        if (xs_dtype == GPSO_F64)
+          launch_prep_leaves<double, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
+                                             as<double>(pe_ts), as<double>(pe_norm));
+        else
+          launch_prep_leaves<double, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
+                                            as<double>(pe_ts), as<double>(pe_norm));
+        g.m = mc;
+        if (launch_paths_eval(s, g) != 0) return launch_status();
+        if ((rc = launch_status())) return rc;
+        if (values)
+          HIPCHECK(hipMemcpy2DAsync(values + off, (size_t)m * 8, pe_vals.p, (size_t)chunk * 8, (size_t)mc * 8, (size_t)ns,
+                                    out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+        if (want_best) launch_paths_argmax(s, as<double>(pe_vals), chunk, off, mc, as<int64_t>(pe_seg), nseg, ns, bi, bv);
+      }
+      if (want_best) {
+        if ((rc = launch_status())) return rc;
+        HIPCHECK(hipMemcpyAsync(hi_.data(), bi, hi_.size() * 8, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(hv_.data(), bv, hv_.size() * 8, hipMemcpyDeviceToHost, s));
+      }
+      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+      HIPCHECK(ctx->wait(s));
+      for (size_t e = 0; e < hi_.size(); ++e) {  // indices relative to the segment start; an empty segment: -1 and a NaN
+        if (best_idx) best_idx[e] = hi_[e] < 0 ? -1 : hi_[e] - so[e % nseg];
+        if (best_val) best_val[e] = hv_[e];
+      }
+      ctx->last_count[0] = ctx->last_count[1] = m;
+      float ms = 0;
+      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+      return GPSO_OK;
+    }
+  }
+  void paths_info(int64_t* s_out, int64_t* f_out) const override {
+    *s_out = res.paths_valid ? pth.s : 0;
+    *f_out = res.paths_valid ? pth.f : 0;
+  }
+
   // ---- best-UCB sequencing: enqueue the local work (winners stay on the device, no host wait) ->
   //      [multi-GPU: all-gather + fold] -> one read-back ------------------------------------------------
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
@@ -4664,6 +4836,25 @@ int gpso_sample_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
                       int64_t s, double* samples, int64_t* best_idx, double* best_val) {
   ENTER();
   return ctx->eng->sample_joint(xs, xs_dtype, xs_mem, m, diag_add, z, s, samples, best_idx, best_val);
+}
+
+int gpso_paths_draw(gpso_ctx* ctx, const double* omega, const double* phase, int64_t f, const double* w, const double* eps,
+                    int64_t s) {
+  ENTER();
+  return ctx->eng->paths_draw(omega, phase, f, w, eps, s);
+}
+
+int gpso_paths_eval(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                    double* values, int out_mem, int64_t* best_idx, double* best_val) {
+  ENTER();
+  return ctx->eng->paths_eval(xs, xs_dtype, xs_mem, m, seg_off, nseg, values, out_mem, best_idx, best_val);
+}
+
+int gpso_paths_info(gpso_ctx* ctx, int64_t* s, int64_t* f) {
+  ENTER();
+  if (!s || !f) return ctx->fail(GPSO_E_ARG, "s and f must not be NULL");
+  ctx->eng->paths_info(s, f);
+  return GPSO_OK;
 }
 
 int gpso_best_ucb(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m,

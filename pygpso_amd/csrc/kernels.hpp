@@ -443,6 +443,34 @@ void launch_joint_draw(hipStream_t st, const double* L, int64_t ldl, const doubl
                        double* f);
 // per row of f [s][m]: the highest value and its index, the lowest on ties (idx, val [s], each nullable)
 void launch_joint_argmax(hipStream_t st, const double* f, int64_t m, int64_t s, int64_t* idx, double* val);
+// ---- paths.hip: pathwise posterior draws of the exact GP ---------------------------------------------
+constexpr int64_t kPathsMaxDraws = 256;       // draws of a path set
+constexpr int64_t kPathsMaxFeatures = 65536;  // random Fourier features of a path set
+constexpr int64_t kPathsChunk = 16384;        // points per launch sequence of gpso_paths_eval: the workspace does not grow with M
+struct PathsEvalLaunch {
+  const double* ts = nullptr;     // [roundup(m, 64) * dp] scaled points, finite rows behind the m live ones
+  const double* xs = nullptr;     // [npad * dp] scaled training rows
+  const double* omega = nullptr;  // [roundup(f, 16) * dp] frequencies in scaled coordinates, zero padding
+  const double* phase = nullptr;  // [roundup(f, 16)]
+  const double* W = nullptr;      // [s][ldw] feature weights, ldw >= f
+  const double* VT = nullptr;     // [roundup(s, 64)][npad] v^T; nullptr: features only, and no constant mean
+  int64_t n = 0, npad = 0, m = 0, s = 0, f = 0, ldw = 0;
+  int dp = 0;
+  KernParams kp{0, 1.0, 0.0, 0.0};
+  double* out = nullptr;          // [s][ldo] values, draw-major; columns up to roundup(m, 64) are written
+  int64_t ldo = 0;
+};
+int launch_paths_eval(hipStream_t st, const PathsEvalLaunch& g);
+// R = (y - c) - P^T - sqrt(noise + s_i) eps^T, U = L^-1 R, VT = (L^-T U)^T for s draws padded to spad = roundup(s, 64):
+// C the dense fit-type L^-1 (read where column <= row < n), P [s][ldp] = Phi(X) w^T, eps [s * n] (nullable), sdiag [npad]
+// (nullable); R, U: roundup(n, 64) * spad doubles each, VT: spad * npad
+void launch_paths_solve(hipStream_t st, const double* C, const double* y, const double* P, int64_t ldp, const double* eps,
+                        const double* sdiag, const KernParams& kp, int64_t n, int64_t npad, int64_t s, double* R, double* U,
+                        double* VT);
+// vals [s][ldv] hold the points [off, off + mc) of the batch: per (draw, segment) their highest value against the running
+// winner in best_i / best_v [s * nseg] (best_i < 0: none yet; indices count from the start of the batch)
+void launch_paths_argmax(hipStream_t st, const double* vals, int64_t ldv, int64_t off, int64_t mc, const int64_t* seg_off_dev, int nseg,
+                         int64_t s, int64_t* best_i, double* best_v);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

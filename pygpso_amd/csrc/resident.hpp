@@ -34,6 +34,7 @@ struct Resident {
   Copy linv_p = Copy::Absent;  // the packed f32 / f64 L^-1 of the native tile kernel (a receiver of a split posterior: absent)
   Copy linv_b = Copy::Absent;  // the 16-bit split pieces (deferred by a fit that returned a gradient: ensure_split_pieces)
   int small_tile_rows = 8;     // tile rows of the 128-padded linv_p that may be non-zero (8: all / unknown)
+  bool paths_valid = false;    // the path set of gpso_paths_draw (omega, b, w, v) belongs to this posterior as it stands
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -62,6 +63,7 @@ struct Resident {
     post = Post::None;
     have_kinv = chol_valid = st_done = st_have = false;
     linv_p = Copy::Absent;
+    paths_valid = false;
     if (!keep_peers) sync_n = -1;
   }
   // A new posterior begins (or an option changed): generation starts over -- float unless double was asked for --, the
@@ -102,12 +104,13 @@ struct Resident {
     linv_p = linv_p_deferred ? Copy::Deferred : Copy::Valid;
     if (split_deferred) linv_b = split_usable_now ? Copy::Deferred : Copy::Absent;
   }
+  void paths_drawn() { paths_valid = true; }  // gpso_paths_draw succeeded; posterior_dropped() and appended() end it
   void split_packed(bool built) { linv_b = built ? Copy::Valid : Copy::Absent; }  // pack_bf16 began / ended
   void linv_p_packed() { small_tile_rows = 8; linv_p = Copy::Valid; }
   // the self-test looks at the extended posterior; the float copies of the inputs are derived again
   void appended(bool first_noise_vector) {
     have_s = have_s || first_noise_vector;
-    have_kinv = st_done = gen32_inputs_ok = false;
+    have_kinv = st_done = gen32_inputs_ok = paths_valid = false;  // (v was solved against the shorter factor)
     small_tile_rows = 8;
   }
   void append_refused() { gen32_inputs_ok = false; }  // not PD: the scaled inputs were put back, their float copies not
@@ -139,7 +142,7 @@ struct Resident {
   // generation arithmetic and predict math: the sender's choice (its self-test ruled), unless this context insists
   void adopted(int sender, bool float_predict, bool math_auto, int gen_mode, int64_t npad) {
     post = Post::Adopted;
-    chol_valid = have_kinv = false;
+    chol_valid = have_kinv = paths_valid = false;
     small_tile_rows = 8;         // linv_p came from elsewhere
     st_done = st_have = false;   // the fitting rank ran the self-test; no targets here
     math_native_fallback = math_auto && (sender & 2) != 0;

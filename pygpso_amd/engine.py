@@ -693,6 +693,61 @@ class HipGPEngine:
                                                 L.dptr(best_val)))
         return samples, best_idx, best_val
 
+    def paths_draw(self, omega, phase, w, eps=None):
+        """Draw S posterior functions of the resident fitted exact GP and keep them on the context (``gpso_paths_draw``):
+        ``omega`` [F, D] frequencies in scaled coordinates, ``phase`` [F], ``w`` [S, F] feature weights, ``eps`` [S, N]
+        standard normals of the observation noise (None: zeros).  ``pygpso_amd.paths`` draws them from a seed.  The set
+        lives until the posterior changes; ``paths_eval`` evaluates it."""
+        omega = L.as_f64(omega)
+        if omega.ndim != 2 or (self.d and omega.shape[1] != self.d):
+            raise ValueError(f"omega must be [F, D] with D={self.d}, got {omega.shape}")
+        f = int(omega.shape[0])
+        phase = L.as_f64(np.asarray(phase).reshape(-1))
+        w = L.as_f64(w)
+        if phase.shape != (f,) or w.ndim != 2 or w.shape[1] != f:
+            raise ValueError(f"phase must be [F] and w [S, F] with F={f}, got {phase.shape} and {w.shape}")
+        s = int(w.shape[0])
+        if eps is not None:
+            eps = L.as_f64(eps)
+            if eps.shape != (s, self.n):
+                raise ValueError(f"eps must be [S, N] = [{s}, {self.n}], got {eps.shape}")
+        self._check(self._lib.gpso_paths_draw(self._h, L.dptr(omega), L.dptr(phase), f, L.dptr(w),
+                                              None if eps is None else L.dptr(eps), s))
+
+    def paths_info(self):
+        """(S, F) of the valid path set, (0, 0) when none is resident."""
+        s, f = np.zeros(1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        self._check(self._lib.gpso_paths_info(self._h, L.i64ptr(s), L.i64ptr(f)))
+        return int(s[0]), int(f[0])
+
+    def paths_eval(self, xs, seg_off=None, want_values=True, out=None):
+        """Evaluate the resident path set at the M rows of ``xs`` (``gpso_paths_eval``; any M).  Returns (values [S, M] or
+        None, best_idx [S, nseg], best_val [S, nseg]): per draw and segment the index relative to the segment start (the
+        lowest on ties) and the value of its highest entry.  ``want_values=False`` leaves the values on the device;
+        ``out``: a contiguous float64 CUDA tensor [S, M] that receives them instead of a host array."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        s, _ = self.paths_info()
+        if seg_off is None:
+            nseg, so_ptr = 1, None
+        else:
+            so = np.ascontiguousarray(seg_off, dtype=np.int64)
+            nseg, so_ptr = int(so.shape[0] - 1), L.i64ptr(so)
+        rows = max(s, 1)
+        best_idx, best_val = np.empty((rows, nseg), dtype=np.int64), np.empty((rows, nseg), dtype=np.float64)
+        if out is not None:
+            if tuple(out.shape) != (s, m) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous [{s}, {m}] tensor")
+            self._order_after(out)
+            values, vptr, vmem = out, C.c_void_p(out.data_ptr()), L.MEM_DEVICE
+        elif want_values:
+            values = np.empty((rows, m), dtype=np.float64)
+            vptr, vmem = C.c_void_p(values.ctypes.data), L.MEM_HOST
+        else:
+            values, vptr, vmem = None, None, L.MEM_HOST
+        self._check(self._lib.gpso_paths_eval(self._h, ptr, dt, mem, m, so_ptr, nseg, vptr, vmem, L.i64ptr(best_idx),
+                                              L.dptr(best_val)))
+        return values, best_idx, best_val
+
     def best_ucb(self, xs, varsigma, seg_off=None):
         """gp_eval_best_ucb per segment -> (idx, mean, var, ucb) arrays of length nseg."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)

@@ -526,6 +526,25 @@ class GPSurrogate:
         _, idx, val = self._draw(self._joint_model("thompson_select"), normed_coords, n_draws, rng, jitter, False)
         return idx, val
 
+    def gp_sample_paths(self, n_paths, n_features=1024, rng=None):
+        """Draw ``n_paths`` posterior functions of the surrogate (pathwise conditioning, ``HipGPR.sample_paths``) and keep
+        them on the device until the model changes.  ``gp_eval_paths`` and ``thompson_select_leaves`` evaluate them at any
+        number of rows -- the leaves the optimiser holds, not a hand-picked 1024.  Stores nothing."""
+        self._joint_model("gp_sample_paths").sample_paths(n_paths, n_features=n_features, rng=rng)
+
+    def gp_eval_paths(self, normed_coords):
+        """The drawn paths at the rows of ``normed_coords``: [S, M].  Stores nothing."""
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        return self._joint_model("gp_eval_paths").eval_paths(coords)[0]
+
+    def thompson_select_leaves(self, normed_coords, seg_off=None):
+        """Thompson sampling over ALL the rows of ``normed_coords`` (any M): (indices [S, nseg], values [S, nseg]), per
+        drawn path of ``gp_sample_paths`` and per segment of ``seg_off`` (None: one segment) the arg-max relative to the
+        segment start (the first on ties) and the maximum.  The values never leave the device.  Stores nothing."""
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        _, idx, val = self._joint_model("thompson_select_leaves").eval_paths(coords, seg_off, want_values=False)
+        return idx, val
+
     def polish(self, normed_coords, objective="ucb", box=None, options=None):
         """Gradient polish of R candidate points on the surrogate: from each row of ``normed_coords`` [R, D], L-BFGS-B
         maximises ``mean + varsigma * var`` (``objective="ucb"``, the package's UCB on the variance) or the mean

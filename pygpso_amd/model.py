@@ -443,6 +443,24 @@ class HipGPR:
         z = _standard_normals(rng, num_samples, Xnew.shape[0])
         return self._predicting(lambda: self.engine.sample_joint(Xnew, z, jitter))[0]
 
+    def sample_paths(self, n_paths, n_features=1024, rng=None):
+        """Draw ``n_paths`` posterior FUNCTIONS of the latent f (pathwise conditioning over ``n_features`` random Fourier
+        features; ``gpso_paths_draw``) and keep them on the engine until the posterior changes; ``eval_paths`` evaluates
+        them at any number of points.  ``rng``: a seed or a ``numpy.random.Generator`` -- every random input is drawn on
+        the host (``pygpso_amd.paths``), so a seed reproduces the set.  No counterpart in the reference."""
+        from .paths import draw_path_inputs
+
+        x, _ = self._data
+        omega, phase, w, eps = draw_path_inputs(self._theta()[0], n_paths, n_features, x.shape[0], x.shape[1], rng)
+        self._predicting(lambda: self.engine.paths_draw(omega, phase, w, eps))
+
+    def eval_paths(self, Xnew, seg_off=None, want_values=True):
+        """The path set of ``sample_paths`` at the rows of Xnew (any M): (values [S, M] or None, best_idx [S, nseg],
+        best_val [S, nseg]) -- per draw and segment of ``seg_off`` the first arg-max relative to the segment start and
+        the maximum.  A posterior that changed since ``sample_paths`` raises: draw again."""
+        Xnew = np.asarray(Xnew)
+        return self._predicting(lambda: self.engine.paths_eval(Xnew, seg_off, want_values=want_values))
+
     def predictive_noise(self):
         """The likelihood's variance in ``predict_y`` (the families with another likelihood override this)."""
         return self.likelihood.variance
