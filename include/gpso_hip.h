@@ -558,13 +558,36 @@ int gpso_sample_joint(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
  * generator on the device, as gpso_sample_joint).
  * Posteriors: one fitted with targets on this context (gpso_loo's condition; after gpso_append / gpso_append_noise too), on
  * GPSO_F64 and GPSO_MIXED contexts.  GPSO_E_ARG: a GPSO_F32 context, s outside [1, 256], f outside [1, 65536], a NULL omega /
- * phase / w, an input that is not finite.  GPSO_E_STATE: no posterior, an installed, adopted or variational one (no targets),
- * or an asynchronous best-UCB ticket open.  A call that fails or is refused leaves the previous path set as it was.
+ * phase / w, an input that is not finite.  GPSO_E_STATE: no posterior, an installed, adopted or variational one (no targets;
+ * gpso_paths_draw_q draws from a variational one), or an asynchronous best-UCB ticket open.  A call that fails or is refused
+ * leaves the previous path set as it was.
  * The set lives until the posterior changes: every fit, append, gpso_set_data, gpso_set_noise_diag, install and hand-off ends
  * it.  Reads only: the posterior, its packed copies, the hyper block, the self-test's verdicts and gpso_posterior_hash stay
  * bit for bit; the same call gives the same set, and a draw's bits do not depend on s.  gpso_last_ms(ctx, 1) covers the call. */
 int gpso_paths_draw(gpso_ctx* ctx, const double* omega /* [f*D] host */, const double* phase /* [f] host */, int64_t f,
                     const double* w /* [s*f] host */, const double* eps /* [s*N] host, nullable */, int64_t s);
+
+/* Pathwise draws of the VARIATIONAL posteriors (Wilson et al. 2020, section 3.2, in GPflow's whitened
+ * form): the path set of the posterior that gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior installed, over
+ * its n resident rows Zr (the training rows of a VGP, the inducing points Z of the sparse two).  With Lu = chol(k(Zr, Zr) +
+ * 1e-6 I), the whitened q(v) = N(mu, Q Q^T) and beta = Lu^-T mu,
+ *   value[q, a] = c + sum_{j < f} phi_j(t_a) w[q, j] + sum_{i < n} k(Zr_i, t_a) v[i, q],
+ *   v[:, q] = beta + Lu^-T (Q eps[q, :] - Lu^-1 P[:, q]),   P[i, q] = sum_j phi_j(Zr_i) w[q, j]
+ * (Q: the lower root of q for the VGP and the SVGP, LB^-T for the SGPR).  With w = 0 and eps = 0 a path is the family's
+ * predictive mean; the draws come from q itself: the shift delta of a Student-t or singular-B install is in the served
+ * variance only, never in a path.  omega, phase, w as gpso_paths_draw; eps[s * n] (nullable = zeros) the whitened normals, n
+ * the RESIDENT row count (gpso_problem_shape).  The set replaces whatever set is resident and is served by gpso_paths_eval /
+ * gpso_paths_info; it costs O(n + f) a point whatever the size of the training set behind a sparse posterior.
+ * GPSO_E_ARG: as gpso_paths_draw.  GPSO_E_STATE: no posterior, a fitted one (gpso_paths_draw's), an installed or adopted one,
+ * the install's factors no longer resident, or an asynchronous best-UCB ticket open.  A call that fails or is refused leaves
+ * the previous path set as it was.  The set lives until the posterior changes: every variational evaluation, natural-gradient
+ * step, install, gpso_vgp_set_q / gpso_svgp_set_q, move of Z, gpso_set_data and hand-off ends it (and the factors' residency
+ * with it); gpso_predict, gpso_predict_grad, gpso_predict_joint and gpso_sample_joint touch none of the factors, so a draw after
+ * them gives the bits of a draw right after the install.  Reads only, as gpso_paths_draw (it writes scratch of the
+ * install's -- vA, vB, the factorisation's work matrix -- to rebuild Lu^-1); a draw's bits do not depend on s.
+ * gpso_last_ms(ctx, 1) covers the call. */
+int gpso_paths_draw_q(gpso_ctx* ctx, const double* omega /* [f*D] host */, const double* phase /* [f] host */, int64_t f,
+                      const double* w /* [s*f] host */, const double* eps /* [s*n] host, nullable */, int64_t s);
 
 /* Evaluates the resident path set at m points (xs, xs_dtype, xs_mem as gpso_predict; any m >= 1, worked off in chunks of
  * 16384 points inside, so the workspace does not grow with m): values[s * m] (draw-major, float64 living in out_mem, nullable);

@@ -130,6 +130,7 @@ SIGNATURES = {
     "gpso_sample_joint": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, C.c_int64,
                                     _c_double_p, _c_int64_p, _c_double_p]),
     "gpso_paths_draw": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64]),
+    "gpso_paths_draw_q": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p, C.c_int64]),
     "gpso_paths_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, C.c_void_p, C.c_int,
                                   _c_int64_p, _c_double_p]),
     "gpso_paths_info": (C.c_int, [C.c_void_p, _c_int64_p, _c_int64_p]),

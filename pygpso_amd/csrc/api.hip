@@ -102,6 +102,7 @@ struct Engine {
                            double* samples, int64_t* best_idx, double* best_val) = 0;
   // pathwise posterior draws: functions kept on the context, evaluated at any number of points (paths.hip)
   virtual int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t s) = 0;
+  virtual int paths_draw_q(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t s) = 0;
   virtual int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values,
                          int out_mem, int64_t* best_idx, double* best_val) = 0;
   virtual void paths_info(int64_t* s, int64_t* f) const = 0;
@@ -491,7 +492,7 @@ struct EngineT : Engine {
     int64_t s = 0, f = 0, ldw = 0;
   };
   PathSet pth, pth_next;
-  DevBuf pth_eps, pth_p, pth_r, pth_u, pe_ts, pe_norm, pe_vals, pe_seg, pe_best;
+  DevBuf pth_eps, pth_p, pth_r, pth_u, pth_x /* gpso_paths_draw_q: Lu^-1 Phi(Zr) w^T */, pe_ts, pe_norm, pe_vals, pe_seg, pe_best;
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -3031,22 +3032,42 @@ struct EngineT : Engine {
     return true;
   }
   int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t ns) override {
+    return paths_draw_impl(false, "gpso_paths_draw", omega, phase, f, w, eps, ns);
+  }
+  // the draw of a variational posterior: v = beta + Lu^-T (Q eps - Lu^-1 Phi(Zr) w^T) from what the
+  // install left in Lf (Lu), alpha_f (beta) and vq_S / svq_S / sgM2 (Q); Lu^-1 is rebuilt from Lf into vA (vB: the copy of
+  // Lu with a unit diagonal on the padding, work: scratch) -- three buffers the install has finished with
+  int paths_draw_q(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t ns) override {
+    return paths_draw_impl(true, "gpso_paths_draw_q", omega, phase, f, w, eps, ns);
+  }
+  int paths_draw_impl(bool variational, const char* who, const double* omega, const double* phase, int64_t f, const double* w,
+                      const double* eps, int64_t ns) {
     if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "gpso_paths_draw needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+      return ctx->fail(GPSO_E_ARG, "%s needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)", who);
     } else {
       ctx->tick_timing();
       if (ns < 1 || ns > kPathsMaxDraws)
-        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw takes 1 to %lld draws (s=%lld)", (long long)kPathsMaxDraws, (long long)ns);
+        return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld draws (s=%lld)", who, (long long)kPathsMaxDraws, (long long)ns);
       if (f < 1 || f > kPathsMaxFeatures)
-        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw takes 1 to %lld features (f=%lld)", (long long)kPathsMaxFeatures, (long long)f);
+        return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld features (f=%lld)", who, (long long)kPathsMaxFeatures, (long long)f);
       if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
-      if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
-        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
-      int rc = refuse_if_async("gpso_paths_draw");
+      if (!variational) {
+        if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
+          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
+      } else {
+        if (res.post == Post::Fitted) return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q draws from a variational posterior: a fitted exact GP takes gpso_paths_draw");
+        if (!(res.variational() && res.chol_valid))
+          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q needs a posterior installed by gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior on this context");
+        // (at present implied by the line above: q_factors is set with the kind and cleared only where the kind is -- no call
+        // overwrites Lf, beta or the root of q and keeps the posterior.  The flag is for the first call that does)
+        if (!res.q_factors)
+          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q: the install's factors (Lu, beta, the root of q) are not resident any more: install again");
+      }
+      int rc = refuse_if_async(who);
       if (rc) return rc;
       if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
           (eps && !all_finite(eps, (size_t)ns * n)))
-        return ctx->fail(GPSO_E_ARG, "gpso_paths_draw: omega, phase, w and eps must be finite");
+        return ctx->fail(GPSO_E_ARG, "%s: omega, phase, w and eps must be finite", who);
       const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
       PathSet& nx = pth_next;
       if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
@@ -3057,6 +3078,7 @@ struct EngineT : Engine {
       if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
       if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
       if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
+      if (variational && (rc = ensure(pth_x, (size_t)n64 * spad * 8))) return rc;
       // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
       std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
       for (int64_t j = 0; j < f; ++j) {
@@ -3074,8 +3096,17 @@ struct EngineT : Engine {
       g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
       g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
       if (launch_paths_eval(s, g) != 0) return launch_status();
-      launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
-                         n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
+      if (!variational) {
+        launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
+                           n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
+      } else {
+        launch_vgp_clean_lower(s, as<double>(Lf), as<double>(vB), n, npad, 1.0);
+        launch_trinv<double>(s, as<double>(vB), as<double>(vA), as<double>(work), npad);
+        const bool sgpr = res.post == Post::Sgpr;
+        const double* Q = sgpr ? as<double>(sgM2) : res.post == Post::Svgp ? as<double>(svq_S) : as<double>(vq_S);
+        launch_paths_solve_q(s, as<double>(vA), Q, sgpr, as<double>(alpha_f), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, n,
+                             npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(pth_x), as<double>(nx.vt));
+      }
       if ((rc = launch_status())) return rc;
       if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
       HIPCHECK(ctx->wait(s));
@@ -4842,6 +4873,12 @@ int gpso_paths_draw(gpso_ctx* ctx, const double* omega, const double* phase, int
                     int64_t s) {
   ENTER();
   return ctx->eng->paths_draw(omega, phase, f, w, eps, s);
+}
+
+int gpso_paths_draw_q(gpso_ctx* ctx, const double* omega, const double* phase, int64_t f, const double* w, const double* eps,
+                      int64_t s) {
+  ENTER();
+  return ctx->eng->paths_draw_q(omega, phase, f, w, eps, s);
 }
 
 int gpso_paths_eval(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,

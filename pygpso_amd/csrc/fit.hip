@@ -3436,4 +3436,13 @@ void launch_install_chol(hipStream_t st, const double* L64, int64_t n, int64_t n
 template void launch_install_chol<float>(hipStream_t, const double*, int64_t, int64_t, float*, float*);
 template void launch_install_chol<double>(hipStream_t, const double*, int64_t, int64_t, double*, double*);
 
+// gpso_set_posterior's sequence for a factor that is already on the device: the 64-wide diagonal blocks, then level doubling
+template <typename T>
+void launch_trinv(hipStream_t st, const T* L, T* linv, T* work, int64_t npad) {
+  (void)hipMemsetAsync(linv, 0, (size_t)npad * npad * sizeof(T), st);
+  hipLaunchKernelGGL((trinv_diag_kernel<T>), dim3((unsigned)(npad / kFitBlock)), dim3(256), 0, st, L, linv, npad);
+  launch_trtri<T>(st, L, linv, work, npad, kFitBlock);
+}
+template void launch_trinv<double>(hipStream_t, const double*, double*, double*, int64_t);
+
 }  // namespace gpso

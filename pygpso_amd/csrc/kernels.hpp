@@ -335,6 +335,10 @@ void launch_convert_out(hipStream_t st, const T* src, int64_t ld_src, double* ds
 // install L (row-major lower, n x n float64 on device) into the padded T buffer + invert diagonal blocks
 template <typename T>
 void launch_install_chol(hipStream_t st, const double* L64, int64_t n, int64_t npad, T* K, T* linv);
+// linv = L^-1 of a padded lower factor already on the device (its lower triangle is read; a non-zero diagonal on the padding
+// too): linv is zeroed, the 64-wide diagonal blocks are inverted, then launch_trtri doubles the levels; work = npad x npad
+template <typename T>
+void launch_trinv(hipStream_t st, const T* L, T* linv, T* work, int64_t npad);
 
 // C = alpha op(A) op(B) + beta C, whole N_pad x N_pad float64 matrices (fit.hip; N_pad a multiple of 64)
 void launch_dgemm(hipStream_t st, const double* A, bool trans_a, const double* B, bool trans_b, double* C, int64_t npad,
@@ -467,6 +471,14 @@ int launch_paths_eval(hipStream_t st, const PathsEvalLaunch& g);
 void launch_paths_solve(hipStream_t st, const double* C, const double* y, const double* P, int64_t ldp, const double* eps,
                         const double* sdiag, const KernParams& kp, int64_t n, int64_t npad, int64_t s, double* R, double* U,
                         double* VT);
+// The draw of a whitened variational posterior over n resident rows: VT = (beta + Lu^-T (Q eps^T -
+// Lu^-1 P^T))^T for s draws padded to spad = roundup(s, 64).  Lui the dense Lu^-1, Q the lower root of the whitened
+// covariance -- q_transposed: Q is the TRANSPOSE of the lower matrix given (the SGPR's LB^-1) --, both npad x npad and read
+// where column <= row < n only; beta [>= n]; P [s][ldp] = Phi(Zr) w^T; eps [s * n] (nullable: zeros).  Pt, E, X:
+// roundup(n, 64) * spad doubles each (Pt ends as the residual, zero on the padding draws); VT: spad * npad
+void launch_paths_solve_q(hipStream_t st, const double* Lui, const double* Q, bool q_transposed, const double* beta, const double* P,
+                          int64_t ldp, const double* eps, int64_t n, int64_t npad, int64_t s, double* Pt, double* E, double* X,
+                          double* VT);
 // vals [s][ldv] hold the points [off, off + mc) of the batch: per (draw, segment) their highest value against the running
 // winner in best_i / best_v [s * nseg] (best_i < 0: none yet; indices count from the start of the batch)
 void launch_paths_argmax(hipStream_t st, const double* vals, int64_t ldv, int64_t off, int64_t mc, const int64_t* seg_off_dev, int nseg,

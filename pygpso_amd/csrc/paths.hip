@@ -15,6 +15,11 @@
 //                       (i, j) read only where j <= i < N
 //   paths_argmax_kernel per (draw, segment) the highest value of a chunk, merged into the running winner: an earlier chunk
 //                       keeps a tie, so the lowest index wins
+// The draw of a whitened variational posterior (gpso_paths_draw_q; section 7k) keeps the evaluation and replaces the solve:
+//     v = beta + Lu^-T (Q eps - Lu^-1 P),   P = Phi(Zr) w^T over the resident rows Zr,
+//   paths_q_lay_kernel  P^T and eps^T in the [row][draw] layout of the products, zero padding
+//   paths_tri_kernel    with a compile-time epilogue: Lu^-1 P^T; Q eps^T (lower Q, or the transpose of the lower LB^-1) minus
+//                       it; Lu^-T of that plus beta, written as v^T
 // No atomics, every reduction in a fixed order; compiled with -ffp-contract=off, every fused multiply-add written out: a
 // point's bits depend neither on its column slot, nor on the rest of the batch, nor on how many draws there are.
 #include "kernels.hpp"
@@ -183,11 +188,15 @@ __global__ __launch_bounds__(kThreads) void paths_resid_kernel(const double* __r
   R[e] = r;
 }
 
-// TRANS false: out[o][col] = sum_{k <= o} C[o][k] B[k][col] (rows o < roundup(n, 64));  true: out[col][o] = sum_{o <= k < n}
-// C[k][o] B[k][col].  C[i][j] is read only where j <= i < n.  k in index order, sixteen a trip
-template <bool TRANS>
+// acc[o][col] = sum_{k <= o} C[o][k] B[k][col] (TRANS false; rows o < roundup(n, 64)) or sum_{o <= k < n} C[k][o] B[k][col] (TRANS
+// true).  C[i][j] is read only where j <= i < n.  k in index order, sixteen a trip.  Written as out[o][col], or out[col][o] with
+// OUT_T, after the compile-time epilogue: kEpiNone acc itself (the exact GP's two products: e and s unused); kEpiMinus acc -
+// e[o][col], e laid out as out; kEpiPlusRow acc + e[o] on o < n and col < s
+enum { kEpiNone = 0, kEpiMinus = 1, kEpiPlusRow = 2 };
+template <bool TRANS, bool OUT_T, int EPI>
 __global__ __launch_bounds__(kThreads) void paths_tri_kernel(const double* __restrict__ C, const double* __restrict__ B, double* __restrict__ out,
-                                                             int64_t n, int64_t npad, int64_t ldb, int64_t ldo) {
+                                                             int64_t n, int64_t npad, int64_t ldb, int64_t ldo, const double* __restrict__ e,
+                                                             int s) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kq = lane >> 4;
   const int64_t col = (int64_t)blockIdx.x * kCols + 16 * wave + (lane & 15), o0 = (int64_t)blockIdx.y * kTriBlock;
   const int64_t n16 = (n + 15) / 16 * 16;
@@ -220,10 +229,27 @@ __global__ __launch_bounds__(kThreads) void paths_tri_kernel(const double* __res
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int64_t o = o0 + 16 * t + kq + 4 * r;
-      if (TRANS) out[col * ldo + o] = acc[t][r];
-      else out[o * ldo + col] = acc[t][r];
+      double v = acc[t][r];
+      if (EPI == kEpiMinus) v = v - e[o * ldo + col];
+      if (EPI == kEpiPlusRow && o < n && col < s) v = v + e[o];
+      if (OUT_T) out[col * ldo + o] = v;
+      else out[o * ldo + col] = v;
     }
   }
+}
+
+// ---- the draw of a whitened variational posterior ------------------------------------------------------
+// Pt[i][sd] = P[sd][i], E[i][sd] = eps[sd][i] (zeros without eps) on i < n, sd < s; zero on the rows up to roundup(n, 64) and on
+// the draws of the padding: the [row][draw] layout the triangular products read
+__global__ __launch_bounds__(kThreads) void paths_q_lay_kernel(const double* __restrict__ P, int64_t ldp, const double* __restrict__ eps,
+                                                               int64_t n, int64_t n64, int s, int64_t spad, double* __restrict__ Pt,
+                                                               double* __restrict__ E) {
+  const int64_t e = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (e >= n64 * spad) return;
+  const int64_t i = e / spad, sd = e - i * spad;
+  const bool live = i < n && sd < s;
+  Pt[e] = live ? P[sd * ldp + i] : 0.0;
+  E[e] = (live && eps != nullptr) ? eps[sd * n + i] : 0.0;
 }
 
 // blockIdx.x: segment, blockIdx.y: draw.  The rows of the segment that lie in [off, off + mc) against the running winner
@@ -296,8 +322,27 @@ void launch_paths_solve(hipStream_t st, const double* C, const double* y, const 
   hipLaunchKernelGGL(paths_resid_kernel, dim3((unsigned)((n * spad + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, y, P, ldp, eps,
                      sdiag, kp.noise, kp.mean_c, n, (int)s, spad, R);
   const dim3 grid((unsigned)(spad / kCols), (unsigned)((n + kTriBlock - 1) / kTriBlock));
-  hipLaunchKernelGGL(paths_tri_kernel<false>, grid, dim3(kThreads), 0, st, C, R, U, n, npad, spad, spad);
-  hipLaunchKernelGGL(paths_tri_kernel<true>, grid, dim3(kThreads), 0, st, C, U, VT, n, npad, spad, npad);
+  const double* none = nullptr;
+  hipLaunchKernelGGL((paths_tri_kernel<false, false, kEpiNone>), grid, dim3(kThreads), 0, st, C, R, U, n, npad, spad, spad, none, 0);
+  hipLaunchKernelGGL((paths_tri_kernel<true, true, kEpiNone>), grid, dim3(kThreads), 0, st, C, U, VT, n, npad, spad, npad, none, 0);
+}
+
+void launch_paths_solve_q(hipStream_t st, const double* Lui, const double* Q, bool q_transposed, const double* beta, const double* P,
+                          int64_t ldp, const double* eps, int64_t n, int64_t npad, int64_t s, double* Pt, double* E, double* X,
+                          double* VT) {
+  const int64_t spad = (s + kCols - 1) / kCols * kCols, n64 = (n + kTriBlock - 1) / kTriBlock * kTriBlock;
+  hipLaunchKernelGGL(paths_q_lay_kernel, dim3((unsigned)((n64 * spad + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, P, ldp, eps, n,
+                     n64, (int)s, spad, Pt, E);
+  const dim3 grid((unsigned)(spad / kCols), (unsigned)(n64 / kTriBlock));
+  const double* none = nullptr;
+  // X = Lu^-1 P^T;  the residual Q eps^T - X over Pt (read by the first product only);  V^T = (Lu^-T residual + beta)^T
+  hipLaunchKernelGGL((paths_tri_kernel<false, false, kEpiNone>), grid, dim3(kThreads), 0, st, Lui, Pt, X, n, npad, spad, spad, none, 0);
+  if (q_transposed)
+    hipLaunchKernelGGL((paths_tri_kernel<true, false, kEpiMinus>), grid, dim3(kThreads), 0, st, Q, E, Pt, n, npad, spad, spad, X, 0);
+  else
+    hipLaunchKernelGGL((paths_tri_kernel<false, false, kEpiMinus>), grid, dim3(kThreads), 0, st, Q, E, Pt, n, npad, spad, spad, X, 0);
+  hipLaunchKernelGGL((paths_tri_kernel<true, true, kEpiPlusRow>), grid, dim3(kThreads), 0, st, Lui, Pt, VT, n, npad, spad, npad, beta,
+                     (int)s);
 }
 
 void launch_paths_argmax(hipStream_t st, const double* vals, int64_t ldv, int64_t off, int64_t mc, const int64_t* seg_off_dev, int nseg,

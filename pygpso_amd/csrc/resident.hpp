@@ -34,7 +34,8 @@ struct Resident {
   Copy linv_p = Copy::Absent;  // the packed f32 / f64 L^-1 of the native tile kernel (a receiver of a split posterior: absent)
   Copy linv_b = Copy::Absent;  // the 16-bit split pieces (deferred by a fit that returned a gradient: ensure_split_pieces)
   int small_tile_rows = 8;     // tile rows of the 128-padded linv_p that may be non-zero (8: all / unknown)
-  bool paths_valid = false;    // the path set of gpso_paths_draw (omega, b, w, v) belongs to this posterior as it stands
+  bool paths_valid = false;    // the path set of gpso_paths_draw / gpso_paths_draw_q (omega, b, w, v) belongs to this posterior as it stands
+  bool q_factors = false;      // a variational install's Lu (Lf), beta (alpha_f) and root Q of q (vq_S / svq_S / sgM2) are still in their buffers
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -63,7 +64,7 @@ struct Resident {
     post = Post::None;
     have_kinv = chol_valid = st_done = st_have = false;
     linv_p = Copy::Absent;
-    paths_valid = false;
+    paths_valid = q_factors = false;
     if (!keep_peers) sync_n = -1;
   }
   // A new posterior begins (or an option changed): generation starts over -- float unless double was asked for --, the
@@ -104,7 +105,7 @@ struct Resident {
     linv_p = linv_p_deferred ? Copy::Deferred : Copy::Valid;
     if (split_deferred) linv_b = split_usable_now ? Copy::Deferred : Copy::Absent;
   }
-  void paths_drawn() { paths_valid = true; }  // gpso_paths_draw succeeded; posterior_dropped() and appended() end it
+  void paths_drawn() { paths_valid = true; }  // gpso_paths_draw(_q) succeeded; posterior_dropped() and appended() end it
   void split_packed(bool built) { linv_b = built ? Copy::Valid : Copy::Absent; }  // pack_bf16 began / ended
   void linv_p_packed() { small_tile_rows = 8; linv_p = Copy::Valid; }
   // the self-test looks at the extended posterior; the float copies of the inputs are derived again
@@ -122,11 +123,15 @@ struct Resident {
   void installed() { post = Post::Installed; chol_valid = true; linv_p = Copy::Valid; }
   // -- the variational families (reset_generation follows).  A VGP call leaves sg_factors alone, the sparse ones drop it
   void variational_begun(bool sparse) { if (sparse) sg_factors = false; posterior_dropped(); }
-  // linv_p was written whole either way; ok: linv holds C = R L^-1 and every factorisation succeeded
+  // linv_p was written whole either way; ok: linv holds C = R L^-1 and every factorisation succeeded.  The install's own
+  // factors stay where gpso_paths_draw_q reads them until variational_begun() -- every call that writes Lf, q or the sparse
+  // factors starts with it -- or any other drop of the posterior: q_factors_kept() / posterior_dropped()
   void variational_ready(Post kind, bool ok) {
     small_tile_rows = 8;
-    if (ok) { post = kind; chol_valid = true; linv_p = Copy::Valid; }
+    if (ok) { post = kind; chol_valid = true; linv_p = Copy::Valid; q_factors_kept(); }
   }
+  // (at present implied by a variational kind with chol_valid: nothing clears it alone)
+  void q_factors_kept() { q_factors = true; }
   // -- hand-off
   void recarved() { small_tile_rows = 8; linv_b = linv_p = Copy::Absent; }  // the arena's slices moved: another layout's bytes
   // gpso_alloc_posterior: as for gpso_set_posterior, the rows about to arrive are neither data nor inducing points of this
@@ -142,7 +147,7 @@ struct Resident {
   // generation arithmetic and predict math: the sender's choice (its self-test ruled), unless this context insists
   void adopted(int sender, bool float_predict, bool math_auto, int gen_mode, int64_t npad) {
     post = Post::Adopted;
-    chol_valid = have_kinv = paths_valid = false;
+    chol_valid = have_kinv = paths_valid = q_factors = false;
     small_tile_rows = 8;         // linv_p came from elsewhere
     st_done = st_have = false;   // the fitting rank ran the self-test; no targets here
     math_native_fallback = math_auto && (sender & 2) != 0;

@@ -698,6 +698,15 @@ class HipGPEngine:
         ``omega`` [F, D] frequencies in scaled coordinates, ``phase`` [F], ``w`` [S, F] feature weights, ``eps`` [S, N]
         standard normals of the observation noise (None: zeros).  ``pygpso_amd.paths`` draws them from a seed.  The set
         lives until the posterior changes; ``paths_eval`` evaluates it."""
+        self._paths_draw(self._lib.gpso_paths_draw, omega, phase, w, eps)
+
+    def paths_draw_q(self, omega, phase, w, eps=None):
+        """``paths_draw`` for the variational posterior that ``vgp_posterior`` / ``sgpr_posterior`` / ``svgp_posterior``
+        installed (``gpso_paths_draw_q``): ``eps`` [S, n] are the whitened normals over the n RESIDENT rows -- the
+        training rows of a VGP, the M inducing points of the sparse two."""
+        self._paths_draw(self._lib.gpso_paths_draw_q, omega, phase, w, eps)
+
+    def _paths_draw(self, entry, omega, phase, w, eps):
         omega = L.as_f64(omega)
         if omega.ndim != 2 or (self.d and omega.shape[1] != self.d):
             raise ValueError(f"omega must be [F, D] with D={self.d}, got {omega.shape}")
@@ -711,8 +720,7 @@ class HipGPEngine:
             eps = L.as_f64(eps)
             if eps.shape != (s, self.n):
                 raise ValueError(f"eps must be [S, N] = [{s}, {self.n}], got {eps.shape}")
-        self._check(self._lib.gpso_paths_draw(self._h, L.dptr(omega), L.dptr(phase), f, L.dptr(w),
-                                              None if eps is None else L.dptr(eps), s))
+        self._check(entry(self._h, L.dptr(omega), L.dptr(phase), f, L.dptr(w), None if eps is None else L.dptr(eps), s))
 
     def paths_info(self):
         """(S, F) of the valid path set, (0, 0) when none is resident."""

@@ -454,6 +454,14 @@ class HipGPR:
         omega, phase, w, eps = draw_path_inputs(self._theta()[0], n_paths, n_features, x.shape[0], x.shape[1], rng)
         self._predicting(lambda: self.engine.paths_draw(omega, phase, w, eps))
 
+    def _sample_paths_q(self, n_rows, n_paths, n_features, rng):
+        """``sample_paths`` of the variational families (``gpso_paths_draw_q``): the same generator in the same order, the
+        normals being the whitened ones over the ``n_rows`` rows the installed posterior lives on."""
+        from .paths import draw_path_inputs
+
+        omega, phase, w, eps = draw_path_inputs(self.kernel.name, n_paths, n_features, n_rows, self._data[0].shape[1], rng)
+        self._predicting(lambda: self.engine.paths_draw_q(omega, phase, w, eps))
+
     def eval_paths(self, Xnew, seg_off=None, want_values=True):
         """The path set of ``sample_paths`` at the rows of Xnew (any M): (values [S, M] or None, best_idx [S, nseg],
         best_val [S, nseg]) -- per draw and segment of ``seg_off`` the first arg-max relative to the segment start and

@@ -214,6 +214,11 @@ class HipSGPR(HipGPR):
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.likelihood.variance)
 
+    def sample_paths(self, n_paths, n_features=1024, rng=None):
+        """``HipGPR.sample_paths`` for the installed posterior over Z (``gpso_paths_draw_q``; ``HipSVGP`` inherits it): the
+        normals are the M whitened ones, and a path costs O(M + F) a point whatever N."""
+        self._sample_paths_q(int(self.engine.n), n_paths, n_features, rng)
+
     # -- reporting -----------------------------------------------------------------------------
     def _z_note(self):
         return "(trained)" if self._z is not None else "(not trained)"

@@ -159,6 +159,11 @@ class HipVGP(HipGPR):
         mean, var = self.predict_y(Xnew)
         return mean, _as_result(np.asarray(var) - self.predictive_noise())
 
+    def sample_paths(self, n_paths, n_features=1024, rng=None):
+        """``HipGPR.sample_paths`` for the installed q (``gpso_paths_draw_q``): the normals are the N whitened ones.  The
+        draws come from q itself -- a Student-t install's shift is in the served variance only."""
+        self._sample_paths_q(self._data[0].shape[0], n_paths, n_features, rng)
+
     # -- training -------------------------------------------------------------------------------
     def _args(self):
         return self.kernel.name, self.n_ls, self._train_mean, float(self.mean_function.c)
