@@ -629,6 +629,55 @@ int gpso_best_ucb_begin(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem,
 int gpso_best_ucb_grow_begin(gpso_ctx* ctx, const double* bounds, int nseg, int depth, double varsigma);
 int gpso_best_ucb_end(gpso_ctx* ctx, int ticket, int64_t* idx, double* mean, double* var, double* ucb);
 
+/* ---- acquisition functions (no counterpart in the reference: it ranks by mean + varsigma * VAR only) ----------------
+ *
+ * What a leaf is ranked by, as a map of the (mean, var) the predict path produces -- maximisation throughout:
+ *   d = mean - incumbent - xi,   s = sqrt(max(s2, 0)),   z = d / s
+ *   GPSO_ACQ_UCB_VAR   mean + varsigma * var      the reference's rule: the bits of gpso_best_ucb
+ *   GPSO_ACQ_UCB_STD   mean + varsigma * s        GP-UCB, in score units; numpy's bits of  m + vs * np.sqrt(v)
+ *   GPSO_ACQ_EI        s * (phi(z) + z * Phi(z))  expected improvement over the incumbent
+ *   GPSO_ACQ_LOGEI     log EI                     finite and accurate where float64 EI is 0.0 (z below about -38)
+ *   GPSO_ACQ_PI        Phi(z)                     probability of improvement
+ * s2 is the predictive variance the call returns (noise included, as the reference's UCB reads it); with latent != 0
+ * it is the latent one, variance - sum before the noise is added.  UCB_VAR reads var as it is; the other kinds clamp s2
+ * at 0 from below.  s == 0: EI = max(d, 0), LOGEI = log max(d, 0) (-inf for d <= 0), PI = 1, 1/2 or 0 by the sign of d.
+ * A leaf with a NaN coordinate gets a NaN value (and wins its segment, as under gpso_best_ucb).
+ * GPSO_E_ARG: acq NULL, an unknown kind, a non-finite varsigma (the UCB kinds) or incumbent / xi (EI, LOGEI, PI). */
+#define GPSO_ACQ_UCB_VAR 0
+#define GPSO_ACQ_UCB_STD 1
+#define GPSO_ACQ_EI 2
+#define GPSO_ACQ_LOGEI 3
+#define GPSO_ACQ_PI 4
+typedef struct {
+  int kind;   /* GPSO_ACQ_* */
+  int latent; /* != 0: EI / LOGEI / PI / UCB_STD read the latent variance */
+  double varsigma, incumbent, xi;
+} gpso_acq;
+
+/* gpso_best_ucb, gpso_best_ucb_begin, gpso_best_ucb_grow and gpso_best_ucb_grow_begin with the acquisition in place of
+ * varsigma: the same arguments, state rules, routes (small-call kernels, two-stage and keyed arg-max, one-launch calls),
+ * first-maximum and NaN rules; `value` receives the winner's acquisition value.  Every posterior the predict path serves
+ * is served (fitted, appended, installed, VGP, SGPR, SVGP).  Tickets of the _begin calls are ended with
+ * gpso_best_ucb_end, and share its two slots.  With kind GPSO_ACQ_UCB_VAR every output has the bits of the gpso_best_ucb*
+ * call.  (No sharded variants: the group fold is acquisition-agnostic, the local halves take varsigma only.) */
+int gpso_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                  const gpso_acq* acq, int64_t* idx, double* mean, double* var, double* value);
+int gpso_best_acq_begin(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
+                        int nseg, const gpso_acq* acq);
+int gpso_best_acq_grow(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq, int64_t* idx,
+                       double* mean, double* var, double* value);
+int gpso_best_acq_grow_begin(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq);
+
+/* gpso_predict with the acquisition column: mean / var / value [m] (float64 living in out_mem, each nullable, not all
+ * three).  mean and var have the bits of gpso_predict on the same batch; value[j] is what gpso_best_acq ranks leaf j by
+ * (np.argmax of it is gpso_best_acq's idx).  State rules and errors as gpso_predict. */
+int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double* mean,
+                    double* var, double* value, int out_mem);
+
+/* The same maps on the host: out[i] from (mean[i], var[i]), n each; with latent != 0 the kinds that read it use
+ * var[i] - noise.  No context and no GPU (as gpso_shard_range); returns GPSO_OK or GPSO_E_ARG. */
+int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out);
+
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 
 /* Centres of levels 0..depth-1 of the ternary subtree under each of nseg boxes, generated on the

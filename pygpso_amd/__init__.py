@@ -6,6 +6,7 @@ Public names mirror the reference package (``gpso/__init__.py:10-12``).
 """
 __version__ = "0.1.0"
 
+from .acquisition import EI, PI, LogEI, UCBStd, UCBVar  # noqa: F401
 from .engine import HipGPEngine  # noqa: F401
 from .gp_surrogate import GPListOfPoints, GPPoint, GPRSurrogate, GPSurrogate, SGPRSurrogate, SVGPSurrogate, VGPSurrogate  # noqa: F401
 from .grids import conditional_surrogate_grids  # noqa: F401

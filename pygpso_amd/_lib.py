@@ -45,6 +45,7 @@ CONTRACTION_AUTO, CONTRACTION_F32, CONTRACTION_F16 = 0, 1, 2
 SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FUSED32 = 0, 1, 2, 3
 OPTF_TOL_VAR, OPTF_TOL_MEAN = 100, 101
 GEN_F64, GEN_F32, GEN_AUTO = 0, 1, 2
+ACQ_UCB_VAR, ACQ_UCB_STD, ACQ_EI, ACQ_LOGEI, ACQ_PI = 0, 1, 2, 3, 4
 FITMATH_NONE, FITMATH_SMALL, FITMATH_F32, FITMATH_F64, FITMATH_BF16X6, FITMATH_F16X3 = 0, 1, 2, 3, 4, 5  # gpso_last_count(ctx, 2)
 GEN_IDS = {"float64": GEN_F64, "f64": GEN_F64, "float32": GEN_F32, "f32": GEN_F32, "auto": GEN_AUTO}
 DTYPE_IDS = {"float64": F64, "fp64": F64, "f64": F64, "float32": F32, "fp32": F32, "f32": F32, "mixed": MIXED}
@@ -63,6 +64,15 @@ KERNEL_IDS = {
 
 _c_double_p = C.POINTER(C.c_double)
 _c_int64_p = C.POINTER(C.c_int64)
+
+
+class GpsoAcq(C.Structure):
+    """``gpso_acq``: what a best-acquisition call ranks by."""
+    _fields_ = [("kind", C.c_int), ("latent", C.c_int), ("varsigma", C.c_double), ("incumbent", C.c_double),
+                ("xi", C.c_double)]
+
+
+_c_acq_p = C.POINTER(GpsoAcq)
 
 # every symbol include/gpso_hip.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -140,6 +150,15 @@ SIGNATURES = {
     "gpso_best_ucb_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, C.c_double]),
     "gpso_best_ucb_grow_begin": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_double]),
     "gpso_best_ucb_end": (C.c_int, [C.c_void_p, C.c_int, _c_int64_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_best_acq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, _c_acq_p,
+                                _c_int64_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_best_acq_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, _c_acq_p]),
+    "gpso_best_acq_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_acq_p, _c_int64_p, _c_double_p,
+                                     _c_double_p, _c_double_p]),
+    "gpso_best_acq_grow_begin": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, _c_acq_p]),
+    "gpso_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int]),
+    "gpso_acq_eval_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, C.c_double, C.c_int64, _c_double_p]),
     "gpso_grow_rows": (C.c_int64, [C.c_int]),
     "gpso_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p]),
     "gpso_best_ucb_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_double,

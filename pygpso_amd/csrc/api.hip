@@ -106,14 +106,17 @@ struct Engine {
   virtual int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values,
                          int out_mem, int64_t* best_idx, double* best_val) = 0;
   virtual void paths_info(int64_t* s, int64_t* f) const = 0;
+  // mean, var and the acquisition column of every leaf (each output nullable)
+  virtual int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
+                         double* value, int out_mem) = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
-                       int nseg, double varsigma, int64_t* idx, double* mean, double* var,
+                       int nseg, const AcqSpec& acq, int64_t* idx, double* mean, double* var,
                        double* ucb) = 0;
   virtual int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
-                             double varsigma, const double* bounds, int depth) = 0;
+                             const AcqSpec& acq, const double* bounds, int depth) = 0;
   virtual int best_ucb_end(int ticket, int64_t* idx, double* mean, double* var, double* ucb) = 0;
   virtual int grow(const double* bounds, int nseg, int d, int depth, double* out) = 0;
-  virtual int best_ucb_grow(const double* bounds, int nseg, int depth, double varsigma,
+  virtual int best_ucb_grow(const double* bounds, int nseg, int depth, const AcqSpec& acq,
                             int64_t* idx, double* mean, double* var, double* ucb) = 0;
   virtual int get_matrix(int which, double* out) = 0;
   virtual int get_vector(int which, double* out) = 0;
@@ -2468,7 +2471,7 @@ struct EngineT : Engine {
   // a LeafFinalize) -- when the batch is ONE chunk the finalize launch is skipped and *defer says what to finalise;
   // otherwise defer->part_var stays NULL and the leaves are finalised here as before
   template <typename TG>
-  int score_leaves_t(const void* xs_dev, int xs_dtype, int64_t m, double varsigma, bool want_ucb,
+  int score_leaves_t(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb,
                      double* mean_dev, double* var_dev, double* ucb_dev, const int64_t* m_live, LeafFinalize* defer,
                      bool prepared = false /* leaves_s / lnorm already hold the scaled rows (one chunk): no prep launch */) {
     // row blocks of L^-1 = partial sums per leaf: the split-bf16 kernel always works on 256-row blocks,
@@ -2567,17 +2570,17 @@ struct EngineT : Engine {
       if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs + 1], s));
       ++ctx->tile_pairs;
       if (defer != nullptr && nchunk == 1 && want_ucb) {
-        *defer = LeafFinalize{as<double>(pvar), as<double>(pmean), nbi, mp, kp.variance, kp.noise, kp.mean_c, varsigma,
-                              mean_dev, var_dev, ucb_dev, fused_prep ? nullptr : lnorm.p, sizeof(TG) == 8};
+        *defer = LeafFinalize{as<double>(pvar), as<double>(pmean), nbi, mp, kp.variance, kp.noise, kp.mean_c, acq.varsigma,
+                              mean_dev, var_dev, ucb_dev, fused_prep ? nullptr : lnorm.p, sizeof(TG) == 8}.with(acq);
         continue;
       }
-      launch_leaf_finalize(s, as<double>(pvar), as<double>(pmean), nbi, mp, mc, kp, varsigma, mean_dev + off,
+      launch_leaf_finalize(s, as<double>(pvar), as<double>(pmean), nbi, mp, mc, kp, acq, mean_dev + off,
                            var_dev + off, want_ucb ? ucb_dev + off : nullptr, fused_prep ? nullptr : lnorm.p, sizeof(TG) == 8);
     }
     return launch_status();  // (no host wait here: the kernel time is read after the call's final sync)
   }
 
-  int score_device_leaves(const void* xs_dev, int xs_dtype, int64_t m, double varsigma, bool want_ucb,
+  int score_device_leaves(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb,
                           double* mean_dev, double* var_dev, double* ucb_dev, const int64_t* m_live = nullptr,
                           LeafFinalize* defer = nullptr, bool prepared = false) {
     if (defer != nullptr) *defer = LeafFinalize{};
@@ -2585,10 +2588,10 @@ struct EngineT : Engine {
       if (!gen_double()) {
         int rc = ensure_generation_inputs();
         if (rc) return rc;
-        return score_leaves_t<float>(xs_dev, xs_dtype, m, varsigma, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
+        return score_leaves_t<float>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
       }
     }
-    return score_leaves_t<double>(xs_dev, xs_dtype, m, varsigma, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
+    return score_leaves_t<double>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
   }
 
   // after the stream has been synchronised: total leaf-tile kernel time of the call
@@ -2805,6 +2808,49 @@ struct EngineT : Engine {
     if (out_mem == GPSO_MEM_HOST) {
       HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
       HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    }
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+    HIPCHECK(ctx->wait(s));
+    collect_tile_ms();
+    ctx->last_count[0] = ctx->last_count[1] = m;
+    float ms = 0;
+    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+    return GPSO_OK;
+  }
+
+  // gpso_predict with the acquisition column (acq.hpp) beside mean and var: the same tiles, the same finalize kernel --
+  // mean / var are gpso_predict's bits, the column is what gpso_best_acq ranks by.  Outputs the caller does not want
+  // stay in the context's own buffers
+  int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
+                 double* value, int out_mem) override {
+    ctx->tick_timing();
+    int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    if (m == 0) return GPSO_OK;
+    if (!mean && !var && !value) return ctx->fail(GPSO_E_ARG, "mean, var and value are all NULL");
+    hipStream_t s = st();
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    const bool host = out_mem == GPSO_MEM_HOST;
+    double *md = mean, *vd = var, *ud = value;
+    if (host || !mean) {
+      if ((rc = ensure(omean, (size_t)m * 8))) return rc;
+      md = as<double>(omean);
+    }
+    if (host || !var) {
+      if ((rc = ensure(ovar, (size_t)m * 8))) return rc;
+      vd = as<double>(ovar);
+    }
+    if (host || !value) {
+      if ((rc = ensure(oucb, (size_t)m * 8))) return rc;
+      ud = as<double>(oucb);
+    }
+    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, vd, ud))) return rc;
+    if (host) {
+      if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      if (value) HIPCHECK(hipMemcpyAsync(value, ud, (size_t)m * 8, hipMemcpyDeviceToHost, s));
     }
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
     HIPCHECK(ctx->wait(s));
@@ -3220,7 +3266,7 @@ struct EngineT : Engine {
   bool one_pending = false;  // the call in flight is a one-launch call: finish_best looks at its fallback verdict
   bool coll_timed = false;   // the call in flight recorded the event pair around its collective (all-gather + fold)
   template <typename TG>
-  int try_one_launch_t(OneLaunch& one, int64_t total, int nseg, double varsigma) {
+  int try_one_launch_t(OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq) {
     const int64_t cpad = (total + kLeafPad - 1) / kLeafPad * kLeafPad;
     int rc;
     if ((rc = ensure(leaves_s, (size_t)cpad * dp * sizeof(TG)))) return rc;
@@ -3242,8 +3288,8 @@ struct EngineT : Engine {
     one.leaves_s = leaves_s.p;
     one.lnorm = lnorm.p;
     one.key = as<int64_t>(grow_key);
-    one.fin = LeafFinalize{as<double>(pvar), as<double>(pmean), 1, cpad, kp.variance, kp.noise, kp.mean_c, varsigma,
-                           as<double>(omean), as<double>(ovar), as<double>(oucb), lnorm.p, sizeof(TG) == 8};
+    one.fin = LeafFinalize{as<double>(pvar), as<double>(pmean), 1, cpad, kp.variance, kp.noise, kp.mean_c, acq.varsigma,
+                           as<double>(omean), as<double>(ovar), as<double>(oucb), lnorm.p, sizeof(TG) == 8}.with(acq);
     one.partial = one_partial.p;
     one.ppos = as<int64_t>(one_ppos);
     one.ticket = static_cast<unsigned*>(one_ctl.p);
@@ -3279,7 +3325,7 @@ struct EngineT : Engine {
     one_pending = true;
     return launch_status();
   }
-  int try_one_launch(OneLaunch& one, int64_t total, int nseg, double varsigma) {
+  int try_one_launch(OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq) {
     if (!small_calls || !one_launch || one_refused || total <= 0 || total > kSmallBestMaxRows || nseg > 16) return 2;
     if (npad != 128 && npad != 256) return 2;
     // measured (tools/micro/one_dbg.py, float64, same box; wall us per best_ucb_grow call, one | three launches):
@@ -3294,16 +3340,16 @@ struct EngineT : Engine {
       if (!gen_double()) {
         int rc = ensure_generation_inputs();
         if (rc) return rc;
-        return try_one_launch_t<float>(one, total, nseg, varsigma);
+        return try_one_launch_t<float>(one, total, nseg, acq);
       }
     }
-    return try_one_launch_t<double>(one, total, nseg, varsigma);
+    return try_one_launch_t<double>(one, total, nseg, acq);
   }
 
   // per segment (mean, var, ucb, bit-cast index relative to the segment start) -> ovals; seg_off: host,
   // nseg + 1 entries over [0, m]
   int enqueue_best_leaves(const void* dev, int xs_dtype, int64_t m, const int64_t* seg_off, int nseg,
-                          double varsigma) {
+                          const AcqSpec& acq) {
     int rc;
     one_pending = false;  // (a call whose result was never read -- gpso_shard_winners -- leaves nothing behind)
     host_direct = nullptr;
@@ -3337,14 +3383,14 @@ struct EngineT : Engine {
       one.raw = dev;
       one.raw_f64 = xs_dtype == GPSO_F64 ? 1 : 0;
       one.seg_off = as<int64_t>(segoff);
-      if ((rc = try_one_launch(one, m, nseg, varsigma)) != 2) {
+      if ((rc = try_one_launch(one, m, nseg, acq)) != 2) {
         ctx->last_count[0] = ctx->last_count[1] = m;
         return rc;
       }
     }
     LeafFinalize fin{};
     if (m > 0)
-      if ((rc = score_device_leaves(dev, xs_dtype, m, varsigma, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin))) return rc;
+      if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin))) return rc;
     // (round 4: the leaves of a one-chunk batch are finalised by the arg-max's first stage, and its second stage writes
     // the winners' records straight into the pinned host memory finish_best reads: two launches and a copy less per call)
     host_direct = result_host((size_t)nseg * 4 + 2);
@@ -3371,7 +3417,7 @@ struct EngineT : Engine {
   // the reference rows [row_lo, row_hi) of the sub-tree under every box, de-duplicated (grow.hip), scored;
   // per segment (mean, var, ucb, bit-cast REFERENCE row index) -> ovals, live row count -> ovals[nseg*4]
   int enqueue_best_grow(const double* bounds, int nseg, int depth, int64_t row_lo, int64_t row_hi,
-                        double varsigma) {
+                        const AcqSpec& acq) {
     if (!bounds) return ctx->fail(GPSO_E_ARG, "bounds must not be NULL");
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
     if (depth < 0 || depth > 16) return ctx->fail(GPSO_E_ARG, "depth %d outside [0, 16]", depth);
@@ -3405,7 +3451,7 @@ struct EngineT : Engine {
         one.depth = depth;
         one.rows = rows;
         one.uniq = uniq;
-        if ((rc = try_one_launch(one, (int64_t)nseg * uniq, nseg, varsigma)) != 2) {
+        if ((rc = try_one_launch(one, (int64_t)nseg * uniq, nseg, acq)) != 2) {
           ctx->last_count[1] = cap;
           return rc;
         }
@@ -3430,7 +3476,7 @@ struct EngineT : Engine {
       if (gen_double())
         launch_grow_unique_prep<double>(s, gb, nseg, d, dp, depth, row_lo, row_hi, ls_dev(), as<double>(leaves_s), as<double>(lnorm), as<int64_t>(grow_key), extra);
       LeafFinalize fin{};
-      if ((rc = score_device_leaves(nullptr, GPSO_F64, cap, varsigma, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin, true)))
+      if ((rc = score_device_leaves(nullptr, GPSO_F64, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin, true)))
         return rc;
       if (fin.part_var == nullptr) return ctx->fail(GPSO_E_STATE, "internal: small growth call was not deferred");
       host_direct = result_host((size_t)nseg * 4 + 2);
@@ -3461,7 +3507,7 @@ struct EngineT : Engine {
                        as<int64_t>(live_cnt));
     LeafFinalize fin{};
     if (cap > 0)
-      if ((rc = score_device_leaves(leaves_raw.p, GPSO_F64, cap, varsigma, true, as<double>(omean), as<double>(ovar),
+      if ((rc = score_device_leaves(leaves_raw.p, GPSO_F64, cap, acq, true, as<double>(omean), as<double>(ovar),
                                     as<double>(oucb), as<int64_t>(live_cnt), &fin)))
         return rc;
     host_direct = result_host((size_t)nseg * 4 + 2);
@@ -3651,7 +3697,7 @@ struct EngineT : Engine {
   }
 
   int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
-               double varsigma, int64_t* idx, double* mean, double* var, double* ucb) override {
+               const AcqSpec& acq, int64_t* idx, double* mean, double* var, double* ucb) override {
     ctx->tick_timing();
     int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
     if (rc) return rc;
@@ -3659,7 +3705,7 @@ struct EngineT : Engine {
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
     const void* dev = nullptr;
     if (m > 0 && (rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    if ((rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, varsigma))) return rc;
+    if ((rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq))) return rc;
     return finish_best(ovals, nseg, 0, idx, mean, var, ucb);
   }
 
@@ -3669,7 +3715,7 @@ struct EngineT : Engine {
   // read, ctypes, Python: 42 us of a 0.77 ms step at C3, profiles/r04_step_timeline.txt).  Every call has its own pinned
   // result slot -- the arg-max kernels write their records there -- and a completion event; the device-side scratch is
   // shared and ordered by the stream.  No timing events, no one-launch kernel (it may ask for a re-run).
-  int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double varsigma,
+  int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
                      const double* bounds, int depth) override {
     const bool grown = bounds != nullptr;
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
@@ -3708,11 +3754,11 @@ struct EngineT : Engine {
         }
       } region(this, ctx->slot_host + (size_t)k * gpso_ctx::kSlotDoubles);
       if (grown) {
-        rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), varsigma);
+        rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq);
       } else {
         const void* dev = nullptr;
         if (m > 0) rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev);
-        if (rc == GPSO_OK) rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, varsigma);
+        if (rc == GPSO_OK) rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq);
       }
       ctx->slot_token[k] = call_token;
     }
@@ -3831,18 +3877,18 @@ struct EngineT : Engine {
   // that repeat an earlier row bit for bit (a centre child repeats its parent: 1/3 of the reference's
   // list, gpso/param_space.py:186-200), scored, and the winner is reported by its REFERENCE row index --
   // the result is what gp_eval_best_ucb(leaf.grow(depth)) returns (grow.hip: grow_unique_kernel).
-  int best_ucb_grow(const double* bounds, int nseg, int depth, double varsigma, int64_t* idx,
+  int best_ucb_grow(const double* bounds, int nseg, int depth, const AcqSpec& acq, int64_t* idx,
                     double* mean, double* var, double* ucb) override {
     ctx->tick_timing();
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     int rc = precision_gate();
     if (rc) return rc;
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
-    if ((rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), varsigma))) return rc;
+    if ((rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq))) return rc;
     rc = finish_best(ovals, nseg, 1, idx, mean, var, ucb);
     if (rc == 1) {  // the one-launch kernel met a near-duplicate it has no slot for: the sequence with the append counter
       one_refused = true;
-      rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), varsigma);
+      rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq);
       one_refused = false;
       if (rc) return rc;
       rc = finish_best(ovals, nseg, 1, idx, mean, var, ucb);
@@ -4936,6 +4982,59 @@ int gpso_best_ucb_grow(gpso_ctx* ctx, const double* bounds, int nseg, int depth,
                        int64_t* idx, double* mean, double* var, double* ucb) {
   ENTER();
   return ctx->eng->best_ucb_grow(bounds, nseg, depth, varsigma, idx, mean, var, ucb);
+}
+
+// ---- acquisition functions (acq.hpp) ----------------------------------------------------------
+// NULL when the record is usable, else what is wrong with it
+static const char* acq_refusal(const gpso_acq* a) {
+  if (!a) return "acq must not be NULL";
+  if (a->kind < GPSO_ACQ_UCB_VAR || a->kind > GPSO_ACQ_PI) return "unknown acquisition kind";
+  const bool ucb = a->kind == GPSO_ACQ_UCB_VAR || a->kind == GPSO_ACQ_UCB_STD;
+  if (ucb && !std::isfinite(a->varsigma)) return "varsigma must be finite";
+  if (!ucb && !std::isfinite(a->incumbent)) return "incumbent must be finite";
+  if (!ucb && !std::isfinite(a->xi)) return "xi must be finite";
+  return nullptr;
+}
+static gpso::AcqSpec acq_spec(const gpso_acq* a) { return gpso::AcqSpec(a->kind, a->latent != 0, a->varsigma, a->incumbent, a->xi); }
+#define ACQ_ENTER()                                              \
+  ENTER();                                                       \
+  if (const char* why = acq_refusal(acq)) return ctx->fail(GPSO_E_ARG, "%s", why)
+
+int gpso_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                  const gpso_acq* acq, int64_t* idx, double* mean, double* var, double* value) {
+  ACQ_ENTER();
+  return ctx->eng->best_ucb(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), idx, mean, var, value);
+}
+
+int gpso_best_acq_begin(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                        const gpso_acq* acq) {
+  ACQ_ENTER();
+  return ctx->eng->best_ucb_begin(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), nullptr, 0);
+}
+
+int gpso_best_acq_grow(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq, int64_t* idx,
+                       double* mean, double* var, double* value) {
+  ACQ_ENTER();
+  return ctx->eng->best_ucb_grow(bounds, nseg, depth, acq_spec(acq), idx, mean, var, value);
+}
+
+int gpso_best_acq_grow_begin(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq) {
+  ACQ_ENTER();
+  if (!bounds) return ctx->fail(GPSO_E_ARG, "bounds must not be NULL");
+  return ctx->eng->best_ucb_begin(nullptr, GPSO_F64, GPSO_MEM_DEVICE, 0, nullptr, nseg, acq_spec(acq), bounds, depth);
+}
+
+int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double* mean,
+                    double* var, double* value, int out_mem) {
+  ACQ_ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  return ctx->eng->acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), mean, var, value, out_mem);
+}
+
+int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out) {
+  if (acq_refusal(acq) != nullptr || n < 0 || (n > 0 && (!mean || !var || !out)) || noise != noise) return GPSO_E_ARG;
+  gpso::acq_eval_host(acq_spec(acq), mean, var, noise, (long long)n, out);
+  return GPSO_OK;
 }
 
 int64_t gpso_padded_n(const gpso_ctx* ctx) {

@@ -5,6 +5,7 @@
 //              TG = generation type of the cross-Gram tile's x.x* contraction and r^2 (float | double;
 //                   double by default also in float contexts, see predict.hip)
 #pragma once
+#include "acq.hpp"
 #include "common.hpp"
 
 namespace gpso {
@@ -136,9 +137,22 @@ struct LeafFinalize {
   // max(r^2, 1e-36) would otherwise turn its r^2 into 0 against every training point (finite garbage, negative variance)
   const void* lnorm = nullptr;
   int lnorm_f64 = 0;
+  // what the `ucb` column holds and the arg-max ranks by (acq.hpp); uniform over a launch.  GPSO_ACQ_UCB_VAR reads
+  // varsigma only and keeps the arithmetic above; the other kinds read the latent variance (variance - sum) when
+  // `latent` is set, the predictive one otherwise
+  int kind = GPSO_ACQ_UCB_VAR, latent = 0;
+  double incumbent = 0, xi = 0;
+  LeafFinalize& with(const AcqSpec& a) {
+    varsigma = a.varsigma;
+    kind = a.kind;
+    latent = a.latent;
+    incumbent = a.incumbent;
+    xi = a.xi;
+    return *this;
+  }
 };
 void launch_leaf_finalize(hipStream_t st, const double* part_var, const double* part_mean, int nbi,
-                          int64_t mpad, int64_t m, const KernParams& kp, double varsigma,
+                          int64_t mpad, int64_t m, const KernParams& kp, const AcqSpec& acq,
                           double* mean, double* var, double* ucb, const void* lnorm = nullptr, int lnorm_f64 = 0);
 void launch_seg_argmax(hipStream_t st, const double* mean, const double* var, const double* ucb,
                        const int64_t* seg_off_dev, int nseg, int nblk, void* partial_dev,

@@ -57,7 +57,11 @@ __device__ __forceinline__ bool leaf_norm_is_nan(const void* lnorm, int f64, int
   const float q = static_cast<const float*>(lnorm)[j];
   return q != q;
 }
-// one leaf: sum the row blocks' partials, form mean / var (+ noise) / ucb, store them; returns ucb
+// one leaf: sum the row blocks' partials, form mean / var (+ noise) / ucb, store them; returns ucb.
+// ACQ false: the reference's rule only (the arg-max kernels of a gpso_best_ucb call: their code as it was before the
+// acquisition maps, registers included); true: whatever f.kind names -- the kind arrives as a kernel argument, so the
+// branch is scalar and uniform over the launch
+template <bool ACQ>
 __device__ __forceinline__ double finalize_leaf(const LeafFinalize& f, int64_t j) {
   double v = 0, mu = 0;
   for (int b = 0; b < f.nbi; ++b) {
@@ -66,14 +70,20 @@ __device__ __forceinline__ double finalize_leaf(const LeafFinalize& f, int64_t j
   }
   if (leaf_norm_is_nan(f.lnorm, f.lnorm_f64, j)) v = mu = __builtin_nan("");  // (a NaN coordinate: NaN out, as the reference)
   // [gpflow base_conditional] fvar = k** - sum A^2 ; predict_y adds the noise variance
-  const double vy = __dadd_rn(__dsub_rn(f.variance, v), f.noise);
+  const double fv = __dsub_rn(f.variance, v);
+  const double vy = __dadd_rn(fv, f.noise);
   const double my = __dadd_rn(mu, f.mean_c);
   f.mean[j] = my;
   f.var[j] = vy;
-  // gpso/gp_surrogate.py:326  ucb = mean + varsigma * var  (two roundings, as numpy does)
-  double prod = f.varsigma * vy;
-  asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
-  const double u = my + prod;
+  double u;
+  if (!ACQ || f.kind == GPSO_ACQ_UCB_VAR) {
+    // gpso/gp_surrogate.py:326  ucb = mean + varsigma * var  (two roundings, as numpy does)
+    double prod = f.varsigma * vy;
+    asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
+    u = my + prod;
+  } else {
+    u = acq_value(AcqSpec(f.kind, f.latent, f.varsigma, f.incumbent, f.xi), my, f.latent ? fv : vy);
+  }
   f.ucb[j] = u;
   return u;
 }
@@ -335,7 +345,7 @@ __device__ __forceinline__ void one_launch_epilogue(const OneLaunch& o, int tid,
   double u = 0;
   int64_t id = -1;
   if (mine_row) {
-    u = finalize_leaf(o.fin, j);
+    u = finalize_leaf<true>(o.fin, j);
     id = (o.mode == 1) ? o.key[j] : j;
   }
   for (int seg = 0; seg < o.nseg; ++seg) {
@@ -896,7 +906,7 @@ template void launch_pack_linv_bf16<double>(hipStream_t, int, const double*, int
 __global__ __launch_bounds__(256) void leaf_finalize_kernel(const double* __restrict__ part_var,
                                                             const double* __restrict__ part_mean,
                                                             int nbi, int64_t mpad, int64_t m,
-                                                            KernParams kp, double varsigma,
+                                                            KernParams kp, AcqSpec acq,
                                                             double* __restrict__ mean,
                                                             double* __restrict__ var,
                                                             double* __restrict__ ucb, const void* __restrict__ lnorm,
@@ -910,15 +920,20 @@ __global__ __launch_bounds__(256) void leaf_finalize_kernel(const double* __rest
   }
   if (leaf_norm_is_nan(lnorm, lnorm_f64, j)) v = mu = __builtin_nan("");
   // [gpflow base_conditional] fvar = k** - sum A^2 ; predict_y adds the noise variance
-  const double vy = __dadd_rn(__dsub_rn(kp.variance, v), kp.noise);
+  const double fv = __dsub_rn(kp.variance, v);
+  const double vy = __dadd_rn(fv, kp.noise);
   const double my = __dadd_rn(mu, kp.mean_c);
   mean[j] = my;
   var[j] = vy;
-  // gpso/gp_surrogate.py:326  ucb = mean + varsigma * var  (two roundings, as numpy does)
   if (ucb) {
-    double prod = varsigma * vy;
-    asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
-    ucb[j] = my + prod;
+    if (acq.kind == GPSO_ACQ_UCB_VAR) {
+      // gpso/gp_surrogate.py:326  ucb = mean + varsigma * var  (two roundings, as numpy does)
+      double prod = acq.varsigma * vy;
+      asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
+      ucb[j] = my + prod;
+    } else {
+      ucb[j] = acq_value(acq, my, acq.latent ? fv : vy);
+    }
   }
 }
 
@@ -942,7 +957,7 @@ __device__ __forceinline__ Best block_best(Best mine, Best* sh) {
 // stage 1: grid (nblk, nseg); each block scans a strided share of its segment.  FIN (round 4): the leaves arrive as
 // the tile kernel's partial sums and are FINALISED here (leaf_finalize_kernel's arithmetic, leaf for leaf: every leaf
 // of [0, M) lies in exactly one segment) -- one launch and one pass over mean / var / ucb less per call
-template <bool FIN>
+template <bool FIN, bool ACQ>
 __global__ __launch_bounds__(256) void seg_argmax_stage1(const double* __restrict__ ucb,
                                                          const int64_t* __restrict__ seg_off,
                                                          Best* __restrict__ partial, LeafFinalize fin) {
@@ -952,7 +967,7 @@ __global__ __launch_bounds__(256) void seg_argmax_stage1(const double* __restric
   Best mine{0.0, -1};
   for (int64_t j = lo + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < hi;
        j += (int64_t)gridDim.x * blockDim.x) {
-    Best c{FIN ? finalize_leaf(fin, j) : ucb[j], j};
+    Best c{FIN ? finalize_leaf<ACQ>(fin, j) : ucb[j], j};
     if (better(c, mine)) mine = c;
   }
   mine = block_best(mine, sh);
@@ -1006,7 +1021,7 @@ __global__ __launch_bounds__(256) void seg_argmax_stage2(const Best* __restrict_
 // [seg * uniq, (seg + 1) * uniq) plus those rows of the appended tail [nseg * uniq, *live) whose key
 // falls into it.  The order is np.argmax's on (ucb, reference row index), so the winner and its index
 // are what scoring the full duplicated list would give.
-template <bool FIN>
+template <bool FIN, bool ACQ>
 __global__ __launch_bounds__(256) void keyed_argmax_stage1(const double* __restrict__ ucb,
                                                            const int64_t* __restrict__ key, int64_t rows,
                                                            int64_t uniq, int nseg,
@@ -1022,7 +1037,7 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage1(const double* __restr
   Best mine{0.0, -1};
   int64_t mypos = -1;
   for (int64_t j = (int64_t)seg * uniq + t0; j < (int64_t)(seg + 1) * uniq; j += stride) {
-    Best c{FIN ? finalize_leaf(fin, j) : ucb[j], key[j]};
+    Best c{FIN ? finalize_leaf<ACQ>(fin, j) : ucb[j], key[j]};
     if (better(c, mine)) {
       mine = c;
       mypos = j;
@@ -1032,7 +1047,7 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage1(const double* __restr
   for (int64_t j = (int64_t)nseg * uniq + t0; j < lv; j += stride) {
     const int64_t kj = key[j];
     if (kj / rows != seg) continue;
-    Best c{FIN ? finalize_leaf(fin, j) : ucb[j], kj};
+    Best c{FIN ? finalize_leaf<ACQ>(fin, j) : ucb[j], kj};
     if (better(c, mine)) {
       mine = c;
       mypos = j;
@@ -1115,7 +1130,7 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage2(const Best* __restric
 // Small batches (round 4): finalize + both arg-max stages in ONE launch of one workgroup.  Every live leaf is finalised
 // exactly once (finalize_leaf), every segment reduced with np.argmax's rule on (ucb, index / reference key): the same
 // records seg_argmax_* / keyed_argmax_* produce, with two launches (and the copy back) less.
-template <bool KEYED>
+template <bool KEYED, bool ACQ>
 __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
   __shared__ Best sh[4];
   __shared__ int64_t shp[4];
@@ -1126,7 +1141,7 @@ __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
     int64_t mypos = -1;
     if constexpr (KEYED) {
       for (int64_t j = (int64_t)seg * a.uniq + tid; j < (int64_t)(seg + 1) * a.uniq; j += 256) {
-        Best c{finalize_leaf(a.fin, j), a.key[j]};
+        Best c{finalize_leaf<ACQ>(a.fin, j), a.key[j]};
         if (better(c, mine)) {
           mine = c;
           mypos = j;
@@ -1135,7 +1150,7 @@ __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
       for (int64_t j = (int64_t)a.nseg * a.uniq + tid; j < live; j += 256) {
         const int64_t kj = a.key[j];
         if (kj / a.rows != seg) continue;
-        Best c{finalize_leaf(a.fin, j), kj};
+        Best c{finalize_leaf<ACQ>(a.fin, j), kj};
         if (better(c, mine)) {
           mine = c;
           mypos = j;
@@ -1143,7 +1158,7 @@ __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
       }
     } else {
       for (int64_t j = a.seg_off[seg] + tid; j < a.seg_off[seg + 1]; j += 256) {
-        Best c{finalize_leaf(a.fin, j), j};
+        Best c{finalize_leaf<ACQ>(a.fin, j), j};
         if (better(c, mine)) {
           mine = c;
           mypos = j;
@@ -1199,8 +1214,11 @@ __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
 }
 
 void launch_small_best(hipStream_t st, const SmallBest& a, bool keyed) {
-  if (keyed) hipLaunchKernelGGL(small_best_kernel<true>, dim3(1), dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(small_best_kernel<false>, dim3(1), dim3(256), 0, st, a);
+  // (the acquisition maps cost registers and code: the reference's rule keeps the kernels it had)
+  const bool acq = a.fin.kind != GPSO_ACQ_UCB_VAR;
+  auto* fn = keyed ? (acq ? small_best_kernel<true, true> : small_best_kernel<true, false>)
+                   : (acq ? small_best_kernel<false, true> : small_best_kernel<false, false>);
+  hipLaunchKernelGGL(fn, dim3(1), dim3(256), 0, st, a);
 }
 
 // multi-GPU: one thread per segment folds the ranks' winners in rank order with the same rule.  A rank's payload is
@@ -1407,22 +1425,29 @@ template int launch_leaf_tiles<float, double>(hipStream_t, const float*, const d
 template int launch_leaf_tiles<double, double>(hipStream_t, const double*, const double*, const double*, const double*, const double*, const double*, double*, double*, int64_t, int, int64_t, const KernParams&, const int64_t*);
 
 void launch_leaf_finalize(hipStream_t st, const double* part_var, const double* part_mean, int nbi,
-                          int64_t mpad, int64_t m, const KernParams& kp, double varsigma,
+                          int64_t mpad, int64_t m, const KernParams& kp, const AcqSpec& acq,
                           double* mean, double* var, double* ucb, const void* lnorm, int lnorm_f64) {
   const int64_t blocks = (m + 255) / 256;
   if (blocks == 0) return;
   hipLaunchKernelGGL(leaf_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part_var,
-                     part_mean, nbi, mpad, m, kp, varsigma, mean, var, ucb, lnorm, lnorm_f64);
+                     part_mean, nbi, mpad, m, kp, acq, mean, var, ucb, lnorm, lnorm_f64);
+}
+
+void acq_eval_host(const AcqSpec& a, const double* mean, const double* var, double noise, long long n, double* out) {
+  for (long long i = 0; i < n; ++i) out[i] = acq_value(a, mean[i], a.latent && a.kind != GPSO_ACQ_UCB_VAR ? var[i] - noise : var[i]);
 }
 
 void launch_seg_argmax(hipStream_t st, const double* mean, const double* var, const double* ucb,
                        const int64_t* seg_off_dev, int nseg, int nblk, void* partial_dev,
                        double* out_vals_dev, const LeafFinalize* fin, double* host_vals, double done_token) {
-  if (fin != nullptr)
-    hipLaunchKernelGGL(seg_argmax_stage1<true>, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+  if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
+    hipLaunchKernelGGL((seg_argmax_stage1<true, true>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+                       seg_off_dev, reinterpret_cast<Best*>(partial_dev), *fin);
+  else if (fin != nullptr)
+    hipLaunchKernelGGL((seg_argmax_stage1<true, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
                        seg_off_dev, reinterpret_cast<Best*>(partial_dev), *fin);
   else
-    hipLaunchKernelGGL(seg_argmax_stage1<false>, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+    hipLaunchKernelGGL((seg_argmax_stage1<false, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
                        seg_off_dev, reinterpret_cast<Best*>(partial_dev), LeafFinalize{});
   hipLaunchKernelGGL(seg_argmax_stage2, dim3((unsigned)nseg), dim3(256), 0, st,
                      reinterpret_cast<const Best*>(partial_dev), nblk, seg_off_dev, mean, var, ucb, nseg,
@@ -1433,11 +1458,14 @@ void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, 
                          const int64_t* key_dev, int64_t rows, int64_t uniq, int nseg, const int64_t* live_dev,
                          int nblk, void* partial_dev, int64_t* pos_dev, double* out_vals_dev, const LeafFinalize* fin,
                          double* host_vals, double done_token) {
-  if (fin != nullptr)
-    hipLaunchKernelGGL(keyed_argmax_stage1<true>, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+  if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
+    hipLaunchKernelGGL((keyed_argmax_stage1<true, true>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+                       rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
+  else if (fin != nullptr)
+    hipLaunchKernelGGL((keyed_argmax_stage1<true, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
   else
-    hipLaunchKernelGGL(keyed_argmax_stage1<false>, dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+    hipLaunchKernelGGL((keyed_argmax_stage1<false, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, LeafFinalize{});
   hipLaunchKernelGGL(keyed_argmax_stage2, dim3((unsigned)nseg), dim3(256), 0, st,
                      reinterpret_cast<const Best*>(partial_dev), pos_dev, nblk, rows, mean, var, ucb, live_dev,

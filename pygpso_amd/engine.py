@@ -806,6 +806,82 @@ class HipGPEngine:
         self._check(self._lib.gpso_best_ucb_end(self._h, int(ticket), L.i64ptr(idx), L.dptr(mean), L.dptr(var), L.dptr(ucb)))
         return idx, mean, var, ucb
 
+    # -- acquisition functions (pygpso_amd/acquisition.py; csrc/acq.hpp) ---------------------------------------------
+    def _seg_args(self, seg_off):
+        if seg_off is None:
+            return 1, None, None
+        so = np.ascontiguousarray(seg_off, dtype=np.int64)
+        return int(so.shape[0] - 1), L.i64ptr(so), so
+
+    def _bounds_arg(self, bounds):
+        b = L.as_f64(bounds)
+        if b.ndim == 2:
+            b = b[None]
+        nseg, d, _ = b.shape
+        if d != self.d:
+            raise ValueError(f"bounds have D={d}, model has D={self.d}")
+        return b, nseg
+
+    def best_acq(self, xs, acq, seg_off=None, incumbent=None):
+        """``best_ucb`` ranked by the acquisition spec ``acq`` -> (idx, mean, var, value) arrays of length nseg."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        nseg, so_ptr, _so = self._seg_args(seg_off)
+        rec = acq.c_struct(incumbent)
+        idx, mean, var, val, pi, pm, pv, pu = self._winner_bufs(nseg)
+        rc = self._lib.gpso_best_acq(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec), pi, pm, pv, pu)
+        if rc < 0:
+            self._check(rc)
+        return idx.copy(), mean.copy(), var.copy(), val.copy()
+
+    def best_acq_begin(self, xs, acq, seg_off=None, incumbent=None):
+        """Non-blocking ``best_acq``: a ticket for ``best_ucb_end`` (the two slots of ``best_ucb_begin``)."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        nseg, so_ptr, _so = self._seg_args(seg_off)
+        rec = acq.c_struct(incumbent)
+        ticket = self._check(self._lib.gpso_best_acq_begin(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec)))
+        self._open_tickets = getattr(self, "_open_tickets", {})
+        self._open_tickets[ticket] = (nseg, keep)
+        return ticket
+
+    def best_acq_grow(self, bounds, depth, acq, incumbent=None):
+        """``best_ucb_grow`` ranked by the acquisition spec ``acq``."""
+        b, nseg = self._bounds_arg(bounds)
+        rec = acq.c_struct(incumbent)
+        idx, mean, var, val, pi, pm, pv, pu = self._winner_bufs(nseg)
+        rc = self._lib.gpso_best_acq_grow(self._h, L.dptr(b), nseg, int(depth), C.byref(rec), pi, pm, pv, pu)
+        if rc < 0:
+            self._check(rc)
+        return idx.copy(), mean.copy(), var.copy(), val.copy()
+
+    def best_acq_grow_begin(self, bounds, depth, acq, incumbent=None):
+        b, nseg = self._bounds_arg(bounds)
+        rec = acq.c_struct(incumbent)
+        ticket = self._check(self._lib.gpso_best_acq_grow_begin(self._h, L.dptr(b), nseg, int(depth), C.byref(rec)))
+        self._open_tickets = getattr(self, "_open_tickets", {})
+        self._open_tickets[ticket] = (nseg, None)
+        return ticket
+
+    def acq_values(self, xs, acq, incumbent=None):
+        """``predict`` with the acquisition column: (mean[M], var[M], value[M]) float64 on the host."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec = acq.c_struct(incumbent)
+        mean, var, val = (np.empty(m, dtype=np.float64) for _ in range(3))
+        self._check(self._lib.gpso_acq_values(self._h, ptr, dt, mem, m, C.byref(rec), C.c_void_p(mean.ctypes.data),
+                                              C.c_void_p(var.ctypes.data), C.c_void_p(val.ctypes.data), L.MEM_HOST))
+        return mean, var, val
+
+    @staticmethod
+    def acq_eval_host(acq, mean, var, noise=0.0, incumbent=None):
+        """The device's acquisition maps on the CPU (``gpso_acq_eval_host``: no context, no GPU) -> value[n]."""
+        mean = L.as_f64(np.asarray(mean).reshape(-1))
+        var = L.as_f64(np.asarray(var).reshape(-1), mean.shape)
+        out = np.empty_like(mean)
+        rec = acq.c_struct(incumbent)
+        rc = L.load().gpso_acq_eval_host(C.byref(rec), L.dptr(mean), L.dptr(var), float(noise), int(mean.shape[0]), L.dptr(out))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_acq_eval_host: bad acquisition record or arguments")
+        return out
+
     # -- ternary geometry ------------------------------------------------------------------------
     def grow_rows(self, depth):
         return int(self._lib.gpso_grow_rows(int(depth)))

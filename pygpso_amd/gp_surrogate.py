@@ -30,6 +30,7 @@ import scipy.optimize
 from scipy.special import erfcinv
 
 from .kernels import KERNEL_CLASSES, Adam, Constant, Gaussian, Kernel, Matern52, MeanFunction, Scipy, StudentT, Zero, _LbfgsbSearch
+from .acquisition import host_value_and_grad, resolve as resolve_acquisition, score_unit_spec
 from .model import HipGPR, _standard_normals
 from .sgpr import HipSGPR
 from .svgp import HipSVGP
@@ -239,7 +240,7 @@ class GPListOfPoints(list):
             self._dirty = True
         return n
 
-    def update_scores(self, indices, mean, var, varsigma):
+    def update_scores(self, indices, mean, var, varsigma, score=None):
         """New (mean, var, ucb) for the points at ``indices``, coordinates and labels kept -- what re-appending a point with
         the SAME coordinates does (it overwrites its own entry), without the look-up.  Only valid while no two stored points
         are duplicates of each other (``_unique``); returns False otherwise and changes nothing."""
@@ -249,7 +250,8 @@ class GPListOfPoints(list):
         for i, m, v in zip(indices, mean, var):
             p = self[i]
             m, v = float(m), float(v)
-            setitem(self, i, GPPoint(p.normed_coord, m, v, float(m + varsigma * v), p.label))  # (coordinates unchanged: the index stays valid)
+            u = float(m + varsigma * v) if score is None else score(m, v)  # (score: the surrogate's rule when it is not the reference's)
+            setitem(self, i, GPPoint(p.normed_coord, m, v, u, p.label))  # (coordinates unchanged: the index stays valid)
         return True
 
     def find_index_by_coords(self, coords):
@@ -358,7 +360,8 @@ class GPSurrogate:
         raise NotImplementedError
 
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01), points=None,
-                 gpflow_model=None, dtype="float64", device=0, engine_options=None, devices=None):
+                 gpflow_model=None, dtype="float64", device=0, engine_options=None, devices=None,
+                 gp_acquisition="ucb_var"):
         """
         :param gp_kernel: kernel spec (``pygpso_amd.kernels.Matern52(...)`` etc.)
         :param gp_meanf: mean-function spec (``Constant(c)``) or None
@@ -375,9 +378,14 @@ class GPSurrogate:
             call is sharded over all of them (RCCL behind the C-ABI, ``HipGPEngineGroup``); results are
             bit-identical to a single device's
         :param engine_options: extra ``HipGPEngine`` keyword arguments (predict_math, generation, ...)
+        :param gp_acquisition: what the loop ranks leaves by: "ucb_var" (the reference's mean + varsigma * VAR, the
+            default) or "ucb_std" (GP-UCB, mean + varsigma * sqrt(VAR)).  Only these are in score units --
+            ``GPSOptimiser._tree_select`` compares a leaf's value with evaluated scores --; "ei", "logei" and "pi" raise
+            ValueError here and are served by ``gp_eval_best_acq`` / ``gp_acq_values`` / ``polish``
         """
         self.gpflow_model = gpflow_model
         self.gp_varsigma = float(varsigma)
+        self.gp_acquisition = score_unit_spec(gp_acquisition, self.gp_varsigma).name
         assert isinstance(gp_kernel, Kernel)
         self.gp_kernel = gp_kernel
         assert gp_meanf is None or isinstance(gp_meanf, MeanFunction)
@@ -464,6 +472,19 @@ class GPSurrogate:
                 self.points.set_noise_at(i, v)
 
     # -- predict / UCB ------------------------------------------------------------------------------
+    def _acquisition_record(self):
+        """What ``save`` adds to the surrogate's record: nothing for the default rule (its files stay what they were)."""
+        return {} if self.gp_acquisition == "ucb_var" else {"gp_acquisition": self.gp_acquisition}
+
+    def _loop_acquisition(self):
+        return resolve_acquisition(self.gp_acquisition, varsigma=self.gp_varsigma)
+
+    def _score_ucb(self, m, v):
+        """The stored ``score_ucb`` of a point with predictive mean ``m`` and variance ``v`` (Python floats)."""
+        if self.gp_acquisition == "ucb_var":
+            return float(m + self.gp_varsigma * v)
+        return float(self._loop_acquisition().host_value(m, v))
+
     def _require_model(self):
         assert isinstance(self.gpflow_model, HipGPR), "GP model not trained yet"
 
@@ -473,8 +494,7 @@ class GPSurrogate:
         mean, var = self.gpflow_model.predict_y(normed_coords)
         for i in range(normed_coords.shape[0]):
             m, v = float(mean[i, 0]), float(var[i, 0])
-            self.points.append(GPPoint(normed_coords[i, :], m, v, float(m + self.gp_varsigma * v),
-                                       PointLabels.gp_based))
+            self.points.append(GPPoint(normed_coords[i, :], m, v, self._score_ucb(m, v), PointLabels.gp_based))
 
     def gp_predict_grad(self, normed_coords):
         """predict_y and its gradients in normed coordinates at the rows of ``normed_coords``: (mean [M], var [M],
@@ -554,8 +574,8 @@ class GPSurrogate:
         ``maxfun``, ``gtol``, ``ftol``, ``maxls`` as SciPy's L-BFGS-B names them; ``ftol`` defaults to ten machine epsilons
         here, so a search ends on its projected gradient (``gtol``, 1e-5).  Changes neither the point store nor
         anything saved.  Returns (coords [R, D], mean [R], var [R], value [R], results)."""
-        if objective not in ("ucb", "mean"):
-            raise ValueError(f"objective={objective!r}: 'ucb' or 'mean'")
+        if objective not in ("ucb", "mean", "ucb_std", "ei", "logei"):
+            raise ValueError(f"objective={objective!r}: 'ucb', 'mean', 'ucb_std', 'ei' or 'logei'")
         starts = np.array(normed_coords, dtype=np.float64, ndmin=2)
         r, d = starts.shape
         if box is None:
@@ -566,8 +586,11 @@ class GPSurrogate:
                 raise ValueError(f"box has shape {box.shape}, expected {(r, d, 2)}")
             lower, upper = box[:, :, 0], box[:, :, 1]
         weight = self.gp_varsigma if objective == "ucb" else 0.0
+        mapped = objective in ("ucb_std", "ei", "logei")  # (the chain rule on the host: acq_value_and_grad)
 
         def value_and_grad(x):
+            if mapped:
+                return self.acq_value_and_grad(x, objective)[2:]
             mean, var, dmean, dvar = self.gp_predict_grad(x)
             return mean + weight * var, dmean + weight * dvar
 
@@ -576,22 +599,58 @@ class GPSurrogate:
         opts.update(options or {})
         results = polish_lockstep(value_and_grad, starts, lower, upper, opts)
         coords = np.stack([np.asarray(r.x, dtype=np.float64) for r in results])
+        if mapped:
+            mean, var, value, _ = self.acq_value_and_grad(coords, objective)
+            return coords, mean, var, value, results
         mean, var, _, _ = self.gp_predict_grad(coords)
         return coords, mean, var, mean + weight * var, results
+
+    def acq_value_and_grad(self, normed_coords, objective, incumbent=None, xi=0.0):
+        """(mean [M], var [M], value [M], dvalue [M, D]) of "ucb_std", "ei" or "logei" at the rows of ``normed_coords``: one
+        ``gp_predict_grad`` call and the chain rule on the host, the quotients of log-EI in their tail-stable form
+        (``pygpso_amd.acquisition.h_parts``).  The incumbent defaults to the largest training target."""
+        mean, var, dmean, dvar = self.gp_predict_grad(normed_coords)
+        if incumbent is None and objective != "ucb_std":
+            incumbent = float(np.max(self.current_training_data[1]))
+        value, grad = host_value_and_grad(objective, mean, var, dmean, dvar, varsigma=self.gp_varsigma,
+                                          incumbent=incumbent, xi=xi)
+        return mean, var, value, grad
 
     def gp_eval_best_ucb(self, normed_coords):
         """(mean, var, ucb) of the row with the highest ucb = mean + varsigma * var; stores nothing."""
         self._require_model()
-        _, mean, var, ucb = self.gpflow_model.best_ucb(normed_coords, self.gp_varsigma)
+        if self.gp_acquisition == "ucb_var":
+            _, mean, var, ucb = self.gpflow_model.best_ucb(normed_coords, self.gp_varsigma)
+        else:
+            _, mean, var, ucb = self.gpflow_model.best_acq(normed_coords, self._loop_acquisition())
         return float(mean[0]), float(var[0]), float(ucb[0])
+
+    def gp_eval_best_acq(self, normed_coords, acquisition, incumbent=None, seg_off=None):
+        """Per segment of ``seg_off`` (None: one) the row of ``normed_coords`` with the highest value of ``acquisition`` --
+        a name ("ucb_var", "ucb_std", "ei", "logei", "pi") or a spec of ``pygpso_amd.acquisition``: (idx, mean, var, value)
+        arrays, idx relative to the segment start, the first on ties.  EI, log-EI and PI improve on ``incumbent``: by
+        default the largest training target, in the units ``_gp_train`` saw.  Stores nothing."""
+        self._require_model()
+        acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        return self.gpflow_model.best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, seg_off, incumbent)
+
+    def gp_acq_values(self, normed_coords, acquisition, incumbent=None):
+        """(mean [M], var [M], value [M]) of every row of ``normed_coords`` under ``acquisition`` (as
+        ``gp_eval_best_acq``); stores nothing."""
+        self._require_model()
+        acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        return self.gpflow_model.acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, incumbent)
 
     def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
         """MI355X path of ``gp_eval_best_ucb(leaf.grow(depth))`` for several leaves at once: the
         ternary sub-tree centres are generated on the device (bit-identical to ``LeafNode.grow``)
         and never cross PCIe.  ``leaf_bounds``: [nleaf, D, 2].  Returns a list of (mean, var, ucb)."""
         self._require_model()
-        _, mean, var, ucb = self.gpflow_model.best_ucb_grow(np.asarray(leaf_bounds, dtype=np.float64),
-                                                             depth, self.gp_varsigma)
+        bounds = np.asarray(leaf_bounds, dtype=np.float64)
+        if self.gp_acquisition == "ucb_var":
+            _, mean, var, ucb = self.gpflow_model.best_ucb_grow(bounds, depth, self.gp_varsigma)
+        else:
+            _, mean, var, ucb = self.gpflow_model.best_acq_grow(bounds, depth, self._loop_acquisition())
         return [(float(m), float(v), float(u)) for m, v, u in zip(mean, var, ucb)]
 
     def gp_update(self):
@@ -612,7 +671,8 @@ class GPSurrogate:
             coords = np.array([self.points[i].normed_coord for i in idx])
             if getattr(self.points, "_unique", False):
                 mean, var = self.gpflow_model.predict_y(coords)
-                if self.points.update_scores(idx, np.asarray(mean)[:, 0], np.asarray(var)[:, 0], self.gp_varsigma):
+                score = None if self.gp_acquisition == "ucb_var" else self._score_ucb
+                if self.points.update_scores(idx, np.asarray(mean)[:, 0], np.asarray(var)[:, 0], self.gp_varsigma, score):
                     return
             self.gp_predict(coords)
 
@@ -629,7 +689,7 @@ class GPRSurrogate(GPSurrogate):
 
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01),
                  gauss_likelihood_sigma=1.0e-3, points=None, gpflow_model=None, dtype="float64",
-                 device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml"):
+                 device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml", gp_acquisition="ucb_var"):
         """
         :param objective: what ``gp_update`` minimises over the hyper-parameters (NOT in the reference, which has the
             first only): "nlml" (default), the negative log marginal likelihood, or "loo", the leave-one-out log
@@ -647,7 +707,7 @@ class GPRSurrogate(GPSurrogate):
             surprising under theta and THIS update re-optimises instead of waiting for the c-th.  None: no guard
         """
         super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf, optimiser=optimiser,
-                         varsigma=varsigma, points=points, gpflow_model=gpflow_model, dtype=dtype,
+                         varsigma=varsigma, gp_acquisition=gp_acquisition, points=points, gpflow_model=gpflow_model, dtype=dtype,
                          device=device, engine_options=engine_options, devices=devices)
         if objective not in ("nlml", "loo"):
             raise ValueError(f"objective must be 'nlml' or 'loo', not {objective!r}")
@@ -792,7 +852,7 @@ class GPRSurrogate(GPSurrogate):
             "gpr_kernel_shape": list(np.shape(model.kernel.lengthscales)),
             "gpr_meanf": type(model.mean_function).__name__,
             "gpr_meanf_shape": [],
-            "gp_varsigma": self.gp_varsigma,
+            "gp_varsigma": self.gp_varsigma, **self._acquisition_record(),
             "gp_likelihood": self.gp_lik_sigma,
             "optimiser": self._optimiser_record(),
             "dtype": self.dtype,
@@ -827,7 +887,7 @@ class GPRSurrogate(GPSurrogate):
                        noise_diag=points.noise_vector(PointLabels.evaluated) if has_noise else None,
                        objective=info.get("objective", "nlml"))
         return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=cls._optimiser_from_record(info["optimiser"]),
-                   gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
+                   gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"], gp_acquisition=info.get("gp_acquisition", "ucb_var"),
                    points=points, gpflow_model=model, dtype=info.get("dtype", "float64"), device=device,
                    devices=devices, refit_every=info.get("refit_every", 1), refit_guard=info.get("refit_guard", 2.0),
                    objective=info.get("objective", "nlml"))
@@ -845,7 +905,7 @@ class SGPRSurrogate(GPSurrogate):
 
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01), gauss_likelihood_sigma=1.0e-3,
                  num_inducing=256, inducing="greedy", points=None, gpflow_model=None, dtype="float64", device=0,
-                 engine_options=None, train_inducing=False):
+                 engine_options=None, train_inducing=False, gp_acquisition="ucb_var"):
         """
         :param gauss_likelihood_sigma: initial noise VARIANCE of the Gaussian likelihood (as ``GPRSurrogate``)
         :param num_inducing: M (ignored when ``inducing`` is an array)
@@ -866,7 +926,7 @@ class SGPRSurrogate(GPSurrogate):
             if inducing.ndim != 2 or inducing.shape[0] < 1 or not np.all(np.isfinite(inducing)):
                 raise ValueError("inducing must be a finite [M, D] array with M >= 1")
             num_inducing = inducing.shape[0]
-        super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf, optimiser=optimiser, varsigma=varsigma, points=points,
+        super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf, optimiser=optimiser, varsigma=varsigma, gp_acquisition=gp_acquisition, points=points,
                          gpflow_model=gpflow_model, dtype=dtype, device=device, engine_options=engine_options)
         self.gp_lik_sigma = gauss_likelihood_sigma
         self.num_inducing = int(num_inducing)
@@ -907,7 +967,7 @@ class SGPRSurrogate(GPSurrogate):
             "gpr_kernel_shape": list(np.shape(model.kernel.lengthscales)),
             "gpr_meanf": type(model.mean_function).__name__,
             "gpr_meanf_shape": [],
-            "gp_varsigma": self.gp_varsigma,
+            "gp_varsigma": self.gp_varsigma, **self._acquisition_record(),
             "gp_likelihood": self.gp_lik_sigma,
             "optimiser": VGPSurrogate._serialise_optimiser(self),
             "dtype": self.dtype,
@@ -946,7 +1006,7 @@ class SGPRSurrogate(GPSurrogate):
         # the Z the saved posterior was built on (the next update chooses again, or -- trained -- continues from it)
         model.set_inducing(z)
         return cls(gp_kernel=kernel, gp_meanf=meanf, optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]),
-                   gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"],
+                   gauss_likelihood_sigma=info["gp_likelihood"], varsigma=info["gp_varsigma"], gp_acquisition=info.get("gp_acquisition", "ucb_var"),
                    num_inducing=info["num_inducing"], inducing=inducing, points=points, gpflow_model=model, dtype=dtype,
                    device=device, train_inducing=train_z)
 
@@ -971,7 +1031,7 @@ class VGPSurrogate(GPSurrogate):
 
     def __init__(self, gp_kernel, gp_meanf=None, likelihood=None, optimiser=None, varsigma=erfcinv(0.01), points=None,
                  gpflow_model=None, natgrad_learning_rate=1.0, train_iterations=VGP_TRAIN_ITERATIONS, dtype="float64",
-                 device=0, engine_options=None):
+                 device=0, engine_options=None, gp_acquisition="ucb_var"):
         """
         :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``; any other
             likelihood raises NotImplementedError
@@ -989,7 +1049,7 @@ class VGPSurrogate(GPSurrogate):
         if dtype not in ("float64", "mixed"):
             raise ValueError(f"VGP trains in float64: dtype must be 'float64' or 'mixed', not {dtype!r}")
         super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf,
-                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma,
+                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma, gp_acquisition=gp_acquisition,
                          points=points, gpflow_model=gpflow_model, dtype=dtype, device=device,
                          engine_options=engine_options)
         self.likelihood = likelihood
@@ -1044,7 +1104,7 @@ class VGPSurrogate(GPSurrogate):
             "vgp_meanf": type(model.mean_function).__name__,
             "vgp_meanf_shape": [1] if isinstance(model.mean_function, Constant) else [],  # (the shape of c)
             "vgp_likelihood": self.likelihood.name,
-            "gp_varsigma": self.gp_varsigma,
+            "gp_varsigma": self.gp_varsigma, **self._acquisition_record(),
             "optimiser": self._serialise_optimiser(),
             "vgp_iters": self.train_iters,
             "vgp_natgrad_lr": self.natgrad_gamma,
@@ -1084,7 +1144,7 @@ class VGPSurrogate(GPSurrogate):
         model = HipVGP(data=(x, y), kernel=kernel, mean_function=meanf, likelihood=likelihood, dtype=dtype,
                        device=device, q_mu=np.array(params[".q_mu"]), q_sqrt=np.array(params[".q_sqrt"]))
         return cls(gp_kernel=kernel, gp_meanf=meanf, likelihood=likelihood,
-                   optimiser=cls._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
+                   optimiser=cls._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"], gp_acquisition=info.get("gp_acquisition", "ucb_var"),
                    points=points, gpflow_model=model, natgrad_learning_rate=info["vgp_natgrad_lr"],
                    train_iterations=info["vgp_iters"], dtype=dtype, device=device)
 
@@ -1110,7 +1170,7 @@ class SVGPSurrogate(GPSurrogate):
     def __init__(self, gp_kernel, gp_meanf=None, likelihood=None, num_inducing=256, inducing="greedy",
                  natgrad_learning_rate=1.0, train_iterations=SVGP_TRAIN_ITERATIONS, optimiser=None,
                  varsigma=erfcinv(0.01), points=None, gpflow_model=None, dtype="float64", device=0, engine_options=None,
-                 train_inducing=False):
+                 train_inducing=False, gp_acquisition="ucb_var"):
         """
         :param likelihood: ``Gaussian(variance)`` (default ``Gaussian(1e-3)``) or ``StudentT(scale, df)``; any other
             likelihood raises NotImplementedError
@@ -1144,7 +1204,7 @@ class SVGPSurrogate(GPSurrogate):
                 raise ValueError("inducing must be a finite [M, D] array with M >= 1")
             num_inducing = inducing.shape[0]
         super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf,
-                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma,
+                         optimiser=optimiser if optimiser is not None else Adam(0.01), varsigma=varsigma, gp_acquisition=gp_acquisition,
                          points=points, gpflow_model=gpflow_model, dtype=dtype, device=device,
                          engine_options=engine_options)
         self.likelihood = likelihood
@@ -1187,7 +1247,7 @@ class SVGPSurrogate(GPSurrogate):
             "svgp_kernel_shape": list(np.shape(model.kernel.lengthscales)),
             "svgp_meanf": type(model.mean_function).__name__,
             "svgp_likelihood": self.likelihood.name,
-            "gp_varsigma": self.gp_varsigma,
+            "gp_varsigma": self.gp_varsigma, **self._acquisition_record(),
             "optimiser": VGPSurrogate._serialise_optimiser(self),
             "svgp_iters": self.train_iters,
             "svgp_natgrad_lr": self.natgrad_gamma,
@@ -1234,5 +1294,5 @@ class SVGPSurrogate(GPSurrogate):
         model.set_q(np.array(params[".q_mu"]), np.array(params[".q_sqrt"]))
         return cls(gp_kernel=kernel, gp_meanf=meanf, likelihood=likelihood, num_inducing=info["num_inducing"],
                    inducing=inducing, natgrad_learning_rate=info["svgp_natgrad_lr"], train_iterations=info["svgp_iters"],
-                   optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"],
+                   optimiser=VGPSurrogate._deserialise_optimiser(info["optimiser"]), varsigma=info["gp_varsigma"], gp_acquisition=info.get("gp_acquisition", "ucb_var"),
                    points=points, gpflow_model=model, dtype=dtype, device=device, train_inducing=train_z)

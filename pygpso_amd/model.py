@@ -491,6 +491,26 @@ class HipGPR:
     def best_ucb_grow(self, bounds, depth, varsigma):
         return self._predicting(lambda: self.engine.best_ucb_grow(bounds, depth, varsigma))
 
+    def _incumbent(self, acq, incumbent):
+        """EI / log-EI / PI improve on the largest training target unless told otherwise."""
+        if incumbent is None and acq.needs_incumbent and acq.incumbent is None:
+            return float(np.max(self._data[1]))
+        return incumbent
+
+    def best_acq(self, Xnew, acq, seg_off=None, incumbent=None):
+        """``best_ucb`` ranked by an acquisition spec (``pygpso_amd.acquisition``): (idx, mean, var, value) per segment."""
+        inc = self._incumbent(acq, incumbent)
+        return self._predicting(lambda: self.engine.best_acq(Xnew, acq, seg_off, incumbent=inc))
+
+    def best_acq_grow(self, bounds, depth, acq, incumbent=None):
+        inc = self._incumbent(acq, incumbent)
+        return self._predicting(lambda: self.engine.best_acq_grow(bounds, depth, acq, incumbent=inc))
+
+    def acq_values(self, Xnew, acq, incumbent=None):
+        """(mean [M], var [M], value [M]): ``predict_y`` with the acquisition column, flat float64 arrays."""
+        inc = self._incumbent(acq, incumbent)
+        return self._predicting(lambda: self.engine.acq_values(np.asarray(Xnew), acq, incumbent=inc))
+
     # -- reporting ----------------------------------------------------------------------------
     def parameter_dict(self):
         return {
