@@ -149,6 +149,14 @@ typedef struct gpso_ctx gpso_ctx;
                                    /* Default 256 MB (268435456): the best of 0 / 64 / 128 / 256 MB at C3 -- +3.6 / +3.7 % predictions/s */
                                    /* on two boxes, level with off on a third; C4 share +2.4 % | level (profiles/park_reload_ab_*.txt). */
                                    /* The buffer (201 MB at C3) is held until the context is destroyed.                                 */
+#define GPSO_OPT_SCREEN 15         /* gpso_best_ucb / _begin on float leaves on the device, one segment, the default float kernels (fp16 */
+                                   /* split, fp16 contraction, fused step), a finite varsigma >= 0.  1 (default): calls of more than    */
+                                   /* 16384 rows are SCREENED -- every leaf's mean is computed alone (the bits the tile kernel gives    */
+                                   /* it), a leaf whose ucb at zero variance share lies below that of the largest mean is dropped, and  */
+                                   /* the tile kernel scores the survivors only; the call's last kernel accepts the record or asks for  */
+                                   /* the general sequence, which the call then runs.  After one refusal the posterior is not screened  */
+                                   /* again until it changes.  0: today's launches exactly.  2: any batch size (tests).  Per context.   */
+                                   /* Same record bits whatever the value; gpso_last_count(ctx, 7) and (ctx, 8) say what happened.      */
 /* floating-point options (gpso_set_option_f64): tolerances of the self-test */
 #define GPSO_OPTF_TOL_VAR 100  /* max |d var| at the training inputs, relative to the kernel variance (default 1e-4; GPSO_F32: 1e-3) */
 #define GPSO_OPTF_TOL_MEAN 101 /* max |d mean| at the training inputs, relative to max |y - c|   (default 1e-4; GPSO_F32: 1e-3) */
@@ -629,6 +637,22 @@ int gpso_best_ucb_begin(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem,
 int gpso_best_ucb_grow_begin(gpso_ctx* ctx, const double* bounds, int nseg, int depth, double varsigma);
 int gpso_best_ucb_end(gpso_ctx* ctx, int ticket, int64_t* idx, double* mean, double* var, double* ucb);
 
+/* Diagnostic: the mean pass and the screen of a screened call (GPSO_OPT_SCREEN) alone, whatever the option and the batch
+ * size say.  Per leaf (host, m each, nullable): my -- the mean, bit for bit gpso_predict's --, ub -- what the leaf's ucb cannot
+ * exceed: my + varsigma * (variance + noise) in the finalize stage's roundings --, flag -- 1.0: the leaf survives.
+ * info (3 doubles, nullable): the survivors' count, the threshold T', and how many survivors a call has room for.
+ * GPSO_E_STATE where no call on this context, batch and varsigma could be screened. */
+int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my,
+                      double* ub, double* flag, double* info);
+/* The screen's arithmetic on the host (csrc/screen.hpp, the header the device code includes; no context, no GPU):
+ * ucb[i] = the finalize stage's ucb of a leaf with mean my[i] and variance share v[i] (NULL: zeros), ub[i] = its bound;
+ * the threshold from the largest finite mean; the survive test; the acceptance test of the survivors' winner. */
+int gpso_screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, int64_t n,
+                          double* ucb /* nullable */, double* ub /* nullable */);
+double gpso_screen_threshold_host(double max_my, double noise, double varsigma);
+int gpso_screen_survives_host(double my, double ub, double threshold);
+int gpso_screen_accepts_host(double u_star, double threshold, int64_t count, int64_t cap);
+
 /* ---- acquisition functions (no counterpart in the reference: it ranks by mean + varsigma * VAR only) ----------------
  *
  * What a leaf is ranked by, as a map of the (mean, var) the predict path produces -- maximisation throughout:
@@ -835,7 +859,9 @@ int gpso_precision_info(gpso_ctx* ctx, double* out);
 /* last-call device timings in milliseconds measured with HIP events on the context's stream:
  * what = 0: dominant predict kernel (leaf tiles) of the last predict/best_ucb call,
  *        1: whole last predict/best_ucb call, 2: whole last gpso_fit_eval / gpso_append call,
- *        3: the collective of the last gpso_best_ucb*_sharded call (ncclAllGather of the winners + the fold kernel). */
+ *        3: the collective of the last gpso_best_ucb*_sharded call (ncclAllGather of the winners + the fold kernel).
+ * After a SCREENED call (GPSO_OPT_SCREEN) what = 0 spans from the start of the mean pass to the end of the survivors' tile
+ * kernel: a figure that prices the batch's algorithmic flops against it prices work the call no longer does. */
 double gpso_last_ms(gpso_ctx* ctx, int what);
 
 /* leaf counts of the last predict / best_ucb / best_ucb_grow call: what = 0: rows the predict kernels
@@ -848,7 +874,11 @@ double gpso_last_ms(gpso_ctx* ctx, int what);
  * what = 3: how many workgroups shared a leaf tile's row blocks in the last launch of a split predict kernel (GPSO_OPT_ROW_LOOP;
  * per context: the last launch THIS context made; for tests and tools).
  * what = 5, 6: k-steps per leaf tile that the last launch of a split predict kernel parked (5) and reloaded instead of generating
- * them (6) under GPSO_OPT_PARK_BYTES; 0 where it parked nothing.  Per context, like what = 3.
+ * them (6) under GPSO_OPT_PARK_BYTES; 0 where it parked nothing.  Per context, like what = 3.  A screened call reports its
+ * batch-sized launch -- the mean pass -- under 3, 5 and 6, not the survivors' launch.
+ * what = 7, 8: the last gpso_best_ucb / gpso_best_ucb_end call under GPSO_OPT_SCREEN: how many leaves survived the screen (7; 0
+ * where the call was not screened), and 8: 0 not screened, 1 screened and accepted, 2 screened, refused and run again by the
+ * general sequence.
  * what = 4: bytes of device memory the buffers of ALL contexts of this process hold now (process-wide, whichever ctx asks;
  * back where it stood once a context is destroyed; for tests and tools). */
 #define GPSO_FITMATH_NONE 0

@@ -41,6 +41,8 @@ OPT_FUSED_PREP = 11
 OPT_FIT_OVERLAP = 12
 OPT_ROW_LOOP = 13
 OPT_PARK_BYTES = 14
+OPT_SCREEN = 15
+SCREEN_NONE, SCREEN_ACCEPTED, SCREEN_REFUSED = 0, 1, 2  # gpso_last_count(ctx, 8)
 CONTRACTION_AUTO, CONTRACTION_F32, CONTRACTION_F16 = 0, 1, 2
 SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FUSED32 = 0, 1, 2, 3
 OPTF_TOL_VAR, OPTF_TOL_MEAN = 100, 101
@@ -159,6 +161,13 @@ SIGNATURES = {
     "gpso_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int]),
     "gpso_acq_eval_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, C.c_double, C.c_int64, _c_double_p]),
+    "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
+                                    _c_double_p, _c_double_p]),
+    "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,
+                                        _c_double_p]),
+    "gpso_screen_threshold_host": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+    "gpso_screen_survives_host": (C.c_int, [C.c_double, C.c_double, C.c_double]),
+    "gpso_screen_accepts_host": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.c_int64]),
     "gpso_grow_rows": (C.c_int64, [C.c_int]),
     "gpso_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p]),
     "gpso_best_ucb_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_double,

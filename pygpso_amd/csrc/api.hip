@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "devbuf.hpp"
 #include "kernels.hpp"
+#include "screen.hpp"
 #include "rccl_api.hpp"
 #include "resident.hpp"
 #include "theta.hpp"
@@ -67,6 +68,10 @@ constexpr int kMaxD = 48;                      // padded input dimension limit (
 constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass of the tile kernel
 // GPSO_OPT_PARK_BYTES as a context is created: 256 MB, the best median of the sweeps 0 | 64 | 128 | 256 MB at C3
 // (profiles/park_reload_ab_sweep_c3.txt, park_reload_ab_pairs.txt; -DGPSO_PARK_BYTES_DEFAULT=... builds the other arms)
+// GPSO_OPT_SCREEN as a context is created (-DGPSO_SCREEN_DEFAULT=0 builds the unscreened arm of an A/B through bench.py)
+#ifndef GPSO_SCREEN_DEFAULT
+#define GPSO_SCREEN_DEFAULT 1
+#endif
 #ifndef GPSO_PARK_BYTES_DEFAULT
 #define GPSO_PARK_BYTES_DEFAULT (256 << 20)
 #endif
@@ -115,6 +120,8 @@ struct Engine {
   virtual int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
                              const AcqSpec& acq, const double* bounds, int depth) = 0;
   virtual int best_ucb_end(int ticket, int64_t* idx, double* mean, double* var, double* ucb) = 0;
+  virtual int screen_probe(const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,
+                           double* flag, double* info) = 0;
   virtual int grow(const double* bounds, int nseg, int d, int depth, double* out) = 0;
   virtual int best_ucb_grow(const double* bounds, int nseg, int depth, const AcqSpec& acq,
                             int64_t* idx, double* mean, double* var, double* ucb) = 0;
@@ -221,7 +228,7 @@ struct gpso_ctx {
   int rank = 0, world = 1;
   // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit; [3] workgroups per
   // leaf tile of this context's last split-kernel launch
-  int64_t last_count[7] = {0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
+  int64_t last_count[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
   int cu_count = 256;  // compute units of `device` (gpso_create): sizes the split predict kernels' and the bf16 GEMMs' grids
   std::string err;
   Engine* eng = nullptr;
@@ -242,6 +249,14 @@ struct gpso_ctx {
   hipEvent_t slot_ev[kSlots] = {};
   int slot_nseg[kSlots] = {0, 0};  // > 0: the slot holds a call that has not been ended
   int slot_mode[kSlots] = {0, 0};
+  // a SCREENED call in the slot: what gpso_best_ucb_end needs to run the general sequence should the call be refused
+  struct SlotScreen {
+    bool on = false;
+    const void* xs = nullptr;
+    int xs_dtype = 0;
+    int64_t m = 0;
+    gpso::AcqSpec acq;
+  } slot_screen[kSlots];
   int slot_next = 0;
   int slots_busy() const { return (slot_nseg[0] > 0) + (slot_nseg[1] > 0); }
 
@@ -480,6 +495,13 @@ struct EngineT : Engine {
   // predict workspace
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
+  // screened best-UCB calls (screen.hip): every leaf's mean, the blocks' maxima, the survivors' raw rows, the control words
+  // (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
+  DevBuf screen_my, screen_bmax, screen_rows, screen_ctl, screen_cols;
+  int screen_mode = GPSO_SCREEN_DEFAULT;  // GPSO_OPT_SCREEN
+  bool screen_pending = false;  // the call in flight is a screened one: finish_best looks at its verdict
+  bool screen_rerun = false;    // the call being enqueued repeats a refused screened call: its counters stay
+  bool tile_span_open = false;  // a screened call's mean pass has recorded the start of the tile kernel's event pair
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
   DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
@@ -591,6 +613,10 @@ struct EngineT : Engine {
         if (value < 0) return ctx->fail(GPSO_E_ARG, "park bytes: 0 (off) or a budget in bytes");
         park_bytes = value;
         park_refused = 0;
+        return GPSO_OK;
+      case GPSO_OPT_SCREEN:
+        if (value < 0 || value > 2) return ctx->fail(GPSO_E_ARG, "screen: 0 (off), 1 (large calls) or 2 (every call it applies to)");
+        screen_mode = value;
         return GPSO_OK;
       case GPSO_OPT_FIT_OVERLAP:
         if (value < 0) return ctx->fail(GPSO_E_ARG, "fit overlap must be >= 0");
@@ -2495,6 +2521,10 @@ struct EngineT : Engine {
     if ((rc = ensure(pmean, (size_t)nbi * cpad * 8))) return rc;
     hipStream_t s = st();
     ctx->tile_pairs = 0;
+    // (the survivors of a screened call: the pair's first event stands in front of the mean pass, and the counters of the
+    // split launch keep describing the batch-sized launch of the mean pass)
+    const bool span_open = tile_span_open;
+    const int64_t keep_counts[3] = {ctx->last_count[3], ctx->last_count[5], ctx->last_count[6]};
     const size_t in_elem = (xs_dtype == GPSO_F64) ? 8 : 4;
     const TG* xsp = nullptr;
     const TG* xnr = nullptr;
@@ -2546,7 +2576,7 @@ struct EngineT : Engine {
         HIPCHECK(hipEventCreate(&e));
         ctx->tile_ev.push_back(e);
       }
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs], s));
+      if (ctx->timing && !span_open) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs], s));
       if (use_bf16) {
         if constexpr (kFloatPredict) {
           SplitLeafLaunch<TG> a;
@@ -2560,6 +2590,7 @@ struct EngineT : Engine {
           a.splits_out = &ctx->last_count[3];
           a.park_bytes = park_bytes; a.park_scratch = &EngineT::park_cb; a.park_owner = this; a.park_out = &ctx->last_count[5];
           rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+          if (span_open) ctx->last_count[3] = keep_counts[0], ctx->last_count[5] = keep_counts[1], ctx->last_count[6] = keep_counts[2];
         }
       } else {
         rc = launch_leaf_tiles<TP, TG>(s, as<TP>(linv_p), xsp, xnr, as<TP>(alpha), as<TG>(leaves_s),
@@ -3346,12 +3377,137 @@ struct EngineT : Engine {
     return try_one_launch_t<double>(one, total, nseg, acq);
   }
 
+  // ---- screened calls (screen.hpp, screen.hip) ----------------------------------------------------------
+  // The result of a best-UCB call is one record, and the tile kernel spends N^2 flops per leaf on the variance of every leaf.
+  // A leaf's mean costs N D.  So: the mean pass (every leaf's mean, the tile kernel's bits), the screen (a leaf survives unless
+  // its ucb at zero variance share lies below T' = the largest mean's), the tile kernel on the survivors' compact list, the
+  // keyed arg-max over it -- whose last kernel accepts the record or asks for the general sequence (finish_best returns 1).
+  // Where: one segment, the reference's rule with a finite varsigma >= 0, float leaves on the device in one chunk, the default
+  // float kernels (fp16 split, fp16 contraction, fused step), m above the small calls' limit (GPSO_OPT_SCREEN = 2: any m),
+  // and no refusal on this posterior so far.  The survivors' launch has room for as many leaf tiles as fill one round of the
+  // chip: CUs / row blocks (at least one) -- more survivors than that is a refusal too.
+  // probe: gpso_screen_probe asks -- whatever the option, the batch size and earlier refusals say
+  bool screen_applies(int xs_dtype, int64_t m, int nseg, const AcqSpec& acq, bool probe = false) const {
+    if (!kFloatPredict || nseg != 1 || m <= 0 || m > kLeafChunk) return false;
+    if (!probe && (screen_mode == 0 || res.screen_refused || (screen_mode == 1 && m <= kSmallBestMaxRows))) return false;
+    if (acq.kind != GPSO_ACQ_UCB_VAR || acq.latent != 0 || !std::isfinite(acq.varsigma) || acq.varsigma < 0.0) return false;
+    if (xs_dtype != GPSO_F32 || !fuse_prep || gen_double() || split_variant != GPSO_SPLIT_KERNEL_AUTO) return false;
+    if (!(bf16_usable() && res.linv_b == Copy::Valid && bf16_fits(false))) return false;
+    return f16_split() && c16_in_use(false);
+  }
+  int64_t screen_cap_rows(int64_t mpad) const {
+    const int nbi = (int)(npad / 256);
+    return std::min<int64_t>(mpad, (int64_t)std::max(1, ctx->cu_count / nbi) * kLeafPad);
+  }
+  // the mean pass and the screen of a batch of float leaves on the device; probe: also every leaf's ub and flag -> screen_cols
+  int enqueue_screen(const void* dev, int64_t m, const AcqSpec& acq, bool probe) {
+    if constexpr (kFloatPredict) {
+      int rc;
+      if ((rc = ensure_generation_inputs())) return rc;
+      const int nbi = (int)(npad / 256);
+      const int64_t mpad = (m + kLeafPad - 1) / kLeafPad * kLeafPad;
+      const int64_t cap = screen_cap_rows(mpad);
+      if ((rc = ensure(pmean, (size_t)nbi * mpad * 8))) return rc;
+      if ((rc = ensure(pvar, (size_t)nbi * mpad * 8))) return rc;
+      if ((rc = ensure(screen_my, (size_t)mpad * 8))) return rc;
+      if ((rc = ensure(screen_bmax, (size_t)(mpad / 256) * 8))) return rc;
+      if ((rc = ensure(screen_rows, (size_t)cap * d * 4))) return rc;
+      if ((rc = ensure(grow_key, (size_t)cap * 8))) return rc;
+      if ((rc = ensure_keep(screen_ctl, 64))) return rc;
+      if (probe && (rc = ensure(screen_cols, (size_t)2 * m * 8))) return rc;
+      hipStream_t s = st();
+      LeafMeanLaunch a;
+      a.xs_h16 = xs_h16.p; a.alpha = as<float>(alpha); a.c16_scale = as<float>(c16_scal);
+      a.raw.x = static_cast<const float*>(dev); a.raw.ls = ls_dev(); a.raw.m = m; a.raw.d = d;
+      a.part_mean = as<double>(pmean);
+      a.npad = npad; a.mpad = mpad; a.n_rows = n; a.dp4 = dp / 4;
+      a.row_loop = row_loop; a.cu_count = ctx->cu_count; a.splits_out = &ctx->last_count[3];
+      if ((rc = launch_leaf_mean(s, kp, a))) return launch_status();
+      ScreenLaunch b;
+      b.part_mean = as<double>(pmean); b.nbi = nbi; b.mpad = mpad; b.m = m;
+      b.variance = kp.variance; b.noise = kp.noise; b.mean_c = kp.mean_c; b.varsigma = acq.varsigma;
+      b.raw = static_cast<const float*>(dev); b.d = d; b.cap = cap;
+      b.my = as<double>(screen_my); b.block_max = as<double>(screen_bmax); b.key = as<int64_t>(grow_key);
+      b.rows_out = as<float>(screen_rows); b.ctl = as<int64_t>(screen_ctl); b.probe = probe ? as<double>(screen_cols) : nullptr;
+      launch_screen(s, b);
+      return launch_status();
+    } else {
+      return ctx->fail(GPSO_E_STATE, "internal: a screened call on a double-predict context");
+    }
+  }
+  // gpso_screen_probe: the mean pass and the screen alone; every leaf's my, ub and survive flag, and what the call would see
+  int screen_probe(const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub, double* flag,
+                   double* info) override {
+    int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    const AcqSpec acq(varsigma);
+    if (!screen_applies(xs_dtype, m, 1, acq, true))
+      return ctx->fail(GPSO_E_STATE, "gpso_screen_probe: no screened call on this context, batch or varsigma (float leaves in one chunk, "
+                                     "the fp16 split with the fp16 contraction and the fused step, a finite varsigma >= 0)");
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    if ((rc = enqueue_screen(dev, m, acq, true))) return rc;
+    hipStream_t s = st();
+    int64_t ctl[3] = {0, 0, 0};
+    if (my) HIPCHECK(hipMemcpyAsync(my, screen_my.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    if (ub) HIPCHECK(hipMemcpyAsync(ub, screen_cols.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    if (flag) HIPCHECK(hipMemcpyAsync(flag, as<double>(screen_cols) + m, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(ctl, screen_ctl.p, 24, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipStreamSynchronize(s));
+    if ((rc = launch_status())) return rc;
+    if (info) {
+      info[0] = (double)ctl[1];
+      std::memcpy(&info[1], &ctl[2], 8);
+      info[2] = (double)screen_cap_rows((m + kLeafPad - 1) / kLeafPad * kLeafPad);
+    }
+    return GPSO_OK;
+  }
+  // the whole screened call; the record (and the verdict) on their way to ovals and pinned host memory
+  int enqueue_best_screened(const void* dev, int64_t m, const AcqSpec& acq) {
+    int rc;
+    hipStream_t s = st();
+    const int64_t mpad = (m + kLeafPad - 1) / kLeafPad * kLeafPad;
+    const int64_t cap = screen_cap_rows(mpad);
+    if ((rc = ensure(best_pos, (size_t)kArgmaxBlocks * 8))) return rc;
+    ctx->tile_pairs = 0;
+    while ((int)ctx->tile_ev.size() < 2) {
+      hipEvent_t e;
+      HIPCHECK(hipEventCreate(&e));
+      ctx->tile_ev.push_back(e);
+    }
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[0], s));
+    ctx->last_count[5] = ctx->last_count[6] = 0;  // (the mean pass parks nothing)
+    if ((rc = enqueue_screen(dev, m, acq, false))) return rc;
+    LeafFinalize fin{};
+    tile_span_open = true;
+    rc = score_device_leaves(screen_rows.p, GPSO_F32, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb),
+                             as<int64_t>(screen_ctl), &fin);
+    tile_span_open = false;
+    if (rc) return rc;
+    if (fin.part_var == nullptr) return ctx->fail(GPSO_E_STATE, "internal: the survivors of a screened call were not deferred");
+    // (float generation: a NaN coordinate reaches the partial sums by itself, as it does in the unscreened call, whose fused
+    // prologue leaves no norms to look at -- the record keeps that NaN's bits, not the finalize stage's own)
+    fin.lnorm = nullptr;
+    host_direct = result_host((size_t)4 + 2);
+    // (the survivors' list as a keyed one of a single segment: no analytic slots, every row in the appended tail, key = the
+    // leaf's index in the caller's batch -- the arg-max ranks and tie-breaks on it)
+    launch_keyed_argmax(s, as<double>(omean), as<double>(ovar), as<double>(oucb), as<int64_t>(grow_key), m, 0, 1,
+                        as<int64_t>(screen_ctl), argmax_blocks(cap, 1), best.p, as<int64_t>(best_pos), as<double>(ovals), &fin,
+                        host_direct, arm_token(true, 1), as<int64_t>(screen_ctl), cap);
+    screen_pending = true;
+    ctx->last_count[0] = ctx->last_count[1] = m;
+    return launch_status();
+  }
+
   // per segment (mean, var, ucb, bit-cast index relative to the segment start) -> ovals; seg_off: host,
   // nseg + 1 entries over [0, m]
+  // may_screen: the caller can run the call again should a screened one be refused (device leaves, finish_best's verdict read)
   int enqueue_best_leaves(const void* dev, int xs_dtype, int64_t m, const int64_t* seg_off, int nseg,
-                          const AcqSpec& acq) {
+                          const AcqSpec& acq, bool may_screen = false) {
     int rc;
     one_pending = false;  // (a call whose result was never read -- gpso_shard_winners -- leaves nothing behind)
+    screen_pending = false;
+    if (!screen_rerun) ctx->last_count[7] = 0, ctx->last_count[8] = kScreenNone;
     host_direct = nullptr;
     call_token = 0.0;
     hipStream_t s = st();
@@ -3377,6 +3533,7 @@ struct EngineT : Engine {
       HIPCHECK(hipStreamSynchronize(s));
       segoff_cache = so;
     }
+    if (may_screen && screen_applies(xs_dtype, m, nseg, acq)) return enqueue_best_screened(dev, m, acq);
     if (m > 0) {  // one launch for the whole call where it applies
       OneLaunch one{};
       one.mode = 2;
@@ -3646,9 +3803,9 @@ struct EngineT : Engine {
   int finish_best(const DevBuf& src, int nseg, int mode, int64_t* idx, double* mean, double* var, double* ucb,
                   int* verdict_out = nullptr, int64_t* who = nullptr) {
     hipStream_t s = st();
-    const bool one = one_pending;
-    one_pending = false;
-    const size_t doubles = (size_t)nseg * 4 + ((mode == 2 || one) ? 2 : mode);
+    const bool one = one_pending, screened = screen_pending;
+    one_pending = screen_pending = false;
+    const size_t doubles = (size_t)nseg * 4 + ((mode == 2 || one || screened) ? 2 : mode);
     double* vals = ctx->pinned_scratch(doubles);
     if (!vals) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     // (mode 0 / 1: the arg-max's second stage has written the records into this very memory: no copy operation)
@@ -3670,6 +3827,7 @@ struct EngineT : Engine {
     // (a centre child does not repeat its parent: the caller re-runs.  Only where a re-run exists -- a folded group
     // payload keeps the GROUP's verdict in this slot, and its half was enqueued with the one-launch kernel refused)
     if (one && mode != 2 && vals[4 * nseg + 1] != 0.0) return 1;
+    if (screened && (rc = screen_verdict(vals))) return rc;
     if (mode == 2) {
       const int verdict = (int)vals[4 * nseg + 1];
       if (verdict_out) *verdict_out = verdict;
@@ -3684,6 +3842,15 @@ struct EngineT : Engine {
     }
     if (mode == 1) std::memcpy(&ctx->last_count[0], &vals[4 * nseg], 8);
     return GPSO_OK;
+  }
+  // a screened call's record (one segment): the survivors' count and the last kernel's verdict -> the counters; a refusal ends
+  // screening on this posterior and returns 1 -- the caller runs the call again, which then takes the general sequence
+  int screen_verdict(const double* vals) {
+    std::memcpy(&ctx->last_count[7], &vals[4], 8);
+    const bool refused = vals[5] != 0.0;
+    ctx->last_count[8] = refused ? kScreenRefused : kScreenAccepted;
+    if (refused) res.screen_was_refused();
+    return refused ? 1 : 0;
   }
   // the group's verdict as this rank's return value: its own failure keeps its own message
   int group_verdict(int verdict, int64_t who, int local_rc, const std::string& local_msg, const char* call) {
@@ -3705,8 +3872,17 @@ struct EngineT : Engine {
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
     const void* dev = nullptr;
     if (m > 0 && (rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    if ((rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq))) return rc;
-    return finish_best(ovals, nseg, 0, idx, mean, var, ucb);
+    const bool may_screen = xs_mem == GPSO_MEM_DEVICE;
+    if ((rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, may_screen))) return rc;
+    rc = finish_best(ovals, nseg, 0, idx, mean, var, ucb);
+    if (rc == 1) {  // a screened call was refused (its posterior is not screened again): the general sequence
+      screen_rerun = true;
+      rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, false);
+      screen_rerun = false;
+      if (rc) return rc;
+      rc = finish_best(ovals, nseg, 0, idx, mean, var, ucb);
+    }
+    return rc;
   }
 
   // ---- the non-blocking pair (round 5): gpso_best_ucb_begin / gpso_best_ucb_grow_begin enqueue a call and return a
@@ -3758,9 +3934,16 @@ struct EngineT : Engine {
       } else {
         const void* dev = nullptr;
         if (m > 0) rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev);
-        if (rc == GPSO_OK) rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq);
+        if (rc == GPSO_OK) rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, xs_mem == GPSO_MEM_DEVICE);
       }
       ctx->slot_token[k] = call_token;
+      // (a screened call: what _end needs to run it again.  The caller keeps device leaves untouched until then)
+      ctx->slot_screen[k].on = screen_pending;
+      ctx->slot_screen[k].xs = xs;
+      ctx->slot_screen[k].xs_dtype = xs_dtype;
+      ctx->slot_screen[k].m = m;
+      ctx->slot_screen[k].acq = acq;
+      screen_pending = false;
     }
     if (rc) return rc;
     if (xs_mem == GPSO_MEM_HOST && !grown && m > 0) HIPCHECK(hipStreamSynchronize(st()));  // (the caller's host leaves are free again on return)
@@ -3793,6 +3976,22 @@ struct EngineT : Engine {
     }
     int rc;
     if ((rc = launch_status())) return rc;
+    if (ctx->slot_screen[ticket].on) {
+      ctx->slot_screen[ticket].on = false;
+      ctx->last_count[0] = ctx->last_count[1] = ctx->slot_screen[ticket].m;
+      if (screen_verdict(vals) != 0) {
+        // refused: the general sequence, now, behind whatever the stream still holds (untimed, like every asynchronous call)
+        const gpso_ctx::SlotScreen sc = ctx->slot_screen[ticket];
+        const bool timing_was = ctx->timing;
+        ctx->timing = false;
+        screen_rerun = true;
+        rc = enqueue_best_leaves(sc.xs, sc.xs_dtype, sc.m, nullptr, 1, sc.acq, false);
+        screen_rerun = false;
+        if (rc == GPSO_OK) rc = finish_best(ovals, 1, 0, idx, mean, var, ucb);
+        ctx->timing = timing_was;
+        return rc;
+      }
+    }
     for (int i = 0; i < nseg; ++i) {
       if (idx) std::memcpy(&idx[i], &vals[4 * i + 3], 8);
       if (mean) mean[i] = vals[4 * i];
@@ -5031,6 +5230,29 @@ int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
   return ctx->eng->acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), mean, var, value, out_mem);
 }
 
+int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,
+                      double* flag, double* info) {
+  ENTER();
+  return ctx->eng->screen_probe(xs, xs_dtype, xs_mem, m, varsigma, my, ub, flag, info);
+}
+
+int gpso_screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, int64_t n,
+                          double* ucb, double* ub) {
+  if (n < 0 || (n > 0 && !my)) return GPSO_E_ARG;
+  gpso::screen_eval_host(my, v, variance, noise, varsigma, (long long)n, ucb, ub);
+  return GPSO_OK;
+}
+
+double gpso_screen_threshold_host(double max_my, double noise, double varsigma) {
+  return gpso::screen_threshold_host(max_my, noise, varsigma);
+}
+
+int gpso_screen_survives_host(double my, double ub, double threshold) { return gpso::screen_survives_host(my, ub, threshold); }
+
+int gpso_screen_accepts_host(double u_star, double threshold, int64_t count, int64_t cap) {
+  return gpso::screen_accepts_host(u_star, threshold, (long long)count, (long long)cap);
+}
+
 int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out) {
   if (acq_refusal(acq) != nullptr || n < 0 || (n > 0 && (!mean || !var || !out)) || noise != noise) return GPSO_E_ARG;
   gpso::acq_eval_host(acq_spec(acq), mean, var, noise, (long long)n, out);
@@ -5229,7 +5451,7 @@ int gpso_comm_abort(gpso_ctx* ctx) {
 }
 
 int64_t gpso_last_count(gpso_ctx* ctx, int what) {
-  if (!ctx || what < 0 || what > 6) return -1;
+  if (!ctx || what < 0 || what > 8) return -1;
   return what == 4 ? g_dev_bytes_held.load(std::memory_order_relaxed) : ctx->last_count[what];
 }
 

@@ -165,7 +165,54 @@ void launch_seg_argmax(hipStream_t st, const double* mean, const double* var, co
 void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, const double* ucb,
                          const int64_t* key_dev, int64_t rows, int64_t uniq, int nseg, const int64_t* live_dev,
                          int nblk, void* partial_dev, int64_t* pos_dev, double* out_vals_dev,
-                         const LeafFinalize* fin = nullptr, double* host_vals = nullptr, double done_token = 0.0);
+                         const LeafFinalize* fin = nullptr, double* host_vals = nullptr, double done_token = 0.0,
+                         const int64_t* screen_ctl = nullptr /* the list holds a screened call's survivors (launch_screen's ctl): the
+                         last kernel judges the record (screen.hpp: screen_accepts) -- status slot 1.0: refused; the slot in front of
+                         it: the survivors' count */, int64_t screen_cap = 0);
+
+// ---- screen.hip: screened best-UCB calls (screen.hpp) ------------------------------------------------------------------
+// The mean pass: part_mean[npad / 256][mpad] as the split tile kernel with the fp16 split and the fp16 contraction writes it
+// (same bits), from the generation of the diagonal k-steps alone.  Float generation; leaves: raw.x (unscaled, the kernel
+// scales them as the tile kernel's prologue does) or leaves_s (scaled).  The grid's second dimension is leaf_row_splits' for
+// a batch of known size -> *splits_out.
+struct LeafMeanLaunch {
+  const void* xs_h16 = nullptr;
+  const float* alpha = nullptr;
+  const float* c16_scale = nullptr;
+  const float* leaves_s = nullptr;
+  RawLeaves raw;
+  double* part_mean = nullptr;
+  int64_t npad = 0, mpad = 0, n_rows = 0;
+  int dp4 = 0;
+  int row_loop = 1, cu_count = 256;
+  int64_t* splits_out = nullptr;
+};
+int launch_leaf_mean(hipStream_t st, const KernParams& kp, const LeafMeanLaunch& a);
+// The screen and the ordered compaction (two launches): my[m], block_max[ceil(m / 256)] scratch; key[cap] the survivors'
+// indices, ascending; rows_out[cap][d] their raw rows; ctl (3 x int64): live rows = min(count, cap), count, T' (bit-cast);
+// probe (nullable, [2][m]): every leaf's ub and survive flag
+struct ScreenLaunch {
+  const double* part_mean = nullptr;
+  int nbi = 0;
+  int64_t mpad = 0, m = 0;
+  double variance = 0, noise = 0, mean_c = 0, varsigma = 0;
+  const float* raw = nullptr;
+  int d = 0;
+  int64_t cap = 0;
+  double* my = nullptr;
+  double* block_max = nullptr;
+  int64_t* key = nullptr;
+  float* rows_out = nullptr;
+  int64_t* ctl = nullptr;
+  double* probe = nullptr;
+};
+void launch_screen(hipStream_t st, const ScreenLaunch& a);
+// screen.hpp on the host (gpso_screen_*_host: the CPU tests)
+void screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, long long n,
+                      double* ucb, double* ub);
+double screen_threshold_host(double max_my, double noise, double varsigma);
+int screen_survives_host(double my, double ub, double threshold);
+int screen_accepts_host(double u_star, double threshold, long long count, long long cap);
 // out_dev[c] = number of live leaves inside chunk c of a batch whose total live count is *live_dev
 void launch_chunk_live(hipStream_t st, const int64_t* live_dev, int64_t chunk, int nchunk, int64_t* out_dev);
 // *acc += sum_i mix(words[i], i, salt)  (64-bit wrap-around sum of a per-word mix: order-independent, so the parallel

@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "grow_device.hpp"
 #include "kernels.hpp"
+#include "screen.hpp"
 #include "leaf_split.hpp"  // (LDS-DMA helpers, the fp16 pair split; the split kernels themselves: predict_split_*.hip)
 
 namespace gpso {
@@ -1089,7 +1090,10 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage2(const Best* __restric
                                                            const int64_t* __restrict__ live, int nseg,
                                                            double* __restrict__ out_vals /*[nseg*4 + 2]*/,
                                                            double* __restrict__ host_vals /* nullable, see seg_argmax_stage2 */,
-                                                           double done_token) {
+                                                           double done_token,
+                                                           const int64_t* __restrict__ screen_ctl /* nullable: the list holds the
+                                                           survivors of a screened call (screen.hip); one segment */,
+                                                           int64_t screen_cap) {
   __shared__ Best sh[4];
   const int seg = blockIdx.x;
   Best mine{0.0, -1};
@@ -1114,13 +1118,20 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage2(const Best* __restric
     if (seg == 0) {
       out_vals[nseg * 4] = __builtin_bit_cast(double, *live);
       out_vals[nseg * 4 + 1] = 0.0;  // status slot of a group payload
+      if (screen_ctl != nullptr) {
+        // a screened call: the survivors' count in place of the live rows, and the verdict on the record (screen.hpp) -- 1.0:
+        // refused, the caller runs the general sequence
+        const double u_star = out_vals[2], threshold = __builtin_bit_cast(double, screen_ctl[2]);
+        out_vals[nseg * 4] = __builtin_bit_cast(double, screen_ctl[1]);
+        out_vals[nseg * 4 + 1] = (mine.i >= 0 && screen_accepts(u_star, threshold, screen_ctl[1], screen_cap)) ? 0.0 : 1.0;
+      }
     }
     if (host_vals != nullptr) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) host_vals[seg * 4 + k] = out_vals[seg * 4 + k];
       if (seg == 0) {
         host_vals[nseg * 4] = out_vals[nseg * 4];
-        host_vals[nseg * 4 + 1] = 0.0;
+        host_vals[nseg * 4 + 1] = out_vals[nseg * 4 + 1];
       }
       if (nseg == 1) publish_done(host_vals, nseg * 4 + 2, done_token);
     }
@@ -1457,7 +1468,7 @@ void launch_seg_argmax(hipStream_t st, const double* mean, const double* var, co
 void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, const double* ucb,
                          const int64_t* key_dev, int64_t rows, int64_t uniq, int nseg, const int64_t* live_dev,
                          int nblk, void* partial_dev, int64_t* pos_dev, double* out_vals_dev, const LeafFinalize* fin,
-                         double* host_vals, double done_token) {
+                         double* host_vals, double done_token, const int64_t* screen_ctl, int64_t screen_cap) {
   if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
     hipLaunchKernelGGL((keyed_argmax_stage1<true, true>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
@@ -1469,7 +1480,7 @@ void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, 
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, LeafFinalize{});
   hipLaunchKernelGGL(keyed_argmax_stage2, dim3((unsigned)nseg), dim3(256), 0, st,
                      reinterpret_cast<const Best*>(partial_dev), pos_dev, nblk, rows, mean, var, ucb, live_dev,
-                     nseg, out_vals_dev, host_vals, done_token);
+                     nseg, out_vals_dev, host_vals, done_token, screen_ctl, screen_cap);
 }
 
 void launch_reduce_winners(hipStream_t st, const double* gathered, const int64_t* base, int world, int nseg,

@@ -36,6 +36,7 @@ struct Resident {
   int small_tile_rows = 8;     // tile rows of the 128-padded linv_p that may be non-zero (8: all / unknown)
   bool paths_valid = false;    // the path set of gpso_paths_draw / gpso_paths_draw_q (omega, b, w, v) belongs to this posterior as it stands
   bool q_factors = false;      // a variational install's Lu (Lf), beta (alpha_f) and root Q of q (vq_S / svq_S / sgM2) are still in their buffers
+  bool screen_refused = false;  // a screened best-UCB call on this posterior was refused (a flat mean prunes nothing): it is not screened again
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -64,9 +65,10 @@ struct Resident {
     post = Post::None;
     have_kinv = chol_valid = st_done = st_have = false;
     linv_p = Copy::Absent;
-    paths_valid = q_factors = false;
+    paths_valid = q_factors = screen_refused = false;
     if (!keep_peers) sync_n = -1;
   }
+  void screen_was_refused() { screen_refused = true; }  // posterior_dropped() and appended() end it
   // A new posterior begins (or an option changed): generation starts over -- float unless double was asked for --, the
   // ladder on its first rung, and the self-test rules again.  Not part of posterior_dropped(): new data, a new noise
   // vector, moved inducing rows and a hand-off's allocation keep the old verdicts until the next posterior begins
@@ -111,7 +113,7 @@ struct Resident {
   // the self-test looks at the extended posterior; the float copies of the inputs are derived again
   void appended(bool first_noise_vector) {
     have_s = have_s || first_noise_vector;
-    have_kinv = st_done = gen32_inputs_ok = paths_valid = false;  // (v was solved against the shorter factor)
+    have_kinv = st_done = gen32_inputs_ok = paths_valid = screen_refused = false;  // (v was solved against the shorter factor)
     small_tile_rows = 8;
   }
   void append_refused() { gen32_inputs_ok = false; }  // not PD: the scaled inputs were put back, their float copies not
@@ -147,7 +149,7 @@ struct Resident {
   // generation arithmetic and predict math: the sender's choice (its self-test ruled), unless this context insists
   void adopted(int sender, bool float_predict, bool math_auto, int gen_mode, int64_t npad) {
     post = Post::Adopted;
-    chol_valid = have_kinv = paths_valid = q_factors = false;
+    chol_valid = have_kinv = paths_valid = q_factors = screen_refused = false;
     small_tile_rows = 8;         // linv_p came from elsewhere
     st_done = st_have = false;   // the fitting rank ran the self-test; no targets here
     math_native_fallback = math_auto && (sender & 2) != 0;

@@ -1,0 +1,52 @@
+// Screened best-UCB calls: the bound, the threshold and the acceptance test.  One restatement for the device (screen.hip,
+// predict.hip: keyed_argmax_stage2) and for the host (gpso_screen_eval_host: the CPU tests), built like acq.hpp.  DESIGN.md 4.1.
+//
+// finalize_leaf (predict.hip) forms, for a leaf with mean my = fl(sum of the row blocks' mean shares + mean_c):
+//     v = sum_b part_var[b]  (>= 0: a sum of squares, starting at 0),  fv = fl(variance - v),  vy = fl(fv + noise),
+//     u = fl(my + fl(varsigma * vy)).
+// Every rounding is monotone, so for varsigma >= 0 the u the kernel computes can never exceed the same expression at v = 0:
+//     ub = fl(my + fl(varsigma * fl(variance + noise))),
+// PROVIDED my is the mean the tile kernel itself computes, bit for bit (screen.hip: leaf_mean_kernel).  A bound in the
+// kernel's own arithmetic: no error analysis, no second product.
+//
+// A call keeps ("survives") every leaf with  !(ub < T'),  T' = fl(max finite my + fl(varsigma * noise)), and every leaf whose
+// mean is not finite (NaN ranks first in the arg-max); it scores the survivors with the tile kernel and ACCEPTS the winner's
+// record iff its ucb u* is NaN or u* >= T': every pruned leaf then had ub < T' <= u* and could neither win nor tie.  T' is the
+// ucb the leaf of the largest mean has when its variance share is exactly zero; nothing relies on that -- a u* below T' is
+// refused and the call runs the general sequence.
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+#include "acq.hpp"
+
+namespace gpso {
+
+// gpso_last_count(ctx, 8)
+constexpr int kScreenNone = 0, kScreenAccepted = 1, kScreenRefused = 2;
+
+// finalize_leaf's ucb under the reference's rule, from the leaf's mean and its summed variance share v
+GPSO_ACQ_HD inline double screen_ucb(double my, double v, double variance, double noise, double varsigma) {
+#pragma clang fp contract(off)
+  const double fv = variance - v;
+  const double vy = fv + noise;
+  return acq_mul_then_add(my, varsigma, vy);
+}
+// ... and what it cannot exceed, whatever v >= 0 turns out to be (varsigma >= 0)
+GPSO_ACQ_HD inline double screen_bound(double my, double variance, double noise, double varsigma) {
+  return screen_ucb(my, 0.0, variance, noise, varsigma);
+}
+// max_my: the largest FINITE mean of the batch; -inf where there is none (then nothing is pruned)
+GPSO_ACQ_HD inline double screen_threshold(double max_my, double noise, double varsigma) {
+  return acq_mul_then_add(max_my, varsigma, noise);
+}
+GPSO_ACQ_HD inline bool screen_finite(double x) { return x - x == 0.0; }
+GPSO_ACQ_HD inline bool screen_survives(double my, double ub, double threshold) {
+  return !screen_finite(my) || !(ub < threshold);
+}
+// the survivors' winner: count survivors (cap: how many the survivors' launch had room for), u_star the winner's ucb
+GPSO_ACQ_HD inline bool screen_accepts(double u_star, double threshold, int64_t count, int64_t cap) {
+  return count > 0 && count <= cap && (u_star != u_star || u_star >= threshold);
+}
+
+}  // namespace gpso

@@ -141,6 +141,45 @@ class HipGPEngine:
         reloaded."""
         self._check(self._lib.gpso_set_option(self._h, L.OPT_PARK_BYTES, int(nbytes)))
 
+    def set_screen(self, mode):
+        """GPSO_OPT_SCREEN (per context): 1 = best-UCB calls of more than 16 384 float device leaves, one segment, are screened by
+        a mean-only bound before the tile kernel (default); 0 = never; 2 = whatever the batch size (tests).  Same record bits.
+        ``last_count(7)``: survivors of the last call; ``last_count(8)``: 0 not screened, 1 accepted, 2 refused and run again."""
+        self._check(self._lib.gpso_set_option(self._h, L.OPT_SCREEN, int(mode)))
+
+    def screen_probe(self, xs, varsigma):
+        """The mean pass and the screen of a screened best-UCB call alone (``gpso_screen_probe``) -> (my[M], ub[M], survives[M]
+        bool, info): every leaf's mean -- ``predict``'s bits --, what its ucb cannot exceed, whether it survives; info =
+        {"survivors", "threshold", "cap"}."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        my, ub, flag = (np.empty(m, dtype=np.float64) for _ in range(3))
+        info = np.zeros(3, dtype=np.float64)
+        self._check(self._lib.gpso_screen_probe(self._h, ptr, dt, mem, m, float(varsigma), L.dptr(my), L.dptr(ub), L.dptr(flag),
+                                                L.dptr(info)))
+        return my, ub, flag != 0.0, {"survivors": int(info[0]), "threshold": float(info[1]), "cap": int(info[2])}
+
+    @staticmethod
+    def screen_eval_host(my, v, variance, noise, varsigma):
+        """csrc/screen.hpp on the CPU (no context, no GPU) -> (ucb[n], ub[n]): the finalize stage's ucb of leaves with means
+        ``my`` and variance shares ``v``, and the bound a screened call prunes by."""
+        my = L.as_f64(np.asarray(my).reshape(-1))
+        v = L.as_f64(np.asarray(v).reshape(-1), my.shape)
+        ucb, ub = np.empty_like(my), np.empty_like(my)
+        rc = L.load().gpso_screen_eval_host(L.dptr(my), L.dptr(v), float(variance), float(noise), float(varsigma),
+                                            int(my.shape[0]), L.dptr(ucb), L.dptr(ub))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_screen_eval_host: bad arguments")
+        return ucb, ub
+
+    @staticmethod
+    def screen_rules_host():
+        """(threshold(max_my, noise, varsigma), survives(my, ub, threshold), accepts(u_star, threshold, count, cap)) of
+        csrc/screen.hpp on the CPU."""
+        lib = L.load()
+        return (lambda max_my, noise, vs: float(lib.gpso_screen_threshold_host(float(max_my), float(noise), float(vs))),
+                lambda my, ub, t: bool(lib.gpso_screen_survives_host(float(my), float(ub), float(t))),
+                lambda u, t, count, cap: bool(lib.gpso_screen_accepts_host(float(u), float(t), int(count), int(cap))))
+
     def set_precision_check(self, on):
         self._check(self._lib.gpso_set_option(self._h, L.OPT_PRECISION_CHECK, 1 if on else 0))
 
@@ -188,7 +227,8 @@ class HipGPEngine:
     def last_count(self, what=0):
         """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list; 2 .. 6: see
         ``gpso_last_count`` in include/gpso_hip.h (4: bytes of device memory the contexts of this process hold now; 5 / 6:
-        k-steps per leaf tile the last split predict launch parked / reloaded under GPSO_OPT_PARK_BYTES)."""
+        k-steps per leaf tile the last split predict launch parked / reloaded under GPSO_OPT_PARK_BYTES; 7 / 8: survivors and
+        verdict -- 0 not screened, 1 accepted, 2 refused -- of the last best-UCB call under GPSO_OPT_SCREEN)."""
         return int(self._lib.gpso_last_count(self._h, int(what)))
 
     FIT_MATH = {L.FITMATH_NONE: None, L.FITMATH_SMALL: "small", L.FITMATH_F32: "f32", L.FITMATH_F64: "f64",
