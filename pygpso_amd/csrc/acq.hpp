@@ -51,7 +51,9 @@ constexpr double kAcqMidTail = -1.0, kAcqFarTail = -10.0;  // where the pieces o
 
 // m + a * b with the product rounded on its own (numpy's two roundings), whatever the translation unit's contraction mode
 GPSO_ACQ_HD inline double acq_mul_then_add(double m, double a, double b) {
+#if defined(__clang__)  // (the library's compiler; another one that includes this for AcqSpec alone does not call the maps)
 #pragma clang fp contract(off)
+#endif
   const double prod = a * b;
   return m + prod;
 }

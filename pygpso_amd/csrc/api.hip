@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/gpso_hip.h"
+#include "best_call.hpp"
 #include "common.hpp"
 #include "devbuf.hpp"
 #include "kernels.hpp"
@@ -213,8 +214,7 @@ struct gpso_ctx {
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
   hipEvent_t ev[8] = {};  // [0..1] spare, [2..3] predict-type call, [4..5] fit, [6..7] the collective of a sharded call
-  std::vector<hipEvent_t> tile_ev;  // start/stop pairs around the leaf-tile kernel, one per chunk
-  int tile_pairs = 0;               // pairs recorded by the call in flight
+  std::vector<hipEvent_t> tile_ev;  // start/stop pairs around the leaf-tile kernel, one per chunk (how many were recorded: TileSpan)
   double last_ms[4] = {0, 0, 0, 0};
   bool timing = true;  // GPSO_OPT_TIMING: does the call in flight record the event pairs gpso_last_ms reads (two to four HIP calls)?
   int timing_every = 1;  // ... 0: never, 1: every fit / predict-type call, k: every k-th one (the others leave gpso_last_ms alone)
@@ -244,38 +244,32 @@ struct gpso_ctx {
   // gpso_best_ucb_begin / _end: two calls may be in flight; each has a pinned result slot of its own and a completion event
   static constexpr int kSlots = 2;
   static constexpr size_t kSlotDoubles = 4 * 1024 + 4;  // nseg <= 1024 per asynchronous call (+ the completion token)
-  double slot_token[kSlots] = {0, 0};
+  gpso::BestTicket<hipEvent_t> tickets[kSlots];  // (best_call.hpp: the enqueue's record, the completion event, in use)
   double* slot_host = nullptr;   // [kSlots][kSlotDoubles], pinned
-  hipEvent_t slot_ev[kSlots] = {};
-  int slot_nseg[kSlots] = {0, 0};  // > 0: the slot holds a call that has not been ended
-  int slot_mode[kSlots] = {0, 0};
-  // a SCREENED call in the slot: what gpso_best_ucb_end needs to run the general sequence should the call be refused
-  struct SlotScreen {
-    bool on = false;
-    const void* xs = nullptr;
-    int xs_dtype = 0;
-    int64_t m = 0;
-    gpso::AcqSpec acq;
-  } slot_screen[kSlots];
-  int slot_next = 0;
-  int slots_busy() const { return (slot_nseg[0] > 0) + (slot_nseg[1] > 0); }
+  int next_ticket = 0;           // tickets are handed out in turn (the other one where that one is still open)
+  int slots_busy() const { return (int)tickets[0].in_use + (int)tickets[1].in_use; }
 
-  // Wait for everything queued on s.  hipStreamSynchronize parks the thread on an interrupt and costs
-  // tens of microseconds to wake up -- as much as the device work of a small fit.  The calling thread
-  // is blocked in this library anyway, so poll an event for up to kSpinMs and only then block.
-  hipError_t wait(hipStream_t s) {
+  // A blocking wait parks the thread on an interrupt and costs tens of microseconds to wake up -- the device work of a small fit.
+  // The calling thread is blocked in this library anyway: poll done() (hipErrorNotReady: go on) for up to kSpinMs, then block().
+  template <int kPollMask, typename Done, typename Block>
+  static hipError_t spin_then_block(Done&& done, Block&& block) {
     constexpr double kSpinMs = 20.0;
-    hipError_t e = hipEventRecord(ev_wait, s);
-    if (e != hipSuccess) return e;
     const auto t0 = std::chrono::steady_clock::now();
     for (int it = 0;; ++it) {
-      e = hipEventQuery(ev_wait);
+      const hipError_t e = done();
       if (e != hipErrorNotReady) return e;
-      if ((it & 63) == 63 &&
+      if ((it & kPollMask) == kPollMask &&
           std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > kSpinMs)
-        return hipStreamSynchronize(s);
+        return block();
     }
   }
+  // wait for everything queued on s
+  hipError_t wait(hipStream_t s) {
+    const hipError_t e = hipEventRecord(ev_wait, s);
+    if (e != hipSuccess) return e;
+    return spin_then_block<63>([&] { return hipEventQuery(ev_wait); }, [&] { return hipStreamSynchronize(s); });
+  }
+  hipError_t wait_event(hipEvent_t ev) { return spin_then_block<63>([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); }); }
   double* pinned_scratch(size_t doubles) {
     if (doubles > pinned_doubles) {
       if (pinned) (void)hipHostFree(pinned);
@@ -300,18 +294,9 @@ struct gpso_ctx {
   }
   double next_token() { return (double)(seq_counter().fetch_add(1) + 1); }  // (exact in a double for 2^53 calls)
   hipError_t wait_token(const double* word, double token, hipStream_t s) {
-    constexpr double kSpinMs = 20.0;
     const volatile double* w = word;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int it = 0;; ++it) {
-      if (*w == token) {
-        std::atomic_thread_fence(std::memory_order_acquire);
-        return hipSuccess;
-      }
-      if ((it & 1023) == 1023 &&
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > kSpinMs)
-        return hipStreamSynchronize(s);
-    }
+    auto arrived = [&] { return *w == token ? (std::atomic_thread_fence(std::memory_order_acquire), hipSuccess) : hipErrorNotReady; };
+    return spin_then_block<1023>(arrived, [&] { return hipStreamSynchronize(s); });
   }
 
   // staging buffer for host -> device copies that must not force a stream synchronisation.  It is
@@ -475,23 +460,15 @@ struct EngineT : Engine {
   }
   bool small_calls = true, one_launch = true, one_launch_everywhere = false;  // GPSO_OPT_SMALL_CALLS
   bool fuse_prep = true;  // GPSO_OPT_FUSED_PREP: float leaves are scaled in the fp16-contraction kernel's prologue (same bits)
-  bool one_refused = false;                    // the one-launch kernel asked for the general sequence (this call only)
   int64_t single_level_max = -1;  // < 0: library default
   bool fused_small = true;        // GPSO_OPT_FIT_FUSED_SMALL
   std::vector<int64_t> segoff_cache;  // what the device copy of seg_off currently holds
-  double* host_direct = nullptr;      // pinned host memory the arg-max of the call in flight writes its records to
-  double* result_slot = nullptr;      // asynchronous call being enqueued: its own pinned slot instead of the shared scratch
-  double* result_host(size_t doubles) { return result_slot != nullptr ? result_slot : ctx->pinned_scratch(doubles + 1); }  // (+ the token's slot)
-  double call_token = 0.0;  // the completion token the LAST kernel of the call in flight writes (0: none -- wait for the event)
-  // a fresh token for the kernel about to be launched as the call's last one, or 0 where the call is timed (events needed)
-  // or that kernel is not a single workgroup
-  double arm_token(bool single_workgroup, int nseg) {
-    call_token = (single_workgroup && !ctx->timing && host_direct != nullptr) ? ctx->next_token() : 0.0;
-    // (whatever an earlier call left in the token's word -- a record of a call with more segments -- cannot pass for it)
-    if (call_token != 0.0) host_direct[4 * nseg + 2] = 0.0;
-    return call_token;
-  }
-  DevBuf extra_cnt;                   // small growth calls: rows appended behind the analytic slots (zero between calls)
+  // A best-UCB call in flight (best_call.hpp): the entry point's plan goes down, the enqueue's record comes back.
+  using BestPlan = gpso::BestPlan; using BestCall = gpso::BestCall; using BestKind = gpso::BestKind;
+  // the pinned memory the call's last kernel -- about to be launched -- writes nseg records to, and the token behind them
+  double* result_host(const BestPlan& plan, BestCall& call, int nseg) { return call.writes_host(plan.slot ? plan.slot : ctx->pinned_scratch((size_t)nseg * 4 + 3)); }
+  double arm_token(BestCall& call, bool single_workgroup, int nseg) { return call.arm_token(single_workgroup, nseg, ctx->next_token()); }
+  DevBuf extra_cnt;                  // small growth calls: rows appended behind the analytic slots (zero between calls)
   // predict workspace
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
@@ -499,9 +476,6 @@ struct EngineT : Engine {
   // (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
   DevBuf screen_my, screen_bmax, screen_rows, screen_ctl, screen_cols;
   int screen_mode = GPSO_SCREEN_DEFAULT;  // GPSO_OPT_SCREEN
-  bool screen_pending = false;  // the call in flight is a screened one: finish_best looks at its verdict
-  bool screen_rerun = false;    // the call being enqueued repeats a refused screened call: its counters stay
-  bool tile_span_open = false;  // a screened call's mean pass has recorded the start of the tile kernel's event pair
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
   DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
@@ -2496,9 +2470,20 @@ struct EngineT : Engine {
   // defer (nullable): the caller's arg-max can finalise the leaves itself (launch_seg_argmax / launch_keyed_argmax with
   // a LeafFinalize) -- when the batch is ONE chunk the finalize launch is skipped and *defer says what to finalise;
   // otherwise defer->part_var stays NULL and the leaves are finalised here as before
+  // are the tile kernel's event pairs recorded, and how many were (collect_tile_ms).  open: the survivors of a screened call -- the
+  // pair's first event stands in front of the mean pass already, and the split launch's counters keep describing that pass
+  struct TileSpan { bool timed; bool open = false; int pairs = 0; };
+  int ensure_tile_events(int pairs) {
+    while ((int)ctx->tile_ev.size() < 2 * pairs) {
+      hipEvent_t e;
+      HIPCHECK(hipEventCreate(&e));
+      ctx->tile_ev.push_back(e);
+    }
+    return GPSO_OK;
+  }
   template <typename TG>
   int score_leaves_t(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb,
-                     double* mean_dev, double* var_dev, double* ucb_dev, const int64_t* m_live, LeafFinalize* defer,
+                     double* mean_dev, double* var_dev, double* ucb_dev, TileSpan& span, const int64_t* m_live, LeafFinalize* defer,
                      bool prepared = false /* leaves_s / lnorm already hold the scaled rows (one chunk): no prep launch */) {
     // row blocks of L^-1 = partial sums per leaf: the split-bf16 kernel always works on 256-row blocks,
     // the native kernels on the shape leaf_tiles_bm picks
@@ -2520,10 +2505,7 @@ struct EngineT : Engine {
     if ((rc = ensure(pvar, (size_t)nbi * cpad * 8))) return rc;
     if ((rc = ensure(pmean, (size_t)nbi * cpad * 8))) return rc;
     hipStream_t s = st();
-    ctx->tile_pairs = 0;
-    // (the survivors of a screened call: the pair's first event stands in front of the mean pass, and the counters of the
-    // split launch keep describing the batch-sized launch of the mean pass)
-    const bool span_open = tile_span_open;
+    span.pairs = 0;
     const int64_t keep_counts[3] = {ctx->last_count[3], ctx->last_count[5], ctx->last_count[6]};
     const size_t in_elem = (xs_dtype == GPSO_F64) ? 8 : 4;
     const TG* xsp = nullptr;
@@ -2571,12 +2553,8 @@ struct EngineT : Engine {
       } else {
         launch_prep_leaves<TG, float>(s, reinterpret_cast<const float*>(src), mc, mp, d, dp, ls_dev(), m_live_c, as<TG>(leaves_s), as<TG>(lnorm));
       }
-      while ((int)ctx->tile_ev.size() < 2 * (ctx->tile_pairs + 1)) {
-        hipEvent_t e;
-        HIPCHECK(hipEventCreate(&e));
-        ctx->tile_ev.push_back(e);
-      }
-      if (ctx->timing && !span_open) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs], s));
+      if ((rc = ensure_tile_events(span.pairs + 1))) return rc;
+      if (span.timed && !span.open) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * span.pairs], s));
       if (use_bf16) {
         if constexpr (kFloatPredict) {
           SplitLeafLaunch<TG> a;
@@ -2590,7 +2568,7 @@ struct EngineT : Engine {
           a.splits_out = &ctx->last_count[3];
           a.park_bytes = park_bytes; a.park_scratch = &EngineT::park_cb; a.park_owner = this; a.park_out = &ctx->last_count[5];
           rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
-          if (span_open) ctx->last_count[3] = keep_counts[0], ctx->last_count[5] = keep_counts[1], ctx->last_count[6] = keep_counts[2];
+          if (span.open) ctx->last_count[3] = keep_counts[0], ctx->last_count[5] = keep_counts[1], ctx->last_count[6] = keep_counts[2];
         }
       } else {
         rc = launch_leaf_tiles<TP, TG>(s, as<TP>(linv_p), xsp, xnr, as<TP>(alpha), as<TG>(leaves_s),
@@ -2598,8 +2576,8 @@ struct EngineT : Engine {
                                        m_live_c);
       }
       if (rc) return launch_status();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * ctx->tile_pairs + 1], s));
-      ++ctx->tile_pairs;
+      if (span.timed) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * span.pairs + 1], s));
+      ++span.pairs;
       if (defer != nullptr && nchunk == 1 && want_ucb) {
         *defer = LeafFinalize{as<double>(pvar), as<double>(pmean), nbi, mp, kp.variance, kp.noise, kp.mean_c, acq.varsigma,
                               mean_dev, var_dev, ucb_dev, fused_prep ? nullptr : lnorm.p, sizeof(TG) == 8}.with(acq);
@@ -2612,32 +2590,28 @@ struct EngineT : Engine {
   }
 
   int score_device_leaves(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb,
-                          double* mean_dev, double* var_dev, double* ucb_dev, const int64_t* m_live = nullptr,
+                          double* mean_dev, double* var_dev, double* ucb_dev, TileSpan& span, const int64_t* m_live = nullptr,
                           LeafFinalize* defer = nullptr, bool prepared = false) {
     if (defer != nullptr) *defer = LeafFinalize{};
     if constexpr (kFloatPredict) {
       if (!gen_double()) {
         int rc = ensure_generation_inputs();
         if (rc) return rc;
-        return score_leaves_t<float>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
+        return score_leaves_t<float>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, span, m_live, defer, prepared);
       }
     }
-    return score_leaves_t<double>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, m_live, defer, prepared);
+    return score_leaves_t<double>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, span, m_live, defer, prepared);
   }
 
   // after the stream has been synchronised: total leaf-tile kernel time of the call
-  void collect_tile_ms() {
-    if (!ctx->timing) {
-      ctx->tile_pairs = 0;
-      return;
-    }
+  void collect_tile_ms(bool timed, int pairs) {
+    if (!timed) return;
     float total = 0;
-    for (int i = 0; i < ctx->tile_pairs; ++i) {
+    for (int i = 0; i < pairs; ++i) {
       float ms = 0;
       if (hipEventElapsedTime(&ms, ctx->tile_ev[2 * i], ctx->tile_ev[2 * i + 1]) == hipSuccess) total += ms;
     }
     ctx->last_ms[0] = total;
-    ctx->tile_pairs = 0;
   }
 
   // ---- precision self-test (see fit.hip: selftest_kernel) ---------------------------------------
@@ -2669,7 +2643,8 @@ struct EngineT : Engine {
     if ((rc = ensure(st_mean, (size_t)n * 8))) return rc;
     if ((rc = ensure(st_var, (size_t)n * 8))) return rc;
     if ((rc = ensure(st_out, 8 * 8))) return rc;  // 6 used
-    if ((rc = score_device_leaves(x64.p, GPSO_F64, n, 0.0, false, as<double>(st_mean), as<double>(st_var), nullptr))) return rc;
+    TileSpan span{ctx->timing};
+    if ((rc = score_device_leaves(x64.p, GPSO_F64, n, 0.0, false, as<double>(st_mean), as<double>(st_var), nullptr, span))) return rc;
     launch_selftest<TF>(st(), as<double>(st_mean), as<double>(st_var), as<double>(y64), as<TF>(alpha_f),
                         as<double>(kinv_diag), n, kp.noise, kp.mean_c, as<double>(st_out), s_dev());
     double* host = ctx->pinned_scratch(8);
@@ -2835,14 +2810,15 @@ struct EngineT : Engine {
       md = as<double>(omean);
       vd = as<double>(ovar);
     }
-    if ((rc = score_device_leaves(dev, xs_dtype, m, 0.0, false, md, vd, nullptr))) return rc;
+    TileSpan span{ctx->timing};
+    if ((rc = score_device_leaves(dev, xs_dtype, m, 0.0, false, md, vd, nullptr, span))) return rc;
     if (out_mem == GPSO_MEM_HOST) {
       HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
       HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
     }
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
     HIPCHECK(ctx->wait(s));
-    collect_tile_ms();
+    collect_tile_ms(span.timed, span.pairs);
     ctx->last_count[0] = ctx->last_count[1] = m;
     float ms = 0;
     if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
@@ -2877,7 +2853,8 @@ struct EngineT : Engine {
       if ((rc = ensure(oucb, (size_t)m * 8))) return rc;
       ud = as<double>(oucb);
     }
-    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, vd, ud))) return rc;
+    TileSpan span{ctx->timing};
+    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, vd, ud, span))) return rc;
     if (host) {
       if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
       if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
@@ -2885,7 +2862,7 @@ struct EngineT : Engine {
     }
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
     HIPCHECK(ctx->wait(s));
-    collect_tile_ms();
+    collect_tile_ms(span.timed, span.pairs);
     ctx->last_count[0] = ctx->last_count[1] = m;
     float ms = 0;
     if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
@@ -3292,12 +3269,10 @@ struct EngineT : Engine {
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
   // Applies when the native tile kernel runs this posterior with ONE row block (N_pad = 128 or 256) and the batch is
   // small.  Returns 0 when the call was enqueued (records on their way to ovals and pinned host memory), 2 when it does
-  // not apply -- the caller goes on with the next-best sequence --, or a negative status.
+  // not apply -- the caller goes on with the next-best sequence --, or a negative status.  mode: finish_best's read-back
   DevBuf one_ctl, one_partial, one_ppos;
-  bool one_pending = false;  // the call in flight is a one-launch call: finish_best looks at its fallback verdict
-  bool coll_timed = false;   // the call in flight recorded the event pair around its collective (all-gather + fold)
   template <typename TG>
-  int try_one_launch_t(OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq) {
+  int try_one_launch_t(const BestPlan& plan, BestCall& call, OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq, int mode) {
     const int64_t cpad = (total + kLeafPad - 1) / kLeafPad * kLeafPad;
     int rc;
     if ((rc = ensure(leaves_s, (size_t)cpad * dp * sizeof(TG)))) return rc;
@@ -3326,8 +3301,8 @@ struct EngineT : Engine {
     one.ticket = static_cast<unsigned*>(one_ctl.p);
     one.fallback = static_cast<unsigned*>(one_ctl.p) + 1;
     one.out_vals = as<double>(ovals);
-    one.host_vals = host_direct = result_host((size_t)nseg * 4 + 2);
-    one.done_token = arm_token(true, nseg);  // (the last-arriving workgroup's thread 0 writes every host record, then the token)
+    one.host_vals = result_host(plan, call, nseg);
+    one.done_token = arm_token(call, true, nseg);  // (the last-arriving workgroup's thread 0 writes every host record, then the token)
     const TG* xsp;
     const TG* xnr;
     if constexpr (sizeof(TG) == 8) {
@@ -3337,27 +3312,22 @@ struct EngineT : Engine {
       xsp = as<float>(xs_p32);
       xnr = as<float>(xnorm32);
     }
-    ctx->tile_pairs = 0;
-    while ((int)ctx->tile_ev.size() < 2) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      ctx->tile_ev.push_back(e);
-    }
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[0], st()));
+    if ((rc = ensure_tile_events(1))) return rc;
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->tile_ev[0], st()));
     rc = launch_leaf_tiles_one<TP, TG>(st(), as<TP>(linv_p), xsp, xnr, as<TP>(alpha), as<double>(pvar), as<double>(pmean),
                                       npad, dp / 4, cpad, kp, one);
     if (rc == 2) {
-      host_direct = nullptr;
+      call.one_launch_declined();
       return 2;
     }
     if (rc) return launch_status();
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[1], st()));
-    ctx->tile_pairs = ctx->timing ? 1 : 0;
-    one_pending = true;
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->tile_ev[1], st()));
+    call.tiles_recorded(plan.timed ? 1 : 0);
+    call.enqueued(BestKind::OneLaunch, nseg, mode);
     return launch_status();
   }
-  int try_one_launch(OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq) {
-    if (!small_calls || !one_launch || one_refused || total <= 0 || total > kSmallBestMaxRows || nseg > 16) return 2;
+  int try_one_launch(const BestPlan& plan, BestCall& call, OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq, int mode) {
+    if (!small_calls || !one_launch || !plan.one_launch || total <= 0 || total > kSmallBestMaxRows || nseg > 16) return 2;
     if (npad != 128 && npad != 256) return 2;
     // measured (tools/micro/one_dbg.py, float64, same box; wall us per best_ucb_grow call, one | three launches):
     // N = 52 / 162 rows 56.3 | 54.1, N = 100 / 1458 rows 61.0 | 59.8, N = 128 / 13122 rows 91.5 | 88.6, N = 256 / 4374 rows
@@ -3371,10 +3341,10 @@ struct EngineT : Engine {
       if (!gen_double()) {
         int rc = ensure_generation_inputs();
         if (rc) return rc;
-        return try_one_launch_t<float>(one, total, nseg, acq);
+        return try_one_launch_t<float>(plan, call, one, total, nseg, acq, mode);
       }
     }
-    return try_one_launch_t<double>(one, total, nseg, acq);
+    return try_one_launch_t<double>(plan, call, one, total, nseg, acq, mode);
   }
 
   // ---- screened calls (screen.hpp, screen.hip) ----------------------------------------------------------
@@ -3463,53 +3433,45 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
   // the whole screened call; the record (and the verdict) on their way to ovals and pinned host memory
-  int enqueue_best_screened(const void* dev, int64_t m, const AcqSpec& acq) {
+  int enqueue_best_screened(const BestPlan& plan, BestCall& call, const void* dev, int64_t m, const AcqSpec& acq) {
     int rc;
     hipStream_t s = st();
     const int64_t mpad = (m + kLeafPad - 1) / kLeafPad * kLeafPad;
     const int64_t cap = screen_cap_rows(mpad);
     if ((rc = ensure(best_pos, (size_t)kArgmaxBlocks * 8))) return rc;
-    ctx->tile_pairs = 0;
-    while ((int)ctx->tile_ev.size() < 2) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      ctx->tile_ev.push_back(e);
-    }
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->tile_ev[0], s));
+    if ((rc = ensure_tile_events(1))) return rc;
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->tile_ev[0], s));
     ctx->last_count[5] = ctx->last_count[6] = 0;  // (the mean pass parks nothing)
     if ((rc = enqueue_screen(dev, m, acq, false))) return rc;
     LeafFinalize fin{};
-    tile_span_open = true;
-    rc = score_device_leaves(screen_rows.p, GPSO_F32, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb),
-                             as<int64_t>(screen_ctl), &fin);
-    tile_span_open = false;
-    if (rc) return rc;
+    TileSpan span{plan.timed, true};
+    if ((rc = score_device_leaves(screen_rows.p, GPSO_F32, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb),
+                                  span, as<int64_t>(screen_ctl), &fin)))
+      return rc;
+    call.tiles_recorded(span.pairs);
     if (fin.part_var == nullptr) return ctx->fail(GPSO_E_STATE, "internal: the survivors of a screened call were not deferred");
     // (float generation: a NaN coordinate reaches the partial sums by itself, as it does in the unscreened call, whose fused
     // prologue leaves no norms to look at -- the record keeps that NaN's bits, not the finalize stage's own)
     fin.lnorm = nullptr;
-    host_direct = result_host((size_t)4 + 2);
+    double* host = result_host(plan, call, 1);
     // (the survivors' list as a keyed one of a single segment: no analytic slots, every row in the appended tail, key = the
     // leaf's index in the caller's batch -- the arg-max ranks and tie-breaks on it)
     launch_keyed_argmax(s, as<double>(omean), as<double>(ovar), as<double>(oucb), as<int64_t>(grow_key), m, 0, 1,
                         as<int64_t>(screen_ctl), argmax_blocks(cap, 1), best.p, as<int64_t>(best_pos), as<double>(ovals), &fin,
-                        host_direct, arm_token(true, 1), as<int64_t>(screen_ctl), cap);
-    screen_pending = true;
+                        host, arm_token(call, true, 1), as<int64_t>(screen_ctl), cap);
+    call.screened(dev, GPSO_F32, m, acq);  // (what a re-run takes: the caller keeps device leaves untouched until the record is read)
     ctx->last_count[0] = ctx->last_count[1] = m;
     return launch_status();
   }
 
   // per segment (mean, var, ucb, bit-cast index relative to the segment start) -> ovals; seg_off: host,
   // nseg + 1 entries over [0, m]
-  // may_screen: the caller can run the call again should a screened one be refused (device leaves, finish_best's verdict read)
-  int enqueue_best_leaves(const void* dev, int xs_dtype, int64_t m, const int64_t* seg_off, int nseg,
-                          const AcqSpec& acq, bool may_screen = false) {
+  // plan.screen: the caller can run the call again should a screened one be refused (device leaves, finish_best's verdict read)
+  int enqueue_best_leaves(const BestPlan& plan, BestCall& call, const void* dev, int xs_dtype, int64_t m, const int64_t* seg_off,
+                          int nseg, const AcqSpec& acq) {
     int rc;
-    one_pending = false;  // (a call whose result was never read -- gpso_shard_winners -- leaves nothing behind)
-    screen_pending = false;
-    if (!screen_rerun) ctx->last_count[7] = 0, ctx->last_count[8] = kScreenNone;
-    host_direct = nullptr;
-    call_token = 0.0;
+    call = BestCall::begun(plan);
+    if (!plan.is_rerun) ctx->last_count[7] = 0, ctx->last_count[8] = kScreenNone;
     hipStream_t s = st();
     if ((rc = ensure(omean, (size_t)m * 8))) return rc;
     if ((rc = ensure(ovar, (size_t)m * 8))) return rc;
@@ -3517,41 +3479,35 @@ struct EngineT : Engine {
     if ((rc = ensure(segoff, (size_t)(nseg + 1) * 8))) return rc;
     if ((rc = ensure(best, (size_t)nseg * kArgmaxBlocks * kArgmaxPartialBytes))) return rc;
     if ((rc = ensure(ovals, (size_t)group_payload_doubles(nseg) * 8))) return rc;
-    std::vector<int64_t> so(nseg + 1);
-    if (seg_off) {
-      for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
-      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
-      for (int i = 0; i < nseg; ++i)
-        if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
-    } else {
-      if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
-      so[0] = 0;
-      so[1] = m;
-    }
+    std::vector<int64_t> so;
+    if ((rc = checked_segments(m, seg_off, nseg, so, "M"))) return rc;
     if (so != segoff_cache) {  // the segmentation rarely changes between calls: upload only then
       HIPCHECK(hipMemcpyAsync(segoff.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
       HIPCHECK(hipStreamSynchronize(s));
       segoff_cache = so;
     }
-    if (may_screen && screen_applies(xs_dtype, m, nseg, acq)) return enqueue_best_screened(dev, m, acq);
+    if (plan.screen && screen_applies(xs_dtype, m, nseg, acq)) return enqueue_best_screened(plan, call, dev, m, acq);
     if (m > 0) {  // one launch for the whole call where it applies
       OneLaunch one{};
       one.mode = 2;
       one.raw = dev;
       one.raw_f64 = xs_dtype == GPSO_F64 ? 1 : 0;
       one.seg_off = as<int64_t>(segoff);
-      if ((rc = try_one_launch(one, m, nseg, acq)) != 2) {
+      if ((rc = try_one_launch(plan, call, one, m, nseg, acq, 0)) != 2) {
         ctx->last_count[0] = ctx->last_count[1] = m;
         return rc;
       }
     }
     LeafFinalize fin{};
+    TileSpan span{plan.timed};
     if (m > 0)
-      if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin))) return rc;
+      if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), span, nullptr, &fin))) return rc;
+    call.tiles_recorded(span.pairs);
     // (round 4: the leaves of a one-chunk batch are finalised by the arg-max's first stage, and its second stage writes
     // the winners' records straight into the pinned host memory finish_best reads: two launches and a copy less per call)
-    host_direct = result_host((size_t)nseg * 4 + 2);
-    if (small_calls && fin.part_var != nullptr && m <= kSmallBestMaxRows && nseg <= 64) {
+    double* host = result_host(plan, call, nseg);
+    const bool small = small_calls && fin.part_var != nullptr && m <= kSmallBestMaxRows && nseg <= 64;
+    if (small) {
       // small batch: finalize and both arg-max stages in one launch of one workgroup
       SmallBest sb{};
       sb.fin = fin;
@@ -3559,29 +3515,29 @@ struct EngineT : Engine {
       sb.m = m;
       sb.nseg = nseg;
       sb.out_vals = as<double>(ovals);
-      sb.host_vals = host_direct;
-      sb.done_token = arm_token(true, nseg);
+      sb.host_vals = host;
+      sb.done_token = arm_token(call, true, nseg);
       launch_small_best(s, sb, false);
     } else {
       launch_seg_argmax(s, as<double>(omean), as<double>(ovar), as<double>(oucb), as<int64_t>(segoff),
-                        nseg, argmax_blocks(m, nseg), best.p, as<double>(ovals), fin.part_var ? &fin : nullptr, host_direct,
-                        arm_token(nseg == 1, nseg));
+                        nseg, argmax_blocks(m, nseg), best.p, as<double>(ovals), fin.part_var ? &fin : nullptr, host,
+                        arm_token(call, nseg == 1, nseg));
     }
+    call.enqueued(small ? BestKind::Small : BestKind::General, nseg, 0);
     ctx->last_count[0] = ctx->last_count[1] = m;
     return launch_status();
   }
 
   // the reference rows [row_lo, row_hi) of the sub-tree under every box, de-duplicated (grow.hip), scored;
   // per segment (mean, var, ucb, bit-cast REFERENCE row index) -> ovals, live row count -> ovals[nseg*4]
-  int enqueue_best_grow(const double* bounds, int nseg, int depth, int64_t row_lo, int64_t row_hi,
-                        const AcqSpec& acq) {
+  int enqueue_best_grow(const BestPlan& plan, BestCall& call, const double* bounds, int nseg, int depth, int64_t row_lo,
+                        int64_t row_hi, const AcqSpec& acq) {
     if (!bounds) return ctx->fail(GPSO_E_ARG, "bounds must not be NULL");
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
     if (depth < 0 || depth > 16) return ctx->fail(GPSO_E_ARG, "depth %d outside [0, 16]", depth);
     int rc;
-    one_pending = false;
-    host_direct = nullptr;
-    call_token = 0.0;
+    call = BestCall::begun(plan);
+    TileSpan span{plan.timed};
     hipStream_t s = st();
     const int64_t rows = gpso_grow_rows(depth);
     const int64_t uniq = grow_unique_before(row_hi) - grow_unique_before(row_lo);
@@ -3601,14 +3557,14 @@ struct EngineT : Engine {
     // value, growth + input scaling in one launch, tiles, one-workgroup finalize + arg-max writing pinned host memory --
     // three launches and no copy operation instead of two copies in, five launches and a copy back
     if (small_calls && cap > 0 && cap <= kSmallBestMaxRows && nseg <= 64 && (size_t)nseg * d * 2 <= (size_t)kGrowBoxDoubles) {
-      if (row_lo == 0 && row_hi == rows && !one_refused) {  // one launch for the whole call where it applies
+      if (row_lo == 0 && row_hi == rows && plan.one_launch) {  // one launch for the whole call where it applies
         OneLaunch one{};
         one.mode = 1;
         std::memcpy(one.boxes.b, bounds, bb);
         one.depth = depth;
         one.rows = rows;
         one.uniq = uniq;
-        if ((rc = try_one_launch(one, (int64_t)nseg * uniq, nseg, acq)) != 2) {
+        if ((rc = try_one_launch(plan, call, one, (int64_t)nseg * uniq, nseg, acq, 1)) != 2) {
           ctx->last_count[1] = cap;
           return rc;
         }
@@ -3633,10 +3589,10 @@ struct EngineT : Engine {
       if (gen_double())
         launch_grow_unique_prep<double>(s, gb, nseg, d, dp, depth, row_lo, row_hi, ls_dev(), as<double>(leaves_s), as<double>(lnorm), as<int64_t>(grow_key), extra);
       LeafFinalize fin{};
-      if ((rc = score_device_leaves(nullptr, GPSO_F64, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), nullptr, &fin, true)))
+      if ((rc = score_device_leaves(nullptr, GPSO_F64, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb), span, nullptr, &fin, true)))
         return rc;
+      call.tiles_recorded(span.pairs);
       if (fin.part_var == nullptr) return ctx->fail(GPSO_E_STATE, "internal: small growth call was not deferred");
-      host_direct = result_host((size_t)nseg * 4 + 2);
       SmallBest sb{};
       sb.fin = fin;
       sb.key = as<int64_t>(grow_key);
@@ -3646,9 +3602,10 @@ struct EngineT : Engine {
       sb.extra = extra;
       sb.nseg = nseg;
       sb.out_vals = as<double>(ovals);
-      sb.host_vals = host_direct;
-      sb.done_token = arm_token(true, nseg);
+      sb.host_vals = result_host(plan, call, nseg);
+      sb.done_token = arm_token(call, true, nseg);
       launch_small_best(s, sb, true);
+      call.enqueued(BestKind::Small, nseg, 1);
       ctx->last_count[1] = cap;
       return launch_status();
     }
@@ -3665,12 +3622,14 @@ struct EngineT : Engine {
     LeafFinalize fin{};
     if (cap > 0)
       if ((rc = score_device_leaves(leaves_raw.p, GPSO_F64, cap, acq, true, as<double>(omean), as<double>(ovar),
-                                    as<double>(oucb), as<int64_t>(live_cnt), &fin)))
+                                    as<double>(oucb), span, as<int64_t>(live_cnt), &fin)))
         return rc;
-    host_direct = result_host((size_t)nseg * 4 + 2);
+    call.tiles_recorded(span.pairs);
+    double* host = result_host(plan, call, nseg);
     launch_keyed_argmax(s, as<double>(omean), as<double>(ovar), as<double>(oucb), as<int64_t>(grow_key), rows, uniq,
                         nseg, as<int64_t>(live_cnt), argmax_blocks(cap, nseg), best.p, as<int64_t>(best_pos), as<double>(ovals),
-                        fin.part_var ? &fin : nullptr, host_direct, arm_token(nseg == 1, nseg));
+                        fin.part_var ? &fin : nullptr, host, arm_token(call, nseg == 1, nseg));
+    call.enqueued(BestKind::General, nseg, 1);
     ctx->last_count[1] = cap;
     return launch_status();
   }
@@ -3700,17 +3659,18 @@ struct EngineT : Engine {
       for (int i = 0; i < nseg; ++i) base[(size_t)r * nseg + i] = std::min(std::max(so[i], rlo), rhi) - so[i];
     }
   }
-  int global_segments(int64_t m_global, const int64_t* seg_off, int nseg, std::vector<int64_t>& so) {
+  // seg_off (host, nseg + 1 entries over [0, m], NULL: one segment), checked -> so
+  int checked_segments(int64_t m, const int64_t* seg_off, int nseg, std::vector<int64_t>& so, const char* m_name = "the global M") {
     so.resize(nseg + 1);
     if (seg_off) {
       for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
-      if (so[0] != 0 || so[nseg] != m_global) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at the global M");
+      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at %s", m_name);
       for (int i = 0; i < nseg; ++i)
         if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
     } else {
       if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
       so[0] = 0;
-      so[1] = m_global;
+      so[1] = m;
     }
     return GPSO_OK;
   }
@@ -3729,7 +3689,8 @@ struct EngineT : Engine {
   }
   // local half of gpso_best_ucb_sharded for (rank, world): rows shard_range(m_global, rank, world) of the batch ->
   // this rank's per-segment winners in ovals (indices relative to the LOCAL piece of each segment), status slot 0
-  int sharded_local(int rank, int world, const void* xs, int xs_dtype, int xs_mem, int64_t m_local, int64_t m_global,
+  // (plan: BestPlan::group_half -- the general sequences for leaves, the sequences with the append counter for grown calls)
+  int sharded_local(const BestPlan& plan, BestCall& call, int rank, int world, const void* xs, int xs_dtype, int xs_mem, int64_t m_local, int64_t m_global,
                     const int64_t* seg_off, int nseg, double varsigma) {
     int rc = check_predict_args(xs, xs_dtype, xs_mem, m_local);
     if (rc) return rc;
@@ -3739,26 +3700,20 @@ struct EngineT : Engine {
       return ctx->fail(GPSO_E_ARG, "rank %d of %d must pass rows [%lld, %lld) of the %lld leaves (gpso_shard_range), got %lld rows",
                        rank, world, (long long)lo, (long long)hi, (long long)m_global, (long long)m_local);
     std::vector<int64_t> so, sl(nseg + 1);
-    if ((rc = global_segments(m_global, seg_off, nseg, so))) return rc;
+    if ((rc = checked_segments(m_global, seg_off, nseg, so))) return rc;
     // local segmentation: the part of every global segment inside [lo, hi)
     for (int i = 0; i <= nseg; ++i) sl[i] = std::min(std::max(so[i], lo), hi) - lo;
     const void* dev = nullptr;
     if (m_local > 0 && (rc = stage_leaves(xs, xs_dtype, xs_mem, m_local, &dev))) return rc;
-    one_refused = true;  // (the status slot of a group payload belongs to the group's verdict: the general sequences)
-    rc = enqueue_best_leaves(dev, xs_dtype, m_local, sl.data(), nseg, varsigma);
-    one_refused = false;
-    return rc;
+    return enqueue_best_leaves(plan, call, dev, xs_dtype, m_local, sl.data(), nseg, varsigma);
   }
-  int sharded_local_grow(int rank, int world, const double* bounds, int nseg, int depth, double varsigma) {
+  int sharded_local_grow(const BestPlan& plan, BestCall& call, int rank, int world, const double* bounds, int nseg, int depth, double varsigma) {
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_broadcast_posterior first");
     int rc = precision_gate();
     if (rc) return rc;
     int64_t lo, hi;
     shard_range(gpso_grow_rows(depth), rank, world, &lo, &hi);
-    one_refused = true;  // (a group payload has no way to ask for a re-run: the sequences with the append counter)
-    rc = enqueue_best_grow(bounds, nseg, depth, lo, hi, varsigma);
-    one_refused = false;
-    return rc;
+    return enqueue_best_grow(plan, call, bounds, nseg, depth, lo, hi, varsigma);
   }
   // after the local half: on failure replace whatever it left in ovals by "no winner" rows and the status
   // (on success the arg-max kernels have written the status slot themselves: no host step on the fast path)
@@ -3782,66 +3737,77 @@ struct EngineT : Engine {
   }
   // multi-GPU: all-gather every rank's payload and fold the winners with the arg-max rule on (ucb, global index)
   // and the statuses with min; base = wbase (uploaded before the local half) or none.  Result -> ovals2.
-  int exchange_winners(int nseg, bool with_base) {
-    RcclApi& R = RcclApi::get();
+  int exchange_winners(const BestPlan& plan, BestCall& call, int nseg, bool with_base) {
     hipStream_t s = st();
-    const int pd = group_payload_doubles(nseg);
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[6], s));
-    RCCLCHECK(R.AllGather(ovals.p, gath.p, (size_t)pd, ncclDouble, ctx->comm, s));
-    // (the fold writes the group's records straight into the pinned memory finish_best reads: no copy operation behind it)
-    host_direct = result_host((size_t)nseg * 4 + 2);
-    launch_reduce_winners(s, as<double>(gath), with_base ? as<int64_t>(wbase) : nullptr, ctx->world, nseg, pd,
-                          as<double>(ovals2), host_direct, arm_token(nseg <= 64, nseg));
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[7], s));
-    coll_timed = ctx->timing;
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[6], s));
+    RCCLCHECK(RcclApi::get().AllGather(ovals.p, gath.p, (size_t)group_payload_doubles(nseg), ncclDouble, ctx->comm, s));
+    enqueue_fold(plan, call, ctx->world, nseg, with_base, plan.timed);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[7], s));
     return launch_status();
   }
+  // gath [world] payloads -> ovals2 and, straight from the kernel, the pinned memory finish_best reads
+  void enqueue_fold(const BestPlan& plan, BestCall& call, int world, int nseg, bool with_base, bool collective_recorded) {
+    double* host = result_host(plan, call, nseg);
+    launch_reduce_winners(st(), as<double>(gath), with_base ? as<int64_t>(wbase) : nullptr, world, nseg, group_payload_doubles(nseg),
+                          as<double>(ovals2), host, arm_token(call, nseg <= 64, nseg));
+    call.folded(nseg, collective_recorded);
+  }
 
-  // one read-back of nseg x (mean, var, ucb, index) [+ the live row count] [+ the group's verdict], then the host
-  // wait.  mode 0: winners only; 1: + live count -> last_count[0]; 2: a folded group payload -- *verdict_out: the worst
-  // status of the group (*who: the rank it came from); the outputs are only written when that is GPSO_OK
-  int finish_best(const DevBuf& src, int nseg, int mode, int64_t* idx, double* mean, double* var, double* ucb,
+  // Consumes the record: the host wait, then nseg x (mean, var, ucb, index) [+ the live row count] [+ the group's verdict]
+  // out of the pinned memory the call's last kernel wrote.  done: a ticket's completion event (NULL: the whole stream).
+  // call.mode 0: winners only; 1: + live count -> last_count[0]; 2: a folded group payload -- *verdict_out: the worst status
+  // of the group (*who: its rank); outputs written only when that is GPSO_OK.  Returns 1: finish_or_rerun
+  int finish_best(BestCall& in_flight, hipEvent_t done, int64_t* idx, double* mean, double* var, double* ucb,
                   int* verdict_out = nullptr, int64_t* who = nullptr) {
+    const BestCall call = in_flight.consumed();
     hipStream_t s = st();
-    const bool one = one_pending, screened = screen_pending;
-    one_pending = screen_pending = false;
-    const size_t doubles = (size_t)nseg * 4 + ((mode == 2 || one || screened) ? 2 : mode);
-    double* vals = ctx->pinned_scratch(doubles);
-    if (!vals) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    // (mode 0 / 1: the arg-max's second stage has written the records into this very memory: no copy operation)
-    const bool direct = host_direct != nullptr && host_direct == vals && src.p == (mode == 2 ? ovals2.p : ovals.p);
-    host_direct = nullptr;
-    if (!direct) HIPCHECK(hipMemcpyAsync(vals, src.p, doubles * 8, hipMemcpyDeviceToHost, s));
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-    const double token = call_token;
-    call_token = 0.0;
-    if (direct && token != 0.0 && !ctx->timing) HIPCHECK(ctx->wait_token(&vals[4 * nseg + 2], token, s));
+    const int nseg = call.nseg;
+    double* vals = call.host;
+    if (vals == nullptr) {  // (no pinned memory when the call was enqueued: a copy operation)
+      if (!(vals = ctx->pinned_scratch((size_t)nseg * 4 + 2))) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+      HIPCHECK(hipMemcpyAsync(vals, call.mode == 2 ? ovals2.p : ovals.p, ((size_t)nseg * 4 + 2) * 8, hipMemcpyDeviceToHost, s));
+      done = nullptr;
+    }
+    if (call.timed) HIPCHECK(hipEventRecord(ctx->ev[3], s));
+    if (call.token != 0.0) HIPCHECK(ctx->wait_token(&vals[4 * nseg + 2], call.token, s));
+    else if (done != nullptr) HIPCHECK(ctx->wait_event(done));
     else HIPCHECK(ctx->wait(s));
     int rc;
     if ((rc = launch_status())) return rc;
-    collect_tile_ms();
+    collect_tile_ms(call.timed, call.tile_pairs);
     float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-    if (coll_timed && hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]) == hipSuccess) ctx->last_ms[3] = ms;
-    coll_timed = false;
-    // (a centre child does not repeat its parent: the caller re-runs.  Only where a re-run exists -- a folded group
-    // payload keeps the GROUP's verdict in this slot, and its half was enqueued with the one-launch kernel refused)
-    if (one && mode != 2 && vals[4 * nseg + 1] != 0.0) return 1;
-    if (screened && (rc = screen_verdict(vals))) return rc;
-    if (mode == 2) {
+    if (call.timed && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
+    if (call.coll_timed && hipEventElapsedTime(&ms, ctx->ev[6], ctx->ev[7]) == hipSuccess) ctx->last_ms[3] = ms;
+    // (a centre child does not repeat its parent: the caller re-runs)
+    if (call.kind == BestKind::OneLaunch && vals[4 * nseg + 1] != 0.0) return 1;
+    if (call.kind == BestKind::Screened) {
+      ctx->last_count[0] = ctx->last_count[1] = call.screen.m;  // (a ticket: other calls have run since it was enqueued)
+      if ((rc = screen_verdict(vals))) return rc;
+    }
+    if (call.mode == 2) {
       const int verdict = (int)vals[4 * nseg + 1];
       if (verdict_out) *verdict_out = verdict;
       if (who) std::memcpy(who, &vals[4 * nseg], 8);
       if (verdict != GPSO_OK) return GPSO_OK;  // (outputs untouched; the caller turns the verdict into its return value)
     }
-    for (int i = 0; i < nseg; ++i) {
+    for (int i = 0; i < nseg; ++i) {  // (the one read-out: a ticket's end comes through here too)
       if (idx) std::memcpy(&idx[i], &vals[4 * i + 3], 8);
       if (mean) mean[i] = vals[4 * i];
       if (var) var[i] = vals[4 * i + 1];
       if (ucb) ucb[i] = vals[4 * i + 2];
     }
-    if (mode == 1) std::memcpy(&ctx->last_count[0], &vals[4 * nseg], 8);
+    if (call.mode == 1) std::memcpy(&ctx->last_count[0], &vals[4 * nseg], 8);
     return GPSO_OK;
+  }
+  // finish; where the call asks for the general sequence (a screened call was refused -- its posterior is not screened again
+  // --, the one-launch kernel met a near-duplicate it has no slot for), enqueue it again under plan.rerun() and finish that
+  template <typename Enqueue>
+  int finish_or_rerun(const BestPlan& plan, BestCall& call, hipEvent_t done, Enqueue&& enqueue, int64_t* idx, double* mean,
+                      double* var, double* ucb) {
+    int rc = finish_best(call, done, idx, mean, var, ucb);
+    if (rc != 1) return rc;
+    if ((rc = enqueue(plan.rerun(), call))) return rc;
+    return finish_best(call, nullptr, idx, mean, var, ucb);
   }
   // a screened call's record (one segment): the survivors' count and the last kernel's verdict -> the counters; a refusal ends
   // screening on this posterior and returns 1 -- the caller runs the call again, which then takes the general sequence
@@ -3869,20 +3835,14 @@ struct EngineT : Engine {
     int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
     if (rc) return rc;
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
+    const BestPlan plan = BestPlan::synchronous(ctx->timing, xs_mem == GPSO_MEM_DEVICE);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
     const void* dev = nullptr;
     if (m > 0 && (rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    const bool may_screen = xs_mem == GPSO_MEM_DEVICE;
-    if ((rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, may_screen))) return rc;
-    rc = finish_best(ovals, nseg, 0, idx, mean, var, ucb);
-    if (rc == 1) {  // a screened call was refused (its posterior is not screened again): the general sequence
-      screen_rerun = true;
-      rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, false);
-      screen_rerun = false;
-      if (rc) return rc;
-      rc = finish_best(ovals, nseg, 0, idx, mean, var, ucb);
-    }
-    return rc;
+    auto enqueue = [&](const BestPlan& p, BestCall& c) { return enqueue_best_leaves(p, c, dev, xs_dtype, m, seg_off, nseg, acq); };
+    BestCall call;
+    if ((rc = enqueue(plan, call))) return rc;
+    return finish_or_rerun(plan, call, nullptr, enqueue, idx, mean, var, ucb);
   }
 
   // ---- the non-blocking pair (round 5): gpso_best_ucb_begin / gpso_best_ucb_grow_begin enqueue a call and return a
@@ -3890,7 +3850,8 @@ struct EngineT : Engine {
   // the second is queued while the first still runs, so the GPU never idles over the host's round trip (pinned-memory
   // read, ctypes, Python: 42 us of a 0.77 ms step at C3, profiles/r04_step_timeline.txt).  Every call has its own pinned
   // result slot -- the arg-max kernels write their records there -- and a completion event; the device-side scratch is
-  // shared and ordered by the stream.  No timing events, no one-launch kernel (it may ask for a re-run).
+  // shared and ordered by the stream.  The ticket (best_call.hpp: BestTicket) holds the enqueue's record until _end consumes
+  // it.  BestPlan::ticket: no timing events, no one-launch kernel; a screened call carries what _end needs to run it again.
   int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
                      const double* bounds, int depth) override {
     const bool grown = bounds != nullptr;
@@ -3899,107 +3860,41 @@ struct EngineT : Engine {
     int rc = grown ? precision_gate() : check_predict_args(xs, xs_dtype, xs_mem, m);
     if (rc) return rc;
     // any free slot (the round-robin one first): calls may be ended out of order, so after begin A, begin B, end B the free slot
-    // is the one slot_next does NOT name -- refuse only when both hold a call
-    int k = ctx->slot_next;
-    if (ctx->slot_nseg[k] > 0) k = (k + 1) % gpso_ctx::kSlots;
-    if (ctx->slot_nseg[k] > 0)
+    // is the one next_ticket does NOT name -- refuse only when both hold a call
+    int k = ctx->next_ticket;
+    if (ctx->tickets[k].in_use) k = (k + 1) % gpso_ctx::kSlots;
+    if (ctx->tickets[k].in_use)
       return ctx->fail(GPSO_E_STATE, "two asynchronous best-UCB calls are already in flight: end one (gpso_best_ucb_end) first");
     if (ctx->slot_host == nullptr) {
       if (hipHostMalloc(reinterpret_cast<void**>(&ctx->slot_host), gpso_ctx::kSlots * gpso_ctx::kSlotDoubles * 8, hipHostMallocCoherent) != hipSuccess)
         return ctx->fail(GPSO_E_OOM, "pinned result slots");
       std::memset(ctx->slot_host, 0, gpso_ctx::kSlots * gpso_ctx::kSlotDoubles * 8);
-      for (auto& ev : ctx->slot_ev) HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+      for (auto& t : ctx->tickets) HIPCHECK(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
     }
-    {
-      // the enqueue runs untimed, into this call's own result slot, with the one-launch kernel refused: whichever way the
-      // region is left (an early return included), the context's synchronous calls find their state as it was
-      struct AsyncRegion {
-        EngineT* e;
-        bool timing_was;
-        AsyncRegion(EngineT* e_, double* slot) : e(e_), timing_was(e_->ctx->timing) {
-          e->ctx->timing = false;
-          e->result_slot = slot;
-          e->one_refused = true;
-        }
-        ~AsyncRegion() {
-          e->one_refused = false;
-          e->result_slot = nullptr;
-          e->host_direct = nullptr;
-          e->call_token = 0.0;
-          e->ctx->timing = timing_was;
-        }
-      } region(this, ctx->slot_host + (size_t)k * gpso_ctx::kSlotDoubles);
-      if (grown) {
-        rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq);
-      } else {
-        const void* dev = nullptr;
-        if (m > 0) rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev);
-        if (rc == GPSO_OK) rc = enqueue_best_leaves(dev, xs_dtype, m, seg_off, nseg, acq, xs_mem == GPSO_MEM_DEVICE);
-      }
-      ctx->slot_token[k] = call_token;
-      // (a screened call: what _end needs to run it again.  The caller keeps device leaves untouched until then)
-      ctx->slot_screen[k].on = screen_pending;
-      ctx->slot_screen[k].xs = xs;
-      ctx->slot_screen[k].xs_dtype = xs_dtype;
-      ctx->slot_screen[k].m = m;
-      ctx->slot_screen[k].acq = acq;
-      screen_pending = false;
+    const BestPlan plan = BestPlan::ticket(ctx->slot_host + (size_t)k * gpso_ctx::kSlotDoubles, xs_mem == GPSO_MEM_DEVICE);
+    BestCall call;
+    if (grown) {
+      rc = enqueue_best_grow(plan, call, bounds, nseg, depth, 0, gpso_grow_rows(depth), acq);
+    } else {
+      const void* dev = nullptr;
+      if (m > 0) rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev);
+      if (rc == GPSO_OK) rc = enqueue_best_leaves(plan, call, dev, xs_dtype, m, seg_off, nseg, acq);
     }
     if (rc) return rc;
     if (xs_mem == GPSO_MEM_HOST && !grown && m > 0) HIPCHECK(hipStreamSynchronize(st()));  // (the caller's host leaves are free again on return)
-    HIPCHECK(hipEventRecord(ctx->slot_ev[k], st()));
-    ctx->slot_nseg[k] = nseg;
-    ctx->slot_mode[k] = grown ? 1 : 0;
-    ctx->slot_next = (k + 1) % gpso_ctx::kSlots;
+    HIPCHECK(hipEventRecord(ctx->tickets[k].ev, st()));
+    ctx->tickets[k].store(call);
+    ctx->next_ticket = (k + 1) % gpso_ctx::kSlots;
     return k;
   }
+  // (a refused screened call runs the general sequence now, behind whatever the stream still holds, untimed like every ticket)
   int best_ucb_end(int ticket, int64_t* idx, double* mean, double* var, double* ucb) override {
-    if (ticket < 0 || ticket >= gpso_ctx::kSlots || ctx->slot_nseg[ticket] <= 0)
+    if (ticket < 0 || ticket >= gpso_ctx::kSlots || !ctx->tickets[ticket].in_use)
       return ctx->fail(GPSO_E_ARG, "ticket %d names no asynchronous call in flight", ticket);
-    const int nseg = ctx->slot_nseg[ticket];
-    ctx->slot_nseg[ticket] = 0;
-    const double* vals = ctx->slot_host + (size_t)ticket * gpso_ctx::kSlotDoubles;
-    // the call's completion token where its last kernel writes one, else its own event: spin (the thread is blocked here
-    // anyway), then block
-    const auto t0 = std::chrono::steady_clock::now();
-    if (ctx->slot_token[ticket] != 0.0) {
-      HIPCHECK(ctx->wait_token(&vals[4 * nseg + 2], ctx->slot_token[ticket], st()));
-    } else
-    for (int it = 0;; ++it) {
-      const hipError_t e = hipEventQuery(ctx->slot_ev[ticket]);
-      if (e == hipSuccess) break;
-      if (e != hipErrorNotReady) return ctx->fail(GPSO_E_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
-      if ((it & 63) == 63 && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 20.0) {
-        HIPCHECK(hipEventSynchronize(ctx->slot_ev[ticket]));
-        break;
-      }
-    }
-    int rc;
-    if ((rc = launch_status())) return rc;
-    if (ctx->slot_screen[ticket].on) {
-      ctx->slot_screen[ticket].on = false;
-      ctx->last_count[0] = ctx->last_count[1] = ctx->slot_screen[ticket].m;
-      if (screen_verdict(vals) != 0) {
-        // refused: the general sequence, now, behind whatever the stream still holds (untimed, like every asynchronous call)
-        const gpso_ctx::SlotScreen sc = ctx->slot_screen[ticket];
-        const bool timing_was = ctx->timing;
-        ctx->timing = false;
-        screen_rerun = true;
-        rc = enqueue_best_leaves(sc.xs, sc.xs_dtype, sc.m, nullptr, 1, sc.acq, false);
-        screen_rerun = false;
-        if (rc == GPSO_OK) rc = finish_best(ovals, 1, 0, idx, mean, var, ucb);
-        ctx->timing = timing_was;
-        return rc;
-      }
-    }
-    for (int i = 0; i < nseg; ++i) {
-      if (idx) std::memcpy(&idx[i], &vals[4 * i + 3], 8);
-      if (mean) mean[i] = vals[4 * i];
-      if (var) var[i] = vals[4 * i + 1];
-      if (ucb) ucb[i] = vals[4 * i + 2];
-    }
-    if (ctx->slot_mode[ticket] == 1) std::memcpy(&ctx->last_count[0], &vals[4 * nseg], 8);
-    return GPSO_OK;
+    BestCall call = ctx->tickets[ticket].take();
+    const BestCall::Rerun sc = call.screen;
+    auto again = [&](const BestPlan& p, BestCall& c) { return enqueue_best_leaves(p, c, sc.xs, sc.xs_dtype, sc.m, nullptr, 1, sc.acq); };
+    return finish_or_rerun(BestPlan::ticket(call.host, true), call, ctx->tickets[ticket].ev, again, idx, mean, var, ucb);
   }
 
   int need_comm() {
@@ -4023,20 +3918,29 @@ struct EngineT : Engine {
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
     if (m_global < 0) return ctx->fail(GPSO_E_ARG, "negative global leaf count");
     std::vector<int64_t> so, base;
-    if ((rc = global_segments(m_global, seg_off, nseg, so))) return rc;
+    if ((rc = checked_segments(m_global, seg_off, nseg, so))) return rc;
     if ((rc = ensure_group_buffers(nseg, ctx->world))) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
+    const BestPlan plan = BestPlan::group_half(ctx->timing);
+    BestCall call = BestCall::begun(plan);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
     segment_bases(m_global, so, nseg, ctx->world, base);
     int local = upload_base(base);
     if (local == GPSO_OK)
-      local = sharded_local(ctx->rank, ctx->world, xs, xs_dtype, xs_mem, m_local, m_global, seg_off, nseg, varsigma);
+      local = sharded_local(plan, call, ctx->rank, ctx->world, xs, xs_dtype, xs_mem, m_local, m_global, seg_off, nseg, varsigma);
+    return finish_group(plan, call, nseg, true, local, "gpso_best_ucb_sharded", idx, mean, var, ucb);
+  }
+  // behind the local half of a group call (grown: without bases): every rank publishes its payload, takes part in the
+  // exchange, finishes the folded record and returns the group's verdict
+  int finish_group(const BestPlan& plan, BestCall& call, int nseg, bool with_base, int local, const char* name, int64_t* idx,
+                   double* mean, double* var, double* ucb) {
     const std::string local_msg = ctx->err;
-    if ((rc = publish_local(nseg, local))) return rc;
-    if ((rc = exchange_winners(nseg, true))) return rc;
+    int rc, verdict = GPSO_OK;
     int64_t who = -1;
-    int verdict = GPSO_OK;
-    if ((rc = finish_best(ovals2, nseg, 2, idx, mean, var, ucb, &verdict, &who))) return rc;
-    return group_verdict(verdict, who, local, local_msg, "gpso_best_ucb_sharded");
+    if ((rc = publish_local(nseg, local))) return rc;
+    if ((rc = exchange_winners(plan, call, nseg, with_base))) return rc;
+    if ((rc = finish_best(call, nullptr, idx, mean, var, ucb, &verdict, &who))) return rc;
+    if (!with_base) ctx->last_count[0] = -1;  // (grown: the local live count stays on the device, no second read-back)
+    return group_verdict(verdict, who, local, local_msg, name);
   }
 
   // ------------------------------------------------------------------------------------------
@@ -4082,17 +3986,12 @@ struct EngineT : Engine {
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     int rc = precision_gate();
     if (rc) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
-    if ((rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq))) return rc;
-    rc = finish_best(ovals, nseg, 1, idx, mean, var, ucb);
-    if (rc == 1) {  // the one-launch kernel met a near-duplicate it has no slot for: the sequence with the append counter
-      one_refused = true;
-      rc = enqueue_best_grow(bounds, nseg, depth, 0, gpso_grow_rows(depth), acq);
-      one_refused = false;
-      if (rc) return rc;
-      rc = finish_best(ovals, nseg, 1, idx, mean, var, ucb);
-    }
-    return rc;
+    const BestPlan plan = BestPlan::synchronous(ctx->timing, false);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
+    auto enqueue = [&](const BestPlan& p, BestCall& c) { return enqueue_best_grow(p, c, bounds, nseg, depth, 0, gpso_grow_rows(depth), acq); };
+    BestCall call;
+    if ((rc = enqueue(plan, call))) return rc;
+    return finish_or_rerun(plan, call, nullptr, enqueue, idx, mean, var, ucb);
   }
 
   // The same on a group: every rank generates and scores the reference rows shard_range(rows, rank, world)
@@ -4106,55 +4005,54 @@ struct EngineT : Engine {
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
     if (depth < 0 || depth > 16) return ctx->fail(GPSO_E_ARG, "depth %d outside [0, 16]", depth);
     if ((rc = ensure_group_buffers(nseg, ctx->world))) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
-    const int local = sharded_local_grow(ctx->rank, ctx->world, bounds, nseg, depth, varsigma);
-    const std::string local_msg = ctx->err;
-    if ((rc = publish_local(nseg, local))) return rc;
-    if ((rc = exchange_winners(nseg, false))) return rc;
-    int64_t who = -1;
-    int verdict = GPSO_OK;
-    if ((rc = finish_best(ovals2, nseg, 2, idx, mean, var, ucb, &verdict, &who))) return rc;
-    ctx->last_count[0] = -1;  // (the local live count stays on the device: no second read-back)
-    return group_verdict(verdict, who, local, local_msg, "gpso_best_ucb_grow_sharded");
+    const BestPlan plan = BestPlan::group_half(ctx->timing);
+    BestCall call = BestCall::begun(plan);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
+    const int local = sharded_local_grow(plan, call, ctx->rank, ctx->world, bounds, nseg, depth, varsigma);
+    return finish_group(plan, call, nseg, false, local, "gpso_best_ucb_grow_sharded", idx, mean, var, ucb);
   }
 
   // ---- the two halves on their own, for an arbitrary (rank, world) and without a communicator: what a group of
   // `world` ranks computes can be replayed on ONE device, the all-gather replaced by the caller's concatenation ----
   int shard_winners(int rank, int world, const void* xs, int xs_dtype, int xs_mem, int64_t m_local, int64_t m_global,
                     const int64_t* seg_off, int nseg, double varsigma, double* payload) override {
-    ctx->tick_timing();
-    if (!payload) return ctx->fail(GPSO_E_ARG, "payload must not be NULL");
-    if (world < 1 || rank < 0 || rank >= world) return ctx->fail(GPSO_E_ARG, "rank %d / world %d", rank, world);
-    if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
-    int rc = ensure_group_buffers(nseg, world);
+    BestPlan plan;
+    BestCall call;
+    const int rc = half_begun(rank, world, nseg, payload, plan, call);
     if (rc) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
-    const int local = sharded_local(rank, world, xs, xs_dtype, xs_mem, m_local, m_global, seg_off, nseg, varsigma);
-    return payload_out(nseg, local, payload);
+    return payload_out(call, nseg, sharded_local(plan, call, rank, world, xs, xs_dtype, xs_mem, m_local, m_global, seg_off, nseg, varsigma), payload);
   }
   int shard_winners_grow(int rank, int world, const double* bounds, int nseg, int depth, double varsigma,
                          double* payload) override {
+    BestPlan plan;
+    BestCall call;
+    const int rc = half_begun(rank, world, nseg, payload, plan, call);
+    if (rc) return rc;
+    return payload_out(call, nseg, sharded_local_grow(plan, call, rank, world, bounds, nseg, depth, varsigma), payload);
+  }
+  // what the two share in front of the half: the arguments, the buffers, the half's plan, the call's first event
+  int half_begun(int rank, int world, int nseg, const double* payload, BestPlan& plan, BestCall& call) {
     ctx->tick_timing();
     if (!payload) return ctx->fail(GPSO_E_ARG, "payload must not be NULL");
     if (world < 1 || rank < 0 || rank >= world) return ctx->fail(GPSO_E_ARG, "rank %d / world %d", rank, world);
     if (nseg < 1) return ctx->fail(GPSO_E_ARG, "nseg must be >= 1");
-    int rc = ensure_group_buffers(nseg, world);
+    const int rc = ensure_group_buffers(nseg, world);
     if (rc) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
-    const int local = sharded_local_grow(rank, world, bounds, nseg, depth, varsigma);
-    return payload_out(nseg, local, payload);
+    plan = BestPlan::group_half(ctx->timing);
+    call = BestCall::begun(plan);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], st()));
+    return GPSO_OK;
   }
-  int payload_out(int nseg, int local, double* payload) {
-    one_pending = false;
-    host_direct = nullptr;
-    call_token = 0.0;
+  // consumes the half's record: the payload is copied from the device, whatever the half's last kernel wrote to pinned memory
+  int payload_out(BestCall& in_flight, int nseg, int local, double* payload) {
+    const BestCall call = in_flight.consumed();
     const std::string local_msg = ctx->err;
     int rc = publish_local(nseg, local);
     if (rc) return rc;
     const size_t pd = (size_t)group_payload_doubles(nseg);
     HIPCHECK(hipMemcpyAsync(payload, ovals.p, pd * 8, hipMemcpyDeviceToHost, st()));
     HIPCHECK(hipStreamSynchronize(st()));
-    collect_tile_ms();
+    collect_tile_ms(call.timed, call.tile_pairs);
     ctx->err = local_msg;
     return local;  // (the payload carries the same status in its last slot)
   }
@@ -4169,23 +4067,23 @@ struct EngineT : Engine {
     int rc = ensure_group_buffers(nseg, world);
     if (rc) return rc;
     hipStream_t s = st();
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+    const BestPlan plan = BestPlan::synchronous(ctx->timing, false);
+    if (plan.timed) HIPCHECK(hipEventRecord(ctx->ev[2], s));
     const bool with_base = m_global >= 0;
     if (with_base) {
       std::vector<int64_t> so, base;
-      if ((rc = global_segments(m_global, seg_off, nseg, so))) return rc;
+      if ((rc = checked_segments(m_global, seg_off, nseg, so))) return rc;
       segment_bases(m_global, so, nseg, world, base);
       if ((rc = upload_base(base))) return rc;
     }
     const int pd = group_payload_doubles(nseg);
     HIPCHECK(hipMemcpyAsync(gath.p, gathered, (size_t)world * pd * 8, hipMemcpyHostToDevice, s));
-    host_direct = result_host((size_t)nseg * 4 + 2);
-    launch_reduce_winners(s, as<double>(gath), with_base ? as<int64_t>(wbase) : nullptr, world, nseg, pd,
-                          as<double>(ovals2), host_direct, arm_token(nseg <= 64, nseg));
+    BestCall call = BestCall::begun(plan);
+    enqueue_fold(plan, call, world, nseg, with_base, false);
     if ((rc = launch_status())) return rc;
     int64_t who = -1;
     int verdict = GPSO_OK;
-    if ((rc = finish_best(ovals2, nseg, 2, idx, mean, var, ucb, &verdict, &who))) return rc;
+    if ((rc = finish_best(call, nullptr, idx, mean, var, ucb, &verdict, &who))) return rc;
     if (verdict != GPSO_OK)
       return ctx->fail(verdict, "gpso_fold_winners: the payload of rank %lld carries status %d", (long long)who, verdict);
     return GPSO_OK;
@@ -4710,8 +4608,8 @@ void gpso_destroy(gpso_ctx* ctx) {
   if (ctx->side_stream) (void)hipStreamDestroy(ctx->side_stream);
   if (ctx->inv_stream) (void)hipStreamDestroy(ctx->inv_stream);
   if (ctx->slot_host) (void)hipHostFree(ctx->slot_host);
-  for (auto& ev : ctx->slot_ev)
-    if (ev) (void)hipEventDestroy(ev);
+  for (auto& t : ctx->tickets)
+    if (t.ev) (void)hipEventDestroy(t.ev);
   // stream, events and pinned buffers go to the pool when they are complete and the pool has room (ContextPool)
   bool complete = ctx->own_stream != nullptr && ctx->ev_wait != nullptr;
   for (auto& ev : ctx->ev) complete = complete && ev != nullptr;

@@ -122,6 +122,23 @@ def inputs(name):
         Z1 = Z0 + 0.04 * np.random.default_rng(4).standard_normal(Z0.shape)
         return NS(X=X, y=y, d=d, m=m, lik=lik, u=u, Z0=Z0, Z1=Z1, s2=O.predictive_noise(lik, pp),
                   leaves=synthetic_leaves(257, d, seed=11))
+    if name == "calls_grown_tickets":  # N_pad = 256: the one-launch kernel applies to a float64 context
+        X, y, th = _problem(200, 3)
+        # grow_bounds(3) at depth 4: 87 bit-distinct rows against 81 analytic slots -- centre children that differ from their
+        # parents in the last bit, which the one-launch kernel has no slot for (it asks for the append-counter sequence).
+        # near: the ``arbitrary`` boxes of tests/test_gpu_parity.py::test_small_call_sequence_gives_the_bits_of_the_general_one
+        # for its (d, depth) = (3, 8) case (4 455 distinct rows against 4 374 slots)
+        rng = np.random.default_rng(8)
+        lo = rng.random((2, 3)) * 0.5
+        near = np.stack([lo, lo + 0.1 + 0.4 * rng.random((2, 3))], axis=2)
+        return NS(X=X, y=y, th=th, grad=False, d=3, leaves=synthetic_leaves(257, 3), bounds=grow_bounds(3), depth=4, near=near, near_depth=8)
+    if name in ("calls_screened", "calls_refused_ticket"):  # tests/test_gpu_screen.py: its shape, its theta, its batches
+        n, d = 768, 12
+        X, y = synthetic_problem(n, d, seed=0)
+        th = gpr.Theta("Matern52", 0.25 * np.sqrt(d) * np.ones(1), 1.0, 1e-3, float(y.mean()))
+        f32 = lambda m, seed: synthetic_leaves(m, d, seed=seed).astype(np.float32)  # noqa: E731
+        return NS(X=X, y=y, th=th, grad=False, d=d, leaves=synthetic_leaves(257, d), a1000=f32(1000, 11), b512=f32(512, 12),
+                  big=f32(BIG_M, 13), big_vs=50.0)
     raise KeyError(name)
 
 
@@ -307,6 +324,99 @@ def _svgp_stage(name):
     return stage
 
 
+# ---- call kinds crossed on one context (csrc/best_call.hpp) -----------------------------------------------
+# Synchronous, ticket and group-half calls, one-launch / small / general / screened sequences, in the orders in which one
+# call's record could be mistaken for another's.  Records that must be equal whatever the history are asserted equal here.
+def _device(eng, a):
+    """float32 leaves where a screened call reads them in place: on the device (a CPU double takes the array itself)."""
+    if getattr(eng, "HOST_LEAVES", False):
+        return a
+    import torch
+
+    return torch.from_numpy(a).cuda()
+
+
+def _counted(eng, call, counters):
+    rec = call()
+    return tuple(rec) + tuple(np.int64(eng.last_count(k)) for k in counters)
+
+
+def _same_record(obs, *keys):
+    for k in WIN:
+        words = [_bits(obs[f"{key}.{k}"]).tobytes() for key in keys]
+        assert all(w == words[0] for w in words), (keys, k, [obs[f"{key}.{k}"] for key in keys])
+
+
+def calls_grown_tickets(eng):
+    """A grown call; a ticket pair -- the same grown call and a ragged batch --, another grown call (near-duplicate centres)
+    while both are open, ended out of order; the grown call again."""
+    p, obs = inputs("calls_grown_tickets"), {}
+    _fit(eng, obs, p.X, p.y, p.th, p.grad)
+    posterior_observables(eng, obs, p.leaves, kinv=p.grad)
+    rows = WIN + ("scored", "asked")
+    grown = lambda: _counted(eng, lambda: eng.best_ucb_grow(p.bounds, p.depth, VS), (0, 1))  # noqa: E731
+    _try(obs, "grow", grown, rows)
+    t_grow = eng.best_ucb_grow_begin(p.bounds, p.depth, VS)
+    t_leaves = eng.best_ucb_begin(p.leaves, VS, SEG_RAGGED)
+    _try(obs, "grow_near", lambda: _counted(eng, lambda: eng.best_ucb_grow(p.near, p.near_depth, VS), (0, 1)), rows)
+    _try(obs, "best_ucb", lambda: eng.best_ucb_end(t_leaves), WIN)
+    _try(obs, "grow_ticket", lambda: _counted(eng, lambda: eng.best_ucb_end(t_grow), (0,)), WIN + ("scored",))
+    _try(obs, "grow_again", grown, rows)
+    _same_record(obs, "grow", "grow_ticket", "grow_again")
+    assert obs["grow.scored"] == obs["grow_ticket.scored"] == obs["grow_again.scored"]
+    return obs
+
+
+SCREEN_ACCEPTED, SCREEN_REFUSED = 1, 2  # (pygpso_amd._lib's ids of last_count(8), restated)
+BIG_M = 24000  # tests/test_gpu_screen.py: with varsigma = 50 every leaf survives, more than a call on 256 CUs has room for
+SCREENED = WIN + ("survivors", "verdict")
+
+
+def calls_screened(eng):
+    """Every call screened (option 2): a ticket on 1 000 leaves, a synchronous call on 512 while it is open, its end; then
+    rank 0's half of the 1 000 -- whose record nobody finishes -- and the synchronous call on them straight behind it."""
+    p, obs = inputs("calls_screened"), {}
+    _fit(eng, obs, p.X, p.y, p.th, p.grad)
+    posterior_observables(eng, obs, p.leaves, kinv=p.grad)
+    a, b = _device(eng, p.a1000), _device(eng, p.b512)
+    eng.set_screen(2)
+    try:
+        t = eng.best_ucb_begin(a, VS)
+        _try(obs, "sync_512", lambda: _counted(eng, lambda: eng.best_ucb(b, VS), (7, 8)), SCREENED)
+        _try(obs, "ticket_1000", lambda: _counted(eng, lambda: eng.best_ucb_end(t), (7, 8)), SCREENED)
+        _try(obs, "half", lambda: eng.shard_winners(0, 2, a[:500], 1000, VS))
+        _try(obs, "sync_1000", lambda: _counted(eng, lambda: eng.best_ucb(a, VS), (7, 8)), SCREENED)
+    finally:
+        eng.set_screen(1)
+    _same_record(obs, "ticket_1000", "sync_1000")
+    assert obs["ticket_1000.survivors"] == obs["sync_1000.survivors"] and obs["ticket_1000.verdict"] == obs["sync_1000.verdict"]
+    return obs
+
+
+def calls_refused_ticket(eng):
+    """A screened call the launch has no room for, through a ticket, ended second behind a small accepted one: the record of
+    the call with the option off.  (Either verdict where the room is at least the batch, as tests/test_gpu_screen.py has it.)"""
+    p, obs = inputs("calls_refused_ticket"), {}
+    _fit(eng, obs, p.X, p.y, p.th, p.grad)
+    posterior_observables(eng, obs, p.leaves, kinv=p.grad)
+    a, big = _device(eng, p.a1000), _device(eng, p.big)
+    eng.set_screen(0)
+    try:
+        _try(obs, "off", lambda: eng.best_ucb(big, p.big_vs), WIN)
+        eng.set_screen(2)
+        cap = eng.screen_probe(big, p.big_vs)[3]["cap"]
+        t_small, t_big = eng.best_ucb_begin(a, VS), eng.best_ucb_begin(big, p.big_vs)
+        _try(obs, "small", lambda: _counted(eng, lambda: eng.best_ucb_end(t_small), (7, 8)), SCREENED)
+        _try(obs, "big", lambda: _counted(eng, lambda: eng.best_ucb_end(t_big), (7, 8)), SCREENED)
+    finally:
+        eng.set_screen(1)
+    _same_record(obs, "big", "off")
+    assert obs["big.verdict"] in (SCREEN_ACCEPTED, SCREEN_REFUSED) and (cap >= BIG_M or obs["big.verdict"] == SCREEN_REFUSED), (cap, obs["big.verdict"])
+    return obs
+
+
+# the dtype each runs in: the one-launch kernel needs native (double) predict math, the screen the default float kernels
+CALL_STAGES = {"float64": ("calls_grown_tickets",), "mixed": (), "float32": ("calls_screened", "calls_refused_ticket")}
 GPR_STAGES = ("gpr_small", "gpr_general", "gpr_nograd", "gpr_wide", "gpr_shrunk_pad", "append_in_place",
               "append_pad_crossing", "batch", "set_posterior", "failed_fit")
 VAR_STAGES = ("vgp_gauss", "vgp_studentt", "sgpr", "sgpr_small_m", "sgpr_moved", "svgp", "svgp_gauss_uz")
@@ -316,6 +426,7 @@ for _n in GPR_STAGES[:5]:
 for _n in GPR_STAGES[5:7]:
     STAGES[_n] = _append_stage(_n)
 STAGES.update(batch=batch, set_posterior=set_posterior, failed_fit=failed_fit)
+STAGES.update(calls_grown_tickets=calls_grown_tickets, calls_screened=calls_screened, calls_refused_ticket=calls_refused_ticket)
 for _n in VAR_STAGES[:2]:
     STAGES[_n] = _vgp_stage(_n)
 for _n in VAR_STAGES[2:5]:
@@ -327,7 +438,7 @@ NO_POSTERIOR = ("batch", "failed_fit")  # stages that leave no predict-ready pos
 
 def stages_for(dtype):
     """The variational and sparse families refuse float32 contexts by design."""
-    return GPR_STAGES if dtype == "float32" else GPR_STAGES + VAR_STAGES
+    return GPR_STAGES + CALL_STAGES[dtype] + (() if dtype == "float32" else VAR_STAGES)
 
 
 # ---- comparison -----------------------------------------------------------------------------------------------------

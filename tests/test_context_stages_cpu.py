@@ -157,6 +157,38 @@ class WholeSurfaceEngine(OracleEngine):
         got = [self.best_ucb(r, varsigma) for r in rows]
         return tuple(np.concatenate([g[j] for g in got]) for j in range(4))
 
+    # -- the call kinds (tests/context_stages.py: CALL_STAGES) pass through: a ticket holds the record of the blocking call,
+    # every screened call is accepted whole (the room is the batch), a half's payload is its winners' records behind one another
+    HOST_LEAVES = True
+
+    def best_ucb_begin(self, xs, varsigma, seg_off=None):
+        return self._open(self.best_ucb(xs, varsigma, seg_off))
+
+    def best_ucb_grow_begin(self, bounds, depth, varsigma):
+        return self._open(self.best_ucb_grow(bounds, depth, varsigma))
+
+    def _open(self, record):
+        self._tickets = getattr(self, "_tickets", {})
+        ticket = min(k for k in (0, 1) if k not in self._tickets)  # (a third call in flight: ValueError, a refusal)
+        self._tickets[ticket] = record
+        return ticket
+
+    def best_ucb_end(self, ticket):
+        return self._tickets.pop(ticket)
+
+    def set_screen(self, mode):
+        pass
+
+    def last_count(self, what=0):
+        return CS.SCREEN_ACCEPTED if what == 8 else 0
+
+    def screen_probe(self, xs, varsigma):
+        return None, None, None, {"survivors": len(xs), "threshold": -np.inf, "cap": len(xs)}
+
+    def shard_winners(self, rank, world, local_leaves, m_global, varsigma, seg_off=None):
+        idx, mean, var, ucb = self.best_ucb(local_leaves, varsigma, seg_off)
+        return np.concatenate([np.column_stack([mean, var, ucb, idx.astype(np.float64)]).reshape(-1), [0.0, 0.0]])
+
     # -- variational GP
     def vgp_set_likelihood(self, kind="Gaussian", df=3.0, n_gh=20):
         self.lik = (kind, df if kind == "StudentT" else None)
@@ -273,6 +305,32 @@ def test_all_seventeen_stages_run_and_return_their_observables(fresh_all):
     assert "bound.grad_z" in fresh_all["sgpr_moved"] and fresh_all["sgpr_moved"]["inducing.Z"].shape == (40, 3)
     assert {"q0.mu", "q1.mu", "q2.S", "elbo.grad_u", "delta"} <= set(fresh_all["svgp"])
     assert {"elbo.grad_z", "q1.mu"} <= set(fresh_all["svgp_gauss_uz"]) and fresh_all["svgp_gauss_uz"]["alpha"].shape == (9,)
+
+
+def test_the_call_stages_run_on_the_whole_surface_double_and_a_ticket_mix_up_is_reported():
+    """CALL_STAGES: every dtype's list is what stages_for adds; each stage runs on the pass-through, asserts its own equal
+    records, and returns the same observables after any other of them.  A double that hands a ticket the record of the call
+    begun BEFORE it fails the stage's own assertion."""
+    calls = [n for names in CS.CALL_STAGES.values() for n in names]
+    assert sorted(calls) == ["calls_grown_tickets", "calls_refused_ticket", "calls_screened"]
+    for dt in ("float64", "mixed", "float32"):
+        assert [n for n in CS.stages_for(dt) if n in calls] == list(CS.CALL_STAGES[dt])
+    fresh_calls = {n: CS.run_stage(WholeSurfaceEngine, n) for n in calls}
+    assert not any(isinstance(v, str) for obs in fresh_calls.values() for v in obs.values())
+    assert {"grow.idx", "grow_near.scored", "best_ucb.ucb", "grow_ticket.mean", "grow_again.asked"} <= set(fresh_calls["calls_grown_tickets"])
+    assert {"sync_512.verdict", "ticket_1000.survivors", "half", "sync_1000.idx"} <= set(fresh_calls["calls_screened"])
+    assert {"off.idx", "small.verdict", "big.ucb"} <= set(fresh_calls["calls_refused_ticket"])
+    assert fresh_calls["calls_grown_tickets"]["best_ucb.idx"][0] == -1  # (the ragged batch's empty segment, through the ticket)
+    assert CS.pair_mismatches(WholeSurfaceEngine, "calls_screened", ["calls_grown_tickets"], fresh_calls) == []
+    assert CS.pair_mismatches(WholeSurfaceEngine, "calls_grown_tickets", ["calls_refused_ticket"], fresh_calls) == []
+
+    class SwapsTickets(WholeSurfaceEngine):
+        def best_ucb_end(self, ticket):
+            other = 1 - ticket
+            return self._tickets.pop(other if other in self._tickets else ticket)
+
+    with pytest.raises((AssertionError, ValueError)):
+        CS.run_stage(SwapsTickets, "calls_grown_tickets")
 
 
 def test_a_walk_over_all_stages_passes_on_the_whole_surface_double(fresh_all):

@@ -155,3 +155,17 @@ def test_devbuf_header_on_its_own(tmp_path):
                     "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout == "devbuf_check: ok\n", (r.returncode, r.stdout, r.stderr)
+
+
+def test_best_call_header_on_its_own(tmp_path):
+    """tools/best_call_check.cpp -- csrc/best_call.hpp compiled by the host compiler alone -- passes its own checks: every plan
+    constructor and its rerun(), a BestCall after each enqueue kind, consumed() back to none, no token without a host
+    pointer, and a ticket that gives a stored call back unchanged."""
+    import shutil
+
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    exe = str(tmp_path / "best_call_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tools", "best_call_check.cpp"),
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "best_call_check: ok\n", (r.returncode, r.stdout, r.stderr)
