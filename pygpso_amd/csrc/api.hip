@@ -213,7 +213,7 @@ struct gpso_ctx {
   int dtype = GPSO_F64;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {};  // [0..1] spare, [2..3] predict-type call, [4..5] fit, [6..7] the collective of a sharded call
+  hipEvent_t ev[8] = {};  // [0..1] spare, [2..3] a point call (points_begin / points_end) or a best-UCB call (finish_best), [4..5] fit, [6..7] the collective of a sharded call
   std::vector<hipEvent_t> tile_ev;  // start/stop pairs around the leaf-tile kernel, one per chunk (how many were recorded: TileSpan)
   double last_ms[4] = {0, 0, 0, 0};
   bool timing = true;  // GPSO_OPT_TIMING: does the call in flight record the event pairs gpso_last_ms reads (two to four HIP calls)?
@@ -2507,7 +2507,6 @@ struct EngineT : Engine {
     hipStream_t s = st();
     span.pairs = 0;
     const int64_t keep_counts[3] = {ctx->last_count[3], ctx->last_count[5], ctx->last_count[6]};
-    const size_t in_elem = (xs_dtype == GPSO_F64) ? 8 : 4;
     const TG* xsp = nullptr;
     const TG* xnr = nullptr;
     if constexpr (sizeof(TG) == 8) {
@@ -2529,7 +2528,6 @@ struct EngineT : Engine {
       const int64_t mc = std::min<int64_t>(chunk, m - off);
       const int64_t mp = (mc + kLeafPad - 1) / kLeafPad * kLeafPad;
       const int64_t* m_live_c = (m_live != nullptr && nchunk > 1) ? as<int64_t>(live_cnt) + 1 + off / chunk : m_live;
-      const char* src = static_cast<const char*>(xs_dev) + (size_t)off * d * in_elem;
       // Round 5: the fp16-contraction kernels scale float leaves in their own prologue (one launch and one dependency gap
       // less per call: 12 us of a 740 us step at C3).  Only where nothing else reads the scaled copies: one chunk, all rows
       // live, the caller's leaves in float.  A NaN coordinate reaches the partial sums by itself on this path (no clamp in
@@ -2537,7 +2535,7 @@ struct EngineT : Engine {
       RawLeaves rawl{};
       if constexpr (kFloatPredict && sizeof(TG) == 4) {
         if (fuse_prep && use_bf16 && !prepared && xs_dtype == GPSO_F32 && nchunk == 1 && m_live_c == nullptr && c16_in_use(false)) {
-          rawl.x = reinterpret_cast<const float*>(src);
+          rawl.x = static_cast<const float*>(xs_dev) + off * d;
           rawl.ls = ls_dev();
           rawl.m = mc;
           rawl.d = d;
@@ -2548,10 +2546,8 @@ struct EngineT : Engine {
         // (nothing to launch)
       } else if (prepared) {
         if (nchunk != 1) return ctx->fail(GPSO_E_STATE, "internal: prepared leaves in more than one chunk");
-      } else if (xs_dtype == GPSO_F64) {
-        launch_prep_leaves<TG, double>(s, reinterpret_cast<const double*>(src), mc, mp, d, dp, ls_dev(), m_live_c, as<TG>(leaves_s), as<TG>(lnorm));
       } else {
-        launch_prep_leaves<TG, float>(s, reinterpret_cast<const float*>(src), mc, mp, d, dp, ls_dev(), m_live_c, as<TG>(leaves_s), as<TG>(lnorm));
+        prep_points<TG>(s, xs_dev, xs_dtype, off, mc, mp, m_live_c, as<TG>(leaves_s), as<TG>(lnorm));
       }
       if ((rc = ensure_tile_events(span.pairs + 1))) return rc;
       if (span.timed && !span.open) HIPCHECK(hipEventRecord(ctx->tile_ev[2 * span.pairs], s));
@@ -2783,60 +2779,78 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int check_predict_args(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
-    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
-    if (m < 0) return ctx->fail(GPSO_E_ARG, "negative leaf count");
+  // ---- the frame of a call that evaluates the resident posterior at points the caller gives: what
+  // such a call refuses about its points, who may read the dense double factor, what the call records, and the way from the
+  // caller's coordinates to scaled rows.  A new point call starts from these
+  static constexpr bool kDenseDouble = sizeof(TF) == 8;  // (GPSO_F64 and GPSO_MIXED contexts: predict_grad, joint, paths)
+  int check_points(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
     if (m > 0 && !xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
     if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
     if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
-    return precision_gate();
+    return GPSO_OK;
   }
-
-  int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var,
-              int out_mem) override {
-    ctx->tick_timing();
-    int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if (m == 0) return GPSO_OK;
-    if (!mean || !var) return ctx->fail(GPSO_E_ARG, "mean / var must not be NULL");
-    hipStream_t s = st();
+  int need_dense_factor(const char* who) {
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (res.post == Post::Adopted || !res.chol_valid)
+      return ctx->fail(GPSO_E_STATE, "%s needs the dense factor of the posterior: an adopted posterior may have travelled without it", who);
+    return refuse_if_async(who);
+  }
+  // open and close: last_ms[1] is the stream time between the two, and the counts and the time describe the same call.  The
+  // open comes after the call's last refusal (a refused call leaves nothing in flight); the close records before it waits
+  int points_begin(hipStream_t* stream) {
+    hipStream_t s = *stream = st();
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    double *md = mean, *vd = var;
-    if (out_mem == GPSO_MEM_HOST) {
-      if ((rc = ensure(omean, (size_t)m * 8))) return rc;
-      if ((rc = ensure(ovar, (size_t)m * 8))) return rc;
-      md = as<double>(omean);
-      vd = as<double>(ovar);
-    }
-    TileSpan span{ctx->timing};
-    if ((rc = score_device_leaves(dev, xs_dtype, m, 0.0, false, md, vd, nullptr, span))) return rc;
-    if (out_mem == GPSO_MEM_HOST) {
-      HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-    }
+    return GPSO_OK;
+  }
+  static constexpr int64_t kNoCounts = -1;  // (gpso_paths_draw: no points, the counts stay the last point call's)
+  int points_end(hipStream_t s, int64_t m) {
     if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
     HIPCHECK(ctx->wait(s));
-    collect_tile_ms(span.timed, span.pairs);
-    ctx->last_count[0] = ctx->last_count[1] = m;
+    if (m != kNoCounts) ctx->last_count[0] = ctx->last_count[1] = m;
     float ms = 0;
     if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
     return GPSO_OK;
   }
+  // rows off .. off + mc of the staged points (dtype xs_dtype) -> mpad scaled rows and their norms
+  template <typename TG>
+  void prep_points(hipStream_t s, const void* dev, int xs_dtype, int64_t off, int64_t mc, int64_t mpad, const int64_t* m_live, TG* ts,
+                   TG* norm) {
+    if (xs_dtype == GPSO_F64)
+      launch_prep_leaves<TG, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), m_live, ts, norm);
+    else
+      launch_prep_leaves<TG, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), m_live, ts, norm);
+  }
 
+  int check_predict_args(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
+    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
+    if (m < 0) return ctx->fail(GPSO_E_ARG, "negative leaf count");
+    int rc = check_points(xs, xs_dtype, xs_mem, m);
+    return rc ? rc : precision_gate();
+  }
+
+  int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var,
+              int out_mem) override {
+    return point_values(xs, xs_dtype, xs_mem, m, 0.0, false, mean, var, nullptr, out_mem);
+  }
   // gpso_predict with the acquisition column (acq.hpp) beside mean and var: the same tiles, the same finalize kernel --
   // mean / var are gpso_predict's bits, the column is what gpso_best_acq ranks by.  Outputs the caller does not want
   // stay in the context's own buffers
   int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
                  double* value, int out_mem) override {
+    return point_values(xs, xs_dtype, xs_mem, m, acq, true, mean, var, value, out_mem);
+  }
+  // the body of both: gpso_predict is gpso_predict_acq without the column (want_ucb false: nothing of it is allocated,
+  // computed or copied) and with both of its outputs required
+  int point_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, bool want_ucb, double* mean, double* var,
+                   double* value, int out_mem) {
     ctx->tick_timing();
     int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
     if (rc) return rc;
     if (m == 0) return GPSO_OK;
-    if (!mean && !var && !value) return ctx->fail(GPSO_E_ARG, "mean, var and value are all NULL");
-    hipStream_t s = st();
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
+    if (!want_ucb && (!mean || !var)) return ctx->fail(GPSO_E_ARG, "mean / var must not be NULL");
+    if (want_ucb && !mean && !var && !value) return ctx->fail(GPSO_E_ARG, "mean, var and value are all NULL");
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
     const void* dev = nullptr;
     if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
     const bool host = out_mem == GPSO_MEM_HOST;
@@ -2849,23 +2863,19 @@ struct EngineT : Engine {
       if ((rc = ensure(ovar, (size_t)m * 8))) return rc;
       vd = as<double>(ovar);
     }
-    if (host || !value) {
+    if (want_ucb && (host || !value)) {
       if ((rc = ensure(oucb, (size_t)m * 8))) return rc;
       ud = as<double>(oucb);
     }
     TileSpan span{ctx->timing};
-    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, vd, ud, span))) return rc;
+    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, want_ucb, md, vd, ud, span))) return rc;
     if (host) {
       if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
       if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
       if (value) HIPCHECK(hipMemcpyAsync(value, ud, (size_t)m * 8, hipMemcpyDeviceToHost, s));
     }
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-    HIPCHECK(ctx->wait(s));
+    if ((rc = points_end(s, m))) return rc;
     collect_tile_ms(span.timed, span.pairs);
-    ctx->last_count[0] = ctx->last_count[1] = m;
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
     return GPSO_OK;
   }
 
@@ -2875,70 +2885,52 @@ struct EngineT : Engine {
   // N_pad x chunk doubles whatever M is
   int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean, double* dvar,
                    int out_mem) override {
-    if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs a GPSO_F64 or GPSO_MIXED context (the dense factor in double)");
-    } else {
-      ctx->tick_timing();
-      if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs at least one test point (m=%lld)", (long long)m);
-      if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
-      if (!mean && !var && !dmean && !dvar) return ctx->fail(GPSO_E_ARG, "mean, var, dmean and dvar are all NULL");
-      if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
-      if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
-      if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
-      if (res.post == Post::Adopted || !res.chol_valid)
-        return ctx->fail(GPSO_E_STATE, "gpso_predict_grad needs the dense factor of the posterior: an adopted posterior may have travelled without it");
-      int rc = refuse_if_async("gpso_predict_grad");
-      if (rc) return rc;
-      const int64_t chunk = std::min<int64_t>(kPredictGradChunk, (m + 63) / 64 * 64);
-      if ((rc = ensure(pg_ts, (size_t)chunk * dp * 8))) return rc;
-      if ((rc = ensure(pg_norm, (size_t)chunk * 8))) return rc;
-      if ((rc = ensure(pg_work, predict_grad_workspace_doubles(npad, dp, chunk) * 8))) return rc;
-      const bool to_host = out_mem == GPSO_MEM_HOST;
-      double *md = mean, *vd = var, *dmd = dmean, *dvd = dvar;
-      if (to_host) {
-        if ((rc = ensure(pg_out, (size_t)m * (2 + 2 * (size_t)d) * 8))) return rc;
-        double* o = as<double>(pg_out);
-        md = mean ? o : nullptr;
-        vd = var ? o + m : nullptr;
-        dmd = dmean ? o + 2 * m : nullptr;
-        dvd = dvar ? o + 2 * m + m * d : nullptr;
-      }
-      hipStream_t s = st();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-      const void* dev = nullptr;
-      if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-      PredictGradLaunch g;
-      g.C = as<double>(linv); g.alpha = as<double>(alpha_f); g.xs = as<double>(xs64); g.ls = ls_dev();
-      g.ts = as<double>(pg_ts); g.n = n; g.npad = npad; g.d = d; g.dp = dp; g.kp = kp; g.work = as<double>(pg_work);
-      for (int64_t off = 0; off < m; off += chunk) {
-        const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
-        if (xs_dtype == GPSO_F64)
-          launch_prep_leaves<double, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
-                                             as<double>(pg_ts), as<double>(pg_norm));
-        else
-          launch_prep_leaves<double, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
-                                            as<double>(pg_ts), as<double>(pg_norm));
-        g.m = mc;
-        g.mean = md ? md + off : nullptr;
-        g.var = vd ? vd + off : nullptr;
-        g.dmean = dmd ? dmd + off * d : nullptr;
-        g.dvar = dvd ? dvd + off * d : nullptr;
-        if (launch_predict_grad(s, g) != 0) return launch_status();
-        if ((rc = launch_status())) return rc;
-      }
-      if (to_host) {
-        if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-        if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-        if (dmean) HIPCHECK(hipMemcpyAsync(dmean, dmd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
-        if (dvar) HIPCHECK(hipMemcpyAsync(dvar, dvd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
-      }
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-      HIPCHECK(ctx->wait(s));
-      ctx->last_count[0] = ctx->last_count[1] = m;  // (as gpso_predict: the counts and last_ms[1] describe the same call)
-      float ms = 0;
-      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-      return GPSO_OK;
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs a GPSO_F64 or GPSO_MIXED context (the dense factor in double)");
+    ctx->tick_timing();
+    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs at least one test point (m=%lld)", (long long)m);
+    int rc = check_points(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    if (!mean && !var && !dmean && !dvar) return ctx->fail(GPSO_E_ARG, "mean, var, dmean and dvar are all NULL");
+    if ((rc = need_dense_factor("gpso_predict_grad"))) return rc;
+    const int64_t chunk = std::min<int64_t>(kPredictGradChunk, (m + 63) / 64 * 64);
+    if ((rc = ensure(pg_ts, (size_t)chunk * dp * 8))) return rc;
+    if ((rc = ensure(pg_norm, (size_t)chunk * 8))) return rc;
+    if ((rc = ensure(pg_work, predict_grad_workspace_doubles(npad, dp, chunk) * 8))) return rc;
+    const bool to_host = out_mem == GPSO_MEM_HOST;
+    double *md = mean, *vd = var, *dmd = dmean, *dvd = dvar;
+    if (to_host) {
+      if ((rc = ensure(pg_out, (size_t)m * (2 + 2 * (size_t)d) * 8))) return rc;
+      double* o = as<double>(pg_out);
+      md = mean ? o : nullptr;
+      vd = var ? o + m : nullptr;
+      dmd = dmean ? o + 2 * m : nullptr;
+      dvd = dvar ? o + 2 * m + m * d : nullptr;
     }
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    PredictGradLaunch g;
+    g.C = as<double>(linv); g.alpha = as<double>(alpha_f); g.xs = as<double>(xs64); g.ls = ls_dev();
+    g.ts = as<double>(pg_ts); g.n = n; g.npad = npad; g.d = d; g.dp = dp; g.kp = kp; g.work = as<double>(pg_work);
+    for (int64_t off = 0; off < m; off += chunk) {
+      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pg_ts), as<double>(pg_norm));
+      g.m = mc;
+      g.mean = md ? md + off : nullptr;
+      g.var = vd ? vd + off : nullptr;
+      g.dmean = dmd ? dmd + off * d : nullptr;
+      g.dvar = dvd ? dvd + off * d : nullptr;
+      if (launch_predict_grad(s, g) != 0) return launch_status();
+      if ((rc = launch_status())) return rc;
+    }
+    if (to_host) {
+      if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      if (dmean) HIPCHECK(hipMemcpyAsync(dmean, dmd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+      if (dvar) HIPCHECK(hipMemcpyAsync(dvar, dvd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+    }
+    return points_end(s, m);
   }
 
   // ---- the joint predictive (joint.hip).  Like gpso_predict_grad it reads the dense fit-type factor,
@@ -2955,12 +2947,7 @@ struct EngineT : Engine {
     hipStream_t s = st();
     const void* dev = nullptr;
     if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    if (xs_dtype == GPSO_F64)
-      launch_prep_leaves<double, double>(s, static_cast<const double*>(dev), m, mc, d, dp, ls_dev(), nullptr, as<double>(pj_ts),
-                                         as<double>(pj_norm));
-    else
-      launch_prep_leaves<double, float>(s, static_cast<const float*>(dev), m, mc, d, dp, ls_dev(), nullptr, as<double>(pj_ts),
-                                        as<double>(pj_norm));
+    prep_points<double>(s, dev, xs_dtype, 0, m, mc, nullptr, as<double>(pj_ts), as<double>(pj_norm));
     PredictGradLaunch g;
     g.C = as<double>(linv); g.xs = as<double>(xs64); g.ts = as<double>(pj_ts); g.n = n; g.npad = npad; g.m = m; g.d = d; g.dp = dp;
     g.kp = kp; g.work = as<double>(pj_v);
@@ -2977,104 +2964,86 @@ struct EngineT : Engine {
     if (m < 1 || m > kPredictGradChunk)
       return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld test points (m=%lld): the joint covariance of more is out of scope", what,
                        (long long)kPredictGradChunk, (long long)m);
-    if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+    int rc = check_points(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
     if (!(diag_add == diag_add) || diag_add - diag_add != 0.0) return ctx->fail(GPSO_E_ARG, "diag_add must be finite");
-    if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
-    if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
-    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
-    if (res.post == Post::Adopted || !res.chol_valid)
-      return ctx->fail(GPSO_E_STATE, "%s needs the dense factor of the posterior: an adopted posterior may have travelled without it", what);
-    return refuse_if_async(what);
-  }
-  int joint_done(hipStream_t s, int64_t m) {
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-    HIPCHECK(ctx->wait(s));
-    ctx->last_count[0] = ctx->last_count[1] = m;  // (as gpso_predict_grad)
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-    return GPSO_OK;
+    return need_dense_factor(what);
   }
 
   int predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
                     int out_mem) override {
-    if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "gpso_predict_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    } else {
-      ctx->tick_timing();
-      if (!cov) return ctx->fail(GPSO_E_ARG, "cov must not be NULL");
-      int rc = joint_check("gpso_predict_joint", xs, xs_dtype, xs_mem, m, diag_add);
-      if (rc) return rc;
-      const bool to_host = out_mem == GPSO_MEM_HOST;
-      double *md = mean, *cd = cov;
-      if (to_host) {
-        if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
-        if ((rc = ensure(pj_sigma, (size_t)m * m * 8))) return rc;
-        md = mean ? as<double>(pj_mu) : nullptr;
-        cd = as<double>(pj_sigma);
-      }
-      hipStream_t s = st();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-      if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, md, cd, m, false))) return rc;
-      if (to_host) {
-        if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)m * m * 8, hipMemcpyDeviceToHost, s));
-      }
-      return joint_done(s, m);
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_predict_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    ctx->tick_timing();
+    if (!cov) return ctx->fail(GPSO_E_ARG, "cov must not be NULL");
+    int rc = joint_check("gpso_predict_joint", xs, xs_dtype, xs_mem, m, diag_add);
+    if (rc) return rc;
+    const bool to_host = out_mem == GPSO_MEM_HOST;
+    double *md = mean, *cd = cov;
+    if (to_host) {
+      if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+      if ((rc = ensure(pj_sigma, (size_t)m * m * 8))) return rc;
+      md = mean ? as<double>(pj_mu) : nullptr;
+      cd = as<double>(pj_sigma);
     }
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, md, cd, m, false))) return rc;
+    if (to_host) {
+      if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)m * m * 8, hipMemcpyDeviceToHost, s));
+    }
+    return points_end(s, m);
   }
 
   // Sigma (identity on the padding up to a multiple of 128) -> launch_potrf as vgp_chol uses it -> F = mu 1^T + Z L^T ->
   // the arg-max per draw.  One wait at the end; a failing pivot is reported then and the outputs hold nothing of use
   int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t ns,
                    double* samples, int64_t* best_idx, double* best_val) override {
-    if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "gpso_sample_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    } else {
-      ctx->tick_timing();
-      if (ns < 1 || ns > kJointMaxDraws)
-        return ctx->fail(GPSO_E_ARG, "gpso_sample_joint takes 1 to %lld draws a call (s=%lld)", (long long)kJointMaxDraws, (long long)ns);
-      if (!z) return ctx->fail(GPSO_E_ARG, "z must not be NULL");
-      if (!samples && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "samples, best_idx and best_val are all NULL");
-      int rc = joint_check("gpso_sample_joint", xs, xs_dtype, xs_mem, m, diag_add);
-      if (rc) return rc;
-      if (ns > ((int64_t)1 << 31) / m) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint: s * m above 2^31 (s=%lld, m=%lld)", (long long)ns, (long long)m);
-      const int64_t mpad = (m + kPadN - 1) / kPadN * kPadN;
-      const size_t mat = (size_t)mpad * mpad * 8;
-      for (DevBuf* b : {&pj_sigma, &pj_l, &pj_linv, &pj_cwork})
-        if ((rc = ensure(*b, mat))) return rc;
-      if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
-      if ((rc = ensure(pj_diag, (size_t)mpad * 8))) return rc;
-      if ((rc = ensure(pj_info, 256))) return rc;
-      if ((rc = ensure(pj_z, (size_t)ns * m * 8))) return rc;
-      if ((rc = ensure(pj_f, (size_t)ns * m * 8))) return rc;
-      if ((rc = ensure(pj_best, (size_t)ns * 16))) return rc;
-      int* info_host = reinterpret_cast<int*>(ctx->pinned_scratch(8));
-      if (!info_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-      hipStream_t s = st();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-      HIPCHECK(hipMemcpyAsync(pj_z.p, z, (size_t)ns * m * 8, hipMemcpyHostToDevice, s));
-      int* info = static_cast<int*>(pj_info.p);
-      launch_vgp_pad_identity(s, as<double>(pj_sigma), 0, mpad, info);  // (Sigma := I, info := INT_MAX; the tiles overwrite their part)
-      if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, as<double>(pj_mu), as<double>(pj_sigma), mpad, true)))
-        return rc;
-      HIPCHECK(hipMemsetAsync(pj_linv.p, 0, mat, s));
-      (void)launch_potrf<double>(s, as<double>(pj_sigma), as<double>(pj_l), as<double>(pj_linv), as<double>(pj_cwork), nullptr, m, mpad,
-                                 as<double>(pj_diag), info, -1, nullptr);
-      HIPCHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
-      launch_joint_draw(s, as<double>(pj_l), mpad, as<double>(pj_z), as<double>(pj_mu), m, ns, as<double>(pj_f));
-      int64_t* bi = as<int64_t>(pj_best);
-      double* bv = reinterpret_cast<double*>(bi + ns);
-      if (best_idx || best_val) launch_joint_argmax(s, as<double>(pj_f), m, ns, bi, bv);
-      if ((rc = launch_status())) return rc;
-      if (samples) HIPCHECK(hipMemcpyAsync(samples, pj_f.p, (size_t)ns * m * 8, hipMemcpyDeviceToHost, s));
-      if (best_idx) HIPCHECK(hipMemcpyAsync(best_idx, bi, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
-      if (best_val) HIPCHECK(hipMemcpyAsync(best_val, bv, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
-      if ((rc = joint_done(s, m))) return rc;
-      if (*info_host != INT_MAX)
-        return ctx->fail(GPSO_E_NOTPD, "gpso_sample_joint: Sigma + diag_add*I is not positive definite: Cholesky failed at pivot %d "
-                                       "(a larger diag_add -- jitter -- is the remedy)", *info_host);
-      return GPSO_OK;
-    }
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    ctx->tick_timing();
+    if (ns < 1 || ns > kJointMaxDraws)
+      return ctx->fail(GPSO_E_ARG, "gpso_sample_joint takes 1 to %lld draws a call (s=%lld)", (long long)kJointMaxDraws, (long long)ns);
+    if (!z) return ctx->fail(GPSO_E_ARG, "z must not be NULL");
+    if (!samples && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "samples, best_idx and best_val are all NULL");
+    int rc = joint_check("gpso_sample_joint", xs, xs_dtype, xs_mem, m, diag_add);
+    if (rc) return rc;
+    if (ns > ((int64_t)1 << 31) / m) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint: s * m above 2^31 (s=%lld, m=%lld)", (long long)ns, (long long)m);
+    const int64_t mpad = (m + kPadN - 1) / kPadN * kPadN;
+    const size_t mat = (size_t)mpad * mpad * 8;
+    for (DevBuf* b : {&pj_sigma, &pj_l, &pj_linv, &pj_cwork})
+      if ((rc = ensure(*b, mat))) return rc;
+    if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+    if ((rc = ensure(pj_diag, (size_t)mpad * 8))) return rc;
+    if ((rc = ensure(pj_info, 256))) return rc;
+    if ((rc = ensure(pj_z, (size_t)ns * m * 8))) return rc;
+    if ((rc = ensure(pj_f, (size_t)ns * m * 8))) return rc;
+    if ((rc = ensure(pj_best, (size_t)ns * 16))) return rc;
+    int* info_host = reinterpret_cast<int*>(ctx->pinned_scratch(8));
+    if (!info_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    HIPCHECK(hipMemcpyAsync(pj_z.p, z, (size_t)ns * m * 8, hipMemcpyHostToDevice, s));
+    int* info = static_cast<int*>(pj_info.p);
+    launch_vgp_pad_identity(s, as<double>(pj_sigma), 0, mpad, info);  // (Sigma := I, info := INT_MAX; the tiles overwrite their part)
+    if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, as<double>(pj_mu), as<double>(pj_sigma), mpad, true)))
+      return rc;
+    HIPCHECK(hipMemsetAsync(pj_linv.p, 0, mat, s));
+    (void)launch_potrf<double>(s, as<double>(pj_sigma), as<double>(pj_l), as<double>(pj_linv), as<double>(pj_cwork), nullptr, m, mpad,
+                               as<double>(pj_diag), info, -1, nullptr);
+    HIPCHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
+    launch_joint_draw(s, as<double>(pj_l), mpad, as<double>(pj_z), as<double>(pj_mu), m, ns, as<double>(pj_f));
+    int64_t* bi = as<int64_t>(pj_best);
+    double* bv = reinterpret_cast<double*>(bi + ns);
+    if (best_idx || best_val) launch_joint_argmax(s, as<double>(pj_f), m, ns, bi, bv);
+    if ((rc = launch_status())) return rc;
+    if (samples) HIPCHECK(hipMemcpyAsync(samples, pj_f.p, (size_t)ns * m * 8, hipMemcpyDeviceToHost, s));
+    if (best_idx) HIPCHECK(hipMemcpyAsync(best_idx, bi, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+    if (best_val) HIPCHECK(hipMemcpyAsync(best_val, bv, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+    if ((rc = points_end(s, m))) return rc;
+    if (*info_host != INT_MAX)
+      return ctx->fail(GPSO_E_NOTPD, "gpso_sample_joint: Sigma + diag_add*I is not positive definite: Cholesky failed at pivot %d "
+                                     "(a larger diag_add -- jitter -- is the remedy)", *info_host);
+    return GPSO_OK;
   }
 
   // ---- pathwise posterior draws (paths.hip).  Both calls read the dense fit-type factor, the scaled
@@ -3096,168 +3065,148 @@ struct EngineT : Engine {
   }
   int paths_draw_impl(bool variational, const char* who, const double* omega, const double* phase, int64_t f, const double* w,
                       const double* eps, int64_t ns) {
-    if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "%s needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)", who);
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "%s needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)", who);
+    ctx->tick_timing();
+    if (ns < 1 || ns > kPathsMaxDraws)
+      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld draws (s=%lld)", who, (long long)kPathsMaxDraws, (long long)ns);
+    if (f < 1 || f > kPathsMaxFeatures)
+      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld features (f=%lld)", who, (long long)kPathsMaxFeatures, (long long)f);
+    if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
+    if (!variational) {
+      if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
+        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
     } else {
-      ctx->tick_timing();
-      if (ns < 1 || ns > kPathsMaxDraws)
-        return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld draws (s=%lld)", who, (long long)kPathsMaxDraws, (long long)ns);
-      if (f < 1 || f > kPathsMaxFeatures)
-        return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld features (f=%lld)", who, (long long)kPathsMaxFeatures, (long long)f);
-      if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
-      if (!variational) {
-        if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
-          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
-      } else {
-        if (res.post == Post::Fitted) return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q draws from a variational posterior: a fitted exact GP takes gpso_paths_draw");
-        if (!(res.variational() && res.chol_valid))
-          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q needs a posterior installed by gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior on this context");
-        // (at present implied by the line above: q_factors is set with the kind and cleared only where the kind is -- no call
-        // overwrites Lf, beta or the root of q and keeps the posterior.  The flag is for the first call that does)
-        if (!res.q_factors)
-          return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q: the install's factors (Lu, beta, the root of q) are not resident any more: install again");
-      }
-      int rc = refuse_if_async(who);
-      if (rc) return rc;
-      if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
-          (eps && !all_finite(eps, (size_t)ns * n)))
-        return ctx->fail(GPSO_E_ARG, "%s: omega, phase, w and eps must be finite", who);
-      const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
-      PathSet& nx = pth_next;
-      if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
-      if ((rc = ensure(nx.phase, (size_t)f16 * 8))) return rc;
-      if ((rc = ensure(nx.w, (size_t)ns * f16 * 8))) return rc;
-      if ((rc = ensure(nx.vt, (size_t)spad * npad * 8))) return rc;
-      if (eps && (rc = ensure(pth_eps, (size_t)ns * n * 8))) return rc;
-      if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
-      if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
-      if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
-      if (variational && (rc = ensure(pth_x, (size_t)n64 * spad * 8))) return rc;
-      // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
-      std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
-      for (int64_t j = 0; j < f; ++j) {
-        std::memcpy(&ho[(size_t)j * dp], omega + (size_t)j * d, (size_t)d * 8);
-        hp[(size_t)j] = phase[j];
-      }
-      for (int64_t r = 0; r < ns; ++r) std::memcpy(&hw[(size_t)r * f16], w + (size_t)r * f, (size_t)f * 8);
-      hipStream_t s = st();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-      HIPCHECK(hipMemcpyAsync(nx.omega.p, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
-      HIPCHECK(hipMemcpyAsync(nx.phase.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, s));
-      HIPCHECK(hipMemcpyAsync(nx.w.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, s));
-      if (eps) HIPCHECK(hipMemcpyAsync(pth_eps.p, eps, (size_t)ns * n * 8, hipMemcpyHostToDevice, s));
-      PathsEvalLaunch g;  // Phi(X) w^T: the evaluation over the training rows, kernel part off
-      g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
-      g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
-      if (launch_paths_eval(s, g) != 0) return launch_status();
-      if (!variational) {
-        launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
-                           n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
-      } else {
-        launch_vgp_clean_lower(s, as<double>(Lf), as<double>(vB), n, npad, 1.0);
-        launch_trinv<double>(s, as<double>(vB), as<double>(vA), as<double>(work), npad);
-        const bool sgpr = res.post == Post::Sgpr;
-        const double* Q = sgpr ? as<double>(sgM2) : res.post == Post::Svgp ? as<double>(svq_S) : as<double>(vq_S);
-        launch_paths_solve_q(s, as<double>(vA), Q, sgpr, as<double>(alpha_f), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, n,
-                             npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(pth_x), as<double>(nx.vt));
-      }
-      if ((rc = launch_status())) return rc;
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-      HIPCHECK(ctx->wait(s));
-      nx.s = ns; nx.f = f; nx.ldw = f16;
-      std::swap(pth, pth_next);
-      res.paths_drawn();
-      float ms = 0;
-      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-      return GPSO_OK;
+      if (res.post == Post::Fitted) return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q draws from a variational posterior: a fitted exact GP takes gpso_paths_draw");
+      if (!(res.variational() && res.chol_valid))
+        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q needs a posterior installed by gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior on this context");
+      // (at present implied by the line above: q_factors is set with the kind and cleared only where the kind is -- no call
+      // overwrites Lf, beta or the root of q and keeps the posterior.  The flag is for the first call that does)
+      if (!res.q_factors)
+        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q: the install's factors (Lu, beta, the root of q) are not resident any more: install again");
     }
+    int rc = refuse_if_async(who);
+    if (rc) return rc;
+    if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
+        (eps && !all_finite(eps, (size_t)ns * n)))
+      return ctx->fail(GPSO_E_ARG, "%s: omega, phase, w and eps must be finite", who);
+    const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
+    PathSet& nx = pth_next;
+    if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
+    if ((rc = ensure(nx.phase, (size_t)f16 * 8))) return rc;
+    if ((rc = ensure(nx.w, (size_t)ns * f16 * 8))) return rc;
+    if ((rc = ensure(nx.vt, (size_t)spad * npad * 8))) return rc;
+    if (eps && (rc = ensure(pth_eps, (size_t)ns * n * 8))) return rc;
+    if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
+    if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
+    if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
+    if (variational && (rc = ensure(pth_x, (size_t)n64 * spad * 8))) return rc;
+    // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
+    std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
+    for (int64_t j = 0; j < f; ++j) {
+      std::memcpy(&ho[(size_t)j * dp], omega + (size_t)j * d, (size_t)d * 8);
+      hp[(size_t)j] = phase[j];
+    }
+    for (int64_t r = 0; r < ns; ++r) std::memcpy(&hw[(size_t)r * f16], w + (size_t)r * f, (size_t)f * 8);
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    HIPCHECK(hipMemcpyAsync(nx.omega.p, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(nx.phase.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemcpyAsync(nx.w.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, s));
+    if (eps) HIPCHECK(hipMemcpyAsync(pth_eps.p, eps, (size_t)ns * n * 8, hipMemcpyHostToDevice, s));
+    PathsEvalLaunch g;  // Phi(X) w^T: the evaluation over the training rows, kernel part off
+    g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
+    g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
+    if (launch_paths_eval(s, g) != 0) return launch_status();
+    if (!variational) {
+      launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
+                         n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
+    } else {
+      launch_vgp_clean_lower(s, as<double>(Lf), as<double>(vB), n, npad, 1.0);
+      launch_trinv<double>(s, as<double>(vB), as<double>(vA), as<double>(work), npad);
+      const bool sgpr = res.post == Post::Sgpr;
+      const double* Q = sgpr ? as<double>(sgM2) : res.post == Post::Svgp ? as<double>(svq_S) : as<double>(vq_S);
+      launch_paths_solve_q(s, as<double>(vA), Q, sgpr, as<double>(alpha_f), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, n,
+                           npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(pth_x), as<double>(nx.vt));
+    }
+    if ((rc = launch_status())) return rc;
+    if ((rc = points_end(s, kNoCounts))) return rc;
+    nx.s = ns; nx.f = f; nx.ldw = f16;
+    std::swap(pth, pth_next);
+    res.paths_drawn();
+    return GPSO_OK;
   }
 
   // M is worked off in chunks of kPathsChunk: values of one chunk [S][chunk], copied out and / or reduced into the running
   // winners per (draw, segment) before the next chunk overwrites them
   int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values, int out_mem,
                  int64_t* best_idx, double* best_val) override {
-    if constexpr (sizeof(TF) != 8) {
-      return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    ctx->tick_timing();
+    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs at least one point (m=%lld)", (long long)m);
+    int rc = check_points(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    if (!values && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "values, best_idx and best_val are all NULL");
+    if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+    if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "nseg=%d outside [1, 1024]", nseg);
+    if (!res.paths_valid)
+      return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
+    if ((rc = refuse_if_async("gpso_paths_eval"))) return rc;
+    std::vector<int64_t> so(nseg + 1);
+    if (seg_off) {
+      for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
+      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
+      for (int i = 0; i < nseg; ++i)
+        if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
     } else {
-      ctx->tick_timing();
-      if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs at least one point (m=%lld)", (long long)m);
-      if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
-      if (!values && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "values, best_idx and best_val are all NULL");
-      if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
-      if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
-      if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
-      if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "nseg=%d outside [1, 1024]", nseg);
-      if (!res.paths_valid)
-        return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
-      int rc = refuse_if_async("gpso_paths_eval");
-      if (rc) return rc;
-      std::vector<int64_t> so(nseg + 1);
-      if (seg_off) {
-        for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
-        if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
-        for (int i = 0; i < nseg; ++i)
-          if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
-      } else {
-        if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
-        so[0] = 0;
-        so[1] = m;
-      }
-      const bool want_best = best_idx || best_val;
-      const int64_t ns = pth.s, chunk = std::min<int64_t>(kPathsChunk, (m + 63) / 64 * 64);
-      if ((rc = ensure(pe_ts, (size_t)chunk * dp * 8))) return rc;
-      if ((rc = ensure(pe_norm, (size_t)chunk * 8))) return rc;
-      if ((rc = ensure(pe_vals, (size_t)ns * chunk * 8))) return rc;
-      if ((rc = ensure(pe_seg, (size_t)(nseg + 1) * 8))) return rc;
-      if ((rc = ensure(pe_best, (size_t)ns * nseg * 16))) return rc;
-      int64_t* bi = as<int64_t>(pe_best);
-      double* bv = reinterpret_cast<double*>(bi + ns * nseg);
-      std::vector<int64_t> hi_(want_best ? (size_t)ns * nseg : 0);
-      std::vector<double> hv_(want_best ? (size_t)ns * nseg : 0);
-      hipStream_t s = st();
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-      const void* dev = nullptr;
-      if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-      if (want_best) {
-        HIPCHECK(hipMemcpyAsync(pe_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
-        HIPCHECK(hipMemsetAsync(pe_best.p, 0xFF, (size_t)ns * nseg * 16, s));  // (index -1: no winner yet; the value a NaN)
-      }
-      PathsEvalLaunch g;
-      g.ts = as<double>(pe_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
-      g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
-      g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.out = as<double>(pe_vals); g.ldo = chunk;
-      for (int64_t off = 0; off < m; off += chunk) {
-        const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
-        if (xs_dtype == GPSO_F64)
-          launch_prep_leaves<double, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
-                                             as<double>(pe_ts), as<double>(pe_norm));
-        else
-          launch_prep_leaves<double, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), nullptr,
-                                            as<double>(pe_ts), as<double>(pe_norm));
-        g.m = mc;
-        if (launch_paths_eval(s, g) != 0) return launch_status();
-        if ((rc = launch_status())) return rc;
-        if (values)
-          HIPCHECK(hipMemcpy2DAsync(values + off, (size_t)m * 8, pe_vals.p, (size_t)chunk * 8, (size_t)mc * 8, (size_t)ns,
-                                    out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-        if (want_best) launch_paths_argmax(s, as<double>(pe_vals), chunk, off, mc, as<int64_t>(pe_seg), nseg, ns, bi, bv);
-      }
-      if (want_best) {
-        if ((rc = launch_status())) return rc;
-        HIPCHECK(hipMemcpyAsync(hi_.data(), bi, hi_.size() * 8, hipMemcpyDeviceToHost, s));
-        HIPCHECK(hipMemcpyAsync(hv_.data(), bv, hv_.size() * 8, hipMemcpyDeviceToHost, s));
-      }
-      if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-      HIPCHECK(ctx->wait(s));
-      for (size_t e = 0; e < hi_.size(); ++e) {  // indices relative to the segment start; an empty segment: -1 and a NaN
-        if (best_idx) best_idx[e] = hi_[e] < 0 ? -1 : hi_[e] - so[e % nseg];
-        if (best_val) best_val[e] = hv_[e];
-      }
-      ctx->last_count[0] = ctx->last_count[1] = m;
-      float ms = 0;
-      if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-      return GPSO_OK;
+      if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
+      so[0] = 0;
+      so[1] = m;
     }
+    const bool want_best = best_idx || best_val;
+    const int64_t ns = pth.s, chunk = std::min<int64_t>(kPathsChunk, (m + 63) / 64 * 64);
+    if ((rc = ensure(pe_ts, (size_t)chunk * dp * 8))) return rc;
+    if ((rc = ensure(pe_norm, (size_t)chunk * 8))) return rc;
+    if ((rc = ensure(pe_vals, (size_t)ns * chunk * 8))) return rc;
+    if ((rc = ensure(pe_seg, (size_t)(nseg + 1) * 8))) return rc;
+    if ((rc = ensure(pe_best, (size_t)ns * nseg * 16))) return rc;
+    int64_t* bi = as<int64_t>(pe_best);
+    double* bv = reinterpret_cast<double*>(bi + ns * nseg);
+    std::vector<int64_t> hi_(want_best ? (size_t)ns * nseg : 0);
+    std::vector<double> hv_(want_best ? (size_t)ns * nseg : 0);
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    if (want_best) {
+      HIPCHECK(hipMemcpyAsync(pe_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+      HIPCHECK(hipMemsetAsync(pe_best.p, 0xFF, (size_t)ns * nseg * 16, s));  // (index -1: no winner yet; the value a NaN)
+    }
+    PathsEvalLaunch g;
+    g.ts = as<double>(pe_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
+    g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
+    g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.out = as<double>(pe_vals); g.ldo = chunk;
+    for (int64_t off = 0; off < m; off += chunk) {
+      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pe_ts), as<double>(pe_norm));
+      g.m = mc;
+      if (launch_paths_eval(s, g) != 0) return launch_status();
+      if ((rc = launch_status())) return rc;
+      if (values)
+        HIPCHECK(hipMemcpy2DAsync(values + off, (size_t)m * 8, pe_vals.p, (size_t)chunk * 8, (size_t)mc * 8, (size_t)ns,
+                                  out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+      if (want_best) launch_paths_argmax(s, as<double>(pe_vals), chunk, off, mc, as<int64_t>(pe_seg), nseg, ns, bi, bv);
+    }
+    if (want_best) {
+      if ((rc = launch_status())) return rc;
+      HIPCHECK(hipMemcpyAsync(hi_.data(), bi, hi_.size() * 8, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipMemcpyAsync(hv_.data(), bv, hv_.size() * 8, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = points_end(s, m))) return rc;
+    for (size_t e = 0; e < hi_.size(); ++e) {  // indices relative to the segment start; an empty segment: -1 and a NaN
+      if (best_idx) best_idx[e] = hi_[e] < 0 ? -1 : hi_[e] - so[e % nseg];
+      if (best_val) best_val[e] = hv_[e];
+    }
+    return GPSO_OK;
   }
   void paths_info(int64_t* s_out, int64_t* f_out) const override {
     *s_out = res.paths_valid ? pth.s : 0;

@@ -288,7 +288,10 @@ def test_logei_ranks_on_the_device_where_ei_is_zero(dtype):
     assert np.all(AO.yardstick(AO.EI, mean_ref, var_ref, incumbent=tau) == 0.0)  # float64 EI is dead on every row
     idx, _, _, best = eng.best_acq(LEAVES_A, A.EI(incumbent=tau), seg_off=SEG_A)
     assert list(idx) == [0, 0, 0] and np.all(best == 0.0)  # every row ties: the first maximum is row 0
+    eng.set_timing(True)
+    eng.predict(LEAVES_A[:7])  # (another count: what is read below describes the acq_values call)
     mean, var, val = eng.acq_values(LEAVES_A, A.LogEI(incumbent=tau))
+    assert eng.last_count(0) == eng.last_count(1) == len(LEAVES_A) and eng.last_ms(1) > 0.0
     assert np.all(np.isfinite(val))
     _check_values("logei", mean, var, val, tau)
     idx = _check_winner(eng, LEAVES_A, SEG_A, A.LogEI(incumbent=tau), mean, var, val, tau)

@@ -3,8 +3,9 @@
 from the same posteriors in a fresh process (a list of engine configurations x shapes); the SHA-1 of mean and variance
 are printed side by side, differing rows marked.  A last section hashes (loss, grad_u, theta) of every entry point in the
 optimiser's variables u (and of the batch) at the shapes of tests/test_gpu_theta.py; --theta runs that section alone.
+--points runs (alone, and only then) the section of the calls that evaluate the posterior at given points: points_section.
 
-    python tools/ab_bits.py [--theta] pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
+    python tools/ab_bits.py [--theta | --points] pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
 """
 import hashlib
 import json
@@ -57,6 +58,67 @@ def theta_section(out):
         eng.close()
 
 
+def points_section(out):
+    """Every output of the calls that evaluate the posterior at given points -- predict, acq_values (EI), predict_grad,
+    predict_joint, sample_joint (fixed normals), paths_draw + paths_eval (two segments) -- on a float64 and a mixed context,
+    from host float64 points and from device float32 points; paths_draw_q + paths_eval after an SGPR install on float64.
+    The suite's smallest shapes: N = 129, D = 3, Matern-5/2, noise 1e-3, M = 130; M = 1024 + 130 crosses predict_grad's
+    chunk, M = 16384 + 3 paths_eval's (on tests/paths_cases.py's N = 17 case, as the suite's chunking test does)."""
+    import numpy as np
+    import torch
+
+    from pygpso_amd import HipGPEngine
+    from pygpso_amd import acquisition as A
+    from tests import paths_cases as pc
+    from tests import sgpr_oracle as SG
+    from tests.helpers import synthetic_problem
+
+    def put(name, *parts):
+        out[name] = hashlib.sha1(b"".join(np.ascontiguousarray(p).tobytes() for p in parts)).hexdigest()[:12]
+
+    def feeds(eng, pts):
+        yield "host f64", pts
+        yield "device f32", torch.from_numpy(pts.astype(np.float32)).to(torch.device("cuda", eng.device))
+
+    kernel, d, m, seg = "Matern52", 3, 130, np.array([0, 70, 130], dtype=np.int64)
+    X, y = synthetic_problem(129, d, seed=17 + 129)
+    ls, c = 0.25 * np.sqrt(d) * np.ones(1), float(y.mean())
+    pts = pc.points_at(1024 + m, d)
+    z = np.random.default_rng(4).standard_normal((3, m))
+    Xc, yc = synthetic_problem(17, d, seed=17 + 17)
+    ptc = pc.points_at(pc.CHUNK + 3, d)
+    for dtype in ("float64", "mixed"):
+        eng = HipGPEngine(dtype)
+        eng.set_data(X, y)
+        eng.fit_eval(kernel, ls, 1.3, 1.0e-3, c, want_grad=False)
+        for feed, xs in feeds(eng, pts):
+            tag = f"{dtype} {feed}"
+            put(f"points predict {tag}", *eng.predict(xs[:m]))
+            put(f"points acq_values EI {tag}", *eng.acq_values(xs[:m], A.EI(incumbent=float(y.max())), incumbent=float(y.max())))
+            put(f"points predict_grad M=130 {tag}", *eng.predict_grad(xs[:m]))
+            put(f"points predict_grad M=1154 {tag}", *eng.predict_grad(xs))
+            put(f"points predict_joint {tag}", *eng.predict_joint(xs[:m], 0.25))
+            put(f"points sample_joint {tag}", *eng.sample_joint(xs[:m], z, 0.25))
+            eng.paths_draw(*pc.inputs(kernel, 17, 64, 129, d, seed=100))
+            put(f"points paths_draw + paths_eval {tag}", *eng.paths_eval(xs[:m], seg_off=seg))
+        eng.close()
+        eng = HipGPEngine(dtype)
+        eng.set_data(Xc, yc)
+        eng.fit_eval(kernel, ls, 1.3, 1.0e-3, float(yc.mean()), want_grad=False)
+        eng.paths_draw(*pc.inputs(kernel, 1, 4, 17, d, seed=110))
+        for feed, xs in feeds(eng, ptc):
+            put(f"points paths_eval M=16387 {dtype} {feed}", *eng.paths_eval(xs, seg_off=np.array([0, 70, pc.CHUNK + 3], dtype=np.int64)))
+        eng.close()
+    eng = HipGPEngine("float64")
+    eng.set_data(X, y)
+    eng.sgpr_set_inducing(np.ascontiguousarray(X[:33]))
+    eng.sgpr_posterior(kernel, SG.initial_u(ls, 1.3, 1.0e-3, c), 1, True, 0.0)
+    eng.paths_draw_q(*pc.inputs(kernel, 17, 64, 33, d, seed=120))
+    for feed, xs in feeds(eng, pts[:m]):
+        put(f"points sgpr paths_draw_q + paths_eval float64 {feed}", *eng.paths_eval(xs, seg_off=seg))
+    eng.close()
+
+
 def worker():
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -65,10 +127,11 @@ def worker():
     from tests.helpers import synthetic_leaves, synthetic_problem
 
     out = {}
-    if "--theta" in sys.argv:
-        theta_section(out)
-        print("AB_BITS " + json.dumps(out), flush=True)
-        return
+    for flag, section in (("--theta", theta_section), ("--points", points_section)):
+        if flag in sys.argv:
+            section(out)
+            print("AB_BITS " + json.dumps(out), flush=True)
+            return
     for n, d, m, kernel in SHAPES:
         X, y = synthetic_problem(n, d, seed=1)
         Xs = synthetic_leaves(m, d, seed=3)

@@ -8,6 +8,7 @@ in a fresh process, alternating A B A B ..., and the medians are printed side by
 --what predict: leaf-tile kernel ms (library events) and wall ms per gpso_best_ucb call, per predict math
 --what fit:     posterior / NLML+gradient ms (library events) at the shape
 --what small:   wall us per fit_eval_u + best_ucb_grow at N = 52, D = 2 (the optimiser loop's calls)
+--what points:  host wall ms of --steps consecutive gpso_predict calls (host points, host outputs) at the shape, --dtype context
 """
 import argparse
 import json
@@ -68,6 +69,19 @@ def worker(args):
                     ts.append(eng.last_ms(2))
                 out[f"{dtype}.{name}"] = {"ms": float(np.median(ts[2:])), "min": float(np.min(ts[2:]))}
             eng.close()
+    elif args.what == "points":
+        leaves = synthetic_leaves(m, d)
+        eng = HipGPEngine(args.dtype)
+        eng.set_data(X, y)
+        eng.fit_eval(*theta, want_grad=False)
+        for _ in range(20):
+            eng.predict(leaves)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            eng.predict(leaves)
+        out["predict_wall_ms"] = (time.perf_counter() - t0) * 1e3
+        out["calls"] = args.steps
+        eng.close()
     else:  # small: the optimiser loop's calls
         from oracle import tree  # (geometry helper only)
 
@@ -96,7 +110,7 @@ def worker(args):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("libs", nargs="*")
-    ap.add_argument("--what", default="predict", choices=["predict", "fit", "small"])
+    ap.add_argument("--what", default="predict", choices=["predict", "fit", "small", "points"])
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--shape", type=int, nargs=3, default=[2048, 12, 65536])
