@@ -702,6 +702,61 @@ int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
  * var[i] - noise.  No context and no GPU (as gpso_shard_range); returns GPSO_OK or GPSO_E_ARG. */
 int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out);
 
+/* ---- latent cross-covariance and greedy batch selection (no counterpart in the reference) ----------------------------
+ *
+ * Every posterior the predict path serves installs mean = k*^T alpha + c, var = variance - |C k*|^2 + noise over its
+ * resident rows, C the dense double factor.  The LATENT posterior covariance between two points is then
+ *     Cov(a, b) = k(t_a, t_b) - k_a^T w_b,   w_b = C^T (C k_b):
+ * one vector of length N per point b (two passes over C), then O(N D) per pair.
+ *
+ * gpso_cross_cov: cov[c * m + j] = Cov(f(xa_j), f(xb_c)) for m points xa (dtype / memory as the leaves of gpso_predict)
+ * and b points xb (host float64, [b * D]); cov is float64 [b * m] living in out_mem.  A row with a NaN coordinate gives
+ * NaNs.  m is worked off in chunks; the bits of an entry depend neither on the chunking nor on the rest of either batch.
+ *
+ * gpso_best_batch: q leaves of one batch, picked greedily under hallucinated updates (GP-BUCB, "kriging believer"): pick
+ * the best leaf, pretend it was observed at its posterior mean with noise variance obs_noise, re-rank, repeat.  The
+ * fantasy observation leaves every mean as it is and lowers the variances near the pick.
+ *   Round 0 reads the (mean, var, value) of gpso_acq_values on the same batch: it goes through the context's predict
+ *     path and has that call's bits.  The first pick with its mean, var and value therefore has the bits of gpso_best_acq
+ *     with one segment.
+ *   Later rounds are double arithmetic on top of that (csrc/batch.hpp): with G[s][.] the columns of the earlier rounds,
+ *     c[j] = Cov(j, p_t) - sum_{s<t} G[s][j] G[s][p_t],  d_t = c[p_t] + obs_noise,  G[t][j] = c[j] / sqrt(d_t),
+ *     s2[j] -= G[t][j]^2.
+ *   idx / mean / var / value [q] (host; mean, var and value nullable): var[t] is the predictive variance pick t was ranked
+ *     by, conditional on the earlier picks; mean[t] is its round-0 mean (the bits of gpso_predict at that row); value[t]
+ *     what it was ranked by.  With acq->latent set the kinds read s2 - noise, as they do today (UCB_VAR never does).  The
+ *     incumbent and xi do not move between rounds.
+ *   obs_noise is the variance of the fantasy observation: absolute, >= 0, the caller's decision as diag_add is (the Python
+ *     layer passes the family's predictive noise).
+ *   Retiring: a picked row is retired, and with it every row whose scaled coordinates equal the pick's exactly (r^2 == 0
+ *     in the column pass: grown leaves repeat rows).  Retired rows never win; their var_after is still updated.
+ *   Ending early: a pick whose value is NaN is still reported and the batch ends after it; the same holds if its d_t is
+ *     not finite or <= 0 (that pick changes no variance); if no live row is left the batch ends.  *n_picked <= q says how
+ *     many entries are valid; the rest of idx / mean / var / value is not written.
+ *   var_after (float64 [m] living in out_mem, nullable): the predictive variance of every row after the n_picked picks.
+ *   The first maximum wins a tie and a NaN beats every number (np.argmax's rule, and gpso_best_ucb's).
+ * GPSO_E_ARG: a GPSO_F32 context (either call); m < 1; q or b outside [1, 64]; q * m > 2^27; NULL xs / xa, xb, cov, acq, idx
+ *   or n_picked; a bad acq (the checks of gpso_best_acq); an obs_noise that is negative or not finite.
+ * GPSO_E_STATE as gpso_predict_grad: no posterior, an adopted one that travelled without the dense factor, an asynchronous
+ *   best-UCB call open.
+ * Both calls are stateless: the posterior, its packed copies, the hyper block, the self-test's verdicts,
+ * gpso_posterior_hash and a resident path set stay bit for bit; the workspaces are the calls' own and grow only.
+ * gpso_last_ms(ctx, 1) covers the call, gpso_last_count(ctx, 0) and (ctx, 1) are m.  gpso_best_batch keeps the scaled
+ * leaves (m * D_pad doubles) and G (q * m doubles) on the device for the length of the call.
+ * Out of scope: segments, grown leaves (_grow), the asynchronous _begin / _end pair, sharded groups, and the screen. */
+int gpso_cross_cov(gpso_ctx* ctx, const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb /* [b*D] host */,
+                   int b, double* cov /* [b*m] */, int out_mem);
+int gpso_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq,
+                    double obs_noise, int q, int64_t* idx, double* mean, double* var, double* value /* [q] host */,
+                    int* n_picked, double* var_after /* [m], nullable */, int out_mem);
+/* The greedy rounds on the host from a given mean[m], predictive s2[m] and LATENT cov[m*m] (noise: what a latent kind
+ * subtracts from s2): the same header, the same roundings, the same end rules; no context and no GPU.  The host sees no
+ * coordinates: a row is retired with the pick when cov cannot tell them apart (Cov(j,j), Cov(j,p) and Cov(p,p) are the
+ * same number).  var / value / var_after nullable.  Returns GPSO_OK or GPSO_E_ARG. */
+int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise,
+                           double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
+                           int* n_picked, double* var_after /* nullable */);
+
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 
 /* Centres of levels 0..depth-1 of the ternary subtree under each of nseg boxes, generated on the

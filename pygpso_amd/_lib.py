@@ -161,6 +161,11 @@ SIGNATURES = {
     "gpso_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int]),
     "gpso_acq_eval_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, C.c_double, C.c_int64, _c_double_p]),
+    "gpso_cross_cov": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_double_p, C.c_int, C.c_void_p, C.c_int]),
+    "gpso_best_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_double, C.c_int, _c_int64_p,
+                                  _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]),
+    "gpso_batch_greedy_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, _c_double_p, C.c_double, C.c_double, C.c_int64, C.c_int,
+                                         _c_int64_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), _c_double_p]),
     "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,

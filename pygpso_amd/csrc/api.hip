@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/gpso_hip.h"
+#include "batch.hpp"
 #include "best_call.hpp"
 #include "common.hpp"
 #include "devbuf.hpp"
@@ -112,6 +113,10 @@ struct Engine {
   virtual int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values,
                          int out_mem, int64_t* best_idx, double* best_val) = 0;
   virtual void paths_info(int64_t* s, int64_t* f) const = 0;
+  // the latent cross-covariance of two point sets, and q leaves of one set picked greedily under hallucinated updates (batch.hip)
+  virtual int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem) = 0;
+  virtual int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx,
+                         double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) = 0;
   // mean, var and the acquisition column of every leaf (each output nullable)
   virtual int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
                          double* value, int out_mem) = 0;
@@ -492,6 +497,11 @@ struct EngineT : Engine {
   };
   PathSet pth, pth_next;
   DevBuf pth_eps, pth_p, pth_r, pth_u, pth_x /* gpso_paths_draw_q: Lu^-1 Phi(Zr) w^T */, pe_ts, pe_norm, pe_vals, pe_seg, pe_best;
+  // gpso_cross_cov / gpso_best_batch (batch.hip): scaled points of a chunk and their norms, the points b (raw, scaled, norms),
+  // K_b | U | W and the latent variances, host-bound results; then the batch call's own: every scaled leaf and its norm, mean,
+  // s2, the value column, G, the live flags, the blocks' maxima, the state words and the pick's scaled row
+  DevBuf cc_ts, cc_norm, cc_braw, cc_tb, cc_bnorm, cc_vec, cc_lv, cc_out;
+  DevBuf bb_ts, bb_norm, bb_mean, bb_s2, bb_val, bb_g, bb_live, bb_bmax, bb_state, bb_tp;
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -3213,6 +3223,136 @@ struct EngineT : Engine {
     *f_out = res.paths_valid ? pth.f : 0;
   }
 
+  // ---- latent cross-covariance and greedy batch selection (batch.hip).  Both calls read the dense
+  // fit-type factor, the scaled rows and the hyper block -- gpso_best_batch also whatever gpso_acq_values reads -- and write
+  // buffers of their own only: the posterior, its packed copies, the self-test's verdicts and a resident path set stay as they are
+  int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem) override {
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    ctx->tick_timing();
+    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov needs at least one point (m=%lld)", (long long)m);
+    if (b < 1 || b > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov takes 1 to %d points b (b=%d)", kBatchMaxPicks, b);
+    int rc = check_points(xa, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    if (!xb || !cov) return ctx->fail(GPSO_E_ARG, "xb and cov must not be NULL");
+    if ((rc = need_dense_factor("gpso_cross_cov"))) return rc;
+    const int64_t chunk = std::min<int64_t>(kBatchChunk, (m + 63) / 64 * 64);
+    if ((rc = ensure(cc_ts, (size_t)chunk * dp * 8))) return rc;
+    if ((rc = ensure(cc_norm, (size_t)chunk * 8))) return rc;
+    if ((rc = ensure(cc_braw, (size_t)kBatchMaxPicks * d * 8))) return rc;
+    if ((rc = ensure(cc_tb, (size_t)kBatchMaxPicks * dp * 8))) return rc;
+    if ((rc = ensure(cc_bnorm, (size_t)kBatchMaxPicks * 8))) return rc;
+    if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, b) * 8))) return rc;
+    if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
+    const bool to_host = out_mem == GPSO_MEM_HOST;
+    double* cd = cov;
+    if (to_host) {
+      if ((rc = ensure(cc_out, (size_t)b * m * 8))) return rc;
+      cd = as<double>(cc_out);
+    }
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xa, xs_dtype, xs_mem, m, &dev))) return rc;
+    HIPCHECK(hipMemcpyAsync(cc_braw.p, xb, (size_t)b * d * 8, hipMemcpyHostToDevice, s));
+    prep_points<double>(s, cc_braw.p, GPSO_F64, 0, b, kBatchMaxPicks, nullptr, as<double>(cc_tb), as<double>(cc_bnorm));
+    BatchPickLaunch pk;
+    pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(cc_tb); pk.n = n; pk.npad = npad; pk.b = b; pk.dp = dp; pk.kp = kp;
+    pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + (size_t)b * npad; pk.W = pk.U + (size_t)b * npad; pk.lv = as<double>(cc_lv);
+    if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
+    BatchColLaunch g;
+    g.ts = as<double>(cc_ts); g.tnorm = as<double>(cc_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.bnorm = as<double>(cc_bnorm);
+    g.n = n; g.npad = npad; g.b = b; g.dp = dp; g.kp = kp; g.ldc = m;
+    for (int64_t off = 0; off < m; off += chunk) {
+      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(cc_ts), as<double>(cc_norm));
+      g.m = mc;
+      g.cov = cd + off;
+      if (launch_batch_cross(s, g) != 0) return launch_status();
+      if ((rc = launch_status())) return rc;
+    }
+    if (to_host) HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)b * m * 8, hipMemcpyDeviceToHost, s));
+    return points_end(s, m);
+  }
+
+  // Round 0 is gpso_acq_values on the batch (the context's predict path: its bits); every later round is double arithmetic
+  // on top: pick vectors, one column launch, one finish launch.  All rounds are enqueued back to back, the picks stay on
+  // the device, one wait at the end
+  int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx,
+                 double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) override {
+    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_best_batch needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
+    ctx->tick_timing();
+    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_best_batch needs at least one leaf (m=%lld)", (long long)m);
+    if (q < 1 || q > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_best_batch picks 1 to %d leaves (q=%d)", kBatchMaxPicks, q);
+    if (m > kBatchMaxCells / q) return ctx->fail(GPSO_E_ARG, "gpso_best_batch: q * m above 2^27 (q=%d, m=%lld)", q, (long long)m);
+    if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+    if (!idx || !n_picked) return ctx->fail(GPSO_E_ARG, "idx and n_picked must not be NULL");
+    if (!(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0) return ctx->fail(GPSO_E_ARG, "obs_noise must be finite and not negative");
+    int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
+    if (rc) return rc;
+    if ((rc = need_dense_factor("gpso_best_batch"))) return rc;
+    const int64_t mall = (m + 63) / 64 * 64, nblk = batch_round_blocks(m);
+    if ((rc = ensure(bb_ts, (size_t)mall * dp * 8))) return rc;
+    if ((rc = ensure(bb_norm, (size_t)mall * 8))) return rc;
+    if ((rc = ensure(bb_mean, (size_t)m * 8))) return rc;
+    if ((rc = ensure(bb_s2, (size_t)m * 8))) return rc;
+    if ((rc = ensure(bb_val, (size_t)m * 8))) return rc;
+    if ((rc = ensure(bb_g, (size_t)q * m * 8))) return rc;
+    if ((rc = ensure(bb_live, (size_t)m))) return rc;
+    if ((rc = ensure(bb_bmax, (size_t)nblk * 16))) return rc;
+    if ((rc = ensure(bb_state, sizeof(BatchState)))) return rc;
+    if ((rc = ensure(bb_tp, (size_t)kMaxD * 8))) return rc;
+    if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, 1) * 8))) return rc;
+    if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
+    BatchState* host = reinterpret_cast<BatchState*>(ctx->pinned_scratch(sizeof(BatchState) / 8 + 1));
+    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    hipStream_t s;
+    if ((rc = points_begin(&s))) return rc;
+    const void* dev = nullptr;
+    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+    BatchState* state = static_cast<BatchState*>(bb_state.p);
+    HIPCHECK(hipMemsetAsync(state, 0, sizeof(BatchState), s));
+    double *md = as<double>(bb_mean), *s2d = as<double>(bb_s2), *vald = as<double>(bb_val), *G = as<double>(bb_g);
+    double* bmax_v = as<double>(bb_bmax);
+    int64_t* bmax_i = reinterpret_cast<int64_t*>(bmax_v + nblk);
+    unsigned char* live = static_cast<unsigned char*>(bb_live.p);
+    TileSpan span{ctx->timing};
+    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, s2d, vald, span))) return rc;
+    for (int64_t off = 0; off < m; off += kBatchChunk) {
+      const int64_t mc = std::min(kBatchChunk, m - off), mpad = (mc + 63) / 64 * 64;
+      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(bb_ts) + off * dp, as<double>(bb_norm) + off);
+    }
+    launch_batch_init(s, vald, m, live, bmax_v, bmax_i);
+    BatchPickLaunch pk;
+    pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(bb_tp); pk.n = n; pk.npad = npad; pk.b = 1; pk.dp = dp; pk.kp = kp;
+    pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + npad; pk.W = pk.U + npad; pk.lv = as<double>(cc_lv); pk.st = state; pk.obs_noise = obs_noise;
+    BatchColLaunch g;
+    g.ts = as<double>(bb_ts); g.tnorm = as<double>(bb_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.n = n; g.npad = npad; g.m = m;
+    g.dp = dp; g.kp = kp; g.st = state; g.G = G; g.s2 = s2d; g.mean = md; g.live = live; g.acq = acq; g.bmax_v = bmax_v; g.bmax_i = bmax_i;
+    for (int t = 0; t < q; ++t) {
+      launch_batch_finish(s, state, t, bmax_v, bmax_i, t == 0 ? batch_init_blocks(m) : nblk, g.ts, dp, md, s2d, G, m, live, as<double>(bb_tp));
+      const bool last = t == q - 1;
+      if (last && !var_after) break;
+      pk.t = g.t = t;
+      g.rank = !last;
+      if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
+      if (launch_batch_round(s, g) != 0) return launch_status();
+    }
+    if ((rc = launch_status())) return rc;
+    HIPCHECK(hipMemcpyAsync(host, state, sizeof(BatchState), hipMemcpyDeviceToHost, s));
+    if (var_after)
+      HIPCHECK(hipMemcpyAsync(var_after, s2d, (size_t)m * 8, out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    if ((rc = points_end(s, m))) return rc;
+    collect_tile_ms(span.timed, span.pairs);
+    *n_picked = host->n_picked;
+    for (int t = 0; t < host->n_picked; ++t) {
+      idx[t] = host->idx[t];
+      if (mean) mean[t] = host->mean[t];
+      if (var) var[t] = host->var[t];
+      if (value) value[t] = host->value[t];
+    }
+    return GPSO_OK;
+  }
+
   // ---- best-UCB sequencing: enqueue the local work (winners stay on the device, no host wait) ->
   //      [multi-GPU: all-gather + fold] -> one read-back ------------------------------------------------
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
@@ -4979,6 +5119,13 @@ int gpso_paths_eval(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
   return ctx->eng->paths_eval(xs, xs_dtype, xs_mem, m, seg_off, nseg, values, out_mem, best_idx, best_val);
 }
 
+int gpso_cross_cov(gpso_ctx* ctx, const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov,
+                   int out_mem) {
+  ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  return ctx->eng->cross_cov(xa, xs_dtype, xs_mem, m, xb, b, cov, out_mem);
+}
+
 int gpso_paths_info(gpso_ctx* ctx, int64_t* s, int64_t* f) {
   ENTER();
   if (!s || !f) return ctx->fail(GPSO_E_ARG, "s and f must not be NULL");
@@ -5075,6 +5222,21 @@ int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
   ACQ_ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
   return ctx->eng->acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), mean, var, value, out_mem);
+}
+
+int gpso_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double obs_noise, int q,
+                    int64_t* idx, double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) {
+  ACQ_ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  return ctx->eng->best_batch(xs, xs_dtype, xs_mem, m, acq_spec(acq), obs_noise, q, idx, mean, var, value, n_picked, var_after, out_mem);
+}
+
+int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise, double obs_noise,
+                           int64_t m, int q, int64_t* idx, double* var, double* value, int* n_picked, double* var_after) {
+  if (acq_refusal(acq) != nullptr || m < 1 || q < 1 || q > gpso::kBatchMaxPicks || m > gpso::kBatchMaxCells / q || !mean || !s2 || !cov ||
+      !idx || !n_picked || noise != noise || !(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0)
+    return GPSO_E_ARG;
+  return gpso::batch_greedy_host(acq_spec(acq), mean, s2, cov, noise, obs_noise, m, q, idx, var, value, n_picked, var_after);
 }
 
 int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,

@@ -544,6 +544,71 @@ void launch_paths_solve_q(hipStream_t st, const double* Lui, const double* Q, bo
 // winner in best_i / best_v [s * nseg] (best_i < 0: none yet; indices count from the start of the batch)
 void launch_paths_argmax(hipStream_t st, const double* vals, int64_t ldv, int64_t off, int64_t mc, const int64_t* seg_off_dev, int nseg,
                          int64_t s, int64_t* best_i, double* best_v);
+// ---- batch.hip: latent cross-covariance and the greedy batch rounds built on it ---------------------------
+constexpr int64_t kBatchChunk = 16384;  // points per launch sequence of gpso_cross_cov / per scaling launch of gpso_best_batch
+// the device words of one gpso_best_batch call (zeroed when it starts)
+struct BatchState {
+  int stop;      // != 0: the batch has ended; the launches still queued do nothing
+  int n_picked;
+  double d, root_d;  // d_t of the round in flight and its square root
+  double gp[64];     // G[s][p_t], s < t
+  int64_t idx[64];
+  double mean[64], var[64], value[64];
+};
+// K_b = k(Xr, t_b), U = C K_b (each [b][npad], rows below n written), W = C^T U as batch_w_slabs(n) partial sums over slabs
+// of rows ([slabs][b][npad]: the column launches add them in their order) and lv[c] = variance - |u_c|^2 for the b scaled
+// points tb [b][dp].  Kb, U and W together: batch_pick_workspace_doubles(n, npad, b) doubles.  C the dense fit-type L^-1, read where column <= row < n.  st (nullable; b == 1): a round of
+// gpso_best_batch -- nothing runs once st->stop is set, and d_t = lv - sum_{s < t} gp[s]^2 + obs_noise, its root and the stop
+// test go to st
+struct BatchPickLaunch {
+  const double* C = nullptr;
+  const double* xs = nullptr;  // [npad * dp] scaled rows
+  const double* tb = nullptr;
+  int64_t n = 0, npad = 0;
+  int b = 0, dp = 0;
+  KernParams kp{0, 1.0, 0.0, 0.0};
+  double *Kb = nullptr, *U = nullptr, *W = nullptr, *lv = nullptr;
+  BatchState* st = nullptr;
+  int t = 0;
+  double obs_noise = 0.0;
+};
+int batch_w_slabs(int64_t n);  // a function of n alone: so are the bits of w
+size_t batch_pick_workspace_doubles(int64_t n, int64_t npad, int b);
+int launch_batch_pick_vectors(hipStream_t st, const BatchPickLaunch& g);
+struct BatchColLaunch {
+  const double* ts = nullptr;     // [roundup(m, 64) * dp] scaled leaves, zero rows behind the m live ones
+  const double* tnorm = nullptr;  // [roundup(m, 64)] their squared norms: a NaN marks a row with a NaN coordinate
+  const double* xs = nullptr;     // [npad * dp] scaled rows
+  const double* W = nullptr;      // launch_batch_pick_vectors' W for the points tb
+  const double* tb = nullptr;     // [b][dp]
+  const double* bnorm = nullptr;  // [b] (launch_batch_cross; nullable)
+  int64_t n = 0, npad = 0, m = 0;
+  int b = 1, dp = 0;
+  KernParams kp{0, 1.0, 0.0, 0.0};
+  double* cov = nullptr;          // launch_batch_cross: cov[c * ldc + j] = Cov(f(t_j), f(tb_c)), ldc >= m
+  int64_t ldc = 0;
+  // launch_batch_round (b == 1: the pick of round t): G [q][m], s2 / mean / live [m], the tiles' maxima [batch_round_blocks(m)]
+  BatchState* st = nullptr;
+  int t = 0;
+  bool rank = true;               // false: G and the downdate only
+  double* G = nullptr;
+  double* s2 = nullptr;
+  const double* mean = nullptr;
+  unsigned char* live = nullptr;
+  AcqSpec acq;
+  double* bmax_v = nullptr;
+  int64_t* bmax_i = nullptr;
+};
+int launch_batch_cross(hipStream_t st, const BatchColLaunch& g);
+int launch_batch_round(hipStream_t st, const BatchColLaunch& g);
+int64_t batch_init_blocks(int64_t m);
+int64_t batch_round_blocks(int64_t m);
+// round 0: live := 1 and the blocks' first maxima of value [m] (bmax_* [batch_init_blocks(m)])
+void launch_batch_init(hipStream_t st, const double* value, int64_t m, unsigned char* live, double* bmax_v, int64_t* bmax_i);
+// the pick of round t from nblocks maxima: its record into st, its scaled row into tp [dp], its history into st->gp
+void launch_batch_finish(hipStream_t st, BatchState* state, int t, const double* bmax_v, const int64_t* bmax_i, int64_t nblocks,
+                         const double* ts, int dp, const double* mean, const double* s2, const double* G, int64_t m, unsigned char* live,
+                         double* tp);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

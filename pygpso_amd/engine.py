@@ -922,6 +922,69 @@ class HipGPEngine:
             raise L.GpsoHipError(rc, "gpso_acq_eval_host: bad acquisition record or arguments")
         return out
 
+    # -- latent cross-covariance and greedy batch selection (csrc/batch.hip, csrc/batch.hpp) --------------------------
+    def cross_cov(self, xa, xb, out=None):
+        """The latent posterior covariance between the M rows of ``xa`` and the B <= 64 rows of ``xb``: cov [B, M]
+        float64, cov[c, j] = Cov(f(xa_j), f(xb_c)) (``gpso_cross_cov``).  float64 and mixed engines; any resident posterior
+        but an adopted one.  ``out`` may be a contiguous [B, M] float64 CUDA tensor to keep the result on the device."""
+        ptr, dt, mem, m, keep = self._leaf_args(xa)
+        xb = L.as_f64(np.atleast_2d(np.asarray(xb, dtype=np.float64)))
+        if xb.ndim != 2 or xb.shape[1] != self.d:
+            raise ValueError(f"xb must be [B, D] with D={self.d}, got {xb.shape}")
+        b = int(xb.shape[0])
+        if out is not None:
+            if tuple(out.shape) != (b, m) or not out.is_contiguous():
+                raise ValueError(f"out must be a contiguous [{b}, {m}] tensor")
+            self._order_after(out)
+            self._check(self._lib.gpso_cross_cov(self._h, ptr, dt, mem, m, L.dptr(xb), b, C.c_void_p(out.data_ptr()), L.MEM_DEVICE))
+            return out
+        cov = np.empty((b, m), dtype=np.float64)
+        self._check(self._lib.gpso_cross_cov(self._h, ptr, dt, mem, m, L.dptr(xb), b, C.c_void_p(cov.ctypes.data), L.MEM_HOST))
+        return cov
+
+    def best_batch(self, xs, spec, q, obs_noise, incumbent=None, want_var_after=False):
+        """``q`` rows of ``xs`` picked greedily under hallucinated updates (``gpso_best_batch``; GP-BUCB): the best row by
+        the acquisition spec ``spec``, then the best once that row counts as observed at its mean with noise variance
+        ``obs_noise``, and so on.  Returns (idx, mean, var, value) of the picks made -- at most ``q``: a NaN value, a
+        fantasy variance that is not positive, or no distinct row left end the batch -- and, with ``want_var_after``, the
+        predictive variance [M] of every row after them as a fifth entry."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec = spec.c_struct(incumbent)
+        q = int(q)
+        cap = max(q, 1)
+        idx = np.full(cap, -1, dtype=np.int64)
+        mean, var, val = (np.full(cap, np.nan, dtype=np.float64) for _ in range(3))
+        n_picked = C.c_int(0)
+        after = np.empty(m, dtype=np.float64) if want_var_after else None
+        self._check(self._lib.gpso_best_batch(self._h, ptr, dt, mem, m, C.byref(rec), float(obs_noise), q, L.i64ptr(idx), L.dptr(mean),
+                                              L.dptr(var), L.dptr(val), C.byref(n_picked),
+                                              None if after is None else C.c_void_p(after.ctypes.data), L.MEM_HOST))
+        k = int(n_picked.value)
+        res = (idx[:k].copy(), mean[:k].copy(), var[:k].copy(), val[:k].copy())
+        return res + (after,) if want_var_after else res
+
+    @staticmethod
+    def batch_greedy_host(spec, mean, s2, cov, noise, obs_noise, q, incumbent=None):
+        """The greedy rounds of ``best_batch`` on the CPU from a given mean [M], predictive variance [M] and latent
+        covariance [M, M] (``gpso_batch_greedy_host``: no context, no GPU) -> (idx, var, value, var_after)."""
+        mean = L.as_f64(np.asarray(mean).reshape(-1))
+        m = int(mean.shape[0])
+        s2 = L.as_f64(np.asarray(s2).reshape(-1), mean.shape)
+        cov = L.as_f64(np.asarray(cov), (m, m))
+        q = int(q)
+        cap = max(q, 1)
+        idx = np.full(cap, -1, dtype=np.int64)
+        var, val = (np.full(cap, np.nan, dtype=np.float64) for _ in range(2))
+        after = np.empty(m, dtype=np.float64)
+        n_picked = C.c_int(0)
+        rec = spec.c_struct(incumbent)
+        rc = L.load().gpso_batch_greedy_host(C.byref(rec), L.dptr(mean), L.dptr(s2), L.dptr(cov), float(noise), float(obs_noise), m, q,
+                                             L.i64ptr(idx), L.dptr(var), L.dptr(val), C.byref(n_picked), L.dptr(after))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_batch_greedy_host: bad acquisition record or arguments")
+        k = int(n_picked.value)
+        return idx[:k].copy(), var[:k].copy(), val[:k].copy(), after
+
     # -- ternary geometry ------------------------------------------------------------------------
     def grow_rows(self, depth):
         return int(self._lib.gpso_grow_rows(int(depth)))

@@ -641,6 +641,26 @@ class GPSurrogate:
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
         return self.gpflow_model.acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, incumbent)
 
+    def gp_cross_cov(self, a, b):
+        """The latent posterior covariance [B, M] between the M rows of ``a`` and the B <= 64 rows of ``b`` (normed
+        coordinates): one ``gpso_cross_cov`` call; stores nothing."""
+        model = self._joint_model("gp_cross_cov")
+        return model.cross_cov(np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64))
+
+    def select_batch(self, normed_coords, q, acquisition=None, incumbent=None, return_var_after=False):
+        """``q`` different rows of ``normed_coords`` to evaluate at once -- a pool of workers -- by greedy selection under
+        hallucinated updates (GP-BUCB, "kriging believer"; one ``gpso_best_batch`` call): the best row, then the best once
+        that row counts as observed at its posterior mean with the model's predictive noise, and so on.  ``acquisition``:
+        as ``gp_eval_best_acq``; None: the surrogate's own (``gp_acquisition``, by default the reference's mean +
+        varsigma * var).  Returns (indices, mean, var, value) of the picks -- fewer than ``q`` when the rows run out or a
+        value is NaN --: ``var`` is the predictive variance a pick was ranked by, given the earlier picks; with
+        ``return_var_after`` a fifth entry holds the predictive variance of every row after all of them.  The first index
+        is ``gp_eval_best_acq``'s.  Stores nothing; a multi-GPU engine group raises NotImplementedError."""
+        model = self._joint_model("select_batch")
+        acq = self._loop_acquisition() if acquisition is None else resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        return model.best_batch(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, q, incumbent=incumbent,
+                                want_var_after=return_var_after)
+
     def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
         """MI355X path of ``gp_eval_best_ucb(leaf.grow(depth))`` for several leaves at once: the
         ternary sub-tree centres are generated on the device (bit-identical to ``LeafNode.grow``)

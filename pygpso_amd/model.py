@@ -511,6 +511,21 @@ class HipGPR:
         inc = self._incumbent(acq, incumbent)
         return self._predicting(lambda: self.engine.acq_values(np.asarray(Xnew), acq, incumbent=inc))
 
+    def cross_cov(self, Xa, Xb):
+        """The latent posterior covariance [B, M] between the M rows of Xa and the B <= 64 rows of Xb, cov[c, j] =
+        Cov(f(Xa_j), f(Xb_c)); float64 and mixed engines."""
+        Xa, Xb = np.asarray(Xa), np.asarray(Xb)
+        return self._predicting(lambda: self.engine.cross_cov(Xa, Xb))
+
+    def best_batch(self, Xnew, acq, q, obs_noise=None, incumbent=None, want_var_after=False):
+        """``q`` rows of Xnew picked greedily under hallucinated updates (GP-BUCB, "kriging believer"): (idx, mean, var,
+        value) of the picks made -- at most ``q`` --, plus the predictive variance [M] after them with ``want_var_after``.
+        ``obs_noise``: the variance of the fantasy observations (None: ``predictive_noise()``)."""
+        inc = self._incumbent(acq, incumbent)
+        noise = self.predictive_noise() if obs_noise is None else obs_noise
+        Xnew = np.asarray(Xnew)
+        return self._predicting(lambda: self.engine.best_batch(Xnew, acq, q, float(noise), incumbent=inc, want_var_after=want_var_after))
+
     # -- reporting ----------------------------------------------------------------------------
     def parameter_dict(self):
         return {
