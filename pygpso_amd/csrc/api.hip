@@ -21,6 +21,7 @@
 #include "best_call.hpp"
 #include "common.hpp"
 #include "devbuf.hpp"
+#include "fit_call.hpp"
 #include "kernels.hpp"
 #include "screen.hpp"
 #include "rccl_api.hpp"
@@ -80,6 +81,8 @@ constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass o
 constexpr int64_t kParkBytesDefault = GPSO_PARK_BYTES_DEFAULT;
 constexpr int kHyperHeader = 8;                // doubles in front of the lengthscales
 static_assert(kThetaMaxLs == kGradMaxLs, "a Theta holds as many lengthscales as the gradient kernels take");
+using FitScratch = gpso::FitScratch<kGradMaxLs, kHyperHeader, kMaxD>;  // (fit_call.hpp: the pinned scratch of a fit call)
+using FitCall = gpso::FitCall<FitScratch>;
 
 struct Engine {
   virtual ~Engine() {}
@@ -896,9 +899,14 @@ struct EngineT : Engine {
     return th;
   }
 
+  // the lengthscale of every padded input dimension, as the hyper block and the one-launch kernels take them: an isotropic
+  // one repeated, the last of n_ls behind them
+  static void expand_ls(const double* ls, int n_ls, double* row) {
+    for (int k = 0; k < kMaxD; ++k) row[k] = ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
+  }
   // th.lik: the noise variance of the hyper block.  upload = false: the caller's kernel writes the device copy of the block
-  // itself (fused small fit)
-  int set_theta(const Theta& th, bool upload = true) {
+  // itself (fused small fit).  stage: a fit call's FitCall::theta_stage(); NULL: the scratch is asked for here
+  int set_theta(const Theta& th, bool upload = true, double* stage = nullptr) {
     if (int rc = theta_status(theta_refusal(th, d, false))) return rc;
     kp.kernel = th.kernel;
     kp.variance = th.variance;
@@ -907,18 +915,16 @@ struct EngineT : Engine {
     n_ls = th.n_ls;
     ls_host.assign(th.ls, th.ls + n_ls);
     if (!upload) return GPSO_OK;
-    // staged in pinned memory (upper half of the scratch; the read-backs use the lower half): the copy
-    // is then a plain stream operation and needs no host synchronisation here
-    static_assert(128 + kHyperHeader + kMaxD <= 256, "pinned scratch layout");
-    double* scratch = ctx->pinned_scratch(256);
-    if (!scratch) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    double* h = scratch + 128;
-    constexpr size_t kHyperBytes = (size_t)(kHyperHeader + kMaxD) * 8;
-    std::memset(h, 0, kHyperBytes);
+    // staged in pinned memory (FitScratch::kThetaAt; the read-backs lie below it): the copy is then a plain stream
+    // operation and needs no host synchronisation here
+    double* scratch = stage ? nullptr : ctx->pinned_scratch(FitScratch::doubles(false));
+    if (!stage && !scratch) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    double* h = stage ? stage : scratch + FitScratch::kThetaAt;
+    std::memset(h, 0, FitScratch::kThetaDoubles * 8);
     h[0] = (double)n; h[1] = (double)d; h[2] = (double)th.kernel; h[3] = (double)n_ls;
     h[4] = th.variance; h[5] = th.lik; h[6] = th.mean_c;
-    for (int k = 0; k < kMaxD; ++k) h[kHyperHeader + k] = th.ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
-    HIPCHECK(hipMemcpyAsync(hyper.p, h, kHyperBytes, hipMemcpyHostToDevice, st()));
+    expand_ls(th.ls, n_ls, h + kHyperHeader);
+    HIPCHECK(hipMemcpyAsync(hyper.p, h, FitScratch::kThetaDoubles * 8, hipMemcpyHostToDevice, st()));
     return GPSO_OK;
   }
 
@@ -1008,172 +1014,180 @@ struct EngineT : Engine {
     if (sizeof(TF) == 4)
       return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context (the LOO objective "
                                    "of a float factor is not supported)");
-    double g_nlml[kGradMaxLs + 3], g_loo[kGradMaxLs + 3], f_loo = 0.0;
-    const int rc = fit_eval_impl(th, nlml, g_nlml, &f_loo, g_loo);
-    if (rc != GPSO_OK) return rc;
-    if (loss) *loss = f_loo;
-    if (grad)
-      for (int h = 0; h < n_ls + 3; ++h) grad[h] = g_loo[h];
+    double g_nlml[kGradMaxLs + 3], f_loo = 0.0;  // (the NLML gradient is computed whether or not the caller wants it)
+    return fit_eval_impl(th, nlml, g_nlml, loss ? loss : &f_loo, grad);
+  }
+
+  // ---- one fit call (fit_call.hpp): the plan is decided here and goes down, the stages fill the record ----
+  int fit_eval_impl(const Theta* thp, double* nlml, double* grad, double* loo_loss, double* loo_grad) {
+    ctx->tick_timing();
+    const FitPlan plan = FitPlan::make(grad != nullptr, loo_loss != nullptr, fused_small && small_fit_eligible(n, dp), ctx->timing, n);
+    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "%s before gpso_set_data", plan.who);
+    if (!thp) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
+    const Theta& th = *thp;
+    int rc = refuse_if_async(plan.who);
+    if (rc) return rc;
+    if (plan.loo && n < 2) return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs at least two training points (N=%lld)", (long long)n);
+    FitCall call = FitCall::begun(ctx->pinned_scratch(FitScratch::doubles(plan.loo)));
+    if (!call.scratch) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+    if (plan.loo && (rc = ensure_loo_buffers())) return rc;
+    if ((rc = ensure_fit_buffers())) return rc;
+    if ((rc = set_theta(th, plan.theta_from_host(), call.theta_stage()))) return rc;
+    // (tile rows of linv_p beyond a one-launch fit's that may hold old data; every other fit writes, or will write, all 8)
+    const int zero_tile_rows = res.fit_begun(plan.tile_rows());
+    reset_generation();
+    hipStream_t s = st();
+    if ((rc = fit_span_begin(s))) return rc;
+    if (grad && (rc = ensure(kinvb, (size_t)npad * npad * sizeof(TF)))) return rc;
+    ctx->last_count[2] = plan.small ? GPSO_FITMATH_SMALL : (sizeof(TF) == 8 ? GPSO_FITMATH_F64 : GPSO_FITMATH_F32);  // (fit_planes_for: the plane paths' own)
+    if ((rc = plan.small ? enqueue_small_fit(plan, call, th, zero_tile_rows, s) : enqueue_dense_fit(plan, call, th, s))) return rc;
+    if (!plan.split_deferred() && (rc = pack_bf16())) return rc;
+    if ((rc = enqueue_loo_tail(plan, call, th, s))) return rc;
+    return finish_fit(plan, call, s, nlml, grad, loo_loss, loo_grad);
+  }
+
+  // The timed span of a fit-side call (gpso_fit_eval*, gpso_fit_eval_u_batch, gpso_append): last_ms[2] is the stream time
+  // between the two.  The close comes behind the call's last launch: it asks whether every launch went out, records its
+  // event BEFORE `wait` ends the call and reads the time behind it
+  int fit_span_begin(hipStream_t s) {
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
+    return GPSO_OK;
+  }
+  template <typename Wait>
+  int fit_span_end(hipStream_t s, Wait&& wait /* -> hipError_t */) {
+    if (int rc = launch_status()) return rc;
+    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
+    HIPCHECK(wait());
+    float ms = 0;
+    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
     return GPSO_OK;
   }
 
-  static constexpr size_t kLooHostAt = 256;  // the LOO scalars in the pinned scratch: behind set_theta's staging block
-  int fit_eval_impl(const Theta* thp, double* nlml, double* grad, double* loo_loss, double* loo_grad) {
-    ctx->tick_timing();
-    const bool want_loo = loo_loss != nullptr;
-    const char* who = want_loo ? "gpso_fit_eval_loo" : "gpso_fit_eval";
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "%s before gpso_set_data", who);
-    if (!thp) return ctx->fail(GPSO_E_ARG, "lengthscales must not be NULL");
-    const Theta& th = *thp;
-    int rc = refuse_if_async(who);
-    if (rc) return rc;
-    if (want_loo) {
-      if (n < 2) return ctx->fail(GPSO_E_ARG, "gpso_fit_eval_loo needs at least two training points (N=%lld)", (long long)n);
-      // (the scratch at its final size before anything below takes a pointer into it)
-      if (!ctx->pinned_scratch(kLooHostAt + 8 + kGradMaxLs + 3)) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-      if ((rc = ensure(loov, (size_t)kLooVecs * npad * 8))) return rc;
-      if ((rc = ensure(loo_scal, (size_t)(8 + kGradMaxLs + 3) * 8))) return rc;
+  // N <= 128: the whole evaluation in ONE launch (fit.hip: small_fit_kernel)
+  int enqueue_small_fit(const FitPlan& plan, FitCall& call, const Theta& th, int zero_tile_rows, hipStream_t s) {
+    SmallFitArgs a{};
+    a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.hyper = as<double>(hyper);
+    expand_ls(th.ls, n_ls, a.ls);
+    a.n = (int)n; a.d = d; a.dp = dp; a.kernel = th.kernel; a.n_ls = n_ls; a.want_grad = plan.grad ? 1 : 0;
+    a.zero_tile_rows = zero_tile_rows;
+    a.variance = th.variance; a.noise = th.lik; a.mean_c = th.mean_c;
+    a.sdiag = s_dev();
+    a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
+    a.Lf = Lf.p; a.linv = linv.p; a.kinv = plan.grad ? kinvb.p : nullptr;
+    a.white = white.p; a.alpha_f = alpha_f.p; a.alpha_p = alpha.p; a.linv_p = linv_p.p;
+    a.diag64 = as<double>(logdet); a.kinv_diag = as<double>(kinv_diag); a.scal = as<double>(scal);
+    // the loss, the factorisation's verdict and the gradient land in pinned host memory straight from the kernel
+    a.scal_host = call.readback();
+    a.done_token = call.arm_fit_token(plan.timed ? 0.0 : ctx->next_token());
+    return launch_small_fit<TF, TP>(s, a) ? launch_status() : GPSO_OK;
+  }
+
+  // Side streams and events of the two-level fits (FitPlanes), made when the first such fit needs them.  Every object under
+  // its own check: what a failed call left half done the next one completes.  The look-ahead stream of a double fit gets
+  // the highest priority, a float fit's is plain non-blocking
+  int ensure_fit_streams(bool with_inverse) {
+    int lo_p = 0, hi_p = 0;
+    if (ctx->side_stream == nullptr && sizeof(TF) == 8) {
+      (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);  // (hi_p = the numerically smallest = highest priority)
+      HIPCHECK(hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, hi_p));
     }
-    rc = ensure_fit_buffers();
-    if (rc) return rc;
-    const bool small = fused_small && small_fit_eligible(n, dp);
-    if ((rc = set_theta(th, !small))) return rc;
-    // (tile rows of linv_p beyond a one-launch fit's that may hold old data; every other fit writes, or will write, all 8)
-    const int zero_tile_rows = res.fit_begun(small ? (int)((n + 15) / 16) : 8);
-    reset_generation();
-    hipStream_t s = st();
-    double fit_token = 0.0;
-    bool linv_p_deferred = false;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
-    if (grad && (rc = ensure(kinvb, (size_t)npad * npad * sizeof(TF)))) return rc;
-    ctx->last_count[2] = small ? GPSO_FITMATH_SMALL : (sizeof(TF) == 8 ? GPSO_FITMATH_F64 : GPSO_FITMATH_F32);
-    if (small) {
-      // N <= 128: the whole evaluation in ONE launch (fit.hip: small_fit_kernel)
-      SmallFitArgs a{};
-      a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.hyper = as<double>(hyper);
-      for (int k = 0; k < kMaxD; ++k) a.ls[k] = th.ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
-      a.n = (int)n; a.d = d; a.dp = dp; a.kernel = th.kernel; a.n_ls = n_ls; a.want_grad = grad ? 1 : 0;
-      a.zero_tile_rows = zero_tile_rows;
-      a.variance = th.variance; a.noise = th.lik; a.mean_c = th.mean_c;
-      a.sdiag = s_dev();
-      a.xs64 = as<double>(xs64); a.xnorm64 = as<double>(xnorm64); a.xs_p64 = as<double>(xs_p64);
-      a.Lf = Lf.p; a.linv = linv.p; a.kinv = grad ? kinvb.p : nullptr;
-      a.white = white.p; a.alpha_f = alpha_f.p; a.alpha_p = alpha.p; a.linv_p = linv_p.p;
-      a.diag64 = as<double>(logdet); a.kinv_diag = as<double>(kinv_diag); a.scal = as<double>(scal);
-      // the loss, the factorisation's verdict and the gradient land in pinned host memory straight from the kernel
-      a.scal_host = ctx->pinned_scratch(8 + kGradMaxLs + 3);
-      if (!a.scal_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-      fit_token = ctx->timing ? 0.0 : ctx->next_token();  // (slot 7 of the scalars: unused by the layout)
-      a.scal_host[7] = 0.0;
-      a.done_token = fit_token;
-      if ((rc = launch_small_fit<TF, TP>(s, a))) return launch_status();
+    if (ctx->side_stream == nullptr) HIPCHECK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+    if (with_inverse && ctx->inv_stream == nullptr) HIPCHECK(hipStreamCreateWithFlags(&ctx->inv_stream, hipStreamNonBlocking));
+    hipEvent_t* const evs[4] = {&ctx->ev_col, &ctx->ev_chain, &ctx->ev_panel, &ctx->ev_inv};  // (the last two: the inverse's)
+    for (int i = 0; i < (with_inverse ? 4 : 2); ++i)
+      if (*evs[i] == nullptr) HIPCHECK(hipEventCreateWithFlags(evs[i], hipEventDisableTiming));
+    return GPSO_OK;
+  }
+  // What launch_potrf gets beside the matrices at these hyper-parameters: *use stays NULL for a single-level fit (and a
+  // two-level one that runs as round 5's did), else it is `planes`, filled
+  int fit_planes_for(const Theta& th, FitPlanes& planes, const FitPlanes** use) {
+    if constexpr (sizeof(TF) == 4) {
+      if (fit_planes_mode == 0 || npad <= (single_level_max >= 0 ? single_level_max : 3584)) return GPSO_OK;
+      for (DevBuf* b : {&pl_L, &pl_X, &pl_XT, &pl_WT})
+        if (int rc = ensure(*b, fit_plane_set_bytes(npad))) return rc;
+      planes = FitPlanes{static_cast<unsigned short*>(pl_L.p), static_cast<unsigned short*>(pl_X.p),
+                         static_cast<unsigned short*>(pl_XT.p), static_cast<unsigned short*>(pl_WT.p),
+                         (int64_t)npad * npad, (int)(npad / 32)};
+      if (int rc = ensure_fit_streams(false)) return rc;
+      planes.cu_count = ctx->cu_count;
+      // fp16 pieces (three MFMAs per product) when the hyper-parameters leave every plane set inside fp16's range
+      // after its power-of-two scaling; bf16 pieces (six) otherwise -- the fallback rung
+      if (fit_planes_mode == 2) (void)fit_plane_scales(th.variance, th.lik, planes, res.have_s ? s_max : 0.0);
+      ctx->last_count[2] = planes.np == 2 ? GPSO_FITMATH_F16X3 : GPSO_FITMATH_BF16X6;
     } else {
-      if ((rc = scale_inputs())) return rc;
-      int* info_dev = reinterpret_cast<int*>(as<double>(scal) + 1);
-      launch_gram<TF>(s, as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<TF>(K), info_dev, s_dev());
-      // (the single-level factorisation writes all of L^-1 that is ever read: no 4 N_pad^2-byte zero fill -- 10 us at C3)
-      if (!potrf_is_single_level<TF>(npad, single_level_max))
-        HIPCHECK(hipMemsetAsync(linv.p, 0, (size_t)npad * npad * sizeof(TF), s));
-      FitPlanes planes{};
-      const FitPlanes* pl = nullptr;
-      if constexpr (sizeof(TF) == 4) {
-        if (fit_planes_mode != 0 && npad > (single_level_max >= 0 ? single_level_max : 3584)) {
-          for (DevBuf* b : {&pl_L, &pl_X, &pl_XT, &pl_WT})
-            if ((rc = ensure(*b, fit_plane_set_bytes(npad)))) return rc;
-          planes = FitPlanes{static_cast<unsigned short*>(pl_L.p), static_cast<unsigned short*>(pl_X.p),
-                             static_cast<unsigned short*>(pl_XT.p), static_cast<unsigned short*>(pl_WT.p),
-                             (int64_t)npad * npad, (int)(npad / 32)};
-          if (ctx->side_stream == nullptr) {
-            HIPCHECK(hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_col, hipEventDisableTiming));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-          }
-          planes.cu_count = ctx->cu_count;
-          planes.side = ctx->side_stream;
-          planes.ev_col = ctx->ev_col;
-          planes.ev_chain = ctx->ev_chain;
-          // fp16 pieces (three MFMAs per product) when the hyper-parameters leave every plane set inside fp16's range
-          // after its power-of-two scaling; bf16 pieces (six) otherwise -- the fallback rung
-          if (fit_planes_mode == 2) (void)fit_plane_scales(th.variance, th.lik, planes, res.have_s ? s_max : 0.0);
-          pl = &planes;
-          ctx->last_count[2] = planes.np == 2 ? GPSO_FITMATH_F16X3 : GPSO_FITMATH_BF16X6;
-        }
-      } else {
-        // double fits above the single-level limit (round 6): the diagonal blocks' chains are looked ahead on a side stream
-        // and the level-doubling inverse runs on a third one, pair by pair, as soon as the panels it reads are final
-        // (fit.hip: launch_potrf) -- GPSO_OPT_FIT_OVERLAP = 0 keeps round 5's sequential schedule (same bits either way)
-        if (fit_overlap && !potrf_is_single_level<TF>(npad, single_level_max)) {
-          if (ctx->side_stream == nullptr) {
-            int lo_p = 0, hi_p = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo_p, &hi_p);  // (hi_p = the numerically smallest = highest priority)
-            HIPCHECK(hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, hi_p));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_col, hipEventDisableTiming));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_chain, hipEventDisableTiming));
-          }
-          if (ctx->inv_stream == nullptr) {
-            HIPCHECK(hipStreamCreateWithFlags(&ctx->inv_stream, hipStreamNonBlocking));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_panel, hipEventDisableTiming));
-            HIPCHECK(hipEventCreateWithFlags(&ctx->ev_inv, hipEventDisableTiming));
-          }
-          planes.side = ctx->side_stream;
-          planes.ev_col = ctx->ev_col;
-          planes.ev_chain = ctx->ev_chain;
-          planes.inv = ctx->inv_stream;
-          planes.ev_panel = ctx->ev_panel;
-          planes.ev_inv = ctx->ev_inv;
-          planes.overlap = fit_overlap;
-          pl = &planes;
-        }
-      }
-      const int done = launch_potrf<TF>(s, as<TF>(K), as<TF>(Lf), as<TF>(linv), as<TF>(work),
-                                        grad ? as<TF>(kinvb) : nullptr, n, npad, as<double>(logdet), info_dev,
-                                        single_level_max, pl);
-      bool inv_done = (done & 1) != 0, xt_ready = false;
-      // (the single-level path leaves the padding blocks of L^-1 unwritten; the K^-1 = L^-T L^-1 GEMM of launch_gradient
-      // would read them -- that path always builds K^-1 beside the factorisation: hold it to that)
-      if (grad && potrf_is_single_level<TF>(npad, single_level_max) && (done & 2) == 0)
-        return ctx->fail(GPSO_E_STATE, "internal: the single-level factorisation did not leave K^-1 for the gradient");
-      if constexpr (sizeof(TF) == 4) {
-        if (!inv_done && pl != nullptr && trtri_bf16_applies(npad, fit_outer_panel(npad))) {
-          launch_trtri_bf16(s, as<float>(linv), planes, npad, fit_outer_panel(npad), grad);
-          inv_done = true;
-          xt_ready = true;
-        }
-      }
-      if (!inv_done) launch_trtri<TF>(s, as<TF>(Lf), as<TF>(linv), as<TF>(work), npad, fit_outer_panel(npad));
-      float* linv_max_out = f16_max_for_fit();  // (may allocate amax_rows: before the argument list below)
-      launch_solve_alpha<TF>(s, as<TF>(linv), as<double>(y64), n, npad, th.mean_c, as<double>(logdet),
-                             as<TF>(white), as<TF>(alpha_f), as<double>(apart), as<double>(kinv_diag),
-                             as<double>(scal), alpha.p, sizeof(TP) == 8, as<float>(amax_rows), linv_max_out);
-      if (grad)
-        launch_gradient<TF>(s, as<TF>(linv), as<TF>(alpha_f), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp,
-                            n_ls, ls_dev(), kp, as<TF>(kinvb), (done & 2) != 0, as<double>(gpart),
-                            as<double>(scal) + 8, xt_ready ? &planes : nullptr);
-      // the packed f32 / f64 copy of L^-1 feeds the NATIVE tile kernel only: a posterior that is going to predict with
-      // split math (the default of float-predict contexts) packs it when -- if ever -- something asks for it
-      // (ensure_linv_p: the self-test walking down GPSO_MATH_AUTO's ladder, a hand-off of all buffers)
-      linv_p_deferred = bf16_usable();
-      if (!linv_p_deferred) launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));  // (alpha's predict-type copy: alpha_sum_kernel)
+      // double fits above the single-level limit (round 6): the diagonal blocks' chains are looked ahead on a side stream
+      // and the level-doubling inverse runs on a third one, pair by pair, as soon as the panels it reads are final
+      // (fit.hip: launch_potrf) -- GPSO_OPT_FIT_OVERLAP = 0 keeps round 5's sequential schedule (same bits either way)
+      if (!fit_overlap || potrf_is_single_level<TF>(npad, single_level_max)) return GPSO_OK;
+      if (int rc = ensure_fit_streams(true)) return rc;
+      planes.inv = ctx->inv_stream;
+      planes.ev_panel = ctx->ev_panel;
+      planes.ev_inv = ctx->ev_inv;
+      planes.overlap = fit_overlap;
     }
-    const bool split_deferred = grad && !small;  // (see ensure_split_pieces)
-    if (!split_deferred && (rc = pack_bf16())) return rc;
-    constexpr size_t kHostDoubles = 8 + kGradMaxLs + 3;
-    double* host = ctx->pinned_scratch(kHostDoubles);
-    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    double loo_token = 0.0;
+    planes.side = ctx->side_stream;
+    planes.ev_col = ctx->ev_col;
+    planes.ev_chain = ctx->ev_chain;
+    *use = &planes;
+    return GPSO_OK;
+  }
+
+  // any N: Gram, factorisation, inverse, alpha and the NLML, the gradient where wanted, the native-type packing
+  int enqueue_dense_fit(const FitPlan& plan, FitCall& call, const Theta& th, hipStream_t s) {
+    if (int rc = scale_inputs()) return rc;
+    int* info_dev = reinterpret_cast<int*>(as<double>(scal) + 1);
+    launch_gram<TF>(s, as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<TF>(K), info_dev, s_dev());
+    // (the single-level factorisation writes all of L^-1 that is ever read: no 4 N_pad^2-byte zero fill -- 10 us at C3)
+    const bool single_level = potrf_is_single_level<TF>(npad, single_level_max);
+    if (!single_level) HIPCHECK(hipMemsetAsync(linv.p, 0, (size_t)npad * npad * sizeof(TF), s));
+    FitPlanes planes{};
+    const FitPlanes* pl = nullptr;
+    if (int rc = fit_planes_for(th, planes, &pl)) return rc;
+    const int done = launch_potrf<TF>(s, as<TF>(K), as<TF>(Lf), as<TF>(linv), as<TF>(work),
+                                      plan.grad ? as<TF>(kinvb) : nullptr, n, npad, as<double>(logdet), info_dev,
+                                      single_level_max, pl);
+    bool inv_done = (done & 1) != 0, xt_ready = false;
+    // (the single-level path leaves the padding blocks of L^-1 unwritten; the K^-1 = L^-T L^-1 GEMM of launch_gradient
+    // would read them -- that path always builds K^-1 beside the factorisation: hold it to that)
+    if (plan.grad && single_level && (done & 2) == 0)
+      return ctx->fail(GPSO_E_STATE, "internal: the single-level factorisation did not leave K^-1 for the gradient");
+    if constexpr (sizeof(TF) == 4) {
+      if (!inv_done && pl != nullptr && trtri_bf16_applies(npad, fit_outer_panel(npad))) {
+        launch_trtri_bf16(s, as<float>(linv), planes, npad, fit_outer_panel(npad), plan.grad);
+        inv_done = true;
+        xt_ready = true;
+      }
+    }
+    if (!inv_done) launch_trtri<TF>(s, as<TF>(Lf), as<TF>(linv), as<TF>(work), npad, fit_outer_panel(npad));
+    float* linv_max_out = f16_max_for_fit();  // (may allocate amax_rows: before the argument list below)
+    launch_solve_alpha<TF>(s, as<TF>(linv), as<double>(y64), n, npad, th.mean_c, as<double>(logdet),
+                           as<TF>(white), as<TF>(alpha_f), as<double>(apart), as<double>(kinv_diag),
+                           as<double>(scal), alpha.p, sizeof(TP) == 8, as<float>(amax_rows), linv_max_out);
+    if (plan.grad)
+      launch_gradient<TF>(s, as<TF>(linv), as<TF>(alpha_f), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp,
+                          n_ls, ls_dev(), kp, as<TF>(kinvb), (done & 2) != 0, as<double>(gpart),
+                          as<double>(scal) + 8, xt_ready ? &planes : nullptr);
+    // the packed f32 / f64 copy of L^-1 feeds the NATIVE tile kernel only: a posterior that is going to predict with
+    // split math (the default of float-predict contexts) packs it when -- if ever -- something asks for it
+    // (ensure_linv_p: the self-test walking down GPSO_MATH_AUTO's ladder, a hand-off of all buffers)
+    call.linv_p_left(bf16_usable());
+    if (!call.linv_p_deferred) launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));  // (alpha's predict-type copy: alpha_sum_kernel)
+    return GPSO_OK;
+  }
+
+  // the LOO launches behind the fit, on the same stream (loo.hip); a plan without LOO enqueues nothing
+  int enqueue_loo_tail(const FitPlan& plan, FitCall& call, const Theta& th, hipStream_t s) {
     if constexpr (sizeof(TF) == 8) {
-      if (want_loo && small) {
+      if (plan.loo && plan.small) {
         // N <= 128: ONE workgroup behind the one-launch fit, its scalars straight into pinned host memory
         LooSmallArgs a{};
         a.kinv = as<double>(kinvb); a.alpha = as<double>(alpha_f); a.kinv_diag = as<double>(kinv_diag);
         a.y64 = as<double>(y64); a.xs = as<double>(xs64); a.ls = ls_dev();
         a.n = (int)n; a.npad = (int)npad; a.dp = dp; a.kernel = th.kernel; a.n_ls = n_ls; a.variance = th.variance;
-        a.vec = nullptr; a.scal = as<double>(loo_scal); a.scal_host = host + kLooHostAt;
-        loo_token = ctx->timing ? 0.0 : ctx->next_token();
-        a.scal_host[7] = 0.0;
-        a.done_token = loo_token;
+        a.vec = nullptr; a.scal = as<double>(loo_scal); a.scal_host = call.loo_readback();
+        a.done_token = call.arm_loo_token(plan.timed ? 0.0 : ctx->next_token());
         if (launch_loo_small(s, a)) return launch_status();
-      } else if (want_loo) {
+      } else if (plan.loo) {
         // any N: S = diag(sqrt c) K^-1 in the Gram buffer, M = S^T S in the factorisation's scratch (both free behind the
         // fit), 2 W over S, then the NLML gradient's own contraction with (kinv := 2 W, alpha := 0); kinvb stays K_y^-1
         double* vec = as<double>(loov);
@@ -1182,17 +1196,22 @@ struct EngineT : Engine {
         launch_gradient<double>(s, as<double>(linv), vec + (size_t)kLooZero * npad, as<double>(xs64), as<double>(xnorm64), n, npad,
                                 d, dp, n_ls, ls_dev(), kp, as<double>(K), true, as<double>(gpart), as<double>(loo_scal) + 8);
         launch_loo_mean_grad(s, vec, n, npad, as<double>(loo_scal) + 8 + n_ls + 2);
-        HIPCHECK(hipMemcpyAsync(host + kLooHostAt, loo_scal.p, kHostDoubles * 8, hipMemcpyDeviceToHost, s));
+        HIPCHECK(hipMemcpyAsync(call.loo_readback(), loo_scal.p, FitScratch::kLooDoubles * 8, hipMemcpyDeviceToHost, s));
       }
     }
-    if ((rc = launch_status())) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
-    if (!small) HIPCHECK(hipMemcpyAsync(host, scal.p, kHostDoubles * 8, hipMemcpyDeviceToHost, s));
-    if (loo_token != 0.0) HIPCHECK(ctx->wait_token(&host[kLooHostAt + 7], loo_token, s));
-    else if (small && fit_token != 0.0 && !ctx->timing && !want_loo) HIPCHECK(ctx->wait_token(&host[7], fit_token, s));
-    else HIPCHECK(ctx->wait(s));
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
+    return GPSO_OK;
+  }
+
+  // closes the span, brings the dense fit's scalars over, waits as the record says, and hands out what the call computed
+  int finish_fit(const FitPlan& plan, const FitCall& call, hipStream_t s, double* nlml, double* grad, double* loo_loss, double* loo_grad) {
+    const double *host = call.readback(), *loo_host = call.loo_readback();
+    const int rc = fit_span_end(s, [&]() -> hipError_t {
+      const hipError_t e = plan.small ? hipSuccess : hipMemcpyAsync(call.readback(), scal.p, FitScratch::kReadbackDoubles * 8, hipMemcpyDeviceToHost, s);
+      if (e != hipSuccess) return e;
+      const FitWait how = call.wait_on(plan);
+      return how == FitWait::Stream ? ctx->wait(s) : ctx->wait_token(call.token_word(how), call.token(how), s);
+    });
+    if (rc) return rc;
     int info;
     std::memcpy(&info, &host[1], sizeof(int));
     if (info != INT_MAX)
@@ -1200,12 +1219,18 @@ struct EngineT : Engine {
     if (nlml) *nlml = host[0];
     if (grad)  // device order: ls..., variance, noise, then -sum(alpha)
       for (int h = 0; h < n_ls + 3; ++h) grad[h] = host[8 + h];
-    if (want_loo) {
-      *loo_loss = host[kLooHostAt];
-      for (int h = 0; h < n_ls + 3; ++h) loo_grad[h] = host[kLooHostAt + 8 + h];
+    if (plan.loo) {
+      *loo_loss = loo_host[0];
+      if (loo_grad)
+        for (int h = 0; h < n_ls + 3; ++h) loo_grad[h] = loo_host[8 + h];
     }
-    res.fit_done(grad != nullptr, linv_p_deferred, split_deferred, bf16_usable());
+    res.fit_done(plan.grad, call.linv_p_deferred, plan.split_deferred(), bf16_usable());
     return GPSO_OK;
+  }
+  // the LOO vectors and scalars on the device (gpso_loo, gpso_fit_eval_loo)
+  int ensure_loo_buffers() {
+    if (int rc = ensure(loov, (size_t)kLooVecs * npad * 8)) return rc;
+    return ensure(loo_scal, FitScratch::kLooDoubles * 8);
   }
   // ---- leave-one-out predictive of the resident fitted posterior (loo.hip): reads alpha and kinv_diag, changes nothing a
   // predict or a later call reads
@@ -1215,8 +1240,7 @@ struct EngineT : Engine {
     int rc = refuse_if_async("gpso_loo");
     if (rc) return rc;
     if (n < 2) return ctx->fail(GPSO_E_ARG, "gpso_loo needs at least two training points (N=%lld)", (long long)n);
-    if ((rc = ensure(loov, (size_t)kLooVecs * npad * 8))) return rc;
-    if ((rc = ensure(loo_scal, (size_t)(8 + kGradMaxLs + 3) * 8))) return rc;
+    if ((rc = ensure_loo_buffers())) return rc;
     hipStream_t s = st();
     double* vec = as<double>(loov);
     launch_loo_points<TF>(s, as<TF>(alpha_f), as<double>(kinv_diag), as<double>(y64), n, npad, vec, as<double>(loo_scal));
@@ -1266,7 +1290,7 @@ struct EngineT : Engine {
       const double* t = th + (size_t)e * H;
       std::memset(r, 0, kSmallBatchTheta * 8);
       r[0] = t[n_ls_]; r[1] = t[n_ls_ + 1]; r[2] = t[n_ls_ + 2];
-      for (int k = 0; k < kMaxD; ++k) r[kHyperHeader + k] = t[n_ls_ == 1 ? 0 : std::min(k, n_ls_ - 1)];
+      expand_ls(t, n_ls_, r + kHyperHeader);
     }
     // results: straight into pinned host memory from the kernel (as the single fit's scalars), read behind the wait
     const size_t out_doubles = (size_t)nv * (1 + H) + ((size_t)nv + 1) / 2;
@@ -1274,7 +1298,7 @@ struct EngineT : Engine {
     if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
     hipStream_t s = st();
     HIPCHECK(hipMemcpyAsync(batch_theta.p, stage, (size_t)nv * kSmallBatchTheta * 8, hipMemcpyHostToDevice, s));
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
+    if ((rc = fit_span_begin(s))) return rc;
     SmallBatchArgs a{};
     a.x64 = as<double>(x64); a.y64 = as<double>(y64); a.theta = as<double>(batch_theta);
     a.loss = host; a.grad = host + nv; a.info = reinterpret_cast<int*>(host + (size_t)nv * (1 + H));
@@ -1284,11 +1308,7 @@ struct EngineT : Engine {
       rc = launch_status();
       return rc ? rc : ctx->fail(GPSO_E_HIP, "internal: the batched fit refused %d entries", nv);
     }
-    if ((rc = launch_status())) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
-    HIPCHECK(ctx->wait(s));
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
+    if ((rc = fit_span_end(s, [&] { return ctx->wait(s); }))) return rc;
     std::memcpy(loss, a.loss, (size_t)nv * 8);
     if (grad) std::memcpy(grad, a.grad, (size_t)nv * H * 8);
     std::memcpy(info, a.info, (size_t)nv * sizeof(int));
@@ -1301,6 +1321,49 @@ struct EngineT : Engine {
     launch_pack_linv<TF, TP>(st(), as<TF>(linv), n, npad, as<TP>(linv_p));
     res.linv_p_packed();
     return launch_status();
+  }
+
+  // gpso_append where extending in place does not pay (`refit` says why): the posterior of the n + k points from scratch at
+  // the resident hyper-parameters.  Returns 1, or the refit's negative status with the first n points' posterior put back
+  int append_by_refit(const double* Xn, const double* yn, const double* sn, int64_t k, bool sn_nonzero, const char* refit, double* nlml) {
+    const int64_t n_new = n + k;
+    std::vector<double> X(x_host), y(y_host);
+    X.insert(X.end(), Xn, Xn + (size_t)k * d);
+    y.insert(y.end(), yn, yn + (size_t)k);
+    // (set_data clears the per-point noise: the refit carries it along, the new points' values behind the resident ones)
+    const bool with_s = res.have_s || sn_nonzero, had_s = res.have_s;
+    std::vector<double> sv;
+    if (with_s) {
+      sv = res.have_s ? s_host : std::vector<double>((size_t)n, 0.0);
+      if (sn != nullptr) sv.insert(sv.end(), sn, sn + (size_t)k);
+      else sv.resize((size_t)n_new, 0.0);
+    }
+    const Theta th = resident_theta();
+    const int d_ = d;
+    const int64_t n_old = n;
+    int rc = set_data(X.data(), y.data(), n_new, d_);
+    if (rc == GPSO_OK && with_s) rc = set_noise_diag(sv.data(), n_new);
+    if (rc == GPSO_OK) rc = fit_eval(&th, nlml, nullptr);
+    if (rc < 0) {
+      // the header's promise holds on this path too: a failed append leaves the posterior of the first n points resident
+      // (set_data dropped it: put the old points back and refit at the resident hyper-parameters -- the fit that
+      // succeeded before the call)
+      const std::string why = ctx->err;
+      X.resize((size_t)n_old * d_);
+      y.resize((size_t)n_old);
+      int rc2 = set_data(X.data(), y.data(), n_old, d_);
+      if (rc2 == GPSO_OK && had_s) {
+        sv.resize((size_t)n_old);
+        rc2 = set_noise_diag(sv.data(), n_old);
+      }
+      if (rc2 == GPSO_OK) rc2 = fit_eval(&th, nullptr, nullptr);
+      if (rc2 < 0) return ctx->fail(rc, "%s (and the posterior of the first %lld points could not be restored: status %d -- "
+                                        "gpso_set_data + gpso_fit_eval start over)", why.c_str(), (long long)n_old, rc2);
+      return ctx->fail(rc, "%s (the posterior of the first %lld points is resident again)", why.c_str(), (long long)n_old);
+    }
+    ctx->fail(1, "gpso_append: posterior of the %lld points refitted from scratch at the resident hyper-parameters (%s)",
+              (long long)n_new, refit);
+    return 1;
   }
 
   // ---- rank-k append at the resident hyper-parameters (append.hip) ------------------------------------------------------
@@ -1337,45 +1400,7 @@ struct EngineT : Engine {
     // (measured, float, N = 2048: append of 64 points 0.55 ms, of 7 points 0.06 ms, posterior fit 0.52 ms -- the k x k corner
     // is factorised by one workgroup; at N = 8192 the same 64 points take 1.1 ms against 4.2: profiles/r05_append_bench.jsonl)
     else if (k > 32 && npad < 4096) refit = "more than 32 new points beside fewer than 4096: the refit is as fast";
-    if (refit != nullptr) {
-      std::vector<double> X(x_host), y(y_host);
-      X.insert(X.end(), Xn, Xn + (size_t)k * d);
-      y.insert(y.end(), yn, yn + (size_t)k);
-      // (set_data clears the per-point noise: the refit carries it along, the new points' values behind the resident ones)
-      const bool with_s = res.have_s || sn_nonzero, had_s = res.have_s;
-      std::vector<double> sv;
-      if (with_s) {
-        sv = res.have_s ? s_host : std::vector<double>((size_t)n, 0.0);
-        if (sn != nullptr) sv.insert(sv.end(), sn, sn + (size_t)k);
-        else sv.resize((size_t)n_new, 0.0);
-      }
-      const Theta th = resident_theta();
-      const int d_ = d;
-      const int64_t n_old = n;
-      int rc = set_data(X.data(), y.data(), n_new, d_);
-      if (rc == GPSO_OK && with_s) rc = set_noise_diag(sv.data(), n_new);
-      if (rc == GPSO_OK) rc = fit_eval(&th, nlml, nullptr);
-      if (rc < 0) {
-        // the header's promise holds on this path too: a failed append leaves the posterior of the first n points resident
-        // (set_data dropped it: put the old points back and refit at the resident hyper-parameters -- the fit that
-        // succeeded before the call)
-        const std::string why = ctx->err;
-        X.resize((size_t)n_old * d_);
-        y.resize((size_t)n_old);
-        int rc2 = set_data(X.data(), y.data(), n_old, d_);
-        if (rc2 == GPSO_OK && had_s) {
-          sv.resize((size_t)n_old);
-          rc2 = set_noise_diag(sv.data(), n_old);
-        }
-        if (rc2 == GPSO_OK) rc2 = fit_eval(&th, nullptr, nullptr);
-        if (rc2 < 0) return ctx->fail(rc, "%s (and the posterior of the first %lld points could not be restored: status %d -- "
-                                          "gpso_set_data + gpso_fit_eval start over)", why.c_str(), (long long)n_old, rc2);
-        return ctx->fail(rc, "%s (the posterior of the first %lld points is resident again)", why.c_str(), (long long)n_old);
-      }
-      ctx->fail(1, "gpso_append: posterior of the %lld points refitted from scratch at the resident hyper-parameters (%s)",
-                (long long)n_new, refit);
-      return 1;
-    }
+    if (refit != nullptr) return append_by_refit(Xn, yn, sn, k, sn_nonzero, refit, nlml);
     hipStream_t s = st();
     int rc;
     const int kpad = append_kp((int)k);
@@ -1390,7 +1415,7 @@ struct EngineT : Engine {
     double* stage = ctx->pinned_stage((size_t)k * d + 2 * (size_t)k);  // (waits for the stream)
     double* host = ctx->pinned_scratch(8);
     if (!stage || !host) return ctx->fail(GPSO_E_OOM, "pinned host staging");
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[4], s));
+    if ((rc = fit_span_begin(s))) return rc;
     // (no copies: append_cross_kernel reads the new points from this pinned buffer and files them in x64 / y64 itself)
     std::memcpy(stage, Xn, (size_t)k * d * 8);
     std::memcpy(stage + (size_t)k * d, yn, (size_t)k * 8);
@@ -1424,11 +1449,7 @@ struct EngineT : Engine {
       if (res.linv_p == Copy::Valid) launch_pack_linv<TF, TP>(s, as<TF>(linv), rows, npad, as<TP>(linv_p), rt0);
     };
     repack(n_new);
-    if ((rc = launch_status())) return rc;
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[5], s));
-    HIPCHECK(ctx->wait(s));
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[4], ctx->ev[5]) == hipSuccess) ctx->last_ms[2] = ms;
+    if ((rc = fit_span_end(s, [&] { return ctx->wait(s); }))) return rc;
     if (host[1] != 1.0) {
       // K22 + noise I - L21 L21^T is not positive definite: the posterior of the n points is still what the device holds
       // (append_cols_kernel did not run); the tiles just repacked and the scaled-input rows go back to their padding state

@@ -169,3 +169,17 @@ def test_best_call_header_on_its_own(tmp_path):
                     "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and r.stdout == "best_call_check: ok\n", (r.returncode, r.stdout, r.stderr)
+
+
+def test_fit_call_header_on_its_own(tmp_path):
+    """tools/fit_call_check.cpp -- csrc/fit_call.hpp compiled by the host compiler alone -- passes its own checks: every plan
+    and its derived members, the wait rule against a written-out table, a token's word zeroed where one is armed, nothing
+    written without a scratch, and the scratch map's sizes."""
+    import shutil
+
+    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+    exe = str(tmp_path / "fit_call_check")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tools", "fit_call_check.cpp"),
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout == "fit_call_check: ok\n", (r.returncode, r.stdout, r.stderr)

@@ -4,8 +4,10 @@ from the same posteriors in a fresh process (a list of engine configurations x s
 are printed side by side, differing rows marked.  A last section hashes (loss, grad_u, theta) of every entry point in the
 optimiser's variables u (and of the batch) at the shapes of tests/test_gpu_theta.py; --theta runs that section alone.
 --points runs (alone, and only then) the section of the calls that evaluate the posterior at given points: points_section.
+--fit runs (alone, and only then) the section of the exact-GP fit call: fit_section, every row once with the library's
+timing on and once with it off (the two wait differently); the pairs must agree with each other as well.
 
-    python tools/ab_bits.py [--theta | --points] pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
+    python tools/ab_bits.py [--theta | --points | --fit] pygpso_amd/libgpso_hip_prev.so pygpso_amd/libgpso_hip.so
 """
 import hashlib
 import json
@@ -119,6 +121,97 @@ def points_section(out):
     eng.close()
 
 
+def fit_section(out):
+    """What a fit call leaves behind, through every branch of it (csrc/api.hip: fit_eval_impl's stages) at the
+    smallest shapes of the suite that reach it: the one-launch fit, the single-level dense fit, the forced two-level fits
+    (double: GPSO_OPT_FIT_OVERLAP 0 / 2 / 3, float: the fp16 and bf16 plane paths), both LOO tails (also behind a plain fit, so
+    the pinned scratch grows between the calls), the batch, and gpso_append in place, by refit and refused.  A fit row hashes
+    (nlml, grad, GPSO_FITMATH_*, L, L^-1, K^-1 with a gradient, alpha), a LOO row the LOO loss and gradient as well."""
+    import numpy as np
+
+    from pygpso_amd import HipGPEngine
+    from pygpso_amd import _lib as L
+    from tests.helpers import synthetic_leaves, synthetic_problem
+
+    def put(name, *parts):
+        out[name] = hashlib.sha1(b"".join(np.ascontiguousarray(np.asarray(p, dtype=np.float64)).tobytes() for p in parts)).hexdigest()[:12]
+
+    def problem(n, d, noise=1.0e-3, seed=None):
+        X, y = synthetic_problem(n, d, seed=17 + n if seed is None else seed)
+        return X, y, ("Matern52", 0.25 * np.sqrt(d) * np.ones(1), 1.3, noise, float(y.mean()))
+
+    def engine(dtype, timed, two_level=False, overlap=None):
+        eng = HipGPEngine(dtype, precision_check=False)
+        eng.set_timing(timed)
+        if two_level:
+            eng.set_fit_single_level_max(0)
+        if overlap is not None:
+            eng._check(eng._lib.gpso_set_option(eng._h, L.OPT_FIT_OVERLAP, overlap))
+        return eng
+
+    def state(eng, kinv):
+        mats = [L.MAT_CHOL, L.MAT_LINV] + ([L.MAT_KINV] if kinv else [])
+        return [eng.last_count(2)] + [eng.get_matrix(m) for m in mats] + [eng.get_vector(L.VEC_ALPHA)]
+
+    def fit_rows(tag, dtype, n, d, timed, noise=1.0e-3, **kw):
+        X, y, th = problem(n, d, noise)
+        for grad in (True, False):
+            eng = engine(dtype, timed, **kw)
+            eng.set_data(X, y)
+            f, g = eng.fit_eval(*th, want_grad=grad)
+            put(f"fit {tag} N={n} D={d} {dtype} grad={int(grad)} {'timed' if timed else 'untimed'}", f, g if grad else [], *state(eng, grad))
+            eng.close()
+
+    for timed in (True, False):
+        t = "timed" if timed else "untimed"
+        for dtype in ("float64", "mixed", "float32"):
+            fit_rows("one-launch", dtype, 52, 2, timed)
+            fit_rows("one-launch", dtype, 128, 3, timed)
+            fit_rows("single-level", dtype, 300, 3, timed)
+        for overlap in (0, 2, 3):
+            fit_rows(f"two-level overlap={overlap}", "float64", 700, 5, timed, two_level=True, overlap=overlap)
+            fit_rows(f"two-level overlap={overlap}", "float64", 1100, 3, timed, two_level=True, overlap=overlap)
+        for noise in (1.0e-3, 1.0e-2):
+            fit_rows(f"two-level planes noise={noise:g}", "float32", 900, 6, timed, noise=noise, two_level=True)
+        for n, d in ((52, 2), (300, 3)):
+            X, y, th = problem(n, d)
+            for dtype in ("float64", "mixed"):
+                for first_a_plain_fit in (False, True) if dtype == "float64" else (False,):
+                    eng = engine(dtype, timed)
+                    eng.set_data(X, y)
+                    if first_a_plain_fit:
+                        eng.fit_eval(*th, want_grad=False)
+                    loss, g, nlml = eng.fit_eval_loo(*th)
+                    put(f"loo N={n} D={d} {dtype} behind_a_fit={int(first_a_plain_fit)} {t}", loss, g, nlml, *state(eng, True))
+                    eng.close()
+        X, y, th = problem(52, 2)
+        eng = engine("float64", timed)
+        eng.set_data(X, y)
+        U = np.array([[0.3, 0.5, -6.0, 0.1], [0.1, 0.2, -5.0, 0.0], [0.3, -800.0, -6.0, 0.1], [-0.2, 0.4, -7.0, 0.3]])
+        put(f"batch fit_eval_u_batch N=52 D=2 float64 {t}", *eng.fit_eval_u_batch("Matern52", U, 1, True))
+        eng.close()
+        for n0, k, d, dtype in ((297, 3, 3, "float64"), (2041, 7, 12, "float32"), (100, 3, 3, "float64")):
+            X, y, th = problem(n0 + k, d)
+            eng = engine(dtype, timed)
+            eng.set_data(X[:n0], y[:n0])
+            eng.fit_eval(*th, want_grad=False)
+            f, in_place = eng.append(X[n0:], y[n0:])
+            put(f"append N={n0}+{k} D={d} {dtype} in_place={int(in_place)} {t}", f, *state(eng, False))
+            eng.close()
+        # the in-place refusal of tests/test_gpu_append.py: a NaN input, the block is not positive definite
+        X, y, th = problem(300, 3, noise=1.0e-6, seed=11)
+        eng = engine("float64", timed)
+        eng.set_data(X, y)
+        eng.fit_eval(*th, want_grad=False)
+        try:
+            eng.append(np.vstack([X[:2], np.full((1, 3), np.nan)]), np.zeros(3))
+            refused = 0
+        except np.linalg.LinAlgError:
+            refused = 1
+        put(f"append N=300+3 D=3 float64 refused={refused} then predict {t}", eng.n, *eng.predict(synthetic_leaves(400, 3)), *state(eng, False))
+        eng.close()
+
+
 def worker():
     sys.path.insert(0, ROOT)
     import numpy as np
@@ -127,7 +220,7 @@ def worker():
     from tests.helpers import synthetic_leaves, synthetic_problem
 
     out = {}
-    for flag, section in (("--theta", theta_section), ("--points", points_section)):
+    for flag, section in (("--theta", theta_section), ("--points", points_section), ("--fit", fit_section)):
         if flag in sys.argv:
             section(out)
             print("AB_BITS " + json.dumps(out), flush=True)
@@ -194,6 +287,12 @@ def main():
         ndiff += not same
         print(("same  " if same else "DIFF  ") + " ".join(hs) + "  " + k)
     print(f"{ndiff} differing rows of {len(res[0])}")
+    if "--fit" in flags:  # timed against untimed, in every library
+        pairs = [(k, k[:-len(" timed")] + " untimed") for k in res[0] if k.endswith(" timed")]
+        bad = [(lib, a) for lib, r in zip(libs, res) for a, b in pairs if r.get(a) != r.get(b)]
+        for lib, a in bad:
+            print("TIMED != UNTIMED  " + lib + "  " + a)
+        print(f"{len(bad)} of {len(pairs) * len(res)} timed rows differ from their untimed row")
     return 0
 
 
