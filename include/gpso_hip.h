@@ -644,6 +644,10 @@ int gpso_best_ucb_end(gpso_ctx* ctx, int ticket, int64_t* idx, double* mean, dou
  * GPSO_E_STATE where no call on this context, batch and varsigma could be screened. */
 int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my,
                       double* ub, double* flag, double* info);
+/* Diagnostic: the compact list the last gpso_screen_probe on this context left for the survivors' launch, as it stood behind
+ * the probe.  *live (nullable): its rows, min(survivors, room).  key[0 .. min(live, max_rows)): the survivors' indices in the
+ * probed batch, ascending; rows[..][D]: their unscaled float rows.  GPSO_E_STATE before the first probe. */
+int gpso_screen_list(gpso_ctx* ctx, int64_t max_rows, int64_t* key, float* rows, int64_t* live);
 /* The screen's arithmetic on the host (csrc/screen.hpp, the header the device code includes; no context, no GPU):
  * ucb[i] = the finalize stage's ucb of a leaf with mean my[i] and variance share v[i] (NULL: zeros), ub[i] = its bound;
  * the threshold from the largest finite mean; the survive test; the acceptance test of the survivors' winner. */
@@ -652,6 +656,10 @@ int gpso_screen_eval_host(const double* my, const double* v, double variance, do
 double gpso_screen_threshold_host(double max_my, double noise, double varsigma);
 int gpso_screen_survives_host(double my, double ub, double threshold);
 int gpso_screen_accepts_host(double u_star, double threshold, int64_t count, int64_t cap);
+/* The compaction's partition of a batch of m leaves: part w of `parts` owns the leaves [*lo, *hi) -- ascending, every leaf
+ * in exactly one part, every range but the last non-empty one a multiple of 64 long; and how many parts a batch is given. */
+int gpso_screen_partition_host(int64_t m, int parts, int w, int64_t* lo, int64_t* hi);
+int gpso_screen_parts_host(int64_t m);
 
 /* ---- acquisition functions (no counterpart in the reference: it ranks by mean + varsigma * VAR only) ----------------
  *

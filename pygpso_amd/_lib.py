@@ -173,6 +173,9 @@ SIGNATURES = {
     "gpso_screen_threshold_host": (C.c_double, [C.c_double, C.c_double, C.c_double]),
     "gpso_screen_survives_host": (C.c_int, [C.c_double, C.c_double, C.c_double]),
     "gpso_screen_accepts_host": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.c_int64]),
+    "gpso_screen_list": (C.c_int, [C.c_void_p, C.c_int64, _c_int64_p, C.POINTER(C.c_float), _c_int64_p]),
+    "gpso_screen_partition_host": (C.c_int, [C.c_int64, C.c_int, C.c_int, _c_int64_p, _c_int64_p]),
+    "gpso_screen_parts_host": (C.c_int, [C.c_int64]),
     "gpso_grow_rows": (C.c_int64, [C.c_int]),
     "gpso_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p]),
     "gpso_best_ucb_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_double,

@@ -131,6 +131,7 @@ struct Engine {
   virtual int best_ucb_end(int ticket, int64_t* idx, double* mean, double* var, double* ucb) = 0;
   virtual int screen_probe(const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,
                            double* flag, double* info) = 0;
+  virtual int screen_list(int64_t max_rows, int64_t* key, float* rows, int64_t* live) = 0;
   virtual int grow(const double* bounds, int nseg, int d, int depth, double* out) = 0;
   virtual int best_ucb_grow(const double* bounds, int nseg, int depth, const AcqSpec& acq,
                             int64_t* idx, double* mean, double* var, double* ucb) = 0;
@@ -480,9 +481,13 @@ struct EngineT : Engine {
   // predict workspace
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
-  // screened best-UCB calls (screen.hip): every leaf's mean, the blocks' maxima, the survivors' raw rows, the control words
-  // (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
-  DevBuf screen_my, screen_bmax, screen_rows, screen_ctl, screen_cols;
+  // screened best-UCB calls (screen.hip): every leaf's mean, the blocks' maxima, the compaction's counts per part, the
+  // survivors' raw rows, the control words (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
+  DevBuf screen_my, screen_bmax, screen_cnt, screen_rows, screen_ctl, screen_cols;
+  // the compact list the last gpso_screen_probe left, copied out behind it (gpso_screen_list): indices, raw rows [live][d]
+  std::vector<int64_t> probe_key;
+  std::vector<float> probe_rows;
+  bool probe_listed = false;
   int screen_mode = GPSO_SCREEN_DEFAULT;  // GPSO_OPT_SCREEN
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
@@ -2563,9 +2568,12 @@ struct EngineT : Engine {
       // less per call: 12 us of a 740 us step at C3).  Only where nothing else reads the scaled copies: one chunk, all rows
       // live, the caller's leaves in float.  A NaN coordinate reaches the partial sums by itself on this path (no clamp in
       // float generation), so the finalize stage needs no norms.
+      // The survivors of a screened call (span.open) are such a batch although only the device knows how many rows live: the
+      // compaction leaves zero rows up to the edge of the last live leaf tile (screen.hip), the tiles behind it leave at once.
       RawLeaves rawl{};
       if constexpr (kFloatPredict && sizeof(TG) == 4) {
-        if (fuse_prep && use_bf16 && !prepared && xs_dtype == GPSO_F32 && nchunk == 1 && m_live_c == nullptr && c16_in_use(false)) {
+        if (fuse_prep && use_bf16 && !prepared && xs_dtype == GPSO_F32 && nchunk == 1 && (m_live_c == nullptr || span.open) &&
+            c16_in_use(false)) {
           rawl.x = static_cast<const float*>(xs_dev) + off * d;
           rawl.ls = ls_dev();
           rawl.m = mc;
@@ -3490,7 +3498,8 @@ struct EngineT : Engine {
       if ((rc = ensure(pmean, (size_t)nbi * mpad * 8))) return rc;
       if ((rc = ensure(pvar, (size_t)nbi * mpad * 8))) return rc;
       if ((rc = ensure(screen_my, (size_t)mpad * 8))) return rc;
-      if ((rc = ensure(screen_bmax, (size_t)(mpad / 256) * 8))) return rc;
+      if ((rc = ensure(screen_bmax, (size_t)(mpad / 128) * 8))) return rc;
+      if ((rc = ensure(screen_cnt, (size_t)kScreenMaxParts * 8))) return rc;
       if ((rc = ensure(screen_rows, (size_t)cap * d * 4))) return rc;
       if ((rc = ensure(grow_key, (size_t)cap * 8))) return rc;
       if ((rc = ensure_keep(screen_ctl, 64))) return rc;
@@ -3500,13 +3509,15 @@ struct EngineT : Engine {
       a.xs_h16 = xs_h16.p; a.alpha = as<float>(alpha); a.c16_scale = as<float>(c16_scal);
       a.raw.x = static_cast<const float*>(dev); a.raw.ls = ls_dev(); a.raw.m = m; a.raw.d = d;
       a.part_mean = as<double>(pmean);
-      a.npad = npad; a.mpad = mpad; a.n_rows = n; a.dp4 = dp / 4;
+      a.npad = npad; a.mpad = mpad; a.m = m; a.n_rows = n; a.dp4 = dp / 4; a.mean_c = kp.mean_c;
+      a.my = as<double>(screen_my); a.block_max = as<double>(screen_bmax);
+      ScreenLaunch b;
+      a.nblk_out = &b.nblk;
       a.row_loop = row_loop; a.cu_count = ctx->cu_count; a.splits_out = &ctx->last_count[3];
       if ((rc = launch_leaf_mean(s, kp, a))) return launch_status();
-      ScreenLaunch b;
-      b.part_mean = as<double>(pmean); b.nbi = nbi; b.mpad = mpad; b.m = m;
-      b.variance = kp.variance; b.noise = kp.noise; b.mean_c = kp.mean_c; b.varsigma = acq.varsigma;
-      b.raw = static_cast<const float*>(dev); b.d = d; b.cap = cap;
+      b.m = m;
+      b.variance = kp.variance; b.noise = kp.noise; b.varsigma = acq.varsigma;
+      b.raw = static_cast<const float*>(dev); b.d = d; b.cap = cap; b.counts = as<int64_t>(screen_cnt);
       b.my = as<double>(screen_my); b.block_max = as<double>(screen_bmax); b.key = as<int64_t>(grow_key);
       b.rows_out = as<float>(screen_rows); b.ctl = as<int64_t>(screen_ctl); b.probe = probe ? as<double>(screen_cols) : nullptr;
       launch_screen(s, b);
@@ -3535,10 +3546,32 @@ struct EngineT : Engine {
     HIPCHECK(hipMemcpyAsync(ctl, screen_ctl.p, 24, hipMemcpyDeviceToHost, s));
     HIPCHECK(hipStreamSynchronize(s));
     if ((rc = launch_status())) return rc;
+    probe_listed = false;
+    probe_key.resize((size_t)ctl[0]);
+    probe_rows.resize((size_t)ctl[0] * d);
+    if (ctl[0] > 0) {
+      HIPCHECK(hipMemcpyAsync(probe_key.data(), grow_key.p, (size_t)ctl[0] * 8, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipMemcpyAsync(probe_rows.data(), screen_rows.p, (size_t)ctl[0] * d * 4, hipMemcpyDeviceToHost, s));
+      HIPCHECK(hipStreamSynchronize(s));
+    }
+    probe_listed = true;
     if (info) {
       info[0] = (double)ctl[1];
       std::memcpy(&info[1], &ctl[2], 8);
       info[2] = (double)screen_cap_rows((m + kLeafPad - 1) / kLeafPad * kLeafPad);
+    }
+    return GPSO_OK;
+  }
+  // gpso_screen_list: the compact list the last gpso_screen_probe left -- the survivors' indices and raw rows
+  int screen_list(int64_t max_rows, int64_t* key, float* rows, int64_t* live) override {
+    if (!probe_listed) return ctx->fail(GPSO_E_STATE, "gpso_screen_list: no gpso_screen_probe on this context yet");
+    if (max_rows < 0 || (max_rows > 0 && (!key || !rows))) return ctx->fail(GPSO_E_ARG, "gpso_screen_list: NULL output or max_rows < 0");
+    const int64_t have = (int64_t)probe_key.size();
+    if (live) *live = have;
+    const int64_t rows_n = std::min(max_rows, have);
+    if (rows_n > 0) {
+      std::memcpy(key, probe_key.data(), (size_t)rows_n * 8);
+      std::memcpy(rows, probe_rows.data(), (size_t)rows_n * d * 4);
     }
     return GPSO_OK;
   }
@@ -5266,6 +5299,11 @@ int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, i
   return ctx->eng->screen_probe(xs, xs_dtype, xs_mem, m, varsigma, my, ub, flag, info);
 }
 
+int gpso_screen_list(gpso_ctx* ctx, int64_t max_rows, int64_t* key, float* rows, int64_t* live) {
+  ENTER();
+  return ctx->eng->screen_list(max_rows, key, rows, live);
+}
+
 int gpso_screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, int64_t n,
                           double* ucb, double* ub) {
   if (n < 0 || (n > 0 && !my)) return GPSO_E_ARG;
@@ -5282,6 +5320,17 @@ int gpso_screen_survives_host(double my, double ub, double threshold) { return g
 int gpso_screen_accepts_host(double u_star, double threshold, int64_t count, int64_t cap) {
   return gpso::screen_accepts_host(u_star, threshold, (long long)count, (long long)cap);
 }
+
+int gpso_screen_partition_host(int64_t m, int parts, int w, int64_t* lo, int64_t* hi) {
+  if (m < 0 || parts < 1 || w < 0 || w >= parts || !lo || !hi) return GPSO_E_ARG;
+  long long a = 0, b = 0;
+  gpso::screen_partition_host((long long)m, parts, w, &a, &b);
+  *lo = a;
+  *hi = b;
+  return GPSO_OK;
+}
+
+int gpso_screen_parts_host(int64_t m) { return gpso::screen_parts_host((long long)m); }
 
 int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out) {
   if (acq_refusal(acq) != nullptr || n < 0 || (n > 0 && (!mean || !var || !out)) || noise != noise) return GPSO_E_ARG;

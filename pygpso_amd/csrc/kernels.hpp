@@ -171,36 +171,47 @@ void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, 
                          it: the survivors' count */, int64_t screen_cap = 0);
 
 // ---- screen.hip: screened best-UCB calls (screen.hpp) ------------------------------------------------------------------
-// The mean pass: part_mean[npad / 256][mpad] as the split tile kernel with the fp16 split and the fp16 contraction writes it
-// (same bits), from the generation of the diagonal k-steps alone.  Float generation; leaves: raw.x (unscaled, the kernel
-// scales them as the tile kernel's prologue does) or leaves_s (scaled).  The grid's second dimension is leaf_row_splits' for
-// a batch of known size -> *splits_out.
+// The mean pass of a batch of m float leaves: my[m], every leaf's mean -- the bits the split tile kernel with the fp16 split and
+// the fp16 contraction, and the finalize stage behind it, give it -- from the generation of the diagonal k-steps alone, and
+// block_max[*nblk_out], the largest FINITE mean of every block of leaves (-inf: none).  Float generation; leaves: raw.x
+// (unscaled, the kernel scales them as the tile kernel's prologue does) or leaves_s (scaled).  A workgroup owns 128 leaves.
+// Where the batch fills the chip (two leaf tiles per CU or more) it walks all their row blocks in ascending order and keeps
+// the f64 sum of the shares in registers: one launch, part_mean untouched.  A smaller batch splits a tile's row blocks over
+// gridDim.y workgroups; their shares go through part_mean[npad / 256][mpad] and a second launch sums them.
+// *splits_out: leaf_row_splits' value for a batch of this size -- what the tile kernel's launch of the same batch would
+// report --, whatever grid the mean pass itself uses.
 struct LeafMeanLaunch {
   const void* xs_h16 = nullptr;
   const float* alpha = nullptr;
   const float* c16_scale = nullptr;
   const float* leaves_s = nullptr;
   RawLeaves raw;
-  double* part_mean = nullptr;
-  int64_t npad = 0, mpad = 0, n_rows = 0;
+  double* part_mean = nullptr;  // scratch, [npad / 256][mpad]
+  int64_t npad = 0, mpad = 0, m = 0, n_rows = 0;
   int dp4 = 0;
+  double mean_c = 0;
+  double* my = nullptr;         // [m]
+  double* block_max = nullptr;  // [mpad / 128]
+  int* nblk_out = nullptr;
   int row_loop = 1, cu_count = 256;
   int64_t* splits_out = nullptr;
 };
 int launch_leaf_mean(hipStream_t st, const KernParams& kp, const LeafMeanLaunch& a);
-// The screen and the ordered compaction (two launches): my[m], block_max[ceil(m / 256)] scratch; key[cap] the survivors'
-// indices, ascending; rows_out[cap][d] their raw rows; ctl (3 x int64): live rows = min(count, cap), count, T' (bit-cast);
+// The screen and the ordered compaction of the mean pass's my / block_max (two launches over screen_parts(m) workgroups, none
+// of which waits for another: every part counts its survivors, then every part sums the counts in front of it and writes its
+// own): key[cap] the survivors' indices, ascending; rows_out[cap][d] their raw rows, and zero rows from the live count up to the
+// next multiple of 256; ctl (3 x int64): live rows = min(count, cap), count, T' (bit-cast); counts[kScreenMaxParts] scratch;
 // probe (nullable, [2][m]): every leaf's ub and survive flag
 struct ScreenLaunch {
-  const double* part_mean = nullptr;
-  int nbi = 0;
-  int64_t mpad = 0, m = 0;
-  double variance = 0, noise = 0, mean_c = 0, varsigma = 0;
+  const double* my = nullptr;
+  const double* block_max = nullptr;
+  int nblk = 0;
+  int64_t m = 0;
+  double variance = 0, noise = 0, varsigma = 0;
   const float* raw = nullptr;
   int d = 0;
-  int64_t cap = 0;
-  double* my = nullptr;
-  double* block_max = nullptr;
+  int64_t cap = 0;  // a multiple of 256
+  int64_t* counts = nullptr;
   int64_t* key = nullptr;
   float* rows_out = nullptr;
   int64_t* ctl = nullptr;
@@ -213,6 +224,8 @@ void screen_eval_host(const double* my, const double* v, double variance, double
 double screen_threshold_host(double max_my, double noise, double varsigma);
 int screen_survives_host(double my, double ub, double threshold);
 int screen_accepts_host(double u_star, double threshold, long long count, long long cap);
+void screen_partition_host(long long m, int parts, int w, long long* lo, long long* hi);
+int screen_parts_host(long long m);
 // out_dev[c] = number of live leaves inside chunk c of a batch whose total live count is *live_dev
 void launch_chunk_live(hipStream_t st, const int64_t* live_dev, int64_t chunk, int nchunk, int64_t* out_dev);
 // *acc += sum_i mix(words[i], i, salt)  (64-bit wrap-around sum of a per-word mix: order-independent, so the parallel

@@ -1,10 +1,16 @@
 // Screened best-UCB calls (screen.hpp): the mean pass, the screen and the ordered compaction.
 //
-//   leaf_mean_kernel     every leaf's share of k*.alpha per row block of L^-1 -- part_mean[bi][col], the bits the split tile
-//                        kernel (leaf_split.hpp: leaf_tiles_bf16_kernel, fp16 split with the fp16 contraction) writes there --
-//                        from the generation of the row blocks' diagonal k-steps alone: no L^-1 panel, no apply, no accumulators
-//   screen_mean_kernel   my = sum of the shares + mean_c (finalize_leaf's sums), and every block's largest finite my
-//   screen_compact_kernel  T', the survive flags, and the survivors' indices (ascending) and raw rows into compact buffers
+//   leaf_mean_kernel       every leaf's mean, the bits the split tile kernel (leaf_split.hpp: leaf_tiles_bf16_kernel, fp16 split
+//                          with the fp16 contraction) and the finalize stage give it, from the generation of the row blocks'
+//                          diagonal k-steps alone: no L^-1 panel, no apply, no accumulators.  A workgroup owns 128 leaves.
+//                          FOLD: it walks all their row blocks, ascending, and sums the shares in f64 registers in finalize_leaf's
+//                          order -> my, and the workgroup's largest finite my -> block_max.  Otherwise (a batch too small to fill
+//                          the chip that way) a leaf tile's row blocks are split over gridDim.y workgroups, the shares go to
+//                          part_mean[bi][col], and
+//   screen_mean_kernel     sums them: my = sum of the shares + mean_c, and every block's largest finite my
+//   screen_count_kernel    T', and how many leaves of every part of the batch (screen.hpp: screen_partition) survive
+//   screen_scatter_kernel  every part sums the counts in front of it and writes its survivors' indices (ascending) and raw rows
+//                          into the compact buffers.  No workgroup waits for another: the launch boundary is the only ordering.
 //
 // Built with the split kernels' flags (Makefile: EXTRA_screen): the per-leaf arithmetic is the tile kernel's, instruction for
 // instruction.
@@ -15,40 +21,45 @@
 
 namespace gpso {
 
+// leaves of a workgroup of the mean pass: kMeanWaves waves x kMeanCT column tiles x 16
+constexpr int kMeanLeaves = 128;
+constexpr int kMeanCT = 2, kMeanWaves = kMeanLeaves / (16 * kMeanCT), kMeanThreads = 64 * kMeanWaves;
+
 // The tile kernel's mean, without the tile kernel.  What it repeats of leaf_tiles_bf16_kernel<2, float, KERNEL, F16, FUSED, C16>,
-// operation for operation: the leaf prologue (fp16 pieces of the scaled leaves, their norm; the raw-leaf scaling path), the
-// row blocks a workgroup owns (the same zig-zag over gridDim.y), and per row block the generation of its diagonal k-steps
-// q_diag0 .. min(q_lim, q_end - 1) -- the steps the fused kernel generates with GMODE 2 / DIAG -- through leaf_bf16_gen<DIAG = true>:
-// the same contraction, map, macc order; then the epilogue's shuffles, conversion and un-scaling.
+// operation for operation: the leaf prologue (fp16 pieces of the scaled leaves, their norm; the raw-leaf scaling path) and per
+// row block the generation of its diagonal k-steps q_diag0 .. min(q_lim, q_end - 1) -- the steps the fused kernel generates with
+// GMODE 2 / DIAG -- through leaf_bf16_gen<DIAG = true>: the same contraction, map, macc order; then the epilogue's shuffles,
+// conversion and un-scaling.  A column's arithmetic depends neither on the column tiles per wave nor on the waves per workgroup.
 // (The prologue is DUPLICATED from the tile kernel, not shared with it: factored out, the default tile kernel would have to
 // keep its 239 VGPRs and its bits through a different inlining -- the copy costs nothing there.  Keep the two in step.)
 // The inputs of a k-step (the X fragments' fp16 pieces and 32 alphas) travel global -> registers -> LDS one step ahead of
-// their use, two buffers, one workgroup barrier per step.
-template <int KERNEL, int C16, int XP>
-__global__ __launch_bounds__(512) void leaf_mean_kernel(const unsigned char* __restrict__ xs_h16, const float* __restrict__ alpha,
-                                                        const float* __restrict__ leaves_s, double* __restrict__ part_mean,
-                                                        int dp4, int64_t mpad, int nbi, float variance, float inv_scale_b,
-                                                        const float* __restrict__ c16_scale, int q_max,
-                                                        const float* __restrict__ raw, const double* __restrict__ raw_ls,
-                                                        int64_t raw_m, int raw_d) {
+// their use, two buffers, one workgroup barrier per step.  Two or more workgroups share a CU, each with its own barrier.
+template <int KERNEL, int C16, int XP, bool FOLD>
+__global__ __launch_bounds__(kMeanThreads) void leaf_mean_kernel(
+    const unsigned char* __restrict__ xs_h16, const float* __restrict__ alpha, const float* __restrict__ leaves_s,
+    double* __restrict__ part_mean, double* __restrict__ my_out, double* __restrict__ block_max, int dp4, int64_t mpad, int64_t m,
+    int nbi, float variance, float inv_scale_b, double mean_c, const float* __restrict__ c16_scale, int q_max,
+    const float* __restrict__ raw, const double* __restrict__ raw_ls, int64_t raw_m, int raw_d) {
   using TG = float;
-  constexpr int RT = 16, CT = 2, NW = 8, NS = 2;
+  constexpr int RT = 16, CT = kMeanCT, NW = kMeanWaves, NT = kMeanThreads, NS = 2;
   constexpr TG SC = (TG)GenScale<KERNEL>::SC;
+  constexpr int xfrag = Bf16Lds<TG, C16>::xfrag(0);  // (the fp16 contraction's does not depend on D)
+  constexpr int xstride = Bf16Lds<TG, C16>::xbytes(0);
+  constexpr int XW = (xfrag / 16 + NT - 1) / NT;  // 16-byte words of a step's fragments per thread
   extern __shared__ __align__(16) unsigned char lds_raw[];
+  __shared__ double sh_best[NW];
   const int S = (int)gridDim.y, split = (int)blockIdx.y;
   const int64_t leaf_tile = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int xstride = Bf16Lds<TG, C16>::xbytes(dp4);
-  const int xfrag = Bf16Lds<TG, C16>::xfrag(dp4);
   unsigned char* xsl = lds_raw;  // [2] X buffers: fragments | 64 TG (unused: the norms ride in the contraction) | alphas
-  TG* xb = reinterpret_cast<TG*>(xsl + 2 * xstride + (size_t)wave * xfrag);
+  TG* xb = reinterpret_cast<TG*>(xsl + 2 * xstride + (size_t)wave * (xfrag / 2 * CT));
   const int64_t col0 = (leaf_tile * NW + wave) * (CT * 16);
   const int dp = dp4 * 4;
 
   // ---- leaf prologue (leaf_tiles_bf16_kernel, C16) ----------------------------------------------------------------------
   TG cm = TG(-2) * SC;
-  float nb_c16[CT] = {0, 0};
+  float nb_c16[CT];
   {
     const float up = c16_scale[1];
     cm *= (TG)c16_scale[2];
@@ -99,114 +110,104 @@ __global__ __launch_bounds__(512) void leaf_mean_kernel(const unsigned char* __r
   const double unscale_m = (double)inv_scale_b;
 
   // ---- the k-steps of this workgroup, row block after row block, as one sequence -------------------------------------------
-  auto rank_of = [&](int j) { return j * S + ((j & 1) ? S - 1 - split : split); };
-  int rbj = 0, bi = 0, q = 0, q_last = -1;
-  auto set_row_block = [&](int j_mine) {  // false: no such row block
-    const int rank = rank_of(j_mine);
-    if (rank >= nbi) return false;
-    bi = nbi - 1 - rank;
-    const int q_diag0 = bi * (RT / 2), q_end = q_diag0 + RT / 2;
-    const int q_lim = min(q_end, q_max);  // (the fused step's: the k-steps from q_max on hold padding points only)
-    q = q_diag0;
-    q_last = min(q_lim, q_end - 1);
-    return true;
+  // FOLD: every row block, ascending (the order finalize_leaf sums the shares in); otherwise the tile kernel's zig-zag over
+  // gridDim.y, heaviest first
+  struct Cursor {
+    int rbj, bi, q, q_last;
+    bool ok;
   };
-  // this thread's share of a step's inputs: one 16-byte word of the fragments (xfrag / 16 <= 512 of them), one alpha
-  const bool has_x = tid * 16 < xfrag, has_a = tid < 32;
-  u32x4 rx = {0, 0, 0, 0};
+  auto set_row_block = [&](Cursor& c) {  // the rbj-th row block of this workgroup (ok false: there is none)
+    const int rank = FOLD ? c.rbj : c.rbj * S + ((c.rbj & 1) ? S - 1 - split : split);
+    c.ok = rank < nbi;
+    c.bi = FOLD ? rank : nbi - 1 - rank;
+    const int q_diag0 = c.bi * (RT / 2), q_end = q_diag0 + RT / 2;
+    const int q_lim = min(q_end, q_max);  // (the fused step's: the k-steps from q_max on hold padding points only)
+    c.q = q_diag0;
+    c.q_last = min(q_lim, q_end - 1);
+  };
+  auto advance = [&](Cursor& c) {
+    if (c.q == c.q_last) {
+      ++c.rbj;
+      set_row_block(c);
+    } else {
+      ++c.q;
+    }
+  };
+  Cursor at{0, 0, 0, 0, false};  // the step to generate next
+  set_row_block(at);
+  if (!at.ok) return;  // (gridDim.y <= nbi: every workgroup owns a row block)
+  Cursor ahead = at;   // the step to fetch next
+  // this thread's share of a step's inputs: XW 16-byte words of the fragments, one alpha
+  u32x4 rx[XW];
   float ra = 0.0f;
-  auto fetch = [&](int qq) {
-    if (has_x) rx = *reinterpret_cast<const u32x4*>(xs_h16 + (size_t)qq * xfrag + tid * 16);
-    if (has_a) ra = alpha[32 * qq + tid];
+#pragma unroll
+  for (int w = 0; w < XW; ++w) rx[w] = u32x4{0, 0, 0, 0};
+  auto fetch = [&]() {  // the inputs of step `ahead`, where there is one
+    if (!ahead.ok) return;
+#pragma unroll
+    for (int w = 0; w < XW; ++w)
+      if ((tid + NT * w) * 16 < xfrag)
+        rx[w] = *reinterpret_cast<const u32x4*>(xs_h16 + (size_t)ahead.q * xfrag + (size_t)(tid + NT * w) * 16);
+    if (tid < 32) ra = alpha[32 * ahead.q + tid];
+    advance(ahead);
   };
   auto stash = [&](int buf) {
     unsigned char* xd = xsl + buf * xstride;
-    if (has_x) *reinterpret_cast<u32x4*>(xd + tid * 16) = rx;
-    if (has_a) *reinterpret_cast<float*>(xd + xfrag + 64 * sizeof(TG) + tid * 4) = ra;
+#pragma unroll
+    for (int w = 0; w < XW; ++w)
+      if ((tid + NT * w) * 16 < xfrag) *reinterpret_cast<u32x4*>(xd + (tid + NT * w) * 16) = rx[w];
+    if (tid < 32) *reinterpret_cast<float*>(xd + xfrag + 64 * sizeof(TG) + tid * 4) = ra;
   };
-  if (!set_row_block(0)) return;  // (gridDim.y <= nbi: every workgroup owns a row block)
-  fetch(q);
-  float macc[CT] = {0.0f, 0.0f};
+  fetch();
+  float macc[CT];
+  double mu[CT];
+#pragma unroll
+  for (int t = 0; t < CT; ++t) macc[t] = 0.0f, mu[t] = 0.0;
   for (int it = 0;; ++it) {
     const int buf = it & 1;
     stash(buf);  // (buffer `buf` was last read two steps ago: every wave has passed the barrier of the step in between)
-    // the step after this one: the next diagonal step of the row block, or the first of the workgroup's next row block
-    const int bi_now = bi, q_now = q;
-    const bool block_ends = q_now == q_last;
-    bool more = true;
-    if (block_ends) more = set_row_block(++rbj);
-    else ++q;
-    if (more) fetch(q);
+    fetch();
     __syncthreads();
     bf16x8 bfrag[NS][CT];  // (the pieces of the split are not used: dead code here)
     leaf_bf16_gen<NS, TG, KERNEL, true, true, C16, CT, XP>(lane, dp4, xsl + buf * xstride, xb, nb, cm, vc, bfrag, macc);
-    (void)q_now;
-    if (block_ends) {  // the tile kernel's epilogue, the mean's half
+    if (at.q == at.q_last) {  // the row block ends: the tile kernel's epilogue, the mean's half
 #pragma unroll
       for (int t = 0; t < CT; ++t) {
         double mm = (double)macc[t];
         mm += __shfl_xor(mm, 16);
         mm += __shfl_xor(mm, 32);
         mm *= unscale_m;
-        if (lane < 16) part_mean[(int64_t)bi_now * mpad + col0 + t * 16 + lane] = mm;
+        if constexpr (FOLD) mu[t] += mm;  // (finalize_leaf: from 0, the row blocks ascending; built without contraction)
+        else if (lane < 16) part_mean[(int64_t)at.bi * mpad + col0 + t * 16 + lane] = mm;
         macc[t] = 0.0f;
       }
     }
-    if (!more) break;  // (workgroup-uniform)
+    advance(at);
+    if (!at.ok) break;  // (workgroup-uniform)
   }
-}
-
-int launch_leaf_mean(hipStream_t st, const KernParams& kp, const LeafMeanLaunch& a) {
-  const int dp4 = a.dp4;
-  const int c16 = leaf_c16_chunks(dp4);
-  if (c16 < 1 || c16 > 2 || a.npad % 256 != 0 || a.mpad % 256 != 0) {
-    note_launch_error("launch_leaf_mean: the fp16 contraction has one or two chunks, N_pad and M_pad are multiples of 256");
-    return 1;
+  if constexpr (FOLD) {  // the mean, and the workgroup's largest finite one over its live leaves
+    double best = -HUGE_VAL;
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+      const int64_t col = col0 + t * 16 + (lane & 15);
+      const double y = __dadd_rn(mu[t], mean_c);
+      if (col < m) {
+        if (lane < 16) my_out[col] = y;
+        if (screen_finite(y)) best = fmax(best, y);
+      }
+    }
+    for (int off = 32; off > 0; off >>= 1) best = fmax(best, __shfl_xor(best, off));
+    if (lane == 0) sh_best[wave] = best;
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < NW; ++w) best = fmax(best, sh_best[w]);
+      block_max[leaf_tile] = best;
+    }
   }
-  const int nbi = (int)(a.npad / 256);
-  // the scales of the fp16 split, as launch_leaf_tiles_bf16_ns forms them
-  int eb = 0;
-  (void)frexp(kp.variance, &eb);
-  const float var_arg = (float)ldexp(kp.variance, 14 - eb);
-  const float inv_b = (float)ldexp(1.0, eb - 14);
-  const int q_max = a.n_rows > 0 ? (int)((a.n_rows + 31) / 32) : (int)(a.npad / 32);
-  const int S = leaf_row_splits(a.row_loop, a.mpad / 256, nbi, a.cu_count, true);
-  if (a.splits_out != nullptr) *a.splits_out = S;
-  const dim3 grid((unsigned)(a.mpad / 256), (unsigned)S);
-  const bool xp = dp4 * 4 + 1 - 32 * (c16 - 1) <= 16;
-  const size_t xfrag = (size_t)c16 * 4096;
-  const size_t lds = 2 * (xfrag + 64 * 4 + 256) + 8 * xfrag;
-#define GPSO_M(K, C, X)                                                                                                   \
-  do {                                                                                                                    \
-    const int rc = ensure_dyn_lds((const void*)leaf_mean_kernel<K, C, X>, (int)lds);                                      \
-    if (rc) return rc;                                                                                                    \
-    hipLaunchKernelGGL((leaf_mean_kernel<K, C, X>), grid, dim3(512), lds, st, static_cast<const unsigned char*>(a.xs_h16), \
-                       a.alpha, a.leaves_s, a.part_mean, dp4, a.mpad, nbi, var_arg, inv_b, a.c16_scale, q_max, a.raw.x,   \
-                       a.raw.ls, a.raw.m, a.raw.d);                                                                       \
-  } while (0)
-#define GPSO_MK(K)                       \
-  do {                                   \
-    if (c16 == 1) {                      \
-      if (xp) GPSO_M(K, 1, 1);           \
-      else GPSO_M(K, 1, 0);              \
-    } else {                             \
-      if (xp) GPSO_M(K, 2, 1);           \
-      else GPSO_M(K, 2, 0);              \
-    }                                    \
-  } while (0)
-  switch (kp.kernel) {
-    case 0: GPSO_MK(0); break;
-    case 1: GPSO_MK(1); break;
-    case 2: GPSO_MK(2); break;
-    default: GPSO_MK(3); break;
-  }
-#undef GPSO_MK
-#undef GPSO_M
-  return 0;
 }
 
 // my of every leaf (finalize_leaf's sums: the shares from 0 upwards in row-block order, then + mean_c) and, per block of 256
-// leaves, the largest finite one (-inf: none)
+// leaves, the largest finite one (-inf: none): behind a mean pass whose workgroups split the row blocks
 __global__ __launch_bounds__(256) void screen_mean_kernel(const double* __restrict__ part_mean, int nbi, int64_t mpad, int64_t m,
                                                           double mean_c, double* __restrict__ my_out,
                                                           double* __restrict__ block_max) {
@@ -226,68 +227,159 @@ __global__ __launch_bounds__(256) void screen_mean_kernel(const double* __restri
   if (threadIdx.x == 0) block_max[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
 }
 
-// One workgroup of 16 waves.  Wave w owns the leaves [w seg, (w + 1) seg), seg a multiple of 64, and walks them 64 at a
-// time (coalesced): a first pass counts its survivors, the waves' counts are scanned, a second pass writes every survivor's
-// index at its rank -- ascending -- and its raw row, as long as the rank is below cap.  ctl: [0] live rows of the compact
-// buffers (min(count, cap)), [1] the survivors' count, [2] T' (bit-cast double).
-// probe (nullable, [2][m]): ub and the flag of every leaf, for gpso_screen_probe.
-__global__ __launch_bounds__(1024) void screen_compact_kernel(const double* __restrict__ my, const double* __restrict__ block_max,
-                                                              int nblk, int64_t m, double variance, double noise, double varsigma,
-                                                              const float* __restrict__ raw, int d, int64_t cap,
-                                                              int64_t* __restrict__ key, float* __restrict__ rows_out,
-                                                              int64_t* __restrict__ ctl, double* __restrict__ probe) {
-  __shared__ double shm[16];
-  __shared__ int64_t shc[16];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+int launch_leaf_mean(hipStream_t st, const KernParams& kp, const LeafMeanLaunch& a) {
+  const int dp4 = a.dp4;
+  const int c16 = leaf_c16_chunks(dp4);
+  if (c16 < 1 || c16 > 2 || a.npad % 256 != 0 || a.mpad % 256 != 0 || a.m < 1 || a.m > a.mpad) {
+    note_launch_error("launch_leaf_mean: the fp16 contraction has one or two chunks, N_pad and M_pad are multiples of 256");
+    return 1;
+  }
+  const int nbi = (int)(a.npad / 256);
+  // the scales of the fp16 split, as launch_leaf_tiles_bf16_ns forms them
+  int eb = 0;
+  (void)frexp(kp.variance, &eb);
+  const float var_arg = (float)ldexp(kp.variance, 14 - eb);
+  const float inv_b = (float)ldexp(1.0, eb - 14);
+  const int q_max = a.n_rows > 0 ? (int)((a.n_rows + 31) / 32) : (int)(a.npad / 32);
+  if (a.splits_out != nullptr) *a.splits_out = leaf_row_splits(a.row_loop, a.mpad / 256, nbi, a.cu_count, true);
+  // One workgroup per leaf tile and all its row blocks where that leaves two workgroups per CU or more; a smaller batch splits
+  // the row blocks of a tile over as many workgroups as brings the grid there (the chain of k-steps of a workgroup shortens as
+  // the chip empties), and pays the second launch.  An explicit GPSO_OPT_ROW_LOOP decides here as it does for the tile kernel:
+  // -1 one workgroup per tile whatever the batch (tests: a small batch then takes the large batches' path), 0 one row block
+  // per workgroup, v >= 2 min(v, row blocks) workgroups.
+  const int64_t ltiles = a.mpad / kMeanLeaves;
+  const int64_t want = 2 * (int64_t)std::max(a.cu_count, 1);
+  int S = ltiles >= want ? 1 : (int)std::min<int64_t>(nbi, (want + ltiles - 1) / ltiles);
+  if (a.row_loop < 0) S = 1;
+  else if (a.row_loop == 0) S = nbi;
+  else if (a.row_loop >= 2) S = std::min(a.row_loop, nbi);
+  const bool fold = S == 1;
+  const dim3 grid((unsigned)ltiles, (unsigned)S);
+  const bool xp = dp4 * 4 + 1 - 32 * (c16 - 1) <= 16;
+  const size_t xfrag = (size_t)c16 * 4096;
+  const size_t lds = 2 * (xfrag + 64 * 4 + 256) + (size_t)kMeanWaves * (xfrag / 2 * kMeanCT);
+#define GPSO_M(K, C, X, F)                                                                                                  \
+  do {                                                                                                                      \
+    const int rc = ensure_dyn_lds((const void*)leaf_mean_kernel<K, C, X, F>, (int)lds);                                     \
+    if (rc) return rc;                                                                                                      \
+    hipLaunchKernelGGL((leaf_mean_kernel<K, C, X, F>), grid, dim3(kMeanThreads), lds, st,                                   \
+                       static_cast<const unsigned char*>(a.xs_h16), a.alpha, a.leaves_s, a.part_mean, a.my, a.block_max, dp4, \
+                       a.mpad, a.m, nbi, var_arg, inv_b, a.mean_c, a.c16_scale, q_max, a.raw.x, a.raw.ls, a.raw.m, a.raw.d); \
+  } while (0)
+#define GPSO_MF(K, C, X)            \
+  do {                              \
+    if (fold) GPSO_M(K, C, X, true); \
+    else GPSO_M(K, C, X, false);    \
+  } while (0)
+#define GPSO_MK(K)                       \
+  do {                                   \
+    if (c16 == 1) {                      \
+      if (xp) GPSO_MF(K, 1, 1);          \
+      else GPSO_MF(K, 1, 0);             \
+    } else {                             \
+      if (xp) GPSO_MF(K, 2, 1);          \
+      else GPSO_MF(K, 2, 0);             \
+    }                                    \
+  } while (0)
+  switch (kp.kernel) {
+    case 0: GPSO_MK(0); break;
+    case 1: GPSO_MK(1); break;
+    case 2: GPSO_MK(2); break;
+    default: GPSO_MK(3); break;
+  }
+#undef GPSO_MK
+#undef GPSO_MF
+#undef GPSO_M
+  int nblk = (int)ltiles;
+  if (!fold) {
+    nblk = (int)((a.m + 255) / 256);
+    hipLaunchKernelGGL(screen_mean_kernel, dim3(nblk), dim3(256), 0, st, a.part_mean, nbi, a.mpad, a.m, a.mean_c, a.my, a.block_max);
+  }
+  if (a.nblk_out != nullptr) *a.nblk_out = nblk;
+  return 0;
+}
+
+// T' by one wave: the largest of the mean pass's block maxima (max is exact: any order gives the same double)
+__device__ __forceinline__ double screen_wave_threshold(const double* __restrict__ block_max, int nblk, int lane, double noise,
+                                                        double varsigma) {
   double best = -HUGE_VAL;
-  for (int b = tid; b < nblk; b += blockDim.x) best = fmax(best, block_max[b]);
+#pragma unroll 8
+  for (int b = lane; b < nblk; b += 64) best = fmax(best, block_max[b]);
   for (int off = 32; off > 0; off >>= 1) best = fmax(best, __shfl_xor(best, off));
-  if (lane == 0) shm[wave] = best;
-  __syncthreads();
-  best = shm[0];
-  for (int w = 1; w < 16; ++w) best = fmax(best, shm[w]);
-  const double T = screen_threshold(best, noise, varsigma);
-  const int64_t seg = ((m + 16 * 64 - 1) / (16 * 64)) * 64;
-  const int64_t lo = wave * seg, hi = lo + seg < m ? lo + seg : m;
-  // (one leaf per lane and load, kUnroll loads in flight per wave: the walk is a chain of global-memory latencies otherwise,
-  // 128 of them per wave at C3)
-  constexpr int kUnroll = 8;
+  return screen_threshold(best, noise, varsigma);
+}
+
+// (one leaf per lane and load, kScreenUnroll loads in flight per wave: a long range is a chain of global-memory latencies otherwise)
+constexpr int kScreenUnroll = 8;
+
+// One wave per part of the batch (screen_partition).  counts[w]: the survivors among the part's leaves; ctl[2]: T' (bit-cast
+// double), for the scatter kernel and the call's last kernel.
+__global__ __launch_bounds__(64) void screen_count_kernel(const double* __restrict__ my, const double* __restrict__ block_max,
+                                                          int nblk, int64_t m, double variance, double noise, double varsigma,
+                                                          int64_t* __restrict__ counts, int64_t* __restrict__ ctl) {
+  const int lane = threadIdx.x, w = blockIdx.x;
+  const double T = screen_wave_threshold(block_max, nblk, lane, noise, varsigma);
+  const ScreenRange r = screen_partition(m, (int)gridDim.x, w);
   int64_t mine = 0;
-  for (int64_t j0 = lo; j0 < hi; j0 += 64 * kUnroll) {
-    double y[kUnroll];
+  for (int64_t j0 = r.lo; j0 < r.hi; j0 += 64 * kScreenUnroll) {
+    double y[kScreenUnroll];
 #pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
+    for (int u = 0; u < kScreenUnroll; ++u) {
       const int64_t j = j0 + 64 * u + lane;
-      y[u] = j < hi ? my[j] : 0.0;
+      y[u] = j < r.hi ? my[j] : 0.0;
     }
 #pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
+    for (int u = 0; u < kScreenUnroll; ++u) {
       const int64_t j = j0 + 64 * u + lane;
-      const bool f = j < hi && screen_survives(y[u], screen_bound(y[u], variance, noise, varsigma), T);
+      const bool f = j < r.hi && screen_survives(y[u], screen_bound(y[u], variance, noise, varsigma), T);
       mine += __popcll(__ballot(f));
     }
   }
-  if (lane == 0) shc[wave] = mine;
-  __syncthreads();
-  int64_t at = 0, total = 0;
-  for (int w = 0; w < 16; ++w) {
-    if (w < wave) at += shc[w];
-    total += shc[w];
+  if (lane == 0) {
+    counts[w] = mine;
+    if (w == 0) ctl[2] = __builtin_bit_cast(int64_t, T);
   }
-  for (int64_t j0 = lo; j0 < hi; j0 += 64 * kUnroll) {
-    double y[kUnroll];
+}
+
+// One wave per part again.  It sums the counts of the parts in front of its own -- the rank of its first survivor -- and all of
+// them, walks its leaves 64 at a time (coalesced) and writes every survivor's index at its rank -- ascending -- as long as the
+// rank is below cap; then the raw rows of its own survivors, and its share of the zero rows between the live count and the next
+// multiple of 256 (the survivors' launch scales the compact rows in its prologue: a row of its last live leaf tile must hold
+// numbers).  ctl: [0] live rows of the compact buffers (min(count, cap)), [1] the survivors' count.
+// probe (nullable, [2][m]): ub and the flag of every leaf, for gpso_screen_probe.
+__global__ __launch_bounds__(64) void screen_scatter_kernel(const double* __restrict__ my, const int64_t* __restrict__ counts,
+                                                            int64_t m, double variance, double noise, double varsigma,
+                                                            const float* __restrict__ raw, int d, int64_t cap,
+                                                            int64_t* __restrict__ key, float* __restrict__ rows_out,
+                                                            int64_t* __restrict__ ctl, double* __restrict__ probe) {
+  const int lane = threadIdx.x, w = blockIdx.x, parts = (int)gridDim.x;
+  const double T = __builtin_bit_cast(double, ctl[2]);
+  long long at = 0, total = 0;
+  for (int g = lane; g < parts; g += 64) {
+    const long long c = counts[g];
+    total += c;
+    if (g < w) at += c;
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    at += __shfl_xor(at, off);
+    total += __shfl_xor(total, off);
+  }
+  const int64_t first = at;
+  const ScreenRange r = screen_partition(m, parts, w);
+  for (int64_t j0 = r.lo; j0 < r.hi; j0 += 64 * kScreenUnroll) {
+    double y[kScreenUnroll];
 #pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {
+    for (int u = 0; u < kScreenUnroll; ++u) {
       const int64_t j = j0 + 64 * u + lane;
-      y[u] = j < hi ? my[j] : 0.0;
+      y[u] = j < r.hi ? my[j] : 0.0;
     }
 #pragma unroll
-    for (int u = 0; u < kUnroll; ++u) {  // (in order: the ranks ascend with the index)
+    for (int u = 0; u < kScreenUnroll; ++u) {  // (in order: the ranks ascend with the index)
       const int64_t j = j0 + 64 * u + lane;
       const double ub = screen_bound(y[u], variance, noise, varsigma);
-      const bool f = j < hi && screen_survives(y[u], ub, T);
+      const bool f = j < r.hi && screen_survives(y[u], ub, T);
       const unsigned long long mask = __ballot(f);
-      if (probe != nullptr && j < hi) {
+      if (probe != nullptr && j < r.hi) {
         probe[j] = ub;
         probe[m + j] = f ? 1.0 : 0.0;
       }
@@ -298,27 +390,31 @@ __global__ __launch_bounds__(1024) void screen_compact_kernel(const double* __re
       at += __popcll(mask);
     }
   }
-  // the survivors' raw rows, by the whole workgroup at once (copied by the lane that found the survivor, a row's d dependent
-  // loads stood in the walk of its wave: 92 us of kernel at C3's 535 survivors)
+  // the raw rows of this part's survivors, by the whole wave at once (copied by the lane that found the survivor, a row's d
+  // dependent loads would stand in the walk)
   __threadfence_block();
   __syncthreads();
-  const int64_t live = total < cap ? total : cap;
-  for (int64_t e = tid; e < live * d; e += blockDim.x) {
-    const int64_t row = e / d;
-    rows_out[e] = raw[key[row] * d + (e - row * d)];
+  const int64_t p_lo = first < cap ? first : cap, p_hi = at < cap ? (int64_t)at : cap;
+  for (int64_t e = lane; e < (p_hi - p_lo) * d; e += 64) {
+    const int64_t row = p_lo + e / d;
+    const int64_t c = e % d;
+    rows_out[row * d + c] = raw[key[row] * d + c];
   }
-  if (tid == 0) {
-    ctl[0] = total < cap ? total : cap;
+  const int64_t live = total < cap ? (int64_t)total : cap;
+  const int64_t padded = (live + 255) / 256 * 256 < cap ? (live + 255) / 256 * 256 : cap;
+  for (int64_t e = live * d + (int64_t)w * 64 + lane; e < padded * d; e += (int64_t)parts * 64) rows_out[e] = 0.0f;
+  if (w == 0 && lane == 0) {
+    ctl[0] = live;
     ctl[1] = total;
-    ctl[2] = __builtin_bit_cast(int64_t, T);
   }
 }
 
 void launch_screen(hipStream_t st, const ScreenLaunch& a) {
-  const int nblk = (int)((a.m + 255) / 256);
-  hipLaunchKernelGGL(screen_mean_kernel, dim3(nblk), dim3(256), 0, st, a.part_mean, a.nbi, a.mpad, a.m, a.mean_c, a.my, a.block_max);
-  hipLaunchKernelGGL(screen_compact_kernel, dim3(1), dim3(1024), 0, st, a.my, a.block_max, nblk, a.m, a.variance, a.noise,
-                     a.varsigma, a.raw, a.d, a.cap, a.key, a.rows_out, a.ctl, a.probe);
+  const int parts = screen_parts(a.m);
+  hipLaunchKernelGGL(screen_count_kernel, dim3(parts), dim3(64), 0, st, a.my, a.block_max, a.nblk, a.m, a.variance, a.noise,
+                     a.varsigma, a.counts, a.ctl);
+  hipLaunchKernelGGL(screen_scatter_kernel, dim3(parts), dim3(64), 0, st, a.my, a.counts, a.m, a.variance, a.noise, a.varsigma,
+                     a.raw, a.d, a.cap, a.key, a.rows_out, a.ctl, a.probe);
 }
 
 void screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, long long n,
@@ -333,5 +429,11 @@ int screen_survives_host(double my, double ub, double threshold) { return screen
 int screen_accepts_host(double u_star, double threshold, long long count, long long cap) {
   return screen_accepts(u_star, threshold, count, cap) ? 1 : 0;
 }
+void screen_partition_host(long long m, int parts, int w, long long* lo, long long* hi) {
+  const ScreenRange r = screen_partition(m, parts, w);
+  *lo = r.lo;
+  *hi = r.hi;
+}
+int screen_parts_host(long long m) { return screen_parts(m); }
 
 }  // namespace gpso

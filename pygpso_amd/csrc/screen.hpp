@@ -49,4 +49,24 @@ GPSO_ACQ_HD inline bool screen_accepts(double u_star, double threshold, int64_t 
   return count > 0 && count <= cap && (u_star != u_star || u_star >= threshold);
 }
 
+// The compaction's partition of a batch of m leaves over `parts` workgroups: part w owns the leaves [lo, hi), ranges of equal
+// length -- a multiple of 64, one coalesced load per lane and step -- in ascending order; the last non-empty range may be
+// shorter, the ranges behind it are empty.  Every leaf belongs to exactly one part.
+struct ScreenRange {
+  int64_t lo, hi;
+};
+GPSO_ACQ_HD inline ScreenRange screen_partition(int64_t m, int parts, int w) {
+  const int64_t span = (int64_t)parts * 64;
+  const int64_t seg = (m + span - 1) / span * 64;
+  const int64_t lo = w * seg < m ? w * seg : m;
+  return ScreenRange{lo, lo + seg < m ? lo + seg : m};
+}
+// how many parts a batch of m leaves is compacted in: one wave per 256 leaves up to kScreenMaxParts (then longer ranges) -- a
+// part sums the counts of all parts in front of it, so their number is what its walk starts behind
+constexpr int kScreenMaxParts = 256;
+inline int screen_parts(int64_t m) {
+  const int64_t p = (m + 255) / 256;
+  return (int)(p < 1 ? 1 : p > kScreenMaxParts ? kScreenMaxParts : p);
+}
+
 }  // namespace gpso

@@ -158,6 +158,38 @@ class HipGPEngine:
                                                 L.dptr(info)))
         return my, ub, flag != 0.0, {"survivors": int(info[0]), "threshold": float(info[1]), "cap": int(info[2])}
 
+    def screen_list(self):
+        """The compact list the last ``screen_probe`` left for the survivors' launch (``gpso_screen_list``) -> (key[live] int64,
+        rows[live, D] float32): the survivors' indices in the probed batch, ascending, and their unscaled rows; live =
+        min(survivors, cap)."""
+        live = np.zeros(1, dtype=np.int64)
+        self._check(self._lib.gpso_screen_list(self._h, 0, None, None, live.ctypes.data_as(C.POINTER(C.c_int64))))
+        n = int(live[0])
+        key = np.empty(n, dtype=np.int64)
+        rows = np.empty((n, self.d), dtype=np.float32)
+        self._check(self._lib.gpso_screen_list(self._h, n, key.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               rows.ctypes.data_as(C.POINTER(C.c_float)), None))
+        return key, rows
+
+    @staticmethod
+    def screen_partition_host(m, parts):
+        """csrc/screen.hpp's partition of a batch of ``m`` leaves over ``parts`` workgroups of the compaction, on the CPU ->
+        [(lo, hi)] * parts."""
+        lib = L.load()
+        lo, hi = C.c_int64(0), C.c_int64(0)
+        out = []
+        for w in range(int(parts)):
+            rc = lib.gpso_screen_partition_host(int(m), int(parts), w, C.byref(lo), C.byref(hi))
+            if rc != L.OK:
+                raise L.GpsoHipError(rc, "gpso_screen_partition_host: bad arguments")
+            out.append((lo.value, hi.value))
+        return out
+
+    @staticmethod
+    def screen_parts_host(m):
+        """How many workgroups the compaction of a batch of ``m`` leaves runs on (csrc/screen.hpp)."""
+        return int(L.load().gpso_screen_parts_host(int(m)))
+
     @staticmethod
     def screen_eval_host(my, v, variance, noise, varsigma):
         """csrc/screen.hpp on the CPU (no context, no GPU) -> (ucb[n], ub[n]): the finalize stage's ucb of leaves with means
