@@ -710,6 +710,60 @@ int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
  * var[i] - noise.  No context and no GPU (as gpso_shard_range); returns GPSO_OK or GPSO_E_ARG. */
 int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out);
 
+/* ---- max-value entropy search (Wang & Jegelka 2017; no counterpart in the reference) ---------------------------------
+ *
+ * GPSO_ACQ_MES ranks a leaf by the expected reduction of the entropy of the optimum's VALUE y*, from K samples of y*:
+ *   value = (1/K) sum_k t(g_k),   g_k = (y*_k - mean) / s,   t(g) = g phi(g) / (2 Phi(g)) - log Phi(g)
+ * terms added in index order, one division by K; s2 as for the other kinds (latent != 0: the latent variance).  s == 0: 0
+ * (a point without uncertainty tells nothing); a NaN mean or s2: NaN, which wins its segment; otherwise the value is >= 0
+ * and finite.  t is evaluated in three pieces that join at g = -1 and g = -10 (csrc/acq.hpp): for g -> -inf both halves grow
+ * like g^2 / 2 and cancel down to log |g|, Phi underflows at g = -38, and for g -> +inf the term needs log1p.
+ * varsigma, incumbent and xi are not read.
+ *
+ * The K maxima are state of the context, not of the gpso_acq record (its layout stays), and they are the caller's numbers:
+ * fits, appends and installs keep them, only the next gpso_acq_set_maxima changes them; they are no part of the posterior
+ * (gpso_posterior_hash, the packed copies and a resident path set do not see them).
+ *   gpso_acq_set_maxima: k in 0..64, k = 0 clears; GPSO_E_ARG for another k, a NULL ystar with k > 0 or an entry that is
+ *     not finite; GPSO_E_STATE while an asynchronous best-UCB ticket is open (its kernels may be reading the set).
+ *   gpso_acq_get_maxima: *k and, where ystar is not NULL, the k values (room for 64).
+ * Every call that takes a gpso_acq serves the kind -- gpso_best_acq, _begin, _grow, _grow_begin, gpso_acq_values,
+ * gpso_best_batch (the maxima stay fixed over the q rounds) -- on every posterior and context type, and returns
+ * GPSO_E_STATE for it while no set is resident.  The kind is never screened.  gpso_acq_eval_host cannot see the maxima and
+ * returns GPSO_E_ARG for it; gpso_acq_mes_eval_host and gpso_batch_greedy_mes_host are the host twins that take them as
+ * arguments (k in 1..64, every value finite; no context and no GPU).  No sharded variants. */
+#define GPSO_ACQ_MES 5
+#define GPSO_ACQ_MAX_MAXIMA 64
+int gpso_acq_set_maxima(gpso_ctx* ctx, const double* ystar /* [k] host; k = 0 clears */, int k);
+int gpso_acq_get_maxima(gpso_ctx* ctx, double* ystar /* [64], nullable */, int* k);
+int gpso_acq_mes_eval_host(const double* ystar, int k, int latent, const double* mean, const double* var, double noise,
+                           int64_t n, double* out);
+
+/* The functions the MES map and gpso_max_logcdf are made of, on their own (csrc/acq.hpp: written out so that host and
+ * device agree to the bit; this entry exists so that a test can hold them to an extended-precision reference):
+ * fn 0: exp(x); 1: log(x); 2: log1p(x), x > -1; 3: erfc(x); 4: T^2 (1 - T R(T)) for 1 <= T <= 10, R Mills' ratio.
+ * No context and no GPU; GPSO_E_ARG for another fn or a NULL pointer. */
+int gpso_acq_math_host(int fn, const double* x, int64_t n, double* out);
+
+/* The law of the maximum over m leaves taken as independent, at g thresholds:
+ *   logcdf[i] = sum_j log Phi((y_i - mean_j) / sqrt(max(var_j - var_sub, 0)))
+ * -- what a Gumbel law is fitted to when y* is sampled without a path set.  mean / var [m]: float64 living in `mem`, the
+ * columns gpso_acq_values writes; var_sub: the noise for the latent law, or 0.  y / logcdf [g]: host, g in 1..64; m >= 1.
+ * A row with a NaN mean or var is skipped, *n_used (nullable) counts the others.  A row with s = 0 adds 0, log 1/2 or
+ * -inf by the sign of y - mean.  log Phi has a tail form, so a threshold far below a leaf's mean gives a large finite
+ * negative number.  One pass: a workgroup of four waves owns 512 consecutive leaves, a thread two of them in registers; the
+ * thresholds are walked in order, and for each the wave folds its 64 lanes' terms in a fixed butterfly and the four waves'
+ * sums are added in wave order -- one partial per workgroup and threshold (a thread's g sums pass through one register in
+ * turn, they do not lie side by side: csrc/maxcdf.hip says why).  A single workgroup then adds the workgroups' partials in
+ * index order, one thread per threshold: m / 512 dependent additions, 137 at m = 70 001 and 2 * 10^5 at m = 10^8, where that
+ * stage is what the call costs.  No floating-point atomics, a grid that depends on m only, the same bits for the same
+ * call.  Reads nothing of the posterior and changes nothing of the context but a
+ * workspace of its own.  GPSO_E_ARG: a NULL pointer, a bad mem, m < 1, g outside 1..64, a var_sub or a y that is NaN;
+ * GPSO_E_STATE while an asynchronous best-UCB ticket is open.  The host twin adds the rows in index order. */
+int gpso_max_logcdf(gpso_ctx* ctx, const double* mean, const double* var, int mem, int64_t m, double var_sub,
+                    const double* y /* [g] host */, int g, double* logcdf /* [g] host */, int64_t* n_used /* nullable */);
+int gpso_max_logcdf_host(const double* mean, const double* var, int64_t m, double var_sub, const double* y, int g,
+                         double* logcdf, int64_t* n_used /* nullable */);
+
 /* ---- latent cross-covariance and greedy batch selection (no counterpart in the reference) ----------------------------
  *
  * Every posterior the predict path serves installs mean = k*^T alpha + c, var = variance - |C k*|^2 + noise over its
@@ -764,6 +818,10 @@ int gpso_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
 int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise,
                            double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
                            int* n_picked, double* var_after /* nullable */);
+/* ... with GPSO_ACQ_MES under the k maxima ystar (latent as in gpso_acq) */
+int gpso_batch_greedy_mes_host(const double* ystar, int k, int latent, const double* mean, const double* s2, const double* cov,
+                               double noise, double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
+                               int* n_picked, double* var_after /* nullable */);
 
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 

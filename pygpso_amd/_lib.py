@@ -47,7 +47,8 @@ CONTRACTION_AUTO, CONTRACTION_F32, CONTRACTION_F16 = 0, 1, 2
 SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FUSED32 = 0, 1, 2, 3
 OPTF_TOL_VAR, OPTF_TOL_MEAN = 100, 101
 GEN_F64, GEN_F32, GEN_AUTO = 0, 1, 2
-ACQ_UCB_VAR, ACQ_UCB_STD, ACQ_EI, ACQ_LOGEI, ACQ_PI = 0, 1, 2, 3, 4
+ACQ_UCB_VAR, ACQ_UCB_STD, ACQ_EI, ACQ_LOGEI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4, 5
+ACQ_MAX_MAXIMA = 64  # gpso_acq_set_maxima keeps at most this many; gpso_max_logcdf takes at most this many thresholds
 FITMATH_NONE, FITMATH_SMALL, FITMATH_F32, FITMATH_F64, FITMATH_BF16X6, FITMATH_F16X3 = 0, 1, 2, 3, 4, 5  # gpso_last_count(ctx, 2)
 GEN_IDS = {"float64": GEN_F64, "f64": GEN_F64, "float32": GEN_F32, "f32": GEN_F32, "auto": GEN_AUTO}
 DTYPE_IDS = {"float64": F64, "fp64": F64, "f64": F64, "float32": F32, "fp32": F32, "f32": F32, "mixed": MIXED}
@@ -161,11 +162,23 @@ SIGNATURES = {
     "gpso_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_int]),
     "gpso_acq_eval_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, C.c_double, C.c_int64, _c_double_p]),
+    "gpso_acq_set_maxima": (C.c_int, [C.c_void_p, _c_double_p, C.c_int]),
+    "gpso_acq_get_maxima": (C.c_int, [C.c_void_p, _c_double_p, C.POINTER(C.c_int)]),
+    "gpso_acq_mes_eval_host": (C.c_int, [_c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, C.c_double, C.c_int64,
+                                         _c_double_p]),
+    "gpso_acq_math_host": (C.c_int, [C.c_int, _c_double_p, C.c_int64, _c_double_p]),
+    "gpso_max_logcdf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_double, _c_double_p, C.c_int,
+                                  _c_double_p, _c_int64_p]),
+    "gpso_max_logcdf_host": (C.c_int, [_c_double_p, _c_double_p, C.c_int64, C.c_double, _c_double_p, C.c_int, _c_double_p,
+                                       _c_int64_p]),
     "gpso_cross_cov": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_double_p, C.c_int, C.c_void_p, C.c_int]),
     "gpso_best_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_double, C.c_int, _c_int64_p,
                                   _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]),
     "gpso_batch_greedy_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, _c_double_p, C.c_double, C.c_double, C.c_int64, C.c_int,
                                          _c_int64_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), _c_double_p]),
+    "gpso_batch_greedy_mes_host": (C.c_int, [_c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, _c_double_p, C.c_double,
+                                             C.c_double, C.c_int64, C.c_int, _c_int64_p, _c_double_p, _c_double_p,
+                                             C.POINTER(C.c_int), _c_double_p]),
     "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,

@@ -11,6 +11,11 @@ optimiser's loop may rank by, because ``GPSOptimiser._tree_select`` compares a l
 
 ``EI``, ``LogEI`` and ``PI`` rank leaves against an incumbent; their values are improvements, log-improvements and
 probabilities, not scores, so they serve ``gp_eval_best_acq`` / ``gp_acq_values`` / ``polish`` but not the loop.
+
+``MES`` (max-value entropy search, Wang & Jegelka 2017) ranks a leaf by the information it carries about the optimum's
+VALUE, from K sampled maxima y* (``max_value_samples`` of the models): (1/K) sum_k t((y*_k - mean) / s) with
+t(g) = g phi(g) / (2 Phi(g)) - log Phi(g).  Its values are nats, not scores; it serves ``gp_eval_best_acq``,
+``gp_acq_values``, ``select_batch`` and ``mes_select``, not the loop and not ``polish``.
 """
 from __future__ import annotations
 
@@ -83,14 +88,29 @@ class PI(EI):
     kind, name = L.ACQ_PI, "pi"
 
 
-BY_NAME = {c.name: c for c in (UCBVar, UCBStd, EI, LogEI, PI)}
+class MES(Acquisition):
+    """``maxima``: the sampled maxima y* (at most 64 finite values) the engine installs on its context before a call
+    (``gpso_acq_set_maxima``); ``None``: the call reads whatever the context holds.  ``latent`` (the default): s is the
+    latent standard deviation, the quantity the entropy of y* is about."""
+
+    kind, name = L.ACQ_MES, "mes"
+
+    def __init__(self, latent=True, maxima=None):
+        super().__init__(latent=latent)
+        self.maxima = None if maxima is None else np.array(maxima, dtype=np.float64).reshape(-1)
+
+    def __repr__(self):
+        return f"MES(latent={self.latent}, maxima={None if self.maxima is None else self.maxima.tolist()})"
+
+
+BY_NAME = {c.name: c for c in (UCBVar, UCBStd, EI, LogEI, PI, MES)}
 BY_NAME["ucb"] = UCBVar
 SCORE_UNIT_NAMES = tuple(n for n, c in BY_NAME.items() if c.score_units and n != "ucb")
 
 
 def resolve(acquisition, varsigma=None, **kwargs):
     """A spec from a spec or a name.  The UCB kinds take ``varsigma``; EI / LogEI / PI take ``xi``, ``latent``,
-    ``incumbent``."""
+    ``incumbent``; MES takes ``latent`` and ``maxima``."""
     if isinstance(acquisition, Acquisition):
         return acquisition
     try:

@@ -123,6 +123,14 @@ struct Engine {
   // mean, var and the acquisition column of every leaf (each output nullable)
   virtual int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
                          double* value, int out_mem) = 0;
+  // GPSO_ACQ_MES: the sampled maxima a context keeps for the epilogues (the caller's numbers: nothing here drops them)
+  virtual int set_maxima(const double* ystar, int k) = 0;
+  double maxima_host[GPSO_ACQ_MAX_MAXIMA] = {};
+  int maxima_k = 0;
+  const double* maxima_dev = nullptr;
+  // sum_j log Phi((y_i - mean_j) / s_j) at g thresholds (maxcdf.hip)
+  virtual int max_logcdf(const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g,
+                         double* logcdf, int64_t* n_used) = 0;
   virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
                        int nseg, const AcqSpec& acq, int64_t* idx, double* mean, double* var,
                        double* ucb) = 0;
@@ -481,6 +489,7 @@ struct EngineT : Engine {
   // predict workspace
   DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
       live_cnt, best_pos, gath, wbase, ovals2, bhdr;
+  DevBuf acq_maxima, mcdf_work, mcdf_in;  // GPSO_ACQ_MES's maxima; gpso_max_logcdf's partials and staged columns
   // screened best-UCB calls (screen.hip): every leaf's mean, the blocks' maxima, the compaction's counts per part, the
   // survivors' raw rows, the control words (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
   DevBuf screen_my, screen_bmax, screen_cnt, screen_rows, screen_ctl, screen_cols;
@@ -2878,6 +2887,57 @@ struct EngineT : Engine {
                  double* value, int out_mem) override {
     return point_values(xs, xs_dtype, xs_mem, m, acq, true, mean, var, value, out_mem);
   }
+  // GPSO_ACQ_MES reads its maxima from this buffer (acq.hpp); no call of this context but the next set_maxima touches it
+  int set_maxima(const double* ystar, int k) override {
+    int rc = refuse_if_async("gpso_acq_set_maxima");
+    if (rc) return rc;
+    if (k < 0 || k > GPSO_ACQ_MAX_MAXIMA) return ctx->fail(GPSO_E_ARG, "k=%d maxima: 0..%d are kept", k, GPSO_ACQ_MAX_MAXIMA);
+    if (k > 0 && !ystar) return ctx->fail(GPSO_E_ARG, "ystar must not be NULL");
+    for (int i = 0; i < k; ++i)
+      if (!std::isfinite(ystar[i])) return ctx->fail(GPSO_E_ARG, "ystar[%d] is not finite", i);
+    if (k > 0) {
+      if ((rc = ensure(acq_maxima, GPSO_ACQ_MAX_MAXIMA * 8))) return rc;
+      HIPCHECK(hipStreamSynchronize(st()));  // (a blocking call's kernels are done; nothing reads the old set)
+      HIPCHECK(hipMemcpy(acq_maxima.p, ystar, (size_t)k * 8, hipMemcpyHostToDevice));
+      std::memcpy(maxima_host, ystar, (size_t)k * 8);
+    }
+    maxima_k = k;
+    maxima_dev = k > 0 ? as<double>(acq_maxima) : nullptr;
+    return GPSO_OK;
+  }
+  int max_logcdf(const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g, double* logcdf,
+                 int64_t* n_used) override {
+    int rc = refuse_if_async("gpso_max_logcdf");
+    if (rc) return rc;
+    if (!mean || !var || !y || !logcdf) return ctx->fail(GPSO_E_ARG, "mean, var, y and logcdf must not be NULL");
+    if (mem != GPSO_MEM_HOST && mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad mem %d", mem);
+    if (m < 1 || g < 1 || g > kMaxCdfThresholds) return ctx->fail(GPSO_E_ARG, "m=%lld, g=%d: m >= 1 and g in 1..%d", (long long)m, g, kMaxCdfThresholds);
+    if (var_sub != var_sub) return ctx->fail(GPSO_E_ARG, "var_sub is NaN");
+    for (int i = 0; i < g; ++i)
+      if (y[i] != y[i]) return ctx->fail(GPSO_E_ARG, "y[%d] is NaN", i);
+    const int64_t nblk = max_logcdf_blocks(m);
+    if ((rc = ensure(mcdf_work, (size_t)(nblk * kMaxCdfSlots + 2 * kMaxCdfSlots) * 8))) return rc;
+    double* partial = as<double>(mcdf_work);
+    double* y_dev = partial + nblk * kMaxCdfSlots;
+    double* out_dev = y_dev + kMaxCdfSlots;
+    const double *md = mean, *vd = var;
+    if (mem == GPSO_MEM_HOST) {
+      if ((rc = ensure(mcdf_in, (size_t)m * 16))) return rc;
+      HIPCHECK(hipMemcpyAsync(mcdf_in.p, mean, (size_t)m * 8, hipMemcpyHostToDevice, st()));
+      HIPCHECK(hipMemcpyAsync(as<double>(mcdf_in) + m, var, (size_t)m * 8, hipMemcpyHostToDevice, st()));
+      md = as<double>(mcdf_in);
+      vd = md + m;
+    }
+    HIPCHECK(hipMemcpyAsync(y_dev, y, (size_t)g * 8, hipMemcpyHostToDevice, st()));
+    launch_max_logcdf(st(), md, vd, m, var_sub, y_dev, g, partial, out_dev);
+    if ((rc = launch_status())) return rc;
+    double out[kMaxCdfSlots];
+    HIPCHECK(hipMemcpyAsync(out, out_dev, (size_t)(g + 1) * 8, hipMemcpyDeviceToHost, st()));
+    HIPCHECK(hipStreamSynchronize(st()));
+    std::memcpy(logcdf, out, (size_t)g * 8);
+    if (n_used) *n_used = (int64_t)out[g];
+    return GPSO_OK;
+  }
   // the body of both: gpso_predict is gpso_predict_acq without the column (want_ucb false: nothing of it is allocated,
   // computed or copied) and with both of its outputs required
   int point_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, bool want_ucb, double* mean, double* var,
@@ -3391,6 +3451,7 @@ struct EngineT : Engine {
   DevBuf one_ctl, one_partial, one_ppos;
   template <typename TG>
   int try_one_launch_t(const BestPlan& plan, BestCall& call, OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq, int mode) {
+    if (acq.kind == GPSO_ACQ_MES) return 2;  // (the tile kernel's epilogue keeps the maps it had: MES takes the next-best sequence)
     const int64_t cpad = (total + kLeafPad - 1) / kLeafPad * kLeafPad;
     int rc;
     if ((rc = ensure(leaves_s, (size_t)cpad * dp * sizeof(TG)))) return rc;
@@ -5233,8 +5294,9 @@ int gpso_best_ucb_grow(gpso_ctx* ctx, const double* bounds, int nseg, int depth,
 
 // ---- acquisition functions (acq.hpp) ----------------------------------------------------------
 // NULL when the record is usable, else what is wrong with it
-static const char* acq_refusal(const gpso_acq* a) {
+static const char* acq_refusal(const gpso_acq* a, bool mes = false /* the call can hand the kind its maxima */) {
   if (!a) return "acq must not be NULL";
+  if (a->kind == GPSO_ACQ_MES) return mes ? nullptr : "GPSO_ACQ_MES needs its maxima: this call cannot see them";
   if (a->kind < GPSO_ACQ_UCB_VAR || a->kind > GPSO_ACQ_PI) return "unknown acquisition kind";
   const bool ucb = a->kind == GPSO_ACQ_UCB_VAR || a->kind == GPSO_ACQ_UCB_STD;
   if (ucb && !std::isfinite(a->varsigma)) return "varsigma must be finite";
@@ -5243,46 +5305,62 @@ static const char* acq_refusal(const gpso_acq* a) {
   return nullptr;
 }
 static gpso::AcqSpec acq_spec(const gpso_acq* a) { return gpso::AcqSpec(a->kind, a->latent != 0, a->varsigma, a->incumbent, a->xi); }
-#define ACQ_ENTER()                                              \
-  ENTER();                                                       \
-  if (const char* why = acq_refusal(acq)) return ctx->fail(GPSO_E_ARG, "%s", why)
+// ... of a call on a context: GPSO_ACQ_MES reads the context's resident maxima
+static gpso::AcqSpec acq_spec(const gpso_ctx* ctx, const gpso_acq* a) {
+  if (a->kind != GPSO_ACQ_MES) return acq_spec(a);
+  return gpso::AcqSpec(a->kind, a->latent != 0, 0.0, 0.0, 0.0, ctx->eng->maxima_dev, ctx->eng->maxima_k);
+}
+static gpso::AcqSpec mes_spec_host(const double* ystar, int k, int latent) {
+  return gpso::AcqSpec(GPSO_ACQ_MES, latent != 0, 0.0, 0.0, 0.0, ystar, k);
+}
+static bool maxima_usable(const double* ystar, int k) {
+  if (!ystar || k < 1 || k > GPSO_ACQ_MAX_MAXIMA) return false;
+  for (int i = 0; i < k; ++i)
+    if (!std::isfinite(ystar[i])) return false;
+  return true;
+}
+#define ACQ_ENTER()                                                                    \
+  ENTER();                                                                             \
+  if (const char* why = acq_refusal(acq, true)) return ctx->fail(GPSO_E_ARG, "%s", why); \
+  if (acq->kind == GPSO_ACQ_MES && ctx->eng->maxima_k == 0)                            \
+  return ctx->fail(GPSO_E_STATE, "GPSO_ACQ_MES without maxima on this context: gpso_acq_set_maxima first")
 
 int gpso_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
                   const gpso_acq* acq, int64_t* idx, double* mean, double* var, double* value) {
   ACQ_ENTER();
-  return ctx->eng->best_ucb(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), idx, mean, var, value);
+  return ctx->eng->best_ucb(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(ctx, acq), idx, mean, var, value);
 }
 
 int gpso_best_acq_begin(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
                         const gpso_acq* acq) {
   ACQ_ENTER();
-  return ctx->eng->best_ucb_begin(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), nullptr, 0);
+  return ctx->eng->best_ucb_begin(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(ctx, acq), nullptr, 0);
 }
 
 int gpso_best_acq_grow(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq, int64_t* idx,
                        double* mean, double* var, double* value) {
   ACQ_ENTER();
-  return ctx->eng->best_ucb_grow(bounds, nseg, depth, acq_spec(acq), idx, mean, var, value);
+  return ctx->eng->best_ucb_grow(bounds, nseg, depth, acq_spec(ctx, acq), idx, mean, var, value);
 }
 
 int gpso_best_acq_grow_begin(gpso_ctx* ctx, const double* bounds, int nseg, int depth, const gpso_acq* acq) {
   ACQ_ENTER();
   if (!bounds) return ctx->fail(GPSO_E_ARG, "bounds must not be NULL");
-  return ctx->eng->best_ucb_begin(nullptr, GPSO_F64, GPSO_MEM_DEVICE, 0, nullptr, nseg, acq_spec(acq), bounds, depth);
+  return ctx->eng->best_ucb_begin(nullptr, GPSO_F64, GPSO_MEM_DEVICE, 0, nullptr, nseg, acq_spec(ctx, acq), bounds, depth);
 }
 
 int gpso_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double* mean,
                     double* var, double* value, int out_mem) {
   ACQ_ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
-  return ctx->eng->acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), mean, var, value, out_mem);
+  return ctx->eng->acq_values(xs, xs_dtype, xs_mem, m, acq_spec(ctx, acq), mean, var, value, out_mem);
 }
 
 int gpso_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double obs_noise, int q,
                     int64_t* idx, double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) {
   ACQ_ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
-  return ctx->eng->best_batch(xs, xs_dtype, xs_mem, m, acq_spec(acq), obs_noise, q, idx, mean, var, value, n_picked, var_after, out_mem);
+  return ctx->eng->best_batch(xs, xs_dtype, xs_mem, m, acq_spec(ctx, acq), obs_noise, q, idx, mean, var, value, n_picked, var_after, out_mem);
 }
 
 int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise, double obs_noise,
@@ -5291,6 +5369,58 @@ int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double
       !idx || !n_picked || noise != noise || !(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0)
     return GPSO_E_ARG;
   return gpso::batch_greedy_host(acq_spec(acq), mean, s2, cov, noise, obs_noise, m, q, idx, var, value, n_picked, var_after);
+}
+
+int gpso_batch_greedy_mes_host(const double* ystar, int k, int latent, const double* mean, const double* s2, const double* cov,
+                               double noise, double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
+                               int* n_picked, double* var_after) {
+  if (!maxima_usable(ystar, k) || m < 1 || q < 1 || q > gpso::kBatchMaxPicks || m > gpso::kBatchMaxCells / q || !mean || !s2 || !cov ||
+      !idx || !n_picked || noise != noise || !(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0)
+    return GPSO_E_ARG;
+  return gpso::batch_greedy_host(mes_spec_host(ystar, k, latent), mean, s2, cov, noise, obs_noise, m, q, idx, var, value, n_picked,
+                                 var_after);
+}
+
+int gpso_acq_set_maxima(gpso_ctx* ctx, const double* ystar, int k) {
+  ENTER();
+  return ctx->eng->set_maxima(ystar, k);
+}
+
+int gpso_acq_get_maxima(gpso_ctx* ctx, double* ystar, int* k) {
+  if (!ctx) return GPSO_E_ARG;
+  if (!k) return ctx->fail(GPSO_E_ARG, "k must not be NULL");
+  *k = ctx->eng->maxima_k;
+  if (ystar) std::memcpy(ystar, ctx->eng->maxima_host, (size_t)*k * 8);
+  return GPSO_OK;
+}
+
+int gpso_acq_mes_eval_host(const double* ystar, int k, int latent, const double* mean, const double* var, double noise, int64_t n,
+                           double* out) {
+  if (!maxima_usable(ystar, k) || n < 0 || (n > 0 && (!mean || !var || !out)) || noise != noise) return GPSO_E_ARG;
+  gpso::acq_eval_host(mes_spec_host(ystar, k, latent), mean, var, noise, (long long)n, out);
+  return GPSO_OK;
+}
+
+int gpso_acq_math_host(int fn, const double* x, int64_t n, double* out) {
+  if (n < 0 || (n > 0 && (!x || !out))) return GPSO_E_ARG;
+  return gpso::acq_math_host(fn, x, (long long)n, out) == 0 ? GPSO_OK : GPSO_E_ARG;
+}
+
+int gpso_max_logcdf(gpso_ctx* ctx, const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g,
+                    double* logcdf, int64_t* n_used) {
+  ENTER();
+  return ctx->eng->max_logcdf(mean, var, mem, m, var_sub, y, g, logcdf, n_used);
+}
+
+int gpso_max_logcdf_host(const double* mean, const double* var, int64_t m, double var_sub, const double* y, int g, double* logcdf,
+                         int64_t* n_used) {
+  if (!mean || !var || !y || !logcdf || m < 1 || g < 1 || g > kMaxCdfThresholds || var_sub != var_sub) return GPSO_E_ARG;
+  for (int i = 0; i < g; ++i)
+    if (y[i] != y[i]) return GPSO_E_ARG;
+  long long used = 0;
+  gpso::max_logcdf_host(mean, var, (long long)m, var_sub, y, g, logcdf, &used);
+  if (n_used) *n_used = used;
+  return GPSO_OK;
 }
 
 int gpso_screen_probe(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,

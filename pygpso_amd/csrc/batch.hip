@@ -218,7 +218,8 @@ __device__ __forceinline__ double w_entry(const ColArgs& a, int c, int64_t i) {
   return w;
 }
 
-template <int NB, bool ROUND>
+// MES: the instance that scores by GPSO_ACQ_MES carries its loop over the maxima; the other kinds' instance does not (acq.hpp)
+template <int NB, bool ROUND, bool MES = false>
 __global__ __launch_bounds__(kThreads) void batch_col_kernel(ColArgs a) {
   if (ROUND && stopped(a.st)) return;
   extern __shared__ __align__(16) unsigned char lds_raw[];
@@ -312,7 +313,7 @@ __global__ __launch_bounds__(kThreads) void batch_col_kernel(ColArgs a) {
         a.live[j] = 0;
       }
       if (alive && a.rank) {
-        v = batch_score(a.acq, a.mean[j], s2, a.noise);
+        v = batch_score<MES>(a.acq, a.mean[j], s2, a.noise);
         vi = j;
       }
     }
@@ -467,7 +468,8 @@ int launch_batch_round(hipStream_t s, const BatchColLaunch& g) {
   a.b = 1; a.dp = g.dp; a.kernel = g.kp.kernel; a.variance = g.kp.variance; a.nz = batch_w_slabs(g.n);
   a.st = g.st; a.t = g.t; a.rank = g.rank ? 1 : 0; a.G = g.G; a.s2 = g.s2; a.mean = g.mean; a.live = g.live; a.acq = g.acq;
   a.noise = g.kp.noise; a.bmax_v = g.bmax_v; a.bmax_i = g.bmax_i;
-  hipLaunchKernelGGL((batch_col_kernel<1, true>), dim3((unsigned)((g.m + kCols - 1) / kCols), 1), dim3(kThreads), col_lds_bytes(g.dp, 1), s, a);
+  auto* fn = g.acq.kind == GPSO_ACQ_MES ? batch_col_kernel<1, true, true> : batch_col_kernel<1, true, false>;
+  hipLaunchKernelGGL(fn, dim3((unsigned)((g.m + kCols - 1) / kCols), 1), dim3(kThreads), col_lds_bytes(g.dp, 1), s, a);
   return 0;
 }
 

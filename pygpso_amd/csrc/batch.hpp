@@ -22,8 +22,9 @@ constexpr int kBatchMaxPicks = 64;                    // q of gpso_best_batch, b
 constexpr int64_t kBatchMaxCells = (int64_t)1 << 27;  // q * m: the doubles of G
 
 // the value a live row is ranked by in the rounds after the first
+template <bool WITH_MES = true>
 GPSO_ACQ_HD inline double batch_score(const AcqSpec& a, double mean, double s2, double noise) {
-  return acq_value(a, mean, (a.latent && a.kind != GPSO_ACQ_UCB_VAR) ? s2 - noise : s2);
+  return acq_value<WITH_MES>(a, mean, (a.latent && a.kind != GPSO_ACQ_UCB_VAR) ? s2 - noise : s2);
 }
 
 // does (v, i) rank before (bv, bi)?  i < 0: no candidate; bi < 0: no holder yet.  A total order, so every merge tree gives

@@ -142,7 +142,12 @@ struct LeafFinalize {
   // `latent` is set, the predictive one otherwise
   int kind = GPSO_ACQ_UCB_VAR, latent = 0;
   double incumbent = 0, xi = 0;
+  // GPSO_ACQ_MES: the context's sampled maxima (device memory) and their count
+  const double* ystar = nullptr;
+  int nystar = 0;
   LeafFinalize& with(const AcqSpec& a) {
+    ystar = a.ystar;
+    nystar = a.nystar;
     varsigma = a.varsigma;
     kind = a.kind;
     latent = a.latent;
@@ -169,6 +174,14 @@ void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, 
                          const int64_t* screen_ctl = nullptr /* the list holds a screened call's survivors (launch_screen's ctl): the
                          last kernel judges the record (screen.hpp: screen_accepts) -- status slot 1.0: refused; the slot in front of
                          it: the survivors' count */, int64_t screen_cap = 0);
+
+// ---- maxcdf.hip: the law of the maximum at g thresholds (gpso_max_logcdf) ------------------------------------------------
+// mean / var [m] and y_dev [g] on the device; partial: max_logcdf_blocks(m) * kMaxCdfSlots doubles; out [g + 1] on the
+// device: the g sums, then the number of rows without a NaN.  Two launches, no atomics, a grid that depends on m only
+constexpr int kMaxCdfThresholds = 64, kMaxCdfSlots = kMaxCdfThresholds + 1, kMaxCdfLeaves = 512;
+inline int64_t max_logcdf_blocks(int64_t m) { return (m + kMaxCdfLeaves - 1) / kMaxCdfLeaves; }
+void launch_max_logcdf(hipStream_t st, const double* mean, const double* var, int64_t m, double var_sub, const double* y_dev, int g,
+                       double* partial, double* out);
 
 // ---- screen.hip: screened best-UCB calls (screen.hpp) ------------------------------------------------------------------
 // The mean pass of a batch of m float leaves: my[m], every leaf's mean -- the bits the split tile kernel with the fp16 split and

@@ -59,10 +59,11 @@ __device__ __forceinline__ bool leaf_norm_is_nan(const void* lnorm, int f64, int
   return q != q;
 }
 // one leaf: sum the row blocks' partials, form mean / var (+ noise) / ucb, store them; returns ucb.
-// ACQ false: the reference's rule only (the arg-max kernels of a gpso_best_ucb call: their code as it was before the
-// acquisition maps, registers included); true: whatever f.kind names -- the kind arrives as a kernel argument, so the
-// branch is scalar and uniform over the launch
-template <bool ACQ>
+// ACQ 0: the reference's rule only (the arg-max kernels of a gpso_best_ucb call: their code as it was before the
+// acquisition maps, registers included); 1: whatever f.kind names among the kinds up to GPSO_ACQ_PI -- the kind arrives as
+// a kernel argument, so the branch is scalar and uniform over the launch; 2: GPSO_ACQ_MES as well -- its loop over the
+// maxima is code and registers the other kinds' kernels do not carry
+template <int ACQ>
 __device__ __forceinline__ double finalize_leaf(const LeafFinalize& f, int64_t j) {
   double v = 0, mu = 0;
   for (int b = 0; b < f.nbi; ++b) {
@@ -83,7 +84,7 @@ __device__ __forceinline__ double finalize_leaf(const LeafFinalize& f, int64_t j
     asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
     u = my + prod;
   } else {
-    u = acq_value(AcqSpec(f.kind, f.latent, f.varsigma, f.incumbent, f.xi), my, f.latent ? fv : vy);
+    u = acq_value<ACQ == 2>(AcqSpec(f.kind, f.latent, f.varsigma, f.incumbent, f.xi, f.ystar, f.nystar), my, f.latent ? fv : vy);
   }
   f.ucb[j] = u;
   return u;
@@ -346,7 +347,7 @@ __device__ __forceinline__ void one_launch_epilogue(const OneLaunch& o, int tid,
   double u = 0;
   int64_t id = -1;
   if (mine_row) {
-    u = finalize_leaf<true>(o.fin, j);
+    u = finalize_leaf<1>(o.fin, j);  // (GPSO_ACQ_MES does not take this route)
     id = (o.mode == 1) ? o.key[j] : j;
   }
   for (int seg = 0; seg < o.nseg; ++seg) {
@@ -904,6 +905,7 @@ template void launch_pack_linv_bf16<float>(hipStream_t, int, const float*, int64
 template void launch_pack_linv_bf16<double>(hipStream_t, int, const double*, int64_t, int64_t, void*, int64_t);
 
 // ---------------------------------------------------------------------------------------------
+template <bool MES>
 __global__ __launch_bounds__(256) void leaf_finalize_kernel(const double* __restrict__ part_var,
                                                             const double* __restrict__ part_mean,
                                                             int nbi, int64_t mpad, int64_t m,
@@ -933,10 +935,12 @@ __global__ __launch_bounds__(256) void leaf_finalize_kernel(const double* __rest
       asm volatile("" : "+v"(prod));  // keep the product rounded on its own: no fma contraction
       ucb[j] = my + prod;
     } else {
-      ucb[j] = acq_value(acq, my, acq.latent ? fv : vy);
+      ucb[j] = acq_value<MES>(acq, my, acq.latent ? fv : vy);
     }
   }
 }
+// which instantiation of the epilogues serves a kind (finalize_leaf)
+static inline int acq_level(int kind) { return kind == GPSO_ACQ_UCB_VAR ? 0 : kind == GPSO_ACQ_MES ? 2 : 1; }
 
 __device__ __forceinline__ Best block_best(Best mine, Best* sh) {
   for (int off = 32; off > 0; off >>= 1) {
@@ -958,7 +962,7 @@ __device__ __forceinline__ Best block_best(Best mine, Best* sh) {
 // stage 1: grid (nblk, nseg); each block scans a strided share of its segment.  FIN (round 4): the leaves arrive as
 // the tile kernel's partial sums and are FINALISED here (leaf_finalize_kernel's arithmetic, leaf for leaf: every leaf
 // of [0, M) lies in exactly one segment) -- one launch and one pass over mean / var / ucb less per call
-template <bool FIN, bool ACQ>
+template <bool FIN, int ACQ>
 __global__ __launch_bounds__(256) void seg_argmax_stage1(const double* __restrict__ ucb,
                                                          const int64_t* __restrict__ seg_off,
                                                          Best* __restrict__ partial, LeafFinalize fin) {
@@ -1022,7 +1026,7 @@ __global__ __launch_bounds__(256) void seg_argmax_stage2(const Best* __restrict_
 // [seg * uniq, (seg + 1) * uniq) plus those rows of the appended tail [nseg * uniq, *live) whose key
 // falls into it.  The order is np.argmax's on (ucb, reference row index), so the winner and its index
 // are what scoring the full duplicated list would give.
-template <bool FIN, bool ACQ>
+template <bool FIN, int ACQ>
 __global__ __launch_bounds__(256) void keyed_argmax_stage1(const double* __restrict__ ucb,
                                                            const int64_t* __restrict__ key, int64_t rows,
                                                            int64_t uniq, int nseg,
@@ -1141,7 +1145,7 @@ __global__ __launch_bounds__(256) void keyed_argmax_stage2(const Best* __restric
 // Small batches (round 4): finalize + both arg-max stages in ONE launch of one workgroup.  Every live leaf is finalised
 // exactly once (finalize_leaf), every segment reduced with np.argmax's rule on (ucb, index / reference key): the same
 // records seg_argmax_* / keyed_argmax_* produce, with two launches (and the copy back) less.
-template <bool KEYED, bool ACQ>
+template <bool KEYED, int ACQ>
 __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
   __shared__ Best sh[4];
   __shared__ int64_t shp[4];
@@ -1226,9 +1230,9 @@ __global__ __launch_bounds__(256) void small_best_kernel(SmallBest a) {
 
 void launch_small_best(hipStream_t st, const SmallBest& a, bool keyed) {
   // (the acquisition maps cost registers and code: the reference's rule keeps the kernels it had)
-  const bool acq = a.fin.kind != GPSO_ACQ_UCB_VAR;
-  auto* fn = keyed ? (acq ? small_best_kernel<true, true> : small_best_kernel<true, false>)
-                   : (acq ? small_best_kernel<false, true> : small_best_kernel<false, false>);
+  const int acq = acq_level(a.fin.kind);
+  auto* fn = keyed ? (acq == 2 ? small_best_kernel<true, 2> : acq ? small_best_kernel<true, 1> : small_best_kernel<true, 0>)
+                   : (acq == 2 ? small_best_kernel<false, 2> : acq ? small_best_kernel<false, 1> : small_best_kernel<false, 0>);
   hipLaunchKernelGGL(fn, dim3(1), dim3(256), 0, st, a);
 }
 
@@ -1440,25 +1444,43 @@ void launch_leaf_finalize(hipStream_t st, const double* part_var, const double* 
                           double* mean, double* var, double* ucb, const void* lnorm, int lnorm_f64) {
   const int64_t blocks = (m + 255) / 256;
   if (blocks == 0) return;
-  hipLaunchKernelGGL(leaf_finalize_kernel, dim3((unsigned)blocks), dim3(256), 0, st, part_var,
-                     part_mean, nbi, mpad, m, kp, acq, mean, var, ucb, lnorm, lnorm_f64);
+  hipLaunchKernelGGL(acq.kind == GPSO_ACQ_MES ? leaf_finalize_kernel<true> : leaf_finalize_kernel<false>, dim3((unsigned)blocks),
+                     dim3(256), 0, st, part_var, part_mean, nbi, mpad, m, kp, acq, mean, var, ucb, lnorm, lnorm_f64);
 }
 
 void acq_eval_host(const AcqSpec& a, const double* mean, const double* var, double noise, long long n, double* out) {
   for (long long i = 0; i < n; ++i) out[i] = acq_value(a, mean[i], a.latent && a.kind != GPSO_ACQ_UCB_VAR ? var[i] - noise : var[i]);
 }
 
+// gpso_acq_math_host: the written-out functions of acq.hpp on their own (tests/test_mes_cpu.py holds them to mpmath)
+int acq_math_host(int fn, const double* x, long long n, double* out) {
+  for (long long i = 0; i < n; ++i) {
+    switch (fn) {
+      case 0: out[i] = acq_exp(x[i]); break;
+      case 1: out[i] = acq_log(x[i]); break;
+      case 2: out[i] = acq_log1p(x[i]); break;
+      case 3: out[i] = acq_erfc(x[i]); break;
+      case 4: out[i] = acq_mills_p(x[i], 0.0); break;
+      default: return -1;
+    }
+  }
+  return 0;
+}
+
 void launch_seg_argmax(hipStream_t st, const double* mean, const double* var, const double* ucb,
                        const int64_t* seg_off_dev, int nseg, int nblk, void* partial_dev,
                        double* out_vals_dev, const LeafFinalize* fin, double* host_vals, double done_token) {
-  if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
-    hipLaunchKernelGGL((seg_argmax_stage1<true, true>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+  if (fin != nullptr && acq_level(fin->kind) == 2)
+    hipLaunchKernelGGL((seg_argmax_stage1<true, 2>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+                       seg_off_dev, reinterpret_cast<Best*>(partial_dev), *fin);
+  else if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
+    hipLaunchKernelGGL((seg_argmax_stage1<true, 1>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
                        seg_off_dev, reinterpret_cast<Best*>(partial_dev), *fin);
   else if (fin != nullptr)
-    hipLaunchKernelGGL((seg_argmax_stage1<true, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+    hipLaunchKernelGGL((seg_argmax_stage1<true, 0>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
                        seg_off_dev, reinterpret_cast<Best*>(partial_dev), *fin);
   else
-    hipLaunchKernelGGL((seg_argmax_stage1<false, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
+    hipLaunchKernelGGL((seg_argmax_stage1<false, 0>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb,
                        seg_off_dev, reinterpret_cast<Best*>(partial_dev), LeafFinalize{});
   hipLaunchKernelGGL(seg_argmax_stage2, dim3((unsigned)nseg), dim3(256), 0, st,
                      reinterpret_cast<const Best*>(partial_dev), nblk, seg_off_dev, mean, var, ucb, nseg,
@@ -1469,14 +1491,17 @@ void launch_keyed_argmax(hipStream_t st, const double* mean, const double* var, 
                          const int64_t* key_dev, int64_t rows, int64_t uniq, int nseg, const int64_t* live_dev,
                          int nblk, void* partial_dev, int64_t* pos_dev, double* out_vals_dev, const LeafFinalize* fin,
                          double* host_vals, double done_token, const int64_t* screen_ctl, int64_t screen_cap) {
-  if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
-    hipLaunchKernelGGL((keyed_argmax_stage1<true, true>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+  if (fin != nullptr && acq_level(fin->kind) == 2)
+    hipLaunchKernelGGL((keyed_argmax_stage1<true, 2>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+                       rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
+  else if (fin != nullptr && fin->kind != GPSO_ACQ_UCB_VAR)
+    hipLaunchKernelGGL((keyed_argmax_stage1<true, 1>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
   else if (fin != nullptr)
-    hipLaunchKernelGGL((keyed_argmax_stage1<true, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+    hipLaunchKernelGGL((keyed_argmax_stage1<true, 0>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, *fin);
   else
-    hipLaunchKernelGGL((keyed_argmax_stage1<false, false>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
+    hipLaunchKernelGGL((keyed_argmax_stage1<false, 0>), dim3((unsigned)nblk, (unsigned)nseg), dim3(256), 0, st, ucb, key_dev,
                        rows, uniq, nseg, live_dev, reinterpret_cast<Best*>(partial_dev), pos_dev, LeafFinalize{});
   hipLaunchKernelGGL(keyed_argmax_stage2, dim3((unsigned)nseg), dim3(256), 0, st,
                      reinterpret_cast<const Best*>(partial_dev), pos_dev, nblk, rows, mean, var, ucb, live_dev,

@@ -894,11 +894,19 @@ class HipGPEngine:
             raise ValueError(f"bounds have D={d}, model has D={self.d}")
         return b, nseg
 
+    def _acq_rec(self, acq, incumbent):
+        """The ``gpso_acq`` record of a call on this context; a spec that carries maxima (``acquisition.MES``) has them
+        installed first, unless they are the resident ones already."""
+        maxima = getattr(acq, "maxima", None)
+        if maxima is not None and not np.array_equal(np.asarray(maxima, dtype=np.float64).reshape(-1), self.acq_get_maxima()):
+            self.acq_set_maxima(maxima)
+        return acq.c_struct(incumbent)
+
     def best_acq(self, xs, acq, seg_off=None, incumbent=None):
         """``best_ucb`` ranked by the acquisition spec ``acq`` -> (idx, mean, var, value) arrays of length nseg."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)
         nseg, so_ptr, _so = self._seg_args(seg_off)
-        rec = acq.c_struct(incumbent)
+        rec = self._acq_rec(acq, incumbent)
         idx, mean, var, val, pi, pm, pv, pu = self._winner_bufs(nseg)
         rc = self._lib.gpso_best_acq(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec), pi, pm, pv, pu)
         if rc < 0:
@@ -909,7 +917,7 @@ class HipGPEngine:
         """Non-blocking ``best_acq``: a ticket for ``best_ucb_end`` (the two slots of ``best_ucb_begin``)."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)
         nseg, so_ptr, _so = self._seg_args(seg_off)
-        rec = acq.c_struct(incumbent)
+        rec = self._acq_rec(acq, incumbent)
         ticket = self._check(self._lib.gpso_best_acq_begin(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec)))
         self._open_tickets = getattr(self, "_open_tickets", {})
         self._open_tickets[ticket] = (nseg, keep)
@@ -918,7 +926,7 @@ class HipGPEngine:
     def best_acq_grow(self, bounds, depth, acq, incumbent=None):
         """``best_ucb_grow`` ranked by the acquisition spec ``acq``."""
         b, nseg = self._bounds_arg(bounds)
-        rec = acq.c_struct(incumbent)
+        rec = self._acq_rec(acq, incumbent)
         idx, mean, var, val, pi, pm, pv, pu = self._winner_bufs(nseg)
         rc = self._lib.gpso_best_acq_grow(self._h, L.dptr(b), nseg, int(depth), C.byref(rec), pi, pm, pv, pu)
         if rc < 0:
@@ -927,7 +935,7 @@ class HipGPEngine:
 
     def best_acq_grow_begin(self, bounds, depth, acq, incumbent=None):
         b, nseg = self._bounds_arg(bounds)
-        rec = acq.c_struct(incumbent)
+        rec = self._acq_rec(acq, incumbent)
         ticket = self._check(self._lib.gpso_best_acq_grow_begin(self._h, L.dptr(b), nseg, int(depth), C.byref(rec)))
         self._open_tickets = getattr(self, "_open_tickets", {})
         self._open_tickets[ticket] = (nseg, None)
@@ -936,7 +944,7 @@ class HipGPEngine:
     def acq_values(self, xs, acq, incumbent=None):
         """``predict`` with the acquisition column: (mean[M], var[M], value[M]) float64 on the host."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)
-        rec = acq.c_struct(incumbent)
+        rec = self._acq_rec(acq, incumbent)
         mean, var, val = (np.empty(m, dtype=np.float64) for _ in range(3))
         self._check(self._lib.gpso_acq_values(self._h, ptr, dt, mem, m, C.byref(rec), C.c_void_p(mean.ctypes.data),
                                               C.c_void_p(var.ctypes.data), C.c_void_p(val.ctypes.data), L.MEM_HOST))
@@ -953,6 +961,105 @@ class HipGPEngine:
         if rc != L.OK:
             raise L.GpsoHipError(rc, "gpso_acq_eval_host: bad acquisition record or arguments")
         return out
+
+    # -- max-value entropy search (csrc/acq.hpp: GPSO_ACQ_MES; csrc/maxcdf.hip) ---------------------------------------
+    def acq_set_maxima(self, ystar):
+        """Install the sampled maxima y* that ``acquisition.MES`` calls on this context read (``gpso_acq_set_maxima``): at
+        most 64 finite values; ``None`` or an empty list clears them.  They are the caller's numbers: fits, appends and
+        installs keep them.  Refused (E_STATE) while an asynchronous best-UCB ticket is open."""
+        ys = np.zeros(0) if ystar is None else L.as_f64(np.asarray(ystar, dtype=np.float64).reshape(-1))
+        self._check(self._lib.gpso_acq_set_maxima(self._h, L.dptr(ys) if ys.size else None, int(ys.size)))
+
+    def acq_get_maxima(self):
+        """The resident maxima -> float64 [k] (k = 0: none)."""
+        buf = np.empty(L.ACQ_MAX_MAXIMA, dtype=np.float64)
+        k = C.c_int(0)
+        self._check(self._lib.gpso_acq_get_maxima(self._h, L.dptr(buf), C.byref(k)))
+        return buf[:int(k.value)].copy()
+
+    @staticmethod
+    def acq_mes_eval_host(ystar, mean, var, noise=0.0, latent=True):
+        """The device's MES map on the CPU (``gpso_acq_mes_eval_host``: no context, no GPU) -> value[n].  With ``latent``
+        the map reads ``var - noise``."""
+        ys = L.as_f64(np.asarray(ystar, dtype=np.float64).reshape(-1))
+        mean = L.as_f64(np.asarray(mean).reshape(-1))
+        var = L.as_f64(np.asarray(var).reshape(-1), mean.shape)
+        out = np.empty_like(mean)
+        rc = L.load().gpso_acq_mes_eval_host(L.dptr(ys) if ys.size else None, int(ys.size), int(bool(latent)), L.dptr(mean), L.dptr(var),
+                                             float(noise), int(mean.shape[0]), L.dptr(out))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_acq_mes_eval_host: 1..64 finite maxima, a noise that is no NaN")
+        return out
+
+    ACQ_MATH = {"exp": 0, "log": 1, "log1p": 2, "erfc": 3, "mills_p": 4}
+
+    @staticmethod
+    def acq_math_host(name, x):
+        """One of the functions the MES map is made of (``gpso_acq_math_host``; csrc/acq.hpp) at the float64 array ``x``."""
+        x = L.as_f64(np.asarray(x, dtype=np.float64).reshape(-1))
+        out = np.empty_like(x)
+        rc = L.load().gpso_acq_math_host(HipGPEngine.ACQ_MATH[name], L.dptr(x), int(x.size), L.dptr(out))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_acq_math_host: bad arguments")
+        return out
+
+    def max_logcdf(self, mean, var, y, var_sub=0.0, want_used=False):
+        """log P(max_j f_j < y_i) under independent leaves: sum_j log Phi((y_i - mean_j) / sqrt(max(var_j - var_sub, 0)))
+        for at most 64 thresholds ``y`` (``gpso_max_logcdf``).  ``mean`` / ``var`` [M]: float64 numpy arrays or contiguous
+        float64 tensors on the engine's device.  Rows with a NaN are skipped; ``want_used`` adds their complement's count."""
+        y = L.as_f64(np.asarray(y, dtype=np.float64).reshape(-1))
+        out = np.empty_like(y)
+        used = C.c_int64(0)
+        if hasattr(mean, "data_ptr"):
+            if str(mean.dtype) != "torch.float64" or str(var.dtype) != "torch.float64" or not mean.is_contiguous() \
+                    or not var.is_contiguous() or mean.numel() != var.numel():
+                raise ValueError("mean / var must be contiguous float64 tensors of one length")
+            self._order_after(mean)
+            self._order_after(var)
+            pm, pv, mem, m = C.c_void_p(mean.data_ptr()), C.c_void_p(var.data_ptr()), L.MEM_DEVICE, int(mean.numel())
+        else:
+            mean = L.as_f64(np.asarray(mean).reshape(-1))
+            var = L.as_f64(np.asarray(var).reshape(-1), mean.shape)
+            pm, pv, mem, m = C.c_void_p(mean.ctypes.data), C.c_void_p(var.ctypes.data), L.MEM_HOST, int(mean.shape[0])
+        self._check(self._lib.gpso_max_logcdf(self._h, pm, pv, mem, m, float(var_sub), L.dptr(y), int(y.size), L.dptr(out),
+                                              C.byref(used)))
+        return (out, int(used.value)) if want_used else out
+
+    @staticmethod
+    def max_logcdf_host(mean, var, y, var_sub=0.0, want_used=False):
+        """``max_logcdf`` on the CPU (``gpso_max_logcdf_host``: no context, no GPU; the rows are added in index order)."""
+        mean = L.as_f64(np.asarray(mean).reshape(-1))
+        var = L.as_f64(np.asarray(var).reshape(-1), mean.shape)
+        y = L.as_f64(np.asarray(y, dtype=np.float64).reshape(-1))
+        out = np.empty_like(y)
+        used = C.c_int64(0)
+        rc = L.load().gpso_max_logcdf_host(L.dptr(mean), L.dptr(var), int(mean.shape[0]), float(var_sub), L.dptr(y), int(y.size),
+                                           L.dptr(out), C.byref(used))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_max_logcdf_host: M >= 1, 1..64 thresholds, no NaN among them")
+        return (out, int(used.value)) if want_used else out
+
+    @staticmethod
+    def batch_greedy_mes_host(ystar, mean, s2, cov, noise, obs_noise, q, latent=True):
+        """``batch_greedy_host`` under MES with the maxima ``ystar`` (``gpso_batch_greedy_mes_host``)."""
+        ys = L.as_f64(np.asarray(ystar, dtype=np.float64).reshape(-1))
+        mean = L.as_f64(np.asarray(mean).reshape(-1))
+        m = int(mean.shape[0])
+        s2 = L.as_f64(np.asarray(s2).reshape(-1), mean.shape)
+        cov = L.as_f64(np.asarray(cov), (m, m))
+        q = int(q)
+        cap = max(q, 1)
+        idx = np.full(cap, -1, dtype=np.int64)
+        var, val = (np.full(cap, np.nan, dtype=np.float64) for _ in range(2))
+        after = np.empty(m, dtype=np.float64)
+        n_picked = C.c_int(0)
+        rc = L.load().gpso_batch_greedy_mes_host(L.dptr(ys) if ys.size else None, int(ys.size), int(bool(latent)), L.dptr(mean), L.dptr(s2),
+                                                 L.dptr(cov), float(noise), float(obs_noise), m, q, L.i64ptr(idx), L.dptr(var),
+                                                 L.dptr(val), C.byref(n_picked), L.dptr(after))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_batch_greedy_mes_host: bad maxima or arguments")
+        k = int(n_picked.value)
+        return idx[:k].copy(), var[:k].copy(), val[:k].copy(), after
 
     # -- latent cross-covariance and greedy batch selection (csrc/batch.hip, csrc/batch.hpp) --------------------------
     def cross_cov(self, xa, xb, out=None):
@@ -981,7 +1088,7 @@ class HipGPEngine:
         fantasy variance that is not positive, or no distinct row left end the batch -- and, with ``want_var_after``, the
         predictive variance [M] of every row after them as a fifth entry."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)
-        rec = spec.c_struct(incumbent)
+        rec = self._acq_rec(spec, incumbent)
         q = int(q)
         cap = max(q, 1)
         idx = np.full(cap, -1, dtype=np.int64)

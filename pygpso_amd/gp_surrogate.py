@@ -609,6 +609,9 @@ class GPSurrogate:
         """(mean [M], var [M], value [M], dvalue [M, D]) of "ucb_std", "ei" or "logei" at the rows of ``normed_coords``: one
         ``gp_predict_grad`` call and the chain rule on the host, the quotients of log-EI in their tail-stable form
         (``pygpso_amd.acquisition.h_parts``).  The incumbent defaults to the largest training target."""
+        if objective not in ("ucb_std", "ei", "logei"):
+            raise ValueError(f"objective={objective!r}: 'ucb_std', 'ei' or 'logei' (MES has no gradient here: rank leaves with "
+                             f"mes_select / gp_eval_best_acq)")
         mean, var, dmean, dvar = self.gp_predict_grad(normed_coords)
         if incumbent is None and objective != "ucb_std":
             incumbent = float(np.max(self.current_training_data[1]))
@@ -627,11 +630,13 @@ class GPSurrogate:
 
     def gp_eval_best_acq(self, normed_coords, acquisition, incumbent=None, seg_off=None):
         """Per segment of ``seg_off`` (None: one) the row of ``normed_coords`` with the highest value of ``acquisition`` --
-        a name ("ucb_var", "ucb_std", "ei", "logei", "pi") or a spec of ``pygpso_amd.acquisition``: (idx, mean, var, value)
+        a name ("ucb_var", "ucb_std", "ei", "logei", "pi", "mes") or a spec of ``pygpso_amd.acquisition``: (idx, mean, var, value)
         arrays, idx relative to the segment start, the first on ties.  EI, log-EI and PI improve on ``incumbent``: by
         default the largest training target, in the units ``_gp_train`` saw.  Stores nothing."""
         self._require_model()
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        if acq.name == "mes":
+            self._joint_model("gp_eval_best_acq with MES")
         return self.gpflow_model.best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, seg_off, incumbent)
 
     def gp_acq_values(self, normed_coords, acquisition, incumbent=None):
@@ -639,7 +644,29 @@ class GPSurrogate:
         ``gp_eval_best_acq``); stores nothing."""
         self._require_model()
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        if acq.name == "mes":
+            self._joint_model("gp_acq_values with MES")
         return self.gpflow_model.acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, incumbent)
+
+    def max_value_samples(self, normed_coords, k=16, method="paths", rng=None, n_features=1024):
+        """``k`` samples of the optimum's value over the rows of ``normed_coords``, in the units ``_gp_train`` saw
+        (``HipGPR.max_value_samples``): ``method="paths"`` -- the maxima of ``k`` drawn posterior functions (replaces a
+        path set of ``gp_sample_paths``) -- or ``"gumbel"`` -- a Gumbel law fitted to the independent-leaves law of the
+        maximum.  Both are clamped from below at the largest training target.  Stores nothing."""
+        model = self._joint_model("max_value_samples")
+        return model.max_value_samples(np.ascontiguousarray(normed_coords, dtype=np.float64), k=k, method=method, rng=rng,
+                                       n_features=n_features)
+
+    def mes_select(self, normed_coords, k=16, method="paths", rng=None, seg_off=None):
+        """Max-value entropy search over the rows of ``normed_coords``: ``k`` samples of the optimum's value
+        (``max_value_samples``, over ALL the rows), then per segment of ``seg_off`` (None: one) the row that tells most
+        about it -- ``acquisition.MES`` on the latent variance, one ``gpso_best_acq`` call.  Returns (idx, mean, var,
+        value) as ``gp_eval_best_acq``; the samples stay installed on the engine (``acq_get_maxima``).  Stores nothing."""
+        from .acquisition import MES
+
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        maxima = self.max_value_samples(coords, k=k, method=method, rng=rng)
+        return self.gpflow_model.best_acq(coords, MES(latent=True, maxima=maxima), seg_off)
 
     def gp_cross_cov(self, a, b):
         """The latent posterior covariance [B, M] between the M rows of ``a`` and the B <= 64 rows of ``b`` (normed

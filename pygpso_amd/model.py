@@ -511,6 +511,40 @@ class HipGPR:
         inc = self._incumbent(acq, incumbent)
         return self._predicting(lambda: self.engine.acq_values(np.asarray(Xnew), acq, incumbent=inc))
 
+    def max_logcdf(self, mean, var, y, var_sub=0.0):
+        """log P(max_j f_j < y_i) over independent leaves with the given (mean, var - var_sub): ``gpso_max_logcdf``."""
+        return self._predicting(lambda: self.engine.max_logcdf(mean, var, y, var_sub))
+
+    def max_value_samples(self, Xnew, k=16, method="paths", rng=None, n_features=1024):
+        """``k`` samples of the optimum's value y* = max f over the rows of Xnew, for ``acquisition.MES(maxima=...)``
+        (``pygpso_amd.mes``).  ``"paths"``: draws ``k`` posterior functions (``sample_paths``, which replaces a resident
+        path set) and takes their maxima over the rows, ``eval_paths``'s ``best_val``.  ``"gumbel"``: one ``acq_values``
+        call, two ``max_logcdf`` calls of 64 thresholds each (more only where the coarse grid over [max mean,
+        max(mean + 6 s)] does not hold the quartiles) and a Gumbel law fitted to the 25 / 50 / 75 % points, sampled by
+        inversion.  Either way the samples are CLAMPED from below at the largest training target, as Wang & Jegelka do:
+        max f is at least the best value seen.  ``rng``: a seed or a ``numpy.random.Generator``; a seed reproduces them."""
+        from . import mes
+        from .acquisition import UCBVar
+
+        Xnew = np.asarray(Xnew)
+        k = int(k)
+        if not 1 <= k <= L.ACQ_MAX_MAXIMA:
+            raise ValueError(f"k={k}: 1..{L.ACQ_MAX_MAXIMA} maxima")
+        best = float(np.max(self._data[1]))
+        if method == "paths":
+            self.sample_paths(k, n_features=n_features, rng=rng)
+            return mes.clamp_at(np.asarray(self.eval_paths(Xnew, want_values=False)[2]).reshape(-1), best)
+        if method != "gumbel":
+            raise ValueError(f"method={method!r}: 'paths' or 'gumbel'")
+        mean, var, _ = self.acq_values(Xnew, UCBVar(0.0))
+        noise = float(self.predictive_noise())
+        ok = ~(np.isnan(mean) | np.isnan(var))
+        if not np.any(ok):
+            raise ValueError("max_value_samples: every row has a NaN prediction")
+        s = np.sqrt(np.maximum(var[ok] - noise, 0.0))
+        a, b, _, _ = mes.gumbel_fit(lambda y: self.max_logcdf(mean, var, y, noise), np.max(mean[ok]), np.max(mean[ok] + 6.0 * s))
+        return mes.clamp_at(mes.gumbel_draw(a, b, k, rng), best)
+
     def cross_cov(self, Xa, Xb):
         """The latent posterior covariance [B, M] between the M rows of Xa and the B <= 64 rows of Xb, cov[c, j] =
         Cov(f(Xa_j), f(Xb_c)); float64 and mixed engines."""
