@@ -2,33 +2,16 @@
 // No torch, no BLAS/solver libraries: every kernel launched here is hand-written (predict.hip,
 // fit.hip, grow.hip).
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <mutex>
-#include <set>
-#include <string>
-#include <utility>
 #include <limits>
-#include <vector>
+#include <set>
+#include <utility>
 
-#include "../../include/gpso_hip.h"
-#include "batch.hpp"
-#include "best_call.hpp"
-#include "common.hpp"
-#include "devbuf.hpp"
-#include "fit_call.hpp"
-#include "kernels.hpp"
-#include "screen.hpp"
-#include "rccl_api.hpp"
-#include "resident.hpp"
-#include "theta.hpp"
+#include "engine_core.hpp"
 
 using namespace gpso;
+using namespace gpso::host;
 
 namespace gpso {
 
@@ -61,146 +44,22 @@ int ensure_dyn_lds(const void* fn, int bytes) {
   return 0;
 }
 
+// launcher-side errors (hipFuncSetAttribute, unsupported GEMM shapes) + the HIP launch status
+int host::EngineCore::launch_status() {
+  HIPCHECK(hipGetLastError());
+  if (!g_launch_error.empty()) {
+    const std::string msg = g_launch_error;
+    g_launch_error.clear();
+    return ctx->fail(GPSO_E_HIP, "%s", msg.c_str());
+  }
+  return GPSO_OK;
+}
+
 }  // namespace gpso
 
 namespace {
 
 thread_local std::string g_create_error;
-
-constexpr int kMaxD = 48;                      // padded input dimension limit (LDS budgets)
-constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass of the tile kernel
-// GPSO_OPT_PARK_BYTES as a context is created: 256 MB, the best median of the sweeps 0 | 64 | 128 | 256 MB at C3
-// (profiles/park_reload_ab_sweep_c3.txt, park_reload_ab_pairs.txt; -DGPSO_PARK_BYTES_DEFAULT=... builds the other arms)
-// GPSO_OPT_SCREEN as a context is created (-DGPSO_SCREEN_DEFAULT=0 builds the unscreened arm of an A/B through bench.py)
-#ifndef GPSO_SCREEN_DEFAULT
-#define GPSO_SCREEN_DEFAULT 1
-#endif
-#ifndef GPSO_PARK_BYTES_DEFAULT
-#define GPSO_PARK_BYTES_DEFAULT (256 << 20)
-#endif
-constexpr int64_t kParkBytesDefault = GPSO_PARK_BYTES_DEFAULT;
-constexpr int kHyperHeader = 8;                // doubles in front of the lengthscales
-static_assert(kThetaMaxLs == kGradMaxLs, "a Theta holds as many lengthscales as the gradient kernels take");
-using FitScratch = gpso::FitScratch<kGradMaxLs, kHyperHeader, kMaxD>;  // (fit_call.hpp: the pinned scratch of a fit call)
-using FitCall = gpso::FitCall<FitScratch>;
-
-struct Engine {
-  virtual ~Engine() {}
-  virtual int set_data(const double* X, const double* y, int64_t n, int d) = 0;
-  // theta crosses this interface as one Theta (theta.hpp): lik is the noise variance, the likelihood's variance or its scale.
-  // (gpso_fit_eval / gpso_fit_eval_loo: th is NULL when the caller passed no lengthscales -- refused where it always was)
-  virtual int fit_eval(const Theta* th, double* nlml, double* grad) = 0;
-  virtual int set_posterior(const double* X, const double* L, const double* alpha, int64_t n, int d, const Theta& th) = 0;
-  // leave-one-out predictive of the resident fitted posterior / one evaluation of the LOO-CV objective (loo.hip)
-  virtual int loo(double* mean, double* var, double* lpd, double* loss) = 0;
-  virtual int fit_eval_loo(const Theta* th, double* loss, double* grad, double* nlml) = 0;
-  virtual int fit_batch_max() = 0;
-  virtual int fit_eval_batch(int kernel, const double* th, int nv, int n_ls, double* loss, double* grad, int* info) = 0;
-  virtual int fit_eval_batch_check(int kernel, int b, int n_ls) = 0;
-  virtual int set_noise_diag(const double* s, int64_t n) = 0;
-  virtual bool has_noise_diag() const = 0;
-  virtual int append(const double* Xnew, const double* ynew, const double* snew, int64_t k, double* nlml) = 0;
-  virtual int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean,
-                      double* var, int out_mem) = 0;
-  // mean, var and their gradients in the test points, from the dense factor (predict_grad.hip)
-  virtual int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean,
-                           double* dvar, int out_mem) = 0;
-  // the joint predictive at m test points: mean and full covariance, or draws and their arg-max (joint.hip)
-  virtual int predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
-                            int out_mem) = 0;
-  virtual int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t s,
-                           double* samples, int64_t* best_idx, double* best_val) = 0;
-  // pathwise posterior draws: functions kept on the context, evaluated at any number of points (paths.hip)
-  virtual int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t s) = 0;
-  virtual int paths_draw_q(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t s) = 0;
-  virtual int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values,
-                         int out_mem, int64_t* best_idx, double* best_val) = 0;
-  virtual void paths_info(int64_t* s, int64_t* f) const = 0;
-  // the latent cross-covariance of two point sets, and q leaves of one set picked greedily under hallucinated updates (batch.hip)
-  virtual int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem) = 0;
-  virtual int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx,
-                         double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) = 0;
-  // mean, var and the acquisition column of every leaf (each output nullable)
-  virtual int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
-                         double* value, int out_mem) = 0;
-  // GPSO_ACQ_MES: the sampled maxima a context keeps for the epilogues (the caller's numbers: nothing here drops them)
-  virtual int set_maxima(const double* ystar, int k) = 0;
-  double maxima_host[GPSO_ACQ_MAX_MAXIMA] = {};
-  int maxima_k = 0;
-  const double* maxima_dev = nullptr;
-  // sum_j log Phi((y_i - mean_j) / s_j) at g thresholds (maxcdf.hip)
-  virtual int max_logcdf(const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g,
-                         double* logcdf, int64_t* n_used) = 0;
-  virtual int best_ucb(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
-                       int nseg, const AcqSpec& acq, int64_t* idx, double* mean, double* var,
-                       double* ucb) = 0;
-  virtual int best_ucb_begin(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
-                             const AcqSpec& acq, const double* bounds, int depth) = 0;
-  virtual int best_ucb_end(int ticket, int64_t* idx, double* mean, double* var, double* ucb) = 0;
-  virtual int screen_probe(const void* xs, int xs_dtype, int xs_mem, int64_t m, double varsigma, double* my, double* ub,
-                           double* flag, double* info) = 0;
-  virtual int screen_list(int64_t max_rows, int64_t* key, float* rows, int64_t* live) = 0;
-  virtual int grow(const double* bounds, int nseg, int d, int depth, double* out) = 0;
-  virtual int best_ucb_grow(const double* bounds, int nseg, int depth, const AcqSpec& acq,
-                            int64_t* idx, double* mean, double* var, double* ucb) = 0;
-  virtual int get_matrix(int which, double* out) = 0;
-  virtual int get_vector(int which, double* out) = 0;
-  virtual int posterior_buffers(void** ptrs, int64_t* nbytes, int cap) = 0;
-  virtual int posterior_span(void** ptr, int64_t* offset, int64_t* nbytes) = 0;
-  virtual int posterior_span_at(int64_t offset, int64_t nbytes, void** ptr) = 0;
-  virtual int posterior_hash(uint64_t* out) = 0;
-  virtual int alloc_posterior(int64_t n, int d) = 0;
-  virtual int adopt_posterior() = 0;
-  virtual int64_t padded_n() const = 0;
-  virtual void problem_shape(int64_t* n_out, int* d_out) const = 0;
-  virtual int set_option(int option, int value) = 0;
-  virtual int set_option_f64(int option, double value) = 0;
-  virtual int precision_info(double* out) = 0;
-  virtual int broadcast_posterior(int root) = 0;
-  virtual int broadcast_posterior_rows(int root) = 0;
-  virtual int posterior_dirty_ranges(int64_t* offsets, int64_t* nbytes, int cap) = 0;
-  virtual int posterior_mark_synced() = 0;
-  virtual int best_ucb_sharded(const void* xs, int xs_dtype, int xs_mem, int64_t m_local, int64_t m_global,
-                               const int64_t* seg_off, int nseg, double varsigma, int64_t* idx, double* mean,
-                               double* var, double* ucb) = 0;
-  virtual int best_ucb_grow_sharded(const double* bounds, int nseg, int depth, double varsigma, int64_t* idx,
-                                    double* mean, double* var, double* ucb) = 0;
-  // the two halves of the sharded calls for an arbitrary (rank, world), without a communicator
-  virtual int shard_winners(int rank, int world, const void* xs, int xs_dtype, int xs_mem, int64_t m_local,
-                            int64_t m_global, const int64_t* seg_off, int nseg, double varsigma, double* payload) = 0;
-  virtual int shard_winners_grow(int rank, int world, const double* bounds, int nseg, int depth, double varsigma,
-                                 double* payload) = 0;
-  virtual int fold_winners(const double* gathered, int world, int64_t m_global, const int64_t* seg_off, int nseg,
-                           int64_t* idx, double* mean, double* var, double* ucb) = 0;
-  // variational GP (vgp.hip)
-  virtual int vgp_set_q(const double* mu, const double* S, int64_t n) = 0;
-  virtual int vgp_get_q(double* mu, double* S) = 0;
-  virtual int vgp_extend_q() = 0;
-  virtual int vgp_natgrad(const Theta& th, double gamma) = 0;
-  virtual int vgp_elbo(const Theta& th, double* loss, double* grad) = 0;
-  virtual int vgp_posterior(const Theta& th) = 0;
-  virtual int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) = 0;
-  // sparse GP regression on inducing points (sgpr.hip)
-  virtual int sgpr_set_inducing(const double* Z, int64_t m) = 0;
-  virtual int sgpr_select_inducing(const Theta& th, int64_t m, int64_t* idx_out) = 0;
-  virtual int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) = 0;
-  virtual int sgpr_get_factor(int which, double* out) = 0;
-  virtual int sgpr_bound(const Theta& th, double* loss, double* grad) = 0;
-  virtual int sgpr_posterior(const Theta& th, double* delta_out) = 0;
-  // ... and at a moving Z (inducing.hip): Z (nullable) replaces the resident inducing rows in place
-  virtual int sgpr_move_inducing(const double* Z) = 0;
-  virtual int sgpr_bound_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) = 0;
-  virtual int svgp_elbo_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) = 0;
-  // sparse variational GP on inducing points (svgp.hip)
-  // s2 > 0: the conjugate start at that noise variance (th.lik is not read); else the prior (th is not read)
-  virtual int svgp_init_q(const Theta& th, double s2) = 0;
-  virtual int svgp_set_q(const double* mu, const double* S, int64_t m) = 0;
-  virtual int svgp_get_q(double* mu, double* S) = 0;
-  virtual int svgp_natgrad(const Theta& th, double gamma) = 0;
-  virtual int svgp_elbo(const Theta& th, double* loss, double* grad) = 0;
-  virtual int svgp_posterior(const Theta& th, double* delta_out) = 0;
-  int vlik_kind = GPSO_LIK_GAUSSIAN;  // the VGP's likelihood (GPSO_LIK_*): what slot n_ls + 1 of u means
-};
 
 // contiguous share [lo, hi) of m items for `rank` of `world`: global order is preserved across ranks
 inline void shard_range(int64_t m, int rank, int world, int64_t* lo, int64_t* hi) {
@@ -211,188 +70,7 @@ inline void shard_range(int64_t m, int rank, int world, int64_t* lo, int64_t* hi
 
 }  // namespace
 
-// current-device guard: HIP calls act on the calling thread's current device
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = (prev == dev) || hipSetDevice(dev) == hipSuccess;
-    if (prev == dev) prev = -1;  // nothing to restore
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-struct gpso_ctx {
-  int device = 0;
-  int dtype = GPSO_F64;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[8] = {};  // [0..1] spare, [2..3] a point call (points_begin / points_end) or a best-UCB call (finish_best), [4..5] fit, [6..7] the collective of a sharded call
-  std::vector<hipEvent_t> tile_ev;  // start/stop pairs around the leaf-tile kernel, one per chunk (how many were recorded: TileSpan)
-  double last_ms[4] = {0, 0, 0, 0};
-  bool timing = true;  // GPSO_OPT_TIMING: does the call in flight record the event pairs gpso_last_ms reads (two to four HIP calls)?
-  int timing_every = 1;  // ... 0: never, 1: every fit / predict-type call, k: every k-th one (the others leave gpso_last_ms alone)
-  long timed_calls = 0;
-  void tick_timing() { timing = timing_every > 0 && (timed_calls++ % timing_every) == 0; }
-  // multi-GPU group (gpso_comm_init): one RCCL communicator per context, collectives on ctx->stream
-  ncclComm_t comm = nullptr;
-  // gpso_comm_abort (callable from another thread): the communicator is gone -- not to be destroyed again, and not to be
-  // handed to a collective again either (need_comm refuses until gpso_comm_destroy + gpso_comm_init)
-  std::atomic<bool> comm_aborted{false};
-  int rank = 0, world = 1;
-  // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit; [3] workgroups per
-  // leaf tile of this context's last split-kernel launch
-  int64_t last_count[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
-  int cu_count = 256;  // compute units of `device` (gpso_create): sizes the split predict kernels' and the bf16 GEMMs' grids
-  std::string err;
-  Engine* eng = nullptr;
-  hipEvent_t ev_wait = nullptr;  // completion marker of the call in flight
-  hipStream_t side_stream = nullptr;  // look-ahead of the two-level fits (kernels.hpp: FitPlanes)
-  hipEvent_t ev_col = nullptr, ev_chain = nullptr;
-  hipStream_t inv_stream = nullptr;   // the overlapped inverse of the two-level double fit
-  hipEvent_t ev_panel = nullptr, ev_inv = nullptr;
-  double* pinned = nullptr;      // pinned host scratch for the small result read-backs
-  size_t pinned_doubles = 0;
-  double* stage = nullptr;       // pinned staging of small host inputs (training data, bounds)
-  size_t stage_doubles = 0;
-  // gpso_best_ucb_begin / _end: two calls may be in flight; each has a pinned result slot of its own and a completion event
-  static constexpr int kSlots = 2;
-  static constexpr size_t kSlotDoubles = 4 * 1024 + 4;  // nseg <= 1024 per asynchronous call (+ the completion token)
-  gpso::BestTicket<hipEvent_t> tickets[kSlots];  // (best_call.hpp: the enqueue's record, the completion event, in use)
-  double* slot_host = nullptr;   // [kSlots][kSlotDoubles], pinned
-  int next_ticket = 0;           // tickets are handed out in turn (the other one where that one is still open)
-  int slots_busy() const { return (int)tickets[0].in_use + (int)tickets[1].in_use; }
-
-  // A blocking wait parks the thread on an interrupt and costs tens of microseconds to wake up -- the device work of a small fit.
-  // The calling thread is blocked in this library anyway: poll done() (hipErrorNotReady: go on) for up to kSpinMs, then block().
-  template <int kPollMask, typename Done, typename Block>
-  static hipError_t spin_then_block(Done&& done, Block&& block) {
-    constexpr double kSpinMs = 20.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int it = 0;; ++it) {
-      const hipError_t e = done();
-      if (e != hipErrorNotReady) return e;
-      if ((it & kPollMask) == kPollMask &&
-          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > kSpinMs)
-        return block();
-    }
-  }
-  // wait for everything queued on s
-  hipError_t wait(hipStream_t s) {
-    const hipError_t e = hipEventRecord(ev_wait, s);
-    if (e != hipSuccess) return e;
-    return spin_then_block<63>([&] { return hipEventQuery(ev_wait); }, [&] { return hipStreamSynchronize(s); });
-  }
-  hipError_t wait_event(hipEvent_t ev) { return spin_then_block<63>([&] { return hipEventQuery(ev); }, [&] { return hipEventSynchronize(ev); }); }
-  double* pinned_scratch(size_t doubles) {
-    if (doubles > pinned_doubles) {
-      if (pinned) (void)hipHostFree(pinned);
-      pinned = nullptr;
-      pinned_doubles = 0;
-      const size_t want = std::max<size_t>(doubles, 256);
-      // (fine-grained -- hipHostMallocCoherent --: kernels write their records and the completion token here WHILE they run,
-      // and the host reads them behind a system-scope release; coarse-grained host memory is only coherent at kernel boundaries)
-      if (hipHostMalloc(reinterpret_cast<void**>(&pinned), want * 8, hipHostMallocCoherent) != hipSuccess) return nullptr;
-      std::memset(pinned, 0, want * 8);  // (no stale completion token)
-      pinned_doubles = want;
-    }
-    return pinned;
-  }
-  // Completion tokens (round 5): where the last kernel of a call is a single workgroup it writes a sequence number behind
-  // its records in pinned host memory and the host spins on THAT word -- no event to record, no driver call per poll.  A
-  // token that does not arrive within kSpinMs falls back to a blocking wait (where a failed launch surfaces as before).
-  // (process-wide: a pinned buffer handed on by a destroyed context -- ContextPool -- never holds a number a later call waits for)
-  static std::atomic<uint64_t>& seq_counter() {
-    static std::atomic<uint64_t> c{0};
-    return c;
-  }
-  double next_token() { return (double)(seq_counter().fetch_add(1) + 1); }  // (exact in a double for 2^53 calls)
-  hipError_t wait_token(const double* word, double token, hipStream_t s) {
-    const volatile double* w = word;
-    auto arrived = [&] { return *w == token ? (std::atomic_thread_fence(std::memory_order_acquire), hipSuccess) : hipErrorNotReady; };
-    return spin_then_block<1023>(arrived, [&] { return hipStreamSynchronize(s); });
-  }
-
-  // staging buffer for host -> device copies that must not force a stream synchronisation.  It is
-  // reused by the next call, so wait for the copies of the previous one first (they are long done in
-  // practice: every entry point ends with a wait on the stream).
-  double* pinned_stage(size_t doubles) {
-    if (stream) (void)hipStreamSynchronize(stream);
-    if (doubles > stage_doubles) {
-      if (stage) (void)hipHostFree(stage);
-      stage = nullptr;
-      stage_doubles = 0;
-      const size_t want = std::max<size_t>(doubles, 4096);
-      if (hipHostMalloc(reinterpret_cast<void**>(&stage), want * 8, hipHostMallocDefault) != hipSuccess) return nullptr;
-      stage_doubles = want;
-    }
-    return stage;
-  }
-
-  int fail(int code, const char* fmt, ...) {
-    char buf[768];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    err = buf;
-    return code;
-  }
-};
-
-// Host-side resources of a context -- its stream, its events, its pinned buffers -- cost ~2 ms to create and ~1 ms to
-// destroy (tools/context_cost.py), a sixth of a whole 50-evaluation GPSO run whose surrogate lives for 32 ms.  gpso_destroy
-// hands them to a small per-device pool and gpso_create takes them from there (at most kKeep sets per device are kept; they
-// are released at process exit by the runtime).  Device memory is not pooled.
-struct ContextPool {
-  struct Set {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_wait = nullptr, ev[8] = {};
-    double *pinned = nullptr, *stage = nullptr;
-    size_t pinned_doubles = 0, stage_doubles = 0;
-  };
-  static constexpr int kKeep = 4, kDevices = 64;
-  std::mutex mu;
-  std::vector<Set> free_sets[kDevices];
-  static ContextPool& get() {
-    static ContextPool* p = new ContextPool();  // (never destroyed: no HIP calls from a static destructor)
-    return *p;
-  }
-  bool take(int device, Set& out) {
-    if (device < 0 || device >= kDevices) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    if (free_sets[device].empty()) return false;
-    out = free_sets[device].back();
-    free_sets[device].pop_back();
-    return true;
-  }
-  bool give(int device, const Set& s) {
-    if (device < 0 || device >= kDevices) return false;
-    std::lock_guard<std::mutex> lock(mu);
-    if ((int)free_sets[device].size() >= kKeep) return false;
-    free_sets[device].push_back(s);
-    return true;
-  }
-};
-
-#define HIPCHECK(call)                                                                     \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return ctx->fail(e_ == hipErrorOutOfMemory ? GPSO_E_OOM : GPSO_E_HIP, "%s failed: %s", \
-                       #call, hipGetErrorString(e_));                                      \
-  } while (0)
-
-#define RCCLCHECK(call)                                                                              \
-  do {                                                                                               \
-    ncclResult_t r_ = (call);                                                                        \
-    if (r_ != ncclSuccess)                                                                           \
-      return ctx->fail(GPSO_E_RCCL, "%s failed: %s", #call, RcclApi::get().GetErrorString(r_));      \
-  } while (0)
-
+namespace gpso::host {
 namespace {
 
 // TF: fit type (Gram, Cholesky, L^-1, alpha);  TP: predict / apply type.
@@ -400,62 +78,15 @@ namespace {
 //   GPSO_F32   -> EngineT<float, float>
 //   GPSO_MIXED -> EngineT<double, float>
 template <typename TF, typename TP>
-struct EngineT : Engine {
-  gpso_ctx* ctx;
-  explicit EngineT(gpso_ctx* c) : ctx(c) {
+struct EngineT : EngineCore {
+  explicit EngineT(gpso_ctx* c) : EngineCore(c, sizeof(TF), sizeof(TP) == 4) {
     check = sizeof(TP) == 4;  // float predict arithmetic: self-test on by default
     // default tolerances: a double factor with a float apply measures 1e-6 .. 3e-5 (bf16x3) -> 1e-4; an
     // all-float engine is a 1e-4-class instrument already at noise 1e-3 -> 1e-3
     tol_var = tol_mean = (sizeof(TF) == 4) ? 1.0e-3 : 1.0e-4;
   }
   static constexpr bool kFloatPredict = sizeof(TP) == 4;
-
-  // problem
-  int64_t n = 0, npad = 0;
-  int d = 0, dp = 0;
-  // which of the buffers below mean something (resident.hpp: the record and its transitions, its only writers)
-  gpso::Resident res{kFloatPredict ? GPSO_MATH_F16X3 : GPSO_MATH_NATIVE};
-  using Post = gpso::Post;
-  using Copy = gpso::Copy;
-  KernParams kp{0, 1.0, 1e-3, 0.0};
-  int n_ls = 1;
-  std::vector<double> ls_host;
-
-  // device buffers.  Fit side: xs64 / xnorm64 (scaled inputs, always double), K, Lf, linv, work, kinvb,
-  // white, alpha_f in TF.  Predict side: linv_p, alpha in TP; xs_p64 (+ xnorm64) or xs_p32 / xnorm32
-  // in the generation type.
-  DevBuf xs_h16, c16_scal;  // fp16 piece pairs of xs32 in the fp16 contraction's fragment order, and their scale (4 floats)
-  DevBuf x64, y64, hyper, xs64, xnorm64, xs_p64, xs32, xnorm32, xs_p32, K, Lf, linv, work, kinvb, linv_p,
-      white, alpha_f, alpha, logdet, scal, gpart, apart, kinv_diag, getter_tmp;
-  // split-bf16 copy of L^-1 (float predict with GPSO_OPT_PREDICT_MATH != native)
-  DevBuf linv_b;
-  DevBuf pl_L, pl_X, pl_XT, pl_WT;  // bf16 plane sets of the two-level float fit (kernels.hpp: FitPlanes)
-  DevBuf app;                       // scratch of gpso_append (kernels.hpp: append_scratch_doubles)
-  std::vector<double> x_host, y_host;  // host mirror of the training data (gpso_append's refit path needs all of it)
-  // per-point observation noise (gpso_set_noise_diag): K_y = k(X, X) + diag(noise + s_i), s fixed.  sdiag [npad] on the
-  // device (zero padding), read wherever a fit adds `noise` to a diagonal; s_dev() is NULL while none is set, and every
-  // such site then runs what it ran before the vector existed
-  DevBuf sdiag;
-  std::vector<double> s_host;  // [n] host mirror (the refit paths of gpso_append, GPSO_VEC_NOISE_DIAG)
-  double s_max = 0.0;          // max s_i: fit_plane_scales' bounds
-  const double* s_dev() const { return res.have_s ? static_cast<const double*>(sdiag.p) : nullptr; }
-  bool has_noise_diag() const override { return res.have_s; }
-  int fit_overlap = 2;              // GPSO_OPT_FIT_OVERLAP (bit 0 look-ahead, bit 1 overlapped inverse: the default): two-level double fits overlap chains, updates and the inverse (0: sequential, round 5)
-  int fit_planes_mode = 2;          // GPSO_OPT_FIT_BF16_SYRK: 0 f32 MFMA | 1 bf16 pieces (6 MFMAs per product) | 2 fp16 pieces (3) where representable
-  // predict math, the OPTION (what the posterior uses: res.math).  GPSO_MATH_AUTO walks the ladder fp16 split (3 MFMAs per
-  // product) -> bf16x6 -> f32 MFMA kernel, one rung down each time the posterior's self-test fails on it (selftest_with_fallback)
   static constexpr int kAutoFirst = kFloatPredict ? GPSO_MATH_F16X3 : GPSO_MATH_NATIVE;
-  bool math_auto = kFloatPredict;
-  // generation of the cross-Gram tile in float-predict contexts, the OPTION (what the posterior uses: res.gen_eff32).  AUTO:
-  // a posterior whose float form misses the tolerances moves to double generation and is tested again (decide_generation)
-  int gen_mode = GPSO_GEN_AUTO;
-  int split_variant = GPSO_SPLIT_KERNEL_AUTO;  // GPSO_OPT_SPLIT_KERNEL
-  int row_loop = 1;  // GPSO_OPT_ROW_LOOP (leaf_split.hpp: leaf_row_splits)
-  // GPSO_OPT_PARK_BYTES (leaf_split.hpp, PARK): the budget of the parked cross-Gram pieces of the default split predict kernel,
-  // and the buffer that holds them -- allocated by the first launch that parks, reused by every later call and chunk
-  int64_t park_bytes = kParkBytesDefault;
-  DevBuf park_buf;
-  size_t park_refused = 0;  // the smallest size an allocation of park_buf failed at: not asked for again (a new budget clears it)
   static void* park_cb(void* owner, size_t bytes) {
     auto* self = static_cast<EngineT*>(owner);
     if (self->park_buf.bytes >= bytes) return self->park_buf.p;
@@ -467,96 +98,11 @@ struct EngineT : Engine {
     }
     return self->park_buf.p;
   }
-  int contraction = GPSO_CONTRACTION_AUTO;     // GPSO_OPT_CONTRACTION
-  // the x.x* contraction of the fp16-split kernel runs on the fp16 pipe under float generation (D_pad + 1 slots in at most
-  // two chunks of 32: every D this library accepts).  Measured in one process on one posterior (tools/c16_check.py,
-  // profiles/r04_c16_check.jsonl), fp16 pipe against the f32 instruction: D = 6 +4 %, 12 +8 %, 20 +17 %, 33 +28 %, 40 +30 %
-  bool c16_in_use(bool gen64) const {
-    if (!kFloatPredict || gen64 || res.c16_fallback || !f16_split() || contraction == GPSO_CONTRACTION_F32 || leaf_c16_chunks(dp / 4) > 2) return false;
-    return leaf_bf16_lds_bytes(2, dp / 4, 4, true) <= 160 * 1024;
-  }
-  bool small_calls = true, one_launch = true, one_launch_everywhere = false;  // GPSO_OPT_SMALL_CALLS
-  bool fuse_prep = true;  // GPSO_OPT_FUSED_PREP: float leaves are scaled in the fp16-contraction kernel's prologue (same bits)
-  int64_t single_level_max = -1;  // < 0: library default
-  bool fused_small = true;        // GPSO_OPT_FIT_FUSED_SMALL
-  std::vector<int64_t> segoff_cache;  // what the device copy of seg_off currently holds
   // A best-UCB call in flight (best_call.hpp): the entry point's plan goes down, the enqueue's record comes back.
   using BestPlan = gpso::BestPlan; using BestCall = gpso::BestCall; using BestKind = gpso::BestKind;
   // the pinned memory the call's last kernel -- about to be launched -- writes nseg records to, and the token behind them
   double* result_host(const BestPlan& plan, BestCall& call, int nseg) { return call.writes_host(plan.slot ? plan.slot : ctx->pinned_scratch((size_t)nseg * 4 + 3)); }
   double arm_token(BestCall& call, bool single_workgroup, int nseg) { return call.arm_token(single_workgroup, nseg, ctx->next_token()); }
-  DevBuf extra_cnt;                  // small growth calls: rows appended behind the analytic slots (zero between calls)
-  // predict workspace
-  DevBuf leaves_raw, leaves_s, lnorm, pvar, pmean, omean, ovar, oucb, segoff, best, oidx, ovals, grow_key,
-      live_cnt, best_pos, gath, wbase, ovals2, bhdr;
-  DevBuf acq_maxima, mcdf_work, mcdf_in;  // GPSO_ACQ_MES's maxima; gpso_max_logcdf's partials and staged columns
-  // screened best-UCB calls (screen.hip): every leaf's mean, the blocks' maxima, the compaction's counts per part, the
-  // survivors' raw rows, the control words (live rows, count, T'), the probe's columns.  The survivors' indices travel in grow_key.
-  DevBuf screen_my, screen_bmax, screen_cnt, screen_rows, screen_ctl, screen_cols;
-  // the compact list the last gpso_screen_probe left, copied out behind it (gpso_screen_list): indices, raw rows [live][d]
-  std::vector<int64_t> probe_key;
-  std::vector<float> probe_rows;
-  bool probe_listed = false;
-  int screen_mode = GPSO_SCREEN_DEFAULT;  // GPSO_OPT_SCREEN
-  DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
-  DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
-  DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
-  // gpso_predict_joint / gpso_sample_joint: scaled test points, V (+ partial |v|^2), partial tiles, mean, Sigma; then the
-  // Cholesky's buffers (factor, inverse, scratch, diagonal, info), the normals, the draws and their winners
-  DevBuf pj_ts, pj_norm, pj_v, pj_part, pj_mu, pj_sigma, pj_l, pj_linv, pj_cwork, pj_diag, pj_info, pj_z, pj_f, pj_best;
-  // gpso_paths_draw / gpso_paths_eval (paths.hip): the resident path set -- frequencies, phases, weights and v^T, padded as
-  // the kernels read them; res.paths_valid says whether it means something -- and the set a draw in progress builds, swapped
-  // in when it succeeds (a failed draw leaves the resident one as it was).  Then the draw's scratch (eps, Phi(X) w^T, R, U)
-  // and the evaluation's: scaled points and values of one chunk, segment offsets, running winners
-  struct PathSet {
-    DevBuf omega, phase, w, vt;
-    int64_t s = 0, f = 0, ldw = 0;
-  };
-  PathSet pth, pth_next;
-  DevBuf pth_eps, pth_p, pth_r, pth_u, pth_x /* gpso_paths_draw_q: Lu^-1 Phi(Zr) w^T */, pe_ts, pe_norm, pe_vals, pe_seg, pe_best;
-  // gpso_cross_cov / gpso_best_batch (batch.hip): scaled points of a chunk and their norms, the points b (raw, scaled, norms),
-  // K_b | U | W and the latent variances, host-bound results; then the batch call's own: every scaled leaf and its norm, mean,
-  // s2, the value column, G, the live flags, the blocks' maxima, the state words and the pick's scaled row
-  DevBuf cc_ts, cc_norm, cc_braw, cc_tb, cc_bnorm, cc_vec, cc_lv, cc_out;
-  DevBuf bb_ts, bb_norm, bb_mean, bb_s2, bb_val, bb_g, bb_live, bb_bmax, bb_state, bb_tp;
-  // precision self-test
-  bool check = false;
-  bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
-  double tol_var = 1.0e-4, tol_mean = 1.0e-4;
-  double st_vals[6] = {0, 0, 0, 0, 0, 0};
-  DevBuf st_mean, st_var, st_out;
-
-  int64_t padded_n() const override { return npad; }
-  void problem_shape(int64_t* n_out, int* d_out) const override {
-    *n_out = n;
-    *d_out = d;
-  }
-
-  // generation type actually used by the resident posterior
-  bool gen_double() const { return !kFloatPredict || !res.gen_eff32; }
-  // the split-bf16 kernel keeps its leaf fragments in LDS: with double generation they do not fit the
-  // 160 KB for D > 24 (bf16x6) / D > 36 (bf16x3) -- those calls run the native f32 kernel instead (accuracy
-  // decides the generation type, the kernel follows)
-  bool bf16_fits(bool gen64) const {
-    return c16_in_use(gen64) || leaf_bf16_lds_bytes(nsplit(), dp / 4, gen64 ? 8 : 4) <= 160 * 1024;
-  }
-  int nsplit() const { return res.math == GPSO_MATH_BF16X6 ? 3 : 2; }
-  bool f16_split() const { return res.math == GPSO_MATH_F16X3; }
-  // bytes of the split copy of L^-1: the planes and, behind them, one 256-byte slot for the power-of-two scale of the
-  // fp16 split (2 floats, written on the device at packing time) -- it travels with the planes in a hand-off.  Under
-  // GPSO_MATH_AUTO room for three planes whatever the stage, so that both sides of a hand-off list the same sizes.
-  // Round 4: the 256-byte scale slot sits IN FRONT of the planes, so that the part of the buffer a posterior uses
-  // (slot + nsplit planes) is a prefix of it -- the posterior arena sends exactly that (posterior_span).
-  size_t split_planes_alloc() const { return (size_t)(math_auto ? 3 : nsplit()) * npad * npad * 2; }
-  size_t split_bytes() const { return split_planes_alloc() + 256; }
-  size_t split_bytes_in_use() const { return (size_t)nsplit() * npad * npad * 2 + 256; }
-  float* f16_scale() const { return reinterpret_cast<float*>(linv_b.p); }
-  void* split_planes() const { return static_cast<char*>(linv_b.p) + 256; }
-  // max |L^-1| of the fp16 split comes out of the fit's own pass over L^-1 (white_kernel leaves row maxima,
-  // alpha_sum_kernel folds them into the scale slot): no extra pass, no memset.  f16_handed_at: where this fit's solve
-  // was told to leave it (cleared by every packing and at the start of every fit).
-  DevBuf amax_rows;
-  const void* f16_handed_at = nullptr;
   // -> where the fit's pass leaves the maximum, nullptr when the fp16 split does not apply to this posterior
   float* f16_max_for_fit() {
     f16_handed_at = nullptr;
@@ -566,7 +112,6 @@ struct EngineT : Engine {
     f16_handed_at = f16_scale();
     return f16_scale();
   }
-  bool bf16_usable() const { return res.split_usable(kFloatPredict, npad); }
 
   // An evaluation WITH gradient is a step of the hyper-parameter search: the next call is another evaluation, not a
   // prediction, and its 16-bit pieces of L^-1 (10 us at C3, 0.5 ms at C5) would be packed for nothing.  They are packed
@@ -594,6 +139,12 @@ struct EngineT : Engine {
     HIPCHECK(hipGetLastError());
     res.split_packed(true);
     return GPSO_OK;
+  }
+  // the typed step of EngineCore::install_predictive: the predict-ready copies of what the install left in linv and alpha_f
+  int pack_predictive(hipStream_t s) override {
+    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
+    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
+    return pack_bf16();
   }
 
   int set_option(int option, int value) override {
@@ -695,329 +246,6 @@ struct EngineT : Engine {
       int rc = pack_bf16();
       if (rc) return rc;
     }
-    return GPSO_OK;
-  }
-
-  int set_option_f64(int option, double value) override {
-    if (!(value > 0.0)) return ctx->fail(GPSO_E_ARG, "tolerance %g must be positive", value);
-    if (option == GPSO_OPTF_TOL_VAR) tol_var = value;
-    else if (option == GPSO_OPTF_TOL_MEAN) tol_mean = value;
-    else return ctx->fail(GPSO_E_ARG, "unknown floating-point option %d", option);
-    return GPSO_OK;
-  }
-
-  hipStream_t st() const { return ctx->stream; }
-  // calls that replace or change the posterior are refused while an asynchronous best-UCB call is open: its kernels
-  // may still be reading what the call would overwrite
-  int refuse_if_async(const char* what) {
-    if (ctx->slots_busy() == 0) return GPSO_OK;
-    return ctx->fail(GPSO_E_STATE, "%s while %d asynchronous best-UCB call(s) are open: gpso_best_ucb_end them first", what, ctx->slots_busy());
-  }
-  double* ls_dev() const { return static_cast<double*>(hyper.p) + kHyperHeader; }
-  template <typename U>
-  U* as(const DevBuf& b) const { return static_cast<U*>(b.p); }
-
-  // room for at least `bytes` in b (devbuf.hpp: grow-only; the stream is synchronised before an old block is freed)
-  int ensure(DevBuf& b, size_t bytes, bool keep = false) {
-    const size_t had = b.bytes;
-    const BufStatus r = b.ensure(bytes, st(), keep);
-    if (!r) return GPSO_OK;
-    if (r.step == BufStep::View)
-      return ctx->fail(GPSO_E_STATE, "internal: a slice of the posterior arena (%zu bytes) was asked to hold %zu", had, bytes);
-    // (indexed by BufStep, in the words these steps have always failed with)
-    static const char* const call[] = {"", "", "hipMalloc(&b.p, bytes)", "hipMemcpyAsync(np_, b.p, b.bytes, hipMemcpyDeviceToDevice, st())",
-                                       "hipStreamSynchronize(st())", "hipFree(b.p)"};
-    const hipError_t e = (hipError_t)r.err;
-    return ctx->fail(e == hipErrorOutOfMemory ? GPSO_E_OOM : GPSO_E_HIP, "%s failed: %s", call[(int)r.step], hipGetErrorString(e));
-  }
-  // like ensure(), but the old contents survive a re-allocation
-  int ensure_keep(DevBuf& b, size_t bytes) { return ensure(b, bytes, true); }
-
-  // launcher-side errors (hipFuncSetAttribute, unsupported GEMM shapes) + the HIP launch status
-  int launch_status() {
-    HIPCHECK(hipGetLastError());
-    if (!gpso::g_launch_error.empty()) {
-      const std::string msg = gpso::g_launch_error;
-      gpso::g_launch_error.clear();
-      return ctx->fail(GPSO_E_HIP, "%s", msg.c_str());
-    }
-    return GPSO_OK;
-  }
-
-  int shape(int64_t n_, int d_) {
-    if (n_ < 1) return ctx->fail(GPSO_E_ARG, "need at least one training point (n=%lld)", (long long)n_);
-    if (d_ < 1 || d_ > kMaxD) return ctx->fail(GPSO_E_ARG, "input dimension %d outside [1, %d]", d_, kMaxD);
-    if (n_ > 65536) return ctx->fail(GPSO_E_ARG, "n=%lld above the supported 65536", (long long)n_);
-    n = n_;
-    d = d_;
-    // Float-predict contexts pad N > 128 to a multiple of 256, the row block of the split predict kernels: with a pad of
-    // 128 every N in (256 k + 128, 256 k + 256] ran them and every N in (256 k, 256 k + 128] fell to the f32 MFMA kernel
-    // (3.2x the time per flop) -- half of all N.  The padding rows are identity rows of the factor: the blocked
-    // factorisation does the same operations on the real rows, up to two 64-column steps more on the padding.
-    const int64_t pad = (kFloatPredict && n > kPadN) ? 2 * kPadN : kPadN;
-    npad = (n + pad - 1) / pad * pad;
-    dp = (d + 3) / 4 * 4;
-    int rc;
-    // (room for the padded size: gpso_append adds rows in place)
-    if ((rc = ensure(x64, (size_t)npad * d * 8))) return rc;
-    if ((rc = ensure(y64, (size_t)npad * 8))) return rc;
-    if ((rc = carve_posterior())) return rc;
-    if (kFloatPredict) {
-      if ((rc = ensure(xs32, (size_t)npad * dp * 4))) return rc;
-      if ((rc = ensure(xnorm32, (size_t)npad * 4))) return rc;
-      if ((rc = ensure(xs_p32, (size_t)npad * dp * 4))) return rc;
-      if ((rc = ensure(xs_h16, (size_t)(npad / 16) * leaf_c16_chunks(dp / 4) * 2048))) return rc;
-      if ((rc = ensure(c16_scal, 16))) return rc;
-    }
-    return GPSO_OK;
-  }
-
-  // ---- the posterior arena (round 4) ----------------------------------------------------------------------------
-  // Everything a peer needs to predict lives in ONE allocation, laid out as
-  //     [ packed L^-1 | hyper block | X / l | its MFMA fragments | norms | alpha | split pieces of L^-1 (scale slot, planes) ]
-  // (each slice 256-byte aligned), so that what a posterior actually uses is one contiguous range whichever predict
-  // math it runs -- native: [packed L^-1 .. alpha], split: [hyper .. the planes in use] -- and gpso_broadcast_posterior
-  // moves it with ONE ncclBroadcast.  The layout is a function of (N_pad, D_pad, predict type) only: every rank of a
-  // group carves the same offsets.  The slices are DevBuf views of the arena.
-  DevBuf arena;
-  int64_t arena_npad = -1;
-  int arena_dp = -1;
-  static size_t up256(size_t b) { return (b + 255) / 256 * 256; }
-  bool split_slot_exists() const { return kFloatPredict && npad % 256 == 0; }
-  int carve_posterior() {
-    if (arena.p != nullptr && arena_npad == npad && arena_dp == dp) return GPSO_OK;
-    const size_t b_linv = up256(packed_linv_elems(npad) * sizeof(TP));
-    const size_t b_hyper = up256((size_t)(kHyperHeader + kMaxD) * 8);
-    const size_t b_xs = up256((size_t)npad * dp * 8);
-    const size_t b_norm = up256((size_t)npad * 8);
-    const size_t b_alpha = up256((size_t)npad * sizeof(TP));
-    // room for three planes whatever the option: GPSO_OPT_PREDICT_MATH may change after the shape is known
-    const size_t b_split = split_slot_exists() ? up256((size_t)3 * npad * npad * 2 + 256) : 0;
-    const size_t total = b_linv + b_hyper + 2 * b_xs + b_norm + b_alpha + b_split;
-    if (arena.bytes < total) {  // (the old slices go first: whatever becomes of the arena, none of them points into a freed block)
-      arena_npad = -1;
-      for (DevBuf* b : {&linv_p, &hyper, &xs64, &xs_p64, &xnorm64, &alpha, &linv_b}) b->drop();
-      int rc = ensure(arena, total);
-      if (rc) return rc;
-    }
-    size_t off = 0;
-    auto slice = [&](DevBuf& b, size_t bytes) {
-      b.slice(arena, off, bytes);
-      off += bytes;
-    };
-    slice(linv_p, b_linv);
-    slice(hyper, b_hyper);
-    slice(xs64, b_xs);
-    slice(xs_p64, b_xs);
-    slice(xnorm64, b_norm);
-    slice(alpha, b_alpha);
-    slice(linv_b, b_split);
-    arena_npad = npad;
-    arena_dp = dp;
-    res.recarved();
-    return GPSO_OK;
-  }
-  // the contiguous range of the arena the resident posterior uses: offset into the arena and length
-  void posterior_range(size_t* off, size_t* bytes) const {
-    const char* base = static_cast<const char*>(arena.p);
-    if (math_in_use() != GPSO_MATH_NATIVE) {
-      *off = (size_t)(static_cast<const char*>(hyper.p) - base);
-      *bytes = (size_t)(static_cast<const char*>(linv_b.p) - static_cast<const char*>(hyper.p)) + split_bytes_in_use();
-    } else {
-      *off = 0;
-      *bytes = (size_t)(static_cast<const char*>(alpha.p) - base) + alpha.bytes;
-    }
-  }
-
-  // ---- what the peers of a group hold of THIS posterior (round 6: gpso_broadcast_posterior_rows) --------------------------------
-  // A hand-off (gpso_broadcast_posterior, or a span copy followed by gpso_posterior_mark_synced / gpso_adopt_posterior)
-  // records the rows the other side then holds; gpso_append extends the posterior in place and leaves the record alone, so
-  // the NEXT hand-off may move only what the appends wrote -- the new rows of the scaled inputs and of each predict-ready
-  // copy of L^-1, alpha, the hyper block -- instead of the whole range (C5: ~1.1 MB instead of 1.07 GB for 7 points).
-  // Anything that makes another posterior clears it (res.sync_n: posterior_dropped), an append that crosses a power of two of the
-  // fp16 scale repacks all rows (res.sync_scale).
-  // the scale slot's [1] (2^-sa) of the fp16 split as the device holds it now; 0 where it does not apply
-  int current_split_scale(float* out) {
-    *out = 0.0f;
-    if (!(kFloatPredict && f16_split() && bf16_usable() && res.linv_b == Copy::Valid)) return GPSO_OK;
-    float* h = reinterpret_cast<float*>(ctx->pinned_scratch(256) + 124);  // (a slot of the scratch nothing else reads)
-    HIPCHECK(hipMemcpyAsync(h, f16_scale() + 1, 4, hipMemcpyDeviceToHost, st()));
-    HIPCHECK(hipStreamSynchronize(st()));
-    *out = *h;
-    return GPSO_OK;
-  }
-  // ranges of the arena (offset, bytes) that differ between the posterior of the first n0 rows and this one of n rows at the
-  // same hyper-parameters, predict math and fp16 scale -- the same list on every rank (a function of n0, n, the layout)
-  void rows_ranges(int64_t n0, std::vector<std::pair<int64_t, int64_t>>& out) const {
-    out.clear();
-    const char* base = static_cast<const char*>(arena.p);
-    auto rel = [&](const DevBuf& b, size_t off, size_t bytes) {
-      if (bytes) out.push_back({(int64_t)(static_cast<const char*>(b.p) - base + off), (int64_t)bytes});
-    };
-    const int64_t rt0 = n0 / 16, rt1 = (n - 1) / 16, npad16 = npad / 16;
-    rel(hyper, 0, (size_t)(kHyperHeader + kMaxD) * 8);
-    rel(xs64, (size_t)n0 * dp * 8, (size_t)(n - n0) * dp * 8);
-    rel(xs_p64, (size_t)rt0 * dp * 16 * 8, (size_t)(rt1 + 1 - rt0) * dp * 16 * 8);  // MFMA fragments: 16-row groups
-    rel(xnorm64, (size_t)n0 * 8, (size_t)(n - n0) * 8);
-    rel(alpha, 0, (size_t)npad * sizeof(TP));  // alpha_1 += R^T a_2: every entry moved
-    if (math_in_use() != GPSO_MATH_NATIVE) {
-      rel(linv_b, 0, 256);  // the scale slot
-      for (int s_ = 0; s_ < nsplit(); ++s_)  // plane s: tile row rt at ((s npad16 + rt) npad 32) bytes behind the slot
-        rel(linv_b, 256 + ((size_t)s_ * npad16 + rt0) * npad * 32, (size_t)(rt1 + 1 - rt0) * npad * 32);
-    } else {
-      const size_t t0 = (size_t)rt0 * (rt0 + 1) / 2, t1 = (size_t)(rt1 + 1) * (rt1 + 2) / 2;  // tiles row-major over the triangle
-      rel(linv_p, t0 * 256 * sizeof(TP), (t1 - t0) * 256 * sizeof(TP));
-    }
-  }
-  // can the peers be brought up to date by rows?  (root side; scale = current_split_scale)
-  bool rows_apply(float scale) const {
-    return res.has_post() && res.sync_n >= 0 && res.sync_n <= n && res.sync_math == math_in_use() && scale == res.sync_scale &&
-           (res.sync_n == n || res.sync_n / 16 <= (n - 1) / 16);
-  }
-
-  int ensure_fit_buffers() {
-    int rc;
-    const size_t s = sizeof(TF);
-    if ((rc = ensure(K, (size_t)npad * npad * s))) return rc;
-    if ((rc = ensure(Lf, (size_t)npad * npad * s))) return rc;
-    if ((rc = ensure(linv, (size_t)npad * npad * s))) return rc;
-    if ((rc = ensure(work, (size_t)npad * npad * s))) return rc;
-    if ((rc = ensure(white, (size_t)npad * s))) return rc;
-    if ((rc = ensure(alpha_f, (size_t)npad * s))) return rc;
-    if ((rc = ensure(logdet, (size_t)npad * 8))) return rc;
-    if ((rc = ensure(kinv_diag, (size_t)npad * 8))) return rc;
-    if ((rc = ensure(apart, alpha_part_doubles(npad) * 8))) return rc;
-    if ((rc = ensure(scal, (size_t)(8 + kGradMaxLs + 3) * 8))) return rc;
-    const size_t nt = (size_t)(npad / 64);
-    if ((rc = ensure(gpart, nt * nt * (size_t)(kGradMaxLs + 2) * 8))) return rc;
-    return GPSO_OK;
-  }
-
-  // GPSO_OK, or the message of what theta_refusal / theta_shape_refusal (theta.hpp) found.  what_lik: the likelihood
-  // parameter's name at this entry point
-  int theta_status(const ThetaRefusal& r, const char* what_lik = "noise variance") {
-    switch (r.rule) {
-      case ThetaRule::None: return GPSO_OK;
-      case ThetaRule::Lik: return ctx->fail(GPSO_E_ARG, "%s %g must be positive", what_lik, r.value);
-      case ThetaRule::Kernel: return ctx->fail(GPSO_E_ARG, "unknown kernel id %d", r.index);
-      case ThetaRule::Nls: return ctx->fail(GPSO_E_ARG, "n_ls=%d must be 1 or D=%d", r.index, d);
-      case ThetaRule::Lengthscale: return ctx->fail(GPSO_E_ARG, "lengthscale[%d]=%g must be positive", r.index, r.value);
-      case ThetaRule::Variance: return ctx->fail(GPSO_E_ARG, "kernel variance %g must be positive", r.value);
-    }
-    return GPSO_OK;
-  }
-  // the resident theta, as a fit at the same hyper-parameters takes it (gpso_append's refit)
-  Theta resident_theta() const {
-    Theta th;
-    theta_from_parts(kp.kernel, ls_host.data(), n_ls, kp.variance, kp.noise, kp.mean_c, &th);
-    return th;
-  }
-
-  // the lengthscale of every padded input dimension, as the hyper block and the one-launch kernels take them: an isotropic
-  // one repeated, the last of n_ls behind them
-  static void expand_ls(const double* ls, int n_ls, double* row) {
-    for (int k = 0; k < kMaxD; ++k) row[k] = ls[n_ls == 1 ? 0 : std::min(k, n_ls - 1)];
-  }
-  // th.lik: the noise variance of the hyper block.  upload = false: the caller's kernel writes the device copy of the block
-  // itself (fused small fit).  stage: a fit call's FitCall::theta_stage(); NULL: the scratch is asked for here
-  int set_theta(const Theta& th, bool upload = true, double* stage = nullptr) {
-    if (int rc = theta_status(theta_refusal(th, d, false))) return rc;
-    kp.kernel = th.kernel;
-    kp.variance = th.variance;
-    kp.noise = th.lik;
-    kp.mean_c = th.mean_c;
-    n_ls = th.n_ls;
-    ls_host.assign(th.ls, th.ls + n_ls);
-    if (!upload) return GPSO_OK;
-    // staged in pinned memory (FitScratch::kThetaAt; the read-backs lie below it): the copy is then a plain stream
-    // operation and needs no host synchronisation here
-    double* scratch = stage ? nullptr : ctx->pinned_scratch(FitScratch::doubles(false));
-    if (!stage && !scratch) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    double* h = stage ? stage : scratch + FitScratch::kThetaAt;
-    std::memset(h, 0, FitScratch::kThetaDoubles * 8);
-    h[0] = (double)n; h[1] = (double)d; h[2] = (double)th.kernel; h[3] = (double)n_ls;
-    h[4] = th.variance; h[5] = th.lik; h[6] = th.mean_c;
-    expand_ls(th.ls, n_ls, h + kHyperHeader);
-    HIPCHECK(hipMemcpyAsync(hyper.p, h, FitScratch::kThetaDoubles * 8, hipMemcpyHostToDevice, st()));
-    return GPSO_OK;
-  }
-
-  // X / lengthscale for the fit (double) and, packed as MFMA fragments, for the predict generation
-  int scale_inputs() {
-    launch_scale_x<double>(st(), as<double>(x64), n, npad, d, dp, ls_dev(), as<double>(xs64), as<double>(xnorm64),
-                           as<double>(xs_p64));
-    return GPSO_OK;
-  }
-  void reset_generation() {
-    f16_handed_at = nullptr;  // (a fit that failed between its solve and its packing leaves nothing behind)
-    res.reset_generation(kFloatPredict, math_auto, gen_mode);
-  }
-  // float copies of the scaled inputs, made when a float-generation predict first needs them, from the
-  // double ones (resident after a fit AND after a hand-off): two short launches, not two per loss evaluation
-  int ensure_generation_inputs() {
-    if (gen_double() || res.gen32_inputs_ok) return GPSO_OK;
-    launch_gen_inputs_f32(st(), as<double>(xs64), npad, dp, as<float>(xs32), as<float>(xnorm32), as<float>(xs_p32));
-    launch_gen_inputs_f16(st(), as<float>(xs32), as<float>(xnorm32), npad, dp, as<float>(c16_scal), xs_h16.p);
-    res.gen_inputs_made();
-    return GPSO_OK;
-  }
-
-  // ------------------------------------------------------------------------------------------
-  int set_data(const double* X, const double* y, int64_t n_, int d_) override { return put_rows(X, y, n_, d_, false); }
-  // keep_stash: the rows are the inducing points of the stashed training set (gpso_sgpr_set_inducing), not new data
-  int put_rows(const double* X, const double* y, int64_t n_, int d_, bool keep_stash) {
-    if (!X || !y) return ctx->fail(GPSO_E_ARG, "X / y must not be NULL");
-    int rc = refuse_if_async("gpso_set_data");
-    if (rc) return rc;
-    rc = shape(n_, d_);
-    if (rc) return rc;
-    // small problems (the optimiser loop: N <= a few hundred) are staged through pinned memory so that
-    // the call needs no stream synchronisation; large ones copy straight from the caller's pages
-    const size_t doubles = (size_t)n * d + (size_t)n;
-    double* stage = doubles <= (1u << 17) ? ctx->pinned_stage(doubles) : nullptr;
-    if (stage) {
-      std::memcpy(stage, X, (size_t)n * d * 8);
-      std::memcpy(stage + (size_t)n * d, y, (size_t)n * 8);
-      HIPCHECK(hipMemcpyAsync(x64.p, stage, (size_t)n * d * 8, hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipMemcpyAsync(y64.p, stage + (size_t)n * d, (size_t)n * 8, hipMemcpyHostToDevice, st()));
-    } else {
-      HIPCHECK(hipMemcpyAsync(x64.p, X, (size_t)n * d * 8, hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipMemcpyAsync(y64.p, y, (size_t)n * 8, hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipStreamSynchronize(st()));
-    }
-    if (X != x_host.data()) x_host.assign(X, X + (size_t)n * d);
-    if (y != y_host.data()) y_host.assign(y, y + (size_t)n);
-    s_host.clear();  // (every gpso_set_data clears the per-point noise: it belonged to the rows just replaced)
-    s_max = 0.0;
-    res.new_data(keep_stash);
-    return GPSO_OK;
-  }
-
-  // s[n_] >= 0 beside the resident data (NULL: none); the posterior is invalidated as by new data
-  int set_noise_diag(const double* sv, int64_t n_) override {
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_set_noise_diag before gpso_set_data");
-    int rc = refuse_if_async("gpso_set_noise_diag");
-    if (rc) return rc;
-    if (n_ != n) return ctx->fail(GPSO_E_ARG, "gpso_set_noise_diag: n=%lld does not match the resident data (N=%lld)", (long long)n_, (long long)n);
-    double top = 0.0;
-    if (sv != nullptr) {
-      for (int64_t i = 0; i < n; ++i) {
-        if (!(sv[i] >= 0.0) || !std::isfinite(sv[i]))
-          return ctx->fail(GPSO_E_ARG, "gpso_set_noise_diag: s[%lld]=%g must be finite and >= 0", (long long)i, sv[i]);
-        top = std::max(top, sv[i]);
-      }
-      if ((rc = ensure(sdiag, (size_t)npad * 8))) return rc;
-      double* stage = ctx->pinned_stage((size_t)npad);  // (waits for the stream)
-      if (!stage) return ctx->fail(GPSO_E_OOM, "pinned host staging");
-      std::memcpy(stage, sv, (size_t)n * 8);
-      std::memset(stage + n, 0, (size_t)(npad - n) * 8);
-      HIPCHECK(hipMemcpyAsync(sdiag.p, stage, (size_t)npad * 8, hipMemcpyHostToDevice, st()));
-      if (sv != s_host.data()) s_host.assign(sv, sv + (size_t)n);
-    } else {
-      s_host.clear();
-    }
-    s_max = top;
-    res.noise_changed(sv != nullptr);
     return GPSO_OK;
   }
 
@@ -1267,28 +495,7 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  // ---- batched evaluation (multi-start hyper-parameter search): fit.hip small_fit_batch_kernel -------------------------
-  // entries one launch may hold for the resident data: one workgroup per CU where the one-launch fit applies, else none
-  int fit_batch_max() override { return (res.have_data && fused_small && small_fit_eligible(n, dp)) ? kSmallBatchMax : 0; }
-
-  // everything a batched call is refused for, before anything is touched
-  int fit_eval_batch_check(int kernel, int b, int n_ls_) override {
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_fit_eval_u_batch before gpso_set_data");
-    int rc = refuse_if_async("gpso_fit_eval_u_batch");
-    if (rc) return rc;
-    if ((rc = theta_status(theta_shape_refusal(kernel, n_ls_, d)))) return rc;
-    if (b < 1) return ctx->fail(GPSO_E_ARG, "a batch needs at least one entry (b=%d)", b);
-    const int cap = fit_batch_max();
-    if (cap == 0) {
-      if (!fused_small) return ctx->fail(GPSO_E_ARG, "no batched evaluation: GPSO_OPT_FIT_FUSED_SMALL is off (gpso_fit_batch_max = 0)");
-      if (n > 128) return ctx->fail(GPSO_E_ARG, "no batched evaluation for N > 128 (N=%lld; gpso_fit_batch_max = 0)", (long long)n);
-      return ctx->fail(GPSO_E_ARG, "no batched evaluation for N > 64 with a padded D > 32 (N=%lld, D=%d; gpso_fit_batch_max = 0)",
-                       (long long)n, d);
-    }
-    if (b > cap) return ctx->fail(GPSO_E_ARG, "b=%d entries exceed the limit of %d per call (gpso_fit_batch_max)", b, cap);
-    return GPSO_OK;
-  }
-
+  // ---- batched evaluation (multi-start hyper-parameter search): fit.hip small_fit_batch_kernel; EngineCore checks the call ----
   // nv <= fit_batch_max() constrained hyper-parameter vectors th[nv][n_ls + 3] = (ls..., variance, noise, c), every one
   // acceptable to set_theta; loss[nv], grad[nv][n_ls + 3] (nullable), info[nv] (failing pivot or INT_MAX).  One launch;
   // no member that describes the resident posterior is touched.
@@ -1493,7 +700,6 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-
   int set_posterior(const double* X, const double* L, const double* alpha64, int64_t n_, int d_, const Theta& th) override {
     if (!X || !L || !alpha64) return ctx->fail(GPSO_E_ARG, "NULL argument");
     int rc = refuse_if_async("gpso_set_posterior");
@@ -1518,995 +724,11 @@ struct EngineT : Engine {
     launch_trtri<TF>(s, as<TF>(Lf), as<TF>(linv), as<TF>(work), npad, kFitBlock);
     HIPCHECK(hipMemsetAsync(alpha_f.p, 0, (size_t)npad * sizeof(TF), s));
     launch_convert_in<TF>(s, tmp + (size_t)n * n, as<TF>(alpha_f), 1, n, npad);
-    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
-    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    if ((rc = pack_bf16())) return rc;
+    if ((rc = pack_predictive(s))) return rc;
     HIPCHECK(hipStreamSynchronize(s));  // the caller's host buffers are free again on return
     if ((rc = launch_status())) return rc;
     res.installed();
     return GPSO_OK;
-  }
-
-  // ---- variational GP (GPflow 2 VGP, whitened, Gaussian likelihood) ----------------------------
-  // q(v) = N(mu, S S^T) lives here beside the training data: vq_mu [N_pad], vq_S [N_pad^2] (lower; identity on the padding).
-  // Every product is a whole-matrix float64 GEMM (launch_dgemm), every factorisation the fit's launch_potrf; the calls leave
-  // the fit's buffers (K, Lf, linv, work) holding VGP intermediates, so they invalidate any GPR posterior first.
-  DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;
-  int64_t vq_n = -1, vq_npad = -1;  // shape q was made for (another shape: q restarts at the prior)
-  static constexpr double kVgpJitter = 1.0e-6;  // GPflow's default_jitter, in the K of the ELBO and of the predictive
-  enum { kVgpR = 0, kVgpFvar = 1, kVgpSrow = 2, kVgpH = 3, kVgpH2 = 4, kVgpZero = 5, kVgpVecs = 6 };
-  double* vvec_at(int k) const { return as<double>(vvec) + (size_t)k * npad; }
-  // vsmall: [0, 6) the -ELBO sums, [8, 8 + kGradMaxLs + 3) the gradient (launch_gradient: n_ls + 3 doubles), then the four
-  // int verdicts of the factorisations (Gram, Lambda, Sigma, I - Sigma) in two doubles of their own
-  static constexpr int kVgpGradAt = 8, kVgpInfoAt = kVgpGradAt + kGradMaxLs + 3, kVgpSmall = kVgpInfoAt + 2;
-  static_assert(kVgpGradAt >= 6 && kVgpInfoAt >= kVgpGradAt + kGradMaxLs + 3, "vsmall layout: sums, gradient and verdicts overlap");
-  int* vinfo() const { return reinterpret_cast<int*>(as<double>(vsmall) + kVgpInfoAt); }
-  // a general scalar likelihood (vlik_kind != GPSO_LIK_GAUSSIAN): df, the Gauss-Hermite rule on the device (vgh: [0, 64)
-  // nodes x sqrt(2), [64, 128) weights / sqrt(pi)) and the per-point vectors of the quadrature (vlvec)
-  DevBuf vgh, vlvec;
-  double vlik_df = 0.0;
-  int vlik_n_gh = 0;
-  enum { kLikM = 0, kLikV = 1, kLikGm = 2, kLikA = 3, kLikT = 4, kLikVe = 5, kLikDve = 6, kLikMu = 7, kLikVecs = 8 };
-  double* lvec_at(int k) const { return as<double>(vlvec) + (size_t)k * npad; }
-  // the f-free part of log p(y | f) at the likelihood parameter p (Student-t: the scale; Gaussian: the variance)
-  double vlik_const(double p) const {
-    if (vlik_kind == GPSO_LIK_STUDENT_T)
-      return std::lgamma(0.5 * (vlik_df + 1.0)) - std::lgamma(0.5 * vlik_df) -
-             0.5 * (std::log(p * p) + std::log(vlik_df) + std::log(M_PI));
-    return -0.5 * (std::log(2.0 * M_PI) + std::log(p));
-  }
-  // m = L mu + c, v = rownorm(L S) (A := L S), then the quadrature at q: gm, a, t, VE, dVE/dp
-  void vgp_quadrature(const double* L, double* A, double p, double mean_c) {
-    hipStream_t s = st();
-    launch_vgp_gemv(s, L, false, as<double>(vq_mu), 0.0, 1.0, mean_c, nullptr, lvec_at(kLikM), n, npad);
-    launch_dgemm(s, L, false, as<double>(vq_S), false, A, npad, 1.0, 0.0);
-    launch_vgp_rownorm(s, A, lvec_at(kLikV), n, npad);
-    launch_vgp_quad(s, as<double>(y64), lvec_at(kLikM), lvec_at(kLikV), as<double>(vgh), vlik_n_gh, vlik_kind, p, vlik_df,
-                    vlik_const(p), mean_c, lvec_at(kLikGm), lvec_at(kLikA), lvec_at(kLikT), lvec_at(kLikVe),
-                    lvec_at(kLikDve), n, npad);
-  }
-
-  int vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) override {
-    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (kind != GPSO_LIK_GAUSSIAN && kind != GPSO_LIK_STUDENT_T && kind != GPSO_LIK_GAUSSIAN_GH)
-      return ctx->fail(GPSO_E_ARG, "unknown likelihood kind %d", kind);
-    if (kind != GPSO_LIK_GAUSSIAN) {
-      if (n_gh < 1 || n_gh > 64) return ctx->fail(GPSO_E_ARG, "n_gh=%d outside [1, 64]", n_gh);
-      if (!gh_x || !gh_w) return ctx->fail(GPSO_E_ARG, "gh_x / gh_w must not be NULL");
-      if (kind == GPSO_LIK_STUDENT_T && !(df > 2.0))
-        return ctx->fail(GPSO_E_ARG, "Student-t df=%g: need df > 2 (a finite predictive variance)", df);
-    }
-    int rc = refuse_if_async("gpso_vgp_set_likelihood");
-    if (rc) return rc;
-    if (kind != GPSO_LIK_GAUSSIAN) {
-      if ((rc = ensure(vgh, 128 * 8))) return rc;
-      double host[128] = {};
-      for (int k = 0; k < n_gh; ++k) {  // (GPflow's ndiagquad: x sqrt(2), w / sqrt(pi))
-        host[k] = gh_x[k] * std::sqrt(2.0);
-        host[64 + k] = gh_w[k] / std::sqrt(M_PI);
-      }
-      HIPCHECK(hipMemcpyAsync(vgh.p, host, sizeof(host), hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipStreamSynchronize(st()));
-    }
-    vlik_kind = kind;
-    vlik_df = kind == GPSO_LIK_STUDENT_T ? df : 0.0;
-    vlik_n_gh = kind == GPSO_LIK_GAUSSIAN ? 0 : n_gh;
-    return launch_status();
-  }
-
-  int vgp_begin(bool sparse = false /* the rows are inducing points: the SGPR's factors go too */) {
-    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "VGP call before gpso_set_data");
-    int rc = refuse_if_async("a VGP call");
-    if (rc) return rc;
-    if ((rc = ensure_fit_buffers())) return rc;
-    const size_t mat = (size_t)npad * npad * 8;
-    for (DevBuf* b : {&vA, &vB, &vC, &vq_S})
-      if ((rc = ensure(*b, mat))) return rc;
-    if ((rc = ensure(vq_mu, (size_t)npad * 8))) return rc;
-    if ((rc = ensure(vvec, (size_t)kVgpVecs * npad * 8))) return rc;
-    if ((rc = ensure(vsmall, kVgpSmall * 8))) return rc;
-    if (vlik_kind != GPSO_LIK_GAUSSIAN && (rc = ensure(vlvec, (size_t)kLikVecs * npad * 8))) return rc;
-    if (vq_n != n || vq_npad != npad) vgp_prior();
-    res.variational_begun(sparse);
-    reset_generation();
-    return GPSO_OK;
-  }
-  void vgp_prior() {
-    (void)hipMemsetAsync(vq_mu.p, 0, (size_t)npad * 8, st());
-    launch_vgp_pad_identity(st(), as<double>(vq_S), 0, npad, nullptr);
-    vq_n = n;
-    vq_npad = npad;
-  }
-  // A (destroyed: lower triangle read, identity padding) = Lout Lout^T; Linv = Lout^-1.  Both leave as clean lower triangles:
-  // zero above the diagonal, pad_diag on the diagonal of the padding, zero elsewhere on it
-  int vgp_chol(double* A, double* Lout, double* Linv, int* info, double pad_diag) {
-    hipStream_t s = st();
-    HIPCHECK(hipMemsetAsync(Linv, 0, (size_t)npad * npad * 8, s));
-    const int done = launch_potrf<double>(s, A, Lout, Linv, as<double>(work), nullptr, n, npad, as<double>(logdet), info,
-                                          single_level_max, nullptr);
-    if (!(done & 1)) launch_trtri<double>(s, Lout, Linv, as<double>(work), npad, fit_outer_panel(npad));
-    launch_vgp_clean_lower(s, Lout, Lout, n, npad, pad_diag);
-    launch_vgp_clean_lower(s, Linv, Linv, n, npad, pad_diag);
-    return GPSO_OK;
-  }
-  // L = chol(k(X, X) + 1e-6 I) into Lf, L^-1 into linv (clean lower, zero padding)
-  int vgp_factor(const Theta& th) {
-    int rc = set_theta(th.with_lik(kVgpJitter));
-    if (rc) return rc;
-    if ((rc = scale_inputs())) return rc;
-    launch_gram<double>(st(), as<double>(xs64), as<double>(xnorm64), n, npad, dp, kp, as<double>(K), vinfo() + 0);
-    return vgp_chol(as<double>(K), as<double>(Lf), as<double>(linv), vinfo() + 0, 0.0);
-  }
-  // wait for the stream, then the verdicts of the factorisations (out: host copy of vsmall)
-  // (kind: whose factorisations these are -- the names in a failure's message)
-  int vgp_finish(double** out, Post kind = Post::Vgp) {
-    double* host = ctx->pinned_scratch(kVgpSmall);
-    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    HIPCHECK(hipMemcpyAsync(host, vsmall.p, kVgpSmall * 8, hipMemcpyDeviceToHost, st()));
-    HIPCHECK(ctx->wait(st()));
-    int rc = launch_status();
-    if (rc) return rc;
-    int info[4];
-    std::memcpy(info, host + kVgpInfoAt, sizeof(info));
-    static const char* what[4] = {"k(X, X) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
-                                  "I - S S^T (reversed order)"};
-    static const char* what_sgpr[4] = {"Kuu = k(Z, Z) + 1e-6 I", "B = I + A A^T", "(unused)", "I - B^-1 (reversed order)"};
-    static const char* what_svgp[4] = {"Kuu = k(Z, Z) + 1e-6 I", "the natural parameter Lambda", "the covariance S S^T of q",
-                                       "I - S S^T (reversed order)"};
-    for (int q = 0; q < 4; ++q)
-      if (info[q] != INT_MAX)
-        return ctx->fail(GPSO_E_NOTPD, "%s is not positive definite: Cholesky failed at pivot %d",
-                         (kind == Post::Svgp ? what_svgp : kind == Post::Sgpr ? what_sgpr : what)[q], info[q]);
-    *out = host;
-    return GPSO_OK;
-  }
-  void vgp_reset_info() {
-    for (int q = 0; q < 4; ++q) launch_vgp_pad_identity(st(), nullptr, 0, 0, vinfo() + q);  // (INT_MAX; no matrix)
-  }
-
-  int vgp_set_q(const double* mu, const double* S, int64_t n_) override {
-    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_set_q before gpso_set_data");
-    if (n_ != n) return ctx->fail(GPSO_E_ARG, "q of %lld points for training data of %lld", (long long)n_, (long long)n);
-    int rc = vgp_begin();
-    if (rc) return rc;
-    if (mu == nullptr || S == nullptr) {  // NULL: the prior
-      vgp_prior();
-      HIPCHECK(ctx->wait(st()));
-      return launch_status();
-    }
-    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
-    double* tmp = as<double>(getter_tmp);
-    hipStream_t s = st();
-    HIPCHECK(hipMemcpyAsync(tmp, S, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(vq_mu.p, 0, (size_t)npad * 8, s));
-    HIPCHECK(hipMemcpyAsync(vq_mu.p, mu, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    launch_vgp_pad_identity(s, as<double>(vq_S), 0, npad, nullptr);
-    launch_convert_in<double>(s, tmp, as<double>(vq_S), n, n, npad);
-    launch_vgp_clean_lower(s, as<double>(vq_S), as<double>(vq_S), n, npad, 1.0);
-    HIPCHECK(hipStreamSynchronize(s));  // (the caller's host buffers are free again on return)
-    vq_n = n;
-    vq_npad = npad;
-    return launch_status();
-  }
-  // data that grew behind the rows q was made for (the caller keeps those rows first, in the same order): q keeps its
-  // leading block and takes the prior (mu = 0, an identity block of S) for the new rows -- on the device, no host copy.
-  // Inside one padded size the padding of q already IS that prior; a new padded size re-lays the leading block out.
-  int vgp_extend_q() override {
-    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_vgp_extend_q before gpso_set_data");
-    if (vq_n < 1 || vq_n > n) return ctx->fail(GPSO_E_STATE, "no variational state of at most %lld rows to extend", (long long)n);
-    int rc = refuse_if_async("gpso_vgp_extend_q");
-    if (rc) return rc;
-    hipStream_t s = st();
-    if (vq_npad != npad) {
-      DevBuf nS, nmu;  // (an early return frees them: q stays as it was)
-      if ((rc = ensure(nS, (size_t)npad * npad * 8))) return rc;
-      if ((rc = ensure(nmu, (size_t)npad * 8))) return rc;
-      launch_vgp_pad_identity(s, as<double>(nS), 0, npad, nullptr);
-      HIPCHECK(hipMemsetAsync(nmu.p, 0, (size_t)npad * 8, s));
-      HIPCHECK(hipMemcpy2DAsync(nS.p, (size_t)npad * 8, vq_S.p, (size_t)vq_npad * 8, (size_t)vq_n * 8, (size_t)vq_n,
-                                hipMemcpyDeviceToDevice, s));
-      HIPCHECK(hipMemcpyAsync(nmu.p, vq_mu.p, (size_t)vq_n * 8, hipMemcpyDeviceToDevice, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      vq_S = std::move(nS);
-      vq_mu = std::move(nmu);
-    }
-    vq_n = n;
-    vq_npad = npad;
-    HIPCHECK(ctx->wait(s));
-    return launch_status();
-  }
-  int vgp_get_q(double* mu, double* S) override {
-    if (vq_n != n || vq_npad != npad || vq_n < 1) return ctx->fail(GPSO_E_STATE, "no variational state for the resident data");
-    int rc;
-    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
-    double* tmp = as<double>(getter_tmp);
-    hipStream_t s = st();
-    if (S) {
-      launch_convert_out<double>(s, as<double>(vq_S), npad, tmp, n, n, 0);
-      HIPCHECK(hipMemcpyAsync(S, tmp, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (mu) HIPCHECK(hipMemcpyAsync(mu, vq_mu.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return launch_status();
-  }
-
-  // the update of q = N(qmu, qS qS^T) from the step's natural parameters Lambda* (vA, destroyed; identity padding) and h*
-  // (vvec kVgpH), at the context's size n: gamma-mixing with q's current natural parameters (Lambda = S^-T S^-1, h =
-  // Lambda mu), then GPflow's natural_to_meanvarsqrt into (mu_out, S_out); the verdicts in vinfo() 1 and 2
-  int vgp_natural_update(const double* qmu, const double* qS, double gamma, double* mu_out, double* S_out) {
-    hipStream_t s = st();
-    double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
-    double *h = vvec_at(kVgpH), *h2 = vvec_at(kVgpH2);
-    int rc;
-    if (gamma != 1.0) {
-      // the current natural parameters: Lambda = S^-T S^-1, h = Lambda mu
-      HIPCHECK(hipMemsetAsync(Cm, 0, (size_t)npad * npad * 8, s));
-      launch_install_chol<double>(s, qS, npad, npad, B, Cm);
-      launch_trtri<double>(s, B, Cm, as<double>(work), npad, kFitBlock);
-      launch_vgp_clean_lower(s, Cm, Cm, n, npad, 0.0);
-      launch_dgemm(s, Cm, true, Cm, false, B, npad, 1.0, 0.0);
-      launch_vgp_gemv(s, B, false, qmu, 0.0, 1.0, 0.0, nullptr, h2, n, npad);
-      launch_vgp_axpby(s, B, A, npad * npad, 1.0 - gamma, gamma);
-      launch_vgp_axpby(s, h2, h, npad, 1.0 - gamma, gamma);
-    }
-    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 1);
-    // V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
-    if ((rc = vgp_chol(A, B, Cm, vinfo() + 1, 0.0))) return rc;
-    launch_dgemm(s, Cm, true, Cm, false, A, npad, 1.0, 0.0);
-    launch_vgp_gemv(s, A, false, h, 0.0, 1.0, 0.0, nullptr, mu_out, n, npad);
-    launch_vgp_pad_identity(s, A, n, npad, vinfo() + 2);
-    return vgp_chol(A, S_out, Cm, vinfo() + 2, 1.0);
-  }
-
-  // one natural-gradient step on q at theta (GPflow's NaturalGradient with a conjugate likelihood, gamma in (0, 1])
-  int vgp_natgrad(const Theta& th, double gamma) override {
-    const double s2 = th.lik, mean_c = th.mean_c;
-    if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
-    int rc = vgp_begin();
-    if (rc) return rc;
-    hipStream_t s = st();
-    vgp_reset_info();
-    if ((rc = vgp_factor(th))) return rc;
-    double *L = as<double>(Lf), *A = as<double>(vA), *B = as<double>(vB), *h = vvec_at(kVgpH);
-    const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
-    if (!general) {
-      launch_vgp_pad_identity(s, A, 0, npad, nullptr);          // A := I
-      launch_dgemm(s, L, true, L, false, A, npad, 1.0 / s2, 1.0);  // Lambda* = I + L^T L / s2
-      launch_vgp_gemv(s, L, true, as<double>(y64), mean_c, 1.0 / s2, 0.0, nullptr, h, n, npad);  // h* = L^T (y - c) / s2
-    } else {
-      // the per-point derivatives at the current q (s2: the likelihood's parameter), then
-      // Lambda* = I + L^T diag(a) L and h* = L^T (gm + a (m - c))
-      vgp_quadrature(L, A, s2, mean_c);
-      launch_vgp_rowscale(s, L, lvec_at(kLikA), B, n, npad);
-      launch_vgp_pad_identity(s, A, 0, npad, nullptr);
-      launch_dgemm(s, L, true, B, false, A, npad, 1.0, 1.0);
-      launch_vgp_gemv(s, L, true, lvec_at(kLikT), 0.0, 1.0, 0.0, nullptr, h, n, npad);
-    }
-    // GPflow's natural_to_meanvarsqrt: V = chol(Lambda)^-1, Sigma = V^T V, mu = Sigma h, S = chol(Sigma)
-    // (a general likelihood builds the new q in scratch -- mu in its vector, S in the Gram's buffer, free by now -- and
-    // commits it only when every factorisation held: GPflow's natgrad assigns nothing when natural_to_meanvarsqrt fails)
-    double* mu_out = general ? lvec_at(kLikMu) : as<double>(vq_mu);
-    double* S_out = general ? as<double>(K) : as<double>(vq_S);
-    if ((rc = vgp_natural_update(as<double>(vq_mu), as<double>(vq_S), gamma, mu_out, S_out))) return rc;
-    double* host;
-    if ((rc = vgp_finish(&host))) {
-      if (!general) vgp_prior();  // (a failed Gaussian step leaves q at the prior, not half written; a general one: q as it was)
-      return rc;
-    }
-    if (general) {
-      HIPCHECK(hipMemcpyAsync(vq_mu.p, mu_out, (size_t)npad * 8, hipMemcpyDeviceToDevice, s));
-      HIPCHECK(hipMemcpyAsync(vq_S.p, S_out, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-      HIPCHECK(ctx->wait(s));
-      return launch_status();
-    }
-    return GPSO_OK;
-  }
-
-  // -ELBO at fixed q and its gradient in the constrained theta: grad[n_ls + 3] = (ls..., variance, s2, c)
-  int vgp_elbo(const Theta& th, double* loss, double* grad) override {
-    const double s2 = th.lik, mean_c = th.mean_c;
-    int rc = vgp_begin();
-    if (rc) return rc;
-    hipStream_t s = st();
-    vgp_reset_info();
-    if ((rc = vgp_factor(th))) return rc;
-    double *L = as<double>(Lf), *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
-    double *Sq = as<double>(vq_S), *mu = as<double>(vq_mu), *r = vvec_at(kVgpR);
-    const bool general = vlik_kind != GPSO_LIK_GAUSSIAN;
-    if (!general) {
-      launch_vgp_gemv(s, L, false, mu, 0.0, 1.0, mean_c, as<double>(y64), r, n, npad);  // r = y - (L mu + c)
-      launch_dgemm(s, L, false, Sq, false, A, npad, 1.0, 0.0);                           // L S
-      launch_vgp_rownorm(s, A, vvec_at(kVgpFvar), n, npad);                              // fvar
-      launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
-      launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma = (L S) S^T
-      launch_vgp_elbo_sums(s, r, vvec_at(kVgpFvar), mu, vvec_at(kVgpSrow), Sq, n, npad, as<double>(vsmall));
-    } else {
-      vgp_quadrature(L, A, s2, mean_c);                                                  // A = L S; gm, a, VE, dVE/dp
-      launch_vgp_rownorm(s, Sq, vvec_at(kVgpSrow), n, npad);
-      launch_dgemm(s, A, false, Sq, true, B, npad, 1.0, 0.0);                            // L Sigma
-      launch_vgp_lik_sums(s, lvec_at(kLikVe), lvec_at(kLikDve), lvec_at(kLikGm), mu, vvec_at(kVgpSrow), Sq, n, npad,
-                          as<double>(vsmall));
-    }
-    if (grad) {
-      if (!general) launch_vgp_lbar(s, B, r, mu, n, npad, 1.0 / s2);   // Lbar
-      else launch_vgp_lbar_w(s, B, lvec_at(kLikA), lvec_at(kLikGm), mu, n, npad);  // Lbar = tril(diag(a) L Sigma - gm mu^T)
-      launch_dgemm(s, L, true, B, false, Cm, npad, 1.0, 0.0);          // P = L^T Lbar
-      launch_vgp_phi_sym(s, Cm, A, n, npad);                           // M = Phi(P) + Phi(P)^T
-      launch_dgemm(s, A, false, Li, false, B, npad, 1.0, 0.0);         // M L^-1
-      launch_dgemm(s, Li, true, B, false, Cm, npad, 1.0, 0.0);         // 2 Kbar = L^-T M L^-1
-      HIPCHECK(hipMemsetAsync(vvec_at(kVgpZero), 0, (size_t)npad * 8, s));
-      // the NLML gradient's contraction with K^-1 := 2 Kbar and alpha := 0: W = Kbar, sum_ij Kbar_ij dK_ij / dtheta
-      launch_gradient<double>(s, Li, vvec_at(kVgpZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(),
-                              kp, Cm, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
-    }
-    double* host;
-    if ((rc = vgp_finish(&host))) return rc;
-    const double N = (double)n;
-    if (general) {  // -sum VE + KL; d/dp = -sum dVE/dp, d/dc = -sum gm
-      *loss = -host[0] + 0.5 * (host[4] + host[3] - N - host[5]);
-      if (grad) {
-        for (int k = 0; k <= n_ls; ++k) grad[k] = host[kVgpGradAt + k];
-        grad[n_ls + 1] = -host[1];
-        grad[n_ls + 2] = -host[2];
-      }
-      return GPSO_OK;
-    }
-    const double data = 0.5 * N * std::log(2.0 * M_PI * s2) + (host[1] + host[2]) / (2.0 * s2);
-    const double kl = 0.5 * (host[4] + host[3] - N - host[5]);
-    *loss = data + kl;
-    if (grad) {
-      for (int k = 0; k <= n_ls; ++k) grad[k] = host[kVgpGradAt + k];  // lengthscales..., kernel variance
-      grad[n_ls + 1] = N / (2.0 * s2) - (host[1] + host[2]) / (2.0 * s2 * s2);
-      grad[n_ls + 2] = -host[0] / s2;
-    }
-    return GPSO_OK;
-  }
-
-  // install under a quadrature likelihood: G = chol J (I - Sigma / (1 + delta)) J into vC (G^-1 in vA), with the
-  // smallest delta of 0, 1e-8, 2e-8, 4e-8, ... <= 1 that makes it positive definite.  A non-log-concave likelihood (the
-  // Student-t: a < 0 in its tails) can leave Sigma above I in a direction, where the predict kernels' one-term form
-  // k** - |C k*|^2 cannot hold var_f exactly; the install then serves k** - k*^T L^-T ((1 + delta) I - Sigma) L^-1 k*
-  // + delta k**, i.e. var_f + delta (k** - |L^-1 k*|^2), in [var_f, var_f + delta k**].
-  int vgp_shifted_root(double* delta_out, bool sigma_ready = false /* K already holds Sigma (the SGPR install: B^-1) */,
-                       const double* qS = nullptr /* the root of Sigma when it is not the VGP's (the SVGP's q) */) {
-    hipStream_t s = st();
-    double *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sig = as<double>(K);
-    if (!qS) qS = as<double>(vq_S);
-    if (!sigma_ready) launch_dgemm(s, qS, false, qS, true, Sig, npad, 1.0, 0.0);  // Sigma (K is free here)
-    int* host = reinterpret_cast<int*>(ctx->pinned_scratch(kVgpSmall));
-    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    for (double delta = 0.0; delta <= 1.0; delta = (delta == 0.0 ? 1.0e-8 : 2.0 * delta)) {
-      HIPCHECK(hipMemsetAsync(A, 0, (size_t)npad * npad * 8, s));
-      launch_vgp_axpby(s, Sig, A, npad * npad, 1.0 / (1.0 + delta), 0.0);
-      launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);
-      int rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0);
-      if (rc) return rc;
-      HIPCHECK(hipMemcpyAsync(host, vinfo(), 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-      HIPCHECK(ctx->wait(s));
-      if ((rc = launch_status())) return rc;
-      if (host[0] != INT_MAX || (sigma_ready && host[1] != INT_MAX) || host[3] == INT_MAX) {  // (a Gram -- or the SGPR's B -- that failed is vgp_finish's to report)
-        *delta_out = delta;
-        return GPSO_OK;
-      }
-    }
-    return ctx->fail(GPSO_E_NOTPD, sigma_ready ? "I - B^-1: no shift delta <= 1 makes it positive definite"
-                                               : "I - S S^T: no shift delta <= 1 makes it positive definite (q far above the prior)");
-  }
-
-  // install the predictive at theta: L^-1 := C = R L^-1 (I - S S^T = R^T R), alpha := L^-T mu, noise := s2, mean := c --
-  // every predict path then serves the VGP unchanged
-  int vgp_posterior(const Theta& th) override {
-    const double s2 = th.lik;
-    int rc = vgp_begin();
-    if (rc) return rc;
-    hipStream_t s = st();
-    vgp_reset_info();
-    if ((rc = vgp_factor(th))) return rc;
-    double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC), *Sq = as<double>(vq_S);
-    launch_vgp_gemv(s, Li, true, as<double>(vq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
-    if (vlik_kind == GPSO_LIK_GAUSSIAN) {
-      launch_dgemm(s, Sq, false, Sq, true, A, npad, 1.0, 0.0);        // Sigma
-      launch_vgp_reverse(s, A, B, n, npad, 0, vinfo() + 3);           // J (I - Sigma) J
-      if ((rc = vgp_chol(B, Cm, A, vinfo() + 3, 0.0))) return rc;     // G
-      launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R = J G^T J
-      launch_dgemm(s, B, false, Li, false, A, npad, 1.0, 0.0);        // C = R L^-1
-      HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-      if ((rc = set_theta(th))) return rc;
-    } else {
-      double shift = 0.0;
-      if ((rc = vgp_shifted_root(&shift))) return rc;                 // G of J (I - Sigma / (1 + delta)) J
-      launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R
-      launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R L^-1
-      HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-      // the likelihood's variance in the predictive: scale^2 df / (df - 2) (Student-t, closed form) or s2; + delta k**
-      const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
-      if ((rc = set_theta(th.with_lik(noise + shift * th.variance)))) return rc;
-    }
-    return install_predictive(Post::Vgp);
-  }
-  // what the three variational installs share once linv holds C and alpha_f holds beta: the predict-ready copies, the
-  // factorisations' verdicts, and the posterior's kind
-  int install_predictive(Post kind) {
-    hipStream_t s = st();
-    int rc;
-    double* host;
-    launch_pack_linv<TF, TP>(s, as<TF>(linv), n, npad, as<TP>(linv_p));
-    launch_convert_vec<TF, TP>(s, as<TF>(alpha_f), as<TP>(alpha), npad);
-    if (!(rc = pack_bf16())) rc = vgp_finish(&host, kind);
-    res.variational_ready(kind, rc == GPSO_OK);
-    return rc;
-  }
-
-
-  // ---- sparse GP regression on inducing points (GPflow 2 SGPR, Gaussian likelihood, Z fixed) --------
-  // gpso_sgpr_set_inducing / gpso_sgpr_select_inducing move the training data (N rows) into buffers of their own (sgX raw,
-  // sgY) and make Z the context's resident rows (n = M): Kuu, its factor and everything M x M then run through the fit's
-  // buffers and kernels at size M_pad exactly as the VGP's do at N_pad, the installed predictive is a posterior over the M
-  // rows Z that every predict path serves, and the rectangular [M_pad x N_pad] work lives in sgKuf / sgA / sgW.
-  DevBuf sgX, sgY, sgXs, sgXn, sgKuf, sgA, sgW, sgPart, sgM1, sgM2, sgM3, sgvecN, sgvecM, sgsmall, sggpart, sgidx;
-  DevBuf sgZpart, sgZg;  // the moving-Z evaluations' slice partials and dF/dZ [M x D] (inducing.hip)
-  std::vector<double> sg_xh;  // host mirror of the training inputs (the rows greedy selection gathers Z from)
-  int64_t sg_n = 0, sg_npad = 0;
-  enum { kSgE = 0, kSgW = 1, kSgT = 2, kSgVecsN = 3 };
-  enum { kSgAe = 0, kSgCv = 1, kSgMu = 2, kSgAvec = 3, kSgRows = 4, kSgZero = 5, kSgVecsM = 6 };
-  static constexpr int kSgGradAt = 16, kSgSmall = kSgGradAt + kGradMaxLs + 1;
-  double* sgn_at(int k) const { return as<double>(sgvecN) + (size_t)k * sg_npad; }
-  double* sgm_at(int k) const { return as<double>(sgvecM) + (size_t)k * npad; }
-
-  int sgpr_need_f64() {
-    if (sizeof(TF) != 8) return ctx->fail(GPSO_E_ARG, "SGPR needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context");
-    return GPSO_OK;
-  }
-  // the resident rows are the caller's data: keep them as the SGPR's training set
-  int sgpr_stash() {
-    if (res.sg_have) return GPSO_OK;
-    if (!res.have_data) return ctx->fail(GPSO_E_STATE, "SGPR call before gpso_set_data");
-    int rc;
-    sg_n = n;
-    sg_npad = npad;  // (a multiple of 128: the tile GEMM's k and n extents)
-    if ((rc = ensure(sgX, (size_t)sg_npad * d * 8))) return rc;
-    if ((rc = ensure(sgY, (size_t)sg_npad * 8))) return rc;
-    HIPCHECK(hipMemcpyAsync(sgX.p, x64.p, (size_t)sg_n * d * 8, hipMemcpyDeviceToDevice, st()));
-    HIPCHECK(hipMemcpyAsync(sgY.p, y64.p, (size_t)sg_n * 8, hipMemcpyDeviceToDevice, st()));
-    HIPCHECK(hipStreamSynchronize(st()));
-    sg_xh = x_host;
-    res.stashed();
-    return GPSO_OK;
-  }
-
-  int sgpr_set_inducing(const double* Z, int64_t m) override {
-    int rc = sgpr_need_f64();
-    if (rc) return rc;
-    if (!Z) return ctx->fail(GPSO_E_ARG, "Z must not be NULL");
-    if (m < 1 || m > 65536) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, 65536]", (long long)m);
-    if (!res.sg_have && !res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_set_inducing before gpso_set_data");
-    if ((rc = refuse_if_async("gpso_sgpr_set_inducing"))) return rc;
-    for (int64_t e = 0; e < m * (int64_t)d; ++e)
-      if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
-    if ((rc = sgpr_stash())) return rc;
-    std::vector<double> zeros((size_t)m, 0.0), zc(Z, Z + (size_t)m * d);  // (Z may alias the mirror set_data overwrites)
-    rc = put_rows(zc.data(), zeros.data(), m, d, true);
-    if (rc) {  // (a HIP / allocation failure: the arguments were checked above.  The resident rows are unknown now)
-      res.rows_unknown();
-      return rc;
-    }
-    svq_m = -1;  // (the SVGP's q restarts at the prior on the new Z)
-    return GPSO_OK;
-  }
-
-  int sgpr_select_inducing(const Theta& th, int64_t m, int64_t* idx_out) override {
-    int rc = sgpr_need_f64();
-    if (rc) return rc;
-    if (!res.sg_have && !res.have_data) return ctx->fail(GPSO_E_STATE, "gpso_sgpr_select_inducing before gpso_set_data");
-    if ((rc = refuse_if_async("gpso_sgpr_select_inducing"))) return rc;
-    const int64_t N = res.sg_have ? sg_n : n;
-    if (m < 1 || m > N) return ctx->fail(GPSO_E_ARG, "m=%lld outside [1, N=%lld]", (long long)m, (long long)N);
-    if ((rc = theta_status(theta_refusal(th, d, false)))) return rc;
-    // (from here on the call replaces whatever posterior was resident: the hyper block is the selection's)
-    res.selection_begun();
-    if ((rc = set_theta(th.with_lik(kVgpJitter)))) return rc;
-    if ((rc = sgpr_stash())) return rc;
-    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
-    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
-    if ((rc = ensure(sgW, (size_t)m * sg_npad * 8))) return rc;
-    if ((rc = ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
-    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
-    if ((rc = ensure(sgidx, (size_t)m * 8))) return rc;
-    hipStream_t s = st();
-    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
-    launch_sgpr_greedy(s, as<double>(sgXs), sg_n, sg_npad, dp, kp, (int)m, as<double>(sgW), sgn_at(0), as<double>(sgsmall),
-                       as<int64_t>(sgidx));
-    std::vector<int64_t> idx((size_t)m);
-    HIPCHECK(hipMemcpyAsync(idx.data(), sgidx.p, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    if ((rc = launch_status())) return rc;
-    std::vector<double> Z((size_t)m * d);
-    for (int64_t j = 0; j < m; ++j) {
-      if (idx[j] == -1)
-        return ctx->fail(GPSO_E_NOTPD, "greedy selection: k(X, X) is numerically of rank %lld < m=%lld at these hyper-parameters "
-                         "(the largest remaining conditional variance is below 1e-12 of the kernel variance): ask for fewer inducing points",
-                         (long long)j, (long long)m);
-      if (idx[j] < 0 || idx[j] >= sg_n) return ctx->fail(GPSO_E_HIP, "greedy selection returned row %lld of %lld", (long long)idx[j], (long long)sg_n);
-      std::memcpy(&Z[(size_t)j * d], &sg_xh[(size_t)idx[j] * d], (size_t)d * 8);
-    }
-    if (idx_out) std::memcpy(idx_out, idx.data(), (size_t)m * 8);
-    return sgpr_set_inducing(Z.data(), m);
-  }
-
-  int sgpr_get_inducing(double* Z, int64_t* m_out, int64_t* n_data_out) override {
-    if (!res.sg_have || !res.sg_have_z) return ctx->fail(GPSO_E_STATE, "no inducing points set (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing)");
-    if (m_out) *m_out = n;
-    if (n_data_out) *n_data_out = sg_n;
-    if (Z) std::memcpy(Z, x_host.data(), (size_t)n * d * 8);
-    return GPSO_OK;
-  }
-
-  // the intermediates of the last successful gpso_sgpr_bound_u, for checks against a reference
-  int sgpr_get_factor(int which, double* out) override {
-    if (!out) return ctx->fail(GPSO_E_ARG, "out must not be NULL");
-    if (which < GPSO_SGPR_KUF || which > GPSO_SGPR_CV) return ctx->fail(GPSO_E_ARG, "unknown SGPR factor id %d", which);
-    if (!res.sg_have || !res.sg_have_z || !res.sg_factors)
-      return ctx->fail(GPSO_E_STATE, "gpso_sgpr_get_factor: no gpso_sgpr_bound_u result resident (any later call but a getter drops it)");
-    int rc = refuse_if_async("gpso_sgpr_get_factor");
-    if (rc) return rc;
-    const double* src = which == GPSO_SGPR_KUF ? as<double>(sgKuf) : which == GPSO_SGPR_LU ? as<double>(Lf)
-                        : which == GPSO_SGPR_LB ? as<double>(vC) : sgm_at(kSgCv);
-    const int64_t rows = n, cols = which == GPSO_SGPR_KUF ? sg_n : which == GPSO_SGPR_CV ? 1 : n;
-    const int64_t ld = which == GPSO_SGPR_KUF ? sg_npad : which == GPSO_SGPR_CV ? 1 : npad;
-    HIPCHECK(hipMemcpy2DAsync(out, (size_t)cols * 8, src, (size_t)ld * 8, (size_t)cols * 8, (size_t)rows, hipMemcpyDeviceToHost, st()));
-    HIPCHECK(hipStreamSynchronize(st()));
-    return GPSO_OK;
-  }
-
-  // Lu (Lf), Lu^-1 (linv), Kuf, A, A A^T (vA), LB (vC), LB^-1 (sgM2), e, A e, cv at theta; the verdicts in vinfo() 0 and 1
-  int sgpr_factor(const Theta& th, const char* who) {
-    const double s2 = th.lik, mean_c = th.mean_c;
-    int rc = sgpr_need_f64();
-    if (rc) return rc;
-    if (!res.sg_have || !res.sg_have_z)
-      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
-    // (what set_theta would refuse, refused here: a rejected call leaves the resident posterior as it was)
-    if ((rc = theta_status(theta_refusal(th, d, true), "noise variance"))) return rc;
-    if ((rc = vgp_begin(true))) return rc;
-    if ((rc = sparse_workspace(false))) return rc;
-    const int nsplit = sparse_nsplit();
-    hipStream_t s = st();
-    vgp_reset_info();
-    if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
-    const double sig = std::sqrt(s2);
-    double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *A = as<double>(sgA);
-    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
-    launch_sgpr_cross_gram(s, as<double>(xs64), as<double>(sgXs), n, npad, sg_n, sg_npad, dp, kp, Kuf);
-    launch_dgemm_rect(s, Li, npad, 1, Kuf, sg_npad, 1, A, sg_npad, npad, sg_npad, npad, 1.0 / sig, 0.0);  // A = Lu^-1 Kuf / sigma
-    // A A^T: the long-K product, split along N into nsplit partial products summed in a fixed order
-    launch_dgemm_rect(s, A, sg_npad, 1, A, 1, sg_npad, as<double>(sgPart), npad, npad, npad, sg_npad, 1.0, 0.0, nsplit);
-    launch_sgpr_splitk_sum(s, as<double>(sgPart), nsplit, n, npad, as<double>(vA), as<double>(vB), vinfo() + 1);
-    if ((rc = vgp_chol(as<double>(vB), as<double>(vC), as<double>(sgM2), vinfo() + 1, 0.0))) return rc;  // LB, LB^-1
-    launch_sgpr_resid(s, as<double>(sgY), mean_c, sgn_at(kSgE), sg_n, sg_npad);
-    launch_sgpr_gemv(s, A, false, sgn_at(kSgE), 1.0, sgm_at(kSgAe), n, npad, sg_n, sg_npad);
-    launch_vgp_gemv(s, as<double>(sgM2), false, sgm_at(kSgAe), 0.0, 1.0 / sig, 0.0, nullptr, sgm_at(kSgCv), n, npad);
-    return GPSO_OK;
-  }
-
-  int sgpr_bound(const Theta& th, double* loss, double* grad) override {
-    return sgpr_bound_impl(th, loss, grad, nullptr, "gpso_sgpr_bound_u");
-  }
-
-  // grad_z (nullable, with grad): also d(-F)/dZ [M * D], from the weights the theta gradient has just formed
-  int sgpr_bound_impl(const Theta& th, double* loss, double* grad, double* grad_z, const char* who) {
-    const double variance = th.variance, s2 = th.lik;
-    int rc = sgpr_factor(th, who);
-    if (rc) return rc;
-    if (grad_z && (rc = inducing_buffers())) return rc;
-    hipStream_t s = st();
-    const double b = 1.0 / s2;
-    double *Li = as<double>(linv), *Kuf = as<double>(sgKuf), *AAT = as<double>(vA), *T1 = as<double>(vB), *LB = as<double>(vC);
-    double *LBi = as<double>(sgM2), *G1 = as<double>(K), *M1 = as<double>(sgM1), *M3 = as<double>(sgM3);
-    if (grad) {
-      launch_dgemm(s, LBi, false, Li, false, T1, npad, 1.0, 0.0);   // T1 = LB^-1 Lu^-1
-      launch_vgp_gemv(s, T1, true, sgm_at(kSgCv), 0.0, s2, 0.0, nullptr, sgm_at(kSgAvec), n, npad);  // a = Q^-1 Kuf e
-      launch_sgpr_gemv(s, Kuf, true, sgm_at(kSgAvec), 1.0, sgn_at(kSgW), n, npad, sg_n, sg_npad);    // w = Kfu a
-      launch_dgemm(s, T1, true, T1, false, G1, npad, 1.0, 0.0);     // Q^-1
-      launch_dgemm(s, Li, true, Li, false, M1, npad, 1.0, 0.0);     // Kuu^-1
-      launch_vgp_axpby(s, M1, G1, npad * npad, b, -b);              // G1 = b (Kuu^-1 - Q^-1)
-      launch_dgemm_rect(s, G1, npad, 1, Kuf, sg_npad, 1, as<double>(sgW), sg_npad, npad, sg_npad, npad, 1.0, 0.0);  // G1 Kuf
-      launch_sgpr_tvec(s, sgn_at(kSgE), sgn_at(kSgW), b * b, -b * b * b, sgn_at(kSgT), sg_n, sg_npad);
-      // dF/dKuf = G1 Kuf + a t^T, contracted with dKuf/dtheta tile by tile
-      launch_sgpr_cross_grad(s, as<double>(sgW), sgm_at(kSgAvec), sgn_at(kSgT), as<double>(xs64), as<double>(sgXs), n, npad,
-                             sg_n, sg_npad, dp, n_ls, ls_dev(), kp, as<double>(sggpart), as<double>(sgsmall) + kSgGradAt);
-      launch_dgemm(s, AAT, false, Li, false, M1, npad, 1.0, 0.0);   // A A^T Lu^-1
-      launch_dgemm(s, Li, true, M1, false, M3, npad, 1.0, 0.0);     // P = Lu^-T A A^T Lu^-1
-      launch_sgpr_wuu(s, G1, M3, sgm_at(kSgAvec), b, M1, n, npad);  // -2 dF/dKuu (M1 is free again)
-      HIPCHECK(hipMemsetAsync(sgm_at(kSgZero), 0, (size_t)npad * 8, s));
-      // the Kuu part: the NLML gradient's contraction with K^-1 := -2 dF/dKuu and alpha := 0
-      launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
-                              M1, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
-      launch_vgp_rownorm(s, LBi, sgm_at(kSgRows), n, npad);
-      // dF/dKuf = G1 Kuf + a t^T is of F, dF/dKuu = -M1 / 2 of F: the loss takes the cross part with -1, the Kuu part with +1
-      if (grad_z && (rc = launch_inducing_grad(s, as<double>(sgW), sgm_at(kSgAvec), sgn_at(kSgT), M1, as<double>(xs64),
-                                               as<double>(sgXs), n, npad, sg_n, sg_npad, d, dp, ls_dev(), kp, -1.0, 1.0,
-                                               as<double>(sgZpart), as<double>(sgZg))))
-        return rc;
-    }
-    launch_sgpr_sums(s, LB, AAT, sgm_at(kSgCv), sgn_at(kSgE), grad ? sgn_at(kSgW) : nullptr, grad ? sgm_at(kSgRows) : nullptr, n,
-                     npad, sg_n, as<double>(sgsmall));
-    double* host;
-    if ((rc = vgp_finish(&host, Post::Sgpr))) return rc;
-    double guu[kGradMaxLs + 1];
-    for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
-    double* h = ctx->pinned_scratch(kSgSmall);
-    if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
-    if (grad && grad_z) HIPCHECK(hipMemcpyAsync(grad_z, sgZg.p, (size_t)n * d * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(ctx->wait(s));
-    const double N = (double)sg_n, M = (double)n;
-    const double F = -0.5 * N * std::log(2.0 * M_PI) - h[0] - 0.5 * N * std::log(s2) - 0.5 * b * h[1] + 0.5 * h[2] -
-                     0.5 * N * variance * b + 0.5 * h[3];
-    *loss = -F;
-    res.bound_ready();
-    if (grad) {
-      // d(-F)/dtheta: the Kuu contraction already is of -F; the cross one is of F; Kdiag: dF/dvariance = -N b / 2
-      for (int k = 0; k <= n_ls; ++k) grad[k] = guu[k] - h[kSgGradAt + k];
-      grad[n_ls] += 0.5 * N * b;
-      const double dF_db = 0.5 * N * s2 - 0.5 * s2 * (M - h[8]) - 0.5 * h[1] + b * h[4] - 0.5 * b * b * h[5] -
-                           0.5 * N * variance + 0.5 * s2 * h[3];
-      grad[n_ls + 1] = b * b * dF_db;
-      grad[n_ls + 2] = -(b * h[6] - b * b * h[7]);
-    }
-    return GPSO_OK;
-  }
-
-  // install the predictive over the rows Z: L^-1 := C = sqrt(1 + delta) R Lu^-1 (I - B^-1 / (1 + delta) = R^T R, delta the
-  // smallest of 0, 1e-8, 2e-8, ... that factors), alpha := Lu^-T LB^-T cv, noise := s2 + delta variance, mean := c
-  int sgpr_posterior(const Theta& th, double* delta_out) override {
-    int rc = sgpr_factor(th, "gpso_sgpr_posterior");
-    if (rc) return rc;
-    hipStream_t s = st();
-    double *Li = as<double>(linv), *LBi = as<double>(sgM2);
-    launch_vgp_gemv(s, LBi, true, sgm_at(kSgCv), 0.0, 1.0, 0.0, nullptr, sgm_at(kSgMu), n, npad);        // mu = LB^-T cv
-    launch_vgp_gemv(s, Li, true, sgm_at(kSgMu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);   // beta = Lu^-T mu
-    launch_dgemm(s, LBi, true, LBi, false, as<double>(K), npad, 1.0, 0.0);                               // B^-1
-    double shift = 0.0;
-    if ((rc = vgp_shifted_root(&shift, true))) return rc;                                                // G in vC
-    launch_vgp_reverse(s, as<double>(vC), as<double>(vB), n, npad, 1, nullptr);                          // R
-    launch_dgemm(s, as<double>(vB), false, Li, false, as<double>(vA), npad, std::sqrt(1.0 + shift), 0.0);
-    HIPCHECK(hipMemcpyAsync(Li, vA.p, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    if ((rc = set_theta(th.with_lik(th.lik + shift * th.variance)))) return rc;
-    if ((rc = install_predictive(Post::Sgpr))) return rc;
-    if (delta_out) *delta_out = shift;
-    return GPSO_OK;
-  }
-
-  // ---- sparse variational GP on inducing points (GPflow 2 SVGP, whitened, full q_sqrt, full batch) --------
-  // Z and the training data are the SGPR's (gpso_sgpr_set_inducing / gpso_sgpr_select_inducing: Z the resident rows, n = M),
-  // the likelihood the VGP's (gpso_vgp_set_likelihood).  q(v) = N(mu, S S^T) over the M inducing values lives in svq_mu
-  // [M_pad] and svq_S [M_pad^2] (lower; identity on the padding), made for the resident Z: a new Z restarts it at the
-  // prior.  A = Lu^-1 Kuf sits in the SGPR's sgA (without its 1 / sigma); svB holds S^T A, later the cross weight g;
-  // svD the column-scaled A diag(a).  The M x M work runs through the fit's and the VGP's buffers at M_pad.
-  DevBuf svq_mu, svq_S, svB, svD, svvecN;
-  int64_t svq_m = -1, svq_mpad = -1;  // the rows q was made for (-1: none; the next call starts q at the prior)
-  enum { kSvM = 0, kSvV = 1, kSvGm = 2, kSvA = 3, kSvT = 4, kSvVe = 5, kSvDve = 6, kSvVecsN = 7 };
-  double* svn_at(int k) const { return as<double>(svvecN) + (size_t)k * sg_npad; }
-  // the long-K products A A^T (SGPR) and A diag(a) A^T (SVGP) are split along N into this many fixed-order partial products
-  int sparse_nsplit() const {
-    int ns = 1;
-    while (ns < 16 && sg_npad % (256 * ns) == 0 && sg_npad / (2 * ns) >= 512) ns *= 2;
-    return ns;
-  }
-  // the rectangular [M_pad x N_pad] and square [M_pad^2] work of an evaluation at the resident M and N.  Each family asks
-  // for its own third rectangle(s) and N-vectors only: sgW / sgvecN the SGPR, svB / svD / svvecN the SVGP
-  int sparse_workspace(bool svgp) {
-    const size_t rect = (size_t)npad * sg_npad * 8, sq = (size_t)npad * npad * 8;
-    int rc;
-    if ((rc = ensure(sgKuf, rect)) || (rc = ensure(sgA, rect))) return rc;
-    if (svgp) {
-      if ((rc = ensure(svB, rect)) || (rc = ensure(svD, rect))) return rc;
-    } else if ((rc = ensure(sgW, rect))) {
-      return rc;
-    }
-    for (DevBuf* b : {&sgM1, &sgM2, &sgM3})
-      if ((rc = ensure(*b, sq))) return rc;
-    if ((rc = ensure(sgPart, sq * sparse_nsplit()))) return rc;
-    if ((rc = ensure(sgXs, (size_t)sg_npad * dp * 8))) return rc;
-    if ((rc = ensure(sgXn, (size_t)sg_npad * 8))) return rc;
-    if ((rc = svgp ? ensure(svvecN, (size_t)kSvVecsN * sg_npad * 8) : ensure(sgvecN, (size_t)kSgVecsN * sg_npad * 8))) return rc;
-    if ((rc = ensure(sgvecM, (size_t)kSgVecsM * npad * 8))) return rc;
-    if ((rc = ensure(sgsmall, kSgSmall * 8))) return rc;
-    return ensure(sggpart, (size_t)(npad / 64) * (sg_npad / 64) * (kGradMaxLs + 1) * 8);
-  }
-
-  int svgp_need_z(const char* who) {
-    int rc = sgpr_need_f64();
-    if (rc) return rc;
-    if (!res.sg_have || !res.sg_have_z)
-      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
-    return GPSO_OK;
-  }
-  void svgp_prior() {
-    (void)hipMemsetAsync(svq_mu.p, 0, (size_t)npad * 8, st());
-    launch_vgp_pad_identity(st(), as<double>(svq_S), 0, npad, nullptr);
-    svq_m = n;
-    svq_mpad = npad;
-  }
-  // q's buffers at the resident M; the prior when q was made for other rows
-  int svgp_q() {
-    int rc;
-    if (svq_m == n && svq_mpad == npad) return GPSO_OK;
-    if ((rc = ensure(svq_mu, (size_t)npad * 8))) return rc;
-    if ((rc = ensure(svq_S, (size_t)npad * npad * 8))) return rc;
-    svgp_prior();
-    return GPSO_OK;
-  }
-
-  // Lu (Lf), Lu^-1 (linv) at theta; rect: also Kuf (sgKuf) and A = Lu^-1 Kuf (sgA).  The verdict of Kuu in vinfo() 0
-  int svgp_begin(const Theta& th, const char* who, bool rect) {
-    int rc = svgp_need_z(who);
-    if (rc) return rc;
-    if ((rc = theta_status(theta_refusal(th, d, true), "likelihood parameter"))) return rc;
-    if ((rc = vgp_begin(true))) return rc;
-    if ((rc = svgp_q())) return rc;
-    if (rect && (rc = sparse_workspace(true))) return rc;
-    hipStream_t s = st();
-    vgp_reset_info();
-    if ((rc = vgp_factor(th))) return rc;  // Kuu = k(Z, Z) + 1e-6 I, Lu, Lu^-1
-    if (!rect) return GPSO_OK;
-    launch_scale_x<double>(s, as<double>(sgX), sg_n, sg_npad, d, dp, ls_dev(), as<double>(sgXs), as<double>(sgXn), nullptr);
-    launch_sgpr_cross_gram(s, as<double>(xs64), as<double>(sgXs), n, npad, sg_n, sg_npad, dp, kp, as<double>(sgKuf));
-    launch_dgemm_rect(s, as<double>(linv), npad, 1, as<double>(sgKuf), sg_npad, 1, as<double>(sgA), sg_npad, npad, sg_npad,
-                      npad, 1.0, 0.0);  // A = Lu^-1 Kuf
-    return GPSO_OK;
-  }
-
-  // the moments of q(f) at the training points (fm = A^T mu + c; fv = variance - |A_j|^2 + |S^T A_j|^2 when want_v) and
-  // the per-point terms of the likelihood there: gm, a = -2 dVE/dv, t = gm + a (fm - c), VE, dVE/dp (closed form for the
-  // Gaussian -- gauss -- else the VGP's Gauss-Hermite kernel)
-  void svgp_pointwise(double variance, double p, double mean_c, bool want_v, bool gauss) {
-    hipStream_t s = st();
-    double *A = as<double>(sgA), *B = want_v ? as<double>(svB) : nullptr;
-    if (want_v)
-      launch_dgemm_rect(s, as<double>(svq_S), 1, npad, A, sg_npad, 1, B, sg_npad, npad, sg_npad, npad, 1.0, 0.0);  // S^T A
-    launch_svgp_moments(s, A, B, as<double>(svq_mu), variance, mean_c, svn_at(kSvM), svn_at(kSvV), n, sg_n, sg_npad);
-    if (gauss)
-      launch_svgp_gauss(s, as<double>(sgY), svn_at(kSvM), svn_at(kSvV), p, mean_c, svn_at(kSvGm), svn_at(kSvA), svn_at(kSvT),
-                        svn_at(kSvVe), svn_at(kSvDve), sg_n, sg_npad);
-    else
-      launch_vgp_quad(s, as<double>(sgY), svn_at(kSvM), svn_at(kSvV), as<double>(vgh), vlik_n_gh, vlik_kind, p, vlik_df,
-                      vlik_const(p), mean_c, svn_at(kSvGm), svn_at(kSvA), svn_at(kSvT), svn_at(kSvVe), svn_at(kSvDve), sg_n,
-                      sg_npad);
-  }
-
-  // P = A diag(a) A^T (into aat) and I + P (into lam, identity padding): the long-K product in its fixed split-K order
-  void svgp_adat(double* aat, double* lam) {
-    hipStream_t s = st();
-    const int ns = sparse_nsplit();
-    launch_svgp_colscale(s, as<double>(sgA), svn_at(kSvA), as<double>(svD), n, npad, sg_n, sg_npad);  // D = A diag(a)
-    launch_dgemm_rect(s, as<double>(sgA), sg_npad, 1, as<double>(svD), 1, sg_npad, as<double>(sgPart), npad, npad, npad,
-                      sg_npad, 1.0, 0.0, ns);
-    launch_sgpr_splitk_sum(s, as<double>(sgPart), ns, n, npad, aat, lam, nullptr);
-  }
-
-  // one natural-gradient step on q (gamma in (0, 1]): Lambda* = I + A diag(a) A^T, h* = A t at the current q, then the
-  // VGP's mixing and natural_to_meanvarsqrt at size M.  conj: the Gaussian step at noise variance p whatever the likelihood
-  // (the conjugate start).  The new q is built in scratch and committed only when every factorisation held: a failed
-  // step returns GPSO_E_NOTPD with q exactly as it was, for every likelihood.
-  int svgp_step(const Theta& th, double gamma, bool conj, const char* who) {
-    const double variance = th.variance, p = th.lik, mean_c = th.mean_c;
-    if (!(gamma > 0.0 && gamma <= 1.0)) return ctx->fail(GPSO_E_ARG, "natural-gradient step %g outside (0, 1]", gamma);
-    int rc = svgp_begin(th, who, true);
-    if (rc) return rc;
-    hipStream_t s = st();
-    const bool gauss = conj || vlik_kind == GPSO_LIK_GAUSSIAN;
-    svgp_pointwise(variance, p, mean_c, !gauss, gauss);  // (the Gaussian's a and t do not depend on fv)
-    svgp_adat(as<double>(sgM1), as<double>(vA));          // Lambda* in vA
-    launch_sgpr_gemv(s, as<double>(sgA), false, svn_at(kSvT), 1.0, vvec_at(kVgpH), n, npad, sg_n, sg_npad);  // h* = A t
-    double *mu_out = sgm_at(kSgMu), *S_out = as<double>(K);
-    if ((rc = vgp_natural_update(as<double>(svq_mu), as<double>(svq_S), gamma, mu_out, S_out))) return rc;
-    double* host;
-    if ((rc = vgp_finish(&host, Post::Svgp))) return rc;
-    HIPCHECK(hipMemcpyAsync(svq_mu.p, mu_out, (size_t)npad * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(hipMemcpyAsync(svq_S.p, S_out, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(ctx->wait(s));
-    return launch_status();
-  }
-
-  int svgp_natgrad(const Theta& th, double gamma) override { return svgp_step(th, gamma, false, "gpso_svgp_natgrad"); }
-
-  int svgp_init_q(const Theta& th, double s2) override {
-    if (s2 > 0.0) return svgp_step(th.with_lik(s2), 1.0, true, "gpso_svgp_init_q");
-    int rc = svgp_need_z("gpso_svgp_init_q");
-    if (rc || (rc = vgp_begin()) || (rc = svgp_q())) return rc;
-    svgp_prior();
-    HIPCHECK(ctx->wait(st()));
-    return launch_status();
-  }
-
-  int svgp_set_q(const double* mu, const double* S, int64_t m) override {
-    int rc = svgp_need_z("gpso_svgp_set_q");
-    if (rc) return rc;
-    if (m != n) return ctx->fail(GPSO_E_ARG, "q of %lld inducing values for %lld inducing points", (long long)m, (long long)n);
-    if ((rc = vgp_begin()) || (rc = svgp_q())) return rc;
-    hipStream_t s = st();
-    if (mu == nullptr || S == nullptr) {
-      svgp_prior();
-      HIPCHECK(ctx->wait(s));
-      return launch_status();
-    }
-    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
-    double* tmp = as<double>(getter_tmp);
-    HIPCHECK(hipMemcpyAsync(tmp, S, (size_t)n * n * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemsetAsync(svq_mu.p, 0, (size_t)npad * 8, s));
-    HIPCHECK(hipMemcpyAsync(svq_mu.p, mu, (size_t)n * 8, hipMemcpyHostToDevice, s));
-    launch_vgp_pad_identity(s, as<double>(svq_S), 0, npad, nullptr);
-    launch_convert_in<double>(s, tmp, as<double>(svq_S), n, n, npad);
-    launch_vgp_clean_lower(s, as<double>(svq_S), as<double>(svq_S), n, npad, 1.0);
-    HIPCHECK(hipStreamSynchronize(s));  // (the caller's host buffers are free again on return)
-    return launch_status();
-  }
-
-  int svgp_get_q(double* mu, double* S) override {
-    int rc = svgp_need_z("gpso_svgp_get_q");
-    if (rc || (rc = refuse_if_async("gpso_svgp_get_q")) || (rc = svgp_q())) return rc;
-    if ((rc = ensure(getter_tmp, (size_t)n * n * 8 + (size_t)n * 8))) return rc;
-    double* tmp = as<double>(getter_tmp);
-    hipStream_t s = st();
-    if (S) {
-      launch_convert_out<double>(s, as<double>(svq_S), npad, tmp, n, n, 0);
-      HIPCHECK(hipMemcpyAsync(S, tmp, (size_t)n * n * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (mu) HIPCHECK(hipMemcpyAsync(mu, svq_mu.p, (size_t)n * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(hipStreamSynchronize(s));
-    return launch_status();
-  }
-
-  // -ELBO = -sum VE + KL(q || N(0, I)) at fixed q and its gradient in the constrained theta: grad[n_ls + 3] = (ls...,
-  // variance, p, c).  With Abar = dELBO/dA = mu gm^T - (Sigma - I) A diag(a):  dELBO/dKuf = Lu^-T Abar = g + a' gm^T
-  // (g = Lu^-T (I - Sigma) A diag(a), a' = Lu^-T mu), contracted tile by tile; d(-ELBO)/dLu = tril(Lu^-T Abar A^T) =
-  // tril(T P + a' (A gm)^T) (T = Lu^-T (I - Sigma), P = A diag(a) A^T), taken to Kuu through the VGP's Cholesky backward
-  // pass and the fit's contraction; the k_diag term sum dVE/dv = -sum a / 2 joins the variance.
-  int svgp_elbo(const Theta& th, double* loss, double* grad) override {
-    return svgp_elbo_impl(th, loss, grad, nullptr, "gpso_svgp_elbo_u");
-  }
-
-  // grad_z (nullable, with grad): also d(-ELBO)/dZ [M * D] at fixed q (whitened: q stays valid while Z moves; the k_diag
-  // term does not depend on Z)
-  int svgp_elbo_impl(const Theta& th, double* loss, double* grad, double* grad_z, const char* who) {
-    const double variance = th.variance, p = th.lik, mean_c = th.mean_c;
-    int rc = svgp_begin(th, who, true);
-    if (rc) return rc;
-    if (grad_z && (rc = inducing_buffers())) return rc;
-    hipStream_t s = st();
-    double *Sq = as<double>(svq_S), *mu = as<double>(svq_mu), *A = as<double>(sgA), *Li = as<double>(linv);
-    svgp_pointwise(variance, p, mean_c, true, vlik_kind == GPSO_LIK_GAUSSIAN);
-    launch_vgp_rownorm(s, Sq, sgm_at(kSgRows), n, npad);
-    launch_svgp_sums(s, svn_at(kSvVe), svn_at(kSvDve), svn_at(kSvGm), svn_at(kSvA), sg_n, mu, sgm_at(kSgRows), Sq, n, npad,
-                     as<double>(sgsmall));
-    if (grad) {
-      double *P = as<double>(sgM1), *Sig = as<double>(sgM2), *T = as<double>(vC), *X1 = as<double>(vA), *X2 = as<double>(vB);
-      svgp_adat(P, as<double>(sgM3));                                   // P = A diag(a) A^T; D = A diag(a) in svD
-      launch_dgemm(s, Sq, false, Sq, true, Sig, npad, 1.0, 0.0);        // Sigma
-      launch_vgp_pad_identity(s, X2, 0, npad, nullptr);
-      launch_vgp_axpby(s, Sig, X2, npad * npad, -1.0, 1.0);             // I - Sigma
-      launch_dgemm(s, Li, true, X2, false, T, npad, 1.0, 0.0);          // T = Lu^-T (I - Sigma)
-      launch_dgemm_rect(s, T, npad, 1, as<double>(svD), sg_npad, 1, as<double>(svB), sg_npad, npad, sg_npad, npad, 1.0,
-                        0.0);                                           // g = T A diag(a)
-      launch_vgp_gemv(s, Li, true, mu, 0.0, 1.0, 0.0, nullptr, sgm_at(kSgAvec), n, npad);  // a' = Lu^-T mu
-      launch_sgpr_cross_grad(s, as<double>(svB), sgm_at(kSgAvec), svn_at(kSvGm), as<double>(xs64), as<double>(sgXs), n, npad,
-                             sg_n, sg_npad, dp, n_ls, ls_dev(), kp, as<double>(sggpart), as<double>(sgsmall) + kSgGradAt);
-      launch_sgpr_gemv(s, A, false, svn_at(kSvGm), -1.0, sgm_at(kSgAe), n, npad, sg_n, sg_npad);  // -A gm
-      launch_dgemm(s, T, false, P, false, X1, npad, 1.0, 0.0);          // T P
-      launch_vgp_lbar(s, X1, sgm_at(kSgAvec), sgm_at(kSgAe), n, npad, 1.0);  // Lbar = tril(T P + a' (A gm)^T)
-      launch_dgemm(s, as<double>(Lf), true, X1, false, T, npad, 1.0, 0.0);  // Lu^T Lbar
-      launch_vgp_phi_sym(s, T, X2, n, npad);                            // M = Phi + Phi^T
-      launch_dgemm(s, X2, false, Li, false, X1, npad, 1.0, 0.0);        // M Lu^-1
-      launch_dgemm(s, Li, true, X1, false, T, npad, 1.0, 0.0);          // 2 Kbar = Lu^-T M Lu^-1
-      HIPCHECK(hipMemsetAsync(sgm_at(kSgZero), 0, (size_t)npad * 8, s));
-      launch_gradient<double>(s, Li, sgm_at(kSgZero), as<double>(xs64), as<double>(xnorm64), n, npad, d, dp, n_ls, ls_dev(), kp,
-                              T, true, as<double>(gpart), as<double>(vsmall) + kVgpGradAt, nullptr);
-      // dELBO/dKuf = g + a' gm^T is of the ELBO, T = 2 d(-ELBO)/dKuu of the loss: -1 and +1 as in the SGPR
-      if (grad_z && (rc = launch_inducing_grad(s, as<double>(svB), sgm_at(kSgAvec), svn_at(kSvGm), T, as<double>(xs64),
-                                               as<double>(sgXs), n, npad, sg_n, sg_npad, d, dp, ls_dev(), kp, -1.0, 1.0,
-                                               as<double>(sgZpart), as<double>(sgZg))))
-        return rc;
-    }
-    double* host;
-    if ((rc = vgp_finish(&host, Post::Svgp))) return rc;
-    double guu[kGradMaxLs + 1];
-    for (int k = 0; k <= n_ls; ++k) guu[k] = grad ? host[kVgpGradAt + k] : 0.0;
-    double* h = ctx->pinned_scratch(kSgSmall);
-    if (!h) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    HIPCHECK(hipMemcpyAsync(h, sgsmall.p, kSgSmall * 8, hipMemcpyDeviceToHost, s));
-    if (grad && grad_z) HIPCHECK(hipMemcpyAsync(grad_z, sgZg.p, (size_t)n * d * 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(ctx->wait(s));
-    *loss = -h[0] + 0.5 * (h[5] + h[4] - (double)n - h[6]);
-    if (grad) {
-      // the Kuu contraction is of -ELBO, the cross one of the ELBO; k_diag: d(-ELBO)/dvariance = -sum dVE/dv = sum a / 2
-      for (int k = 0; k <= n_ls; ++k) grad[k] = guu[k] - h[kSgGradAt + k];
-      grad[n_ls] += 0.5 * h[3];
-      grad[n_ls + 1] = -h[1];
-      grad[n_ls + 2] = -h[2];
-    }
-    return GPSO_OK;
-  }
-
-  // install the predictive over the rows Z: the VGP's install with L := Lu and q := the SVGP's q (C = sqrt(1 + delta) R
-  // Lu^-1 with I - S S^T / (1 + delta) = R^T R, beta = Lu^-T mu, noise := the likelihood's variance + delta variance)
-  int svgp_posterior(const Theta& th, double* delta_out) override {
-    const double p = th.lik;
-    int rc = svgp_begin(th, "gpso_svgp_posterior", false);
-    if (rc) return rc;
-    hipStream_t s = st();
-    double *Li = as<double>(linv), *A = as<double>(vA), *B = as<double>(vB), *Cm = as<double>(vC);
-    launch_vgp_gemv(s, Li, true, as<double>(svq_mu), 0.0, 1.0, 0.0, nullptr, as<double>(alpha_f), n, npad);  // beta
-    double shift = 0.0;
-    if ((rc = vgp_shifted_root(&shift, false, as<double>(svq_S)))) return rc;  // G of J (I - Sigma / (1 + delta)) J
-    launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);                         // R
-    launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R Lu^-1
-    HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? p * p * vlik_df / (vlik_df - 2.0) : p;
-    if ((rc = set_theta(th.with_lik(noise + shift * th.variance)))) return rc;
-    if ((rc = install_predictive(Post::Svgp))) return rc;
-    if (delta_out) *delta_out = shift;
-    return GPSO_OK;
-  }
-
-  // ---- the sparse models at a moving Z (inducing.hip) ---------------------------------------------
-  // Z replaces the resident inducing rows IN PLACE: same M, the training data buffers untouched, no allocation, no upload
-  // of X or y, the SVGP's q kept (it is whitened: valid at any Z).  Everything that could refuse the call is checked
-  // before the rows are touched, so a rejected call leaves the context as it was.
-  int inducing_buffers() {
-    int rc = ensure(sgZpart, (size_t)(inducing_slices(npad, sg_npad) + 1) * npad * (dp + 1) * 8);
-    if (rc) return rc;
-    return ensure(sgZg, (size_t)n * d * 8);
-  }
-  int inducing_args(const char* who, const double* Z) {
-    int rc = sgpr_need_f64();
-    if (rc) return rc;
-    if (!res.sg_have || !res.sg_have_z)
-      return ctx->fail(GPSO_E_STATE, "%s needs the data and the inducing points: gpso_set_data, then gpso_sgpr_set_inducing or gpso_sgpr_select_inducing", who);
-    if ((rc = refuse_if_async(who))) return rc;
-    if (Z)
-      for (int64_t e = 0; e < n * (int64_t)d; ++e)
-        if (!std::isfinite(Z[e])) return ctx->fail(GPSO_E_ARG, "Z holds a non-finite value at element %lld", (long long)e);
-    return GPSO_OK;
-  }
-  int inducing_put(const double* Z) {
-    const size_t doubles = (size_t)n * d;
-    double* stage = doubles <= (1u << 17) ? ctx->pinned_stage(doubles) : nullptr;
-    if (stage) {
-      std::memcpy(stage, Z, doubles * 8);
-      HIPCHECK(hipMemcpyAsync(x64.p, stage, doubles * 8, hipMemcpyHostToDevice, st()));
-    } else {
-      HIPCHECK(hipMemcpyAsync(x64.p, Z, doubles * 8, hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipStreamSynchronize(st()));
-    }
-    if (Z != x_host.data()) std::memcpy(x_host.data(), Z, doubles * 8);
-    // (whatever was built on the old rows is gone; the data, q and the likelihood stay)
-    res.inducing_moved();
-    return GPSO_OK;
-  }
-
-  int sgpr_move_inducing(const double* Z) override {
-    if (!Z) return ctx->fail(GPSO_E_ARG, "Z must not be NULL");
-    int rc = inducing_args("gpso_sgpr_move_inducing", Z);
-    if (rc) return rc;
-    return inducing_put(Z);
-  }
-
-  int sgpr_bound_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) override {
-    int rc = inducing_args("gpso_sgpr_bound_uz", Z);
-    if (rc || (rc = theta_status(theta_refusal(th, d, true), "noise variance"))) return rc;
-    if (Z && (rc = inducing_put(Z))) return rc;
-    return sgpr_bound_impl(th, loss, grad, grad_z, "gpso_sgpr_bound_uz");
-  }
-
-  int svgp_elbo_z(const Theta& th, const double* Z, double* loss, double* grad, double* grad_z) override {
-    int rc = inducing_args("gpso_svgp_elbo_uz", Z);
-    if (rc || (rc = theta_status(theta_refusal(th, d, true), "likelihood parameter"))) return rc;
-    if (Z && (rc = inducing_put(Z))) return rc;
-    return svgp_elbo_impl(th, loss, grad, grad_z, "gpso_svgp_elbo_uz");
   }
 
   // ------------------------------------------------------------------------------------------
@@ -2515,9 +737,6 @@ struct EngineT : Engine {
   // defer (nullable): the caller's arg-max can finalise the leaves itself (launch_seg_argmax / launch_keyed_argmax with
   // a LeafFinalize) -- when the batch is ONE chunk the finalize launch is skipped and *defer says what to finalise;
   // otherwise defer->part_var stays NULL and the leaves are finalised here as before
-  // are the tile kernel's event pairs recorded, and how many were (collect_tile_ms).  open: the survivors of a screened call -- the
-  // pair's first event stands in front of the mean pass already, and the split launch's counters keep describing that pass
-  struct TileSpan { bool timed; bool open = false; int pairs = 0; };
   int ensure_tile_events(int pairs) {
     while ((int)ctx->tile_ev.size() < 2 * pairs) {
       hipEvent_t e;
@@ -2633,9 +852,9 @@ struct EngineT : Engine {
     return launch_status();  // (no host wait here: the kernel time is read after the call's final sync)
   }
 
-  int score_device_leaves(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb,
-                          double* mean_dev, double* var_dev, double* ucb_dev, TileSpan& span, const int64_t* m_live = nullptr,
-                          LeafFinalize* defer = nullptr, bool prepared = false) {
+  int score_device_leaves(const void* xs_dev, int xs_dtype, int64_t m, const AcqSpec& acq, bool want_ucb, double* mean_dev,
+                          double* var_dev, double* ucb_dev, TileSpan& span, const int64_t* m_live = nullptr,
+                          LeafFinalize* defer = nullptr, bool prepared = false) override {
     if (defer != nullptr) *defer = LeafFinalize{};
     if constexpr (kFloatPredict) {
       if (!gen_double()) {
@@ -2645,17 +864,6 @@ struct EngineT : Engine {
       }
     }
     return score_leaves_t<double>(xs_dev, xs_dtype, m, acq, want_ucb, mean_dev, var_dev, ucb_dev, span, m_live, defer, prepared);
-  }
-
-  // after the stream has been synchronised: total leaf-tile kernel time of the call
-  void collect_tile_ms(bool timed, int pairs) {
-    if (!timed) return;
-    float total = 0;
-    for (int i = 0; i < pairs; ++i) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ctx->tile_ev[2 * i], ctx->tile_ev[2 * i + 1]) == hipSuccess) total += ms;
-    }
-    ctx->last_ms[0] = total;
   }
 
   // ---- precision self-test (see fit.hip: selftest_kernel) ---------------------------------------
@@ -2777,11 +985,8 @@ struct EngineT : Engine {
     }
     return rc;
   }
-  int math_in_use() const {
-    return (bf16_usable() && res.linv_b == Copy::Valid && bf16_fits(gen_double())) ? res.math : GPSO_MATH_NATIVE;
-  }
   // called at the top of every predict-type entry point
-  int precision_gate() {
+  int precision_gate() override {
     int rc = decide_generation();
     if (rc) return rc;
     if (!can_selftest()) return GPSO_OK;
@@ -2814,68 +1019,6 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int stage_leaves(const void* xs, int xs_dtype, int xs_mem, int64_t m, const void** dev_ptr) {
-    if (xs_mem == GPSO_MEM_DEVICE) {
-      *dev_ptr = xs;
-      return GPSO_OK;
-    }
-    const size_t bytes = (size_t)m * d * ((xs_dtype == GPSO_F64) ? 8 : 4);
-    int rc = ensure(leaves_raw, bytes);
-    if (rc) return rc;
-    HIPCHECK(hipMemcpyAsync(leaves_raw.p, xs, bytes, hipMemcpyHostToDevice, st()));
-    *dev_ptr = leaves_raw.p;
-    return GPSO_OK;
-  }
-
-  // ---- the frame of a call that evaluates the resident posterior at points the caller gives: what
-  // such a call refuses about its points, who may read the dense double factor, what the call records, and the way from the
-  // caller's coordinates to scaled rows.  A new point call starts from these
-  static constexpr bool kDenseDouble = sizeof(TF) == 8;  // (GPSO_F64 and GPSO_MIXED contexts: predict_grad, joint, paths)
-  int check_points(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
-    if (m > 0 && !xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
-    if (xs_dtype != GPSO_F64 && xs_dtype != GPSO_F32) return ctx->fail(GPSO_E_ARG, "bad xs_dtype %d", xs_dtype);
-    if (xs_mem != GPSO_MEM_HOST && xs_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad xs_mem %d", xs_mem);
-    return GPSO_OK;
-  }
-  int need_dense_factor(const char* who) {
-    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
-    if (res.post == Post::Adopted || !res.chol_valid)
-      return ctx->fail(GPSO_E_STATE, "%s needs the dense factor of the posterior: an adopted posterior may have travelled without it", who);
-    return refuse_if_async(who);
-  }
-  // open and close: last_ms[1] is the stream time between the two, and the counts and the time describe the same call.  The
-  // open comes after the call's last refusal (a refused call leaves nothing in flight); the close records before it waits
-  int points_begin(hipStream_t* stream) {
-    hipStream_t s = *stream = st();
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[2], s));
-    return GPSO_OK;
-  }
-  static constexpr int64_t kNoCounts = -1;  // (gpso_paths_draw: no points, the counts stay the last point call's)
-  int points_end(hipStream_t s, int64_t m) {
-    if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[3], s));
-    HIPCHECK(ctx->wait(s));
-    if (m != kNoCounts) ctx->last_count[0] = ctx->last_count[1] = m;
-    float ms = 0;
-    if (ctx->timing && hipEventElapsedTime(&ms, ctx->ev[2], ctx->ev[3]) == hipSuccess) ctx->last_ms[1] = ms;
-    return GPSO_OK;
-  }
-  // rows off .. off + mc of the staged points (dtype xs_dtype) -> mpad scaled rows and their norms
-  template <typename TG>
-  void prep_points(hipStream_t s, const void* dev, int xs_dtype, int64_t off, int64_t mc, int64_t mpad, const int64_t* m_live, TG* ts,
-                   TG* norm) {
-    if (xs_dtype == GPSO_F64)
-      launch_prep_leaves<TG, double>(s, static_cast<const double*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), m_live, ts, norm);
-    else
-      launch_prep_leaves<TG, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), m_live, ts, norm);
-  }
-
-  int check_predict_args(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
-    if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
-    if (m < 0) return ctx->fail(GPSO_E_ARG, "negative leaf count");
-    int rc = check_points(xs, xs_dtype, xs_mem, m);
-    return rc ? rc : precision_gate();
-  }
-
   int predict(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var,
               int out_mem) override {
     return point_values(xs, xs_dtype, xs_mem, m, 0.0, false, mean, var, nullptr, out_mem);
@@ -2886,57 +1029,6 @@ struct EngineT : Engine {
   int acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean, double* var,
                  double* value, int out_mem) override {
     return point_values(xs, xs_dtype, xs_mem, m, acq, true, mean, var, value, out_mem);
-  }
-  // GPSO_ACQ_MES reads its maxima from this buffer (acq.hpp); no call of this context but the next set_maxima touches it
-  int set_maxima(const double* ystar, int k) override {
-    int rc = refuse_if_async("gpso_acq_set_maxima");
-    if (rc) return rc;
-    if (k < 0 || k > GPSO_ACQ_MAX_MAXIMA) return ctx->fail(GPSO_E_ARG, "k=%d maxima: 0..%d are kept", k, GPSO_ACQ_MAX_MAXIMA);
-    if (k > 0 && !ystar) return ctx->fail(GPSO_E_ARG, "ystar must not be NULL");
-    for (int i = 0; i < k; ++i)
-      if (!std::isfinite(ystar[i])) return ctx->fail(GPSO_E_ARG, "ystar[%d] is not finite", i);
-    if (k > 0) {
-      if ((rc = ensure(acq_maxima, GPSO_ACQ_MAX_MAXIMA * 8))) return rc;
-      HIPCHECK(hipStreamSynchronize(st()));  // (a blocking call's kernels are done; nothing reads the old set)
-      HIPCHECK(hipMemcpy(acq_maxima.p, ystar, (size_t)k * 8, hipMemcpyHostToDevice));
-      std::memcpy(maxima_host, ystar, (size_t)k * 8);
-    }
-    maxima_k = k;
-    maxima_dev = k > 0 ? as<double>(acq_maxima) : nullptr;
-    return GPSO_OK;
-  }
-  int max_logcdf(const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g, double* logcdf,
-                 int64_t* n_used) override {
-    int rc = refuse_if_async("gpso_max_logcdf");
-    if (rc) return rc;
-    if (!mean || !var || !y || !logcdf) return ctx->fail(GPSO_E_ARG, "mean, var, y and logcdf must not be NULL");
-    if (mem != GPSO_MEM_HOST && mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad mem %d", mem);
-    if (m < 1 || g < 1 || g > kMaxCdfThresholds) return ctx->fail(GPSO_E_ARG, "m=%lld, g=%d: m >= 1 and g in 1..%d", (long long)m, g, kMaxCdfThresholds);
-    if (var_sub != var_sub) return ctx->fail(GPSO_E_ARG, "var_sub is NaN");
-    for (int i = 0; i < g; ++i)
-      if (y[i] != y[i]) return ctx->fail(GPSO_E_ARG, "y[%d] is NaN", i);
-    const int64_t nblk = max_logcdf_blocks(m);
-    if ((rc = ensure(mcdf_work, (size_t)(nblk * kMaxCdfSlots + 2 * kMaxCdfSlots) * 8))) return rc;
-    double* partial = as<double>(mcdf_work);
-    double* y_dev = partial + nblk * kMaxCdfSlots;
-    double* out_dev = y_dev + kMaxCdfSlots;
-    const double *md = mean, *vd = var;
-    if (mem == GPSO_MEM_HOST) {
-      if ((rc = ensure(mcdf_in, (size_t)m * 16))) return rc;
-      HIPCHECK(hipMemcpyAsync(mcdf_in.p, mean, (size_t)m * 8, hipMemcpyHostToDevice, st()));
-      HIPCHECK(hipMemcpyAsync(as<double>(mcdf_in) + m, var, (size_t)m * 8, hipMemcpyHostToDevice, st()));
-      md = as<double>(mcdf_in);
-      vd = md + m;
-    }
-    HIPCHECK(hipMemcpyAsync(y_dev, y, (size_t)g * 8, hipMemcpyHostToDevice, st()));
-    launch_max_logcdf(st(), md, vd, m, var_sub, y_dev, g, partial, out_dev);
-    if ((rc = launch_status())) return rc;
-    double out[kMaxCdfSlots];
-    HIPCHECK(hipMemcpyAsync(out, out_dev, (size_t)(g + 1) * 8, hipMemcpyDeviceToHost, st()));
-    HIPCHECK(hipStreamSynchronize(st()));
-    std::memcpy(logcdf, out, (size_t)g * 8);
-    if (n_used) *n_used = (int64_t)out[g];
-    return GPSO_OK;
   }
   // the body of both: gpso_predict is gpso_predict_acq without the column (want_ucb false: nothing of it is allocated,
   // computed or copied) and with both of its outputs required
@@ -2978,477 +1070,12 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  // ---- mean, var and their gradients in the test points (predict_grad.hip).  Reads the dense fit-type
-  // factor, alpha_f, xs64 and the hyper block and writes buffers of its own only: the posterior, its packed copies and the
-  // self-test's verdicts stay as they are.  M is worked off in chunks of kPredictGradChunk, so the workspace is a few
-  // N_pad x chunk doubles whatever M is
-  int predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean, double* dvar,
-                   int out_mem) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs a GPSO_F64 or GPSO_MIXED context (the dense factor in double)");
-    ctx->tick_timing();
-    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs at least one test point (m=%lld)", (long long)m);
-    int rc = check_points(xs, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if (!mean && !var && !dmean && !dvar) return ctx->fail(GPSO_E_ARG, "mean, var, dmean and dvar are all NULL");
-    if ((rc = need_dense_factor("gpso_predict_grad"))) return rc;
-    const int64_t chunk = std::min<int64_t>(kPredictGradChunk, (m + 63) / 64 * 64);
-    if ((rc = ensure(pg_ts, (size_t)chunk * dp * 8))) return rc;
-    if ((rc = ensure(pg_norm, (size_t)chunk * 8))) return rc;
-    if ((rc = ensure(pg_work, predict_grad_workspace_doubles(npad, dp, chunk) * 8))) return rc;
-    const bool to_host = out_mem == GPSO_MEM_HOST;
-    double *md = mean, *vd = var, *dmd = dmean, *dvd = dvar;
-    if (to_host) {
-      if ((rc = ensure(pg_out, (size_t)m * (2 + 2 * (size_t)d) * 8))) return rc;
-      double* o = as<double>(pg_out);
-      md = mean ? o : nullptr;
-      vd = var ? o + m : nullptr;
-      dmd = dmean ? o + 2 * m : nullptr;
-      dvd = dvar ? o + 2 * m + m * d : nullptr;
-    }
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    PredictGradLaunch g;
-    g.C = as<double>(linv); g.alpha = as<double>(alpha_f); g.xs = as<double>(xs64); g.ls = ls_dev();
-    g.ts = as<double>(pg_ts); g.n = n; g.npad = npad; g.d = d; g.dp = dp; g.kp = kp; g.work = as<double>(pg_work);
-    for (int64_t off = 0; off < m; off += chunk) {
-      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
-      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pg_ts), as<double>(pg_norm));
-      g.m = mc;
-      g.mean = md ? md + off : nullptr;
-      g.var = vd ? vd + off : nullptr;
-      g.dmean = dmd ? dmd + off * d : nullptr;
-      g.dvar = dvd ? dvd + off * d : nullptr;
-      if (launch_predict_grad(s, g) != 0) return launch_status();
-      if ((rc = launch_status())) return rc;
-    }
-    if (to_host) {
-      if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-      if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-      if (dmean) HIPCHECK(hipMemcpyAsync(dmean, dmd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
-      if (dvar) HIPCHECK(hipMemcpyAsync(dvar, dvd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
-    }
-    return points_end(s, m);
-  }
-
-  // ---- the joint predictive (joint.hip).  Like gpso_predict_grad it reads the dense fit-type factor,
-  // alpha_f, xs64 and the hyper block and writes buffers of its own only.  joint_enqueue scales the test
-  // points, forms V with predict_grad.hip's apply stage and launches mean and Sigma (into `cov`, leading dimension ldc)
-  int joint_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean_dev,
-                    double* cov_dev, int64_t ldc, bool pad_identity) {
-    const int64_t mc = (m + 63) / 64 * 64;
-    int rc;
-    if ((rc = ensure(pj_ts, (size_t)mc * dp * 8))) return rc;
-    if ((rc = ensure(pj_norm, (size_t)mc * 8))) return rc;
-    if ((rc = ensure(pj_v, predict_grad_apply_workspace_doubles(npad, mc) * 8))) return rc;
-    if ((rc = ensure(pj_part, std::max<size_t>(joint_partial_doubles(n, m), 1) * 8))) return rc;
-    hipStream_t s = st();
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    prep_points<double>(s, dev, xs_dtype, 0, m, mc, nullptr, as<double>(pj_ts), as<double>(pj_norm));
-    PredictGradLaunch g;
-    g.C = as<double>(linv); g.xs = as<double>(xs64); g.ts = as<double>(pj_ts); g.n = n; g.npad = npad; g.m = m; g.d = d; g.dp = dp;
-    g.kp = kp; g.work = as<double>(pj_v);
-    if (launch_predict_grad_apply(s, g) != 0) return launch_status();
-    JointLaunch j;
-    j.V = as<double>(pj_v); j.ts = as<double>(pj_ts); j.alpha = as<double>(alpha_f); j.xs = as<double>(xs64);
-    j.n = n; j.npad = npad; j.m = m; j.dp = dp; j.kp = kp; j.diag_add = diag_add; j.part = as<double>(pj_part);
-    j.mean = mean_dev; j.cov = cov_dev; j.ldc = ldc; j.pad_identity = pad_identity;
-    (void)launch_joint(s, j);  // (a refused shape is on record: launch_status reports it)
-    return launch_status();
-  }
-  // the conditions gpso_predict_joint and gpso_sample_joint share with gpso_predict_grad
-  int joint_check(const char* what, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add) {
-    if (m < 1 || m > kPredictGradChunk)
-      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld test points (m=%lld): the joint covariance of more is out of scope", what,
-                       (long long)kPredictGradChunk, (long long)m);
-    int rc = check_points(xs, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if (!(diag_add == diag_add) || diag_add - diag_add != 0.0) return ctx->fail(GPSO_E_ARG, "diag_add must be finite");
-    return need_dense_factor(what);
-  }
-
-  int predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
-                    int out_mem) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_predict_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    ctx->tick_timing();
-    if (!cov) return ctx->fail(GPSO_E_ARG, "cov must not be NULL");
-    int rc = joint_check("gpso_predict_joint", xs, xs_dtype, xs_mem, m, diag_add);
-    if (rc) return rc;
-    const bool to_host = out_mem == GPSO_MEM_HOST;
-    double *md = mean, *cd = cov;
-    if (to_host) {
-      if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
-      if ((rc = ensure(pj_sigma, (size_t)m * m * 8))) return rc;
-      md = mean ? as<double>(pj_mu) : nullptr;
-      cd = as<double>(pj_sigma);
-    }
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, md, cd, m, false))) return rc;
-    if (to_host) {
-      if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)m * m * 8, hipMemcpyDeviceToHost, s));
-    }
-    return points_end(s, m);
-  }
-
-  // Sigma (identity on the padding up to a multiple of 128) -> launch_potrf as vgp_chol uses it -> F = mu 1^T + Z L^T ->
-  // the arg-max per draw.  One wait at the end; a failing pivot is reported then and the outputs hold nothing of use
-  int sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t ns,
-                   double* samples, int64_t* best_idx, double* best_val) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    ctx->tick_timing();
-    if (ns < 1 || ns > kJointMaxDraws)
-      return ctx->fail(GPSO_E_ARG, "gpso_sample_joint takes 1 to %lld draws a call (s=%lld)", (long long)kJointMaxDraws, (long long)ns);
-    if (!z) return ctx->fail(GPSO_E_ARG, "z must not be NULL");
-    if (!samples && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "samples, best_idx and best_val are all NULL");
-    int rc = joint_check("gpso_sample_joint", xs, xs_dtype, xs_mem, m, diag_add);
-    if (rc) return rc;
-    if (ns > ((int64_t)1 << 31) / m) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint: s * m above 2^31 (s=%lld, m=%lld)", (long long)ns, (long long)m);
-    const int64_t mpad = (m + kPadN - 1) / kPadN * kPadN;
-    const size_t mat = (size_t)mpad * mpad * 8;
-    for (DevBuf* b : {&pj_sigma, &pj_l, &pj_linv, &pj_cwork})
-      if ((rc = ensure(*b, mat))) return rc;
-    if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
-    if ((rc = ensure(pj_diag, (size_t)mpad * 8))) return rc;
-    if ((rc = ensure(pj_info, 256))) return rc;
-    if ((rc = ensure(pj_z, (size_t)ns * m * 8))) return rc;
-    if ((rc = ensure(pj_f, (size_t)ns * m * 8))) return rc;
-    if ((rc = ensure(pj_best, (size_t)ns * 16))) return rc;
-    int* info_host = reinterpret_cast<int*>(ctx->pinned_scratch(8));
-    if (!info_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    HIPCHECK(hipMemcpyAsync(pj_z.p, z, (size_t)ns * m * 8, hipMemcpyHostToDevice, s));
-    int* info = static_cast<int*>(pj_info.p);
-    launch_vgp_pad_identity(s, as<double>(pj_sigma), 0, mpad, info);  // (Sigma := I, info := INT_MAX; the tiles overwrite their part)
-    if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, as<double>(pj_mu), as<double>(pj_sigma), mpad, true)))
-      return rc;
-    HIPCHECK(hipMemsetAsync(pj_linv.p, 0, mat, s));
-    (void)launch_potrf<double>(s, as<double>(pj_sigma), as<double>(pj_l), as<double>(pj_linv), as<double>(pj_cwork), nullptr, m, mpad,
-                               as<double>(pj_diag), info, -1, nullptr);
-    HIPCHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
-    launch_joint_draw(s, as<double>(pj_l), mpad, as<double>(pj_z), as<double>(pj_mu), m, ns, as<double>(pj_f));
-    int64_t* bi = as<int64_t>(pj_best);
-    double* bv = reinterpret_cast<double*>(bi + ns);
-    if (best_idx || best_val) launch_joint_argmax(s, as<double>(pj_f), m, ns, bi, bv);
-    if ((rc = launch_status())) return rc;
-    if (samples) HIPCHECK(hipMemcpyAsync(samples, pj_f.p, (size_t)ns * m * 8, hipMemcpyDeviceToHost, s));
-    if (best_idx) HIPCHECK(hipMemcpyAsync(best_idx, bi, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
-    if (best_val) HIPCHECK(hipMemcpyAsync(best_val, bv, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
-    if ((rc = points_end(s, m))) return rc;
-    if (*info_host != INT_MAX)
-      return ctx->fail(GPSO_E_NOTPD, "gpso_sample_joint: Sigma + diag_add*I is not positive definite: Cholesky failed at pivot %d "
-                                     "(a larger diag_add -- jitter -- is the remedy)", *info_host);
-    return GPSO_OK;
-  }
-
-  // ---- pathwise posterior draws (paths.hip).  Both calls read the dense fit-type factor, the scaled
-  // rows, y, the per-point noise and the hyper block and write buffers of their own only: the posterior, its packed copies and
-  // the self-test's verdicts stay as they are.  gpso_paths_draw builds the set beside the resident one and swaps it in at the end
-  static bool all_finite(const double* v, size_t len) {
-    for (size_t i = 0; i < len; ++i)
-      if (!std::isfinite(v[i])) return false;
-    return true;
-  }
-  int paths_draw(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t ns) override {
-    return paths_draw_impl(false, "gpso_paths_draw", omega, phase, f, w, eps, ns);
-  }
-  // the draw of a variational posterior: v = beta + Lu^-T (Q eps - Lu^-1 Phi(Zr) w^T) from what the
-  // install left in Lf (Lu), alpha_f (beta) and vq_S / svq_S / sgM2 (Q); Lu^-1 is rebuilt from Lf into vA (vB: the copy of
-  // Lu with a unit diagonal on the padding, work: scratch) -- three buffers the install has finished with
-  int paths_draw_q(const double* omega, const double* phase, int64_t f, const double* w, const double* eps, int64_t ns) override {
-    return paths_draw_impl(true, "gpso_paths_draw_q", omega, phase, f, w, eps, ns);
-  }
-  int paths_draw_impl(bool variational, const char* who, const double* omega, const double* phase, int64_t f, const double* w,
-                      const double* eps, int64_t ns) {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "%s needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)", who);
-    ctx->tick_timing();
-    if (ns < 1 || ns > kPathsMaxDraws)
-      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld draws (s=%lld)", who, (long long)kPathsMaxDraws, (long long)ns);
-    if (f < 1 || f > kPathsMaxFeatures)
-      return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld features (f=%lld)", who, (long long)kPathsMaxFeatures, (long long)f);
-    if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
-    if (!variational) {
-      if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
-        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
-    } else {
-      if (res.post == Post::Fitted) return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q draws from a variational posterior: a fitted exact GP takes gpso_paths_draw");
-      if (!(res.variational() && res.chol_valid))
-        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q needs a posterior installed by gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior on this context");
-      // (at present implied by the line above: q_factors is set with the kind and cleared only where the kind is -- no call
-      // overwrites Lf, beta or the root of q and keeps the posterior.  The flag is for the first call that does)
-      if (!res.q_factors)
-        return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q: the install's factors (Lu, beta, the root of q) are not resident any more: install again");
-    }
-    int rc = refuse_if_async(who);
-    if (rc) return rc;
-    if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
-        (eps && !all_finite(eps, (size_t)ns * n)))
-      return ctx->fail(GPSO_E_ARG, "%s: omega, phase, w and eps must be finite", who);
-    const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
-    PathSet& nx = pth_next;
-    if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
-    if ((rc = ensure(nx.phase, (size_t)f16 * 8))) return rc;
-    if ((rc = ensure(nx.w, (size_t)ns * f16 * 8))) return rc;
-    if ((rc = ensure(nx.vt, (size_t)spad * npad * 8))) return rc;
-    if (eps && (rc = ensure(pth_eps, (size_t)ns * n * 8))) return rc;
-    if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
-    if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
-    if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
-    if (variational && (rc = ensure(pth_x, (size_t)n64 * spad * 8))) return rc;
-    // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
-    std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
-    for (int64_t j = 0; j < f; ++j) {
-      std::memcpy(&ho[(size_t)j * dp], omega + (size_t)j * d, (size_t)d * 8);
-      hp[(size_t)j] = phase[j];
-    }
-    for (int64_t r = 0; r < ns; ++r) std::memcpy(&hw[(size_t)r * f16], w + (size_t)r * f, (size_t)f * 8);
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    HIPCHECK(hipMemcpyAsync(nx.omega.p, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(nx.phase.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(hipMemcpyAsync(nx.w.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, s));
-    if (eps) HIPCHECK(hipMemcpyAsync(pth_eps.p, eps, (size_t)ns * n * 8, hipMemcpyHostToDevice, s));
-    PathsEvalLaunch g;  // Phi(X) w^T: the evaluation over the training rows, kernel part off
-    g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
-    g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
-    if (launch_paths_eval(s, g) != 0) return launch_status();
-    if (!variational) {
-      launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
-                         n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
-    } else {
-      launch_vgp_clean_lower(s, as<double>(Lf), as<double>(vB), n, npad, 1.0);
-      launch_trinv<double>(s, as<double>(vB), as<double>(vA), as<double>(work), npad);
-      const bool sgpr = res.post == Post::Sgpr;
-      const double* Q = sgpr ? as<double>(sgM2) : res.post == Post::Svgp ? as<double>(svq_S) : as<double>(vq_S);
-      launch_paths_solve_q(s, as<double>(vA), Q, sgpr, as<double>(alpha_f), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, n,
-                           npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(pth_x), as<double>(nx.vt));
-    }
-    if ((rc = launch_status())) return rc;
-    if ((rc = points_end(s, kNoCounts))) return rc;
-    nx.s = ns; nx.f = f; nx.ldw = f16;
-    std::swap(pth, pth_next);
-    res.paths_drawn();
-    return GPSO_OK;
-  }
-
-  // M is worked off in chunks of kPathsChunk: values of one chunk [S][chunk], copied out and / or reduced into the running
-  // winners per (draw, segment) before the next chunk overwrites them
-  int paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values, int out_mem,
-                 int64_t* best_idx, double* best_val) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    ctx->tick_timing();
-    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs at least one point (m=%lld)", (long long)m);
-    int rc = check_points(xs, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if (!values && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "values, best_idx and best_val are all NULL");
-    if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
-    if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "nseg=%d outside [1, 1024]", nseg);
-    if (!res.paths_valid)
-      return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
-    if ((rc = refuse_if_async("gpso_paths_eval"))) return rc;
-    std::vector<int64_t> so(nseg + 1);
-    if (seg_off) {
-      for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
-      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
-      for (int i = 0; i < nseg; ++i)
-        if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
-    } else {
-      if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
-      so[0] = 0;
-      so[1] = m;
-    }
-    const bool want_best = best_idx || best_val;
-    const int64_t ns = pth.s, chunk = std::min<int64_t>(kPathsChunk, (m + 63) / 64 * 64);
-    if ((rc = ensure(pe_ts, (size_t)chunk * dp * 8))) return rc;
-    if ((rc = ensure(pe_norm, (size_t)chunk * 8))) return rc;
-    if ((rc = ensure(pe_vals, (size_t)ns * chunk * 8))) return rc;
-    if ((rc = ensure(pe_seg, (size_t)(nseg + 1) * 8))) return rc;
-    if ((rc = ensure(pe_best, (size_t)ns * nseg * 16))) return rc;
-    int64_t* bi = as<int64_t>(pe_best);
-    double* bv = reinterpret_cast<double*>(bi + ns * nseg);
-    std::vector<int64_t> hi_(want_best ? (size_t)ns * nseg : 0);
-    std::vector<double> hv_(want_best ? (size_t)ns * nseg : 0);
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    if (want_best) {
-      HIPCHECK(hipMemcpyAsync(pe_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
-      HIPCHECK(hipMemsetAsync(pe_best.p, 0xFF, (size_t)ns * nseg * 16, s));  // (index -1: no winner yet; the value a NaN)
-    }
-    PathsEvalLaunch g;
-    g.ts = as<double>(pe_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
-    g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
-    g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.out = as<double>(pe_vals); g.ldo = chunk;
-    for (int64_t off = 0; off < m; off += chunk) {
-      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
-      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pe_ts), as<double>(pe_norm));
-      g.m = mc;
-      if (launch_paths_eval(s, g) != 0) return launch_status();
-      if ((rc = launch_status())) return rc;
-      if (values)
-        HIPCHECK(hipMemcpy2DAsync(values + off, (size_t)m * 8, pe_vals.p, (size_t)chunk * 8, (size_t)mc * 8, (size_t)ns,
-                                  out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-      if (want_best) launch_paths_argmax(s, as<double>(pe_vals), chunk, off, mc, as<int64_t>(pe_seg), nseg, ns, bi, bv);
-    }
-    if (want_best) {
-      if ((rc = launch_status())) return rc;
-      HIPCHECK(hipMemcpyAsync(hi_.data(), bi, hi_.size() * 8, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipMemcpyAsync(hv_.data(), bv, hv_.size() * 8, hipMemcpyDeviceToHost, s));
-    }
-    if ((rc = points_end(s, m))) return rc;
-    for (size_t e = 0; e < hi_.size(); ++e) {  // indices relative to the segment start; an empty segment: -1 and a NaN
-      if (best_idx) best_idx[e] = hi_[e] < 0 ? -1 : hi_[e] - so[e % nseg];
-      if (best_val) best_val[e] = hv_[e];
-    }
-    return GPSO_OK;
-  }
-  void paths_info(int64_t* s_out, int64_t* f_out) const override {
-    *s_out = res.paths_valid ? pth.s : 0;
-    *f_out = res.paths_valid ? pth.f : 0;
-  }
-
-  // ---- latent cross-covariance and greedy batch selection (batch.hip).  Both calls read the dense
-  // fit-type factor, the scaled rows and the hyper block -- gpso_best_batch also whatever gpso_acq_values reads -- and write
-  // buffers of their own only: the posterior, its packed copies, the self-test's verdicts and a resident path set stay as they are
-  int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    ctx->tick_timing();
-    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov needs at least one point (m=%lld)", (long long)m);
-    if (b < 1 || b > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov takes 1 to %d points b (b=%d)", kBatchMaxPicks, b);
-    int rc = check_points(xa, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if (!xb || !cov) return ctx->fail(GPSO_E_ARG, "xb and cov must not be NULL");
-    if ((rc = need_dense_factor("gpso_cross_cov"))) return rc;
-    const int64_t chunk = std::min<int64_t>(kBatchChunk, (m + 63) / 64 * 64);
-    if ((rc = ensure(cc_ts, (size_t)chunk * dp * 8))) return rc;
-    if ((rc = ensure(cc_norm, (size_t)chunk * 8))) return rc;
-    if ((rc = ensure(cc_braw, (size_t)kBatchMaxPicks * d * 8))) return rc;
-    if ((rc = ensure(cc_tb, (size_t)kBatchMaxPicks * dp * 8))) return rc;
-    if ((rc = ensure(cc_bnorm, (size_t)kBatchMaxPicks * 8))) return rc;
-    if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, b) * 8))) return rc;
-    if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
-    const bool to_host = out_mem == GPSO_MEM_HOST;
-    double* cd = cov;
-    if (to_host) {
-      if ((rc = ensure(cc_out, (size_t)b * m * 8))) return rc;
-      cd = as<double>(cc_out);
-    }
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xa, xs_dtype, xs_mem, m, &dev))) return rc;
-    HIPCHECK(hipMemcpyAsync(cc_braw.p, xb, (size_t)b * d * 8, hipMemcpyHostToDevice, s));
-    prep_points<double>(s, cc_braw.p, GPSO_F64, 0, b, kBatchMaxPicks, nullptr, as<double>(cc_tb), as<double>(cc_bnorm));
-    BatchPickLaunch pk;
-    pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(cc_tb); pk.n = n; pk.npad = npad; pk.b = b; pk.dp = dp; pk.kp = kp;
-    pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + (size_t)b * npad; pk.W = pk.U + (size_t)b * npad; pk.lv = as<double>(cc_lv);
-    if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
-    BatchColLaunch g;
-    g.ts = as<double>(cc_ts); g.tnorm = as<double>(cc_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.bnorm = as<double>(cc_bnorm);
-    g.n = n; g.npad = npad; g.b = b; g.dp = dp; g.kp = kp; g.ldc = m;
-    for (int64_t off = 0; off < m; off += chunk) {
-      const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
-      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(cc_ts), as<double>(cc_norm));
-      g.m = mc;
-      g.cov = cd + off;
-      if (launch_batch_cross(s, g) != 0) return launch_status();
-      if ((rc = launch_status())) return rc;
-    }
-    if (to_host) HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)b * m * 8, hipMemcpyDeviceToHost, s));
-    return points_end(s, m);
-  }
-
-  // Round 0 is gpso_acq_values on the batch (the context's predict path: its bits); every later round is double arithmetic
-  // on top: pick vectors, one column launch, one finish launch.  All rounds are enqueued back to back, the picks stay on
-  // the device, one wait at the end
-  int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx,
-                 double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) override {
-    if constexpr (!kDenseDouble) return ctx->fail(GPSO_E_ARG, "gpso_best_batch needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)");
-    ctx->tick_timing();
-    if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_best_batch needs at least one leaf (m=%lld)", (long long)m);
-    if (q < 1 || q > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_best_batch picks 1 to %d leaves (q=%d)", kBatchMaxPicks, q);
-    if (m > kBatchMaxCells / q) return ctx->fail(GPSO_E_ARG, "gpso_best_batch: q * m above 2^27 (q=%d, m=%lld)", q, (long long)m);
-    if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
-    if (!idx || !n_picked) return ctx->fail(GPSO_E_ARG, "idx and n_picked must not be NULL");
-    if (!(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0) return ctx->fail(GPSO_E_ARG, "obs_noise must be finite and not negative");
-    int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
-    if (rc) return rc;
-    if ((rc = need_dense_factor("gpso_best_batch"))) return rc;
-    const int64_t mall = (m + 63) / 64 * 64, nblk = batch_round_blocks(m);
-    if ((rc = ensure(bb_ts, (size_t)mall * dp * 8))) return rc;
-    if ((rc = ensure(bb_norm, (size_t)mall * 8))) return rc;
-    if ((rc = ensure(bb_mean, (size_t)m * 8))) return rc;
-    if ((rc = ensure(bb_s2, (size_t)m * 8))) return rc;
-    if ((rc = ensure(bb_val, (size_t)m * 8))) return rc;
-    if ((rc = ensure(bb_g, (size_t)q * m * 8))) return rc;
-    if ((rc = ensure(bb_live, (size_t)m))) return rc;
-    if ((rc = ensure(bb_bmax, (size_t)nblk * 16))) return rc;
-    if ((rc = ensure(bb_state, sizeof(BatchState)))) return rc;
-    if ((rc = ensure(bb_tp, (size_t)kMaxD * 8))) return rc;
-    if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, 1) * 8))) return rc;
-    if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
-    BatchState* host = reinterpret_cast<BatchState*>(ctx->pinned_scratch(sizeof(BatchState) / 8 + 1));
-    if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
-    hipStream_t s;
-    if ((rc = points_begin(&s))) return rc;
-    const void* dev = nullptr;
-    if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
-    BatchState* state = static_cast<BatchState*>(bb_state.p);
-    HIPCHECK(hipMemsetAsync(state, 0, sizeof(BatchState), s));
-    double *md = as<double>(bb_mean), *s2d = as<double>(bb_s2), *vald = as<double>(bb_val), *G = as<double>(bb_g);
-    double* bmax_v = as<double>(bb_bmax);
-    int64_t* bmax_i = reinterpret_cast<int64_t*>(bmax_v + nblk);
-    unsigned char* live = static_cast<unsigned char*>(bb_live.p);
-    TileSpan span{ctx->timing};
-    if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, s2d, vald, span))) return rc;
-    for (int64_t off = 0; off < m; off += kBatchChunk) {
-      const int64_t mc = std::min(kBatchChunk, m - off), mpad = (mc + 63) / 64 * 64;
-      prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(bb_ts) + off * dp, as<double>(bb_norm) + off);
-    }
-    launch_batch_init(s, vald, m, live, bmax_v, bmax_i);
-    BatchPickLaunch pk;
-    pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(bb_tp); pk.n = n; pk.npad = npad; pk.b = 1; pk.dp = dp; pk.kp = kp;
-    pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + npad; pk.W = pk.U + npad; pk.lv = as<double>(cc_lv); pk.st = state; pk.obs_noise = obs_noise;
-    BatchColLaunch g;
-    g.ts = as<double>(bb_ts); g.tnorm = as<double>(bb_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.n = n; g.npad = npad; g.m = m;
-    g.dp = dp; g.kp = kp; g.st = state; g.G = G; g.s2 = s2d; g.mean = md; g.live = live; g.acq = acq; g.bmax_v = bmax_v; g.bmax_i = bmax_i;
-    for (int t = 0; t < q; ++t) {
-      launch_batch_finish(s, state, t, bmax_v, bmax_i, t == 0 ? batch_init_blocks(m) : nblk, g.ts, dp, md, s2d, G, m, live, as<double>(bb_tp));
-      const bool last = t == q - 1;
-      if (last && !var_after) break;
-      pk.t = g.t = t;
-      g.rank = !last;
-      if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
-      if (launch_batch_round(s, g) != 0) return launch_status();
-    }
-    if ((rc = launch_status())) return rc;
-    HIPCHECK(hipMemcpyAsync(host, state, sizeof(BatchState), hipMemcpyDeviceToHost, s));
-    if (var_after)
-      HIPCHECK(hipMemcpyAsync(var_after, s2d, (size_t)m * 8, out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
-    if ((rc = points_end(s, m))) return rc;
-    collect_tile_ms(span.timed, span.pairs);
-    *n_picked = host->n_picked;
-    for (int t = 0; t < host->n_picked; ++t) {
-      idx[t] = host->idx[t];
-      if (mean) mean[t] = host->mean[t];
-      if (var) var[t] = host->var[t];
-      if (value) value[t] = host->value[t];
-    }
-    return GPSO_OK;
-  }
-
   // ---- best-UCB sequencing: enqueue the local work (winners stay on the device, no host wait) ->
   //      [multi-GPU: all-gather + fold] -> one read-back ------------------------------------------------
   // ---- one-launch small calls (predict.hip: leaf_tiles_v2_one_kernel) -------------------------------------------------
   // Applies when the native tile kernel runs this posterior with ONE row block (N_pad = 128 or 256) and the batch is
   // small.  Returns 0 when the call was enqueued (records on their way to ovals and pinned host memory), 2 when it does
   // not apply -- the caller goes on with the next-best sequence --, or a negative status.  mode: finish_best's read-back
-  DevBuf one_ctl, one_partial, one_ppos;
   template <typename TG>
   int try_one_launch_t(const BestPlan& plan, BestCall& call, OneLaunch& one, int64_t total, int nseg, const AcqSpec& acq, int mode) {
     if (acq.kind == GPSO_ACQ_MES) return 2;  // (the tile kernel's epilogue keeps the maps it had: MES takes the next-best sequence)
@@ -3620,19 +1247,6 @@ struct EngineT : Engine {
       info[0] = (double)ctl[1];
       std::memcpy(&info[1], &ctl[2], 8);
       info[2] = (double)screen_cap_rows((m + kLeafPad - 1) / kLeafPad * kLeafPad);
-    }
-    return GPSO_OK;
-  }
-  // gpso_screen_list: the compact list the last gpso_screen_probe left -- the survivors' indices and raw rows
-  int screen_list(int64_t max_rows, int64_t* key, float* rows, int64_t* live) override {
-    if (!probe_listed) return ctx->fail(GPSO_E_STATE, "gpso_screen_list: no gpso_screen_probe on this context yet");
-    if (max_rows < 0 || (max_rows > 0 && (!key || !rows))) return ctx->fail(GPSO_E_ARG, "gpso_screen_list: NULL output or max_rows < 0");
-    const int64_t have = (int64_t)probe_key.size();
-    if (live) *live = have;
-    const int64_t rows_n = std::min(max_rows, have);
-    if (rows_n > 0) {
-      std::memcpy(key, probe_key.data(), (size_t)rows_n * 8);
-      std::memcpy(rows, probe_rows.data(), (size_t)rows_n * d * 4);
     }
     return GPSO_OK;
   }
@@ -4615,19 +2229,9 @@ struct EngineT : Engine {
     if (nbytes) *nbytes = (int64_t)bytes;
     return GPSO_OK;
   }
-  // where a span (offset, nbytes) announced by a peer lands in THIS context's arena (after gpso_alloc_posterior)
-  int posterior_span_at(int64_t offset, int64_t nbytes, void** ptr) override {
-    if (arena.p == nullptr) return ctx->fail(GPSO_E_STATE, "gpso_alloc_posterior first");
-    if (offset < 0 || nbytes <= 0 || offset % 256 != 0 || (size_t)offset + (size_t)nbytes > arena.bytes)
-      return ctx->fail(GPSO_E_ARG, "posterior span [%lld, +%lld) does not fit this context's arena of %zu bytes (different "
-                       "dtype / shape on the sender?)", (long long)offset, (long long)nbytes, arena.bytes);
-    *ptr = static_cast<char*>(arena.p) + offset;
-    return GPSO_OK;
-  }
   // 64-bit fingerprint of the predict-ready posterior (the buffers gpso_posterior_buffers lists, the parts in use):
   // two contexts that ran the same deterministic fit hold the same value -- what a group that REPLICATES the fit on
   // every rank compares instead of broadcasting ("measure both")
-  DevBuf hash_out;
   int posterior_hash(uint64_t* out) override {
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident");
     int rc = settle_and_flag(true);
@@ -4658,15 +2262,6 @@ struct EngineT : Engine {
     return GPSO_OK;
   }
 
-  int alloc_posterior(int64_t n_, int d_) override {
-    int rc = refuse_if_async("gpso_alloc_posterior");
-    if (rc) return rc;
-    rc = shape(n_, d_);
-    if (rc) return rc;
-    res.shape_allocated();
-    return GPSO_OK;
-  }
-
   int adopt_posterior() override {
     if (npad == 0) return ctx->fail(GPSO_E_STATE, "gpso_alloc_posterior first");
     double* h = ctx->pinned_scratch(kHyperHeader + kMaxD);
@@ -4692,6 +2287,7 @@ struct EngineT : Engine {
 };
 
 }  // namespace
+}  // namespace gpso::host
 
 // ---- the optimiser's vector u -> theta -> the engine, and the gradient back (theta.hpp) --------------------------------------
 // theta (theta.hpp) from the optimiser's vector u, or why not.  lik_floor: what stands in front of the softplus of slot n_ls + 1

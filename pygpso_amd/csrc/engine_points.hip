@@ -1,0 +1,517 @@
+// EngineCore's calls that evaluate the resident posterior at points the caller gives and read the dense double factor for it
+// (DESIGN.md sections 7h-7n: predict_grad, the joint predictive, pathwise draws, cross-covariance, batch selection), and the two
+// untyped calls of max-value entropy search.  No typed buffer is touched here: a float fit is refused by need_double_fit.
+#include <climits>
+#include <vector>
+
+#include "engine_core.hpp"
+
+namespace gpso::host {
+
+// GPSO_ACQ_MES reads its maxima from this buffer (acq.hpp); no call of this context but the next set_maxima touches it
+int EngineCore::set_maxima(const double* ystar, int k) {
+  int rc = refuse_if_async("gpso_acq_set_maxima");
+  if (rc) return rc;
+  if (k < 0 || k > GPSO_ACQ_MAX_MAXIMA) return ctx->fail(GPSO_E_ARG, "k=%d maxima: 0..%d are kept", k, GPSO_ACQ_MAX_MAXIMA);
+  if (k > 0 && !ystar) return ctx->fail(GPSO_E_ARG, "ystar must not be NULL");
+  for (int i = 0; i < k; ++i)
+    if (!std::isfinite(ystar[i])) return ctx->fail(GPSO_E_ARG, "ystar[%d] is not finite", i);
+  if (k > 0) {
+    if ((rc = ensure(acq_maxima, GPSO_ACQ_MAX_MAXIMA * 8))) return rc;
+    HIPCHECK(hipStreamSynchronize(st()));  // (a blocking call's kernels are done; nothing reads the old set)
+    HIPCHECK(hipMemcpy(acq_maxima.p, ystar, (size_t)k * 8, hipMemcpyHostToDevice));
+    std::memcpy(maxima_host, ystar, (size_t)k * 8);
+  }
+  maxima_k = k;
+  maxima_dev = k > 0 ? as<double>(acq_maxima) : nullptr;
+  return GPSO_OK;
+}
+int EngineCore::max_logcdf(const double* mean, const double* var, int mem, int64_t m, double var_sub, const double* y, int g, double* logcdf,
+               int64_t* n_used) {
+  int rc = refuse_if_async("gpso_max_logcdf");
+  if (rc) return rc;
+  if (!mean || !var || !y || !logcdf) return ctx->fail(GPSO_E_ARG, "mean, var, y and logcdf must not be NULL");
+  if (mem != GPSO_MEM_HOST && mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad mem %d", mem);
+  if (m < 1 || g < 1 || g > kMaxCdfThresholds) return ctx->fail(GPSO_E_ARG, "m=%lld, g=%d: m >= 1 and g in 1..%d", (long long)m, g, kMaxCdfThresholds);
+  if (var_sub != var_sub) return ctx->fail(GPSO_E_ARG, "var_sub is NaN");
+  for (int i = 0; i < g; ++i)
+    if (y[i] != y[i]) return ctx->fail(GPSO_E_ARG, "y[%d] is NaN", i);
+  const int64_t nblk = max_logcdf_blocks(m);
+  if ((rc = ensure(mcdf_work, (size_t)(nblk * kMaxCdfSlots + 2 * kMaxCdfSlots) * 8))) return rc;
+  double* partial = as<double>(mcdf_work);
+  double* y_dev = partial + nblk * kMaxCdfSlots;
+  double* out_dev = y_dev + kMaxCdfSlots;
+  const double *md = mean, *vd = var;
+  if (mem == GPSO_MEM_HOST) {
+    if ((rc = ensure(mcdf_in, (size_t)m * 16))) return rc;
+    HIPCHECK(hipMemcpyAsync(mcdf_in.p, mean, (size_t)m * 8, hipMemcpyHostToDevice, st()));
+    HIPCHECK(hipMemcpyAsync(as<double>(mcdf_in) + m, var, (size_t)m * 8, hipMemcpyHostToDevice, st()));
+    md = as<double>(mcdf_in);
+    vd = md + m;
+  }
+  HIPCHECK(hipMemcpyAsync(y_dev, y, (size_t)g * 8, hipMemcpyHostToDevice, st()));
+  launch_max_logcdf(st(), md, vd, m, var_sub, y_dev, g, partial, out_dev);
+  if ((rc = launch_status())) return rc;
+  double out[kMaxCdfSlots];
+  HIPCHECK(hipMemcpyAsync(out, out_dev, (size_t)(g + 1) * 8, hipMemcpyDeviceToHost, st()));
+  HIPCHECK(hipStreamSynchronize(st()));
+  std::memcpy(logcdf, out, (size_t)g * 8);
+  if (n_used) *n_used = (int64_t)out[g];
+  return GPSO_OK;
+}
+
+// ---- mean, var and their gradients in the test points (predict_grad.hip).  Reads the dense fit-type
+// factor, alpha_f, xs64 and the hyper block and writes buffers of its own only: the posterior, its packed copies and the
+// self-test's verdicts stay as they are.  M is worked off in chunks of kPredictGradChunk, so the workspace is a few
+// N_pad x chunk doubles whatever M is
+int EngineCore::predict_grad(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* mean, double* var, double* dmean, double* dvar,
+                 int out_mem) {
+  if (int rcd = need_double_fit("gpso_predict_grad needs a GPSO_F64 or GPSO_MIXED context (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_predict_grad needs at least one test point (m=%lld)", (long long)m);
+  int rc = check_points(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if (!mean && !var && !dmean && !dvar) return ctx->fail(GPSO_E_ARG, "mean, var, dmean and dvar are all NULL");
+  if ((rc = need_dense_factor("gpso_predict_grad"))) return rc;
+  const int64_t chunk = std::min<int64_t>(kPredictGradChunk, (m + 63) / 64 * 64);
+  if ((rc = ensure(pg_ts, (size_t)chunk * dp * 8))) return rc;
+  if ((rc = ensure(pg_norm, (size_t)chunk * 8))) return rc;
+  if ((rc = ensure(pg_work, predict_grad_workspace_doubles(npad, dp, chunk) * 8))) return rc;
+  const bool to_host = out_mem == GPSO_MEM_HOST;
+  double *md = mean, *vd = var, *dmd = dmean, *dvd = dvar;
+  if (to_host) {
+    if ((rc = ensure(pg_out, (size_t)m * (2 + 2 * (size_t)d) * 8))) return rc;
+    double* o = as<double>(pg_out);
+    md = mean ? o : nullptr;
+    vd = var ? o + m : nullptr;
+    dmd = dmean ? o + 2 * m : nullptr;
+    dvd = dvar ? o + 2 * m + m * d : nullptr;
+  }
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  PredictGradLaunch g;
+  g.C = as<double>(linv); g.alpha = as<double>(alpha_f); g.xs = as<double>(xs64); g.ls = ls_dev();
+  g.ts = as<double>(pg_ts); g.n = n; g.npad = npad; g.d = d; g.dp = dp; g.kp = kp; g.work = as<double>(pg_work);
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+    prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pg_ts), as<double>(pg_norm));
+    g.m = mc;
+    g.mean = md ? md + off : nullptr;
+    g.var = vd ? vd + off : nullptr;
+    g.dmean = dmd ? dmd + off * d : nullptr;
+    g.dvar = dvd ? dvd + off * d : nullptr;
+    if (launch_predict_grad(s, g) != 0) return launch_status();
+    if ((rc = launch_status())) return rc;
+  }
+  if (to_host) {
+    if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    if (var) HIPCHECK(hipMemcpyAsync(var, vd, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    if (dmean) HIPCHECK(hipMemcpyAsync(dmean, dmd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+    if (dvar) HIPCHECK(hipMemcpyAsync(dvar, dvd, (size_t)m * d * 8, hipMemcpyDeviceToHost, s));
+  }
+  return points_end(s, m);
+}
+
+// ---- the joint predictive (joint.hip).  Like gpso_predict_grad it reads the dense fit-type factor,
+// alpha_f, xs64 and the hyper block and writes buffers of its own only.  joint_enqueue scales the test
+// points, forms V with predict_grad.hip's apply stage and launches mean and Sigma (into `cov`, leading dimension ldc)
+int EngineCore::joint_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean_dev,
+                  double* cov_dev, int64_t ldc, bool pad_identity) {
+  const int64_t mc = (m + 63) / 64 * 64;
+  int rc;
+  if ((rc = ensure(pj_ts, (size_t)mc * dp * 8))) return rc;
+  if ((rc = ensure(pj_norm, (size_t)mc * 8))) return rc;
+  if ((rc = ensure(pj_v, predict_grad_apply_workspace_doubles(npad, mc) * 8))) return rc;
+  if ((rc = ensure(pj_part, std::max<size_t>(joint_partial_doubles(n, m), 1) * 8))) return rc;
+  hipStream_t s = st();
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  prep_points<double>(s, dev, xs_dtype, 0, m, mc, nullptr, as<double>(pj_ts), as<double>(pj_norm));
+  PredictGradLaunch g;
+  g.C = as<double>(linv); g.xs = as<double>(xs64); g.ts = as<double>(pj_ts); g.n = n; g.npad = npad; g.m = m; g.d = d; g.dp = dp;
+  g.kp = kp; g.work = as<double>(pj_v);
+  if (launch_predict_grad_apply(s, g) != 0) return launch_status();
+  JointLaunch j;
+  j.V = as<double>(pj_v); j.ts = as<double>(pj_ts); j.alpha = as<double>(alpha_f); j.xs = as<double>(xs64);
+  j.n = n; j.npad = npad; j.m = m; j.dp = dp; j.kp = kp; j.diag_add = diag_add; j.part = as<double>(pj_part);
+  j.mean = mean_dev; j.cov = cov_dev; j.ldc = ldc; j.pad_identity = pad_identity;
+  (void)launch_joint(s, j);  // (a refused shape is on record: launch_status reports it)
+  return launch_status();
+}
+// the conditions gpso_predict_joint and gpso_sample_joint share with gpso_predict_grad
+int EngineCore::joint_check(const char* what, const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add) {
+  if (m < 1 || m > kPredictGradChunk)
+    return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld test points (m=%lld): the joint covariance of more is out of scope", what,
+                     (long long)kPredictGradChunk, (long long)m);
+  int rc = check_points(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if (!(diag_add == diag_add) || diag_add - diag_add != 0.0) return ctx->fail(GPSO_E_ARG, "diag_add must be finite");
+  return need_dense_factor(what);
+}
+
+int EngineCore::predict_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, double* mean, double* cov,
+                  int out_mem) {
+  if (int rcd = need_double_fit("gpso_predict_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (!cov) return ctx->fail(GPSO_E_ARG, "cov must not be NULL");
+  int rc = joint_check("gpso_predict_joint", xs, xs_dtype, xs_mem, m, diag_add);
+  if (rc) return rc;
+  const bool to_host = out_mem == GPSO_MEM_HOST;
+  double *md = mean, *cd = cov;
+  if (to_host) {
+    if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+    if ((rc = ensure(pj_sigma, (size_t)m * m * 8))) return rc;
+    md = mean ? as<double>(pj_mu) : nullptr;
+    cd = as<double>(pj_sigma);
+  }
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, md, cd, m, false))) return rc;
+  if (to_host) {
+    if (mean) HIPCHECK(hipMemcpyAsync(mean, md, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)m * m * 8, hipMemcpyDeviceToHost, s));
+  }
+  return points_end(s, m);
+}
+
+// Sigma (identity on the padding up to a multiple of 128) -> launch_potrf as vgp_chol uses it -> F = mu 1^T + Z L^T ->
+// the arg-max per draw.  One wait at the end; a failing pivot is reported then and the outputs hold nothing of use
+int EngineCore::sample_joint(const void* xs, int xs_dtype, int xs_mem, int64_t m, double diag_add, const double* z, int64_t ns,
+                 double* samples, int64_t* best_idx, double* best_val) {
+  if (int rcd = need_double_fit("gpso_sample_joint needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (ns < 1 || ns > kJointMaxDraws)
+    return ctx->fail(GPSO_E_ARG, "gpso_sample_joint takes 1 to %lld draws a call (s=%lld)", (long long)kJointMaxDraws, (long long)ns);
+  if (!z) return ctx->fail(GPSO_E_ARG, "z must not be NULL");
+  if (!samples && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "samples, best_idx and best_val are all NULL");
+  int rc = joint_check("gpso_sample_joint", xs, xs_dtype, xs_mem, m, diag_add);
+  if (rc) return rc;
+  if (ns > ((int64_t)1 << 31) / m) return ctx->fail(GPSO_E_ARG, "gpso_sample_joint: s * m above 2^31 (s=%lld, m=%lld)", (long long)ns, (long long)m);
+  const int64_t mpad = (m + kPadN - 1) / kPadN * kPadN;
+  const size_t mat = (size_t)mpad * mpad * 8;
+  for (DevBuf* b : {&pj_sigma, &pj_l, &pj_linv, &pj_cwork})
+    if ((rc = ensure(*b, mat))) return rc;
+  if ((rc = ensure(pj_mu, (size_t)m * 8))) return rc;
+  if ((rc = ensure(pj_diag, (size_t)mpad * 8))) return rc;
+  if ((rc = ensure(pj_info, 256))) return rc;
+  if ((rc = ensure(pj_z, (size_t)ns * m * 8))) return rc;
+  if ((rc = ensure(pj_f, (size_t)ns * m * 8))) return rc;
+  if ((rc = ensure(pj_best, (size_t)ns * 16))) return rc;
+  int* info_host = reinterpret_cast<int*>(ctx->pinned_scratch(8));
+  if (!info_host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  HIPCHECK(hipMemcpyAsync(pj_z.p, z, (size_t)ns * m * 8, hipMemcpyHostToDevice, s));
+  int* info = static_cast<int*>(pj_info.p);
+  launch_vgp_pad_identity(s, as<double>(pj_sigma), 0, mpad, info);  // (Sigma := I, info := INT_MAX; the tiles overwrite their part)
+  if ((rc = joint_enqueue(xs, xs_dtype, xs_mem, m, diag_add, as<double>(pj_mu), as<double>(pj_sigma), mpad, true)))
+    return rc;
+  HIPCHECK(hipMemsetAsync(pj_linv.p, 0, mat, s));
+  (void)launch_potrf<double>(s, as<double>(pj_sigma), as<double>(pj_l), as<double>(pj_linv), as<double>(pj_cwork), nullptr, m, mpad,
+                             as<double>(pj_diag), info, -1, nullptr);
+  HIPCHECK(hipMemcpyAsync(info_host, info, sizeof(int), hipMemcpyDeviceToHost, s));
+  launch_joint_draw(s, as<double>(pj_l), mpad, as<double>(pj_z), as<double>(pj_mu), m, ns, as<double>(pj_f));
+  int64_t* bi = as<int64_t>(pj_best);
+  double* bv = reinterpret_cast<double*>(bi + ns);
+  if (best_idx || best_val) launch_joint_argmax(s, as<double>(pj_f), m, ns, bi, bv);
+  if ((rc = launch_status())) return rc;
+  if (samples) HIPCHECK(hipMemcpyAsync(samples, pj_f.p, (size_t)ns * m * 8, hipMemcpyDeviceToHost, s));
+  if (best_idx) HIPCHECK(hipMemcpyAsync(best_idx, bi, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+  if (best_val) HIPCHECK(hipMemcpyAsync(best_val, bv, (size_t)ns * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = points_end(s, m))) return rc;
+  if (*info_host != INT_MAX)
+    return ctx->fail(GPSO_E_NOTPD, "gpso_sample_joint: Sigma + diag_add*I is not positive definite: Cholesky failed at pivot %d "
+                                   "(a larger diag_add -- jitter -- is the remedy)", *info_host);
+  return GPSO_OK;
+}
+
+// ---- pathwise posterior draws (paths.hip).  Both calls read the dense fit-type factor, the scaled
+// rows, y, the per-point noise and the hyper block and write buffers of their own only: the posterior, its packed copies and
+// the self-test's verdicts stay as they are.  gpso_paths_draw builds the set beside the resident one and swaps it in at the end
+static bool all_finite(const double* v, size_t len) {
+  for (size_t i = 0; i < len; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+// the draw of a variational posterior: v = beta + Lu^-T (Q eps - Lu^-1 Phi(Zr) w^T) from what the
+// install left in Lf (Lu), alpha_f (beta) and vq_S / svq_S / sgM2 (Q); Lu^-1 is rebuilt from Lf into vA (vB: the copy of
+// Lu with a unit diagonal on the padding, work: scratch) -- three buffers the install has finished with
+int EngineCore::paths_draw_impl(bool variational, const char* who, const double* omega, const double* phase, int64_t f, const double* w,
+                    const double* eps, int64_t ns) {
+  if (int rcd = need_double_fit(" needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)", who)) return rcd;
+  ctx->tick_timing();
+  if (ns < 1 || ns > kPathsMaxDraws)
+    return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld draws (s=%lld)", who, (long long)kPathsMaxDraws, (long long)ns);
+  if (f < 1 || f > kPathsMaxFeatures)
+    return ctx->fail(GPSO_E_ARG, "%s takes 1 to %lld features (f=%lld)", who, (long long)kPathsMaxFeatures, (long long)f);
+  if (!omega || !phase || !w) return ctx->fail(GPSO_E_ARG, "omega, phase and w must not be NULL");
+  if (!variational) {
+    if (!(res.post == Post::Fitted && res.st_have && res.have_data && res.chol_valid))
+      return ctx->fail(GPSO_E_STATE, "gpso_paths_draw needs a posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval)");
+  } else {
+    if (res.post == Post::Fitted) return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q draws from a variational posterior: a fitted exact GP takes gpso_paths_draw");
+    if (!(res.variational() && res.chol_valid))
+      return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q needs a posterior installed by gpso_vgp_posterior, gpso_sgpr_posterior or gpso_svgp_posterior on this context");
+    // (at present implied by the line above: q_factors is set with the kind and cleared only where the kind is -- no call
+    // overwrites Lf, beta or the root of q and keeps the posterior.  The flag is for the first call that does)
+    if (!res.q_factors)
+      return ctx->fail(GPSO_E_STATE, "gpso_paths_draw_q: the install's factors (Lu, beta, the root of q) are not resident any more: install again");
+  }
+  int rc = refuse_if_async(who);
+  if (rc) return rc;
+  if (!all_finite(omega, (size_t)f * d) || !all_finite(phase, (size_t)f) || !all_finite(w, (size_t)ns * f) ||
+      (eps && !all_finite(eps, (size_t)ns * n)))
+    return ctx->fail(GPSO_E_ARG, "%s: omega, phase, w and eps must be finite", who);
+  const int64_t f16 = (f + 15) / 16 * 16, spad = (ns + 63) / 64 * 64, n64 = (n + 63) / 64 * 64;
+  PathSet& nx = pth_next;
+  if ((rc = ensure(nx.omega, (size_t)f16 * dp * 8))) return rc;
+  if ((rc = ensure(nx.phase, (size_t)f16 * 8))) return rc;
+  if ((rc = ensure(nx.w, (size_t)ns * f16 * 8))) return rc;
+  if ((rc = ensure(nx.vt, (size_t)spad * npad * 8))) return rc;
+  if (eps && (rc = ensure(pth_eps, (size_t)ns * n * 8))) return rc;
+  if ((rc = ensure(pth_p, (size_t)ns * n64 * 8))) return rc;
+  if ((rc = ensure(pth_r, (size_t)n64 * spad * 8))) return rc;
+  if ((rc = ensure(pth_u, (size_t)n64 * spad * 8))) return rc;
+  if (variational && (rc = ensure(pth_x, (size_t)n64 * spad * 8))) return rc;
+  // the layouts the kernels read: D_pad columns, rows up to a multiple of 16, zeros on the padding
+  std::vector<double> ho((size_t)f16 * dp, 0.0), hp((size_t)f16, 0.0), hw((size_t)ns * f16, 0.0);
+  for (int64_t j = 0; j < f; ++j) {
+    std::memcpy(&ho[(size_t)j * dp], omega + (size_t)j * d, (size_t)d * 8);
+    hp[(size_t)j] = phase[j];
+  }
+  for (int64_t r = 0; r < ns; ++r) std::memcpy(&hw[(size_t)r * f16], w + (size_t)r * f, (size_t)f * 8);
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  HIPCHECK(hipMemcpyAsync(nx.omega.p, ho.data(), ho.size() * 8, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(nx.phase.p, hp.data(), hp.size() * 8, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemcpyAsync(nx.w.p, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, s));
+  if (eps) HIPCHECK(hipMemcpyAsync(pth_eps.p, eps, (size_t)ns * n * 8, hipMemcpyHostToDevice, s));
+  PathsEvalLaunch g;  // Phi(X) w^T: the evaluation over the training rows, kernel part off
+  g.ts = g.xs = as<double>(xs64); g.omega = as<double>(nx.omega); g.phase = as<double>(nx.phase); g.W = as<double>(nx.w);
+  g.n = n; g.npad = npad; g.m = n; g.s = ns; g.f = f; g.ldw = f16; g.dp = dp; g.kp = kp; g.out = as<double>(pth_p); g.ldo = n64;
+  if (launch_paths_eval(s, g) != 0) return launch_status();
+  if (!variational) {
+    launch_paths_solve(s, as<double>(linv), as<double>(y64), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, s_dev(), kp,
+                       n, npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(nx.vt));
+  } else {
+    launch_vgp_clean_lower(s, as<double>(Lf), as<double>(vB), n, npad, 1.0);
+    launch_trinv<double>(s, as<double>(vB), as<double>(vA), as<double>(work), npad);
+    const bool sgpr = res.post == Post::Sgpr;
+    const double* Q = sgpr ? as<double>(sgM2) : res.post == Post::Svgp ? as<double>(svq_S) : as<double>(vq_S);
+    launch_paths_solve_q(s, as<double>(vA), Q, sgpr, as<double>(alpha_f), as<double>(pth_p), n64, eps ? as<double>(pth_eps) : nullptr, n,
+                         npad, ns, as<double>(pth_r), as<double>(pth_u), as<double>(pth_x), as<double>(nx.vt));
+  }
+  if ((rc = launch_status())) return rc;
+  if ((rc = points_end(s, kNoCounts))) return rc;
+  nx.s = ns; nx.f = f; nx.ldw = f16;
+  std::swap(pth, pth_next);
+  res.paths_drawn();
+  return GPSO_OK;
+}
+
+// M is worked off in chunks of kPathsChunk: values of one chunk [S][chunk], copied out and / or reduced into the running
+// winners per (draw, segment) before the next chunk overwrites them
+int EngineCore::paths_eval(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, double* values, int out_mem,
+               int64_t* best_idx, double* best_val) {
+  if (int rcd = need_double_fit("gpso_paths_eval needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_eval needs at least one point (m=%lld)", (long long)m);
+  int rc = check_points(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if (!values && !best_idx && !best_val) return ctx->fail(GPSO_E_ARG, "values, best_idx and best_val are all NULL");
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "nseg=%d outside [1, 1024]", nseg);
+  if (!res.paths_valid)
+    return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
+  if ((rc = refuse_if_async("gpso_paths_eval"))) return rc;
+  std::vector<int64_t> so(nseg + 1);
+  if (seg_off) {
+    for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
+    if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at M");
+    for (int i = 0; i < nseg; ++i)
+      if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
+  } else {
+    if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
+    so[0] = 0;
+    so[1] = m;
+  }
+  const bool want_best = best_idx || best_val;
+  const int64_t ns = pth.s, chunk = std::min<int64_t>(kPathsChunk, (m + 63) / 64 * 64);
+  if ((rc = ensure(pe_ts, (size_t)chunk * dp * 8))) return rc;
+  if ((rc = ensure(pe_norm, (size_t)chunk * 8))) return rc;
+  if ((rc = ensure(pe_vals, (size_t)ns * chunk * 8))) return rc;
+  if ((rc = ensure(pe_seg, (size_t)(nseg + 1) * 8))) return rc;
+  if ((rc = ensure(pe_best, (size_t)ns * nseg * 16))) return rc;
+  int64_t* bi = as<int64_t>(pe_best);
+  double* bv = reinterpret_cast<double*>(bi + ns * nseg);
+  std::vector<int64_t> hi_(want_best ? (size_t)ns * nseg : 0);
+  std::vector<double> hv_(want_best ? (size_t)ns * nseg : 0);
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  if (want_best) {
+    HIPCHECK(hipMemcpyAsync(pe_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(hipMemsetAsync(pe_best.p, 0xFF, (size_t)ns * nseg * 16, s));  // (index -1: no winner yet; the value a NaN)
+  }
+  PathsEvalLaunch g;
+  g.ts = as<double>(pe_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
+  g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
+  g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.out = as<double>(pe_vals); g.ldo = chunk;
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+    prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(pe_ts), as<double>(pe_norm));
+    g.m = mc;
+    if (launch_paths_eval(s, g) != 0) return launch_status();
+    if ((rc = launch_status())) return rc;
+    if (values)
+      HIPCHECK(hipMemcpy2DAsync(values + off, (size_t)m * 8, pe_vals.p, (size_t)chunk * 8, (size_t)mc * 8, (size_t)ns,
+                                out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+    if (want_best) launch_paths_argmax(s, as<double>(pe_vals), chunk, off, mc, as<int64_t>(pe_seg), nseg, ns, bi, bv);
+  }
+  if (want_best) {
+    if ((rc = launch_status())) return rc;
+    HIPCHECK(hipMemcpyAsync(hi_.data(), bi, hi_.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(hipMemcpyAsync(hv_.data(), bv, hv_.size() * 8, hipMemcpyDeviceToHost, s));
+  }
+  if ((rc = points_end(s, m))) return rc;
+  for (size_t e = 0; e < hi_.size(); ++e) {  // indices relative to the segment start; an empty segment: -1 and a NaN
+    if (best_idx) best_idx[e] = hi_[e] < 0 ? -1 : hi_[e] - so[e % nseg];
+    if (best_val) best_val[e] = hv_[e];
+  }
+  return GPSO_OK;
+}
+
+// ---- latent cross-covariance and greedy batch selection (batch.hip).  Both calls read the dense
+// fit-type factor, the scaled rows and the hyper block -- gpso_best_batch also whatever gpso_acq_values reads -- and write
+// buffers of their own only: the posterior, its packed copies, the self-test's verdicts and a resident path set stay as they are
+int EngineCore::cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem) {
+  if (int rcd = need_double_fit("gpso_cross_cov needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov needs at least one point (m=%lld)", (long long)m);
+  if (b < 1 || b > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_cross_cov takes 1 to %d points b (b=%d)", kBatchMaxPicks, b);
+  int rc = check_points(xa, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if (!xb || !cov) return ctx->fail(GPSO_E_ARG, "xb and cov must not be NULL");
+  if ((rc = need_dense_factor("gpso_cross_cov"))) return rc;
+  const int64_t chunk = std::min<int64_t>(kBatchChunk, (m + 63) / 64 * 64);
+  if ((rc = ensure(cc_ts, (size_t)chunk * dp * 8))) return rc;
+  if ((rc = ensure(cc_norm, (size_t)chunk * 8))) return rc;
+  if ((rc = ensure(cc_braw, (size_t)kBatchMaxPicks * d * 8))) return rc;
+  if ((rc = ensure(cc_tb, (size_t)kBatchMaxPicks * dp * 8))) return rc;
+  if ((rc = ensure(cc_bnorm, (size_t)kBatchMaxPicks * 8))) return rc;
+  if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, b) * 8))) return rc;
+  if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
+  const bool to_host = out_mem == GPSO_MEM_HOST;
+  double* cd = cov;
+  if (to_host) {
+    if ((rc = ensure(cc_out, (size_t)b * m * 8))) return rc;
+    cd = as<double>(cc_out);
+  }
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xa, xs_dtype, xs_mem, m, &dev))) return rc;
+  HIPCHECK(hipMemcpyAsync(cc_braw.p, xb, (size_t)b * d * 8, hipMemcpyHostToDevice, s));
+  prep_points<double>(s, cc_braw.p, GPSO_F64, 0, b, kBatchMaxPicks, nullptr, as<double>(cc_tb), as<double>(cc_bnorm));
+  BatchPickLaunch pk;
+  pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(cc_tb); pk.n = n; pk.npad = npad; pk.b = b; pk.dp = dp; pk.kp = kp;
+  pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + (size_t)b * npad; pk.W = pk.U + (size_t)b * npad; pk.lv = as<double>(cc_lv);
+  if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
+  BatchColLaunch g;
+  g.ts = as<double>(cc_ts); g.tnorm = as<double>(cc_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.bnorm = as<double>(cc_bnorm);
+  g.n = n; g.npad = npad; g.b = b; g.dp = dp; g.kp = kp; g.ldc = m;
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+    prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(cc_ts), as<double>(cc_norm));
+    g.m = mc;
+    g.cov = cd + off;
+    if (launch_batch_cross(s, g) != 0) return launch_status();
+    if ((rc = launch_status())) return rc;
+  }
+  if (to_host) HIPCHECK(hipMemcpyAsync(cov, cd, (size_t)b * m * 8, hipMemcpyDeviceToHost, s));
+  return points_end(s, m);
+}
+
+// Round 0 is gpso_acq_values on the batch (the context's predict path: its bits); every later round is double arithmetic
+// on top: pick vectors, one column launch, one finish launch.  All rounds are enqueued back to back, the picks stay on
+// the device, one wait at the end
+int EngineCore::best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx,
+               double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem) {
+  if (int rcd = need_double_fit("gpso_best_batch needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_best_batch needs at least one leaf (m=%lld)", (long long)m);
+  if (q < 1 || q > kBatchMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_best_batch picks 1 to %d leaves (q=%d)", kBatchMaxPicks, q);
+  if (m > kBatchMaxCells / q) return ctx->fail(GPSO_E_ARG, "gpso_best_batch: q * m above 2^27 (q=%d, m=%lld)", q, (long long)m);
+  if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+  if (!idx || !n_picked) return ctx->fail(GPSO_E_ARG, "idx and n_picked must not be NULL");
+  if (!(obs_noise >= 0.0) || obs_noise - obs_noise != 0.0) return ctx->fail(GPSO_E_ARG, "obs_noise must be finite and not negative");
+  int rc = check_predict_args(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if ((rc = need_dense_factor("gpso_best_batch"))) return rc;
+  const int64_t mall = (m + 63) / 64 * 64, nblk = batch_round_blocks(m);
+  if ((rc = ensure(bb_ts, (size_t)mall * dp * 8))) return rc;
+  if ((rc = ensure(bb_norm, (size_t)mall * 8))) return rc;
+  if ((rc = ensure(bb_mean, (size_t)m * 8))) return rc;
+  if ((rc = ensure(bb_s2, (size_t)m * 8))) return rc;
+  if ((rc = ensure(bb_val, (size_t)m * 8))) return rc;
+  if ((rc = ensure(bb_g, (size_t)q * m * 8))) return rc;
+  if ((rc = ensure(bb_live, (size_t)m))) return rc;
+  if ((rc = ensure(bb_bmax, (size_t)nblk * 16))) return rc;
+  if ((rc = ensure(bb_state, sizeof(BatchState)))) return rc;
+  if ((rc = ensure(bb_tp, (size_t)kMaxD * 8))) return rc;
+  if ((rc = ensure(cc_vec, batch_pick_workspace_doubles(n, npad, 1) * 8))) return rc;
+  if ((rc = ensure(cc_lv, (size_t)kBatchMaxPicks * 8))) return rc;
+  BatchState* host = reinterpret_cast<BatchState*>(ctx->pinned_scratch(sizeof(BatchState) / 8 + 1));
+  if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  BatchState* state = static_cast<BatchState*>(bb_state.p);
+  HIPCHECK(hipMemsetAsync(state, 0, sizeof(BatchState), s));
+  double *md = as<double>(bb_mean), *s2d = as<double>(bb_s2), *vald = as<double>(bb_val), *G = as<double>(bb_g);
+  double* bmax_v = as<double>(bb_bmax);
+  int64_t* bmax_i = reinterpret_cast<int64_t*>(bmax_v + nblk);
+  unsigned char* live = static_cast<unsigned char*>(bb_live.p);
+  TileSpan span{ctx->timing};
+  if ((rc = score_device_leaves(dev, xs_dtype, m, acq, true, md, s2d, vald, span))) return rc;
+  for (int64_t off = 0; off < m; off += kBatchChunk) {
+    const int64_t mc = std::min(kBatchChunk, m - off), mpad = (mc + 63) / 64 * 64;
+    prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(bb_ts) + off * dp, as<double>(bb_norm) + off);
+  }
+  launch_batch_init(s, vald, m, live, bmax_v, bmax_i);
+  BatchPickLaunch pk;
+  pk.C = as<double>(linv); pk.xs = as<double>(xs64); pk.tb = as<double>(bb_tp); pk.n = n; pk.npad = npad; pk.b = 1; pk.dp = dp; pk.kp = kp;
+  pk.Kb = as<double>(cc_vec); pk.U = pk.Kb + npad; pk.W = pk.U + npad; pk.lv = as<double>(cc_lv); pk.st = state; pk.obs_noise = obs_noise;
+  BatchColLaunch g;
+  g.ts = as<double>(bb_ts); g.tnorm = as<double>(bb_norm); g.xs = pk.xs; g.W = pk.W; g.tb = pk.tb; g.n = n; g.npad = npad; g.m = m;
+  g.dp = dp; g.kp = kp; g.st = state; g.G = G; g.s2 = s2d; g.mean = md; g.live = live; g.acq = acq; g.bmax_v = bmax_v; g.bmax_i = bmax_i;
+  for (int t = 0; t < q; ++t) {
+    launch_batch_finish(s, state, t, bmax_v, bmax_i, t == 0 ? batch_init_blocks(m) : nblk, g.ts, dp, md, s2d, G, m, live, as<double>(bb_tp));
+    const bool last = t == q - 1;
+    if (last && !var_after) break;
+    pk.t = g.t = t;
+    g.rank = !last;
+    if (launch_batch_pick_vectors(s, pk) != 0) return launch_status();
+    if (launch_batch_round(s, g) != 0) return launch_status();
+  }
+  if ((rc = launch_status())) return rc;
+  HIPCHECK(hipMemcpyAsync(host, state, sizeof(BatchState), hipMemcpyDeviceToHost, s));
+  if (var_after)
+    HIPCHECK(hipMemcpyAsync(var_after, s2d, (size_t)m * 8, out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+  if ((rc = points_end(s, m))) return rc;
+  collect_tile_ms(span.timed, span.pairs);
+  *n_picked = host->n_picked;
+  for (int t = 0; t < host->n_picked; ++t) {
+    idx[t] = host->idx[t];
+    if (mean) mean[t] = host->mean[t];
+    if (var) var[t] = host->var[t];
+    if (value) value[t] = host->value[t];
+  }
+  return GPSO_OK;
+}
+
+}  // namespace gpso::host

@@ -1,7 +1,7 @@
 """
 Float64 numpy / scipy restatement of GPflow 2's ``SVGP`` (whitened, full q_sqrt, full batch, inducing points Z fixed) with
-the Gaussian or the Student-t likelihood -- the checker of the device SVGP path (pygpso_amd/csrc/svgp.hip, api.hip
-EngineT::svgp_*, ``pygpso_amd.svgp.HipSVGP``).  Test infrastructure only: the product never imports it.
+the Gaussian or the Student-t likelihood -- the checker of the device SVGP path (pygpso_amd/csrc/svgp.hip,
+engine_variational.hip EngineCore::svgp_*, ``pygpso_amd.svgp.HipSVGP``).  Test infrastructure only: the product never imports it.
 
 A likelihood is ``(kind, df)`` as in tests/vgp_studentt_oracle.py: ``("Gaussian", None)`` (closed form), ``("GaussianGH",
 None)`` (the same Gaussian through 20-point Gauss-Hermite quadrature) or ``("StudentT", df)``; u as the VGP's.

@@ -1,7 +1,7 @@
 """
 Float64 numpy restatement of GPflow 2's whitened ``VGP`` with a general scalar likelihood -- ``StudentT(scale, df)``, or the
 Gaussian through the same quadrature -- the checker of the device's quadrature path (pygpso_amd/csrc/vgp.hip:
-vgp_quad_kernel and friends; api.hip EngineT::vgp_*).  Test infrastructure only: the product never imports it.
+vgp_quad_kernel and friends; engine_variational.hip EngineCore::vgp_*).  Test infrastructure only: the product never imports it.
 
 What GPflow does: ``ScalarLikelihood.variational_expectations`` by Gauss-Hermite quadrature with 20 points (nodes x sqrt(2),
 weights / sqrt(pi)), the -ELBO as -sum VE + KL, its gradient by autodiff (the derivatives of the quadrature sum, below), and

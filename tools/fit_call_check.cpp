@@ -13,7 +13,7 @@
 
 using namespace gpso;
 
-// the library's constants (kernels.hpp: kGradMaxLs; api.hip: kHyperHeader, kMaxD)
+// the library's constants (kernels.hpp: kGradMaxLs; context.hpp: kHyperHeader, kMaxD)
 using Map = FitScratch<64, 8, 48>;
 using Call = FitCall<Map>;
 
