@@ -823,6 +823,69 @@ int gpso_batch_greedy_mes_host(const double* ystar, int k, int latent, const dou
                                double noise, double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
                                int* n_picked, double* var_after /* nullable */);
 
+/* ---- the hyper-parameter ensemble: K posteriors of the same data, the integrated acquisition ----
+ * No counterpart in the reference, which ranks every leaf under one hyper-parameter vector.  An ensemble holds up to
+ * GPSO_ENSEMBLE_MAX posteriors of the RESIDENT DATA at different theta -- samples of p(theta | y), as
+ * pygpso_amd/hyper_sampler.py draws them -- and the integrated calls score every leaf under all of them and rank by the
+ * average (Snoek, Larochelle & Adams 2012).
+ *
+ * Where it applies: an exact-GP posterior fitted on this context (gpso_fit_eval*, with or without a noise vector, after
+ * gpso_append too), N <= 128, D <= 48, a GPSO_F64 or GPSO_MIXED context (the rule of gpso_predict_grad).  gpso_ensemble_max
+ * is 32 where a push can apply to the resident data, else 0.
+ *
+ * gpso_ensemble_push: the resident posterior becomes the next member; returns its index (>= 0) or a status (< 0).  A
+ * member is a device-to-device copy, on the context's stream, of what a point call reads -- the hyper block, the scaled
+ * rows, the dense double L^-1, alpha, the kernel kind -- into buffers of the ensemble's own (32 x (128 KB + the rows)).
+ * Nothing is computed: a member holds the bits the context's fit at its theta left.  All members share N, D and the kernel.
+ *   GPSO_E_ARG: a GPSO_F32 context; N > 128.   GPSO_E_STATE: no posterior, or a variational, installed (gpso_set_posterior)
+ *   or adopted one; a 33rd member; a posterior whose N, D or kernel disagrees with the members'; an asynchronous call open.
+ * gpso_ensemble_clear: no members.  GPSO_E_STATE while an asynchronous call is open.
+ * gpso_ensemble_info: *k members; theta (nullable) [k * 51]: per member 48 lengthscales (as the hyper block expands
+ * them), kernel variance, noise variance, constant mean.
+ * Lifetime: the members describe the data.  gpso_set_data, gpso_append*, gpso_set_noise_diag, gpso_set_posterior, every
+ * variational and sparse call that replaces the posterior or its rows, gpso_alloc_posterior and gpso_adopt_posterior end
+ * the ensemble (k = 0).  A refit at another theta does not, and changes no bit of a later integrated call.  The ensemble is
+ * no part of gpso_posterior_hash, the packed copies, a broadcast or a path set; pushing, clearing and the integrated
+ * calls leave all of those, the hyper block and the posterior bit for bit.
+ *
+ * The integrated calls.  Per member k and leaf j (one launch, a workgroup per 64 leaves and member): the leaf scaled by
+ * member k's lengthscales, k* from direct differences in double, V = L_k^-1 k* on the f64 MFMA,
+ *     mean_kj = alpha_k^T k* + c_k,   var_kj = (variance_k - sum_i V_i^2) + noise_k        (predictive)
+ * then, per leaf (a second launch), with a_kj acq's map (gpso_acq_values' per-member value; a latent kind reads
+ * var_kj - noise_k; incumbent, xi and varsigma are the caller's single numbers):
+ *     UCB_VAR, UCB_STD, EI, PI:  value_j = (sum_k a_kj) / K          index order, one division
+ *     LOGEI:  value_j = mx + log(sum_k exp(l_kj - mx)) - log K,  mx = max_k l_kj     (the log of the mean EI; -inf if all are)
+ *     mean_mix_j = (sum_k mean_kj) / K,   var_mix_j = (sum_k (var_kj + (mean_kj - mean_mix_j)^2)) / K
+ * A NaN member gives a NaN value; a leaf with a NaN coordinate is NaN in every member.  K = 1 returns the member's own
+ * three numbers.  The same call gives the same bits: no atomics, every sum in a fixed order.  A member's columns agree
+ * with gpso_predict on a context fitted at its theta to the float64 row of DESIGN.md 2.1, not bit for bit.
+ * gpso_ensemble_best_acq: per segment (seg_off / nseg as gpso_best_ucb) the arg-max of value -- the first maximum wins, a
+ *   NaN beats every number -- with idx relative to the segment (-1 and NaNs for an empty one); mean_mix / var_mix / value
+ *   [nseg] host, nullable: the winner's entries of gpso_ensemble_acq_values' columns, bit for bit.
+ * gpso_ensemble_acq_values: mean_mix / var_mix / value [m] and member_mean / member_var [k * m] (member-major), each
+ *   nullable, in out_mem.
+ * gpso_ensemble_fold_host: the fold alone on the host from given member columns [k * m] and noise [k] (nullable unless a
+ *   latent kind reads it): the same header, the same roundings; no context and no GPU.  GPSO_OK or GPSO_E_ARG.
+ * GPSO_E_ARG: a GPSO_F32 context; GPSO_ACQ_MES (its maxima belong to one theta) or another bad acq; m < 1; k * m > 2^28;
+ *   bad dtype / memory; nseg outside [1, 1024] or bad seg_off; NULL xs, idx, or every output.
+ * GPSO_E_STATE: no ensemble resident; an asynchronous best-UCB call open.
+ * gpso_last_ms(ctx, 1) covers a call; gpso_last_count(ctx, 0) and (ctx, 1) are m.
+ * Out of scope: grown leaves (_grow), the _begin / _end pair, sharded groups, the screen, gpso_best_batch on an ensemble,
+ * the variational families, GPSO_F32. */
+#define GPSO_ENSEMBLE_MAX 32
+int gpso_ensemble_max(gpso_ctx* ctx);
+int gpso_ensemble_push(gpso_ctx* ctx);
+int gpso_ensemble_clear(gpso_ctx* ctx);
+int gpso_ensemble_info(gpso_ctx* ctx, int* k, double* theta /* [k*(48+3)], nullable */);
+int gpso_ensemble_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
+                           int nseg, const gpso_acq* acq, int64_t* idx, double* mean_mix, double* var_mix, double* value);
+int gpso_ensemble_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq,
+                             double* mean_mix, double* var_mix, double* value /* [m], each nullable */,
+                             double* member_mean, double* member_var /* [k*m], nullable */, int out_mem);
+int gpso_ensemble_fold_host(const gpso_acq* acq, const double* member_mean, const double* member_var,
+                            const double* noise /* [k] */, int k, int64_t m, double* mean_mix, double* var_mix,
+                            double* value);
+
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 
 /* Centres of levels 0..depth-1 of the ternary subtree under each of nseg boxes, generated on the

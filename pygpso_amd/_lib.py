@@ -48,6 +48,8 @@ SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FU
 OPTF_TOL_VAR, OPTF_TOL_MEAN = 100, 101
 GEN_F64, GEN_F32, GEN_AUTO = 0, 1, 2
 ACQ_UCB_VAR, ACQ_UCB_STD, ACQ_EI, ACQ_LOGEI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4, 5
+ENSEMBLE_MAX = 32  # members of a hyper-parameter ensemble; gpso_ensemble_info reports ENSEMBLE_THETA doubles per member
+ENSEMBLE_THETA = 48 + 3
 ACQ_MAX_MAXIMA = 64  # gpso_acq_set_maxima keeps at most this many; gpso_max_logcdf takes at most this many thresholds
 FITMATH_NONE, FITMATH_SMALL, FITMATH_F32, FITMATH_F64, FITMATH_BF16X6, FITMATH_F16X3 = 0, 1, 2, 3, 4, 5  # gpso_last_count(ctx, 2)
 GEN_IDS = {"float64": GEN_F64, "f64": GEN_F64, "float32": GEN_F32, "f32": GEN_F32, "auto": GEN_AUTO}
@@ -179,6 +181,16 @@ SIGNATURES = {
     "gpso_batch_greedy_mes_host": (C.c_int, [_c_double_p, C.c_int, C.c_int, _c_double_p, _c_double_p, _c_double_p, C.c_double,
                                              C.c_double, C.c_int64, C.c_int, _c_int64_p, _c_double_p, _c_double_p,
                                              C.POINTER(C.c_int), _c_double_p]),
+    "gpso_ensemble_max": (C.c_int, [C.c_void_p]),
+    "gpso_ensemble_push": (C.c_int, [C.c_void_p]),
+    "gpso_ensemble_clear": (C.c_int, [C.c_void_p]),
+    "gpso_ensemble_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _c_double_p]),
+    "gpso_ensemble_best_acq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, _c_acq_p,
+                                         _c_int64_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_ensemble_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpso_ensemble_fold_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int64, _c_double_p,
+                                          _c_double_p, _c_double_p]),
     "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,

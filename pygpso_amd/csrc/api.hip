@@ -1477,21 +1477,6 @@ struct EngineT : EngineCore {
       for (int i = 0; i < nseg; ++i) base[(size_t)r * nseg + i] = std::min(std::max(so[i], rlo), rhi) - so[i];
     }
   }
-  // seg_off (host, nseg + 1 entries over [0, m], NULL: one segment), checked -> so
-  int checked_segments(int64_t m, const int64_t* seg_off, int nseg, std::vector<int64_t>& so, const char* m_name = "the global M") {
-    so.resize(nseg + 1);
-    if (seg_off) {
-      for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
-      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at %s", m_name);
-      for (int i = 0; i < nseg; ++i)
-        if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
-    } else {
-      if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
-      so[0] = 0;
-      so[1] = m;
-    }
-    return GPSO_OK;
-  }
   std::vector<int64_t> wbase_cache;  // what the device copy of the bases holds (they change with the batch shape only)
   int upload_base(const std::vector<int64_t>& base) {
     if (wbase.p != nullptr && base == wbase_cache) return GPSO_OK;
@@ -2957,6 +2942,52 @@ int gpso_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
   ACQ_ENTER();
   if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
   return ctx->eng->best_batch(xs, xs_dtype, xs_mem, m, acq_spec(ctx, acq), obs_noise, q, idx, mean, var, value, n_picked, var_after, out_mem);
+}
+
+// ---- the hyper-parameter ensemble (ensemble.hpp) -------------------------------------------------
+int gpso_ensemble_max(gpso_ctx* ctx) { return ctx ? ctx->eng->ensemble_max() : 0; }
+
+int gpso_ensemble_push(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->ensemble_push();
+}
+
+int gpso_ensemble_clear(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->ensemble_clear();
+}
+
+int gpso_ensemble_info(gpso_ctx* ctx, int* k, double* theta) {
+  if (!ctx) return GPSO_E_ARG;
+  return ctx->eng->ensemble_info(k, theta);
+}
+
+int gpso_ensemble_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                           const gpso_acq* acq, int64_t* idx, double* mean_mix, double* var_mix, double* value) {
+  ENTER();
+  if (acq && acq->kind == GPSO_ACQ_MES)
+    return ctx->fail(GPSO_E_ARG, "gpso_ensemble_best_acq: GPSO_ACQ_MES is not integrated over an ensemble: its maxima belong to one theta");
+  if (const char* why = acq_refusal(acq)) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_best_acq: %s", why);
+  return ctx->eng->ensemble_best_acq(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), idx, mean_mix, var_mix, value);
+}
+
+int gpso_ensemble_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq, double* mean_mix,
+                             double* var_mix, double* value, double* member_mean, double* member_var, int out_mem) {
+  ENTER();
+  if (acq && acq->kind == GPSO_ACQ_MES)
+    return ctx->fail(GPSO_E_ARG, "gpso_ensemble_acq_values: GPSO_ACQ_MES is not integrated over an ensemble: its maxima belong to one theta");
+  if (const char* why = acq_refusal(acq)) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_acq_values: %s", why);
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_acq_values: bad out_mem %d", out_mem);
+  return ctx->eng->ensemble_acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), mean_mix, var_mix, value, member_mean, member_var, out_mem);
+}
+
+int gpso_ensemble_fold_host(const gpso_acq* acq, const double* member_mean, const double* member_var, const double* noise, int k, int64_t m,
+                            double* mean_mix, double* var_mix, double* value) {
+  if (acq_refusal(acq) != nullptr || !member_mean || !member_var || k < 1 || k > gpso::kEnsembleMax || m < 1) return GPSO_E_ARG;
+  if (acq->latent != 0 && acq->kind != GPSO_ACQ_UCB_VAR && !noise) return GPSO_E_ARG;
+  if (!mean_mix && !var_mix && !value) return GPSO_E_ARG;
+  gpso::ensemble_fold_host(acq_spec(acq), member_mean, member_var, noise, k, m, mean_mix, var_mix, value);
+  return GPSO_OK;
 }
 
 int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise, double obs_noise,

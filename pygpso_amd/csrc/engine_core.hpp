@@ -10,6 +10,7 @@
 #include "batch.hpp"
 #include "context.hpp"
 #include "devbuf.hpp"
+#include "ensemble.hpp"
 #include "resident.hpp"
 #include "screen.hpp"
 
@@ -568,6 +569,21 @@ struct EngineCore {
       launch_prep_leaves<TG, float>(s, static_cast<const float*>(dev) + off * d, mc, mpad, d, dp, ls_dev(), m_live, ts, norm);
   }
 
+  // seg_off of a best-UCB / best-acquisition call (host, nseg + 1 entries over [0, m], NULL: one segment), checked -> so
+  int checked_segments(int64_t m, const int64_t* seg_off, int nseg, std::vector<int64_t>& so, const char* m_name = "the global M") {
+    so.resize(nseg + 1);
+    if (seg_off) {
+      for (int i = 0; i <= nseg; ++i) so[i] = seg_off[i];
+      if (so[0] != 0 || so[nseg] != m) return ctx->fail(GPSO_E_ARG, "seg_off must start at 0 and end at %s", m_name);
+      for (int i = 0; i < nseg; ++i)
+        if (so[i + 1] < so[i]) return ctx->fail(GPSO_E_ARG, "seg_off must be non-decreasing");
+    } else {
+      if (nseg != 1) return ctx->fail(GPSO_E_ARG, "seg_off == NULL requires nseg == 1");
+      so[0] = 0;
+      so[1] = m;
+    }
+    return GPSO_OK;
+  }
   int check_predict_args(const void* xs, int xs_dtype, int xs_mem, int64_t m) {
     if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "no posterior resident: call gpso_fit_eval / gpso_set_posterior first");
     if (m < 0) return ctx->fail(GPSO_E_ARG, "negative leaf count");
@@ -633,6 +649,29 @@ struct EngineCore {
   }
   int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem);
   int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx, double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem);
+
+  // ---- the hyper-parameter ensemble (ensemble.hpp, ensemble.hip).  The members' copies -- kEnsembleMax
+  // slots each of the hyper block, the scaled rows, the dense double L^-1 and alpha -- belong to the ensemble and to nothing
+  // else: no fit, hand-off, hash or path set reads them.  res.ensemble says whether they describe the resident data; ens_k
+  // counts them while it does.  Then the calls' workspaces: the members' columns [K][m], the three folded columns, the
+  // segment offsets, the arg-max's partials and records
+  DevBuf ens_hyper, ens_xs, ens_linv, ens_alpha;
+  DevBuf ens_mean, ens_var, ens_mix, ens_seg, ens_part, ens_out;
+  int ens_k = 0, ens_d = 0, ens_dp = 0, ens_kernel = 0;
+  int64_t ens_n = 0;
+  std::vector<double> ens_theta;  // [ens_k][kEnsembleTheta]: what gpso_ensemble_info reports
+  static constexpr int64_t kEnsHyperStride = kHyperHeader + kMaxD;
+  int ensemble_count() const { return res.ensemble ? ens_k : 0; }
+  int ensemble_max() const { return (fit_elem == 8 && res.have_data && n <= kEnsembleMaxN) ? kEnsembleMax : 0; }
+  int ensemble_push();
+  int ensemble_clear();
+  int ensemble_info(int* k, double* theta) const;
+  int ensemble_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq);
+  int ensemble_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, hipStream_t* s);
+  int ensemble_acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean_mix, double* var_mix,
+                          double* value, double* member_mean, double* member_var, int out_mem);
+  int ensemble_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
+                        int64_t* idx, double* mean_mix, double* var_mix, double* value);
 
   // ---- the variational and sparse families (engine_variational.hip says what each buffer holds) ----
   DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;  // the VGP: q(v) = N(mu, S S^T), three matrices, the vectors, the sums and verdicts

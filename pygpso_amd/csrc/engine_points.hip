@@ -514,4 +514,152 @@ int EngineCore::best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, 
   return GPSO_OK;
 }
 
+// ---- the hyper-parameter ensemble (ensemble.hip).  A push copies what a point call reads of the
+// resident posterior -- device to device, on the context's stream, nothing computed -- into slots that only the integrated
+// calls read; those read nothing of the resident posterior, so a refit at another theta between them changes no bit of theirs.
+// Every call here leaves the posterior, its packed copies, the hyper block, gpso_posterior_hash and a path set as they are
+int EngineCore::ensemble_push() {
+  if (int rcd = need_double_fit("gpso_ensemble_push needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  if (!res.has_post()) return ctx->fail(GPSO_E_STATE, "gpso_ensemble_push: no posterior resident: call gpso_fit_eval first");
+  if (res.post != Post::Fitted || !res.chol_valid || !res.have_data)
+    return ctx->fail(GPSO_E_STATE, "gpso_ensemble_push needs an exact-GP posterior fitted with targets on this context (gpso_set_data + gpso_fit_eval): "
+                                   "a variational, installed or adopted posterior is no member of an ensemble");
+  if (n > kEnsembleMaxN) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_push: N=%lld above the ensemble's %d (gpso_ensemble_max = 0)", (long long)n, kEnsembleMaxN);
+  int rc = refuse_if_async("gpso_ensemble_push");
+  if (rc) return rc;
+  const int k = ensemble_count();
+  if (k >= kEnsembleMax) return ctx->fail(GPSO_E_STATE, "gpso_ensemble_push: the ensemble is full (%d members: GPSO_ENSEMBLE_MAX)", kEnsembleMax);
+  if (k > 0 && (n != ens_n || d != ens_d || kp.kernel != ens_kernel))
+    return ctx->fail(GPSO_E_STATE, "gpso_ensemble_push: the resident posterior (N=%lld, D=%d, kernel %d) disagrees with the ensemble's members "
+                                   "(N=%lld, D=%d, kernel %d): gpso_ensemble_clear first", (long long)n, d, kp.kernel, (long long)ens_n, ens_d, ens_kernel);
+  // (k == 0: the slots may be re-allocated for another D_pad, nothing in them is kept; k > 0: the shape is the same, nothing grows)
+  const size_t b_xs = (size_t)npad * dp * 8, b_linv = (size_t)npad * npad * 8, b_alpha = (size_t)npad * 8, b_hyper = (size_t)kEnsHyperStride * 8;
+  if ((rc = ensure(ens_hyper, kEnsembleMax * b_hyper))) return rc;
+  if ((rc = ensure(ens_xs, kEnsembleMax * b_xs))) return rc;
+  if ((rc = ensure(ens_linv, kEnsembleMax * b_linv))) return rc;
+  if ((rc = ensure(ens_alpha, kEnsembleMax * b_alpha))) return rc;
+  hipStream_t s = st();
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(ens_hyper.p) + k * b_hyper, hyper.p, b_hyper, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(ens_xs.p) + k * b_xs, xs64.p, b_xs, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(ens_linv.p) + k * b_linv, linv.p, b_linv, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(ens_alpha.p) + k * b_alpha, alpha_f.p, b_alpha, hipMemcpyDeviceToDevice, s));
+  if (k == 0) {
+    ens_n = n; ens_d = d; ens_dp = dp; ens_kernel = kp.kernel;
+    ens_theta.clear();
+  }
+  ens_theta.resize((size_t)(k + 1) * kEnsembleTheta);
+  double* row = &ens_theta[(size_t)k * kEnsembleTheta];
+  expand_ls(ls_host.data(), n_ls, row);
+  row[kMaxD] = kp.variance; row[kMaxD + 1] = kp.noise; row[kMaxD + 2] = kp.mean_c;
+  ens_k = k + 1;
+  res.ensemble_pushed();
+  return k;
+}
+
+int EngineCore::ensemble_clear() {
+  int rc = refuse_if_async("gpso_ensemble_clear");
+  if (rc) return rc;
+  ens_k = 0;
+  res.ensemble_cleared();
+  return GPSO_OK;
+}
+
+int EngineCore::ensemble_info(int* k, double* theta) const {
+  if (!k) return ctx->fail(GPSO_E_ARG, "k must not be NULL");
+  *k = ensemble_count();
+  if (theta && *k > 0) std::memcpy(theta, ens_theta.data(), (size_t)*k * kEnsembleTheta * 8);
+  return GPSO_OK;
+}
+
+// what both integrated calls refuse, before anything is allocated or enqueued
+int EngineCore::ensemble_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq) {
+  if (int rcd = need_double_fit(" needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the members' factors are double)", who)) return rcd;
+  const int k = ensemble_count();
+  if (k == 0)
+    return ctx->fail(GPSO_E_STATE, "%s: no ensemble resident for this data: gpso_ensemble_push after a fit (new data, an append, a noise vector, "
+                                   "an install and a hand-off end the ensemble)", who);
+  if (acq.kind == GPSO_ACQ_MES) return ctx->fail(GPSO_E_ARG, "%s: GPSO_ACQ_MES is not integrated over an ensemble: its maxima belong to one theta", who);
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "%s needs at least one leaf (m=%lld)", who, (long long)m);
+  if (m > ((int64_t)1 << 28) / k) return ctx->fail(GPSO_E_ARG, "%s: k * m above 2^28 (k=%d, m=%lld)", who, k, (long long)m);
+  int rc = check_points(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  return refuse_if_async(who);
+}
+
+// ... and what both enqueue behind their refusals: the workspaces, the members' columns (stage 1) and the fold (stage 2).  On
+// return the stream is open (points_begin), ens_mean / ens_var hold [K][m] and ens_mix the three folded columns
+int EngineCore::ensemble_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, hipStream_t* s) {
+  ctx->tick_timing();
+  const int k = ensemble_count();
+  int rc;
+  if ((rc = ensure(ens_mean, (size_t)k * m * 8))) return rc;
+  if ((rc = ensure(ens_var, (size_t)k * m * 8))) return rc;
+  if ((rc = ensure(ens_mix, (size_t)3 * m * 8))) return rc;
+  if ((rc = points_begin(s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  EnsembleMembersLaunch g;
+  g.hyper = as<double>(ens_hyper); g.xs = as<double>(ens_xs); g.linv = as<double>(ens_linv); g.alpha = as<double>(ens_alpha);
+  g.hyper_stride = kEnsHyperStride; g.leaves = dev; g.leaves_f64 = xs_dtype == GPSO_F64 ? 1 : 0; g.m = m; g.ld = m;
+  g.n = (int)ens_n; g.npad = kPadN; g.d = ens_d; g.dp = ens_dp; g.kernel = ens_kernel; g.k = k;
+  g.mean = as<double>(ens_mean); g.var = as<double>(ens_var);
+  if (launch_ensemble_members(*s, g) != 0) return launch_status();
+  double* mix = as<double>(ens_mix);
+  launch_ensemble_fold(*s, acq, g.mean, g.var, g.hyper, kEnsHyperStride, k, m, m, mix, mix + m, mix + 2 * m);
+  return launch_status();
+}
+
+int EngineCore::ensemble_acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double* mean_mix, double* var_mix,
+                                    double* value, double* member_mean, double* member_var, int out_mem) {
+  int rc = ensemble_refusals("gpso_ensemble_acq_values", xs, xs_dtype, xs_mem, m, acq);
+  if (rc) return rc;
+  if (!mean_mix && !var_mix && !value && !member_mean && !member_var)
+    return ctx->fail(GPSO_E_ARG, "gpso_ensemble_acq_values: every output is NULL");
+  hipStream_t s;
+  if ((rc = ensemble_enqueue(xs, xs_dtype, xs_mem, m, acq, &s))) return rc;
+  const hipMemcpyKind kind = out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const double* mix = as<double>(ens_mix);
+  const size_t col = (size_t)m * 8, cols = (size_t)ensemble_count() * col;
+  if (mean_mix) HIPCHECK(hipMemcpyAsync(mean_mix, mix, col, kind, s));
+  if (var_mix) HIPCHECK(hipMemcpyAsync(var_mix, mix + m, col, kind, s));
+  if (value) HIPCHECK(hipMemcpyAsync(value, mix + 2 * m, col, kind, s));
+  if (member_mean) HIPCHECK(hipMemcpyAsync(member_mean, ens_mean.p, cols, kind, s));
+  if (member_var) HIPCHECK(hipMemcpyAsync(member_var, ens_var.p, cols, kind, s));
+  return points_end(s, m);
+}
+
+// the folded columns feed the arg-max gpso_best_acq's general route runs (launch_seg_argmax): its segments (checked_segments,
+// that route's check), its first maximum, its NaN-wins rule.  One read-back of nseg records
+int EngineCore::ensemble_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
+                                  int64_t* idx, double* mean_mix, double* var_mix, double* value) {
+  int rc = ensemble_refusals("gpso_ensemble_best_acq", xs, xs_dtype, xs_mem, m, acq);
+  if (rc) return rc;
+  if (!idx) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_best_acq: idx must not be NULL");
+  if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "gpso_ensemble_best_acq: nseg=%d outside [1, 1024]", nseg);
+  std::vector<int64_t> so;
+  if ((rc = checked_segments(m, seg_off, nseg, so, "M"))) return rc;
+  const int nblk = argmax_blocks(m, nseg);
+  if ((rc = ensure(ens_seg, (size_t)(nseg + 1) * 8))) return rc;
+  if ((rc = ensure(ens_part, (size_t)nseg * kArgmaxBlocks * kArgmaxPartialBytes))) return rc;
+  if ((rc = ensure(ens_out, (size_t)(nseg * 4 + 2) * 8))) return rc;
+  hipStream_t s;
+  if ((rc = ensemble_enqueue(xs, xs_dtype, xs_mem, m, acq, &s))) return rc;
+  HIPCHECK(hipMemcpyAsync(ens_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+  const double* mix = as<double>(ens_mix);
+  launch_seg_argmax(s, mix, mix + m, mix + 2 * m, as<int64_t>(ens_seg), nseg, nblk, ens_part.p, as<double>(ens_out));
+  if ((rc = launch_status())) return rc;
+  std::vector<double> rec((size_t)nseg * 4);
+  HIPCHECK(hipMemcpyAsync(rec.data(), ens_out.p, rec.size() * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = points_end(s, m))) return rc;
+  for (int i = 0; i < nseg; ++i) {
+    if (mean_mix) mean_mix[i] = rec[(size_t)i * 4];
+    if (var_mix) var_mix[i] = rec[(size_t)i * 4 + 1];
+    if (value) value[i] = rec[(size_t)i * 4 + 2];
+    int64_t w;
+    std::memcpy(&w, &rec[(size_t)i * 4 + 3], 8);
+    idx[i] = w;
+  }
+  return GPSO_OK;
+}
+
 }  // namespace gpso::host

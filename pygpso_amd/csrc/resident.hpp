@@ -37,6 +37,9 @@ struct Resident {
   bool paths_valid = false;    // the path set of gpso_paths_draw / gpso_paths_draw_q (omega, b, w, v) belongs to this posterior as it stands
   bool q_factors = false;      // a variational install's Lu (Lf), beta (alpha_f) and root Q of q (vq_S / svq_S / sgM2) are still in their buffers
   bool screen_refused = false;  // a screened best-UCB call on this posterior was refused (a flat mean prunes nothing): it is not screened again
+  // ---- the hyper-parameter ensemble (ensemble.hpp): its members are posteriors of the resident DATA at other theta, so a
+  // refit leaves them alone and whatever changes the data, its noise vector or whose rows these are ends them: data_changed()
+  bool ensemble = false;
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -68,6 +71,10 @@ struct Resident {
     paths_valid = q_factors = screen_refused = false;
     if (!keep_peers) sync_n = -1;
   }
+  void ensemble_pushed() { ensemble = true; }     // gpso_ensemble_push succeeded
+  void ensemble_cleared() { ensemble = false; }  // gpso_ensemble_clear
+  // the rows, their targets or their noise are no longer what the ensemble's members were fitted on
+  void data_changed() { ensemble = false; }
   void screen_was_refused() { screen_refused = true; }  // posterior_dropped() and appended() end it
   // A new posterior begins (or an option changed): generation starts over -- float unless double was asked for --, the
   // ladder on its first rung, and the self-test rules again.  Not part of posterior_dropped(): new data, a new noise
@@ -81,16 +88,17 @@ struct Resident {
   // -- the data.  as_inducing: the rows are the Z that gpso_sgpr_set_inducing puts beside the stashed training set
   void new_data(bool as_inducing) {
     have_data = true;
+    data_changed();
     have_s = sg_factors = false;  // (the per-point noise belonged to the rows just replaced)
     sg_have_z = as_inducing;
     if (!as_inducing) sg_have = false;
     posterior_dropped();
   }
-  void noise_changed(bool have_vector) { have_s = have_vector; sg_factors = false; posterior_dropped(); }
+  void noise_changed(bool have_vector) { have_s = have_vector; sg_factors = false; data_changed(); posterior_dropped(); }
   void stashed() { sg_have = true; sg_have_z = false; }
-  void rows_unknown() { sg_have = sg_have_z = have_data = false; }  // an upload of Z failed half-way
-  void inducing_moved() { sg_factors = false; posterior_dropped(); }  // same M, in place: the data and q stay
-  void selection_begun() { sg_factors = false; posterior_dropped(true); }
+  void rows_unknown() { sg_have = sg_have_z = have_data = false; data_changed(); }  // an upload of Z failed half-way
+  void inducing_moved() { sg_factors = false; data_changed(); posterior_dropped(); }  // same M, in place: the data and q stay
+  void selection_begun() { sg_factors = false; data_changed(); posterior_dropped(true); }
   void bound_ready() { sg_factors = true; }  // gpso_sgpr_bound_u succeeded
   // -- the exact GP (each *_begun is followed by reset_generation)
   // rows: the tile rows of linv_p this fit writes (a one-launch fit's own; else 8) -> those that may hold older data
@@ -113,18 +121,20 @@ struct Resident {
   // the self-test looks at the extended posterior; the float copies of the inputs are derived again
   void appended(bool first_noise_vector) {
     have_s = have_s || first_noise_vector;
+    data_changed();
     have_kinv = st_done = gen32_inputs_ok = paths_valid = screen_refused = false;  // (v was solved against the shorter factor)
     small_tile_rows = 8;
   }
   void append_refused() { gen32_inputs_ok = false; }  // not PD: the scaled inputs were put back, their float copies not
   void install_begun() {  // y unknown: a later fit needs gpso_set_data (and gpso_set_noise_diag behind it)
     have_data = have_s = sg_have = sg_have_z = sg_factors = false;
+    data_changed();
     small_tile_rows = 8;  // (linv_p is about to be written whole)
     posterior_dropped();
   }
   void installed() { post = Post::Installed; chol_valid = true; linv_p = Copy::Valid; }
   // -- the variational families (reset_generation follows).  A VGP call leaves sg_factors alone, the sparse ones drop it
-  void variational_begun(bool sparse) { if (sparse) sg_factors = false; posterior_dropped(); }
+  void variational_begun(bool sparse) { if (sparse) sg_factors = false; data_changed(); posterior_dropped(); }
   // linv_p was written whole either way; ok: linv holds C = R L^-1 and every factorisation succeeded.  The install's own
   // factors stay where gpso_paths_draw_q reads them until variational_begun() -- every call that writes Lf, q or the sparse
   // factors starts with it -- or any other drop of the posterior: q_factors_kept() / posterior_dropped()
@@ -138,7 +148,7 @@ struct Resident {
   void recarved() { small_tile_rows = 8; linv_b = linv_p = Copy::Absent; }  // the arena's slices moved: another layout's bytes
   // gpso_alloc_posterior: as for gpso_set_posterior, the rows about to arrive are neither data nor inducing points of this
   // context.  have_s stays: the variational entry points refuse on it with GPSO_E_ARG before they look for data
-  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; posterior_dropped(); }
+  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; data_changed(); posterior_dropped(); }
   // slot 7 of the hyper block, which travels: 1 = float generation, 2 = GPSO_MATH_AUTO settled on the f32 MFMA kernel,
   // 4 = the split pieces are built, 8 = the packed L^-1 travels too, 16 = float generation keeps the f32 contraction,
   // 256 x the predict math (which split the pieces are: a receiver under GPSO_MATH_AUTO follows)
@@ -149,6 +159,7 @@ struct Resident {
   // generation arithmetic and predict math: the sender's choice (its self-test ruled), unless this context insists
   void adopted(int sender, bool float_predict, bool math_auto, int gen_mode, int64_t npad) {
     post = Post::Adopted;
+    data_changed();
     chol_valid = have_kinv = paths_valid = q_factors = screen_refused = false;
     small_tile_rows = 8;         // linv_p came from elsewhere
     st_done = st_have = false;   // the fitting rank ran the self-test; no targets here

@@ -950,6 +950,66 @@ class HipGPEngine:
                                               C.c_void_p(var.ctypes.data), C.c_void_p(val.ctypes.data), L.MEM_HOST))
         return mean, var, val
 
+    # -- the hyper-parameter ensemble (csrc/ensemble.hpp) -------------------------------------
+    def ensemble_max(self):
+        """Members an ensemble on the resident data may hold (32), or 0 where it does not apply."""
+        return int(self._lib.gpso_ensemble_max(self._h))
+
+    def ensemble_push(self):
+        """The resident posterior becomes the next member of the ensemble -> its index."""
+        return self._check(self._lib.gpso_ensemble_push(self._h))
+
+    def ensemble_clear(self):
+        self._check(self._lib.gpso_ensemble_clear(self._h))
+
+    def ensemble_info(self):
+        """-> (k, theta[k, 51]): per member 48 lengthscales, kernel variance, noise variance, constant mean."""
+        k = C.c_int(0)
+        theta = np.zeros((L.ENSEMBLE_MAX, L.ENSEMBLE_THETA), dtype=np.float64)
+        self._check(self._lib.gpso_ensemble_info(self._h, C.byref(k), L.dptr(theta)))
+        return int(k.value), theta[:k.value].copy()
+
+    def ensemble_best_acq(self, xs, acq, seg_off=None, incumbent=None):
+        """``best_acq`` under the integrated acquisition of the resident ensemble -> (idx, mean_mix, var_mix, value)
+        arrays of length nseg."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        nseg, so_ptr, _so = self._seg_args(seg_off)
+        rec = acq.c_struct(incumbent)
+        idx = np.empty(nseg, dtype=np.int64)
+        mean, var, val = (np.empty(nseg, dtype=np.float64) for _ in range(3))
+        self._check(self._lib.gpso_ensemble_best_acq(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec), L.i64ptr(idx),
+                                                     L.dptr(mean), L.dptr(var), L.dptr(val)))
+        return idx, mean, var, val
+
+    def ensemble_acq_values(self, xs, acq, incumbent=None, want_members=False):
+        """-> (mean_mix[M], var_mix[M], value[M]) float64 on the host; with ``want_members`` also the members' columns
+        (member_mean[K, M], member_var[K, M])."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec = acq.c_struct(incumbent)
+        mean, var, val = (np.empty(m, dtype=np.float64) for _ in range(3))
+        k = self.ensemble_info()[0] if want_members else 0
+        mm, mv = (np.empty((k, m), dtype=np.float64) for _ in range(2))
+        pm, pv = (C.c_void_p(a.ctypes.data) if want_members and k > 0 else None for a in (mm, mv))
+        self._check(self._lib.gpso_ensemble_acq_values(self._h, ptr, dt, mem, m, C.byref(rec), C.c_void_p(mean.ctypes.data),
+                                                       C.c_void_p(var.ctypes.data), C.c_void_p(val.ctypes.data), pm, pv, L.MEM_HOST))
+        return (mean, var, val, mm, mv) if want_members else (mean, var, val)
+
+    @staticmethod
+    def ensemble_fold_host(acq, member_mean, member_var, noise=None, incumbent=None):
+        """The device's fold on the CPU (``gpso_ensemble_fold_host``: no context, no GPU): member columns [K, M] and the
+        members' noise variances [K] -> (mean_mix[M], var_mix[M], value[M])."""
+        mm = L.as_f64(np.atleast_2d(member_mean))
+        mv = L.as_f64(np.atleast_2d(member_var), mm.shape)
+        k, m = mm.shape
+        nz = None if noise is None else L.as_f64(np.asarray(noise).reshape(-1), (k,))
+        mean, var, val = (np.empty(m, dtype=np.float64) for _ in range(3))
+        rec = acq.c_struct(incumbent)
+        rc = L.load().gpso_ensemble_fold_host(C.byref(rec), L.dptr(mm), L.dptr(mv), None if nz is None else L.dptr(nz), int(k), int(m),
+                                              L.dptr(mean), L.dptr(var), L.dptr(val))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_ensemble_fold_host: bad acquisition record (GPSO_ACQ_MES is not integrated) or arguments")
+        return mean, var, val
+
     @staticmethod
     def acq_eval_host(acq, mean, var, noise=0.0, incumbent=None):
         """The device's acquisition maps on the CPU (``gpso_acq_eval_host``: no context, no GPU) -> value[n]."""

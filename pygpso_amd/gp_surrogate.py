@@ -736,8 +736,28 @@ class GPRSurrogate(GPSurrogate):
 
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01),
                  gauss_likelihood_sigma=1.0e-3, points=None, gpflow_model=None, dtype="float64",
-                 device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml", gp_acquisition="ucb_var"):
+                 device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml", gp_acquisition="ucb_var",
+                 hyper="point", n_theta=16, hyper_priors=None, hyper_seed=0, hyper_options=None):
         """
+        :param hyper: "point" (default, the reference's way): every leaf is ranked under the one hyper-parameter vector the
+            search found.  "marginal" (NOT in the reference): the integrated acquisition of Snoek, Larochelle & Adams (2012)
+            -- ``gp_update`` runs the search with priors in the loss (a MAP search), draws ``n_theta`` samples of
+            p(theta | y) by HMC from the optimum (``HipGPR.sample_hyper``) and installs their posteriors as an ensemble on
+            the engine (``HipGPR.install_ensemble``); while it is resident ``gp_eval_best_ucb``, ``gp_eval_best_ucb_grow``,
+            ``gp_eval_best_acq``, ``gp_acq_values``, ``gp_predict`` (the mixture's moments) and the rescoring of
+            ``gp_update`` go through the integrated calls.  Every other method keeps reading the MAP posterior.  N <= 128,
+            "float64" / "mixed", one GPU, ``refit_every`` = 1, ``objective="nlml"``; MES and ``select_batch`` raise ValueError;
+            ``gp_update`` raises ValueError at the 129th evaluated point (``GPSOptimiser`` warns at construction when its
+            budget can get there).  ``gp_kernel`` and ``gp_meanf`` are deep-copied: the priors are attached to the copies,
+            never to the caller's objects (a model passed in as ``gpflow_model`` is the caller's and gets them).  Nothing of it is
+            saved: a surrogate loaded with ``from_saved`` is a "point" one until constructed otherwise
+        :param n_theta: members of the ensemble (1 .. 32)
+        :param hyper_priors: dictionary with the keys ``lengthscales``, ``variance``, ``noise``, ``mean`` of
+            ``pygpso_amd.priors`` objects; None: ``priors.default_priors()`` -- LogNormal(median 0.5, sigma 1) on the
+            lengthscales of the unit cube, LogNormal(1, 1.5) on the kernel variance, LogNormal(1e-3, 2) on the noise: choices,
+            not measurements
+        :param hyper_seed: seeds the sampler, together with the number of the update: the same seed gives the same run
+        :param hyper_options: keyword arguments of ``hyper_sampler.sample_theta`` (chains, burn, leapfrog, step, thin, ...)
         :param objective: what ``gp_update`` minimises over the hyper-parameters (NOT in the reference, which has the
             first only): "nlml" (default), the negative log marginal likelihood, or "loo", the leave-one-out log
             pseudo-likelihood (Rasmussen & Williams 5.4.2) -- the usual alternative when the kernel family is misspecified;
@@ -753,6 +773,13 @@ class GPRSurrogate(GPSurrogate):
             exceeds the fit's own average (NLML / N) by more than ``refit_guard`` nats per point the new points are
             surprising under theta and THIS update re-optimises instead of waiting for the c-th.  None: no guard
         """
+        if hyper == "marginal":
+            # (the priors are attached to the kernel and the mean function: the surrogate works on copies of its own, so that
+            # the caller's objects, which another surrogate or a bare HipGPR may share, never carry a prior they were not given)
+            import copy
+
+            gp_kernel = copy.deepcopy(gp_kernel)
+            gp_meanf = copy.deepcopy(gp_meanf)
         super().__init__(gp_kernel=gp_kernel, gp_meanf=gp_meanf, optimiser=optimiser,
                          varsigma=varsigma, gp_acquisition=gp_acquisition, points=points, gpflow_model=gpflow_model, dtype=dtype,
                          device=device, engine_options=engine_options, devices=devices)
@@ -764,6 +791,31 @@ class GPRSurrogate(GPSurrogate):
         self.refit_guard = None if refit_guard is None else float(refit_guard)
         self.guard_refits = 0  # updates the guard turned into re-optimisations
         self._updates = 0  # gp_update calls so far (refit_every counts them)
+        if hyper not in ("point", "marginal"):
+            raise ValueError(f"hyper must be 'point' or 'marginal', not {hyper!r}")
+        self.hyper = hyper
+        self.n_theta = int(n_theta)
+        self.hyper_priors = hyper_priors
+        self.hyper_seed = int(hyper_seed)
+        self.hyper_options = dict(hyper_options or {})
+        self._ensemble_live = False  # an ensemble drawn for the model's current data is resident on the engine
+        self.last_hyper_info = None  # the sampler's info of the last update
+        if hyper == "marginal":
+            if dtype == "float32":
+                raise ValueError("hyper='marginal' needs the dense double factor: dtype='float64' or 'mixed'")
+            if objective != "nlml":
+                raise ValueError("hyper='marginal' samples p(theta | y), the marginal likelihood times the priors: objective must be "
+                                 "'nlml' (exp(-LOO loss) is no likelihood of theta)")
+            if self.devices is not None and len(self.devices) > 1:
+                raise ValueError("hyper='marginal' runs on one GPU: the ensemble is not sharded over an engine group")
+            if not 1 <= self.n_theta <= 32:
+                raise ValueError(f"n_theta={n_theta}: 1..32 members")
+            if self.refit_every != 1:
+                raise ValueError("hyper='marginal' draws a new ensemble at every update: refit_every must be 1")
+            if hyper_priors is None:
+                from .priors import default_priors
+
+                self.hyper_priors = default_priors()
 
     @classmethod
     def default(cls, dtype="float64", device=0, engine_options=None, devices=None):
@@ -840,7 +892,99 @@ class GPRSurrogate(GPSurrogate):
                 if s is not None:
                     self.gpflow_model.noise_diag = s
         self._updates += 1
-        self.optimiser.minimize(self.gpflow_model.training_loss, self.gpflow_model.trainable_variables)
+        if self.hyper != "marginal":
+            self.optimiser.minimize(self.gpflow_model.training_loss, self.gpflow_model.trainable_variables)
+            return
+        # the search with the priors in the loss (MAP), the samples from its optimum, their posteriors on the engine
+        from . import priors
+
+        self._ensemble_live = False
+        model = self.gpflow_model
+        if x.shape[0] > 128:
+            raise ValueError(f"hyper='marginal' holds at most 128 evaluated points (N={x.shape[0]}): the ensemble's limit")
+        priors.attach(model, self.hyper_priors if self.hyper_priors is not None else priors.default_priors())
+        self.optimiser.minimize(model.training_loss, model.trainable_variables)
+        rng = np.random.default_rng([self.hyper_seed, self._updates])
+        U, self.last_hyper_info = model.sample_hyper(self.n_theta, rng=rng, **self.hyper_options)
+        installed, skipped = model.install_ensemble(U)
+        self.last_hyper_info["installed"], self.last_hyper_info["skipped"] = installed, skipped
+        self._ensemble_live = installed > 0
+
+    # -- hyper="marginal": the calls that rank or score leaves go through the integrated ones while an ensemble is resident --
+    def _refuse_marginal(self, what):
+        if self.hyper == "marginal":
+            raise ValueError(f"{what} is not available with hyper='marginal': it reads one hyper-parameter vector")
+
+    def gp_eval_best_ucb(self, normed_coords):
+        if not self._ensemble_live:
+            return super().gp_eval_best_ucb(normed_coords)
+        _, mean, var, ucb = self.gpflow_model.ensemble_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), self._loop_acquisition())
+        return float(mean[0]), float(var[0]), float(ucb[0])
+
+    def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
+        if not self._ensemble_live:
+            return super().gp_eval_best_ucb_grow(leaf_bounds, depth)
+        # (the integrated call takes rows, not boxes: the centres come from gpso_grow -- LeafNode.grow's bits -- and go back as
+        # one segment per box)
+        bounds = np.asarray(leaf_bounds, dtype=np.float64)
+        bounds = bounds[None] if bounds.ndim == 2 else bounds
+        coords = self.gpflow_model.engine.grow(bounds, depth)
+        nseg, rows, d = coords.shape
+        seg_off = np.arange(nseg + 1, dtype=np.int64) * rows
+        _, mean, var, ucb = self.gpflow_model.ensemble_best_acq(coords.reshape(nseg * rows, d), self._loop_acquisition(), seg_off)
+        return [(float(m), float(v), float(u)) for m, v, u in zip(mean, var, ucb)]
+
+    def gp_eval_best_acq(self, normed_coords, acquisition, incumbent=None, seg_off=None):
+        acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        if acq.name == "mes":
+            self._refuse_marginal("MES")
+        if not self._ensemble_live:
+            return super().gp_eval_best_acq(normed_coords, acquisition, incumbent, seg_off)
+        return self.gpflow_model.ensemble_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, seg_off, incumbent)
+
+    def gp_acq_values(self, normed_coords, acquisition, incumbent=None):
+        acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
+        if acq.name == "mes":
+            self._refuse_marginal("MES")
+        if not self._ensemble_live:
+            return super().gp_acq_values(normed_coords, acquisition, incumbent)
+        return self.gpflow_model.ensemble_acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, incumbent)
+
+    def mes_select(self, *args, **kwargs):
+        self._refuse_marginal("mes_select")
+        return super().mes_select(*args, **kwargs)
+
+    def max_value_samples(self, *args, **kwargs):
+        self._refuse_marginal("max_value_samples")
+        return super().max_value_samples(*args, **kwargs)
+
+    def select_batch(self, *args, **kwargs):
+        self._refuse_marginal("select_batch")
+        return super().select_batch(*args, **kwargs)
+
+    def gp_predict(self, normed_coords):
+        """``hyper="marginal"``: the moments of the ensemble's mixture at ``normed_coords`` and the integrated value of the
+        loop's acquisition -- what ``gp_eval_best_ucb`` ranks by --, stored as gp_based points."""
+        if not self._ensemble_live:
+            return super().gp_predict(normed_coords)
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        mean, var, val = self.gpflow_model.ensemble_acq_values(coords, self._loop_acquisition())
+        for i in range(coords.shape[0]):
+            self.points.append(GPPoint(normed_coords[i, :], float(mean[i]), float(var[i]), float(val[i]), PointLabels.gp_based))
+
+    def gp_update(self):
+        if self.hyper != "marginal":
+            return super().gp_update()
+        x_train, y_train = self.current_training_data
+        s_train = self.current_training_noise
+        if s_train is None:
+            self._gp_train(x=x_train, y=y_train[:, np.newaxis])
+        else:
+            self._gp_train(x=x_train, y=y_train[:, np.newaxis], s=s_train)
+        # the gp-based points are rescored under the new ensemble: re-appended, each overwrites its own entry (the reference's way)
+        idx = [i for i, p in enumerate(self.points) if p.label == PointLabels.gp_based]
+        if idx:
+            self.gp_predict(np.array([self.points[i].normed_coord for i in idx]))
 
     def loo_diagnostics(self):
         """Does the surrogate predict its own data?  The leave-one-out predictive of every evaluated point at the current

@@ -16,6 +16,9 @@ class Kernel:
     """Stationary kernel spec: ``lengthscales`` scalar (isotropic) or [D] (ARD), ``variance``."""
 
     name = None
+    # priors on the hyper-parameters (pygpso_amd.priors; None: no term in the training loss)
+    lengthscales_prior = None
+    variance_prior = None
 
     def __init__(self, variance=1.0, lengthscales=1.0):
         self.variance = float(variance)
@@ -53,7 +56,7 @@ KERNEL_CLASSES = {c.name: c for c in (Matern52, Matern32, Matern12, SquaredExpon
 
 
 class MeanFunction:
-    pass
+    c_prior = None  # prior on a trained constant (pygpso_amd.priors; None: no term)
 
 
 class Constant(MeanFunction):

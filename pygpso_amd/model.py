@@ -271,9 +271,47 @@ class HipGPR:
         return (self.kernel.name, np.atleast_1d(np.asarray(self.kernel.lengthscales, dtype=np.float64)),
                 self.kernel.variance, self.likelihood.variance, float(self.mean_function.c))
 
+    # -- priors (pygpso_amd/priors.py) --------------------------------------------------------------
+    def _prior_slots(self):
+        """One (prior, transform) per optimiser variable in ``_pack``'s order, or None when no prior is attached -- the
+        default, under which the loss is the device's number and nothing is added to it."""
+        from . import priors as P
+
+        ls, var = self.kernel.lengthscales_prior, self.kernel.variance_prior
+        noise = getattr(self.likelihood, "variance_prior", None)
+        mean = self.mean_function.c_prior if self._train_mean else None
+        if ls is None and var is None and noise is None and mean is None:
+            return None
+        slots = [(ls, P.SOFTPLUS)] * self.n_ls + [(var, P.SOFTPLUS), (noise, P.SOFTPLUS)]
+        if self._train_mean:
+            slots.append((mean, P.IDENTITY))
+        return slots
+
+    def neg_log_prior(self, u=None):
+        """-log p(theta(u)) - log |d theta / d u| at ``u`` (None: the current hyper-parameters); 0.0 without priors."""
+        from . import priors as P
+
+        slots = self._prior_slots()
+        if slots is None:
+            return 0.0
+        return P.neg_log_prior_u(self._pack() if u is None else u, slots)[0]
+
     # -- loss ---------------------------------------------------------------------------------
     def _loss_and_grad(self, u):
-        """f(u), df/du for L-BFGS-B: one device evaluation (Gram -> Cholesky -> ... -> gradient)."""
+        """f(u), df/du for L-BFGS-B: one device evaluation, plus -- where priors are attached -- the prior term and its
+        u-gradient, added on the host after the device has returned (GPflow 2's ``log_prior_density``, Jacobian included).
+        Without priors the device's numbers are returned as they came."""
+        f, gu = self._device_loss_and_grad(u)
+        slots = self._prior_slots()
+        if slots is None:
+            return f, gu
+        from . import priors as P
+
+        p, gp = P.neg_log_prior_u(u, slots)
+        return f + p, gu + gp
+
+    def _device_loss_and_grad(self, u):
+        """The objective and its u-gradient from the device: Gram -> Cholesky -> ... -> gradient."""
         self._device_theta = None
         k = self.n_ls
         if self.objective == "loo":
@@ -310,7 +348,17 @@ class HipGPR:
         (``Scipy(restarts=R)``) in one launch where the one-launch fit applies.  Returns (loss [B], grad [B, nu], ok [B]);
         a failed row (not positive definite) has ok False.  The batched launch leaves the device's posterior alone, so
         what the model knows about it stands; the row-by-row fallbacks (N > 128, an engine without the batched call) replace
-        it as any fit does."""
+        it as any fit does.  The prior term is added as in ``_loss_and_grad``."""
+        loss, grad, ok = self._device_loss_and_grad_batch(U)
+        slots = self._prior_slots()
+        if slots is None:
+            return loss, grad, ok
+        from . import priors as P
+
+        p, gp = P.neg_log_prior_u(np.atleast_2d(np.asarray(U, dtype=np.float64)), slots)
+        return loss + p, grad + gp, ok
+
+    def _device_loss_and_grad_batch(self, U):
         U = np.atleast_2d(np.asarray(U, dtype=np.float64))
         if self.objective == "loo" or not hasattr(self.engine, "fit_eval_u_batch"):
             # an engine without the batched call (a multi-GPU group, a test double), or the LOO objective (the batched
@@ -318,7 +366,7 @@ class HipGPR:
             loss, grad, ok = np.full(U.shape[0], np.nan), np.full(U.shape, np.nan), np.zeros(U.shape[0], dtype=bool)
             for b, u in enumerate(U):
                 try:
-                    loss[b], grad[b] = self._loss_and_grad(u)
+                    loss[b], grad[b] = self._device_loss_and_grad(u)
                     ok[b] = True
                 except np.linalg.LinAlgError:
                     self._device_theta = None
@@ -351,9 +399,12 @@ class HipGPR:
         the LOO-CV loss."""
         self._resident = False
         self._ensure_resident()
+        # (with priors attached the loss carries their term, as GPflow's training_loss does; log_marginal_likelihood never)
+        prior = self.neg_log_prior() if self._prior_slots() is not None else None
         if self.objective == "loo":
-            return self.engine.loo()[3]
-        return self._last_nlml
+            loss = self.engine.loo()[3]
+            return loss if prior is None else loss + prior
+        return self._last_nlml if prior is None else self._last_nlml + prior
 
     def log_marginal_likelihood(self):
         self._resident = False
@@ -559,6 +610,62 @@ class HipGPR:
         noise = self.predictive_noise() if obs_noise is None else obs_noise
         Xnew = np.asarray(Xnew)
         return self._predicting(lambda: self.engine.best_batch(Xnew, acq, q, float(noise), incumbent=inc, want_var_after=want_var_after))
+
+    # -- hyper-parameter uncertainty: samples of p(theta | y) and the ensemble of their posteriors --
+    def sample_hyper(self, n_samples, rng=None, **sampler_options):
+        """``n_samples`` draws U [K, nu] of the posterior over the optimiser's variables, by HMC from the current
+        hyper-parameters (``hyper_sampler.sample_theta`` over ``_loss_and_grad_batch``: one launch per leapfrog step for
+        all chains where ``fit_batch_max() > 0``; elsewhere -- N > 128, a multi-GPU group -- the same chains through the
+        row-by-row fallback: correct, and slower by the number of chains).  Needs a prior on at least one trained
+        parameter (``ValueError`` otherwise).  The model's hyper-parameters are not changed; the device's posterior may be
+        (the fallback fits row by row), and the next predict-type call refits where it has to.  Returns (U, info)."""
+        from .hyper_sampler import sample_theta
+
+        if self._loss_and_grad_batch is None:
+            raise NotImplementedError(f"sample_hyper is not available on {type(self).__name__}")
+        slots = self._prior_slots()
+        proper = slots is not None and any(p is not None for p, _ in slots)
+        return sample_theta(self._loss_and_grad_batch, self._pack(), n_samples, proper=proper, rng=rng, **sampler_options)
+
+    def install_ensemble(self, U):
+        """Make the posteriors at the rows of ``U [K, nu]`` (K <= 32) the engine's ensemble: per row one ``fit_eval_u`` and
+        one ``ensemble_push``, then one fit back at the model's own hyper-parameters, so that the resident posterior, its
+        hash and what the model knows of it are what they were.  A row whose matrix is not positive definite is skipped.
+        Returns (installed, skipped)."""
+        U = np.atleast_2d(np.asarray(U, dtype=np.float64))
+        if not hasattr(self.engine, "ensemble_push"):
+            raise NotImplementedError(f"the hyper-parameter ensemble is not available on {type(self.engine).__name__}")
+        if U.shape[0] > L.ENSEMBLE_MAX:
+            raise ValueError(f"install_ensemble: {U.shape[0]} rows, at most {L.ENSEMBLE_MAX}")
+        self.engine.ensemble_clear()
+        installed = skipped = 0
+        c_fixed = float(self.mean_function.c)
+        for u in U:
+            try:
+                self.engine.fit_eval_u(self.kernel.name, u, self.n_ls, self._train_mean, c_fixed)
+            except np.linalg.LinAlgError:
+                skipped += 1
+                continue
+            self.engine.ensemble_push()
+            installed += 1
+        # back at the model's own theta: the same fit the model would make, the same bits
+        self._device_theta = None
+        self._resident = False
+        self._ensure_resident()
+        return installed, skipped
+
+    def ensemble_size(self):
+        return self.engine.ensemble_info()[0] if hasattr(self.engine, "ensemble_info") else 0
+
+    def ensemble_best_acq(self, Xnew, acq, seg_off=None, incumbent=None):
+        """``best_acq`` under the integrated acquisition of the installed ensemble: (idx, mean_mix, var_mix, value)."""
+        inc = self._incumbent(acq, incumbent)
+        return self.engine.ensemble_best_acq(np.asarray(Xnew), acq, seg_off, incumbent=inc)
+
+    def ensemble_acq_values(self, Xnew, acq, incumbent=None, want_members=False):
+        """(mean_mix [M], var_mix [M], value [M]) of the installed ensemble (+ the members' columns [K, M])."""
+        inc = self._incumbent(acq, incumbent)
+        return self.engine.ensemble_acq_values(np.asarray(Xnew), acq, incumbent=inc, want_members=want_members)
 
     # -- reporting ----------------------------------------------------------------------------
     def parameter_dict(self):

@@ -80,6 +80,9 @@ class GPSOptimiser:
         self.callbacks = callbacks
         self.gp_surr = gp_surrogate or GPRSurrogate.default()
         assert isinstance(self.gp_surr, GPSurrogate)
+        if getattr(self.gp_surr, "hyper", "point") == "marginal" and stopping_condition == "evaluations" and budget > 128:
+            logging.warning(f"hyper='marginal' holds at most 128 evaluated points and the budget is {budget} evaluations: the update "
+                            "after the 128th will raise ValueError")
         self.saver = saver
         if saver is not None:
             assert callable(getattr(saver, "save_runs", None))
