@@ -886,6 +886,86 @@ int gpso_ensemble_fold_host(const gpso_acq* acq, const double* member_mean, cons
                             const double* noise /* [k] */, int k, int64_t m, double* mean_mix, double* var_mix,
                             double* value);
 
+/* ---- outcome constraints: J GP feasibility models and the constrained acquisition ------------
+ * No counterpart in the reference.  Gardner et al. (2014), Gelbart, Snoek & Adams (2014): every constrained output c_i(x)
+ * has an exact GP of its own, and a leaf is ranked by the objective's acquisition weighted or gated by the probability
+ * that the latent constraint functions are satisfied.
+ *
+ * The constraint set.  A context holds up to GPSO_CONSTRAINTS_MAX posteriors of OTHER targets in buffers of the set's own.
+ * gpso_constraint_push: the exact-GP posterior resident on `src` -- another context on the same device, or ctx itself --
+ *   becomes the next member; returns its index (>= 0) or a status (< 0).  The copy is gpso_ensemble_push's (hyper block,
+ *   scaled rows, dense double L^-1, alpha, kernel kind), device to device; src's stream is waited for; nothing is
+ *   computed.  sense = +1: feasible where c(x) <= threshold; sense = -1: feasible where c(x) >= threshold.
+ *   Where it applies is gpso_ensemble_push's rule, on src: an exact GP fitted there (with or without a noise vector, after
+ *   gpso_append too), N <= 128, D <= 48, GPSO_F64 or GPSO_MIXED on both contexts; all members share N, D and the kernel.
+ *   GPSO_E_ARG: a GPSO_F32 context (either); N > 128; different devices; NULL src; a sense other than +1 / -1; a threshold
+ *     that is not finite.
+ *   GPSO_E_STATE: no posterior on src, or a variational, sparse, installed or adopted one; a 17th member; a posterior whose
+ *     N, D or kernel disagrees with the members'; an asynchronous call open on either context.
+ * gpso_constraint_clear: no members.  GPSO_E_STATE while an asynchronous call is open.
+ * gpso_constraint_info: *k members; theta (nullable) [k * 51] as gpso_ensemble_info; threshold [k], sense [k] (nullable).
+ * gpso_constraint_max: GPSO_CONSTRAINTS_MAX where ctx can hold a set -- a GPSO_F64 or GPSO_MIXED context whose resident data,
+ *   if it has any yet, has N <= 128 (a push itself depends on src, and may come before ctx has data) --, else 0.
+ * Lifetime: the set belongs to the CONTEXT, not to its data -- a constraint model has its own targets.  gpso_set_data,
+ * gpso_append, a noise vector and a refit on ctx keep it; gpso_constraint_clear, gpso_alloc_posterior and gpso_destroy end
+ * it.  A constrained call whose objective's N, D or kernel differs from the members' is refused (GPSO_E_STATE): the set is
+ * stale.  The set is no part of gpso_posterior_hash, the packed copies, a broadcast, a path set or the ensemble; push, clear
+ * and the constrained calls leave all of those and the posterior bit for bit.
+ *
+ * The constrained calls.  The objective is the posterior resident on ctx (the same rule as a member: exact GP fitted here,
+ * N <= 128); its predictive columns (mean_j, var_j) and the members' (mean_ij, var_ij) come from the ensemble's stage 1
+ * (one launch on the context's own buffers, one over the set: nothing of size N^2 is copied per call).  Then per leaf j:
+ *     s2_i = max(var_ij - noise_i, 0);  z_i = sense_i (t_i - mean_ij) / sqrt(s2_i);  lp_i = log Phi(z_i)
+ *     (s2_i = 0: lp_i = 0 where sense_i (t_i - mean_ij) >= 0, else -inf)
+ *     logpof_j = sum_i lp_i          index order, from its first term; a NaN anywhere: NaN
+ *     a0 = acq's map on the objective (gpso_acq_values' value; a latent kind reads var_j - noise)
+ *   cspec.mode GPSO_CON_WEIGHT: EI, PI: value = a0 exp(logpof); LOGEI: value = l0 + logpof; -inf where logpof <
+ *     log_pof_min.  The UCB kinds are refused (GPSO_E_ARG): a signed value cannot be weighted.
+ *   GPSO_CON_GATE: value = a0 where logpof >= log_pof_min, else -inf; a0's own bits, in score units.  log_pof_min = -inf
+ *     (no gate) returns the unconstrained values of the same columns.
+ *   GPSO_CON_FEASIBILITY: value = logpof (the rule while no feasible point is known).
+ * log Phi is accurate far into the tail (finite to z = -1e150).  The same call gives the same bits: no atomics.
+ * gpso_constrained_best_acq: per segment (seg_off / nseg as gpso_best_ucb) the arg-max of value -- the first maximum wins,
+ *   a NaN beats every number -- with idx relative to the segment (-1 and NaNs for an empty one); mean / var / value /
+ *   logpof [nseg] host, nullable: the winner's entries of gpso_constrained_acq_values' columns, bit for bit.
+ * gpso_constrained_acq_values: mean / var / value / logpof [m] and member_mean / member_var [k * m] (member-major), each
+ *   nullable, in out_mem.
+ * gpso_constrained_fold_host: the fold alone on the host from given columns -- objective mean / var [m] and its noise
+ *   variance, member columns [k * m], member_noise / threshold / sense [k]: the same header, the same roundings; no
+ *   context and no GPU.  mean / var may be NULL in GPSO_CON_FEASIBILITY.  GPSO_OK or GPSO_E_ARG.
+ * GPSO_E_ARG: GPSO_ACQ_MES or another bad acq; a bad cspec (mode; log_pof_min NaN or > 0); a UCB kind in weight mode; a
+ *   GPSO_F32 context; N > 128; m < 1; (k + 1) * m > 2^28; bad dtype / memory; nseg outside [1, 1024] or bad seg_off; NULL xs,
+ *   idx, or every output.
+ * GPSO_E_STATE: no set; a stale set; no exact-GP posterior fitted on ctx; an ensemble resident on ctx; an asynchronous
+ *   best-UCB call open.
+ * gpso_last_ms(ctx, 1) covers a call; gpso_last_count(ctx, 0) and (ctx, 1) are m.
+ * Out of scope: N > 128, GPSO_F32, variational and sparse members, _begin / _end, grown leaves on the device, sharded and
+ * screened variants, gpso_best_batch under constraints, MES, the ensemble together with constraints. */
+#define GPSO_CONSTRAINTS_MAX 16
+#define GPSO_CON_WEIGHT 0
+#define GPSO_CON_GATE 1
+#define GPSO_CON_FEASIBILITY 2
+typedef struct {
+  int mode;           /* GPSO_CON_* */
+  double log_pof_min; /* <= 0; -INFINITY: no gate */
+} gpso_cspec;
+int gpso_constraint_max(gpso_ctx* ctx);
+int gpso_constraint_push(gpso_ctx* ctx, gpso_ctx* src, double threshold, int sense);
+int gpso_constraint_clear(gpso_ctx* ctx);
+int gpso_constraint_info(gpso_ctx* ctx, int* k, double* theta /* [k*(48+3)] */, double* threshold /* [k] */,
+                         int* sense /* [k], each nullable */);
+int gpso_constrained_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off,
+                              int nseg, const gpso_acq* acq, const gpso_cspec* cspec, int64_t* idx, double* mean,
+                              double* var, double* value, double* logpof);
+int gpso_constrained_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq,
+                                const gpso_cspec* cspec, double* mean, double* var, double* value,
+                                double* logpof /* [m], each nullable */, double* member_mean,
+                                double* member_var /* [k*m], nullable */, int out_mem);
+int gpso_constrained_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, const double* mean, const double* var,
+                               double noise, const double* member_mean, const double* member_var,
+                               const double* member_noise, const double* threshold, const int* sense, int k, int64_t m,
+                               double* value, double* logpof);
+
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 
 /* Centres of levels 0..depth-1 of the ternary subtree under each of nseg boxes, generated on the

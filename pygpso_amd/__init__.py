@@ -12,5 +12,6 @@ from .gp_surrogate import GPListOfPoints, GPPoint, GPRSurrogate, GPSurrogate, SG
 from .grids import conditional_surrogate_grids  # noqa: F401
 from .optimisation import GPSOCallback, GPSOptimiser  # noqa: F401
 from .param_space import LeafNode, ParameterSpace  # noqa: F401
+from .constraints import ConstrainedAcq, Constraint  # noqa: F401
 from .priors import LogNormal, Normal  # noqa: F401
 from .utils import PointLabels  # noqa: F401

@@ -50,6 +50,9 @@ GEN_F64, GEN_F32, GEN_AUTO = 0, 1, 2
 ACQ_UCB_VAR, ACQ_UCB_STD, ACQ_EI, ACQ_LOGEI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4, 5
 ENSEMBLE_MAX = 32  # members of a hyper-parameter ensemble; gpso_ensemble_info reports ENSEMBLE_THETA doubles per member
 ENSEMBLE_THETA = 48 + 3
+CONSTRAINTS_MAX = 16  # members of a context's constraint set; gpso_constraint_info reports ENSEMBLE_THETA doubles per member
+CON_WEIGHT, CON_GATE, CON_FEASIBILITY = 0, 1, 2  # gpso_cspec.mode
+CON_MODES = {"weight": CON_WEIGHT, "gate": CON_GATE, "feasibility": CON_FEASIBILITY}
 ACQ_MAX_MAXIMA = 64  # gpso_acq_set_maxima keeps at most this many; gpso_max_logcdf takes at most this many thresholds
 FITMATH_NONE, FITMATH_SMALL, FITMATH_F32, FITMATH_F64, FITMATH_BF16X6, FITMATH_F16X3 = 0, 1, 2, 3, 4, 5  # gpso_last_count(ctx, 2)
 GEN_IDS = {"float64": GEN_F64, "f64": GEN_F64, "float32": GEN_F32, "f32": GEN_F32, "auto": GEN_AUTO}
@@ -78,6 +81,14 @@ class GpsoAcq(C.Structure):
 
 
 _c_acq_p = C.POINTER(GpsoAcq)
+
+
+class GpsoCspec(C.Structure):
+    """``gpso_cspec``: how a constrained call combines the acquisition with the probability of feasibility."""
+    _fields_ = [("mode", C.c_int), ("log_pof_min", C.c_double)]
+
+
+_c_cspec_p = C.POINTER(GpsoCspec)
 
 # every symbol include/gpso_hip.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -191,6 +202,17 @@ SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "gpso_ensemble_fold_host": (C.c_int, [_c_acq_p, _c_double_p, _c_double_p, _c_double_p, C.c_int, C.c_int64, _c_double_p,
                                           _c_double_p, _c_double_p]),
+    "gpso_constraint_max": (C.c_int, [C.c_void_p]),
+    "gpso_constraint_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_int]),
+    "gpso_constraint_clear": (C.c_int, [C.c_void_p]),
+    "gpso_constraint_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _c_double_p, _c_double_p, C.POINTER(C.c_int)]),
+    "gpso_constrained_best_acq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, _c_acq_p,
+                                            _c_cspec_p, _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_constrained_acq_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_acq_p, _c_cspec_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gpso_constrained_fold_host": (C.c_int, [_c_acq_p, _c_cspec_p, _c_double_p, _c_double_p, C.c_double, _c_double_p, _c_double_p,
+                                             _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int, C.c_int64, _c_double_p,
+                                             _c_double_p]),
     "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,

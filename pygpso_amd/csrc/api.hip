@@ -2990,6 +2990,79 @@ int gpso_ensemble_fold_host(const gpso_acq* acq, const double* member_mean, cons
   return GPSO_OK;
 }
 
+// ---- outcome constraints (constraints.hpp) -------------------------------------------------------
+int gpso_constraint_max(gpso_ctx* ctx) { return ctx ? ctx->eng->constraint_max() : 0; }
+
+int gpso_constraint_push(gpso_ctx* ctx, gpso_ctx* src, double threshold, int sense) {
+  ENTER();
+  if (!src) return ctx->fail(GPSO_E_ARG, "gpso_constraint_push: src must not be NULL");
+  return ctx->eng->constraint_push(*src->eng, threshold, sense);
+}
+
+int gpso_constraint_clear(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->constraint_clear();
+}
+
+int gpso_constraint_info(gpso_ctx* ctx, int* k, double* theta, double* threshold, int* sense) {
+  if (!ctx) return GPSO_E_ARG;
+  return ctx->eng->constraint_info(k, theta, threshold, sense);
+}
+
+// what the constrained calls refuse about their two records before the engine looks at the context
+static const char* constrained_refusal(const gpso_acq* acq, const gpso_cspec* cspec) {
+  if (acq && acq->kind == GPSO_ACQ_MES) return "GPSO_ACQ_MES is not served under constraints";
+  if (const char* why = acq_refusal(acq)) return why;
+  if (!cspec) return "cspec must not be NULL";
+  if (cspec->mode != GPSO_CON_WEIGHT && cspec->mode != GPSO_CON_GATE && cspec->mode != GPSO_CON_FEASIBILITY) return "unknown cspec.mode";
+  if (cspec->log_pof_min != cspec->log_pof_min || cspec->log_pof_min > 0.0) return "cspec.log_pof_min must be a log-probability (<= 0; -inf: no gate)";
+  if (cspec->mode == GPSO_CON_WEIGHT && (acq->kind == GPSO_ACQ_UCB_VAR || acq->kind == GPSO_ACQ_UCB_STD))
+    return "a UCB kind is signed and cannot be weighted by a probability: use GPSO_CON_GATE, or EI / log-EI / PI";
+  return nullptr;
+}
+static gpso::ConSpec con_spec(const gpso_cspec* c) {
+  gpso::ConSpec s;
+  s.mode = c->mode;
+  s.log_pof_min = c->log_pof_min;
+  return s;
+}
+
+int gpso_constrained_best_acq(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                              const gpso_acq* acq, const gpso_cspec* cspec, int64_t* idx, double* mean, double* var, double* value,
+                              double* logpof) {
+  ENTER();
+  if (const char* why = constrained_refusal(acq, cspec)) return ctx->fail(GPSO_E_ARG, "gpso_constrained_best_acq: %s", why);
+  return ctx->eng->constrained_best_acq(xs, xs_dtype, xs_mem, m, seg_off, nseg, acq_spec(acq), con_spec(cspec), idx, mean, var, value, logpof);
+}
+
+int gpso_constrained_acq_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_acq* acq,
+                                const gpso_cspec* cspec, double* mean, double* var, double* value, double* logpof, double* member_mean,
+                                double* member_var, int out_mem) {
+  ENTER();
+  if (const char* why = constrained_refusal(acq, cspec)) return ctx->fail(GPSO_E_ARG, "gpso_constrained_acq_values: %s", why);
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "gpso_constrained_acq_values: bad out_mem %d", out_mem);
+  return ctx->eng->constrained_acq_values(xs, xs_dtype, xs_mem, m, acq_spec(acq), con_spec(cspec), mean, var, value, logpof, member_mean,
+                                          member_var, out_mem);
+}
+
+int gpso_constrained_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, const double* mean, const double* var, double noise,
+                               const double* member_mean, const double* member_var, const double* member_noise, const double* threshold,
+                               const int* sense, int k, int64_t m, double* value, double* logpof) {
+  if (constrained_refusal(acq, cspec) != nullptr || !member_mean || !member_var || !member_noise || !threshold || !sense || k < 1 ||
+      k > gpso::kConstraintsMax || m < 1 || noise != noise || (!value && !logpof))
+    return GPSO_E_ARG;
+  if (cspec->mode != GPSO_CON_FEASIBILITY && (!mean || !var)) return GPSO_E_ARG;
+  double thr[gpso::kConstraintsMax], sn[gpso::kConstraintsMax];
+  for (int i = 0; i < k; ++i) {
+    if ((sense[i] != 1 && sense[i] != -1) || !std::isfinite(threshold[i]) || member_noise[i] != member_noise[i]) return GPSO_E_ARG;
+    thr[i] = threshold[i];
+    sn[i] = (double)sense[i];
+  }
+  gpso::constrained_fold_host(acq_spec(acq), con_spec(cspec), mean, var, noise, member_mean, member_var, member_noise, thr, sn, k, (long long)m,
+                              value, logpof);
+  return GPSO_OK;
+}
+
 int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise, double obs_noise,
                            int64_t m, int q, int64_t* idx, double* var, double* value, int* n_picked, double* var_after) {
   if (acq_refusal(acq) != nullptr || m < 1 || q < 1 || q > gpso::kBatchMaxPicks || m > gpso::kBatchMaxCells / q || !mean || !s2 || !cov ||

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "batch.hpp"
+#include "constraints.hpp"
 #include "context.hpp"
 #include "devbuf.hpp"
 #include "ensemble.hpp"
@@ -672,6 +673,33 @@ struct EngineCore {
                           double* value, double* member_mean, double* member_var, int out_mem);
   int ensemble_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
                         int64_t* idx, double* mean_mix, double* var_mix, double* value);
+
+  // ---- outcome constraints (constraints.hpp, constraints.hip).  The set's copies -- kConstraintsMax
+  // slots each of a constraint model's hyper block, scaled rows, dense double L^-1 and alpha -- belong to the set and to
+  // nothing else: no fit, hand-off, hash, path set or ensemble reads them.  The set is the CONTEXT's, not its data's: the
+  // members have targets of their own, so res.constraints survives new data and refits and ends with gpso_constraint_clear
+  // and gpso_alloc_posterior; con_k, written by a push alone, counts the members while it holds (constraint_count()).  Then the calls' workspaces: the columns [1 + J][m]
+  // (row 0: the objective's), value and logpof [2][m], the segment offsets, the arg-max's partials and records, the
+  // winners' logpof
+  DevBuf con_hyper, con_xs, con_linv, con_alpha;
+  DevBuf con_mean, con_var, con_val, con_seg, con_part, con_out, con_win;
+  int con_k = 0, con_d = 0, con_dp = 0, con_kernel = 0;
+  int64_t con_n = 0;
+  std::vector<double> con_theta;  // [con_k][kEnsembleTheta]: what gpso_constraint_info reports
+  double con_thr[kConstraintsMax] = {}, con_sense[kConstraintsMax] = {};
+  int constraint_count() const { return res.constraints ? con_k : 0; }
+  // (a push depends on src, not on this context's data: a context without data yet can be given members.  Data of more than
+  // kEnsembleMaxN rows cannot be the objective of a constrained call, so the answer is 0 there)
+  int constraint_max() const { return (fit_elem == 8 && (!res.have_data || n <= kEnsembleMaxN)) ? kConstraintsMax : 0; }
+  int constraint_push(EngineCore& src, double threshold, int sense);
+  int constraint_clear();
+  int constraint_info(int* k, double* theta, double* threshold, int* sense) const;
+  int constrained_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con);
+  int constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s);
+  int constrained_acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, double* mean,
+                             double* var, double* value, double* logpof, double* member_mean, double* member_var, int out_mem);
+  int constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
+                           const ConSpec& con, int64_t* idx, double* mean, double* var, double* value, double* logpof);
 
   // ---- the variational and sparse families (engine_variational.hip says what each buffer holds) ----
   DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;  // the VGP: q(v) = N(mu, S S^T), three matrices, the vectors, the sums and verdicts

@@ -662,4 +662,209 @@ int EngineCore::ensemble_best_acq(const void* xs, int xs_dtype, int xs_mem, int6
   return GPSO_OK;
 }
 
+// ---- outcome constraints (constraints.hip).  A push copies what a point call reads of the posterior
+// resident on `src` -- this context or another on the same device -- into the next slot of THIS context's set: device to
+// device, nothing computed.  The constrained calls read the objective from the context's own buffers (a K = 1 launch of the
+// ensemble's stage 1: no copy, whatever was refitted) and the members from the set.  Every call here leaves both posteriors,
+// their packed copies, the hyper blocks, gpso_posterior_hash, a path set and an ensemble as they are
+namespace {
+// the ensemble's rule (section 7q) on the context `e`, in the words of the call `who`; what: whose posterior is meant
+int member_refusal(gpso_ctx* report, EngineCore& e, const char* who, const char* what) {
+  if (e.fit_elem != 8)
+    return report->fail(GPSO_E_ARG, "%s needs GPSO_F64 or GPSO_MIXED contexts -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double): %s is GPSO_F32", who, what);
+  if (!e.res.has_post()) return report->fail(GPSO_E_STATE, "%s: no posterior resident on %s: call gpso_fit_eval first", who, what);
+  if (e.res.post != Post::Fitted || !e.res.chol_valid || !e.res.have_data)
+    return report->fail(GPSO_E_STATE, "%s needs an exact-GP posterior fitted with targets on %s (gpso_set_data + gpso_fit_eval): a variational, "
+                                      "sparse, installed or adopted posterior is neither an objective nor a constraint model", who, what);
+  if (e.n > kEnsembleMaxN) return report->fail(GPSO_E_ARG, "%s: N=%lld on %s above the constraint set's %d", who, (long long)e.n, what, kEnsembleMaxN);
+  return GPSO_OK;
+}
+}  // namespace
+
+int EngineCore::constraint_push(EngineCore& src, double threshold, int sense) {
+  const char* who = "gpso_constraint_push";
+  if (src.ctx->device != ctx->device)
+    return ctx->fail(GPSO_E_ARG, "%s: src lives on device %d, ctx on device %d: a member is copied device to device on one device", who, src.ctx->device, ctx->device);
+  if (fit_elem != 8) return ctx->fail(GPSO_E_ARG, "%s needs GPSO_F64 or GPSO_MIXED contexts -- dtype=\"float64\" or \"mixed\": ctx is GPSO_F32", who);
+  if (sense != 1 && sense != -1) return ctx->fail(GPSO_E_ARG, "%s: sense=%d is neither +1 (feasible where c <= threshold) nor -1 (c >= threshold)", who, sense);
+  if (!std::isfinite(threshold)) return ctx->fail(GPSO_E_ARG, "%s: the threshold must be finite", who);
+  int rc = member_refusal(ctx, src, who, "src");
+  if (rc) return rc;
+  if ((rc = refuse_if_async(who))) return rc;
+  if (src.ctx->slots_busy() != 0)
+    return ctx->fail(GPSO_E_STATE, "%s while %d asynchronous best-UCB call(s) are open on src: gpso_best_ucb_end them first", who, src.ctx->slots_busy());
+  const int k = constraint_count();
+  if (k >= kConstraintsMax) return ctx->fail(GPSO_E_STATE, "%s: the set is full (%d members: GPSO_CONSTRAINTS_MAX)", who, kConstraintsMax);
+  if (k > 0 && (src.n != con_n || src.d != con_d || src.kp.kernel != con_kernel))
+    return ctx->fail(GPSO_E_STATE, "%s: the posterior on src (N=%lld, D=%d, kernel %d) disagrees with the set's members (N=%lld, D=%d, kernel %d): "
+                                   "gpso_constraint_clear first", who, (long long)src.n, src.d, src.kp.kernel, (long long)con_n, con_d, con_kernel);
+  // (k == 0: the slots may be re-allocated for another D_pad, nothing in them is kept; k > 0: the shape is the same, nothing grows)
+  const size_t b_xs = (size_t)src.npad * src.dp * 8, b_linv = (size_t)src.npad * src.npad * 8, b_alpha = (size_t)src.npad * 8,
+               b_hyper = (size_t)kEnsHyperStride * 8;
+  if ((rc = ensure(con_hyper, kConstraintsMax * b_hyper))) return rc;
+  if ((rc = ensure(con_xs, kConstraintsMax * b_xs))) return rc;
+  if ((rc = ensure(con_linv, kConstraintsMax * b_linv))) return rc;
+  if ((rc = ensure(con_alpha, kConstraintsMax * b_alpha))) return rc;
+  hipStream_t s = st();
+  const bool other = src.st() != s;
+  if (other) HIPCHECK(hipStreamSynchronize(src.st()));  // what src's fit enqueued is in its buffers
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(con_hyper.p) + k * b_hyper, src.hyper.p, b_hyper, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(con_xs.p) + k * b_xs, src.xs64.p, b_xs, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(con_linv.p) + k * b_linv, src.linv.p, b_linv, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(static_cast<char*>(con_alpha.p) + k * b_alpha, src.alpha_f.p, b_alpha, hipMemcpyDeviceToDevice, s));
+  if (other) HIPCHECK(hipStreamSynchronize(s));  // (src may be refitted the moment this returns: the copies have left it)
+  if (k == 0) {
+    con_n = src.n; con_d = src.d; con_dp = src.dp; con_kernel = src.kp.kernel;
+    con_theta.clear();
+  }
+  con_theta.resize((size_t)(k + 1) * kEnsembleTheta);
+  double* row = &con_theta[(size_t)k * kEnsembleTheta];
+  expand_ls(src.ls_host.data(), src.n_ls, row);
+  row[kMaxD] = src.kp.variance; row[kMaxD + 1] = src.kp.noise; row[kMaxD + 2] = src.kp.mean_c;
+  con_thr[k] = threshold;
+  con_sense[k] = (double)sense;
+  con_k = k + 1;
+  res.constraint_pushed();
+  return k;
+}
+
+int EngineCore::constraint_clear() {
+  int rc = refuse_if_async("gpso_constraint_clear");
+  if (rc) return rc;
+  con_k = 0;
+  res.constraints_cleared();
+  return GPSO_OK;
+}
+
+int EngineCore::constraint_info(int* k, double* theta, double* threshold, int* sense) const {
+  if (!k) return ctx->fail(GPSO_E_ARG, "k must not be NULL");
+  *k = constraint_count();
+  if (theta && *k > 0) std::memcpy(theta, con_theta.data(), (size_t)*k * kEnsembleTheta * 8);
+  for (int i = 0; i < *k; ++i) {
+    if (threshold) threshold[i] = con_thr[i];
+    if (sense) sense[i] = (int)con_sense[i];
+  }
+  return GPSO_OK;
+}
+
+// what both constrained calls refuse, before anything is allocated or enqueued
+int EngineCore::constrained_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con) {
+  if (acq.kind == GPSO_ACQ_MES) return ctx->fail(GPSO_E_ARG, "%s: GPSO_ACQ_MES is not served under constraints", who);
+  if (con.mode != GPSO_CON_WEIGHT && con.mode != GPSO_CON_GATE && con.mode != GPSO_CON_FEASIBILITY)
+    return ctx->fail(GPSO_E_ARG, "%s: cspec.mode=%d is none of GPSO_CON_WEIGHT, GPSO_CON_GATE, GPSO_CON_FEASIBILITY", who, con.mode);
+  if (con.log_pof_min != con.log_pof_min || con.log_pof_min > 0.0)
+    return ctx->fail(GPSO_E_ARG, "%s: cspec.log_pof_min must be a log-probability (<= 0; -inf: no gate)", who);
+  if (con.mode == GPSO_CON_WEIGHT && (acq.kind == GPSO_ACQ_UCB_VAR || acq.kind == GPSO_ACQ_UCB_STD))
+    return ctx->fail(GPSO_E_ARG, "%s: a UCB kind is signed and cannot be weighted by a probability: use GPSO_CON_GATE, or EI / log-EI / PI", who);
+  int rc = member_refusal(ctx, *this, who, "ctx (the objective)");
+  if (rc) return rc;
+  const int k = constraint_count();
+  if (k == 0) return ctx->fail(GPSO_E_STATE, "%s: no constraint set on this context: gpso_constraint_push first (gpso_alloc_posterior ends a set)", who);
+  if (ensemble_count() > 0)
+    return ctx->fail(GPSO_E_STATE, "%s: a hyper-parameter ensemble is resident on this context: constraints are not integrated over it "
+                                   "(gpso_ensemble_clear first)", who);
+  if (n != con_n || d != con_d || kp.kernel != con_kernel)
+    return ctx->fail(GPSO_E_STATE, "%s: the objective (N=%lld, D=%d, kernel %d) no longer has the shape of the set's members (N=%lld, D=%d, "
+                                   "kernel %d): the set is stale, gpso_constraint_clear and push models of the new rows",
+                     who, (long long)n, d, kp.kernel, (long long)con_n, con_d, con_kernel);
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "%s needs at least one leaf (m=%lld)", who, (long long)m);
+  if (m > ((int64_t)1 << 28) / (k + 1)) return ctx->fail(GPSO_E_ARG, "%s: (J + 1) * m above 2^28 (J=%d, m=%lld)", who, k, (long long)m);
+  if ((rc = check_points(xs, xs_dtype, xs_mem, m))) return rc;
+  return refuse_if_async(who);
+}
+
+// ... and what both enqueue behind their refusals: the workspaces, the columns (stage 1: one launch for the objective on the
+// context's own buffers, one for the J members) and the fold (stage 2).  On return the stream is open (points_begin),
+// con_mean / con_var hold [1 + J][m] with the objective in row 0, con_val holds value [m] then logpof [m]
+int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s) {
+  ctx->tick_timing();
+  const int k = constraint_count();
+  int rc;
+  if ((rc = ensure(con_mean, (size_t)(k + 1) * m * 8))) return rc;
+  if ((rc = ensure(con_var, (size_t)(k + 1) * m * 8))) return rc;
+  if ((rc = ensure(con_val, (size_t)2 * m * 8))) return rc;
+  if ((rc = points_begin(s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  EnsembleMembersLaunch g;
+  g.hyper = as<double>(hyper); g.xs = as<double>(xs64); g.linv = as<double>(linv); g.alpha = as<double>(alpha_f);
+  g.hyper_stride = kEnsHyperStride; g.leaves = dev; g.leaves_f64 = xs_dtype == GPSO_F64 ? 1 : 0; g.m = m; g.ld = m;
+  g.n = (int)n; g.npad = kPadN; g.d = d; g.dp = dp; g.kernel = kp.kernel; g.k = 1;
+  g.mean = as<double>(con_mean); g.var = as<double>(con_var);
+  if (launch_ensemble_members(*s, g) != 0) return launch_status();
+  EnsembleMembersLaunch c = g;
+  c.hyper = as<double>(con_hyper); c.xs = as<double>(con_xs); c.linv = as<double>(con_linv); c.alpha = as<double>(con_alpha);
+  c.n = (int)con_n; c.d = con_d; c.dp = con_dp; c.kernel = con_kernel; c.k = k;
+  c.mean = g.mean + m; c.var = g.var + m;
+  if (launch_ensemble_members(*s, c) != 0) return launch_status();
+  ConFoldLaunch f;
+  f.acq = acq; f.con = con;
+  f.obj_mean = g.mean; f.obj_var = g.var; f.obj_hyper = g.hyper;
+  f.cmean = c.mean; f.cvar = c.var; f.chyper = c.hyper; f.hyper_stride = kEnsHyperStride;
+  for (int i = 0; i < k; ++i) { f.thr[i] = con_thr[i]; f.sense[i] = con_sense[i]; }
+  f.nj = k; f.ld = m; f.m = m;
+  f.value = as<double>(con_val); f.logpof = f.value + m;
+  launch_constrained_fold(*s, f);
+  return launch_status();
+}
+
+int EngineCore::constrained_acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, double* mean,
+                                       double* var, double* value, double* logpof, double* member_mean, double* member_var, int out_mem) {
+  int rc = constrained_refusals("gpso_constrained_acq_values", xs, xs_dtype, xs_mem, m, acq, con);
+  if (rc) return rc;
+  if (!mean && !var && !value && !logpof && !member_mean && !member_var)
+    return ctx->fail(GPSO_E_ARG, "gpso_constrained_acq_values: every output is NULL");
+  hipStream_t s;
+  if ((rc = constrained_enqueue(xs, xs_dtype, xs_mem, m, acq, con, &s))) return rc;
+  const hipMemcpyKind kind = out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const double *cm = as<double>(con_mean), *cv = as<double>(con_var), *val = as<double>(con_val);
+  const size_t col = (size_t)m * 8, cols = (size_t)constraint_count() * col;
+  if (mean) HIPCHECK(hipMemcpyAsync(mean, cm, col, kind, s));
+  if (var) HIPCHECK(hipMemcpyAsync(var, cv, col, kind, s));
+  if (value) HIPCHECK(hipMemcpyAsync(value, val, col, kind, s));
+  if (logpof) HIPCHECK(hipMemcpyAsync(logpof, val + m, col, kind, s));
+  if (member_mean) HIPCHECK(hipMemcpyAsync(member_mean, cm + m, cols, kind, s));
+  if (member_var) HIPCHECK(hipMemcpyAsync(member_var, cv + m, cols, kind, s));
+  return points_end(s, m);
+}
+
+// the objective's columns and the folded value feed the arg-max gpso_best_acq's general route runs (launch_seg_argmax): its
+// segments (checked_segments, that route's check), its first maximum, its NaN-wins rule; a gather picks the winners' logpof.
+// One read-back of nseg records and nseg doubles
+int EngineCore::constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
+                                     const ConSpec& con, int64_t* idx, double* mean, double* var, double* value, double* logpof) {
+  int rc = constrained_refusals("gpso_constrained_best_acq", xs, xs_dtype, xs_mem, m, acq, con);
+  if (rc) return rc;
+  if (!idx) return ctx->fail(GPSO_E_ARG, "gpso_constrained_best_acq: idx must not be NULL");
+  if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "gpso_constrained_best_acq: nseg=%d outside [1, 1024]", nseg);
+  std::vector<int64_t> so;
+  if ((rc = checked_segments(m, seg_off, nseg, so, "M"))) return rc;
+  const int nblk = argmax_blocks(m, nseg);
+  if ((rc = ensure(con_seg, (size_t)(nseg + 1) * 8))) return rc;
+  if ((rc = ensure(con_part, (size_t)nseg * kArgmaxBlocks * kArgmaxPartialBytes))) return rc;
+  if ((rc = ensure(con_out, (size_t)(nseg * 4 + 2) * 8))) return rc;
+  if ((rc = ensure(con_win, (size_t)nseg * 8))) return rc;
+  hipStream_t s;
+  if ((rc = constrained_enqueue(xs, xs_dtype, xs_mem, m, acq, con, &s))) return rc;
+  HIPCHECK(hipMemcpyAsync(con_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+  const double* val = as<double>(con_val);
+  launch_seg_argmax(s, as<double>(con_mean), as<double>(con_var), val, as<int64_t>(con_seg), nseg, nblk, con_part.p, as<double>(con_out));
+  launch_constrained_gather(s, val + m, as<int64_t>(con_seg), as<double>(con_out), nseg, as<double>(con_win));
+  if ((rc = launch_status())) return rc;
+  std::vector<double> rec((size_t)nseg * 5);
+  HIPCHECK(hipMemcpyAsync(rec.data(), con_out.p, (size_t)nseg * 4 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(rec.data() + (size_t)nseg * 4, con_win.p, (size_t)nseg * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = points_end(s, m))) return rc;
+  for (int i = 0; i < nseg; ++i) {
+    if (mean) mean[i] = rec[(size_t)i * 4];
+    if (var) var[i] = rec[(size_t)i * 4 + 1];
+    if (value) value[i] = rec[(size_t)i * 4 + 2];
+    if (logpof) logpof[i] = rec[(size_t)nseg * 4 + i];
+    int64_t w;
+    std::memcpy(&w, &rec[(size_t)i * 4 + 3], 8);
+    idx[i] = w;
+  }
+  return GPSO_OK;
+}
+
 }  // namespace gpso::host

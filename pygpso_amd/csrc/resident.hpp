@@ -40,6 +40,10 @@ struct Resident {
   // ---- the hyper-parameter ensemble (ensemble.hpp): its members are posteriors of the resident DATA at other theta, so a
   // refit leaves them alone and whatever changes the data, its noise vector or whose rows these are ends them: data_changed()
   bool ensemble = false;
+  // ---- the constraint set (constraints.hpp): posteriors of OTHER targets, copied in from wherever they were fitted.  It
+  // belongs to the context, not to the resident data: new data, a refit, an append and an install leave it alone (a scoring
+  // call compares shapes); gpso_constraint_clear and gpso_alloc_posterior end it
+  bool constraints = false;
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -71,6 +75,8 @@ struct Resident {
     paths_valid = q_factors = screen_refused = false;
     if (!keep_peers) sync_n = -1;
   }
+  void constraint_pushed() { constraints = true; }      // gpso_constraint_push succeeded
+  void constraints_cleared() { constraints = false; }  // gpso_constraint_clear
   void ensemble_pushed() { ensemble = true; }     // gpso_ensemble_push succeeded
   void ensemble_cleared() { ensemble = false; }  // gpso_ensemble_clear
   // the rows, their targets or their noise are no longer what the ensemble's members were fitted on
@@ -148,7 +154,7 @@ struct Resident {
   void recarved() { small_tile_rows = 8; linv_b = linv_p = Copy::Absent; }  // the arena's slices moved: another layout's bytes
   // gpso_alloc_posterior: as for gpso_set_posterior, the rows about to arrive are neither data nor inducing points of this
   // context.  have_s stays: the variational entry points refuse on it with GPSO_E_ARG before they look for data
-  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; data_changed(); posterior_dropped(); }
+  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; data_changed(); constraints_cleared(); posterior_dropped(); }
   // slot 7 of the hyper block, which travels: 1 = float generation, 2 = GPSO_MATH_AUTO settled on the f32 MFMA kernel,
   // 4 = the split pieces are built, 8 = the packed L^-1 travels too, 16 = float generation keeps the f32 contraction,
   // 256 x the predict math (which split the pieces are: a receiver under GPSO_MATH_AUTO follows)

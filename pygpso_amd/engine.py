@@ -1010,6 +1010,85 @@ class HipGPEngine:
             raise L.GpsoHipError(rc, "gpso_ensemble_fold_host: bad acquisition record (GPSO_ACQ_MES is not integrated) or arguments")
         return mean, var, val
 
+    # -- outcome constraints (csrc/constraints.hpp) ------------------------------------------
+    def constraint_max(self):
+        """Members a constraint set on this context may hold (16), or 0 where a push does not apply."""
+        return int(self._lib.gpso_constraint_max(self._h))
+
+    def constraint_push(self, src, threshold, sense):
+        """The exact-GP posterior resident on ``src`` (another engine on this device, or ``self``) becomes the next
+        member of this context's constraint set -> its index.  ``sense`` +1: feasible where c <= threshold; -1: where
+        c >= threshold."""
+        return self._check(self._lib.gpso_constraint_push(self._h, src._h, float(threshold), int(sense)))
+
+    def constraint_clear(self):
+        self._check(self._lib.gpso_constraint_clear(self._h))
+
+    def constraint_info(self):
+        """-> (k, theta[k, 51], threshold[k], sense[k]); theta as ``ensemble_info``."""
+        k = C.c_int(0)
+        theta = np.zeros((L.CONSTRAINTS_MAX, L.ENSEMBLE_THETA), dtype=np.float64)
+        thr = np.zeros(L.CONSTRAINTS_MAX, dtype=np.float64)
+        sense = np.zeros(L.CONSTRAINTS_MAX, dtype=np.intc)
+        self._check(self._lib.gpso_constraint_info(self._h, C.byref(k), L.dptr(theta), L.dptr(thr),
+                                                   sense.ctypes.data_as(C.POINTER(C.c_int))))
+        return int(k.value), theta[:k.value].copy(), thr[:k.value].copy(), sense[:k.value].astype(np.int64)
+
+    @staticmethod
+    def _cspec(mode, log_pof_min):
+        return L.GpsoCspec(L.CON_MODES[mode] if isinstance(mode, str) else int(mode), float(log_pof_min))
+
+    def constrained_best_acq(self, xs, acq, mode="gate", log_pof_min=-np.inf, seg_off=None, incumbent=None):
+        """``best_acq`` under the resident constraint set -> (idx, mean, var, value, logpof) arrays of length nseg."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        nseg, so_ptr, _so = self._seg_args(seg_off)
+        rec, cs = acq.c_struct(incumbent), self._cspec(mode, log_pof_min)
+        idx = np.empty(nseg, dtype=np.int64)
+        mean, var, val, lp = (np.empty(nseg, dtype=np.float64) for _ in range(4))
+        self._check(self._lib.gpso_constrained_best_acq(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec), C.byref(cs), L.i64ptr(idx),
+                                                        L.dptr(mean), L.dptr(var), L.dptr(val), L.dptr(lp)))
+        return idx, mean, var, val, lp
+
+    def constrained_acq_values(self, xs, acq, mode="gate", log_pof_min=-np.inf, incumbent=None, want_members=False):
+        """-> (mean[M], var[M], value[M], logpof[M]) float64 on the host: the objective's predictive columns, the ranked
+        value and the log probability of feasibility; with ``want_members`` also the constraint models' columns
+        (member_mean[J, M], member_var[J, M])."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec, cs = acq.c_struct(incumbent), self._cspec(mode, log_pof_min)
+        mean, var, val, lp = (np.empty(m, dtype=np.float64) for _ in range(4))
+        k = self.constraint_info()[0] if want_members else 0
+        mm, mv = (np.empty((k, m), dtype=np.float64) for _ in range(2))
+        pm, pv = (C.c_void_p(a.ctypes.data) if want_members and k > 0 else None for a in (mm, mv))
+        self._check(self._lib.gpso_constrained_acq_values(self._h, ptr, dt, mem, m, C.byref(rec), C.byref(cs), C.c_void_p(mean.ctypes.data),
+                                                          C.c_void_p(var.ctypes.data), C.c_void_p(val.ctypes.data),
+                                                          C.c_void_p(lp.ctypes.data), pm, pv, L.MEM_HOST))
+        return (mean, var, val, lp, mm, mv) if want_members else (mean, var, val, lp)
+
+    @staticmethod
+    def constrained_fold_host(acq, mean, var, noise, member_mean, member_var, member_noise, threshold, sense, mode="gate",
+                              log_pof_min=-np.inf, incumbent=None):
+        """The device's constrained fold on the CPU (``gpso_constrained_fold_host``: no context, no GPU): the objective's
+        columns [M] and noise variance, the members' columns [J, M], noise variances, thresholds and senses [J] ->
+        (value[M], logpof[M])."""
+        mm = L.as_f64(np.atleast_2d(member_mean))
+        mv = L.as_f64(np.atleast_2d(member_var), mm.shape)
+        k, m = mm.shape
+        om, ov = L.as_f64(np.asarray(mean).reshape(-1), (m,)), L.as_f64(np.asarray(var).reshape(-1), (m,))
+        nz = L.as_f64(np.asarray(member_noise, dtype=np.float64).reshape(-1), (k,))
+        thr = L.as_f64(np.asarray(threshold, dtype=np.float64).reshape(-1), (k,))
+        sn = np.ascontiguousarray(np.asarray(sense).reshape(-1), dtype=np.intc)
+        if sn.shape != (k,):
+            raise ValueError(f"sense must have {k} entries")
+        val, lp = (np.empty(m, dtype=np.float64) for _ in range(2))
+        rec, cs = acq.c_struct(incumbent), HipGPEngine._cspec(mode, log_pof_min)
+        rc = L.load().gpso_constrained_fold_host(C.byref(rec), C.byref(cs), L.dptr(om), L.dptr(ov), float(noise), L.dptr(mm), L.dptr(mv),
+                                                 L.dptr(nz), L.dptr(thr), sn.ctypes.data_as(C.POINTER(C.c_int)), int(k), int(m),
+                                                 L.dptr(val), L.dptr(lp))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_constrained_fold_host: bad acquisition record (GPSO_ACQ_MES is not served, a UCB kind "
+                                     "cannot be weighted), constraint record or arguments")
+        return val, lp
+
     @staticmethod
     def acq_eval_host(acq, mean, var, noise=0.0, incumbent=None):
         """The device's acquisition maps on the CPU (``gpso_acq_eval_host``: no context, no GPU) -> value[n]."""

@@ -96,9 +96,35 @@ class GPListOfPoints(list):
         # GPPoint: keyed by the point's coordinate row, as the index above is; a point without an entry has variance 0
         self._noise = {}
         self.noise_given = False  # was a variance ever stored (``current_training_noise`` is None until then)
+        # observed values of the constrained outputs of an evaluated point (``GPRSurrogate(constraints=...)``), kept the same
+        # way: keyed by the point's coordinate row, empty unless constraints are in use
+        self._cvals = {}
         if args and isinstance(args[0], GPListOfPoints):  # (a copy of a store keeps its variances)
             self._noise = dict(args[0]._noise)
             self.noise_given = args[0].noise_given
+            self._cvals = dict(args[0]._cvals)
+
+    # -- observed constraint outputs (parallel store) -------------------------------------------------
+    def set_constraint_values_at(self, index, values):
+        """The J observed constraint outputs of the point stored at ``index``."""
+        values = tuple(float(v) for v in np.asarray(values, dtype=np.float64).reshape(-1))
+        if not all(math.isfinite(v) for v in values):
+            raise ValueError(f"constraint values {values} must be finite")
+        self._index()
+        self._cvals[self._rows[index]] = values
+
+    def constraint_values_at(self, index):
+        self._index()
+        return self._cvals.get(self._rows[index])
+
+    def constraint_matrix(self, label=None):
+        """[n, J] observed constraint outputs of the stored points (of ``label`` only when given), in list order; a point
+        without an entry raises (every evaluated point of a constrained run has one)."""
+        self._index()
+        rows = [self._cvals.get(self._rows[i]) for i, p in enumerate(self) if label is None or p.label == label]
+        if any(r is None for r in rows):
+            raise ValueError("an evaluated point has no constraint values: append(coords, scores, constraint_values=...) stores them")
+        return np.array(rows, dtype=np.float64).reshape(len(rows), -1)
 
     # -- per-point score variances (parallel store) ---------------------------------------------------
     def set_noise_at(self, index, variance):
@@ -737,8 +763,27 @@ class GPRSurrogate(GPSurrogate):
     def __init__(self, gp_kernel, gp_meanf=None, optimiser=None, varsigma=erfcinv(0.01),
                  gauss_likelihood_sigma=1.0e-3, points=None, gpflow_model=None, dtype="float64",
                  device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml", gp_acquisition="ucb_var",
-                 hyper="point", n_theta=16, hyper_priors=None, hyper_seed=0, hyper_options=None):
+                 hyper="point", n_theta=16, hyper_priors=None, hyper_seed=0, hyper_options=None,
+                 constraints=None, constraint_mode="gate", pof_min=0.5):
         """
+        :param constraints: a list of ``pygpso_amd.constraints.Constraint`` (NOT in the reference; None, the default: no
+            constraints, nothing changes).  The objective returns J further outputs beside the score; ``append`` takes them as
+            ``constraint_values`` [n, J] and keeps them beside the points.  ``gp_update`` trains one ``HipGPR`` per constraint
+            on the evaluated rows -- its own engine, deep copies of ``gp_kernel`` and ``gp_meanf`` as given here, the usual
+            search, warm-started from its last optimum -- and installs them as the engine's constraint set
+            (``HipGPR.install_constraints``).  While the set is resident ``gp_eval_best_ucb``, ``gp_eval_best_ucb_grow``,
+            ``gp_eval_best_acq``, ``gp_acq_values`` and the rescoring of ``gp_update`` go through the constrained calls
+            (Gardner et al. 2014; Gelbart, Snoek & Adams 2014): a leaf whose probability of feasibility is below ``pof_min`` is
+            worth -inf.  N <= 128, "float64" / "mixed", one GPU, ``refit_every`` = 1, ``hyper="point"``; MES and
+            ``select_batch`` raise ValueError.  Nothing of it is saved (``save`` raises while constraints are set).  The
+            constraint models are always trained on the marginal likelihood, whatever ``objective`` says of the scores' model:
+            the LOO objective was added for a misspecified model of the SCORE.  EI, log-EI and PI improve by default on the
+            best FEASIBLE observation (``highest_feasible_score``; Gardner et al. 2014), on the largest score while none is
+            feasible.  ``close_constraint_models()`` closes the models' engines
+        :param constraint_mode: how the loop's calls combine the acquisition with the probability of feasibility: "gate"
+            (default: the acquisition's own value, in score units, or -inf) -- the only mode under which the loop's
+            score-unit acquisition keeps its units; "weight" and "feasibility" serve ``constrained_select``
+        :param pof_min: the smallest probability of feasibility a leaf may have (0: no gate)
         :param hyper: "point" (default, the reference's way): every leaf is ranked under the one hyper-parameter vector the
             search found.  "marginal" (NOT in the reference): the integrated acquisition of Snoek, Larochelle & Adams (2012)
             -- ``gp_update`` runs the search with priors in the loss (a MAP search), draws ``n_theta`` samples of
@@ -816,6 +861,33 @@ class GPRSurrogate(GPSurrogate):
                 from .priors import default_priors
 
                 self.hyper_priors = default_priors()
+        self.constraints = []
+        self._constraint_models = None  # one HipGPR per constraint, in order, once trained
+        self._constraints_live = False  # models of the model's current rows are installed on the engine
+        if constraints:
+            import copy
+
+            from .constraints import ConstrainedAcq, Constraint
+
+            self.constraints = list(constraints)
+            if not all(isinstance(c, Constraint) for c in self.constraints):
+                raise TypeError("constraints must be pygpso_amd.constraints.Constraint objects")
+            if len(self.constraints) > 16:
+                raise ValueError(f"{len(self.constraints)} constraints: a constraint set holds at most 16 models")
+            if constraint_mode != "gate":
+                raise ValueError(f"constraint_mode={constraint_mode!r}: the loop's acquisition is in score units and only 'gate' keeps "
+                                 "them (use constrained_select for 'weight' and 'feasibility')")
+            if dtype == "float32":
+                raise ValueError("constraints need the dense double factor: dtype='float64' or 'mixed'")
+            if self.devices is not None and len(self.devices) > 1:
+                raise ValueError("constraints run on one GPU: the constraint set is not sharded over an engine group")
+            if self.refit_every != 1:
+                raise ValueError("constraints: every update retrains the constraint models on the objective's rows, refit_every must be 1")
+            if hyper != "point":
+                raise ValueError("constraints are not integrated over a hyper-parameter ensemble: hyper must be 'point'")
+            ConstrainedAcq(None, constraint_mode, pof_min)  # (validates pof_min)
+            self._constraint_specs = (copy.deepcopy(gp_kernel), copy.deepcopy(gp_meanf))
+        self.constraint_mode, self.pof_min = constraint_mode, float(pof_min)
 
     @classmethod
     def default(cls, dtype="float64", device=0, engine_options=None, devices=None):
@@ -833,8 +905,117 @@ class GPRSurrogate(GPSurrogate):
             devices=devices,
         )
 
-    def _gp_train(self, x, y, s=None):
-        """``s`` [N] (None: none): the known variance of each score, a fixed per-point noise term beside the trained one."""
+    # -- constraints=[...]: the observed constraint outputs ride beside the points, the models beside the objective's --
+    def append(self, coords, scores, score_vars=None, constraint_values=None):
+        """``constraint_values`` [n, J] (with ``constraints=`` only, and then required): the observed outputs of the J
+        constrained quantities at ``coords``, kept beside the points as the score variances are."""
+        if not self.constraints:
+            if constraint_values is not None:
+                raise ValueError("constraint_values given, but the surrogate was constructed without constraints=")
+            return super().append(coords, scores, score_vars)
+        if constraint_values is None:
+            raise ValueError(f"the surrogate has {len(self.constraints)} constraints: append needs constraint_values [n, J]")
+        cv = np.asarray(constraint_values, dtype=np.float64)
+        if cv.shape != (coords.shape[0], len(self.constraints)):
+            raise ValueError(f"constraint_values has shape {cv.shape}, not {(coords.shape[0], len(self.constraints))}")
+        if not np.all(np.isfinite(cv)):
+            raise ValueError("constraint_values must be finite")
+        for i in range(coords.shape[0]):
+            had = self.points.find_by_coords(coords[i])
+            if had is not None and had.label == PointLabels.evaluated:
+                continue  # (an evaluated duplicate keeps its score, and so its variance and its constraint values)
+            super().append(coords[i:i + 1], scores[i:i + 1], None if score_vars is None else score_vars[i:i + 1])
+            self.points.set_constraint_values_at(self.points.find_index_by_coords(coords[i]), cv[i])
+
+    @property
+    def current_training_constraints(self):
+        """[N, J] observed constraint outputs aligned with ``current_training_data``; None without constraints."""
+        return self.points.constraint_matrix(PointLabels.evaluated) if self.constraints else None
+
+    @property
+    def highest_feasible_score(self):
+        """The best evaluated point whose OBSERVED constraint outputs all keep their bounds (None: none does); without
+        constraints ``highest_score``."""
+        if not self.constraints:
+            return self.highest_score
+        from .constraints import feasible_rows
+
+        ev = self._with_label(PointLabels.evaluated)
+        if not ev:
+            return None
+        ok = feasible_rows(self.constraints, self.points.constraint_matrix(PointLabels.evaluated))
+        cand = [p for p, good in zip(ev, ok) if good]
+        return max(cand, key=lambda p: p.score_mu) if cand else None
+
+    def _constrained_incumbent(self, acq, incumbent):
+        """The incumbent of EI / log-EI / PI under constraints: the caller's, else the best score OBSERVED feasible -- an
+        infeasible high score as incumbent would flatten EI over the whole feasible region.  None (the model's default,
+        the largest training target) while no evaluated point is feasible or none carries constraint values."""
+        if incumbent is not None or not acq.needs_incumbent or acq.incumbent is not None or not self.points._cvals:
+            return incumbent
+        best = self.highest_feasible_score
+        return None if best is None else float(best.score_mu)
+
+    def close_constraint_models(self):
+        """Close the engines of the constraint models (each has a context of its own); the next ``gp_update`` opens new ones.
+        The set already copied onto the objective's engine stays usable."""
+        for model in self._constraint_models or []:
+            if getattr(model, "_owns_engine", False) and hasattr(model.engine, "close"):
+                model.engine.close()
+        self._constraint_models = None
+
+    def _constrained_acq(self, acq=None, mode=None):
+        from .constraints import ConstrainedAcq
+
+        return ConstrainedAcq(self._loop_acquisition() if acq is None else acq, self.constraint_mode if mode is None else mode, self.pof_min)
+
+    def _train_constraints(self, x, c):
+        """One HipGPR per constraint on the rows ``x`` with the column of ``c`` [N, J] as targets, then the set."""
+        import copy
+
+        self._constraints_live = False
+        if c is None:
+            raise ValueError(f"the surrogate has {len(self.constraints)} constraints: _gp_train needs their observed values c [N, J]")
+        c = np.asarray(c, dtype=np.float64)
+        if c.shape != (x.shape[0], len(self.constraints)):
+            raise ValueError(f"c has shape {c.shape}, not {(x.shape[0], len(self.constraints))}")
+        if x.shape[0] > 128:
+            raise ValueError(f"constraints hold at most 128 evaluated points (N={x.shape[0]}): the constraint set's limit")
+        if self._constraint_models is None:
+            kernel, meanf = self._constraint_specs
+            self._constraint_models = []
+            for j in range(len(self.constraints)):
+                engine = self.engine_factory() if self.engine_factory is not None else None
+                self._constraint_models.append(HipGPR(data=(x, c[:, j:j + 1]), kernel=copy.deepcopy(kernel), mean_function=copy.deepcopy(meanf),
+                                                      noise_variance=self.gp_lik_sigma, dtype=self.dtype, device=self.device, engine=engine,
+                                                      engine_options=self.engine_options))
+        else:
+            for j, model in enumerate(self._constraint_models):
+                model.data = (x, c[:, j:j + 1])  # hyper-parameters warm-start from the last optimum
+        for model in self._constraint_models:
+            self.optimiser.minimize(model.training_loss, model.trainable_variables)
+        self.gpflow_model.install_constraints(zip(self._constraint_models, self.constraints))
+        self._constraints_live = True
+
+    def constrained_select(self, leaves, acq=None, mode="weight", incumbent=None, seg_off=None):
+        """For use outside the loop: per segment of ``seg_off`` the row of ``leaves`` (normed coordinates) that the
+        constrained acquisition ranks first -- ``acq`` a name or a spec (None: the surrogate's own), ``mode`` "weight",
+        "gate" or "feasibility", the surrogate's ``pof_min``.  Returns (idx, mean, var, value, logpof).  Stores nothing."""
+        self._require_model()
+        if not self._constraints_live:
+            raise ValueError("constrained_select: no constraint models are installed (constraints= and one gp_update first)")
+        spec = self._loop_acquisition() if acq is None else resolve_acquisition(acq, varsigma=self.gp_varsigma)
+        return self.gpflow_model.constrained_best_acq(np.ascontiguousarray(leaves, dtype=np.float64), self._constrained_acq(spec, mode),
+                                                      seg_off, self._constrained_incumbent(spec, incumbent))
+
+    def _gp_train(self, x, y, s=None, c=None):
+        """``s`` [N] (None: none): the known variance of each score, a fixed per-point noise term beside the trained one.
+        ``c`` [N, J]: the observed constraint outputs (``constraints=`` only)."""
+        self._gp_train_objective(x, y, s)
+        if self.constraints:
+            self._train_constraints(x, c)
+
+    def _gp_train_objective(self, x, y, s=None):
         assert x.shape[0] == y.shape[0]
         assert x.ndim == 2 and y.ndim == 2
         if s is not None:
@@ -911,17 +1092,33 @@ class GPRSurrogate(GPSurrogate):
         self._ensemble_live = installed > 0
 
     # -- hyper="marginal": the calls that rank or score leaves go through the integrated ones while an ensemble is resident --
-    def _refuse_marginal(self, what):
+    def _refuse_unserved(self, what):
+        """What neither a hyper-parameter ensemble nor a constraint set serves (MES, batch selection) is refused in words."""
         if self.hyper == "marginal":
             raise ValueError(f"{what} is not available with hyper='marginal': it reads one hyper-parameter vector")
+        if self.constraints:
+            raise ValueError(f"{what} is not available with constraints: it is not served under a constraint set")
 
     def gp_eval_best_ucb(self, normed_coords):
+        if self._constraints_live:
+            _, mean, var, ucb, _ = self.gpflow_model.constrained_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64),
+                                                                          self._constrained_acq())
+            return float(mean[0]), float(var[0]), float(ucb[0])
         if not self._ensemble_live:
             return super().gp_eval_best_ucb(normed_coords)
         _, mean, var, ucb = self.gpflow_model.ensemble_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), self._loop_acquisition())
         return float(mean[0]), float(var[0]), float(ucb[0])
 
     def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
+        if self._constraints_live:
+            # (as below: the constrained call takes rows, the centres come from gpso_grow and go back as one segment per box)
+            bounds = np.asarray(leaf_bounds, dtype=np.float64)
+            bounds = bounds[None] if bounds.ndim == 2 else bounds
+            coords = np.asarray(self.gpflow_model.engine.grow(bounds, depth))
+            nseg, rows, d = coords.shape
+            seg_off = np.arange(nseg + 1, dtype=np.int64) * rows
+            _, mean, var, ucb, _ = self.gpflow_model.constrained_best_acq(coords.reshape(nseg * rows, d), self._constrained_acq(), seg_off)
+            return [(float(m), float(v), float(u)) for m, v, u in zip(mean, var, ucb)]
         if not self._ensemble_live:
             return super().gp_eval_best_ucb_grow(leaf_bounds, depth)
         # (the integrated call takes rows, not boxes: the centres come from gpso_grow -- LeafNode.grow's bits -- and go back as
@@ -937,7 +1134,10 @@ class GPRSurrogate(GPSurrogate):
     def gp_eval_best_acq(self, normed_coords, acquisition, incumbent=None, seg_off=None):
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
         if acq.name == "mes":
-            self._refuse_marginal("MES")
+            self._refuse_unserved("MES")
+        if self._constraints_live:
+            return self.gpflow_model.constrained_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), self._constrained_acq(acq),
+                                                          seg_off, self._constrained_incumbent(acq, incumbent))[:4]
         if not self._ensemble_live:
             return super().gp_eval_best_acq(normed_coords, acquisition, incumbent, seg_off)
         return self.gpflow_model.ensemble_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, seg_off, incumbent)
@@ -945,26 +1145,35 @@ class GPRSurrogate(GPSurrogate):
     def gp_acq_values(self, normed_coords, acquisition, incumbent=None):
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
         if acq.name == "mes":
-            self._refuse_marginal("MES")
+            self._refuse_unserved("MES")
+        if self._constraints_live:
+            return self.gpflow_model.constrained_acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), self._constrained_acq(acq),
+                                                            self._constrained_incumbent(acq, incumbent))[:3]
         if not self._ensemble_live:
             return super().gp_acq_values(normed_coords, acquisition, incumbent)
         return self.gpflow_model.ensemble_acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, incumbent)
 
     def mes_select(self, *args, **kwargs):
-        self._refuse_marginal("mes_select")
+        self._refuse_unserved("mes_select")
         return super().mes_select(*args, **kwargs)
 
     def max_value_samples(self, *args, **kwargs):
-        self._refuse_marginal("max_value_samples")
+        self._refuse_unserved("max_value_samples")
         return super().max_value_samples(*args, **kwargs)
 
     def select_batch(self, *args, **kwargs):
-        self._refuse_marginal("select_batch")
+        self._refuse_unserved("select_batch")
         return super().select_batch(*args, **kwargs)
 
     def gp_predict(self, normed_coords):
         """``hyper="marginal"``: the moments of the ensemble's mixture at ``normed_coords`` and the integrated value of the
         loop's acquisition -- what ``gp_eval_best_ucb`` ranks by --, stored as gp_based points."""
+        if self._constraints_live:  # (a gated point is stored with -inf: the loop never evaluates it)
+            coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+            mean, var, val, _ = self.gpflow_model.constrained_acq_values(coords, self._constrained_acq())
+            for i in range(coords.shape[0]):
+                self.points.append(GPPoint(normed_coords[i, :], float(mean[i]), float(var[i]), float(val[i]), PointLabels.gp_based))
+            return
         if not self._ensemble_live:
             return super().gp_predict(normed_coords)
         coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
@@ -973,6 +1182,15 @@ class GPRSurrogate(GPSurrogate):
             self.points.append(GPPoint(normed_coords[i, :], float(mean[i]), float(var[i]), float(val[i]), PointLabels.gp_based))
 
     def gp_update(self):
+        if self.constraints:
+            x_train, y_train = self.current_training_data
+            self._gp_train(x=x_train, y=y_train[:, np.newaxis], s=self.current_training_noise, c=self.current_training_constraints)
+            # the gp-based points are rescored under the new models and the gate: re-appended, each overwrites its own entry
+            # (the base class's in-place ``update_scores`` recomputes a score from (mean, var) alone and cannot gate)
+            idx = [i for i, p in enumerate(self.points) if p.label == PointLabels.gp_based]
+            if idx:
+                self.gp_predict(np.array([self.points[i].normed_coord for i in idx]))
+            return
         if self.hyper != "marginal":
             return super().gp_update()
         x_train, y_train = self.current_training_data
@@ -1031,6 +1249,9 @@ class GPRSurrogate(GPSurrogate):
         """Points, hyper-parameters and settings as JSON.  ``points_noise.json`` exists in ``folder`` afterwards exactly when
         some stored score variance is non-zero: it is written then, and otherwise a copy left by an earlier save is deleted
         (``GPListOfPoints.save_noise``)."""
+        if self.constraints:
+            raise ValueError("a surrogate with constraints is not saved: the observed constraint outputs and the constraint models have "
+                             "no place in the saved folder")
         os.makedirs(folder, exist_ok=True)
         self.points.save(os.path.join(folder, self.POINTS_FILE))
         self.points.save_noise(os.path.join(folder, self.POINTS_NOISE_FILE))

@@ -667,6 +667,52 @@ class HipGPR:
         inc = self._incumbent(acq, incumbent)
         return self.engine.ensemble_acq_values(np.asarray(Xnew), acq, incumbent=inc, want_members=want_members)
 
+    # -- outcome constraints: GP models of other outputs on this model's rows -----------------------
+    def install_constraints(self, models):
+        """Make ``models`` -- pairs ``(HipGPR, pygpso_amd.constraints.Constraint)``, each model trained on THIS model's
+        rows with the constrained output as its targets, on an engine of its own -- the engine's constraint set: per pair
+        one ``constraint_push`` (a device-to-device copy of the model's resident posterior; a fit there only if it is not
+        resident).  This model's own posterior is not touched.  Returns the number installed."""
+        if not hasattr(self.engine, "constraint_push"):
+            raise NotImplementedError(f"outcome constraints are not available on {type(self.engine).__name__}")
+        models = list(models)
+        if not 1 <= len(models) <= L.CONSTRAINTS_MAX:
+            raise ValueError(f"install_constraints: {len(models)} models, 1..{L.CONSTRAINTS_MAX}")
+        x = self._data[0]
+        for model, con in models:
+            if model._data[0].shape != x.shape or not np.array_equal(model._data[0], x):
+                raise ValueError(f"install_constraints: the model of {con.name!r} was trained on other rows than the objective's")
+        self.engine.constraint_clear()
+        for model, con in models:
+            model._ensure_resident()
+            self.engine.constraint_push(model.engine, con.threshold, con.sense)
+        return len(models)
+
+    def constraint_count(self):
+        return self.engine.constraint_info()[0] if hasattr(self.engine, "constraint_info") else 0
+
+    @staticmethod
+    def _constrained_args(cacq):
+        from .constraints import ConstrainedAcq
+
+        if not isinstance(cacq, ConstrainedAcq):
+            raise TypeError("a pygpso_amd.constraints.ConstrainedAcq is needed")
+        return cacq.acq, cacq.mode, cacq.log_pof_min
+
+    def constrained_best_acq(self, Xnew, cacq, seg_off=None, incumbent=None):
+        """``best_acq`` under the installed constraints (``cacq``: a ``ConstrainedAcq`` over an acquisition spec):
+        (idx, mean, var, value, logpof) per segment."""
+        acq, mode, lpm = self._constrained_args(cacq)
+        inc = self._incumbent(acq, incumbent)
+        return self._predicting(lambda: self.engine.constrained_best_acq(np.asarray(Xnew), acq, mode, lpm, seg_off, incumbent=inc))
+
+    def constrained_acq_values(self, Xnew, cacq, incumbent=None, want_members=False):
+        """(mean [M], var [M], value [M], logpof [M]) under the installed constraints (+ the models' columns [J, M])."""
+        acq, mode, lpm = self._constrained_args(cacq)
+        inc = self._incumbent(acq, incumbent)
+        return self._predicting(lambda: self.engine.constrained_acq_values(np.asarray(Xnew), acq, mode, lpm, incumbent=inc,
+                                                                          want_members=want_members))
+
     # -- reporting ----------------------------------------------------------------------------
     def parameter_dict(self):
         return {

@@ -74,6 +74,8 @@ class GPSOptimiser:
         self.n_eval_counter = 0
         self.iterations = 0
         self.eval_repeats_noise = False  # (``run``: store the variance of each aggregated score with its point)
+        self.constraints = []  # (``run(objective, constraints=[...])``: the objective returns (score, c_1 .. c_J))
+        self._last_constraint_values = None  # [n, J] of the evaluation just made, aggregated over the repeats like the scores
         self.n_workers = n_workers
         callbacks = callbacks or []
         assert all(isinstance(cb, GPSOCallback) for cb in callbacks)
@@ -138,7 +140,9 @@ class GPSOptimiser:
             all_scores = self.evaluate_objective_function(all_coords)
         self.param_space.score = float(all_scores[-1])
         self.param_space.label = PointLabels.evaluated
-        if self.eval_repeats_noise:
+        if self.constraints:
+            self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores, constraint_values=self._last_constraint_values)
+        elif self.eval_repeats_noise:
             self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores, score_vars=all_vars)
         else:
             self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores)
@@ -217,7 +221,11 @@ class GPSOptimiser:
             point = self._point_of(leaf)
             if point.label == PointLabels.gp_based:
                 orig = self.param_space.denormalise_coords(point.normed_coord[np.newaxis, :])
-                if self.eval_repeats_noise:
+                if self.constraints:
+                    new_score = float(self.evaluate_objective_function(orig)[0])
+                    self.gp_surr.append(point.normed_coord[np.newaxis, :], np.array([new_score]),
+                                        constraint_values=self._last_constraint_values)
+                elif self.eval_repeats_noise:
                     scores, variances = self.evaluate_objective_function(orig)
                     new_score = float(scores[0])
                     self.gp_surr.append(point.normed_coord[np.newaxis, :], np.array([new_score]),
@@ -231,6 +239,13 @@ class GPSOptimiser:
                 logging.debug(f"Leaf {leaf.name} updated to new evaluated score: {leaf.score}")
         logging.debug(f"Level to explore in the next iteration: {levels_to_explore}")
         return levels_to_explore
+
+    def _all_candidates_gated(self):
+        """Is every leaf the loop could still evaluate -- unsampled, gp-based -- worth -inf (or NaN)?"""
+        for node in self.param_space.iter_preorder():
+            if not node.sampled and node.label == PointLabels.gp_based and node.score > -np.inf:
+                return False
+        return True
 
     # -- objective -----------------------------------------------------------------------------
     def evaluate_objective_function(self, orig_coords):
@@ -253,6 +268,14 @@ class GPSOptimiser:
             for i, coords in enumerate(orig_coords):
                 self.saver.save_runs(results[i::n], scores[i::n],
                                      dict(zip(self.param_space.parameter_names, coords)))
+        if self.constraints:
+            # every evaluation returned (score, c_1 .. c_J): the repeats of each column are aggregated by the same function
+            cube = np.array(scores).astype(float).reshape((self.eval_repeats, orig_coords.shape[0], -1))
+            if cube.shape[2] != 1 + len(self.constraints):
+                raise ValueError(f"the objective must return (score, c_1 .. c_{len(self.constraints)}): got {cube.shape[2]} numbers")
+            agg = np.asarray(self.eval_repeats_function(cube))
+            self._last_constraint_values = agg[:, 1:]
+            return agg[:, 0]
         table = np.array(scores).astype(float).reshape((self.eval_repeats, -1))
         if self.eval_repeats_noise:
             # the variance of the MEAN of the repeats: what the aggregated score is known to, a fixed per-point noise term
@@ -272,7 +295,15 @@ class GPSOptimiser:
         while cond:
             self._run_callbacks(CallbackTypes.pre_iteration)
             self._tree_explore(levels_to_explore=explore_levels, seed=self.expl_seed)
+            evals_before = self.n_eval_counter
             explore_levels = self._tree_select()
+            if self.constraints and self.n_eval_counter == evals_before and self._all_candidates_gated():
+                # nothing was evaluated and no unsampled gp-based leaf is worth more than -inf: every candidate is gated.  The
+                # evaluated centres would go on being split without an evaluation ever being made, so the run ends here
+                logging.warning(f"every unsampled leaf has a probability of feasibility below pof_min={self.gp_surr.pof_min}: "
+                                f"nothing left to evaluate, ending the run after {self.iterations} iteration(s) (lower pof_min, or "
+                                "relax the constraints)")
+                break
             update_idx = self._gp_update(update_idx)
             self.iterations += 1
             highest_ucb = self.gp_surr.highest_ucb
@@ -288,6 +319,8 @@ class GPSOptimiser:
         self._run_callbacks(CallbackTypes.pre_finalise)
         self.last_explored_levels = explore_levels
         self.last_update_idx = update_idx
+        if self.constraints:  # (the best point that was OBSERVED to keep every bound; None when none did)
+            return self.gp_surr.highest_feasible_score
         return self.gp_surr.highest_score
 
     @staticmethod
@@ -300,14 +333,54 @@ class GPSOptimiser:
         if eval_repeats_function is not np.mean:
             raise ValueError("eval_repeats_noise is the variance of the mean of the repeats: eval_repeats_function must be np.mean")
 
+    def _set_constraints(self, constraints):
+        """``run``'s constraints: what does not go together with them is refused in words."""
+        self.constraints = list(constraints or [])
+        surr_has = list(getattr(self.gp_surr, "constraints", None) or [])
+        if not self.constraints:
+            if surr_has:
+                raise ValueError(f"the surrogate was constructed with {len(surr_has)} constraints: pass them to run(objective, constraints=[...]) "
+                                 "too (the objective must return their values)")
+            return
+        if not isinstance(self.gp_surr, GPRSurrogate):
+            raise ValueError(f"constraints are modelled by GPRSurrogate, not by {type(self.gp_surr).__name__}")
+        if self.saver is not None:
+            raise ValueError("constraints and a saver: the saver's (result, score) pairs have no place for the constraint outputs")
+        if self.eval_repeats_noise:
+            raise ValueError("constraints and eval_repeats_noise: per-point noise of the constraint outputs is not modelled")
+        if self.gp_surr.refit_every != 1:
+            raise ValueError("constraints: refit_every must be 1 (every update retrains the constraint models)")
+        if getattr(self.gp_surr, "hyper", "point") != "point":
+            raise ValueError("constraints are not integrated over a hyper-parameter ensemble: hyper must be 'point'")
+        if self.method != "tree":
+            raise ValueError("constraints drive the tree exploration only")
+        if surr_has:
+            same = len(surr_has) == len(self.constraints) and all(
+                (a.name, a.threshold, a.sense) == (b.name, b.threshold, b.sense) for a, b in zip(surr_has, self.constraints))
+            if not same:
+                raise ValueError("run(constraints=...) differs from the list the surrogate was constructed with")
+        else:
+            raise ValueError("run(constraints=...) needs a surrogate that models them: construct it as GPRSurrogate(constraints=[...]) "
+                             "with the same list")
+
     def run(self, objective_function, init_samples=None, eval_repeats=1, eval_repeats_function=np.mean,
-            eval_repeats_noise=False, **kwargs):
-        """``eval_repeats_noise`` (not in the reference): with ``eval_repeats`` >= 2 and the mean as the aggregate, store
+            eval_repeats_noise=False, constraints=None, **kwargs):
+        """``constraints`` (not in the reference): a list of ``pygpso_amd.constraints.Constraint``.  The objective then
+        returns ``(score, c_1 .. c_J)``; initial samples and selected leaves store both, repeats aggregate the constraint
+        outputs with the same function as the scores, and leaves are ranked in gate mode under the surrogate's score-unit
+        acquisition (the surrogate must have been constructed with the same list: ``GPRSurrogate(constraints=...)``).  A gated leaf is never evaluated.
+        A leaf is scored by the best centre of its sub-tree (``exploration_depth`` levels) and evaluated at its own centre, as
+        without constraints: with ``exploration_depth`` > 1 the gate a leaf passed is its best sub-leaf's, so the evaluated
+        point itself may have a probability of feasibility below ``pof_min``; only with ``exploration_depth`` = 1 is every
+        evaluated point one that passed the gate.  An iteration in which every candidate is gated ends the run with a warning.  Returns the best point observed feasible (None: none was).  Refused with
+        constraints: a saver, ``save_state``, ``refit_every`` > 1, ``hyper="marginal"``, ``eval_repeats_noise``.
+        ``eval_repeats_noise`` (not in the reference): with ``eval_repeats`` >= 2 and the mean as the aggregate, store
         the variance of each mean score, var(repeats, ddof=1) / eval_repeats, with its point; the surrogate then models it
         as a fixed per-point noise term beside the trained one (``GPRSurrogate``).  False: the reference's behaviour."""
         assert callable(objective_function)
         self._check_repeats_noise(eval_repeats_noise, eval_repeats, eval_repeats_function)
         self.eval_repeats_noise = bool(eval_repeats_noise)
+        self._set_constraints(constraints)
         self.obj_func = objective_function
         self.eval_repeats = eval_repeats
         assert callable(eval_repeats_function)
@@ -332,6 +405,9 @@ class GPSOptimiser:
 
     # -- persistence -----------------------------------------------------------------------------
     def save_state(self, folder):
+        if self.constraints:
+            raise ValueError("a run with constraints is not saved (save_state / resume_from_saved): the constraint outputs and models "
+                             "have no place in the saved folder")
         os.makedirs(folder, exist_ok=True)
         logging.warning("When saving, all callbacks and saver will be lost!")
         self.param_space.save(os.path.join(folder, self.PARAM_SPACE_FILE))
