@@ -332,13 +332,24 @@ int gpso_set_posterior(gpso_ctx* ctx, const double* X, const double* L, const do
  * installs the predictive variance var_f + scale^2 df / (df - 2).  Under either quadrature kind S S^T can exceed I in a
  * direction; the install then serves var_f + delta (k** - |L^-1 k*|^2), delta the first of 0, 1e-8, 2e-8, ... for which
  * I - S S^T / (1 + delta) factorises: never below var_f, at most delta k** above it.  GPSO_LIK_GAUSSIAN_GH: the Gaussian through the
- * same quadrature sequence as the Student-t (u as GPSO_LIK_GAUSSIAN): a check of that sequence against the closed form. */
+ * same quadrature sequence as the Student-t (u as GPSO_LIK_GAUSSIAN): a check of that sequence against the closed form.
+ * GPSO_LIK_BERNOULLI: a GP classifier.  The targets of gpso_set_data are labels: a point is a success
+ * (s = +1) iff y > 0.5, otherwise s = -1, and log p(y | f) = log Phi(s f), the EXACT probit -- not GPflow's inv_probit, which
+ * mixes a 1e-3 jitter in; the exact one is log-concave.  It has no parameter: slot n_ls + 1 of u stays in the vector (one
+ * layout), is decoded as GPSO_LIK_GAUSSIAN's and read by nothing; grad_u[n_ls + 1] is exactly 0.0.  Every gpso_vgp_* call
+ * serves it through the quadrature sequence.  gpso_vgp_posterior installs noise 0: gpso_predict and every leaf call on the
+ * context then return the LATENT mean and variance of f, and gpso_predict_prob (below) maps them to P(success).  With a
+ * log-concave likelihood S S^T stays below I and the shift delta is 0.  The sparse family does not serve it: every gpso_svgp_*
+ * call returns GPSO_E_ARG while it is set.  The kind has no df: gpso_vgp_set_likelihood takes df = 0 with it and answers
+ * GPSO_E_ARG to any other value (kind 3 with a df was refused before the kind existed, a test of the Student-t's arguments
+ * holds the library to that, and so it stays refused: DESIGN.md section 7s). */
 #define GPSO_LIK_GAUSSIAN 0
 #define GPSO_LIK_STUDENT_T 1
 #define GPSO_LIK_GAUSSIAN_GH 2
+#define GPSO_LIK_BERNOULLI 3
 
 /* Replaces: choosing the likelihood of gpflow.models.VGP(likelihood=...) (gpso/gp_surrogate.py:536-541).  kind:
- * GPSO_LIK_*; df: the Student-t's degrees of freedom (> 2; ignored otherwise); gh_x[n_gh], gh_w[n_gh]: the Gauss-Hermite
+ * GPSO_LIK_*; df: the Student-t's degrees of freedom (> 2; 0 under GPSO_LIK_BERNOULLI; ignored otherwise); gh_x[n_gh], gh_w[n_gh]: the Gauss-Hermite
  * nodes and weights of numpy.polynomial.hermite.hermgauss(n_gh) (GPflow's 20 points), 1 <= n_gh <= 64 (both ignored
  * for GPSO_LIK_GAUSSIAN).  Anything else: GPSO_E_ARG.  Takes effect at the next gpso_vgp_* call; q is kept.  The
  * same setting is the likelihood of the sparse variational GP (gpso_svgp_*, below).
@@ -965,6 +976,57 @@ int gpso_constrained_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, con
                                double noise, const double* member_mean, const double* member_var,
                                const double* member_noise, const double* threshold, const int* sense, int k, int64_t m,
                                double* value, double* logpof);
+
+/* ---- failed evaluations: the success probability and the success member ------------------------
+ * No counterpart in the reference.  Gelbart, Snoek & Adams (2014), the constraint that is only observed as "it worked / it
+ * did not": a GP classifier (a VGP under GPSO_LIK_BERNOULLI, installed by gpso_vgp_posterior) of whether an evaluation
+ * returns a finite score, and its probability of success weighting or gating the acquisition.
+ *
+ * gpso_success_prob_host: the probit map alone on the host, no context and no GPU: for n latent (mean, var) pairs
+ *   logprob = log Phi(mean / sqrt(1 + max(var, 0))) and prob = exp(logprob), the device's text and roundings; a NaN in gives
+ *   a NaN out.  logprob / prob nullable, not both.  GPSO_OK or GPSO_E_ARG.
+ * gpso_predict_prob: P(success) at m points of the Bernoulli install resident on ctx.  Stage 1 is the ensemble's member
+ *   kernel with K = 1 on the context's own buffers (the latent mean and variance), then one thread per point of the map above.
+ *   prob / logprob / mean / var [m] in out_mem, each nullable, not all.  Where it applies is gpso_ensemble_push's rule: N <= 128,
+ *   D <= 48, GPSO_F64 or GPSO_MIXED.
+ *   GPSO_E_ARG: a GPSO_F32 context; N > 128; m < 1 or > 2^28; bad dtype / memory; NULL xs; every output NULL.
+ *   GPSO_E_STATE: no posterior, or any other than a Bernoulli install (a Gaussian or Student-t VGP, an exact GP, a sparse,
+ *     installed or adopted one); an asynchronous best-UCB call open.
+ * gpso_success_push: the Bernoulli install resident on `src` (a context on the same device) is copied into the ONE slot of the
+ *   success member on ctx: the four device-to-device copies of gpso_constraint_push (hyper block, scaled rows, dense double C,
+ *   beta), nothing computed; a member already there is replaced.  The member's N and kernel may differ from the objective's --
+ *   the classifier is trained on failed points the objective never sees --, D must agree, N <= 128.
+ *   GPSO_E_ARG: a GPSO_F32 context (either); N > 128; different devices; NULL src; D on src differing from the data on ctx.
+ *   GPSO_E_STATE: src holds no Bernoulli install; an asynchronous call open on either context.
+ * gpso_success_clear: no member.  GPSO_E_STATE while an asynchronous call is open.
+ * gpso_success_info: *present 0 / 1; *n (nullable) the member's N; theta (nullable) [51] as a row of gpso_ensemble_info.
+ * Lifetime: the constraint set's.  The member belongs to the CONTEXT: gpso_set_data, gpso_append and refits of the objective
+ * keep it; gpso_success_clear, gpso_alloc_posterior and gpso_destroy end it.  It is no part of gpso_posterior_hash, the packed
+ * copies, a broadcast, a path set, the ensemble, the constraint set's count or gpso_constraint_info; push and clear leave both
+ * posteriors bit for bit.
+ *
+ * While a member is resident gpso_constrained_acq_values and gpso_constrained_best_acq take it in: one more K = 1 stage-1
+ * launch with the member's own N and kernel writes row 1 + J of the [1 + J + 1][m] workspace, and the fold adds
+ * log Phi(mean_s / sqrt(1 + var_s)) to logpof as its LAST term, behind the J constraints in index order; the sum still starts
+ * at its first term, so with J = 0 the success term IS logpof.  J = 0 is served when, and only when, a member is resident.
+ * Modes, kinds, the gate, the NaN rules, the arg-max and the gather are unchanged.  gpso_constrained_acq_values' member_mean /
+ * member_var then hold [(J + 1) * m]: the member's latent columns follow the constraints'.  A member whose D differs from the
+ * objective's: GPSO_E_STATE.
+ * gpso_constrained_success_fold_host: that fold on the host, as gpso_constrained_fold_host with success_mean / success_var
+ *   [m]; k may be 0 (the member arrays are then not read).
+ * Out of scope: the sparse families as classifier, N > 128, GPSO_F32, _begin / _end, grown leaves, sharded and screened
+ * variants, gpso_best_batch, MES, the ensemble. */
+int gpso_success_prob_host(const double* mean, const double* var, int64_t n, double* logprob, double* prob);
+int gpso_predict_prob(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* prob, double* logprob,
+                      double* mean, double* var /* [m], each nullable */, int out_mem);
+int gpso_success_push(gpso_ctx* ctx, gpso_ctx* src);
+int gpso_success_clear(gpso_ctx* ctx);
+int gpso_success_info(gpso_ctx* ctx, int* present, int64_t* n, double* theta /* [48+3], nullable */);
+int gpso_constrained_success_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, const double* mean, const double* var,
+                                       double noise, const double* member_mean, const double* member_var,
+                                       const double* member_noise, const double* threshold, const int* sense, int k,
+                                       int64_t m, const double* success_mean, const double* success_var, double* value,
+                                       double* logpof);
 
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 

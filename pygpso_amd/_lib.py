@@ -25,8 +25,8 @@ UNIQUE_ID_BYTES = 128
 MAT_CHOL, MAT_LINV, MAT_KINV, MAT_GRAM = 0, 1, 2, 3
 VEC_ALPHA, VEC_WHITE, VEC_NOISE_DIAG = 0, 1, 2
 SGPR_KUF, SGPR_LU, SGPR_LB, SGPR_CV = 0, 1, 2, 3
-LIK_GAUSSIAN, LIK_STUDENT_T, LIK_GAUSSIAN_GH = 0, 1, 2
-LIKELIHOOD_IDS = {"Gaussian": LIK_GAUSSIAN, "StudentT": LIK_STUDENT_T, "GaussianGH": LIK_GAUSSIAN_GH}
+LIK_GAUSSIAN, LIK_STUDENT_T, LIK_GAUSSIAN_GH, LIK_BERNOULLI = 0, 1, 2, 3
+LIKELIHOOD_IDS = {"Gaussian": LIK_GAUSSIAN, "StudentT": LIK_STUDENT_T, "GaussianGH": LIK_GAUSSIAN_GH, "Bernoulli": LIK_BERNOULLI}
 OPT_PREDICT_MATH = 1
 OPT_FIT_SINGLE_LEVEL_MAX = 2
 OPT_GENERATION = 3
@@ -213,6 +213,15 @@ SIGNATURES = {
     "gpso_constrained_fold_host": (C.c_int, [_c_acq_p, _c_cspec_p, _c_double_p, _c_double_p, C.c_double, _c_double_p, _c_double_p,
                                              _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int, C.c_int64, _c_double_p,
                                              _c_double_p]),
+    "gpso_constrained_success_fold_host": (C.c_int, [_c_acq_p, _c_cspec_p, _c_double_p, _c_double_p, C.c_double, _c_double_p,
+                                                     _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int, C.c_int64,
+                                                     _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_success_prob_host": (C.c_int, [_c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p]),
+    "gpso_predict_prob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_int]),
+    "gpso_success_push": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gpso_success_clear": (C.c_int, [C.c_void_p]),
+    "gpso_success_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), _c_int64_p, _c_double_p]),
     "gpso_screen_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_double, _c_double_p, _c_double_p,
                                     _c_double_p, _c_double_p]),
     "gpso_screen_eval_host": (C.c_int, [_c_double_p, _c_double_p, C.c_double, C.c_double, C.c_double, C.c_int64, _c_double_p,

@@ -2693,9 +2693,15 @@ int gpso_sgpr_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, in
 }
 
 // ---- sparse variational GP on inducing points (theta from u as the VGP's: vlik_floor) ------------------------------------
+// the Bernoulli kind is the dense VGP's alone: the sparse family refuses it whole, it does not half-serve it
+static int refuse_bernoulli_sparse(gpso_ctx* ctx, const char* who) {
+  if (ctx->eng->vlik_kind != GPSO_LIK_BERNOULLI) return GPSO_OK;
+  return ctx->fail(GPSO_E_ARG, "%s: GPSO_LIK_BERNOULLI is served by the dense variational GP (gpso_vgp_*) only, not by the sparse family", who);
+}
 int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double noise_variance) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_init_q")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   Theta th{};
   if (!(noise_variance > 0.0)) return ctx->eng->svgp_init_q(th, 0.0);  // the prior
@@ -2706,6 +2712,7 @@ int gpso_svgp_init_q(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
 
 int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_set_q")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if ((mu == nullptr) != (S == nullptr)) return ctx->fail(GPSO_E_ARG, "mu and S: both or neither");
   return ctx->eng->svgp_set_q(mu, S, m);
@@ -2713,12 +2720,14 @@ int gpso_svgp_set_q(gpso_ctx* ctx, const double* mu, const double* S, int64_t m)
 
 int gpso_svgp_get_q(gpso_ctx* ctx, double* mu, double* S) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_get_q")) return rcb;
   return ctx->eng->svgp_get_q(mu, S);
 }
 
 int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                       double gamma) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_natgrad")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   Theta th;
   int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
@@ -2729,6 +2738,7 @@ int gpso_svgp_natgrad(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int 
 int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                      double* loss, double* grad_u, double* theta_out) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_elbo_u")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), grad_u, false, theta_out,
@@ -2738,6 +2748,7 @@ int gpso_svgp_elbo_u(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int t
 int gpso_svgp_posterior(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                         double* delta_out) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_posterior")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   Theta th;
   int rc = theta_of_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), &th);
@@ -2764,6 +2775,7 @@ int gpso_sgpr_bound_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int
 int gpso_svgp_elbo_uz(gpso_ctx* ctx, int kernel, const double* u, int n_ls, int train_mean, double mean_c_fixed,
                       const double* Z, double* loss, double* grad_u, double* grad_z, double* theta_out) {
   ENTER();
+  if (int rcb = refuse_bernoulli_sparse(ctx, "gpso_svgp_elbo_uz")) return rcb;
   if (int rcs = refuse_noise_diag(ctx)) return rcs;
   if (!loss) return ctx->fail(GPSO_E_ARG, "loss must not be NULL");
   return eval_in_u(ctx, kernel, u, n_ls, train_mean, mean_c_fixed, vlik_floor(ctx), grad_u, grad_z != nullptr, theta_out,
@@ -3061,6 +3073,56 @@ int gpso_constrained_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, con
   gpso::constrained_fold_host(acq_spec(acq), con_spec(cspec), mean, var, noise, member_mean, member_var, member_noise, thr, sn, k, (long long)m,
                               value, logpof);
   return GPSO_OK;
+}
+
+int gpso_constrained_success_fold_host(const gpso_acq* acq, const gpso_cspec* cspec, const double* mean, const double* var, double noise,
+                                       const double* member_mean, const double* member_var, const double* member_noise,
+                                       const double* threshold, const int* sense, int k, int64_t m, const double* success_mean,
+                                       const double* success_var, double* value, double* logpof) {
+  if (constrained_refusal(acq, cspec) != nullptr || !success_mean || !success_var || k < 0 || k > gpso::kConstraintsMax || m < 1 ||
+      noise != noise || (!value && !logpof))
+    return GPSO_E_ARG;
+  if (k > 0 && (!member_mean || !member_var || !member_noise || !threshold || !sense)) return GPSO_E_ARG;
+  if (cspec->mode != GPSO_CON_FEASIBILITY && (!mean || !var)) return GPSO_E_ARG;
+  double thr[gpso::kConstraintsMax] = {}, sn[gpso::kConstraintsMax] = {};
+  for (int i = 0; i < k; ++i) {
+    if ((sense[i] != 1 && sense[i] != -1) || !std::isfinite(threshold[i]) || member_noise[i] != member_noise[i]) return GPSO_E_ARG;
+    thr[i] = threshold[i];
+    sn[i] = (double)sense[i];
+  }
+  gpso::constrained_success_fold_host(acq_spec(acq), con_spec(cspec), mean, var, noise, member_mean, member_var, member_noise, thr, sn, k,
+                                      (long long)m, success_mean, success_var, value, logpof);
+  return GPSO_OK;
+}
+
+// ---- failed evaluations (success.hpp) ----------------------------------------------------------------
+int gpso_success_prob_host(const double* mean, const double* var, int64_t n, double* logprob, double* prob) {
+  if (!mean || !var || n < 1 || (!logprob && !prob)) return GPSO_E_ARG;
+  gpso::success_prob_host(mean, var, (long long)n, logprob, prob);
+  return GPSO_OK;
+}
+
+int gpso_predict_prob(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, double* prob, double* logprob, double* mean,
+                      double* var, int out_mem) {
+  ENTER();
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "gpso_predict_prob: bad out_mem %d", out_mem);
+  return ctx->eng->predict_prob(xs, xs_dtype, xs_mem, m, prob, logprob, mean, var, out_mem);
+}
+
+int gpso_success_push(gpso_ctx* ctx, gpso_ctx* src) {
+  ENTER();
+  if (!src) return ctx->fail(GPSO_E_ARG, "gpso_success_push: src must not be NULL");
+  return ctx->eng->success_push(*src->eng);
+}
+
+int gpso_success_clear(gpso_ctx* ctx) {
+  ENTER();
+  return ctx->eng->success_clear();
+}
+
+int gpso_success_info(gpso_ctx* ctx, int* present, int64_t* n, double* theta) {
+  ENTER();
+  return ctx->eng->success_info(present, n, theta);
 }
 
 int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double* s2, const double* cov, double noise, double obs_noise,

@@ -6,6 +6,8 @@
 // members' noise variances are read once per thread from their hyper blocks, thresholds and senses ride in the launch record.
 // Column reads and the two stores are coalesced (lane j reads col[i * ld + j]); nothing is shared between threads, so there
 // are no atomics and a leaf's bits depend neither on its slot nor on the batch.
+// With a success member (section 7s) the fold is success.hip's con_success_fold_kernel: a translation unit of its own, so that
+// this one compiles to what it was.
 // con_gather_kernel: one thread per segment picks the winner's logpof by the index launch_seg_argmax left.
 // Compiled with -ffp-contract=off; every fused multiply-add is written out.
 #include "constraints.hpp"
@@ -53,6 +55,7 @@ void constrained_fold_host(const AcqSpec& a, const ConSpec& c, const double* mea
 }
 
 void launch_constrained_fold(hipStream_t st, const ConFoldLaunch& g) {
+  if (g.smean != nullptr) return launch_constrained_success_fold(st, g);  // (success.hip: the member's term closes logpof)
   hipLaunchKernelGGL(con_fold_kernel, dim3((unsigned)((g.m + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, g);
 }
 

@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "acq.hpp"
+#include "success.hpp"
 
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -55,16 +56,12 @@ GPSO_ACQ_HD inline double con_log_pof_term(double mean, double var, double noise
   return acq_log_ncdf(sense * z, sense * zl);
 }
 
-// the two numbers of leaf j.  (om, ov, onoise): the objective's predictive column entries and its noise variance;
-// thr / sense / cnoise [J]: the members' thresholds, senses (+1: c <= t, -1: c >= t) and noise variances
-GPSO_ACQ_HD inline void constrained_fold_leaf(const AcqSpec& a, const ConSpec& c, double om, double ov, double onoise, const double* cmean,
-                                              const double* cvar, const double* cnoise, const double* thr, const double* sense, int nj,
-                                              int64_t ld, int64_t j, double* value, double* logpof) {
+// what the mode makes of a leaf's logpof `lp` and the objective's (om, ov): the value the arg-max ranks by
+GPSO_ACQ_HD inline void constrained_value_leaf(const AcqSpec& a, const ConSpec& c, double om, double ov, double onoise, double lp, double* value,
+                                               double* logpof) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
-  double lp = con_log_pof_term(cmean[j], cvar[j], cnoise[0], thr[0], sense[0]);
-  for (int i = 1; i < nj; ++i) lp += con_log_pof_term(cmean[i * ld + j], cvar[i * ld + j], cnoise[i], thr[i], sense[i]);
   *logpof = lp;
   if (c.mode == GPSO_CON_FEASIBILITY) {
     *value = lp;
@@ -85,10 +82,46 @@ GPSO_ACQ_HD inline void constrained_fold_leaf(const AcqSpec& a, const ConSpec& c
   else *value = a0 * acq_exp(lp);
 }
 
+// the two numbers of leaf j.  (om, ov, onoise): the objective's predictive column entries and its noise variance;
+// thr / sense / cnoise [J]: the members' thresholds, senses (+1: c <= t, -1: c >= t) and noise variances
+GPSO_ACQ_HD inline void constrained_fold_leaf(const AcqSpec& a, const ConSpec& c, double om, double ov, double onoise, const double* cmean,
+                                              const double* cvar, const double* cnoise, const double* thr, const double* sense, int nj,
+                                              int64_t ld, int64_t j, double* value, double* logpof) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  double lp = con_log_pof_term(cmean[j], cvar[j], cnoise[0], thr[0], sense[0]);
+  for (int i = 1; i < nj; ++i) lp += con_log_pof_term(cmean[i * ld + j], cvar[i * ld + j], cnoise[i], thr[i], sense[i]);
+  constrained_value_leaf(a, c, om, ov, onoise, lp, value, logpof);
+}
+
+// ... with a success member (success.hpp): its log-probability at the latent (smean, svar) of leaf j is
+// the LAST term of logpof, behind the nj constraints in index order; nj = 0: it IS logpof (the sum starts at its first term)
+GPSO_ACQ_HD inline void constrained_success_fold_leaf(const AcqSpec& a, const ConSpec& c, double om, double ov, double onoise,
+                                                      const double* cmean, const double* cvar, const double* cnoise, const double* thr,
+                                                      const double* sense, int nj, int64_t ld, int64_t j, double smean, double svar,
+                                                      double* value, double* logpof) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double ls = success_log_prob(smean, svar);
+  double lp = ls;
+  if (nj > 0) {
+    lp = con_log_pof_term(cmean[j], cvar[j], cnoise[0], thr[0], sense[0]);
+    for (int i = 1; i < nj; ++i) lp += con_log_pof_term(cmean[i * ld + j], cvar[i * ld + j], cnoise[i], thr[i], sense[i]);
+    lp += ls;
+  }
+  constrained_value_leaf(a, c, om, ov, onoise, lp, value, logpof);
+}
+
 // host loop of gpso_constrained_fold_host (constraints.hip: built without contraction, like the device fold)
 void constrained_fold_host(const AcqSpec& a, const ConSpec& c, const double* mean, const double* var, double noise, const double* cmean,
                            const double* cvar, const double* cnoise, const double* thr, const double* sense, int nj, long long m,
                            double* value, double* logpof);
+// ... and of gpso_constrained_success_fold_host (success.hip): smean / svar [m] the success member's latent columns; nj may be 0
+void constrained_success_fold_host(const AcqSpec& a, const ConSpec& c, const double* mean, const double* var, double noise, const double* cmean,
+                                   const double* cvar, const double* cnoise, const double* thr, const double* sense, int nj, long long m,
+                                   const double* smean, const double* svar, double* value, double* logpof);
 
 #if defined(__HIPCC__)
 // ---- constraints.hip ---------------------------------------------------------------------------------------------------
@@ -109,12 +142,20 @@ struct ConFoldLaunch {
   int64_t ld = 0, m = 0;
   double* value = nullptr;   // [m]
   double* logpof = nullptr;  // [m]
+  // (behind everything section 7r's record holds, whose offsets stay what they were)
+  const double* smean = nullptr;  // [m] the success member's latent columns (success.hpp); NULL: none, the fold of section 7r
+  const double* svar = nullptr;
 };
-// one thread per leaf: constrained_fold_leaf
+// one thread per leaf: constrained_fold_leaf, or constrained_success_fold_leaf where smean is set (nj may then be 0)
 void launch_constrained_fold(hipStream_t st, const ConFoldLaunch& g);
 // the winner's logpof per segment: out[i] = logpof[seg_off[i] + idx_i], idx_i read from launch_seg_argmax's records
 // (rec[4 i + 3], a bit-cast int64; -1: an empty segment, NaN)
 void launch_constrained_gather(hipStream_t st, const double* logpof, const int64_t* seg_off_dev, const double* rec, int nseg, double* out);
+// ---- success.hip -------------------------------------------------------------------------------------------------------
+// launch_constrained_fold's route where g.smean is set: constrained_success_fold_leaf, one thread per leaf
+void launch_constrained_success_fold(hipStream_t st, const ConFoldLaunch& g);
+// one thread per point: logprob[j] = success_log_prob(mean[j], var[j]), prob[j] = acq_exp of it
+void launch_success_map(hipStream_t st, const double* mean, const double* var, int64_t m, double* logprob, double* prob);
 #endif
 
 }  // namespace gpso

@@ -701,6 +701,21 @@ struct EngineCore {
   int constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
                            const ConSpec& con, int64_t* idx, double* mean, double* var, double* value, double* logpof);
 
+  // ---- failed evaluations (success.hpp).  The success member: ONE slot of the four copies a constraint
+  // member has, of a Bernoulli-installed classifier posterior (res.bernoulli on its context) with an N and a kernel of its own.
+  // Its lifetime is the constraint set's (res.success); while it is resident the constrained calls add its log-probability to
+  // logpof as the last term, and serve J = 0.  suc_mean / suc_var / suc_val: gpso_predict_prob's columns and its two outputs
+  DevBuf suc_hyper, suc_xs, suc_linv, suc_alpha;
+  DevBuf suc_mean, suc_var, suc_val;
+  int suc_d = 0, suc_dp = 0, suc_kernel = 0;
+  int64_t suc_n = 0;
+  double suc_theta[kEnsembleTheta] = {};  // what gpso_success_info reports
+  bool success_present() const { return res.success; }
+  int predict_prob(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* prob, double* logprob, double* mean, double* var, int out_mem);
+  int success_push(EngineCore& src);
+  int success_clear();
+  int success_info(int* present, int64_t* n_out, double* theta) const;
+
   // ---- the variational and sparse families (engine_variational.hip says what each buffer holds) ----
   DevBuf vq_mu, vq_S, vA, vB, vC, vvec, vsmall;  // the VGP: q(v) = N(mu, S S^T), three matrices, the vectors, the sums and verdicts
   int64_t vq_n = -1, vq_npad = -1;  // shape q was made for (another shape: q restarts at the prior)

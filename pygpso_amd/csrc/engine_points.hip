@@ -759,29 +759,36 @@ int EngineCore::constrained_refusals(const char* who, const void* xs, int xs_dty
   int rc = member_refusal(ctx, *this, who, "ctx (the objective)");
   if (rc) return rc;
   const int k = constraint_count();
-  if (k == 0) return ctx->fail(GPSO_E_STATE, "%s: no constraint set on this context: gpso_constraint_push first (gpso_alloc_posterior ends a set)", who);
+  const bool suc = success_present();
+  if (k == 0 && !suc) return ctx->fail(GPSO_E_STATE, "%s: no constraint set on this context: gpso_constraint_push first (gpso_alloc_posterior ends a set)", who);
   if (ensemble_count() > 0)
     return ctx->fail(GPSO_E_STATE, "%s: a hyper-parameter ensemble is resident on this context: constraints are not integrated over it "
                                    "(gpso_ensemble_clear first)", who);
-  if (n != con_n || d != con_d || kp.kernel != con_kernel)
+  if (suc && d != suc_d)
+    return ctx->fail(GPSO_E_STATE, "%s: the objective has D=%d, the success member D=%d: the member is stale, gpso_success_clear and push "
+                                   "a classifier of these inputs", who, d, suc_d);
+  if (k > 0 && (n != con_n || d != con_d || kp.kernel != con_kernel))
     return ctx->fail(GPSO_E_STATE, "%s: the objective (N=%lld, D=%d, kernel %d) no longer has the shape of the set's members (N=%lld, D=%d, "
                                    "kernel %d): the set is stale, gpso_constraint_clear and push models of the new rows",
                      who, (long long)n, d, kp.kernel, (long long)con_n, con_d, con_kernel);
   if (m < 1) return ctx->fail(GPSO_E_ARG, "%s needs at least one leaf (m=%lld)", who, (long long)m);
-  if (m > ((int64_t)1 << 28) / (k + 1)) return ctx->fail(GPSO_E_ARG, "%s: (J + 1) * m above 2^28 (J=%d, m=%lld)", who, k, (long long)m);
+  if (m > ((int64_t)1 << 28) / (k + 1 + (suc ? 1 : 0))) return ctx->fail(GPSO_E_ARG, "%s: (J + 1) * m above 2^28 (J=%d, m=%lld)", who, k, (long long)m);
   if ((rc = check_points(xs, xs_dtype, xs_mem, m))) return rc;
   return refuse_if_async(who);
 }
 
 // ... and what both enqueue behind their refusals: the workspaces, the columns (stage 1: one launch for the objective on the
 // context's own buffers, one for the J members) and the fold (stage 2).  On return the stream is open (points_begin),
-// con_mean / con_var hold [1 + J][m] with the objective in row 0, con_val holds value [m] then logpof [m]
+// con_mean / con_var hold [1 + J][m] with the objective in row 0, con_val holds value [m] then logpof [m].  With a success
+// member (section 7s) one more K = 1 launch, with the member's own n and kernel, writes row 1 + J, and the fold reads it last
 int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s) {
   ctx->tick_timing();
   const int k = constraint_count();
+  const bool suc = success_present();
+  const size_t rows = (size_t)k + 1 + (suc ? 1 : 0);
   int rc;
-  if ((rc = ensure(con_mean, (size_t)(k + 1) * m * 8))) return rc;
-  if ((rc = ensure(con_var, (size_t)(k + 1) * m * 8))) return rc;
+  if ((rc = ensure(con_mean, rows * m * 8))) return rc;
+  if ((rc = ensure(con_var, rows * m * 8))) return rc;
   if ((rc = ensure(con_val, (size_t)2 * m * 8))) return rc;
   if ((rc = points_begin(s))) return rc;
   const void* dev = nullptr;
@@ -796,13 +803,21 @@ int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, in
   c.hyper = as<double>(con_hyper); c.xs = as<double>(con_xs); c.linv = as<double>(con_linv); c.alpha = as<double>(con_alpha);
   c.n = (int)con_n; c.d = con_d; c.dp = con_dp; c.kernel = con_kernel; c.k = k;
   c.mean = g.mean + m; c.var = g.var + m;
-  if (launch_ensemble_members(*s, c) != 0) return launch_status();
+  if (k > 0 && launch_ensemble_members(*s, c) != 0) return launch_status();
+  EnsembleMembersLaunch u = g;
+  if (suc) {
+    u.hyper = as<double>(suc_hyper); u.xs = as<double>(suc_xs); u.linv = as<double>(suc_linv); u.alpha = as<double>(suc_alpha);
+    u.n = (int)suc_n; u.d = suc_d; u.dp = suc_dp; u.kernel = suc_kernel; u.k = 1;
+    u.mean = g.mean + (int64_t)(k + 1) * m; u.var = g.var + (int64_t)(k + 1) * m;
+    if (launch_ensemble_members(*s, u) != 0) return launch_status();
+  }
   ConFoldLaunch f;
   f.acq = acq; f.con = con;
   f.obj_mean = g.mean; f.obj_var = g.var; f.obj_hyper = g.hyper;
   f.cmean = c.mean; f.cvar = c.var; f.chyper = c.hyper; f.hyper_stride = kEnsHyperStride;
   for (int i = 0; i < k; ++i) { f.thr[i] = con_thr[i]; f.sense[i] = con_sense[i]; }
   f.nj = k; f.ld = m; f.m = m;
+  if (suc) { f.smean = u.mean; f.svar = u.var; }
   f.value = as<double>(con_val); f.logpof = f.value + m;
   launch_constrained_fold(*s, f);
   return launch_status();
@@ -818,7 +833,8 @@ int EngineCore::constrained_acq_values(const void* xs, int xs_dtype, int xs_mem,
   if ((rc = constrained_enqueue(xs, xs_dtype, xs_mem, m, acq, con, &s))) return rc;
   const hipMemcpyKind kind = out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   const double *cm = as<double>(con_mean), *cv = as<double>(con_var), *val = as<double>(con_val);
-  const size_t col = (size_t)m * 8, cols = (size_t)constraint_count() * col;
+  // (the member columns: the J constraints', then the success member's where one is resident)
+  const size_t col = (size_t)m * 8, cols = ((size_t)constraint_count() + (success_present() ? 1 : 0)) * col;
   if (mean) HIPCHECK(hipMemcpyAsync(mean, cm, col, kind, s));
   if (var) HIPCHECK(hipMemcpyAsync(var, cv, col, kind, s));
   if (value) HIPCHECK(hipMemcpyAsync(value, val, col, kind, s));
@@ -864,6 +880,108 @@ int EngineCore::constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, i
     std::memcpy(&w, &rec[(size_t)i * 4 + 3], 8);
     idx[i] = w;
   }
+  return GPSO_OK;
+}
+
+// ---- failed evaluations: the success probability and the success member (success.hpp) -----------------
+namespace {
+// a Bernoulli-installed classifier posterior within the ensemble's rule (section 7q) on `e`, in the words of the call `who`
+int bernoulli_refusal(gpso_ctx* report, EngineCore& e, const char* who, const char* what) {
+  if (e.fit_elem != 8)
+    return report->fail(GPSO_E_ARG, "%s needs GPSO_F64 or GPSO_MIXED contexts -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double): %s is GPSO_F32", who, what);
+  if (!e.res.has_post()) return report->fail(GPSO_E_STATE, "%s: no posterior resident on %s: call gpso_vgp_posterior under GPSO_LIK_BERNOULLI first", who, what);
+  if (e.res.post != Post::Vgp || !e.res.bernoulli || !e.res.chol_valid)
+    return report->fail(GPSO_E_STATE, "%s needs a variational GP installed under GPSO_LIK_BERNOULLI on %s (gpso_vgp_set_likelihood + gpso_vgp_posterior): "
+                                      "any other posterior has no success probability", who, what);
+  if (e.n > kEnsembleMaxN) return report->fail(GPSO_E_ARG, "%s: N=%lld on %s above %d", who, (long long)e.n, what, kEnsembleMaxN);
+  return GPSO_OK;
+}
+}  // namespace
+
+// P(success) at m points of the Bernoulli install resident here: stage 1 of the ensemble with K = 1 on the context's own
+// buffers (the LATENT mean and variance: the install's noise slot is 0), then one thread per point of success.hpp's map
+int EngineCore::predict_prob(const void* xs, int xs_dtype, int xs_mem, int64_t m, double* prob, double* logprob, double* mean, double* var,
+                             int out_mem) {
+  const char* who = "gpso_predict_prob";
+  int rc = bernoulli_refusal(ctx, *this, who, "ctx");
+  if (rc) return rc;
+  if (!prob && !logprob && !mean && !var) return ctx->fail(GPSO_E_ARG, "%s: every output is NULL", who);
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "%s needs at least one point (m=%lld)", who, (long long)m);
+  if (m > ((int64_t)1 << 28)) return ctx->fail(GPSO_E_ARG, "%s: m above 2^28 (m=%lld)", who, (long long)m);
+  if ((rc = check_points(xs, xs_dtype, xs_mem, m))) return rc;
+  if ((rc = refuse_if_async(who))) return rc;
+  ctx->tick_timing();
+  if ((rc = ensure(suc_mean, (size_t)m * 8))) return rc;
+  if ((rc = ensure(suc_var, (size_t)m * 8))) return rc;
+  if ((rc = ensure(suc_val, (size_t)2 * m * 8))) return rc;
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  EnsembleMembersLaunch g;
+  g.hyper = as<double>(hyper); g.xs = as<double>(xs64); g.linv = as<double>(linv); g.alpha = as<double>(alpha_f);
+  g.hyper_stride = kEnsHyperStride; g.leaves = dev; g.leaves_f64 = xs_dtype == GPSO_F64 ? 1 : 0; g.m = m; g.ld = m;
+  g.n = (int)n; g.npad = kPadN; g.d = d; g.dp = dp; g.kernel = kp.kernel; g.k = 1;
+  g.mean = as<double>(suc_mean); g.var = as<double>(suc_var);
+  if (launch_ensemble_members(s, g) != 0) return launch_status();
+  double* val = as<double>(suc_val);
+  launch_success_map(s, g.mean, g.var, m, val, val + m);
+  if ((rc = launch_status())) return rc;
+  const hipMemcpyKind kind = out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const size_t col = (size_t)m * 8;
+  if (logprob) HIPCHECK(hipMemcpyAsync(logprob, val, col, kind, s));
+  if (prob) HIPCHECK(hipMemcpyAsync(prob, val + m, col, kind, s));
+  if (mean) HIPCHECK(hipMemcpyAsync(mean, g.mean, col, kind, s));
+  if (var) HIPCHECK(hipMemcpyAsync(var, g.var, col, kind, s));
+  return points_end(s, m);
+}
+
+// the four copies gpso_constraint_push makes, into the one slot of the success member: device to device, nothing computed
+int EngineCore::success_push(EngineCore& src) {
+  const char* who = "gpso_success_push";
+  if (src.ctx->device != ctx->device)
+    return ctx->fail(GPSO_E_ARG, "%s: src lives on device %d, ctx on device %d: a member is copied device to device on one device", who, src.ctx->device, ctx->device);
+  if (fit_elem != 8) return ctx->fail(GPSO_E_ARG, "%s needs GPSO_F64 or GPSO_MIXED contexts -- dtype=\"float64\" or \"mixed\": ctx is GPSO_F32", who);
+  int rc = bernoulli_refusal(ctx, src, who, "src");
+  if (rc) return rc;
+  if (res.have_data && src.d != d)
+    return ctx->fail(GPSO_E_ARG, "%s: the classifier on src has D=%d, the data on ctx D=%d", who, src.d, d);
+  if ((rc = refuse_if_async(who))) return rc;
+  if (src.ctx->slots_busy() != 0)
+    return ctx->fail(GPSO_E_STATE, "%s while %d asynchronous best-UCB call(s) are open on src: gpso_best_ucb_end them first", who, src.ctx->slots_busy());
+  const size_t b_xs = (size_t)src.npad * src.dp * 8, b_linv = (size_t)src.npad * src.npad * 8, b_alpha = (size_t)src.npad * 8,
+               b_hyper = (size_t)kEnsHyperStride * 8;
+  if ((rc = ensure(suc_hyper, b_hyper))) return rc;
+  if ((rc = ensure(suc_xs, b_xs))) return rc;
+  if ((rc = ensure(suc_linv, b_linv))) return rc;
+  if ((rc = ensure(suc_alpha, b_alpha))) return rc;
+  hipStream_t s = st();
+  const bool other = src.st() != s;
+  if (other) HIPCHECK(hipStreamSynchronize(src.st()));  // what src's install enqueued is in its buffers
+  HIPCHECK(hipMemcpyAsync(suc_hyper.p, src.hyper.p, b_hyper, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(suc_xs.p, src.xs64.p, b_xs, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(suc_linv.p, src.linv.p, b_linv, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipMemcpyAsync(suc_alpha.p, src.alpha_f.p, b_alpha, hipMemcpyDeviceToDevice, s));
+  HIPCHECK(hipStreamSynchronize(s));  // (src may be retrained the moment this returns: the copies have left it)
+  suc_n = src.n; suc_d = src.d; suc_dp = src.dp; suc_kernel = src.kp.kernel;
+  expand_ls(src.ls_host.data(), src.n_ls, suc_theta);
+  suc_theta[kMaxD] = src.kp.variance; suc_theta[kMaxD + 1] = src.kp.noise; suc_theta[kMaxD + 2] = src.kp.mean_c;
+  res.success_pushed();
+  return GPSO_OK;
+}
+
+int EngineCore::success_clear() {
+  int rc = refuse_if_async("gpso_success_clear");
+  if (rc) return rc;
+  res.success_cleared();
+  return GPSO_OK;
+}
+
+int EngineCore::success_info(int* present, int64_t* n_out, double* theta) const {
+  if (!present) return ctx->fail(GPSO_E_ARG, "present must not be NULL");
+  *present = success_present() ? 1 : 0;
+  if (n_out) *n_out = *present ? suc_n : 0;
+  if (theta && *present) std::memcpy(theta, suc_theta, sizeof(suc_theta));
   return GPSO_OK;
 }
 

@@ -24,6 +24,7 @@ int* EngineCore::vinfo() const { return reinterpret_cast<int*>(as<double>(vsmall
 enum { kLikM = 0, kLikV = 1, kLikGm = 2, kLikA = 3, kLikT = 4, kLikVe = 5, kLikDve = 6, kLikMu = 7, kLikVecs = 8 };
 // the f-free part of log p(y | f) at the likelihood parameter p (Student-t: the scale; Gaussian: the variance)
 double EngineCore::vlik_const(double p) const {
+  if (vlik_kind == GPSO_LIK_BERNOULLI) return 0.0;  // (log Phi(s f) has no f-free part and no parameter)
   if (vlik_kind == GPSO_LIK_STUDENT_T)
     return std::lgamma(0.5 * (vlik_df + 1.0)) - std::lgamma(0.5 * vlik_df) -
            0.5 * (std::log(p * p) + std::log(vlik_df) + std::log(M_PI));
@@ -42,13 +43,15 @@ void EngineCore::vgp_quadrature(const double* L, double* A, double p, double mea
 
 int EngineCore::vgp_set_likelihood(int kind, double df, int n_gh, const double* gh_x, const double* gh_w) {
   if (int rcd = need_double_fit("the variational GP needs a float64 fit: open a GPSO_F64 or GPSO_MIXED context")) return rcd;
-  if (kind != GPSO_LIK_GAUSSIAN && kind != GPSO_LIK_STUDENT_T && kind != GPSO_LIK_GAUSSIAN_GH)
+  if (kind != GPSO_LIK_GAUSSIAN && kind != GPSO_LIK_STUDENT_T && kind != GPSO_LIK_GAUSSIAN_GH && kind != GPSO_LIK_BERNOULLI)
     return ctx->fail(GPSO_E_ARG, "unknown likelihood kind %d", kind);
   if (kind != GPSO_LIK_GAUSSIAN) {
     if (n_gh < 1 || n_gh > 64) return ctx->fail(GPSO_E_ARG, "n_gh=%d outside [1, 64]", n_gh);
     if (!gh_x || !gh_w) return ctx->fail(GPSO_E_ARG, "gh_x / gh_w must not be NULL");
     if (kind == GPSO_LIK_STUDENT_T && !(df > 2.0))
       return ctx->fail(GPSO_E_ARG, "Student-t df=%g: need df > 2 (a finite predictive variance)", df);
+    if (kind == GPSO_LIK_BERNOULLI && df != 0.0)
+      return ctx->fail(GPSO_E_ARG, "Bernoulli df=%g: the kind has no parameter, pass df = 0", df);
   }
   int rc = refuse_if_async("gpso_vgp_set_likelihood");
   if (rc) return rc;
@@ -323,7 +326,7 @@ int EngineCore::vgp_elbo(const Theta& th, double* loss, double* grad) {
     *loss = -host[0] + 0.5 * (host[4] + host[3] - N - host[5]);
     if (grad) {
       for (int k = 0; k <= n_ls; ++k) grad[k] = host[kVgpGradAt + k];
-      grad[n_ls + 1] = -host[1];
+      grad[n_ls + 1] = vlik_kind == GPSO_LIK_BERNOULLI ? 0.0 : -host[1];  // (no parameter: exactly 0.0, not -0.0)
       grad[n_ls + 2] = -host[2];
     }
     return GPSO_OK;
@@ -394,11 +397,15 @@ int EngineCore::vgp_posterior(const Theta& th) {
     launch_vgp_reverse(s, Cm, B, n, npad, 1, nullptr);              // R
     launch_dgemm(s, B, false, Li, false, A, npad, std::sqrt(1.0 + shift), 0.0);  // C = sqrt(1 + delta) R L^-1
     HIPCHECK(hipMemcpyAsync(Li, A, (size_t)npad * npad * 8, hipMemcpyDeviceToDevice, s));
-    // the likelihood's variance in the predictive: scale^2 df / (df - 2) (Student-t, closed form) or s2; + delta k**
-    const double noise = vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
+    // the likelihood's variance in the predictive: scale^2 df / (df - 2) (Student-t, closed form) or s2; + delta k**.
+    // Bernoulli: 0 -- the install serves the LATENT mean and variance (log-concave: delta is 0), gpso_predict_prob maps them
+    const double noise = vlik_kind == GPSO_LIK_BERNOULLI ? 0.0
+                         : vlik_kind == GPSO_LIK_STUDENT_T ? s2 * s2 * vlik_df / (vlik_df - 2.0) : s2;
     if ((rc = set_theta(th.with_lik(noise + shift * th.variance)))) return rc;
   }
-  return install_predictive(Post::Vgp);
+  if ((rc = install_predictive(Post::Vgp))) return rc;
+  if (vlik_kind == GPSO_LIK_BERNOULLI) res.bernoulli_installed();
+  return GPSO_OK;
 }
 // what the three variational installs share once linv holds C and alpha_f holds beta: the predict-ready copies, the
 // factorisations' verdicts, and the posterior's kind

@@ -36,6 +36,7 @@ struct Resident {
   int small_tile_rows = 8;     // tile rows of the 128-padded linv_p that may be non-zero (8: all / unknown)
   bool paths_valid = false;    // the path set of gpso_paths_draw / gpso_paths_draw_q (omega, b, w, v) belongs to this posterior as it stands
   bool q_factors = false;      // a variational install's Lu (Lf), beta (alpha_f) and root Q of q (vq_S / svq_S / sgM2) are still in their buffers
+  bool bernoulli = false;      // a Post::Vgp install under GPSO_LIK_BERNOULLI: (mean, var) are the latent's, noise slot 0 (success.hpp)
   bool screen_refused = false;  // a screened best-UCB call on this posterior was refused (a flat mean prunes nothing): it is not screened again
   // ---- the hyper-parameter ensemble (ensemble.hpp): its members are posteriors of the resident DATA at other theta, so a
   // refit leaves them alone and whatever changes the data, its noise vector or whose rows these are ends them: data_changed()
@@ -44,6 +45,9 @@ struct Resident {
   // belongs to the context, not to the resident data: new data, a refit, an append and an install leave it alone (a scoring
   // call compares shapes); gpso_constraint_clear and gpso_alloc_posterior end it
   bool constraints = false;
+  // ---- the success member (success.hpp): ONE Bernoulli-installed classifier posterior, copied in beside the constraint set
+  // and with its lifetime: gpso_success_clear and gpso_alloc_posterior end it
+  bool success = false;
   // ---- what the precision self-test ruled on it
   bool st_have = false;          // a posterior with targets is resident (one fitted here): the self-test can run
   bool st_done = false;          // st_vals are this posterior's, in the arithmetic now in use
@@ -72,9 +76,11 @@ struct Resident {
     post = Post::None;
     have_kinv = chol_valid = st_done = st_have = false;
     linv_p = Copy::Absent;
-    paths_valid = q_factors = screen_refused = false;
+    paths_valid = q_factors = screen_refused = bernoulli = false;
     if (!keep_peers) sync_n = -1;
   }
+  void success_pushed() { success = true; }    // gpso_success_push succeeded
+  void success_cleared() { success = false; }  // gpso_success_clear
   void constraint_pushed() { constraints = true; }      // gpso_constraint_push succeeded
   void constraints_cleared() { constraints = false; }  // gpso_constraint_clear
   void ensemble_pushed() { ensemble = true; }     // gpso_ensemble_push succeeded
@@ -150,11 +156,12 @@ struct Resident {
   }
   // (at present implied by a variational kind with chol_valid: nothing clears it alone)
   void q_factors_kept() { q_factors = true; }
+  void bernoulli_installed() { bernoulli = true; }  // gpso_vgp_posterior under the Bernoulli kind succeeded; posterior_dropped() ends it
   // -- hand-off
   void recarved() { small_tile_rows = 8; linv_b = linv_p = Copy::Absent; }  // the arena's slices moved: another layout's bytes
   // gpso_alloc_posterior: as for gpso_set_posterior, the rows about to arrive are neither data nor inducing points of this
   // context.  have_s stays: the variational entry points refuse on it with GPSO_E_ARG before they look for data
-  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; data_changed(); constraints_cleared(); posterior_dropped(); }
+  void shape_allocated() { have_data = sg_have = sg_have_z = sg_factors = false; data_changed(); constraints_cleared(); success_cleared(); posterior_dropped(); }
   // slot 7 of the hyper block, which travels: 1 = float generation, 2 = GPSO_MATH_AUTO settled on the f32 MFMA kernel,
   // 4 = the split pieces are built, 8 = the packed L^-1 travels too, 16 = float generation keeps the f32 contraction,
   // 256 x the predict math (which split the pieces are: a receiver under GPSO_MATH_AUTO follows)

@@ -173,6 +173,14 @@ __global__ __launch_bounds__(kThreads) void vgp_elbo_sums_kernel(const double* _
 // through the quadrature: the variance sigma^2), psi'(f) = d psi / df, dp = d psi / d p.  cst: the f-free part of psi.
 __device__ __forceinline__ void vgp_lik_eval(int kind, double y, double f, double p, double nu, double cst, double* psi,
                                              double* dpsi, double* dp) {
+  if (kind == 3) {  // Bernoulli, exact probit link: y is a label (success iff y > 0.5), no parameter
+    const double s = y > 0.5 ? 1.0 : -1.0;
+    const double lp = acq_log_ncdf(s * f, 0.0);
+    *psi = lp;
+    *dpsi = s * exp(-0.5 * f * f - 0.91893853320467274178 - lp);  // s phi(f) / Phi(s f); 1/2 log 2 pi
+    *dp = 0.0;
+    return;
+  }
   const double e = y - f;
   if (kind == 1) {  // Student-t
     const double den = nu * p * p + e * e;

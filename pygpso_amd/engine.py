@@ -459,11 +459,14 @@ class HipGPEngine:
     # -- variational GP (include/gpso_hip.h: gpso_vgp_*) ---------------------------------------------------------------
     def vgp_set_likelihood(self, kind="Gaussian", df=3.0, n_gh=20):
         """The VGP's likelihood: "Gaussian" (closed form, the default), "StudentT" (``df`` > 2, slot n_ls + 1 of u: the
-        scale) or "GaussianGH" (the Gaussian through the quadrature sequence), with the ``n_gh``-point Gauss-Hermite rule
+        scale), "GaussianGH" (the Gaussian through the quadrature sequence) or "Bernoulli" (exact probit link; the targets
+        are labels, success iff y > 0.5; slot n_ls + 1 of u is read by nothing), with the ``n_gh``-point Gauss-Hermite rule
         of ``numpy.polynomial.hermite.hermgauss`` (GPflow's)."""
         kid = L.LIKELIHOOD_IDS[kind] if isinstance(kind, str) else int(kind)
         x, w = np.polynomial.hermite.hermgauss(int(n_gh))
         x, w = L.as_f64(x), L.as_f64(w)
+        if kid == L.LIK_BERNOULLI:
+            df = 0.0  # (the kind has no df: the library takes 0 and refuses anything else)
         self._check(self._lib.gpso_vgp_set_likelihood(self._h, kid, float(df), int(n_gh), L.dptr(x), L.dptr(w)))
 
     def vgp_set_q(self, mu=None, S=None):
@@ -1056,7 +1059,8 @@ class HipGPEngine:
         ptr, dt, mem, m, keep = self._leaf_args(xs)
         rec, cs = acq.c_struct(incumbent), self._cspec(mode, log_pof_min)
         mean, var, val, lp = (np.empty(m, dtype=np.float64) for _ in range(4))
-        k = self.constraint_info()[0] if want_members else 0
+        # (while a success member is resident its latent columns follow the constraint models' as one more row)
+        k = self.constraint_info()[0] + (1 if self.success_info()[0] else 0) if want_members else 0
         mm, mv = (np.empty((k, m), dtype=np.float64) for _ in range(2))
         pm, pv = (C.c_void_p(a.ctypes.data) if want_members and k > 0 else None for a in (mm, mv))
         self._check(self._lib.gpso_constrained_acq_values(self._h, ptr, dt, mem, m, C.byref(rec), C.byref(cs), C.c_void_p(mean.ctypes.data),
@@ -1088,6 +1092,74 @@ class HipGPEngine:
             raise L.GpsoHipError(rc, "gpso_constrained_fold_host: bad acquisition record (GPSO_ACQ_MES is not served, a UCB kind "
                                      "cannot be weighted), constraint record or arguments")
         return val, lp
+
+    @staticmethod
+    def constrained_success_fold_host(acq, mean, var, noise, member_mean, member_var, member_noise, threshold, sense, success_mean,
+                                      success_var, mode="gate", log_pof_min=-np.inf, incumbent=None):
+        """``constrained_fold_host`` with a success member (``gpso_constrained_success_fold_host``): its latent columns
+        ``success_mean`` / ``success_var`` [M] add ``success_log_prob`` to logpof as the last term.  J = 0 (``member_mean``
+        None or of zero rows) is served: the success term then is logpof.  -> (value[M], logpof[M])."""
+        sm = L.as_f64(np.asarray(success_mean).reshape(-1))
+        m = sm.shape[0]
+        sv = L.as_f64(np.asarray(success_var).reshape(-1), (m,))
+        mm = np.zeros((0, m)) if member_mean is None else L.as_f64(np.asarray(member_mean, dtype=np.float64).reshape(-1, m))
+        k = mm.shape[0]
+        mv = np.zeros((0, m)) if member_var is None else L.as_f64(np.asarray(member_var, dtype=np.float64).reshape(-1, m), (k, m))
+        om, ov = L.as_f64(np.asarray(mean).reshape(-1), (m,)), L.as_f64(np.asarray(var).reshape(-1), (m,))
+        nz = L.as_f64(np.asarray([] if member_noise is None else member_noise, dtype=np.float64).reshape(-1), (k,))
+        thr = L.as_f64(np.asarray([] if threshold is None else threshold, dtype=np.float64).reshape(-1), (k,))
+        sn = np.ascontiguousarray(np.asarray([] if sense is None else sense).reshape(-1), dtype=np.intc)
+        if sn.shape != (k,):
+            raise ValueError(f"sense must have {k} entries")
+        val, lp = (np.empty(m, dtype=np.float64) for _ in range(2))
+        rec, cs = acq.c_struct(incumbent), HipGPEngine._cspec(mode, log_pof_min)
+        some = k > 0
+        rc = L.load().gpso_constrained_success_fold_host(
+            C.byref(rec), C.byref(cs), L.dptr(om), L.dptr(ov), float(noise), L.dptr(mm) if some else None, L.dptr(mv) if some else None,
+            L.dptr(nz) if some else None, L.dptr(thr) if some else None, sn.ctypes.data_as(C.POINTER(C.c_int)) if some else None, int(k),
+            int(m), L.dptr(sm), L.dptr(sv), L.dptr(val), L.dptr(lp))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_constrained_success_fold_host: bad acquisition record (GPSO_ACQ_MES is not served, a UCB "
+                                     "kind cannot be weighted), constraint record or arguments")
+        return val, lp
+
+    # -- failed evaluations (csrc/success.hpp; DESIGN.md section 7s) ------------------------------------------------
+    @staticmethod
+    def success_prob_host(mean, var):
+        """The device's probit map on the CPU (``gpso_success_prob_host``: no context, no GPU): latent (mean, var) [n] ->
+        (prob[n], logprob[n]) with logprob = log Phi(mean / sqrt(1 + max(var, 0)))."""
+        mean = L.as_f64(np.asarray(mean, dtype=np.float64).reshape(-1))
+        var = L.as_f64(np.asarray(var, dtype=np.float64).reshape(-1), mean.shape)
+        lp, pr = np.empty_like(mean), np.empty_like(mean)
+        rc = L.load().gpso_success_prob_host(L.dptr(mean), L.dptr(var), int(mean.shape[0]), L.dptr(lp), L.dptr(pr))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_success_prob_host: bad arguments")
+        return pr, lp
+
+    def predict_prob(self, xs, want_latent=False):
+        """P(success) at the points ``xs`` of the Bernoulli-installed VGP resident here (``gpso_predict_prob``) ->
+        (prob[M], logprob[M]); with ``want_latent`` also the latent (mean[M], var[M]) the map read."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        pr, lp, mean, var = (np.empty(m, dtype=np.float64) for _ in range(4))
+        lat = (C.c_void_p(mean.ctypes.data), C.c_void_p(var.ctypes.data)) if want_latent else (None, None)
+        self._check(self._lib.gpso_predict_prob(self._h, ptr, dt, mem, m, C.c_void_p(pr.ctypes.data), C.c_void_p(lp.ctypes.data),
+                                                lat[0], lat[1], L.MEM_HOST))
+        return (pr, lp, mean, var) if want_latent else (pr, lp)
+
+    def success_push(self, src):
+        """The Bernoulli-installed classifier posterior resident on ``src`` (another engine on this device) becomes this
+        context's success member: the constrained calls then add its log-probability to logpof, and serve J = 0."""
+        self._check(self._lib.gpso_success_push(self._h, src._h))
+
+    def success_clear(self):
+        self._check(self._lib.gpso_success_clear(self._h))
+
+    def success_info(self):
+        """-> (present, n, theta[51]); theta as a row of ``ensemble_info`` (zeros while no member is resident)."""
+        present, n = C.c_int(0), C.c_int64(0)
+        theta = np.zeros(L.ENSEMBLE_THETA, dtype=np.float64)
+        self._check(self._lib.gpso_success_info(self._h, C.byref(present), C.byref(n), L.dptr(theta)))
+        return bool(present.value), int(n.value), theta
 
     @staticmethod
     def acq_eval_host(acq, mean, var, noise=0.0, incumbent=None):

@@ -99,10 +99,27 @@ class GPListOfPoints(list):
         # observed values of the constrained outputs of an evaluated point (``GPRSurrogate(constraints=...)``), kept the same
         # way: keyed by the point's coordinate row, empty unless constraints are in use
         self._cvals = {}
+        # evaluated points whose objective returned no finite score (``GPRSurrogate(failures="classify")``), kept the same
+        # way: the coordinate rows of the failed ones, empty unless failures are in use
+        self._failed = set()
         if args and isinstance(args[0], GPListOfPoints):  # (a copy of a store keeps its variances)
             self._noise = dict(args[0]._noise)
             self.noise_given = args[0].noise_given
             self._cvals = dict(args[0]._cvals)
+            self._failed = set(args[0]._failed)
+
+    # -- failed evaluations (parallel store) ----------------------------------------------------------
+    def mark_failed_at(self, index):
+        """The evaluation of the point stored at ``index`` returned no finite score."""
+        self._index()
+        self._failed.add(self._rows[index])
+
+    def failed_mask(self, label=None):
+        """[n] bool over the stored points (of ``label`` only when given), in list order: was the evaluation a failure?"""
+        if not self._failed:
+            return np.zeros(sum(1 for p in self if label is None or p.label == label), dtype=bool)
+        self._index()
+        return np.array([self._rows[i] in self._failed for i, p in enumerate(self) if label is None or p.label == label], dtype=bool)
 
     # -- observed constraint outputs (parallel store) -------------------------------------------------
     def set_constraint_values_at(self, index, values):
@@ -764,8 +781,24 @@ class GPRSurrogate(GPSurrogate):
                  gauss_likelihood_sigma=1.0e-3, points=None, gpflow_model=None, dtype="float64",
                  device=0, engine_options=None, devices=None, refit_every=1, refit_guard=2.0, objective="nlml", gp_acquisition="ucb_var",
                  hyper="point", n_theta=16, hyper_priors=None, hyper_seed=0, hyper_options=None,
-                 constraints=None, constraint_mode="gate", pof_min=0.5):
+                 constraints=None, constraint_mode="gate", pof_min=0.5, failures=None, classifier_schedule=None):
         """
+        :param failures: None (default: nothing changes -- a non-finite score poisons the fit, as ever) or "classify" (NOT in
+            the reference): ``append`` accepts non-finite scores.  Such points are kept with their coordinates and marked
+            failed; they never enter the training set of the objective's GP or of a constraint model.  While at least one
+            failure is held, ``gp_update`` also trains a GP classifier -- one ``HipVGP`` under the Bernoulli likelihood
+            (exact probit) on ALL attempted points, label 0 for a failure and 1 for a finite score, on an engine of its own,
+            with deep copies of ``gp_kernel`` and ``gp_meanf`` as given here and q kept across updates -- and installs it as
+            the engine's success member (``HipGPR.install_success``).  While the member is resident the routes that go through
+            the constrained calls under ``constraints=`` do so here too, in gate mode with ``log_pof_min = log(pof_min)`` on
+            the product of the probability of success and, if there are constraints, their probabilities (Gelbart, Snoek &
+            Adams 2014).  Before the first failure there is no classifier and no member and every call is the call of
+            ``failures=None``.  ``highest_score`` ignores failed points.  N <= 128 attempted points, "float64" / "mixed", one
+            GPU, ``refit_every`` = 1, ``hyper="point"``; nothing of it is saved.  ``close_constraint_models()`` also closes the
+            classifier's engine
+        :param classifier_schedule: how the classifier is trained at every update, a dictionary with the keys ``iterations``
+            (natural-gradient step on q, then one optimiser step on theta, that many times), ``natgrad_gamma`` and
+            ``optimiser``; None: 10 iterations, gamma 0.5, ``Adam(0.05)`` -- a choice, not a measurement
         :param constraints: a list of ``pygpso_amd.constraints.Constraint`` (NOT in the reference; None, the default: no
             constraints, nothing changes).  The objective returns J further outputs beside the score; ``append`` takes them as
             ``constraint_values`` [n, J] and keeps them beside the points.  ``gp_update`` trains one ``HipGPR`` per constraint
@@ -888,6 +921,73 @@ class GPRSurrogate(GPSurrogate):
             ConstrainedAcq(None, constraint_mode, pof_min)  # (validates pof_min)
             self._constraint_specs = (copy.deepcopy(gp_kernel), copy.deepcopy(gp_meanf))
         self.constraint_mode, self.pof_min = constraint_mode, float(pof_min)
+        if failures not in (None, "classify"):
+            raise ValueError(f"failures must be None or 'classify', not {failures!r}")
+        self.failures = failures
+        self._classifier = None  # the HipVGP under the Bernoulli likelihood, once a failure is held
+        self._success_live = False  # a classifier of the points attempted so far is installed as the engine's success member
+        if failures is not None:
+            import copy
+
+            from .constraints import ConstrainedAcq
+
+            if dtype == "float32":
+                raise ValueError("failures='classify' needs the dense double factor: dtype='float64' or 'mixed'")
+            if self.devices is not None and len(self.devices) > 1:
+                raise ValueError("failures='classify' runs on one GPU: the success member is not sharded over an engine group")
+            if self.refit_every != 1:
+                raise ValueError("failures='classify': every update retrains the classifier on the attempted points, refit_every must be 1")
+            if hyper != "point":
+                raise ValueError("failures='classify' is not integrated over a hyper-parameter ensemble: hyper must be 'point'")
+            ConstrainedAcq(None, "gate", pof_min)  # (validates pof_min)
+            self._classifier_specs = (copy.deepcopy(gp_kernel), copy.deepcopy(gp_meanf))
+            sched = {"iterations": 10, "natgrad_gamma": 0.5, "optimiser": None}
+            unknown = set(classifier_schedule or {}) - set(sched)
+            if unknown:
+                raise ValueError(f"classifier_schedule: unknown keys {sorted(unknown)}")
+            sched.update(classifier_schedule or {})
+            if sched["optimiser"] is None:
+                sched["optimiser"] = Adam(0.05)
+            if not (int(sched["iterations"]) >= 1 and 0.0 < float(sched["natgrad_gamma"]) <= 1.0):
+                raise ValueError("classifier_schedule: iterations >= 1 and natgrad_gamma in (0, 1]")
+            self.classifier_schedule = sched
+
+    # -- failures="classify": failed points stay in the store (label evaluated, score -inf, marked failed) and out of every
+    # regression model's training set --
+    def _failed_evaluated(self):
+        """[num_evaluated] bool: which evaluated points are failures (all False without ``failures=``)."""
+        return self.points.failed_mask(PointLabels.evaluated)
+
+    @property
+    def num_failed(self):
+        return int(self._failed_evaluated().sum()) if self.failures else 0
+
+    @property
+    def highest_score(self):
+        if not self.failures:
+            return super().highest_score
+        cand = [p for p, bad in zip(self._with_label(PointLabels.evaluated), self._failed_evaluated()) if not bad]
+        if cand:
+            return max(cand, key=lambda p: p.score_mu)
+
+    @property
+    def current_training_data(self):
+        if not self.failures:
+            return super().current_training_data
+        ev = [p for p, bad in zip(self._with_label(PointLabels.evaluated), self._failed_evaluated()) if not bad]
+        return np.array([p.normed_coord for p in ev]), np.array([p.score_mu for p in ev])
+
+    @property
+    def current_training_noise(self):
+        s = super().current_training_noise
+        return s if s is None or not self.failures else s[~self._failed_evaluated()]
+
+    @property
+    def current_attempts(self):
+        """(coords [A, D], labels [A]) of every ATTEMPTED point in list order: label 1 for a finite score, 0 for a failure --
+        the classifier's training set."""
+        ev = self._with_label(PointLabels.evaluated)
+        return np.array([p.normed_coord for p in ev]), (~self._failed_evaluated()).astype(np.float64)
 
     @classmethod
     def default(cls, dtype="float64", device=0, engine_options=None, devices=None):
@@ -909,6 +1009,11 @@ class GPRSurrogate(GPSurrogate):
     def append(self, coords, scores, score_vars=None, constraint_values=None):
         """``constraint_values`` [n, J] (with ``constraints=`` only, and then required): the observed outputs of the J
         constrained quantities at ``coords``, kept beside the points as the score variances are."""
+        if self.failures:
+            scores = np.asarray(scores, dtype=np.float64)
+            ok = np.isfinite(scores)
+            if not ok.all():
+                return self._append_with_failures(coords, scores, ok, score_vars, constraint_values)
         if not self.constraints:
             if constraint_values is not None:
                 raise ValueError("constraint_values given, but the surrogate was constructed without constraints=")
@@ -927,10 +1032,39 @@ class GPRSurrogate(GPSurrogate):
             super().append(coords[i:i + 1], scores[i:i + 1], None if score_vars is None else score_vars[i:i + 1])
             self.points.set_constraint_values_at(self.points.find_index_by_coords(coords[i]), cv[i])
 
+    def _append_with_failures(self, coords, scores, ok, score_vars, constraint_values):
+        """``append`` when some score is not finite: the finite rows go the usual way; a failed row is stored at its
+        coordinates as an evaluated point worth -inf and marked failed (an evaluated duplicate keeps what it has).  Whatever
+        came with a failed row -- a score variance, constraint outputs -- is dropped: nothing was observed there."""
+        assert coords.ndim == 2 and scores.ndim == 1 and coords.shape[0] == scores.shape[0]
+        if not ok.any() and self.highest_score is None:
+            raise ValueError("append: no finite score, here or held: the objective's GP needs at least one evaluated point "
+                             "(failures='classify' models where evaluations fail, not a run in which every one does)")
+        for i in range(coords.shape[0]):  # (row by row: the store keeps the caller's order)
+            if ok[i]:
+                self.append(coords[i:i + 1], scores[i:i + 1], None if score_vars is None else np.asarray(score_vars)[i:i + 1],
+                            None if constraint_values is None else np.asarray(constraint_values)[i:i + 1])
+                continue
+            c = coords[i]
+            had = self.points.find_by_coords(c)
+            if had is not None and had.label == PointLabels.evaluated:
+                continue
+            i = self.points.append(GPPoint(c, -np.inf, 0.0, -np.inf, PointLabels.evaluated))
+            self.points.mark_failed_at(i)
+
     @property
     def current_training_constraints(self):
         """[N, J] observed constraint outputs aligned with ``current_training_data``; None without constraints."""
-        return self.points.constraint_matrix(PointLabels.evaluated) if self.constraints else None
+        if not self.constraints:
+            return None
+        if not self.failures or not self.num_failed:
+            return self.points.constraint_matrix(PointLabels.evaluated)
+        keep = set(np.flatnonzero(~self._failed_evaluated()).tolist())
+        ev = [i for i, p in enumerate(self.points) if p.label == PointLabels.evaluated]
+        rows = [self.points.constraint_values_at(i) for k, i in enumerate(ev) if k in keep]
+        if any(r is None for r in rows):
+            raise ValueError("an evaluated point has no constraint values: append(coords, scores, constraint_values=...) stores them")
+        return np.array(rows, dtype=np.float64).reshape(len(rows), -1)
 
     @property
     def highest_feasible_score(self):
@@ -941,9 +1075,11 @@ class GPRSurrogate(GPSurrogate):
         from .constraints import feasible_rows
 
         ev = self._with_label(PointLabels.evaluated)
+        if self.failures and self.num_failed:  # (a failed point observed nothing: neither a score nor constraint outputs)
+            ev = [p for p, bad in zip(ev, self._failed_evaluated()) if not bad]
         if not ev:
             return None
-        ok = feasible_rows(self.constraints, self.points.constraint_matrix(PointLabels.evaluated))
+        ok = feasible_rows(self.constraints, self.current_training_constraints)
         cand = [p for p, good in zip(ev, ok) if good]
         return max(cand, key=lambda p: p.score_mu) if cand else None
 
@@ -959,10 +1095,11 @@ class GPRSurrogate(GPSurrogate):
     def close_constraint_models(self):
         """Close the engines of the constraint models (each has a context of its own); the next ``gp_update`` opens new ones.
         The set already copied onto the objective's engine stays usable."""
-        for model in self._constraint_models or []:
+        for model in list(self._constraint_models or []) + ([self._classifier] if self._classifier is not None else []):
             if getattr(model, "_owns_engine", False) and hasattr(model.engine, "close"):
                 model.engine.close()
         self._constraint_models = None
+        self._classifier = None
 
     def _constrained_acq(self, acq=None, mode=None):
         from .constraints import ConstrainedAcq
@@ -1014,6 +1151,38 @@ class GPRSurrogate(GPSurrogate):
         self._gp_train_objective(x, y, s)
         if self.constraints:
             self._train_constraints(x, c)
+        if self.failures and self.num_failed:
+            self._train_classifier(*self.current_attempts)
+
+    @property
+    def _gate_live(self):
+        """Do the loop's calls go through the constrained ones: a constraint set or a success member is installed."""
+        return self._constraints_live or self._success_live
+
+    def _train_classifier(self, xa, labels):
+        """One HipVGP under the Bernoulli likelihood on every attempted point (``xa`` [A, D], ``labels`` [A] in {0, 1}),
+        trained by ``classifier_schedule``, installed and pushed as the engine's success member."""
+        import copy
+
+        self._success_live = False
+        if xa.shape[0] > 128:
+            raise ValueError(f"failures='classify' holds at most 128 attempted points (A={xa.shape[0]}): the success member's limit")
+        y = np.asarray(labels, dtype=np.float64)[:, np.newaxis]
+        if self._classifier is None:
+            from .kernels import Bernoulli
+
+            kernel, meanf = self._classifier_specs
+            engine = self.engine_factory() if self.engine_factory is not None else None
+            self._classifier = HipVGP(data=(xa, y), kernel=copy.deepcopy(kernel), mean_function=copy.deepcopy(meanf), likelihood=Bernoulli(),
+                                      dtype=self.dtype, device=self.device, engine=engine, engine_options=self.engine_options)
+        else:
+            self._classifier.data = (xa, y)  # (held rows keep their q, new rows get the prior: pygpso_amd.vgp)
+        model, sched = self._classifier, self.classifier_schedule
+        for _ in range(int(sched["iterations"])):
+            model.natgrad(float(sched["natgrad_gamma"]))
+            sched["optimiser"].minimize(model.training_loss, model.trainable_variables)
+        self.gpflow_model.install_success(model)
+        self._success_live = True
 
     def _gp_train_objective(self, x, y, s=None):
         assert x.shape[0] == y.shape[0]
@@ -1098,9 +1267,11 @@ class GPRSurrogate(GPSurrogate):
             raise ValueError(f"{what} is not available with hyper='marginal': it reads one hyper-parameter vector")
         if self.constraints:
             raise ValueError(f"{what} is not available with constraints: it is not served under a constraint set")
+        if self.failures:
+            raise ValueError(f"{what} is not available with failures='classify': it is not served under a success member")
 
     def gp_eval_best_ucb(self, normed_coords):
-        if self._constraints_live:
+        if self._gate_live:
             _, mean, var, ucb, _ = self.gpflow_model.constrained_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64),
                                                                           self._constrained_acq())
             return float(mean[0]), float(var[0]), float(ucb[0])
@@ -1110,7 +1281,7 @@ class GPRSurrogate(GPSurrogate):
         return float(mean[0]), float(var[0]), float(ucb[0])
 
     def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
-        if self._constraints_live:
+        if self._gate_live:
             # (as below: the constrained call takes rows, the centres come from gpso_grow and go back as one segment per box)
             bounds = np.asarray(leaf_bounds, dtype=np.float64)
             bounds = bounds[None] if bounds.ndim == 2 else bounds
@@ -1135,7 +1306,7 @@ class GPRSurrogate(GPSurrogate):
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
         if acq.name == "mes":
             self._refuse_unserved("MES")
-        if self._constraints_live:
+        if self._gate_live:
             return self.gpflow_model.constrained_best_acq(np.ascontiguousarray(normed_coords, dtype=np.float64), self._constrained_acq(acq),
                                                           seg_off, self._constrained_incumbent(acq, incumbent))[:4]
         if not self._ensemble_live:
@@ -1146,7 +1317,7 @@ class GPRSurrogate(GPSurrogate):
         acq = resolve_acquisition(acquisition, varsigma=self.gp_varsigma)
         if acq.name == "mes":
             self._refuse_unserved("MES")
-        if self._constraints_live:
+        if self._gate_live:
             return self.gpflow_model.constrained_acq_values(np.ascontiguousarray(normed_coords, dtype=np.float64), self._constrained_acq(acq),
                                                             self._constrained_incumbent(acq, incumbent))[:3]
         if not self._ensemble_live:
@@ -1168,7 +1339,7 @@ class GPRSurrogate(GPSurrogate):
     def gp_predict(self, normed_coords):
         """``hyper="marginal"``: the moments of the ensemble's mixture at ``normed_coords`` and the integrated value of the
         loop's acquisition -- what ``gp_eval_best_ucb`` ranks by --, stored as gp_based points."""
-        if self._constraints_live:  # (a gated point is stored with -inf: the loop never evaluates it)
+        if self._gate_live:  # (a gated point is stored with -inf: the loop never evaluates it)
             coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
             mean, var, val, _ = self.gpflow_model.constrained_acq_values(coords, self._constrained_acq())
             for i in range(coords.shape[0]):
@@ -1182,7 +1353,7 @@ class GPRSurrogate(GPSurrogate):
             self.points.append(GPPoint(normed_coords[i, :], float(mean[i]), float(var[i]), float(val[i]), PointLabels.gp_based))
 
     def gp_update(self):
-        if self.constraints:
+        if self.constraints or (self.failures and self.num_failed):
             x_train, y_train = self.current_training_data
             self._gp_train(x=x_train, y=y_train[:, np.newaxis], s=self.current_training_noise, c=self.current_training_constraints)
             # the gp-based points are rescored under the new models and the gate: re-appended, each overwrites its own entry
@@ -1249,6 +1420,9 @@ class GPRSurrogate(GPSurrogate):
         """Points, hyper-parameters and settings as JSON.  ``points_noise.json`` exists in ``folder`` afterwards exactly when
         some stored score variance is non-zero: it is written then, and otherwise a copy left by an earlier save is deleted
         (``GPListOfPoints.save_noise``)."""
+        if self.failures:
+            raise ValueError("a surrogate with failures='classify' is not saved: the failed points and the classifier have no place in "
+                             "the saved folder")
         if self.constraints:
             raise ValueError("a surrogate with constraints is not saved: the observed constraint outputs and the constraint models have "
                              "no place in the saved folder")

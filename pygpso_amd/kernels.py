@@ -106,6 +106,16 @@ class StudentT:
         return f"StudentT(scale={self.scale}, df={self.df})"
 
 
+class Bernoulli:
+    """Bernoulli likelihood spec for a GP classifier: labels in {0, 1}, p(y = 1 | f) = Phi(f), the EXACT probit link (not
+    ``gpflow.likelihoods.Bernoulli``'s ``inv_probit``, which mixes a 1e-3 jitter in).  No parameters."""
+
+    name = "Bernoulli"
+
+    def __repr__(self):
+        return "Bernoulli()"
+
+
 class Adam:
     """Keras's Adam (``tf.optimizers.Adam(learning_rate)``, the VGP surrogate's default optimiser,
     gpso/gp_surrogate.py:543): ``minimize(closure, variables)`` takes ONE step on the model's unconstrained vector,

@@ -688,6 +688,18 @@ class HipGPR:
             self.engine.constraint_push(model.engine, con.threshold, con.sense)
         return len(models)
 
+    def install_success(self, classifier):
+        """Make ``classifier`` -- a ``HipVGP`` under the Bernoulli likelihood on an engine of its own, trained on every
+        ATTEMPTED point with label 1 where the score was finite -- the engine's success member (``success_push``: a
+        device-to-device copy of its installed posterior; the install there only if it is not resident).  The constrained
+        calls then add its log-probability of success to logpof.  This model's own posterior is not touched."""
+        if not hasattr(self.engine, "success_push"):
+            raise NotImplementedError(f"a success member is not available on {type(self.engine).__name__}")
+        if not getattr(classifier, "_bernoulli", False):
+            raise ValueError("install_success: the classifier must be a HipVGP with likelihood=Bernoulli()")
+        classifier._ensure_resident()
+        self.engine.success_push(classifier.engine)
+
     def constraint_count(self):
         return self.engine.constraint_info()[0] if hasattr(self.engine, "constraint_info") else 0
 

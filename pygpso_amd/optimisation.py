@@ -76,6 +76,7 @@ class GPSOptimiser:
         self.eval_repeats_noise = False  # (``run``: store the variance of each aggregated score with its point)
         self.constraints = []  # (``run(objective, constraints=[...])``: the objective returns (score, c_1 .. c_J))
         self._last_constraint_values = None  # [n, J] of the evaluation just made, aggregated over the repeats like the scores
+        self.failures = None  # (``run(objective, failures="classify")``: a non-finite score is a failed evaluation, not a score)
         self.n_workers = n_workers
         callbacks = callbacks or []
         assert all(isinstance(cb, GPSOCallback) for cb in callbacks)
@@ -139,6 +140,8 @@ class GPSOptimiser:
         else:
             all_scores = self.evaluate_objective_function(all_coords)
         self.param_space.score = float(all_scores[-1])
+        if self.failures and not np.isfinite(self.param_space.score):
+            self.param_space.score = -np.inf  # (a failed centre: evaluated, worth -inf)
         self.param_space.label = PointLabels.evaluated
         if self.constraints:
             self.gp_surr.append(self.param_space.normalise_coords(all_coords), all_scores, constraint_values=self._last_constraint_values)
@@ -225,6 +228,9 @@ class GPSOptimiser:
                     new_score = float(self.evaluate_objective_function(orig)[0])
                     self.gp_surr.append(point.normed_coord[np.newaxis, :], np.array([new_score]),
                                         constraint_values=self._last_constraint_values)
+                elif self.failures:
+                    new_score = float(self.evaluate_objective_function(orig)[0])
+                    self.gp_surr.append(point.normed_coord[np.newaxis, :], np.array([new_score]))
                 elif self.eval_repeats_noise:
                     scores, variances = self.evaluate_objective_function(orig)
                     new_score = float(scores[0])
@@ -234,6 +240,8 @@ class GPSOptimiser:
                     new_score = float(self.evaluate_objective_function(orig)[0])
                     self.gp_surr.points.append(
                         GPPoint(point.normed_coord, new_score, 0.0, 0.0, PointLabels.evaluated))
+                if self.failures and not np.isfinite(new_score):
+                    new_score = -np.inf  # a failed evaluation: the leaf is evaluated, worth -inf, and never selected for splitting
                 leaf.score = new_score
                 leaf.label = PointLabels.evaluated
                 logging.debug(f"Leaf {leaf.name} updated to new evaluated score: {leaf.score}")
@@ -274,9 +282,16 @@ class GPSOptimiser:
             if cube.shape[2] != 1 + len(self.constraints):
                 raise ValueError(f"the objective must return (score, c_1 .. c_{len(self.constraints)}): got {cube.shape[2]} numbers")
             agg = np.asarray(self.eval_repeats_function(cube))
+            if self.failures:  # (one non-finite number in any repeat: the evaluation failed, whatever the aggregate makes of it)
+                agg = np.array(agg, dtype=np.float64)
+                agg[~np.isfinite(cube).all(axis=(0, 2)), 0] = np.nan
             self._last_constraint_values = agg[:, 1:]
             return agg[:, 0]
         table = np.array(scores).astype(float).reshape((self.eval_repeats, -1))
+        if self.failures:
+            agg = np.array(self.eval_repeats_function(table), dtype=np.float64)
+            agg[~np.isfinite(table).all(axis=0)] = np.nan
+            return agg
         if self.eval_repeats_noise:
             # the variance of the MEAN of the repeats: what the aggregated score is known to, a fixed per-point noise term
             return self.eval_repeats_function(table), np.var(table, axis=0, ddof=1) / self.eval_repeats
@@ -297,7 +312,7 @@ class GPSOptimiser:
             self._tree_explore(levels_to_explore=explore_levels, seed=self.expl_seed)
             evals_before = self.n_eval_counter
             explore_levels = self._tree_select()
-            if self.constraints and self.n_eval_counter == evals_before and self._all_candidates_gated():
+            if (self.constraints or self.failures) and self.n_eval_counter == evals_before and self._all_candidates_gated():
                 # nothing was evaluated and no unsampled gp-based leaf is worth more than -inf: every candidate is gated.  The
                 # evaluated centres would go on being split without an evaluation ever being made, so the run ends here
                 logging.warning(f"every unsampled leaf has a probability of feasibility below pof_min={self.gp_surr.pof_min}: "
@@ -363,9 +378,42 @@ class GPSOptimiser:
             raise ValueError("run(constraints=...) needs a surrogate that models them: construct it as GPRSurrogate(constraints=[...]) "
                              "with the same list")
 
+    def _set_failures(self, failures):
+        """``run``'s failures: what does not go together with them is refused in words."""
+        if failures not in (None, "classify"):
+            raise ValueError(f"failures must be None or 'classify', not {failures!r}")
+        self.failures = failures
+        surr_has = getattr(self.gp_surr, "failures", None)
+        if failures is None:
+            if surr_has:
+                raise ValueError("the surrogate was constructed with failures='classify': pass it to run(objective, failures='classify') too")
+            return
+        if not isinstance(self.gp_surr, GPRSurrogate):
+            raise ValueError(f"failed evaluations are modelled by GPRSurrogate, not by {type(self.gp_surr).__name__}")
+        if self.saver is not None:
+            raise ValueError("failures='classify' and a saver: the saver's (result, score) pairs have no place for a failed evaluation")
+        if self.eval_repeats_noise:
+            raise ValueError("failures='classify' and eval_repeats_noise: a failed evaluation has no score variance")
+        if self.gp_surr.refit_every != 1:
+            raise ValueError("failures='classify': refit_every must be 1 (every update retrains the classifier)")
+        if getattr(self.gp_surr, "hyper", "point") != "point":
+            raise ValueError("failures='classify' is not integrated over a hyper-parameter ensemble: hyper must be 'point'")
+        if self.method != "tree":
+            raise ValueError("failures='classify' drives the tree exploration only")
+        if not surr_has:
+            raise ValueError("run(failures='classify') needs a surrogate that models them: construct it as GPRSurrogate(failures='classify')")
+
     def run(self, objective_function, init_samples=None, eval_repeats=1, eval_repeats_function=np.mean,
-            eval_repeats_noise=False, constraints=None, **kwargs):
-        """``constraints`` (not in the reference): a list of ``pygpso_amd.constraints.Constraint``.  The objective then
+            eval_repeats_noise=False, constraints=None, failures=None, **kwargs):
+        """``failures`` (not in the reference): None, or "classify" -- an evaluation whose score is not finite (NaN, +-inf; any
+        repeat of it under ``eval_repeats``) is recorded as FAILED: its leaf is evaluated, carries the score -inf and is never
+        selected for splitting, and the surrogate (constructed as ``GPRSurrogate(failures="classify")``) models the
+        probability of success and gates the leaves by it, together with ``constraints`` if there are any.  An iteration in
+        which nothing was evaluated and every unsampled gp-based leaf is gated ends the run with a warning.  Returns the best
+        finite score.  Refused with failures: a saver, ``save_state`` / ``resume_from_saved``, ``refit_every`` > 1,
+        ``eval_repeats_noise``, ``hyper="marginal"``, a surrogate other than ``GPRSurrogate``, ``exploration_method="sample"`` (as
+        with constraints: the gate is the tree loop's).
+        ``constraints`` (not in the reference): a list of ``pygpso_amd.constraints.Constraint``.  The objective then
         returns ``(score, c_1 .. c_J)``; initial samples and selected leaves store both, repeats aggregate the constraint
         outputs with the same function as the scores, and leaves are ranked in gate mode under the surrogate's score-unit
         acquisition (the surrogate must have been constructed with the same list: ``GPRSurrogate(constraints=...)``).  A gated leaf is never evaluated.
@@ -381,6 +429,7 @@ class GPSOptimiser:
         self._check_repeats_noise(eval_repeats_noise, eval_repeats, eval_repeats_function)
         self.eval_repeats_noise = bool(eval_repeats_noise)
         self._set_constraints(constraints)
+        self._set_failures(failures)
         self.obj_func = objective_function
         self.eval_repeats = eval_repeats
         assert callable(eval_repeats_function)
@@ -405,6 +454,9 @@ class GPSOptimiser:
 
     # -- persistence -----------------------------------------------------------------------------
     def save_state(self, folder):
+        if self.failures:
+            raise ValueError("a run with failures='classify' is not saved (save_state / resume_from_saved): the failed points and the "
+                             "classifier have no place in the saved folder")
         if self.constraints:
             raise ValueError("a run with constraints is not saved (save_state / resume_from_saved): the constraint outputs and models "
                              "have no place in the saved folder")
