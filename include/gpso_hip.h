@@ -1028,6 +1028,75 @@ int gpso_constrained_success_fold_host(const gpso_acq* acq, const gpso_cspec* cs
                                        int64_t m, const double* success_mean, const double* success_var, double* value,
                                        double* logpof);
 
+/* ---- bi-objective search: a Pareto front and the exact expected hypervolume improvement ---------
+ * No counterpart in the reference.  Emmerich, Giannakoglou & Naujoks (2006); Emmerich, Yang, Deutz et al. (2016): with two
+ * objectives to MAXIMISE, a leaf is ranked by the expected growth of the hypervolume its outcome adds to the front found so
+ * far.  The first objective is the posterior resident on ctx.  The second is ONE MEMBER of the constraint set -- an output
+ * declared as a constraint already has its exact GP there --, named by gpso_ehvi.member; nothing new is made resident, and
+ * gpso_constraint_push, the set's lifetime and the constrained calls are what they were.  The REMAINING members, and the
+ * success member where one is resident, stay constraints: their logpof weights or gates the EHVI.
+ *
+ * gpso_ehvi: member -- objective 2's index in the set; latent -- non-zero: s^2 = max(var - noise, 0) for both objectives,
+ *   noise being slot 5 of each model's own hyper block, zero: the predictive variance clamped at 0; p and front -- the front
+ *   as p pairs (f1, f2), host memory, f1 strictly ascending, f2 strictly descending, every point strictly above ref in both
+ *   coordinates, p <= GPSO_EHVI_FRONT_MAX (p = 0: no front yet, front may be NULL); ref -- the reference point (r1, r2).
+ * Per leaf, with a_0 = r1, a_k = f1 of point k, a_{p+1} = +inf, strip heights h_k = f2 of point k + 1 (k < p), h_p = r2,
+ * Y1 ~ N(mean1, s1^2) and Y2 ~ N(mean2, s2^2) independent, g(x) = E[(Y1 - x)+] = s1 H((mean1 - x) / s1), e_k = E[(Y2 - h_k)+],
+ * H(z) = phi(z) + z Phi(z) (s = 0: max(mean - x, 0)):
+ *     EHVI = sum_{k=0..p} (g(a_k) - g(a_{k+1})) e_k,     g(+inf) = 0          (exact; p = 0: g(r1) e_0)
+ * The p + 1 terms occupy slots 0 .. p of 64, the rest are +0.0, and are added as slot[i] += slot[i + w] for w = 32, 16, 8,
+ * 4, 2, 1: an order that is the same on the device (a wave a leaf, a strip a lane, six shuffle steps) and on the host, so a
+ * device value has the bits of gpso_ehvi_fold_host on the same columns; exp and erfc are the library's own, not libm's.
+ * A NaN mean or variance of either objective: NaN (the arg-max then picks it); a mean of -inf: 0; else a mean of +inf: +inf.
+ *     logpof = sum of the constrained calls' log Phi terms over the members OTHER than `member`, index order, from its
+ *              first term; the success member's term last; no term at all: +0.0
+ *   cspec NULL: value = EHVI (logpof is still reported).
+ *   GPSO_CON_WEIGHT: value = EHVI exp(logpof); -inf where logpof < log_pof_min.
+ *   GPSO_CON_GATE: value = EHVI's own bits where logpof >= log_pof_min, else -inf; log_pof_min = -inf: no gate.
+ *   A NaN logpof gives a NaN value in both modes but the open gate.
+ * gpso_ehvi_values: value / logpof [m] and mean / var [2 m] -- the objective's column, then the member's --, each nullable,
+ *   in out_mem.  The columns are gpso_constrained_acq_values' (the same stage 1), bit for bit.
+ * gpso_best_ehvi: per segment (seg_off / nseg as gpso_constrained_best_acq) the arg-max of value: the first maximum wins, a
+ *   NaN beats every number, idx is relative to the segment (-1 and NaNs for an empty one); value / logpof [nseg] and mean /
+ *   var [2 nseg] host, nullable: the winner's entries of gpso_ehvi_values' columns, bit for bit.
+ * gpso_ehvi_fold_host: the fold alone on the host, no context and no GPU (ehvi->member is ignored): the two objectives'
+ *   columns [m] and noise variances, the OTHER members' columns [k m] (objective 2 already left out; k >= 0, at most 15) with
+ *   other_noise / threshold / sense [k], success_mean / success_var [m] (both NULL: no success member).  GPSO_OK or GPSO_E_ARG.
+ * GPSO_E_ARG: NULL ehvi; member outside [0, J); p outside [0, 63]; p > 0 with a NULL front; a front or reference entry that
+ *   is not finite; f1 not strictly ascending; f2 not strictly descending; a front point not strictly above ref in both
+ *   coordinates; cspec with GPSO_CON_FEASIBILITY (gpso_constrained_* serve it), an unknown mode, or log_pof_min NaN or > 0;
+ *   a GPSO_F32 context; N > 128; m < 1; (J + 1) * m > 2^28; bad dtype / memory / out_mem; nseg outside [1, 1024] or bad
+ *   seg_off; NULL xs, idx, or every output.
+ * GPSO_E_STATE: no constraint set (a success member alone is no objective); a stale set or success member; no exact-GP
+ *   posterior fitted on ctx; an ensemble resident on ctx; an asynchronous best-UCB call open.
+ * Every refusal comes before anything is allocated or enqueued.  The calls leave both posteriors, gpso_posterior_hash, the
+ * set and the success member as they are.  gpso_last_ms(ctx, 1) covers a call; gpso_last_count(ctx, 0) and (ctx, 1) are m.
+ * A front of more than 63 points is the caller's to thin (pygpso_amd.pareto.truncate_front: the EHVI over a subset of the
+ * front is an upper bound).
+ * Out of scope: more than two objectives; log-EHVI (float64 EHVI is exactly 0 far behind the front, such leaves tie and the
+ * first wins: the follow-up, as log-EI was to EI); correlated objectives; N > 128 and GPSO_F32; _begin / _end, grown
+ * leaves, sharded and screened variants; gpso_best_batch; the ensemble; the optimiser's loop (EHVI is not in score units). */
+#define GPSO_EHVI_FRONT_MAX 63
+typedef struct {
+  int member;          /* objective 2: its index in the constraint set */
+  int latent;          /* non-zero: both objectives without their noise variance */
+  int p;               /* points of the front, 0 .. GPSO_EHVI_FRONT_MAX */
+  const double* front; /* host [2 p]: (f1, f2) pairs, f1 ascending; NULL where p = 0 */
+  double ref[2];       /* the reference point (r1, r2) */
+} gpso_ehvi;
+int gpso_ehvi_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_ehvi* ehvi,
+                     const gpso_cspec* cspec /* nullable */, double* value, double* logpof /* [m] */, double* mean,
+                     double* var /* [2 m]: objective, then member; each nullable */, int out_mem);
+int gpso_best_ehvi(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg,
+                   const gpso_ehvi* ehvi, const gpso_cspec* cspec /* nullable */, int64_t* idx, double* value,
+                   double* logpof /* [nseg] */, double* mean, double* var /* [2 nseg], each nullable */);
+int gpso_ehvi_fold_host(const gpso_ehvi* ehvi /* member ignored */, const gpso_cspec* cspec /* nullable */,
+                        const double* mean1, const double* var1, double noise1, const double* mean2, const double* var2,
+                        double noise2, const double* other_mean, const double* other_var /* [k m] */,
+                        const double* other_noise, const double* threshold, const int* sense /* [k] */, int k /* >= 0 */,
+                        int64_t m, const double* success_mean, const double* success_var /* [m], nullable */,
+                        double* value, double* logpof);
+
 /* ---- ternary geometry on device (LeafNode.grow, gpso/param_space.py:175-200,257-307) -------- */
 
 /* Centres of levels 0..depth-1 of the ternary subtree under each of nseg boxes, generated on the

@@ -90,6 +90,16 @@ class GpsoCspec(C.Structure):
 
 _c_cspec_p = C.POINTER(GpsoCspec)
 
+EHVI_FRONT_MAX = 63  # points of the front a gpso_ehvi record may carry
+
+
+class GpsoEhvi(C.Structure):
+    """``gpso_ehvi``: objective 2's member index, the front and the reference point of an EHVI call."""
+    _fields_ = [("member", C.c_int), ("latent", C.c_int), ("p", C.c_int), ("front", C.POINTER(C.c_double)), ("ref", C.c_double * 2)]
+
+
+_c_ehvi_p = C.POINTER(GpsoEhvi)
+
 # every symbol include/gpso_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "gpso_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
@@ -216,6 +226,13 @@ SIGNATURES = {
     "gpso_constrained_success_fold_host": (C.c_int, [_c_acq_p, _c_cspec_p, _c_double_p, _c_double_p, C.c_double, _c_double_p,
                                                      _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int, C.c_int64,
                                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_ehvi_values": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_ehvi_p, _c_cspec_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_int]),
+    "gpso_best_ehvi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, _c_ehvi_p, _c_cspec_p,
+                                 _c_int64_p, _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
+    "gpso_ehvi_fold_host": (C.c_int, [_c_ehvi_p, _c_cspec_p, _c_double_p, _c_double_p, C.c_double, _c_double_p, _c_double_p, C.c_double,
+                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_int, C.c_int64,
+                                      _c_double_p, _c_double_p, _c_double_p, _c_double_p]),
     "gpso_success_prob_host": (C.c_int, [_c_double_p, _c_double_p, C.c_int64, _c_double_p, _c_double_p]),
     "gpso_predict_prob": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_int]),

@@ -3095,6 +3095,63 @@ int gpso_constrained_success_fold_host(const gpso_acq* acq, const gpso_cspec* cs
   return GPSO_OK;
 }
 
+// ---- bi-objective search (ehvi.hpp) ---------------------------------------------------------------------
+// what the EHVI calls refuse about their two records before the engine looks at the context
+static const char* ehvi_refusal(const gpso_ehvi* e, const gpso_cspec* cspec) {
+  if (!e) return "ehvi must not be NULL";
+  if (const char* why = gpso::ehvi_front_refusal(e->p, e->front, e->ref)) return why;
+  if (!cspec) return nullptr;
+  if (cspec->mode == GPSO_CON_FEASIBILITY) return "GPSO_CON_FEASIBILITY ranks by logpof alone: gpso_constrained_best_acq / gpso_constrained_acq_values serve it";
+  if (cspec->mode != GPSO_CON_WEIGHT && cspec->mode != GPSO_CON_GATE) return "unknown cspec.mode";
+  if (cspec->log_pof_min != cspec->log_pof_min || cspec->log_pof_min > 0.0) return "cspec.log_pof_min must be a log-probability (<= 0; -inf: no gate)";
+  return nullptr;
+}
+static gpso::EhviSpec ehvi_spec(const gpso_ehvi* e, const gpso_cspec* cspec) {
+  gpso::EhviSpec s;
+  s.member = e->member;
+  s.latent = e->latent != 0 ? 1 : 0;
+  s.p = e->p;
+  gpso::ehvi_strips(e->p, e->front, e->ref, s.xa, s.xh);
+  s.has_con = cspec != nullptr;
+  if (cspec) s.con = con_spec(cspec);
+  return s;
+}
+
+int gpso_ehvi_values(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_ehvi* ehvi, const gpso_cspec* cspec,
+                     double* value, double* logpof, double* mean, double* var, int out_mem) {
+  ENTER();
+  if (const char* why = ehvi_refusal(ehvi, cspec)) return ctx->fail(GPSO_E_ARG, "gpso_ehvi_values: %s", why);
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "gpso_ehvi_values: bad out_mem %d", out_mem);
+  return ctx->eng->ehvi_values(xs, xs_dtype, xs_mem, m, ehvi_spec(ehvi, cspec), value, logpof, mean, var, out_mem);
+}
+
+int gpso_best_ehvi(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const gpso_ehvi* ehvi,
+                   const gpso_cspec* cspec, int64_t* idx, double* value, double* logpof, double* mean, double* var) {
+  ENTER();
+  if (const char* why = ehvi_refusal(ehvi, cspec)) return ctx->fail(GPSO_E_ARG, "gpso_best_ehvi: %s", why);
+  return ctx->eng->best_ehvi(xs, xs_dtype, xs_mem, m, seg_off, nseg, ehvi_spec(ehvi, cspec), idx, value, logpof, mean, var);
+}
+
+int gpso_ehvi_fold_host(const gpso_ehvi* ehvi, const gpso_cspec* cspec, const double* mean1, const double* var1, double noise1,
+                        const double* mean2, const double* var2, double noise2, const double* other_mean, const double* other_var,
+                        const double* other_noise, const double* threshold, const int* sense, int k, int64_t m, const double* success_mean,
+                        const double* success_var, double* value, double* logpof) {
+  if (ehvi_refusal(ehvi, cspec) != nullptr || !mean1 || !var1 || !mean2 || !var2 || noise1 != noise1 || noise2 != noise2 || k < 0 ||
+      k > gpso::kConstraintsMax - 1 || m < 1 || (!value && !logpof) || (success_mean == nullptr) != (success_var == nullptr))
+    return GPSO_E_ARG;
+  if (k > 0 && (!other_mean || !other_var || !other_noise || !threshold || !sense)) return GPSO_E_ARG;
+  double thr[gpso::kConstraintsMax] = {}, sn[gpso::kConstraintsMax] = {};
+  for (int i = 0; i < k; ++i) {
+    if ((sense[i] != 1 && sense[i] != -1) || !std::isfinite(threshold[i]) || other_noise[i] != other_noise[i]) return GPSO_E_ARG;
+    thr[i] = threshold[i];
+    sn[i] = (double)sense[i];
+  }
+  const gpso::EhviSpec s = ehvi_spec(ehvi, cspec);
+  gpso::ehvi_fold_host(s.latent, s.p, s.xa, s.xh, s.has_con, s.con, mean1, var1, noise1, mean2, var2, noise2, other_mean, other_var, other_noise,
+                       thr, sn, k, (long long)m, success_mean, success_var, value, logpof);
+  return GPSO_OK;
+}
+
 // ---- failed evaluations (success.hpp) ----------------------------------------------------------------
 int gpso_success_prob_host(const double* mean, const double* var, int64_t n, double* logprob, double* prob) {
   if (!mean || !var || n < 1 || (!logprob && !prob)) return GPSO_E_ARG;

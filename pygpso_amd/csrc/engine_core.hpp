@@ -11,6 +11,7 @@
 #include "constraints.hpp"
 #include "context.hpp"
 #include "devbuf.hpp"
+#include "ehvi.hpp"
 #include "ensemble.hpp"
 #include "resident.hpp"
 #include "screen.hpp"
@@ -695,11 +696,22 @@ struct EngineCore {
   int constraint_clear();
   int constraint_info(int* k, double* theta, double* threshold, int* sense) const;
   int constrained_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con);
+  int constrained_columns(const void* xs, int xs_dtype, int xs_mem, int64_t m, hipStream_t* s);
   int constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s);
   int constrained_acq_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, double* mean,
                              double* var, double* value, double* logpof, double* member_mean, double* member_var, int out_mem);
   int constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const AcqSpec& acq,
                            const ConSpec& con, int64_t* idx, double* mean, double* var, double* value, double* logpof);
+
+  // ---- bi-objective search (ehvi.hpp, ehvi.hip).  Nothing resident of its own: objective 2 is a member
+  // of the constraint set, the columns are the constrained calls' (constrained_columns), value and logpof land in con_val and
+  // the winners' three extra columns (objective 2's mean and variance, logpof) in con_win [3][nseg]
+  int ehvi_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e);
+  int ehvi_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e, hipStream_t* s);
+  int ehvi_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e, double* value, double* logpof, double* mean,
+                  double* var, int out_mem);
+  int best_ehvi(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const EhviSpec& e, int64_t* idx,
+                double* value, double* logpof, double* mean, double* var);
 
   // ---- failed evaluations (success.hpp).  The success member: ONE slot of the four copies a constraint
   // member has, of a Bernoulli-installed classifier posterior (res.bernoulli on its context) with an N and a kernel of its own.

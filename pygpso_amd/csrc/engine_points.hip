@@ -777,11 +777,12 @@ int EngineCore::constrained_refusals(const char* who, const void* xs, int xs_dty
   return refuse_if_async(who);
 }
 
-// ... and what both enqueue behind their refusals: the workspaces, the columns (stage 1: one launch for the objective on the
-// context's own buffers, one for the J members) and the fold (stage 2).  On return the stream is open (points_begin),
-// con_mean / con_var hold [1 + J][m] with the objective in row 0, con_val holds value [m] then logpof [m].  With a success
-// member (section 7s) one more K = 1 launch, with the member's own n and kernel, writes row 1 + J, and the fold reads it last
-int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s) {
+// ... and what both enqueue behind their refusals, in two stages.  The column stage (constrained_columns): the workspaces and
+// stage 1 -- one launch for the objective on the context's own buffers, one for the J members; with a success member (section
+// 7s) one more K = 1 launch, with the member's own n and kernel, writes row 1 + J.  On return the stream is open
+// (points_begin) and con_mean / con_var hold [1 + J (+ 1)][m] with the objective in row 0; con_val [2][m] is allocated.  The
+// EHVI calls (section 7t) run the same stage and fold the columns differently
+int EngineCore::constrained_columns(const void* xs, int xs_dtype, int xs_mem, int64_t m, hipStream_t* s) {
   ctx->tick_timing();
   const int k = constraint_count();
   const bool suc = success_present();
@@ -811,13 +812,23 @@ int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, in
     u.mean = g.mean + (int64_t)(k + 1) * m; u.var = g.var + (int64_t)(k + 1) * m;
     if (launch_ensemble_members(*s, u) != 0) return launch_status();
   }
+  return launch_status();
+}
+
+// ... and the fold (stage 2) over those columns: con_val holds value [m] then logpof [m]; the fold reads the success member's
+// row last
+int EngineCore::constrained_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, const ConSpec& con, hipStream_t* s) {
+  int rc = constrained_columns(xs, xs_dtype, xs_mem, m, s);
+  if (rc) return rc;
+  const int k = constraint_count();
+  double *cm = as<double>(con_mean), *cv = as<double>(con_var);
   ConFoldLaunch f;
   f.acq = acq; f.con = con;
-  f.obj_mean = g.mean; f.obj_var = g.var; f.obj_hyper = g.hyper;
-  f.cmean = c.mean; f.cvar = c.var; f.chyper = c.hyper; f.hyper_stride = kEnsHyperStride;
+  f.obj_mean = cm; f.obj_var = cv; f.obj_hyper = as<double>(hyper);
+  f.cmean = cm + m; f.cvar = cv + m; f.chyper = as<double>(con_hyper); f.hyper_stride = kEnsHyperStride;
   for (int i = 0; i < k; ++i) { f.thr[i] = con_thr[i]; f.sense[i] = con_sense[i]; }
   f.nj = k; f.ld = m; f.m = m;
-  if (suc) { f.smean = u.mean; f.svar = u.var; }
+  if (success_present()) { f.smean = cm + (int64_t)(k + 1) * m; f.svar = cv + (int64_t)(k + 1) * m; }
   f.value = as<double>(con_val); f.logpof = f.value + m;
   launch_constrained_fold(*s, f);
   return launch_status();
@@ -876,6 +887,113 @@ int EngineCore::constrained_best_acq(const void* xs, int xs_dtype, int xs_mem, i
     if (var) var[i] = rec[(size_t)i * 4 + 1];
     if (value) value[i] = rec[(size_t)i * 4 + 2];
     if (logpof) logpof[i] = rec[(size_t)nseg * 4 + i];
+    int64_t w;
+    std::memcpy(&w, &rec[(size_t)i * 4 + 3], 8);
+    idx[i] = w;
+  }
+  return GPSO_OK;
+}
+
+// ---- bi-objective search (ehvi.hpp, ehvi.hip).  What both EHVI calls refuse, before anything is
+// allocated or enqueued: the constrained calls' state rules (in those calls' words, under this call's name), then a set that
+// holds no constraint model at all, then objective 2's index.  The record itself -- the front, the reference point, cspec --
+// was checked by the C-ABI entry
+int EngineCore::ehvi_refusals(const char* who, const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e) {
+  int rc = constrained_refusals(who, xs, xs_dtype, xs_mem, m, AcqSpec(GPSO_ACQ_EI, e.latent, 0.0, 0.0, 0.0), e.has_con ? e.con : ConSpec());
+  if (rc) return rc;
+  const int k = constraint_count();
+  if (k == 0)
+    return ctx->fail(GPSO_E_STATE, "%s: no constraint set on this context: objective 2 is a member of the set (gpso_constraint_push its model "
+                                   "first; a success member alone is no objective)", who);
+  if (e.member < 0 || e.member >= k) return ctx->fail(GPSO_E_ARG, "%s: member=%d outside [0, %d): objective 2 is a member of the set", who, e.member, k);
+  return GPSO_OK;
+}
+
+// the constrained calls' column stage, then the EHVI fold: con_val holds value [m] then logpof [m]
+int EngineCore::ehvi_enqueue(const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e, hipStream_t* s) {
+  int rc = constrained_columns(xs, xs_dtype, xs_mem, m, s);
+  if (rc) return rc;
+  const int k = constraint_count();
+  double *cm = as<double>(con_mean), *cv = as<double>(con_var);
+  EhviFoldLaunch f;
+  std::memcpy(f.xa, e.xa, sizeof(f.xa));
+  std::memcpy(f.xh, e.xh, sizeof(f.xh));
+  f.p = e.p; f.latent = e.latent; f.has_con = e.has_con ? 1 : 0; f.con = e.con;
+  f.obj_mean = cm; f.obj_var = cv; f.obj_hyper = as<double>(hyper);
+  f.cmean = cm + m; f.cvar = cv + m; f.chyper = as<double>(con_hyper); f.hyper_stride = kEnsHyperStride;
+  f.member = e.member;
+  for (int i = 0; i < k; ++i) {
+    if (i == e.member) continue;
+    f.oidx[f.nother] = i; f.othr[f.nother] = con_thr[i]; f.osense[f.nother] = con_sense[i];
+    ++f.nother;
+  }
+  if (success_present()) { f.smean = cm + (int64_t)(k + 1) * m; f.svar = cv + (int64_t)(k + 1) * m; }
+  f.ld = m; f.m = m;
+  f.value = as<double>(con_val); f.logpof = f.value + m;
+  launch_ehvi_fold(*s, f);
+  return launch_status();
+}
+
+int EngineCore::ehvi_values(const void* xs, int xs_dtype, int xs_mem, int64_t m, const EhviSpec& e, double* value, double* logpof, double* mean,
+                            double* var, int out_mem) {
+  int rc = ehvi_refusals("gpso_ehvi_values", xs, xs_dtype, xs_mem, m, e);
+  if (rc) return rc;
+  if (!value && !logpof && !mean && !var) return ctx->fail(GPSO_E_ARG, "gpso_ehvi_values: every output is NULL");
+  hipStream_t s;
+  if ((rc = ehvi_enqueue(xs, xs_dtype, xs_mem, m, e, &s))) return rc;
+  const hipMemcpyKind kind = out_mem == GPSO_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  const double *cm = as<double>(con_mean), *cv = as<double>(con_var), *val = as<double>(con_val);
+  const size_t col = (size_t)m * 8;
+  const int64_t row2 = (int64_t)(1 + e.member) * m;  // objective 2's row of the columns
+  if (value) HIPCHECK(hipMemcpyAsync(value, val, col, kind, s));
+  if (logpof) HIPCHECK(hipMemcpyAsync(logpof, val + m, col, kind, s));
+  if (mean) {
+    HIPCHECK(hipMemcpyAsync(mean, cm, col, kind, s));
+    HIPCHECK(hipMemcpyAsync(mean + m, cm + row2, col, kind, s));
+  }
+  if (var) {
+    HIPCHECK(hipMemcpyAsync(var, cv, col, kind, s));
+    HIPCHECK(hipMemcpyAsync(var + m, cv + row2, col, kind, s));
+  }
+  return points_end(s, m);
+}
+
+// the arg-max of the constrained calls (launch_seg_argmax: its segments, its first maximum, its NaN-wins rule) over the EHVI
+// fold's value; the gather runs once per extra winner column -- objective 2's mean and variance, logpof
+int EngineCore::best_ehvi(const void* xs, int xs_dtype, int xs_mem, int64_t m, const int64_t* seg_off, int nseg, const EhviSpec& e, int64_t* idx,
+                          double* value, double* logpof, double* mean, double* var) {
+  int rc = ehvi_refusals("gpso_best_ehvi", xs, xs_dtype, xs_mem, m, e);
+  if (rc) return rc;
+  if (!idx) return ctx->fail(GPSO_E_ARG, "gpso_best_ehvi: idx must not be NULL");
+  if (nseg < 1 || nseg > 1024) return ctx->fail(GPSO_E_ARG, "gpso_best_ehvi: nseg=%d outside [1, 1024]", nseg);
+  std::vector<int64_t> so;
+  if ((rc = checked_segments(m, seg_off, nseg, so, "M"))) return rc;
+  const int nblk = argmax_blocks(m, nseg);
+  if ((rc = ensure(con_seg, (size_t)(nseg + 1) * 8))) return rc;
+  if ((rc = ensure(con_part, (size_t)nseg * kArgmaxBlocks * kArgmaxPartialBytes))) return rc;
+  if ((rc = ensure(con_out, (size_t)(nseg * 4 + 2) * 8))) return rc;
+  if ((rc = ensure(con_win, (size_t)3 * nseg * 8))) return rc;
+  hipStream_t s;
+  if ((rc = ehvi_enqueue(xs, xs_dtype, xs_mem, m, e, &s))) return rc;
+  HIPCHECK(hipMemcpyAsync(con_seg.p, so.data(), (size_t)(nseg + 1) * 8, hipMemcpyHostToDevice, s));
+  const double *cm = as<double>(con_mean), *cv = as<double>(con_var), *val = as<double>(con_val);
+  const int64_t row2 = (int64_t)(1 + e.member) * m;
+  double* win = as<double>(con_win);
+  launch_seg_argmax(s, cm, cv, val, as<int64_t>(con_seg), nseg, nblk, con_part.p, as<double>(con_out));
+  launch_constrained_gather(s, cm + row2, as<int64_t>(con_seg), as<double>(con_out), nseg, win);
+  launch_constrained_gather(s, cv + row2, as<int64_t>(con_seg), as<double>(con_out), nseg, win + nseg);
+  launch_constrained_gather(s, val + m, as<int64_t>(con_seg), as<double>(con_out), nseg, win + 2 * nseg);
+  if ((rc = launch_status())) return rc;
+  std::vector<double> rec((size_t)nseg * 7);
+  HIPCHECK(hipMemcpyAsync(rec.data(), con_out.p, (size_t)nseg * 4 * 8, hipMemcpyDeviceToHost, s));
+  HIPCHECK(hipMemcpyAsync(rec.data() + (size_t)nseg * 4, con_win.p, (size_t)nseg * 3 * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = points_end(s, m))) return rc;
+  const double* w3 = rec.data() + (size_t)nseg * 4;
+  for (int i = 0; i < nseg; ++i) {
+    if (mean) { mean[i] = rec[(size_t)i * 4]; mean[nseg + i] = w3[i]; }
+    if (var) { var[i] = rec[(size_t)i * 4 + 1]; var[nseg + i] = w3[nseg + i]; }
+    if (value) value[i] = rec[(size_t)i * 4 + 2];
+    if (logpof) logpof[i] = w3[2 * nseg + i];
     int64_t w;
     std::memcpy(&w, &rec[(size_t)i * 4 + 3], 8);
     idx[i] = w;

@@ -1123,6 +1123,83 @@ class HipGPEngine:
                                      "kind cannot be weighted), constraint record or arguments")
         return val, lp
 
+    # -- bi-objective search (csrc/ehvi.hpp) ---------------------------------------------------
+    @staticmethod
+    def _ehvi_rec(member, front, ref, latent):
+        """The ``gpso_ehvi`` record and the array its ``front`` points into (keep it alive over the call)."""
+        f = L.as_f64(np.zeros((0, 2)) if front is None else np.asarray(front, dtype=np.float64).reshape(-1, 2))
+        r = L.as_f64(np.asarray(ref, dtype=np.float64).reshape(-1), (2,))
+        rec = L.GpsoEhvi(int(member), 1 if latent else 0, int(f.shape[0]), L.dptr(f) if f.shape[0] else None, (C.c_double * 2)(r[0], r[1]))
+        return rec, f
+
+    @staticmethod
+    def _ehvi_cspec(mode, log_pof_min):
+        """``None``: no cspec (value = EHVI); else the ``gpso_cspec`` of ``mode``."""
+        return None if mode is None else HipGPEngine._cspec(mode, log_pof_min)
+
+    def ehvi_values(self, xs, member, front, ref, latent=True, mode=None, log_pof_min=-np.inf):
+        """The exact EHVI of (the objective, constraint-set member ``member``) over ``front`` [P, 2] (rows (f1, f2), f1
+        ascending) and the reference point ``ref`` at the points ``xs`` -> (value[M], logpof[M], mean[2, M], var[2, M]):
+        the ranked value (``mode`` None: the EHVI; "weight" / "gate": under the other members' logpof), logpof, and the two
+        objectives' predictive columns (row 0: the objective, row 1: the member)."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec, _front = self._ehvi_rec(member, front, ref, latent)
+        cs = self._ehvi_cspec(mode, log_pof_min)
+        val, lp = (np.empty(m, dtype=np.float64) for _ in range(2))
+        mean, var = (np.empty((2, m), dtype=np.float64) for _ in range(2))
+        self._check(self._lib.gpso_ehvi_values(self._h, ptr, dt, mem, m, C.byref(rec), None if cs is None else C.byref(cs),
+                                               C.c_void_p(val.ctypes.data), C.c_void_p(lp.ctypes.data), C.c_void_p(mean.ctypes.data),
+                                               C.c_void_p(var.ctypes.data), L.MEM_HOST))
+        return val, lp, mean, var
+
+    def best_ehvi(self, xs, member, front, ref, latent=True, mode=None, log_pof_min=-np.inf, seg_off=None):
+        """Per segment the arg-max of ``ehvi_values``' value -> (idx[nseg], value[nseg], logpof[nseg], mean[2, nseg],
+        var[2, nseg])."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        nseg, so_ptr, _so = self._seg_args(seg_off)
+        rec, _front = self._ehvi_rec(member, front, ref, latent)
+        cs = self._ehvi_cspec(mode, log_pof_min)
+        idx = np.empty(nseg, dtype=np.int64)
+        val, lp = (np.empty(nseg, dtype=np.float64) for _ in range(2))
+        mean, var = (np.empty((2, nseg), dtype=np.float64) for _ in range(2))
+        self._check(self._lib.gpso_best_ehvi(self._h, ptr, dt, mem, m, so_ptr, nseg, C.byref(rec), None if cs is None else C.byref(cs),
+                                             L.i64ptr(idx), L.dptr(val), L.dptr(lp), L.dptr(mean), L.dptr(var)))
+        return idx, val, lp, mean, var
+
+    @staticmethod
+    def ehvi_fold_host(front, ref, mean1, var1, noise1, mean2, var2, noise2, other_mean=None, other_var=None, other_noise=None,
+                       threshold=None, sense=None, success_mean=None, success_var=None, latent=True, mode=None, log_pof_min=-np.inf):
+        """The device's EHVI fold on the CPU (``gpso_ehvi_fold_host``: no context, no GPU): the two objectives' columns [M]
+        and noise variances, the OTHER members' columns [K, M] (objective 2 left out; K >= 0) with their noise variances,
+        thresholds and senses [K], the success member's latent columns [M] or None -> (value[M], logpof[M])."""
+        m1 = L.as_f64(np.asarray(mean1, dtype=np.float64).reshape(-1))
+        m = m1.shape[0]
+        v1, m2, v2 = (L.as_f64(np.asarray(a, dtype=np.float64).reshape(-1), (m,)) for a in (var1, mean2, var2))
+        om = np.zeros((0, m)) if other_mean is None else L.as_f64(np.asarray(other_mean, dtype=np.float64).reshape(-1, m))
+        k = om.shape[0]
+        ov = np.zeros((0, m)) if other_var is None else L.as_f64(np.asarray(other_var, dtype=np.float64).reshape(-1, m), (k, m))
+        nz = L.as_f64(np.asarray([] if other_noise is None else other_noise, dtype=np.float64).reshape(-1), (k,))
+        thr = L.as_f64(np.asarray([] if threshold is None else threshold, dtype=np.float64).reshape(-1), (k,))
+        sn = np.ascontiguousarray(np.asarray([] if sense is None else sense).reshape(-1), dtype=np.intc)
+        if sn.shape != (k,):
+            raise ValueError(f"sense must have {k} entries")
+        sm = None if success_mean is None else L.as_f64(np.asarray(success_mean, dtype=np.float64).reshape(-1), (m,))
+        sv = None if success_var is None else L.as_f64(np.asarray(success_var, dtype=np.float64).reshape(-1), (m,))
+        val, lp = (np.empty(m, dtype=np.float64) for _ in range(2))
+        rec, _front = HipGPEngine._ehvi_rec(0, front, ref, latent)
+        cs = HipGPEngine._ehvi_cspec(mode, log_pof_min)
+        some = k > 0
+        rc = L.load().gpso_ehvi_fold_host(
+            C.byref(rec), None if cs is None else C.byref(cs), L.dptr(m1), L.dptr(v1), float(noise1), L.dptr(m2), L.dptr(v2), float(noise2),
+            L.dptr(om) if some else None, L.dptr(ov) if some else None, L.dptr(nz) if some else None, L.dptr(thr) if some else None,
+            sn.ctypes.data_as(C.POINTER(C.c_int)) if some else None, int(k), int(m), None if sm is None else L.dptr(sm),
+            None if sv is None else L.dptr(sv), L.dptr(val), L.dptr(lp))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_ehvi_fold_host: bad front (at most 63 finite points, f1 strictly ascending, f2 strictly "
+                                     "descending, every point strictly above the finite reference point), constraint record "
+                                     "(feasibility mode is not served) or arguments")
+        return val, lp
+
     # -- failed evaluations (csrc/success.hpp; DESIGN.md section 7s) ------------------------------------------------
     @staticmethod
     def success_prob_host(mean, var):

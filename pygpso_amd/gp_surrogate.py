@@ -1145,6 +1145,93 @@ class GPRSurrogate(GPSurrogate):
         return self.gpflow_model.constrained_best_acq(np.ascontiguousarray(leaves, dtype=np.float64), self._constrained_acq(spec, mode),
                                                       seg_off, self._constrained_incumbent(spec, incumbent))
 
+    # -- bi-objective search (pygpso_amd.pareto): the score and ONE lower-bounded constraint output as two
+    # objectives to maximise.  Outside the loop: EHVI is not in score units --
+    def _second_objective(self, second):
+        """The index of the constraint that serves as objective 2: a name or an index of a ``lower=`` constraint."""
+        if isinstance(second, str):
+            names = [c.name for c in self.constraints]
+            if second not in names:
+                raise ValueError(f"no constraint named {second!r} (constraints: {names})")
+            j = names.index(second)
+        else:
+            j = int(second)
+            if not 0 <= j < len(self.constraints):
+                raise ValueError(f"second={second}: the surrogate has {len(self.constraints)} constraints")
+        if self.constraints[j].sense != -1:
+            raise ValueError(f"{self.constraints[j]!r} is an upper bound: objective 2 is MAXIMISED above a reference value, declare it "
+                             "with lower=")
+        return j
+
+    def _ehvi_reference(self, j, scores, ref):
+        """(r1, r2): the caller's entries, else ``default_reference`` of the scores and the constraint's bound."""
+        from .pareto import default_reference
+
+        r1, r2 = (None, None) if ref is None else ref
+        if r1 is None:
+            if scores.shape[0] == 0:
+                raise ValueError("no evaluated point yet: a reference value for the score (ref=(r1, None)) is needed")
+            r1 = default_reference(scores.reshape(-1, 1))[0]
+        if r2 is None:
+            r2 = self.constraints[j].threshold
+        r = np.array([r1, r2], dtype=np.float64)
+        if not np.all(np.isfinite(r)):
+            raise ValueError(f"the reference point {r.tolist()} must be finite")
+        return r
+
+    def pareto_front(self, second, ref=None):
+        """The trade-off found so far between the score and the constraint output ``second`` (a name or an index of a
+        ``lower=`` constraint), both maximised -> (coords [P, D], front [P, 2]): the evaluated points on the front in
+        normed coordinates and their (score, f2) rows, score ascending.  A point counts when it is evaluated, not failed,
+        its OBSERVED outputs keep every OTHER bound, and it lies strictly above the reference point ``ref`` = (r1, r2)
+        (None entries: ``default_reference`` of the scores, and the constraint's own bound)."""
+        from .constraints import feasible_rows
+        from .pareto import pareto_front
+
+        j = self._second_objective(second)
+        x, y = self.current_training_data
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64).reshape(-1)
+        r = self._ehvi_reference(j, y, ref)
+        if y.shape[0] == 0:
+            return np.zeros((0, 0)), np.zeros((0, 2))
+        c = self.current_training_constraints
+        others = [i for i in range(len(self.constraints)) if i != j]
+        ok = feasible_rows([self.constraints[i] for i in others], c[:, others]) if others else np.ones(y.shape[0], dtype=bool)
+        Y = np.column_stack([y, c[:, j]])
+        ok &= (Y[:, 0] > r[0]) & (Y[:, 1] > r[1])
+        rows = np.flatnonzero(ok)
+        front, at = pareto_front(Y[rows])
+        return x[rows[at]], front
+
+    def ehvi_select(self, leaves, second, ref=None, mode="weight", seg_off=None):
+        """For use outside the loop: per segment of ``seg_off`` the row of ``leaves`` (normed coordinates) of the largest
+        exact expected hypervolume improvement of (score, constraint output ``second``) over ``pareto_front(second, ref)``,
+        weighted ("weight") or left as it is ("gate") by the probability that the OTHER constraints (and the evaluation
+        itself, under ``failures='classify'``) hold.  The surrogate's ``pof_min`` gates in BOTH modes, as in
+        ``constrained_select``: a leaf whose probability is below it is worth -inf, weighted or not (``pof_min=0``: no
+        gate).  ``mode=None``: the EHVI alone, no gate.  Returns
+        (idx, value, logpof, mean [2, nseg], var [2, nseg]).  Stores nothing.  A front of more than 63 points is thinned
+        (``pareto.truncate_front``, with a warning)."""
+        from .constraints import ConstrainedAcq
+        from .distributed import HipGPEngineGroup
+        from .pareto import truncate_front
+
+        if not self._constraints_live:
+            raise ValueError("ehvi_select: no constraint models are installed (constraints= with objective 2 as a lower= constraint, "
+                             "and one gp_update first)")
+        self._require_model()
+        if isinstance(self.gpflow_model.engine, HipGPEngineGroup):
+            raise NotImplementedError("ehvi_select: not offered on a multi-GPU engine group")
+        if mode not in (None, "weight", "gate"):
+            raise ValueError(f"mode must be None, 'weight' or 'gate', not {mode!r}")
+        j = self._second_objective(second)
+        r = self._ehvi_reference(j, np.asarray(self.current_training_data[1], dtype=np.float64).reshape(-1), ref)
+        _, front = self.pareto_front(j, r)
+        front = truncate_front(front, r)
+        cspec = None if mode is None else ConstrainedAcq(None, mode, self.pof_min)
+        return self.gpflow_model.best_ehvi(np.ascontiguousarray(leaves, dtype=np.float64), j, front, r, latent=True, cspec=cspec,
+                                           seg_off=seg_off)
+
     def _gp_train(self, x, y, s=None, c=None):
         """``s`` [N] (None: none): the known variance of each score, a fixed per-point noise term beside the trained one.
         ``c`` [N, J]: the observed constraint outputs (``constraints=`` only)."""

@@ -725,6 +725,29 @@ class HipGPR:
         return self._predicting(lambda: self.engine.constrained_acq_values(np.asarray(Xnew), acq, mode, lpm, incumbent=inc,
                                                                           want_members=want_members))
 
+    def _ehvi_args(self, cspec):
+        """``cspec``: None (value = EHVI) or a ``ConstrainedAcq`` whose mode and ``pof_min`` enter (its acquisition does not)."""
+        if cspec is None:
+            return None, -np.inf
+        self._constrained_args(cspec)
+        return cspec.mode, cspec.log_pof_min
+
+    def ehvi_values(self, Xnew, member, front, ref, latent=True, cspec=None):
+        """The exact EHVI of (this model, installed constraint model ``member``) over ``front`` [P, 2] and ``ref`` at
+        ``Xnew``: (value [M], logpof [M], mean [2, M], var [2, M])."""
+        if not hasattr(self.engine, "ehvi_values"):
+            raise NotImplementedError(f"EHVI is not available on {type(self.engine).__name__}")
+        mode, lpm = self._ehvi_args(cspec)
+        return self._predicting(lambda: self.engine.ehvi_values(np.asarray(Xnew), member, front, ref, latent, mode, lpm))
+
+    def best_ehvi(self, Xnew, member, front, ref, latent=True, cspec=None, seg_off=None):
+        """Per segment the row of ``Xnew`` of the largest ``ehvi_values`` value: (idx, value, logpof, mean [2, nseg],
+        var [2, nseg])."""
+        if not hasattr(self.engine, "best_ehvi"):
+            raise NotImplementedError(f"EHVI is not available on {type(self.engine).__name__}")
+        mode, lpm = self._ehvi_args(cspec)
+        return self._predicting(lambda: self.engine.best_ehvi(np.asarray(Xnew), member, front, ref, latent, mode, lpm, seg_off))
+
     # -- reporting ----------------------------------------------------------------------------
     def parameter_dict(self):
         return {
