@@ -625,6 +625,62 @@ int gpso_paths_eval(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int
 /* Draws and features of the valid path set; 0, 0 when none is resident. */
 int gpso_paths_info(gpso_ctx* ctx, int64_t* s, int64_t* f);
 
+/* Monte-Carlo batch acquisition over the resident path set (no counterpart in the reference): q rows
+ * of a batch picked by sequential greedy selection of the sample-average qEI / qNoisyEI / qPI over the S draws, which are
+ * the fixed base samples.  With V[s][j] the value of draw s at row j (gpso_paths_eval's bits) and t[s] the draw's bar:
+ *   GPSO_MC_QEI: gain(j) = (1/S) sum_s max(V[s][j] - t[s] - x[s], 0) -- draw order, double, nothing fused, one division.
+ *     x[s] is xi until a pick (or a pending point) has cleared the draw's bar by more than xi, and 0 from then on.  After
+ *     pick p the bar of every cleared draw moves: t[s] = max(t[s], V[s][p]); a draw the picks have not cleared keeps its
+ *     bar.  At xi = 0 that is max(V - t, 0) and t = max(t, V[p]) in every draw.  The margin is charged once per draw, so
+ *     the gains add up to the batch's value (below) whatever xi is.  The pick's fantasy therefore moves the means: a draw
+ *     in which the pick is high has a higher bar from then on.
+ *   GPSO_MC_QPI: gain(j) = (1/S) #{ s : not yet improved, V[s][j] > t[s] + xi } -- an integer count, one division.  The bars
+ *     stay; a draw is improved once a pick (or a pending point) has cleared its original bar.
+ *   Initial bars: incumbent_s[s] (host, [S]) when given, else acq->incumbent for every draw.  qNoisyEI is GPSO_MC_QEI with
+ *     incumbent_s[s] = the maximum of draw s over the evaluated points (gpso_paths_eval's best_val over them).
+ *   pending [b * D] (host float64, nullable with b = 0): points still being evaluated.  They are evaluated by the same
+ *     kernel as b more columns and folded into the bars (QEI) or the flags (QPI) before round 0, in their order, as picks
+ *     are; they are never candidates.
+ *   Arg-max: the first maximum wins a tie and a NaN beats every number (gpso_best_batch's rule).  A row with a NaN among
+ *     its terms (QPI: anywhere in its column) has a NaN gain.
+ *   A picked row is retired.  A row whose column equals the pick's in every draw has gain 0 from then on, so it is not
+ *     picked again (no coordinate comparison is made).
+ *   Ending: round 0's pick is always reported; a later round whose best gain is not > 0 ends the batch without reporting
+ *     that pick; a NaN gain is reported and ends the batch; no live row left ends it.  *n_picked <= q says how many entries
+ *     are valid; the rest of idx / gain / batch_value is not written.
+ *   idx / gain / batch_value [q] (host; the last two nullable): the pick, the gain it was ranked by, and the running sum of
+ *     the gains in pick order -- for QEI the batch's sample-average value (1/S) sum_s max over the picks of the improvement.
+ *   gain0 [m] (float64 living in out_mem, nullable): every row's round-0 gain -- at q = 1 the plain sample-average EI / PI.
+ * gpso_paths_batch_host: the same rounds on the host from given values [s * (m + b)] (draw-major: row s holds the m
+ *   candidates, then the b pending columns) -- the same header, the same roundings, the same end rules; no context and no
+ *   GPU.  A device gain has its bits on the same values.  incumbent_s as above; gain / batch_value / gain0 nullable.
+ *   Returns GPSO_OK or GPSO_E_ARG (a NULL acq / values / idx / n_picked, s outside [1, 256], and the bounds below).
+ * GPSO_E_STATE (gpso_paths_eval's conditions): no valid path set, or an asynchronous best-UCB ticket open.
+ * GPSO_E_ARG: a GPSO_F32 context; m < 1; q outside [1, 64]; b outside [0, 64], or b > 0 with pending NULL; S * (m + b) >
+ *   2^26; NULL xs / acq / idx / n_picked; an unknown kind; a xi, incumbent (where it is read) or incumbent_s entry that is
+ *   NaN.  +-inf bars are allowed: -inf makes round 0 rank by +inf ties, and the first row wins.
+ * Reads only: the posterior, its packed copies, the hyper block, the self-test's verdicts, gpso_posterior_hash and the path
+ * set stay bit for bit (a gpso_paths_eval after the call returns the bits of one before it); the workspace -- S * (m + b)
+ * doubles, padded -- is the call's own and grows only.  The same call gives the same bits; a row's gain0 bits depend neither
+ * on the rest of the batch nor on its place in it.  gpso_last_ms(ctx, 1) covers the call and (ctx, 0) its rounds alone --
+ * the fold of the pending columns, the q round and fold launches, the read-back of the picks; the rest is stage A --;
+ * gpso_last_count(ctx, 0) and (ctx, 1) are m.
+ * Out of scope: segments, grown leaves (_grow), the asynchronous _begin / _end pair, sharded groups. */
+#define GPSO_MC_QEI 0
+#define GPSO_MC_QPI 1
+typedef struct {
+  int kind;         /* GPSO_MC_QEI, GPSO_MC_QPI */
+  double xi;        /* improvement margin, in the paths' (latent) units */
+  double incumbent; /* the bar of every draw when incumbent_s is NULL */
+} gpso_mcacq;
+int gpso_paths_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_mcacq* acq,
+                          const double* incumbent_s /* [S] host, nullable */, const double* pending /* [b*D] host, nullable */,
+                          int b, int q, int64_t* idx, double* gain, double* batch_value /* [q] host, last two nullable */,
+                          int* n_picked, double* gain0 /* [m], nullable */, int out_mem);
+int gpso_paths_batch_host(const gpso_mcacq* acq, const double* values /* [s*(m+b)] draw-major */, int64_t s, int64_t m, int b,
+                          const double* incumbent_s, int q, int64_t* idx, double* gain, double* batch_value, int* n_picked,
+                          double* gain0);
+
 /* Replaces: GPSurrogate.gp_eval_best_ucb (gpso/gp_surrogate.py:313-328): predict_y, then
  * ucb = mean + varsigma * VAR, then first arg-max -- per segment.  seg_off[nseg+1] (host) delimits
  * independent leaf batches (NULL with nseg = 1 means one segment [0, M)); outputs (host, nseg each):

@@ -100,6 +100,18 @@ class GpsoEhvi(C.Structure):
 
 _c_ehvi_p = C.POINTER(GpsoEhvi)
 
+MC_QEI, MC_QPI = 0, 1  # gpso_mcacq.kind
+MC_KINDS = {"qei": MC_QEI, "qnei": MC_QEI, "qpi": MC_QPI}  # (qNoisyEI is QEI under per-draw bars)
+MC_MAX_PICKS = MC_MAX_PENDING = 64
+
+
+class GpsoMcAcq(C.Structure):
+    """``gpso_mcacq``: what a Monte-Carlo batch call over the path draws ranks by."""
+    _fields_ = [("kind", C.c_int), ("xi", C.c_double), ("incumbent", C.c_double)]
+
+
+_c_mcacq_p = C.POINTER(GpsoMcAcq)
+
 # every symbol include/gpso_hip.h declares: (restype, argtypes)
 SIGNATURES = {
     "gpso_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int]),
@@ -170,6 +182,10 @@ SIGNATURES = {
     "gpso_paths_eval": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p, C.c_int, C.c_void_p, C.c_int,
                                   _c_int64_p, _c_double_p]),
     "gpso_paths_info": (C.c_int, [C.c_void_p, _c_int64_p, _c_int64_p]),
+    "gpso_paths_best_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_mcacq_p, _c_double_p, _c_double_p, C.c_int,
+                                        C.c_int, _c_int64_p, _c_double_p, _c_double_p, C.POINTER(C.c_int), C.c_void_p, C.c_int]),
+    "gpso_paths_batch_host": (C.c_int, [_c_mcacq_p, _c_double_p, C.c_int64, C.c_int64, C.c_int, _c_double_p, C.c_int, _c_int64_p,
+                                        _c_double_p, _c_double_p, C.POINTER(C.c_int), _c_double_p]),
     "gpso_best_ucb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, _c_int64_p,
                                 C.c_int, C.c_double, _c_int64_p, _c_double_p, _c_double_p,
                                 _c_double_p]),

@@ -3190,6 +3190,26 @@ int gpso_batch_greedy_host(const gpso_acq* acq, const double* mean, const double
   return gpso::batch_greedy_host(acq_spec(acq), mean, s2, cov, noise, obs_noise, m, q, idx, var, value, n_picked, var_after);
 }
 
+// ---- Monte-Carlo batch acquisition over the path draws (mcbatch.hpp) --------------------------------------
+int gpso_paths_best_batch(gpso_ctx* ctx, const void* xs, int xs_dtype, int xs_mem, int64_t m, const gpso_mcacq* acq, const double* incumbent_s,
+                          const double* pending, int b, int q, int64_t* idx, double* gain, double* batch_value, int* n_picked, double* gain0,
+                          int out_mem) {
+  ENTER();
+  if (!acq) return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch: acq must not be NULL");
+  return ctx->eng->paths_best_batch(xs, xs_dtype, xs_mem, m, acq->kind, acq->xi, acq->incumbent, incumbent_s, pending, b, q, idx, gain,
+                                    batch_value, n_picked, gain0, out_mem);
+}
+
+int gpso_paths_batch_host(const gpso_mcacq* acq, const double* values, int64_t s, int64_t m, int b, const double* incumbent_s, int q,
+                          int64_t* idx, double* gain, double* batch_value, int* n_picked, double* gain0) {
+  if (!acq || !values || !idx || !n_picked || s < 1 || s > gpso::kMcMaxDraws || m < 1 || q < 1 || q > gpso::kMcMaxPicks || b < 0 ||
+      b > gpso::kMcMaxPending || m + b > gpso::kMcMaxCells / s || gpso::mc_refusal(acq->kind, acq->xi, acq->incumbent, incumbent_s, s) != nullptr)
+    return GPSO_E_ARG;
+  std::vector<double> bars((size_t)s, acq->incumbent);
+  if (incumbent_s) std::memcpy(bars.data(), incumbent_s, (size_t)s * 8);
+  return gpso::mc_batch_host(acq->kind, acq->xi, values, m + b, (int)s, m, b, bars.data(), q, idx, gain, batch_value, n_picked, gain0);
+}
+
 int gpso_batch_greedy_mes_host(const double* ystar, int k, int latent, const double* mean, const double* s2, const double* cov,
                                double noise, double obs_noise, int64_t m, int q, int64_t* idx, double* var, double* value,
                                int* n_picked, double* var_after) {

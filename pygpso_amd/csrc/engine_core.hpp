@@ -13,6 +13,7 @@
 #include "devbuf.hpp"
 #include "ehvi.hpp"
 #include "ensemble.hpp"
+#include "mcbatch.hpp"
 #include "resident.hpp"
 #include "screen.hpp"
 
@@ -119,6 +120,10 @@ struct EngineCore {
   // s2, the value column, G, the live flags, the blocks' maxima, the state words and the pick's scaled row
   DevBuf cc_ts, cc_norm, cc_braw, cc_tb, cc_bnorm, cc_vec, cc_lv, cc_out;
   DevBuf bb_ts, bb_norm, bb_mean, bb_s2, bb_val, bb_g, bb_live, bb_bmax, bb_state, bb_tp;
+  // gpso_paths_best_batch (mcbatch.hip): scaled points of a chunk and their norms, the raw pending rows, the S x ld value matrix
+  // (grow-only; gpso_paths_eval's pe_* buffers and the path set are not touched), the live flags, the blocks' maxima, the
+  // state words, host-bound round-0 gains
+  DevBuf mc_ts, mc_norm, mc_praw, mc_vals, mc_live, mc_bmax, mc_state, mc_g0;
   // precision self-test
   bool check = false;
   bool can_selftest() const { return check && res.st_have && res.have_data; }  // (posteriors from outside carry no targets)
@@ -651,6 +656,7 @@ struct EngineCore {
   }
   int cross_cov(const void* xa, int xs_dtype, int xs_mem, int64_t m, const double* xb, int b, double* cov, int out_mem);
   int best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, const AcqSpec& acq, double obs_noise, int q, int64_t* idx, double* mean, double* var, double* value, int* n_picked, double* var_after, int out_mem);
+  int paths_best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, int kind, double xi, double incumbent, const double* incumbent_s, const double* pending, int b, int q, int64_t* idx, double* gain, double* batch_value, int* n_picked, double* gain0, int out_mem);
 
   // ---- the hyper-parameter ensemble (ensemble.hpp, ensemble.hip).  The members' copies -- kEnsembleMax
   // slots each of the hyper block, the scaled rows, the dense double L^-1 and alpha -- belong to the ensemble and to nothing

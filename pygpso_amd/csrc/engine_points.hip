@@ -2,6 +2,7 @@
 // (DESIGN.md sections 7h-7n: predict_grad, the joint predictive, pathwise draws, cross-covariance, batch selection), and the two
 // untyped calls of max-value entropy search.  No typed buffer is touched here: a float fit is refused by need_double_fit.
 #include <climits>
+#include <cstddef>
 #include <vector>
 
 #include "engine_core.hpp"
@@ -510,6 +511,99 @@ int EngineCore::best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, 
     if (mean) mean[t] = host->mean[t];
     if (var) var[t] = host->var[t];
     if (value) value[t] = host->value[t];
+  }
+  return GPSO_OK;
+}
+
+// ---- Monte-Carlo batch acquisition over the path draws (mcbatch.hip).  Stage A is gpso_paths_eval's
+// kernel over the call's own chunk buffers, writing the S x ld value matrix (candidates, then the pending points from column
+// roundup(m, 64) on); then the q rounds back to back, the end rules decided on the device, one wait.  Reads the path set and
+// what gpso_paths_eval reads; writes buffers of its own only
+int EngineCore::paths_best_batch(const void* xs, int xs_dtype, int xs_mem, int64_t m, int kind, double xi, double incumbent,
+                                 const double* incumbent_s, const double* pending, int b, int q, int64_t* idx, double* gain,
+                                 double* batch_value, int* n_picked, double* gain0, int out_mem) {
+  if (int rcd = need_double_fit("gpso_paths_best_batch needs a GPSO_F64 or GPSO_MIXED context -- dtype=\"float64\" or \"mixed\" -- (the dense factor in double)")) return rcd;
+  ctx->tick_timing();
+  if (m < 1) return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch needs at least one leaf (m=%lld)", (long long)m);
+  if (q < 1 || q > kMcMaxPicks) return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch picks 1 to %d leaves (q=%d)", kMcMaxPicks, q);
+  if (b < 0 || b > kMcMaxPending) return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch takes 0 to %d pending points (b=%d)", kMcMaxPending, b);
+  if (b > 0 && !pending) return ctx->fail(GPSO_E_ARG, "pending must not be NULL with b=%d", b);
+  if (!xs) return ctx->fail(GPSO_E_ARG, "xs must not be NULL");
+  if (!idx || !n_picked) return ctx->fail(GPSO_E_ARG, "idx and n_picked must not be NULL");
+  int rc = check_points(xs, xs_dtype, xs_mem, m);
+  if (rc) return rc;
+  if (out_mem != GPSO_MEM_HOST && out_mem != GPSO_MEM_DEVICE) return ctx->fail(GPSO_E_ARG, "bad out_mem %d", out_mem);
+  if (!res.paths_valid)
+    return ctx->fail(GPSO_E_STATE, "no path set resident for this posterior: call gpso_paths_draw (every fit, append, new data, noise vector, install and hand-off ends the set)");
+  if ((rc = refuse_if_async("gpso_paths_best_batch"))) return rc;
+  const int64_t ns = pth.s;
+  if (const char* why = mc_refusal(kind, xi, incumbent, incumbent_s, ns)) return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch: %s", why);
+  if (m + b > kMcMaxCells / ns)
+    return ctx->fail(GPSO_E_ARG, "gpso_paths_best_batch: S * (m + b) above 2^26 (S=%lld, m=%lld, b=%d)", (long long)ns, (long long)m, b);
+  const int64_t mall = (m + 63) / 64 * 64, chunk = std::min<int64_t>(kPathsChunk, mall), ldv = mall + (b > 0 ? 64 : 0);
+  const int64_t nblk = mc_round_blocks(m);
+  if ((rc = ensure(mc_ts, (size_t)chunk * dp * 8))) return rc;
+  if ((rc = ensure(mc_norm, (size_t)chunk * 8))) return rc;
+  if ((rc = ensure(mc_vals, (size_t)ns * ldv * 8))) return rc;
+  if ((rc = ensure(mc_live, (size_t)m))) return rc;
+  if ((rc = ensure(mc_bmax, (size_t)nblk * 16))) return rc;
+  if ((rc = ensure(mc_state, sizeof(McState)))) return rc;
+  if (b > 0 && (rc = ensure(mc_praw, (size_t)kMcMaxPending * d * 8))) return rc;
+  const bool g0_host = gain0 && out_mem == GPSO_MEM_HOST;
+  if (g0_host && (rc = ensure(mc_g0, (size_t)m * 8))) return rc;
+  constexpr size_t kRecordBytes = offsetof(McState, bar);
+  McState* host = reinterpret_cast<McState*>(ctx->pinned_scratch(sizeof(McState) / 8 + 1));
+  if (!host) return ctx->fail(GPSO_E_OOM, "pinned host scratch");
+  std::vector<double> bars((size_t)ns, incumbent);
+  if (incumbent_s) std::memcpy(bars.data(), incumbent_s, (size_t)ns * 8);
+  hipStream_t s;
+  if ((rc = points_begin(&s))) return rc;
+  const void* dev = nullptr;
+  if ((rc = stage_leaves(xs, xs_dtype, xs_mem, m, &dev))) return rc;
+  McState* state = static_cast<McState*>(mc_state.p);
+  HIPCHECK(hipMemsetAsync(state, 0, sizeof(McState), s));
+  HIPCHECK(hipMemcpyAsync(state->bar, bars.data(), (size_t)ns * 8, hipMemcpyHostToDevice, s));
+  HIPCHECK(hipMemsetAsync(mc_live.p, 1, (size_t)m, s));
+  double* V = as<double>(mc_vals);
+  PathsEvalLaunch g;
+  g.ts = as<double>(mc_ts); g.xs = as<double>(xs64); g.omega = as<double>(pth.omega); g.phase = as<double>(pth.phase);
+  g.W = as<double>(pth.w); g.VT = as<double>(pth.vt);
+  g.n = n; g.npad = npad; g.s = ns; g.f = pth.f; g.ldw = pth.ldw; g.dp = dp; g.kp = kp; g.ldo = ldv;
+  for (int64_t off = 0; off < m; off += chunk) {
+    const int64_t mc = std::min(chunk, m - off), mpad = (mc + 63) / 64 * 64;
+    prep_points<double>(s, dev, xs_dtype, off, mc, mpad, nullptr, as<double>(mc_ts), as<double>(mc_norm));
+    g.m = mc;
+    g.out = V + off;  // (columns off .. off + mpad: below mall, so inside the row)
+    if (launch_paths_eval(s, g) != 0) return launch_status();
+    if ((rc = launch_status())) return rc;
+  }
+  if (b > 0) {  // the pending points: b more columns by the same kernel, from column mall on
+    HIPCHECK(hipMemcpyAsync(mc_praw.p, pending, (size_t)b * d * 8, hipMemcpyHostToDevice, s));
+    prep_points<double>(s, mc_praw.p, GPSO_F64, 0, b, 64, nullptr, as<double>(mc_ts), as<double>(mc_norm));
+    g.m = b;
+    g.out = V + mall;
+    if (launch_paths_eval(s, g) != 0) return launch_status();
+  }
+  if (ctx->timing) HIPCHECK(hipEventRecord(ctx->ev[0], s));  // (stage A ends here: gpso_last_ms(ctx, 0) is the rounds alone)
+  McLaunch r;
+  r.st = state; r.V = V; r.ld = ldv; r.m = m; r.pcol = mall; r.s = (int)ns; r.b = b; r.kind = kind; r.xi = xi;
+  r.live = static_cast<unsigned char*>(mc_live.p);
+  r.bmax_v = as<double>(mc_bmax);
+  r.bmax_i = reinterpret_cast<int64_t*>(r.bmax_v + nblk);
+  if (launch_mc_init(s, r) != 0) return launch_status();
+  double* g0_dev = !gain0 ? nullptr : g0_host ? as<double>(mc_g0) : gain0;
+  for (int t = 0; t < q; ++t) launch_mc_round(s, r, t, g0_dev);
+  if ((rc = launch_status())) return rc;
+  HIPCHECK(hipMemcpyAsync(host, state, kRecordBytes, hipMemcpyDeviceToHost, s));
+  if (g0_host) HIPCHECK(hipMemcpyAsync(gain0, g0_dev, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+  if ((rc = points_end(s, m))) return rc;
+  float rounds_ms = 0;
+  if (ctx->timing && hipEventElapsedTime(&rounds_ms, ctx->ev[0], ctx->ev[3]) == hipSuccess) ctx->last_ms[0] = rounds_ms;
+  *n_picked = host->n_picked;
+  for (int t = 0; t < host->n_picked; ++t) {
+    idx[t] = host->idx[t];
+    if (gain) gain[t] = host->gain[t];
+    if (batch_value) batch_value[t] = host->value[t];
   }
   return GPSO_OK;
 }

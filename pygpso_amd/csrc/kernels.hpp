@@ -635,6 +635,34 @@ void launch_batch_init(hipStream_t st, const double* value, int64_t m, unsigned 
 void launch_batch_finish(hipStream_t st, BatchState* state, int t, const double* bmax_v, const int64_t* bmax_i, int64_t nblocks,
                          const double* ts, int dp, const double* mean, const double* s2, const double* G, int64_t m, unsigned char* live,
                          double* tp);
+// ---- mcbatch.hip: Monte-Carlo batch acquisition over the path draws (mcbatch.hpp) --------------------------
+// the device words of one gpso_paths_best_batch call (zeroed when it starts, then bar := the initial bars); the host reads
+// back the part in front of bar
+struct McState {
+  int stop;      // != 0: the batch has ended; the launches still queued do nothing
+  int n_picked;
+  int64_t idx[64];
+  double gain[64], value[64];
+  double bar[256];   // QEI: the draws' current bars; QPI: their original ones
+  double thr[256];   // QPI: bar + xi
+  int cleared[256];  // a pick or a pending point has cleared the draw's bar by more than xi
+};
+struct McLaunch {
+  McState* st = nullptr;
+  const double* V = nullptr;  // [s][ld] draw-major values: candidates in columns 0 .. m - 1, pending points in pcol .. pcol + b - 1
+  int64_t ld = 0, m = 0, pcol = 0;
+  int s = 0, b = 0, kind = 0;
+  double xi = 0.0;
+  unsigned char* live = nullptr;  // [m], 1 on entry
+  double* bmax_v = nullptr;       // [mc_round_blocks(m)]
+  int64_t* bmax_i = nullptr;
+};
+int64_t mc_round_blocks(int64_t m);
+// the pending columns folded into st->bar / st->cleared, st->thr set
+int launch_mc_init(hipStream_t st, const McLaunch& g);
+// round t: every live row's gain (round 0 also into gain0 [m], nullable), the blocks' first maxima, then the one-workgroup fold
+// that makes the pick, writes its record, retires the row and applies it to the bars or flags
+void launch_mc_round(hipStream_t st, const McLaunch& g, int t, double* gain0);
 // ---- sgpr.hip: sparse GP regression on inducing points (rectangular [M_pad x N_pad] float64 buffers, zero padding) -------
 // C (m x n, leading dimension ldc) = alpha opA opB + beta C with opA(i, k) = A[i * sai + k * sak], opB(k, j) = B[k * sbk +
 // j * sbj] (fit.hip: the LDS-DMA tile GEMM behind launch_dgemm; m, n multiples of 64, each operand unit-stride in one index).

@@ -831,6 +831,75 @@ class HipGPEngine:
                                               L.dptr(best_val)))
         return values, best_idx, best_val
 
+    # -- Monte-Carlo batch acquisition over the path draws (csrc/mcbatch.hip, csrc/mcbatch.hpp) ------------------------
+    @staticmethod
+    def _mc_rec(kind, xi, incumbent, incumbent_s):
+        if kind not in L.MC_KINDS:
+            raise ValueError(f"kind={kind!r}: one of {sorted(L.MC_KINDS)}")
+        if incumbent_s is None and incumbent is None:
+            raise ValueError("one of incumbent and incumbent_s is needed")
+        bars = None if incumbent_s is None else L.as_f64(np.asarray(incumbent_s, dtype=np.float64).reshape(-1))
+        return L.GpsoMcAcq(L.MC_KINDS[kind], float(xi), 0.0 if incumbent is None else float(incumbent)), bars
+
+    def paths_best_batch(self, xs, q, kind="qei", incumbent=None, incumbent_s=None, pending=None, xi=0.0, want_gain0=False):
+        """``q`` rows of ``xs`` picked greedily by the sample-average batch acquisition over the resident path set
+        (``gpso_paths_best_batch``): ``kind`` "qei" (or "qnei", the same arithmetic -- pass the per-draw bars) or "qpi".
+        The bars: ``incumbent_s`` [S], or the scalar ``incumbent`` for every draw.  ``pending`` [B, D], B <= 64: points
+        still being evaluated, folded into the bars and never returned.  Returns (idx, gain, batch_value) of the picks
+        made -- at most ``q`` -- and with ``want_gain0`` every row's round-0 gain [M] as a fourth entry.  The values
+        never leave the device."""
+        ptr, dt, mem, m, keep = self._leaf_args(xs)
+        rec, bars = self._mc_rec(kind, xi, incumbent, incumbent_s)
+        s, _ = self.paths_info()
+        if bars is not None and s and bars.shape != (s,):
+            raise ValueError(f"incumbent_s must be [S] with S={s}, got {bars.shape}")
+        if pending is None:
+            pend, b = None, 0
+        else:
+            pend = L.as_f64(np.atleast_2d(np.asarray(pending, dtype=np.float64)))
+            if pend.ndim != 2 or pend.shape[1] != self.d:
+                raise ValueError(f"pending must be [B, D] with D={self.d}, got {pend.shape}")
+            b = int(pend.shape[0])
+        q = int(q)
+        cap = max(q, 1)
+        idx = np.full(cap, -1, dtype=np.int64)
+        gain, value = (np.full(cap, np.nan, dtype=np.float64) for _ in range(2))
+        n_picked = C.c_int(0)
+        gain0 = np.empty(m, dtype=np.float64) if want_gain0 else None
+        self._check(self._lib.gpso_paths_best_batch(self._h, ptr, dt, mem, m, C.byref(rec), None if bars is None else L.dptr(bars),
+                                                    None if b == 0 else L.dptr(pend), b, q, L.i64ptr(idx), L.dptr(gain), L.dptr(value),
+                                                    C.byref(n_picked), None if gain0 is None else C.c_void_p(gain0.ctypes.data),
+                                                    L.MEM_HOST))
+        k = int(n_picked.value)
+        res = (idx[:k].copy(), gain[:k].copy(), value[:k].copy())
+        return res + (gain0,) if want_gain0 else res
+
+    @staticmethod
+    def paths_batch_host(values, q, kind="qei", incumbent=None, incumbent_s=None, n_pending=0, xi=0.0):
+        """The rounds of ``paths_best_batch`` on the CPU from given ``values`` [S, M + B] -- the M candidates, then the
+        ``n_pending`` = B pending columns -- (``gpso_paths_batch_host``: no context, no GPU) -> (idx, gain, batch_value,
+        gain0)."""
+        values = L.as_f64(np.asarray(values, dtype=np.float64))
+        if values.ndim != 2:
+            raise ValueError(f"values must be [S, M + B], got {values.shape}")
+        s, b = int(values.shape[0]), int(n_pending)
+        m = int(values.shape[1]) - b
+        rec, bars = HipGPEngine._mc_rec(kind, xi, incumbent, incumbent_s)
+        if bars is not None and bars.shape != (s,):
+            raise ValueError(f"incumbent_s must be [S] with S={s}, got {bars.shape}")
+        q = int(q)
+        cap = max(q, 1)
+        idx = np.full(cap, -1, dtype=np.int64)
+        gain, value = (np.full(cap, np.nan, dtype=np.float64) for _ in range(2))
+        gain0 = np.empty(max(m, 1), dtype=np.float64)
+        n_picked = C.c_int(0)
+        rc = L.load().gpso_paths_batch_host(C.byref(rec), L.dptr(values), s, m, b, None if bars is None else L.dptr(bars), q,
+                                            L.i64ptr(idx), L.dptr(gain), L.dptr(value), C.byref(n_picked), L.dptr(gain0))
+        if rc != L.OK:
+            raise L.GpsoHipError(rc, "gpso_paths_batch_host: bad record, bars or arguments")
+        k = int(n_picked.value)
+        return idx[:k].copy(), gain[:k].copy(), value[:k].copy(), gain0[:max(m, 0)]
+
     def best_ucb(self, xs, varsigma, seg_off=None):
         """gp_eval_best_ucb per segment -> (idx, mean, var, ucb) arrays of length nseg."""
         ptr, dt, mem, m, keep = self._leaf_args(xs)

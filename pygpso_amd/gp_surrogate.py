@@ -731,6 +731,34 @@ class GPSurrogate:
         return model.best_batch(np.ascontiguousarray(normed_coords, dtype=np.float64), acq, q, incumbent=incumbent,
                                 want_var_after=return_var_after)
 
+    def select_batch_mc(self, normed_coords, q, kind="qnei", n_paths=64, n_features=1024, rng=None, incumbent=None, pending=None,
+                        xi=0.0, return_gain0=False):
+        """``q`` different rows of ``normed_coords`` for a pool of workers by the Monte-Carlo batch acquisition over
+        posterior draws (one ``gpso_paths_best_batch`` call): the sample-average qNoisyEI (``kind="qnei"``), qEI
+        (``"qei"``) or qPI (``"qpi"``) over the drawn paths, picked by sequential greedy selection over those fixed
+        draws.  Unlike ``select_batch`` a pick moves the means: a draw in which the pick is high raises that draw's bar.
+        A path set is drawn (``n_paths``, ``n_features``, ``rng`` as ``gp_sample_paths``) unless a valid one is
+        resident.  The bars: for "qnei" each draw's own maximum over the evaluated points (one ``eval_paths`` call, the
+        values stay on the device) -- no observed score enters --; for "qei" / "qpi" ``incumbent``, by default the best
+        evaluated score.  ``pending`` [B, D]: points still being evaluated; they raise the bars and are never returned.
+        Returns (indices, gain, batch_value) of the picks -- fewer than ``q`` when no draw can improve any more --, in
+        the paths' latent units; with ``return_gain0`` a fourth entry holds every row's round-0 gain, at ``q = 1`` the
+        plain sample-average EI / PI of each row.  Stores nothing; a multi-GPU engine group raises NotImplementedError."""
+        if kind not in ("qnei", "qei", "qpi"):
+            raise ValueError(f"kind={kind!r}: 'qnei', 'qei' or 'qpi'")
+        model = self._joint_model("select_batch_mc")
+        coords = np.ascontiguousarray(normed_coords, dtype=np.float64)
+        if model._predicting(lambda: model.engine.paths_info())[0] == 0:
+            model.sample_paths(n_paths, n_features=n_features, rng=rng)
+        bars = None
+        if kind == "qnei":
+            x_train, _ = self.current_training_data
+            bars = np.asarray(model.eval_paths(np.ascontiguousarray(x_train, dtype=np.float64), want_values=False)[2])[:, 0]
+        elif incumbent is None:
+            incumbent = float(np.max(self.current_training_data[1]))
+        return model.mc_batch(coords, q, kind, incumbent=incumbent if bars is None else None, incumbent_s=bars, pending=pending, xi=xi,
+                              want_gain0=return_gain0)
+
     def gp_eval_best_ucb_grow(self, leaf_bounds, depth):
         """MI355X path of ``gp_eval_best_ucb(leaf.grow(depth))`` for several leaves at once: the
         ternary sub-tree centres are generated on the device (bit-identical to ``LeafNode.grow``)
@@ -1422,6 +1450,10 @@ class GPRSurrogate(GPSurrogate):
     def select_batch(self, *args, **kwargs):
         self._refuse_unserved("select_batch")
         return super().select_batch(*args, **kwargs)
+
+    def select_batch_mc(self, *args, **kwargs):
+        self._refuse_unserved("select_batch_mc")
+        return super().select_batch_mc(*args, **kwargs)
 
     def gp_predict(self, normed_coords):
         """``hyper="marginal"``: the moments of the ensemble's mixture at ``normed_coords`` and the integrated value of the

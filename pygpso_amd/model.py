@@ -520,6 +520,20 @@ class HipGPR:
         Xnew = np.asarray(Xnew)
         return self._predicting(lambda: self.engine.paths_eval(Xnew, seg_off, want_values=want_values))
 
+    def mc_batch(self, Xnew, q, kind, incumbent=None, incumbent_s=None, pending=None, xi=0.0, want_gain0=False):
+        """``q`` rows of Xnew picked greedily by the sample-average qEI / qNoisyEI / qPI over the path set of
+        ``sample_paths`` (``kind``: "qei", "qnei", "qpi"; ``gpso_paths_best_batch``): (idx, gain, batch_value) of the
+        picks made, plus every row's round-0 gain [M] with ``want_gain0``.  The bars are ``incumbent_s`` [S] per draw or
+        the scalar ``incumbent`` (None: the largest training target); ``pending`` [B, D] are points still being
+        evaluated.  In the paths' latent units.  A posterior that changed since ``sample_paths`` raises: draw again."""
+        if not hasattr(self.engine, "paths_best_batch"):
+            raise NotImplementedError(f"mc_batch is not available on {type(self.engine).__name__}")
+        if incumbent is None and incumbent_s is None:
+            incumbent = float(np.max(self._data[1]))
+        Xnew = np.asarray(Xnew)
+        return self._predicting(lambda: self.engine.paths_best_batch(Xnew, q, kind, incumbent=incumbent, incumbent_s=incumbent_s,
+                                                                     pending=pending, xi=xi, want_gain0=want_gain0))
+
     def predictive_noise(self):
         """The likelihood's variance in ``predict_y`` (the families with another likelihood override this)."""
         return self.likelihood.variance
