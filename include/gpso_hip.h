@@ -157,6 +157,19 @@ typedef struct gpso_ctx gpso_ctx;
                                    /* the general sequence, which the call then runs.  After one refusal the posterior is not screened  */
                                    /* again until it changes.  0: today's launches exactly.  2: any batch size (tests).  Per context.   */
                                    /* Same record bits whatever the value; gpso_last_count(ctx, 7) and (ctx, 8) say what happened.      */
+#define GPSO_OPT_SURVIVOR_TILE 16  /* the tile of the split predict kernels' default family (fp16 split, fp16 contraction, fused step,  */
+                                   /* float generation).  WIDE: a workgroup of 8 waves owns 256 leaves, two column tiles of 16 per      */
+                                   /* wave -- the batch kernel.  NARROW: a workgroup of 4 waves owns 64 leaves, one column tile per     */
+                                   /* wave, one wave per SIMD: the few hundred survivors of a screened call (GPSO_OPT_SCREEN) spread    */
+                                   /* over four times as many compute units, and a wave's k-step is half as long.  0 (default): the     */
+                                   /* survivors' launch of a screened call takes the narrow tile up to the survivor count a makespan    */
+                                   /* model gives it (gpso_survivor_narrow_max_host) and the wide one above -- chosen on the device:    */
+                                   /* both launches are enqueued and one leaves at once --, every other launch is wide.  1: wide        */
+                                   /* everywhere.  2:                                                                                   */
+                                   /* narrow wherever the default family runs on float leaves, gpso_predict included (tests: every      */
+                                   /* leaf's bits, not only a winner's).  Per context.  Same bits whatever the value: a leaf's          */
+                                   /* arithmetic depends neither on its lane nor on its wave nor on its workgroup.                      */
+                                   /* gpso_last_count(ctx, 9) says which tile the last launch used.                                     */
 /* floating-point options (gpso_set_option_f64): tolerances of the self-test */
 #define GPSO_OPTF_TOL_VAR 100  /* max |d var| at the training inputs, relative to the kernel variance (default 1e-4; GPSO_F32: 1e-3) */
 #define GPSO_OPTF_TOL_MEAN 101 /* max |d mean| at the training inputs, relative to max |y - c|   (default 1e-4; GPSO_F32: 1e-3) */
@@ -727,6 +740,11 @@ int gpso_screen_accepts_host(double u_star, double threshold, int64_t count, int
  * in exactly one part, every range but the last non-empty one a multiple of 64 long; and how many parts a batch is given. */
 int gpso_screen_partition_host(int64_t m, int parts, int w, int64_t* lo, int64_t* hi);
 int gpso_screen_parts_host(int64_t m);
+/* GPSO_OPT_SURVIVOR_TILE = 0: up to how many survivors the survivors' launch of a screened call takes the narrow tile (a multiple of
+ * 64, at most room; 0: none) -- the makespan model of csrc/screen.hpp for a posterior of row_blocks = N_pad / 256 row blocks of
+ * L^-1 on a device of `cus` compute units, in a launch with room for `room` rows.  Above it the wide tile runs.  Negative
+ * (GPSO_E_ARG) on bad arguments.  No context, no GPU. */
+int64_t gpso_survivor_narrow_max_host(int row_blocks, int cus, int64_t room);
 
 /* ---- acquisition functions (no counterpart in the reference: it ranks by mean + varsigma * VAR only) ----------------
  *
@@ -1330,6 +1348,8 @@ double gpso_last_ms(gpso_ctx* ctx, int what);
  * what = 7, 8: the last gpso_best_ucb / gpso_best_ucb_end call under GPSO_OPT_SCREEN: how many leaves survived the screen (7; 0
  * where the call was not screened), and 8: 0 not screened, 1 screened and accepted, 2 screened, refused and run again by the
  * general sequence.
+ * what = 9: leaves per workgroup of the last launch of a split predict kernel this context made: 256 (the wide tile) or 64 (the
+ * narrow one, GPSO_OPT_SURVIVOR_TILE) -- after a screened call the survivors' launch, unlike 3, 5 and 6.  For tests and tools.
  * what = 4: bytes of device memory the buffers of ALL contexts of this process hold now (process-wide, whichever ctx asks;
  * back where it stood once a context is destroyed; for tests and tools). */
 #define GPSO_FITMATH_NONE 0

@@ -42,6 +42,7 @@ OPT_FIT_OVERLAP = 12
 OPT_ROW_LOOP = 13
 OPT_PARK_BYTES = 14
 OPT_SCREEN = 15
+OPT_SURVIVOR_TILE = 16
 SCREEN_NONE, SCREEN_ACCEPTED, SCREEN_REFUSED = 0, 1, 2  # gpso_last_count(ctx, 8)
 CONTRACTION_AUTO, CONTRACTION_F32, CONTRACTION_F16 = 0, 1, 2
 SPLIT_KERNEL_AUTO, SPLIT_KERNEL_TWO_PHASE, SPLIT_KERNEL_FUSED16, SPLIT_KERNEL_FUSED32 = 0, 1, 2, 3
@@ -264,6 +265,7 @@ SIGNATURES = {
     "gpso_screen_accepts_host": (C.c_int, [C.c_double, C.c_double, C.c_int64, C.c_int64]),
     "gpso_screen_list": (C.c_int, [C.c_void_p, C.c_int64, _c_int64_p, C.POINTER(C.c_float), _c_int64_p]),
     "gpso_screen_partition_host": (C.c_int, [C.c_int64, C.c_int, C.c_int, _c_int64_p, _c_int64_p]),
+    "gpso_survivor_narrow_max_host": (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
     "gpso_screen_parts_host": (C.c_int, [C.c_int64]),
     "gpso_grow_rows": (C.c_int64, [C.c_int]),
     "gpso_grow": (C.c_int, [C.c_void_p, _c_double_p, C.c_int, C.c_int, C.c_int, _c_double_p]),

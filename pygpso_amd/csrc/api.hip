@@ -170,6 +170,11 @@ struct EngineT : EngineCore {
         if (value < 0 || value > 2) return ctx->fail(GPSO_E_ARG, "screen: 0 (off), 1 (large calls) or 2 (every call it applies to)");
         screen_mode = value;
         return GPSO_OK;
+      case GPSO_OPT_SURVIVOR_TILE:
+        if (value < 0 || value > 2)
+          return ctx->fail(GPSO_E_ARG, "survivor tile: 0 (narrow for a screened call's survivors), 1 (wide everywhere) or 2 (narrow wherever the default kernels run)");
+        survivor_tile = value;
+        return GPSO_OK;
       case GPSO_OPT_FIT_OVERLAP:
         if (value < 0) return ctx->fail(GPSO_E_ARG, "fit overlap must be >= 0");
         fit_overlap = value;
@@ -828,9 +833,28 @@ struct EngineT : EngineCore {
           a.part_var = as<double>(pvar); a.part_mean = as<double>(pmean);
           a.npad = npad; a.dp4 = dp / 4; a.mpad = mp; a.n_rows = n;
           a.step32 = split_variant == GPSO_SPLIT_KERNEL_FUSED32; a.row_loop = row_loop; a.cu_count = ctx->cu_count;
-          a.splits_out = &ctx->last_count[3];
+          // GPSO_OPT_SURVIVOR_TILE = 2: the narrow tile for float leaves whatever the call (the launcher keeps the wide kernel
+          // outside the default family)
+          if (survivor_tile == 2 && xs_dtype == GPSO_F32) a.tile = LeafTile::Narrow;
+          a.splits_out = &ctx->last_count[3]; a.tile_out = &ctx->last_count[9];
           a.park_bytes = park_bytes; a.park_scratch = &EngineT::park_cb; a.park_owner = this; a.park_out = &ctx->last_count[5];
-          rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+          if (span.open && m_live_c != nullptr && span.narrow_max > 0) {
+            // A screened call's survivors (m_live_c: the screen's control block).  A few hundred leaves are a chain on a handful
+            // of CUs under the wide tile and spread over four times as many under the narrow one; near the room's edge the wide
+            // tile is the faster one.  Only the device knows the count: where both can happen both launches are enqueued, each
+            // behind the live-row word the compaction left for ITS tile -- the other one's is zero, and it leaves at once.
+            const bool both = span.narrow_max < mp;
+            a.tile = LeafTile::Narrow;
+            if (both) a.m_live = m_live_c + kScreenCtlNarrow;
+            rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+            if (rc == 0 && both) {
+              a.tile = LeafTile::Wide;
+              a.m_live = m_live_c + kScreenCtlWide;
+              rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+            }
+          } else {
+            rc = launch_leaf_tiles_bf16<TG>(s, kp, a, split_variant);
+          }
           if (span.open) ctx->last_count[3] = keep_counts[0], ctx->last_count[5] = keep_counts[1], ctx->last_count[6] = keep_counts[2];
         }
       } else {
@@ -1176,7 +1200,14 @@ struct EngineT : EngineCore {
     return std::min<int64_t>(mpad, (int64_t)std::max(1, ctx->cu_count / nbi) * kLeafPad);
   }
   // the mean pass and the screen of a batch of float leaves on the device; probe: also every leaf's ub and flag -> screen_cols
-  int enqueue_screen(const void* dev, int64_t m, const AcqSpec& acq, bool probe) {
+  // GPSO_OPT_SURVIVOR_TILE for a survivors' launch with room for cap rows: 1 -- no count takes the narrow tile, 2 -- every count,
+  // 0 -- the counts the makespan model gives it (screen.hpp)
+  int64_t survivor_narrow_rows(int64_t cap) const {
+    if (survivor_tile == 1) return 0;
+    if (survivor_tile == 2) return cap;
+    return survivor_narrow_max((int)(npad / 256), ctx->cu_count, cap);
+  }
+  int enqueue_screen(const void* dev, int64_t m, const AcqSpec& acq, bool probe, int64_t narrow_max = 0) {
     if constexpr (kFloatPredict) {
       int rc;
       if ((rc = ensure_generation_inputs())) return rc;
@@ -1205,7 +1236,7 @@ struct EngineT : EngineCore {
       if ((rc = launch_leaf_mean(s, kp, a))) return launch_status();
       b.m = m;
       b.variance = kp.variance; b.noise = kp.noise; b.varsigma = acq.varsigma;
-      b.raw = static_cast<const float*>(dev); b.d = d; b.cap = cap; b.counts = as<int64_t>(screen_cnt);
+      b.raw = static_cast<const float*>(dev); b.d = d; b.cap = cap; b.narrow_max = narrow_max; b.counts = as<int64_t>(screen_cnt);
       b.my = as<double>(screen_my); b.block_max = as<double>(screen_bmax); b.key = as<int64_t>(grow_key);
       b.rows_out = as<float>(screen_rows); b.ctl = as<int64_t>(screen_ctl); b.probe = probe ? as<double>(screen_cols) : nullptr;
       launch_screen(s, b);
@@ -1260,9 +1291,10 @@ struct EngineT : EngineCore {
     if ((rc = ensure_tile_events(1))) return rc;
     if (plan.timed) HIPCHECK(hipEventRecord(ctx->tile_ev[0], s));
     ctx->last_count[5] = ctx->last_count[6] = 0;  // (the mean pass parks nothing)
-    if ((rc = enqueue_screen(dev, m, acq, false))) return rc;
+    const int64_t narrow_max = survivor_narrow_rows(cap);
+    if ((rc = enqueue_screen(dev, m, acq, false, narrow_max))) return rc;
     LeafFinalize fin{};
-    TileSpan span{plan.timed, true};
+    TileSpan span{plan.timed, true, 0, narrow_max};
     if ((rc = score_device_leaves(screen_rows.p, GPSO_F32, cap, acq, true, as<double>(omean), as<double>(ovar), as<double>(oucb),
                                   span, as<int64_t>(screen_ctl), &fin)))
       return rc;
@@ -1277,7 +1309,7 @@ struct EngineT : EngineCore {
     launch_keyed_argmax(s, as<double>(omean), as<double>(ovar), as<double>(oucb), as<int64_t>(grow_key), m, 0, 1,
                         as<int64_t>(screen_ctl), argmax_blocks(cap, 1), best.p, as<int64_t>(best_pos), as<double>(ovals), &fin,
                         host, arm_token(call, true, 1), as<int64_t>(screen_ctl), cap);
-    call.screened(dev, GPSO_F32, m, acq);  // (what a re-run takes: the caller keeps device leaves untouched until the record is read)
+    call.screened(dev, GPSO_F32, m, acq, narrow_max);  // (what a re-run takes: the caller keeps device leaves untouched until the record is read)
     ctx->last_count[0] = ctx->last_count[1] = m;
     return launch_status();
   }
@@ -1585,7 +1617,7 @@ struct EngineT : EngineCore {
     if (call.kind == BestKind::OneLaunch && vals[4 * nseg + 1] != 0.0) return 1;
     if (call.kind == BestKind::Screened) {
       ctx->last_count[0] = ctx->last_count[1] = call.screen.m;  // (a ticket: other calls have run since it was enqueued)
-      if ((rc = screen_verdict(vals))) return rc;
+      if ((rc = screen_verdict(call, vals))) return rc;
     }
     if (call.mode == 2) {
       const int verdict = (int)vals[4 * nseg + 1];
@@ -1614,8 +1646,9 @@ struct EngineT : EngineCore {
   }
   // a screened call's record (one segment): the survivors' count and the last kernel's verdict -> the counters; a refusal ends
   // screening on this posterior and returns 1 -- the caller runs the call again, which then takes the general sequence
-  int screen_verdict(const double* vals) {
+  int screen_verdict(const BestCall& call, const double* vals) {
     std::memcpy(&ctx->last_count[7], &vals[4], 8);
+    ctx->last_count[9] = ctx->last_count[7] <= call.narrow_max ? 64 : 256;  // (the tile this count's survivors' launch ran)
     const bool refused = vals[5] != 0.0;
     ctx->last_count[8] = refused ? kScreenRefused : kScreenAccepted;
     if (refused) res.screen_was_refused();
@@ -3301,6 +3334,11 @@ int gpso_screen_partition_host(int64_t m, int parts, int w, int64_t* lo, int64_t
 
 int gpso_screen_parts_host(int64_t m) { return gpso::screen_parts_host((long long)m); }
 
+int64_t gpso_survivor_narrow_max_host(int row_blocks, int cus, int64_t room) {
+  if (row_blocks < 1 || cus < 1 || room < 0) return GPSO_E_ARG;
+  return gpso::survivor_narrow_max(row_blocks, cus, room);
+}
+
 int gpso_acq_eval_host(const gpso_acq* acq, const double* mean, const double* var, double noise, int64_t n, double* out) {
   if (acq_refusal(acq) != nullptr || n < 0 || (n > 0 && (!mean || !var || !out)) || noise != noise) return GPSO_E_ARG;
   gpso::acq_eval_host(acq_spec(acq), mean, var, noise, (long long)n, out);
@@ -3499,7 +3537,7 @@ int gpso_comm_abort(gpso_ctx* ctx) {
 }
 
 int64_t gpso_last_count(gpso_ctx* ctx, int what) {
-  if (!ctx || what < 0 || what > 8) return -1;
+  if (!ctx || what < 0 || what > 9) return -1;
   return what == 4 ? g_dev_bytes_held.load(std::memory_order_relaxed) : ctx->last_count[what];
 }
 

@@ -45,6 +45,7 @@ struct BestCall {
     int64_t m = 0;
     AcqSpec acq;
   } screen;
+  int64_t narrow_max = 0;  // ... and up to how many survivors its survivors' launch took the narrow tile (gpso_last_count 9)
 
   bool none() const { return kind == BestKind::None; }
   // ==== transitions ====
@@ -70,9 +71,10 @@ struct BestCall {
   // the last launch of enqueue_best_leaves / _grow (General, Small), try_one_launch_t (OneLaunch)
   void enqueued(BestKind k, int nseg_, int mode_) { kind = k; nseg = nseg_; mode = mode_; }
   // enqueue_best_screened
-  void screened(const void* xs, int xs_dtype, int64_t m, const AcqSpec& acq) {
+  void screened(const void* xs, int xs_dtype, int64_t m, const AcqSpec& acq, int64_t narrow_max_) {
     enqueued(BestKind::Screened, 1, 0);
     screen = Rerun{xs, xs_dtype, m, acq};
+    narrow_max = narrow_max_;
   }
   // enqueue_fold (gpso_best_ucb(_grow)_sharded behind the all-gather, gpso_fold_winners): the tile pairs of the half stay
   void folded(int nseg_, bool collective_recorded) {

@@ -29,6 +29,10 @@ constexpr int64_t kLeafChunk = (int64_t)1 << 20;  // leaves processed per pass o
 #ifndef GPSO_SCREEN_DEFAULT
 #define GPSO_SCREEN_DEFAULT 1
 #endif
+// GPSO_OPT_SURVIVOR_TILE as a context is created (-DGPSO_SURVIVOR_TILE_DEFAULT=1 builds the wide arm of an A/B through bench.py)
+#ifndef GPSO_SURVIVOR_TILE_DEFAULT
+#define GPSO_SURVIVOR_TILE_DEFAULT 0
+#endif
 #ifndef GPSO_PARK_BYTES_DEFAULT
 #define GPSO_PARK_BYTES_DEFAULT (256 << 20)
 #endif
@@ -76,7 +80,7 @@ struct gpso_ctx {
   int rank = 0, world = 1;
   // leaves scored / leaves asked for by the last predict-type call; [2] GPSO_FITMATH_* of the last fit; [3] workgroups per
   // leaf tile of this context's last split-kernel launch
-  int64_t last_count[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
+  int64_t last_count[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // ([4] is not stored: gpso_last_count)
   int cu_count = 256;  // compute units of `device` (gpso_create): sizes the split predict kernels' and the bf16 GEMMs' grids
   std::string err;
   gpso::host::EngineCore* eng = nullptr;

@@ -99,6 +99,9 @@ struct EngineCore {
   std::vector<float> probe_rows;
   bool probe_listed = false;
   int screen_mode = GPSO_SCREEN_DEFAULT;  // GPSO_OPT_SCREEN
+  // GPSO_OPT_SURVIVOR_TILE: 0 the narrow tile for the survivors' launch of a screened call, 1 wide everywhere, 2 narrow wherever
+  // the default family runs on float device leaves (tests)
+  int survivor_tile = GPSO_SURVIVOR_TILE_DEFAULT;
   DevBuf batch_theta;  // theta records of a batched evaluation (fit_eval_batch)
   DevBuf loov, loo_scal;  // leave-one-out: the per-point vectors (kernels.hpp: kLoo*) and [0] loss, [8 ..] gradient
   DevBuf pg_ts, pg_norm, pg_work, pg_out;  // gpso_predict_grad: scaled test points of a chunk, the workspace, host-bound results
@@ -507,7 +510,8 @@ struct EngineCore {
 
   // are the tile kernel's event pairs recorded, and how many were (collect_tile_ms).  open: the survivors of a screened call -- the
   // pair's first event stands in front of the mean pass already, and the split launch's counters keep describing that pass
-  struct TileSpan { bool timed; bool open = false; int pairs = 0; };
+  // narrow_max (open): survivor counts up to this take the narrow tile (screen.hpp: survivor_narrow_max; what the compaction was told)
+  struct TileSpan { bool timed; bool open = false; int pairs = 0; int64_t narrow_max = 0; };
   // after the stream has been synchronised: total leaf-tile kernel time of the call
   void collect_tile_ms(bool timed, int pairs) {
     if (!timed) return;

@@ -50,9 +50,11 @@ void launch_pack_linv_bf16(hipStream_t st, int nsplit, const TF* linv, int64_t n
 // of a wave are fp16 piece pairs of 32-dimension chunks instead of float groups of four dimensions
 bool leaf_step32_built();  // predict_split_f32.hip: was the library built with -DGPSO_STEP32=1 (leaf_split.hpp)
 inline int leaf_c16_chunks(int dp4) { return (dp4 + 8) / 8; }  // D_pad inputs + the norm slot, 32 slots per chunk
-inline size_t leaf_bf16_lds_bytes(int nsplit, int dp4, int tg_bytes, bool c16 = false) {
+// nw, ct: waves per workgroup and column tiles per wave (8 x 2; the narrow kernel: 4 x 1) -- a wave's leaf fragments are ct
+// halves of a k-step's X fragments
+inline size_t leaf_bf16_lds_bytes(int nsplit, int dp4, int tg_bytes, bool c16 = false, int nw = 8, int ct = 2) {
   const size_t xfrag = c16 ? (size_t)leaf_c16_chunks(dp4) * 4096 : (size_t)2 * dp4 * 64 * tg_bytes;
-  return (size_t)2 * nsplit * 16 * 64 * 16 + (size_t)3 * (xfrag + 64 * tg_bytes + 256) + (size_t)8 * xfrag;
+  return (size_t)2 * nsplit * 16 * 64 * 16 + (size_t)3 * (xfrag + 64 * tg_bytes + 256) + (size_t)nw * (xfrag / 2 * ct);
 }
 // fp16 piece pairs of the float scaled inputs in the fragment order of the fp16 contraction (predict.hip); scal: 4 device
 // floats ([0] max |x / l|, [1] := 2^sx, [2] := 2^-2sx); xs_h16: npad / 16 * leaf_c16_chunks * 2 KB
@@ -66,6 +68,8 @@ struct RawLeaves {
   int64_t m = 0;
   int d = 0;
 };
+// the leaves a workgroup of the split kernels owns: 256 (8 waves x 2 column tiles of 16) or 64 (4 waves x 1)
+enum class LeafTile : int { Wide = 0, Narrow = 1 };
 // What one launch of the split leaf-tile kernels reads and reports (launch_leaf_tiles_bf16): the posterior's operands,
 // the leaf batch, and the launching context's own settings -- nothing about a launch lives outside this struct
 template <typename TG>
@@ -92,9 +96,13 @@ struct SplitLeafLaunch {
   int64_t n_rows = 0;  // N (0: unknown) -- the fused step stops at the k-steps that hold padding points only
   RawLeaves raw;       // (fp16 contraction only)
   bool step32 = false;  // GPSO_SPLIT_KERNEL_FUSED32 -- the fused step on the 32x32x16 instruction, where built
+  // Narrow: 64 leaves per workgroup (4 waves x 1 column tile) where the default family runs -- fp16 split, fp16 contraction,
+  // fused step, float generation (leaf_narrow_applies); every other launch is the wide kernel whatever this says.  Same bits.
+  LeafTile tile = LeafTile::Wide;
   int row_loop = 1;     // GPSO_OPT_ROW_LOOP of the launching context (leaf_split.hpp: leaf_row_splits)
   int cu_count = 256;   // compute units of the launching context's device
   int64_t* splits_out = nullptr;  // (nullable) receives the workgroups per leaf tile the launcher chose
+  int64_t* tile_out = nullptr;    // (nullable) receives the leaves per workgroup of the kernel launched: 256 wide, 64 narrow
   // GPSO_OPT_PARK_BYTES of the launching context (leaf_split.hpp, PARK): the budget (0: off), and who grants a device buffer of
   // at least `bytes` for the parked pieces (nullptr to decline: the launch then parks nothing); owner: the launching context
   int64_t park_bytes = 0;
@@ -106,6 +114,13 @@ struct SplitLeafLaunch {
 // (TG, FUSED, KS) in predict_split_*.hip
 template <typename TG, bool FUSED, int KS /* kernel families 0-1 | 2-3 */>
 int launch_leaf_tiles_bf16_v(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a);
+// the narrow kernels (predict_split_f32_narrow.hip: all four kernel families in one translation unit), and where they exist
+int launch_leaf_tiles_narrow(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<float>& a);
+template <typename TG>
+inline bool leaf_narrow_applies(const SplitLeafLaunch<TG>& a, bool fused) {
+  return sizeof(TG) == 4 && fused && a.nsplit == 2 && a.f16_inv_scale_a != nullptr && a.xs_h16 != nullptr && a.c16_scale != nullptr &&
+         !a.step32 && leaf_c16_chunks(a.dp4) <= 2;
+}
 // variant: GPSO_OPT_SPLIT_KERNEL (0 the fused step, 1 the two-phase step)
 template <typename TG>
 inline int launch_leaf_tiles_bf16(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a, int variant = 0) {
@@ -224,6 +239,7 @@ struct ScreenLaunch {
   const float* raw = nullptr;
   int d = 0;
   int64_t cap = 0;  // a multiple of 256
+  int64_t narrow_max = 0;  // counts up to this take the narrow tile of the survivors' launch (screen.hpp: survivor_narrow_max)
   int64_t* counts = nullptr;
   int64_t* key = nullptr;
   float* rows_out = nullptr;

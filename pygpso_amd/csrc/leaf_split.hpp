@@ -360,11 +360,11 @@ __device__ __forceinline__ void leaf_bf16_gen(int lane, int dp4,
 
 // apply: acc[rt][t] += sum over the kept piece products, small terms first.  DIAG: k-steps of the diagonal block --
 // the tiles above the diagonal are all zero and skipped per row tile; off-diagonal steps are one branch-free stretch
-template <int NS, bool F16, bool DIAG>
+template <int NS, bool F16, bool DIAG, int CT = 2>
 __device__ __forceinline__ void leaf_bf16_apply(int q, int q_diag0, int lane, const u32x4* panel_b /* [NS][16][64] */,
-                                                const bf16x8 (&bfrag)[NS][2], f32x4 (&acc)[16][2]) {
+                                                const bf16x8 (&bfrag)[NS][CT], f32x4 (&acc)[16][CT]) {
   static_assert(!F16 || NS == 2, "the fp16 split has two pieces");
-  constexpr int RT = 16, CT = 2;
+  constexpr int RT = 16;
   u32x4 a[2][NS];
 #pragma unroll
   for (int sp = 0; sp < NS; ++sp) a[0][sp] = panel_b[(sp * RT + 0) * 64 + lane];
@@ -414,16 +414,17 @@ __device__ __forceinline__ void leaf_bf16_apply(int q, int q_diag0, int lane, co
 // per step (disassembly), in the steps that already have the least matrix work to hide them behind.
 // RTL: row tiles of the block that hold training rows (16, or 8 for a LAST row block with <= 128 of them: the tiles
 // beyond are all zero and are not applied; the map of the next step is then dealt over row tiles 1 .. RTL - 1)
-template <int NS, typename TG, int KERNEL, bool F16, int ASKIP, int GMODE, int C16 = 0, int RTL = 16, int XP = 0>
+// CT: column tiles of 16 leaves per wave (2; 1 in the narrow kernel -- the map is then one tile's 8 values, dealt the same way)
+template <int NS, typename TG, int KERNEL, bool F16, int ASKIP, int GMODE, int C16 = 0, int RTL = 16, int XP = 0, int CT = 2>
 __device__ __forceinline__ void leaf_bf16_fused_step(int q, int q_diag0, int lane, int dp4,
                                                      const u32x4* panel_b /* [NS][16][64]: L^-1 pieces of step q */,
                                                      const unsigned char* xs_n /* inputs of step q + 1 */, const TG* xb,
-                                                     const TG (&nb)[2], const TG cm, const float (&vc)[3],
-                                                     const bf16x8 (&bcur)[NS][2], bf16x8 (&bnxt)[NS][2],
-                                                     f32x4 (&acc)[16][2], float (&macc)[2]) {
+                                                     const TG (&nb)[CT], const TG cm, const float (&vc)[3],
+                                                     const bf16x8 (&bcur)[NS][CT], bf16x8 (&bnxt)[NS][CT],
+                                                     f32x4 (&acc)[16][CT], float (&macc)[CT]) {
   using MG = Mfma<TG>;
   using vecG = typename MG::vec4;
-  constexpr int RT = 16, CT = 2;
+  constexpr int RT = 16;
   constexpr TG SC = (TG)GenScale<KERNEL>::SC;
   constexpr bool GEN = GMODE != 0;
   const int XF = Bf16Lds<TG, C16>::xfrag(dp4);
@@ -446,10 +447,10 @@ __device__ __forceinline__ void leaf_bf16_fused_step(int q, int q_diag0, int lan
   // value e = 8 t + j, j = 4 h + r (column tile t, 16-point half h, accumulator register r); ops in stage-major order --
   // within a stage every op is independent of its neighbours, and an op's input is at least 16 ops old:
   //   norms x SC (8) | combine (16) | sqrt (16; none for the squared exponential) | exp2 (16) | polynomial x exponential
-  //   (16) | k*.alpha (16; GMODE 2) | split of pair (t, j) (8)
-  constexpr int E = 16;
+  //   (16) | k*.alpha (16; GMODE 2) | split of pair (t, j) (8)      (CT = 1: 8 values, 4 pairs)
+  constexpr int E = 8 * CT;
   constexpr int O_COMB = C16 != 0 ? 0 : 8, O_SQRT = O_COMB + E, O_EXP = O_SQRT + (KERNEL == 3 ? 0 : E), O_POLY = O_EXP + E,
-                O_MEAN = O_POLY + E, O_SPLIT = O_MEAN + (GMODE == 2 ? E : 0), NOPS = O_SPLIT + 8;
+                O_MEAN = O_POLY + E, O_SPLIT = O_MEAN + (GMODE == 2 ? E : 0), NOPS = O_SPLIT + 4 * CT;
   float p[CT][8], ex[CT][8];
   TG na[2][4];
   f32x4 al4[2];
@@ -702,8 +703,15 @@ __device__ __forceinline__ void leaf_bf16_fused_half(int lane, int dp4, const u3
 // wave's vmcnt(0) in leaf_sync, a full step after the issue) and the read of what it brought: the barriers of the steps in the
 // loop, and one of its own behind the read of step 0 at the top of a later row block.
 // Default kernels only: fp16 split, fused step, one chunk of the fp16 contraction.
-template <int NS, typename TG, int KERNEL, bool F16 = false, bool FUSED = false, int C16 = 0, bool M32P = false, int XP = 0, bool PARK = false>
-__global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
+// NW, CT: waves per workgroup and column tiles of 16 leaves per wave.  8 x 2 is the batch kernel: 256 leaves per workgroup, two
+// waves per SIMD.  4 x 1 is the NARROW kernel of a screened call's survivors (predict_split_f32_narrow.hip; fp16 split, fused
+// step, fp16 contraction): 64 leaves per workgroup, one wave per SIMD, every wave a DMA wave -- a few hundred leaves then spread
+// over four times as many CUs, and a wave's step carries half the apply MFMAs and half the generated values with no partner on
+// its SIMD's issue port.  Everything a wave computes for a column tile is independent of its other tile, of its wave and of its
+// workgroup: the same part_var / part_mean bits per leaf whatever the geometry (tests/test_gpu_screen_narrow.py).
+template <int NS, typename TG, int KERNEL, bool F16 = false, bool FUSED = false, int C16 = 0, bool M32P = false, int XP = 0, bool PARK = false,
+          int NW = 8, int CT = 2>
+__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void leaf_tiles_bf16_kernel(
     const u32x4* __restrict__ linv_b, const TG* __restrict__ xs_p, const TG* __restrict__ xnorm,
     const float* __restrict__ alpha, const TG* __restrict__ leaves_s,
     const TG* __restrict__ lnorm, double* __restrict__ part_var, double* __restrict__ part_mean,
@@ -713,7 +721,9 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     scales them itself ((float)(x / l), rows beyond raw_m are padding): no prep launch in front of this kernel */,
     const double* __restrict__ raw_ls, int64_t raw_m, int raw_d,
     unsigned char* __restrict__ park /* PARK: park_steps x 32 KB per workgroup of the launch */, int park_steps) {
-  constexpr int RT = 16, CT = 2, NW = 8;
+  constexpr int RT = 16;
+  static_assert((NW == 8 && CT == 2) || (NW == 4 && CT == 1 && FUSED && F16 && NS == 2 && C16 != 0 && !M32P && !PARK && sizeof(TG) == 4),
+                "the narrow kernel: the default family only (no parking, no 32x32x16 step, no stagger)");
   static_assert(!PARK || (FUSED && F16 && NS == 2 && C16 == 1 && !M32P && !kLeafStagger && sizeof(TG) == 4), "PARK: the default kernels only");
   constexpr TG SC = (TG)GenScale<KERNEL>::SC;
   constexpr bool M32 = M32P && FUSED && F16 && NS == 2 && C16 != 0 && sizeof(TG) == 4;
@@ -735,7 +745,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   if (m_live != nullptr && leaf_tile * (NW * CT * 16) >= *m_live) return;  // workgroup-uniform
   // STAG (round 6): waves 4-7 run half a step behind waves 0-3 (leaf_bf16_fused_half); the L^-1 pieces then live in a ring of
   // three buffers -- where that fits the 160 KB (one chunk of the fp16 contraction: D <= 28)
-  constexpr bool STAG = kLeafStagger && FUSED && NS == 2 && F16 && C16 == 1;
+  constexpr bool STAG = kLeafStagger && FUSED && NS == 2 && F16 && C16 == 1 && NW == 8;
   constexpr int PBUF = STAG ? 3 : 2;
   u32x4* panel = reinterpret_cast<u32x4*>(lds_raw);                 // [PBUF][NS][RT][64]
   unsigned char* xsl = reinterpret_cast<unsigned char*>(panel + PBUF * NS * RT * 64);  // [3] X buffers
@@ -744,7 +754,9 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   const int xstride = Bf16Lds<TG, C16>::xbytes(dp4);
   const int xfrag = Bf16Lds<TG, C16>::xfrag(dp4);
   // this wave's leaf fragments: [CT][dp4][64] TG, or (C16) [CT][chunk][piece][64] x 16 bytes
-  TG* xb = reinterpret_cast<TG*>(xsl + 3 * xstride + (size_t)wave * xfrag);
+  // (a k-step's X fragments are two 16-point halves: a wave's CT column tiles take CT halves' worth -- leaf_bf16_lds_bytes)
+  const int lfrag = CT == 2 ? xfrag : xfrag / 2 * CT;
+  TG* xb = reinterpret_cast<TG*>(xsl + 3 * xstride + (size_t)wave * lfrag);
 
   const int64_t col0 = (leaf_tile * NW + wave) * (CT * 16);
   const int dp = dp4 * 4;
@@ -769,7 +781,9 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   // first, so waves 0-3 are through a fused step in 3 700 clocks and would wait 1 800 at the barrier for waves 4-7, which
   // need 5 000 (stamps, tools/micro/leaf_bf16_phases.hip): the DMA issue (~650 clocks per wave when dealt evenly) is the
   // work that can be moved, and it goes to the waves that have the time.  Otherwise all eight waves share it.
-  constexpr int DW = (FUSED != 0 && NS == 2) ? NW / 2 : NW;
+  // The narrow kernel (NW = 4) has one wave per SIMD and no half with time to spare: all four carry them, 8 fragments each --
+  // the duties of the wide kernel's waves 0-3, address for address.
+  constexpr int DW = (FUSED != 0 && NS == 2 && NW == 8) ? NW / 2 : NW;
   constexpr int FPW = NS * RT / DW;  // fragments of the L^-1 pieces per DMA wave: 8 / 4 (two pieces) or 6 (three)
   static_assert(FPW * DW == NS * RT && FPW * 1024 <= 8192 && RT == 16, "window of a wave's fragments");
   const bool dma_wave = wave < DW;
@@ -871,7 +885,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   set_row_block(0);
   issue_block_start(true);
   TG cm = TG(-2) * SC;
-  float nb_c16[CT] = {0, 0};
+  float nb_c16[CT] = {};
   if constexpr (C16) {
     // the leaves' side of the fp16 contraction: B operand of the 16x16x32 instruction, lane l element j = leaf
     // col0 + 16 t + (l & 15), dimension 32 cc + 8 (l >> 4) + j, scaled like the training side and split the same way
@@ -942,7 +956,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   float macc32 = 0.0f;
   u32x4 bfrag32[2][2];
   const M32Lanes ml = m32_lanes<C16 != 0 ? C16 : 1>(lane);
-  const float nb32 = M32 ? (float)(((lane >> 4) & 1) ? nb[1] : nb[0]) : 0.0f;
+  const float nb32 = M32 ? (float)(((lane >> 4) & 1) ? nb[CT - 1] : nb[0]) : 0.0f;
   (void)acc32; (void)macc32; (void)bfrag32; (void)ml; (void)nb32;
   // ---- the row blocks of this workgroup, heaviest first -------------------------------------------------------------------
   // (every step ends with a workgroup barrier, the last one included: when the DMAs of the next row block's first steps are
@@ -951,7 +965,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
   // free there.  The second set of wave-uniform pointers spills 87 scalar registers into vector lanes inside the hot loop: C3
   // 0.7193 | 0.7221 ms against 0.7464 | 0.7304 without the prefetch, C4 / C5 +2.5 %.  r06_predict_experiments.txt.)
   // ---- PARK: this wave's window (behind the leaf fragments) and its slots: slot s of workgroup w at ((w P + s) 8 + wave) 4 KB --
-  u32x4* const pwin = reinterpret_cast<u32x4*>(xsl + 3 * xstride + (size_t)NW * xfrag) + wave * (NS * CT * 64);
+  u32x4* const pwin = reinterpret_cast<u32x4*>(xsl + 3 * xstride + (size_t)NW * lfrag) + wave * (NS * CT * 64);
   // (ONE wave-uniform 64-bit base lives across the loops -- this wave's slot 0; a slot is 32 KB further per step)
   const unsigned char* const park_w =
       PARK ? park + ((size_t)(((unsigned)(leaf_tile * S + split) * (unsigned)park_steps) * NW + wave) << 12) : nullptr;
@@ -1019,7 +1033,8 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
       for (int t = 0; t < CT; ++t) acc[rt][t] = f32x4{0, 0, 0, 0};
-    macc[0] = macc[1] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < CT; ++t) macc[t] = 0.0f;
   }
   leaf_sync();
 
@@ -1048,8 +1063,8 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
         // step 0 (q = 0) issues the DMA of step 2 into EVERY window as soon as it starts, waves 0-3 on behalf of waves 4-7: all
         // eight reads of step 0 must have returned first.  (In the loop the barrier of the reload step does this.)
         leaf_sync();
-      } else if (q_diag0 == 0) leaf_bf16_gen<NS, TG, KERNEL, F16, true, C16, 2, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
-      else leaf_bf16_gen<NS, TG, KERNEL, F16, false, C16, 2, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
+      } else if (q_diag0 == 0) leaf_bf16_gen<NS, TG, KERNEL, F16, true, C16, CT, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
+      else leaf_bf16_gen<NS, TG, KERNEL, F16, false, C16, CT, XP>(lane, dp4, xsl, xb, nb, cm, vc, bfrag, macc);
     }
     // Measured and NOT kept (tools/ab_time.py, same box, f16x3 at C3: two-phase 0.850 | this 0.7955 ms): the step's DMAs
     // dealt behind the MFMAs of row tiles 1, 2, ... like the map (+2 %); a ring of THREE buffers of L^-1 pieces with the
@@ -1065,7 +1080,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
 #define GPSO_RELOAD_STEP()                                                                                            \
   {                                                                                                                   \
     issue_for(q);                                                                                                     \
-    leaf_bf16_fused_step<NS, TG, KERNEL, F16, 0, 0, C16, RTL, XP>(q, q_diag0, lane, dp4,                              \
+    leaf_bf16_fused_step<NS, TG, KERNEL, F16, 0, 0, C16, RTL, XP, CT>(q, q_diag0, lane, dp4,                          \
                                                                  panel + (q & 1) * NS * RT * 64,                      \
                                                                  xsl + ((q + 1) % 3) * xstride, xb, nb, cm, vc,       \
                                                                  bfrag, bnxt, acc, macc);                             \
@@ -1107,7 +1122,7 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
       GPSO_BSTAMP(q, 4);                                                                                              \
       leaf_sync();                                                                                                \
     } else {                                                                                                          \
-      leaf_bf16_fused_step<NS, TG, KERNEL, F16, ASKIP, GMODE, C16, RTL, XP>(q, q_diag0, lane, dp4,                    \
+      leaf_bf16_fused_step<NS, TG, KERNEL, F16, ASKIP, GMODE, C16, RTL, XP, CT>(q, q_diag0, lane, dp4,                \
                                                                    panel + (q & 1) * NS * RT * 64,                    \
                                                                    xsl + ((q + 1) % 3) * xstride, xb, nb, cm, vc,     \
                                                                    bfrag, bnxt, acc, macc);                           \
@@ -1173,11 +1188,11 @@ __global__ __launch_bounds__(512, 2) void leaf_tiles_bf16_kernel(
     if (!ahead || q == 0) issue_for(q);                                                                               \
     else if (q >= 2) issue_for(q - 1); /* (this wave's iteration q starts in interval q - 1) */                       \
     GPSO_BSTAMP(q, 1);                                                                                                \
-    leaf_bf16_gen<NS, TG, KERNEL, F16, DIAGF, C16, 2, XP>(lane, dp4, xsl + (q % 3) * xstride, xb, nb, cm, vc, bfrag, macc); \
+    leaf_bf16_gen<NS, TG, KERNEL, F16, DIAGF, C16, CT, XP>(lane, dp4, xsl + (q % 3) * xstride, xb, nb, cm, vc, bfrag, macc); \
     GPSO_BSTAMP(q, 2);                                                                                                \
     if (ahead && q > 0) leaf_sync();                                                                              \
     GPSO_BSTAMP(q, 3);                                                                                                \
-    leaf_bf16_apply<NS, F16, DIAGF>(q, q_diag0, lane, panel + (q & 1) * NS * RT * 64, bfrag, acc);                    \
+    leaf_bf16_apply<NS, F16, DIAGF, CT>(q, q_diag0, lane, panel + (q & 1) * NS * RT * 64, bfrag, acc);                    \
     GPSO_BSTAMP(q, 4);                                                                                                \
     if (!ahead) leaf_sync();                                                                                      \
     GPSO_BSTAMP(q, 5);                                                                                                \
@@ -1291,8 +1306,10 @@ inline int leaf_row_splits(int mode, int64_t ltiles, int nbi, int ncu, bool live
 // FUSED and KS (kernel families 0-1: Matern-5/2, -3/2 | 2-3: Matern-1/2, squared exponential) are template parameters of
 // the launchers: each (TG, FUSED, KS) slice of the kernels is instantiated in a translation unit of its own
 // (launch_leaf_tiles_bf16_v<TG, FUSED, KS>, predict_split_*.hip), and the slices compile in parallel
-template <bool FUSED, int KS, int NS, typename TG, bool F16 = false, int C16 = 0>
+// NARROW: the 4-wave, one-column-tile geometry (64 leaves per workgroup) in place of the batch kernel's 8 x 2 (256)
+template <bool FUSED, int KS, int NS, typename TG, bool F16 = false, int C16 = 0, bool NARROW = false>
 static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a) {
+  constexpr int NW = NARROW ? 4 : 8, CT = NARROW ? 1 : 2, kTile = NW * CT * 16;  // (mpad is a multiple of 256, so of either tile)
   const int64_t npad = a.npad, mpad = a.mpad;
   const int dp4 = a.dp4;
   // what only the fp16 contraction reads: its X fragments (in place of xs_p), its scales, the caller's raw leaves
@@ -1301,8 +1318,8 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   const RawLeaves rawl = C16 ? a.raw : RawLeaves{};
   const int nbi = (int)(npad / 256);
   const dim3 grid((unsigned)(mpad / 256), (unsigned)nbi);
-  constexpr bool STAG = kLeafStagger && FUSED && NS == 2 && F16 && C16 == 1;
-  const size_t lds = leaf_bf16_lds_bytes(NS, dp4, (int)sizeof(TG), C16 != 0) + (STAG ? (size_t)NS * 16 * 64 * 16 : 0);  // (a third buffer of L^-1 pieces)
+  constexpr bool STAG = kLeafStagger && FUSED && NS == 2 && F16 && C16 == 1 && !NARROW;
+  const size_t lds = leaf_bf16_lds_bytes(NS, dp4, (int)sizeof(TG), C16 != 0, NW, CT) + (STAG ? (size_t)NS * 16 * 64 * 16 : 0);  // (a third buffer of L^-1 pieces)
   if (C16 ? leaf_c16_chunks(dp4) != C16 : 2 * dp4 * (int)(sizeof(TG) / 4) > 32) {  // the X fragments of a k-step are one DMA window of 32 pieces (C16: 8)
     note_launch_error("launch_leaf_tiles_bf16: more than 32 X pieces per k-step");
     return 1;
@@ -1313,12 +1330,13 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   const float var_arg = F16 ? (float)ldexp(kp.variance, 14 - eb) : (float)kp.variance;
   const float inv_b = F16 ? (float)ldexp(1.0, eb - 14) : 1.0f;
   const int q_max = a.n_rows > 0 ? (int)((a.n_rows + 31) / 32) : (int)(npad / 32);
-  const int S = leaf_row_splits(a.row_loop, mpad / 256, nbi, a.cu_count, a.m_live == nullptr);
+  const int S = leaf_row_splits(a.row_loop, mpad / kTile, nbi, a.cu_count, a.m_live == nullptr);
   if (a.splits_out != nullptr) *a.splits_out = S;
-  const dim3 grid_s((unsigned)(mpad / 256), (unsigned)S);
+  if (a.tile_out != nullptr) *a.tile_out = kTile;
+  const dim3 grid_s((unsigned)(mpad / kTile), (unsigned)S);
   // FUSED (GPSO_SPLIT_KERNEL_AUTO): the fused step; otherwise round 3's two-phase step.  Same bits either way.
   // a.step32 (GPSO_SPLIT_KERNEL_FUSED32): the fused step on the 32x32x16 instruction, where that kernel exists
-  constexpr bool kHasM32 = kLeafStep32 && FUSED && F16 && NS == 2 && C16 != 0 && sizeof(TG) == 4;
+  constexpr bool kHasM32 = kLeafStep32 && FUSED && F16 && NS == 2 && C16 != 0 && sizeof(TG) == 4 && !NARROW;
   const bool m32 = kHasM32 && a.step32;
   // xp: the last chunk of the fp16 contraction uses <= 16 slots (the scaled inputs and the norm slot behind them)
   const bool xp = C16 != 0 && dp4 * 4 + 1 - 32 * (C16 - 1) <= 16;
@@ -1327,7 +1345,7 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   // row block nbi - 1 - S (split S - 1): 4 (nbi - 1 - S) steps, none unless a workgroup owns at least three row blocks at S = 1.
   // P = what the budget pays for (32 KB per parked step and workgroup of the launch), where the kernel exists, its window (one
   // 4 KB per wave) still fits the 160 KB of LDS, and the context grants the scratch; otherwise 0: the kernel without PARK.
-  constexpr bool kHasPark = FUSED && F16 && NS == 2 && C16 == 1 && sizeof(TG) == 4 && !kLeafStagger;
+  constexpr bool kHasPark = FUSED && F16 && NS == 2 && C16 == 1 && sizeof(TG) == 4 && !kLeafStagger && !NARROW;
   constexpr size_t kParkWindow = (size_t)8 * 4096, kParkStepBytes = (size_t)8 * 4096;
   int park_steps = 0;
   unsigned char* park = nullptr;
@@ -1352,9 +1370,9 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
   }
 #define GPSO_L2(K, M32, XP, PK, LDS)                                                                \
   do {                                                                                              \
-    const int rc = ensure_dyn_lds((const void*)leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK>, (int)(LDS)); \
+    const int rc = ensure_dyn_lds((const void*)leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK, NW, CT>, (int)(LDS)); \
     if (rc) return rc;                                                                              \
-    hipLaunchKernelGGL((leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK>), grid_s, dim3(512), (LDS), st, \
+    hipLaunchKernelGGL((leaf_tiles_bf16_kernel<NS, TG, K, F16, FUSED, C16, M32, XP, PK, NW, CT>), grid_s, dim3(NW * 64), (LDS), st, \
                        static_cast<const u32x4*>(a.linv_b), xs_p, a.xnorm, a.alpha, a.leaves_s, a.lnorm, \
                        a.part_var, a.part_mean, (int)(npad / 16), dp4, mpad, nbi, var_arg, a.m_live, \
                        a.f16_inv_scale_a, inv_b, c16_scale, q_max, rawl.x, rawl.ls, rawl.m, rawl.d, park, park_steps); \
@@ -1398,6 +1416,9 @@ static int launch_leaf_tiles_bf16_ns(hipStream_t st, const KernParams& kp, const
 
 template <typename TG, bool FUSED, int KS>
 int launch_leaf_tiles_bf16_v(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<TG>& a) {
+  if constexpr (sizeof(TG) == 4 && FUSED) {  // the narrow tile, where the launch asks for it and the default family runs
+    if (a.tile == LeafTile::Narrow && leaf_narrow_applies(a, FUSED)) return launch_leaf_tiles_narrow(st, kp, a);
+  }
   if (a.f16_inv_scale_a != nullptr) {  // fp16 split (nsplit == 2 pieces)
     if constexpr (sizeof(TG) == 4) {
       if (a.xs_h16 != nullptr && a.c16_scale != nullptr) {  // ... with the contraction on the fp16 pipe as well
@@ -1409,5 +1430,11 @@ int launch_leaf_tiles_bf16_v(hipStream_t st, const KernParams& kp, const SplitLe
   }
   if (a.nsplit == 3) return launch_leaf_tiles_bf16_ns<FUSED, KS, 3, TG>(st, kp, a);
   return launch_leaf_tiles_bf16_ns<FUSED, KS, 2, TG>(st, kp, a);
+}
+// the narrow kernels of one slice of kernel families (leaf_narrow_applies holds): fp16 split, fused step, fp16 contraction
+template <int KS>
+int launch_leaf_tiles_narrow_v(hipStream_t st, const KernParams& kp, const SplitLeafLaunch<float>& a) {
+  if (leaf_c16_chunks(a.dp4) == 1) return launch_leaf_tiles_bf16_ns<true, KS, 2, float, true, 1, true>(st, kp, a);
+  return launch_leaf_tiles_bf16_ns<true, KS, 2, float, true, 2, true>(st, kp, a);
 }
 }  // namespace gpso

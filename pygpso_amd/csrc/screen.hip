@@ -345,13 +345,16 @@ __global__ __launch_bounds__(64) void screen_count_kernel(const double* __restri
 // them, walks its leaves 64 at a time (coalesced) and writes every survivor's index at its rank -- ascending -- as long as the
 // rank is below cap; then the raw rows of its own survivors, and its share of the zero rows between the live count and the next
 // multiple of 256 (the survivors' launch scales the compact rows in its prologue: a row of its last live leaf tile must hold
-// numbers).  ctl: [0] live rows of the compact buffers (min(count, cap)), [1] the survivors' count.
+// numbers).  ctl: [0] live rows of the compact buffers (min(count, cap)), [1] the survivors' count; [kScreenCtlNarrow] /
+// [kScreenCtlWide]: the live rows again for the launch whose tile this count takes (count <= narrow_max: the narrow one), 0 for
+// the other -- which then leaves at once (screen.hpp: survivor_narrow_max).
 // probe (nullable, [2][m]): ub and the flag of every leaf, for gpso_screen_probe.
 __global__ __launch_bounds__(64) void screen_scatter_kernel(const double* __restrict__ my, const int64_t* __restrict__ counts,
                                                             int64_t m, double variance, double noise, double varsigma,
                                                             const float* __restrict__ raw, int d, int64_t cap,
                                                             int64_t* __restrict__ key, float* __restrict__ rows_out,
-                                                            int64_t* __restrict__ ctl, double* __restrict__ probe) {
+                                                            int64_t* __restrict__ ctl, double* __restrict__ probe,
+                                                            int64_t narrow_max) {
   const int lane = threadIdx.x, w = blockIdx.x, parts = (int)gridDim.x;
   const double T = __builtin_bit_cast(double, ctl[2]);
   long long at = 0, total = 0;
@@ -406,6 +409,8 @@ __global__ __launch_bounds__(64) void screen_scatter_kernel(const double* __rest
   if (w == 0 && lane == 0) {
     ctl[0] = live;
     ctl[1] = total;
+    ctl[kScreenCtlNarrow] = total <= narrow_max ? live : 0;
+    ctl[kScreenCtlWide] = total <= narrow_max ? 0 : live;
   }
 }
 
@@ -414,7 +419,7 @@ void launch_screen(hipStream_t st, const ScreenLaunch& a) {
   hipLaunchKernelGGL(screen_count_kernel, dim3(parts), dim3(64), 0, st, a.my, a.block_max, a.nblk, a.m, a.variance, a.noise,
                      a.varsigma, a.counts, a.ctl);
   hipLaunchKernelGGL(screen_scatter_kernel, dim3(parts), dim3(64), 0, st, a.my, a.counts, a.m, a.variance, a.noise, a.varsigma,
-                     a.raw, a.d, a.cap, a.key, a.rows_out, a.ctl, a.probe);
+                     a.raw, a.d, a.cap, a.key, a.rows_out, a.ctl, a.probe, a.narrow_max);
 }
 
 void screen_eval_host(const double* my, const double* v, double variance, double noise, double varsigma, long long n,

@@ -49,6 +49,33 @@ GPSO_ACQ_HD inline bool screen_accepts(double u_star, double threshold, int64_t 
   return count > 0 && count <= cap && (u_star != u_star || u_star >= threshold);
 }
 
+// The survivors' launch has two tiles (leaf_split.hpp: the batch kernel's 256 leaves per workgroup, or the narrow 64), and only
+// the device knows the count: both are enqueued, each behind a live-row word of its own in the screen's control block, of which
+// the compaction zeroes one -- that launch leaves at once.  Words of screen_ctl: [0] live rows, [1] the count, [2] T', and
+constexpr int kScreenCtlNarrow = 3, kScreenCtlWide = 4;  // the live rows as the narrow / the wide launch sees them
+// Up to how many survivors the narrow tile is the faster one: a makespan model written like leaf_row_splits, in k-steps of the
+// wide kernel.  Either launch gives a workgroup one row block (8 (b + 1) k-steps for block b), heaviest first, one workgroup per
+// CU at a time (neither tile's LDS fits a CU twice).  A launch lasts as long as its heaviest block's chain, 8 nbi steps, or as
+// the chip's share of all its steps, tiles x 4 nbi (nbi + 1) / CUs, whichever is longer; a narrow step takes kNarrowStep of a
+// wide one (measured on lists of 28 .. 2 048 rows, where both launches are chain-bound: 66 against 128 us at N = 2048, 262
+// against 500 us at N = 8192 -- profiles/screen_narrow_ab.txt).  Below the crossover the wide launch is its chain and the narrow
+// one gains; above it the narrow launch is its share of four times as many workgroups, each with the whole row block's L^-1
+// traffic and DMA issue to itself, and loses (N = 2048: x 0.92 at 6 144 rows, x 1.10 at the room's 8 192; model: 6 976).
+// -> the largest count, a multiple of 64 and at most cap, that takes the narrow tile; 0: none.  Monotone: a count above it never does.
+inline int64_t survivor_narrow_max(int nbi, int ncu, int64_t cap) {
+  constexpr double kNarrowStep = 0.52;
+  if (nbi < 1 || ncu < 1) return 0;
+  const double chain = 8.0 * nbi, per_tile = 4.0 * nbi * (nbi + 1.0) / ncu;
+  int64_t best = 0;
+  for (int64_t c = 64; c <= cap; c += 64) {
+    const double narrow = kNarrowStep * (chain > per_tile * (double)(c / 64) ? chain : per_tile * (double)(c / 64));
+    const double wide = chain > per_tile * (double)((c + 255) / 256) ? chain : per_tile * (double)((c + 255) / 256);
+    if (!(narrow < wide)) break;
+    best = c;
+  }
+  return best;
+}
+
 // The compaction's partition of a batch of m leaves over `parts` workgroups: part w owns the leaves [lo, hi), ranges of equal
 // length -- a multiple of 64, one coalesced load per lane and step -- in ascending order; the last non-empty range may be
 // shorter, the ranges behind it are empty.  Every leaf belongs to exactly one part.

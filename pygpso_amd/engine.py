@@ -147,6 +147,14 @@ class HipGPEngine:
         ``last_count(7)``: survivors of the last call; ``last_count(8)``: 0 not screened, 1 accepted, 2 refused and run again."""
         self._check(self._lib.gpso_set_option(self._h, L.OPT_SCREEN, int(mode)))
 
+    def set_survivor_tile(self, mode):
+        """GPSO_OPT_SURVIVOR_TILE (per context): 0 = the survivors' launch of a screened best-UCB call runs the narrow tile of the
+        split predict kernel (4 waves x 16 leaves: 64 leaves per workgroup) up to the survivor count a makespan model gives it
+        (``gpso_survivor_narrow_max_host``), the wide one above, every other launch the wide one (default); 1 = wide everywhere;
+        2 = narrow wherever the default float kernels run on float leaves, ``predict`` included (tests).  Same bits.
+        ``last_count(9)``: leaves per workgroup of the last split predict launch (256 or 64)."""
+        self._check(self._lib.gpso_set_option(self._h, L.OPT_SURVIVOR_TILE, int(mode)))
+
     def screen_probe(self, xs, varsigma):
         """The mean pass and the screen of a screened best-UCB call alone (``gpso_screen_probe``) -> (my[M], ub[M], survives[M]
         bool, info): every leaf's mean -- ``predict``'s bits --, what its ucb cannot exceed, whether it survives; info =
@@ -260,7 +268,8 @@ class HipGPEngine:
         """0: leaves the kernels scored in the last predict-type call, 1: leaves of the reference's list; 2 .. 6: see
         ``gpso_last_count`` in include/gpso_hip.h (4: bytes of device memory the contexts of this process hold now; 5 / 6:
         k-steps per leaf tile the last split predict launch parked / reloaded under GPSO_OPT_PARK_BYTES; 7 / 8: survivors and
-        verdict -- 0 not screened, 1 accepted, 2 refused -- of the last best-UCB call under GPSO_OPT_SCREEN)."""
+        verdict -- 0 not screened, 1 accepted, 2 refused -- of the last best-UCB call under GPSO_OPT_SCREEN; 9: leaves per
+        workgroup of the last split predict launch, 256 or 64 -- GPSO_OPT_SURVIVOR_TILE)."""
         return int(self._lib.gpso_last_count(self._h, int(what)))
 
     FIT_MATH = {L.FITMATH_NONE: None, L.FITMATH_SMALL: "small", L.FITMATH_F32: "f32", L.FITMATH_F64: "f64",

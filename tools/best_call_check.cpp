@@ -102,9 +102,9 @@ static void calls() {
     c.tiles_recorded(1);
     c.writes_host(host);
     c.arm_token(true, 1, 12.0);
-    c.screened(leaves, 1, 24000, AcqSpec(50.0));
+    c.screened(leaves, 1, 24000, AcqSpec(50.0), 15744);
     CHECK(c.kind == BestKind::Screened && c.nseg == 1 && c.mode == 0 && c.screen.xs == leaves && c.screen.xs_dtype == 1 &&
-          c.screen.m == 24000 && c.screen.acq.varsigma == 50.0 && c.token == 12.0 && host[4 + 2] == 0.0);
+          c.screen.m == 24000 && c.screen.acq.varsigma == 50.0 && c.narrow_max == 15744 && c.token == 12.0 && host[4 + 2] == 0.0);
     CHECK(c.consumed().screen.m == 24000 && c.none() && c.screen.xs == nullptr && c.screen.m == 0);
   }
   // folded: the half's tile pairs stay, the half's pointer and token are replaced
@@ -131,7 +131,7 @@ static void tickets() {
   c.tiles_recorded(1);
   c.writes_host(host);
   c.arm_token(true, 1, 21.0);
-  c.screened(host, 1, 512, AcqSpec(2, 1, 0.5, 0.25, 0.125));
+  c.screened(host, 1, 512, AcqSpec(2, 1, 0.5, 0.25, 0.125), 512);
   t.ev = 5;
   t.store(c);
   CHECK(t.in_use && same(t.call, c));

@@ -2,7 +2,8 @@
 // stamps of wave 0 (generates step q, then applies it) and wave 4 (applies step q, then generates q + 1) of
 // the heaviest workgroup, inside the real kernel at the C3 shape:
 //   0 step begin | 1 LDS-DMA issued | 2 generation done | 3 (waves 4-7: barrier) | 4 apply issued | 5 (waves 0-3: barrier)
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I pygpso_amd/csrc tools/micro/leaf_bf16_phases.hip -o tools/micro/leaf_bf16_phases.bin
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I pygpso_amd/csrc tools/micro/leaf_bf16_phases.hip pygpso_amd/csrc/predict_split_f32_narrow.hip \
+//         -o tools/micro/leaf_bf16_phases.bin
 __device__ long long g_bst[2 * 64 * 8];
 #ifndef GPSO_NOSTAMP  // -DGPSO_NOSTAMP: the kernel as shipped (clean kernel times of the ablation builds)
 #define GPSO_BSTAMP(q, i)                                                                              \

@@ -3,7 +3,7 @@
 //   0 step begin | 1 LDS-DMA issued | 2 work done (apply: 48 MFMAs; generator: the next step's pieces) | 3 behind the barrier
 // plus HW_REG_HW_ID of every wave (which SIMD / CU it landed on).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -Xclang -target-feature -Xclang -packed-fp32-ops \
-//         -I pygpso_amd/csrc tools/micro/leaf_spec_phases.hip -o tools/micro/leaf_spec_phases.bin
+//         -I pygpso_amd/csrc tools/micro/leaf_spec_phases.hip pygpso_amd/csrc/predict_split_f32_narrow.hip -o tools/micro/leaf_spec_phases.bin
 __device__ long long g_sst[16 * 64 * 4];
 __device__ unsigned g_hwid[16];
 #define GPSO_SSTAMP(q, i)                                                                              \

@@ -2,9 +2,9 @@
 // the real kernel on synthetic data, R launches on the same inputs, every launch's mean / variance partials compared
 // bit by bit with the first one's.  Two builds:
 //   as shipped   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -I pygpso_amd/csrc
-//                  tools/micro/packed_mean_probe.hip -o tools/micro/packed_mean_probe.bin
+//                  tools/micro/packed_mean_probe.hip pygpso_amd/csrc/predict_split_f32_narrow.hip -o tools/micro/packed_mean_probe.bin
 //   packed       hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -DGPSO_PROBE_PACKED_MEAN -I pygpso_amd/csrc
-//                  tools/micro/packed_mean_probe.hip -o tools/micro/packed_mean_probe_packed.bin
+//                  tools/micro/packed_mean_probe.hip pygpso_amd/csrc/predict_split_f32_narrow.hip -o tools/micro/packed_mean_probe_packed.bin
 // (round 4: the GPSO_PROBE_* hooks the packed / dump builds need are no longer in predict.hip -- git apply
 //  tools/attic/predict_hooks.patch first; the hunt is parked: profiles/r03_packed_mean.txt)
 // (packed: SLP vectorisation on and the empty asm behind the mean updates left out, so the two column tiles' means
